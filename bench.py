@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — rendered frames/s of the generator forward (+ blend) at 512x512.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode frame|chain|clips]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode frame|chain|clips] [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic input:
   frame  (default) one 512x512 frame (B=1, fp32) through Generator.forward plus the driver's blend,
@@ -16,7 +16,12 @@ with their code; the driver's own torch.distributed.run launch takes the other b
 they reach the other ranks through ONE RCCL broadcast of the folded blob, and every rank then renders its own
 frames with no further communication (weak scaling).
 
-Printed JSON (rank 0): metric/value/unit as the contract asks, plus
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs when --dump-outputs DIR is given,
+and prints its line.  What the headline figure does not need runs only with --full, after the timed steps: the roofline
+profiling pass, the CPU baseline and its parity check, the other BASELINE configurations (other_configs) and the
+replica check of --mode clips; without --full those fields of the line are null.
+
+Printed JSON (rank 0): metric/value/unit/ms_per_step as the contract asks, plus (with --full)
   roofline     dominant kernel class (the convolutions): algorithmic FLOPs per forward / device time of EVERY launch
                that takes part in computing them - the matrix-core kernels AND the Winograd transforms and split-K
                slab sums around them - measured with HIP events on the launch stream in a separate profiling
@@ -64,9 +69,15 @@ def parse_args(argv=None):
                     help="fp32 mode only: f32 (default) = exact-fp32 matrix-core products everywhere, the reference's arithmetic; bf16x3 = "
                          "the plain GEMMs of the frame form each product from six bf16 products of three-way split operands "
                          "(rib_set_products; opt-in, named in config.workload, never the headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline figure does not need: the roofline profiling pass, the "
+                         "CPU-oracle baseline and parity, the other BASELINE configurations and the clips replica check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32; at most 64 MB in all, larger "
+                         "outputs as a fixed seeded sample of their elements)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default run only: skip the short measurements of BASELINE configs[2] (32-frame bf16 chain) and configs[4] "
-                         "(1024x1024 batch 4) that are attached to the line as other_configs")
+                    help="--full run of the default workload only: skip the short measurements of BASELINE configs[2] (32-frame "
+                         "bf16 chain) and configs[4] (1024x1024 batch 4) that are attached to the line as other_configs")
     ap.add_argument("--inflight", type=int, default=1,
                     help="independent frames in flight per GPU: each on its own HIP stream with its own handle and "
                          "workspace (segments between key frames are independent, SURVEY F9); every forward stays batch=B")
@@ -78,7 +89,37 @@ def parse_args(argv=None):
     ap.add_argument("--no-tuning", action="store_true", help="ignore the measured tables: every launch takes the analytic cost model's choice")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-frames", type=int, default=8, help="timed CPU-oracle passes of the cpu_baseline leg (>= 5)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 * 10**6          # --dump-outputs: all .npy files together
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(outdir, arrays, log):
+    """Write {name: device tensor} as outdir/<name>.npy, float32 (float64 tensors stay float64).  When the arrays together
+    exceed DUMP_BUDGET_BYTES, every array gives up the same fraction of its elements: what is written is the 1-D sample
+    x.flatten()[idx] with idx the sorted indices drawn without replacement by a generator seeded with DUMP_SAMPLE_SEED, so
+    two runs with the same arguments write the same elements and compare output for output."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = (t if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    frac = min(1.0, (DUMP_BUDGET_BYTES - 4096 * len(host)) / max(1, total))
+    for name, a in host.items():
+        shape = a.shape
+        if frac < 1.0:
+            k = int(a.size * frac)
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a))
+        log("dumped %s %s %s%s" % (name, a.dtype, list(shape), "" if frac >= 1.0 else " as a seeded sample of %d elements" % a.size))
 
 
 def cpu_model_name():
@@ -216,7 +257,7 @@ def main():
         def step(i=0):
             g, st = lanes[i % len(lanes)]
             with torch.cuda.stream(st):
-                return g.chain(key, labels, dains, want_all=False)[2]
+                return g.chain(key, labels, dains, want_all=False)
     else:
         # per-rank synthetic inputs (rank r renders its own frames)
         label, fake, prev = [t.to(dev) for t in synth.make_inputs(spec, B, H, W, 1000 * rank)]
@@ -229,12 +270,12 @@ def main():
             def step(i=0):
                 g, st = lanes[i % len(lanes)]
                 with torch.cuda.stream(st):
-                    return g.chain(prev, labels, dains, want_all=False)[2]
+                    return g.chain(prev, labels, dains, want_all=False)
         else:
             def step(i=0):
                 g, st = lanes[i % len(lanes)]
                 with torch.cuda.stream(st):
-                    return g.forward_blend(label, None, fake, prev)[2]     # forward + blend (the mask head writes the fused frame)
+                    return g.forward_blend(label, None, fake, prev)     # forward + blend (the mask head writes the fused frame)
 
     log("weights ready, warming up")
     for i in range(max(args.warmup, len(lanes))):
@@ -259,8 +300,13 @@ def main():
         dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
     fps = world * frames_per_step * args.steps / dt
+    # what the last timed step handed its caller: (img, mask, fuse) of the frame, or the segment's fused frames
+    # (chain / clips, want_all=False returns no imgs / masks)
+    outputs = {n: t for n, t in zip(("img", "mask", "fuse"), out) if t is not None}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs, log)
 
-    # ---- control-plane exchange (after the timed region): per-rank rates, blob checksums, replica check ----
+    # ---- control-plane exchange (after the timed region): per-rank rates, blob checksums, replica check (--full) ----
     per_rank_fps = ribdist.gather_rows(torch.tensor([frames_per_step * args.steps / dt_rank], dtype=torch.float64, device=dev), rank, world).flatten().tolist()
     # host-bound or device-bound?  per rank: time the launch thread spent enqueueing the timed steps vs the time until the
     # device finished them.  enqueue << total: the host runs ahead (device-bound); enqueue ~ total: the host is the limiter
@@ -275,15 +321,15 @@ def main():
     else:
         idents = ["rank 0 local_rank 0 " + ident]
     replica = None
-    if args.mode == "clips":
-        last = ribdist.gather_rows(out[-1].contiguous(), rank, world)      # every rank's last fused frame, [world,1,3,H,W]
+    if args.full and args.mode == "clips":
+        last = ribdist.gather_rows(outputs["fuse"][-1].contiguous(), rank, world)      # every rank's last fused frame, [world,1,3,H,W]
         if rank == 0:
             # rank 0 (whose weights came from load_state_dict, not from the broadcast) renders every rank's clip
             # itself, as a 1-GPU run would, and compares the last frames bit for bit
             eq = []
             for r in range(world):
                 if r == 0:
-                    mine = out[-1]
+                    mine = outputs["fuse"][-1]
                 else:
                     k_r, l_r, d_r = [t.to(dev) for t in clip_inputs(spec, synth, r, args.frames, H, W)]
                     mine = G.chain(k_r, l_r, d_r, want_all=False)[2][-1]
@@ -298,132 +344,134 @@ def main():
         return
 
     log("timed region done: %d steps, %.3f ms/step" % (args.steps, ms_per_step))
-    # ---- roofline of the dominant kernel class: profiling pass (not in the timed region) ----
-    # Every launch of the pass carries a (start, stop) HIP event pair bound to the dispatch itself (hipExtLaunchKernelGGL,
-    # rib_profile_begin_kernels): the difference is the kernel's own execution time on the launch stream - the duration
-    # rocprofv3 --kernel-trace reports for it - with no event packet between two launches.  (Rounds 1-3 put one event in
-    # FRONT of every launch and modelled the event cost away; that correction was only valid for one lane and one rank,
-    # ADVICE r03.)  The classes therefore do NOT add up to the timed step: the difference is the dependent-launch gaps.
-    flops = G.forward_flops(B, H, W)
-    G.profile_begin(kernels=True)
-    nprof = 20 if args.mode == "frame" else 1      # (5 steps gave the class time a run-to-run spread of +-3 %)
-    log("profile pass (separate from the timed region, after it): %d step(s) with an event pair on every dispatch" % nprof)
-    for _ in range(nprof):
-        step()
-    prof = G.profile_collect()
-    if args.mode != "frame":
-        nprof = nprof * args.frames          # per-forward averages
-    # The convolution class = the matrix-core launches (k_igemm incl. the Winograd-domain batched GEMMs, k_conv_lowc,
-    # k_conv_head) PLUS the launches that are part of computing those same convolutions: Winograd input / output
-    # transforms and split-K slab sums (class "conv_aux").
-    n_launch = sum(v["launches"] for v in prof.values()) / nprof
-    kernel_sum_ms = sum(v["ms"] for v in prof.values()) / nprof
-    step_ms_one = ms_per_step / (frames_per_step / B) if args.mode != "frame" else ms_per_step     # per forward
-    mm_ms = prof["igemm"]["ms"] / nprof
-    aux_ms = prof["conv_aux"]["ms"] / nprof
-    conv_ms = mm_ms + aux_ms
-    conv_launches = (prof["igemm"]["launches"] + prof["conv_aux"]["launches"]) / nprof
-    conv_tflops = flops["igemm"] / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-    spade_ms = prof["spade"]["ms"] / nprof
-    classes = {k: {"launches_per_step": v["launches"] / nprof, "kernel_ms_per_step": v["ms"] / nprof} for k, v in prof.items()}
-    # executed matrix work: the three mask-network upsample convolutions run as 2x2 phase convolutions, 4/9 of their
-    # nine-tap count, the Winograd-domain GEMMs execute 4/9 (F(2x2)) or 1/4 (F(4x4)) of theirs; everything
-    # else executes what it is priced at (channel padding not counted)
-    executed = 0.0
-    for info in G.launch_info(B, H, W):
-        if info["class"] == 0:
-            tile = info["tile"]
-            executed += info["flops"] * (0.25 if "wino4" in tile else 4.0 / 9.0 if ("ups1" in tile or "wino" in tile) else 1.0)
-    # rocprofv3 basis of the same class and HBM bytes per launch from the committed passes (tools/prof_ops.py,
-    # tools/pmc_traffic.py: FETCH_SIZE x2 on gfx950 + WRITE_SIZE, separate rocprofv3 --pmc passes); bench.py itself
-    # cannot read counters or kernel traces, so these are pointers to committed measurements of the same workload,
-    # NOT measured in this run.  They are only quoted when the committed files were made by THIS build (the stamp
-    # rib_build_info() reports is stored beside them by tools/refresh_profiles.sh).
     from render_in_between_amd import _native
     build = _native.build_info()
-    traffic = traffic_step = traffic_src = None
-    rocprof_basis = None
     default_workload = (B, H, W) == (1, 512, 512) and args.dtype == "f32" and args.mode == "frame"
-    prof_stamp = None
-    # the newest round's committed passes (profiles/rNN_build_stamp.txt is written by tools/refresh_profiles.sh rNN)
-    tags = sorted(f[:3] for f in os.listdir(os.path.join(ROOT, "profiles")) if f[3:] == "_build_stamp.txt" and f[0] == "r")
-    tag = tags[-1] if tags else "r00"
-    sp = os.path.join(ROOT, "profiles", tag + "_build_stamp.txt")
-    if os.path.exists(sp):
-        with open(sp) as f:
-            prof_stamp = f.read().split()[0]
-    same_build = prof_stamp == build["stamp"]
-    tp = os.path.join(ROOT, "profiles", tag + "_pmc_traffic.json")
-    if os.path.exists(tp) and default_workload:
-        with open(tp) as f:
-            tj = json.load(f)
-        cb = sum(tj["classes"].get(k, {}).get("hbm_bytes_corrected", 0.0) for k in ("igemm", "conv_aux"))
-        cl = sum(tj["classes"].get(k, {}).get("launches", 0) for k in ("igemm", "conv_aux"))
-        traffic = cb / max(1, cl)
-        traffic_step = tj["total_hbm_bytes_per_step"]
-        traffic_src = ("profiles/" + tag + "_pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of tools/prof_ops.py; not measured in "
-                       "this run; made by build %s, this run is build %s)" % (prof_stamp, build["stamp"]))
-    rp = os.path.join(ROOT, "profiles", tag + "_prof_ops_512.json")
-    if os.path.exists(rp) and default_workload:
-        with open(rp) as f:
-            rj = json.load(f)
-        us = sum(o["us"] for o in rj["ops"] if o["class"] in (0, 6))
-        nl = sum(1 for o in rj["ops"] if o["class"] in (0, 6))
-        if us > 0:
-            rocprof_basis = {"source": "profiles/" + tag + "_prof_ops_512.json (rocprofv3 --kernel-trace of tools/prof_ops.py --run; not measured in this run)",
-                             "made_by_build": prof_stamp, "same_build_as_this_run": same_build,
-                             "class_us_per_step": us, "launches_per_step": nl, "avg_launch_us": us / nl,
-                             "achieved_tflops": flops["igemm"] / (us * 1e-6) / 1e12, "frac": flops["igemm"] / (us * 1e-6) / 1e12 / PEAK_F32_MFMA_TFLOPS}
-    peak = {"f32": PEAK_F32_MFMA_TFLOPS, "bf16": PEAK_BF16_MFMA_TFLOPS, "f16": PEAK_BF16_MFMA_TFLOPS}[args.dtype]
-    # fused-minimum HBM model of SURVEY 8(d) (every conv reads its input and writes its output once, one extra read per
-    # normalised tensor, one cond read per SPADE layer, weights once): 2.82 GB per 512x512 fp32 frame, of which 0.123 GB
-    # are weights; activations scale with the pixel count, bf16 storage halves everything
-    alg_bytes = frame_bytes_model(B, H, W, args.dtype)
-    hbm_gbs = alg_bytes * (frames_per_step / B) / (ms_per_step * 1e-3) / 1e9
-    # headline fraction: the live kernel-time figure, unless the committed rocprofv3 trace of this very build says less
-    live_frac = conv_tflops / peak
-    frac, frac_basis = live_frac, "live: HIP event pairs bound to each dispatch (hipExtLaunchKernelGGL) on the launch stream"
-    if rocprof_basis and same_build and rocprof_basis["frac"] < live_frac:
-        frac, frac_basis = rocprof_basis["frac"], "rocprofv3 --kernel-trace of the same build (lower than the live figure %.4f)" % live_frac
-    roofline = {
-        "bound": "mfma",
-        # "algorithmic" = nine-tap 2*MAC count of SURVEY 8(d) over the convolutions of the class
-        "kernel": "convolution class: k_igemm (%s MFMA implicit GEMM, incl. the Winograd-domain batched GEMMs), k_conv_lowc (first layers), "
-                  "k_conv_head (2 heads) = %d matrix-core launches/step, PLUS their %d Winograd-transform / split-K-sum launches/step"
-                  % (args.dtype, int(prof["igemm"]["launches"] / nprof), int(prof["conv_aux"]["launches"] / nprof)),
-        "achieved": frac * peak, "peak": peak, "unit": "TFLOP/s",
-        "frac": frac, "frac_basis": frac_basis,
-        "live_achieved": conv_tflops, "live_frac": live_frac,
-        "avg_launch_us": conv_ms * 1e3 / max(1.0, conv_launches),
-        "class_kernel_ms_per_step": conv_ms, "matrix_core_launches_ms_per_step": mm_ms, "transform_and_splitk_sum_launches_ms_per_step": aux_ms,
-        "algorithmic_gflop_per_step": flops["igemm"] / 1e9,
-        "executed_gflop_per_step": executed / 1e9,
-        "executed_tflops": executed / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0,
-        "frac_executed": (executed / (conv_ms * 1e-3) / 1e12 / peak) if conv_ms > 0 else 0.0,
-        "rocprof_basis": rocprof_basis,
-        "traffic": traffic,
-        "traffic_bytes_per_step_all_classes": traffic_step,
-        "traffic_source": traffic_src,
-        "classes": classes,
-        "kernel_time_sum_ms_per_step": kernel_sum_ms, "timed_step_ms": step_ms_one,
-        "launch_gaps_ms_per_step": step_ms_one - kernel_sum_ms, "launches_per_step": n_launch,
-        "spade_tflops": flops["spade"] / (spade_ms * 1e-3) / 1e12 if spade_ms > 0 else 0.0,
-        "whole_step_frac_of_mfma_roof": (sum(flops.values()) * (frames_per_step / B) / (PEAK_F32_MFMA_TFLOPS * 1e12)) / (ms_per_step * 1e-3),
-        "whole_step_algorithmic_hbm_gbs": hbm_gbs, "whole_step_frac_of_hbm_roof": hbm_gbs / PEAK_HBM_GBS,
-    }
-    if args.dtype != "f32":
-        # with 16-bit matrix cores (2.5 PFLOP/s) the frame's roof is HBM (0.18 ms at 512x512): report against that;
-        # the matrix-core figures of the convolution class stay in the object for reference
-        roofline.update({"bound": "hbm", "mfma_achieved_tflops": conv_tflops, "mfma_frac": conv_tflops / peak,
-                         "kernel": "whole frame (the bf16 frame is bound by HBM, not by any one kernel): fused-minimum bytes of SURVEY 8(d) / frame time",
-                         "achieved": hbm_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": hbm_gbs / PEAK_HBM_GBS,
-                         "frac_basis": "fused-minimum bytes / timed step", "algorithmic_bytes_per_frame": alg_bytes})
+    roofline = None
+    if args.full:
+        # ---- roofline of the dominant kernel class: profiling pass (not in the timed region) ----
+        # Every launch of the pass carries a (start, stop) HIP event pair bound to the dispatch itself (hipExtLaunchKernelGGL,
+        # rib_profile_begin_kernels): the difference is the kernel's own execution time on the launch stream - the duration
+        # rocprofv3 --kernel-trace reports for it - with no event packet between two launches.  (Rounds 1-3 put one event in
+        # FRONT of every launch and modelled the event cost away; that correction was only valid for one lane and one rank,
+        # ADVICE r03.)  The classes therefore do NOT add up to the timed step: the difference is the dependent-launch gaps.
+        flops = G.forward_flops(B, H, W)
+        G.profile_begin(kernels=True)
+        nprof = 20 if args.mode == "frame" else 1      # (5 steps gave the class time a run-to-run spread of +-3 %)
+        log("profile pass (separate from the timed region, after it): %d step(s) with an event pair on every dispatch" % nprof)
+        for _ in range(nprof):
+            step()
+        prof = G.profile_collect()
+        if args.mode != "frame":
+            nprof = nprof * args.frames          # per-forward averages
+        # The convolution class = the matrix-core launches (k_igemm incl. the Winograd-domain batched GEMMs, k_conv_lowc,
+        # k_conv_head) PLUS the launches that are part of computing those same convolutions: Winograd input / output
+        # transforms and split-K slab sums (class "conv_aux").
+        n_launch = sum(v["launches"] for v in prof.values()) / nprof
+        kernel_sum_ms = sum(v["ms"] for v in prof.values()) / nprof
+        step_ms_one = ms_per_step / (frames_per_step / B) if args.mode != "frame" else ms_per_step     # per forward
+        mm_ms = prof["igemm"]["ms"] / nprof
+        aux_ms = prof["conv_aux"]["ms"] / nprof
+        conv_ms = mm_ms + aux_ms
+        conv_launches = (prof["igemm"]["launches"] + prof["conv_aux"]["launches"]) / nprof
+        conv_tflops = flops["igemm"] / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+        spade_ms = prof["spade"]["ms"] / nprof
+        classes = {k: {"launches_per_step": v["launches"] / nprof, "kernel_ms_per_step": v["ms"] / nprof} for k, v in prof.items()}
+        # executed matrix work: the three mask-network upsample convolutions run as 2x2 phase convolutions, 4/9 of their
+        # nine-tap count, the Winograd-domain GEMMs execute 4/9 (F(2x2)) or 1/4 (F(4x4)) of theirs; everything
+        # else executes what it is priced at (channel padding not counted)
+        executed = 0.0
+        for info in G.launch_info(B, H, W):
+            if info["class"] == 0:
+                tile = info["tile"]
+                executed += info["flops"] * (0.25 if "wino4" in tile else 4.0 / 9.0 if ("ups1" in tile or "wino" in tile) else 1.0)
+        # rocprofv3 basis of the same class and HBM bytes per launch from the committed passes (tools/prof_ops.py,
+        # tools/pmc_traffic.py: FETCH_SIZE x2 on gfx950 + WRITE_SIZE, separate rocprofv3 --pmc passes); bench.py itself
+        # cannot read counters or kernel traces, so these are pointers to committed measurements of the same workload,
+        # NOT measured in this run.  They are only quoted when the committed files were made by THIS build (the stamp
+        # rib_build_info() reports is stored beside them by tools/refresh_profiles.sh).
+        traffic = traffic_step = traffic_src = None
+        rocprof_basis = None
+        prof_stamp = None
+        # the newest round's committed passes (profiles/rNN_build_stamp.txt is written by tools/refresh_profiles.sh rNN)
+        tags = sorted(f[:3] for f in os.listdir(os.path.join(ROOT, "profiles")) if f[3:] == "_build_stamp.txt" and f[0] == "r")
+        tag = tags[-1] if tags else "r00"
+        sp = os.path.join(ROOT, "profiles", tag + "_build_stamp.txt")
+        if os.path.exists(sp):
+            with open(sp) as f:
+                prof_stamp = f.read().split()[0]
+        same_build = prof_stamp == build["stamp"]
+        tp = os.path.join(ROOT, "profiles", tag + "_pmc_traffic.json")
+        if os.path.exists(tp) and default_workload:
+            with open(tp) as f:
+                tj = json.load(f)
+            cb = sum(tj["classes"].get(k, {}).get("hbm_bytes_corrected", 0.0) for k in ("igemm", "conv_aux"))
+            cl = sum(tj["classes"].get(k, {}).get("launches", 0) for k in ("igemm", "conv_aux"))
+            traffic = cb / max(1, cl)
+            traffic_step = tj["total_hbm_bytes_per_step"]
+            traffic_src = ("profiles/" + tag + "_pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of tools/prof_ops.py; not measured in "
+                           "this run; made by build %s, this run is build %s)" % (prof_stamp, build["stamp"]))
+        rp = os.path.join(ROOT, "profiles", tag + "_prof_ops_512.json")
+        if os.path.exists(rp) and default_workload:
+            with open(rp) as f:
+                rj = json.load(f)
+            us = sum(o["us"] for o in rj["ops"] if o["class"] in (0, 6))
+            nl = sum(1 for o in rj["ops"] if o["class"] in (0, 6))
+            if us > 0:
+                rocprof_basis = {"source": "profiles/" + tag + "_prof_ops_512.json (rocprofv3 --kernel-trace of tools/prof_ops.py --run; not measured in this run)",
+                                 "made_by_build": prof_stamp, "same_build_as_this_run": same_build,
+                                 "class_us_per_step": us, "launches_per_step": nl, "avg_launch_us": us / nl,
+                                 "achieved_tflops": flops["igemm"] / (us * 1e-6) / 1e12, "frac": flops["igemm"] / (us * 1e-6) / 1e12 / PEAK_F32_MFMA_TFLOPS}
+        peak = {"f32": PEAK_F32_MFMA_TFLOPS, "bf16": PEAK_BF16_MFMA_TFLOPS, "f16": PEAK_BF16_MFMA_TFLOPS}[args.dtype]
+        # fused-minimum HBM model of SURVEY 8(d) (every conv reads its input and writes its output once, one extra read per
+        # normalised tensor, one cond read per SPADE layer, weights once): 2.82 GB per 512x512 fp32 frame, of which 0.123 GB
+        # are weights; activations scale with the pixel count, bf16 storage halves everything
+        alg_bytes = frame_bytes_model(B, H, W, args.dtype)
+        hbm_gbs = alg_bytes * (frames_per_step / B) / (ms_per_step * 1e-3) / 1e9
+        # headline fraction: the live kernel-time figure, unless the committed rocprofv3 trace of this very build says less
+        live_frac = conv_tflops / peak
+        frac, frac_basis = live_frac, "live: HIP event pairs bound to each dispatch (hipExtLaunchKernelGGL) on the launch stream"
+        if rocprof_basis and same_build and rocprof_basis["frac"] < live_frac:
+            frac, frac_basis = rocprof_basis["frac"], "rocprofv3 --kernel-trace of the same build (lower than the live figure %.4f)" % live_frac
+        roofline = {
+            "bound": "mfma",
+            # "algorithmic" = nine-tap 2*MAC count of SURVEY 8(d) over the convolutions of the class
+            "kernel": "convolution class: k_igemm (%s MFMA implicit GEMM, incl. the Winograd-domain batched GEMMs), k_conv_lowc (first layers), "
+                      "k_conv_head (2 heads) = %d matrix-core launches/step, PLUS their %d Winograd-transform / split-K-sum launches/step"
+                      % (args.dtype, int(prof["igemm"]["launches"] / nprof), int(prof["conv_aux"]["launches"] / nprof)),
+            "achieved": frac * peak, "peak": peak, "unit": "TFLOP/s",
+            "frac": frac, "frac_basis": frac_basis,
+            "live_achieved": conv_tflops, "live_frac": live_frac,
+            "avg_launch_us": conv_ms * 1e3 / max(1.0, conv_launches),
+            "class_kernel_ms_per_step": conv_ms, "matrix_core_launches_ms_per_step": mm_ms, "transform_and_splitk_sum_launches_ms_per_step": aux_ms,
+            "algorithmic_gflop_per_step": flops["igemm"] / 1e9,
+            "executed_gflop_per_step": executed / 1e9,
+            "executed_tflops": executed / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0,
+            "frac_executed": (executed / (conv_ms * 1e-3) / 1e12 / peak) if conv_ms > 0 else 0.0,
+            "rocprof_basis": rocprof_basis,
+            "traffic": traffic,
+            "traffic_bytes_per_step_all_classes": traffic_step,
+            "traffic_source": traffic_src,
+            "classes": classes,
+            "kernel_time_sum_ms_per_step": kernel_sum_ms, "timed_step_ms": step_ms_one,
+            "launch_gaps_ms_per_step": step_ms_one - kernel_sum_ms, "launches_per_step": n_launch,
+            "spade_tflops": flops["spade"] / (spade_ms * 1e-3) / 1e12 if spade_ms > 0 else 0.0,
+            "whole_step_frac_of_mfma_roof": (sum(flops.values()) * (frames_per_step / B) / (PEAK_F32_MFMA_TFLOPS * 1e12)) / (ms_per_step * 1e-3),
+            "whole_step_algorithmic_hbm_gbs": hbm_gbs, "whole_step_frac_of_hbm_roof": hbm_gbs / PEAK_HBM_GBS,
+        }
+        if args.dtype != "f32":
+            # with 16-bit matrix cores (2.5 PFLOP/s) the frame's roof is HBM (0.18 ms at 512x512): report against that;
+            # the matrix-core figures of the convolution class stay in the object for reference
+            roofline.update({"bound": "hbm", "mfma_achieved_tflops": conv_tflops, "mfma_frac": conv_tflops / peak,
+                             "kernel": "whole frame (the bf16 frame is bound by HBM, not by any one kernel): fused-minimum bytes of SURVEY 8(d) / frame time",
+                             "achieved": hbm_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": hbm_gbs / PEAK_HBM_GBS,
+                             "frac_basis": "fused-minimum bytes / timed step", "algorithmic_bytes_per_frame": alg_bytes})
 
-    log("profile pass done: conv %.3f ms/step" % conv_ms)
+        log("profile pass done: conv %.3f ms/step" % conv_ms)
     # ---- parity on the bench inputs + CPU baseline (oracle timed on the host cores) ----
     cpu = None
     parity = None
-    if not args.no_cpu_baseline and args.mode == "frame" and world == 1:   # rank 0 at N=1 only
+    if args.full and not args.no_cpu_baseline and args.mode == "frame" and world == 1:   # rank 0 at N=1 only
         from oracle import generator_ref
         R = generator_ref.RefGenerator(spec, sd)
         # the oracle is timed "with os.cpu_count() threads and again with 8 threads".  The GPU boxes show 256 CPUs
@@ -463,9 +511,9 @@ def main():
 
     # ---- the other single-GPU BASELINE configurations, measured briefly in the same process: the
     # 32-frame bf16 chain (configs[2]) and one 1024x1024 batch-4 fp32 forward (configs[4]); plus the opt-in split-product
-    # setting on the headline workload, named as such.  Only beside the default command's line; never part of `value`.
+    # setting on the headline workload, named as such.  Only beside the line of the default workload run with --full; never part of `value`.
     others = None
-    if default_workload and world == 1 and args.products == "f32" and not args.no_other_configs and not args.no_tuning and args.inflight == 1:
+    if args.full and default_workload and world == 1 and args.products == "f32" and not args.no_other_configs and not args.no_tuning and args.inflight == 1:
         others = []
         if sd is None:
             sd = synth.make_state_dict(spec, 0)

@@ -245,6 +245,10 @@ def test_a_failed_start_up_names_rank_device_backend_and_ipc_mode(monkeypatch, c
     for k, v in (("RANK", "5"), ("WORLD_SIZE", "8"), ("LOCAL_RANK", "5"), ("HSA_ENABLE_IPC_MODE_LEGACY", "0"), ("MASTER_ADDR", "127.0.0.1"), ("MASTER_PORT", "29400")):
         monkeypatch.setenv(k, v)
     monkeypatch.delenv("RIB_BENCH_DEVICE", raising=False)
+    # the failure line asks torch whether a GPU is visible: start the GPU runtime first, so that what its own start-up
+    # prints on a GPU machine (e.g. libdrm's notice about amdgpu.ids) is not taken for the phase's output
+    torch.cuda.is_available()
+    capfd.readouterr()
     with pytest.raises(RuntimeError, match="unhandled system error"):
         with ribdist.startup_phase("init_process_group(nccl) + first communicator"):
             raise RuntimeError("NCCL error in: ProcessGroupNCCL.cpp:2000, unhandled system error\nhipIpcGetMemHandle: invalid argument")

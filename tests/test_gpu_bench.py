@@ -21,7 +21,7 @@ def _bench(*flags):
 
 @pytest.mark.gpu
 def test_bench_line_has_the_contract_fields_and_a_live_roofline():
-    j = _bench("--size", "64", "--cpu-frames", "5")
+    j = _bench("--full", "--size", "64", "--cpu-frames", "5")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in j, k
@@ -40,11 +40,37 @@ def test_bench_line_has_the_contract_fields_and_a_live_roofline():
 
 @pytest.mark.gpu
 def test_bench_other_modes_and_shapes():
-    j = _bench("--no-cpu-baseline", "--height", "64", "--width", "96", "--mode", "chain", "--frames", "4", "--batch", "2")
+    j = _bench("--full", "--no-cpu-baseline", "--height", "64", "--width", "96", "--mode", "chain", "--frames", "4", "--batch", "2")
     assert j["config"]["height"] == 64 and j["config"]["width"] == 96 and j["config"]["frames_per_step_per_gpu"] == 8
     assert j["cpu_baseline"] is None and j["value"] > 0
-    j = _bench("--no-cpu-baseline", "--size", "64", "--mode", "clips", "--frames", "3", "--graph", "--dtype", "bf16")
+    j = _bench("--full", "--no-cpu-baseline", "--size", "64", "--mode", "clips", "--frames", "3", "--graph", "--dtype", "bf16")
     g = j["config"]["graph_replay"]
     assert g["captures"] >= 1 and g["captures"] + g["replays"] == 1 + 3      # warm-up + timed steps (the profiling pass launches kernel by kernel)
     assert j["config"]["replica_check"]["all_equal"] and j["roofline"]["bound"] == "hbm"
     assert len(j["config"]["per_rank_host_enqueue_ms_per_step"]) == 1
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_what_the_last_step_returned(tmp_path):
+    """Without --full the line carries the headline only (no profiling pass, CPU baseline or other configurations), and
+    --dump-outputs writes the last timed step's (img, mask, fuse) as float32 .npy files: they are the frame the oracle
+    computes from the same seeded weights and inputs."""
+    import numpy as np
+    import render_in_between_amd as rib
+    from render_in_between_amd import synth
+    from oracle import generator_ref
+    j = _bench("--size", "64", "--steps", "5", "--dump-outputs", str(tmp_path))
+    assert j["steps"] == 5 and j["warmup"] == 1 and j["dtype"] == "f32" and j["higher_is_better"] is True
+    assert j["unit"] == "frames/s" and j["value"] > 0 and abs(j["value"] - 1e3 / j["ms_per_step"]) < 1e-6 * j["value"]
+    assert j["roofline"] is None and j["cpu_baseline"] is None and j["parity"] is None and j["other_configs"] is None
+    got = {n: np.load(str(tmp_path / (n + ".npy"))) for n in ("img", "mask", "fuse")}
+    assert sorted(os.listdir(str(tmp_path))) == ["fuse.npy", "img.npy", "mask.npy"]
+    assert got["img"].shape == (1, 3, 64, 64) and got["mask"].shape == (1, 1, 64, 64) and got["fuse"].shape == (1, 3, 64, 64)
+    assert all(a.dtype == np.float32 for a in got.values())
+    spec = rib.GenSpec.from_cfg(rib.hsm_gen_config())
+    sd = synth.make_state_dict(spec, 0)
+    label, fake, prev = synth.make_inputs(spec, 1, 64, 64, 0)
+    oimg, omask = generator_ref.RefGenerator(spec, sd)(label, None, fake, prev)
+    assert float(np.abs(got["img"] - oimg.numpy()).max()) <= 1e-3
+    assert float(np.abs(got["mask"] - omask.numpy()).max()) <= 1e-3
+    assert float(np.abs(got["fuse"] - generator_ref.blend(oimg, omask, fake).numpy()).max()) <= 1e-3

@@ -10,9 +10,9 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # which build made these files: bench.py quotes the committed rocprofv3 / PMC figures only beside the same build's stamp
 python3 -c "import sys; sys.path.insert(0, '$ROOT'); from render_in_between_amd import _native; b = _native.build_info(); print(b['stamp'], b['raw'])" > $OUT/${TAG}_build_stamp.txt
-echo "[refresh] bench (default command)"; python3 $ROOT/bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+echo "[refresh] bench (default command, with --full)"; python3 $ROOT/bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 echo "[refresh] rocprofv3 --stats of the bench command"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -o bench -- python3 $ROOT/bench.py --no-cpu-baseline --no-other-configs > $OUT/${TAG}_bench_prof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -o bench -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-other-configs > $OUT/${TAG}_bench_prof.log 2>&1
 cp $OUT/prof_bench/bench_kernel_stats.csv $OUT/${TAG}_bench_kernel_stats.csv
 echo "[refresh] per-op table"
 rocprofv3 --kernel-trace --output-format csv -d $OUT/prof_ops -- python3 $ROOT/tools/prof_ops.py --run > $OUT/${TAG}_prof_ops.log 2>&1
@@ -47,7 +47,7 @@ echo "[refresh] other shapes and modes"
 rm -f $OUT/${TAG}_other_shapes.jsonl $OUT/${TAG}_other_shapes.err
 for flags in "--height 320 --width 480" "--height 320 --width 480 --no-tuning" "--height 320 --width 480 --dtype bf16" "--height 320 --width 480 --dtype bf16 --no-tuning" "--height 320 --width 480 --mode chain --frames 16 --batch 8" "--height 320 --width 480 --dtype bf16 --mode chain --frames 16 --batch 8" "--mode chain --frames 32" "--mode chain --frames 32 --batch 4" "--mode chain --frames 32 --batch 8" "--mode chain --frames 32 --batch 3 --plan-batch 4" "--mode chain --frames 32 --batch 1 --plan-batch 4" "--height 320 --width 480 --mode chain --frames 16 --batch 3 --plan-batch 8" "--mode clips --frames 32" "--mode clips --frames 32 --graph" "--dtype bf16" "--dtype bf16 --mode chain --frames 32" "--dtype bf16 --mode chain --frames 32 --batch 4" "--dtype f16" "--dtype f16 --mode chain --frames 32" "--inflight 3" "--batch 2" "--batch 4" "--batch 8" "--size 1024 --batch 4" "--size 1024 --batch 4 --dtype bf16" "--size 1024" "--size 256"; do
   echo "## $flags" >> $OUT/${TAG}_other_shapes.jsonl
-  python3 $ROOT/bench.py --no-cpu-baseline --steps 20 --warmup 5 $flags >> $OUT/${TAG}_other_shapes.jsonl 2>> $OUT/${TAG}_other_shapes.err
+  python3 $ROOT/bench.py --full --no-cpu-baseline --steps 20 --warmup 5 $flags >> $OUT/${TAG}_other_shapes.jsonl 2>> $OUT/${TAG}_other_shapes.err
 done
 echo "[refresh] exact fp32 against the opt-in split products: frame rate A/B in this box, error of both against an fp64 oracle"
 rm -f $OUT/${TAG}_x3_frame_ab.txt
@@ -67,17 +67,17 @@ torch.save({"state_dict": synth.make_state_dict(rib.GenSpec.from_cfg(rib.hsm_gen
 PYEOF
 (cd $ROOT && python3 tools/verify_checkpoint.py /tmp/synth_netG.pth --out /tmp/synth_gold --sizes 64 128 256 --report $OUT/${TAG}_verify_checkpoint_synthetic.json > /dev/null 2>&1) || echo "verify_checkpoint failed"
 echo "[refresh] bf16 kernel stats (config 3)"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bf16 -o bench -- python3 $ROOT/bench.py --no-cpu-baseline --dtype bf16 --mode chain --frames 32 --steps 10 --warmup 2 > $OUT/${TAG}_bench_bf16_prof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bf16 -o bench -- python3 $ROOT/bench.py --full --no-cpu-baseline --dtype bf16 --mode chain --frames 32 --steps 10 --warmup 2 > $OUT/${TAG}_bench_bf16_prof.log 2>&1
 cp $OUT/prof_bf16/bench_kernel_stats.csv $OUT/${TAG}_bench_bf16_kernel_stats.csv
 echo "[refresh] multi-rank rehearsals on one GPU (the ranks share device 0, gloo instead of RCCL; at most 6 processes may use the card): BASELINE config 4 shape"
 cd $ROOT
-RIB_BENCH_DEVICE=0 RIB_DIST_BACKEND=gloo python3 bench.py --gpus 2 --mode clips --steps 3 --warmup 1 2> $OUT/${TAG}_clips_2ranks_1gpu.err | grep '^{' > $OUT/${TAG}_clips_2ranks_1gpu.json      # (gloo prints its connection banner on stdout)
+RIB_BENCH_DEVICE=0 RIB_DIST_BACKEND=gloo python3 bench.py --full --gpus 2 --mode clips --steps 3 --warmup 1 2> $OUT/${TAG}_clips_2ranks_1gpu.err | grep '^{' > $OUT/${TAG}_clips_2ranks_1gpu.json      # (gloo prints its connection banner on stdout)
 # five ranks on the one GPU (their parent process counts against the limit of 6), launch by launch and as graph replays: replicas bit-equal, host-enqueue vs device time per rank
 # (the known-good reference log for the first real multi-GPU run; the card is time-shared, so the rates say nothing)
 rm -f $OUT/${TAG}_clips_5ranks_1gpu.jsonl
 for flags in "" "--graph"; do
   echo "## bench.py --gpus 5 --mode clips --frames 16 $flags" >> $OUT/${TAG}_clips_5ranks_1gpu.jsonl
-  RIB_BENCH_DEVICE=0 RIB_DIST_BACKEND=gloo timeout -k 10 400 python3 bench.py --gpus 5 --mode clips --frames 16 --steps 2 --warmup 1 $flags 2>> $OUT/${TAG}_clips_5ranks_1gpu.err | grep '^{' | python3 -c "
+  RIB_BENCH_DEVICE=0 RIB_DIST_BACKEND=gloo timeout -k 10 400 python3 bench.py --full --gpus 5 --mode clips --frames 16 --steps 2 --warmup 1 $flags 2>> $OUT/${TAG}_clips_5ranks_1gpu.err | grep '^{' | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read()); c = d['config']
 print(json.dumps({'value': d['value'], 'n_gpus': d['n_gpus'], 'replica_check': c['replica_check'], 'blob_checksum_equal_on_all_ranks': c['blob_checksum_equal_on_all_ranks'],
