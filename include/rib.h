@@ -160,6 +160,15 @@ int rib_blend(rib_handle* h, int B, int C, int H, int W, const float* img, const
 /* uint8 HWC frame = uint8(clip(x*0.5+0.5,0,1)*255), truncating (PGNR/utils/utils.py:129-142). */
 int rib_quantise(rib_handle* h, int B, int C, int H, int W, const float* img_nchw,
                  uint8_t* out_nhwc, void* hip_stream);
+/* ---- quality metrics against ground truth (PGNR/models/evaluator.py:149-163, piq defaults; restated from piq, unpinned) ----
+ * Masked PSNR / SSIM of B frames: pred, target NCHW fp32 in [-1,1] (C = 3); mask [B,H,W] in [0,1] or NULL.
+ * x = clamp(pred*0.5+0.5, 0, 1)*mask (likewise y); psnr[b] = -10 log10(mean (x-y)^2 + 1e-8) at full resolution;
+ * ssim[b] = mean of the 11x11 gaussian (sigma 1.5, valid) SSIM map after f x f average pooling, f = max(1, round(min(H,W)/256)).
+ * Per-frame results on the device; the pooled side must be at least 11 (RIB_ERR_INVALID otherwise, as piq raises).
+ * Deterministic: no atomics, a frame's values do not depend on B.  The workspace is sized for C = 3; 0 = invalid shape. */
+size_t rib_quality_workspace_bytes(rib_handle* h, int B, int H, int W);
+int rib_quality(rib_handle* h, int B, int C, int H, int W, const float* pred, const float* target,
+                const float* mask, float* psnr, float* ssim, void* workspace, size_t workspace_bytes, void* hip_stream);
 /* ---- label-map rasterisation --------------------------------------------------
  * Replaces, per frame, Dataset._generate_skeleton + _generate_pose_map
  * (PGNR/datasets/HSM_auto_dataset.py:205-251; drawing rules PGNR/utils/keypoint2img.py:36-88,132-147)

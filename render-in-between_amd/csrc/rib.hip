@@ -11,6 +11,7 @@
 //   * the autoregressive segment driver (PGNR/models/evaluator.py:238-262).
 #include "kernels.hip.h"
 #include "raster.hip.h"
+#include "quality.hip.h"
 #include <hip/hip_ext.h>
 #include "../../include/rib.h"
 
@@ -2728,6 +2729,47 @@ int rib_quantise(rib_handle* h, int B, int C, int H, int W, const float* img, ui
   const size_t total = (size_t)B * C * H * W;
   const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 4096);
   RIB_KLAUNCH(k_quantise, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream), img, out, C, H * W, total);
+  HIP_TRY(h, hipGetLastError());
+  return RIB_OK;
+}
+
+// rib_quality: the pooling factor, the tile grid and the workspace of one shape (quality.hip.h)
+static bool quality_shape(int H, int W, int* f, int* Hp, int* Wp, int* tilesX, int* tilesY) {
+  if (H < 1 || W < 1) return false;
+  *f = std::max(1, (int)std::nearbyint(std::min(H, W) / 256.0));     // Python's round: half to even (fe default mode)
+  *Hp = H / *f; *Wp = W / *f;
+  if (*Hp < QUAL_K || *Wp < QUAL_K) return false;
+  *tilesX = (*Wp - (QUAL_K - 1) + QUAL_OW - 1) / QUAL_OW;
+  *tilesY = (*Hp - (QUAL_K - 1) + QUAL_OH - 1) / QUAL_OH;
+  return true;
+}
+
+static size_t quality_ws_bytes(int B, int C, int tilesX, int tilesY) {
+  return align256((size_t)B * C * tilesX * tilesY * 2 * sizeof(double));
+}
+
+size_t rib_quality_workspace_bytes(rib_handle* h, int B, int H, int W) {
+  int f, Hp, Wp, tx, ty;
+  if (!h || B < 1 || !quality_shape(H, W, &f, &Hp, &Wp, &tx, &ty)) return 0;
+  return quality_ws_bytes(B, 3, tx, ty);
+}
+
+int rib_quality(rib_handle* h, int B, int C, int H, int W, const float* pred, const float* target, const float* mask,
+                float* psnr, float* ssim, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  if (!h) return RIB_ERR_INVALID;
+  if (!pred || !target || !psnr || !ssim || !workspace) return fail(h, RIB_ERR_INVALID, "rib_quality: null pointer");
+  int f, Hp, Wp, tilesX, tilesY;
+  if (B < 1 || C < 1 || !quality_shape(H, W, &f, &Hp, &Wp, &tilesX, &tilesY))
+    return fail(h, RIB_ERR_INVALID, fmt("rib_quality: B=%d C=%d H=%d W=%d: the pooled frame must be at least %d x %d", B, C, H, W, QUAL_K, QUAL_K));
+  const size_t need = quality_ws_bytes(B, C, tilesX, tilesY);
+  if (workspace_bytes < need) return fail(h, RIB_ERR_WORKSPACE, fmt("rib_quality: workspace %zu < required %zu bytes", workspace_bytes, need));
+  if (h->device >= 0) HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  double* partials = reinterpret_cast<double*>(workspace);
+  RIB_KLAUNCH(k_quality_tiles, dim3(tilesX * tilesY, B * C), dim3(256), 0, st, pred, target, mask, C, H, W, f, Hp, Wp, tilesX, tilesY, partials);
+  HIP_TRY(h, hipGetLastError());
+  RIB_KLAUNCH(k_quality_finalize, dim3(B), dim3(256), 0, st, (const double*)partials, C, tilesX * tilesY, H, W,
+              Hp - (QUAL_K - 1), Wp - (QUAL_K - 1), psnr, ssim);
   HIP_TRY(h, hipGetLastError());
   return RIB_OK;
 }

@@ -26,6 +26,13 @@ Differences from the reference, none of which change a pixel:
   * multi-GPU: the independent units (the segments between key frames, evaluator.py:240-244, over all clips,
     :169-171) are dealt round-robin to the ranks of the process group (distributed.shard_units); every rank
     decodes, renders and writes only its own frames, with no communication after the weight broadcast.
+
+Ground-truth metrics (metrics=True with a gt_dir; the reference measures in evaluate_from_dataset, evaluator.py:113-134): every
+non-key frame (i % sample_rate != 0; at sample_rate 2 exactly the reference's rule, :116) is measured twice against gt_dir's
+frame i - its fused frame (OURS) and its DAIN frame (DAIN) - with compute_metrics' PSNR / SSIM (metrics.py), optionally under
+a mask from mask_dir/<clip>/.  The native path decodes the GT frame in the frame's own decode task, measures on the GPU
+(rib_quality) right after the unit's chain and brings the per-frame values home in the unit's one device-to-host copy.
+<save_dir>/metrics.json reports every clip (the reference keeps only the last clip's dict) and the mean over all frames.
 """
 from __future__ import annotations
 
@@ -40,6 +47,7 @@ import numpy as np
 import torch
 
 from . import io_worker, rasterise
+from . import metrics as _metrics
 
 
 def sample_rate_of(num_pose: int, num_key: int) -> int:
@@ -295,16 +303,19 @@ class Evaluator:
         self._pool = None                                   # created on first use, kept across calls (thread start-up is ~2 ms each)
         self._finishers = None
         self.timings = {}                                   # seconds per phase of the last evaluate_from_folder
+        self.metrics = None                                 # per-frame ground-truth records of the last call with metrics=True
+        self.metrics_report = None                          # ... and the report written to <save_dir>/metrics.json
         self.height = cfg.model_height                      # HSM_auto_dataset.py:55-56
         self.width = cfg.model_width
         self.gauss_sigma = getattr(cfg, "gauss_sigma", 5)
         self.skeleton_thres = getattr(cfg, "skeleton_thres", 0.001)
         self.foot_thres = getattr(cfg, "foot_thres", 0.001)
 
-    def _shm_fits(self):
+    def _shm_fits(self, frames_per_slot=1.0):
         """Is there room in /dev/shm for the pipeline's windows of shared staging blocks?  (A container may mount 64 MB there,
-        and a write beyond it is a bus error, not an exception: the file-side work then stays on threads, with a warning.)"""
-        unit = max(1, self.chunk) * (self.batch or self.default_batch()) * self.height * self.width * 3
+        and a write beyond it is a bus error, not an exception: the file-side work then stays on threads, with a warning.)
+        frames_per_slot: staged frames per output frame (metrics: DAIN + GT frame + mask)."""
+        unit = int(max(1, self.chunk) * (self.batch or self.default_batch()) * self.height * self.width * 3 * frames_per_slot)
         need = (DECODE_AHEAD + MAX_UNITS_IN_FLIGHT + 4) * unit
         try:
             st = os.statvfs("/dev/shm")
@@ -423,19 +434,34 @@ class Evaluator:
             if graph:
                 model.set_graph_replay(True)
 
+    # ---- ground-truth metrics (evaluator.py:149-163) ------------------------------------------------
+    def compute_metrics(self, pred, target, mask=None):
+        """The reference's compute_metrics: frames [B,3,H,W] in [-1,1], mask [B,H,W] or None -> batch-mean (PSNR, SSIM) as 0-d
+        tensors (piq's psnr(data_range=1, reduction='mean') and ssim(data_range=1), restated in metrics.py).  Device tensors
+        are measured by the HIP kernels of the last native model this Evaluator drove, CPU tensors by the torch statement."""
+        p, s_ = _metrics.psnr_ssim(pred, target, mask, model=getattr(self, "_quality_model", None))
+        return p.mean(), s_.mean()
+
     # ---- the driver ------------------------------------------------------------------------------
     @torch.no_grad()
     def evaluate_from_folder(self, model, train_dir, dain_dir, pose_dir, save_dir, gt_dir=None, gen_vid=False,
-                             rank=None, world=None):
+                             rank=None, world=None, metrics=False, mask_dir=None):
         """rank / world: this process's share of the independent units (default: the torch.distributed process
         group when one is initialised, else everything).  Returns the frames THIS rank wrote.
         The call is one `_FolderPipeline` (below): plan a clip -> decode -> upload -> render -> sink, pipelined over units
         of `chunk` x B frames; the launch thread only enqueues, decode of later units and encode of finished ones overlap
-        the GPU work."""
+        the GPU work.
+        metrics=True (needs gt_dir): every non-key frame is measured against gt_dir's frame i, fused (OURS) and DAIN frame,
+        optionally under mask_dir/<clip>/ masks (grayscale at the model size, > 127 -> 1); the per-frame records of all ranks
+        end up in self.metrics and <save_dir>/metrics.json (written by rank 0).  metrics=False changes nothing."""
         if gen_vid:
             # the reference also writes <save_dir>/<clip>.mp4 (evaluator.py:267-269, utils.make_video); not built, and
             # silently ignoring the flag would drop an output the caller asked for
             raise NotImplementedError("evaluate_from_folder: gen_vid is not supported")
+        if metrics and gt_dir is None:
+            raise ValueError("evaluate_from_folder: metrics=True needs gt_dir (the ground-truth frames)")
+        if mask_dir is not None and not metrics:
+            raise ValueError("evaluate_from_folder: mask_dir is a setting of metrics=True")
         if rank is None or world is None:
             import torch.distributed as dist
             rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
@@ -443,8 +469,11 @@ class Evaluator:
         if self._pool is None:
             self._pool = ThreadPoolExecutor(self.io_threads)          # decode + encode workers
             self._finishers = ThreadPoolExecutor(max(4, self.lanes + 2))  # wait for a unit's copy, then fan out its encodes
-        pipe = _FolderPipeline(self, model, rank, world, gt_dir)
+        self.metrics = self.metrics_report = None
+        pipe = _FolderPipeline(self, model, rank, world, gt_dir, metrics=bool(metrics), mask_dir=mask_dir)
         self.timings = pipe.tm
+        if metrics and pipe.native:
+            self._quality_model = model
         try:
             with self._plan_policy(model, pipe.native):
                 for sub in [f for f in sorted(os.listdir(pose_dir)) if os.path.isdir(os.path.join(pose_dir, f))]:
@@ -455,7 +484,10 @@ class Evaluator:
                     else:
                         pipe.run_reference(clip)
                     clip = None
-                return pipe.drain()
+                written = pipe.drain()
+            if metrics:
+                self.metrics, self.metrics_report = pipe.report(save_dir)
+            return written
         finally:
             del pipe                 # the units' tensor views of the shared blocks die with it ...
             _shm_trim()              # ... so the surplus blocks can be unmapped
@@ -464,7 +496,15 @@ class Evaluator:
 class _Clip:
     """What this rank renders of one clip, and where every frame's pieces are while the clip is in the pipeline."""
 
-    def __init__(self, names, dain_list, image_list, pose_list, gtlist, sample_rate, keys, segs, units):
+    def __init__(self, names, dain_list, image_list, pose_list, gtlist, sample_rate, keys, segs, units, sub="", measure=False,
+                 mask_list=None):
+        self.sub = sub                      # the clip's directory name
+        self.measure = measure              # metrics: every generated frame is measured against gtlist[i]
+        self.mask_list = mask_list          # metrics: mask file of every frame index, or None
+        self.records = {}                   # metrics: frame index -> {i, file, DAIN_PSNR, DAIN_SSIM, OURS_PSNR, OURS_SSIM}
+        self.stage_gt = {}                  # metrics: unit -> uint8 [Tc,B,H,W,3] staged GT frames (same block as `stage`)
+        self.stage_mask = {}                # metrics with masks: unit -> uint8 [Tc,B,H,W] staged 0/1 masks
+        self.meas = {}                      # metrics: unit -> (GT frames [Tc*B,3,H,W], masks [Tc*B,H,W] or None) on the device
         self.names = names                  # output file of every frame index
         self.dain_list, self.image_list, self.pose_list, self.gtlist = dain_list, image_list, pose_list, gtlist
         self.sample_rate = sample_rate
@@ -503,14 +543,20 @@ class _FolderPipeline:
     host until its files exist, and the GPU renders faster than PNGs get written.  Every stage can be driven on its own
     (tests/test_driver.py)."""
 
-    def __init__(self, ev, model, rank, world, gt_dir):
+    def __init__(self, ev, model, rank, world, gt_dir, metrics=False, mask_dir=None):
         self.ev, self.model, self.rank, self.world, self.gt_dir = ev, model, rank, world, gt_dir
+        self.metrics, self.mask_dir = metrics, mask_dir
         self.native = hasattr(model, "chain") and hasattr(model, "quantise")
+        if self.native and metrics and not hasattr(model, "quality"):
+            raise RuntimeError("metrics=True: this model has no GPU quality kernel (rib_quality)")
         self.gpu_labels = self.native and ev.label_fn is None and hasattr(model, "rasterise")
-        self.procs = _process_pool(ev.io_threads) if (self.native and ev.io_mode == "process" and ev._shm_fits()) else None
+        per_slot = (1.0 + (1.0 if metrics else 0.0) + (1.0 / 3 if mask_dir is not None else 0.0))
+        self.procs = _process_pool(ev.io_threads) if (self.native and ev.io_mode == "process" and ev._shm_fits(per_slot)) else None
         self.pool, self.finishers = ev._pool, ev._finishers
         self.level = ev.png_compress_level
         self.tm = {"load": 0.0, "rasterise": 0.0, "generate": 0.0, "save": 0.0, "frames": 0, "peak_units_in_flight": 0}
+        if metrics:
+            self.tm["metrics"] = 0.0             # launch thread: enqueueing the measurements (native) or measuring (reference), + the report
         self.t_wall = time.perf_counter()
         self.unit = 0                        # running index of independent units over all clips (the round-robin deal)
         self.inflight = collections.deque()  # sink futures of the units enqueued but not yet written (call-wide window)
@@ -547,6 +593,14 @@ class _FolderPipeline:
         seq_len = (len(image_list) - 1) * sample_rate + 1
         names = [os.path.join(frames_dir, os.path.basename(dain_list[i]))[:-4] + ".png" for i in range(seq_len)]
         gtlist = _list(os.path.join(self.gt_dir, sub), ("jpg", "png")) if self.gt_dir is not None else None
+        mask_list = None
+        if self.metrics:
+            if len(gtlist) < seq_len:
+                raise ValueError("metrics: %s has %d ground-truth frames, the clip has %d" % (os.path.join(self.gt_dir, sub), len(gtlist), seq_len))
+            if self.mask_dir is not None:
+                mask_list = _list(os.path.join(self.mask_dir, sub), ("jpg", "png"))
+                if len(mask_list) < seq_len:
+                    raise ValueError("metrics: %s has %d masks, the clip has %d frames" % (os.path.join(self.mask_dir, sub), len(mask_list), seq_len))
         keys, segs = split_segments(seq_len, sample_rate)
         # this rank's share: a segment is one unit of the deal and brings the key frame it starts from along (that frame is
         # decoded for the chain anyway); a key frame without a segment (the last one) is a unit of its own
@@ -569,7 +623,8 @@ class _FolderPipeline:
                 step = ev.chunk if ev.chunk > 0 else T
                 for c0 in range(0, T, step):
                     units.append((gi, members, c0, min(T, c0 + step)))
-        clip = _Clip(names, dain_list, image_list, pose_list, gtlist, sample_rate, my_keys, segs, units)
+        clip = _Clip(names, dain_list, image_list, pose_list, gtlist, sample_rate, my_keys, segs, units, sub=sub,
+                     measure=self.metrics, mask_list=mask_list)
         self.clips.append(clip)
         return clip
 
@@ -582,6 +637,10 @@ class _FolderPipeline:
             ui, t, b = clip.slot[i]
             clip.stage[ui][t, b].copy_(dain)
             dain = None
+            if clip.measure:                     # the GT frame (and mask) of a measured frame, through the same resize
+                clip.stage_gt[ui][t, b].copy_(ev.load_image_u8(clip.gtlist[i])[0])
+                if clip.mask_list is not None:
+                    clip.stage_mask[ui][t, b].copy_(torch.from_numpy(io_worker.load_mask_u8(clip.mask_list[i], ev.width, ev.height)))
         ref_img = clip.ref_image(i)
         gt = ev.load_image(ref_img)[0] if i % clip.sample_rate == 0 else None
         pose = ev.load_pose(clip.pose_list[i], self.image_size(ref_img))
@@ -595,11 +654,19 @@ class _FolderPipeline:
         from concurrent.futures import Future
         ev = self.ev
         name, off = "", -1
+        extra = ()
         if i in clip.slot:
             ui, t, b = clip.slot[i]
             name, off = clip.stage_blk[ui].name, (t * clip.stage[ui].shape[1] + b) * ev.height * ev.width * 3
+            if clip.measure:                     # GT frame (and mask) of a measured frame: further sections of the same block
+                Tc, Bc = clip.stage[ui].shape[:2]
+                k = t * Bc + b
+                fsz = ev.height * ev.width * 3
+                mask_off = Tc * Bc * fsz * 2 + k * ev.height * ev.width if clip.mask_list is not None else -1
+                extra = (Tc * Bc * fsz + k * fsz, clip.mask_list[i] if clip.mask_list is not None else None, mask_off)
         src = self.procs.submit(io_worker.load_frame_shm, name, off, clip.dain_list[i], clip.ref_image(i), clip.pose_list[i],
-                                i % clip.sample_rate == 0, self.gpu_labels, ev.width, ev.height, ev.resize, ev.skeleton_thres, ev.foot_thres)
+                                i % clip.sample_rate == 0, self.gpu_labels, ev.width, ev.height, ev.resize, ev.skeleton_thres, ev.foot_thres,
+                                *extra)
         out = Future()
 
         def unpack(f):
@@ -627,12 +694,19 @@ class _FolderPipeline:
             ui = clip.opened
             _, members, c0, c1 = clip.units[ui]
             shape = (c1 - c0, len(members), ev.height, ev.width, 3)
+            nb = shape[0] * shape[1] * ev.height * ev.width * 3
+            # metrics: [DAIN frames | GT frames | masks] side by side in the unit's one staging block
+            total = nb * 2 + (nb // 3 if clip.mask_list is not None else 0) if clip.measure else nb
             if self.procs is not None:      # shared with the decode workers and page-locked (back on the free list once uploaded)
-                nb = shape[0] * shape[1] * ev.height * ev.width * 3
-                clip.stage_blk[ui] = _shm_get(nb)               # (size classes of 1 MB: the block may be larger than the unit)
-                clip.stage[ui] = clip.stage_blk[ui].t[:nb].view(*shape)
+                clip.stage_blk[ui] = _shm_get(total)            # (size classes of 1 MB: the block may be larger than the unit)
+                flat = clip.stage_blk[ui].t[:total]
             else:
-                clip.stage[ui] = torch.empty(shape, dtype=torch.uint8, pin_memory=True)
+                flat = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            clip.stage[ui] = flat[:nb].view(*shape)
+            if clip.measure:
+                clip.stage_gt[ui] = flat[nb:2 * nb].view(*shape)
+                if clip.mask_list is not None:
+                    clip.stage_mask[ui] = flat[2 * nb:].view(*shape[:4])
             for b, si in enumerate(members):
                 for t in range(c0, c1):
                     clip.slot[clip.segs[si][1][t]] = (ui, t - c0, b)
@@ -667,9 +741,15 @@ class _FolderPipeline:
             dn = clip.stage[ui].to(g.device, non_blocking=True).permute(0, 1, 4, 2, 3).to(torch.float32)
             dn = ((dn / 255.0 - 0.5) / 0.5).contiguous()                      # [Tc,B,3,H,W]
             gtd = gt.to(g.device) if gt is not None else None
+            if clip.measure:                   # the GT frames normalised as the DAIN frames are; masks 0/1 -> float
+                gtf = clip.stage_gt[ui].to(g.device, non_blocking=True).permute(0, 1, 4, 2, 3).to(torch.float32)
+                gtf = ((gtf / 255.0 - 0.5) / 0.5).reshape(Tc * Bc, 3, ev.height, ev.width).contiguous()
+                mk = (clip.stage_mask[ui].to(g.device, non_blocking=True).to(torch.float32).reshape(Tc * Bc, ev.height, ev.width)
+                      if ui in clip.stage_mask else None)
+                clip.meas[ui] = (gtf, mk)
             ready = torch.cuda.Event()
             ready.record(self.up)
-        for t_ in (lab, dn, gtd):
+        for t_ in (lab, dn, gtd) + tuple(clip.meas.get(ui, ())):
             if t_ is not None:
                 t_.record_stream(st)
         return lab, dn, gtd, ready
@@ -683,6 +763,8 @@ class _FolderPipeline:
             st.wait_event(ready)
             fz = g.chain(gtd if c0 == 0 else clip.prev_of[gi], lab, dn, want_all=False)[2]      # [Tc,B,3,H,W]
             clip.prev_of[gi] = fz[-1]
+            if clip.measure:
+                return self._render_measured(clip, ui, g, st, fz, lab, dn, gtd)
             q = g.quantise(fz.reshape(-1, *fz.shape[2:]))                  # [Tc*B,H,W,3] uint8
             out_blk = _shm_get(q.numel()) if self.procs is not None else None       # shared with the encode workers, page-locked
             pinned = out_blk.t[:q.numel()].view(q.shape) if out_blk is not None else torch.empty(q.shape, dtype=torch.uint8, pin_memory=True)
@@ -690,6 +772,32 @@ class _FolderPipeline:
             done = torch.cuda.Event()
             done.record(st)
         return {"done": done, "pinned": pinned, "out_blk": out_blk, "keep": (fz, q, lab, dn, gtd)}
+
+    def _render_measured(self, clip, ui, g, st, fz, lab, dn, gtd):
+        """render() of a measured unit (on the lane's stream, inside its stream context): the quantised frames and the
+        per-frame metrics - rib_quality of the fused frames and of the DAIN frames against the GT frames - share one device
+        buffer, [uint8 frames | float32 [4, Tc*B]: OURS PSNR, OURS SSIM, DAIN PSNR, DAIN SSIM], and come home in the unit's
+        one device-to-host copy."""
+        t0 = time.perf_counter()
+        n = fz.shape[0] * fz.shape[1]
+        frames = fz.reshape(n, *fz.shape[2:])
+        nq = frames.numel()                                              # uint8 bytes of the quantised frames
+        off = (nq + 255) // 256 * 256
+        total = off + 4 * n * 4
+        buf = torch.empty(total, dtype=torch.uint8, device=g.device)
+        q = g.quantise(frames, out=buf[:nq].view(n, frames.shape[2], frames.shape[3], frames.shape[1]))
+        vals = buf[off:].view(torch.float32).view(4, n)
+        gtf, mk = clip.meas.pop(ui)
+        g.quality(frames, gtf, mk, out=vals[0:2])
+        g.quality(dn.reshape(n, *dn.shape[2:]), gtf, mk, out=vals[2:4])
+        out_blk = _shm_get(total) if self.procs is not None else None
+        flat = out_blk.t[:total] if out_blk is not None else torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        flat.copy_(buf, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(st)
+        self.tm["metrics"] += time.perf_counter() - t0
+        return {"done": done, "pinned": flat[:nq].view(q.shape), "out_blk": out_blk, "keep": (fz, q, lab, dn, gtd, buf, gtf, mk),
+                "qual": flat[off:].view(torch.float32).view(4, n)}
 
     # ---- stage 4: sink ---------------------------------------------------------------------------------------------------
     def sink(self, clip, ui, r, t_loaded, t_enq):
@@ -701,8 +809,12 @@ class _FolderPipeline:
         # per unit: inputs decoded, launches enqueued, results on the host, files written (seconds since the call began)
         mark = [round(t_loaded, 4), round(t_enq, 4), round(time.perf_counter() - self.t_wall, 4)]
         self.tm.setdefault("timeline", []).append(mark)
+        if r.get("qual") is not None:           # the unit's per-frame metrics rode in the same copy
+            self.record(clip, out_frames, r.pop("qual").numpy().astype(np.float64))
         in_blk = clip.stage_blk.pop(ui, None)
-        clip.stage.pop(ui, None)                # (the view of the block goes before the block does)
+        clip.stage.pop(ui, None)                # (the views of the block go before the block does)
+        clip.stage_gt.pop(ui, None)
+        clip.stage_mask.pop(ui, None)
         if in_blk is not None:
             _shm_put(in_blk)
         out_blk = r["out_blk"]
@@ -774,8 +886,62 @@ class _FolderPipeline:
             tm["generate"] += time.perf_counter() - t2
             for t, i in enumerate(frames):
                 clip.futs[i] = self.pool.submit(self.save_host, outs[t], clip.names[i])
+            if clip.measure:                     # the torch statement of the metric (metrics.py), frame by frame
+                t3 = time.perf_counter()
+                vals = np.zeros((4, len(frames)))
+                for t, i in enumerate(frames):
+                    gt_i = ev.load_image(clip.gtlist[i])[0].unsqueeze(0)
+                    mk = (torch.from_numpy(io_worker.load_mask_u8(clip.mask_list[i], ev.width, ev.height)).float().unsqueeze(0)
+                          if clip.mask_list is not None else None)
+                    for row, x in ((0, outs[t]), (2, dn[t])):
+                        p_, s_ = _metrics.psnr_ssim(x.detach().cpu().float(), gt_i, mk)
+                        vals[row, t], vals[row + 1, t] = float(p_[0]), float(s_[0])
+                self.record(clip, frames, vals)
+                tm["metrics"] += time.perf_counter() - t3
         tm["units"] = tm.get("units", 0)
         tm["frames"] += len(clip.futs)
+
+    # ---- metrics ---------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def record(clip, frames, vals):
+        """vals [4, len(frames)]: OURS PSNR, OURS SSIM, DAIN PSNR, DAIN SSIM of each frame -> clip.records."""
+        for j, i in enumerate(frames):
+            clip.records[i] = {"i": int(i), "file": os.path.basename(clip.names[i]),
+                               "DAIN_PSNR": float(vals[2, j]), "DAIN_SSIM": float(vals[3, j]),
+                               "OURS_PSNR": float(vals[0, j]), "OURS_SSIM": float(vals[1, j])}
+
+    def report(self, save_dir):
+        """After drain(): the per-frame records of every rank (all_gather_object under a process group; rank 0 writes
+        <save_dir>/metrics.json) -> (records [{clip, i, file, 4 values}] in clip and frame order, the report dict)."""
+        import json
+        t0 = time.perf_counter()
+        mine = [dict(r, clip=clip.sub) for clip in self.clips for _, r in sorted(clip.records.items())]
+        rows = [mine]
+        import torch.distributed as dist
+        grouped = self.world > 1 and dist.is_available() and dist.is_initialized()
+        if grouped:
+            rows = [None] * dist.get_world_size()
+            dist.all_gather_object(rows, mine)
+        order = {c.sub: k for k, c in enumerate(self.clips)}
+        recs = sorted((r for part in rows for r in part), key=lambda r: (order.get(r["clip"], len(order)), r["clip"], r["i"]))
+        clips = {}
+        for r in recs:
+            clips.setdefault(r["clip"], []).append({k: v for k, v in r.items() if k != "clip"})
+        rep = {"protocol": dict(_metrics.PROTOCOL,
+                                measured_frames="every non-key frame (i % sample_rate != 0): its fused frame (OURS) and its DAIN "
+                                                "frame (DAIN) against gt_dir's frame i; at sample_rate 2 the reference's rule "
+                                                "(PGNR/models/evaluator.py:116)",
+                                mask=("mask_dir/<clip>/ grayscale at the model size, value > 127 -> 1" if self.mask_dir is not None else None),
+                                clips_reported="every clip (the reference returns only the last clip's dict: it is overwritten per clip)"),
+               "clips": {c: dict(_metrics.mean_record(pf), frames=len(pf), per_frame=pf) for c, pf in clips.items()},
+               "overall": dict(_metrics.mean_record(recs), frames=len(recs))}
+        if self.rank == 0 or not grouped:
+            name = "metrics.json" if (self.world == 1 or grouped) else "metrics_rank%d.json" % self.rank
+            os.makedirs(save_dir, exist_ok=True)
+            with open(os.path.join(save_dir, name), "w") as f:
+                json.dump(rep, f, indent=1)
+        self.tm["metrics"] = self.tm.get("metrics", 0.0) + time.perf_counter() - t0
+        return recs, rep
 
     def drain(self):
         """Waits for every file of the call, in frame order as the reference writes them; returns the names this rank wrote."""

@@ -361,12 +361,44 @@ class Generator:
         _native.check(self._h, self._lib.rib_blend(self._h, B, Cc, H, W, _ptr(img), _ptr(mask), _ptr(dain), _ptr(out), self._stream()))
         return out
 
-    def quantise(self, img):
+    def quantise(self, img, out=None):
+        """out: optional contiguous uint8 [B,H,W,C] destination on the device (e.g. a view of a larger buffer)."""
         img = img.to(self.device, torch.float32).contiguous()
         B, Cc, H, W = img.shape
-        out = torch.empty((B, H, W, Cc), dtype=torch.uint8, device=self.device)
+        if out is None:
+            out = torch.empty((B, H, W, Cc), dtype=torch.uint8, device=self.device)
+        assert out.shape == (B, H, W, Cc) and out.dtype == torch.uint8 and out.is_contiguous() and out.device == self.device
         _native.check(self._h, self._lib.rib_quantise(self._h, B, Cc, H, W, _ptr(img), _ptr(out), self._stream()))
         return out
+
+    def quality(self, pred, target, mask=None, out=None):
+        """Masked PSNR / SSIM of B frames against ground truth (rib_quality; metrics.py states the metric):
+        pred, target [B,3,H,W] in [-1,1], mask [B,H,W] or None -> (psnr[B], ssim[B]) float32 device tensors, enqueued on
+        the current stream.  out: optional float32 [2,B] device destination (row 0 PSNR, row 1 SSIM)."""
+        pred = self._prep(pred, 3, "pred")
+        B, Cc, H, W = pred.shape
+        target = self._prep(target, 3, "target", (B, H, W))
+        if mask is not None:
+            if tuple(mask.shape) != (B, H, W):
+                raise ValueError("mask must be [B,H,W] = %s, got %s" % ((B, H, W), tuple(mask.shape)))
+            mask = mask.to(self.device, torch.float32).contiguous()
+        n = self._lib.rib_quality_workspace_bytes(self._h, B, H, W)
+        if n == 0:
+            from .metrics import downsample_factor
+            f = downsample_factor(H, W)
+            raise ValueError("SSIM: the frame is %dx%d after %dx downsampling, smaller than the 11x11 window" % (H // f, W // f, f))
+        cache = self.__dict__.setdefault("_quality_ws", {})
+        ws = cache.get((B, H, W))
+        if ws is None:
+            ws = cache[(B, H, W)] = torch.empty(n, dtype=torch.uint8, device=self.device)
+        if out is None:
+            out = torch.empty((2, B), dtype=torch.float32, device=self.device)
+        assert out.shape == (2, B) and out.dtype == torch.float32 and out.is_contiguous() and out.device == self.device
+        with torch.cuda.device(self.device):
+            _native.check(self._h, self._lib.rib_quality(
+                self._h, B, Cc, H, W, _ptr(pred), _ptr(target), _ptr(mask), _ptr(out[0]), _ptr(out[1]),
+                _ptr(ws), ws.numel(), self._stream()))
+        return out[0], out[1]
 
     def warp(self, img, flow):
         img = img.to(self.device, torch.float32).contiguous(); flow = flow.to(self.device, torch.float32).contiguous()

@@ -11,6 +11,10 @@ Multi-GPU (new; the reference is single-device): `--gpus N` starts N ranks, one 
 torch.distributed.run yourself).  Rank 0 reads and folds the checkpoint, the folded blob reaches the other ranks in
 ONE RCCL broadcast, and the independent segments between key frames (PGNR/models/evaluator.py:240-244) of all clips
 (:169-171) are dealt round-robin to the ranks; every rank writes its own frames into the same output tree.
+
+Ground-truth metrics (new; the reference measures only in evaluate_from_dataset): `--gt-dir DIR --metrics [--mask-dir DIR]`
+measures every generated frame and its DAIN frame against DIR/<clip>/ (PSNR / SSIM of Evaluator.compute_metrics) and writes
+<save-dir>/Generated_frames/metrics.json.
 """
 import argparse
 import os
@@ -66,13 +70,19 @@ def summary_line(evaluator, rank=0, world=1):
     from render_in_between_amd.evaluator import cpu_budget
     tm = evaluator.timings
     wall = max(tm.get("wall", 0.0), 1e-9)
-    return ("[rank %d/%d] %d frames in %.2f s = %.1f frames/s | load %.2f s, rasterise %.2f s, generate %.2f s, save tail %.2f s | "
+    line = ("[rank %d/%d] %d frames in %.2f s = %.1f frames/s | load %.2f s, rasterise %.2f s, generate %.2f s, save tail %.2f s | "
             "%d units, <= %d in flight | %d file workers (%s), CPU budget %d cores | PNG level %s, batch %d, %s plans"
             % (rank, world, tm.get("frames", 0), wall, tm.get("frames", 0) / wall, tm.get("load", 0.0), tm.get("rasterise", 0.0),
                tm.get("generate", 0.0), tm.get("save", 0.0), tm.get("units", 0), tm.get("peak_units_in_flight", 0),
                evaluator.io_threads, evaluator.io_mode, cpu_budget(),
                "reference (zlib 6)" if evaluator.png_compress_level is None else str(evaluator.png_compress_level),
                evaluator.batch or evaluator.default_batch(), "batch-invariant" if evaluator.reproducible else "per-batch"))
+    rep = getattr(evaluator, "metrics_report", None)
+    if "metrics" in tm and rep is not None:
+        o = rep["overall"]
+        line += (" | metrics over %d frames: DAIN PSNR %.4f SSIM %.6f, OURS PSNR %.4f SSIM %.6f, metric time %.2f s"
+                 % (o["frames"], o["DAIN_PSNR"], o["DAIN_SSIM"], o["OURS_PSNR"], o["OURS_SSIM"], tm["metrics"]))
+    return line
 
 
 def main(opts):
@@ -99,7 +109,8 @@ def main(opts):
     dain_dir = os.path.join(opts.input_dir, "DAIN")
     pose_dir = os.path.join(opts.input_dir, "Predict_motion")
     save_dir = os.path.join(opts.save_dir, "Generated_frames")
-    written = evaluator.evaluate_from_folder(net_G, train_dir, dain_dir, pose_dir, save_dir, gt_dir=None, gen_vid=False)
+    written = evaluator.evaluate_from_folder(net_G, train_dir, dain_dir, pose_dir, save_dir, gt_dir=opts.gt_dir, gen_vid=False,
+                                             metrics=opts.metrics, mask_dir=opts.mask_dir)
     print(summary_line(evaluator, rank, world))
     if world > 1:
         print("[rank {}/{}] wrote {} frames".format(rank, world, len(written)))
@@ -107,7 +118,7 @@ def main(opts):
         torch.distributed.destroy_process_group()
 
 
-if __name__ == "__main__":
+def build_parser():
     parser = argparse.ArgumentParser(description="pose-guided neural rendering inference (MI355X)")
     parser.add_argument("--config", type=str, default=os.path.join(_HERE, "configs", "HSM.yaml"), help="Path to the config file.")
     parser.add_argument("--save-dir", type=str, default="../example", help="outputs path")
@@ -128,7 +139,28 @@ if __name__ == "__main__":
                         help="(default) every group size follows the kernel choices of the full group, so a frame's bytes do not depend "
                              "on segment grouping, on --gpus N or on --batch 1 vs N-rank shares; --no-reproducible lets ragged groups "
                              "run their own measured tables (frames then agree to ~1e-5, at most one uint8 step)")
-    opts = parser.parse_args()
+    parser.add_argument("--gt-dir", type=str, default=None,
+                        help="ground-truth frames, <gt-dir>/<clip>/*.png at the high frame rate (the reference's commented-out flag, "
+                             "PGNR/inference.py:34): key frames and chain starts come from it, and the keypoints scale with its size")
+    parser.add_argument("--metrics", action="store_true",
+                        help="measure every generated frame and its DAIN frame against --gt-dir (PSNR / SSIM of compute_metrics, on the "
+                             "GPU); writes <save-dir>/Generated_frames/metrics.json (not in the reference's folder driver)")
+    parser.add_argument("--mask-dir", type=str, default=None,
+                        help="with --metrics: <mask-dir>/<clip>/ grayscale masks at the model size (value > 127 = measured pixel)")
+    return parser
+
+
+def parse_args(argv=None):
+    parser = build_parser()
+    opts = parser.parse_args(argv)
     if opts.png_level != "reference" and opts.png_level not in [str(i) for i in range(10)]:
         parser.error("--png-level must be 'reference' or a zlib level 0-9")
-    main(opts)
+    if opts.metrics and opts.gt_dir is None:
+        parser.error("--metrics needs --gt-dir (the ground-truth frames)")
+    if opts.mask_dir is not None and not opts.metrics:
+        parser.error("--mask-dir is a setting of --metrics")
+    return opts
+
+
+if __name__ == "__main__":
+    main(parse_args())

@@ -98,13 +98,32 @@ def _attach(name):
     return shm
 
 
-def load_frame_shm(shm_name, offset, dain_path, ref_img_path, pose_path, is_key, want_tables, width, height, resize, thres1, thres2):
+def load_mask_u8(path, width, height):
+    """Ground-truth mask of a measured frame (Evaluator metrics): a grayscale image at the model size, value > 127 -> 1, else 0
+    (uint8 HW).  Any other size is an error: the mask is not resized."""
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.size != (width, height):
+            raise ValueError("mask %s is %dx%d, the frames are %dx%d (masks are not resized)" % (path, im.size[0], im.size[1], width, height))
+        return (np.asarray(im.convert("L"), dtype=np.uint8) > 127).astype(np.uint8)
+
+
+def load_frame_shm(shm_name, offset, dain_path, ref_img_path, pose_path, is_key, want_tables, width, height, resize, thres1, thres2,
+                   gt_offset=-1, mask_path=None, mask_offset=-1):
     """load_frame with the DAIN frame written to bytes [offset, offset + H*W*3) of a shared block (offset < 0: not wanted,
-    the frame is a key frame that passes through); returns (None, key frame uint8 HWC or None, tables)."""
+    the frame is a key frame that passes through); returns (None, key frame uint8 HWC or None, tables).
+    A measured frame (Evaluator metrics) also has its ground-truth frame - ref_img_path, which is gt_dir's frame i - decoded
+    through the same resize to bytes [gt_offset, +H*W*3), and its mask (load_mask_u8) to [mask_offset, +H*W)."""
     if offset >= 0:
         dain, _ = decode_resized_u8(dain_path, width, height, resize)
         dst = np.ndarray((height, width, 3), np.uint8, buffer=_attach(shm_name).buf, offset=offset)
         dst[...] = dain
+    if gt_offset >= 0:
+        dst = np.ndarray((height, width, 3), np.uint8, buffer=_attach(shm_name).buf, offset=gt_offset)
+        dst[...] = decode_resized_u8(ref_img_path, width, height, resize)[0]
+    if mask_offset >= 0:
+        dst = np.ndarray((height, width), np.uint8, buffer=_attach(shm_name).buf, offset=mask_offset)
+        dst[...] = load_mask_u8(mask_path, width, height)
     gt = decode_resized_u8(ref_img_path, width, height, resize)[0] if is_key else None
     lm, conf = scaled_pose(pose_path, image_size(ref_img_path), width, height)
     pose = rasterise.frame_tables(lm, conf, height, width, thres1, thres2) if want_tables else (lm, conf)
