@@ -169,6 +169,21 @@ int rib_quantise(rib_handle* h, int B, int C, int H, int W, const float* img_nch
 size_t rib_quality_workspace_bytes(rib_handle* h, int B, int H, int W);
 int rib_quality(rib_handle* h, int B, int C, int H, int W, const float* pred, const float* target,
                 const float* mask, float* psnr, float* ssim, void* workspace, size_t workspace_bytes, void* hip_stream);
+/* ---- frame resize of the folder driver (PGNR/models/evaluator.py:18-26,219-221) ----
+ * The reference resizes every frame to the model size with A.Resize(interpolation=cv2.INTER_CUBIC) on the host.  This is
+ * OpenCV's 8-bit INTER_CUBIC as resize.py restates it, for N frames of one source size: src uint8 NHWC [N,H0,W0,3] (C = 3
+ * is part of the entry) -> H x W.  ix, cx [W,4] and iy, cy [H,4] int32 device arrays: the clamped tap indices and the
+ * 11-bit fixed-point coefficients of each output column / row, made on the host (resize._cubic_taps; the float32 weight
+ * arithmetic is not restated on the device).  v = sum_j cy[j] * (sum_i cx[i] * src[iy[j]][ix[i]]) in int32, then
+ * (v + 2^21) >> 22 saturated to 0..255: integer only, so bit-exact to the host function whatever the summation order.
+ * Outputs, either may be NULL but not both: out_u8_nhwc [N,H,W,3] uint8, and out_f32_nchw [N,3,H,W] fp32 holding
+ * ToTensor + Normalize(0.5, 0.5) of it, (u8 / 255 - 0.5) / 0.5, bit-identical to that expression evaluated by torch on
+ * the device (a division by a host scalar is a multiplication by its fp32 reciprocal there).  H0 == H and W0 == W is
+ * allowed (a copy / the normalisation alone).  Indices outside the source are clamped.  One launch, no workspace, no
+ * atomics: a frame's bytes do not depend on N.  Sizes < 1, N > 65535, a NULL input or both outputs NULL: RIB_ERR_INVALID. */
+int rib_resize_cubic(rib_handle* h, int N, int H0, int W0, int H, int W, const uint8_t* src_u8_nhwc,
+                        const int32_t* ix, const int32_t* cx, const int32_t* iy, const int32_t* cy,
+                        uint8_t* out_u8_nhwc, float* out_f32_nchw, void* hip_stream);
 /* ---- label-map rasterisation --------------------------------------------------
  * Replaces, per frame, Dataset._generate_skeleton + _generate_pose_map
  * (PGNR/datasets/HSM_auto_dataset.py:205-251; drawing rules PGNR/utils/keypoint2img.py:36-88,132-147)

@@ -12,6 +12,7 @@
 #include "kernels.hip.h"
 #include "raster.hip.h"
 #include "quality.hip.h"
+#include "resize.hip.h"
 #include <hip/hip_ext.h>
 #include "../../include/rib.h"
 
@@ -2729,6 +2730,24 @@ int rib_quantise(rib_handle* h, int B, int C, int H, int W, const float* img, ui
   const size_t total = (size_t)B * C * H * W;
   const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 4096);
   RIB_KLAUNCH(k_quantise, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream), img, out, C, H * W, total);
+  HIP_TRY(h, hipGetLastError());
+  return RIB_OK;
+}
+
+int rib_resize_cubic(rib_handle* h, int N, int H0, int W0, int H, int W, const uint8_t* src, const int32_t* ix, const int32_t* cx,
+                        const int32_t* iy, const int32_t* cy, uint8_t* out_u8, float* out_f32, void* hip_stream) {
+  if (!h) return RIB_ERR_INVALID;
+  if (!src || !ix || !cx || !iy || !cy) return fail(h, RIB_ERR_INVALID, "rib_resize_cubic: null pointer");
+  if (!out_u8 && !out_f32) return fail(h, RIB_ERR_INVALID, "rib_resize_cubic: both outputs are null");
+  if (N < 1 || H0 < 1 || W0 < 1 || H < 1 || W < 1 || N > 65535)
+    return fail(h, RIB_ERR_INVALID, fmt("rib_resize_cubic: N=%d H0=%d W0=%d H=%d W=%d: sizes must be positive (N <= 65535)", N, H0, W0, H, W));
+  if ((size_t)H0 * W0 * 3 > (size_t)INT32_MAX || (size_t)H * W * 3 > (size_t)INT32_MAX)
+    return fail(h, RIB_ERR_INVALID, "rib_resize_cubic: a frame must be smaller than 2 GiB");
+  if (h->device >= 0) HIP_TRY(h, hipSetDevice(h->device));
+  const int tilesX = (W * 3 + RSZ_TW - 1) / RSZ_TW, tilesY = (H + RSZ_TH - 1) / RSZ_TH;
+  RIB_KLAUNCH(k_resize_cubic_u8, dim3(tilesX * tilesY, N), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream), src,
+              reinterpret_cast<const int4*>(ix), reinterpret_cast<const int4*>(cx), reinterpret_cast<const int4*>(iy),
+              reinterpret_cast<const int4*>(cy), out_u8, out_f32, H0, W0, H, W, tilesX);
   HIP_TRY(h, hipGetLastError());
   return RIB_OK;
 }

@@ -252,13 +252,61 @@ def cpu_budget():
     return n
 
 
+def _shm_free_bytes():
+    """Bytes /dev/shm can still hand out, plus the staging blocks this process already holds (they are reused, not allocated again)."""
+    try:
+        st = os.statvfs("/dev/shm")
+        free = st.f_bavail * st.f_frsize
+    except OSError:
+        free = 0
+    return free + sum(b.nbytes for b in _SHM_ALL)
+
+
+def shm_windows_bytes(unit_bytes):
+    """Shared staging memory the pipeline's windows need when one unit stages `unit_bytes`."""
+    return (DECODE_AHEAD + MAX_UNITS_IN_FLIGHT + 4) * int(unit_bytes)
+
+
+def plan_gpu_resize(dain_sizes, gt_sizes, model_size, slots_per_unit, mask=False, shm_free=None):
+    """Which frame lists of a clip does Evaluator(resize_on="gpu") stage at their SOURCE size for the GPU resize
+    (rib_resize_cubic), and which fall back to the host resize?  A pure function of sizes and budgets.
+    dain_sizes / gt_sizes: [(w0, h0)] header sizes of the clip's DAIN frames / measured ground-truth frames (gt_sizes None: no
+    metrics); model_size (W, H); slots_per_unit: frames of one pipeline unit (chunk x batch); mask: a mask is staged per slot
+    too; shm_free: bytes the shared staging blocks may take (None: staging is not in shared memory, no budget applies).
+    -> ({"DAIN": (w0, h0) or None, "GT": (w0, h0) or None}, [(list name, reason)]): the source size of each list that goes to
+    the GPU (None: host resize) and one reason per list that was asked for and falls back.
+    Rules: the sizes inside a list must be uniform (the two lists may differ from each other); then the unit's staging block
+    at the real per-slot bytes must fit the pipeline's windows in shm_free - if it does not, the GT list goes back to the model
+    size first, then the DAIN list."""
+    W, H = model_size
+    src, why = {"DAIN": None, "GT": None}, []
+    for name, sizes in (("DAIN", dain_sizes), ("GT", gt_sizes)):
+        if sizes is None:
+            continue
+        kinds = sorted(set(tuple(s_) for s_ in sizes))
+        if len(kinds) == 1:
+            src[name] = kinds[0]
+        elif kinds:
+            why.append((name, "mixed frame sizes (%s)" % ", ".join("%dx%d" % k for k in kinds[:4])))
+    if shm_free is not None:
+        def need():
+            per_slot = sum((s_[0] * s_[1] if s_ is not None else W * H) * 3 for n_, s_ in src.items() if n_ == "DAIN" or gt_sizes is not None)
+            return shm_windows_bytes(slots_per_unit * (per_slot + (W * H if mask else 0)))
+        for name in ("GT", "DAIN"):
+            if src[name] is not None and need() > shm_free:
+                why.append((name, "the staging windows at %dx%d need %.0f MB of shared memory, %.0f MB are free"
+                            % (src[name][0], src[name][1], need() / 1e6, shm_free / 1e6)))
+                src[name] = None
+    return src, why
+
+
 def _list(d, exts):
     return [os.path.join(d, f) for f in sorted(os.listdir(d)) if f.endswith(exts)]
 
 
 class Evaluator:
     def __init__(self, cfg, lanes=2, label_fn=None, png_compress_level=None, resize="cv2", batch=None, chunk=4, io_threads=None,
-                 io_mode="process", reproducible=True):
+                 io_mode="process", reproducible=True, resize_on="host"):
         """batch: independent segments of equal length rendered as ONE chain of that batch size (None: by frame size,
         `default_batch`; 1: every segment on its own, the round-1..3 behaviour).
         reproducible (default True): every chain of the call - full groups, the ragged last group of a clip, a rank's
@@ -279,9 +327,19 @@ class Evaluator:
         label_fn(frames, H, W) -> [T, 22, H, W]: rasteriser override for models that only speak the
         reference's call protocol (the tests pass the CPU oracle); by default the model's GPU
         rasteriser is used and a model without one is an error (no host fallback).
-        resize: "cv2" = OpenCV INTER_CUBIC restated (resize.py; what the reference's A.Resize computes), "pil" = PIL BICUBIC."""
+        resize: "cv2" = OpenCV INTER_CUBIC restated (resize.py; what the reference's A.Resize computes), "pil" = PIL BICUBIC.
+        resize_on: "host" (default): the file workers resize every frame (resize.py); "gpu": the DAIN frames - and under
+        metrics=True the ground-truth frames - are decoded at their own size and resized by the model's HIP kernel
+        (Generator.resize_u8 / rib_resize_cubic, bit-exact to the host function, so the files are the same); needs
+        resize="cv2" and a native model.  Key frames are resized on the host either way.  A clip whose list has mixed sizes,
+        or whose source-size staging does not fit /dev/shm, falls back to the host resize for that list and says so."""
         if resize not in ("cv2", "pil"):
             raise ValueError("resize must be 'cv2' or 'pil'")
+        if resize_on not in ("host", "gpu"):
+            raise ValueError("resize_on must be 'host' or 'gpu'")
+        if resize_on == "gpu" and resize != "cv2":
+            raise ValueError("resize_on='gpu' needs resize='cv2' (PIL's BICUBIC is not on the GPU)")
+        self.resize_on = resize_on
         if io_mode not in ("process", "thread"):
             raise ValueError("io_mode must be 'process' or 'thread'")
         self.io_mode = io_mode
@@ -316,13 +374,8 @@ class Evaluator:
         and a write beyond it is a bus error, not an exception: the file-side work then stays on threads, with a warning.)
         frames_per_slot: staged frames per output frame (metrics: DAIN + GT frame + mask)."""
         unit = int(max(1, self.chunk) * (self.batch or self.default_batch()) * self.height * self.width * 3 * frames_per_slot)
-        need = (DECODE_AHEAD + MAX_UNITS_IN_FLIGHT + 4) * unit
-        try:
-            st = os.statvfs("/dev/shm")
-            free = st.f_bavail * st.f_frsize
-        except OSError:
-            free = 0
-        free += sum(b.nbytes for b in _SHM_ALL)             # blocks this process already holds are reused, not allocated again
+        need = shm_windows_bytes(unit)
+        free = _shm_free_bytes()
         if free < need:
             import warnings
             warnings.warn("Evaluator: /dev/shm has %.0f MB free, the shared staging blocks of the worker processes need %.0f MB: "
@@ -518,6 +571,8 @@ class _Clip:
         self.futs = {}                      # frame index -> future of its file name, or (unit future, position in the unit)
         self.opened = 0                     # units whose staging block and decode tasks exist
         self.prev_of = {}                   # group -> last fused frames [B,3,H,W] on its lane
+        # resize_on="gpu": (w0, h0) at which the DAIN / GT frames are staged for the GPU resize; None: resized on the host
+        self.src_dain = self.src_gt = None
 
     def ref_image(self, i):
         """evaluator.py:209-212: the "gt" image of frame i is gtlist[i] when a gt_dir is given, else the key frame of its
@@ -534,7 +589,7 @@ class _FolderPipeline:
 
         plan_clip   directory listing -> this rank's key frames, segments, groups and units
         decode      open_units / submit_load: staging block per unit, one decode task per frame (threads or worker processes)
-        upload      DAIN frames + label rasterisation + ToTensor/Normalize on the upload stream
+        upload      DAIN frames + label rasterisation + ToTensor/Normalize (resize_on="gpu": + the cubic resize) on the upload stream
         render      the unit's batched chain, the quantiser and ONE device-to-host copy on the lane's stream
         sink        when the copy has landed: PNG encodes, blocks back to the free lists
 
@@ -549,6 +604,8 @@ class _FolderPipeline:
         self.native = hasattr(model, "chain") and hasattr(model, "quantise")
         if self.native and metrics and not hasattr(model, "quality"):
             raise RuntimeError("metrics=True: this model has no GPU quality kernel (rib_quality)")
+        if ev.resize_on == "gpu" and not (self.native and hasattr(model, "resize_u8")):
+            raise RuntimeError("resize_on='gpu': this model has no GPU resize kernel (rib_resize_cubic)")
         self.gpu_labels = self.native and ev.label_fn is None and hasattr(model, "rasterise")
         per_slot = (1.0 + (1.0 if metrics else 0.0) + (1.0 / 3 if mask_dir is not None else 0.0))
         self.procs = _process_pool(ev.io_threads) if (self.native and ev.io_mode == "process" and ev._shm_fits(per_slot)) else None
@@ -625,6 +682,17 @@ class _FolderPipeline:
                     units.append((gi, members, c0, min(T, c0 + step)))
         clip = _Clip(names, dain_list, image_list, pose_list, gtlist, sample_rate, my_keys, segs, units, sub=sub,
                      measure=self.metrics, mask_list=mask_list)
+        if ev.resize_on == "gpu" and units:
+            # the header sizes of the frames this rank stages (cached: the keypoint scaling reads the same headers)
+            staged = [i for _, frames in segs for i in frames]
+            slots = max((c1 - c0) * len(members) for _, members, c0, c1 in units)
+            src, why = plan_gpu_resize([self.image_size(dain_list[i]) for i in staged],
+                                       [self.image_size(gtlist[i]) for i in staged] if self.metrics else None,
+                                       (ev.width, ev.height), slots, mask=mask_list is not None,
+                                       shm_free=_shm_free_bytes() if self.procs is not None else None)
+            clip.src_dain, clip.src_gt = src["DAIN"], src["GT"]
+            for name, reason in why:
+                print("resize_on='gpu': clip {}: the {} list falls back to the host resize: {}".format(sub, name, reason))
         self.clips.append(clip)
         return clip
 
@@ -632,15 +700,21 @@ class _FolderPipeline:
     def decode_here(self, clip, i):
         """Pre-load of frame i on a pool thread (evaluator.py:205-235)."""
         ev = self.ev
-        dain, _ = (ev.load_image_u8 if self.native else ev.load_image)(clip.dain_list[i])
+        staged_raw = i in clip.slot and clip.src_dain is not None
+        dain = None if staged_raw else (ev.load_image_u8 if self.native else ev.load_image)(clip.dain_list[i])[0]
         if i in clip.slot:
             ui, t, b = clip.slot[i]
-            clip.stage[ui][t, b].copy_(dain)
+            if staged_raw:                       # resize_on="gpu": at the file's own size, straight into the slot
+                io_worker.decode_raw_into(clip.stage[ui][t, b].numpy(), 0, clip.dain_list[i], clip.src_dain)
+            else:
+                clip.stage[ui][t, b].copy_(dain)
             dain = None
-            if clip.measure:                     # the GT frame (and mask) of a measured frame, through the same resize
+            if clip.measure and clip.src_gt is not None:
+                io_worker.decode_raw_into(clip.stage_gt[ui][t, b].numpy(), 0, clip.gtlist[i], clip.src_gt)
+            elif clip.measure:                   # the GT frame (and mask) of a measured frame, through the same resize
                 clip.stage_gt[ui][t, b].copy_(ev.load_image_u8(clip.gtlist[i])[0])
-                if clip.mask_list is not None:
-                    clip.stage_mask[ui][t, b].copy_(torch.from_numpy(io_worker.load_mask_u8(clip.mask_list[i], ev.width, ev.height)))
+            if clip.measure and clip.mask_list is not None:
+                clip.stage_mask[ui][t, b].copy_(torch.from_numpy(io_worker.load_mask_u8(clip.mask_list[i], ev.width, ev.height)))
         ref_img = clip.ref_image(i)
         gt = ev.load_image(ref_img)[0] if i % clip.sample_rate == 0 else None
         pose = ev.load_pose(clip.pose_list[i], self.image_size(ref_img))
@@ -657,13 +731,16 @@ class _FolderPipeline:
         extra = ()
         if i in clip.slot:
             ui, t, b = clip.slot[i]
-            name, off = clip.stage_blk[ui].name, (t * clip.stage[ui].shape[1] + b) * ev.height * ev.width * 3
+            Tc, Bc = clip.stage[ui].shape[:2]
+            k = t * Bc + b
+            fsz = clip.stage[ui][0, 0].numel()   # a slot of the DAIN section: the model size, or the source size (resize_on="gpu")
+            name, off = clip.stage_blk[ui].name, k * fsz
             if clip.measure:                     # GT frame (and mask) of a measured frame: further sections of the same block
-                Tc, Bc = clip.stage[ui].shape[:2]
-                k = t * Bc + b
-                fsz = ev.height * ev.width * 3
-                mask_off = Tc * Bc * fsz * 2 + k * ev.height * ev.width if clip.mask_list is not None else -1
-                extra = (Tc * Bc * fsz + k * fsz, clip.mask_list[i] if clip.mask_list is not None else None, mask_off)
+                gsz = clip.stage_gt[ui][0, 0].numel()
+                mask_off = Tc * Bc * (fsz + gsz) + k * ev.height * ev.width if clip.mask_list is not None else -1
+                extra = (Tc * Bc * fsz + k * gsz, clip.mask_list[i] if clip.mask_list is not None else None, mask_off)
+            if clip.src_dain is not None or clip.src_gt is not None:
+                extra = (extra or (-1, None, -1)) + (clip.src_dain, clip.src_gt if clip.measure else None)
         src = self.procs.submit(io_worker.load_frame_shm, name, off, clip.dain_list[i], clip.ref_image(i), clip.pose_list[i],
                                 i % clip.sample_rate == 0, self.gpu_labels, ev.width, ev.height, ev.resize, ev.skeleton_thres, ev.foot_thres,
                                 *extra)
@@ -693,10 +770,13 @@ class _FolderPipeline:
         while clip.opened <= min(upto, len(clip.units) - 1):
             ui = clip.opened
             _, members, c0, c1 = clip.units[ui]
-            shape = (c1 - c0, len(members), ev.height, ev.width, 3)
-            nb = shape[0] * shape[1] * ev.height * ev.width * 3
+            # a section is staged at the model size, or (resize_on="gpu") at the list's source size for the GPU resize
+            (wd, hd), (wg, hg) = clip.src_dain or (ev.width, ev.height), clip.src_gt or (ev.width, ev.height)
+            shape, shape_gt = (c1 - c0, len(members), hd, wd, 3), (c1 - c0, len(members), hg, wg, 3)
+            shape_mask = (c1 - c0, len(members), ev.height, ev.width)
+            nb, nb_gt, nb_mask = (int(np.prod(s_)) for s_ in (shape, shape_gt, shape_mask))
             # metrics: [DAIN frames | GT frames | masks] side by side in the unit's one staging block
-            total = nb * 2 + (nb // 3 if clip.mask_list is not None else 0) if clip.measure else nb
+            total = nb + nb_gt + (nb_mask if clip.mask_list is not None else 0) if clip.measure else nb
             if self.procs is not None:      # shared with the decode workers and page-locked (back on the free list once uploaded)
                 clip.stage_blk[ui] = _shm_get(total)            # (size classes of 1 MB: the block may be larger than the unit)
                 flat = clip.stage_blk[ui].t[:total]
@@ -704,9 +784,9 @@ class _FolderPipeline:
                 flat = torch.empty(total, dtype=torch.uint8, pin_memory=True)
             clip.stage[ui] = flat[:nb].view(*shape)
             if clip.measure:
-                clip.stage_gt[ui] = flat[nb:2 * nb].view(*shape)
+                clip.stage_gt[ui] = flat[nb:nb + nb_gt].view(*shape_gt)
                 if clip.mask_list is not None:
-                    clip.stage_mask[ui] = flat[2 * nb:].view(*shape[:4])
+                    clip.stage_mask[ui] = flat[nb + nb_gt:].view(*shape_mask)
             for b, si in enumerate(members):
                 for t in range(c0, c1):
                     clip.slot[clip.segs[si][1][t]] = (ui, t - c0, b)
@@ -738,12 +818,19 @@ class _FolderPipeline:
             else:
                 lab = ev.make_labels(g if hasattr(g, "rasterise") else self.model, poses)
             lab = lab.to(g.device).reshape(Tc, Bc, *lab.shape[1:])            # [Tc,B,22,H,W]
-            dn = clip.stage[ui].to(g.device, non_blocking=True).permute(0, 1, 4, 2, 3).to(torch.float32)
-            dn = ((dn / 255.0 - 0.5) / 0.5).contiguous()                      # [Tc,B,3,H,W]
+            if clip.src_dain is not None:      # resize_on="gpu": resize + ToTensor + Normalize in one kernel (rib_resize_cubic)
+                dn = g.resize_u8(clip.stage[ui].to(g.device, non_blocking=True).flatten(0, 1), ev.width, ev.height,
+                                 normalised=True).view(Tc, Bc, 3, ev.height, ev.width)
+            else:
+                dn = clip.stage[ui].to(g.device, non_blocking=True).permute(0, 1, 4, 2, 3).to(torch.float32)
+                dn = ((dn / 255.0 - 0.5) / 0.5).contiguous()                      # [Tc,B,3,H,W]
             gtd = gt.to(g.device) if gt is not None else None
             if clip.measure:                   # the GT frames normalised as the DAIN frames are; masks 0/1 -> float
-                gtf = clip.stage_gt[ui].to(g.device, non_blocking=True).permute(0, 1, 4, 2, 3).to(torch.float32)
-                gtf = ((gtf / 255.0 - 0.5) / 0.5).reshape(Tc * Bc, 3, ev.height, ev.width).contiguous()
+                if clip.src_gt is not None:
+                    gtf = g.resize_u8(clip.stage_gt[ui].to(g.device, non_blocking=True).flatten(0, 1), ev.width, ev.height, normalised=True)
+                else:
+                    gtf = clip.stage_gt[ui].to(g.device, non_blocking=True).permute(0, 1, 4, 2, 3).to(torch.float32)
+                    gtf = ((gtf / 255.0 - 0.5) / 0.5).reshape(Tc * Bc, 3, ev.height, ev.width).contiguous()
                 mk = (clip.stage_mask[ui].to(g.device, non_blocking=True).to(torch.float32).reshape(Tc * Bc, ev.height, ev.width)
                       if ui in clip.stage_mask else None)
                 clip.meas[ui] = (gtf, mk)

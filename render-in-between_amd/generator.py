@@ -400,6 +400,51 @@ class Generator:
                 _ptr(ws), ws.numel(), self._stream()))
         return out[0], out[1]
 
+    def resize_u8(self, frames_u8, width, height, normalised=False, out=None):
+        """The folder driver's frame resize on the GPU (rib_resize_cubic): uint8 [N,H0,W0,3] (or [H0,W0,3]) on this device
+        -> uint8 [N,height,width,3] (or [height,width,3]), bit-exact to resize.resize_cubic_u8; normalised=True: float32
+        [N,3,height,width] holding ToTensor + Normalize(0.5, 0.5) of it, ((u8 / 255.0 - 0.5) / 0.5) as torch evaluates it
+        on the device.  A frame already at the target size comes back as a copy (or normalised).  The tap tables of
+        resize._cubic_taps are built once per (H0, W0, height, width) and kept on the device.  Enqueued on the current
+        stream.  out: optional contiguous destination of the result's shape and dtype."""
+        if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8 or frames_u8.dim() not in (3, 4) or frames_u8.shape[-1] != 3:
+            raise ValueError("frames_u8 must be a uint8 [N,H0,W0,3] or [H0,W0,3] tensor, got %s %s"
+                             % (getattr(frames_u8, "dtype", type(frames_u8)), tuple(getattr(frames_u8, "shape", ()))))
+        if frames_u8.device != self.device:
+            raise ValueError("resize_u8: frames_u8 is on %s, the generator on %s (upload the frames first)" % (frames_u8.device, self.device))
+        width, height = int(width), int(height)
+        single = frames_u8.dim() == 3
+        src = (frames_u8.unsqueeze(0) if single else frames_u8).contiguous()
+        N, H0, W0, _ = src.shape
+        if min(N, H0, W0) < 1 or width < 1 or height < 1:
+            raise ValueError("resize_u8: empty frames or a non-positive target size (%s -> %dx%d)" % (tuple(src.shape), width, height))
+        shape, dtype = ((N, 3, height, width), torch.float32) if normalised else ((N, height, width, 3), torch.uint8)
+        if out is None:
+            res = torch.empty(shape, dtype=dtype, device=self.device)
+        else:
+            res = out.unsqueeze(0) if (single and out.dim() == 3) else out
+            if tuple(res.shape) != shape or res.dtype != dtype or not res.is_contiguous() or res.device != self.device:
+                raise ValueError("resize_u8: out must be a contiguous %s %s tensor on %s" % (shape, dtype, self.device))
+        cache = self.__dict__.setdefault("_resize_taps", {})
+        taps = cache.get((H0, W0, height, width))
+        if taps is None:
+            from .resize import _cubic_taps
+            import numpy as np
+            (ix, cx), (iy, cy) = _cubic_taps(width, W0), _cubic_taps(height, H0)
+            host = np.concatenate([a.astype(np.int32).reshape(-1) for a in (ix, cx, iy, cy)])
+            # (kept for the life of the handle: a few KB per size pair, and a launch enqueued on another stream may still read it)
+            taps = cache[(H0, W0, height, width)] = torch.from_numpy(host).to(self.device)
+        nx, ny = width * 4 * 4, height * 4 * 4            # bytes of one table of each axis
+        base = taps.data_ptr()
+        tabs = [C.c_void_p(base + o) for o in (0, nx, 2 * nx, 2 * nx + ny)]
+        with torch.cuda.device(self.device):
+            _native.check(self._h, self._lib.rib_resize_cubic(
+                self._h, N, H0, W0, height, width, _ptr(src), *tabs,
+                _ptr(None if normalised else res), _ptr(res if normalised else None), self._stream()))
+        if out is not None:
+            return out
+        return res[0] if single else res
+
     def warp(self, img, flow):
         img = img.to(self.device, torch.float32).contiguous(); flow = flow.to(self.device, torch.float32).contiguous()
         B, Cc, H, W = img.shape

@@ -71,12 +71,13 @@ def summary_line(evaluator, rank=0, world=1):
     tm = evaluator.timings
     wall = max(tm.get("wall", 0.0), 1e-9)
     line = ("[rank %d/%d] %d frames in %.2f s = %.1f frames/s | load %.2f s, rasterise %.2f s, generate %.2f s, save tail %.2f s | "
-            "%d units, <= %d in flight | %d file workers (%s), CPU budget %d cores | PNG level %s, batch %d, %s plans"
+            "%d units, <= %d in flight | %d file workers (%s), CPU budget %d cores | PNG level %s, batch %d, %s plans | resize on %s"
             % (rank, world, tm.get("frames", 0), wall, tm.get("frames", 0) / wall, tm.get("load", 0.0), tm.get("rasterise", 0.0),
                tm.get("generate", 0.0), tm.get("save", 0.0), tm.get("units", 0), tm.get("peak_units_in_flight", 0),
                evaluator.io_threads, evaluator.io_mode, cpu_budget(),
                "reference (zlib 6)" if evaluator.png_compress_level is None else str(evaluator.png_compress_level),
-               evaluator.batch or evaluator.default_batch(), "batch-invariant" if evaluator.reproducible else "per-batch"))
+               evaluator.batch or evaluator.default_batch(), "batch-invariant" if evaluator.reproducible else "per-batch",
+               getattr(evaluator, "resize_on", "host")))
     rep = getattr(evaluator, "metrics_report", None)
     if "metrics" in tm and rep is not None:
         o = rep["overall"]
@@ -104,7 +105,7 @@ def main(opts):
         ribdist.init_process_group(os.environ.get("RIB_DIST_BACKEND"), device)
     net_G = load_generator(config, device, rank, world, opts.dtype)
     evaluator = Evaluator(config, batch=opts.batch or None, reproducible=opts.reproducible,
-                          png_compress_level=None if opts.png_level == "reference" else int(opts.png_level))
+                          png_compress_level=None if opts.png_level == "reference" else int(opts.png_level), resize_on=opts.resize_on)
     train_dir = os.path.join(opts.input_dir, "inputs")
     dain_dir = os.path.join(opts.input_dir, "DAIN")
     pose_dir = os.path.join(opts.input_dir, "Predict_motion")
@@ -147,6 +148,11 @@ def build_parser():
                              "GPU); writes <save-dir>/Generated_frames/metrics.json (not in the reference's folder driver)")
     parser.add_argument("--mask-dir", type=str, default=None,
                         help="with --metrics: <mask-dir>/<clip>/ grayscale masks at the model size (value > 127 = measured pixel)")
+    parser.add_argument("--resize-on", choices=("host", "gpu"), default="host",
+                        help="where the DAIN frames (and, with --metrics, the ground-truth frames) are resized to the model size: 'host' "
+                             "(default): by the file workers, as the reference does; 'gpu': decoded at their own size and resized by the "
+                             "HIP kernel, bit-exact to the host resize - the same files, less CPU per frame when the inputs are larger "
+                             "than the model size (key frames stay on the host)")
     return parser
 
 

@@ -29,6 +29,18 @@ def decode_resized_u8(path, width, height, resize="cv2"):
     return resize_cubic_u8(np.asarray(img, dtype=np.uint8), width, height), (w0, h0)
 
 
+def decode_raw_into(buf, offset, path, size):
+    """The "do not resize" decode of Evaluator(resize_on="gpu"): PIL decode -> RGB uint8 HWC at the file's OWN size, written to
+    bytes [offset, offset + h0*w0*3) of `buf` (a shared block's buffer, or any writable buffer); the GPU resizes it
+    (rib_resize_cubic).  size = (w0, h0) the plan read from the file's header: the section was laid out for it."""
+    from PIL import Image
+    img = Image.open(path).convert("RGB")
+    if tuple(img.size) != tuple(size):
+        raise ValueError("%s is %dx%d, its staging slot was planned for %dx%d" % (path, img.size[0], img.size[1], size[0], size[1]))
+    dst = np.ndarray((size[1], size[0], 3), np.uint8, buffer=buf, offset=offset)
+    dst[...] = np.asarray(img, dtype=np.uint8)
+
+
 def normalised_chw(u8):
     """ToTensor + Normalize(0.5, 0.5) (HSM_auto_dataset.py:73-75) of a uint8 HWC frame: float32 CHW in [-1, 1]."""
     a = u8.astype(np.float32) / 255.0
@@ -109,16 +121,22 @@ def load_mask_u8(path, width, height):
 
 
 def load_frame_shm(shm_name, offset, dain_path, ref_img_path, pose_path, is_key, want_tables, width, height, resize, thres1, thres2,
-                   gt_offset=-1, mask_path=None, mask_offset=-1):
+                   gt_offset=-1, mask_path=None, mask_offset=-1, dain_raw=None, gt_raw=None):
     """load_frame with the DAIN frame written to bytes [offset, offset + H*W*3) of a shared block (offset < 0: not wanted,
     the frame is a key frame that passes through); returns (None, key frame uint8 HWC or None, tables).
     A measured frame (Evaluator metrics) also has its ground-truth frame - ref_img_path, which is gt_dir's frame i - decoded
-    through the same resize to bytes [gt_offset, +H*W*3), and its mask (load_mask_u8) to [mask_offset, +H*W)."""
-    if offset >= 0:
+    through the same resize to bytes [gt_offset, +H*W*3), and its mask (load_mask_u8) to [mask_offset, +H*W).
+    dain_raw / gt_raw = (w0, h0) (Evaluator(resize_on="gpu")): that frame is NOT resized here but written at its own size,
+    h0*w0*3 bytes from its offset (decode_raw_into); the key frame and the keypoints are unaffected."""
+    if offset >= 0 and dain_raw is not None:
+        decode_raw_into(_attach(shm_name).buf, offset, dain_path, dain_raw)
+    elif offset >= 0:
         dain, _ = decode_resized_u8(dain_path, width, height, resize)
         dst = np.ndarray((height, width, 3), np.uint8, buffer=_attach(shm_name).buf, offset=offset)
         dst[...] = dain
-    if gt_offset >= 0:
+    if gt_offset >= 0 and gt_raw is not None:
+        decode_raw_into(_attach(shm_name).buf, gt_offset, ref_img_path, gt_raw)
+    elif gt_offset >= 0:
         dst = np.ndarray((height, width, 3), np.uint8, buffer=_attach(shm_name).buf, offset=gt_offset)
         dst[...] = decode_resized_u8(ref_img_path, width, height, resize)[0]
     if mask_offset >= 0:

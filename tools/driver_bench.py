@@ -2,11 +2,13 @@
 """End-to-end rate of the folder driver (json + PNG in, PNG out) on a synthetic clip.
 
     python tools/driver_bench.py [--size 512 | --height 320 --width 480] [--keys 5] [--rate 32] [--lanes 2] [--batch B] [--chunk 4]
+                                  [--src-width 1920 --src-height 1080] [--resize-on host|gpu]
 
 Writes a clip in the reference's directory layout (inputs/ DAIN/ Predict_motion/), runs
 Evaluator.evaluate_from_folder twice (the first run also builds launch plans) and prints the
 phase times of the second: load (decode + json), rasterise (GPU), generate (GPU chains + quantise +
-one D2H copy), save (PNG encode).
+one D2H copy), save (PNG encode).  --src-width / --src-height write the input frames at that size (default: the model size),
+so that the driver has to resize them; --resize-on says where (Evaluator(resize_on=...)).
 """
 import argparse, json, os, sys, tempfile, time
 import numpy as np, torch
@@ -16,21 +18,22 @@ from render_in_between_amd import evaluator as ev, synth
 from tools.raster_bench import person
 
 
-def write_clip(root, n_key, rate, H, W):
+def write_clip(root, n_key, rate, H, W, src_h=0, src_w=0):
     from PIL import Image
     rng = np.random.default_rng(0)
     n = (n_key - 1) * rate + 1
     for d in ("inputs", "DAIN", "Predict_motion"):
         os.makedirs(os.path.join(root, d, "clip"))
     spec = rib.GenSpec.from_cfg(rib.hsm_gen_config())
+    sh, sw = src_h or H, src_w or W          # the files' size; the keypoints below are in the same pixels
     def img(seed):
-        a = np.asarray(synth.smooth_image(spec, 1, H, W, seed))[0]
+        a = np.asarray(synth.smooth_image(spec, 1, sh, sw, seed))[0]
         return ((a * 0.5 + 0.5).clip(0, 1) * 255).astype(np.uint8).transpose(1, 2, 0)
     for k in range(n_key):
         Image.fromarray(img(k)).save(os.path.join(root, "inputs", "clip", "%04d.png" % k))
     for i in range(n):
         Image.fromarray(img(100 + i)).save(os.path.join(root, "DAIN", "clip", "f%04d.png" % i))
-        lm, conf = person(rng, H, W)
+        lm, conf = person(rng, sh, sw)
         body = np.zeros((25, 3)); idx = list(range(15)) + [19, 22]
         for j, k in enumerate(idx):
             body[k] = (lm[j][0], lm[j][1], conf[j])
@@ -57,6 +60,9 @@ def main():
     ap.add_argument("--io-mode", default="process", choices=("process", "thread"))
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--dtype", default="f32")
+    ap.add_argument("--src-width", type=int, default=0, help="width of the synthetic input files (0: the model width)")
+    ap.add_argument("--src-height", type=int, default=0, help="height of the synthetic input files (0: the model height)")
+    ap.add_argument("--resize-on", default="host", choices=("host", "gpu"), help="where the DAIN frames are resized (Evaluator(resize_on=...))")
     a = ap.parse_args()
     H, W = (a.height or a.size), (a.width or a.size)
     cfg = rib.AttrDict(gen=rib.hsm_gen_config(), model_height=H, model_width=W, gauss_sigma=5, skeleton_thres=0.001, foot_thres=0.001)
@@ -64,9 +70,9 @@ def main():
     G = rib.Generator(cfg.gen, compute_dtype=a.dtype).eval()
     G.load_state_dict(synth.make_state_dict(spec, 0, power_iters=3))
     with tempfile.TemporaryDirectory() as root:
-        n = write_clip(root, a.keys, a.rate, H, W)
+        n = write_clip(root, a.keys, a.rate, H, W, a.src_height, a.src_width)
         E = ev.Evaluator(cfg, lanes=a.lanes, batch=a.batch or None, chunk=a.chunk, io_threads=a.io_threads or None,
-                         png_compress_level=None if a.compress < 0 else a.compress, io_mode=a.io_mode)
+                         png_compress_level=None if a.compress < 0 else a.compress, io_mode=a.io_mode, resize_on=a.resize_on)
         dirs = [os.path.join(root, d) for d in ("inputs", "DAIN", "Predict_motion")]
         walls = []
         for rep in range(1 + a.reps):           # the first run also builds launch plans and pools: not counted
@@ -80,6 +86,7 @@ def main():
     print(json.dumps({"height": H, "width": W, "dtype": a.dtype, "frames": n, "generated": gen, "lanes": a.lanes,
                       "batch": a.batch or E.default_batch(), "chunk": a.chunk, "io_threads": E.io_threads, "io_mode": a.io_mode,
                       "cpus": len(os.sched_getaffinity(0)), "cpu_budget": ev.cpu_budget(), "png_compress_level": a.compress,
+                      "src_height": a.src_height or H, "src_width": a.src_width or W, "resize_on": a.resize_on,
                       "wall_s": wall, "wall_s_runs": [round(w, 4) for w in walls[1:]], "frames_per_s_end_to_end": n / wall,
                       "phase_s_last_run": {k: round(v, 4) for k, v in tm.items() if k not in ("frames", "units", "timeline", "peak_units_in_flight")},
                       "peak_units_in_flight": tm.get("peak_units_in_flight"),
