@@ -27,6 +27,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <variant>
 #include <vector>
 
 
@@ -497,44 +498,68 @@ struct PRef {
 // and the label branch on side streams: measured slower three times - two queues cost more than the overlap returns on
 // this runtime - and incompatible with the lifetime-shared workspace; retired in round 3.)
 
+// One planned launch: the fields every launch shares, a few launch selectors, the parameter struct of ITS kernel family
+// with the scalar fields filled in, and one list of pointer bindings - which pointer field of that struct resolves to which
+// PRef.  The bindings are the only home of a pointer: run_plan resolves them, the workspace lifetime analysis walks them
+// (Builder::for_each_pref) and the byte model asks them (bound()); the pointer fields of `params` itself stay null.
+using OpParams = std::variant<PackParams, IgemmParams, FinalizeParams, PoolParams, InAddParams, SplitEpiParams, ModulateParams,
+                              WinoInParams, WinoOutParams, LowcParams, GemmDmaParams>;      // in the order of OpKind
+static_assert(std::is_same<std::variant_alternative_t<OP_IGEMM, OpParams>, IgemmParams>::value &&
+              std::is_same<std::variant_alternative_t<OP_GEMM, OpParams>, GemmDmaParams>::value, "OpParams follows OpKind");
 struct Op {
-  OpKind kind;
-  int kclass;
+  int kclass = 0;
   std::string name;
-  // igemm
-  const Variant* var = nullptr;
   std::string for_op;        // a finalize launch emitted on behalf of this consumer (rib_time_op times them together)
   bool label_only = false;   // depends on the label map only (pack.label, down_first, the mask network's label branch)
+  dim3 grid;
+  double flops = 0;
+  const Variant* var = nullptr;   // k_igemm / k_gemm_dma tile
   int small_co = 0;   // > 0: a head convolution with small_co output channels: k_conv_head (matrix cores, taps as GEMM
                       //      columns) when `head`, else k_conv_small (direct, vector ALUs), instead of k_igemm
   bool head = false;
   bool fuse_blend = false;   // the mask head also writes the driver's blend into user slot U_FUSE when the caller gave one
-  IgemmParams ip;   // scalar fields pre-filled; pointers resolved from the PRefs below
-  PRef x, pro_scale, pro_shift, w, bias, y, res, y_nchw, stat, xm, m_scale, m_shift, ys0, ys1, slab, x2, w2;
-  PRef m_part;   // consumer-side InstanceNorm finalize in the SPADE epilogue (IgemmParams)
-  // consumer-side finalize in k_wino_in / k_spade_modulate (slot 0) and k_in_add (slots 0, 1): the StatSrc pointers
-  PRef st_part[2], st_gamma[2], st_beta[2];
-  // split-K epilogue
-  SplitEpiParams sp; PRef s_slab, s_bias, s_y, s_res, s_stat;
-  // unfused SPADE modulate
-  ModulateParams mp; PRef m_slab, m_bias, m_xm, m_sc, m_sh, m_ys0, m_ys1;
-  dim3 grid;
-  double flops = 0;
-  // finalize
-  FinalizeParams fp; PRef f_part, f_gamma, f_beta, f_scale, f_shift;
-  // pool
-  PoolParams pp; PRef p_x, p_y, p_stat;
-  // in_add
-  InAddParams ap; PRef a_t1, a_sc1, a_sh1, a_ts, a_scs, a_shs, a_x, a_out;
-  // pack
-  PackParams kp; PRef k_s0, k_s1, k_s2, k_dst;
-  LowcParams lc; PRef lc_s0, lc_s1, lc_s2, lc_w, lc_bias, lc_y, lc_stat; int lowc_ce = 0, lowc_ncol = 0, lowc_tw = 32;
-  // Winograd transforms
-  WinoInParams wi; PRef wi_x, wi_sc, wi_sh, wi_v, wi_slab, wi_sbias, wi_x2, wi_xres, wi_o, wi_sc2, wi_sh2; int wi_mode = 0;
-  WinoOutParams wo; PRef wo_m, wo_bias, wo_y, wo_res, wo_stat;
-  GemmDmaParams gp; PRef g_a, g_b, g_c;      // OP_GEMM: k_gemm_dma (tile = var)
-  bool wino = false;   // this k_igemm launch is the 16- / 36-way batched Winograd-domain GEMM (executes 4/9 or 1/4 of its nine-tap FLOP count)
+  bool wino = false;   // this GEMM launch is the 16- / 36-way batched Winograd-domain GEMM (executes 4/9 or 1/4 of its nine-tap FLOP count)
   int wino_m = 0;      // 2 or 4 on the three launches of a Winograd convolution
+  int wi_mode = 0;     // k_wino_in: WSRC_PLAIN / WSRC_SPADE / WSRC_JOIN
+  int lowc_ce = 0, lowc_ncol = 0, lowc_tw = 32;
+  OpParams params;
+  struct Binding { PRef ref; unsigned field = 0; };      // field: byte offset of the pointer inside `params`
+  static constexpr int kMaxBindings = 24;            // (the largest families, k_igemm and k_wino_in, have 18 pointers)
+  Binding binds[kMaxBindings];
+  int nbinds = 0;
+
+  OpKind kind() const { return (OpKind)params.index(); }
+  template <class P> const P& as() const { return std::get<P>(params); }
+  // a pointer field of the parameter struct P (or of a StatSrc inside it) as its byte offset; P must be this op's family
+  template <class P, class T> unsigned field_of(T* P::*f) const {
+    return (unsigned)(reinterpret_cast<const char*>(&(as<P>().*f)) - reinterpret_cast<const char*>(&params));
+  }
+  template <class P, class T> unsigned field_of(StatSrc P::*s, T* StatSrc::*f) const {
+    return (unsigned)(reinterpret_cast<const char*>(&((as<P>().*s).*f)) - reinterpret_cast<const char*>(&params));
+  }
+  PRef ref_at(unsigned field) const {
+    for (int i = 0; i < nbinds; ++i) if (binds[i].field == field) return binds[i].ref;
+    return PRef();
+  }
+  // binding a field again replaces its reference; a null reference unbinds it
+  void bind_at(unsigned field, PRef r) {
+    int i = 0;
+    while (i < nbinds && binds[i].field != field) ++i;
+    if (r.sp == PS_NULL) { if (i < nbinds) binds[i] = binds[--nbinds]; return; }
+    if (i == kMaxBindings) abort();      // (unreachable: a family has fewer pointer fields than that)
+    binds[i] = Binding{r, field};
+    if (i == nbinds) ++nbinds;
+  }
+  template <class P, class T> bool bound(T* P::*f) const { return ref_at(field_of(f)).sp != PS_NULL; }
+};
+// An Op under construction, typed by its kernel family: bind() takes pointer fields of P only, so a misspelt field or a
+// field of another family does not compile.  push() stores the Op part.
+template <class P> struct OpOf : Op {
+  OpOf(int kclass_, const std::string& name_) { kclass = kclass_; name = name_; memset(&params.emplace<P>(), 0, sizeof(P)); }
+  P& p() { return std::get<P>(params); }
+  template <class T> void bind(T* P::*f, PRef r) { bind_at(field_of(f), r); }
+  template <class T> void bind(StatSrc P::*s, T* StatSrc::*f, PRef r) { bind_at(field_of(s, f), r); }
+  template <class T> PRef ref(T* P::*f) const { return ref_at(field_of(f)); }
 };
 
 struct PendingStats {
@@ -990,8 +1015,9 @@ struct FusionPolicy {
   bool fuse_shortcut = !getenv("RIB_NO_FUSE_SHORTCUT");
   // buffers with disjoint lifetimes share workspace bytes (assign_physical)
   bool ws_reuse = !getenv("RIB_NO_WS_REUSE");
-  // level i of the mask network's label encoder and of its image encoder in ONE paired launch (batch-1 frame plans)
-  bool pair_mask_encoders = !getenv("RIB_NO_PAIR");
+  // level i of the mask network's label encoder and of its image encoder in ONE paired launch (batch-1 frame plans).
+  // Asked on every forward, ahead of the plan cache (plan_pairs): a function of its own, so that asking reads this switch alone
+  static bool pair_mask_encoders() { return !getenv("RIB_NO_PAIR"); }
 };
 
 struct Builder {
@@ -1019,16 +1045,30 @@ struct Builder {
     out->pend = ps;
   }
   // A light consumer (k_wino_in, k_spade_modulate, k_in_add: channel slices of 64) reduces the producer's partials itself:
-  // fills the StatSrc scalars and the op's PRefs from the pending finalize of n, which then never launches unless another
-  // consumer needs the arrays.  false: the partials are gone / too many / the launch is forced -> the caller materializes.
-  bool take_partials(const Norm& n, StatSrc& st, Op& op, int slot) {
+  // fills the scalars of the op's StatSrc `src` and binds its pointers from the pending finalize of n, which then never
+  // launches unless another consumer needs the arrays.  false: the partials are gone / too many / the launch is forced ->
+  // the caller materializes.
+  template <class P> bool take_partials(const Norm& n, OpOf<P>& op, StatSrc P::*src) {
     if (!has_partials(n) || n.pend->tiles > STATS_MAX_PARTIALS) return false;
     const PendingStats& ps = *n.pend;
-    memset(&st, 0, sizeof st);
+    StatSrc& st = op.p().*src;
     st.tiles = ps.tiles; st.Cs = ps.Cs; st.inv_count = ps.inv_count;
-    op.st_part[slot] = WS(ps.part_off);
-    if (ps.affine) { op.st_gamma[slot] = WT(ps.g_off); op.st_beta[slot] = WT(ps.be_off); }
+    op.bind(src, &StatSrc::part, WS(ps.part_off));
+    if (ps.affine) { op.bind(src, &StatSrc::gamma, WT(ps.g_off)); op.bind(src, &StatSrc::beta, WT(ps.be_off)); }
     return true;
+  }
+  // the k_stats_finalize launch of a producer that left `tiles` partial sums per image (Cs columns, C of them stored) at part_off
+  OpOf<FinalizeParams> finalize_op(const std::string& producer, size_t part_off, int tiles, int Cs, int C, const Norm& out, size_t choff,
+                                   int H, int W, const ConvDef* affine, int images) {
+    OpOf<FinalizeParams> f(RIB_KC_STATS, producer + ".stats");
+    FinalizeParams& q = f.p();
+    q.tiles = tiles; q.Cs = Cs; q.C = C; q.ld = out.ld; q.off = (int)choff;
+    q.inv_count = 1.0f / ((float)H * (float)W); q.eps = 1e-5f;
+    f.bind(&FinalizeParams::part, WS(part_off));
+    if (affine) { f.bind(&FinalizeParams::gamma, WT(affine->g_off)); f.bind(&FinalizeParams::beta, WT(affine->be_off)); }
+    f.bind(&FinalizeParams::scale, WS(out.sc)); f.bind(&FinalizeParams::shift, WS(out.sh));
+    f.grid = dim3((Cs + 15) / 16, images, 1);
+    return f;
   }
   // gamma/beta slab of a condition level (cond_level_gemm): [B][H*W][ld] fp32, group columns at SpadeGroup::col0
   struct LevelSlab { size_t off = 0; int ld = 0; };
@@ -1089,6 +1129,7 @@ struct Builder {
   static PRef WS(size_t off) { PRef r; r.sp = PS_WS; r.off = off; return r; }
   static PRef WT(size_t off) { PRef r; r.sp = PS_WEIGHT; r.off = off; return r; }
   static PRef US(int slot) { PRef r; r.sp = PS_USER; r.off = (size_t)slot; return r; }
+  static PRef WINO(int set) { PRef r; r.sp = PS_WINO; r.off = (size_t)set; return r; }
   void tap(const std::string& name, const Act& a) { P->taps.push_back(Tap{name, a.off, a.Cp, a.C, a.H, a.W}); }
 
   // ---- generic convolution launch --------------------------------------------------------
@@ -1172,9 +1213,8 @@ struct Builder {
     const Variant* v = ch.v;
     if (!v) { error = fmt("%s: no kernel variant for Cin=%d stride=%d ks=%d ups=%d", opname.c_str(), c.cinp, c.stride, c.ks, (int)a.ups); return false; }
     const int S = ch.ksplit;
-    Op op; op.kind = OP_IGEMM; op.kclass = RIB_KC_IGEMM; op.name = opname; op.var = v;
-    IgemmParams& p = op.ip;
-    memset(&p, 0, sizeof p);
+    OpOf<IgemmParams> op(RIB_KC_IGEMM, opname); op.var = v;
+    IgemmParams& p = op.p();
     p.Hin = a.in.H; p.Win = a.in.W; p.xC = a.in.Cp; p.Cin = c.cinp;
     p.pro_ld = a.pro ? a.pro->ld : 0; p.pro_lrelu = a.pro_lrelu ? 1 : 0;
     p.CoutPad = c.coutp;
@@ -1184,7 +1224,7 @@ struct Builder {
     p.xcd_chunk = xcd_chunk_of(p.tilesX * p.tilesY);
     if (a.ups && (!c.ups_in || c.ks != 3 || c.stride != 1)) { error = opname + ": no phase filters for this upsample convolution"; return false; }
     p.act = a.act; p.ksplit = S;
-    op.x = WS(a.in.off);
+    op.bind(&IgemmParams::x, WS(a.in.off));
     // heads with 1..4 output channels (conv_img, conv_mask.0): direct convolution on the vector ALUs; the
     // matrix-core kernels would pad N to 16 columns.  y_nchw's channel count is Cout of the conv itself.
     const bool small = c.cout <= 4 && c.ks == 3 && c.stride == 1 && !a.ups && !a.res && !a.aux && !a.want_stats &&
@@ -1194,25 +1234,26 @@ struct Builder {
       // (a consumer-side finalize in the PROLOGUE was tried and removed: its (scale, shift) table cost every prologue
       // variant 4 KB of LDS - an occupancy step for several of them - to save four launches; the SPADE epilogue keeps its own)
       materialize(*a.pro, opname);
-      op.pro_scale = WS(a.pro->sc + a.pro_choff * sizeof(float)); op.pro_shift = WS(a.pro->sh + a.pro_choff * sizeof(float));
+      op.bind(&IgemmParams::pro_scale, WS(a.pro->sc + a.pro_choff * sizeof(float)));
+      op.bind(&IgemmParams::pro_shift, WS(a.pro->sh + a.pro_choff * sizeof(float)));
     }
     // matrix-core kernels of a bf16 handle read the bf16 filter copies; the direct head convolutions keep fp32 filters
     const bool w16 = h->mc16() && !small;
-    op.w = WT(a.ups ? (w16 ? c.wp16_off : c.wp_off) : (w16 ? c.w16_off : c.w_off)); op.bias = WT(c.b_off);
+    op.bind(&IgemmParams::w, WT(a.ups ? (w16 ? c.wp16_off : c.wp_off) : (w16 ? c.w16_off : c.w_off))); op.bind(&IgemmParams::bias, WT(c.b_off));
     double aux_flops = 0.0;
     if (a.aux) {
       if (c.ks != 3 || c.stride != 1 || a.ups || !c.fb_off || a.aux->ks != 1 || a.aux->coutp != c.coutp || a.aux_in.Cp != a.aux->cinp ||
           a.aux_in.H != Hout || a.aux_in.W != Wout) { error = opname + ": fused shortcut operand does not fit"; return false; }
-      op.x2 = WS(a.aux_in.off); op.w2 = WT(h->mc16() ? a.aux->w16_off : a.aux->w_off); op.bias = WT(c.fb_off);
+      op.bind(&IgemmParams::x2, WS(a.aux_in.off)); op.bind(&IgemmParams::w2, WT(h->mc16() ? a.aux->w16_off : a.aux->w_off)); op.bind(&IgemmParams::bias, WT(c.fb_off));
       p.x2C = a.aux_in.Cp; p.Cin2 = a.aux->cinp;
       aux_flops = 2.0 * a.aux->cin * a.aux->cout * (double)Hout * Wout * B;
     }
     if (a.y_user.sp != PS_NULL) {
-      op.y = a.y_user; p.yC = c.cout; p.yoff = 0; p.Cout = c.cout; p.y_f32 = 1;   // a caller's fp32 tensor
+      op.bind(&IgemmParams::y, a.y_user); p.yC = c.cout; p.yoff = 0; p.Cout = c.cout; p.y_f32 = 1;   // a caller's fp32 tensor
     } else if (a.y_none) {
-      op.y = PRef(); p.yC = 0; p.yoff = 0; p.Cout = a.cout_store >= 0 ? a.cout_store : c.cout;
+      p.yC = 0; p.yoff = 0; p.Cout = a.cout_store >= 0 ? a.cout_store : c.cout;
     } else {
-      op.y = WS(a.out.off); p.yC = a.out.Cp; p.yoff = a.yoff;
+      op.bind(&IgemmParams::y, WS(a.out.off)); p.yC = a.out.Cp; p.yoff = a.yoff;
       p.Cout = a.cout_store >= 0 ? a.cout_store : h->padc(c.cout);
       if (a.out.H != Hout || a.out.W != Wout) { error = fmt("%s: output size mismatch", opname.c_str()); return false; }
     }
@@ -1223,8 +1264,8 @@ struct Builder {
       p.b_stride = (unsigned)(a.pair->b_off - c.b_off);
       p.pair = a.pair_merge ? 1 : 0; p.pair_yoff = a.pair_yoff;
     }
-    if (a.res) { op.res = WS(a.res->off); p.resC = a.res->Cp; p.res_ups = a.res_ups ? 1 : 0; }
-    op.y_nchw = a.y_nchw;
+    if (a.res) { op.bind(&IgemmParams::res, WS(a.res->off)); p.resC = a.res->Cp; p.res_ups = a.res_ups ? 1 : 0; }
+    op.bind(&IgemmParams::y_nchw, a.y_nchw);
     if (a.y_none && !(small && c.cout <= 3 && (c.cinp == 16 || c.cinp == 32) && pol.head_conv && a.y_nchw.sp != PS_NULL)) {
       error = opname + ": only the head kernel can run without an NHWC destination"; return false;
     }
@@ -1249,41 +1290,35 @@ struct Builder {
     P->flops[RIB_KC_IGEMM] += op.flops;
     if (a.pair && (S != 1 || v->NF == 0)) { error = opname + ": a paired launch cannot split K or use the 16-column path"; return false; }
     if (S == 1) {
-      if (a.want_stats) { part_off = alloc((size_t)nB * tiles * 2 * c.coutp * sizeof(double)); op.stat = WS(part_off); }
+      if (a.want_stats) { part_off = alloc((size_t)nB * tiles * 2 * c.coutp * sizeof(double)); op.bind(&IgemmParams::stat_part, WS(part_off)); }
       push(op);
     } else {
       // split-K: the conv writes raw partial slabs; a second kernel sums them and runs the epilogue
       const size_t slab_off = alloc((size_t)S * B * Hout * Wout * c.coutp * sizeof(float));
-      op.slab = WS(slab_off);
-      Op e; e.kind = OP_SPLITEPI; e.kclass = RIB_KC_CONVAUX; e.name = opname + ".splitk_sum";
-      memset(&e.sp, 0, sizeof e.sp);
-      e.sp.ksplit = S; e.sp.B = B; e.sp.CoutPad = c.coutp; e.sp.yC = p.yC; e.sp.yoff = p.yoff; e.sp.Cout = p.Cout;
-      e.sp.act = p.act; e.sp.resC = p.resC; e.sp.res_ups = p.res_ups; e.sp.Hout = Hout; e.sp.Wout = Wout;
+      op.bind(&IgemmParams::slab, WS(slab_off));
+      OpOf<SplitEpiParams> e(RIB_KC_CONVAUX, opname + ".splitk_sum");
+      SplitEpiParams& q = e.p();
+      q.ksplit = S; q.B = B; q.CoutPad = c.coutp; q.yC = p.yC; q.yoff = p.yoff; q.Cout = p.Cout;
+      q.act = p.act; q.resC = p.resC; q.res_ups = p.res_ups; q.Hout = Hout; q.Wout = Wout;
       const int slots = 256 / (c.coutp / 4), ppb = slots * 4;
       const int blocks = (Hout * Wout + ppb - 1) / ppb;
-      e.sp.blocks = blocks;
-      e.s_slab = WS(slab_off); e.s_bias = op.bias; e.s_y = op.y; e.s_res = op.res;
-      if (a.want_stats) { part_off = alloc((size_t)B * blocks * 2 * c.coutp * sizeof(double)); e.s_stat = WS(part_off); }
+      q.blocks = blocks;
+      // the epilogue launch takes over the convolution's bias, destination and residual
+      e.bind(&SplitEpiParams::slab, WS(slab_off)); e.bind(&SplitEpiParams::bias, op.ref(&IgemmParams::bias));
+      e.bind(&SplitEpiParams::y, op.ref(&IgemmParams::y)); e.bind(&SplitEpiParams::res, op.ref(&IgemmParams::res));
+      if (a.want_stats) { part_off = alloc((size_t)B * blocks * 2 * c.coutp * sizeof(double)); e.bind(&SplitEpiParams::stat_part, WS(part_off)); }
       e.grid = dim3(blocks, B, 1);
       tiles = blocks;   // the statistics partials now come from the epilogue kernel's blocks
-      op.y = PRef(); op.res = PRef();
+      op.bind(&IgemmParams::y, PRef()); op.bind(&IgemmParams::res, PRef());
       push(op);
       push(e);
     }
     if (a.want_stats) {
-      Op f; f.kind = OP_FINALIZE; f.kclass = RIB_KC_STATS; f.name = opname + ".stats";
-      memset(&f.fp, 0, sizeof f.fp);
-      f.fp.tiles = tiles; f.fp.Cs = c.coutp; f.fp.C = h->padc(c.cout);
-      f.fp.ld = a.stats_out->ld; f.fp.off = (int)a.stats_choff;
-      f.fp.inv_count = 1.0f / ((float)Hout * (float)Wout); f.fp.eps = 1e-5f;
-      f.f_part = WS(part_off);
-      if (a.affine) { f.f_gamma = WT(c.g_off); f.f_beta = WT(c.be_off); }
-      f.f_scale = WS(a.stats_out->sc); f.f_shift = WS(a.stats_out->sh);
-      f.grid = dim3(c.coutp / 16, nB, 1);
-      if (a.pair) { f.fp.g_stride = a.affine ? (int)(a.pair->g_off - c.g_off) : 0; f.fp.pair_merge = a.pair_merge ? 1 : 0; f.fp.pair_off = a.pair_yoff; }
+      OpOf<FinalizeParams> f = finalize_op(opname, part_off, tiles, c.coutp, h->padc(c.cout), *a.stats_out, a.stats_choff, Hout, Wout, a.affine ? &c : nullptr, nB);
+      if (a.pair) { f.p().g_stride = a.affine ? (int)(a.pair->g_off - c.g_off) : 0; f.p().pair_merge = a.pair_merge ? 1 : 0; f.p().pair_off = a.pair_yoff; }
       // (a channel offset means two producers share the arrays - the concatenated encoders of the mask network -
       // and consumers would need two partial sources: those keep their launch; so does a paired launch)
-      finalize_or_defer(f, a.stats_out, a.stats_choff != 0 || a.stats_now || a.pair != nullptr, part_off, tiles, c.coutp, f.fp.inv_count, a.affine, c.g_off, c.be_off);
+      finalize_or_defer(f, a.stats_out, a.stats_choff != 0 || a.stats_now || a.pair != nullptr, part_off, tiles, c.coutp, f.p().inv_count, a.affine, c.g_off, c.be_off);
     }
     return true;
   }
@@ -1295,9 +1330,8 @@ struct Builder {
     if (!c.wl_off || c.ks != 3 || c.stride != 1 || a.ups || a.pro || a.res || a.aux || a.y_nchw.sp != PS_NULL || a.y_user.sp != PS_NULL ||
         a.in.uc[0] + a.in.uc[1] + a.in.uc[2] != c.cin) { error = opname + ": not a layer k_conv_lowc can run"; return false; }
     if (a.out.H != H || a.out.W != W) { error = fmt("%s: output size mismatch", opname.c_str()); return false; }
-    Op op; op.kind = OP_LOWC; op.kclass = RIB_KC_IGEMM; op.name = opname; op.lowc_ce = c.lowc_ce; op.lowc_ncol = c.lowc_ncol;
-    memset(&op.lc, 0, sizeof op.lc);
-    LowcParams& p = op.lc;
+    OpOf<LowcParams> op(RIB_KC_IGEMM, opname); op.lowc_ce = c.lowc_ce; op.lowc_ncol = c.lowc_ncol;
+    LowcParams& p = op.p();
     p.c0 = a.in.uc[0]; p.c1 = a.in.uc[1]; p.c2 = a.in.uc[2];
     p.H = H; p.W = W; p.yC = a.out.Cp; p.yoff = a.yoff; p.Cout = a.cout_store >= 0 ? a.cout_store : h->padc(c.cout);
     p.act = a.act; p.CoutPad = c.coutp;
@@ -1308,26 +1342,18 @@ struct Builder {
     op.lowc_tw = tw;
     p.tilesX = (W + tw - 1) / tw; p.tilesY = (H + 7) / 8;
     if (p.Cout > c.lowc_ncol || c.cout > c.lowc_ncol) { error = opname + ": more output columns than the k_conv_lowc instantiation has"; return false; }
-    op.lc_s0 = US(a.in.usrc[0]); if (p.c1) op.lc_s1 = US(a.in.usrc[1]); if (p.c2) op.lc_s2 = US(a.in.usrc[2]);
-    op.lc_w = WT(c.wl_off); op.lc_bias = WT(c.b_off); op.lc_y = WS(a.out.off);
+    op.bind(&LowcParams::s0, US(a.in.usrc[0])); if (p.c1) op.bind(&LowcParams::s1, US(a.in.usrc[1])); if (p.c2) op.bind(&LowcParams::s2, US(a.in.usrc[2]));
+    op.bind(&LowcParams::w, WT(c.wl_off)); op.bind(&LowcParams::bias, WT(c.b_off)); op.bind(&LowcParams::y, WS(a.out.off));
     const int tiles = p.tilesX * p.tilesY;
     size_t part_off = 0;
-    if (a.want_stats) { part_off = alloc((size_t)B * tiles * 2 * c.coutp * sizeof(double)); op.lc_stat = WS(part_off); }
+    if (a.want_stats) { part_off = alloc((size_t)B * tiles * 2 * c.coutp * sizeof(double)); op.bind(&LowcParams::stat_part, WS(part_off)); }
     op.grid = dim3(tiles, B, 1);
     op.flops = 2.0 * c.cin * 9.0 * c.cout * (double)H * W * B;
     P->flops[RIB_KC_IGEMM] += op.flops;
     push(op);
     if (a.want_stats) {
-      Op f; f.kind = OP_FINALIZE; f.kclass = RIB_KC_STATS; f.name = opname + ".stats";
-      memset(&f.fp, 0, sizeof f.fp);
-      f.fp.tiles = tiles; f.fp.Cs = c.coutp; f.fp.C = h->padc(c.cout);
-      f.fp.ld = a.stats_out->ld; f.fp.off = (int)a.stats_choff;
-      f.fp.inv_count = 1.0f / ((float)H * (float)W); f.fp.eps = 1e-5f;
-      f.f_part = WS(part_off);
-      if (a.affine) { f.f_gamma = WT(c.g_off); f.f_beta = WT(c.be_off); }
-      f.f_scale = WS(a.stats_out->sc); f.f_shift = WS(a.stats_out->sh);
-      f.grid = dim3(c.coutp / 16, B, 1);
-      finalize_or_defer(f, a.stats_out, a.stats_choff != 0 || a.stats_now, part_off, tiles, c.coutp, f.fp.inv_count, a.affine, c.g_off, c.be_off);
+      OpOf<FinalizeParams> f = finalize_op(opname, part_off, tiles, c.coutp, h->padc(c.cout), *a.stats_out, a.stats_choff, H, W, a.affine ? &c : nullptr, B);
+      finalize_or_defer(f, a.stats_out, a.stats_choff != 0 || a.stats_now, part_off, tiles, c.coutp, f.p().inv_count, a.affine, c.g_off, c.be_off);
     }
     return true;
   }
@@ -1347,39 +1373,39 @@ struct Builder {
     const size_t v_off = alloc((size_t)B * NP * ntiles * c.cinp * sizeof(float));
     const size_t m_off = alloc((size_t)B * NP * ntiles * c.coutp * sizeof(float));
     {   // input transform (with the convolution's prologue)
-      Op op; op.kind = OP_WINO_IN; op.kclass = RIB_KC_CONVAUX; op.name = opname + ".wino_in"; op.for_op = gname; op.wino_m = wm;
-      memset(&op.wi, 0, sizeof op.wi);
-      op.wi.H = a.in.H; op.wi.W = a.in.W; op.wi.xC = a.in.Cp; op.wi.Cin = c.cinp; op.wi.tilesY = tilesY; op.wi.tilesX = tilesX;
-      op.wi.pro_lrelu = a.pro_lrelu ? 1 : 0;
-      op.wi_x = WS(a.in.off); op.wi_v = WS(v_off);
+      OpOf<WinoInParams> op(RIB_KC_CONVAUX, opname + ".wino_in"); op.for_op = gname; op.wino_m = wm;
+      WinoInParams& wi = op.p();
+      wi.H = a.in.H; wi.W = a.in.W; wi.xC = a.in.Cp; wi.Cin = c.cinp; wi.tilesY = tilesY; wi.tilesX = tilesX;
+      wi.pro_lrelu = a.pro_lrelu ? 1 : 0;
+      op.bind(&WinoInParams::x, WS(a.in.off)); op.bind(&WinoInParams::v, WS(v_off));
       if (a.in.lazy) {
         const LazySrc& L = *a.in.lazy;
         if (a.pro || a.pro_lrelu) { error = gname + ": a lazy input carries its own prologue"; return false; }
         op.wi_mode = L.mode;
-        op.wi_x = WS(L.x.off); op.wi.xC = L.x.Cp;
-        op.wi.pro_ld = L.nx.ld;
-        if (!take_partials(L.nx, op.wi.st, op, 0)) { materialize(L.nx, gname); op.wi_sc = WS(L.nx.sc); op.wi_sh = WS(L.nx.sh); }
+        op.bind(&WinoInParams::x, WS(L.x.off)); wi.xC = L.x.Cp;
+        wi.pro_ld = L.nx.ld;
+        if (!take_partials(L.nx, op, &WinoInParams::st)) { materialize(L.nx, gname); op.bind(&WinoInParams::pro_scale, WS(L.nx.sc)); op.bind(&WinoInParams::pro_shift, WS(L.nx.sh)); }
         if (L.mode == WSRC_SPADE) {
-          op.wi.x_ups = L.x_ups ? 1 : 0; op.wi.pro_lrelu = L.lrelu ? 1 : 0;
-          op.wi_slab = WS(L.slab_off); op.wi.slab_ld = L.slab_ld; op.wi.col0 = L.col0; op.wi_sbias = WT(L.sbias_off);
+          wi.x_ups = L.x_ups ? 1 : 0; wi.pro_lrelu = L.lrelu ? 1 : 0;
+          op.bind(&WinoInParams::slab, WS(L.slab_off)); wi.slab_ld = L.slab_ld; wi.col0 = L.col0; op.bind(&WinoInParams::sbias, WT(L.sbias_off));
         } else {
           if (L.has2) {
-            op.wi_x2 = WS(L.x2.off);
+            op.bind(&WinoInParams::x2, WS(L.x2.off));
             if (L.n2.ld != L.nx.ld) { error = gname + ": join operands with different statistics rows"; return false; }
-            if (!take_partials(L.n2, op.wi.st2, op, 1)) { materialize(L.n2, gname); op.wi_sc2 = WS(L.n2.sc); op.wi_sh2 = WS(L.n2.sh); }
-          } else op.wi_xres = WS(L.xres.off);
-          op.wi_o = WS(L.o.off);
+            if (!take_partials(L.n2, op, &WinoInParams::st2)) { materialize(L.n2, gname); op.bind(&WinoInParams::pro2_scale, WS(L.n2.sc)); op.bind(&WinoInParams::pro2_shift, WS(L.n2.sh)); }
+          } else op.bind(&WinoInParams::xres, WS(L.xres.off));
+          op.bind(&WinoInParams::o, WS(L.o.off));
         }
-      } else if (a.pro && !(a.pro_choff == 0 && take_partials(*a.pro, op.wi.st, op, 0))) {
+      } else if (a.pro && !(a.pro_choff == 0 && take_partials(*a.pro, op, &WinoInParams::st))) {
         materialize(*a.pro, gname);
-        op.wi.pro_ld = a.pro->ld;
-        op.wi_sc = WS(a.pro->sc + a.pro_choff * sizeof(float)); op.wi_sh = WS(a.pro->sh + a.pro_choff * sizeof(float));
+        wi.pro_ld = a.pro->ld;
+        op.bind(&WinoInParams::pro_scale, WS(a.pro->sc + a.pro_choff * sizeof(float))); op.bind(&WinoInParams::pro_shift, WS(a.pro->sh + a.pro_choff * sizeof(float)));
       }
       // workgroup = (16 (tile, transformed row) units per pass) x (slice of 64 channels)
       const int nsl = (c.cinp + 63) / 64, units = ntiles * (wm + 2);
       // (every workgroup that reduces partials re-reads tiles x 64 channels x 16 bytes: few, fatter workgroups then)
-      op.wi.nslices = nsl; op.wi.ublocks = std::max(1, std::min((units + 15) / 16, (op.wi.st.tiles > 0 ? 512 : 4096) / nsl));
-      op.grid = dim3(op.wi.ublocks * nsl, B, 1);
+      wi.nslices = nsl; wi.ublocks = std::max(1, std::min((units + 15) / 16, (wi.st.tiles > 0 ? 512 : 4096) / nsl));
+      op.grid = dim3(wi.ublocks * nsl, B, 1);
       push(op);
     }
     {   // the 16 / 36 GEMMs as one 1x1 "convolution" of NP*B samples of a tilesY x tilesX image, one filter set per position
@@ -1399,60 +1425,49 @@ struct Builder {
       if (!v) { error = gname + ": no 1x1 kernel variant"; return false; }
       const int set = ensure_wino_set(h, (int)(&c - h->convs.data()), wm);
       if (set < 0) { error = gname + ": " + h->err; return false; }
-      Op op; op.kind = OP_IGEMM; op.kclass = RIB_KC_IGEMM; op.name = gname; op.var = v; op.wino = true; op.wino_m = wm;
-      op.flops = 2.0 * c.cin * 9.0 * c.cout * (double)Hout * Wout * B;      // the convolution's algorithmic count (executed: 4/9 or 1/4 of it)
+      const double fl = 2.0 * c.cin * 9.0 * c.cout * (double)Hout * Wout * B;      // the convolution's algorithmic count (executed: 4/9 or 1/4 of it)
+      P->flops[RIB_KC_IGEMM] += fl;
       if (v->dma()) {
         // M[n*NP + xi] = V[n*NP + xi] . U[xi]^T: Z = B*NP problems of ntiles x coutp x cinp
-        op.kind = OP_GEMM;
-        GemmDmaParams& g = op.gp;
-        memset(&g, 0, sizeof g);
+        OpOf<GemmDmaParams> op(RIB_KC_IGEMM, gname); op.var = v; op.wino = true; op.wino_m = wm; op.flops = fl;
+        GemmDmaParams& g = op.p();
         g.M = ntiles; g.N = c.coutp; g.K = c.cinp; g.lda = c.cinp; g.ldc = c.coutp;
         g.sA = (size_t)ntiles * c.cinp; g.sB = (size_t)c.coutp * c.cinp; g.sC = (size_t)ntiles * c.coutp; g.modB = NP;
-        op.g_a = WS(v_off); op.g_b = PRef(); op.g_b.sp = PS_WINO; op.g_b.off = (size_t)set; op.g_c = WS(m_off);
+        op.bind(&GemmDmaParams::A, WS(v_off)); op.bind(&GemmDmaParams::B, WINO(set)); op.bind(&GemmDmaParams::C, WS(m_off));
         op.grid = dim3((ntiles + v->BM() - 1) / v->BM(), (c.coutp + v->BN() - 1) / v->BN(), B * NP);
-        P->flops[RIB_KC_IGEMM] += op.flops;
         push(op);
       } else {
-      IgemmParams& p = op.ip;
-      memset(&p, 0, sizeof p);
+      OpOf<IgemmParams> op(RIB_KC_IGEMM, gname); op.var = v; op.wino = true; op.wino_m = wm; op.flops = fl;
+      IgemmParams& p = op.p();
       p.Hin = tilesY; p.Win = tilesX; p.xC = c.cinp; p.Cin = c.cinp; p.CoutPad = c.coutp; p.Hout = tilesY; p.Wout = tilesX;
       p.tilesX = (tilesX + v->TW() - 1) / v->TW(); p.tilesY = (tilesY + v->TH() - 1) / v->TH(); p.xcd_chunk = xcd_chunk_of(p.tilesX * p.tilesY);
       p.act = ACT_NONE; p.ksplit = 1; p.yC = c.coutp; p.yoff = 0; p.Cout = c.coutp;
       p.w_mod = NP; p.w_stride = (unsigned)((size_t)c.coutp * c.cinp);
-      op.x = WS(v_off); op.w = PRef(); op.w.sp = PS_WINO; op.w.off = (size_t)set; op.bias = WT(c.zero_off); op.y = WS(m_off);
+      op.bind(&IgemmParams::x, WS(v_off)); op.bind(&IgemmParams::w, WINO(set)); op.bind(&IgemmParams::bias, WT(c.zero_off)); op.bind(&IgemmParams::y, WS(m_off));
       op.grid = dim3(p.tilesX * p.tilesY, (c.coutp + v->BN() - 1) / v->BN(), B * NP);
-      P->flops[RIB_KC_IGEMM] += op.flops;
       push(op);
       }
     }
     {   // output transform + the convolution's epilogue
-      Op op; op.kind = OP_WINO_OUT; op.kclass = RIB_KC_CONVAUX; op.name = opname + ".wino_out"; op.for_op = gname; op.wino_m = wm;
-      memset(&op.wo, 0, sizeof op.wo);
+      OpOf<WinoOutParams> op(RIB_KC_CONVAUX, opname + ".wino_out"); op.for_op = gname; op.wino_m = wm;
+      WinoOutParams& wo = op.p();
       // workgroup = (16 (tile, output row) units per pass) x (slice of 64 channels); ONE statistics partial per unit block,
       // at most STATS_MAX_PARTIALS of them, so the consumer of the normalised tensor can reduce them itself
       const int nsl = (c.coutp + 63) / 64, units = ntiles * wm;
       const int blocks = std::max(1, std::min((units + 15) / 16, (int)STATS_MAX_PARTIALS));
-      op.wo.tilesY = tilesY; op.wo.tilesX = tilesX; op.wo.CoutPad = c.coutp; op.wo.ublocks = blocks; op.wo.nslices = nsl;
-      op.wo.yC = a.out.Cp; op.wo.yoff = a.yoff; op.wo.Cout = a.cout_store >= 0 ? a.cout_store : h->padc(c.cout);
-      op.wo.Hout = Hout; op.wo.Wout = Wout; op.wo.act = a.act;
+      wo.tilesY = tilesY; wo.tilesX = tilesX; wo.CoutPad = c.coutp; wo.ublocks = blocks; wo.nslices = nsl;
+      wo.yC = a.out.Cp; wo.yoff = a.yoff; wo.Cout = a.cout_store >= 0 ? a.cout_store : h->padc(c.cout);
+      wo.Hout = Hout; wo.Wout = Wout; wo.act = a.act;
       if (a.out.H != Hout || a.out.W != Wout) { error = fmt("%s: output size mismatch", opname.c_str()); return false; }
-      op.wo_m = WS(m_off); op.wo_bias = WT(c.b_off); op.wo_y = WS(a.out.off);
-      if (a.res) { op.wo_res = WS(a.res->off); op.wo.resC = a.res->Cp; }
+      op.bind(&WinoOutParams::m, WS(m_off)); op.bind(&WinoOutParams::bias, WT(c.b_off)); op.bind(&WinoOutParams::y, WS(a.out.off));
+      if (a.res) { op.bind(&WinoOutParams::res, WS(a.res->off)); wo.resC = a.res->Cp; }
       size_t part_off = 0;
-      if (a.want_stats) { part_off = alloc((size_t)B * blocks * 2 * c.coutp * sizeof(double)); op.wo_stat = WS(part_off); }
+      if (a.want_stats) { part_off = alloc((size_t)B * blocks * 2 * c.coutp * sizeof(double)); op.bind(&WinoOutParams::stat_part, WS(part_off)); }
       op.grid = dim3(blocks * nsl, B, 1);
       push(op);
       if (a.want_stats) {
-        Op f; f.kind = OP_FINALIZE; f.kclass = RIB_KC_STATS; f.name = opname + ".stats";
-        memset(&f.fp, 0, sizeof f.fp);
-        f.fp.tiles = blocks; f.fp.Cs = c.coutp; f.fp.C = h->padc(c.cout);
-        f.fp.ld = a.stats_out->ld; f.fp.off = (int)a.stats_choff;
-        f.fp.inv_count = 1.0f / ((float)Hout * (float)Wout); f.fp.eps = 1e-5f;
-        f.f_part = WS(part_off);
-        if (a.affine) { f.f_gamma = WT(c.g_off); f.f_beta = WT(c.be_off); }
-        f.f_scale = WS(a.stats_out->sc); f.f_shift = WS(a.stats_out->sh);
-        f.grid = dim3(c.coutp / 16, B, 1);
-        finalize_or_defer(f, a.stats_out, a.stats_choff != 0 || a.stats_now, part_off, blocks, c.coutp, f.fp.inv_count, a.affine, c.g_off, c.be_off);
+        OpOf<FinalizeParams> f = finalize_op(opname, part_off, blocks, c.coutp, h->padc(c.cout), *a.stats_out, a.stats_choff, Hout, Wout, a.affine ? &c : nullptr, B);
+        finalize_or_defer(f, a.stats_out, a.stats_choff != 0 || a.stats_now, part_off, blocks, c.coutp, f.p().inv_count, a.affine, c.g_off, c.be_off);
       }
     }
     return true;
@@ -1494,35 +1509,29 @@ struct Builder {
     const Variant* v = ch.v;
     if (!v) { error = name + ": no 1x1 kernel variant"; return false; }
     const size_t slab_off = alloc((size_t)B * cond.H * cond.W * N * sizeof(float));
-    Op op; op.kind = OP_IGEMM; op.kclass = RIB_KC_SPADE; op.name = name; op.var = v;
-    op.flops = fl;
+    P->flops[RIB_KC_SPADE] += fl;
+    LevelSlab ls; ls.off = slab_off; ls.ld = N;
+    level_slab[level] = ls;
     if (v->dma()) {
       // slab[b] = cond[b] . W_level^T: B problems of (H*W) x N x Cp
-      op.kind = OP_GEMM;
-      GemmDmaParams& g = op.gp;
-      memset(&g, 0, sizeof g);
+      OpOf<GemmDmaParams> op(RIB_KC_SPADE, name); op.var = v; op.flops = fl;
+      GemmDmaParams& g = op.p();
       g.M = cond.H * cond.W; g.N = N; g.K = cond.Cp; g.lda = cond.Cp; g.ldc = N;
       g.sA = (size_t)g.M * cond.Cp; g.sB = 0; g.sC = (size_t)g.M * N; g.modB = 0;
-      op.g_a = WS(cond.off); op.g_b = WT(h->mc16() ? first.w16_off : first.w_off); op.g_c = WS(slab_off);
+      op.bind(&GemmDmaParams::A, WS(cond.off)); op.bind(&GemmDmaParams::B, WT(h->mc16() ? first.w16_off : first.w_off)); op.bind(&GemmDmaParams::C, WS(slab_off));
       op.grid = dim3((g.M + v->BM() - 1) / v->BM(), (N + v->BN() - 1) / v->BN(), B);
-      P->flops[RIB_KC_SPADE] += fl;
       push(op);
-      LevelSlab ls; ls.off = slab_off; ls.ld = N;
-      level_slab[level] = ls;
       return true;
     }
-    IgemmParams& p = op.ip;
-    memset(&p, 0, sizeof p);
+    OpOf<IgemmParams> op(RIB_KC_SPADE, name); op.var = v; op.flops = fl;
+    IgemmParams& p = op.p();
     p.Hin = cond.H; p.Win = cond.W; p.xC = cond.Cp; p.Cin = cond.Cp;
     p.CoutPad = N; p.Hout = cond.H; p.Wout = cond.W; p.ksplit = 1;
     p.tilesX = (cond.W + v->TW() - 1) / v->TW(); p.tilesY = (cond.H + v->TH() - 1) / v->TH(); p.xcd_chunk = xcd_chunk_of(p.tilesX * p.tilesY);
-    op.x = WS(cond.off); op.w = WT(h->mc16() ? first.w16_off : first.w_off); op.bias = WT(first.b_off); op.slab = WS(slab_off);
+    op.bind(&IgemmParams::x, WS(cond.off)); op.bind(&IgemmParams::w, WT(h->mc16() ? first.w16_off : first.w_off));
+    op.bind(&IgemmParams::bias, WT(first.b_off)); op.bind(&IgemmParams::slab, WS(slab_off));
     op.grid = dim3(p.tilesX * p.tilesY, (N + v->BN() - 1) / v->BN(), B);
-    op.flops = fl;
-    P->flops[RIB_KC_SPADE] += fl;
     push(op);
-    LevelSlab ls; ls.off = slab_off; ls.ld = N;
-    level_slab[level] = ls;
     return true;
   }
 
@@ -1586,42 +1595,41 @@ struct Builder {
       } else {
         const Variant* cv = uf.v; S = uf.ksplit;
         slab_off = alloc((size_t)S * B * Hout * Wout * sg.npad * sizeof(float)); slab_ld = sg.npad;
-        Op op; op.kind = OP_IGEMM; op.kclass = RIB_KC_SPADE; op.name = key + ".spade"; op.var = cv;
-        IgemmParams& p = op.ip;
-        memset(&p, 0, sizeof p);
+        OpOf<IgemmParams> op(RIB_KC_SPADE, key + ".spade"); op.var = cv;
+        IgemmParams& p = op.p();
         p.Hin = cond.H; p.Win = cond.W; p.xC = cond.Cp; p.Cin = cond.Cp;
         p.CoutPad = sg.npad; p.Hout = Hout; p.Wout = Wout; p.ksplit = S;
         p.tilesX = (Wout + cv->TW() - 1) / cv->TW(); p.tilesY = (Hout + cv->TH() - 1) / cv->TH(); p.xcd_chunk = xcd_chunk_of(p.tilesX * p.tilesY);
-        op.x = WS(cond.off); op.w = WT(h->mc16() ? sg.w16_off : sg.w_off); op.bias = WT(sg.b_off); op.slab = WS(slab_off);
+        op.bind(&IgemmParams::x, WS(cond.off)); op.bind(&IgemmParams::w, WT(h->mc16() ? sg.w16_off : sg.w_off));
+        op.bind(&IgemmParams::bias, WT(sg.b_off)); op.bind(&IgemmParams::slab, WS(slab_off));
         op.grid = dim3(p.tilesX * p.tilesY, (sg.npad + cv->BN() - 1) / cv->BN(), B * S);
         op.flops = 2.0 * sg.cond * 2.0 * sg.nsets * sg.C * (double)Hout * Wout * B;
         P->flops[RIB_KC_SPADE] += op.flops;
         push(op);
       }
-      Op mo; mo.kind = OP_MODULATE; mo.kclass = RIB_KC_ELTWISE; mo.name = key + ".spade.modulate";
-      memset(&mo.mp, 0, sizeof mo.mp);
-      mo.mp.ksplit = S; mo.mp.B = B; mo.mp.slab_ld = slab_ld; mo.mp.col0 = col0; mo.mp.xmC = x.Cp; mo.mp.xm_ups = x_ups ? 1 : 0;
-      mo.mp.m_ld = nx.ld; mo.mp.C = sg.Cp; mo.mp.nsets = sg.nsets; mo.mp.act0 = act0 ? ACT_LRELU : ACT_NONE; mo.mp.act1 = ACT_NONE;
-      mo.mp.Hout = Hout; mo.mp.Wout = Wout;
-      mo.m_slab = WS(slab_off); mo.m_bias = WT(sg.b_off); mo.m_xm = WS(x.off);
+      OpOf<ModulateParams> mo(RIB_KC_ELTWISE, key + ".spade.modulate");
+      ModulateParams& mp = mo.p();
+      mp.ksplit = S; mp.B = B; mp.slab_ld = slab_ld; mp.col0 = col0; mp.xmC = x.Cp; mp.xm_ups = x_ups ? 1 : 0;
+      mp.m_ld = nx.ld; mp.C = sg.Cp; mp.nsets = sg.nsets; mp.act0 = act0 ? ACT_LRELU : ACT_NONE; mp.act1 = ACT_NONE;
+      mp.Hout = Hout; mp.Wout = Wout;
+      mo.bind(&ModulateParams::slab, WS(slab_off)); mo.bind(&ModulateParams::bias, WT(sg.b_off)); mo.bind(&ModulateParams::xm, WS(x.off));
       // a slice of 64 virtual channels lies inside one set when C is a multiple of 64: the modulate can then reduce the
       // producer's partials of its own channels
-      if (!(sg.Cp % 64 == 0 && nx.pend && !nx.pend->affine && sg.Cp <= nx.pend->Cs && take_partials(nx, mo.mp.st, mo, 0))) {
+      if (!(sg.Cp % 64 == 0 && nx.pend && !nx.pend->affine && sg.Cp <= nx.pend->Cs && take_partials(nx, mo, &ModulateParams::st))) {
         materialize(nx, key + ".spade");
-        mo.m_sc = WS(nx.sc); mo.m_sh = WS(nx.sh);
+        mo.bind(&ModulateParams::m_scale, WS(nx.sc)); mo.bind(&ModulateParams::m_shift, WS(nx.sh));
       }
-      mo.m_ys0 = WS(ys0->off); if (sg.nsets == 2) mo.m_ys1 = WS(ys1->off);
+      mo.bind(&ModulateParams::ys0, WS(ys0->off)); if (sg.nsets == 2) mo.bind(&ModulateParams::ys1, WS(ys1->off));
       const int nsl = (sg.nsets * sg.Cp + 63) / 64;
-      mo.mp.nslices = nsl; mo.mp.pblocks = std::max(1, std::min((Hout * Wout + 15) / 16, (mo.mp.st.tiles > 0 ? 384 : 2048) / nsl));
-      mo.grid = dim3(mo.mp.pblocks * nsl, B, 1);
+      mp.nslices = nsl; mp.pblocks = std::max(1, std::min((Hout * Wout + 15) / 16, (mp.st.tiles > 0 ? 384 : 2048) / nsl));
+      mo.grid = dim3(mp.pblocks * nsl, B, 1);
       push(mo);
       return true;
     }
     *ys0 = act(sg.C, Hout, Wout);
     if (sg.nsets == 2) *ys1 = act(sg.C, Hout, Wout);
-    Op op; op.kind = OP_IGEMM; op.kclass = RIB_KC_SPADE; op.name = key + ".spade"; op.var = v;
-    IgemmParams& p = op.ip;
-    memset(&p, 0, sizeof p);
+    OpOf<IgemmParams> op(RIB_KC_SPADE, key + ".spade"); op.var = v;
+    IgemmParams& p = op.p();
     p.Hin = cond.H; p.Win = cond.W; p.xC = cond.Cp; p.Cin = cond.Cp;
     const bool one_frag = v->NF == 1;      // [gamma(16) | beta(16)] layout
     const int ncols = one_frag ? 32 : sg.npad;
@@ -1630,17 +1638,17 @@ struct Builder {
     p.ksplit = 1;
     p.xmC = x.Cp; p.xm_ups = x_ups ? 1 : 0; p.m_ld = nx.ld; p.C = sg.Cp; p.nsets = sg.nsets;
     p.act0 = act0 ? ACT_LRELU : ACT_NONE; p.act1 = ACT_NONE;
-    op.x = WS(cond.off); op.w = WT(h->mc16() ? sg.w16_off : sg.w_off); op.bias = WT(sg.b_off);
-    if (one_frag) { op.w = WT(sg.w1_off); op.bias = WT(sg.b1_off); }
-    op.xm = WS(x.off);
+    op.bind(&IgemmParams::x, WS(cond.off)); op.bind(&IgemmParams::w, WT(h->mc16() ? sg.w16_off : sg.w_off)); op.bind(&IgemmParams::bias, WT(sg.b_off));
+    if (one_frag) { op.bind(&IgemmParams::w, WT(sg.w1_off)); op.bind(&IgemmParams::bias, WT(sg.b1_off)); }
+    op.bind(&IgemmParams::xm, WS(x.off));
     if (has_partials(nx) && !nx.pend->affine && sg.Cp <= nx.pend->Cs) {   // consumer-side finalize in the SPADE epilogue
       const PendingStats& ps = *nx.pend;
-      op.m_part = WS(ps.part_off); p.m_tiles = ps.tiles; p.m_Cs = ps.Cs; p.m_inv = ps.inv_count;
+      op.bind(&IgemmParams::m_part, WS(ps.part_off)); p.m_tiles = ps.tiles; p.m_Cs = ps.Cs; p.m_inv = ps.inv_count;
     } else {
       materialize(nx, key + ".spade");
-      op.m_scale = WS(nx.sc); op.m_shift = WS(nx.sh);
+      op.bind(&IgemmParams::m_scale, WS(nx.sc)); op.bind(&IgemmParams::m_shift, WS(nx.sh));
     }
-    op.ys0 = WS(ys0->off); if (sg.nsets == 2) op.ys1 = WS(ys1->off);
+    op.bind(&IgemmParams::ys0, WS(ys0->off)); if (sg.nsets == 2) op.bind(&IgemmParams::ys1, WS(ys1->off));
     op.grid = dim3(p.tilesX * p.tilesY, (ncols + v->BN() - 1) / v->BN(), B);
     op.flops = 2.0 * sg.cond * 2.0 * sg.nsets * sg.C * (double)Hout * Wout * B;
     P->flops[RIB_KC_SPADE] += op.flops;
@@ -1768,15 +1776,9 @@ struct Builder {
     return true;
   }
 
+  // every workspace reference of a launch
   template <typename F> static void for_each_pref(Op& op, F f) {
-    PRef* all[] = {&op.x, &op.pro_scale, &op.pro_shift, &op.w, &op.bias, &op.y, &op.res, &op.y_nchw, &op.stat, &op.xm, &op.m_scale,
-                   &op.m_shift, &op.ys0, &op.ys1, &op.slab, &op.x2, &op.w2, &op.m_part,
-                   &op.s_slab, &op.s_bias, &op.s_y, &op.s_res, &op.s_stat, &op.m_slab, &op.m_bias, &op.m_xm, &op.m_sc, &op.m_sh,
-                   &op.m_ys0, &op.m_ys1, &op.f_part, &op.f_gamma, &op.f_beta, &op.f_scale, &op.f_shift, &op.p_x, &op.p_y, &op.p_stat,
-                   &op.a_t1, &op.a_sc1, &op.a_sh1, &op.a_ts, &op.a_scs, &op.a_shs, &op.a_x, &op.a_out, &op.k_s0, &op.k_s1, &op.k_s2, &op.k_dst,
-                   &op.wi_x, &op.wi_sc, &op.wi_sh, &op.wi_v, &op.wi_slab, &op.wi_x2, &op.wi_xres, &op.wi_o, &op.wi_sc2, &op.wi_sh2, &op.wo_m, &op.wo_bias, &op.wo_y, &op.wo_res, &op.wo_stat,
-                   &op.lc_s0, &op.lc_s1, &op.lc_s2, &op.lc_w, &op.lc_bias, &op.lc_y, &op.lc_stat, &op.st_part[0], &op.st_part[1], &op.g_a, &op.g_c};
-    for (PRef* r : all) if (r->sp == PS_WS) f(*r);
+    for (int i = 0; i < op.nbinds; ++i) if (op.binds[i].ref.sp == PS_WS) f(op.binds[i].ref);
   }
   AllocRec* alloc_of(size_t voff) {
     // allocations are in increasing voff order
@@ -1855,10 +1857,9 @@ struct Builder {
     Act L = vL ? virt(c.label_nc, H, W, U_LABEL, c.label_nc) : act(c.label_nc, H, W);
     if (!vL && L.Cp > 32) { error = "input channel counts above 32 are not supported by the pack kernel"; return false; }
     if (!vL) {
-      Op op; op.kind = OP_PACK; op.kclass = RIB_KC_PACK; op.name = "pack.label";
-      memset(&op.kp, 0, sizeof op.kp);
-      op.kp.c0 = c.label_nc; op.kp.c1 = 0; op.kp.c2 = 0; op.kp.dC = L.Cp; op.kp.HW = H * W;
-      op.k_s0 = US(U_LABEL); op.k_dst = WS(L.off);
+      OpOf<PackParams> op(RIB_KC_PACK, "pack.label");
+      op.p().c0 = c.label_nc; op.p().dC = L.Cp; op.p().HW = H * W;
+      op.bind(&PackParams::s0, US(U_LABEL)); op.bind(&PackParams::dst, WS(L.off));
       op.grid = dim3((H * W + 63) / 64, B, 1);
       push(op);
     }
@@ -1900,11 +1901,10 @@ struct Builder {
     F.Ein = vE ? virt(c.image_nc * 2, H, W, U_FAKE, c.image_nc, U_PREV, c.image_nc) : act(c.image_nc * 2, H, W);     // cat([img_fake, img_prev]) generator.py:197
     F.I9 = vI ? virt(c.image_nc * 3, H, W, U_PREV, c.image_nc, U_FAKE, c.image_nc, U_IMG, c.image_nc) : act(c.image_nc * 3, H, W);   // cat([img_prev, img_fake, img]) generator.py:232
     auto pack = [&](const std::string& nm, const Act& dst, int s0, int c0, int s1, int c1) {
-      Op op; op.kind = OP_PACK; op.kclass = RIB_KC_PACK; op.name = nm;
-      memset(&op.kp, 0, sizeof op.kp);
-      op.kp.c0 = c0; op.kp.c1 = c1; op.kp.c2 = 0; op.kp.dC = dst.Cp; op.kp.HW = H * W;
-      op.k_s0 = US(s0); if (c1) op.k_s1 = US(s1);
-      op.k_dst = WS(dst.off);
+      OpOf<PackParams> op(RIB_KC_PACK, nm);
+      op.p().c0 = c0; op.p().c1 = c1; op.p().dC = dst.Cp; op.p().HW = H * W;
+      op.bind(&PackParams::s0, US(s0)); if (c1) op.bind(&PackParams::s1, US(s1));
+      op.bind(&PackParams::dst, WS(dst.off));
       op.grid = dim3((H * W + 63) / 64, B, 1);
       push(op);
     };
@@ -1996,19 +1996,13 @@ struct Builder {
         const int slots = 256 / (out.Cp / 4), ppb = slots * 4;
         const int blocks = (pooled.H * pooled.W + ppb - 1) / ppb;
         const size_t part = alloc((size_t)B * blocks * 2 * out.Cp * sizeof(double));
-        Op op; op.kind = OP_POOL; op.kclass = RIB_KC_POOL; op.name = "down_" + std::to_string(i) + ".pool";
-        memset(&op.pp, 0, sizeof op.pp);
-        op.pp.H = out.H; op.pp.W = out.W; op.pp.C = out.Cp; op.pp.blocks = blocks;
-        op.p_x = WS(out.off); op.p_y = WS(pooled.off); op.p_stat = WS(part);
+        OpOf<PoolParams> op(RIB_KC_POOL, "down_" + std::to_string(i) + ".pool");
+        op.p().H = out.H; op.p().W = out.W; op.p().C = out.Cp; op.p().blocks = blocks;
+        op.bind(&PoolParams::x, WS(out.off)); op.bind(&PoolParams::y, WS(pooled.off)); op.bind(&PoolParams::stat_part, WS(part));
         op.grid = dim3(blocks, B, 1);
         push(op);
-        Op f; f.kind = OP_FINALIZE; f.kclass = RIB_KC_STATS; f.name = op.name + ".stats";
-        memset(&f.fp, 0, sizeof f.fp);
-        f.fp.tiles = blocks; f.fp.Cs = out.Cp; f.fp.C = out.Cp; f.fp.ld = np.ld; f.fp.off = 0;
-        f.fp.inv_count = 1.0f / ((float)pooled.H * (float)pooled.W); f.fp.eps = 1e-5f;
-        f.f_part = WS(part); f.f_scale = WS(np.sc); f.f_shift = WS(np.sh);
-        f.grid = dim3((out.Cp + 15) / 16, B, 1);
-        finalize_or_defer(f, &np, false, part, blocks, out.Cp, f.fp.inv_count, false, 0, 0);
+        OpOf<FinalizeParams> f = finalize_op(op.name, part, blocks, out.Cp, out.Cp, np, 0, pooled.H, pooled.W, nullptr, B);
+        finalize_or_defer(f, &np, false, part, blocks, out.Cp, f.p().inv_count, false, 0, 0);
         x = pooled; nx = np;
       } else { x = out; nx = nout; }
     }
@@ -2089,19 +2083,19 @@ struct Builder {
           continue;
         }
       }
-      Op op; op.kind = OP_INADD; op.kclass = RIB_KC_ELTWISE; op.name = bn + ".join";
-      memset(&op.ap, 0, sizeof op.ap);
-      op.ap.C = o.Cp; op.ap.HW = Hm * Wm; op.ap.ld = n1.ld;
-      op.a_t1 = WS(t1.off);
-      if (!take_partials(n1, op.ap.st1, op, 0)) { materialize(n1); op.a_sc1 = WS(n1.sc); op.a_sh1 = WS(n1.sh); }
+      OpOf<InAddParams> op(RIB_KC_ELTWISE, bn + ".join");
+      InAddParams& ap = op.p();
+      ap.C = o.Cp; ap.HW = Hm * Wm; ap.ld = n1.ld;
+      op.bind(&InAddParams::t1, WS(t1.off));
+      if (!take_partials(n1, op, &InAddParams::st1)) { materialize(n1); op.bind(&InAddParams::sc1, WS(n1.sc)); op.bind(&InAddParams::sh1, WS(n1.sh)); }
       if (learned) {
-        op.a_ts = WS(ts.off);
-        if (!take_partials(ns, op.ap.sts, op, 1)) { materialize(ns); op.a_scs = WS(ns.sc); op.a_shs = WS(ns.sh); }
-      } else op.a_x = WS(xin_stored.off);
-      op.a_out = WS(o.off);
+        op.bind(&InAddParams::ts, WS(ts.off));
+        if (!take_partials(ns, op, &InAddParams::sts)) { materialize(ns); op.bind(&InAddParams::scs, WS(ns.sc)); op.bind(&InAddParams::shs, WS(ns.sh)); }
+      } else op.bind(&InAddParams::xres, WS(xin_stored.off));
+      op.bind(&InAddParams::out, WS(o.off));
       const int nsl = (o.Cp + 63) / 64;
-      op.ap.nslices = nsl; op.ap.pblocks = std::max(1, std::min((Hm * Wm + 15) / 16, ((op.ap.st1.tiles > 0 || op.ap.sts.tiles > 0) ? 384 : 2048) / nsl));
-      op.grid = dim3(op.ap.pblocks * nsl, B, 1);
+      ap.nslices = nsl; ap.pblocks = std::max(1, std::min((Hm * Wm + 15) / 16, ((ap.st1.tiles > 0 || ap.sts.tiles > 0) ? 384 : 2048) / nsl));
+      op.grid = dim3(ap.pblocks * nsl, B, 1);
       push(op);
       tap("mask.res_" + std::to_string(i), o);
       r = o; first = false;
@@ -2137,7 +2131,7 @@ struct Builder {
 // level by level at batch 1 (Builder::mask_branches_paired) - same kernels, same choices, bit-identical frames.
 enum { PLAN_LABELS = 1, PLAN_UNPAIRED = 2 };
 inline bool plan_pairs(int B, int flags) {
-  return FusionPolicy().pair_mask_encoders && B == 1 && !(flags & (PLAN_LABELS | PLAN_UNPAIRED));
+  return FusionPolicy::pair_mask_encoders() && B == 1 && !(flags & (PLAN_LABELS | PLAN_UNPAIRED));
 }
 Plan* get_plan(rib_handle* h, int B, int H, int W, int flags = 0, int tuneB = 0) {
   const bool labels_only = (flags & PLAN_LABELS) != 0;
@@ -2175,12 +2169,12 @@ Plan* get_plan(rib_handle* h, int B, int H, int W, int flags = 0, int tuneB = 0)
 struct Resolver {
   char* ws; float* blob; const void* user[U_COUNT];
   const rib_handle* h = nullptr;     // for PS_WINO
-  template <typename T> T* get(const PRef& r) const {
+  void* get(const PRef& r) const {
     switch (r.sp) {
-      case PS_WS: return reinterpret_cast<T*>(ws + r.off);
-      case PS_WEIGHT: return reinterpret_cast<T*>(blob + r.off);
-      case PS_WINO: return reinterpret_cast<T*>(h->wino_sets[r.off].d);
-      case PS_USER: return reinterpret_cast<T*>(const_cast<void*>(user[r.off]));
+      case PS_WS: return ws + r.off;
+      case PS_WEIGHT: return blob + r.off;
+      case PS_WINO: return h->wino_sets[r.off].d;
+      case PS_USER: return const_cast<void*>(user[r.off]);
       default: return nullptr;
     }
   }
@@ -2226,17 +2220,15 @@ int run_plan(rib_handle* h, Plan* P, const Resolver& R, hipStream_t st, bool ski
       HIP_TRY(h, hipEventRecord(e0, st));
       h->prof_events.push_back({op.kclass, e0});
     }
-    switch (op.kind) {
+    // the launch's own copy of its parameters: scalars as planned, every bound pointer resolved
+    OpParams params = op.params;
+    for (int i = 0; i < op.nbinds; ++i) {
+      void* ptr = R.get(op.binds[i].ref);
+      memcpy(reinterpret_cast<char*>(&params) + op.binds[i].field, &ptr, sizeof ptr);
+    }
+    switch (op.kind()) {
       case OP_IGEMM: {
-        IgemmParams p = op.ip;
-        p.x = R.get<const float>(op.x); p.pro_scale = R.get<const float>(op.pro_scale); p.pro_shift = R.get<const float>(op.pro_shift);
-        p.w = R.get<const float>(op.w); p.bias = R.get<const float>(op.bias);
-        p.y = R.get<float>(op.y); p.res = R.get<const float>(op.res); p.y_nchw = R.get<float>(op.y_nchw);
-        p.stat_part = R.get<double>(op.stat); p.slab = R.get<float>(op.slab);
-        p.x2 = R.get<const float>(op.x2); p.w2 = R.get<const float>(op.w2);
-        p.xm = R.get<const float>(op.xm); p.m_scale = R.get<const float>(op.m_scale); p.m_shift = R.get<const float>(op.m_shift);
-        p.ys0 = R.get<float>(op.ys0); p.ys1 = R.get<float>(op.ys1);
-        p.m_part = R.get<const double>(op.m_part);
+        IgemmParams& p = std::get<IgemmParams>(params);
         p.zeros = R.blob + h->zero_off;
         if (op.small_co > 0 && op.head) {
           if (op.fuse_blend && R.user[U_FUSE]) {
@@ -2255,55 +2247,20 @@ int run_plan(rib_handle* h, Plan* P, const Resolver& R, hipStream_t st, bool ski
         } else
         RIB_KLAUNCH(pick_igemm_fn(op.var, p), op.grid, dim3(256 * op.var->KW), 0, st, p);
       } break;
-      case OP_GEMM: {
-        GemmDmaParams p = op.gp;
-        p.A = R.get<const float>(op.g_a); p.B = R.get<const float>(op.g_b); p.C = R.get<float>(op.g_c);
-        RIB_KLAUNCH(h->products == RIB_PRODUCTS_BF16X3 && op.var->gfn_x3 ? op.var->gfn_x3 : op.var->gfn, op.grid, dim3(256), 0, st, p);
-      } break;
+      case OP_GEMM:
+        RIB_KLAUNCH(h->products == RIB_PRODUCTS_BF16X3 && op.var->gfn_x3 ? op.var->gfn_x3 : op.var->gfn, op.grid, dim3(256), 0, st, std::get<GemmDmaParams>(params));
+        break;
       case OP_FINALIZE: {
-        FinalizeParams p = op.fp;
-        p.part = R.get<const double>(op.f_part); p.gamma = R.get<const float>(op.f_gamma); p.beta = R.get<const float>(op.f_beta);
-        p.scale = R.get<float>(op.f_scale); p.shift = R.get<float>(op.f_shift);
+        const FinalizeParams& p = std::get<FinalizeParams>(params);
         if (p.tiles > 512) RIB_KLAUNCH(k_stats_finalize<4>, dim3((p.Cs + 3) / 4, op.grid.y, op.grid.z), dim3(1024), 0, st, p);
         else RIB_KLAUNCH(k_stats_finalize<16>, op.grid, dim3(1024), 0, st, p);
       } break;
-      case OP_MODULATE: {
-        ModulateParams p = op.mp;
-        p.slab = R.get<const float>(op.m_slab); p.bias = R.get<const float>(op.m_bias); p.xm = R.get<const float>(op.m_xm);
-        p.m_scale = R.get<const float>(op.m_sc); p.m_shift = R.get<const float>(op.m_sh);
-        p.st.part = R.get<const double>(op.st_part[0]); p.st.gamma = R.get<const float>(op.st_gamma[0]); p.st.beta = R.get<const float>(op.st_beta[0]);
-        p.ys0 = R.get<float>(op.m_ys0); p.ys1 = R.get<float>(op.m_ys1);
-        RIB_LAUNCH_ST(bf16, k_spade_modulate, op.grid, dim3(256), 0, st, p);
-      } break;
-      case OP_SPLITEPI: {
-        SplitEpiParams p = op.sp;
-        p.slab = R.get<const float>(op.s_slab); p.bias = R.get<const float>(op.s_bias); p.y = R.get<float>(op.s_y);
-        p.res = R.get<const float>(op.s_res); p.stat_part = R.get<double>(op.s_stat);
-        RIB_LAUNCH_ST(bf16, k_splitk_epilogue, op.grid, dim3(256), 0, st, p);
-      } break;
-      case OP_POOL: {
-        PoolParams p = op.pp;
-        p.x = R.get<const float>(op.p_x); p.y = R.get<float>(op.p_y); p.stat_part = R.get<double>(op.p_stat);
-        RIB_LAUNCH_ST(bf16, k_avgpool, op.grid, dim3(256), 0, st, p);
-      } break;
-      case OP_INADD: {
-        InAddParams p = op.ap;
-        p.t1 = R.get<const float>(op.a_t1); p.sc1 = R.get<const float>(op.a_sc1); p.sh1 = R.get<const float>(op.a_sh1);
-        p.ts = R.get<const float>(op.a_ts); p.scs = R.get<const float>(op.a_scs); p.shs = R.get<const float>(op.a_shs);
-        p.xres = R.get<const float>(op.a_x); p.out = R.get<float>(op.a_out);
-        p.st1.part = R.get<const double>(op.st_part[0]); p.st1.gamma = R.get<const float>(op.st_gamma[0]); p.st1.beta = R.get<const float>(op.st_beta[0]);
-        p.sts.part = R.get<const double>(op.st_part[1]); p.sts.gamma = R.get<const float>(op.st_gamma[1]); p.sts.beta = R.get<const float>(op.st_beta[1]);
-        RIB_LAUNCH_ST(bf16, k_in_add, op.grid, dim3(256), 0, st, p);
-      } break;
+      case OP_MODULATE: RIB_LAUNCH_ST(bf16, k_spade_modulate, op.grid, dim3(256), 0, st, std::get<ModulateParams>(params)); break;
+      case OP_SPLITEPI: RIB_LAUNCH_ST(bf16, k_splitk_epilogue, op.grid, dim3(256), 0, st, std::get<SplitEpiParams>(params)); break;
+      case OP_POOL: RIB_LAUNCH_ST(bf16, k_avgpool, op.grid, dim3(256), 0, st, std::get<PoolParams>(params)); break;
+      case OP_INADD: RIB_LAUNCH_ST(bf16, k_in_add, op.grid, dim3(256), 0, st, std::get<InAddParams>(params)); break;
       case OP_WINO_IN: {
-        WinoInParams p = op.wi;
-        p.x = R.get<const float>(op.wi_x); p.pro_scale = R.get<const float>(op.wi_sc); p.pro_shift = R.get<const float>(op.wi_sh);
-        p.v = R.get<float>(op.wi_v);
-        p.st.part = R.get<const double>(op.st_part[0]); p.st.gamma = R.get<const float>(op.st_gamma[0]); p.st.beta = R.get<const float>(op.st_beta[0]);
-        p.slab = R.get<const float>(op.wi_slab); p.sbias = R.get<const float>(op.wi_sbias);
-        p.x2 = R.get<const float>(op.wi_x2); p.xres = R.get<const float>(op.wi_xres); p.o = R.get<float>(op.wi_o);
-        p.pro2_scale = R.get<const float>(op.wi_sc2); p.pro2_shift = R.get<const float>(op.wi_sh2);
-        p.st2.part = R.get<const double>(op.st_part[1]); p.st2.gamma = R.get<const float>(op.st_gamma[1]); p.st2.beta = R.get<const float>(op.st_beta[1]);
+        const WinoInParams& p = std::get<WinoInParams>(params);
         if (op.wino_m == 4) {
           if (op.wi_mode == WSRC_SPADE) RIB_KLAUNCH(k_wino4_in<WSRC_SPADE>, op.grid, dim3(256), 0, st, p);
           else if (op.wi_mode == WSRC_JOIN) RIB_KLAUNCH(k_wino4_in<WSRC_JOIN>, op.grid, dim3(256), 0, st, p);
@@ -2314,26 +2271,12 @@ int run_plan(rib_handle* h, Plan* P, const Resolver& R, hipStream_t st, bool ski
           else RIB_KLAUNCH(k_wino_in<WSRC_PLAIN>, op.grid, dim3(256), 0, st, p);
         }
       } break;
-      case OP_WINO_OUT: {
-        WinoOutParams p = op.wo;
-        p.m = R.get<const float>(op.wo_m); p.bias = R.get<const float>(op.wo_bias); p.y = R.get<float>(op.wo_y);
-        p.res = R.get<const float>(op.wo_res); p.stat_part = R.get<double>(op.wo_stat);
-        if (op.wino_m == 4) RIB_KLAUNCH(k_wino4_out, op.grid, dim3(256), 0, st, p);
-        else RIB_KLAUNCH(k_wino_out, op.grid, dim3(256), 0, st, p);
-      } break;
-      case OP_LOWC: {
-        LowcParams p = op.lc;
-        p.s0 = R.get<const float>(op.lc_s0); p.s1 = R.get<const float>(op.lc_s1); p.s2 = R.get<const float>(op.lc_s2);
-        p.w = R.get<const float>(op.lc_w); p.bias = R.get<const float>(op.lc_bias); p.y = R.get<float>(op.lc_y);
-        p.stat_part = R.get<double>(op.lc_stat);
-        launch_lowc(op.lowc_ce, op.lowc_ncol, op.lowc_tw, op.grid, st, p);
-      } break;
-      case OP_PACK: {
-        PackParams p = op.kp;
-        p.s0 = R.get<const float>(op.k_s0); p.s1 = R.get<const float>(op.k_s1); p.s2 = R.get<const float>(op.k_s2);
-        p.dst = R.get<float>(op.k_dst);
-        RIB_LAUNCH_ST(bf16, k_pack, op.grid, dim3(256), 0, st, p);
-      } break;
+      case OP_WINO_OUT:
+        if (op.wino_m == 4) RIB_KLAUNCH(k_wino4_out, op.grid, dim3(256), 0, st, std::get<WinoOutParams>(params));
+        else RIB_KLAUNCH(k_wino_out, op.grid, dim3(256), 0, st, std::get<WinoOutParams>(params));
+        break;
+      case OP_LOWC: launch_lowc(op.lowc_ce, op.lowc_ncol, op.lowc_tw, op.grid, st, std::get<LowcParams>(params)); break;
+      case OP_PACK: RIB_LAUNCH_ST(bf16, k_pack, op.grid, dim3(256), 0, st, std::get<PackParams>(params)); break;
     }
   }
   g_prof_pair = ProfPair();
@@ -3146,17 +3089,17 @@ int rib_debug_spade_weight(rib_handle* h, const char* conv_name, float* w_2c_by_
 
 // Launch list of a plan, for the CPU-side structure tests: "<name>|<kernel class>|<grid>|<tile>"
 static int launch_info_head(const Op& op, char* buf, size_t buflen) {
-  if (op.kind == OP_IGEMM && op.small_co > 0)
+  if (op.kind() == OP_IGEMM && op.small_co > 0)
     snprintf(buf, buflen, "%s|%d|%u,%u,%u|%s 16x16 tile, %d output channels%s|%.0f", op.name.c_str(), op.kclass, op.grid.x, op.grid.y, op.grid.z,
              op.head ? "head (taps as MFMA columns)" : "direct (vector ALUs)", op.small_co, op.fuse_blend ? " + fused blend" : "", op.flops);
-  else if (op.kind == OP_IGEMM)
+  else if (op.kind() == OP_IGEMM)
     snprintf(buf, buflen, "%s|%d|%u,%u,%u|tile %dx%d BN %d BK %d s%d k%d ups%d ksplit%d kw%d tb%d%s v%d|%.0f", op.name.c_str(), op.kclass, op.grid.x, op.grid.y, op.grid.z,
-             op.var->TH(), op.var->TW(), op.var->BN(), op.var->BK, op.var->STRIDE, op.var->KS, (int)op.var->UPS, op.ip.ksplit, op.var->KW, op.var->DMAK ? 100 + (op.var->TB == 9 ? 9 : 0) : op.var->TB,
+             op.var->TH(), op.var->TW(), op.var->BN(), op.var->BK, op.var->STRIDE, op.var->KS, (int)op.var->UPS, op.as<IgemmParams>().ksplit, op.var->KW, op.var->DMAK ? 100 + (op.var->TB == 9 ? 9 : 0) : op.var->TB,
              op.wino ? (op.wino_m == 4 ? " wino4" : " wino") : "", (int)(op.var - kVariants), op.flops);      // (v<n>: index into rib_variant_info)
-  else if (op.kind == OP_GEMM)
+  else if (op.kind() == OP_GEMM)
     snprintf(buf, buflen, "%s|%d|%u,%u,%u|gemm (LDS-DMA staged operands) tile %dx%d BK 32, %d x [%d x %d x %d]%s|%.0f", op.name.c_str(), op.kclass, op.grid.x, op.grid.y, op.grid.z,
-             op.var->BM(), op.var->BN(), (int)op.grid.z, op.gp.M, op.gp.N, op.gp.K, op.wino ? (op.wino_m == 4 ? " wino4" : " wino") : "", op.flops);
-  else if (op.kind == OP_LOWC)
+             op.var->BM(), op.var->BN(), (int)op.grid.z, op.as<GemmDmaParams>().M, op.as<GemmDmaParams>().N, op.as<GemmDmaParams>().K, op.wino ? (op.wino_m == 4 ? " wino4" : " wino") : "", op.flops);
+  else if (op.kind() == OP_LOWC)
     snprintf(buf, buflen, "%s|%d|%u,%u,%u|lowc (caller's NCHW tensors, K = 9 x %d real channels) 8x%d tile, %d columns|%.0f", op.name.c_str(), op.kclass,
              op.grid.x, op.grid.y, op.grid.z, op.lowc_ce, op.lowc_tw, op.lowc_ncol, op.flops);
   else
@@ -3166,64 +3109,68 @@ static int launch_info_head(const Op& op, char* buf, size_t buflen) {
 
 // Algorithmic HBM bytes of one launch (tools/prof_ops.py prices every launch against max(FLOPs / MFMA peak, these bytes / HBM)):
 // every operand the launch NEEDS read once, every result written once - activations in the storage type, filters and
-// statistics as stored; halo re-reads, split-K re-reads and L2 misses are exactly what this leaves out.
+// statistics as stored; halo re-reads, split-K re-reads and L2 misses are exactly what this leaves out.  Whether a launch
+// has an optional operand (residual, split-K slab, fused shortcut, join) is asked of its bindings: the pointer fields of the
+// planned parameter structs are null until run_plan resolves its own copy.
 static double op_algorithmic_bytes(const rib_handle* h, const Plan* P, const Op& op) {
   const double e = h->esz(), Bn = P->B;
-  switch (op.kind) {
+  switch (op.kind()) {
     case OP_IGEMM: {
-      const IgemmParams& p = op.ip;
-      const double samples = op.ip.pair ? 2.0 * Bn : Bn;      // a paired launch carries two convolutions per image
+      const IgemmParams& p = op.as<IgemmParams>();
+      const double samples = p.pair ? 2.0 * Bn : Bn;      // a paired launch carries two convolutions per image
       const int taps = op.var ? op.var->KS * op.var->KS : 9;
       double b = samples * p.Hin * p.Win * (double)p.Cin * e                         // input (or SPADE condition map)
-                 + (double)p.CoutPad * taps * p.Cin * e * (op.ip.pair ? 2.0 : 1.0)   // filters
+                 + (double)p.CoutPad * taps * p.Cin * e * (p.pair ? 2.0 : 1.0)      // filters
                  + p.CoutPad * 4.0;                                                    // bias
       if (op.var && op.var->SPADE) {
         b += Bn * p.Hout * p.Wout * (double)p.C * e / (p.xm_ups ? 4.0 : 1.0);          // tensor being normalised
         b += Bn * p.Hout * p.Wout * (double)p.C * e * p.nsets;                         // modulated outputs
-      } else if (p.slab) {
+      } else if (op.bound(&IgemmParams::slab)) {
         b += (double)p.ksplit * samples * p.Hout * p.Wout * p.CoutPad * 4.0;           // split-K partial slabs (fp32)
       } else {
         b += samples * p.Hout * p.Wout * (double)p.Cout * (op.small_co > 0 || p.y_f32 ? 4.0 : e);
-        if (p.res) b += samples * p.Hout * p.Wout * (double)p.Cout * e / (p.res_ups ? 4.0 : 1.0);
-        if (p.x2) b += samples * p.Hout * p.Wout * (double)p.Cin2 * e + (double)p.CoutPad * p.Cin2 * e;
-        if (p.bl_fuse) b += Bn * p.Hout * p.Wout * 3.0 * 4.0 * 3.0;                     // blend: img + dain read, fuse written (fp32 NCHW)
+        if (op.bound(&IgemmParams::res)) b += samples * p.Hout * p.Wout * (double)p.Cout * e / (p.res_ups ? 4.0 : 1.0);
+        if (op.bound(&IgemmParams::x2)) b += samples * p.Hout * p.Wout * (double)p.Cin2 * e + (double)p.CoutPad * p.Cin2 * e;
+        // blend: img + dain read, fuse written (fp32 NCHW).  Whether it runs is known per call only (did the caller pass a
+        // fused frame?); priced for every launch that can carry it
+        if (op.fuse_blend) b += Bn * p.Hout * p.Wout * 3.0 * 4.0 * 3.0;
       }
       return b;
     }
     case OP_GEMM: {
-      const GemmDmaParams& g = op.gp;
+      const GemmDmaParams& g = op.as<GemmDmaParams>();
       const double Z = op.grid.z;
       return Z * g.M * (double)g.K * e + (g.modB ? (double)g.modB : 1.0) * g.N * (double)g.K * e + Z * g.M * (double)g.N * 4.0;
     }
     case OP_LOWC: {
-      const LowcParams& l = op.lc;
+      const LowcParams& l = op.as<LowcParams>();
       return Bn * l.H * l.W * (double)(l.c0 + l.c1 + l.c2) * 4.0 + Bn * l.H * l.W * (double)l.Cout * e + 9.0 * (l.c0 + l.c1 + l.c2) * l.Cout * 4.0;
     }
-    case OP_POOL: return Bn * op.pp.H * op.pp.W * (double)op.pp.C * e * 1.25;
-    case OP_INADD: return Bn * op.ap.HW * (double)op.ap.C * e * 3.0;
+    case OP_POOL: { const PoolParams& q = op.as<PoolParams>(); return Bn * q.H * q.W * (double)q.C * e * 1.25; }
+    case OP_INADD: { const InAddParams& q = op.as<InAddParams>(); return Bn * q.HW * (double)q.C * e * 3.0; }
     case OP_SPLITEPI: {
-      const SplitEpiParams& q = op.sp;
-      return (double)q.ksplit * q.B * q.Hout * q.Wout * q.CoutPad * 4.0 + (double)q.B * q.Hout * q.Wout * q.Cout * e * (q.res ? 2.0 : 1.0);
+      const SplitEpiParams& q = op.as<SplitEpiParams>();
+      return (double)q.ksplit * q.B * q.Hout * q.Wout * q.CoutPad * 4.0 + (double)q.B * q.Hout * q.Wout * q.Cout * e * (op.bound(&SplitEpiParams::res) ? 2.0 : 1.0);
     }
     case OP_MODULATE: {
-      const ModulateParams& m = op.mp;
+      const ModulateParams& m = op.as<ModulateParams>();
       const double px = (double)m.B * m.Hout * m.Wout;
       return px * 2.0 * m.C * m.nsets * 4.0 * m.ksplit + px * m.C * e / (m.xm_ups ? 4.0 : 1.0) + px * m.C * e * m.nsets;
     }
     case OP_WINO_IN: {
-      const WinoInParams& w = op.wi;
+      const WinoInParams& w = op.as<WinoInParams>();
       const int T = op.wino_m + 2;
       double b = Bn * w.H * w.W * (double)w.Cin * e / (w.x_ups ? 4.0 : 1.0) + Bn * w.tilesY * w.tilesX * (double)T * T * w.Cin * e;
-      if (op.wi_mode != 0 && w.slab) b += Bn * w.H * w.W * 2.0 * w.Cin * 4.0;          // gamma/beta columns of the level slab
-      if (w.x2 || w.xres) b += Bn * w.H * w.W * (double)w.Cin * e * 2.0;               // join: second operand read, join stored
+      if (op.wi_mode != 0 && op.bound(&WinoInParams::slab)) b += Bn * w.H * w.W * 2.0 * w.Cin * 4.0;          // gamma/beta columns of the level slab
+      if (op.bound(&WinoInParams::x2) || op.bound(&WinoInParams::xres)) b += Bn * w.H * w.W * (double)w.Cin * e * 2.0;               // join: second operand read, join stored
       return b;
     }
     case OP_WINO_OUT: {
-      const WinoOutParams& w = op.wo;
+      const WinoOutParams& w = op.as<WinoOutParams>();
       const int T = op.wino_m + 2;
-      return Bn * w.tilesY * w.tilesX * (double)T * T * w.CoutPad * 4.0 + Bn * w.Hout * w.Wout * (double)w.Cout * e * (w.res ? 2.0 : 1.0);
+      return Bn * w.tilesY * w.tilesX * (double)T * T * w.CoutPad * 4.0 + Bn * w.Hout * w.Wout * (double)w.Cout * e * (op.bound(&WinoOutParams::res) ? 2.0 : 1.0);
     }
-    case OP_FINALIZE: return Bn * op.fp.tiles * 2.0 * op.fp.Cs * 8.0;
+    case OP_FINALIZE: { const FinalizeParams& q = op.as<FinalizeParams>(); return Bn * q.tiles * 2.0 * q.Cs * 8.0; }
     default: return 0.0;
   }
 }

@@ -260,6 +260,39 @@ def test_plan_flops_and_shape_rules(lib):
     lib.rib_destroy(h)
 
 
+def test_launch_bytes_count_the_optional_operands(lib):
+    """The byte model of rib_debug_launch_info (the HBM floor tools/prof_ops.py prices a launch against) asks the launch's
+    pointer bindings which optional operands it has.  A launch that adds a residual reads exactly one more activation,
+    B*H*W*C elements of the storage type, than its residual-free twin; a split-K launch writes its ksplit partial slabs."""
+    spec, h = host_handle(lib, rib.hsm_gen_config())
+    B, H, W = 1, 512, 512
+    buf = C.create_string_buffer(512)
+    info = {}
+    for i in range(lib.rib_num_launches(h, B, H, W)):
+        assert lib.rib_debug_launch_info(h, B, H, W, i, buf, 512) == 0
+        name, _, grid, tile, _, nbytes = buf.value.decode().split("|")
+        info[name] = (grid, tile, int(nbytes))
+    convs = {c.name: c for c in rib.conv_inventory(spec)}
+    # res_1: conv_block_0 and conv_block_1 are the same convolution shape; only conv_block_1 adds the block's input
+    c0, c1 = convs["res_1.conv_block_0"], convs["res_1.conv_block_1"]
+    assert (c0.cin, c0.cout, c0.ksize, c0.stride) == (c1.cin, c1.cout, c1.ksize, c1.stride)
+    plain, with_res = info["res_1.conv_block_0.wino_out"], info["res_1.conv_block_1.wino_out"]
+    assert plain[0] == with_res[0]
+    hr, wr = H >> spec.num_down_img, W >> spec.num_down_img
+    assert with_res[2] - plain[2] == B * hr * wr * c1.cout * 4              # one fp32 activation read
+    # a grid-level split-K convolution: input + filters + bias + ksplit slabs of fp32 partial sums, nothing else
+    cd = convs["ref_embedding.down_3"]
+    grid, tile, nbytes = info["ref_embedding.down_3"]
+    ksplit = int(re.search(r"ksplit(\d+)", tile).group(1))
+    assert ksplit >= 2 and "ref_embedding.down_3.splitk_sum" in info
+    hin, win = H >> 3, W >> 3
+    hout, wout = hin // cd.stride, win // cd.stride
+    assert cd.cin % 32 == 0 and cd.cout % 32 == 0                            # no channel padding in the terms below
+    slab = ksplit * B * hout * wout * cd.cout * 4
+    assert nbytes == B * hin * win * cd.cin * 4 + cd.cout * cd.ksize ** 2 * cd.cin * 4 + cd.cout * 4 + slab
+    lib.rib_destroy(h)
+
+
 def test_unsupported_configs_fail_loudly(lib):
     spec = rib.GenSpec.from_cfg(rib.hsm_gen_config(embed=dict(num_filters=24)))
     c = _native.RibConfig(**{n: getattr(spec, n) for n in FIELDS})
