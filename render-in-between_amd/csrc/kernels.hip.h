@@ -31,6 +31,9 @@ struct GemmDmaParams {
   int M, N, K, lda, ldc;
   size_t sA, sB, sC;      // element strides of the batch index z (B: of z % modB)
   int modB;               // 0: one B for every z
+  // K extent per position (the learned 1x1 shortcut of a res block in the Winograd domain): problems whose position
+  // z % modB has its bit set in kmask run K + K2 channels, the others K; the rows of A (lda) and of B hold K + K2 either way
+  int K2; unsigned long long kmask;
 };
 
 // ST = ST_BF16 / ST_F16: A and B hold 16-bit elements (lda, K, sA, sB in elements), a 128-byte row chunk is 64 of them, a
@@ -85,7 +88,8 @@ __global__ __launch_bounds__(256) void k_gemm_dma(const GemmDmaParams p) {
   for (int nf = 0; nf < NF; ++nf)
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc[nf][r] = 0.f; if constexpr (X3 == 2) acc_s[nf][r] = 0.f; }
-  const int nch = p.K / (BK * EPW);
+  const int ldb = (p.K + p.K2) / EPW;
+  const int nch = (p.K + (p.K2 && ((p.kmask >> (z % p.modB)) & 1ull) ? p.K2 : 0)) / (BK * EPW);
   typedef __attribute__((address_space(3))) void lds_void;
   const uint32_t lds0 = (uint32_t)(size_t)(lds_void*)smem;
   // this lane's source rows: fill j of a wave covers tile rows [wave * 8 + 32 j, + 8) of the stacked (A rows | B rows) tile;
@@ -97,7 +101,7 @@ __global__ __launch_bounds__(256) void k_gemm_dma(const GemmDmaParams p) {
     const bool isA = 32 * j < BM;                                     // (BM is a multiple of 32: a fill never straddles A | B)
     const int row = isA ? trow : trow - BM;
     const int ls = (lane & 7) ^ ((row >> 1) & 7);
-    src[j] = isA ? A + (size_t)min(m0 + row, p.M - 1) * (p.lda / EPW) + ls * 4 : B + (size_t)min(n0 + row, p.N - 1) * (p.K / EPW) + ls * 4;
+    src[j] = isA ? A + (size_t)min(m0 + row, p.M - 1) * (p.lda / EPW) + ls * 4 : B + (size_t)min(n0 + row, p.N - 1) * ldb + ls * 4;
   }
   auto fill = [&](int st, int kc) {
 #pragma unroll
@@ -431,7 +435,25 @@ struct WinoInParams {
   // WSRC_JOIN: the input is the mask network's residual join (k_in_add's arithmetic), out = IN(x) + (x2 ? IN2(x2) : xres),
   // which the unit that owns a pixel also stores to o (the next join's residual); no activation
   const float* x2; const float* xres; float* o; const float* pro2_scale; const float* pro2_shift; StatSrc st2;
+  int ldv;                                   // channels of a V row (Cin, or Cin + Cin2 with a second source)
+  // Second source (k_wino_in<MODE, MODE2>): the input of the block's learned 1x1 shortcut, which rides in the batched GEMM
+  // as Cin2 extra K columns behind the main channels.  A 1x1 filter is a 3x3 filter with only its centre tap, so its
+  // Winograd-domain filter G g G^T is non-zero only where row AND column of the position are one of the middle ones
+  // (4 of 16 / 16 of 36 positions), and V of this source is written at those positions only - they read the tile's own
+  // m x m pixels, no halo.  The last nslices2 of the nslices channel slices belong to it; it is WSRC_PLAIN (x2 stored) or
+  // WSRC_SPADE (x2 = tensor being normalised, st2 / pro2_*: its statistics, slab2 / col0_2 / sbias2: its gamma/beta)
+  int nslices2, Cin2, xC2, x2_ups, lrelu2, pro2_ld;
+  const float* slab2; int slab2_ld, col0_2; const float* sbias2;
 };
+// the parameters of the second source in the places of the first
+__device__ __forceinline__ WinoInParams wino_second(const WinoInParams& p) {
+  WinoInParams q = p;
+  q.x = p.x2; q.xC = p.xC2; q.Cin = p.Cin2; q.x_ups = p.x2_ups; q.pro_lrelu = p.lrelu2;
+  q.pro_scale = p.pro2_scale; q.pro_shift = p.pro2_shift; q.pro_ld = p.pro2_ld; q.st = p.st2;
+  q.slab = p.slab2; q.slab_ld = p.slab2_ld; q.col0 = p.col0_2; q.sbias = p.sbias2;
+  q.x2 = nullptr; q.v = p.v + p.Cin;
+  return q;
+}
 
 // out = IN(x) * (1 + gamma) + beta with the roundings pinned (two fused multiply-adds), shared by k_spade_modulate and the
 // Winograd input transforms that apply the modulation on the fly: bit-identical either way
@@ -521,22 +543,21 @@ __device__ __forceinline__ float4 wino_value(const WinoInParams& p, const WinoCo
 #define RIB_F4_SUB(a, b) make_float4((a).x - (b).x, (a).y - (b).y, (a).z - (b).z, (a).w - (b).w)
 #define RIB_F4_ADD(a, b) make_float4((a).x + (b).x, (a).y + (b).y, (a).z + (b).z, (a).w + (b).w)
 
-template <int MODE>
-__global__ __launch_bounds__(256) void k_wino_in(const WinoInParams p) {
+// SC: the source of the 1x1 shortcut - rows and columns 1, 2 of the transformed tile only
+template <int MODE, bool SC>
+__device__ __forceinline__ void wino_in_slice(const WinoInParams& p, int slice, int ub, double* red, float* s_sc, float* s_sh) {
   // thread = ((tile, row r of the transformed tile), 4 channels of the slice): a row needs two input rows (8 elements)
-  __shared__ double red[4 * 64 * 2];
-  __shared__ float s_sc[64], s_sh[64];
   const int c4n = p.Cin / 4;
   const int n = blockIdx.y;
-  const int slice = blockIdx.x % p.nslices, ub = blockIdx.x / p.nslices;
   const int c4 = slice * 16 + (threadIdx.x & 15);
   const bool cok = c4 < c4n;
   const int ntiles = p.tilesY * p.tilesX;
+  constexpr int NR = SC ? 2 : 4, Q0 = SC ? 1 : 0, Q1 = SC ? 3 : 4;
   WinoConsts<MODE> kc;
   wino_in_consts<MODE>(p, n, slice, c4, cok, red, s_sc, s_sh, kc);
   if (!cok) return;
-  for (int u = ub * 16 + (threadIdx.x >> 4); u < ntiles * 4; u += p.ublocks * 16) {
-    const int r = u & 3, tile = u >> 2;
+  for (int u = ub * 16 + (threadIdx.x >> 4); u < ntiles * NR; u += p.ublocks * 16) {
+    const int r = SC ? 1 + (u & 1) : u & 3, tile = SC ? u >> 1 : u >> 2;
     const int ty = tile / p.tilesX, tx = tile % p.tilesX;
     // B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]: row r of B^T d is d[ia] + sg * d[ib]
     const int ia = r == 0 ? 0 : (r == 2 ? 2 : 1), ib = r == 0 ? 2 : (r == 1 ? 2 : (r == 2 ? 1 : 3));
@@ -545,13 +566,13 @@ __global__ __launch_bounds__(256) void k_wino_in(const WinoInParams p) {
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
+      for (int q = Q0; q < Q1; ++q) {
         const int iy = 2 * ty - 1 + (a ? ib : ia), ix = 2 * tx - 1 + q;
         wino_fetch<MODE>(p, n, min(max(iy, 0), p.H - 1), min(max(ix, 0), p.W - 1), c4, d[a][q]);
       }
     float4 t[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
+    for (int q = Q0; q < Q1; ++q) {
       float4 v[2];
 #pragma unroll
       for (int a = 0; a < 2; ++a) {
@@ -566,13 +587,26 @@ __global__ __launch_bounds__(256) void k_wino_in(const WinoInParams p) {
       }
       t[q] = make_float4(v[0].x + sg * v[1].x, v[0].y + sg * v[1].y, v[0].z + sg * v[1].z, v[0].w + sg * v[1].w);
     }
-    const size_t plane = (size_t)ntiles * p.Cin;              // one position's [tiles][Cin] matrix
-    float* vb = p.v + (size_t)n * 16 * plane + (size_t)tile * p.Cin + c4 * 4;
-    *reinterpret_cast<float4*>(vb + (size_t)(r * 4 + 0) * plane) = RIB_F4_SUB(t[0], t[2]);
+    const size_t plane = (size_t)ntiles * p.ldv;              // one position's [tiles][ldv] matrix
+    float* vb = p.v + (size_t)n * 16 * plane + (size_t)tile * p.ldv + c4 * 4;
+    if constexpr (!SC) *reinterpret_cast<float4*>(vb + (size_t)(r * 4 + 0) * plane) = RIB_F4_SUB(t[0], t[2]);
     *reinterpret_cast<float4*>(vb + (size_t)(r * 4 + 1) * plane) = RIB_F4_ADD(t[1], t[2]);
     *reinterpret_cast<float4*>(vb + (size_t)(r * 4 + 2) * plane) = RIB_F4_SUB(t[2], t[1]);
-    *reinterpret_cast<float4*>(vb + (size_t)(r * 4 + 3) * plane) = RIB_F4_SUB(t[1], t[3]);
+    if constexpr (!SC) *reinterpret_cast<float4*>(vb + (size_t)(r * 4 + 3) * plane) = RIB_F4_SUB(t[1], t[3]);
   }
+}
+
+// MODE2 >= 0: with a second source (WinoInParams), whose channel slices are workgroups of their own
+template <int MODE, int MODE2 = -1>
+__global__ __launch_bounds__(256) void k_wino_in(const WinoInParams p) {
+  __shared__ double red[4 * 64 * 2];
+  __shared__ float s_sc[64], s_sh[64];
+  const int slice = blockIdx.x % p.nslices, ub = blockIdx.x / p.nslices;
+  if constexpr (MODE2 >= 0) {
+    const int n1 = p.nslices - p.nslices2;
+    if (slice >= n1) { wino_in_slice<MODE2, true>(wino_second(p), slice - n1, ub, red, s_sc, s_sh); return; }
+  }
+  wino_in_slice<MODE, false>(p, slice, ub, red, s_sc, s_sh);
 }
 
 struct WinoOutParams {
@@ -688,21 +722,20 @@ __device__ __forceinline__ float4 f4_fma(float a, float4 x, float4 acc) {
 __device__ __forceinline__ float4 f4_scale(float a, float4 x) { return make_float4(a * x.x, a * x.y, a * x.z, a * x.w); }
 
 // thread = ((tile, transformed row r), 4 channels of the slice); row r of B^T d needs the 3 or 4 input rows with a non-zero coefficient
-template <int MODE>
-__global__ __launch_bounds__(256) void k_wino4_in(const WinoInParams p) {
-  __shared__ double red[4 * 64 * 2];
-  __shared__ float s_sc[64], s_sh[64];
+// SC: the source of the 1x1 shortcut - rows and columns 1..4 of the transformed tile only
+template <int MODE, bool SC>
+__device__ __forceinline__ void wino4_in_slice(const WinoInParams& p, int slice, int ub, double* red, float* s_sc, float* s_sh) {
   const int c4n = p.Cin / 4;
   const int n = blockIdx.y;
-  const int slice = blockIdx.x % p.nslices, ub = blockIdx.x / p.nslices;
   const int c4 = slice * 16 + (threadIdx.x & 15);
   const bool cok = c4 < c4n;
   const int ntiles = p.tilesY * p.tilesX;
+  constexpr int NR = SC ? 4 : 6, Q0 = SC ? 1 : 0, Q1 = SC ? 5 : 6;
   WinoConsts<MODE> kc;
   wino_in_consts<MODE>(p, n, slice, c4, cok, red, s_sc, s_sh, kc);
   if (!cok) return;
-  for (int u = ub * 16 + (threadIdx.x >> 4); u < ntiles * 6; u += p.ublocks * 16) {
-    const int r = u % 6, tile = u / 6;
+  for (int u = ub * 16 + (threadIdx.x >> 4); u < ntiles * NR; u += p.ublocks * 16) {
+    const int r = SC ? 1 + u % 4 : u % 6, tile = u / NR;
     const int ty = tile / p.tilesX, tx = tile % p.tilesX;
     // rows with a non-zero coefficient: r = 0 -> {0, 2, 4}; r = 1..4 -> {1, 2, 3, 4}; r = 5 -> {1, 3, 5}
     const int a0 = r == 0 ? 0 : 1, da = (r == 0 || r == 5) ? 2 : 1, na = (r == 0 || r == 5) ? 3 : 4;
@@ -715,7 +748,7 @@ __global__ __launch_bounds__(256) void k_wino4_in(const WinoInParams p) {
 #pragma unroll
       for (int k = 0; k < 4; ++k)
 #pragma unroll
-        for (int q = 0; q < 6; ++q) {
+        for (int q = Q0; q < Q1; ++q) {
           const int iy = 4 * ty - 1 + a0 + min(k, na - 1) * da, ix = 4 * tx - 1 + q;
           wino_fetch<MODE>(p, n, min(max(iy, 0), p.H - 1), min(max(ix, 0), p.W - 1), c4, d[k][q]);
         }
@@ -725,7 +758,7 @@ __global__ __launch_bounds__(256) void k_wino4_in(const WinoInParams p) {
         const float coef = k < na ? kWino4BT[r][a] : 0.f;
         const int iy = 4 * ty - 1 + a;
 #pragma unroll
-        for (int q = 0; q < 6; ++q) {
+        for (int q = Q0; q < Q1; ++q) {
           const int ix = 4 * tx - 1 + q;
           float4 w = wino_value<MODE>(p, kc, d[k][q]);
           if (!(iy >= 0 && iy < p.H && ix >= 0 && ix < p.W)) w = make_float4(0.f, 0.f, 0.f, 0.f);   // zero padding after the prologue
@@ -741,9 +774,9 @@ __global__ __launch_bounds__(256) void k_wino4_in(const WinoInParams p) {
         const int iy = 4 * ty - 1 + a;
         WinoRaw<MODE> d[6];
 #pragma unroll
-        for (int q = 0; q < 6; ++q) wino_fetch<MODE>(p, n, min(max(iy, 0), p.H - 1), min(max(4 * tx - 1 + q, 0), p.W - 1), c4, d[q]);
+        for (int q = Q0; q < Q1; ++q) wino_fetch<MODE>(p, n, min(max(iy, 0), p.H - 1), min(max(4 * tx - 1 + q, 0), p.W - 1), c4, d[q]);
 #pragma unroll
-        for (int q = 0; q < 6; ++q) {
+        for (int q = Q0; q < Q1; ++q) {
           const int ix = 4 * tx - 1 + q;
           const bool inb = iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
           float4 w = wino_value<MODE>(p, kc, d[q]);
@@ -755,20 +788,34 @@ __global__ __launch_bounds__(256) void k_wino4_in(const WinoInParams p) {
         }
       }
     }
-    const size_t plane = (size_t)ntiles * p.Cin;
-    float* vb = p.v + (size_t)n * 36 * plane + (size_t)tile * p.Cin + c4 * 4;
+    const size_t plane = (size_t)ntiles * p.ldv;
+    float* vb = p.v + (size_t)n * 36 * plane + (size_t)tile * p.ldv + c4 * 4;
     // columns: V[r][j] = sum_q B^T[j][q] t[q] (compile-time coefficients)
-    const float4 e24 = f4_fma(-45.f / 16, t[2], t[4]);                 // -45/16 t2 + t4
-    const float4 o13 = f4_fma(-45.f / 16, t[3], t[5]);                 // -45/16 t3 + t5
     const float4 ev1 = f4_fma(-9.f / 4, t[2], t[4]), od1 = f4_fma(-27.f / 16, t[1], f4_scale(3.f / 4, t[3]));
     const float4 ev2 = f4_fma(-9.f / 16, t[2], t[4]), od2 = f4_fma(-27.f / 32, t[1], f4_scale(3.f / 2, t[3]));
-    *reinterpret_cast<float4*>(vb + (size_t)(r * 6 + 0) * plane) = f4_fma(81.f / 64, t[0], e24);
+    if constexpr (!SC) {
+      const float4 e24 = f4_fma(-45.f / 16, t[2], t[4]);               // -45/16 t2 + t4
+      const float4 o13 = f4_fma(-45.f / 16, t[3], t[5]);               // -45/16 t3 + t5
+      *reinterpret_cast<float4*>(vb + (size_t)(r * 6 + 0) * plane) = f4_fma(81.f / 64, t[0], e24);
+      *reinterpret_cast<float4*>(vb + (size_t)(r * 6 + 5) * plane) = f4_fma(81.f / 64, t[1], o13);
+    }
     *reinterpret_cast<float4*>(vb + (size_t)(r * 6 + 1) * plane) = RIB_F4_ADD(ev1, od1);
     *reinterpret_cast<float4*>(vb + (size_t)(r * 6 + 2) * plane) = RIB_F4_SUB(ev1, od1);
     *reinterpret_cast<float4*>(vb + (size_t)(r * 6 + 3) * plane) = RIB_F4_ADD(ev2, od2);
     *reinterpret_cast<float4*>(vb + (size_t)(r * 6 + 4) * plane) = RIB_F4_SUB(ev2, od2);
-    *reinterpret_cast<float4*>(vb + (size_t)(r * 6 + 5) * plane) = f4_fma(81.f / 64, t[1], o13);
   }
+}
+
+template <int MODE, int MODE2 = -1>
+__global__ __launch_bounds__(256) void k_wino4_in(const WinoInParams p) {
+  __shared__ double red[4 * 64 * 2];
+  __shared__ float s_sc[64], s_sh[64];
+  const int slice = blockIdx.x % p.nslices, ub = blockIdx.x / p.nslices;
+  if constexpr (MODE2 >= 0) {
+    const int n1 = p.nslices - p.nslices2;
+    if (slice >= n1) { wino4_in_slice<MODE2, true>(wino_second(p), slice - n1, ub, red, s_sc, s_sh); return; }
+  }
+  wino4_in_slice<MODE, false>(p, slice, ub, red, s_sc, s_sh);
 }
 
 // grid (ublocks * nslices, B); thread = ((tile, output row r of the 4x4 tile), 4 channels of the slice)

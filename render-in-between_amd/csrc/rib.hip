@@ -163,6 +163,7 @@ struct ConvDef {
   // blob, made on the device from the folded filters when a plan first needs one (WinoSet, ensure_wino_set); zero_off: a
   // zero bias vector for the batched GEMM (the real bias is added by the output transform)
   bool wino_ok = false; size_t zero_off = 0;
+  bool wino_s_ok = false;   // conv_block_1 of a learned-shortcut block: may run in the Winograd domain with the shortcut fused in (no blob space)
   size_t wl_off = 0; int lowc_ce = 0, lowc_ncol = 0;   // k_conv_lowc filter [9*CE/KG][KG][NCOL] (real-channel K order), CE / NCOL of its instantiation
 };
 
@@ -521,10 +522,11 @@ struct Op {
   bool wino = false;   // this GEMM launch is the 16- / 36-way batched Winograd-domain GEMM (executes 4/9 or 1/4 of its nine-tap FLOP count)
   int wino_m = 0;      // 2 or 4 on the three launches of a Winograd convolution
   int wi_mode = 0;     // k_wino_in: WSRC_PLAIN / WSRC_SPADE / WSRC_JOIN
+  int wi_mode2 = -1;   // k_wino_in with a second source (the 1x1 shortcut's input): WSRC_PLAIN / WSRC_SPADE; -1: none
   int lowc_ce = 0, lowc_ncol = 0, lowc_tw = 32;
   OpParams params;
   struct Binding { PRef ref; unsigned field = 0; };      // field: byte offset of the pointer inside `params`
-  static constexpr int kMaxBindings = 24;            // (the largest families, k_igemm and k_wino_in, have 18 pointers)
+  static constexpr int kMaxBindings = 24;            // (the largest families, k_wino_in and k_igemm, have 20 and 18 pointers)
   Binding binds[kMaxBindings];
   int nbinds = 0;
 
@@ -639,9 +641,10 @@ struct rib_handle {
   // Winograd-domain filter sets U = G g G^T, [positions][CoutPad][CinPad] fp32 each, made on the device from the folded
   // filters of the blob when a plan first asks for one (round 3: they were 391 of the blob's 514 MB, both sets of every layer,
   // folded on the host, uploaded and broadcast; a 512x512 frame uses 17 of the 34)
-  struct WinoSet { int conv = 0, wm = 0; float* d = nullptr; size_t floats = 0; };
+  // aux >= 0: the set also carries the 1x1 shortcut convolution `aux` as extra K columns (rows of cinp + its cinp floats)
+  struct WinoSet { int conv = 0, wm = 0; float* d = nullptr; size_t floats = 0; int aux = -1; };
   std::vector<WinoSet> wino_sets;
-  std::map<std::pair<int, int>, int> wino_index;
+  std::map<std::array<int, 3>, int> wino_index;      // (conv, wm, aux)
   bool weights_ready = false;
   int prec_mode = PREC_F32;    // rib_set_compute_dtype: PREC_BF16 / PREC_F16 = 16-bit storage + 16-bit matrix-core operands
   int prec() const { return prec_mode; }
@@ -724,7 +727,8 @@ const ConvDef& conv_of(const rib_handle* h, const std::string& name) {
 // rows / columns are zeros and stay zeros).  fp64 with the roundings of the plain expression (no contraction), stored fp32.
 // F(2x2): G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1].  F(4x4): Cook-Toom with the points {0, +-3/4, +-3/2, inf}
 // (kernels.hip.h, k_wino4_in): G[j] = (1, a_j, a_j^2) / prod_{k != j} (a_j - a_k), last row (0, 0, 1).
-__global__ __launch_bounds__(256) void k_wino_filters(const float* w, float* u, int coutp, int cinp, int wm) {
+// ldu: floats of a row of U (cinp, or cinp + the channels of a fused 1x1 shortcut: k_wino_filters_1x1 fills that tail)
+__global__ __launch_bounds__(256) void k_wino_filters(const float* w, float* u, int coutp, int cinp, int wm, int ldu) {
 #pragma clang fp contract(off)
   const double G2[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
   const double G4[6][3] = {{64.0 / 81, 0, 0},
@@ -745,7 +749,25 @@ __global__ __launch_bounds__(256) void k_wino_filters(const float* w, float* u, 
   for (int r = 0; r < T; ++r)
     for (int q = 0; q < T; ++q) {
       const double* Gq = wm == 2 ? G2[q] : G4[q];
-      u[((size_t)(r * T + q) * coutp + o) * cinp + i] = (float)(t[r][0] * Gq[0] + t[r][1] * Gq[1] + t[r][2] * Gq[2]);
+      u[((size_t)(r * T + q) * coutp + o) * ldu + i] = (float)(t[r][0] * Gq[0] + t[r][1] * Gq[1] + t[r][2] * Gq[2]);
+    }
+}
+// The learned 1x1 shortcut of a res block as extra K columns of conv_block_1's set: a 1x1 filter is the 3x3 filter with only
+// its centre tap, so U_s[r][q] = (G[r][1] w) G[q][1] - zero wherever r or q is a first / last row of G (12 of 16 / 20 of 36
+// positions: the GEMM never reads those, GemmDmaParams::kmask).  w: [coutp][cin2] (the blob's 1x1 layout), columns col0.. of U.
+__global__ __launch_bounds__(256) void k_wino_filters_1x1(const float* w, float* u, int coutp, int cin2, int wm, int ldu, int col0) {
+#pragma clang fp contract(off)
+  const double G2c[4] = {0, 0.5, -0.5, 0};
+  const double G4c[6] = {0, -32.0 / 81, 32.0 / 81, 16.0 / 81, -16.0 / 81, 0};
+  const int T = wm + 2;
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (size_t)coutp * cin2) return;
+  const int o = (int)(idx / cin2), i = (int)(idx % cin2);
+  const double g = (double)w[(size_t)o * cin2 + i];
+  for (int r = 0; r < T; ++r)
+    for (int q = 0; q < T; ++q) {
+      const double gr = wm == 2 ? G2c[r] : G4c[r], gq = wm == 2 ? G2c[q] : G4c[q];
+      u[((size_t)(r * T + q) * coutp + o) * ldu + col0 + i] = (float)((gr * g) * gq);
     }
 }
 
@@ -755,19 +777,26 @@ int fill_wino_set(rib_handle* h, int si, hipStream_t st) {
   const ConvDef& c = h->convs[ws.conv];
   if (!ws.d || !h->d_blob) return RIB_OK;
   const size_t n = (size_t)c.coutp * c.cinp;
-  RIB_KLAUNCH(k_wino_filters, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, h->d_blob + c.w_off, ws.d, c.coutp, c.cinp, ws.wm);
+  const int k2 = ws.aux >= 0 ? h->convs[ws.aux].cinp : 0;
+  RIB_KLAUNCH(k_wino_filters, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, h->d_blob + c.w_off, ws.d, c.coutp, c.cinp, ws.wm, c.cinp + k2);
   HIP_TRY(h, hipGetLastError());
+  if (k2) {
+    const size_t n2 = (size_t)c.coutp * k2;
+    RIB_KLAUNCH(k_wino_filters_1x1, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, h->d_blob + h->convs[ws.aux].w_off, ws.d, c.coutp, k2, ws.wm, c.cinp + k2, c.cinp);
+    HIP_TRY(h, hipGetLastError());
+  }
   return RIB_OK;
 }
 
 // index of the F(wm x wm) filter set of conv `ci`, created on first use (plan build): device memory + the transform when the
 // weights are already there.  Synchronises the device (before and after the transform) once per new set: plan builds are
 // one-time work, and include/rib.h says so for every entry point that can build a plan.  < 0: error (h->err).
-int ensure_wino_set(rib_handle* h, int ci, int wm) {
-  auto it = h->wino_index.find({ci, wm});
+int ensure_wino_set(rib_handle* h, int ci, int wm, int aux = -1) {
+  auto it = h->wino_index.find({ci, wm, aux});
   if (it != h->wino_index.end()) return it->second;
   const ConvDef& c = h->convs[ci];
-  rib_handle::WinoSet ws; ws.conv = ci; ws.wm = wm; ws.floats = (size_t)(wm + 2) * (wm + 2) * c.coutp * c.cinp;
+  rib_handle::WinoSet ws; ws.conv = ci; ws.wm = wm; ws.aux = aux;
+  ws.floats = (size_t)(wm + 2) * (wm + 2) * c.coutp * (c.cinp + (aux >= 0 ? h->convs[aux].cinp : 0));
   if (h->device >= 0) {
     hipError_t e = hipSetDevice(h->device);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&ws.d), ws.floats * sizeof(float));
@@ -775,7 +804,7 @@ int ensure_wino_set(rib_handle* h, int ci, int wm) {
   }
   const int si = (int)h->wino_sets.size();
   h->wino_sets.push_back(ws);
-  h->wino_index[{ci, wm}] = si;
+  h->wino_index[{ci, wm, aux}] = si;
   if (h->device >= 0 && h->weights_ready) {
     // the blob may still be landing on a (non-blocking) stream of the caller's - rib_import_weights returns behind an
     // asynchronous copy - and the NULL stream does not order against such a stream: drain the device first, then transform
@@ -877,13 +906,15 @@ void assign_weight_layout(rib_handle* h) {
     }
     for (auto& sg : h->spades) sg.b_off = take(sg.npad);
   }
-  for (auto& c : h->convs) { c.wino_ok = false; c.zero_off = 0; }
+  for (auto& c : h->convs) { c.wino_ok = false; c.wino_s_ok = false; c.zero_off = 0; }
   if (h->prec() == PREC_F32 && !getenv("RIB_NO_WINO")) {
     // 3x3 stride-1 convolutions with >= 128 input channels that own their launch (no fused 1x1 shortcut, no upsampled
     // input): the deep residual blocks of the generator and of the mask network
     for (auto& c : h->convs) {
       // (measured per layer at 512x512, transforms included: 512->512 at 32x32 58 -> 38 us, 256->256 at 64x64 47-52 -> 42 us,
       // 512->256 at 64x64 95 -> 63 us; 128->128 at 64x64 gains nothing: the two transforms cost ~13 us per layer)
+      // (with a fused 1x1 shortcut: eligible at any width - only a measured table entry switches such a layer over)
+      if (c.used && c.ks == 3 && c.stride == 1 && !c.ups_in && c.fb_off != 0 && c.cout >= 64 && c.cinp % 32 == 0 && 128 % (c.coutp / 4) == 0) c.wino_s_ok = true;
       if (!c.used || c.ks != 3 || c.stride != 1 || c.ups_in || c.fb_off != 0 || c.cin < 256 || c.cout < 64 || c.cinp % 32 || 128 % (c.coutp / 4)) continue;
       // the plan picks F(4x4) or F(2x2) per layer from the map size (conv_wino) and asks for that filter set then
       c.wino_ok = true;
@@ -1013,6 +1044,11 @@ struct FusionPolicy {
   bool lazy_sources = !getenv("RIB_NO_LAZY");
   // the learned 1x1 shortcut of a res block as extra K chunks of conv_block_1 (one launch less, no shortcut tensor)
   bool fuse_shortcut = !getenv("RIB_NO_FUSE_SHORTCUT");
+  // conv_block_1 of a learned-shortcut block in the Winograd domain, the shortcut as extra K columns at the centre-tap positions
+  // (Builder::shortcut_wino_m).  On only where the tuned table has an entry for the layer's .wino / .wino4 launch - shapes nobody
+  // measured keep the direct launch; RIB_NO_WINO_SHORTCUT=1: nowhere; RIB_WINO_SHORTCUT_M=2 / 4: wherever eligible, that tile
+  bool wino_shortcut = !getenv("RIB_NO_WINO_SHORTCUT");
+  int wino_shortcut_m = getenv("RIB_WINO_SHORTCUT_M") ? atoi(getenv("RIB_WINO_SHORTCUT_M")) : 0;
   // buffers with disjoint lifetimes share workspace bytes (assign_physical)
   bool ws_reuse = !getenv("RIB_NO_WS_REUSE");
   // level i of the mask network's label encoder and of its image encoder in ONE paired launch (batch-1 frame plans).
@@ -1162,10 +1198,26 @@ struct Builder {
   // Winograd F(2x2, 3x3) / F(4x4, 3x3) on the small maps (k_wino_in / batched 1x1 k_igemm / k_wino_out; kernels.hip.h):
   // maps up to 128x128 (1024x1024 frames: +3.5 % at batch 1 and 4); beyond that V and M (4x the activation each)
   // leave the caches and the direct kernel, which fills the chip there, was not beaten
-  bool runs_wino(const ConvArgs& a, int Hout, int Wout) const {
+  // (opname: of a convolution with a fused shortcut - the tuned table decides for those, shortcut_wino_m)
+  bool runs_wino(const ConvArgs& a, int Hout, int Wout, const std::string& opname = std::string()) const {
     const ConvDef& c = *a.cd;
-    return h->prec() == PREC_F32 && c.wino_ok && !a.ups && !a.aux && !a.res_ups && !a.pair && !a.in.virt && a.y_nchw.sp == PS_NULL &&
-           a.y_user.sp == PS_NULL && (long)Hout * Wout <= pol.wino_max_px && Hout >= 2 && Wout >= 2;
+    return h->prec() == PREC_F32 && (a.aux ? c.wino_s_ok : c.wino_ok) && !a.ups && !a.res_ups && !a.pair && !a.in.virt && a.y_nchw.sp == PS_NULL &&
+           a.y_user.sp == PS_NULL && (long)Hout * Wout <= pol.wino_max_px && Hout >= 2 && Wout >= 2 &&
+           (!a.aux || (!a.res && shortcut_wino_m(c, *a.aux, opname, Hout, Wout) != 0));
+  }
+  // F(4x4, 3x3) where its per-position GEMM still has >= 256 rows (conv_wino), else F(2x2, 3x3)
+  int default_wino_m(int Hout, int Wout) const { return (long)TB_() * ((Hout + 3) / 4) * ((Wout + 3) / 4) >= 256 ? 4 : 2; }
+  // Winograd tile (2 / 4) of a 3x3 convolution with its learned 1x1 shortcut fused in, 0: it stays a direct launch.  The cost
+  // model keeps the direct launch; a tuned entry for "<op>.wino" or "<op>.wino4" of this shape (its variant: the GEMM tile)
+  // switches the layer over.  The batched GEMM with a K extent per position exists in k_gemm_dma only.
+  int shortcut_wino_m(const ConvDef& c, const ConvDef& s, const std::string& opname, int Hout, int Wout) const {
+    if (!pol.wino_shortcut || !pol.fuse_shortcut || opname.empty() || !c.fb_off || s.ks != 1 || s.coutp != c.coutp || s.cinp % 32 != 0 || c.cinp % 32 != 0) return 0;
+    if (!pick_gemm_dma(h->prec(), 16, 64, c.coutp, c.cinp)) return 0;
+    if (pol.wino_shortcut_m == 2 || pol.wino_shortcut_m == 4) return pol.wino_shortcut_m;
+    const int d = default_wino_m(Hout, Wout);
+    for (int m : {d, 6 - d})
+      if (h->choices.count(fmt("%d,%d,%d|%s%s", TB_(), P->H, P->W, opname.c_str(), m == 2 ? ".wino" : ".wino4"))) return m;
+    return 0;
   }
   // would conv `cd` on an HxW map (stride 1, plain arguments) run in the Winograd domain?  (callers that want to hand it a lazy input)
   bool would_wino(const ConvDef& cd, int H, int W) const { ConvArgs t; t.cd = &cd; return runs_wino(t, H, W); }
@@ -1185,8 +1237,9 @@ struct Builder {
       }
     }
     if (a.in.Cp != c.cinp) { error = fmt("%s: input channels %d != expected %d", opname.c_str(), a.in.Cp, c.cinp); return false; }
-    if (runs_wino(a, Hout, Wout)) return conv_wino(a, opname, Hout, Wout);
+    if (runs_wino(a, Hout, Wout, opname)) return conv_wino(a, opname, Hout, Wout);
     if (a.in.lazy) { error = opname + ": a lazy input (" + a.in.lazy->name + ") needs the Winograd path"; return false; }
+    if (a.aux && a.aux_in.lazy) { error = opname + ": a lazy shortcut input (" + a.aux_in.lazy->name + ") needs the Winograd path"; return false; }
     // split-K needs the slab-summing epilogue: float4 channel groups that tile a 256-thread block,
     // and no NCHW side copy
     const bool can_split = (256 % (c.coutp / 4) == 0) && a.y_nchw.sp == PS_NULL && !a.pair && !a.no_split && pol.split_k;
@@ -1366,17 +1419,24 @@ struct Builder {
     // 256->256 at 64x64 42.4 -> 37.3 us, 512->256 at 64x64 67.4 -> 56.2; 512->512 at 32x32 38.3 -> 41.0 (kept on F(2x2)).
     // RIB_WINO_M = 2 / 4 forces one of them.
     const int wino_force = pol.wino_force;
-    const int wm = wino_force == 2 || wino_force == 4 ? wino_force : ((long)TB_() * ((Hout + 3) / 4) * ((Wout + 3) / 4) >= 256 ? 4 : 2);
+    const int wm = a.aux ? shortcut_wino_m(c, *a.aux, opname, Hout, Wout) : (wino_force == 2 || wino_force == 4 ? wino_force : default_wino_m(Hout, Wout));
     const int NP = (wm + 2) * (wm + 2);      // output tile edge, Winograd positions
     const int tilesY = (Hout + wm - 1) / wm, tilesX = (Wout + wm - 1) / wm, ntiles = tilesY * tilesX;
     const std::string gname = opname + (wm == 2 ? ".wino" : ".wino4");
-    const size_t v_off = alloc((size_t)B * NP * ntiles * c.cinp * sizeof(float));
+    // a fused 1x1 shortcut: K2 more columns in every row of V and U, written / read at the centre-tap positions only (kmask)
+    const int K2 = a.aux ? a.aux->cinp : 0, ldv = c.cinp + K2;
+    unsigned long long kmask = 0;
+    if (a.aux) {
+      if (a.aux_in.Cp != K2 || a.aux_in.H != Hout || a.aux_in.W != Wout || a.in.H != Hout || a.in.W != Wout) { error = opname + ": fused shortcut operand does not fit"; return false; }
+      for (int r = 1; r <= wm; ++r) for (int q = 1; q <= wm; ++q) kmask |= 1ull << (r * (wm + 2) + q);
+    }
+    const size_t v_off = alloc((size_t)B * NP * ntiles * ldv * sizeof(float));
     const size_t m_off = alloc((size_t)B * NP * ntiles * c.coutp * sizeof(float));
     {   // input transform (with the convolution's prologue)
       OpOf<WinoInParams> op(RIB_KC_CONVAUX, opname + ".wino_in"); op.for_op = gname; op.wino_m = wm;
       WinoInParams& wi = op.p();
       wi.H = a.in.H; wi.W = a.in.W; wi.xC = a.in.Cp; wi.Cin = c.cinp; wi.tilesY = tilesY; wi.tilesX = tilesX;
-      wi.pro_lrelu = a.pro_lrelu ? 1 : 0;
+      wi.pro_lrelu = a.pro_lrelu ? 1 : 0; wi.ldv = ldv;
       op.bind(&WinoInParams::x, WS(a.in.off)); op.bind(&WinoInParams::v, WS(v_off));
       if (a.in.lazy) {
         const LazySrc& L = *a.in.lazy;
@@ -1401,8 +1461,21 @@ struct Builder {
         wi.pro_ld = a.pro->ld;
         op.bind(&WinoInParams::pro_scale, WS(a.pro->sc + a.pro_choff * sizeof(float))); op.bind(&WinoInParams::pro_shift, WS(a.pro->sh + a.pro_choff * sizeof(float)));
       }
+      if (a.aux) {      // second source: the shortcut's input, stored or the never-stored second set of the block's first SPADE
+        if (op.wi_mode == WSRC_JOIN) { error = gname + ": a join cannot carry a second source"; return false; }
+        wi.nslices2 = (K2 + 63) / 64; wi.Cin2 = K2; wi.xC2 = a.aux_in.Cp;
+        op.wi_mode2 = WSRC_PLAIN;
+        if (a.aux_in.lazy) {
+          const LazySrc& L = *a.aux_in.lazy;
+          if (L.mode != WSRC_SPADE) { error = gname + ": lazy shortcut input of an unknown kind"; return false; }
+          op.wi_mode2 = WSRC_SPADE;
+          op.bind(&WinoInParams::x2, WS(L.x.off)); wi.xC2 = L.x.Cp; wi.pro2_ld = L.nx.ld; wi.x2_ups = L.x_ups ? 1 : 0; wi.lrelu2 = L.lrelu ? 1 : 0;
+          if (!take_partials(L.nx, op, &WinoInParams::st2)) { materialize(L.nx, gname); op.bind(&WinoInParams::pro2_scale, WS(L.nx.sc)); op.bind(&WinoInParams::pro2_shift, WS(L.nx.sh)); }
+          op.bind(&WinoInParams::slab2, WS(L.slab_off)); wi.slab2_ld = L.slab_ld; wi.col0_2 = L.col0; op.bind(&WinoInParams::sbias2, WT(L.sbias_off));
+        } else op.bind(&WinoInParams::x2, WS(a.aux_in.off));
+      }
       // workgroup = (16 (tile, transformed row) units per pass) x (slice of 64 channels)
-      const int nsl = (c.cinp + 63) / 64, units = ntiles * (wm + 2);
+      const int nsl = (c.cinp + 63) / 64 + wi.nslices2, units = ntiles * (wm + 2);
       // (every workgroup that reduces partials re-reads tiles x 64 channels x 16 bytes: few, fatter workgroups then)
       wi.nslices = nsl; wi.ublocks = std::max(1, std::min((units + 15) / 16, (wi.st.tiles > 0 ? 512 : 4096) / nsl));
       op.grid = dim3(wi.ublocks * nsl, B, 1);
@@ -1416,23 +1489,26 @@ struct Builder {
       auto it = h->choices.find(fmt("%d,%d,%d|%s", TB_(), P->H, P->W, gname.c_str()));
       if (it != h->choices.end()) {
         const Variant& tv = kVariants[it->second.first];
-        if (tv.BF16 != h->prec() || tv.KS != 1 || tv.STRIDE != 1 || tv.UPS || tv.SPADE || tv.NF == 0 || c.cinp % tv.BK != 0 || it->second.second != 1) {
+        if (tv.BF16 != h->prec() || tv.KS != 1 || tv.STRIDE != 1 || tv.UPS || tv.SPADE || tv.NF == 0 || c.cinp % tv.BK != 0 || it->second.second != 1 || (a.aux && !tv.dma())) {
           error = fmt("%s: tuned choice (variant %d, ksplit %d) does not fit this layer", gname.c_str(), it->second.first, it->second.second); return false;
         }
         ch.v = &tv; ch.ksplit = 1;
       }
       const Variant* v = ch.v;
       if (!v) { error = gname + ": no 1x1 kernel variant"; return false; }
-      const int set = ensure_wino_set(h, (int)(&c - h->convs.data()), wm);
+      if (a.aux && !v->dma()) { error = gname + ": the fused shortcut needs a k_gemm_dma tile"; return false; }
+      const int set = ensure_wino_set(h, (int)(&c - h->convs.data()), wm, a.aux ? (int)(a.aux - h->convs.data()) : -1);
       if (set < 0) { error = gname + ": " + h->err; return false; }
-      const double fl = 2.0 * c.cin * 9.0 * c.cout * (double)Hout * Wout * B;      // the convolution's algorithmic count (executed: 4/9 or 1/4 of it)
+      // the convolution's algorithmic count (executed: 4/9 or 1/4 of it) + the shortcut's (executed as it is)
+      const double fl = 2.0 * c.cin * 9.0 * c.cout * (double)Hout * Wout * B + (a.aux ? 2.0 * a.aux->cin * a.aux->cout * (double)Hout * Wout * B : 0.0);
       P->flops[RIB_KC_IGEMM] += fl;
       if (v->dma()) {
         // M[n*NP + xi] = V[n*NP + xi] . U[xi]^T: Z = B*NP problems of ntiles x coutp x cinp
         OpOf<GemmDmaParams> op(RIB_KC_IGEMM, gname); op.var = v; op.wino = true; op.wino_m = wm; op.flops = fl;
         GemmDmaParams& g = op.p();
-        g.M = ntiles; g.N = c.coutp; g.K = c.cinp; g.lda = c.cinp; g.ldc = c.coutp;
-        g.sA = (size_t)ntiles * c.cinp; g.sB = (size_t)c.coutp * c.cinp; g.sC = (size_t)ntiles * c.coutp; g.modB = NP;
+        g.M = ntiles; g.N = c.coutp; g.K = c.cinp; g.lda = ldv; g.ldc = c.coutp;
+        g.sA = (size_t)ntiles * ldv; g.sB = (size_t)c.coutp * ldv; g.sC = (size_t)ntiles * c.coutp; g.modB = NP;
+        g.K2 = K2; g.kmask = kmask;
         op.bind(&GemmDmaParams::A, WS(v_off)); op.bind(&GemmDmaParams::B, WINO(set)); op.bind(&GemmDmaParams::C, WS(m_off));
         op.grid = dim3((ntiles + v->BM() - 1) / v->BM(), (c.coutp + v->BN() - 1) / v->BN(), B * NP);
         push(op);
@@ -1459,7 +1535,7 @@ struct Builder {
       wo.yC = a.out.Cp; wo.yoff = a.yoff; wo.Cout = a.cout_store >= 0 ? a.cout_store : h->padc(c.cout);
       wo.Hout = Hout; wo.Wout = Wout; wo.act = a.act;
       if (a.out.H != Hout || a.out.W != Wout) { error = fmt("%s: output size mismatch", opname.c_str()); return false; }
-      op.bind(&WinoOutParams::m, WS(m_off)); op.bind(&WinoOutParams::bias, WT(c.b_off)); op.bind(&WinoOutParams::y, WS(a.out.off));
+      op.bind(&WinoOutParams::m, WS(m_off)); op.bind(&WinoOutParams::bias, WT(a.aux ? c.fb_off : c.b_off)); op.bind(&WinoOutParams::y, WS(a.out.off));
       if (a.res) { op.bind(&WinoOutParams::res, WS(a.res->off)); wo.resC = a.res->Cp; }
       size_t part_off = 0;
       if (a.want_stats) { part_off = alloc((size_t)B * blocks * 2 * c.coutp * sizeof(double)); op.bind(&WinoOutParams::stat_part, WS(part_off)); }
@@ -1537,9 +1613,11 @@ struct Builder {
 
   // ---- SPADE launch: ys0 (= lrelu(mod0(x))), optional ys1 (= mods(x), no activation) -------
   // lazy_ok: the only consumer of ys0 is a convolution that runs in the Winograd domain - when this SPADE is just a modulate
-  // of the level's gamma/beta slab (one set), ys0 is not stored: the convolution's input transform computes it (LazySrc)
+  // of the level's gamma/beta slab, ys0 is not stored: the convolution's input transform computes it (LazySrc).
+  // lazy1_ok: the same for ys1, the second set (the input of the learned shortcut, consumed by conv_block_1's input transform
+  // as its second source).  A set whose consumer needs it stored is produced by k_spade_modulate, for that set alone.
   bool spade(const std::string& key, const Act& cond, const Act& x, bool x_ups, const Norm& nx,
-             Act* ys0, Act* ys1, bool act0, bool lazy_ok = false) {
+             Act* ys0, Act* ys1, bool act0, bool lazy_ok = false, bool lazy1_ok = false) {
     const SpadeGroup& sg = h->spades[h->spade_index.at(key)];
     const int Hout = x_ups ? x.H * 2 : x.H, Wout = x_ups ? x.W * 2 : x.W;
     if (cond.H != Hout || cond.W != Wout) { error = fmt("%s: cond map %dx%d != %dx%d (SPADE resize must be the identity)", key.c_str(), cond.H, cond.W, Hout, Wout); return false; }
@@ -1577,17 +1655,26 @@ struct Builder {
     if (from_level) unfused = true;
     if (!unfused && !v) { error = "no SPADE variant"; return false; }
     const bool no_lazy = !pol.lazy_sources;
-    if (from_level && lazy_ok && sg.nsets == 1 && !h->keep_taps && !no_lazy && h->prec() == PREC_F32) {
+    // sets that are never stored; set 1 lies (Cp / 32) gamma/beta column groups of 64 behind set 0, in the slab and in the bias
+    const bool can_lazy = from_level && !h->keep_taps && !no_lazy && h->prec() == PREC_F32;
+    // (set 0 of a two-set SPADE only together with set 1: where conv_block_1 keeps its direct launch the plan stays as it was)
+    const bool lz1 = can_lazy && lazy1_ok && sg.nsets == 2 && sg.Cp % 32 == 0;
+    const bool lz0 = can_lazy && lazy_ok && (sg.nsets == 1 || lz1);
+    const int set1_col = sg.Cp / 32 * 64;
+    for (int set = 0; set < 2; ++set) {
+      if (!(set ? lz1 : lz0)) continue;
       auto L = std::make_shared<LazySrc>();
-      L->mode = WSRC_SPADE; L->name = key + ".spade.modulate"; L->x = x; L->nx = nx; L->x_ups = x_ups; L->lrelu = act0;
-      L->slab_off = lvl->second.off; L->slab_ld = lvl->second.ld; L->col0 = sg.col0; L->sbias_off = sg.b_off;
+      L->mode = WSRC_SPADE; L->name = key + ".spade.modulate"; L->x = x; L->nx = nx; L->x_ups = x_ups; L->lrelu = set ? false : act0;
+      L->slab_off = lvl->second.off; L->slab_ld = lvl->second.ld; L->col0 = sg.col0 + set * set1_col; L->sbias_off = sg.b_off + set * set1_col;
       Act y; y.C = sg.C; y.Cp = sg.Cp; y.H = Hout; y.W = Wout; y.lazy = L;
-      *ys0 = y;
-      return true;
+      *(set ? ys1 : ys0) = y;
     }
+    if (lz0 && (lz1 || sg.nsets == 1)) return true;
+    // the stored sets: both, or set 0 alone when only set 1 is lazy (a launch over the first set's columns)
+    const int mnsets = lz1 ? 1 : sg.nsets;
     if (unfused) {
       *ys0 = act(sg.C, Hout, Wout);
-      if (sg.nsets == 2) *ys1 = act(sg.C, Hout, Wout);
+      if (sg.nsets == 2 && !lz1) *ys1 = act(sg.C, Hout, Wout);
       int S = 1, slab_ld = 0, col0 = 0;
       size_t slab_off = 0;
       if (from_level) {
@@ -1610,7 +1697,7 @@ struct Builder {
       OpOf<ModulateParams> mo(RIB_KC_ELTWISE, key + ".spade.modulate");
       ModulateParams& mp = mo.p();
       mp.ksplit = S; mp.B = B; mp.slab_ld = slab_ld; mp.col0 = col0; mp.xmC = x.Cp; mp.xm_ups = x_ups ? 1 : 0;
-      mp.m_ld = nx.ld; mp.C = sg.Cp; mp.nsets = sg.nsets; mp.act0 = act0 ? ACT_LRELU : ACT_NONE; mp.act1 = ACT_NONE;
+      mp.m_ld = nx.ld; mp.C = sg.Cp; mp.nsets = mnsets; mp.act0 = act0 ? ACT_LRELU : ACT_NONE; mp.act1 = ACT_NONE;
       mp.Hout = Hout; mp.Wout = Wout;
       mo.bind(&ModulateParams::slab, WS(slab_off)); mo.bind(&ModulateParams::bias, WT(sg.b_off)); mo.bind(&ModulateParams::xm, WS(x.off));
       // a slice of 64 virtual channels lies inside one set when C is a multiple of 64: the modulate can then reduce the
@@ -1619,8 +1706,8 @@ struct Builder {
         materialize(nx, key + ".spade");
         mo.bind(&ModulateParams::m_scale, WS(nx.sc)); mo.bind(&ModulateParams::m_shift, WS(nx.sh));
       }
-      mo.bind(&ModulateParams::ys0, WS(ys0->off)); if (sg.nsets == 2) mo.bind(&ModulateParams::ys1, WS(ys1->off));
-      const int nsl = (sg.nsets * sg.Cp + 63) / 64;
+      mo.bind(&ModulateParams::ys0, WS(ys0->off)); if (mnsets == 2) mo.bind(&ModulateParams::ys1, WS(ys1->off));
+      const int nsl = (mnsets * sg.Cp + 63) / 64;
       mp.nslices = nsl; mp.pblocks = std::max(1, std::min((Hout * Wout + 15) / 16, (mp.st.tiles > 0 ? 384 : 2048) / nsl));
       mo.grid = dim3(mp.pblocks * nsl, B, 1);
       push(mo);
@@ -1666,23 +1753,24 @@ struct Builder {
     Act ys0, ys1;
     Act hbuf = act(c0.cout, Hout, Wout);
     Norm nh = norm(hbuf.Cp);
+    // learned shortcut (residual.py:98-108): its 1x1 convolution on SPADE_s(x) is fused into conv_block_1's launch as extra
+    // K chunks accumulating into the same output tile - of the direct kernel, or of the Winograd-domain GEMM (wino1 below)
+    const bool fuse_s = learned && pol.fuse_shortcut;
+    // conv_block_1 runs in the Winograd domain with an identity shortcut at the same resolution (the res blocks), or with a
+    // fused learned shortcut where the tuned table says so (shortcut_wino_m); both SPADE outputs it consumes are then lazy
+    bool wino1;
+    { ConvArgs t; t.cd = &c1;
+      if (fuse_s) t.aux = &conv_of(h, name + ".conv_block_s"); else { t.res = &x; t.res_ups = !learned && x_ups; }
+      wino1 = runs_wino(t, Hout, Wout, name + ".conv_block_1"); }
     { ConvArgs a; a.cd = &c0; a.out = hbuf; a.want_stats = true; a.stats_out = &nh;
-      if (!spade(name + ".0", cond, x, x_ups, nx, &ys0, &ys1, true, runs_wino(a, Hout, Wout))) return false;
+      if (!spade(name + ".0", cond, x, x_ups, nx, &ys0, &ys1, true, runs_wino(a, Hout, Wout), fuse_s && wino1)) return false;
       if (!ys0.lazy) tap(name + ".ys0", ys0);
       a.in = ys0;
       if (!conv(a, name + ".conv_block_0")) return false; }
     tap(name + ".h", hbuf);
     Act y1, dummy;
-    {
-      // conv_block_1 runs in the Winograd domain only with an identity shortcut at the same resolution (the res blocks)
-      ConvArgs t; t.cd = &c1; t.res = &x; t.res_ups = !learned && x_ups;
-      const bool lazy1 = !learned && runs_wino(t, Hout, Wout);
-      if (!spade(name + ".1", cond, hbuf, false, nh, &y1, &dummy, true, lazy1)) return false;
-    }
+    if (!spade(name + ".1", cond, hbuf, false, nh, &y1, &dummy, true, (!learned || fuse_s) && wino1)) return false;
     if (!y1.lazy) tap(name + ".y1", y1);
-    // learned shortcut (residual.py:98-108): its 1x1 convolution on SPADE_s(x) is fused into
-    // conv_block_1's launch as extra K chunks accumulating into the same output tile
-    const bool fuse_s = learned && pol.fuse_shortcut;
     Act outs;
     if (learned && !fuse_s) {
       const ConvDef& cs = conv_of(h, name + ".conv_block_s");
@@ -2261,7 +2349,16 @@ int run_plan(rib_handle* h, Plan* P, const Resolver& R, hipStream_t st, bool ski
       case OP_INADD: RIB_LAUNCH_ST(bf16, k_in_add, op.grid, dim3(256), 0, st, std::get<InAddParams>(params)); break;
       case OP_WINO_IN: {
         const WinoInParams& p = std::get<WinoInParams>(params);
-        if (op.wino_m == 4) {
+        if (op.wi_mode2 >= 0) {      // with the shortcut's input as a second source
+          const bool s1 = op.wi_mode == WSRC_SPADE, s2 = op.wi_mode2 == WSRC_SPADE;
+#define RIB_WINO_IN2(K)                                                                                     \
+          if (s1 && s2) RIB_KLAUNCH((K<WSRC_SPADE, WSRC_SPADE>), op.grid, dim3(256), 0, st, p);             \
+          else if (s1) RIB_KLAUNCH((K<WSRC_SPADE, WSRC_PLAIN>), op.grid, dim3(256), 0, st, p);              \
+          else if (s2) RIB_KLAUNCH((K<WSRC_PLAIN, WSRC_SPADE>), op.grid, dim3(256), 0, st, p);              \
+          else RIB_KLAUNCH((K<WSRC_PLAIN, WSRC_PLAIN>), op.grid, dim3(256), 0, st, p)
+          if (op.wino_m == 4) { RIB_WINO_IN2(k_wino4_in); } else { RIB_WINO_IN2(k_wino_in); }
+#undef RIB_WINO_IN2
+        } else if (op.wino_m == 4) {
           if (op.wi_mode == WSRC_SPADE) RIB_KLAUNCH(k_wino4_in<WSRC_SPADE>, op.grid, dim3(256), 0, st, p);
           else if (op.wi_mode == WSRC_JOIN) RIB_KLAUNCH(k_wino4_in<WSRC_JOIN>, op.grid, dim3(256), 0, st, p);
           else RIB_KLAUNCH(k_wino4_in<WSRC_PLAIN>, op.grid, dim3(256), 0, st, p);
@@ -3098,7 +3195,7 @@ static int launch_info_head(const Op& op, char* buf, size_t buflen) {
              op.wino ? (op.wino_m == 4 ? " wino4" : " wino") : "", (int)(op.var - kVariants), op.flops);      // (v<n>: index into rib_variant_info)
   else if (op.kind() == OP_GEMM)
     snprintf(buf, buflen, "%s|%d|%u,%u,%u|gemm (LDS-DMA staged operands) tile %dx%d BK 32, %d x [%d x %d x %d]%s|%.0f", op.name.c_str(), op.kclass, op.grid.x, op.grid.y, op.grid.z,
-             op.var->BM(), op.var->BN(), (int)op.grid.z, op.as<GemmDmaParams>().M, op.as<GemmDmaParams>().N, op.as<GemmDmaParams>().K, op.wino ? (op.wino_m == 4 ? " wino4" : " wino") : "", op.flops);
+             op.var->BM(), op.var->BN(), (int)op.grid.z, op.as<GemmDmaParams>().M, op.as<GemmDmaParams>().N, op.as<GemmDmaParams>().K, (std::string(op.wino ? (op.wino_m == 4 ? " wino4" : " wino") : "") + (op.as<GemmDmaParams>().K2 ? fmt(" + K %d of the 1x1 shortcut at %d positions", op.as<GemmDmaParams>().K2, __builtin_popcountll(op.as<GemmDmaParams>().kmask)) : std::string())).c_str(), op.flops);
   else if (op.kind() == OP_LOWC)
     snprintf(buf, buflen, "%s|%d|%u,%u,%u|lowc (caller's NCHW tensors, K = 9 x %d real channels) 8x%d tile, %d columns|%.0f", op.name.c_str(), op.kclass,
              op.grid.x, op.grid.y, op.grid.z, op.lowc_ce, op.lowc_tw, op.lowc_ncol, op.flops);
@@ -3140,7 +3237,10 @@ static double op_algorithmic_bytes(const rib_handle* h, const Plan* P, const Op&
     case OP_GEMM: {
       const GemmDmaParams& g = op.as<GemmDmaParams>();
       const double Z = op.grid.z;
-      return Z * g.M * (double)g.K * e + (g.modB ? (double)g.modB : 1.0) * g.N * (double)g.K * e + Z * g.M * (double)g.N * 4.0;
+      // (a fused shortcut: K2 more columns of both operands at the positions of kmask)
+      const double z2 = g.K2 ? Bn * __builtin_popcountll(g.kmask) : 0.0, nb2 = g.K2 ? (double)__builtin_popcountll(g.kmask) : 0.0;
+      return Z * g.M * (double)g.K * e + (g.modB ? (double)g.modB : 1.0) * g.N * (double)g.K * e + Z * g.M * (double)g.N * 4.0 +
+             z2 * g.M * (double)g.K2 * e + nb2 * g.N * (double)g.K2 * e;
     }
     case OP_LOWC: {
       const LowcParams& l = op.as<LowcParams>();
@@ -3162,6 +3262,10 @@ static double op_algorithmic_bytes(const rib_handle* h, const Plan* P, const Op&
       const int T = op.wino_m + 2;
       double b = Bn * w.H * w.W * (double)w.Cin * e / (w.x_ups ? 4.0 : 1.0) + Bn * w.tilesY * w.tilesX * (double)T * T * w.Cin * e;
       if (op.wi_mode != 0 && op.bound(&WinoInParams::slab)) b += Bn * w.H * w.W * 2.0 * w.Cin * 4.0;          // gamma/beta columns of the level slab
+      if (op.wi_mode2 >= 0) {      // second source: read once (+ its gamma/beta columns when it is a lazy SPADE), V at m x m positions
+        b += Bn * w.H * w.W * (double)w.Cin2 * e / (w.x2_ups ? 4.0 : 1.0) + Bn * w.tilesY * w.tilesX * (double)op.wino_m * op.wino_m * w.Cin2 * e;
+        if (op.bound(&WinoInParams::slab2)) b += Bn * w.H * w.W * 2.0 * w.Cin2 * 4.0;
+      } else
       if (op.bound(&WinoInParams::x2) || op.bound(&WinoInParams::xres)) b += Bn * w.H * w.W * (double)w.Cin * e * 2.0;               // join: second operand read, join stored
       return b;
     }
