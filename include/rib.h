@@ -209,6 +209,26 @@ int rib_rasterise(rib_handle* h, int T, int H, int W,
                   const rib_stroke* strokes, int n_edges, const uint8_t* colors_rgb, int stroke_halfwidth,
                   const int32_t* peaks, int n_maps, const double* weights, int radius,
                   float* labels, void* workspace, size_t workspace_bytes, void* hip_stream);
+/* ---- pose mask of the ground-truth metrics ----
+ * The reference measures PSNR / SSIM under the human-centric mask that _generate_human_mask draws from the frame's own
+ * keypoints (PGNR/datasets/HSM_auto_dataset.py:254-334, used at :390; PGNR/models/evaluator.py:118,122): cv2.circle, filled,
+ * on every valid joint (radius 30 on joint 0, 15 elsewhere) and cv2.line on every limb whose two joints are valid
+ * (thickness t = 30 for head / arms / legs, 40 for the three body lines; head (0,1), hand (1,2)(2,3)(3,4)(1,5)(5,6)(6,7),
+ * legs (8,9)(9,10)(10,11)(8,12)(12,13)(13,14), body (1,8)(2,9)(5,12), and for 19 joints also (4,18)(7,17)(11,16)(14,15)).
+ * Restated from OpenCV's drawing, unpinned (cv2 is not in this image); the definition is an exact integer one with OpenCV's
+ * structure.  Pixel (px, py) of frame t is 1.0 iff one of these holds, else 0.0:
+ *   disc   (px-Px)^2 + (py-Py)^2 <= R*R + R  for a valid joint P (R = 30 / 15) or an end point of a drawn limb (R = t/2);
+ *   slab   for a drawn limb A -> B with A != B, d = B-A, L2 = d.d, v = (px,py)-A, h = t/2:
+ *          0 <= v.d <= L2  and  4 (vx*dy - vy*dx)^2 <= (2h+1)^2 * L2
+ * i.e. the pixel centre lies within R + 1/2 of the point / within h + 1/2 of the segment: OpenCV sets the pixels on the ideal
+ * outline.  rasterise.human_mask is the same statement on the host, bit for bit (integers only, no floating point).
+ * peaks: HOST pointer [T][n_joints][2], the convention of the rasteriser's peaks ((x, y), x = -1: joint off); it is copied
+ * to page-locked staging memory of the handle before the call returns and sent on `stream`: the call only enqueues.
+ * mask [T,H,W] fp32 on the device, every element written; it is what the quality entry takes as its mask.  One launch, no
+ * atomics, no workspace: a frame's bytes do not depend on T.  n_joints other than 18 / 19, T < 1 (or > 65535), H or W
+ * outside 1..16384, a peak outside the frame, NULL pointers: RIB_ERR_INVALID with a rib_last_error text. */
+int rib_human_mask(rib_handle* h, int T, int H, int W, const int32_t* peaks, int n_joints,
+                   float* mask /* [T,H,W] device */, void* hip_stream);
 
 /* Extension op named by the north star but absent from the reference: bilinear
  * flow-grid warp, semantics of torch.nn.functional.grid_sample(img, base+flow*2/(size-1),

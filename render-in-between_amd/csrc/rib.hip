@@ -13,6 +13,7 @@
 #include "raster.hip.h"
 #include "quality.hip.h"
 #include "resize.hip.h"
+#include "human_mask.hip.h"
 #include <hip/hip_ext.h>
 #include "../../include/rib.h"
 
@@ -673,6 +674,11 @@ struct rib_handle {
   struct RasterStage { char* host = nullptr; size_t bytes = 0; hipEvent_t done = nullptr; };
   RasterStage raster_stage[2];
   int raster_next = 0;
+  // rib_human_mask: the same two-slot scheme for its peak table, with the device copy of the table beside the page-locked one (the
+  // entry takes no workspace); a slot's event follows the kernel that reads it
+  struct MaskStage { int32_t* host = nullptr; int32_t* dev = nullptr; size_t bytes = 0; hipEvent_t done = nullptr; };
+  MaskStage mask_stage[2];
+  int mask_next = 0;
   bool profiling = false;
   bool prof_kernels = false;   // rib_profile_begin_kernels: (start, stop) pairs bound to the dispatches instead of interval events
   std::vector<std::pair<int, hipEvent_t>> prof_events;   // (class of the launch behind the event, -1: end of a plan run)
@@ -2440,6 +2446,11 @@ void rib_destroy(rib_handle* h) {
   if (!h) return;
   drop_chain_graphs(h);
   for (auto& rs : h->raster_stage) { if (rs.host) (void)hipHostFree(rs.host); if (rs.done) (void)hipEventDestroy(rs.done); }
+  for (auto& ms : h->mask_stage) {
+    if (ms.done) { (void)hipEventSynchronize(ms.done); (void)hipEventDestroy(ms.done); }
+    if (ms.host) (void)hipHostFree(ms.host);
+    if (ms.dev) (void)hipFree(ms.dev);
+  }
   if (h->d_blob) (void)hipFree(h->d_blob);
   free_wino_sets(h);
   for (auto& pe : h->prof_events) (void)hipEventDestroy(pe.second);
@@ -2937,6 +2948,47 @@ int rib_rasterise(rib_handle* h, int T, int H, int W, const rib_stroke* strokes,
   sp.T = T; sp.H = H; sp.W = W; sp.label_nc = 3 + n_maps; sp.bw = stroke_halfwidth;
   RIB_KLAUNCH(k_skeleton, dim3(T), dim3(256), 0, st, sp);
   HIP_TRY(h, hipGetLastError());
+  return RIB_OK;
+}
+
+int rib_human_mask(rib_handle* h, int T, int H, int W, const int32_t* peaks, int n_joints, float* mask, void* hip_stream) {
+  if (!h) return RIB_ERR_INVALID;
+  if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_human_mask: host-only handle");
+  if (!peaks || !mask) return fail(h, RIB_ERR_INVALID, "rib_human_mask: null pointer");
+  if (n_joints != 18 && n_joints != 19) return fail(h, RIB_ERR_INVALID, fmt("rib_human_mask: a pose has 18 or 19 joints, got %d", n_joints));
+  if (T < 1 || T > 65535 || H < 1 || W < 1 || H > HMASK_MAX_SIDE || W > HMASK_MAX_SIDE)
+    return fail(h, RIB_ERR_INVALID, fmt("rib_human_mask: T=%d H=%d W=%d: 1 <= T <= 65535, H and W in 1..%d", T, H, W, HMASK_MAX_SIDE));
+  const size_t n = (size_t)T * n_joints;
+  for (size_t i = 0; i < n; ++i) {
+    const int32_t x = peaks[2 * i], y = peaks[2 * i + 1];
+    if (x >= W || (x >= 0 && (y < 0 || y >= H))) return fail(h, RIB_ERR_INVALID, fmt("rib_human_mask: peak %zu (%d, %d) outside the frame", i, x, y));
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  HIP_TRY(h, hipSetDevice(h->device));
+  rib_handle::MaskStage& ms = h->mask_stage[h->mask_next];
+  h->mask_next ^= 1;
+  if (ms.done) HIP_TRY(h, hipEventSynchronize(ms.done));        // the kernel that read this slot two calls ago
+  else HIP_TRY(h, hipEventCreateWithFlags(&ms.done, hipEventDisableTiming));
+  const size_t bytes = n * 2 * sizeof(int32_t);
+  if (ms.bytes < bytes) {
+    if (ms.host) (void)hipHostFree(ms.host);
+    if (ms.dev) (void)hipFree(ms.dev);
+    ms.host = ms.dev = nullptr; ms.bytes = 0;
+    const size_t cap = align256(bytes);
+    HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&ms.host), cap, hipHostMallocDefault));
+    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&ms.dev), cap));
+    ms.bytes = cap;
+  }
+  memcpy(ms.host, peaks, bytes);
+  HIP_TRY(h, hipMemcpyAsync(ms.dev, ms.host, bytes, hipMemcpyHostToDevice, st));
+  MaskParams mp;
+  mp.peaks = ms.dev; mp.mask = mask; mp.T = T; mp.H = H; mp.W = W; mp.nj = n_joints;
+  mp.tilesX = (W + HMASK_TW - 1) / HMASK_TW;
+  mp.vec = (W % 4 == 0 && (reinterpret_cast<uintptr_t>(mask) & 15) == 0) ? 1 : 0;
+  const int tilesY = (H + HMASK_TH - 1) / HMASK_TH;
+  RIB_KLAUNCH(k_human_mask, dim3(mp.tilesX * tilesY, T), dim3(256), 0, st, mp);
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipEventRecord(ms.done, st));
   return RIB_OK;
 }
 

@@ -30,7 +30,9 @@ Differences from the reference, none of which change a pixel:
 Ground-truth metrics (metrics=True with a gt_dir; the reference measures in evaluate_from_dataset, evaluator.py:113-134): every
 non-key frame (i % sample_rate != 0; at sample_rate 2 exactly the reference's rule, :116) is measured twice against gt_dir's
 frame i - its fused frame (OURS) and its DAIN frame (DAIN) - with compute_metrics' PSNR / SSIM (metrics.py), optionally under
-a mask from mask_dir/<clip>/.  The native path decodes the GT frame in the frame's own decode task, measures on the GPU
+a mask: files from mask_dir/<clip>/, or (pose_mask=True) the human-centric mask the reference measures under, drawn from the
+frame's own pose (rasterise.human_mask; on the native path by the HIP kernel behind Generator.human_mask, from the peak table the
+unit already carries).  The native path decodes the GT frame in the frame's own decode task, measures on the GPU
 (rib_quality) right after the unit's chain and brings the per-frame values home in the unit's one device-to-host copy.
 <save_dir>/metrics.json reports every clip (the reference keeps only the last clip's dict) and the mean over all frames.
 """
@@ -498,7 +500,7 @@ class Evaluator:
     # ---- the driver ------------------------------------------------------------------------------
     @torch.no_grad()
     def evaluate_from_folder(self, model, train_dir, dain_dir, pose_dir, save_dir, gt_dir=None, gen_vid=False,
-                             rank=None, world=None, metrics=False, mask_dir=None):
+                             rank=None, world=None, metrics=False, mask_dir=None, pose_mask=False):
         """rank / world: this process's share of the independent units (default: the torch.distributed process
         group when one is initialised, else everything).  Returns the frames THIS rank wrote.
         The call is one `_FolderPipeline` (below): plan a clip -> decode -> upload -> render -> sink, pipelined over units
@@ -506,7 +508,10 @@ class Evaluator:
         the GPU work.
         metrics=True (needs gt_dir): every non-key frame is measured against gt_dir's frame i, fused (OURS) and DAIN frame,
         optionally under mask_dir/<clip>/ masks (grayscale at the model size, > 127 -> 1); the per-frame records of all ranks
-        end up in self.metrics and <save_dir>/metrics.json (written by rank 0).  metrics=False changes nothing."""
+        end up in self.metrics and <save_dir>/metrics.json (written by rank 0).  metrics=False changes nothing.
+        pose_mask=True (with metrics, instead of mask_dir): the mask of a measured frame is the reference's human-centric mask
+        (_generate_human_mask restated from OpenCV's drawing, unpinned: rasterise.human_mask) of that frame's pose - on the
+        native path drawn by rib_human_mask on the upload stream, next to the label rasterisation; nothing is staged for it."""
         if gen_vid:
             # the reference also writes <save_dir>/<clip>.mp4 (evaluator.py:267-269, utils.make_video); not built, and
             # silently ignoring the flag would drop an output the caller asked for
@@ -515,6 +520,10 @@ class Evaluator:
             raise ValueError("evaluate_from_folder: metrics=True needs gt_dir (the ground-truth frames)")
         if mask_dir is not None and not metrics:
             raise ValueError("evaluate_from_folder: mask_dir is a setting of metrics=True")
+        if pose_mask and not metrics:
+            raise ValueError("evaluate_from_folder: pose_mask is a setting of metrics=True")
+        if pose_mask and mask_dir is not None:
+            raise ValueError("evaluate_from_folder: pose_mask and mask_dir are two sources of the one mask: give one of them")
         if rank is None or world is None:
             import torch.distributed as dist
             rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
@@ -523,7 +532,7 @@ class Evaluator:
             self._pool = ThreadPoolExecutor(self.io_threads)          # decode + encode workers
             self._finishers = ThreadPoolExecutor(max(4, self.lanes + 2))  # wait for a unit's copy, then fan out its encodes
         self.metrics = self.metrics_report = None
-        pipe = _FolderPipeline(self, model, rank, world, gt_dir, metrics=bool(metrics), mask_dir=mask_dir)
+        pipe = _FolderPipeline(self, model, rank, world, gt_dir, metrics=bool(metrics), mask_dir=mask_dir, pose_mask=bool(pose_mask))
         self.timings = pipe.tm
         if metrics and pipe.native:
             self._quality_model = model
@@ -598,12 +607,14 @@ class _FolderPipeline:
     host until its files exist, and the GPU renders faster than PNGs get written.  Every stage can be driven on its own
     (tests/test_driver.py)."""
 
-    def __init__(self, ev, model, rank, world, gt_dir, metrics=False, mask_dir=None):
+    def __init__(self, ev, model, rank, world, gt_dir, metrics=False, mask_dir=None, pose_mask=False):
         self.ev, self.model, self.rank, self.world, self.gt_dir = ev, model, rank, world, gt_dir
-        self.metrics, self.mask_dir = metrics, mask_dir
+        self.metrics, self.mask_dir, self.pose_mask = metrics, mask_dir, pose_mask
         self.native = hasattr(model, "chain") and hasattr(model, "quantise")
         if self.native and metrics and not hasattr(model, "quality"):
             raise RuntimeError("metrics=True: this model has no GPU quality kernel (rib_quality)")
+        if self.native and pose_mask and not hasattr(model, "human_mask"):
+            raise RuntimeError("pose_mask=True: this model has no GPU mask kernel (rib_human_mask)")
         if ev.resize_on == "gpu" and not (self.native and hasattr(model, "resize_u8")):
             raise RuntimeError("resize_on='gpu': this model has no GPU resize kernel (rib_resize_cubic)")
         self.gpu_labels = self.native and ev.label_fn is None and hasattr(model, "rasterise")
@@ -622,6 +633,12 @@ class _FolderPipeline:
         self._sizes = {}
 
     # ---- helpers --------------------------------------------------------------------------------------------------------
+    def peaks_of(self, pose):
+        """A decoded frame's pose -> its [19, 2] peak table: the rasteriser tables carry it; (landmarks, conf) go through peak_table."""
+        if self.gpu_labels:
+            return pose[1]
+        return rasterise.peak_table(pose[0], pose[1], self.ev.height, self.ev.width, self.ev.skeleton_thres)
+
     def image_size(self, path):              # header only; the keypoints scale with THIS image
         if path not in self._sizes:
             from PIL import Image
@@ -833,6 +850,8 @@ class _FolderPipeline:
                     gtf = ((gtf / 255.0 - 0.5) / 0.5).reshape(Tc * Bc, 3, ev.height, ev.width).contiguous()
                 mk = (clip.stage_mask[ui].to(g.device, non_blocking=True).to(torch.float32).reshape(Tc * Bc, ev.height, ev.width)
                       if ui in clip.stage_mask else None)
+                if self.pose_mask:             # drawn here from the unit's own peaks (rib_human_mask): no file, no staging
+                    mk = g.human_mask(np.stack([self.peaks_of(p_) for p_ in poses]), ev.height, ev.width)
                 clip.meas[ui] = (gtf, mk)
             ready = torch.cuda.Event()
             ready.record(self.up)
@@ -980,6 +999,8 @@ class _FolderPipeline:
                     gt_i = ev.load_image(clip.gtlist[i])[0].unsqueeze(0)
                     mk = (torch.from_numpy(io_worker.load_mask_u8(clip.mask_list[i], ev.width, ev.height)).float().unsqueeze(0)
                           if clip.mask_list is not None else None)
+                    if self.pose_mask:           # the host statement of the mask, from this frame's pose
+                        mk = torch.from_numpy(rasterise.human_mask(self.peaks_of(poses[t]), ev.height, ev.width)).float().unsqueeze(0)
                     for row, x in ((0, outs[t]), (2, dn[t])):
                         p_, s_ = _metrics.psnr_ssim(x.detach().cpu().float(), gt_i, mk)
                         vals[row, t], vals[row + 1, t] = float(p_[0]), float(s_[0])
@@ -1018,7 +1039,8 @@ class _FolderPipeline:
                                 measured_frames="every non-key frame (i % sample_rate != 0): its fused frame (OURS) and its DAIN "
                                                 "frame (DAIN) against gt_dir's frame i; at sample_rate 2 the reference's rule "
                                                 "(PGNR/models/evaluator.py:116)",
-                                mask=("mask_dir/<clip>/ grayscale at the model size, value > 127 -> 1" if self.mask_dir is not None else None),
+                                mask=("mask_dir/<clip>/ grayscale at the model size, value > 127 -> 1" if self.mask_dir is not None
+                                      else (_metrics.POSE_MASK if self.pose_mask else None)),
                                 clips_reported="every clip (the reference returns only the last clip's dict: it is overwritten per clip)"),
                "clips": {c: dict(_metrics.mean_record(pf), frames=len(pf), per_frame=pf) for c, pf in clips.items()},
                "overall": dict(_metrics.mean_record(recs), frames=len(recs))}

@@ -476,6 +476,37 @@ class Generator:
                 peaks.ctypes.data, P, weights.ctypes.data, radius, _ptr(out), _ptr(ws), ws.numel(), self._stream()))
         return out
 
+    def human_mask(self, peaks, height, width, out=None):
+        """The human-centric mask of the ground-truth metrics drawn on the GPU (rib_human_mask; _generate_human_mask restated
+        from OpenCV's drawing, unpinned - rasterise.human_mask states the definition and is bit-equal): peaks [T, n, 2] (or
+        [n, 2]) int host array of rasterise.peak_table, n = 18 or 19 -> float32 0/1 [T, H, W] on this device, enqueued on the
+        current stream; it is what `quality` takes as its mask.  out: optional contiguous destination of that shape."""
+        import numpy as np
+        from . import rasterise as R
+        if torch.is_tensor(peaks):
+            peaks = peaks.detach().cpu().numpy()
+        peaks = np.asarray(peaks)
+        if peaks.ndim == 2:
+            peaks = peaks[None]
+        if peaks.ndim != 3 or peaks.shape[2] != 2 or peaks.shape[0] < 1 or peaks.dtype.kind not in "iu":
+            raise ValueError("human_mask: peaks must be an integer [T, n, 2] array (rasterise.peak_table), got %s %s" % (peaks.dtype, peaks.shape))
+        R.mask_limbs(peaks.shape[1])                                 # 18 or 19 joints
+        height, width = int(height), int(width)
+        if not (1 <= height <= R.MASK_MAX_SIDE and 1 <= width <= R.MASK_MAX_SIDE):
+            raise ValueError("human_mask: height and width must be in 1..%d, got %dx%d" % (R.MASK_MAX_SIDE, height, width))
+        on = peaks[..., 0] >= 0
+        if np.any(peaks[..., 0] >= width) or np.any(on & ((peaks[..., 1] < 0) | (peaks[..., 1] >= height))):
+            raise ValueError("human_mask: a peak lies outside the %dx%d frame (peak_table gives (-1, -1) for such a joint)" % (height, width))
+        peaks = np.ascontiguousarray(peaks, np.int32)
+        T, n = peaks.shape[:2]
+        if out is None:
+            out = torch.empty((T, height, width), dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != (T, height, width) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("human_mask: out must be a contiguous float32 %s tensor on %s" % ((T, height, width), self.device))
+        with torch.cuda.device(self.device):
+            _native.check(self._h, self._lib.rib_human_mask(self._h, T, height, width, peaks.ctypes.data, n, _ptr(out), self._stream()))
+        return out
+
     # ---- introspection / measurement -----------------------------------------------------------
     def enable_taps(self, on=True):
         """Debug: keep every tapped intermediate intact until the end of a forward (buffers with disjoint lifetimes

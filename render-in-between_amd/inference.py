@@ -12,9 +12,10 @@ torch.distributed.run yourself).  Rank 0 reads and folds the checkpoint, the fol
 ONE RCCL broadcast, and the independent segments between key frames (PGNR/models/evaluator.py:240-244) of all clips
 (:169-171) are dealt round-robin to the ranks; every rank writes its own frames into the same output tree.
 
-Ground-truth metrics (new; the reference measures only in evaluate_from_dataset): `--gt-dir DIR --metrics [--mask-dir DIR]`
+Ground-truth metrics (new; the reference measures only in evaluate_from_dataset): `--gt-dir DIR --metrics [--mask-dir DIR | --pose-mask]`
 measures every generated frame and its DAIN frame against DIR/<clip>/ (PSNR / SSIM of Evaluator.compute_metrics) and writes
-<save-dir>/Generated_frames/metrics.json.
+<save-dir>/Generated_frames/metrics.json.  `--pose-mask` measures under the human-centric mask the reference measures under
+(_generate_human_mask, drawn from each frame's own pose on the GPU; restated from OpenCV's drawing, unpinned).
 """
 import argparse
 import os
@@ -111,7 +112,7 @@ def main(opts):
     pose_dir = os.path.join(opts.input_dir, "Predict_motion")
     save_dir = os.path.join(opts.save_dir, "Generated_frames")
     written = evaluator.evaluate_from_folder(net_G, train_dir, dain_dir, pose_dir, save_dir, gt_dir=opts.gt_dir, gen_vid=False,
-                                             metrics=opts.metrics, mask_dir=opts.mask_dir)
+                                             metrics=opts.metrics, mask_dir=opts.mask_dir, pose_mask=opts.pose_mask)
     print(summary_line(evaluator, rank, world))
     if world > 1:
         print("[rank {}/{}] wrote {} frames".format(rank, world, len(written)))
@@ -148,6 +149,10 @@ def build_parser():
                              "GPU); writes <save-dir>/Generated_frames/metrics.json (not in the reference's folder driver)")
     parser.add_argument("--mask-dir", type=str, default=None,
                         help="with --metrics: <mask-dir>/<clip>/ grayscale masks at the model size (value > 127 = measured pixel)")
+    parser.add_argument("--pose-mask", action="store_true",
+                        help="with --metrics, instead of --mask-dir: measure under the human-centric mask the reference measures under, "
+                             "drawn on the GPU from each frame's own pose json (_generate_human_mask: a disc on every joint, a thick line "
+                             "on every limb; restated from OpenCV's drawing, unpinned)")
     parser.add_argument("--resize-on", choices=("host", "gpu"), default="host",
                         help="where the DAIN frames (and, with --metrics, the ground-truth frames) are resized to the model size: 'host' "
                              "(default): by the file workers, as the reference does; 'gpu': decoded at their own size and resized by the "
@@ -165,6 +170,10 @@ def parse_args(argv=None):
         parser.error("--metrics needs --gt-dir (the ground-truth frames)")
     if opts.mask_dir is not None and not opts.metrics:
         parser.error("--mask-dir is a setting of --metrics")
+    if opts.pose_mask and not opts.metrics:
+        parser.error("--pose-mask is a setting of --metrics")
+    if opts.pose_mask and opts.mask_dir is not None:
+        parser.error("--pose-mask and --mask-dir are two sources of the one mask: give one of them")
     return opts
 
 

@@ -31,6 +31,8 @@ PROTOCOL = {"source": "PGNR/models/evaluator.py:149-163 compute_metrics, piq def
             "value_range": "frames in [-1,1] -> clamp(x*0.5+0.5, 0, 1) * mask", "psnr_data_range": 1.0, "psnr_eps": EPS,
             "ssim_data_range": 1.0, "ssim_window": WINDOW, "ssim_sigma": SIGMA, "ssim_k1": 0.01, "ssim_k2": 0.03,
             "ssim_downsample": "f = max(1, round(min(H,W)/256)), avg_pool2d(f)", "ssim_padding": "valid"}
+# the `mask` field of a report measured under pose_mask=True (rasterise.human_mask; PGNR/datasets/HSM_auto_dataset.py:254-334)
+POSE_MASK = "pose: _generate_human_mask restated from OpenCV's drawing, unpinned"
 
 
 def downsample_factor(H, W):

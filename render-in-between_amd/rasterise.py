@@ -7,8 +7,12 @@ What stays on the host is file parsing and per-limb scalar work:
   * stroke_table         keypoint2img.py:66-88,132-147      one fitted line per limb -> rib_stroke
   * peak_table           PGNR/datasets/HSM_auto_dataset.py:215-231   one-hot positions
   * gaussian_weights     the kernel scipy.ndimage.gaussian_filter builds (sigma, truncate 4)
-Every pixel is produced on the GPU.  There is no CPU rasteriser in the product: the CPU
-restatement lives in oracle/rasterise_ref.py and only the tests use it.
+  * human_mask           HSM_auto_dataset.py:254-334        the metrics' human-centric mask: the DEFINITION
+Every label pixel is produced on the GPU.  There is no CPU label rasteriser in the product: the CPU
+restatement lives in oracle/rasterise_ref.py and only the tests use it.  human_mask is the one host
+rasteriser here: it states the pose mask's integer definition, which csrc/human_mask.hip.h evaluates
+on the GPU (Generator.human_mask); the driver uses the host function only for models behind the
+reference's call protocol (CPU).
 
 Line fit.  A limb joins two joints, so the reference's curve_fit(linear, ...) has an exact
 answer, the line through them: a = dy/dx, b = y0 - a*x0.  curve_fit reaches it only to ~1e-12,
@@ -141,6 +145,81 @@ def peak_table(landmarks, conf, height, width, thres=0.001):
     for i, ((x, y), c) in enumerate(zip(landmarks, conf)):
         if x >= 0 and y >= 0 and c > thres and x < width and y < height:
             out[i] = (int(x), int(y))
+    return out
+
+
+# ---- human-centric mask of the ground-truth metrics -------------------------------------------
+# _generate_human_mask (HSM_auto_dataset.py:254-334): (joint a, joint b, cv2.line thickness); the last four only for 19 joints
+MASK_LIMBS = ([(0, 1, 30)]                                                                       # head
+              + [(a, b, 30) for a, b in ((1, 2), (2, 3), (3, 4), (1, 5), (5, 6), (6, 7))]        # hand
+              + [(a, b, 30) for a, b in ((8, 9), (9, 10), (10, 11), (8, 12), (12, 13), (13, 14))]  # legs
+              + [(a, b, 40) for a, b in ((1, 8), (2, 9), (5, 12))]                               # body
+              + [(4, 18, 30), (7, 17, 30), (11, 16, 30), (14, 15, 30)])                          # hand tips, feet (n == 19)
+MASK_JOINT_RADIUS = (30, 15)          # cv2.circle radius of joint 0, of every other joint
+MASK_MAX_SIDE = 16384                 # the device kernel's int32 products hold up to this frame side
+
+
+def mask_limbs(n_joints):
+    """The limb table of a pose of n_joints joints (18 or 19; k_human_mask knows the same two)."""
+    if n_joints not in (18, 19):
+        raise ValueError("human mask: a pose has 18 or 19 joints, got %d" % n_joints)
+    return MASK_LIMBS if n_joints == 19 else MASK_LIMBS[:-4]
+
+
+def human_mask(peaks, height, width):
+    """The human-centric mask the reference measures PSNR / SSIM under (_generate_human_mask, HSM_auto_dataset.py:254-334,
+    the first of its two results; evaluator.py:118,122), restated from OpenCV's drawing, unpinned (cv2 is not in this image).
+    peaks: [n, 2] int (x, y) of peak_table, (-1, -1) = joint off - the reference's dict_pose_line.  -> [H, W] bool.
+    The definition this project owns, all in integers; a pixel (px, py) is set iff one of these holds:
+      disc(P, R)      (px-Px)^2 + (py-Py)^2 <= R*R + R                       (pixel centre within R + 1/2 of P)
+                      for every valid joint i, R = 30 if i == 0 else 15 (cv2.circle, filled), and for both ends of every limb
+                      of MASK_LIMBS whose two joints are valid, R = thickness / 2 (cv2.line's round caps)
+      slab(A, B, h)   with d = B - A, L2 = d.d, v = (px, py) - A:  0 <= v.d <= L2  and  4 (vx dy - vy dx)^2 <= (2h+1)^2 L2
+                      for every such limb with A != B, h = thickness / 2     (within h + 1/2 of the segment, between its ends)
+    R + 1/2, not R: OpenCV's integer circle and the outline FillConvexPoly traces both set the pixels ON the ideal outline.
+    A union, so order-free.  `mask > 128` after cvtColor is the identity on a 0/255 drawing; the training-only part_mask
+    is not built.  csrc/human_mask.hip.h evaluates the same integer tests on the GPU, bit for bit."""
+    peaks = np.asarray(peaks)
+    if peaks.ndim != 2 or peaks.shape[1] != 2:
+        raise ValueError("human mask: peaks must be [n, 2], got %s" % (peaks.shape,))
+    height, width = int(height), int(width)
+    if not (1 <= height <= MASK_MAX_SIDE and 1 <= width <= MASK_MAX_SIDE):
+        raise ValueError("human mask: height and width must be in 1..%d, got %dx%d" % (MASK_MAX_SIDE, height, width))
+    limbs = mask_limbs(len(peaks))
+    peaks = peaks.astype(np.int64)
+    out = np.zeros((height, width), bool)
+
+    def window(x0, x1, y0, y1, grow):         # the part of the frame a shape can reach, as index grids
+        xa, xb = max(0, x0 - grow), min(width, x1 + grow + 1)
+        ya, yb = max(0, y0 - grow), min(height, y1 + grow + 1)
+        if xa >= xb or ya >= yb:
+            return None
+        return (slice(ya, yb), slice(xa, xb)), np.arange(xa, xb, dtype=np.int64)[None, :], np.arange(ya, yb, dtype=np.int64)[:, None]
+
+    def disc(P, R):
+        win = window(P[0], P[0], P[1], P[1], R + 1)
+        if win is not None:
+            sl, px, py = win
+            out[sl] |= (px - P[0]) ** 2 + (py - P[1]) ** 2 <= R * R + R
+
+    valid = [bool(p[0] >= 0) for p in peaks]
+    for i, P in enumerate(peaks):
+        if valid[i]:
+            disc(P, MASK_JOINT_RADIUS[0] if i == 0 else MASK_JOINT_RADIUS[1])
+    for a, b, t in limbs:
+        if not (valid[a] and valid[b]):
+            continue
+        A, B, h = peaks[a], peaks[b], t // 2
+        disc(A, h)
+        disc(B, h)
+        dx, dy = int(B[0] - A[0]), int(B[1] - A[1])
+        L2 = dx * dx + dy * dy
+        win = window(min(A[0], B[0]), max(A[0], B[0]), min(A[1], B[1]), max(A[1], B[1]), h + 1) if L2 else None
+        if win is not None:
+            sl, px, py = win
+            vx, vy = px - A[0], py - A[1]
+            dot, cross = vx * dx + vy * dy, vx * dy - vy * dx
+            out[sl] |= (dot >= 0) & (dot <= L2) & (4 * cross * cross <= (2 * h + 1) ** 2 * L2)
     return out
 
 

@@ -2,13 +2,15 @@
 """End-to-end rate of the folder driver (json + PNG in, PNG out) on a synthetic clip.
 
     python tools/driver_bench.py [--size 512 | --height 320 --width 480] [--keys 5] [--rate 32] [--lanes 2] [--batch B] [--chunk 4]
-                                  [--src-width 1920 --src-height 1080] [--resize-on host|gpu]
+                                  [--src-width 1920 --src-height 1080] [--resize-on host|gpu] [--metrics [--pose-mask]]
 
 Writes a clip in the reference's directory layout (inputs/ DAIN/ Predict_motion/), runs
 Evaluator.evaluate_from_folder twice (the first run also builds launch plans) and prints the
 phase times of the second: load (decode + json), rasterise (GPU), generate (GPU chains + quantise +
 one D2H copy), save (PNG encode).  --src-width / --src-height write the input frames at that size (default: the model size),
-so that the driver has to resize them; --resize-on says where (Evaluator(resize_on=...)).
+so that the driver has to resize them; --resize-on says where (Evaluator(resize_on=...)).  --metrics also writes a ground-truth
+frame per frame (gt/) and measures every generated frame against it (evaluate_from_folder(metrics=True)); --pose-mask measures
+under the mask drawn from each frame's pose (pose_mask=True), so that the cost of either can be read off two runs.
 """
 import argparse, json, os, sys, tempfile, time
 import numpy as np, torch
@@ -18,11 +20,11 @@ from render_in_between_amd import evaluator as ev, synth
 from tools.raster_bench import person
 
 
-def write_clip(root, n_key, rate, H, W, src_h=0, src_w=0):
+def write_clip(root, n_key, rate, H, W, src_h=0, src_w=0, gt=False):
     from PIL import Image
     rng = np.random.default_rng(0)
     n = (n_key - 1) * rate + 1
-    for d in ("inputs", "DAIN", "Predict_motion"):
+    for d in ("inputs", "DAIN", "Predict_motion") + (("gt",) if gt else ()):
         os.makedirs(os.path.join(root, d, "clip"))
     spec = rib.GenSpec.from_cfg(rib.hsm_gen_config())
     sh, sw = src_h or H, src_w or W          # the files' size; the keypoints below are in the same pixels
@@ -33,6 +35,8 @@ def write_clip(root, n_key, rate, H, W, src_h=0, src_w=0):
         Image.fromarray(img(k)).save(os.path.join(root, "inputs", "clip", "%04d.png" % k))
     for i in range(n):
         Image.fromarray(img(100 + i)).save(os.path.join(root, "DAIN", "clip", "f%04d.png" % i))
+        if gt:
+            Image.fromarray(img(1000 + i)).save(os.path.join(root, "gt", "clip", "f%04d.png" % i))
         lm, conf = person(rng, sh, sw)
         body = np.zeros((25, 3)); idx = list(range(15)) + [19, 22]
         for j, k in enumerate(idx):
@@ -63,30 +67,37 @@ def main():
     ap.add_argument("--src-width", type=int, default=0, help="width of the synthetic input files (0: the model width)")
     ap.add_argument("--src-height", type=int, default=0, help="height of the synthetic input files (0: the model height)")
     ap.add_argument("--resize-on", default="host", choices=("host", "gpu"), help="where the DAIN frames are resized (Evaluator(resize_on=...))")
+    ap.add_argument("--metrics", action="store_true", help="measure every generated frame against a synthetic ground-truth frame (metrics=True)")
+    ap.add_argument("--pose-mask", action="store_true", help="with --metrics: under the mask drawn from each frame's pose (pose_mask=True)")
     a = ap.parse_args()
+    if a.pose_mask and not a.metrics:
+        ap.error("--pose-mask is a setting of --metrics")
     H, W = (a.height or a.size), (a.width or a.size)
     cfg = rib.AttrDict(gen=rib.hsm_gen_config(), model_height=H, model_width=W, gauss_sigma=5, skeleton_thres=0.001, foot_thres=0.001)
     spec = rib.GenSpec.from_cfg(cfg.gen)
     G = rib.Generator(cfg.gen, compute_dtype=a.dtype).eval()
     G.load_state_dict(synth.make_state_dict(spec, 0, power_iters=3))
     with tempfile.TemporaryDirectory() as root:
-        n = write_clip(root, a.keys, a.rate, H, W, a.src_height, a.src_width)
+        n = write_clip(root, a.keys, a.rate, H, W, a.src_height, a.src_width, gt=a.metrics)
         E = ev.Evaluator(cfg, lanes=a.lanes, batch=a.batch or None, chunk=a.chunk, io_threads=a.io_threads or None,
                          png_compress_level=None if a.compress < 0 else a.compress, io_mode=a.io_mode, resize_on=a.resize_on)
         dirs = [os.path.join(root, d) for d in ("inputs", "DAIN", "Predict_motion")]
         walls = []
         for rep in range(1 + a.reps):           # the first run also builds launch plans and pools: not counted
             t0 = time.perf_counter()
-            out = E.evaluate_from_folder(G, *dirs, os.path.join(root, "out%d" % rep))
+            out = E.evaluate_from_folder(G, *dirs, os.path.join(root, "out%d" % rep), gt_dir=os.path.join(root, "gt") if a.metrics else None,
+                                         metrics=a.metrics, pose_mask=a.pose_mask)
             torch.cuda.synchronize()
             walls.append(time.perf_counter() - t0)
         tm = dict(E.timings)
+        overall = dict(E.metrics_report["overall"]) if a.metrics else None
     gen = n - a.keys
     wall = sorted(walls[1:])[len(walls[1:]) // 2]
     print(json.dumps({"height": H, "width": W, "dtype": a.dtype, "frames": n, "generated": gen, "lanes": a.lanes,
                       "batch": a.batch or E.default_batch(), "chunk": a.chunk, "io_threads": E.io_threads, "io_mode": a.io_mode,
                       "cpus": len(os.sched_getaffinity(0)), "cpu_budget": ev.cpu_budget(), "png_compress_level": a.compress,
                       "src_height": a.src_height or H, "src_width": a.src_width or W, "resize_on": a.resize_on,
+                      "metrics": a.metrics, "pose_mask": a.pose_mask, "metrics_overall": overall,
                       "wall_s": wall, "wall_s_runs": [round(w, 4) for w in walls[1:]], "frames_per_s_end_to_end": n / wall,
                       "phase_s_last_run": {k: round(v, 4) for k, v in tm.items() if k not in ("frames", "units", "timeline", "peak_units_in_flight")},
                       "peak_units_in_flight": tm.get("peak_units_in_flight"),

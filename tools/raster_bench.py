@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Label rasterisation rate: GPU (rib_rasterise, whole clip per call) vs the CPU oracle per frame.
 
-    python tools/raster_bench.py [--size 512] [--frames 256] [--cpu-frames 3]
+    python tools/raster_bench.py [--size 512] [--frames 256] [--cpu-frames 3] [--mask]
+
+--mask also draws the pose mask of the same frames (rib_human_mask) and checks it against rasterise.human_mask; under
+`rocprofv3 --kernel-trace --stats` one run then lists k_human_mask beside k_heatmaps and k_skeleton.
 """
 import argparse, json, os, sys, time
 import numpy as np, torch
@@ -26,6 +29,7 @@ def main():
     ap.add_argument("--frames", type=int, default=256)
     ap.add_argument("--cpu-frames", type=int, default=3)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--mask", action="store_true", help="also time Generator.human_mask on the same peak tables")
     a = ap.parse_args()
     H = W = a.size
     rng = np.random.default_rng(0)
@@ -47,6 +51,16 @@ def main():
         torch.cuda.synchronize()
         ms = (time.perf_counter() - t0) * 1e3 / a.reps
         out["gpu_T%d" % T] = {"ms_per_call": ms, "frames_per_s": T / ms * 1e3}
+        if a.mask:
+            G.human_mask(peaks[:T], H, W)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.reps):
+                mk = G.human_mask(peaks[:T], H, W)
+            torch.cuda.synchronize()
+            out["gpu_T%d" % T]["mask_ms_per_call"] = (time.perf_counter() - t0) * 1e3 / a.reps
+            out["gpu_T%d" % T]["mask_coverage"] = float(mk.mean())
+            out["gpu_T%d" % T]["mask_bit_exact_vs_host"] = bool(np.array_equal(mk[-1].cpu().numpy() != 0, R.human_mask(peaks[:T][-1], H, W)))
     res = {"size": a.size, "host_tables_ms_per_frame": host_ms, **out}
     if a.cpu_frames:
         from oracle import rasterise_ref as O               # the CPU side of the comparison only
