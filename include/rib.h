@@ -229,6 +229,22 @@ int rib_rasterise(rib_handle* h, int T, int H, int W,
  * outside 1..16384, a peak outside the frame, NULL pointers: RIB_ERR_INVALID with a rib_last_error text. */
 int rib_human_mask(rib_handle* h, int T, int H, int W, const int32_t* peaks, int n_joints,
                    float* mask /* [T,H,W] device */, void* hip_stream);
+/* ---- six-pane diagnostic sheet of the folder driver (PGNR/models/evaluator.py:260-269, utils/visualize.py make_video) ----
+ * T sheets in one launch: row 0 Predict | Mask | Fuse, row 1 DAIN | Ground Truth | Skeleton, each pane H x W, 8 px of white
+ * (255) around and between the panes and a 24 px title bar over each pane row: out uint8 [T,SH,SW,3] with
+ * SH = 2 (H + 24) + 3 * 8, SW = 3 W + 4 * 8, every byte written by the launch (nothing has to be cleared).  The layout and
+ * the titles are this project's, not matplotlib's; panel.py (layout, compose_host) states the sheet on the host, bit-equal.
+ * Inputs fp32 NCHW on the device: pred, fuse, dain, gt [T,3,H,W], mask [T,1,H,W], label [T,label_nc,H,W] (channels 0..2 are
+ * the skeleton image; label_nc >= 3).  A 3-channel pane holds uint8(clip(x*0.5+0.5,0,1)*255) - the arithmetic of
+ * rib_quantise, evaluated by the same device function; the Mask pane uint8(double(m)*255.0), truncating, no clip (m in
+ * [0,1]), on all three channels (tensor2images, PGNR/utils/utils.py:122-147).
+ * pred, mask and fuse may be NULL together: key-frame mode, Predict = Fuse = gt and Mask = 0 (evaluator.py:240-244).
+ * titles: uint8 0/1 [2,24,SW] on the device or NULL; a set pixel of title bar r is drawn (0,0,255).
+ * Enqueues one launch on `stream`, no synchronisation, no workspace, no atomics: a sheet's bytes do not depend on T.
+ * T outside 1..65535, H outside 1..16384, W outside 1..4096, label_nc < 3, a sheet of 2 GiB or more, a NULL dain / gt / label /
+ * out, or only some of pred / mask / fuse NULL: RIB_ERR_INVALID with a rib_last_error text, nothing launched. */
+int rib_panel(rib_handle* h, int T, int H, int W, int label_nc, const float* pred, const float* mask, const float* fuse,
+              const float* dain, const float* gt, const float* label, const uint8_t* titles, uint8_t* out, void* hip_stream);
 
 /* Extension op named by the north star but absent from the reference: bilinear
  * flow-grid warp, semantics of torch.nn.functional.grid_sample(img, base+flow*2/(size-1),

@@ -1619,15 +1619,20 @@ __global__ __launch_bounds__(256) void k_blend(const float* img, const float* ma
 }
 
 // uint8 HWC = uint8(clip(x*0.5+0.5, 0, 1)*255)  (truncation; PGNR/utils/utils.py:129-142; the
-// reference evaluates this in float64, so do we)
+// reference evaluates this in float64, so do we).  One statement of the arithmetic for every kernel that writes a frame's
+// bytes (k_quantise here, k_panel in panel.hip.h); tests/golden/quant_ref.npz pins it to the reference's bytes.
+__device__ inline uint8_t quantise_u8(float x) {
+  double v = (double)x * 0.5 + 0.5;
+  v = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);
+  return (uint8_t)(v * 255.0);
+}
+
 __global__ __launch_bounds__(256) void k_quantise(const float* img, uint8_t* out, int C, int HW, size_t total) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const size_t c = i % C;
     const size_t pix = (i / C) % HW;
     const size_t n = i / ((size_t)C * HW);
-    double v = (double)img[(n * C + c) * HW + pix] * 0.5 + 0.5;
-    v = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);
-    out[i] = (uint8_t)(v * 255.0);
+    out[i] = quantise_u8(img[(n * C + c) * HW + pix]);
   }
 }
 

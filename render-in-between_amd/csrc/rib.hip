@@ -14,6 +14,7 @@
 #include "quality.hip.h"
 #include "resize.hip.h"
 #include "human_mask.hip.h"
+#include "panel.hip.h"
 #include <hip/hip_ext.h>
 #include "../../include/rib.h"
 
@@ -2989,6 +2990,32 @@ int rib_human_mask(rib_handle* h, int T, int H, int W, const int32_t* peaks, int
   RIB_KLAUNCH(k_human_mask, dim3(mp.tilesX * tilesY, T), dim3(256), 0, st, mp);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipEventRecord(ms.done, st));
+  return RIB_OK;
+}
+
+int rib_panel(rib_handle* h, int T, int H, int W, int label_nc, const float* pred, const float* mask, const float* fuse,
+              const float* dain, const float* gt, const float* label, const uint8_t* titles, uint8_t* out, void* hip_stream) {
+  if (!h) return RIB_ERR_INVALID;
+  if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_panel: host-only handle");
+  if (!dain || !gt || !label || !out) return fail(h, RIB_ERR_INVALID, "rib_panel: null pointer");
+  const int given = (pred ? 1 : 0) + (mask ? 1 : 0) + (fuse ? 1 : 0);
+  if (given != 0 && given != 3) return fail(h, RIB_ERR_INVALID, "rib_panel: pred, mask and fuse are NULL together (key-frame mode) or not at all");
+  if (T < 1 || T > 65535 || H < 1 || W < 1 || H > PANEL_MAX_H || W > PANEL_MAX_W || label_nc < 3)
+    return fail(h, RIB_ERR_INVALID, fmt("rib_panel: T=%d H=%d W=%d label_nc=%d: 1 <= T <= 65535, H in 1..%d, W in 1..%d, label_nc >= 3",
+                                        T, H, W, label_nc, PANEL_MAX_H, PANEL_MAX_W));
+  PanelParams pp;
+  pp.pred = pred; pp.mask = mask; pp.fuse = fuse; pp.dain = dain; pp.gt = gt; pp.label = label; pp.titles = titles; pp.out = out;
+  pp.H = H; pp.W = W; pp.label_nc = label_nc;
+  pp.SH = 2 * (H + PANEL_TITLE) + 3 * PANEL_GUTTER;
+  pp.SW = 3 * W + 4 * PANEL_GUTTER;
+  if ((size_t)pp.SH * pp.SW * 3 > (size_t)INT32_MAX) return fail(h, RIB_ERR_INVALID, "rib_panel: a sheet must be smaller than 2 GiB");
+  uintptr_t bits = reinterpret_cast<uintptr_t>(dain) | reinterpret_cast<uintptr_t>(gt) | reinterpret_cast<uintptr_t>(label);
+  if (pred) bits |= reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(mask) | reinterpret_cast<uintptr_t>(fuse);
+  pp.vec = (W % 4 == 0 && (bits & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0) ? 1 : 0;
+  HIP_TRY(h, hipSetDevice(h->device));
+  const size_t lds = (size_t)pp.SW * 3 + 32;             // the row at its phase inside a 16-byte line, rounded up to whole lines
+  RIB_KLAUNCH(k_panel, dim3(pp.SH, T), dim3(256), lds, reinterpret_cast<hipStream_t>(hip_stream), pp);
+  HIP_TRY(h, hipGetLastError());
   return RIB_OK;
 }
 

@@ -50,6 +50,7 @@ import torch
 
 from . import io_worker, rasterise
 from . import metrics as _metrics
+from . import panel as _panel
 
 
 def sample_rate_of(num_pose: int, num_key: int) -> int:
@@ -302,6 +303,19 @@ def plan_gpu_resize(dain_sizes, gt_sizes, model_size, slots_per_unit, mask=False
     return src, why
 
 
+def normalise_exact(u8):
+    """ToTensor + Normalize(0.5, 0.5) of uint8 [.., H, W, 3] frames on their device, bit-equal to what the HOST computes
+    (io_worker.normalised_chw: float32(u8) / 255 correctly rounded, then (a - 0.5) / 0.5) -> float32 [.., 3, H, W], contiguous.
+    torch evaluates `x / 255.0` on the GPU as a multiplication by the fp32 reciprocal, which differs from the division in the
+    last bit for 111 of the 256 values (csrc/resize.hip.h) - invisible to the generator, but the truncating quantiser turns it
+    into a grey level, and the sheets' DAIN / Ground Truth panes are held to the bytes tensor2images makes of the host's
+    tensor.  The quotient is formed in float64 and rounded once: n / 255 is never within 2^-9 ulp of a float32 rounding
+    boundary (its binary expansion repeats n's 8 bits), so the result is the correctly rounded float32 quotient whichever
+    way the float64 division is carried out."""
+    a = (u8.to(torch.float64) / 255.0).to(torch.float32)
+    return ((a - 0.5) / 0.5).movedim(-1, -3).contiguous()
+
+
 def _list(d, exts):
     return [os.path.join(d, f) for f in sorted(os.listdir(d)) if f.endswith(exts)]
 
@@ -500,7 +514,8 @@ class Evaluator:
     # ---- the driver ------------------------------------------------------------------------------
     @torch.no_grad()
     def evaluate_from_folder(self, model, train_dir, dain_dir, pose_dir, save_dir, gt_dir=None, gen_vid=False,
-                             rank=None, world=None, metrics=False, mask_dir=None, pose_mask=False):
+                             rank=None, world=None, metrics=False, mask_dir=None, pose_mask=False,
+                             panels=False, panel_frames=False, panel_quality=90, panel_fps=30):
         """rank / world: this process's share of the independent units (default: the torch.distributed process
         group when one is initialised, else everything).  Returns the frames THIS rank wrote.
         The call is one `_FolderPipeline` (below): plan a clip -> decode -> upload -> render -> sink, pipelined over units
@@ -511,11 +526,24 @@ class Evaluator:
         end up in self.metrics and <save_dir>/metrics.json (written by rank 0).  metrics=False changes nothing.
         pose_mask=True (with metrics, instead of mask_dir): the mask of a measured frame is the reference's human-centric mask
         (_generate_human_mask restated from OpenCV's drawing, unpinned: rasterise.human_mask) of that frame's pose - on the
-        native path drawn by rib_human_mask on the upload stream, next to the label rasterisation; nothing is staged for it."""
+        native path drawn by rib_human_mask on the upload stream, next to the label rasterisation; nothing is staged for it.
+        panels=True: every frame i - key frames included - also gets a six-pane diagnostic sheet (panel.py: Predict | Mask | Fuse
+        over DAIN | Ground Truth | Skeleton; the Ground Truth pane is gt_dir's frame i, else the segment's left key frame),
+        written by whichever rank rendered the frame to <save_dir>/<clip>_panels/%04d.jpg (JPEG quality panel_quality) and, with
+        panel_frames, losslessly to %04d.png.  On the native path the sheets are composed by rib_panel on the lane's stream
+        and ride home in the unit's one copy; a model that only speaks the reference's protocol goes through
+        panel.compose_host.  Rank 0 then muxes <save_dir>/<clip>.avi (Motion-JPEG, panel_fps frames/s; panel.assemble) from the
+        folder, removes the JPEG sheets and - unless panel_frames - the folder.  (Ranks without a process group cannot know when
+        the others are done: the caller runs panel.assemble once they are.)  panels=False changes nothing."""
         if gen_vid:
-            # the reference also writes <save_dir>/<clip>.mp4 (evaluator.py:267-269, utils.make_video); not built, and
-            # silently ignoring the flag would drop an output the caller asked for
-            raise NotImplementedError("evaluate_from_folder: gen_vid is not supported")
+            # the reference also writes <save_dir>/<clip>.mp4 (evaluator.py:267-269, utils.make_video) from a matplotlib canvas
+            # through an H.264 encoder; neither is built, and silently ignoring the flag would drop an output the caller asked for
+            raise NotImplementedError("evaluate_from_folder: gen_vid (the matplotlib / mp4 video) is not supported; panels=True "
+                                      "writes the six-pane sheets as <save_dir>/<clip>.avi")
+        if not panels and (panel_frames or panel_quality != 90 or panel_fps != 30):
+            raise ValueError("evaluate_from_folder: panel_frames, panel_quality and panel_fps are settings of panels=True")
+        if panels and not (1 <= int(panel_quality) <= 100 and float(panel_fps) > 0):
+            raise ValueError("evaluate_from_folder: panel_quality must be in 1..100 and panel_fps positive")
         if metrics and gt_dir is None:
             raise ValueError("evaluate_from_folder: metrics=True needs gt_dir (the ground-truth frames)")
         if mask_dir is not None and not metrics:
@@ -532,7 +560,8 @@ class Evaluator:
             self._pool = ThreadPoolExecutor(self.io_threads)          # decode + encode workers
             self._finishers = ThreadPoolExecutor(max(4, self.lanes + 2))  # wait for a unit's copy, then fan out its encodes
         self.metrics = self.metrics_report = None
-        pipe = _FolderPipeline(self, model, rank, world, gt_dir, metrics=bool(metrics), mask_dir=mask_dir, pose_mask=bool(pose_mask))
+        pipe = _FolderPipeline(self, model, rank, world, gt_dir, metrics=bool(metrics), mask_dir=mask_dir, pose_mask=bool(pose_mask),
+                               panels=bool(panels), panel_frames=bool(panel_frames), panel_quality=int(panel_quality))
         self.timings = pipe.tm
         if metrics and pipe.native:
             self._quality_model = model
@@ -549,6 +578,8 @@ class Evaluator:
                 written = pipe.drain()
             if metrics:
                 self.metrics, self.metrics_report = pipe.report(save_dir)
+            if panels:
+                pipe.assemble_panels(save_dir, panel_fps)
             return written
         finally:
             del pipe                 # the units' tensor views of the shared blocks die with it ...
@@ -582,6 +613,19 @@ class _Clip:
         self.prev_of = {}                   # group -> last fused frames [B,3,H,W] on its lane
         # resize_on="gpu": (w0, h0) at which the DAIN / GT frames are staged for the GPU resize; None: resized on the host
         self.src_dain = self.src_gt = None
+        # panels: the sheets' folder; GT frames are staged for the Ground Truth pane whenever a gt_dir is given (want_gt: staged,
+        # measured or not); the DAIN frames of a first chunk's key frames get a section of the unit's block (key_slot: key frame
+        # index -> (unit, b)); key_of: group -> its key frames [B,3,H,W] on the device (the Ground Truth pane without a gt_dir);
+        # pan: unit -> what upload() prepared for the unit's sheets
+        self.panel_dir = None
+        self.want_gt = measure
+        self.stage_key, self.key_slot, self.key_of, self.pan = {}, {}, {}, {}
+        self.sheet_futs = []                # futures of sheet files that ride in no unit's sink
+
+    def sheet_names(self, i, png):
+        """(jpg, png or None) of frame i's sheet."""
+        base = os.path.join(self.panel_dir, "%04d" % i)
+        return base + ".jpg", (base + ".png" if png else None)
 
     def ref_image(self, i):
         """evaluator.py:209-212: the "gt" image of frame i is gtlist[i] when a gt_dir is given, else the key frame of its
@@ -607,9 +651,11 @@ class _FolderPipeline:
     host until its files exist, and the GPU renders faster than PNGs get written.  Every stage can be driven on its own
     (tests/test_driver.py)."""
 
-    def __init__(self, ev, model, rank, world, gt_dir, metrics=False, mask_dir=None, pose_mask=False):
+    def __init__(self, ev, model, rank, world, gt_dir, metrics=False, mask_dir=None, pose_mask=False,
+                 panels=False, panel_frames=False, panel_quality=90):
         self.ev, self.model, self.rank, self.world, self.gt_dir = ev, model, rank, world, gt_dir
         self.metrics, self.mask_dir, self.pose_mask = metrics, mask_dir, pose_mask
+        self.panels, self.panel_frames, self.panel_quality = panels, panel_frames, panel_quality
         self.native = hasattr(model, "chain") and hasattr(model, "quantise")
         if self.native and metrics and not hasattr(model, "quality"):
             raise RuntimeError("metrics=True: this model has no GPU quality kernel (rib_quality)")
@@ -617,8 +663,16 @@ class _FolderPipeline:
             raise RuntimeError("pose_mask=True: this model has no GPU mask kernel (rib_human_mask)")
         if ev.resize_on == "gpu" and not (self.native and hasattr(model, "resize_u8")):
             raise RuntimeError("resize_on='gpu': this model has no GPU resize kernel (rib_resize_cubic)")
+        if self.native and panels and not hasattr(model, "panel"):
+            raise RuntimeError("panels=True: this model has no GPU sheet kernel (rib_panel)")
         self.gpu_labels = self.native and ev.label_fn is None and hasattr(model, "rasterise")
-        per_slot = (1.0 + (1.0 if metrics else 0.0) + (1.0 / 3 if mask_dir is not None else 0.0))
+        per_slot = (1.0 + (1.0 if (metrics or (panels and gt_dir is not None)) else 0.0) + (1.0 / 3 if mask_dir is not None else 0.0))
+        if panels:                           # a unit's download block also carries its sheets (six panes and the borders per frame)
+            sh, sw = _panel.layout(ev.height, ev.width)["sheet"]
+            per_slot += 2.0 * sh * sw / (ev.height * ev.width)
+            self.sheet_hw = (sh, sw)
+            self.titles = _panel.title_bitmap(ev.width)
+            self.titles_dev = None           # ... on the device, uploaded once (native path)
         self.procs = _process_pool(ev.io_threads) if (self.native and ev.io_mode == "process" and ev._shm_fits(per_slot)) else None
         self.pool, self.finishers = ev._pool, ev._finishers
         self.level = ev.png_compress_level
@@ -699,6 +753,12 @@ class _FolderPipeline:
                     units.append((gi, members, c0, min(T, c0 + step)))
         clip = _Clip(names, dain_list, image_list, pose_list, gtlist, sample_rate, my_keys, segs, units, sub=sub,
                      measure=self.metrics, mask_list=mask_list)
+        if self.panels:
+            if gtlist is not None and len(gtlist) < seq_len:
+                raise ValueError("panels: %s has %d ground-truth frames, the clip has %d" % (os.path.join(self.gt_dir, sub), len(gtlist), seq_len))
+            clip.want_gt = gtlist is not None
+            clip.panel_dir = _panel.sheet_dir(save_dir, sub)
+            os.makedirs(clip.panel_dir, exist_ok=True)
         if ev.resize_on == "gpu" and units:
             # the header sizes of the frames this rank stages (cached: the keypoint scaling reads the same headers)
             staged = [i for _, frames in segs for i in frames]
@@ -726,12 +786,16 @@ class _FolderPipeline:
             else:
                 clip.stage[ui][t, b].copy_(dain)
             dain = None
-            if clip.measure and clip.src_gt is not None:
+            if clip.want_gt and clip.src_gt is not None:
                 io_worker.decode_raw_into(clip.stage_gt[ui][t, b].numpy(), 0, clip.gtlist[i], clip.src_gt)
-            elif clip.measure:                   # the GT frame (and mask) of a measured frame, through the same resize
+            elif clip.want_gt:                   # the GT frame (and mask) of a measured frame, through the same resize
                 clip.stage_gt[ui][t, b].copy_(ev.load_image_u8(clip.gtlist[i])[0])
             if clip.measure and clip.mask_list is not None:
                 clip.stage_mask[ui][t, b].copy_(torch.from_numpy(io_worker.load_mask_u8(clip.mask_list[i], ev.width, ev.height)))
+        elif i in clip.key_slot:                 # panels: a key frame's DAIN frame, for its sheet
+            ui, b, _ = clip.key_slot[i]
+            clip.stage_key[ui][b].copy_(dain)
+            dain = None
         ref_img = clip.ref_image(i)
         gt = ev.load_image(ref_img)[0] if i % clip.sample_rate == 0 else None
         pose = ev.load_pose(clip.pose_list[i], self.image_size(ref_img))
@@ -752,12 +816,15 @@ class _FolderPipeline:
             k = t * Bc + b
             fsz = clip.stage[ui][0, 0].numel()   # a slot of the DAIN section: the model size, or the source size (resize_on="gpu")
             name, off = clip.stage_blk[ui].name, k * fsz
-            if clip.measure:                     # GT frame (and mask) of a measured frame: further sections of the same block
+            if clip.want_gt:                     # GT frame (and mask) of a measured frame: further sections of the same block
                 gsz = clip.stage_gt[ui][0, 0].numel()
                 mask_off = Tc * Bc * (fsz + gsz) + k * ev.height * ev.width if clip.mask_list is not None else -1
                 extra = (Tc * Bc * fsz + k * gsz, clip.mask_list[i] if clip.mask_list is not None else None, mask_off)
             if clip.src_dain is not None or clip.src_gt is not None:
                 extra = (extra or (-1, None, -1)) + (clip.src_dain, clip.src_gt if clip.measure else None)
+        elif i in clip.key_slot:                 # panels: a key frame's DAIN frame goes to the key section, at the model size
+            ui, _, off = clip.key_slot[i]
+            name = clip.stage_blk[ui].name
         src = self.procs.submit(io_worker.load_frame_shm, name, off, clip.dain_list[i], clip.ref_image(i), clip.pose_list[i],
                                 i % clip.sample_rate == 0, self.gpu_labels, ev.width, ev.height, ev.resize, ev.skeleton_thres, ev.foot_thres,
                                 *extra)
@@ -792,18 +859,29 @@ class _FolderPipeline:
             shape, shape_gt = (c1 - c0, len(members), hd, wd, 3), (c1 - c0, len(members), hg, wg, 3)
             shape_mask = (c1 - c0, len(members), ev.height, ev.width)
             nb, nb_gt, nb_mask = (int(np.prod(s_)) for s_ in (shape, shape_gt, shape_mask))
-            # metrics: [DAIN frames | GT frames | masks] side by side in the unit's one staging block
-            total = nb + nb_gt + (nb_mask if clip.mask_list is not None else 0) if clip.measure else nb
+            # metrics / panels: [DAIN frames | GT frames | masks | DAIN frames of the key frames] side by side in the unit's one
+            # staging block; the last section only for a first chunk under panels (key-frame sheets)
+            if not clip.want_gt:
+                nb_gt = 0
+            if clip.mask_list is None:
+                nb_mask = 0
+            fkey = ev.height * ev.width * 3
+            nb_key = len(members) * fkey if (self.panels and c0 == 0) else 0
+            total = nb + nb_gt + nb_mask + nb_key
             if self.procs is not None:      # shared with the decode workers and page-locked (back on the free list once uploaded)
                 clip.stage_blk[ui] = _shm_get(total)            # (size classes of 1 MB: the block may be larger than the unit)
                 flat = clip.stage_blk[ui].t[:total]
             else:
                 flat = torch.empty(total, dtype=torch.uint8, pin_memory=True)
             clip.stage[ui] = flat[:nb].view(*shape)
-            if clip.measure:
+            if clip.want_gt:
                 clip.stage_gt[ui] = flat[nb:nb + nb_gt].view(*shape_gt)
-                if clip.mask_list is not None:
-                    clip.stage_mask[ui] = flat[nb + nb_gt:].view(*shape_mask)
+            if clip.mask_list is not None:
+                clip.stage_mask[ui] = flat[nb + nb_gt:nb + nb_gt + nb_mask].view(*shape_mask)
+            if nb_key:
+                clip.stage_key[ui] = flat[total - nb_key:].view(len(members), ev.height, ev.width, 3)
+                for b, si in enumerate(members):
+                    clip.key_slot[clip.segs[si][0]] = (ui, b, total - nb_key + b * fkey)
             for b, si in enumerate(members):
                 for t in range(c0, c1):
                     clip.slot[clip.segs[si][1][t]] = (ui, t - c0, b)
@@ -825,37 +903,65 @@ class _FolderPipeline:
         rasterisation, the upload of the staged DAIN frames with ToTensor + Normalize(0.5, 0.5) on the GPU
         (HSM_auto_dataset.py:73-75) and the key frames; the lane joins through the returned event.  -> (lab, dn, gtd, ready)."""
         ev = self.ev
-        _, members, c0, c1 = clip.units[ui]
+        gi, members, c0, c1 = clip.units[ui]
         Tc, Bc = c1 - c0, len(members)
         if self.up is None:
             self.up = torch.cuda.Stream(device=self.model.device)
+        # panels: the label maps of a first chunk's key frames (their sheets' Skeleton pane) are drawn in the unit's own call
+        key_poses = [clip.loads[clip.segs[si][0]].result(timeout=IO_TIMEOUT_S)[2] for si in members] if (self.panels and c0 == 0) else []
         with torch.cuda.stream(self.up):
             if self.gpu_labels:
-                lab = rasterise.rasterise_tables(g, poses, ev.height, ev.width, ev.gauss_sigma)
+                lab = rasterise.rasterise_tables(g, poses + key_poses, ev.height, ev.width, ev.gauss_sigma)
             else:
-                lab = ev.make_labels(g if hasattr(g, "rasterise") else self.model, poses)
-            lab = lab.to(g.device).reshape(Tc, Bc, *lab.shape[1:])            # [Tc,B,22,H,W]
+                lab = ev.make_labels(g if hasattr(g, "rasterise") else self.model, poses + key_poses)
+            lab = lab.to(g.device)
+            klab = lab[Tc * Bc:] if key_poses else None
+            lab = lab[:Tc * Bc].reshape(Tc, Bc, *lab.shape[1:])              # [Tc,B,22,H,W]
+            staged = clip.stage[ui].to(g.device, non_blocking=True)
             if clip.src_dain is not None:      # resize_on="gpu": resize + ToTensor + Normalize in one kernel (rib_resize_cubic)
-                dn = g.resize_u8(clip.stage[ui].to(g.device, non_blocking=True).flatten(0, 1), ev.width, ev.height,
-                                 normalised=True).view(Tc, Bc, 3, ev.height, ev.width)
+                dn = g.resize_u8(staged.flatten(0, 1), ev.width, ev.height, normalised=True).view(Tc, Bc, 3, ev.height, ev.width)
             else:
-                dn = clip.stage[ui].to(g.device, non_blocking=True).permute(0, 1, 4, 2, 3).to(torch.float32)
+                dn = staged.permute(0, 1, 4, 2, 3).to(torch.float32)
                 dn = ((dn / 255.0 - 0.5) / 0.5).contiguous()                      # [Tc,B,3,H,W]
             gtd = gt.to(g.device) if gt is not None else None
-            if clip.measure:                   # the GT frames normalised as the DAIN frames are; masks 0/1 -> float
+            gtf = staged_gt = None
+            if clip.want_gt:
+                staged_gt = clip.stage_gt[ui].to(g.device, non_blocking=True)
+            if clip.measure:                   # the GT frames normalised as the DAIN frames are
                 if clip.src_gt is not None:
-                    gtf = g.resize_u8(clip.stage_gt[ui].to(g.device, non_blocking=True).flatten(0, 1), ev.width, ev.height, normalised=True)
+                    gtf = g.resize_u8(staged_gt.flatten(0, 1), ev.width, ev.height, normalised=True)
                 else:
-                    gtf = clip.stage_gt[ui].to(g.device, non_blocking=True).permute(0, 1, 4, 2, 3).to(torch.float32)
+                    gtf = staged_gt.permute(0, 1, 4, 2, 3).to(torch.float32)
                     gtf = ((gtf / 255.0 - 0.5) / 0.5).reshape(Tc * Bc, 3, ev.height, ev.width).contiguous()
+            if clip.measure:                   # masks 0/1 -> float
                 mk = (clip.stage_mask[ui].to(g.device, non_blocking=True).to(torch.float32).reshape(Tc * Bc, ev.height, ev.width)
                       if ui in clip.stage_mask else None)
                 if self.pose_mask:             # drawn here from the unit's own peaks (rib_human_mask): no file, no staging
                     mk = g.human_mask(np.stack([self.peaks_of(p_) for p_ in poses]), ev.height, ev.width)
                 clip.meas[ui] = (gtf, mk)
+            if self.panels:
+                if self.titles_dev is None:
+                    self.titles_dev = torch.from_numpy(self.titles).to(g.device)
+                if c0 == 0:
+                    clip.key_of[gi] = gtd
+                # the DAIN / Ground Truth panes show the bytes tensor2images makes of the HOST's tensors (normalise_exact says why the
+                # tensors the generator and the metrics read - normalised with torch's reciprocal - are not shown); frames staged at
+                # their source size (resize_on="gpu") come out of the resize kernel as uint8 first
+                def shown(u8, src):
+                    if src is not None:
+                        u8 = g.resize_u8(u8.flatten(0, 1), ev.width, ev.height)
+                    return normalise_exact(u8).reshape(Tc * Bc, 3, ev.height, ev.width)
+                dnp = shown(staged, clip.src_dain)
+                kdn = normalise_exact(clip.stage_key[ui].to(g.device, non_blocking=True)) if key_poses else None
+                if staged_gt is not None:
+                    gtp = shown(staged_gt, clip.src_gt)
+                else:                          # no gt_dir: the Ground Truth pane is the segment's left key frame (evaluator.py:209-212)
+                    keys = clip.key_of[gi]
+                    gtp = keys.unsqueeze(0).expand(Tc, *keys.shape).reshape(Tc * Bc, *keys.shape[1:])
+                clip.pan[ui] = (gtp, klab, kdn, clip.key_of[gi], dnp)
             ready = torch.cuda.Event()
             ready.record(self.up)
-        for t_ in (lab, dn, gtd) + tuple(clip.meas.get(ui, ())):
+        for t_ in (lab, dn, gtd) + tuple(clip.meas.get(ui, ())) + tuple(clip.pan.get(ui, ())):
             if t_ is not None:
                 t_.record_stream(st)
         return lab, dn, gtd, ready
@@ -867,8 +973,10 @@ class _FolderPipeline:
         gi, _, c0, _ = clip.units[ui]
         with torch.cuda.stream(st):
             st.wait_event(ready)
-            fz = g.chain(gtd if c0 == 0 else clip.prev_of[gi], lab, dn, want_all=False)[2]      # [Tc,B,3,H,W]
+            imgs, masks, fz = g.chain(gtd if c0 == 0 else clip.prev_of[gi], lab, dn, want_all=self.panels)      # fz [Tc,B,3,H,W]
             clip.prev_of[gi] = fz[-1]
+            if self.panels:
+                return self._render_panels(clip, ui, g, st, imgs, masks, fz, lab, dn, gtd)
             if clip.measure:
                 return self._render_measured(clip, ui, g, st, fz, lab, dn, gtd)
             q = g.quantise(fz.reshape(-1, *fz.shape[2:]))                  # [Tc*B,H,W,3] uint8
@@ -905,6 +1013,93 @@ class _FolderPipeline:
         return {"done": done, "pinned": flat[:nq].view(q.shape), "out_blk": out_blk, "keep": (fz, q, lab, dn, gtd, buf, gtf, mk),
                 "qual": flat[off:].view(torch.float32).view(4, n)}
 
+    def _render_panels(self, clip, ui, g, st, imgs, masks, fz, lab, dn, gtd):
+        """render() of a unit under panels=True (on the lane's stream, inside its stream context): one device buffer,
+        [uint8 frames | float32 [4, Tc*B] metrics (measured units) | uint8 sheets [Tc*B + keys, SH, SW, 3]], filled by the
+        quantiser, rib_quality and rib_panel - one launch for the unit's frames and, in a first chunk, one in key-frame mode for
+        the key frames the unit starts from - and brought home in the unit's one device-to-host copy."""
+        t0 = time.perf_counter()
+        n = fz.shape[0] * fz.shape[1]
+        H, W = fz.shape[3], fz.shape[4]
+        frames = fz.reshape(n, 3, H, W)
+        nq = frames.numel()
+        SH, SW = self.sheet_hw
+        gtp, klab, kdn, keys, dnp = clip.pan.pop(ui)
+        nk = kdn.shape[0] if kdn is not None else 0
+        off_v = (nq + 255) // 256 * 256
+        off_s = (off_v + (4 * n * 4 if clip.measure else 0) + 255) // 256 * 256
+        total = off_s + (n + nk) * SH * SW * 3
+        buf = torch.empty(total, dtype=torch.uint8, device=g.device)
+        q = g.quantise(frames, out=buf[:nq].view(n, H, W, 3))
+        keep = [fz, imgs, masks, q, lab, dn, gtd, buf, gtp, klab, kdn, keys, dnp]
+        if clip.measure:
+            vals = buf[off_v:off_v + 16 * n].view(torch.float32).view(4, n)
+            gtm, mk = clip.meas.pop(ui)
+            g.quality(frames, gtm, mk, out=vals[0:2])
+            g.quality(dn.reshape(n, 3, H, W), gtm, mk, out=vals[2:4])
+            keep += [gtm, mk]
+        sheets = buf[off_s:].view(n + nk, SH, SW, 3)
+        g.panel(imgs.reshape(n, 3, H, W), masks.reshape(n, 1, H, W), frames, dnp, gtp, lab.reshape(n, *lab.shape[2:]),
+                titles=self.titles_dev, out=sheets[:n])
+        if nk:
+            g.panel(None, None, None, kdn, keys, klab, titles=self.titles_dev, out=sheets[n:])
+        out_blk = _shm_get(total) if self.procs is not None else None
+        flat = out_blk.t[:total] if out_blk is not None else torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        flat.copy_(buf, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(st)
+        self.tm["panels"] = self.tm.get("panels", 0.0) + time.perf_counter() - t0
+        _, members, c0, _ = clip.units[ui]
+        return {"done": done, "pinned": flat[:nq].view(q.shape), "out_blk": out_blk, "keep": tuple(keep),
+                "qual": flat[off_v:off_v + 16 * n].view(torch.float32).view(4, n) if clip.measure else None,
+                "sheets": flat[off_s:].view(n + nk, SH, SW, 3), "sheet_off": off_s,
+                "sheet_frames": clip.unit_frames(ui) + ([clip.segs[si][0] for si in members] if nk else [])}
+
+    def save_sheets(self, clip, frames, sheets, out_blk=None, off=0):
+        """Submits the encodes of the sheets of `frames` (uint8 [n, SH, SW, 3] on the host; out_blk: the shared block they lie
+        in, from byte `off`) -> futures."""
+        SH, SW = self.sheet_hw
+        if out_blk is not None:
+            return [self.procs.submit(io_worker.save_sheet_shm, out_blk.name, off + j * SH * SW * 3, SH, SW,
+                                      *clip.sheet_names(i, self.panel_frames), self.panel_quality) for j, i in enumerate(frames)]
+        sn = sheets.numpy()
+        return [self.pool.submit(io_worker.save_sheet, sn[j], *clip.sheet_names(i, self.panel_frames), self.panel_quality)
+                for j, i in enumerate(frames)]
+
+    def loose_key_sheets(self, clip, g, st):
+        """panels: the sheets of this rank's key frames that start no unit of its own (a clip's last key frame; every key frame of
+        a model that renders nothing): a small unit of their own - labels, one rib_panel launch in key-frame mode, one copy."""
+        ev = self.ev
+        loose = [k for k in clip.keys if k not in clip.key_slot]
+        if not loose:
+            return
+        got = [clip.loads[k].result(timeout=IO_TIMEOUT_S) for k in loose]
+        dains = list(self.pool.map(lambda k: ev.load_image_u8(clip.dain_list[k])[0], loose))
+        poses = [g_[2] for g_ in got]
+        with torch.cuda.stream(st):
+            if self.gpu_labels:
+                klab = rasterise.rasterise_tables(g, poses, ev.height, ev.width, ev.gauss_sigma)
+            else:
+                klab = ev.make_labels(g if hasattr(g, "rasterise") else self.model, poses).to(g.device)
+            if self.titles_dev is None:
+                self.titles_dev = torch.from_numpy(self.titles).to(g.device)
+            kdn = normalise_exact(torch.stack(dains).to(g.device))
+            keys = torch.stack([g_[1] for g_ in got]).to(g.device)
+            sheets = g.panel(None, None, None, kdn, keys, klab, titles=self.titles_dev)
+            out_blk = _shm_get(sheets.numel()) if self.procs is not None else None
+            pinned = (out_blk.t[:sheets.numel()] if out_blk is not None else torch.empty(sheets.numel(), dtype=torch.uint8, pin_memory=True)).view(sheets.shape)
+            pinned.copy_(sheets, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(st)
+
+        def finish(keep=(sheets, kdn, keys, klab)):
+            done.synchronize()
+            res = [f.result(timeout=IO_TIMEOUT_S) for f in self.save_sheets(clip, loose, pinned, out_blk)]
+            if out_blk is not None:
+                _shm_put(out_blk)
+            return res
+        clip.sheet_futs.append(self.finishers.submit(finish))
+
     # ---- stage 4: sink ---------------------------------------------------------------------------------------------------
     def sink(self, clip, ui, r, t_loaded, t_enq):
         """Runs on a finisher thread: waits for the unit's copy, hands the staging block back, fans the PNG encodes out and
@@ -921,19 +1116,26 @@ class _FolderPipeline:
         clip.stage.pop(ui, None)                # (the views of the block go before the block does)
         clip.stage_gt.pop(ui, None)
         clip.stage_mask.pop(ui, None)
+        clip.stage_key.pop(ui, None)
         if in_blk is not None:
             _shm_put(in_blk)
         out_blk = r["out_blk"]
+        # panels: the JPEG (and PNG) encodes of the unit's sheets fan out beside the PNG encodes of its frames
+        sheet_fs = self.save_sheets(clip, r["sheet_frames"], r["sheets"], out_blk, r["sheet_off"]) if r.get("sheets") is not None else []
         if out_blk is not None:
             fsz = ev.height * ev.width * 3
             fs = [self.procs.submit(io_worker.save_png_shm, out_blk.name, j * fsz, ev.height, ev.width, clip.names[out_frames[j]], self.level)
                   for j in range(len(out_frames))]
             res = [f.result(timeout=IO_TIMEOUT_S) for f in fs]
-            r["pinned"] = None
+            for f in sheet_fs:
+                f.result(timeout=IO_TIMEOUT_S)
+            r["pinned"] = r["sheets"] = None
             _shm_put(out_blk)
         else:
             qn = r["pinned"].numpy()
             res = list(self.pool.map(lambda j: self.save_q(qn[j], clip.names[out_frames[j]]), range(len(out_frames))))
+            for f in sheet_fs:
+                f.result(timeout=IO_TIMEOUT_S)
         r["keep"] = None
         mark.append(round(time.perf_counter() - self.t_wall, 4))
         return res
@@ -965,6 +1167,8 @@ class _FolderPipeline:
                 clip.futs[i] = (seg_fut, j)
         for k in clip.keys:
             self.submit_load(clip, k)
+        if self.panels:
+            self.loose_key_sheets(clip, *(lanes[0] if lanes else (self.model, torch.cuda.current_stream(self.model.device))))
         tm["units"] = tm.get("units", 0) + len(clip.units)
         tm["frames"] += len(clip.futs)
 
@@ -983,15 +1187,24 @@ class _FolderPipeline:
             dn = torch.stack([g[0] for g in got]).unsqueeze(1)
             lab = ev.make_labels(model, poses).unsqueeze(1)
             t2 = time.perf_counter()
-            prev, outs = gt, []
+            prev, outs, shown = gt, [], []
             for t in range(len(frames)):
                 img, mask = model(lab[t], None, dn[t], prev)
                 prev = img * mask.repeat(1, 3, 1, 1) + dn[t].to(img.device) * (1 - mask.repeat(1, 3, 1, 1))
                 outs.append(prev)
+                shown.append((img, mask))
             tm["rasterise"] += t2 - t1
             tm["generate"] += time.perf_counter() - t2
             for t, i in enumerate(frames):
                 clip.futs[i] = self.pool.submit(self.save_host, outs[t], clip.names[i])
+            if self.panels:                      # the host statement of the sheet (panel.compose_host), a segment at a time
+                def host(xs):
+                    return torch.cat([x.detach().cpu().float() for x in xs]).numpy()
+                gtp = [ev.load_image(clip.gtlist[i])[0].unsqueeze(0) for i in frames] if clip.gtlist is not None else [gt] * len(frames)
+                sheets = _panel.compose_host(host([p_[0] for p_ in shown]), host([p_[1] for p_ in shown]), host(outs), host(list(dn)),
+                                             host(gtp), host(list(lab)), self.titles)
+                for t, i in enumerate(frames):
+                    clip.sheet_futs.append(self.pool.submit(io_worker.save_sheet, sheets[t], *clip.sheet_names(i, self.panel_frames), self.panel_quality))
             if clip.measure:                     # the torch statement of the metric (metrics.py), frame by frame
                 t3 = time.perf_counter()
                 vals = np.zeros((4, len(frames)))
@@ -1006,6 +1219,12 @@ class _FolderPipeline:
                         vals[row, t], vals[row + 1, t] = float(p_[0]), float(s_[0])
                 self.record(clip, frames, vals)
                 tm["metrics"] += time.perf_counter() - t3
+        if self.panels:                          # the key frames' sheets: the key-frame rule
+            for k in clip.keys:
+                dain, key, pose = clip.loads[k].result()
+                klab = ev.make_labels(model, [pose]).detach().cpu().float().numpy()
+                sheet = _panel.compose_host(None, None, None, dain.unsqueeze(0).numpy(), key.unsqueeze(0).numpy(), klab, self.titles)[0]
+                clip.sheet_futs.append(self.pool.submit(io_worker.save_sheet, sheet, *clip.sheet_names(k, self.panel_frames), self.panel_quality))
         tm["units"] = tm.get("units", 0)
         tm["frames"] += len(clip.futs)
 
@@ -1052,6 +1271,20 @@ class _FolderPipeline:
         self.tm["metrics"] = self.tm.get("metrics", 0.0) + time.perf_counter() - t0
         return recs, rep
 
+    def assemble_panels(self, save_dir, fps):
+        """After drain(): every rank's sheets are in <save_dir>/<clip>_panels/ - rank 0 (after a barrier, under a process group)
+        makes <save_dir>/<clip>.avi of each clip's folder (panel.assemble).  Ranks dealt by hand (rank / world arguments without a
+        process group) cannot know when the others are done: the caller assembles."""
+        t0 = time.perf_counter()
+        import torch.distributed as dist
+        grouped = self.world > 1 and dist.is_available() and dist.is_initialized()
+        if grouped:
+            dist.barrier()
+        if self.world == 1 or (grouped and self.rank == 0):
+            for clip in self.clips:
+                _panel.assemble(save_dir, clip.sub, fps, keep_frames=self.panel_frames)
+        self.tm["panels"] = self.tm.get("panels", 0.0) + time.perf_counter() - t0
+
     def drain(self):
         """Waits for every file of the call, in frame order as the reference writes them; returns the names this rank wrote."""
         written: List[str] = []
@@ -1064,6 +1297,8 @@ class _FolderPipeline:
                 res = f[0].result()[f[1]] if isinstance(f, tuple) else f.result()
                 assert res == name
                 written.append(name)
+            for f in clip.sheet_futs:                                              # panels: sheets that rode in no unit's sink
+                f.result()
         self.tm["save"] = time.perf_counter() - t5                                 # tail: encodes still running after the last enqueue
         self.tm["wall"] = time.perf_counter() - self.t_wall
         return written

@@ -507,6 +507,48 @@ class Generator:
             _native.check(self._h, self._lib.rib_human_mask(self._h, T, height, width, peaks.ctypes.data, n, _ptr(out), self._stream()))
         return out
 
+    def panel(self, pred, mask, fuse, dain, gt, label, titles=None, out=None):
+        """The six-pane diagnostic sheets of T frames composed on the GPU (rib_panel, csrc/panel.hip.h; panel.compose_host is
+        the definition and is bit-equal): float32 device tensors pred, fuse, dain, gt [T,3,H,W], mask [T,1,H,W], label
+        [T,label_nc,H,W] -> uint8 [T,SH,SW,3] (panel.layout), one launch on the current stream, every byte written.
+        pred, mask and fuse None together: key-frame mode (Predict = Fuse = gt, Mask = 0).
+        titles: 0/1 [2,24,SW] (panel.title_bitmap; a host array is uploaded once per width and kept), or None: no text.
+        out: optional contiguous uint8 destination of the result's shape, e.g. a view into a larger buffer."""
+        from . import panel as P
+        if (pred is None) != (mask is None) or (pred is None) != (fuse is None):
+            raise ValueError("panel: pred, mask and fuse are None together (key-frame mode) or not at all")
+        dain = self._prep(dain, 3, "dain")
+        T, _, H, W = dain.shape
+        gt = self._prep(gt, 3, "gt", (T, H, W))
+        if not torch.is_tensor(label) or label.dim() != 4 or label.shape[1] < 3:
+            raise ValueError("panel: label must be a [T,>=3,H,W] tensor, got %s" % (tuple(getattr(label, "shape", ())),))
+        label = self._prep(label, label.shape[1], "label", (T, H, W))
+        if pred is not None:
+            pred, fuse = self._prep(pred, 3, "pred", (T, H, W)), self._prep(fuse, 3, "fuse", (T, H, W))
+            mask = self._prep(mask, 1, "mask", (T, H, W))
+        SH, SW = P.layout(H, W)["sheet"]
+        if titles is not None and not (torch.is_tensor(titles) and titles.device == self.device):
+            import numpy as np
+            host = np.ascontiguousarray(titles.cpu().numpy() if torch.is_tensor(titles) else titles)
+            if host.shape != (2, P.TITLE_H, SW):
+                raise ValueError("panel: titles must be [2, %d, %d], got %s" % (P.TITLE_H, SW, host.shape))
+            cache = self.__dict__.setdefault("_panel_titles", {})
+            key = (SW, host.tobytes())
+            if key not in cache:
+                cache[key] = torch.from_numpy((host != 0).astype(np.uint8)).to(self.device)
+            titles = cache[key]
+        if titles is not None and (tuple(titles.shape) != (2, P.TITLE_H, SW) or titles.dtype != torch.uint8 or not titles.is_contiguous()):
+            raise ValueError("panel: titles must be a contiguous uint8 [2, %d, %d] tensor" % (P.TITLE_H, SW))
+        if out is None:
+            out = torch.empty((T, SH, SW, 3), dtype=torch.uint8, device=self.device)
+        elif tuple(out.shape) != (T, SH, SW, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("panel: out must be a contiguous uint8 %s tensor on %s" % ((T, SH, SW, 3), self.device))
+        with torch.cuda.device(self.device):
+            _native.check(self._h, self._lib.rib_panel(
+                self._h, T, H, W, label.shape[1], _ptr(pred), _ptr(mask), _ptr(fuse), _ptr(dain), _ptr(gt), _ptr(label),
+                _ptr(titles), _ptr(out), self._stream()))
+        return out
+
     # ---- introspection / measurement -----------------------------------------------------------
     def enable_taps(self, on=True):
         """Debug: keep every tapped intermediate intact until the end of a forward (buffers with disjoint lifetimes

@@ -16,6 +16,11 @@ Ground-truth metrics (new; the reference measures only in evaluate_from_dataset)
 measures every generated frame and its DAIN frame against DIR/<clip>/ (PSNR / SSIM of Evaluator.compute_metrics) and writes
 <save-dir>/Generated_frames/metrics.json.  `--pose-mask` measures under the human-centric mask the reference measures under
 (_generate_human_mask, drawn from each frame's own pose on the GPU; restated from OpenCV's drawing, unpinned).
+
+Diagnostic sheets (the counterpart of the reference's gen_vid=True): `--panels [--panel-frames] [--panel-quality Q] [--panel-fps N]`
+composes, per frame, Predict | Mask | Fuse over DAIN | Ground Truth | Skeleton on the GPU and writes
+<save-dir>/Generated_frames/<clip>.avi (Motion-JPEG in a plain RIFF AVI: no H.264 encoder is available here; the layout and the
+titles are this project's, not matplotlib's); `--panel-frames` keeps the lossless sheets in <clip>_panels/%04d.png.
 """
 import argparse
 import os
@@ -112,7 +117,10 @@ def main(opts):
     pose_dir = os.path.join(opts.input_dir, "Predict_motion")
     save_dir = os.path.join(opts.save_dir, "Generated_frames")
     written = evaluator.evaluate_from_folder(net_G, train_dir, dain_dir, pose_dir, save_dir, gt_dir=opts.gt_dir, gen_vid=False,
-                                             metrics=opts.metrics, mask_dir=opts.mask_dir, pose_mask=opts.pose_mask)
+                                             metrics=opts.metrics, mask_dir=opts.mask_dir, pose_mask=opts.pose_mask,
+                                             panels=opts.panels, panel_frames=opts.panel_frames,
+                                             panel_quality=90 if opts.panel_quality is None else opts.panel_quality,
+                                             panel_fps=30 if opts.panel_fps is None else opts.panel_fps)
     print(summary_line(evaluator, rank, world))
     if world > 1:
         print("[rank {}/{}] wrote {} frames".format(rank, world, len(written)))
@@ -158,6 +166,14 @@ def build_parser():
                              "(default): by the file workers, as the reference does; 'gpu': decoded at their own size and resized by the "
                              "HIP kernel, bit-exact to the host resize - the same files, less CPU per frame when the inputs are larger "
                              "than the model size (key frames stay on the host)")
+    parser.add_argument("--panels", action="store_true",
+                        help="also compose a six-pane diagnostic sheet per frame on the GPU (Predict, Mask, Fuse / DAIN, Ground Truth, "
+                             "Skeleton) and write <save-dir>/Generated_frames/<clip>.avi, Motion-JPEG (the counterpart of the "
+                             "reference's gen_vid; the frames themselves are unchanged)")
+    parser.add_argument("--panel-frames", action="store_true",
+                        help="with --panels: keep the lossless sheets as <clip>_panels/%%04d.png (the reference's save_frame)")
+    parser.add_argument("--panel-quality", type=int, default=None, help="with --panels: JPEG quality of the video's frames, 1-100 (default 90)")
+    parser.add_argument("--panel-fps", type=float, default=None, help="with --panels: frames per second of the video (default 30)")
     return parser
 
 
@@ -174,6 +190,12 @@ def parse_args(argv=None):
         parser.error("--pose-mask is a setting of --metrics")
     if opts.pose_mask and opts.mask_dir is not None:
         parser.error("--pose-mask and --mask-dir are two sources of the one mask: give one of them")
+    if not opts.panels and (opts.panel_frames or opts.panel_quality is not None or opts.panel_fps is not None):
+        parser.error("--panel-frames, --panel-quality and --panel-fps are settings of --panels")
+    if opts.panel_quality is not None and not 1 <= opts.panel_quality <= 100:
+        parser.error("--panel-quality must be in 1..100")
+    if opts.panel_fps is not None and not opts.panel_fps > 0:
+        parser.error("--panel-fps must be positive")
     return opts
 
 

@@ -153,6 +153,18 @@ def save_png_shm(shm_name, offset, height, width, name, compress_level=None):
     return save_png(np.ndarray((height, width, 3), np.uint8, buffer=_attach(shm_name).buf, offset=offset), name, compress_level)
 
 
+def save_sheet(u8, jpg_name, png_name=None, quality=90):
+    """A diagnostic sheet uint8 [SH, SW, 3] (panel.py) -> its JPEG, the frame of the clip's video, and with png_name the
+    lossless copy (Evaluator panels / panel_frames)."""
+    from . import panel
+    return panel.save_sheet(u8, jpg_name, quality, png_name)
+
+
+def save_sheet_shm(shm_name, offset, height, width, jpg_name, png_name=None, quality=90):
+    """save_sheet of the sheet at bytes [offset, ..) of a shared block."""
+    return save_sheet(np.ndarray((height, width, 3), np.uint8, buffer=_attach(shm_name).buf, offset=offset), jpg_name, png_name, quality)
+
+
 def warm():
     """Initialiser of a fresh worker process.  (1) One BLAS / OpenMP thread: numpy's OpenBLAS starts one thread per core of the
     host in EVERY process and they spin between calls - 32 workers x 256 threads on the GPU boxes made a 10 ms decode take 500 ms
