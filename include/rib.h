@@ -245,6 +245,29 @@ int rib_human_mask(rib_handle* h, int T, int H, int W, const int32_t* peaks, int
  * out, or only some of pred / mask / fuse NULL: RIB_ERR_INVALID with a rib_last_error text, nothing launched. */
 int rib_panel(rib_handle* h, int T, int H, int W, int label_nc, const float* pred, const float* mask, const float* fuse,
               const float* dain, const float* gt, const float* label, const uint8_t* titles, uint8_t* out, void* hip_stream);
+/* ---- baseline JPEG of the diagnostic sheets, encoded on the GPU (the video frames of evaluate_from_folder(panels=True)) ----
+ * T images uint8 NHWC [T,H,W,3] on the device -> T complete JFIF files: baseline sequential DCT (SOF0), 8 bit, Y Cb Cr 4:2:0
+ * (MCU 16 x 16: Y00 Y01 Y10 Y11 Cb Cr), one interleaved scan, the Annex K quantisation tables of ITU-T T.81 under the IJG
+ * quality scaling (quality 1..100) and the four Annex K Huffman tables - the tables PIL writes by default - with a restart
+ * interval of one MCU row (DRI = ceil(W/16); RST0..7 cycle), which is what makes the encoder parallel.  Sizes that are no
+ * multiple of 16 repeat the last column and row.  The stream is this project's, restated from T.81, unpinned: panel.py
+ * (jpeg_encode_host) states every byte in integer arithmetic - fixed-point colour conversion, a 13-bit integer DCT with a
+ * rounding shift per pass, division to the nearest with halves away from zero - and the kernels are bit-equal to it.
+ * Frame t's file starts at dst + t * dst_stride and lengths[t] (device, int32) receives its size.  rib_jpeg_max_bytes(H, W)
+ * is an upper bound of one file, header included (a block codes at most 64 symbols of at most 16 + 11 bits, every byte may be
+ * stuffed); with dst_stride >= rib_jpeg_max_bytes no frame is refused.  A smaller dst_stride (at least the 629-byte header
+ * and EOI) is allowed: a frame whose file would not fit writes nothing and gets lengths[t] = 0 - the call only enqueues and
+ * returns RIB_OK, the caller reads the refusal from lengths.  Bytes of a frame's stride behind lengths[t] are not written.
+ * workspace: rib_jpeg_workspace_bytes(h, T, H, W) bytes on the device, 16-byte aligned (one staging slot per restart segment,
+ * sized by the same bound, and the segment lengths); nothing has to be cleared.
+ * Enqueues two launches on `stream` (segments; lengths scan + assembly), no synchronisation, no atomics on global memory, no
+ * floats: a frame's bytes do not depend on T.  T outside 1..65535, H or W outside 1..65535, quality outside 1..100, a
+ * dst_stride below 631 or of 2 GiB or more, a NULL or misaligned pointer: RIB_ERR_INVALID with a rib_last_error text, nothing
+ * launched (the two size queries return 0). */
+size_t rib_jpeg_workspace_bytes(rib_handle* h, int T, int H, int W);
+size_t rib_jpeg_max_bytes(int H, int W);
+int rib_jpeg(rib_handle* h, int T, int H, int W, const uint8_t* src_u8_nhwc, int quality,
+             uint8_t* dst, size_t dst_stride, int32_t* lengths, void* workspace, void* hip_stream);
 
 /* Extension op named by the north star but absent from the reference: bilinear
  * flow-grid warp, semantics of torch.nn.functional.grid_sample(img, base+flow*2/(size-1),

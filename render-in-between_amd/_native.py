@@ -65,6 +65,9 @@ SIGNATURES = {
                                 C.c_void_p]),
     "rib_human_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "rib_panel": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 9),
+    "rib_jpeg_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "rib_jpeg_max_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "rib_jpeg": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rib_set_debug_taps": (C.c_int, [C.c_void_p, C.c_int]),
     "rib_num_taps": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "rib_tap_info": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char_p),

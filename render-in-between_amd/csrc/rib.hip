@@ -15,6 +15,7 @@
 #include "resize.hip.h"
 #include "human_mask.hip.h"
 #include "panel.hip.h"
+#include "jpeg.hip.h"
 #include <hip/hip_ext.h>
 #include "../../include/rib.h"
 
@@ -3015,6 +3016,49 @@ int rib_panel(rib_handle* h, int T, int H, int W, int label_nc, const float* pre
   HIP_TRY(h, hipSetDevice(h->device));
   const size_t lds = (size_t)pp.SW * 3 + 32;             // the row at its phase inside a 16-byte line, rounded up to whole lines
   RIB_KLAUNCH(k_panel, dim3(pp.SH, T), dim3(256), lds, reinterpret_cast<hipStream_t>(hip_stream), pp);
+  HIP_TRY(h, hipGetLastError());
+  return RIB_OK;
+}
+
+size_t rib_jpeg_max_bytes(int H, int W) {
+  if (H < 1 || W < 1 || H > JPEG_MAX_DIM || W > JPEG_MAX_DIM) return 0;
+  const size_t rows = (size_t)(H + 15) / 16;
+  return (size_t)JPEG_HEADER_BYTES + rows * jpeg_seg_bound((W + 15) / 16) + 2 * (rows - 1) + 2;
+}
+
+size_t rib_jpeg_workspace_bytes(rib_handle* h, int T, int H, int W) {
+  if (!h || T < 1 || T > 65535 || H < 1 || W < 1 || H > JPEG_MAX_DIM || W > JPEG_MAX_DIM) return 0;
+  const size_t segs = (size_t)T * ((size_t)(H + 15) / 16);
+  return segs * jpeg_seg_bound((W + 15) / 16) + 256 + segs * sizeof(int32_t);      // the slots, then the segment lengths
+}
+
+int rib_jpeg(rib_handle* h, int T, int H, int W, const uint8_t* src_u8_nhwc, int quality, uint8_t* dst, size_t dst_stride,
+             int32_t* lengths, void* workspace, void* hip_stream) {
+  if (!h) return RIB_ERR_INVALID;
+  if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_jpeg: host-only handle");
+  if (!src_u8_nhwc || !dst || !lengths || !workspace) return fail(h, RIB_ERR_INVALID, "rib_jpeg: null pointer");
+  if (T < 1 || T > 65535 || H < 1 || W < 1 || H > JPEG_MAX_DIM || W > JPEG_MAX_DIM || quality < 1 || quality > 100)
+    return fail(h, RIB_ERR_INVALID, fmt("rib_jpeg: T=%d H=%d W=%d quality=%d: 1 <= T <= 65535, H and W in 1..%d, quality in 1..100",
+                                        T, H, W, quality, JPEG_MAX_DIM));
+  if (dst_stride < (size_t)JPEG_HEADER_BYTES + 2 || dst_stride > (size_t)INT32_MAX)
+    return fail(h, RIB_ERR_INVALID, fmt("rib_jpeg: dst_stride=%zu: at least the header (%d bytes) and EOI, below 2 GiB", dst_stride, JPEG_HEADER_BYTES));
+  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0 || (reinterpret_cast<uintptr_t>(lengths) & 3) != 0)
+    return fail(h, RIB_ERR_INVALID, "rib_jpeg: workspace must be 16-byte aligned, lengths 4-byte aligned");
+  JpegParams jp;
+  jp.src = src_u8_nhwc; jp.H = H; jp.W = W; jp.quality = quality;
+  jp.rows = (H + 15) / 16; jp.cols = (W + 15) / 16;
+  jp.slot = (uint32_t)jpeg_seg_bound(jp.cols);
+  const size_t segs = (size_t)T * jp.rows;
+  jp.seg = static_cast<uint8_t*>(workspace);
+  jp.seglen = reinterpret_cast<int32_t*>(jp.seg + (segs * jp.slot + 255) / 256 * 256);
+  JpegAssembleParams ap;
+  ap.seg = jp.seg; ap.seglen = jp.seglen; ap.dst = dst; ap.lengths = lengths; ap.dst_stride = dst_stride; ap.rows = jp.rows; ap.slot = jp.slot;
+  jpeg_make_header(ap.header, H, W, quality);
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  RIB_KLAUNCH(k_jpeg_segments, dim3(jp.rows, T), dim3(256), 0, st, jp);
+  HIP_TRY(h, hipGetLastError());
+  RIB_KLAUNCH(k_jpeg_assemble, dim3(jp.rows, T), dim3(256), 0, st, ap);
   HIP_TRY(h, hipGetLastError());
   return RIB_OK;
 }

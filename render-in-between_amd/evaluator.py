@@ -515,7 +515,7 @@ class Evaluator:
     @torch.no_grad()
     def evaluate_from_folder(self, model, train_dir, dain_dir, pose_dir, save_dir, gt_dir=None, gen_vid=False,
                              rank=None, world=None, metrics=False, mask_dir=None, pose_mask=False,
-                             panels=False, panel_frames=False, panel_quality=90, panel_fps=30):
+                             panels=False, panel_frames=False, panel_quality=90, panel_fps=30, panel_encode="host"):
         """rank / world: this process's share of the independent units (default: the torch.distributed process
         group when one is initialised, else everything).  Returns the frames THIS rank wrote.
         The call is one `_FolderPipeline` (below): plan a clip -> decode -> upload -> render -> sink, pipelined over units
@@ -534,14 +534,22 @@ class Evaluator:
         and ride home in the unit's one copy; a model that only speaks the reference's protocol goes through
         panel.compose_host.  Rank 0 then muxes <save_dir>/<clip>.avi (Motion-JPEG, panel_fps frames/s; panel.assemble) from the
         folder, removes the JPEG sheets and - unless panel_frames - the folder.  (Ranks without a process group cannot know when
-        the others are done: the caller runs panel.assemble once they are.)  panels=False changes nothing."""
+        the others are done: the caller runs panel.assemble once they are.)  panels=False changes nothing.
+        panel_encode="gpu" (with panels; default "host": PIL in the file workers, the files of before): the sheets' JPEG files
+        are panel.jpeg_encode_host's bytes - baseline 4:2:0 with the tables PIL uses, one restart segment per MCU row, stated in
+        integers - written on the native path by rib_jpeg right behind rib_panel: the lengths ride home in the unit's copy, the
+        finisher then fetches exactly the files' bytes and writes %04d.jpg itself, no worker and no PIL involved; the raw sheets
+        stay on the device unless panel_frames wants the lossless copies.  A model behind the reference's protocol encodes
+        with jpeg_encode_host on the host: the same files."""
         if gen_vid:
             # the reference also writes <save_dir>/<clip>.mp4 (evaluator.py:267-269, utils.make_video) from a matplotlib canvas
             # through an H.264 encoder; neither is built, and silently ignoring the flag would drop an output the caller asked for
             raise NotImplementedError("evaluate_from_folder: gen_vid (the matplotlib / mp4 video) is not supported; panels=True "
                                       "writes the six-pane sheets as <save_dir>/<clip>.avi")
-        if not panels and (panel_frames or panel_quality != 90 or panel_fps != 30):
-            raise ValueError("evaluate_from_folder: panel_frames, panel_quality and panel_fps are settings of panels=True")
+        if panel_encode not in ("host", "gpu"):
+            raise ValueError("evaluate_from_folder: panel_encode must be 'host' or 'gpu', got %r" % (panel_encode,))
+        if not panels and (panel_frames or panel_quality != 90 or panel_fps != 30 or panel_encode != "host"):
+            raise ValueError("evaluate_from_folder: panel_frames, panel_quality, panel_fps and panel_encode are settings of panels=True")
         if panels and not (1 <= int(panel_quality) <= 100 and float(panel_fps) > 0):
             raise ValueError("evaluate_from_folder: panel_quality must be in 1..100 and panel_fps positive")
         if metrics and gt_dir is None:
@@ -561,7 +569,8 @@ class Evaluator:
             self._finishers = ThreadPoolExecutor(max(4, self.lanes + 2))  # wait for a unit's copy, then fan out its encodes
         self.metrics = self.metrics_report = None
         pipe = _FolderPipeline(self, model, rank, world, gt_dir, metrics=bool(metrics), mask_dir=mask_dir, pose_mask=bool(pose_mask),
-                               panels=bool(panels), panel_frames=bool(panel_frames), panel_quality=int(panel_quality))
+                               panels=bool(panels), panel_frames=bool(panel_frames), panel_quality=int(panel_quality),
+                               panel_encode=panel_encode)
         self.timings = pipe.tm
         if metrics and pipe.native:
             self._quality_model = model
@@ -652,7 +661,7 @@ class _FolderPipeline:
     (tests/test_driver.py)."""
 
     def __init__(self, ev, model, rank, world, gt_dir, metrics=False, mask_dir=None, pose_mask=False,
-                 panels=False, panel_frames=False, panel_quality=90):
+                 panels=False, panel_frames=False, panel_quality=90, panel_encode="host"):
         self.ev, self.model, self.rank, self.world, self.gt_dir = ev, model, rank, world, gt_dir
         self.metrics, self.mask_dir, self.pose_mask = metrics, mask_dir, pose_mask
         self.panels, self.panel_frames, self.panel_quality = panels, panel_frames, panel_quality
@@ -665,11 +674,15 @@ class _FolderPipeline:
             raise RuntimeError("resize_on='gpu': this model has no GPU resize kernel (rib_resize_cubic)")
         if self.native and panels and not hasattr(model, "panel"):
             raise RuntimeError("panels=True: this model has no GPU sheet kernel (rib_panel)")
+        self.jpeg_gpu = panels and panel_encode == "gpu"     # the sheets' JPEG files are jpeg_encode_host's bytes (rib_jpeg on the native path)
+        if self.native and self.jpeg_gpu and not hasattr(model, "jpeg_into"):
+            raise RuntimeError("panel_encode='gpu': this model has no GPU JPEG kernels (rib_jpeg)")
         self.gpu_labels = self.native and ev.label_fn is None and hasattr(model, "rasterise")
         per_slot = (1.0 + (1.0 if (metrics or (panels and gt_dir is not None)) else 0.0) + (1.0 / 3 if mask_dir is not None else 0.0))
         if panels:                           # a unit's download block also carries its sheets (six panes and the borders per frame)
             sh, sw = _panel.layout(ev.height, ev.width)["sheet"]
-            per_slot += 2.0 * sh * sw / (ev.height * ev.width)
+            if not self.jpeg_gpu or panel_frames:                # (under panel_encode="gpu" only the lossless copies need the raw sheets)
+                per_slot += 2.0 * sh * sw / (ev.height * ev.width)
             self.sheet_hw = (sh, sw)
             self.titles = _panel.title_bitmap(ev.width)
             self.titles_dev = None           # ... on the device, uploaded once (native path)
@@ -1017,7 +1030,10 @@ class _FolderPipeline:
         """render() of a unit under panels=True (on the lane's stream, inside its stream context): one device buffer,
         [uint8 frames | float32 [4, Tc*B] metrics (measured units) | uint8 sheets [Tc*B + keys, SH, SW, 3]], filled by the
         quantiser, rib_quality and rib_panel - one launch for the unit's frames and, in a first chunk, one in key-frame mode for
-        the key frames the unit starts from - and brought home in the unit's one device-to-host copy."""
+        the key frames the unit starts from - and brought home in the unit's one device-to-host copy.
+        panel_encode="gpu": rib_jpeg encodes the sheets right there; the buffer carries [.. | int32 file lengths [Tc*B + keys]]
+        in the sheets' place (and the sheets behind them only under panel_frames), the files stay on the device until the
+        unit's sink knows their lengths (fetch_jpeg)."""
         t0 = time.perf_counter()
         n = fz.shape[0] * fz.shape[1]
         H, W = fz.shape[3], fz.shape[4]
@@ -1027,8 +1043,10 @@ class _FolderPipeline:
         gtp, klab, kdn, keys, dnp = clip.pan.pop(ui)
         nk = kdn.shape[0] if kdn is not None else 0
         off_v = (nq + 255) // 256 * 256
-        off_s = (off_v + (4 * n * 4 if clip.measure else 0) + 255) // 256 * 256
-        total = off_s + (n + nk) * SH * SW * 3
+        off_l = (off_v + (4 * n * 4 if clip.measure else 0) + 255) // 256 * 256
+        off_s = off_l + ((4 * (n + nk) + 255) // 256 * 256 if self.jpeg_gpu else 0)
+        home = not self.jpeg_gpu or self.panel_frames        # the raw sheets travel home
+        total = off_s + ((n + nk) * SH * SW * 3 if home else 0)
         buf = torch.empty(total, dtype=torch.uint8, device=g.device)
         q = g.quantise(frames, out=buf[:nq].view(n, H, W, 3))
         keep = [fz, imgs, masks, q, lab, dn, gtd, buf, gtp, klab, kdn, keys, dnp]
@@ -1038,11 +1056,15 @@ class _FolderPipeline:
             g.quality(frames, gtm, mk, out=vals[0:2])
             g.quality(dn.reshape(n, 3, H, W), gtm, mk, out=vals[2:4])
             keep += [gtm, mk]
-        sheets = buf[off_s:].view(n + nk, SH, SW, 3)
+        sheets = buf[off_s:].view(n + nk, SH, SW, 3) if home else torch.empty((n + nk, SH, SW, 3), dtype=torch.uint8, device=g.device)
         g.panel(imgs.reshape(n, 3, H, W), masks.reshape(n, 1, H, W), frames, dnp, gtp, lab.reshape(n, *lab.shape[2:]),
                 titles=self.titles_dev, out=sheets[:n])
         if nk:
             g.panel(None, None, None, kdn, keys, klab, titles=self.titles_dev, out=sheets[n:])
+        jpeg = None
+        if self.jpeg_gpu:
+            jpeg = self.encode_jpeg(g, sheets, buf[off_l:off_l + 4 * (n + nk)].view(torch.int32))
+            keep += [sheets, jpeg]
         out_blk = _shm_get(total) if self.procs is not None else None
         flat = out_blk.t[:total] if out_blk is not None else torch.empty(total, dtype=torch.uint8, pin_memory=True)
         flat.copy_(buf, non_blocking=True)
@@ -1052,19 +1074,50 @@ class _FolderPipeline:
         _, members, c0, _ = clip.units[ui]
         return {"done": done, "pinned": flat[:nq].view(q.shape), "out_blk": out_blk, "keep": tuple(keep),
                 "qual": flat[off_v:off_v + 16 * n].view(torch.float32).view(4, n) if clip.measure else None,
-                "sheets": flat[off_s:].view(n + nk, SH, SW, 3), "sheet_off": off_s,
+                "sheets": flat[off_s:].view(n + nk, SH, SW, 3) if home else None, "sheet_off": off_s,
+                "jpeg": jpeg + (flat[off_l:off_l + 4 * (n + nk)].view(torch.int32),) if jpeg else None,
                 "sheet_frames": clip.unit_frames(ui) + ([clip.segs[si][0] for si in members] if nk else [])}
 
     def save_sheets(self, clip, frames, sheets, out_blk=None, off=0):
         """Submits the encodes of the sheets of `frames` (uint8 [n, SH, SW, 3] on the host; out_blk: the shared block they lie
-        in, from byte `off`) -> futures."""
+        in, from byte `off`) -> futures.  panel_encode="gpu": only the lossless copies are left to encode (panel_frames)."""
         SH, SW = self.sheet_hw
+        names = [clip.sheet_names(i, self.panel_frames) for i in frames]
+        if self.jpeg_gpu:
+            names = [(None, png) for _, png in names]
         if out_blk is not None:
             return [self.procs.submit(io_worker.save_sheet_shm, out_blk.name, off + j * SH * SW * 3, SH, SW,
-                                      *clip.sheet_names(i, self.panel_frames), self.panel_quality) for j, i in enumerate(frames)]
+                                      *names[j], self.panel_quality) for j in range(len(frames))]
         sn = sheets.numpy()
-        return [self.pool.submit(io_worker.save_sheet, sn[j], *clip.sheet_names(i, self.panel_frames), self.panel_quality)
-                for j, i in enumerate(frames)]
+        return [self.pool.submit(io_worker.save_sheet, sn[j], *names[j], self.panel_quality) for j in range(len(frames))]
+
+    def encode_jpeg(self, g, sheets, lengths):
+        """panel_encode="gpu", on the lane's stream: rib_jpeg of the sheets uint8 [n, SH, SW, 3] on the device -> (files, cap):
+        frame j's file at files[j * cap:], its size in lengths[j] (int32 [n] on the device, a view of the unit's download
+        buffer).  cap is the proven bound of a file (rib_jpeg_max_bytes): no frame can be refused."""
+        SH, SW = self.sheet_hw
+        cap = g.jpeg_max_bytes(SH, SW)
+        files = torch.empty(sheets.shape[0] * cap, dtype=torch.uint8, device=g.device)
+        g.jpeg_into(sheets, files, lengths, self.panel_quality, cap)
+        return files, cap
+
+    def fetch_jpeg(self, clip, frames, jpeg):
+        """panel_encode="gpu", on a finisher thread once the unit's copy is home: jpeg = (files, cap, lengths on the host) -
+        exactly the files' bytes come home and are written as the sheets' %04d.jpg, by this thread: no worker, no PIL."""
+        files, cap, lengths = jpeg
+        sizes = [int(v) for v in lengths.tolist()]
+        if not all(0 < v <= cap for v in sizes):
+            raise RuntimeError("panel_encode='gpu': rib_jpeg refused a sheet (lengths %s, cap %d)" % (sizes, cap))
+        with torch.cuda.stream(self.copy_stream(files.device)):
+            host = [files[j * cap:j * cap + sizes[j]].cpu() for j in range(len(frames))]     # each returns when its bytes are home
+        return [_panel.save_jpeg(host[j].numpy().tobytes(), clip.sheet_names(i, False)[0]) for j, i in enumerate(frames)]
+
+    def copy_stream(self, device):
+        """The stream of the finishers' exact-size file copies (one per device): the lane's work they read is complete."""
+        streams = self.__dict__.setdefault("_copy_streams", {})
+        if device not in streams:
+            streams[device] = torch.cuda.Stream(device)
+        return streams[device]
 
     def loose_key_sheets(self, clip, g, st):
         """panels: the sheets of this rank's key frames that start no unit of its own (a clip's last key frame; every key frame of
@@ -1086,15 +1139,25 @@ class _FolderPipeline:
             kdn = normalise_exact(torch.stack(dains).to(g.device))
             keys = torch.stack([g_[1] for g_ in got]).to(g.device)
             sheets = g.panel(None, None, None, kdn, keys, klab, titles=self.titles_dev)
-            out_blk = _shm_get(sheets.numel()) if self.procs is not None else None
-            pinned = (out_blk.t[:sheets.numel()] if out_blk is not None else torch.empty(sheets.numel(), dtype=torch.uint8, pin_memory=True)).view(sheets.shape)
-            pinned.copy_(sheets, non_blocking=True)
+            jpeg = out_blk = pinned = None
+            if self.jpeg_gpu:                    # the files stay on the device until their lengths are home
+                lengths = torch.empty(len(loose), dtype=torch.int32, device=g.device)
+                home = torch.empty(len(loose), dtype=torch.int32, pin_memory=True)
+                jpeg = self.encode_jpeg(g, sheets, lengths)
+                home.copy_(lengths, non_blocking=True)
+                jpeg = jpeg + (home,)
+            if not self.jpeg_gpu or self.panel_frames:
+                out_blk = _shm_get(sheets.numel()) if self.procs is not None else None
+                pinned = (out_blk.t[:sheets.numel()] if out_blk is not None else torch.empty(sheets.numel(), dtype=torch.uint8, pin_memory=True)).view(sheets.shape)
+                pinned.copy_(sheets, non_blocking=True)
             done = torch.cuda.Event()
             done.record(st)
 
         def finish(keep=(sheets, kdn, keys, klab)):
             done.synchronize()
-            res = [f.result(timeout=IO_TIMEOUT_S) for f in self.save_sheets(clip, loose, pinned, out_blk)]
+            res = self.fetch_jpeg(clip, loose, jpeg) if jpeg is not None else []
+            if pinned is not None:
+                res += [f.result(timeout=IO_TIMEOUT_S) for f in self.save_sheets(clip, loose, pinned, out_blk)]
             if out_blk is not None:
                 _shm_put(out_blk)
             return res
@@ -1122,10 +1185,14 @@ class _FolderPipeline:
         out_blk = r["out_blk"]
         # panels: the JPEG (and PNG) encodes of the unit's sheets fan out beside the PNG encodes of its frames
         sheet_fs = self.save_sheets(clip, r["sheet_frames"], r["sheets"], out_blk, r["sheet_off"]) if r.get("sheets") is not None else []
+        jpeg = r.pop("jpeg", None)              # panel_encode="gpu": the files' bytes come home now that their lengths have,
+                                                # while the workers encode the PNGs
         if out_blk is not None:
             fsz = ev.height * ev.width * 3
             fs = [self.procs.submit(io_worker.save_png_shm, out_blk.name, j * fsz, ev.height, ev.width, clip.names[out_frames[j]], self.level)
                   for j in range(len(out_frames))]
+            if jpeg is not None:
+                self.fetch_jpeg(clip, r["sheet_frames"], jpeg)
             res = [f.result(timeout=IO_TIMEOUT_S) for f in fs]
             for f in sheet_fs:
                 f.result(timeout=IO_TIMEOUT_S)
@@ -1133,7 +1200,10 @@ class _FolderPipeline:
             _shm_put(out_blk)
         else:
             qn = r["pinned"].numpy()
-            res = list(self.pool.map(lambda j: self.save_q(qn[j], clip.names[out_frames[j]]), range(len(out_frames))))
+            saves = self.pool.map(lambda j: self.save_q(qn[j], clip.names[out_frames[j]]), range(len(out_frames)))
+            if jpeg is not None:
+                self.fetch_jpeg(clip, r["sheet_frames"], jpeg)
+            res = list(saves)
             for f in sheet_fs:
                 f.result(timeout=IO_TIMEOUT_S)
         r["keep"] = None
@@ -1172,6 +1242,12 @@ class _FolderPipeline:
         tm["units"] = tm.get("units", 0) + len(clip.units)
         tm["frames"] += len(clip.futs)
 
+    @property
+    def sheet_saver(self):
+        """The host encoder of a sheet on the reference path: PIL, or under panel_encode="gpu" the definition the GPU encoder
+        is held to (panel.jpeg_encode_host) - the same files as the native path writes."""
+        return io_worker.save_sheet_defined if self.jpeg_gpu else io_worker.save_sheet
+
     def run_reference(self, clip):
         """Any callable that only speaks the reference's protocol (img, mask = model(label, None, dain, prev)): frame by frame."""
         ev, tm, model = self.ev, self.tm, self.model
@@ -1204,7 +1280,7 @@ class _FolderPipeline:
                 sheets = _panel.compose_host(host([p_[0] for p_ in shown]), host([p_[1] for p_ in shown]), host(outs), host(list(dn)),
                                              host(gtp), host(list(lab)), self.titles)
                 for t, i in enumerate(frames):
-                    clip.sheet_futs.append(self.pool.submit(io_worker.save_sheet, sheets[t], *clip.sheet_names(i, self.panel_frames), self.panel_quality))
+                    clip.sheet_futs.append(self.pool.submit(self.sheet_saver, sheets[t], *clip.sheet_names(i, self.panel_frames), self.panel_quality))
             if clip.measure:                     # the torch statement of the metric (metrics.py), frame by frame
                 t3 = time.perf_counter()
                 vals = np.zeros((4, len(frames)))
@@ -1224,7 +1300,7 @@ class _FolderPipeline:
                 dain, key, pose = clip.loads[k].result()
                 klab = ev.make_labels(model, [pose]).detach().cpu().float().numpy()
                 sheet = _panel.compose_host(None, None, None, dain.unsqueeze(0).numpy(), key.unsqueeze(0).numpy(), klab, self.titles)[0]
-                clip.sheet_futs.append(self.pool.submit(io_worker.save_sheet, sheet, *clip.sheet_names(k, self.panel_frames), self.panel_quality))
+                clip.sheet_futs.append(self.pool.submit(self.sheet_saver, sheet, *clip.sheet_names(k, self.panel_frames), self.panel_quality))
         tm["units"] = tm.get("units", 0)
         tm["frames"] += len(clip.futs)
 

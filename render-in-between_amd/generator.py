@@ -549,6 +549,64 @@ class Generator:
                 _ptr(titles), _ptr(out), self._stream()))
         return out
 
+    def jpeg_max_bytes(self, height, width):
+        """Upper bound of one JPEG file of a height x width image, header included (rib_jpeg_max_bytes; panel.jpeg_max_bytes)."""
+        n = int(self._lib.rib_jpeg_max_bytes(int(height), int(width)))
+        if n == 0:
+            raise ValueError("jpeg: height and width must be in 1..65535, got %dx%d" % (height, width))
+        return n
+
+    def jpeg_into(self, sheets_u8, dst, lengths, quality=90, cap=None):
+        """The lower-level form of jpeg(): encodes uint8 [T,SH,SW,3] on this device into the caller's buffers and only enqueues
+        (two launches on the current stream, no synchronisation).  dst: a contiguous 1-D uint8 device tensor of at least
+        T * cap bytes, any byte alignment - frame t's file starts at dst[t * cap]; lengths: a contiguous int32 [T] device
+        tensor receiving each file's size.  cap (default dst.numel() // T) below jpeg_max_bytes(SH, SW) is allowed: a frame
+        whose file would not fit writes nothing and gets length 0, which the caller has to check once the lengths are home.
+        Bytes of a frame's cap behind its length are not written.  -> cap."""
+        if not torch.is_tensor(sheets_u8) or sheets_u8.dim() != 4 or sheets_u8.shape[-1] != 3 or sheets_u8.dtype != torch.uint8 \
+                or sheets_u8.device != self.device or not sheets_u8.is_contiguous():
+            raise ValueError("jpeg: sheets must be a contiguous uint8 [T,SH,SW,3] tensor on %s" % (self.device,))
+        T, SH, SW, _ = sheets_u8.shape
+        if isinstance(quality, bool) or int(quality) != quality or not 1 <= int(quality) <= 100:
+            raise ValueError("jpeg: quality must be an integer in 1..100, got %r" % (quality,))
+        self.jpeg_max_bytes(SH, SW)
+        if T < 1 or T > 65535:
+            raise ValueError("jpeg: 1 <= T <= 65535 frames, got %d" % T)
+        if dst.dim() != 1 or dst.dtype != torch.uint8 or dst.device != self.device or not dst.is_contiguous():
+            raise ValueError("jpeg: dst must be a contiguous 1-D uint8 tensor on %s" % (self.device,))
+        if tuple(lengths.shape) != (T,) or lengths.dtype != torch.int32 or lengths.device != self.device or not lengths.is_contiguous():
+            raise ValueError("jpeg: lengths must be a contiguous int32 [%d] tensor on %s" % (T, self.device))
+        cap = dst.numel() // T if cap is None else int(cap)
+        from . import panel as P
+        if cap < P.JPEG_HEADER_BYTES + 2 or cap >= 2 ** 31 or T * cap > dst.numel():
+            raise ValueError("jpeg: cap=%d: at least the %d-byte header and EOI, below 2 GiB, and T * cap within dst (%d bytes)"
+                             % (cap, P.JPEG_HEADER_BYTES, dst.numel()))
+        n = int(self._lib.rib_jpeg_workspace_bytes(self._h, T, SH, SW))
+        cache = self.__dict__.setdefault("_jpeg_ws", {})
+        ws = cache.get((T, SH, SW))
+        if ws is None:
+            ws = cache[(T, SH, SW)] = torch.empty(n, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _native.check(self._h, self._lib.rib_jpeg(self._h, T, SH, SW, _ptr(sheets_u8), int(quality), _ptr(dst), cap, _ptr(lengths),
+                                                      _ptr(ws), self._stream()))
+        return cap
+
+    def jpeg(self, sheets_u8, quality=90):
+        """Baseline JPEG files of T images on the GPU (rib_jpeg, csrc/jpeg.hip.h; panel.jpeg_encode_host is the definition and is
+        bit-equal): uint8 [T,SH,SW,3] on this device -> list of T bytes objects.  Every file has jpeg_max_bytes(SH, SW) of
+        room, so none is refused; the lengths come home first, then exactly the files' bytes."""
+        if not torch.is_tensor(sheets_u8) or sheets_u8.dim() != 4:
+            raise ValueError("jpeg: sheets must be a uint8 [T,SH,SW,3] tensor")
+        T, SH, SW, _ = sheets_u8.shape
+        cap = self.jpeg_max_bytes(SH, SW)
+        dst = torch.empty(T * cap, dtype=torch.uint8, device=self.device)
+        lengths = torch.empty(T, dtype=torch.int32, device=self.device)
+        self.jpeg_into(sheets_u8, dst, lengths, quality, cap)
+        n = lengths.cpu().tolist()
+        if not all(v > 0 for v in n):
+            raise RuntimeError("jpeg: a frame exceeded rib_jpeg_max_bytes (%d bytes): the staging bound is wrong" % cap)
+        return [dst[t * cap:t * cap + n[t]].cpu().numpy().tobytes() for t in range(T)]
+
     # ---- introspection / measurement -----------------------------------------------------------
     def enable_taps(self, on=True):
         """Debug: keep every tapped intermediate intact until the end of a forward (buffers with disjoint lifetimes

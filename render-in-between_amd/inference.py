@@ -21,6 +21,9 @@ Diagnostic sheets (the counterpart of the reference's gen_vid=True): `--panels [
 composes, per frame, Predict | Mask | Fuse over DAIN | Ground Truth | Skeleton on the GPU and writes
 <save-dir>/Generated_frames/<clip>.avi (Motion-JPEG in a plain RIFF AVI: no H.264 encoder is available here; the layout and the
 titles are this project's, not matplotlib's); `--panel-frames` keeps the lossless sheets in <clip>_panels/%04d.png.
+`--panel-encode gpu` encodes the video's JPEG frames on the GPU (rib_jpeg: baseline 4:2:0 with PIL's tables and one restart
+segment per MCU row, bit-equal to panel.jpeg_encode_host; the stream is ours, restated from ITU-T T.81, unpinned) instead of
+with PIL in the file workers (`host`, the default): the files' bytes come home instead of the raw sheets.
 """
 import argparse
 import os
@@ -120,7 +123,8 @@ def main(opts):
                                              metrics=opts.metrics, mask_dir=opts.mask_dir, pose_mask=opts.pose_mask,
                                              panels=opts.panels, panel_frames=opts.panel_frames,
                                              panel_quality=90 if opts.panel_quality is None else opts.panel_quality,
-                                             panel_fps=30 if opts.panel_fps is None else opts.panel_fps)
+                                             panel_fps=30 if opts.panel_fps is None else opts.panel_fps,
+                                             panel_encode=opts.panel_encode or "host")
     print(summary_line(evaluator, rank, world))
     if world > 1:
         print("[rank {}/{}] wrote {} frames".format(rank, world, len(written)))
@@ -174,6 +178,9 @@ def build_parser():
                         help="with --panels: keep the lossless sheets as <clip>_panels/%%04d.png (the reference's save_frame)")
     parser.add_argument("--panel-quality", type=int, default=None, help="with --panels: JPEG quality of the video's frames, 1-100 (default 90)")
     parser.add_argument("--panel-fps", type=float, default=None, help="with --panels: frames per second of the video (default 30)")
+    parser.add_argument("--panel-encode", choices=("host", "gpu"), default=None,
+                        help="with --panels: where the video's JPEG frames are encoded. 'host' (default): PIL in the file workers; 'gpu': "
+                             "the HIP encoder (baseline 4:2:0, PIL's tables, a restart segment per MCU row; --panel-quality applies to both)")
     return parser
 
 
@@ -190,8 +197,8 @@ def parse_args(argv=None):
         parser.error("--pose-mask is a setting of --metrics")
     if opts.pose_mask and opts.mask_dir is not None:
         parser.error("--pose-mask and --mask-dir are two sources of the one mask: give one of them")
-    if not opts.panels and (opts.panel_frames or opts.panel_quality is not None or opts.panel_fps is not None):
-        parser.error("--panel-frames, --panel-quality and --panel-fps are settings of --panels")
+    if not opts.panels and (opts.panel_frames or opts.panel_quality is not None or opts.panel_fps is not None or opts.panel_encode is not None):
+        parser.error("--panel-frames, --panel-quality, --panel-fps and --panel-encode are settings of --panels")
     if opts.panel_quality is not None and not 1 <= opts.panel_quality <= 100:
         parser.error("--panel-quality must be in 1..100")
     if opts.panel_fps is not None and not opts.panel_fps > 0:

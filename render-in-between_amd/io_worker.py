@@ -160,6 +160,16 @@ def save_sheet(u8, jpg_name, png_name=None, quality=90):
     return panel.save_sheet(u8, jpg_name, quality, png_name)
 
 
+def save_sheet_defined(u8, jpg_name, png_name=None, quality=90):
+    """save_sheet with the JPEG file stated by panel.jpeg_encode_host (Evaluator panel_encode="gpu" on the host path)."""
+    from . import panel
+    panel.save_jpeg(panel.jpeg_encode_host(u8, quality), jpg_name)
+    if png_name is not None:
+        from PIL import Image
+        Image.fromarray(u8).save(png_name)
+    return jpg_name
+
+
 def save_sheet_shm(shm_name, offset, height, width, jpg_name, png_name=None, quality=90):
     """save_sheet of the sheet at bytes [offset, ..) of a shared block."""
     return save_sheet(np.ndarray((height, width, 3), np.uint8, buffer=_attach(shm_name).buf, offset=offset), jpg_name, png_name, quality)

@@ -10,6 +10,8 @@ RIFF AVI (no H.264 encoder, ffmpeg or imageio is available to this project):
     title_bitmap(W)       the two title bars as a 0/1 bitmap, from the glyph table below (no PIL fonts: they differ between machines)
     compose_host(...)     THE definition of the sheet's bytes; rib_panel (csrc/panel.hip.h, Generator.panel) is bit-equal to it
     write_mjpeg_avi(...)  JPEG files -> <clip>.avi; assemble(...) does it for a clip's sheet folder
+    jpeg_encode_host(...) THE definition of a sheet's JPEG file when the GPU encodes it (panel_encode="gpu"): baseline 4:2:0 in
+                          integers only; rib_jpeg (csrc/jpeg.hip.h, Generator.jpeg) is bit-equal to it
 
 Pane values: a 3-channel pane is uint8(clip(x * 0.5 + 0.5, 0, 1) * 255) in float64, truncating - the arithmetic of
 rib_quantise, pinned to the reference's bytes by tests/golden/quant_ref.npz.  The 1-channel Mask pane is
@@ -153,12 +155,273 @@ def sheet_dir(save_dir, clip):
 
 
 def save_sheet(u8, jpg_name, quality=90, png_name=None):
-    """One sheet uint8 [SH, SW, 3] -> its JPEG (the video's frame) and, with png_name, the lossless copy."""
+    """One sheet uint8 [SH, SW, 3] -> its JPEG (the video's frame; jpg_name None: it is written elsewhere) and, with png_name,
+    the lossless copy."""
     from PIL import Image
     im = Image.fromarray(u8)
-    im.save(jpg_name, format="JPEG", quality=int(quality))
+    if jpg_name is not None:
+        im.save(jpg_name, format="JPEG", quality=int(quality))
     if png_name is not None:
         im.save(png_name)
+    return jpg_name
+
+
+# ---- baseline JPEG in integers: the definition rib_jpeg is held to ---------------------------------------------------------
+# ITU-T T.81 Annex K: the two quantisation tables (K.1, K.2, natural order) and the four "typical" Huffman tables (K.3 - K.6:
+# 16 code-length counts, then the symbols in code order)
+_JPEG_QBASE = (
+    (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99),
+    (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99)
+    + (99,) * 32)
+_JPEG_DC_BITS = ((0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), (0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0))
+_JPEG_DC_VALS = tuple(range(12))
+_JPEG_AC_BITS = ((0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125), (0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119))
+_JPEG_AC_VALS = (
+    bytes.fromhex("01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a"
+                  "434445464748494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aa"
+                  "b2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa"),
+    bytes.fromhex("000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a"
+                  "434445464748494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aa"
+                  "b2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa"))
+# position in the block (row * 8 + column) of the k-th coefficient in zig-zag order (T.81 figure A.6)
+_JPEG_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+# the DCT matrix in 13 fractional bits, K[u][x] = round(8192 * c(u)/2 * cos((2x + 1) u pi / 16)), c(0) = 1/sqrt(2), c(u) = 1 otherwise:
+# seven magnitudes, 4096 cos(k pi / 16) rounded for k = 1..7 (k = 4 is also row 0), written out
+_JPEG_DCT = ((2896, 2896, 2896, 2896, 2896, 2896, 2896, 2896),
+             (4017, 3406, 2276, 799, -799, -2276, -3406, -4017),
+             (3784, 1567, -1567, -3784, -3784, -1567, 1567, 3784),
+             (3406, -799, -4017, -2276, 2276, 4017, 799, -3406),
+             (2896, -2896, -2896, 2896, 2896, -2896, -2896, 2896),
+             (2276, -4017, 799, 3406, -3406, -799, 4017, -2276),
+             (1567, -3784, 3784, -1567, -1567, 3784, -3784, 1567),
+             (799, -2276, 3406, -4017, 4017, -3406, 2276, -799))
+JPEG_HEADER_BYTES = 629
+
+
+def jpeg_qtables(quality):
+    """The two Annex K tables under the IJG quality scaling, natural order, int32 [2, 64]: scale = 5000 // q below 50, else
+    200 - 2 q; entry = clamp((base * scale + 50) // 100, 1, 255).  These are the tables PIL stores for the same quality."""
+    if isinstance(quality, bool) or int(quality) != quality or not 1 <= int(quality) <= 100:
+        raise ValueError("jpeg: quality must be an integer in 1..100, got %r" % (quality,))
+    q = int(quality)
+    scale = 5000 // q if q < 50 else 200 - 2 * q
+    return np.clip((np.array(_JPEG_QBASE, np.int32) * scale + 50) // 100, 1, 255).astype(np.int32)
+
+
+def _jpeg_huffman(bits, vals):
+    """(code, length) per symbol, uint32 [256] each (length 0: no code), by T.81 Annex C: codes of one length count up, the
+    first code of the next length is the count doubled."""
+    code = np.zeros(256, np.uint32)
+    size = np.zeros(256, np.uint32)
+    c, k = 0, 0
+    for length in range(1, 17):
+        for _ in range(bits[length - 1]):
+            code[vals[k]], size[vals[k]] = c, length
+            c, k = c + 1, k + 1
+        c <<= 1
+    return code, size
+
+
+_JPEG_HUFF = None
+
+
+def _jpeg_tables():
+    global _JPEG_HUFF
+    if _JPEG_HUFF is None:
+        _JPEG_HUFF = {"dc": [_jpeg_huffman(_JPEG_DC_BITS[c], _JPEG_DC_VALS) for c in range(2)],
+                      "ac": [_jpeg_huffman(_JPEG_AC_BITS[c], _JPEG_AC_VALS[c]) for c in range(2)]}
+    return _JPEG_HUFF
+
+
+def jpeg_header(SH, SW, quality):
+    """The JPEG_HEADER_BYTES bytes in front of the entropy-coded data: SOI, APP0 (JFIF 1.01, density 1:1, no thumbnail), DQT
+    luminance, DQT chrominance (zig-zag order), SOF0 (8 bit, SH x SW, Y 2x2 table 0, Cb 1x1 table 1, Cr 1x1 table 1), DHT DC 0,
+    AC 0, DC 1, AC 1, DRI (the MCUs of one MCU row), SOS (Y: tables 0/0, Cb and Cr: 1/1; Ss 0, Se 63, Ah/Al 0)."""
+    q = jpeg_qtables(quality)
+    zz = list(_JPEG_ZIGZAG)
+    out = b"\xff\xd8" + b"\xff\xe0" + struct.pack(">H5sBBBHHBB", 16, b"JFIF\0", 1, 1, 0, 1, 1, 0, 0)
+    for c in range(2):
+        out += b"\xff\xdb" + struct.pack(">HB", 67, c) + bytes(int(v) for v in q[c][zz])
+    out += b"\xff\xc0" + struct.pack(">HBHHB", 17, 8, SH, SW, 3) + bytes((1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1))
+    for c in range(2):
+        out += b"\xff\xc4" + struct.pack(">HB", 19 + 12, c) + bytes(_JPEG_DC_BITS[c]) + bytes(_JPEG_DC_VALS)
+        out += b"\xff\xc4" + struct.pack(">HB", 19 + 162, 0x10 | c) + bytes(_JPEG_AC_BITS[c]) + _JPEG_AC_VALS[c]
+    out += b"\xff\xdd" + struct.pack(">HH", 4, (SW + 15) // 16)
+    out += b"\xff\xda" + struct.pack(">HB", 12, 3) + bytes((1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0))
+    assert len(out) == JPEG_HEADER_BYTES
+    return out
+
+
+def jpeg_segment_bound(SW):
+    """Upper bound of one restart segment's bytes, stuffing included: a block emits at most 64 symbols (one DC, 63 AC) of at
+    most 16 + 11 bits (the longest code and the longest value field; the true worst case, 20 + 63 * 26 bits, is smaller), so an
+    MCU row of n = 6 * ceil(SW / 16) blocks is at most 216 n bytes before the padding to a byte (216 n is whole already) and
+    twice that when every byte is 0xFF and gets a zero behind it."""
+    return 2 * 216 * 6 * ((int(SW) + 15) // 16)
+
+
+def jpeg_max_bytes(SH, SW):
+    """Upper bound of one file: header, every segment at its bound, a 2-byte RSTn between segments, EOI (rib_jpeg_max_bytes)."""
+    rows = (int(SH) + 15) // 16
+    return JPEG_HEADER_BYTES + rows * jpeg_segment_bound(SW) + 2 * (rows - 1) + 2
+
+
+def _jpeg_size(a):
+    """Number of bits of |v| (the category of T.81 tables F.1 / F.2), 0 for 0: int32 array."""
+    a = np.abs(a)
+    return sum((a >= (1 << k)).astype(np.int32) for k in range(12))
+
+
+def jpeg_coefficients(u8, quality=90):
+    """The quantised coefficients of one image uint8 [SH, SW, 3] in coding order: int32 [rows, 6 * cols, 64] - per MCU row, per
+    MCU the blocks Y00 Y01 Y10 Y11 Cb Cr, each in zig-zag order.  See jpeg_encode_host for the arithmetic."""
+    u8 = np.asarray(u8)
+    SH, SW = u8.shape[:2]
+    rows, cols = (SH + 15) // 16, (SW + 15) // 16
+    p = np.pad(u8, ((0, rows * 16 - SH), (0, cols * 16 - SW), (0, 0)), mode="edge").astype(np.int32)
+    r, g, b = p[..., 0], p[..., 1], p[..., 2]
+    y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16
+    cb = (-11059 * r - 21709 * g + 32768 * b + 8421375) >> 16
+    cr = (32768 * r - 27439 * g - 5329 * b + 8421375) >> 16
+    half = lambda c: (c[0::2, 0::2] + c[0::2, 1::2] + c[1::2, 0::2] + c[1::2, 1::2] + 2) >> 2
+    yb = y.reshape(rows, 2, 8, cols, 2, 8).transpose(0, 3, 1, 4, 2, 5).reshape(rows, cols, 4, 8, 8)
+    cbb, crb = (half(c).reshape(rows, 8, cols, 8).transpose(0, 2, 1, 3).reshape(rows, cols, 1, 8, 8) for c in (cb, cr))
+    s = np.concatenate([yb, cbb, crb], axis=2).astype(np.int32) - 128                       # [rows, cols, 6, y, x]
+    K = np.array(_JPEG_DCT, np.int32)
+    t = (np.einsum("ux,rcbyx->rcbyu", K, s) + 512) >> 10                                    # rows of the block: 3 fractional bits stay
+    F = (np.einsum("vy,rcbyu->rcbvu", K, t) + 32768) >> 16                                  # columns
+    assert t.dtype == np.int32 and F.dtype == np.int32
+    Q = jpeg_qtables(quality).reshape(2, 8, 8)[[0, 0, 0, 0, 1, 1]]                          # [6, 8, 8]
+    q = np.sign(F) * ((np.abs(F) + (Q >> 1)) // Q)
+    return q.reshape(rows, cols * 6, 64)[..., list(_JPEG_ZIGZAG)].astype(np.int32)
+
+
+def _jpeg_segment(zz, st):
+    """The entropy-coded bytes of one restart segment: zz int32 [n, 64], the blocks of an MCU row in coding order."""
+    H = _jpeg_tables()
+    n = zz.shape[0]
+    comp = np.tile(np.array([0, 0, 0, 0, 1, 2]), n // 6)
+    tab = (comp > 0).astype(np.int64)                                                       # Huffman table of the block
+    dc = zz[:, 0].astype(np.int64)
+    diff = dc.copy()
+    for c in range(3):                                                                      # predictor: the component's previous block, 0 at the start
+        m = np.nonzero(comp == c)[0]
+        diff[m[1:]] -= dc[m[:-1]]
+    cat = _jpeg_size(diff).astype(np.int64)
+    dcode = np.stack([H["dc"][c][0] for c in range(2)]).astype(np.uint64)
+    dsize = np.stack([H["dc"][c][1] for c in range(2)]).astype(np.int64)
+    vbits = np.where(diff < 0, diff + (1 << cat) - 1, diff).astype(np.uint64)
+    keys = [np.arange(n, dtype=np.int64) * 65]
+    codes = [(dcode[tab, cat] << cat.astype(np.uint64)) | vbits]
+    sizes = [dsize[tab, cat] + cat]
+    bi, ki = np.nonzero(zz[:, 1:])                                                          # in block, then zig-zag order
+    ki = ki + 1
+    v = zz[bi, ki].astype(np.int64)
+    first = np.ones(len(bi), bool)
+    first[1:] = bi[1:] != bi[:-1]
+    prev = np.where(first, 0, np.concatenate([[0], ki[:-1]]))
+    run = ki - prev - 1
+    nz, r = run >> 4, run & 15                                                              # ZRL symbols, then the run of the symbol
+    sz = _jpeg_size(v).astype(np.int64)
+    t = tab[bi]
+    acode = np.stack([H["ac"][c][0] for c in range(2)]).astype(np.uint64)
+    asize = np.stack([H["ac"][c][1] for c in range(2)]).astype(np.int64)
+    zc, zl = acode[:, 0xF0], asize[:, 0xF0]
+    rep = np.zeros((2, 4), np.uint64)
+    for c in range(2):
+        for j in range(1, 4):
+            rep[c, j] = (rep[c, j - 1] << np.uint64(zl[c])) | zc[c]
+    sym = (r << 4) | sz
+    hl = asize[t, sym]
+    if len(sym) and (hl == 0).any():
+        raise ValueError("jpeg: an AC coefficient outside the 10 bits the tables code")
+    vb = np.where(v < 0, v + (1 << sz) - 1, v).astype(np.uint64)
+    keys.append(bi * 65 + ki)
+    codes.append((rep[t, nz] << (hl + sz).astype(np.uint64)) | (acode[t, sym] << sz.astype(np.uint64)) | vb)
+    sizes.append(nz * zl[t] + hl + sz)
+    last = np.zeros(n, np.int64)
+    last[bi] = ki                                                                           # the largest: ki ascends inside a block
+    eob = np.nonzero(last < 63)[0]
+    keys.append(eob * 65 + 64)
+    codes.append(acode[tab[eob], 0])
+    sizes.append(asize[tab[eob], 0])
+    key, code, size = np.concatenate(keys), np.concatenate(codes), np.concatenate(sizes)
+    order = np.argsort(key, kind="stable")
+    code, size = code[order], size[order]
+    total = int(size.sum())
+    idx = np.repeat(np.arange(len(size)), size)
+    pos = np.arange(total) - np.repeat(np.cumsum(size) - size, size)
+    bits = ((code[idx] >> (size[idx] - 1 - pos).astype(np.uint64)) & np.uint64(1)).astype(np.uint8)
+    bits = np.concatenate([bits, np.ones(-total % 8, np.uint8)])                            # the segment is padded with 1-bits
+    data = np.packbits(bits)
+    ff = np.nonzero(data == 0xFF)[0]
+    st["stuffed"] += len(ff)
+    st["zrl"] += int(nz.sum())
+    st["no_eob"] += n - len(eob)
+    st["max_dc_category"] = max(st["max_dc_category"], int(cat.max()))
+    st["segments"] += 1
+    return np.insert(data, ff + 1, 0).tobytes()
+
+
+def jpeg_encode_host(u8, quality=90, stats=False):
+    """THE definition of a sheet's JPEG file under panel_encode="gpu": uint8 [SH, SW, 3], any size from 1 x 1 to 65535 x 65535
+    -> the bytes of a complete JFIF file (uint8 [T, SH, SW, 3] -> a list of T files; a file does not depend on its neighbours).
+    rib_jpeg (csrc/jpeg.hip.h, Generator.jpeg) writes the same bytes.  stats=True: -> (bytes, {"stuffed": stuffed 0xFF bytes,
+    "zrl": ZRL symbols, "no_eob": blocks whose coefficient 63 is non-zero, "max_dc_category", "segments"}).
+
+    Format: baseline sequential DCT (SOF0), 8 bit, Y Cb Cr at 4:2:0 (MCU 16 x 16: Y00 Y01 Y10 Y11 Cb Cr), one interleaved scan,
+    the Annex K quantisation tables under the IJG quality scaling (jpeg_qtables) and the four Annex K Huffman tables - what PIL
+    writes by default at the same quality, up to the arithmetic below - and a restart interval of one MCU row: every MCU row is
+    a byte-aligned segment with its own DC predictors, RST0..7 cycling between them.  Header: jpeg_header.  No floats anywhere:
+
+      edge      the image is padded to multiples of 16 by repeating its last column and row; SOF0 carries the true size
+      colour    Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+                Cb = (-11059 R - 21709 G + 32768 B + 8421375) >> 16        (8421375 = 128 * 65536 + 32767)
+                Cr = ( 32768 R - 27439 G -  5329 B + 8421375) >> 16        all three in 0..255, sums non-negative
+      chroma    per 2 x 2 pixels (a + b + c + d + 2) >> 2 of the Cb (Cr) values above
+      shift     s = sample - 128, in -128..127
+      DCT       K[u][x] = round(8192 * c(u)/2 * cos((2x+1) u pi/16)) as seven written-out integers (_JPEG_DCT); int32 throughout:
+                  rows      t[y][u] = (sum_x K[u][x] s[y][x] + 512) >> 10          (arithmetic shift: floor)
+                  columns   F[v][u] = (sum_y K[v][y] t[y][u] + 32768) >> 16
+                bound: sum_x |K[u][x]| <= 8 * 2896 = 23168 (row 0; the other rows sum to at most 20996), so the row sums are at
+                most 23168 * 128 = 2965504 < 2^22 and |t| <= 2897; the column sums are at most 23168 * 2897 + 32768 = 67150464
+                < 2^27; |F| <= 1025.  DC: F[0][0] is in -1024..1016, so a DC difference is at most 2040 (category <= 11); an AC
+                coefficient is at most 20996 * 23168 * 128 / 2^26 + 2 < 930 in magnitude (category <= 10).  int16 holds t and F.
+      quantise  q = sign(F) * ((|F| + (Q >> 1)) // Q): to the nearest, halves away from zero
+      order     zig-zag (_JPEG_ZIGZAG)
+      DC        diff to the component's previous block in the segment (0 at its start); category n = bits of |diff|, 0..11; the
+                category's code, then n bits: diff if diff >= 0, else diff + 2^n - 1
+      AC        per non-zero coefficient: a run of r zeros before it - r >> 4 ZRL symbols (0xF0), then symbol (r & 15) << 4 | n
+                and n bits as for DC; EOB (0x00) after the last one unless coefficient 63 is non-zero
+      bytes     bits most significant first; the segment's last byte is filled with 1-bits; then every 0xFF byte (a filled
+                last byte included) is followed by 0x00
+    """
+    u8 = np.asarray(u8)
+    if u8.dtype != np.uint8 or u8.ndim not in (3, 4) or u8.shape[-1] != 3 or min(u8.shape[-3:-1]) < 1 or max(u8.shape[-3:-1]) > 65535:
+        raise ValueError("jpeg_encode_host: uint8 [SH, SW, 3] or [T, SH, SW, 3] expected, got %s %s" % (u8.dtype, u8.shape))
+    jpeg_qtables(quality)
+    if u8.ndim == 4:
+        res = [jpeg_encode_host(a, quality, stats) for a in u8]
+        return res if not stats else ([r[0] for r in res], [r[1] for r in res])
+    SH, SW = u8.shape[:2]
+    zz = jpeg_coefficients(u8, quality)
+    st = {"stuffed": 0, "zrl": 0, "no_eob": 0, "max_dc_category": 0, "segments": 0}
+    parts = [jpeg_header(SH, SW, quality)]
+    for k in range(zz.shape[0]):
+        if k:
+            parts.append(bytes((0xFF, 0xD0 + (k - 1) % 8)))
+        parts.append(_jpeg_segment(zz[k], st))
+    parts.append(b"\xff\xd9")
+    data = b"".join(parts)
+    return (data, st) if stats else data
+
+
+def save_jpeg(data, jpg_name):
+    """The bytes of a finished JPEG file -> jpg_name."""
+    with open(jpg_name, "wb") as f:
+        f.write(data)
     return jpg_name
 
 

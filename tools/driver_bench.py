@@ -2,7 +2,7 @@
 """End-to-end rate of the folder driver (json + PNG in, PNG out) on a synthetic clip.
 
     python tools/driver_bench.py [--size 512 | --height 320 --width 480] [--keys 5] [--rate 32] [--lanes 2] [--batch B] [--chunk 4]
-                                  [--src-width 1920 --src-height 1080] [--resize-on host|gpu] [--metrics [--pose-mask]] [--panels]
+                                  [--src-width 1920 --src-height 1080] [--resize-on host|gpu] [--metrics [--pose-mask]] [--panels [--panel-encode host|gpu]]
 
 Writes a clip in the reference's directory layout (inputs/ DAIN/ Predict_motion/), runs
 Evaluator.evaluate_from_folder twice (the first run also builds launch plans) and prints the
@@ -11,7 +11,7 @@ one D2H copy), save (PNG encode).  --src-width / --src-height write the input fr
 so that the driver has to resize them; --resize-on says where (Evaluator(resize_on=...)).  --metrics also writes a ground-truth
 frame per frame (gt/) and measures every generated frame against it (evaluate_from_folder(metrics=True)); --pose-mask measures
 under the mask drawn from each frame's pose (pose_mask=True), so that the cost of either can be read off two runs.  --panels also composes the six-pane diagnostic sheet of every frame and
-writes the clip's Motion-JPEG video (evaluate_from_folder(panels=True)).
+writes the clip's Motion-JPEG video (evaluate_from_folder(panels=True)); --panel-encode says where its JPEG frames are encoded.
 """
 import argparse, json, os, sys, tempfile, time
 import numpy as np, torch
@@ -71,7 +71,10 @@ def main():
     ap.add_argument("--metrics", action="store_true", help="measure every generated frame against a synthetic ground-truth frame (metrics=True)")
     ap.add_argument("--pose-mask", action="store_true", help="with --metrics: under the mask drawn from each frame's pose (pose_mask=True)")
     ap.add_argument("--panels", action="store_true", help="also write the diagnostic sheets and the clip's video (panels=True)")
+    ap.add_argument("--panel-encode", default="host", choices=("host", "gpu"), help="with --panels: PIL in the file workers or rib_jpeg (panel_encode=...)")
     a = ap.parse_args()
+    if a.panel_encode != "host" and not a.panels:
+        ap.error("--panel-encode is a setting of --panels")
     if a.pose_mask and not a.metrics:
         ap.error("--pose-mask is a setting of --metrics")
     H, W = (a.height or a.size), (a.width or a.size)
@@ -88,7 +91,7 @@ def main():
         for rep in range(1 + a.reps):           # the first run also builds launch plans and pools: not counted
             t0 = time.perf_counter()
             out = E.evaluate_from_folder(G, *dirs, os.path.join(root, "out%d" % rep), gt_dir=os.path.join(root, "gt") if a.metrics else None,
-                                         metrics=a.metrics, pose_mask=a.pose_mask, panels=a.panels)
+                                         metrics=a.metrics, pose_mask=a.pose_mask, panels=a.panels, panel_encode=a.panel_encode)
             torch.cuda.synchronize()
             walls.append(time.perf_counter() - t0)
         tm = dict(E.timings)
@@ -99,7 +102,7 @@ def main():
                       "batch": a.batch or E.default_batch(), "chunk": a.chunk, "io_threads": E.io_threads, "io_mode": a.io_mode,
                       "cpus": len(os.sched_getaffinity(0)), "cpu_budget": ev.cpu_budget(), "png_compress_level": a.compress,
                       "src_height": a.src_height or H, "src_width": a.src_width or W, "resize_on": a.resize_on,
-                      "metrics": a.metrics, "pose_mask": a.pose_mask, "metrics_overall": overall, "panels": a.panels,
+                      "metrics": a.metrics, "pose_mask": a.pose_mask, "metrics_overall": overall, "panels": a.panels, "panel_encode": a.panel_encode,
                       "wall_s": wall, "wall_s_runs": [round(w, 4) for w in walls[1:]], "frames_per_s_end_to_end": n / wall,
                       "phase_s_last_run": {k: round(v, 4) for k, v in tm.items() if k not in ("frames", "units", "timeline", "peak_units_in_flight")},
                       "peak_units_in_flight": tm.get("peak_units_in_flight"),

@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """The sheet kernel on its own: rib_panel (Generator.panel) on T frames of H x W, for a kernel trace.
 
-    rocprofv3 --kernel-trace --stats -d DIR -- python tools/panel_bench.py [--size 512] [--frames 16] [--reps 20]
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/panel_bench.py [--size 512] [--frames 16] [--reps 20] [--jpeg [--quality 90]]
 
 Prints one JSON line: the launch's wall time between two events (median of --reps, after a warm-up), its byte floor
 (16 floats read + 18 bytes written per source pixel) and what that floor takes at 6.3 TB/s.  The kernel's own time is
-k_panel's row of the trace's kernel statistics.
+k_panel's row of the trace's kernel statistics.  --jpeg also times rib_jpeg (Generator.jpeg_into) on the composed sheets, on
+its own pair of events: "jpeg_*" keys; its byte floor is the sheets read once and the files written twice (staging slot, file)
+and read once; the kernels' own times are the k_jpeg_segments and k_jpeg_assemble rows.  The sheets are composed from smooth
+synthetic frames (a noise sheet would measure the entropy coder at its worst, ten times a real sheet's bytes).
 """
 import argparse, json, os, sys
 import torch
@@ -21,11 +24,17 @@ def main():
     ap.add_argument("--width", type=int, default=0)
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--jpeg", action="store_true", help="also encode the sheets (rib_jpeg) and time that separately")
+    ap.add_argument("--quality", type=int, default=90)
     a = ap.parse_args()
     H, W, T = a.height or a.size, a.width or a.size, a.frames
     G = rib.Generator(rib.hsm_gen_config()).eval()                 # no weights needed: the sheet kernel reads none
     g = torch.Generator(device="cuda").manual_seed(0)
-    rnd = lambda c: torch.rand(T, c, H, W, device="cuda", generator=g) * 2.4 - 1.2
+    if a.jpeg:        # smooth frames: low-resolution noise, bilinearly enlarged, so that the JPEG sizes are those of pictures
+        rnd = lambda c: torch.nn.functional.interpolate(torch.rand(T, c, max(H // 16, 2), max(W // 16, 2), device="cuda", generator=g) * 2.4 - 1.2,
+                                                        size=(H, W), mode="bilinear", align_corners=False).contiguous()
+    else:
+        rnd = lambda c: torch.rand(T, c, H, W, device="cuda", generator=g) * 2.4 - 1.2
     pred, fuse, dain, gt, label = rnd(3), rnd(3), rnd(3), rnd(3), rnd(G.spec.label_nc)
     mask = torch.rand(T, 1, H, W, device="cuda", generator=g)
     titles = torch.from_numpy(panel.title_bitmap(W)).cuda()
@@ -44,9 +53,30 @@ def main():
         ms.append(e0.elapsed_time(e1))
     ms.sort()
     floor = (64 + 18) * H * W * T
+    extra = {}
+    if a.jpeg:
+        cap = G.jpeg_max_bytes(SH, SW)
+        files = torch.empty(T * cap, dtype=torch.uint8, device="cuda")
+        lengths = torch.empty(T, dtype=torch.int32, device="cuda")
+        for _ in range(3):
+            G.jpeg_into(out, files, lengths, a.quality, cap)
+        torch.cuda.synchronize()
+        js = []
+        for _ in range(a.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            G.jpeg_into(out, files, lengths, a.quality, cap)
+            e1.record()
+            e1.synchronize()
+            js.append(e0.elapsed_time(e1))
+        js.sort()
+        sizes = lengths.cpu().tolist()
+        jfloor = out.numel() + 3 * sum(sizes)
+        extra = {"jpeg_quality": a.quality, "jpeg_event_us_median": round(js[len(js) // 2] * 1e3, 2), "jpeg_event_us_min": round(js[0] * 1e3, 2),
+                 "jpeg_file_bytes_mean": sum(sizes) // T, "jpeg_floor_bytes": jfloor, "jpeg_floor_us_at_6.3TB/s": round(jfloor / 6.3e12 * 1e6, 2)}
     print(json.dumps({"height": H, "width": W, "frames": T, "sheet": [SH, SW], "event_us_median": round(ms[len(ms) // 2] * 1e3, 2),
                       "event_us_min": round(ms[0] * 1e3, 2), "floor_bytes": floor, "written_bytes": out.numel(),
-                      "floor_us_at_6.3TB/s": round(floor / 6.3e12 * 1e6, 2)}))
+                      "floor_us_at_6.3TB/s": round(floor / 6.3e12 * 1e6, 2), **extra}))
 
 
 if __name__ == "__main__":
