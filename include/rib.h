@@ -349,10 +349,12 @@ int rib_set_plan_batch(rib_handle* h, int n);
 int rib_get_plan_batch(const rib_handle* h);
 
 /* ---- build identity (no reference counterpart: the reference is interpreted Python).  A static string
- *   "librib stamp=<lib> shards=<s0>,...,<s23> consistent=<0|1> variants=<n> compiler=<...>"
- * where <lib> is the content hash (csrc/build.py: sha256 over rib.hip, kernels.hip.h, igemm.hip.h, raster.hip.h,
- * variants.def, variants.hip.h, igemm_shard.hip, include/rib.h + flags + compiler version) rib.o was compiled with and <si> the hash
- * shard object i carries (24 of them, csrc/variants.hip.h); consistent=1 when all carry the hash rib.o expected of them.  bench.py
+ *   "librib stamp=<lib> shards=<s0>,...,<s23> consistent=<0|1> variants=<n> frame=<f> compiler=<...>"
+ * where <lib> is the content hash (csrc/build.py: sha256 over rib.hip, kernels.hip.h, rib_host.h, pixel_ops.hip.h, igemm.hip.h,
+ * variants.def, variants.hip.h, igemm_shard.hip, include/rib.h + flags + compiler version) rib.o was compiled with, <si> the hash
+ * shard object i carries (24 of them, csrc/variants.hip.h) and <f> the hash of frame.o (frame.hip and the kernel headers of the
+ * frame utilities: rib_blend ... rib_jpeg); consistent=1 when all shards carry the hash rib.o expected of them and frame.o was
+ * compiled against the same shared headers (rib_host.h, pixel_ops.hip.h, this file) as rib.o.  bench.py
  * prints it in its JSON line; tests/test_native_host.py compares it with the hashes of the tracked tree. ---- */
 const char* rib_build_info(void);
 

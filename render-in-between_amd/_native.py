@@ -118,11 +118,11 @@ def lib():
 
 
 def build_info():
-    """{'stamp': <lib hash>, 'shards': [8 hashes], 'consistent': bool, 'variants': int, 'raw': str} of the loaded library
+    """{'stamp': <lib hash>, 'shards': [hashes], 'frame': <frame.o hash>, 'consistent': bool, 'variants': int, 'raw': str} of the loaded library
     (rib_build_info, include/rib.h; the hashes are csrc/build.py's content hashes of the sources)."""
     raw = lib().rib_build_info().decode()
     kv = dict(tok.split("=", 1) for tok in raw.split(" compiler=")[0].split()[1:])
-    return {"stamp": kv["stamp"], "shards": kv["shards"].split(","), "consistent": kv["consistent"] == "1",
+    return {"stamp": kv["stamp"], "shards": kv["shards"].split(","), "frame": kv.get("frame"), "consistent": kv["consistent"] == "1",
             "variants": int(kv["variants"]), "raw": raw}
 
 

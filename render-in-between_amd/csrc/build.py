@@ -3,9 +3,12 @@
     python render-in-between_amd/csrc/build.py [--force] [--jobs N] [--check]
 
 hipcc cross-compiles without a GPU; the built .so files are git-ignored but travel to the GPU box with
-the gpurun snapshot.  librib.so is linked from rib.o (runtime, C ABI, the small kernels) and RIB_NSECTIONS (variants.hip.h: 24)
-igemm_shard_<s>.o objects, each holding one section of the k_igemm tile variants (variants.def): the
-kernel instantiations dominate the build and compile as a queue of parallel jobs (about 2 min on 8 cores).
+the working tree.  librib.so is linked from two host objects - rib.o (rib.hip: the generator runtime, its C ABI and the
+small kernels of kernels.hip.h) and frame.o (frame.hip: the folder driver's frame utilities and their kernel headers) - and
+RIB_NSECTIONS (variants.hip.h: 24) igemm_shard_<s>.o objects, each holding one section of the k_igemm tile variants
+(variants.def): the kernel instantiations dominate the build and compile as a queue of parallel jobs (about 2 min on 8
+cores).  Every object has its own dependency list (RIB_DEPS, FRAME_DEPS, SHARD_DEPS): editing jpeg.hip.h rebuilds frame.o only,
+editing the planner rebuilds rib.o only; rib_host.h, pixel_ops.hip.h and rib.h (SHARED_DEPS) are what the objects share.
 
 Build stamps.  Every object is compiled with -DRIB_BUILD_STAMP="<hash>" where <hash> is the sha256 over the CONTENT
 of the sources that object is made from plus the compiler flags and the compiler's version line, and keeps it as a
@@ -37,8 +40,13 @@ def _nsections():
 NSECTIONS = _nsections()        # shard objects (variants.hip.h); more than cores: the compiles run as a job queue
 SRC = os.path.join(HERE, "rib.hip")
 SHARD_SRC = os.path.join(HERE, "igemm_shard.hip")
-SHARD_DEPS = [SHARD_SRC] + [os.path.join(HERE, f) for f in ("igemm.hip.h", "variants.hip.h", "variants.def")]
-DEPS = [SRC, os.path.join(HERE, "kernels.hip.h"), os.path.join(HERE, "raster.hip.h"), os.path.join(HERE, "quality.hip.h"), os.path.join(HERE, "resize.hip.h"), os.path.join(HERE, "human_mask.hip.h"), os.path.join(HERE, "panel.hip.h"), os.path.join(HERE, "jpeg.hip.h"), os.path.join(INC, "rib.h")] + SHARD_DEPS[1:]
+FRAME_SRC = os.path.join(HERE, "frame.hip")
+PIXEL_OPS = os.path.join(HERE, "pixel_ops.hip.h")       # blend1 / quantise_u8: included by igemm.hip.h, frame_kernels.hip.h, panel.hip.h
+SHARED_DEPS = [os.path.join(HERE, "rib_host.h"), PIXEL_OPS, os.path.join(INC, "rib.h")]      # what rib.o and frame.o share
+SHARD_DEPS = [SHARD_SRC] + [os.path.join(HERE, f) for f in ("igemm.hip.h", "variants.hip.h", "variants.def")] + [PIXEL_OPS]
+RIB_DEPS = [SRC, os.path.join(HERE, "kernels.hip.h")] + SHARED_DEPS + SHARD_DEPS[1:-1]
+FRAME_DEPS = [FRAME_SRC] + [os.path.join(HERE, f) for f in ("frame_kernels.hip.h", "raster.hip.h", "quality.hip.h", "resize.hip.h", "human_mask.hip.h", "panel.hip.h", "jpeg.hip.h")] + SHARED_DEPS
+DEPS = RIB_DEPS + [d for d in FRAME_DEPS if d not in RIB_DEPS]      # every file the two host objects are made from
 OUT = os.path.join(HERE, "librib.so")
 # stage 1 (motion transformer, include/rib_motion.h) is its own small library
 MOTION_SRC = os.path.join(HERE, "motion.hip")
@@ -82,8 +90,9 @@ def stamp_of(deps, extra=()):
 
 
 def tree_stamps():
-    """{tag: stamp} the tracked sources build to: 'lib' (rib.o: everything), 'shard0'..'shard7', 'motion'."""
-    st = {"lib": stamp_of(DEPS + [SHARD_SRC]), "motion": stamp_of(MOTION_DEPS)}
+    """{tag: stamp} the tracked sources build to: 'lib' (rib.o: the runtime and everything the shards are made from, whose
+    stamp it checks), 'frame' (frame.o), 'shard0'..'shard<NSECTIONS-1>', 'motion'."""
+    st = {"lib": stamp_of(RIB_DEPS + [SHARD_SRC]), "frame": stamp_of(FRAME_DEPS), "motion": stamp_of(MOTION_DEPS)}
     shard = stamp_of(SHARD_DEPS)
     for s in range(NSECTIONS):
         st["shard%d" % s] = shard
@@ -134,17 +143,21 @@ def build(force=False, verbose=True, jobs=None):
         _compile_shared(MOTION_SRC, MOTION_OUT, _stamp_def(want["motion"]), verbose)
     os.makedirs(OBJ, exist_ok=True)
     work = []
-    rib_o = os.path.join(OBJ, "rib.o")
+    # the two host objects come first in the queue (rib.o is the longest single compile); both carry the hash of the headers they
+    # share, and rib.o the hash it expects of the shards: rib_build_info() compares them at run time (`consistent`)
+    shared = ['-DRIB_SHARED_STAMP="%s"' % stamp_of(SHARED_DEPS)]
+    rib_o, frame_o = os.path.join(OBJ, "rib.o"), os.path.join(OBJ, "frame.o")
     if force or embedded_stamps(rib_o).get("lib") != want["lib"]:
-        work.append((SRC, rib_o, _stamp_def(want["lib"]) + ['-DRIB_SHARD_STAMP="%s"' % want["shard0"]]))
-    objs = [rib_o]
+        work.append((SRC, rib_o, _stamp_def(want["lib"]) + shared + ['-DRIB_SHARD_STAMP="%s"' % want["shard0"]]))
+    if force or embedded_stamps(frame_o).get("frame") != want["frame"]:
+        work.append((FRAME_SRC, frame_o, _stamp_def(want["frame"]) + shared))
+    objs = [rib_o, frame_o]
     for s in range(NSECTIONS):
         o = os.path.join(OBJ, "igemm_shard_%d.o" % s)
         objs.append(o)
         if force or embedded_stamps(o).get("shard%d" % s) != want["shard%d" % s]:
             work.append((SHARD_SRC, o, _stamp_def(want["shard%d" % s]) + ["-DRIB_SECTION=%d" % s, "-DRIB_ON_%d=RIB_KEEP" % s]))
     if work:
-        work.sort(key=lambda w: w[0] != SRC)          # rib.o first: it is the longest single compile
         jobs = jobs or max(1, min(len(work), os.cpu_count() or 1))
         with ThreadPoolExecutor(jobs) as ex:
             for f in [ex.submit(_compile_obj, s, o, d, verbose) for s, o, d in work]:

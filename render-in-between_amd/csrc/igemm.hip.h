@@ -25,6 +25,8 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "pixel_ops.hip.h"      // blend1 (the mask head's fused blend, kernels.hip.h)
+
 namespace rib {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -40,13 +42,6 @@ __device__ __forceinline__ bf16x8 to_bf16x8(const float4 lo, const float4 hi) {
 }
 
 enum { ACT_NONE = 0, ACT_LRELU = 1, ACT_TANH = 2, ACT_SIGMOID = 3 };
-
-// fuse = img*m + dain*(1-m) (PGNR/models/evaluator.py:256-258) with torch's roundings: two products, one difference,
-// one sum, nothing contracted into an fma - the stand-alone k_blend and the blend fused into the mask head agree bit
-// for bit with each other and with the reference's expression
-__device__ __forceinline__ float blend1(float img, float m, float dain) {
-  return __fadd_rn(__fmul_rn(img, m), __fmul_rn(dain, __fsub_rn(1.f, m)));
-}
 
 // ---- storage type ST of the activations / filters: ST_F32 (default, the reference's arithmetic), ST_BF16 (BASELINE
 // configs[2]: bf16 NHWC tensors in HBM and bf16 tiles in LDS - half the bytes everywhere - bf16 matrix-core

@@ -7,7 +7,7 @@
 //
 //   sheet   2 rows x 3 panes of H x W, PANEL_GUTTER px of white (255) around and between them, a PANEL_TITLE px title bar
 //           over each pane row: SH = 2 (H + 24) + 3 * 8, SW = 3 W + 4 * 8, uint8 HWC.
-//   panes   3-channel panes: quantise_u8 (kernels.hip.h, the arithmetic of rib_quantise); the 1-channel Mask pane:
+//   panes   3-channel panes: quantise_u8 (pixel_ops.hip.h, the arithmetic of rib_quantise); the 1-channel Mask pane:
 //           uint8(double(m) * 255.0), truncating, no clip, on all three channels; Skeleton: label channels 0..2.
 //   titles  optional 0/1 bitmap [2, 24, SW] (made on the host from panel.py's glyph table): a set pixel is (0, 0, 255).
 //   key     pred == mask == fuse == NULL: Predict and Fuse show gt, Mask is 0 (a key frame passes through the driver).
@@ -30,7 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "kernels.hip.h"
+#include "pixel_ops.hip.h"
 
 namespace rib {
 

@@ -9,21 +9,16 @@
 //     restate Generator.forward (PGNR/models/generator.py:181-234) and MaskGenerator.forward
 //     (:493-510);
 //   * the autoregressive segment driver (PGNR/models/evaluator.py:238-262).
+//
+// The folder driver's frame utilities (rib_blend ... rib_jpeg) are a second object, frame.hip; rib_host.h holds what the two share.
 #include "kernels.hip.h"
-#include "raster.hip.h"
-#include "quality.hip.h"
-#include "resize.hip.h"
-#include "human_mask.hip.h"
-#include "panel.hip.h"
-#include "jpeg.hip.h"
+#include "rib_host.h"
 #include <hip/hip_ext.h>
-#include "../../include/rib.h"
 
 #include <algorithm>
 #include <array>
 #include <climits>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -81,29 +76,22 @@ namespace { struct ProfPair { hipEvent_t start = nullptr, stop = nullptr; }; thr
     else hipLaunchKernelGGL(KERNEL, grid, block, lds, st, __VA_ARGS__);                                                      \
   } while (0)
 
-#if !defined(RIB_BUILD_STAMP) || !defined(RIB_SHARD_STAMP)
-#error "compile through csrc/build.py (-DRIB_BUILD_STAMP / -DRIB_SHARD_STAMP: content hashes of the sources, see build.py)"
+#if !defined(RIB_BUILD_STAMP) || !defined(RIB_SHARD_STAMP) || !defined(RIB_SHARED_STAMP)
+#error "compile through csrc/build.py (-DRIB_BUILD_STAMP / -DRIB_SHARD_STAMP / -DRIB_SHARED_STAMP: content hashes of the sources, see build.py)"
 #endif
-// the stamp strings of the RIB_NSECTIONS k_igemm shard objects (igemm_shard.hip) and this object's own
+// the stamp strings of the RIB_NSECTIONS k_igemm shard objects (igemm_shard.hip), of frame.o (frame.hip) and this object's own
 extern "C" {
 #define RIB_X(s) extern const char rib_stamp_section_##s[];
 RIB_FOR_SECTIONS(RIB_X)
 #undef RIB_X
+extern const char rib_stamp_frame[];             // "rib-stamp frame <hash>"
+extern const char rib_frame_shared_stamp[];      // the hash of the shared headers (rib_host.h ...) frame.o was compiled against
 }
 extern "C" __attribute__((used, visibility("hidden"))) const char kLibStamp[] = "rib-stamp lib " RIB_BUILD_STAMP;
 
 namespace {
 
 thread_local std::string g_create_error;
-
-std::string fmt(const char* f, ...) {
-  char buf[1024];
-  va_list ap;
-  va_start(ap, f);
-  vsnprintf(buf, sizeof buf, f, ap);
-  va_end(ap);
-  return buf;
-}
 
 // channel padding of an activation: 8, 16, or a multiple of 32 (so that every tensor admits the
 // 16- or 32-channel K chunks of the fast kernel variants; the 22-channel label map becomes 32)
@@ -138,7 +126,6 @@ inline uint16_t host_f16(float f) {
 }
 inline int pad32(int c) { return (c + 31) / 32 * 32; }
 inline int pick_bk(int cp) { return cp % 32 == 0 ? 32 : (cp % 16 == 0 ? 16 : 8); }
-inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 
 // ------------------------------------------------------------------------------------------
 // layer inventory (mirrors render_in_between_amd/spec.py; pinned by the state-dict key test)
@@ -624,10 +611,8 @@ struct Plan {
 
 }  // namespace
 
-struct rib_handle {
+struct rib_handle : rib::FrameState {     // device, err, label_nc and the frame utilities' own state: rib_host.h
   Cfg g;
-  int device = 0;
-  std::string err;
   std::vector<ConvDef> convs;
   std::map<std::string, int> conv_index;
   std::vector<TensorDef> tensors;
@@ -655,7 +640,6 @@ struct rib_handle {
   bool mc16() const { return prec_mode != PREC_F32; }                    // the matrix-core kernels read 16-bit filter copies, 16-channel steps
   int padc(int c) const { return mc16() ? pad16(c) : pad8(c); }          // channel padding of an activation
   int esz() const { return mc16() ? 2 : 4; }                       // bytes per stored activation element
-  bool warp_lds_ready = false; // rib_warp has raised k_warp's dynamic-LDS limit on this handle's device
   bool keep_taps = false;      // rib_set_debug_taps: intermediate activations stay intact until the end of a forward
   // rib_set_plan_batch: > 0 = every launch plan, whatever its batch, follows the kernel choices (tuned table / cost model, split-K,
   // Winograd tile, fused or level-wise SPADE) of THIS batch size, so that a sample's arithmetic does not depend on how many other
@@ -671,16 +655,6 @@ struct rib_handle {
   std::vector<ChainGraph> chain_graphs;
   bool graph_replay = false;
   uint64_t graph_clock = 0, graph_captures = 0, graph_replays = 0;
-  // rib_rasterise: page-locked staging for the host tables (two slots; a slot is reused once the copy out of it has completed,
-  // which its event says), so that the call only enqueues - the caller's pageable arrays are free again on return
-  struct RasterStage { char* host = nullptr; size_t bytes = 0; hipEvent_t done = nullptr; };
-  RasterStage raster_stage[2];
-  int raster_next = 0;
-  // rib_human_mask: the same two-slot scheme for its peak table, with the device copy of the table beside the page-locked one (the
-  // entry takes no workspace); a slot's event follows the kernel that reads it
-  struct MaskStage { int32_t* host = nullptr; int32_t* dev = nullptr; size_t bytes = 0; hipEvent_t done = nullptr; };
-  MaskStage mask_stage[2];
-  int mask_next = 0;
   bool profiling = false;
   bool prof_kernels = false;   // rib_profile_begin_kernels: (start, stop) pairs bound to the dispatches instead of interval events
   std::vector<std::pair<int, hipEvent_t>> prof_events;   // (class of the launch behind the event, -1: end of a plan run)
@@ -690,16 +664,9 @@ struct rib_handle {
   double prof_ms[RIB_KC_COUNT] = {0};
 };
 
-namespace {
+__attribute__((visibility("hidden"))) rib::FrameState* rib::frame_state(rib_handle* h) { return h; }
 
-#define HIP_TRY(h, expr)                                                                   \
-  do {                                                                                     \
-    hipError_t e_ = (expr);                                                                \
-    if (e_ != hipSuccess) {                                                                \
-      (h)->err = fmt("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return RIB_ERR_HIP;                                                                  \
-    }                                                                                      \
-  } while (0)
+namespace {
 
 // instantiated chain graphs hold the plans' kernel parameters: whatever rebuilds plans or moves the blob drops them
 // an instantiated graph may still be queued or running on the stream of its last launch (the launch only enqueues): that stream
@@ -717,11 +684,6 @@ void drop_chain_graphs(rib_handle* h) {
   if (h->device >= 0) (void)hipSetDevice(h->device);      // (the device-wide wait below must be this handle's device)
   for (auto& g : h->chain_graphs) destroy_chain_graph(g);
   h->chain_graphs.clear();
-}
-
-int fail(rib_handle* h, int code, const std::string& msg) {
-  h->err = msg;
-  return code;
 }
 
 const ConvDef& conv_of(const rib_handle* h, const std::string& name) {
@@ -1012,12 +974,6 @@ const std::vector<float>* tensor_data(rib_handle* h, const std::string& name) {
 // ------------------------------------------------------------------------------------------
 // plan builder
 // ------------------------------------------------------------------------------------------
-// XCD-aware tile order (RIB_NO_XCD=1 disables): needs the tile count to be a multiple of 8
-static int xcd_chunk_of(int tiles) {
-  static const bool off = getenv("RIB_NO_XCD") != nullptr;
-  return (!off && tiles >= 64 && tiles % 8 == 0) ? tiles / 8 : 0;
-}
-
 // ------------------------------------------------------------------------------------------
 // FusionPolicy: every decision of the launch plan that is a POLICY rather than arithmetic - which launches are fused, which
 // kernel family serves a layer, where a tensor is never materialised - by name, with the switch that turns it off for an
@@ -2418,7 +2374,7 @@ int rib_create(const rib_config* cfg, int device, rib_handle** out) {
     return bad("invalid hyper-parameters");
   if (c.emb_down != c.num_down_img) return bad("embed.num_downsamples must equal num_downsamples_img (HSM.yaml: 4/4)");
   std::unique_ptr<rib_handle> h(new rib_handle());
-  h->g.c = c; h->device = device;
+  h->g.c = c; h->device = device; h->label_nc = c.label_nc;
   h->graph_replay = getenv("RIB_GRAPH") != nullptr && atoi(getenv("RIB_GRAPH")) != 0;
   for (int i = 0; i <= c.emb_down; ++i) {
     if (h->g.cond_ch(i) != h->g.emb_ch(i)) return bad("embed/generator max_num_filters disagree on the cond map width");
@@ -2447,12 +2403,7 @@ int rib_create(const rib_config* cfg, int device, rib_handle** out) {
 void rib_destroy(rib_handle* h) {
   if (!h) return;
   drop_chain_graphs(h);
-  for (auto& rs : h->raster_stage) { if (rs.host) (void)hipHostFree(rs.host); if (rs.done) (void)hipEventDestroy(rs.done); }
-  for (auto& ms : h->mask_stage) {
-    if (ms.done) { (void)hipEventSynchronize(ms.done); (void)hipEventDestroy(ms.done); }
-    if (ms.host) (void)hipHostFree(ms.host);
-    if (ms.dev) (void)hipFree(ms.dev);
-  }
+  h->stage.release();
   if (h->d_blob) (void)hipFree(h->d_blob);
   free_wino_sets(h);
   for (auto& pe : h->prof_events) (void)hipEventDestroy(pe.second);
@@ -2764,303 +2715,6 @@ int rib_forward_blend(rib_handle* h, int B, int H, int W, const float* label, co
   rc = run_plan(h, P, R, reinterpret_cast<hipStream_t>(hip_stream));
   if (rc == RIB_OK && fuse && !fused) rc = rib_blend(h, B, h->g.c.image_nc, H, W, img, mask, img_fake, fuse, hip_stream);
   return rc;
-}
-
-int rib_blend(rib_handle* h, int B, int C, int H, int W, const float* img, const float* mask,
-              const float* dain, float* fuse, void* hip_stream) {
-  if (!h || !img || !mask || !dain || !fuse) return RIB_ERR_INVALID;
-  if (h->device >= 0) HIP_TRY(h, hipSetDevice(h->device));
-  const size_t total = (size_t)B * C * H * W;
-  const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 4096);
-  RIB_KLAUNCH(k_blend, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream), img, mask, dain, fuse, C, H * W, total);
-  HIP_TRY(h, hipGetLastError());
-  return RIB_OK;
-}
-
-int rib_quantise(rib_handle* h, int B, int C, int H, int W, const float* img, uint8_t* out, void* hip_stream) {
-  if (!h || !img || !out) return RIB_ERR_INVALID;
-  if (h->device >= 0) HIP_TRY(h, hipSetDevice(h->device));
-  const size_t total = (size_t)B * C * H * W;
-  const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 4096);
-  RIB_KLAUNCH(k_quantise, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream), img, out, C, H * W, total);
-  HIP_TRY(h, hipGetLastError());
-  return RIB_OK;
-}
-
-int rib_resize_cubic(rib_handle* h, int N, int H0, int W0, int H, int W, const uint8_t* src, const int32_t* ix, const int32_t* cx,
-                        const int32_t* iy, const int32_t* cy, uint8_t* out_u8, float* out_f32, void* hip_stream) {
-  if (!h) return RIB_ERR_INVALID;
-  if (!src || !ix || !cx || !iy || !cy) return fail(h, RIB_ERR_INVALID, "rib_resize_cubic: null pointer");
-  if (!out_u8 && !out_f32) return fail(h, RIB_ERR_INVALID, "rib_resize_cubic: both outputs are null");
-  if (N < 1 || H0 < 1 || W0 < 1 || H < 1 || W < 1 || N > 65535)
-    return fail(h, RIB_ERR_INVALID, fmt("rib_resize_cubic: N=%d H0=%d W0=%d H=%d W=%d: sizes must be positive (N <= 65535)", N, H0, W0, H, W));
-  if ((size_t)H0 * W0 * 3 > (size_t)INT32_MAX || (size_t)H * W * 3 > (size_t)INT32_MAX)
-    return fail(h, RIB_ERR_INVALID, "rib_resize_cubic: a frame must be smaller than 2 GiB");
-  if (h->device >= 0) HIP_TRY(h, hipSetDevice(h->device));
-  const int tilesX = (W * 3 + RSZ_TW - 1) / RSZ_TW, tilesY = (H + RSZ_TH - 1) / RSZ_TH;
-  RIB_KLAUNCH(k_resize_cubic_u8, dim3(tilesX * tilesY, N), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream), src,
-              reinterpret_cast<const int4*>(ix), reinterpret_cast<const int4*>(cx), reinterpret_cast<const int4*>(iy),
-              reinterpret_cast<const int4*>(cy), out_u8, out_f32, H0, W0, H, W, tilesX);
-  HIP_TRY(h, hipGetLastError());
-  return RIB_OK;
-}
-
-// rib_quality: the pooling factor, the tile grid and the workspace of one shape (quality.hip.h)
-static bool quality_shape(int H, int W, int* f, int* Hp, int* Wp, int* tilesX, int* tilesY) {
-  if (H < 1 || W < 1) return false;
-  *f = std::max(1, (int)std::nearbyint(std::min(H, W) / 256.0));     // Python's round: half to even (fe default mode)
-  *Hp = H / *f; *Wp = W / *f;
-  if (*Hp < QUAL_K || *Wp < QUAL_K) return false;
-  *tilesX = (*Wp - (QUAL_K - 1) + QUAL_OW - 1) / QUAL_OW;
-  *tilesY = (*Hp - (QUAL_K - 1) + QUAL_OH - 1) / QUAL_OH;
-  return true;
-}
-
-static size_t quality_ws_bytes(int B, int C, int tilesX, int tilesY) {
-  return align256((size_t)B * C * tilesX * tilesY * 2 * sizeof(double));
-}
-
-size_t rib_quality_workspace_bytes(rib_handle* h, int B, int H, int W) {
-  int f, Hp, Wp, tx, ty;
-  if (!h || B < 1 || !quality_shape(H, W, &f, &Hp, &Wp, &tx, &ty)) return 0;
-  return quality_ws_bytes(B, 3, tx, ty);
-}
-
-int rib_quality(rib_handle* h, int B, int C, int H, int W, const float* pred, const float* target, const float* mask,
-                float* psnr, float* ssim, void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (!h) return RIB_ERR_INVALID;
-  if (!pred || !target || !psnr || !ssim || !workspace) return fail(h, RIB_ERR_INVALID, "rib_quality: null pointer");
-  int f, Hp, Wp, tilesX, tilesY;
-  if (B < 1 || C < 1 || !quality_shape(H, W, &f, &Hp, &Wp, &tilesX, &tilesY))
-    return fail(h, RIB_ERR_INVALID, fmt("rib_quality: B=%d C=%d H=%d W=%d: the pooled frame must be at least %d x %d", B, C, H, W, QUAL_K, QUAL_K));
-  const size_t need = quality_ws_bytes(B, C, tilesX, tilesY);
-  if (workspace_bytes < need) return fail(h, RIB_ERR_WORKSPACE, fmt("rib_quality: workspace %zu < required %zu bytes", workspace_bytes, need));
-  if (h->device >= 0) HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  double* partials = reinterpret_cast<double*>(workspace);
-  RIB_KLAUNCH(k_quality_tiles, dim3(tilesX * tilesY, B * C), dim3(256), 0, st, pred, target, mask, C, H, W, f, Hp, Wp, tilesX, tilesY, partials);
-  HIP_TRY(h, hipGetLastError());
-  RIB_KLAUNCH(k_quality_finalize, dim3(B), dim3(256), 0, st, (const double*)partials, C, tilesX * tilesY, H, W,
-              Hp - (QUAL_K - 1), Wp - (QUAL_K - 1), psnr, ssim);
-  HIP_TRY(h, hipGetLastError());
-  return RIB_OK;
-}
-
-int rib_warp(rib_handle* h, int B, int C, int H, int W, const float* img, const float* flow, float* out, void* hip_stream) {
-  if (!h || !img || !flow || !out) return RIB_ERR_INVALID;
-  if (h->device >= 0) HIP_TRY(h, hipSetDevice(h->device));
-  if (B < 1 || C < 1 || C > 8 || H < 1 || W < 1) return fail(h, RIB_ERR_INVALID, "rib_warp: 1 <= C <= 8 channels (the staged window must fit in LDS)");
-  const int tilesX = (W + WARP_TW - 1) / WARP_TW, tilesY = (H + WARP_TH - 1) / WARP_TH;
-  const size_t lds = (size_t)C * WARP_WH * WARP_PITCH * sizeof(float);      // 16 KB per channel
-  // k_warp's dynamic-LDS limit is raised once per HANDLE, with the handle's device current (the attribute may be kept per
-  // device: a process that drives two GPUs must not leave the second one at the 64 KB default), and a failure is reported
-  // by the call that met it, not cached for the life of the process
-  if (!h->warp_lds_ready) {
-    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_warp), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * WARP_WH * WARP_PITCH * (int)sizeof(float)));
-    h->warp_lds_ready = true;
-  }
-  RIB_KLAUNCH(k_warp, dim3(tilesX * tilesY, B), dim3(256), lds, reinterpret_cast<hipStream_t>(hip_stream), img, flow, out, C, H, W, tilesX, xcd_chunk_of(tilesX * tilesY));
-  HIP_TRY(h, hipGetLastError());
-  return RIB_OK;
-}
-
-static_assert(sizeof(rib_stroke) == sizeof(RasterStroke) && sizeof(rib_stroke) == 48, "rib_stroke layout");
-
-namespace {
-struct RasterLayout { size_t strokes, colors, peaks, weights, canvas, total; };
-static RasterLayout raster_layout(int T, int H, int W, int n_edges, int n_maps, int radius) {
-  RasterLayout L; size_t o = 0;
-  L.strokes = o; o += align256((size_t)T * n_edges * sizeof(rib_stroke));
-  L.colors = o;  o += align256((size_t)n_edges * sizeof(uint32_t));
-  L.peaks = o;   o += align256((size_t)T * n_maps * 2 * sizeof(int32_t));
-  L.weights = o; o += align256((size_t)(radius + 1) * sizeof(double));
-  L.canvas = o;  o += align256((size_t)T * H * W * sizeof(uint32_t));
-  L.total = o;
-  return L;
-}
-}  // namespace
-
-size_t rib_rasterise_workspace_bytes(rib_handle* h, int T, int H, int W, int n_edges, int n_maps, int radius) {
-  if (!h || T < 1 || H < 1 || W < 1 || n_edges < 0 || n_maps < 0 || radius < 0) return 0;
-  return raster_layout(T, H, W, n_edges, n_maps, radius).total;
-}
-
-int rib_rasterise(rib_handle* h, int T, int H, int W, const rib_stroke* strokes, int n_edges,
-                  const uint8_t* colors_rgb, int stroke_halfwidth, const int32_t* peaks, int n_maps,
-                  const double* weights, int radius, float* labels, void* workspace, size_t workspace_bytes,
-                  void* hip_stream) {
-  if (!h) return RIB_ERR_INVALID;
-  if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_rasterise: host-only handle");
-  if (T < 1 || H < 1 || W < 1 || !labels || !workspace || (n_edges > 0 && (!strokes || !colors_rgb)) ||
-      (n_maps > 0 && (!peaks || !weights)))
-    return fail(h, RIB_ERR_INVALID, "rib_rasterise: bad argument");
-  if (3 + n_maps != h->g.c.label_nc)
-    return fail(h, RIB_ERR_INVALID, fmt("rib_rasterise: 3 + %d maps != label_nc %d", n_maps, h->g.c.label_nc));
-  if (H > RASTER_MAXPTS || W > RASTER_MAXPTS) return fail(h, RIB_ERR_INVALID, fmt("rib_rasterise: H, W <= %d", RASTER_MAXPTS));
-  if (radius > 127 || stroke_halfwidth < 1 || stroke_halfwidth > 16) return fail(h, RIB_ERR_INVALID, "rib_rasterise: radius <= 127, 1 <= stroke half-width <= 16");
-  for (size_t i = 0; i < (size_t)T * n_edges; ++i)
-    if (strokes[i].n < 0 || strokes[i].n > RASTER_MAXPTS) return fail(h, RIB_ERR_INVALID, fmt("rib_rasterise: stroke %zu has %d samples", i, strokes[i].n));
-  for (size_t i = 0; i < (size_t)T * n_maps; ++i) {
-    const int32_t x = peaks[2 * i], y = peaks[2 * i + 1];
-    if (x >= W || (x >= 0 && (y < 0 || y >= H))) return fail(h, RIB_ERR_INVALID, fmt("rib_rasterise: peak %zu (%d, %d) outside the frame", i, x, y));
-  }
-  const RasterLayout L = raster_layout(T, H, W, n_edges, n_maps, radius);
-  if (workspace_bytes < L.total) return fail(h, RIB_ERR_WORKSPACE, fmt("workspace %zu < required %zu bytes", workspace_bytes, L.total));
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  char* ws = reinterpret_cast<char*>(workspace);
-  HIP_TRY(h, hipSetDevice(h->device));
-  // The four tables sit at the head of the workspace in one contiguous range [0, L.canvas): they are assembled in a page-locked
-  // staging slot and go over in ONE asynchronous copy.  (Rounds 1-3 copied from the caller's pageable arrays and then
-  // synchronised the stream so that the arrays could be reused: where the upload stream shares a hardware queue with the
-  // stream a chain runs on, that wait was the previous segment's whole chain - 60 ms per call, profiles/r04_prof_driver.txt.)
-  {
-    rib_handle::RasterStage& rs = h->raster_stage[h->raster_next];
-    h->raster_next ^= 1;
-    if (rs.done) HIP_TRY(h, hipEventSynchronize(rs.done));      // the copy out of this slot two calls ago
-    else HIP_TRY(h, hipEventCreateWithFlags(&rs.done, hipEventDisableTiming));
-    if (rs.bytes < L.canvas) {
-      if (rs.host) (void)hipHostFree(rs.host);
-      rs.host = nullptr; rs.bytes = 0;
-      HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&rs.host), L.canvas, hipHostMallocDefault));
-      rs.bytes = L.canvas;
-    }
-    memset(rs.host, 0, L.canvas);
-    if (n_edges > 0) {
-      memcpy(rs.host + L.strokes, strokes, (size_t)T * n_edges * sizeof(rib_stroke));
-      uint32_t* packed = reinterpret_cast<uint32_t*>(rs.host + L.colors);
-      for (int e = 0; e < n_edges; ++e)
-        packed[e] = (uint32_t)colors_rgb[3 * e] | ((uint32_t)colors_rgb[3 * e + 1] << 8) | ((uint32_t)colors_rgb[3 * e + 2] << 16);
-    }
-    if (n_maps > 0) {
-      memcpy(rs.host + L.peaks, peaks, (size_t)T * n_maps * 2 * sizeof(int32_t));
-      memcpy(rs.host + L.weights, weights, (size_t)(radius + 1) * sizeof(double));
-    }
-    HIP_TRY(h, hipMemcpyAsync(ws, rs.host, L.canvas, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipEventRecord(rs.done, st));
-  }
-  if (n_maps > 0) {
-    HeatParams hp;
-    hp.peaks = reinterpret_cast<const int32_t*>(ws + L.peaks); hp.w = reinterpret_cast<const double*>(ws + L.weights);
-    hp.r = radius; hp.label = labels; hp.T = T; hp.H = H; hp.W = W; hp.nmaps = n_maps; hp.label_nc = 3 + n_maps; hp.ch0 = 3;
-    RIB_KLAUNCH(k_heatmaps, dim3((H * W + 255) / 256, n_maps, T), dim3(256), 0, st, hp);
-  }
-  SkelParams sp;
-  sp.strokes = reinterpret_cast<const RasterStroke*>(ws + L.strokes); sp.colors = reinterpret_cast<const uint32_t*>(ws + L.colors);
-  sp.nedges = n_edges; sp.canvas = reinterpret_cast<uint32_t*>(ws + L.canvas); sp.label = labels;
-  sp.T = T; sp.H = H; sp.W = W; sp.label_nc = 3 + n_maps; sp.bw = stroke_halfwidth;
-  RIB_KLAUNCH(k_skeleton, dim3(T), dim3(256), 0, st, sp);
-  HIP_TRY(h, hipGetLastError());
-  return RIB_OK;
-}
-
-int rib_human_mask(rib_handle* h, int T, int H, int W, const int32_t* peaks, int n_joints, float* mask, void* hip_stream) {
-  if (!h) return RIB_ERR_INVALID;
-  if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_human_mask: host-only handle");
-  if (!peaks || !mask) return fail(h, RIB_ERR_INVALID, "rib_human_mask: null pointer");
-  if (n_joints != 18 && n_joints != 19) return fail(h, RIB_ERR_INVALID, fmt("rib_human_mask: a pose has 18 or 19 joints, got %d", n_joints));
-  if (T < 1 || T > 65535 || H < 1 || W < 1 || H > HMASK_MAX_SIDE || W > HMASK_MAX_SIDE)
-    return fail(h, RIB_ERR_INVALID, fmt("rib_human_mask: T=%d H=%d W=%d: 1 <= T <= 65535, H and W in 1..%d", T, H, W, HMASK_MAX_SIDE));
-  const size_t n = (size_t)T * n_joints;
-  for (size_t i = 0; i < n; ++i) {
-    const int32_t x = peaks[2 * i], y = peaks[2 * i + 1];
-    if (x >= W || (x >= 0 && (y < 0 || y >= H))) return fail(h, RIB_ERR_INVALID, fmt("rib_human_mask: peak %zu (%d, %d) outside the frame", i, x, y));
-  }
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  HIP_TRY(h, hipSetDevice(h->device));
-  rib_handle::MaskStage& ms = h->mask_stage[h->mask_next];
-  h->mask_next ^= 1;
-  if (ms.done) HIP_TRY(h, hipEventSynchronize(ms.done));        // the kernel that read this slot two calls ago
-  else HIP_TRY(h, hipEventCreateWithFlags(&ms.done, hipEventDisableTiming));
-  const size_t bytes = n * 2 * sizeof(int32_t);
-  if (ms.bytes < bytes) {
-    if (ms.host) (void)hipHostFree(ms.host);
-    if (ms.dev) (void)hipFree(ms.dev);
-    ms.host = ms.dev = nullptr; ms.bytes = 0;
-    const size_t cap = align256(bytes);
-    HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&ms.host), cap, hipHostMallocDefault));
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&ms.dev), cap));
-    ms.bytes = cap;
-  }
-  memcpy(ms.host, peaks, bytes);
-  HIP_TRY(h, hipMemcpyAsync(ms.dev, ms.host, bytes, hipMemcpyHostToDevice, st));
-  MaskParams mp;
-  mp.peaks = ms.dev; mp.mask = mask; mp.T = T; mp.H = H; mp.W = W; mp.nj = n_joints;
-  mp.tilesX = (W + HMASK_TW - 1) / HMASK_TW;
-  mp.vec = (W % 4 == 0 && (reinterpret_cast<uintptr_t>(mask) & 15) == 0) ? 1 : 0;
-  const int tilesY = (H + HMASK_TH - 1) / HMASK_TH;
-  RIB_KLAUNCH(k_human_mask, dim3(mp.tilesX * tilesY, T), dim3(256), 0, st, mp);
-  HIP_TRY(h, hipGetLastError());
-  HIP_TRY(h, hipEventRecord(ms.done, st));
-  return RIB_OK;
-}
-
-int rib_panel(rib_handle* h, int T, int H, int W, int label_nc, const float* pred, const float* mask, const float* fuse,
-              const float* dain, const float* gt, const float* label, const uint8_t* titles, uint8_t* out, void* hip_stream) {
-  if (!h) return RIB_ERR_INVALID;
-  if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_panel: host-only handle");
-  if (!dain || !gt || !label || !out) return fail(h, RIB_ERR_INVALID, "rib_panel: null pointer");
-  const int given = (pred ? 1 : 0) + (mask ? 1 : 0) + (fuse ? 1 : 0);
-  if (given != 0 && given != 3) return fail(h, RIB_ERR_INVALID, "rib_panel: pred, mask and fuse are NULL together (key-frame mode) or not at all");
-  if (T < 1 || T > 65535 || H < 1 || W < 1 || H > PANEL_MAX_H || W > PANEL_MAX_W || label_nc < 3)
-    return fail(h, RIB_ERR_INVALID, fmt("rib_panel: T=%d H=%d W=%d label_nc=%d: 1 <= T <= 65535, H in 1..%d, W in 1..%d, label_nc >= 3",
-                                        T, H, W, label_nc, PANEL_MAX_H, PANEL_MAX_W));
-  PanelParams pp;
-  pp.pred = pred; pp.mask = mask; pp.fuse = fuse; pp.dain = dain; pp.gt = gt; pp.label = label; pp.titles = titles; pp.out = out;
-  pp.H = H; pp.W = W; pp.label_nc = label_nc;
-  pp.SH = 2 * (H + PANEL_TITLE) + 3 * PANEL_GUTTER;
-  pp.SW = 3 * W + 4 * PANEL_GUTTER;
-  if ((size_t)pp.SH * pp.SW * 3 > (size_t)INT32_MAX) return fail(h, RIB_ERR_INVALID, "rib_panel: a sheet must be smaller than 2 GiB");
-  uintptr_t bits = reinterpret_cast<uintptr_t>(dain) | reinterpret_cast<uintptr_t>(gt) | reinterpret_cast<uintptr_t>(label);
-  if (pred) bits |= reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(mask) | reinterpret_cast<uintptr_t>(fuse);
-  pp.vec = (W % 4 == 0 && (bits & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0) ? 1 : 0;
-  HIP_TRY(h, hipSetDevice(h->device));
-  const size_t lds = (size_t)pp.SW * 3 + 32;             // the row at its phase inside a 16-byte line, rounded up to whole lines
-  RIB_KLAUNCH(k_panel, dim3(pp.SH, T), dim3(256), lds, reinterpret_cast<hipStream_t>(hip_stream), pp);
-  HIP_TRY(h, hipGetLastError());
-  return RIB_OK;
-}
-
-size_t rib_jpeg_max_bytes(int H, int W) {
-  if (H < 1 || W < 1 || H > JPEG_MAX_DIM || W > JPEG_MAX_DIM) return 0;
-  const size_t rows = (size_t)(H + 15) / 16;
-  return (size_t)JPEG_HEADER_BYTES + rows * jpeg_seg_bound((W + 15) / 16) + 2 * (rows - 1) + 2;
-}
-
-size_t rib_jpeg_workspace_bytes(rib_handle* h, int T, int H, int W) {
-  if (!h || T < 1 || T > 65535 || H < 1 || W < 1 || H > JPEG_MAX_DIM || W > JPEG_MAX_DIM) return 0;
-  const size_t segs = (size_t)T * ((size_t)(H + 15) / 16);
-  return segs * jpeg_seg_bound((W + 15) / 16) + 256 + segs * sizeof(int32_t);      // the slots, then the segment lengths
-}
-
-int rib_jpeg(rib_handle* h, int T, int H, int W, const uint8_t* src_u8_nhwc, int quality, uint8_t* dst, size_t dst_stride,
-             int32_t* lengths, void* workspace, void* hip_stream) {
-  if (!h) return RIB_ERR_INVALID;
-  if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_jpeg: host-only handle");
-  if (!src_u8_nhwc || !dst || !lengths || !workspace) return fail(h, RIB_ERR_INVALID, "rib_jpeg: null pointer");
-  if (T < 1 || T > 65535 || H < 1 || W < 1 || H > JPEG_MAX_DIM || W > JPEG_MAX_DIM || quality < 1 || quality > 100)
-    return fail(h, RIB_ERR_INVALID, fmt("rib_jpeg: T=%d H=%d W=%d quality=%d: 1 <= T <= 65535, H and W in 1..%d, quality in 1..100",
-                                        T, H, W, quality, JPEG_MAX_DIM));
-  if (dst_stride < (size_t)JPEG_HEADER_BYTES + 2 || dst_stride > (size_t)INT32_MAX)
-    return fail(h, RIB_ERR_INVALID, fmt("rib_jpeg: dst_stride=%zu: at least the header (%d bytes) and EOI, below 2 GiB", dst_stride, JPEG_HEADER_BYTES));
-  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0 || (reinterpret_cast<uintptr_t>(lengths) & 3) != 0)
-    return fail(h, RIB_ERR_INVALID, "rib_jpeg: workspace must be 16-byte aligned, lengths 4-byte aligned");
-  JpegParams jp;
-  jp.src = src_u8_nhwc; jp.H = H; jp.W = W; jp.quality = quality;
-  jp.rows = (H + 15) / 16; jp.cols = (W + 15) / 16;
-  jp.slot = (uint32_t)jpeg_seg_bound(jp.cols);
-  const size_t segs = (size_t)T * jp.rows;
-  jp.seg = static_cast<uint8_t*>(workspace);
-  jp.seglen = reinterpret_cast<int32_t*>(jp.seg + (segs * jp.slot + 255) / 256 * 256);
-  JpegAssembleParams ap;
-  ap.seg = jp.seg; ap.seglen = jp.seglen; ap.dst = dst; ap.lengths = lengths; ap.dst_stride = dst_stride; ap.rows = jp.rows; ap.slot = jp.slot;
-  jpeg_make_header(ap.header, H, W, quality);
-  HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  RIB_KLAUNCH(k_jpeg_segments, dim3(jp.rows, T), dim3(256), 0, st, jp);
-  HIP_TRY(h, hipGetLastError());
-  RIB_KLAUNCH(k_jpeg_assemble, dim3(jp.rows, T), dim3(256), 0, st, ap);
-  HIP_TRY(h, hipGetLastError());
-  return RIB_OK;
 }
 
 namespace {
@@ -3428,7 +3082,8 @@ const char* rib_build_info(void) {
       ok = ok && strcmp(hash, RIB_SHARD_STAMP) == 0;
       s += std::string(i ? "," : "") + hash;
     }
-    s += fmt(" consistent=%d variants=%d compiler=%s", ok ? 1 : 0, kNumVariants, __VERSION__);
+    ok = ok && strcmp(rib_frame_shared_stamp, RIB_SHARED_STAMP) == 0;      // both host objects saw the same rib::FrameState
+    s += fmt(" consistent=%d variants=%d frame=%s compiler=%s", ok ? 1 : 0, kNumVariants, rib_stamp_frame + sizeof("rib-stamp frame ") - 1, __VERSION__);
     return s;
   }();
   return info.c_str();

@@ -64,7 +64,7 @@ def _build_module():
 def test_library_is_what_the_tracked_sources_build(lib):
     """the measured binary must be the one the tree compiles to.  Every object of librib.so carries
     the content hash of the sources it was compiled from (csrc/build.py); the hashes of the tree as it is now, the hashes
-    found in the .so file and the ones rib_build_info() reports at run time must all agree, for every object (rib.o and the shard objects)."""
+    found in the .so file and the ones rib_build_info() reports at run time must all agree, for every object (rib.o, frame.o and the shard objects)."""
     b = _build_module()
     want = b.tree_stamps()
     assert b.check() == [], "librib.so / libribmotion.so were not built from this tree: run csrc/build.py"
@@ -73,9 +73,17 @@ def test_library_is_what_the_tracked_sources_build(lib):
     info = _native.build_info()
     assert info["consistent"] and info["stamp"] == want["lib"]
     assert info["shards"] == [want["shard%d" % s] for s in range(b.NSECTIONS)]
+    # frame.o (the folder driver's frame utilities) carries its own stamp: tree == file == run-time report
+    assert "frame" in want and "frame" in have and info["frame"] is not None
+    assert want["frame"] == have["frame"] == info["frame"] == b.stamp_of(b.FRAME_DEPS)
+    assert "frame=%s" % want["frame"] in info["raw"].split(" compiler=")[0].split()
     assert info["variants"] == lib.rib_num_variants()
     # a changed source changes the stamp (content, not mtime)
     assert b.stamp_of(b.SHARD_DEPS, extra=("x",)) != want["shard0"]
+    # jpeg.hip.h is hashed into frame.o's stamp and into no other object's: editing it rebuilds frame.o only
+    names = lambda deps: [os.path.basename(d) for d in deps]          # noqa: E731
+    assert "jpeg.hip.h" in names(b.FRAME_DEPS) and "jpeg.hip.h" not in names(b.RIB_DEPS) + names(b.SHARD_DEPS)
+    assert b.stamp_of(b.FRAME_DEPS, extra=("x",)) != want["frame"]
 
 
 def test_library_exports_only_the_declared_c_abi(lib):
