@@ -269,6 +269,31 @@ size_t rib_jpeg_max_bytes(int H, int W);
 int rib_jpeg(rib_handle* h, int T, int H, int W, const uint8_t* src_u8_nhwc, int quality,
              uint8_t* dst, size_t dst_stride, int32_t* lengths, void* workspace, void* hip_stream);
 
+/* ---- motion-compensated interpolation (MCI) of a segment's two key frames: the folder driver's background="mci" ----
+ * This project's interpolation, NOT DAIN (the reference reads one DAIN frame per output frame; DAIN is an external network with
+ * its own CUDA ops): the generator was trained on DAIN backgrounds and the quality of this substitute on real footage has not
+ * been measured.  background.py (mci_field_host, mci_frames_host) states both results in integers - luma, a three-level
+ * pyramid, bilateral 8x8 block matching (full search over [-4,4]^2 at quarter size, i.e. +-32 px of motion between the key
+ * frames; +-1 refinements at half and full size; the minimum of (cost, dx^2+dy^2, dy, dx)), a 3x3 median, a bilinear per-pixel
+ * field in 1/256 px, two fixed-point bilinear samples and a blend - and the kernels are bit-equal to it.
+ * rib_mci_field: a_u8, b_u8 uint8 NHWC [B,H,W,3] on the device (left and right key frame of B segments at the model size) ->
+ * field_i16 int16 [B,Hb,Wb,2] on the device, (dx, dy) per 8x8 block of the intermediate frame (rib_mci_field_shape:
+ * Hb = ceil(H/8), Wb = ceil(W/8)); once per segment.  workspace: rib_mci_workspace_bytes(h, B, H, W) bytes on the device, 16-byte
+ * aligned, nothing to clear.  Five launches on `stream` (luma + pyramid, three searches, median), no atomics, no
+ * synchronisation: a segment's field does not depend on B.
+ * rib_mci_frames: frames k_first .. k_first + T - 1 (0 <= k <= sample_rate, a power of two <= 1024; k = 0 is A, k = sample_rate
+ * is B) of all B segments in ONE launch: out_f32_nchw float32 [T,B,3,H,W], ((u8 / 255 - 0.5) / 0.5) exactly as the driver's
+ * upload computes it (the arithmetic of rib_resize_cubic's float output), and / or out_u8_nhwc uint8 [T,B,H,W,3]; a NULL output
+ * is not wanted (both NULL is an error).  Every element written; a frame's bytes do not depend on T or B.
+ * B outside 1..32767, B * Hb * Wb >= 2^30, T < 1, T * B > 65535, H or W outside 1..16384, a bad sample_rate or frame range, NULL or misaligned pointers:
+ * RIB_ERR_INVALID with a rib_last_error text, nothing launched (the size query returns 0). */
+void rib_mci_field_shape(int H, int W, int* Hb, int* Wb);
+size_t rib_mci_workspace_bytes(rib_handle* h, int B, int H, int W);
+int rib_mci_field(rib_handle* h, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
+                  void* workspace, void* hip_stream);
+int rib_mci_frames(rib_handle* h, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const int16_t* field_i16,
+                   int sample_rate, int k_first, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream);
+
 /* Extension op named by the north star but absent from the reference: bilinear
  * flow-grid warp, semantics of torch.nn.functional.grid_sample(img, base+flow*2/(size-1),
  * 'bilinear', padding_mode='border', align_corners=True).  flow [B,2,H,W] in pixels (x,y). */
@@ -353,7 +378,7 @@ int rib_get_plan_batch(const rib_handle* h);
  * where <lib> is the content hash (csrc/build.py: sha256 over rib.hip, kernels.hip.h, rib_host.h, pixel_ops.hip.h, igemm.hip.h,
  * variants.def, variants.hip.h, igemm_shard.hip, include/rib.h + flags + compiler version) rib.o was compiled with, <si> the hash
  * shard object i carries (24 of them, csrc/variants.hip.h) and <f> the hash of frame.o (frame.hip and the kernel headers of the
- * frame utilities: rib_blend ... rib_jpeg); consistent=1 when all shards carry the hash rib.o expected of them and frame.o was
+ * frame utilities: rib_blend ... rib_mci_frames); consistent=1 when all shards carry the hash rib.o expected of them and frame.o was
  * compiled against the same shared headers (rib_host.h, pixel_ops.hip.h, this file) as rib.o.  bench.py
  * prints it in its JSON line; tests/test_native_host.py compares it with the hashes of the tracked tree. ---- */
 const char* rib_build_info(void);

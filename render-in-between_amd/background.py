@@ -1,0 +1,217 @@
+"""Motion-compensated interpolation (MCI) of a segment's two key frames: the background source of the folder driver's
+`background="mci"`, stated in integers.  It is THIS PROJECT'S interpolation, not DAIN: the reference reads one background
+frame per output frame from <input>/DAIN/ (an external network with its own CUDA extension ops); the generator only
+needs "a plausible frame at time t made from the two key frames", which the mask network keeps where the person is not.
+The generator was trained on DAIN backgrounds; the quality of this substitute on real footage has not been measured.
+
+The two functions below ARE the definition; the HIP kernels (csrc/mci.hip.h: rib_mci_field / rib_mci_frames) are held
+bit-equal to them (tests/test_gpu_mci.py).  Every step is integer or fixed point with a stated order and stated tie-breaks:
+
+  luma       Y = (77 R + 150 G + 29 B + 128) >> 8.
+  pyramid    levels 0 (full), 1, 2; level l+1 is ceil(h/2) x ceil(w/2), a pixel is (the sum of its 2x2 parents, coordinates
+             clamped to the edge, + 2) >> 2.
+  matching   bilateral block matching: one displacement d = (dx, dy) per BLOCK x BLOCK block of the INTERMEDIATE frame's grid
+             (so the field has no holes), cost(d) = sum over the block's pixels p inside the image of
+             |Y_A(clamp(p - d)) - Y_B(clamp(p + d))| + LAMBDA * (|dx| + |dy|).
+  search     level 2: every d in [-SEARCH_TOP, SEARCH_TOP]^2 (+-4 at quarter size, i.e. +-32 px of motion between the key frames
+             at full size: faster motion falls outside the search); levels 1 and 0: start = twice the displacement of the coarser
+             block that holds this block's centre (block (by >> 1, bx >> 1)), candidates start + [-REFINE, REFINE]^2.  The winner
+             is the minimum of the tuple (cost, dx*dx + dy*dy, dy, dx) - packed into one integer (pack_key), so it does not
+             depend on the order of evaluation.
+  median     3x3 componentwise median over the level-0 block field, coordinates clamped at the border.
+  per pixel  D(p): bilinear between the four nearest block centres (block b's centre is at 8 b + 3.5), block coordinates
+             clamped at the border; the weights are exact in 1/16 per axis, so D is an exact integer in 1/256 px
+             (FIELD_FRAC_BITS = 8) - no rounding.
+  frame k    of a segment with sample rate s (a power of two, 0 <= k <= s): a = A sampled at p - (2k/s) D(p), b = B sampled at
+             p + (2(s-k)/s) D(p); the offsets are rounded to 1/256 px (SAMPLE_FRAC_BITS = 8) as (2k D + s/2) >> log2 s and
+             (2(s-k) D + s/2) >> log2 s (arithmetic shifts: floor); a sample is bilinear with edge clamp,
+             (sum of the four taps times their 8-bit weight products + 2^15) >> 16, per channel;
+             out = ((s-k) a + k b + s/2) >> log2 s.
+
+No occlusion reasoning and no sub-pel search: see DESIGN ("Motion-compensated backgrounds") for what that costs."""
+from __future__ import annotations
+
+import numpy as np
+
+BLOCK = 8                 # block side, on every pyramid level
+LEVELS = 3                # pyramid levels 0..2
+SEARCH_TOP = 4            # level 2: full search over [-4, 4]^2
+REFINE = 1                # levels 1, 0: start + [-1, 1]^2
+LAMBDA = 4                # cost of one pixel of |dx| + |dy| (a block's SAD is at most 64 * 255)
+FIELD_FRAC_BITS = 8       # D(p) in 1/256 px: 4 bits of bilinear weight per axis
+SAMPLE_FRAC_BITS = 8      # sampling positions in 1/256 px
+MAX_DISP = 2 * (2 * SEARCH_TOP + REFINE) + REFINE      # 19: the largest |dx|, |dy| of the level-0 field
+KEY_BIAS = 32             # pack_key: dy + 32, dx + 32 in 6 bits each (MAX_DISP < 32)
+MAX_SAMPLE_RATE = 1024
+
+
+def field_shape(height, width):
+    """(Hb, Wb) of the block field of a height x width frame: ceil(H/8), ceil(W/8)."""
+    return (int(height) + BLOCK - 1) // BLOCK, (int(width) + BLOCK - 1) // BLOCK
+
+
+def luma(u8):
+    """uint8 [H, W, 3] -> uint8 [H, W]."""
+    v = u8.astype(np.int32)
+    return ((77 * v[..., 0] + 150 * v[..., 1] + 29 * v[..., 2] + 128) >> 8).astype(np.uint8)
+
+
+def down2(y):
+    """One pyramid step of a uint8 [h, w] plane."""
+    h, w = y.shape
+    r0, c0 = 2 * np.arange((h + 1) // 2), 2 * np.arange((w + 1) // 2)
+    r1, c1 = np.minimum(r0 + 1, h - 1), np.minimum(c0 + 1, w - 1)
+    v = y.astype(np.int32)
+    return ((v[r0][:, c0] + v[r0][:, c1] + v[r1][:, c0] + v[r1][:, c1] + 2) >> 2).astype(np.uint8)
+
+
+def pyramid(y):
+    out = [y]
+    for _ in range(LEVELS - 1):
+        out.append(down2(out[-1]))
+    return out
+
+
+def pack_key(cost, dx, dy):
+    """The tuple (cost, dx*dx + dy*dy, dy, dx) as one non-negative integer whose order is the tuple's order."""
+    return (cost.astype(np.int64) << 22) | ((dx * dx + dy * dy).astype(np.int64) << 12) | ((dy + KEY_BIAS).astype(np.int64) << 6) \
+        | (dx + KEY_BIAS).astype(np.int64)
+
+
+def block_cost(ya, yb, dx, dy):
+    """cost(d) of every block of one level: ya, yb uint8 [h, w]; dx, dy int [Hb, Wb] -> int64 [Hb, Wb]."""
+    h, w = ya.shape
+    Hb, Wb = field_shape(h, w)
+    px = np.repeat(np.repeat(dx, BLOCK, 0), BLOCK, 1)[:h, :w]
+    py = np.repeat(np.repeat(dy, BLOCK, 0), BLOCK, 1)[:h, :w]
+    Y, X = np.mgrid[0:h, 0:w]
+    a = ya[np.clip(Y - py, 0, h - 1), np.clip(X - px, 0, w - 1)].astype(np.int32)
+    b = yb[np.clip(Y + py, 0, h - 1), np.clip(X + px, 0, w - 1)].astype(np.int32)
+    sad = np.zeros((Hb * BLOCK, Wb * BLOCK), np.int64)
+    sad[:h, :w] = np.abs(a - b)
+    return sad.reshape(Hb, BLOCK, Wb, BLOCK).sum((1, 3)) + LAMBDA * (np.abs(dx) + np.abs(dy))
+
+
+def search(ya, yb, sx, sy, radius):
+    """The winner of start + [-radius, radius]^2 for every block: sx, sy int [Hb, Wb] -> (dx, dy) int32 [Hb, Wb]."""
+    best = None
+    for ddy in range(-radius, radius + 1):
+        for ddx in range(-radius, radius + 1):
+            dx, dy = sx + ddx, sy + ddy
+            key = pack_key(block_cost(ya, yb, dx, dy), dx, dy)
+            best = key if best is None else np.minimum(best, key)
+    return ((best & 63) - KEY_BIAS).astype(np.int32), (((best >> 6) & 63) - KEY_BIAS).astype(np.int32)
+
+
+def median3(f):
+    """3x3 median of an int [Hb, Wb] plane, coordinates clamped at the border."""
+    p = np.pad(f, 1, mode="edge")
+    Hb, Wb = f.shape
+    nine = np.stack([p[j:j + Hb, i:i + Wb] for j in range(3) for i in range(3)])
+    return np.sort(nine, axis=0)[4]
+
+
+def block_field_levels(a_u8, b_u8):
+    """The block fields of levels 2, 1, 0 before the median: [(dx, dy)] coarse to fine (the tests look at them)."""
+    pa, pb = pyramid(luma(a_u8)), pyramid(luma(b_u8))
+    out = []
+    dx = dy = None
+    for lvl in range(LEVELS - 1, -1, -1):
+        Hb, Wb = field_shape(*pa[lvl].shape)
+        if dx is None:
+            sx = sy = np.zeros((Hb, Wb), np.int32)
+            radius = SEARCH_TOP
+        else:
+            by, bx = np.arange(Hb) >> 1, np.arange(Wb) >> 1
+            sx, sy = 2 * dx[by][:, bx], 2 * dy[by][:, bx]
+            radius = REFINE
+        dx, dy = search(pa[lvl], pb[lvl], sx, sy, radius)
+        out.append((dx, dy))
+    return out
+
+
+def mci_field_host(a_u8, b_u8):
+    """The block displacement field of a key-frame pair: a_u8, b_u8 uint8 [H, W, 3] (left and right key frame at the model
+    size) -> int16 [Hb, Wb, 2], [..., 0] = dx, [..., 1] = dy, in full-size pixels of HALF the motion between the key frames
+    (the intermediate frame's pixel p shows A's p - d and B's p + d)."""
+    a_u8, b_u8 = np.asarray(a_u8), np.asarray(b_u8)
+    if a_u8.dtype != np.uint8 or a_u8.ndim != 3 or a_u8.shape[2] != 3 or a_u8.shape != b_u8.shape or b_u8.dtype != np.uint8:
+        raise ValueError("mci_field_host: two uint8 [H, W, 3] frames of one size, got %s %s and %s %s"
+                         % (a_u8.dtype, a_u8.shape, b_u8.dtype, b_u8.shape))
+    dx, dy = block_field_levels(a_u8, b_u8)[-1]
+    return np.stack([median3(dx), median3(dy)], -1).astype(np.int16)
+
+
+def pixel_field(field, height, width):
+    """D(p) of every pixel: int16 [Hb, Wb, 2] -> (Dx, Dy) int32 [H, W] in 1/256 px."""
+    Hb, Wb = field_shape(height, width)
+    if tuple(field.shape) != (Hb, Wb, 2):
+        raise ValueError("mci: the field of a %dx%d frame is [%d, %d, 2], got %s" % (height, width, Hb, Wb, tuple(field.shape)))
+    f = field.astype(np.int32)
+    ty, tx = 2 * np.arange(height) - (BLOCK - 1), 2 * np.arange(width) - (BLOCK - 1)     # position in 1/16 block from centre 0
+    r0, fy = ty >> 4, (ty & 15)[:, None, None]
+    c0, fx = tx >> 4, (tx & 15)[None, :, None]
+    r1, r0 = np.clip(r0 + 1, 0, Hb - 1), np.clip(r0, 0, Hb - 1)
+    c1, c0 = np.clip(c0 + 1, 0, Wb - 1), np.clip(c0, 0, Wb - 1)
+    d = (16 - fy) * ((16 - fx) * f[r0][:, c0] + fx * f[r0][:, c1]) + fy * ((16 - fx) * f[r1][:, c0] + fx * f[r1][:, c1])
+    return d[..., 0], d[..., 1]
+
+
+def sample_bilinear(img, py, px):
+    """img uint8 [H, W, 3] at positions (py, px) int32 [H, W] in 1/256 px, edge clamp -> int32 [H, W, 3] in 0..255."""
+    h, w = img.shape[:2]
+    y0, x0 = py >> SAMPLE_FRAC_BITS, px >> SAMPLE_FRAC_BITS
+    fy, fx = (py & 255)[..., None], (px & 255)[..., None]
+    y1, y0 = np.clip(y0 + 1, 0, h - 1), np.clip(y0, 0, h - 1)
+    x1, x0 = np.clip(x0 + 1, 0, w - 1), np.clip(x0, 0, w - 1)
+    v = img.astype(np.int32)
+    return ((256 - fy) * ((256 - fx) * v[y0, x0] + fx * v[y0, x1]) + fy * ((256 - fx) * v[y1, x0] + fx * v[y1, x1]) + (1 << 15)) >> 16
+
+
+def log2_rate(sample_rate):
+    s = int(sample_rate)
+    if s < 1 or s > MAX_SAMPLE_RATE or s & (s - 1):
+        raise ValueError("mci: the sample rate must be a power of two in 1..%d, got %r" % (MAX_SAMPLE_RATE, sample_rate))
+    return s.bit_length() - 1
+
+
+def mci_frames_host(a_u8, b_u8, field, sample_rate, ks):
+    """Frames ks (each 0 <= k <= sample_rate; k = 0 is A, k = sample_rate is B) of the segment between the key frames a_u8 and
+    b_u8 (uint8 [H, W, 3]) from their block field (mci_field_host) -> uint8 [len(ks), H, W, 3]."""
+    a_u8, b_u8, field = np.asarray(a_u8), np.asarray(b_u8), np.asarray(field)
+    if a_u8.dtype != np.uint8 or a_u8.ndim != 3 or a_u8.shape[2] != 3 or a_u8.shape != b_u8.shape or b_u8.dtype != np.uint8:
+        raise ValueError("mci_frames_host: two uint8 [H, W, 3] frames of one size, got %s and %s" % (a_u8.shape, b_u8.shape))
+    s, ls = int(sample_rate), log2_rate(sample_rate)
+    H, W = a_u8.shape[:2]
+    Dx, Dy = pixel_field(field, H, W)
+    Y, X = np.mgrid[0:H, 0:W]
+    Y, X = (Y << SAMPLE_FRAC_BITS).astype(np.int32), (X << SAMPLE_FRAC_BITS).astype(np.int32)
+    out = np.empty((len(ks), H, W, 3), np.uint8)
+    for j, k in enumerate(ks):
+        k = int(k)
+        if not 0 <= k <= s:
+            raise ValueError("mci_frames_host: frame %d is outside the segment 0..%d" % (k, s))
+        ax, ay = (2 * k * Dx + s // 2) >> ls, (2 * k * Dy + s // 2) >> ls
+        bx, by = (2 * (s - k) * Dx + s // 2) >> ls, (2 * (s - k) * Dy + s // 2) >> ls
+        a = sample_bilinear(a_u8, Y - ay, X - ax)
+        b = sample_bilinear(b_u8, Y + by, X + bx)
+        out[j] = (((s - k) * a + k * b + s // 2) >> ls).astype(np.uint8)
+    return out
+
+
+def normalised(u8):
+    """ToTensor + Normalize(0.5, 0.5) of uint8 [.., H, W, 3] frames as the host computes it for a decoded file
+    (io_worker.normalised_chw: a true division by 255) -> float32 [.., 3, H, W]: what the sheets' DAIN pane shows."""
+    a = np.asarray(u8).astype(np.float32) / 255.0
+    return np.ascontiguousarray(np.moveaxis((a - 0.5) / 0.5, -1, -3))
+
+
+def normalised_upload(u8):
+    """The same two operations as the native path's upload - and rib_mci_frames' float output - evaluates them on the device:
+    float32(u8) times the fp32 reciprocal of 255, minus 0.5, times 2, each rounded to float32 (csrc/resize.hip.h rsz_normalise;
+    it differs from the division in the last bit for 111 of the 256 values) -> float32 [.., 3, H, W].  It is what the generator
+    is fed under background="mci" on EITHER path: a model behind the reference's protocol reads the very floats the native
+    chain reads, so the two paths write the same files."""
+    a = np.asarray(u8).astype(np.float32) * np.float32(1.0 / 255.0)
+    a = (a - np.float32(0.5)) * np.float32(2.0)
+    return np.ascontiguousarray(np.moveaxis(a, -1, -3))

@@ -1,5 +1,5 @@
 // frame.hip — the folder driver's frame utilities behind the C ABI (include/rib.h): blend, quantise, cubic resize, PSNR/SSIM,
-// flow warp, label rasteriser, pose mask, diagnostic sheet and JPEG encoder.  The second host object of librib.so (frame.o,
+// flow warp, label rasteriser, pose mask, diagnostic sheet, JPEG encoder and the motion-compensated background (MCI).  The second host object of librib.so (frame.o,
 // csrc/build.py).  None of these entries touches a launch plan, the weight blob or a tuned choice: of a handle they use the
 // device index, the error string and the small state of rib::FrameState (rib_host.h), reached through frame_state().
 //
@@ -13,6 +13,7 @@
 #include "human_mask.hip.h"
 #include "panel.hip.h"
 #include "jpeg.hip.h"
+#include "mci.hip.h"
 #include "rib_host.h"
 
 #include <algorithm>
@@ -320,6 +321,101 @@ int rib_jpeg(rib_handle* handle, int T, int H, int W, const uint8_t* src_u8_nhwc
   hipLaunchKernelGGL(k_jpeg_segments, dim3(jp.rows, T), dim3(256), 0, st, jp);
   HIP_TRY(h, hipGetLastError());
   hipLaunchKernelGGL(k_jpeg_assemble, dim3(jp.rows, T), dim3(256), 0, st, ap);
+  HIP_TRY(h, hipGetLastError());
+  return RIB_OK;
+}
+// rib_mci_*: the workspace of one (B, H, W) - the three luma levels of the 2B key frames and the block fields of levels 2, 1 and
+// 0 (before the median)
+namespace {
+struct MciLayout { int h[3], w[3], Hb[3], Wb[3]; size_t y[3], f[3], total; };
+static bool mci_layout(int B, int H, int W, MciLayout* L) {
+  if (B < 1 || B > 32767 || H < 1 || W < 1 || H > MCI_MAX_SIDE || W > MCI_MAX_SIDE) return false;
+  size_t o = 0;
+  for (int l = 0; l < 3; ++l) {
+    L->h[l] = l ? (L->h[l - 1] + 1) / 2 : H; L->w[l] = l ? (L->w[l - 1] + 1) / 2 : W;
+    L->Hb[l] = (L->h[l] + MCI_BLOCK - 1) / MCI_BLOCK; L->Wb[l] = (L->w[l] + MCI_BLOCK - 1) / MCI_BLOCK;
+    L->y[l] = o; o += align256((size_t)2 * B * L->h[l] * L->w[l]);
+  }
+  if ((size_t)B * L->Hb[0] * L->Wb[0] > (size_t)INT32_MAX / 2) return false;      // block indices (and their (dx, dy) pairs) stay in int
+  for (int l = 0; l < 3; ++l) { L->f[l] = o; o += align256((size_t)B * L->Hb[l] * L->Wb[l] * 2 * sizeof(int16_t)); }
+  L->total = o;
+  return true;
+}
+}  // namespace
+
+void rib_mci_field_shape(int H, int W, int* Hb, int* Wb) {
+  if (Hb) *Hb = H < 1 ? 0 : (H + MCI_BLOCK - 1) / MCI_BLOCK;
+  if (Wb) *Wb = W < 1 ? 0 : (W + MCI_BLOCK - 1) / MCI_BLOCK;
+}
+
+size_t rib_mci_workspace_bytes(rib_handle* h, int B, int H, int W) {
+  MciLayout L;
+  if (!h || !mci_layout(B, H, W, &L)) return 0;
+  return L.total;
+}
+
+int rib_mci_field(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
+                  void* workspace, void* hip_stream) {
+  FrameState* h = frame_state(handle);
+  if (!h) return RIB_ERR_INVALID;
+  if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_mci_field: host-only handle");
+  if (!a_u8 || !b_u8 || !field_i16 || !workspace) return fail(h, RIB_ERR_INVALID, "rib_mci_field: null pointer");
+  MciLayout L;
+  if (!mci_layout(B, H, W, &L))
+    return fail(h, RIB_ERR_INVALID, fmt("rib_mci_field: B=%d H=%d W=%d: 1 <= B <= 32767, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", B, H, W, MCI_MAX_SIDE));
+  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0 || (reinterpret_cast<uintptr_t>(field_i16) & 3) != 0)
+    return fail(h, RIB_ERR_INVALID, "rib_mci_field: workspace must be 16-byte aligned, the field 4-byte aligned");
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  uint8_t* ws = static_cast<uint8_t*>(workspace);
+  MciLumaParams lp;
+  lp.a = a_u8; lp.b = b_u8; lp.y0 = ws + L.y[0]; lp.y1 = ws + L.y[1]; lp.y2 = ws + L.y[2];
+  lp.B = B; lp.H = H; lp.W = W; lp.h1 = L.h[1]; lp.w1 = L.w[1]; lp.h2 = L.h[2]; lp.w2 = L.w[2]; lp.tilesX = (W + 31) / 32;
+  hipLaunchKernelGGL(k_mci_luma_pyramid, dim3(lp.tilesX * ((H + 31) / 32), 2 * B), dim3(256), 0, st, lp);
+  HIP_TRY(h, hipGetLastError());
+  for (int l = 2; l >= 0; --l) {
+    MciSearchParams sp;
+    sp.y = ws + L.y[l]; sp.coarse = l == 2 ? nullptr : reinterpret_cast<const int16_t*>(ws + L.f[l + 1]);
+    sp.out = reinterpret_cast<int16_t*>(ws + L.f[l]);
+    sp.B = B; sp.h = L.h[l]; sp.w = L.w[l]; sp.Hb = L.Hb[l]; sp.Wb = L.Wb[l];
+    sp.Hbc = l == 2 ? 1 : L.Hb[l + 1]; sp.Wbc = l == 2 ? 1 : L.Wb[l + 1];
+    const dim3 grid((sp.Hb * sp.Wb + MCI_RUN - 1) / MCI_RUN, B);
+    if (l == 2) hipLaunchKernelGGL(k_mci_search<MCI_TOP_R>, grid, dim3(256), 0, st, sp);
+    else hipLaunchKernelGGL(k_mci_search<1>, grid, dim3(256), 0, st, sp);
+    HIP_TRY(h, hipGetLastError());
+  }
+  const int n = B * L.Hb[0] * L.Wb[0];
+  hipLaunchKernelGGL(k_mci_median, dim3(std::min((n + 255) / 256, 1024)), dim3(256), 0, st,
+                     reinterpret_cast<const int16_t*>(ws + L.f[0]), field_i16, B, L.Hb[0], L.Wb[0]);
+  HIP_TRY(h, hipGetLastError());
+  return RIB_OK;
+}
+
+int rib_mci_frames(rib_handle* handle, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const int16_t* field_i16,
+                   int sample_rate, int k_first, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream) {
+  FrameState* h = frame_state(handle);
+  if (!h) return RIB_ERR_INVALID;
+  if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_mci_frames: host-only handle");
+  if (!a_u8 || !b_u8 || !field_i16) return fail(h, RIB_ERR_INVALID, "rib_mci_frames: null pointer");
+  if (!out_f32_nchw && !out_u8_nhwc) return fail(h, RIB_ERR_INVALID, "rib_mci_frames: both outputs are null");
+  MciLayout L;
+  if (T < 1 || !mci_layout(B, H, W, &L) || (size_t)T * B > 65535)
+    return fail(h, RIB_ERR_INVALID, fmt("rib_mci_frames: T=%d B=%d H=%d W=%d: T, B >= 1, T * B <= 65535, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", T, B, H, W, MCI_MAX_SIDE));
+  if (sample_rate < 1 || sample_rate > MCI_MAX_RATE || (sample_rate & (sample_rate - 1)) != 0)
+    return fail(h, RIB_ERR_INVALID, fmt("rib_mci_frames: sample_rate=%d: a power of two in 1..%d", sample_rate, MCI_MAX_RATE));
+  if (k_first < 0 || k_first + T - 1 > sample_rate)
+    return fail(h, RIB_ERR_INVALID, fmt("rib_mci_frames: frames %d..%d are outside the segment 0..%d", k_first, k_first + T - 1, sample_rate));
+  if ((reinterpret_cast<uintptr_t>(field_i16) & 1) != 0 || (reinterpret_cast<uintptr_t>(out_f32_nchw) & 3) != 0)
+    return fail(h, RIB_ERR_INVALID, "rib_mci_frames: misaligned pointer");
+  MciFramesParams fp;
+  fp.a = a_u8; fp.b = b_u8; fp.field = field_i16; fp.out_f32 = out_f32_nchw; fp.out_u8 = out_u8_nhwc;
+  fp.T = T; fp.B = B; fp.H = H; fp.W = W; fp.Hb = L.Hb[0]; fp.Wb = L.Wb[0]; fp.s = sample_rate; fp.k_first = k_first;
+  fp.ls = 0;
+  while ((1 << fp.ls) < sample_rate) ++fp.ls;
+  fp.vec = (W % 4 == 0 && (reinterpret_cast<uintptr_t>(out_f32_nchw) & 15) == 0 && (reinterpret_cast<uintptr_t>(out_u8_nhwc) & 3) == 0) ? 1 : 0;
+  HIP_TRY(h, hipSetDevice(h->device));
+  const size_t lds = out_u8_nhwc ? (size_t)W * 3 + 32 : 0;
+  hipLaunchKernelGGL(k_mci_frames, dim3(H, T * B), dim3(256), lds, reinterpret_cast<hipStream_t>(hip_stream), fp);
   HIP_TRY(h, hipGetLastError());
   return RIB_OK;
 }

@@ -1,0 +1,280 @@
+// mci.hip.h — motion-compensated interpolation of a segment's two key frames: the folder driver's background="mci"
+// (rib_mci_field / rib_mci_frames, include/rib.h).  This project's interpolation, not DAIN.
+//
+// background.py (mci_field_host, mci_frames_host) states the result in integers; every kernel here is bit-equal to it.
+//
+//   k_mci_luma_pyramid  grid (tiles of 32 x 32, 2B): luma Y = (77 R + 150 G + 29 B + 128) >> 8 of one tile and, from LDS, its
+//                       16 x 16 of level 1 and 8 x 8 of level 2 ((2x2 parents, clamped, + 2) >> 2): aligned tiles nest, a
+//                       clamped parent is the tile's own.  Image n < B is A[n], else B[n - B].
+//   k_mci_search<R>     grid (runs of MCI_RUN blocks, B): bilateral block matching of one pyramid level.  A workgroup owns a
+//                       run of MCI_RUN consecutive blocks; it stages, once, the two luma windows of every block - (8 + 2R)^2
+//                       bytes of A around p - start and of B around p + start, already clamped - in LDS; a wave then takes a
+//                       block, its lanes the candidates (R = 4: 81 candidates, one per lane in two passes; R = 1: 9
+//                       candidates x 4 row pairs, summed over the 4 lanes by shuffles), and the winner is the wave minimum
+//                       of the packed key (cost << 22 | dx^2 + dy^2 << 12 | dy + 32 << 6 | dx + 32): the order of the tuple
+//                       (cost, |d|^2, dy, dx), whatever the lane order.  No atomics.
+//   k_mci_median        3x3 componentwise median of the level-0 field, clamped.
+//   k_mci_frames        grid (H, T * B): a workgroup owns ONE row of one frame; a thread takes 4 consecutive x: D(p) bilinear
+//                       from the block field (exact, 1/256 px), the two fixed-point bilinear samples, the blend; float4 stores
+//                       per channel plane of the normalised NCHW tensor, and the uint8 NHWC row through LDS as 16-byte
+//                       stores contiguous across the wave (k_panel's scheme).  Either output may be null.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "resize.hip.h"      // rsz_normalise: ToTensor + Normalize(0.5, 0.5) as the driver's upload computes it
+
+namespace rib {
+
+constexpr int MCI_BLOCK = 8, MCI_LAMBDA = 4, MCI_TOP_R = 4, MCI_KEY_BIAS = 32;      // background.py BLOCK, LAMBDA, SEARCH_TOP, KEY_BIAS
+constexpr int MCI_RUN = 8;                  // blocks per workgroup of k_mci_search
+constexpr int MCI_MAX_SIDE = 16384, MCI_MAX_RATE = 1024;
+
+struct MciLumaParams {
+  const uint8_t *a, *b;                     // [B, H, W, 3]
+  uint8_t *y0, *y1, *y2;                    // [2B, h_l, w_l]
+  int B, H, W, h1, w1, h2, w2, tilesX;
+};
+
+__global__ __launch_bounds__(256) void k_mci_luma_pyramid(MciLumaParams p) {
+  __shared__ uint8_t s0[32][32];
+  __shared__ uint8_t s1[16][16];
+  const int tid = threadIdx.x, n = blockIdx.y;
+  const int ty = blockIdx.x / p.tilesX, tx = blockIdx.x - ty * p.tilesX;
+  const uint8_t* src = (n < p.B ? p.a + (size_t)n * p.H * p.W * 3 : p.b + (size_t)(n - p.B) * p.H * p.W * 3);
+  const int y00 = ty * 32, x00 = tx * 32;
+  for (int i = tid; i < 1024; i += 256) {
+    const int ly = i >> 5, lx = i & 31, y = y00 + ly, x = x00 + lx;
+    if (y < p.H && x < p.W) {
+      const uint8_t* px = src + ((size_t)y * p.W + x) * 3;
+      const uint8_t v = (uint8_t)((77 * px[0] + 150 * px[1] + 29 * px[2] + 128) >> 8);
+      s0[ly][lx] = v;
+      p.y0[((size_t)n * p.H + y) * p.W + x] = v;
+    }
+  }
+  __syncthreads();
+  {
+    const int ly = tid >> 4, lx = tid & 15, y = ty * 16 + ly, x = tx * 16 + lx;
+    if (y < p.h1 && x < p.w1) {
+      const int r0 = 2 * ly, r1 = min(2 * y + 1, p.H - 1) - y00, c0 = 2 * lx, c1 = min(2 * x + 1, p.W - 1) - x00;
+      const uint8_t v = (uint8_t)((s0[r0][c0] + s0[r0][c1] + s0[r1][c0] + s0[r1][c1] + 2) >> 2);
+      s1[ly][lx] = v;
+      p.y1[((size_t)n * p.h1 + y) * p.w1 + x] = v;
+    }
+  }
+  __syncthreads();
+  if (tid < 64) {
+    const int ly = tid >> 3, lx = tid & 7, y = ty * 8 + ly, x = tx * 8 + lx;
+    if (y < p.h2 && x < p.w2) {
+      const int r0 = 2 * ly, r1 = min(2 * y + 1, p.h1 - 1) - ty * 16, c0 = 2 * lx, c1 = min(2 * x + 1, p.w1 - 1) - tx * 16;
+      p.y2[((size_t)n * p.h2 + y) * p.w2 + x] = (uint8_t)((s1[r0][c0] + s1[r0][c1] + s1[r1][c0] + s1[r1][c1] + 2) >> 2);
+    }
+  }
+}
+
+struct MciSearchParams {
+  const uint8_t* y;                         // [2B, h, w]: A[b] at b, B[b] at B + b
+  const int16_t* coarse;                    // [B, Hbc, Wbc, 2] (dx, dy) of the coarser level, or null (start = 0)
+  int16_t* out;                             // [B, Hb, Wb, 2]
+  int B, h, w, Hb, Wb, Hbc, Wbc;
+};
+
+template <int R>
+__global__ __launch_bounds__(256) void k_mci_search(MciSearchParams p) {
+  constexpr int WS = MCI_BLOCK + 2 * R, WIN = WS * WS, SIDE = 2 * R + 1, NC = SIDE * SIDE;
+  constexpr int PARTS = (NC * 4 <= 64) ? 4 : 1, ROWS = MCI_BLOCK / PARTS;
+  __shared__ uint8_t s_win[MCI_RUN][2][WIN];
+  __shared__ int s_start[MCI_RUN][2];
+  const int tid = threadIdx.x, b = blockIdx.y;
+  const int nblk = p.Hb * p.Wb, blk0 = blockIdx.x * MCI_RUN;
+  if (tid < MCI_RUN) {
+    int sx = 0, sy = 0;
+    const int blk = blk0 + tid;
+    if (blk < nblk && p.coarse) {
+      const int by = blk / p.Wb, bx = blk - by * p.Wb;
+      const int16_t* c = p.coarse + (((size_t)b * p.Hbc + min(by >> 1, p.Hbc - 1)) * p.Wbc + min(bx >> 1, p.Wbc - 1)) * 2;
+      sx = 2 * c[0]; sy = 2 * c[1];
+    }
+    s_start[tid][0] = sx; s_start[tid][1] = sy;
+  }
+  __syncthreads();
+  for (int i = tid; i < MCI_RUN * 2 * WIN; i += 256) {
+    const int j = i / (2 * WIN), rem = i - j * 2 * WIN, which = rem / WIN, e = rem - which * WIN;
+    const int wy = e / WS, wx = e - wy * WS, blk = blk0 + j;
+    if (blk < nblk) {
+      const int by = blk / p.Wb, bx = blk - by * p.Wb, sgn = which ? 1 : -1;
+      const int y = min(max(MCI_BLOCK * by + sgn * s_start[j][1] - R + wy, 0), p.h - 1);
+      const int x = min(max(MCI_BLOCK * bx + sgn * s_start[j][0] - R + wx, 0), p.w - 1);
+      s_win[j][which][e] = p.y[((size_t)(which ? p.B + b : b) * p.h + y) * p.w + x];
+    }
+  }
+  __syncthreads();
+  const int wave = tid >> 6, lane = tid & 63;
+  for (int j = wave; j < MCI_RUN; j += 4) {
+    const int blk = blk0 + j;
+    if (blk >= nblk) break;                 // (uniform per wave; no barrier below)
+    const int by = blk / p.Wb, bx = blk - by * p.Wb;
+    const int ph = min(MCI_BLOCK, p.h - MCI_BLOCK * by), pw = min(MCI_BLOCK, p.w - MCI_BLOCK * bx);
+    const int sx = s_start[j][0], sy = s_start[j][1];
+    const uint8_t *wa = s_win[j][0], *wb = s_win[j][1];
+    unsigned long long best = ~0ull;
+    for (int c0 = 0; c0 < NC * PARTS; c0 += 64) {
+      const int id = c0 + lane, c = id / PARTS, part = id - c * PARTS;
+      const bool active = c < NC;
+      const int ddy = active ? c / SIDE - R : 0, ddx = active ? c - (c / SIDE) * SIDE - R : 0;
+      int sad = 0;
+      for (int r = part * ROWS; r < (part + 1) * ROWS; ++r) {
+        if (r < ph) {
+          const uint8_t* ra = wa + (r - ddy + R) * WS + (R - ddx);
+          const uint8_t* rb = wb + (r + ddy + R) * WS + (R + ddx);
+          for (int x = 0; x < pw; ++x) sad += abs((int)ra[x] - (int)rb[x]);
+        }
+      }
+#pragma unroll
+      for (int m = 1; m < PARTS; m <<= 1) sad += __shfl_xor(sad, m);
+      const int dx = sx + ddx, dy = sy + ddy;
+      const unsigned long long key = ((unsigned long long)(sad + MCI_LAMBDA * (abs(dx) + abs(dy))) << 22) |
+                                     ((unsigned long long)(dx * dx + dy * dy) << 12) |
+                                     ((unsigned long long)((dy + MCI_KEY_BIAS) & 63) << 6) | (unsigned long long)((dx + MCI_KEY_BIAS) & 63);
+      if (active && key < best) best = key;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      const unsigned long long o = __shfl_xor(best, m);
+      if (o < best) best = o;
+    }
+    if (lane == 0) {
+      int16_t* o = p.out + ((size_t)b * nblk + blk) * 2;
+      o[0] = (int16_t)((int)(best & 63) - MCI_KEY_BIAS);
+      o[1] = (int16_t)((int)((best >> 6) & 63) - MCI_KEY_BIAS);
+    }
+  }
+}
+
+// the median of nine by a fixed network of 19 compare-exchanges (statically indexed: the values stay in registers)
+__device__ inline void mci_cx(int& a, int& b) { const int lo = min(a, b), hi = max(a, b); a = lo; b = hi; }
+__device__ inline int mci_median9(int v[9]) {
+  mci_cx(v[1], v[2]); mci_cx(v[4], v[5]); mci_cx(v[7], v[8]);
+  mci_cx(v[0], v[1]); mci_cx(v[3], v[4]); mci_cx(v[6], v[7]);
+  mci_cx(v[1], v[2]); mci_cx(v[4], v[5]); mci_cx(v[7], v[8]);
+  mci_cx(v[0], v[3]); mci_cx(v[5], v[8]); mci_cx(v[4], v[7]);
+  mci_cx(v[3], v[6]); mci_cx(v[1], v[4]); mci_cx(v[2], v[5]);
+  mci_cx(v[4], v[7]); mci_cx(v[4], v[2]); mci_cx(v[6], v[4]);
+  mci_cx(v[4], v[2]);
+  return v[4];
+}
+
+__global__ __launch_bounds__(256) void k_mci_median(const int16_t* __restrict__ in, int16_t* __restrict__ out, int B, int Hb, int Wb) {
+  const int nblk = Hb * Wb;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < B * nblk; i += gridDim.x * 256) {
+    const int b = i / nblk, blk = i - b * nblk, by = blk / Wb, bx = blk - by * Wb;
+    int vx[9], vy[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      const int y = min(max(by + k / 3 - 1, 0), Hb - 1), x = min(max(bx + k % 3 - 1, 0), Wb - 1);
+      const int16_t* s = in + ((size_t)b * nblk + y * Wb + x) * 2;
+      vx[k] = s[0]; vy[k] = s[1];
+    }
+    out[(size_t)i * 2] = (int16_t)mci_median9(vx);
+    out[(size_t)i * 2 + 1] = (int16_t)mci_median9(vy);
+  }
+}
+
+struct MciFramesParams {
+  const uint8_t *a, *b;                     // [B, H, W, 3]
+  const int16_t* field;                     // [B, Hb, Wb, 2]
+  float* out_f32;                           // [T, B, 3, H, W] or null
+  uint8_t* out_u8;                          // [T, B, H, W, 3] or null
+  int T, B, H, W, Hb, Wb, s, ls, k_first;
+  int vec;                                  // W % 4 == 0 and the outputs are aligned: float4 stores, dword LDS writes
+};
+
+// one bilinear sample of an RGB frame at (py, px) in 1/256 px, edge clamp (background.sample_bilinear)
+__device__ inline void mci_sample(const uint8_t* img, int H, int W, int py, int px, int v[3]) {
+  const int fy = py & 255, fx = px & 255;
+  const int y0 = min(max(py >> 8, 0), H - 1), y1 = min(max((py >> 8) + 1, 0), H - 1);
+  const int x0 = min(max(px >> 8, 0), W - 1), x1 = min(max((px >> 8) + 1, 0), W - 1);
+  const uint8_t *p00 = img + ((size_t)y0 * W + x0) * 3, *p01 = img + ((size_t)y0 * W + x1) * 3;
+  const uint8_t *p10 = img + ((size_t)y1 * W + x0) * 3, *p11 = img + ((size_t)y1 * W + x1) * 3;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    v[c] = ((256 - fy) * ((256 - fx) * p00[c] + fx * p01[c]) + fy * ((256 - fx) * p10[c] + fx * p11[c]) + (1 << 15)) >> 16;
+}
+
+__global__ __launch_bounds__(256) void k_mci_frames(MciFramesParams p) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_mci[];
+  const int y = blockIdx.x, tb = blockIdx.y, t = tb / p.B, bi = tb - t * p.B;
+  const int H = p.H, W = p.W, k = p.k_first + t, s = p.s, ls = p.ls;
+  const int rowbytes = W * 3;
+  uint8_t* grow = p.out_u8 ? p.out_u8 + ((size_t)tb * H + y) * (size_t)rowbytes : nullptr;
+  const int shift = (int)(reinterpret_cast<uintptr_t>(grow) & 15);
+  uint8_t* srow = s_mci + shift;
+  const uint8_t* A = p.a + (size_t)bi * H * W * 3;
+  const uint8_t* Bf = p.b + (size_t)bi * H * W * 3;
+  const int16_t* fld = p.field + (size_t)bi * p.Hb * p.Wb * 2;
+  const int tyy = 2 * y - (MCI_BLOCK - 1), fy = tyy & 15;
+  const int r0 = min(max(tyy >> 4, 0), p.Hb - 1), r1 = min(max((tyy >> 4) + 1, 0), p.Hb - 1);
+  const size_t HW = (size_t)H * W;
+  const int W4 = (W + 3) >> 2;
+  for (int item = threadIdx.x; item < W4; item += 256) {
+    const int x0 = item * 4;
+    uint8_t q[12];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int x = min(x0 + j, W - 1);
+      const int txx = 2 * x - (MCI_BLOCK - 1), fx = txx & 15;
+      const int c0 = min(max(txx >> 4, 0), p.Wb - 1), c1 = min(max((txx >> 4) + 1, 0), p.Wb - 1);
+      const int16_t *f00 = fld + (r0 * p.Wb + c0) * 2, *f01 = fld + (r0 * p.Wb + c1) * 2;
+      const int16_t *f10 = fld + (r1 * p.Wb + c0) * 2, *f11 = fld + (r1 * p.Wb + c1) * 2;
+      const int Dx = (16 - fy) * ((16 - fx) * f00[0] + fx * f01[0]) + fy * ((16 - fx) * f10[0] + fx * f11[0]);
+      const int Dy = (16 - fy) * ((16 - fx) * f00[1] + fx * f01[1]) + fy * ((16 - fx) * f10[1] + fx * f11[1]);
+      const int ax = (2 * k * Dx + (s >> 1)) >> ls, ay = (2 * k * Dy + (s >> 1)) >> ls;
+      const int bx = (2 * (s - k) * Dx + (s >> 1)) >> ls, by = (2 * (s - k) * Dy + (s >> 1)) >> ls;
+      int va[3], vb[3];
+      mci_sample(A, H, W, (y << 8) - ay, (x << 8) - ax, va);
+      mci_sample(Bf, H, W, (y << 8) + by, (x << 8) + bx, vb);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) q[j * 3 + c] = (uint8_t)(((s - k) * va[c] + k * vb[c] + (s >> 1)) >> ls);
+    }
+    if (p.out_f32) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        float* dst = p.out_f32 + ((size_t)tb * 3 + c) * HW + (size_t)y * W + x0;
+        if (p.vec) {
+          *reinterpret_cast<float4*>(dst) = make_float4(rsz_normalise(q[c]), rsz_normalise(q[3 + c]), rsz_normalise(q[6 + c]), rsz_normalise(q[9 + c]));
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (x0 + j < W) dst[j] = rsz_normalise(q[j * 3 + c]);
+        }
+      }
+    }
+    if (grow) {
+      uint8_t* dst = srow + x0 * 3;
+      if (p.vec) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d)
+          reinterpret_cast<uint32_t*>(dst)[d] = (uint32_t)q[4 * d] | ((uint32_t)q[4 * d + 1] << 8) | ((uint32_t)q[4 * d + 2] << 16) | ((uint32_t)q[4 * d + 3] << 24);
+      } else {
+        const int nb = min(4, W - x0) * 3;
+#pragma unroll
+        for (int j = 0; j < 12; ++j)
+          if (j < nb) dst[j] = q[j];
+      }
+    }
+  }
+  if (!grow) return;                        // (uniform: no thread reaches the barrier)
+  __syncthreads();
+  const int nlines = (shift + rowbytes + 15) >> 4;
+  uint8_t* gline = grow - shift;            // 16-byte aligned; only bytes [shift, shift + rowbytes) are this row's
+  for (int j = threadIdx.x; j < nlines; j += 256) {
+    const int lo = j * 16;
+    if (lo >= shift && lo + 16 <= shift + rowbytes) {
+      *reinterpret_cast<uint4*>(gline + lo) = reinterpret_cast<const uint4*>(s_mci)[j];
+    } else {
+      for (int kk = max(lo, shift); kk < min(lo + 16, shift + rowbytes); ++kk) gline[kk] = s_mci[kk];
+    }
+  }
+}
+
+}  // namespace rib

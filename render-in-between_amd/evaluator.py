@@ -48,6 +48,7 @@ from typing import List
 import numpy as np
 import torch
 
+from . import background as _background
 from . import io_worker, rasterise
 from . import metrics as _metrics
 from . import panel as _panel
@@ -515,7 +516,8 @@ class Evaluator:
     @torch.no_grad()
     def evaluate_from_folder(self, model, train_dir, dain_dir, pose_dir, save_dir, gt_dir=None, gen_vid=False,
                              rank=None, world=None, metrics=False, mask_dir=None, pose_mask=False,
-                             panels=False, panel_frames=False, panel_quality=90, panel_fps=30, panel_encode="host"):
+                             panels=False, panel_frames=False, panel_quality=90, panel_fps=30, panel_encode="host",
+                             background="dain"):
         """rank / world: this process's share of the independent units (default: the torch.distributed process
         group when one is initialised, else everything).  Returns the frames THIS rank wrote.
         The call is one `_FolderPipeline` (below): plan a clip -> decode -> upload -> render -> sink, pipelined over units
@@ -540,7 +542,20 @@ class Evaluator:
         integers - written on the native path by rib_jpeg right behind rib_panel: the lengths ride home in the unit's copy, the
         finisher then fetches exactly the files' bytes and writes %04d.jpg itself, no worker and no PIL involved; the raw sheets
         stay on the device unless panel_frames wants the lossless copies.  A model behind the reference's protocol encodes
-        with jpeg_encode_host on the host: the same files."""
+        with jpeg_encode_host on the host: the same files.
+        background="mci" (default "dain": one background frame per output frame from dain_dir, as the reference): the
+        background frames are a motion-compensated interpolation of each segment's two key frames (background.py states it in
+        integers; this project's interpolation, NOT DAIN - the generator was trained on DAIN backgrounds, the quality on real
+        footage has not been measured, and motion beyond +-32 px between key frames falls outside the search).  dain_dir may be
+        None and is never listed or read; a frame's file is named after its pose file (stem without a trailing "_keypoints").
+        On the native path the field is made once per group of segments (rib_mci_field) and every unit's frames by one launch
+        (rib_mci_frames) on the upload stream - no DAIN bytes are staged or decoded; a model behind the reference's protocol is
+        fed mci_frames_host, normalised as the native upload normalises (background.normalised_upload): the same files.  The DAIN_* metrics and the sheets' DAIN pane then show the MCI frames."""
+        if background not in ("dain", "mci"):
+            raise ValueError("evaluate_from_folder: background must be 'dain' or 'mci', got %r" % (background,))
+        if background == "mci" and self.resize_on == "gpu":
+            raise ValueError("evaluate_from_folder: background='mci' with resize_on='gpu' is not supported (there is no DAIN list to "
+                             "plan the GPU resize for)")
         if gen_vid:
             # the reference also writes <save_dir>/<clip>.mp4 (evaluator.py:267-269, utils.make_video) from a matplotlib canvas
             # through an H.264 encoder; neither is built, and silently ignoring the flag would drop an output the caller asked for
@@ -570,7 +585,8 @@ class Evaluator:
         self.metrics = self.metrics_report = None
         pipe = _FolderPipeline(self, model, rank, world, gt_dir, metrics=bool(metrics), mask_dir=mask_dir, pose_mask=bool(pose_mask),
                                panels=bool(panels), panel_frames=bool(panel_frames), panel_quality=int(panel_quality),
-                               panel_encode=panel_encode)
+                               panel_encode=panel_encode, background=background)
+        self.background = background
         self.timings = pipe.tm
         if metrics and pipe.native:
             self._quality_model = model
@@ -630,6 +646,11 @@ class _Clip:
         self.want_gt = measure
         self.stage_key, self.key_slot, self.key_of, self.pan = {}, {}, {}, {}
         self.sheet_futs = []                # futures of sheet files that ride in no unit's sink
+        # background="mci": key frame index -> its uint8 HWC bytes as decoded and resized (filled by the decode tasks);
+        # group -> (left keys, right keys uint8 [B,H,W,3], field int16 [B,Hb,Wb,2]) on the device, made in the group's first
+        # chunk and kept for its later chunks beside prev_of; both are released at the end of run_native / run_reference
+        self.key_u8, self.mci_of = {}, {}
+        self.stage_mk = {}                  # background="mci": first-chunk unit -> uint8 [2,B,H,W,3] section of its staging block
 
     def sheet_names(self, i, png):
         """(jpg, png or None) of frame i's sheet."""
@@ -661,7 +682,8 @@ class _FolderPipeline:
     (tests/test_driver.py)."""
 
     def __init__(self, ev, model, rank, world, gt_dir, metrics=False, mask_dir=None, pose_mask=False,
-                 panels=False, panel_frames=False, panel_quality=90, panel_encode="host"):
+                 panels=False, panel_frames=False, panel_quality=90, panel_encode="host", background="dain"):
+        self.mci = background == "mci"
         self.ev, self.model, self.rank, self.world, self.gt_dir = ev, model, rank, world, gt_dir
         self.metrics, self.mask_dir, self.pose_mask = metrics, mask_dir, pose_mask
         self.panels, self.panel_frames, self.panel_quality = panels, panel_frames, panel_quality
@@ -674,6 +696,8 @@ class _FolderPipeline:
             raise RuntimeError("resize_on='gpu': this model has no GPU resize kernel (rib_resize_cubic)")
         if self.native and panels and not hasattr(model, "panel"):
             raise RuntimeError("panels=True: this model has no GPU sheet kernel (rib_panel)")
+        if self.native and self.mci and not hasattr(model, "mci_frames"):
+            raise RuntimeError("background='mci': this model has no GPU interpolation kernels (rib_mci_field / rib_mci_frames)")
         self.jpeg_gpu = panels and panel_encode == "gpu"     # the sheets' JPEG files are jpeg_encode_host's bytes (rib_jpeg on the native path)
         if self.native and self.jpeg_gpu and not hasattr(model, "jpeg_into"):
             raise RuntimeError("panel_encode='gpu': this model has no GPU JPEG kernels (rib_jpeg)")
@@ -728,11 +752,19 @@ class _FolderPipeline:
         frames_dir = os.path.join(save_dir, sub)
         os.makedirs(frames_dir, exist_ok=True)
         image_list = _list(os.path.join(train_dir, sub), ("jpg", "png"))
-        dain_list = _list(os.path.join(dain_dir, sub), ("jpg", "png"))
+        dain_list = None if self.mci else _list(os.path.join(dain_dir, sub), ("jpg", "png"))
         pose_list = _list(os.path.join(pose_dir, sub), ("json",))
+        if self.mci and len(image_list) < 2:
+            raise ValueError("background='mci': clip %s has %d key frame(s); a segment needs two" % (sub, len(image_list)))
         sample_rate = sample_rate_of(len(pose_list), len(image_list))
         seq_len = (len(image_list) - 1) * sample_rate + 1
-        names = [os.path.join(frames_dir, os.path.basename(dain_list[i]))[:-4] + ".png" for i in range(seq_len)]
+        if self.mci:                         # no DAIN list to name the frames after: the pose file's stem
+            def stem(path):
+                base = os.path.splitext(os.path.basename(path))[0]
+                return base[:-len("_keypoints")] if base.endswith("_keypoints") else base
+            names = [os.path.join(frames_dir, stem(pose_list[i]) + ".png") for i in range(seq_len)]
+        else:
+            names = [os.path.join(frames_dir, os.path.basename(dain_list[i]))[:-4] + ".png" for i in range(seq_len)]
         gtlist = _list(os.path.join(self.gt_dir, sub), ("jpg", "png")) if self.gt_dir is not None else None
         mask_list = None
         if self.metrics:
@@ -791,12 +823,12 @@ class _FolderPipeline:
         """Pre-load of frame i on a pool thread (evaluator.py:205-235)."""
         ev = self.ev
         staged_raw = i in clip.slot and clip.src_dain is not None
-        dain = None if staged_raw else (ev.load_image_u8 if self.native else ev.load_image)(clip.dain_list[i])[0]
+        dain = None if (staged_raw or self.mci) else (ev.load_image_u8 if self.native else ev.load_image)(clip.dain_list[i])[0]
         if i in clip.slot:
             ui, t, b = clip.slot[i]
             if staged_raw:                       # resize_on="gpu": at the file's own size, straight into the slot
                 io_worker.decode_raw_into(clip.stage[ui][t, b].numpy(), 0, clip.dain_list[i], clip.src_dain)
-            else:
+            elif not self.mci:                   # (background="mci": nothing to stage, the background frames are made on the GPU)
                 clip.stage[ui][t, b].copy_(dain)
             dain = None
             if clip.want_gt and clip.src_gt is not None:
@@ -805,12 +837,17 @@ class _FolderPipeline:
                 clip.stage_gt[ui][t, b].copy_(ev.load_image_u8(clip.gtlist[i])[0])
             if clip.measure and clip.mask_list is not None:
                 clip.stage_mask[ui][t, b].copy_(torch.from_numpy(io_worker.load_mask_u8(clip.mask_list[i], ev.width, ev.height)))
-        elif i in clip.key_slot:                 # panels: a key frame's DAIN frame, for its sheet
+        elif i in clip.key_slot and not self.mci:        # panels: a key frame's DAIN frame, for its sheet
             ui, b, _ = clip.key_slot[i]
             clip.stage_key[ui][b].copy_(dain)
             dain = None
         ref_img = clip.ref_image(i)
-        gt = ev.load_image(ref_img)[0] if i % clip.sample_rate == 0 else None
+        if self.mci and i % clip.sample_rate == 0:       # one decode: the uint8 bytes for the interpolation, normalised for the chain
+            u8 = ev._decode_resized_u8(ref_img)[0]
+            clip.key_u8[i] = torch.from_numpy(u8.copy())
+            gt = torch.from_numpy(io_worker.normalised_chw(u8))
+        else:
+            gt = ev.load_image(ref_img)[0] if i % clip.sample_rate == 0 else None
         pose = ev.load_pose(clip.pose_list[i], self.image_size(ref_img))
         if self.gpu_labels:                      # host tables of the GPU rasteriser, built here in the worker
             pose = rasterise.frame_tables(pose[0], pose[1], ev.height, ev.width, ev.skeleton_thres, ev.foot_thres)
@@ -828,7 +865,7 @@ class _FolderPipeline:
             Tc, Bc = clip.stage[ui].shape[:2]
             k = t * Bc + b
             fsz = clip.stage[ui][0, 0].numel()   # a slot of the DAIN section: the model size, or the source size (resize_on="gpu")
-            name, off = clip.stage_blk[ui].name, k * fsz
+            name, off = clip.stage_blk[ui].name, (-1 if self.mci else k * fsz)
             if clip.want_gt:                     # GT frame (and mask) of a measured frame: further sections of the same block
                 gsz = clip.stage_gt[ui][0, 0].numel()
                 mask_off = Tc * Bc * (fsz + gsz) + k * ev.height * ev.width if clip.mask_list is not None else -1
@@ -838,7 +875,7 @@ class _FolderPipeline:
         elif i in clip.key_slot:                 # panels: a key frame's DAIN frame goes to the key section, at the model size
             ui, _, off = clip.key_slot[i]
             name = clip.stage_blk[ui].name
-        src = self.procs.submit(io_worker.load_frame_shm, name, off, clip.dain_list[i], clip.ref_image(i), clip.pose_list[i],
+        src = self.procs.submit(io_worker.load_frame_shm, name, off, None if self.mci else clip.dain_list[i], clip.ref_image(i), clip.pose_list[i],
                                 i % clip.sample_rate == 0, self.gpu_labels, ev.width, ev.height, ev.resize, ev.skeleton_thres, ev.foot_thres,
                                 *extra)
         out = Future()
@@ -846,6 +883,8 @@ class _FolderPipeline:
         def unpack(f):
             try:
                 _, gt, pose = f.result()
+                if self.mci and gt is not None:          # the key frame's uint8 bytes as decoded and resized, for the interpolation
+                    clip.key_u8[i] = torch.from_numpy(gt)
                 out.set_result((None, torch.from_numpy(io_worker.normalised_chw(gt)) if gt is not None else None, pose))
             except BaseException as e:              # noqa: BLE001 (handed to whoever waits for the frame)
                 out.set_exception(e)
@@ -871,6 +910,8 @@ class _FolderPipeline:
             (wd, hd), (wg, hg) = clip.src_dain or (ev.width, ev.height), clip.src_gt or (ev.width, ev.height)
             shape, shape_gt = (c1 - c0, len(members), hd, wd, 3), (c1 - c0, len(members), hg, wg, 3)
             shape_mask = (c1 - c0, len(members), ev.height, ev.width)
+            if self.mci:                        # no DAIN section: the unit stages no DAIN bytes
+                shape = (c1 - c0, len(members), 0, 0, 3)
             nb, nb_gt, nb_mask = (int(np.prod(s_)) for s_ in (shape, shape_gt, shape_mask))
             # metrics / panels: [DAIN frames | GT frames | masks | DAIN frames of the key frames] side by side in the unit's one
             # staging block; the last section only for a first chunk under panels (key-frame sheets)
@@ -879,8 +920,10 @@ class _FolderPipeline:
             if clip.mask_list is None:
                 nb_mask = 0
             fkey = ev.height * ev.width * 3
-            nb_key = len(members) * fkey if (self.panels and c0 == 0) else 0
-            total = nb + nb_gt + nb_mask + nb_key
+            nb_key = len(members) * fkey if (self.panels and c0 == 0 and not self.mci) else 0
+            # background="mci", first chunk: the group's left and right key frames' bytes go up from the unit's own block too
+            nb_mk = 2 * len(members) * fkey if (self.mci and c0 == 0) else 0
+            total = max(1, nb + nb_gt + nb_mask + nb_mk) if self.mci else nb + nb_gt + nb_mask + nb_key
             if self.procs is not None:      # shared with the decode workers and page-locked (back on the free list once uploaded)
                 clip.stage_blk[ui] = _shm_get(total)            # (size classes of 1 MB: the block may be larger than the unit)
                 flat = clip.stage_blk[ui].t[:total]
@@ -891,16 +934,24 @@ class _FolderPipeline:
                 clip.stage_gt[ui] = flat[nb:nb + nb_gt].view(*shape_gt)
             if clip.mask_list is not None:
                 clip.stage_mask[ui] = flat[nb + nb_gt:nb + nb_gt + nb_mask].view(*shape_mask)
+            if nb_mk:
+                clip.stage_mk[ui] = flat[total - nb_mk:total].view(2, len(members), ev.height, ev.width, 3)
             if nb_key:
                 clip.stage_key[ui] = flat[total - nb_key:].view(len(members), ev.height, ev.width, 3)
                 for b, si in enumerate(members):
                     clip.key_slot[clip.segs[si][0]] = (ui, b, total - nb_key + b * fkey)
+            elif self.panels and c0 == 0:       # background="mci": a key frame's own bytes are its background pane, nothing is staged
+                for b, si in enumerate(members):
+                    clip.key_slot[clip.segs[si][0]] = (ui, b, -1)
             for b, si in enumerate(members):
                 for t in range(c0, c1):
                     clip.slot[clip.segs[si][1][t]] = (ui, t - c0, b)
             # decode in the order the launch thread will ask for the frames: the unit's key frames first
             for i in ([clip.segs[si][0] for si in members] if c0 == 0 else []) + clip.unit_frames(ui):
                 self.submit_load(clip, i)
+            if self.mci and c0 == 0:            # the right key frames: decoded (not written: that is their own unit's rank)
+                for si in members:
+                    self.submit_load(clip, clip.segs[si][0] + clip.sample_rate)
             clip.opened += 1
 
     # ---- stage 2: upload -------------------------------------------------------------------------------------------------
@@ -930,12 +981,29 @@ class _FolderPipeline:
             lab = lab.to(g.device)
             klab = lab[Tc * Bc:] if key_poses else None
             lab = lab[:Tc * Bc].reshape(Tc, Bc, *lab.shape[1:])              # [Tc,B,22,H,W]
-            staged = clip.stage[ui].to(g.device, non_blocking=True)
-            if clip.src_dain is not None:      # resize_on="gpu": resize + ToTensor + Normalize in one kernel (rib_resize_cubic)
-                dn = g.resize_u8(staged.flatten(0, 1), ev.width, ev.height, normalised=True).view(Tc, Bc, 3, ev.height, ev.width)
+            staged = dnu8 = None
+            if self.mci:
+                if c0 == 0:                    # once per group: the key frames' bytes go up and the field is made
+                    ks = [clip.segs[si][0] for si in members]
+                    for k in ks:
+                        clip.loads[k + clip.sample_rate].result(timeout=IO_TIMEOUT_S)
+                    mk = clip.stage_mk[ui]    # page-locked, part of the unit's block: it goes back to the pool with it (sink)
+                    for b, k in enumerate(ks):
+                        mk[0, b].copy_(clip.key_u8[k])
+                        mk[1, b].copy_(clip.key_u8[k + clip.sample_rate])
+                    kab = mk.to(g.device, non_blocking=True)
+                    clip.mci_of[gi] = (kab[0], kab[1], g.mci_field(kab[0], kab[1]))
+                ka, kb, field = clip.mci_of[gi]
+                dn = g.mci_frames(ka, kb, field, clip.sample_rate, k_first=c0 + 1, count=Tc, normalised="both" if self.panels else True)
+                if self.panels:
+                    dn, dnu8 = dn
             else:
-                dn = staged.permute(0, 1, 4, 2, 3).to(torch.float32)
-                dn = ((dn / 255.0 - 0.5) / 0.5).contiguous()                      # [Tc,B,3,H,W]
+                staged = clip.stage[ui].to(g.device, non_blocking=True)
+                if clip.src_dain is not None:      # resize_on="gpu": resize + ToTensor + Normalize in one kernel (rib_resize_cubic)
+                    dn = g.resize_u8(staged.flatten(0, 1), ev.width, ev.height, normalised=True).view(Tc, Bc, 3, ev.height, ev.width)
+                else:
+                    dn = staged.permute(0, 1, 4, 2, 3).to(torch.float32)
+                    dn = ((dn / 255.0 - 0.5) / 0.5).contiguous()                      # [Tc,B,3,H,W]
             gtd = gt.to(g.device) if gt is not None else None
             gtf = staged_gt = None
             if clip.want_gt:
@@ -964,8 +1032,11 @@ class _FolderPipeline:
                     if src is not None:
                         u8 = g.resize_u8(u8.flatten(0, 1), ev.width, ev.height)
                     return normalise_exact(u8).reshape(Tc * Bc, 3, ev.height, ev.width)
-                dnp = shown(staged, clip.src_dain)
-                kdn = normalise_exact(clip.stage_key[ui].to(g.device, non_blocking=True)) if key_poses else None
+                dnp = normalise_exact(dnu8.flatten(0, 1)) if self.mci else shown(staged, clip.src_dain)
+                if self.mci:                   # a key frame's background is frame k = 0 of its segment: the key frame itself
+                    kdn = normalise_exact(clip.mci_of[gi][0]) if key_poses else None
+                else:
+                    kdn = normalise_exact(clip.stage_key[ui].to(g.device, non_blocking=True)) if key_poses else None
                 if staged_gt is not None:
                     gtp = shown(staged_gt, clip.src_gt)
                 else:                          # no gt_dir: the Ground Truth pane is the segment's left key frame (evaluator.py:209-212)
@@ -1127,7 +1198,10 @@ class _FolderPipeline:
         if not loose:
             return
         got = [clip.loads[k].result(timeout=IO_TIMEOUT_S) for k in loose]
-        dains = list(self.pool.map(lambda k: ev.load_image_u8(clip.dain_list[k])[0], loose))
+        if self.mci:                             # a key frame's background is the key frame itself (frame k = 0 of the interpolation)
+            dains = [clip.key_u8[k] for k in loose]
+        else:
+            dains = list(self.pool.map(lambda k: ev.load_image_u8(clip.dain_list[k])[0], loose))
         poses = [g_[2] for g_ in got]
         with torch.cuda.stream(st):
             if self.gpu_labels:
@@ -1180,6 +1254,7 @@ class _FolderPipeline:
         clip.stage_gt.pop(ui, None)
         clip.stage_mask.pop(ui, None)
         clip.stage_key.pop(ui, None)
+        clip.stage_mk.pop(ui, None)
         if in_blk is not None:
             _shm_put(in_blk)
         out_blk = r["out_blk"]
@@ -1241,6 +1316,10 @@ class _FolderPipeline:
             self.loose_key_sheets(clip, *(lanes[0] if lanes else (self.model, torch.cuda.current_stream(self.model.device))))
         tm["units"] = tm.get("units", 0) + len(clip.units)
         tm["frames"] += len(clip.futs)
+        # background="mci": the groups' key frames and fields are only read by launches already enqueued on the upload stream,
+        # where they were allocated: released with the clip (pipe.clips keeps the _Clip itself until drain)
+        clip.mci_of.clear()
+        clip.key_u8.clear()
 
     @property
     def sheet_saver(self):
@@ -1251,16 +1330,27 @@ class _FolderPipeline:
     def run_reference(self, clip):
         """Any callable that only speaks the reference's protocol (img, mask = model(label, None, dain, prev)): frame by frame."""
         ev, tm, model = self.ev, self.tm, self.model
-        for i in sorted(set(clip.keys) | {i for _, frames in clip.segs for i in frames}):
+        right = {k + clip.sample_rate for k, _ in clip.segs} if self.mci else set()     # decoded, written by their own rank
+        for i in sorted(set(clip.keys) | right | {i for _, frames in clip.segs for i in frames}):
             self.submit_load(clip, i)
         for k, frames in clip.segs:
             t0 = time.perf_counter()
             got = [clip.loads[i].result() for i in frames]
             gt = clip.loads[k].result()[1].unsqueeze(0)
+            if self.mci:
+                clip.loads[k + clip.sample_rate].result()
             t1 = time.perf_counter()
             tm["load"] += t1 - t0
             poses = [g[2] for g in got]
-            dn = torch.stack([g[0] for g in got]).unsqueeze(1)
+            if self.mci:                         # the host definition of the background frames (background.py)
+                ka, kb = clip.key_u8[k].numpy(), clip.key_u8[k + clip.sample_rate].numpy()
+                u8 = _background.mci_frames_host(ka, kb, _background.mci_field_host(ka, kb), clip.sample_rate, [i - k for i in frames])
+                # the floats the native chain reads (the device's normalisation, stated on the host); the sheets' DAIN pane
+                # shows the host's normalisation, as the native path's does (normalise_exact)
+                dn = torch.from_numpy(_background.normalised_upload(u8)).unsqueeze(1)
+                dn_shown = torch.from_numpy(_background.normalised(u8)).unsqueeze(1)
+            else:
+                dn = dn_shown = torch.stack([g[0] for g in got]).unsqueeze(1)
             lab = ev.make_labels(model, poses).unsqueeze(1)
             t2 = time.perf_counter()
             prev, outs, shown = gt, [], []
@@ -1277,7 +1367,7 @@ class _FolderPipeline:
                 def host(xs):
                     return torch.cat([x.detach().cpu().float() for x in xs]).numpy()
                 gtp = [ev.load_image(clip.gtlist[i])[0].unsqueeze(0) for i in frames] if clip.gtlist is not None else [gt] * len(frames)
-                sheets = _panel.compose_host(host([p_[0] for p_ in shown]), host([p_[1] for p_ in shown]), host(outs), host(list(dn)),
+                sheets = _panel.compose_host(host([p_[0] for p_ in shown]), host([p_[1] for p_ in shown]), host(outs), host(list(dn_shown)),
                                              host(gtp), host(list(lab)), self.titles)
                 for t, i in enumerate(frames):
                     clip.sheet_futs.append(self.pool.submit(self.sheet_saver, sheets[t], *clip.sheet_names(i, self.panel_frames), self.panel_quality))
@@ -1298,11 +1388,14 @@ class _FolderPipeline:
         if self.panels:                          # the key frames' sheets: the key-frame rule
             for k in clip.keys:
                 dain, key, pose = clip.loads[k].result()
+                if self.mci:                     # frame k = 0 of the interpolation: the key frame itself
+                    dain = key
                 klab = ev.make_labels(model, [pose]).detach().cpu().float().numpy()
                 sheet = _panel.compose_host(None, None, None, dain.unsqueeze(0).numpy(), key.unsqueeze(0).numpy(), klab, self.titles)[0]
                 clip.sheet_futs.append(self.pool.submit(self.sheet_saver, sheet, *clip.sheet_names(k, self.panel_frames), self.panel_quality))
         tm["units"] = tm.get("units", 0)
         tm["frames"] += len(clip.futs)
+        clip.key_u8.clear()
 
     # ---- metrics ---------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -1339,6 +1432,8 @@ class _FolderPipeline:
                                 clips_reported="every clip (the reference returns only the last clip's dict: it is overwritten per clip)"),
                "clips": {c: dict(_metrics.mean_record(pf), frames=len(pf), per_frame=pf) for c, pf in clips.items()},
                "overall": dict(_metrics.mean_record(recs), frames=len(recs))}
+        if self.mci:                             # the DAIN_* values measure the interpolated background (the keys keep their names)
+            rep["background"] = "mci"
         if self.rank == 0 or not grouped:
             name = "metrics.json" if (self.world == 1 or grouped) else "metrics_rank%d.json" % self.rank
             os.makedirs(save_dir, exist_ok=True)

@@ -549,6 +549,83 @@ class Generator:
                 _ptr(titles), _ptr(out), self._stream()))
         return out
 
+    # ---- motion-compensated background (background.py states both results; csrc/mci.hip.h) ------------------------------
+    def _mci_pair(self, a_u8, b_u8, who):
+        for x in (a_u8, b_u8):
+            if not torch.is_tensor(x) or x.dtype != torch.uint8 or x.dim() not in (3, 4) or x.shape[-1] != 3:
+                raise ValueError("%s: key frames must be uint8 [B,H,W,3] or [H,W,3] tensors, got %s %s"
+                                 % (who, getattr(x, "dtype", type(x)), tuple(getattr(x, "shape", ()))))
+            if x.device != self.device:
+                raise ValueError("%s: a key frame is on %s, the generator on %s (upload the frames first)" % (who, x.device, self.device))
+        if a_u8.shape != b_u8.shape:
+            raise ValueError("%s: the two key frames differ in shape: %s and %s" % (who, tuple(a_u8.shape), tuple(b_u8.shape)))
+        single = a_u8.dim() == 3
+        a = (a_u8.unsqueeze(0) if single else a_u8).contiguous()
+        b = (b_u8.unsqueeze(0) if single else b_u8).contiguous()
+        if min(a.shape[:3]) < 1:
+            raise ValueError("%s: empty key frames %s" % (who, tuple(a.shape)))
+        return a, b, single
+
+    def mci_field(self, a_u8, b_u8):
+        """The block displacement field of B key-frame pairs on the GPU (rib_mci_field; background.mci_field_host is the
+        definition and is bit-equal): a_u8, b_u8 uint8 [B,H,W,3] (or [H,W,3]) on this device, the left and right key frame of
+        each segment at the model size -> int16 [B,Hb,Wb,2] (or [Hb,Wb,2]), (dx, dy) per 8x8 block.  This project's
+        interpolation, not DAIN.  Five launches on the current stream."""
+        a, b, single = self._mci_pair(a_u8, b_u8, "mci_field")
+        B, H, W, _ = a.shape
+        n = int(self._lib.rib_mci_workspace_bytes(self._h, B, H, W))
+        if n == 0:
+            raise ValueError("mci_field: B=%d H=%d W=%d: 1 <= B <= 32767, H and W in 1..16384" % (B, H, W))
+        from .background import field_shape
+        Hb, Wb = field_shape(H, W)
+        with torch.cuda.device(self.device):
+            ws = torch.empty(n, dtype=torch.uint8, device=self.device)      # (per call: it belongs to the stream the call is enqueued on)
+            field = torch.empty((B, Hb, Wb, 2), dtype=torch.int16, device=self.device)
+            _native.check(self._h, self._lib.rib_mci_field(self._h, B, H, W, _ptr(a), _ptr(b), _ptr(field), _ptr(ws), self._stream()))
+        return field[0] if single else field
+
+    def mci_frames(self, a_u8, b_u8, field, sample_rate, k_first=1, count=None, normalised=True, out=None):
+        """Frames k_first .. k_first + count - 1 (count None: up to sample_rate - 1) of B segments from their key frames and
+        block fields, all in one launch (rib_mci_frames; background.mci_frames_host is the definition and is bit-equal):
+        a_u8, b_u8 uint8 [B,H,W,3], field int16 [B,Hb,Wb,2] (mci_field) on this device, sample_rate a power of two.
+        normalised=True: float32 [T,B,3,H,W], ToTensor + Normalize(0.5, 0.5) as the folder driver's upload computes it;
+        False: uint8 [T,B,H,W,3]; "both": the pair (float32, uint8).  [H,W,3] key frames give [T,3,H,W] / [T,H,W,3].
+        out: optional contiguous destination (for "both": a pair)."""
+        a, b, single = self._mci_pair(a_u8, b_u8, "mci_frames")
+        B, H, W, _ = a.shape
+        from .background import field_shape, log2_rate
+        Hb, Wb = field_shape(H, W)
+        log2_rate(sample_rate)
+        s = int(sample_rate)
+        if not torch.is_tensor(field) or field.dtype != torch.int16 or field.device != self.device:
+            raise ValueError("mci_frames: field must be an int16 tensor on %s (mci_field)" % (self.device,))
+        f = (field.unsqueeze(0) if field.dim() == 3 else field).contiguous()
+        if tuple(f.shape) != (B, Hb, Wb, 2):
+            raise ValueError("mci_frames: the field of %d %dx%d segments is [%d, %d, %d, 2], got %s" % (B, H, W, B, Hb, Wb, tuple(field.shape)))
+        k_first = int(k_first)
+        T = (s - k_first) if count is None else int(count)
+        if T < 1 or k_first < 0 or k_first + T - 1 > s:
+            raise ValueError("mci_frames: frames %d..%d are outside the segment 0..%d" % (k_first, k_first + T - 1, s))
+        if normalised not in (True, False, "both"):
+            raise ValueError("mci_frames: normalised must be True, False or 'both'")
+        fshape, ushape = (T, B, 3, H, W), (T, B, H, W, 3)
+        of, ou = (out if normalised == "both" else (out, None) if normalised else (None, out)) if out is not None else (None, None)
+
+        def dest(t, shape, dtype):
+            if t is None:
+                return torch.empty(shape, dtype=dtype, device=self.device)
+            v = t.unsqueeze(1) if (single and t.dim() == 4) else t
+            if tuple(v.shape) != shape or v.dtype != dtype or not v.is_contiguous() or v.device != self.device:
+                raise ValueError("mci_frames: out must be a contiguous %s %s tensor on %s" % (shape, dtype, self.device))
+            return v
+        with torch.cuda.device(self.device):
+            rf = dest(of, fshape, torch.float32) if normalised in (True, "both") else None
+            ru = dest(ou, ushape, torch.uint8) if normalised in (False, "both") else None
+            _native.check(self._h, self._lib.rib_mci_frames(self._h, T, B, H, W, _ptr(a), _ptr(b), _ptr(f), s, k_first,
+                                                            _ptr(rf), _ptr(ru), self._stream()))
+        res = tuple((r[:, 0] if single else r) for r in (rf, ru) if r is not None)
+        return res if normalised == "both" else res[0]
+
     def jpeg_max_bytes(self, height, width):
         """Upper bound of one JPEG file of a height x width image, header included (rib_jpeg_max_bytes; panel.jpeg_max_bytes)."""
         n = int(self._lib.rib_jpeg_max_bytes(int(height), int(width)))

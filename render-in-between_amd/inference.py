@@ -24,6 +24,12 @@ titles are this project's, not matplotlib's); `--panel-frames` keeps the lossles
 `--panel-encode gpu` encodes the video's JPEG frames on the GPU (rib_jpeg: baseline 4:2:0 with PIL's tables and one restart
 segment per MCU row, bit-equal to panel.jpeg_encode_host; the stream is ours, restated from ITU-T T.81, unpinned) instead of
 with PIL in the file workers (`host`, the default): the files' bytes come home instead of the raw sheets.
+
+Backgrounds without a DAIN folder: `--background mci` makes every background frame on the GPU from the segment's two key
+frames - a classical motion-compensated interpolation (background.py states it in integers; rib_mci_field / rib_mci_frames) -
+and never reads <input>/DAIN.  It is this project's interpolation, not DAIN: the generator was trained on DAIN backgrounds, the
+quality on real footage has not been measured, and motion beyond +-32 px between key frames falls outside the search.  Frames
+are then named after their pose files.  The default, `--background dain`, is the reference's contract.
 """
 import argparse
 import os
@@ -80,13 +86,14 @@ def summary_line(evaluator, rank=0, world=1):
     tm = evaluator.timings
     wall = max(tm.get("wall", 0.0), 1e-9)
     line = ("[rank %d/%d] %d frames in %.2f s = %.1f frames/s | load %.2f s, rasterise %.2f s, generate %.2f s, save tail %.2f s | "
-            "%d units, <= %d in flight | %d file workers (%s), CPU budget %d cores | PNG level %s, batch %d, %s plans | resize on %s"
+            "%d units, <= %d in flight | %d file workers (%s), CPU budget %d cores | PNG level %s, batch %d, %s plans | resize on %s | background %s"
             % (rank, world, tm.get("frames", 0), wall, tm.get("frames", 0) / wall, tm.get("load", 0.0), tm.get("rasterise", 0.0),
                tm.get("generate", 0.0), tm.get("save", 0.0), tm.get("units", 0), tm.get("peak_units_in_flight", 0),
                evaluator.io_threads, evaluator.io_mode, cpu_budget(),
                "reference (zlib 6)" if evaluator.png_compress_level is None else str(evaluator.png_compress_level),
                evaluator.batch or evaluator.default_batch(), "batch-invariant" if evaluator.reproducible else "per-batch",
-               getattr(evaluator, "resize_on", "host")))
+               getattr(evaluator, "resize_on", "host"),
+               {"dain": "DAIN frames", "mci": "mci (interpolated from the key frames)"}[getattr(evaluator, "background", "dain")]))
     rep = getattr(evaluator, "metrics_report", None)
     if "metrics" in tm and rep is not None:
         o = rep["overall"]
@@ -116,7 +123,7 @@ def main(opts):
     evaluator = Evaluator(config, batch=opts.batch or None, reproducible=opts.reproducible,
                           png_compress_level=None if opts.png_level == "reference" else int(opts.png_level), resize_on=opts.resize_on)
     train_dir = os.path.join(opts.input_dir, "inputs")
-    dain_dir = os.path.join(opts.input_dir, "DAIN")
+    dain_dir = os.path.join(opts.input_dir, "DAIN") if opts.background == "dain" else None
     pose_dir = os.path.join(opts.input_dir, "Predict_motion")
     save_dir = os.path.join(opts.save_dir, "Generated_frames")
     written = evaluator.evaluate_from_folder(net_G, train_dir, dain_dir, pose_dir, save_dir, gt_dir=opts.gt_dir, gen_vid=False,
@@ -124,7 +131,7 @@ def main(opts):
                                              panels=opts.panels, panel_frames=opts.panel_frames,
                                              panel_quality=90 if opts.panel_quality is None else opts.panel_quality,
                                              panel_fps=30 if opts.panel_fps is None else opts.panel_fps,
-                                             panel_encode=opts.panel_encode or "host")
+                                             panel_encode=opts.panel_encode or "host", background=opts.background)
     print(summary_line(evaluator, rank, world))
     if world > 1:
         print("[rank {}/{}] wrote {} frames".format(rank, world, len(written)))
@@ -181,6 +188,11 @@ def build_parser():
     parser.add_argument("--panel-encode", choices=("host", "gpu"), default=None,
                         help="with --panels: where the video's JPEG frames are encoded. 'host' (default): PIL in the file workers; 'gpu': "
                              "the HIP encoder (baseline 4:2:0, PIL's tables, a restart segment per MCU row; --panel-quality applies to both)")
+    parser.add_argument("--background", default="dain",
+                        help="where the background frames come from. 'dain' (default): <input-dir>/DAIN/<clip>/, one frame per output "
+                             "frame, as the reference; 'mci': interpolated on the GPU from each segment's two key frames (motion-compensated, "
+                             "this project's, not DAIN; the generator was trained on DAIN backgrounds and the quality on real footage has "
+                             "not been measured) - no DAIN folder is read, frames are named after their pose files")
     return parser
 
 
@@ -189,6 +201,10 @@ def parse_args(argv=None):
     opts = parser.parse_args(argv)
     if opts.png_level != "reference" and opts.png_level not in [str(i) for i in range(10)]:
         parser.error("--png-level must be 'reference' or a zlib level 0-9")
+    if opts.background not in ("dain", "mci"):
+        parser.error("--background must be 'dain' or 'mci', got %r" % (opts.background,))
+    if opts.background == "mci" and opts.resize_on == "gpu":
+        parser.error("--background mci with --resize-on gpu is not supported (there is no DAIN list to plan the GPU resize for)")
     if opts.metrics and opts.gt_dir is None:
         parser.error("--metrics needs --gt-dir (the ground-truth frames)")
     if opts.mask_dir is not None and not opts.metrics:

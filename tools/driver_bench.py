@@ -72,7 +72,11 @@ def main():
     ap.add_argument("--pose-mask", action="store_true", help="with --metrics: under the mask drawn from each frame's pose (pose_mask=True)")
     ap.add_argument("--panels", action="store_true", help="also write the diagnostic sheets and the clip's video (panels=True)")
     ap.add_argument("--panel-encode", default="host", choices=("host", "gpu"), help="with --panels: PIL in the file workers or rib_jpeg (panel_encode=...)")
+    ap.add_argument("--background", default="dain", choices=("dain", "mci"),
+                    help="'mci': the background frames are interpolated on the GPU from the key frames and the clip's DAIN folder is not read (background=...)")
     a = ap.parse_args()
+    if a.background == "mci" and a.resize_on == "gpu":
+        ap.error("--background mci with --resize-on gpu is not supported")
     if a.panel_encode != "host" and not a.panels:
         ap.error("--panel-encode is a setting of --panels")
     if a.pose_mask and not a.metrics:
@@ -87,11 +91,14 @@ def main():
         E = ev.Evaluator(cfg, lanes=a.lanes, batch=a.batch or None, chunk=a.chunk, io_threads=a.io_threads or None,
                          png_compress_level=None if a.compress < 0 else a.compress, io_mode=a.io_mode, resize_on=a.resize_on)
         dirs = [os.path.join(root, d) for d in ("inputs", "DAIN", "Predict_motion")]
+        if a.background == "mci":
+            dirs[1] = None
         walls = []
         for rep in range(1 + a.reps):           # the first run also builds launch plans and pools: not counted
             t0 = time.perf_counter()
             out = E.evaluate_from_folder(G, *dirs, os.path.join(root, "out%d" % rep), gt_dir=os.path.join(root, "gt") if a.metrics else None,
-                                         metrics=a.metrics, pose_mask=a.pose_mask, panels=a.panels, panel_encode=a.panel_encode)
+                                         metrics=a.metrics, pose_mask=a.pose_mask, panels=a.panels, panel_encode=a.panel_encode,
+                                         background=a.background)
             torch.cuda.synchronize()
             walls.append(time.perf_counter() - t0)
         tm = dict(E.timings)
@@ -101,7 +108,7 @@ def main():
     print(json.dumps({"height": H, "width": W, "dtype": a.dtype, "frames": n, "generated": gen, "lanes": a.lanes,
                       "batch": a.batch or E.default_batch(), "chunk": a.chunk, "io_threads": E.io_threads, "io_mode": a.io_mode,
                       "cpus": len(os.sched_getaffinity(0)), "cpu_budget": ev.cpu_budget(), "png_compress_level": a.compress,
-                      "src_height": a.src_height or H, "src_width": a.src_width or W, "resize_on": a.resize_on,
+                      "src_height": a.src_height or H, "src_width": a.src_width or W, "resize_on": a.resize_on, "background": a.background,
                       "metrics": a.metrics, "pose_mask": a.pose_mask, "metrics_overall": overall, "panels": a.panels, "panel_encode": a.panel_encode,
                       "wall_s": wall, "wall_s_runs": [round(w, 4) for w in walls[1:]], "frames_per_s_end_to_end": n / wall,
                       "phase_s_last_run": {k: round(v, 4) for k, v in tm.items() if k not in ("frames", "units", "timeline", "peak_units_in_flight")},

@@ -1,0 +1,67 @@
+#!/usr/bin/env python3
+"""The motion-compensated background on its own: rib_mci_field and rib_mci_frames (Generator.mci_field / mci_frames) on one
+unit - B segments of H x W at sample rate s - for a kernel trace.
+
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/mci_bench.py [--size 512] [--batch 4] [--rate 8] [--reps 20] [--u8]
+
+Prints one JSON line: the wall time of the field's five launches and of the frames launch between two events (median of
+--reps, after a warm-up), the frames launch's byte floor (12 bytes of float32 out per pixel and frame, 3 more with --u8, the
+two key frames once) and what that floor takes at 6.3 TB/s.  The kernels' own times are the k_mci_luma_pyramid, k_mci_search,
+k_mci_median and k_mci_frames rows of the trace's kernel statistics.  The key frames are a smooth synthetic scene and its
+translate, so that the search does real work.
+"""
+import argparse, json, os, sys
+import torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import render_in_between_amd as rib
+
+
+def timed(fn, reps):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    ms.sort()
+    return ms
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--height", type=int, default=0)
+    ap.add_argument("--width", type=int, default=0)
+    ap.add_argument("--batch", type=int, default=4)
+    ap.add_argument("--rate", type=int, default=8)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--u8", action="store_true", help="also write the uint8 NHWC frames (the sheets' DAIN pane)")
+    a = ap.parse_args()
+    H, W, B, s = a.height or a.size, a.width or a.size, a.batch, a.rate
+    G = rib.Generator(rib.hsm_gen_config()).eval()                 # no weights needed: these kernels read none
+    g = torch.Generator(device="cuda").manual_seed(0)
+    big = torch.nn.functional.interpolate(torch.rand(B, 3, (H + 32) // 8, (W + 32) // 8, device="cuda", generator=g) * 255,
+                                          size=(H + 32, W + 32), mode="bilinear", align_corners=False)
+    big = (big + torch.rand(B, 3, H + 32, W + 32, device="cuda", generator=g) * 24).clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1)
+    ka, kb = big[:, 16:16 + H, 16:16 + W].contiguous(), big[:, 10:10 + H, 24:24 + W].contiguous()
+    field = G.mci_field(ka, kb)
+    T = s - 1
+    f32 = torch.empty(T, B, 3, H, W, dtype=torch.float32, device="cuda")
+    u8 = torch.empty(T, B, H, W, 3, dtype=torch.uint8, device="cuda") if a.u8 else None
+    fms = timed(lambda: G.mci_field(ka, kb), a.reps)
+    rms = timed(lambda: G.mci_frames(ka, kb, field, s, normalised="both" if a.u8 else True, out=(f32, u8) if a.u8 else f32), a.reps)
+    floor = (12 + (3 if a.u8 else 0)) * H * W * T * B + 2 * 3 * H * W * B
+    print(json.dumps({"height": H, "width": W, "batch": B, "rate": s, "frames": T * B, "u8": a.u8,
+                      "field_event_us_median": round(fms[len(fms) // 2] * 1e3, 2), "field_event_us_min": round(fms[0] * 1e3, 2),
+                      "frames_event_us_median": round(rms[len(rms) // 2] * 1e3, 2), "frames_event_us_min": round(rms[0] * 1e3, 2),
+                      "frames_floor_bytes": floor, "frames_floor_us_at_6.3TB/s": round(floor / 6.3e12 * 1e6, 2),
+                      "field_nonzero_fraction": round(float((field != 0).float().mean()), 3)}))
+
+
+if __name__ == "__main__":
+    main()
