@@ -268,6 +268,13 @@ size_t rib_jpeg_workspace_bytes(rib_handle* h, int T, int H, int W);
 size_t rib_jpeg_max_bytes(int H, int W);
 int rib_jpeg(rib_handle* h, int T, int H, int W, const uint8_t* src_u8_nhwc, int quality,
              uint8_t* dst, size_t dst_stride, int32_t* lengths, void* workspace, void* hip_stream);
+/* rib_jpeg_float: the same files from the frames the chain produces - fp32 NCHW [T,3,H,W] in [-1, 1], 4-byte aligned - without the
+ * uint8 copy in between: byte for byte rib_jpeg(rib_quantise(src)), i.e. panel.jpeg_encode_host(panel.quantise_host(src)).
+ * Only the kernel's first step differs (the three channel planes are read, float4 where a row segment is 16-byte aligned and
+ * whole, and quantised with rib_quantise's arithmetic); the contract is rib_jpeg's: the same two size queries, the same
+ * workspace, refusals and errors, two launches, no atomics, a frame's bytes independent of T. */
+int rib_jpeg_float(rib_handle* h, int T, int H, int W, const float* src_f32_nchw, int quality,
+                 uint8_t* dst, size_t dst_stride, int32_t* lengths, void* workspace, void* hip_stream);
 
 /* ---- motion-compensated interpolation (MCI) of a segment's two key frames: the folder driver's background="mci" ----
  * This project's interpolation, NOT DAIN (the reference reads one DAIN frame per output frame; DAIN is an external network with

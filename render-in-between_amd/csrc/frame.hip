@@ -293,21 +293,25 @@ size_t rib_jpeg_workspace_bytes(rib_handle* h, int T, int H, int W) {
   return segs * jpeg_seg_bound((W + 15) / 16) + 256 + segs * sizeof(int32_t);      // the slots, then the segment lengths
 }
 
-int rib_jpeg(rib_handle* handle, int T, int H, int W, const uint8_t* src_u8_nhwc, int quality, uint8_t* dst, size_t dst_stride,
-             int32_t* lengths, void* workspace, void* hip_stream) {
+// rib_jpeg / rib_jpeg_float: one contract, two sources (k_jpeg_segments<uint8_t> / <float>, jpeg.hip.h)
+extern "C++" {
+template <typename S>
+static int jpeg_enqueue(const char* entry, rib_handle* handle, int T, int H, int W, const S* src, int quality, uint8_t* dst, size_t dst_stride,
+                        int32_t* lengths, void* workspace, void* hip_stream) {
   FrameState* h = frame_state(handle);
   if (!h) return RIB_ERR_INVALID;
-  if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_jpeg: host-only handle");
-  if (!src_u8_nhwc || !dst || !lengths || !workspace) return fail(h, RIB_ERR_INVALID, "rib_jpeg: null pointer");
+  if (h->device < 0) return fail(h, RIB_ERR_INVALID, fmt("%s: host-only handle", entry));
+  if (!src || !dst || !lengths || !workspace) return fail(h, RIB_ERR_INVALID, fmt("%s: null pointer", entry));
   if (T < 1 || T > 65535 || H < 1 || W < 1 || H > JPEG_MAX_DIM || W > JPEG_MAX_DIM || quality < 1 || quality > 100)
-    return fail(h, RIB_ERR_INVALID, fmt("rib_jpeg: T=%d H=%d W=%d quality=%d: 1 <= T <= 65535, H and W in 1..%d, quality in 1..100",
-                                        T, H, W, quality, JPEG_MAX_DIM));
+    return fail(h, RIB_ERR_INVALID, fmt("%s: T=%d H=%d W=%d quality=%d: 1 <= T <= 65535, H and W in 1..%d, quality in 1..100",
+                                        entry, T, H, W, quality, JPEG_MAX_DIM));
   if (dst_stride < (size_t)JPEG_HEADER_BYTES + 2 || dst_stride > (size_t)INT32_MAX)
-    return fail(h, RIB_ERR_INVALID, fmt("rib_jpeg: dst_stride=%zu: at least the header (%d bytes) and EOI, below 2 GiB", dst_stride, JPEG_HEADER_BYTES));
+    return fail(h, RIB_ERR_INVALID, fmt("%s: dst_stride=%zu: at least the header (%d bytes) and EOI, below 2 GiB", entry, dst_stride, JPEG_HEADER_BYTES));
   if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0 || (reinterpret_cast<uintptr_t>(lengths) & 3) != 0)
-    return fail(h, RIB_ERR_INVALID, "rib_jpeg: workspace must be 16-byte aligned, lengths 4-byte aligned");
-  JpegParams jp;
-  jp.src = src_u8_nhwc; jp.H = H; jp.W = W; jp.quality = quality;
+    return fail(h, RIB_ERR_INVALID, fmt("%s: workspace must be 16-byte aligned, lengths 4-byte aligned", entry));
+  if ((reinterpret_cast<uintptr_t>(src) & (alignof(S) - 1)) != 0) return fail(h, RIB_ERR_INVALID, fmt("%s: the source must be 4-byte aligned", entry));
+  JpegParamsT<S> jp;
+  jp.src = src; jp.H = H; jp.W = W; jp.quality = quality;
   jp.rows = (H + 15) / 16; jp.cols = (W + 15) / 16;
   jp.slot = (uint32_t)jpeg_seg_bound(jp.cols);
   const size_t segs = (size_t)T * jp.rows;
@@ -318,11 +322,22 @@ int rib_jpeg(rib_handle* handle, int T, int H, int W, const uint8_t* src_u8_nhwc
   jpeg_make_header(ap.header, H, W, quality);
   HIP_TRY(h, hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  hipLaunchKernelGGL(k_jpeg_segments, dim3(jp.rows, T), dim3(256), 0, st, jp);
+  hipLaunchKernelGGL((k_jpeg_segments<S>), dim3(jp.rows, T), dim3(256), 0, st, jp);
   HIP_TRY(h, hipGetLastError());
   hipLaunchKernelGGL(k_jpeg_assemble, dim3(jp.rows, T), dim3(256), 0, st, ap);
   HIP_TRY(h, hipGetLastError());
   return RIB_OK;
+}
+}  // extern "C++"
+
+int rib_jpeg(rib_handle* handle, int T, int H, int W, const uint8_t* src_u8_nhwc, int quality, uint8_t* dst, size_t dst_stride,
+             int32_t* lengths, void* workspace, void* hip_stream) {
+  return jpeg_enqueue<uint8_t>("rib_jpeg", handle, T, H, W, src_u8_nhwc, quality, dst, dst_stride, lengths, workspace, hip_stream);
+}
+
+int rib_jpeg_float(rib_handle* handle, int T, int H, int W, const float* src_f32_nchw, int quality, uint8_t* dst, size_t dst_stride,
+                 int32_t* lengths, void* workspace, void* hip_stream) {
+  return jpeg_enqueue<float>("rib_jpeg_float", handle, T, H, W, src_f32_nchw, quality, dst, dst_stride, lengths, workspace, hip_stream);
 }
 // rib_mci_*: the workspace of one (B, H, W) - the three luma levels of the 2B key frames and the block fields of levels 2, 1 and
 // 0 (before the median)

@@ -8,7 +8,10 @@
 //   k_jpeg_segments  grid (MCU rows, T), 256 threads: a workgroup owns ONE restart segment (one MCU row of one frame) and walks
 //                    it in chunks of JPEG_CHUNK MCUs (96 blocks, 256 pixels wide):
 //                      1. the chunk's 16 sheet rows come in as aligned dwords into LDS (byte loads only where a dword would
-//                         reach outside the source tensor);
+//                         reach outside the source tensor); the float instantiation (rib_jpeg_float: frames fp32 NCHW in [-1, 1])
+//                         reads four pixels of the three channel planes per thread instead - float4 where the plane's row
+//                         segment is 16-byte aligned and whole, scalar loads otherwise - quantises them (quantise_u8: the
+//                         arithmetic of k_quantise) and stores the same interleaved RGB bytes, at phase 0;
 //                      2. a thread per 2 x 2 pixels: fixed-point Y Cb Cr, chroma as the rounded mean, level shift, int16
 //                         samples block by block in LDS (edge MCUs read the last column / row again);
 //                      3. the DCT row pass, a thread per block row, in place; the column pass, a thread per block column, into
@@ -28,12 +31,15 @@
 // Staging bound: a block emits at most 64 symbols (one DC, 63 AC) of at most 16 + 11 bits (the true worst case, 20 + 63 * 26
 // bits, is smaller: a ZRL or an EOB stands for coefficients that would each cost more), i.e. 216 bytes; a segment of
 // n = 6 * cols blocks is at most 216 n bytes before stuffing and twice that when every byte is 0xFF.
-// No atomics on global memory, no floats, nothing depends on T or on the order in which workgroups run.
+// No atomics on global memory, no floats behind step 1, nothing depends on T or on the order in which workgroups run.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <initializer_list>
+#include <type_traits>
+
+#include "pixel_ops.hip.h"
 
 namespace rib {
 
@@ -109,13 +115,15 @@ inline void jpeg_make_header(JpegHeader& hd, int H, int W, int quality) {
   put({0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0});
 }
 
-struct JpegParams {
-  const uint8_t* src;       // [T, H, W, 3]
+template <typename S>
+struct JpegParamsT {
+  const S* src;             // uint8_t: [T, H, W, 3]; float: [T, 3, H, W] in [-1, 1]
   uint8_t* seg;             // [T, rows] slots of `slot` bytes
   int32_t* seglen;          // [T, rows]: bytes of the segment, -1: the slot would have been exceeded
   int H, W, quality, rows, cols;
   uint32_t slot;
 };
+using JpegParams = JpegParamsT<uint8_t>;
 
 // one pass of the 8-point DCT in 13 fractional bits: o[u] = (sum_x K[u][x] s[x] + rnd) >> sh (panel._JPEG_DCT)
 __device__ inline void jpeg_dct8(const int s[8], int o[8], int rnd, int sh) {
@@ -163,7 +171,22 @@ struct JpegBits {
   __device__ void finish() { if (n > 0) atomicOr(&words[wi], __builtin_bswap32((uint32_t)(acc >> 32))); }
 };
 
-__global__ __launch_bounds__(256) void k_jpeg_segments(JpegParams p) {
+// four pixels of one channel plane's row as bytes 0..3 (float source): `valid` of them exist
+__device__ inline uint32_t jpeg_quantise4(const float* a, int valid) {
+  if (valid >= 4 && (reinterpret_cast<uintptr_t>(a) & 15) == 0) {
+    const float4 v = *reinterpret_cast<const float4*>(a);
+    return (uint32_t)quantise_u8(v.x) | ((uint32_t)quantise_u8(v.y) << 8) | ((uint32_t)quantise_u8(v.z) << 16) | ((uint32_t)quantise_u8(v.w) << 24);
+  }
+  uint32_t r = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (k < valid) r |= (uint32_t)quantise_u8(a[k]) << (8 * k);
+  return r;
+}
+
+template <typename S>
+__global__ __launch_bounds__(256) void k_jpeg_segments(JpegParamsT<S> p) {
+  constexpr bool kU8 = std::is_same<S, uint8_t>::value;
   __shared__ __attribute__((aligned(16))) uint32_t s_a[JPEG_A_WORDS];            // the chunk's raw rows, later its bit buffer
   __shared__ __attribute__((aligned(16))) int16_t s_coef[JPEG_BLOCKS * JPEG_BLOCK_STRIDE];
   __shared__ uint32_t s_ac[2][256];        // code << 8 | length by symbol
@@ -207,8 +230,12 @@ __global__ __launch_bounds__(256) void k_jpeg_segments(JpegParams p) {
 
   const int y0 = row * 16;
   const int nrows = min(16, H - y0);                     // sheet rows this MCU row really has
-  const uint8_t* const src_lo = p.src;
-  const uint8_t* const src_hi = p.src + (size_t)gridDim.y * H * W * 3;
+  const uint8_t* src_lo = nullptr;
+  const uint8_t* src_hi = nullptr;
+  if constexpr (kU8) {
+    src_lo = p.src;
+    src_hi = p.src + (size_t)gridDim.y * H * W * 3;
+  }
   uint8_t* const out = p.seg + ((size_t)t * p.rows + row) * p.slot;
   uint32_t outpos = 0;                                   // bytes of the segment so far (uniform)
   int carrybits = 0;                                     // bits of the unfinished byte carried into this chunk (uniform)
@@ -219,7 +246,9 @@ __global__ __launch_bounds__(256) void k_jpeg_segments(JpegParams p) {
     const int x0 = m0 * 16;
     const int npx = min(ncm * 16, W - x0);               // sheet columns this chunk really has
     // ---- 1. the chunk's rows -> LDS, at their own phase inside a dword ----
-    const uint8_t* g0 = p.src + (((size_t)t * H + y0) * W + x0) * 3;
+    const uint8_t* g0 = nullptr;                         // uint8 source: the chunk's first byte
+    if constexpr (kU8) {
+    g0 = p.src + (((size_t)t * H + y0) * W + x0) * 3;
     for (int ry = 0; ry < nrows; ++ry) {
       const uint8_t* g = g0 + (size_t)ry * W * 3;
       const int phase = (int)(reinterpret_cast<uintptr_t>(g) & 3);
@@ -238,6 +267,22 @@ __global__ __launch_bounds__(256) void k_jpeg_segments(JpegParams p) {
         s_a[(ry * JPEG_RAW_STRIDE >> 2) + j] = v;
       }
     }
+    } else {
+      // float source: a thread takes four pixels of a row from each of the three planes (12 bytes, three dwords of the row)
+      const int nq4 = (npx + 3) >> 2;                    // <= 64
+      const size_t plane = (size_t)H * W;
+      const float* f0 = p.src + (size_t)t * 3 * plane + (size_t)y0 * W + x0;
+      for (int task = tid; task < nrows * nq4; task += 256) {
+        const int ry = task / nq4, j = task - ry * nq4;
+        const float* a = f0 + (size_t)ry * W + 4 * j;
+        const int valid = npx - 4 * j;                   // >= 1: pixels of this row from 4 j on
+        const uint32_t r = jpeg_quantise4(a, valid), g = jpeg_quantise4(a + plane, valid), b = jpeg_quantise4(a + 2 * plane, valid);
+        uint32_t* d = s_a + (ry * JPEG_RAW_STRIDE >> 2) + 3 * j;      // bytes R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
+        d[0] = (r & 0xFFu) | ((g & 0xFFu) << 8) | ((b & 0xFFu) << 16) | ((r & 0xFF00u) << 16);
+        d[1] = ((g >> 8) & 0xFFu) | (b & 0xFF00u) | (r & 0xFF0000u) | ((g & 0xFF0000u) << 8);
+        d[2] = ((b >> 16) & 0xFFu) | ((r >> 16) & 0xFF00u) | ((g >> 8) & 0xFF0000u) | (b & 0xFF000000u);
+      }
+    }
     __syncthreads();
     // ---- 2. colour, chroma mean, level shift ----
     for (int q = tid; q < ncm * 8 * 8; q += 256) {       // 2 x 2 pixels each: 8 quad rows, 8 quad columns per MCU
@@ -247,8 +292,9 @@ __global__ __launch_bounds__(256) void k_jpeg_segments(JpegParams p) {
       for (int dy = 0; dy < 2; ++dy) {
         const int py = qy * 2 + dy;
         const int ry = min(py, nrows - 1);
-        const uint8_t* g = g0 + (size_t)ry * W * 3;
-        const uint8_t* lrow = s_raw + ry * JPEG_RAW_STRIDE + (int)(reinterpret_cast<uintptr_t>(g) & 3);
+        int phase = 0;                                   // the float source's bytes start the LDS row
+        if constexpr (kU8) phase = (int)(reinterpret_cast<uintptr_t>(g0 + (size_t)ry * W * 3) & 3);
+        const uint8_t* lrow = s_raw + ry * JPEG_RAW_STRIDE + phase;
 #pragma unroll
         for (int dx = 0; dx < 2; ++dx) {
           const int px = qx * 2 + dx;

@@ -52,6 +52,7 @@ from . import background as _background
 from . import io_worker, rasterise
 from . import metrics as _metrics
 from . import panel as _panel
+from . import video as _video
 
 
 def sample_rate_of(num_pose: int, num_key: int) -> int:
@@ -517,7 +518,7 @@ class Evaluator:
     def evaluate_from_folder(self, model, train_dir, dain_dir, pose_dir, save_dir, gt_dir=None, gen_vid=False,
                              rank=None, world=None, metrics=False, mask_dir=None, pose_mask=False,
                              panels=False, panel_frames=False, panel_quality=90, panel_fps=30, panel_encode="host",
-                             background="dain"):
+                             background="dain", video=False, video_fps=30, video_quality=90, video_frames=False, frames="png"):
         """rank / world: this process's share of the independent units (default: the torch.distributed process
         group when one is initialised, else everything).  Returns the frames THIS rank wrote.
         The call is one `_FolderPipeline` (below): plan a clip -> decode -> upload -> render -> sink, pipelined over units
@@ -550,7 +551,17 @@ class Evaluator:
         None and is never listed or read; a frame's file is named after its pose file (stem without a trailing "_keypoints").
         On the native path the field is made once per group of segments (rib_mci_field) and every unit's frames by one launch
         (rib_mci_frames) on the upload stream - no DAIN bytes are staged or decoded; a model behind the reference's protocol is
-        fed mci_frames_host, normalised as the native upload normalises (background.normalised_upload): the same files.  The DAIN_* metrics and the sheets' DAIN pane then show the MCI frames."""
+        fed mci_frames_host, normalised as the native upload normalises (background.normalised_upload): the same files.  The DAIN_* metrics and the sheets' DAIN pane then show the MCI frames.
+        video=True: every frame i of a clip - key frames included - is also written as a JPEG file, <save_dir>/<clip>_video/%04d.jpg
+        (quality video_quality), by whichever rank rendered it, and rank 0 then muxes <save_dir>/<clip>_video.avi (Motion-JPEG,
+        video_fps frames/s; video.assemble) and removes the .jpg files unless video_frames keeps them.  (<clip>.avi stays the
+        sheets' video; both may be asked for.  Ranks without a process group: the caller runs video.assemble.)  A frame's file is
+        panel.jpeg_encode_host of exactly the uint8 array its PNG holds (video.py).  On the native path a unit's fused frames are
+        encoded from their float tensors by one rib_jpeg_float on the lane's stream (a first chunk's key frames by another), the
+        lengths ride home in the unit's one copy and the finisher fetches exactly the files' bytes and writes them: no worker,
+        no PIL.  A model behind the reference's protocol encodes with jpeg_encode_host on the host: the same files.
+        frames="none" (only with video=True; default "png"): no frame PNG is encoded, staged or written and the frames' raw bytes
+        stay on the device; the call returns the names of the .jpg files this rank wrote.  video=False changes nothing."""
         if background not in ("dain", "mci"):
             raise ValueError("evaluate_from_folder: background must be 'dain' or 'mci', got %r" % (background,))
         if background == "mci" and self.resize_on == "gpu":
@@ -560,13 +571,15 @@ class Evaluator:
             # the reference also writes <save_dir>/<clip>.mp4 (evaluator.py:267-269, utils.make_video) from a matplotlib canvas
             # through an H.264 encoder; neither is built, and silently ignoring the flag would drop an output the caller asked for
             raise NotImplementedError("evaluate_from_folder: gen_vid (the matplotlib / mp4 video) is not supported; panels=True "
-                                      "writes the six-pane sheets as <save_dir>/<clip>.avi")
+                                      "writes the six-pane sheets as <save_dir>/<clip>.avi, video=True the frames themselves as "
+                                      "<save_dir>/<clip>_video.avi")
         if panel_encode not in ("host", "gpu"):
             raise ValueError("evaluate_from_folder: panel_encode must be 'host' or 'gpu', got %r" % (panel_encode,))
         if not panels and (panel_frames or panel_quality != 90 or panel_fps != 30 or panel_encode != "host"):
             raise ValueError("evaluate_from_folder: panel_frames, panel_quality, panel_fps and panel_encode are settings of panels=True")
         if panels and not (1 <= int(panel_quality) <= 100 and float(panel_fps) > 0):
             raise ValueError("evaluate_from_folder: panel_quality must be in 1..100 and panel_fps positive")
+        _video.check_settings(video, video_fps, video_quality, video_frames, frames)
         if metrics and gt_dir is None:
             raise ValueError("evaluate_from_folder: metrics=True needs gt_dir (the ground-truth frames)")
         if mask_dir is not None and not metrics:
@@ -585,7 +598,8 @@ class Evaluator:
         self.metrics = self.metrics_report = None
         pipe = _FolderPipeline(self, model, rank, world, gt_dir, metrics=bool(metrics), mask_dir=mask_dir, pose_mask=bool(pose_mask),
                                panels=bool(panels), panel_frames=bool(panel_frames), panel_quality=int(panel_quality),
-                               panel_encode=panel_encode, background=background)
+                               panel_encode=panel_encode, background=background, video=bool(video), video_quality=int(video_quality),
+                               video_frames=bool(video_frames), write_png=frames == "png")
         self.background = background
         self.timings = pipe.tm
         if metrics and pipe.native:
@@ -605,6 +619,8 @@ class Evaluator:
                 self.metrics, self.metrics_report = pipe.report(save_dir)
             if panels:
                 pipe.assemble_panels(save_dir, panel_fps)
+            if video:
+                pipe.assemble_video(save_dir, video_fps)
             return written
         finally:
             del pipe                 # the units' tensor views of the shared blocks die with it ...
@@ -651,11 +667,18 @@ class _Clip:
         # chunk and kept for its later chunks beside prev_of; both are released at the end of run_native / run_reference
         self.key_u8, self.mci_of = {}, {}
         self.stage_mk = {}                  # background="mci": first-chunk unit -> uint8 [2,B,H,W,3] section of its staging block
+        # video: the folder of the frames' .jpg files; out_names: what drain() reports for every frame index - the PNG, or under
+        # frames="none" the .jpg
+        self.video_dir = None
+        self.out_names = names
 
     def sheet_names(self, i, png):
         """(jpg, png or None) of frame i's sheet."""
         base = os.path.join(self.panel_dir, "%04d" % i)
         return base + ".jpg", (base + ".png" if png else None)
+
+    def video_name(self, i):
+        return os.path.join(self.video_dir, "%04d.jpg" % i)
 
     def ref_image(self, i):
         """evaluator.py:209-212: the "gt" image of frame i is gtlist[i] when a gt_dir is given, else the key frame of its
@@ -682,8 +705,11 @@ class _FolderPipeline:
     (tests/test_driver.py)."""
 
     def __init__(self, ev, model, rank, world, gt_dir, metrics=False, mask_dir=None, pose_mask=False,
-                 panels=False, panel_frames=False, panel_quality=90, panel_encode="host", background="dain"):
+                 panels=False, panel_frames=False, panel_quality=90, panel_encode="host", background="dain",
+                 video=False, video_quality=90, video_frames=False, write_png=True):
         self.mci = background == "mci"
+        # video: the frames' JPEG files (video.py); write_png False (frames="none"): they are the only files of a frame
+        self.video, self.video_quality, self.video_frames, self.write_png = video, video_quality, video_frames, write_png
         self.ev, self.model, self.rank, self.world, self.gt_dir = ev, model, rank, world, gt_dir
         self.metrics, self.mask_dir, self.pose_mask = metrics, mask_dir, pose_mask
         self.panels, self.panel_frames, self.panel_quality = panels, panel_frames, panel_quality
@@ -701,6 +727,8 @@ class _FolderPipeline:
         self.jpeg_gpu = panels and panel_encode == "gpu"     # the sheets' JPEG files are jpeg_encode_host's bytes (rib_jpeg on the native path)
         if self.native and self.jpeg_gpu and not hasattr(model, "jpeg_into"):
             raise RuntimeError("panel_encode='gpu': this model has no GPU JPEG kernels (rib_jpeg)")
+        if self.native and video and not hasattr(model, "jpeg_f32_into"):
+            raise RuntimeError("video=True: this model has no GPU JPEG kernels for float frames (rib_jpeg_float)")
         self.gpu_labels = self.native and ev.label_fn is None and hasattr(model, "rasterise")
         per_slot = (1.0 + (1.0 if (metrics or (panels and gt_dir is not None)) else 0.0) + (1.0 / 3 if mask_dir is not None else 0.0))
         if panels:                           # a unit's download block also carries its sheets (six panes and the borders per frame)
@@ -742,15 +770,29 @@ class _FolderPipeline:
             return self.procs.submit(io_worker.save_png, q, name, self.level).result(timeout=IO_TIMEOUT_S)
         return io_worker.save_png(q, name, self.level)
 
-    def save_host(self, x, name):            # utils/utils.py:129-142 on the host
+    @staticmethod
+    def host_u8(x):                          # utils/utils.py:129-142 on the host: the uint8 HWC array of a frame's PNG
         a = np.transpose(x[0].cpu().float().numpy(), (1, 2, 0)) * np.array([0.5] * 3) + np.array([0.5] * 3)
-        return self.save_q((np.clip(a, 0, 1) * 255.0).astype(np.uint8), name)
+        return (np.clip(a, 0, 1) * 255.0).astype(np.uint8)
+
+    def save_host(self, x, name):
+        return self.save_q(self.host_u8(x), name)
+
+    def save_frame_host(self, clip, i, x):
+        """Frame i's files from its float tensor x [1,3,H,W] on the host (key frames; every frame of the reference path): the
+        PNG unless frames="none", and under video=True - on the reference path: the native path encodes every frame on the
+        GPU - the .jpg of the same uint8 array."""
+        u8 = self.host_u8(x)
+        if self.video and not self.native:
+            _video.save_frame_host(u8, clip.video_name(i), self.video_quality)
+        return self.save_q(u8, clip.names[i]) if self.write_png else clip.video_name(i)
 
     # ---- stage 0: plan ---------------------------------------------------------------------------------------------------
     def plan_clip(self, sub, train_dir, dain_dir, pose_dir, save_dir):
         ev = self.ev
         frames_dir = os.path.join(save_dir, sub)
-        os.makedirs(frames_dir, exist_ok=True)
+        if self.write_png:
+            os.makedirs(frames_dir, exist_ok=True)
         image_list = _list(os.path.join(train_dir, sub), ("jpg", "png"))
         dain_list = None if self.mci else _list(os.path.join(dain_dir, sub), ("jpg", "png"))
         pose_list = _list(os.path.join(pose_dir, sub), ("json",))
@@ -798,6 +840,11 @@ class _FolderPipeline:
                     units.append((gi, members, c0, min(T, c0 + step)))
         clip = _Clip(names, dain_list, image_list, pose_list, gtlist, sample_rate, my_keys, segs, units, sub=sub,
                      measure=self.metrics, mask_list=mask_list)
+        if self.video:
+            clip.video_dir = _video.video_dir(save_dir, sub)
+            os.makedirs(clip.video_dir, exist_ok=True)
+            if not self.write_png:
+                clip.out_names = [clip.video_name(i) for i in range(seq_len)]
         if self.panels:
             if gtlist is not None and len(gtlist) < seq_len:
                 raise ValueError("panels: %s has %d ground-truth frames, the clip has %d" % (os.path.join(self.gt_dir, sub), len(gtlist), seq_len))
@@ -895,9 +942,10 @@ class _FolderPipeline:
         if i in clip.loads:
             return
         clip.loads[i] = self.decode_in_worker(clip, i) if self.procs is not None else self.pool.submit(self.decode_here, clip, i)
-        if i in clip.keys and i not in clip.futs:          # key frames pass through (evaluator.py:240-244)
+        # key frames pass through (evaluator.py:240-244); native path under frames="none": their only file comes from the GPU
+        if i in clip.keys and i not in clip.futs and (self.write_png or not self.native):
             clip.futs[i] = self.finishers.submit(
-                lambda: self.save_host(clip.loads[i].result(timeout=IO_TIMEOUT_S)[1].unsqueeze(0), clip.names[i]))
+                lambda: self.save_frame_host(clip, i, clip.loads[i].result(timeout=IO_TIMEOUT_S)[1].unsqueeze(0)))
 
     def open_units(self, clip, upto):
         """Staging block, slots and decode tasks of the units up to index `upto`: the launch thread keeps DECODE_AHEAD units open
@@ -1063,6 +1111,8 @@ class _FolderPipeline:
                 return self._render_panels(clip, ui, g, st, imgs, masks, fz, lab, dn, gtd)
             if clip.measure:
                 return self._render_measured(clip, ui, g, st, fz, lab, dn, gtd)
+            if self.video:
+                return self._render_video(clip, ui, g, st, fz, lab, dn, gtd)
             q = g.quantise(fz.reshape(-1, *fz.shape[2:]))                  # [Tc*B,H,W,3] uint8
             out_blk = _shm_get(q.numel()) if self.procs is not None else None       # shared with the encode workers, page-locked
             pinned = out_blk.t[:q.numel()].view(q.shape) if out_blk is not None else torch.empty(q.shape, dtype=torch.uint8, pin_memory=True)
@@ -1079,23 +1129,73 @@ class _FolderPipeline:
         t0 = time.perf_counter()
         n = fz.shape[0] * fz.shape[1]
         frames = fz.reshape(n, *fz.shape[2:])
-        nq = frames.numel()                                              # uint8 bytes of the quantised frames
+        nq = frames.numel() if self.write_png else 0                     # uint8 bytes of the quantised frames (frames="none": none)
         off = (nq + 255) // 256 * 256
-        total = off + 4 * n * 4
+        off_w = off + 4 * n * 4                                          # video: the int32 lengths of the frames' (and keys') files
+        nv = self.video_count(clip, ui)
+        total = off_w + 4 * nv
         buf = torch.empty(total, dtype=torch.uint8, device=g.device)
-        q = g.quantise(frames, out=buf[:nq].view(n, frames.shape[2], frames.shape[3], frames.shape[1]))
-        vals = buf[off:].view(torch.float32).view(4, n)
+        q = g.quantise(frames, out=buf[:nq].view(n, frames.shape[2], frames.shape[3], frames.shape[1])) if self.write_png else None
+        vals = buf[off:off_w].view(torch.float32).view(4, n)
         gtf, mk = clip.meas.pop(ui)
         g.quality(frames, gtf, mk, out=vals[0:2])
         g.quality(dn.reshape(n, *dn.shape[2:]), gtf, mk, out=vals[2:4])
+        vid = self.encode_video(clip, ui, g, frames, gtd, buf[off_w:].view(torch.int32)) if self.video else None
         out_blk = _shm_get(total) if self.procs is not None else None
         flat = out_blk.t[:total] if out_blk is not None else torch.empty(total, dtype=torch.uint8, pin_memory=True)
         flat.copy_(buf, non_blocking=True)
         done = torch.cuda.Event()
         done.record(st)
         self.tm["metrics"] += time.perf_counter() - t0
-        return {"done": done, "pinned": flat[:nq].view(q.shape), "out_blk": out_blk, "keep": (fz, q, lab, dn, gtd, buf, gtf, mk),
-                "qual": flat[off:].view(torch.float32).view(4, n)}
+        return {"done": done, "pinned": flat[:nq].view(q.shape) if q is not None else None, "out_blk": out_blk,
+                "keep": (fz, q, lab, dn, gtd, buf, gtf, mk, vid), "qual": flat[off:off_w].view(torch.float32).view(4, n),
+                "video": vid + (flat[off_w:total].view(torch.int32),) if vid else None}
+
+    def video_count(self, clip, ui):
+        """video: the files a unit encodes - its frames and, in a first chunk, the key frames it starts from (else 0)."""
+        if not self.video:
+            return 0
+        _, members, c0, c1 = clip.units[ui]
+        return (c1 - c0) * len(members) + (len(members) if c0 == 0 else 0)
+
+    def video_frames_of(self, clip, ui):
+        """The frame indices of a unit's video files, in the order encode_video writes them."""
+        _, members, c0, _ = clip.units[ui]
+        return clip.unit_frames(ui) + ([clip.segs[si][0] for si in members] if c0 == 0 else [])
+
+    def encode_video(self, clip, ui, g, frames, gtd, lengths):
+        """video=True, on the lane's stream: rib_jpeg_float of the unit's fused frames float [n,3,H,W] and - in a first chunk - of
+        the key frames gtd [B,3,H,W] it starts from, one call each -> (files, cap): file j at files[j * cap:], its size in
+        lengths[j] (int32 on the device, a view of the unit's download buffer).  cap is the proven bound (rib_jpeg_max_bytes)."""
+        n, _, H, W = frames.shape
+        nk = lengths.numel() - n
+        cap = g.jpeg_max_bytes(H, W)
+        files = torch.empty((n + nk) * cap, dtype=torch.uint8, device=g.device)
+        g.jpeg_f32_into(frames.to(torch.float32).contiguous(), files[:n * cap], lengths[:n], self.video_quality, cap)
+        if nk:
+            g.jpeg_f32_into(gtd.to(torch.float32).contiguous(), files[n * cap:], lengths[n:], self.video_quality, cap)
+        return files, cap
+
+    def _render_video(self, clip, ui, g, st, fz, lab, dn, gtd):
+        """render() of a plain unit under video=True (on the lane's stream, inside its stream context): one device buffer,
+        [uint8 frames (not under frames="none") | int32 file lengths [Tc*B + keys]], filled by the quantiser and rib_jpeg_float
+        and brought home in the unit's one copy; the files stay on the device until the sink knows their lengths."""
+        n = fz.shape[0] * fz.shape[1]
+        H, W = fz.shape[3], fz.shape[4]
+        frames = fz.reshape(n, 3, H, W)
+        nq = frames.numel() if self.write_png else 0
+        off_w = (nq + 255) // 256 * 256
+        total = off_w + 4 * self.video_count(clip, ui)
+        buf = torch.empty(total, dtype=torch.uint8, device=g.device)
+        q = g.quantise(frames, out=buf[:nq].view(n, H, W, 3)) if self.write_png else None
+        vid = self.encode_video(clip, ui, g, frames, gtd, buf[off_w:].view(torch.int32))
+        out_blk = _shm_get(total) if self.procs is not None else None
+        flat = out_blk.t[:total] if out_blk is not None else torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        flat.copy_(buf, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(st)
+        return {"done": done, "pinned": flat[:nq].view(n, H, W, 3) if q is not None else None, "out_blk": out_blk,
+                "keep": (fz, q, lab, dn, gtd, buf, vid), "video": vid + (flat[off_w:total].view(torch.int32),)}
 
     def _render_panels(self, clip, ui, g, st, imgs, masks, fz, lab, dn, gtd):
         """render() of a unit under panels=True (on the lane's stream, inside its stream context): one device buffer,
@@ -1109,17 +1209,19 @@ class _FolderPipeline:
         n = fz.shape[0] * fz.shape[1]
         H, W = fz.shape[3], fz.shape[4]
         frames = fz.reshape(n, 3, H, W)
-        nq = frames.numel()
+        nq = frames.numel() if self.write_png else 0
         SH, SW = self.sheet_hw
         gtp, klab, kdn, keys, dnp = clip.pan.pop(ui)
         nk = kdn.shape[0] if kdn is not None else 0
         off_v = (nq + 255) // 256 * 256
         off_l = (off_v + (4 * n * 4 if clip.measure else 0) + 255) // 256 * 256
-        off_s = off_l + ((4 * (n + nk) + 255) // 256 * 256 if self.jpeg_gpu else 0)
+        off_w = off_l + ((4 * (n + nk) + 255) // 256 * 256 if self.jpeg_gpu else 0)      # video: the lengths of the frames' files
+        nv = self.video_count(clip, ui)
+        off_s = off_w + (4 * nv + 255) // 256 * 256
         home = not self.jpeg_gpu or self.panel_frames        # the raw sheets travel home
         total = off_s + ((n + nk) * SH * SW * 3 if home else 0)
         buf = torch.empty(total, dtype=torch.uint8, device=g.device)
-        q = g.quantise(frames, out=buf[:nq].view(n, H, W, 3))
+        q = g.quantise(frames, out=buf[:nq].view(n, H, W, 3)) if self.write_png else None
         keep = [fz, imgs, masks, q, lab, dn, gtd, buf, gtp, klab, kdn, keys, dnp]
         if clip.measure:
             vals = buf[off_v:off_v + 16 * n].view(torch.float32).view(4, n)
@@ -1136,6 +1238,10 @@ class _FolderPipeline:
         if self.jpeg_gpu:
             jpeg = self.encode_jpeg(g, sheets, buf[off_l:off_l + 4 * (n + nk)].view(torch.int32))
             keep += [sheets, jpeg]
+        vid = None
+        if self.video:
+            vid = self.encode_video(clip, ui, g, frames, gtd, buf[off_w:off_w + 4 * nv].view(torch.int32))
+            keep += [vid]
         out_blk = _shm_get(total) if self.procs is not None else None
         flat = out_blk.t[:total] if out_blk is not None else torch.empty(total, dtype=torch.uint8, pin_memory=True)
         flat.copy_(buf, non_blocking=True)
@@ -1143,7 +1249,8 @@ class _FolderPipeline:
         done.record(st)
         self.tm["panels"] = self.tm.get("panels", 0.0) + time.perf_counter() - t0
         _, members, c0, _ = clip.units[ui]
-        return {"done": done, "pinned": flat[:nq].view(q.shape), "out_blk": out_blk, "keep": tuple(keep),
+        return {"done": done, "pinned": flat[:nq].view(q.shape) if q is not None else None, "out_blk": out_blk, "keep": tuple(keep),
+                "video": vid + (flat[off_w:off_w + 4 * nv].view(torch.int32),) if vid else None,
                 "qual": flat[off_v:off_v + 16 * n].view(torch.float32).view(4, n) if clip.measure else None,
                 "sheets": flat[off_s:].view(n + nk, SH, SW, 3) if home else None, "sheet_off": off_s,
                 "jpeg": jpeg + (flat[off_l:off_l + 4 * (n + nk)].view(torch.int32),) if jpeg else None,
@@ -1172,16 +1279,19 @@ class _FolderPipeline:
         g.jpeg_into(sheets, files, lengths, self.panel_quality, cap)
         return files, cap
 
-    def fetch_jpeg(self, clip, frames, jpeg):
+    def fetch_jpeg(self, clip, frames, jpeg, video=False):
         """panel_encode="gpu", on a finisher thread once the unit's copy is home: jpeg = (files, cap, lengths on the host) -
-        exactly the files' bytes come home and are written as the sheets' %04d.jpg, by this thread: no worker, no PIL."""
+        exactly the files' bytes come home and are written as the sheets' %04d.jpg, by this thread: no worker, no PIL.
+        video: the files are the frames' own (encode_video) and go to the clip's video folder."""
         files, cap, lengths = jpeg
         sizes = [int(v) for v in lengths.tolist()]
         if not all(0 < v <= cap for v in sizes):
-            raise RuntimeError("panel_encode='gpu': rib_jpeg refused a sheet (lengths %s, cap %d)" % (sizes, cap))
+            raise RuntimeError("%s refused a %s (lengths %s, cap %d)" % ("video=True: rib_jpeg_float" if video else "panel_encode='gpu': rib_jpeg",
+                                                                          "frame" if video else "sheet", sizes, cap))
         with torch.cuda.stream(self.copy_stream(files.device)):
             host = [files[j * cap:j * cap + sizes[j]].cpu() for j in range(len(frames))]     # each returns when its bytes are home
-        return [_panel.save_jpeg(host[j].numpy().tobytes(), clip.sheet_names(i, False)[0]) for j, i in enumerate(frames)]
+        return [_panel.save_jpeg(host[j].numpy().tobytes(), clip.video_name(i) if video else clip.sheet_names(i, False)[0])
+                for j, i in enumerate(frames)]
 
     def copy_stream(self, device):
         """The stream of the finishers' exact-size file copies (one per device): the lane's work they read is complete."""
@@ -1237,6 +1347,35 @@ class _FolderPipeline:
             return res
         clip.sheet_futs.append(self.finishers.submit(finish))
 
+    def loose_key_video(self, clip, g, st):
+        """video: the files of this rank's key frames that start no unit of its own (a clip's last key frame; every key frame of
+        a rank that renders nothing) - the rule of loose_key_sheets: a small unit of their own, one rib_jpeg_float, the lengths
+        home first, then exactly the files' bytes."""
+        started = {k for k, _ in clip.segs}
+        loose = [k for k in clip.keys if k not in started]
+        if not loose:
+            return
+        keys = torch.stack([clip.loads[k].result(timeout=IO_TIMEOUT_S)[1] for k in loose])
+        with torch.cuda.stream(st):
+            keys = keys.to(g.device, torch.float32).contiguous()
+            cap = g.jpeg_max_bytes(*keys.shape[2:])
+            files = torch.empty(len(loose) * cap, dtype=torch.uint8, device=g.device)
+            lengths = torch.empty(len(loose), dtype=torch.int32, device=g.device)
+            home = torch.empty(len(loose), dtype=torch.int32, pin_memory=True)
+            g.jpeg_f32_into(keys, files, lengths, self.video_quality, cap)
+            home.copy_(lengths, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(st)
+
+        def finish(keep=(keys, lengths)):
+            done.synchronize()
+            return self.fetch_jpeg(clip, loose, (files, cap, home), video=True)
+        fut = self.finishers.submit(finish)
+        clip.sheet_futs.append(fut)
+        if not self.write_png:
+            for j, k in enumerate(loose):
+                clip.futs[k] = (fut, j)
+
     # ---- stage 4: sink ---------------------------------------------------------------------------------------------------
     def sink(self, clip, ui, r, t_loaded, t_enq):
         """Runs on a finisher thread: waits for the unit's copy, hands the staging block back, fans the PNG encodes out and
@@ -1262,28 +1401,36 @@ class _FolderPipeline:
         sheet_fs = self.save_sheets(clip, r["sheet_frames"], r["sheets"], out_blk, r["sheet_off"]) if r.get("sheets") is not None else []
         jpeg = r.pop("jpeg", None)              # panel_encode="gpu": the files' bytes come home now that their lengths have,
                                                 # while the workers encode the PNGs
+        vid = r.pop("video", None)              # video: likewise the frames' own files
+        vres = None
         if out_blk is not None:
             fsz = ev.height * ev.width * 3
             fs = [self.procs.submit(io_worker.save_png_shm, out_blk.name, j * fsz, ev.height, ev.width, clip.names[out_frames[j]], self.level)
-                  for j in range(len(out_frames))]
+                  for j in range(len(out_frames))] if self.write_png else []
             if jpeg is not None:
                 self.fetch_jpeg(clip, r["sheet_frames"], jpeg)
+            if vid is not None:
+                vres = self.fetch_jpeg(clip, self.video_frames_of(clip, ui), vid, video=True)
             res = [f.result(timeout=IO_TIMEOUT_S) for f in fs]
             for f in sheet_fs:
                 f.result(timeout=IO_TIMEOUT_S)
             r["pinned"] = r["sheets"] = None
             _shm_put(out_blk)
         else:
-            qn = r["pinned"].numpy()
-            saves = self.pool.map(lambda j: self.save_q(qn[j], clip.names[out_frames[j]]), range(len(out_frames)))
+            saves = []
+            if self.write_png:
+                qn = r["pinned"].numpy()
+                saves = self.pool.map(lambda j: self.save_q(qn[j], clip.names[out_frames[j]]), range(len(out_frames)))
             if jpeg is not None:
                 self.fetch_jpeg(clip, r["sheet_frames"], jpeg)
+            if vid is not None:
+                vres = self.fetch_jpeg(clip, self.video_frames_of(clip, ui), vid, video=True)
             res = list(saves)
             for f in sheet_fs:
                 f.result(timeout=IO_TIMEOUT_S)
         r["keep"] = None
         mark.append(round(time.perf_counter() - self.t_wall, 4))
-        return res
+        return res if self.write_png else vres      # frames="none": the .jpg names, the unit's frames and then its key frames
 
     # ---- drivers ---------------------------------------------------------------------------------------------------------
     def run_native(self, clip):
@@ -1308,12 +1455,14 @@ class _FolderPipeline:
             seg_fut = self.finishers.submit(self.sink, clip, ui, r, t1 - self.t_wall, t3 - self.t_wall)
             self.inflight.append(seg_fut)
             tm["peak_units_in_flight"] = max(tm["peak_units_in_flight"], len(self.inflight))
-            for j, i in enumerate(clip.unit_frames(ui)):
+            for j, i in enumerate(clip.unit_frames(ui) if self.write_png else self.video_frames_of(clip, ui)):
                 clip.futs[i] = (seg_fut, j)
         for k in clip.keys:
             self.submit_load(clip, k)
         if self.panels:
             self.loose_key_sheets(clip, *(lanes[0] if lanes else (self.model, torch.cuda.current_stream(self.model.device))))
+        if self.video:
+            self.loose_key_video(clip, *(lanes[0] if lanes else (self.model, torch.cuda.current_stream(self.model.device))))
         tm["units"] = tm.get("units", 0) + len(clip.units)
         tm["frames"] += len(clip.futs)
         # background="mci": the groups' key frames and fields are only read by launches already enqueued on the upload stream,
@@ -1362,7 +1511,7 @@ class _FolderPipeline:
             tm["rasterise"] += t2 - t1
             tm["generate"] += time.perf_counter() - t2
             for t, i in enumerate(frames):
-                clip.futs[i] = self.pool.submit(self.save_host, outs[t], clip.names[i])
+                clip.futs[i] = self.pool.submit(self.save_frame_host, clip, i, outs[t])
             if self.panels:                      # the host statement of the sheet (panel.compose_host), a segment at a time
                 def host(xs):
                     return torch.cat([x.detach().cpu().float() for x in xs]).numpy()
@@ -1456,12 +1605,26 @@ class _FolderPipeline:
                 _panel.assemble(save_dir, clip.sub, fps, keep_frames=self.panel_frames)
         self.tm["panels"] = self.tm.get("panels", 0.0) + time.perf_counter() - t0
 
+    def assemble_video(self, save_dir, fps):
+        """After drain(): every rank's frame files are in <save_dir>/<clip>_video/ - rank 0 (after a barrier, under a process
+        group) makes <save_dir>/<clip>_video.avi of each clip's folder (video.assemble).  Ranks dealt by hand cannot know when
+        the others are done: the caller assembles."""
+        t0 = time.perf_counter()
+        import torch.distributed as dist
+        grouped = self.world > 1 and dist.is_available() and dist.is_initialized()
+        if grouped:
+            dist.barrier()
+        if self.world == 1 or (grouped and self.rank == 0):
+            for clip in self.clips:
+                _video.assemble(save_dir, clip.sub, fps, keep_frames=self.video_frames)
+        self.tm["video"] = self.tm.get("video", 0.0) + time.perf_counter() - t0
+
     def drain(self):
         """Waits for every file of the call, in frame order as the reference writes them; returns the names this rank wrote."""
         written: List[str] = []
         t5 = time.perf_counter()
         for clip in self.clips:
-            for i, name in enumerate(clip.names):
+            for i, name in enumerate(clip.out_names):
                 if i not in clip.futs:
                     continue                                                       # another rank's frame
                 f = clip.futs[i]

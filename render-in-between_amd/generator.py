@@ -684,6 +684,53 @@ class Generator:
             raise RuntimeError("jpeg: a frame exceeded rib_jpeg_max_bytes (%d bytes): the staging bound is wrong" % cap)
         return [dst[t * cap:t * cap + n[t]].cpu().numpy().tobytes() for t in range(T)]
 
+    def jpeg_f32_into(self, frames, dst, lengths, quality=90, cap=None):
+        """jpeg_into() for the frames the chain produces (rib_jpeg_float): float32 [T,3,H,W] in [-1, 1], contiguous, on this device
+        - the files of jpeg_into(quantise(frames), ...) without the uint8 copy in between.  dst, lengths, cap, the refusal of a
+        frame that does not fit and the return value are jpeg_into's."""
+        if not torch.is_tensor(frames) or frames.dim() != 4 or frames.shape[1] != 3 or frames.dtype != torch.float32 \
+                or frames.device != self.device or not frames.is_contiguous():
+            raise ValueError("jpeg_f32: frames must be a contiguous float32 [T,3,H,W] tensor on %s" % (self.device,))
+        T, _, H, W = frames.shape
+        if isinstance(quality, bool) or int(quality) != quality or not 1 <= int(quality) <= 100:
+            raise ValueError("jpeg_f32: quality must be an integer in 1..100, got %r" % (quality,))
+        self.jpeg_max_bytes(H, W)
+        if T < 1 or T > 65535:
+            raise ValueError("jpeg_f32: 1 <= T <= 65535 frames, got %d" % T)
+        if dst.dim() != 1 or dst.dtype != torch.uint8 or dst.device != self.device or not dst.is_contiguous():
+            raise ValueError("jpeg_f32: dst must be a contiguous 1-D uint8 tensor on %s" % (self.device,))
+        if tuple(lengths.shape) != (T,) or lengths.dtype != torch.int32 or lengths.device != self.device or not lengths.is_contiguous():
+            raise ValueError("jpeg_f32: lengths must be a contiguous int32 [%d] tensor on %s" % (T, self.device))
+        cap = dst.numel() // T if cap is None else int(cap)
+        from . import panel as P
+        if cap < P.JPEG_HEADER_BYTES + 2 or cap >= 2 ** 31 or T * cap > dst.numel():
+            raise ValueError("jpeg_f32: cap=%d: at least the %d-byte header and EOI, below 2 GiB, and T * cap within dst (%d bytes)"
+                             % (cap, P.JPEG_HEADER_BYTES, dst.numel()))
+        n = int(self._lib.rib_jpeg_workspace_bytes(self._h, T, H, W))
+        cache = self.__dict__.setdefault("_jpeg_ws", {})         # shared with jpeg_into: the workspace of a shape is the same
+        ws = cache.get((T, H, W))
+        if ws is None:
+            ws = cache[(T, H, W)] = torch.empty(n, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _native.check(self._h, self._lib.rib_jpeg_float(self._h, T, H, W, _ptr(frames), int(quality), _ptr(dst), cap, _ptr(lengths),
+                                                          _ptr(ws), self._stream()))
+        return cap
+
+    def jpeg_f32(self, frames, quality=90):
+        """Baseline JPEG files of T float frames on the GPU (rib_jpeg_float): float32 [T,3,H,W] in [-1, 1] on this device -> list of
+        T bytes objects, panel.jpeg_encode_host(panel.quantise_host(frames)) byte for byte (= jpeg(quantise(frames)))."""
+        if not torch.is_tensor(frames) or frames.dim() != 4:
+            raise ValueError("jpeg_f32: frames must be a float32 [T,3,H,W] tensor")
+        T, _, H, W = frames.shape
+        cap = self.jpeg_max_bytes(H, W)
+        dst = torch.empty(T * cap, dtype=torch.uint8, device=self.device)
+        lengths = torch.empty(T, dtype=torch.int32, device=self.device)
+        self.jpeg_f32_into(frames, dst, lengths, quality, cap)
+        n = lengths.cpu().tolist()
+        if not all(v > 0 for v in n):
+            raise RuntimeError("jpeg_f32: a frame exceeded rib_jpeg_max_bytes (%d bytes): the staging bound is wrong" % cap)
+        return [dst[t * cap:t * cap + n[t]].cpu().numpy().tobytes() for t in range(T)]
+
     # ---- introspection / measurement -----------------------------------------------------------
     def enable_taps(self, on=True):
         """Debug: keep every tapped intermediate intact until the end of a forward (buffers with disjoint lifetimes

@@ -25,6 +25,13 @@ titles are this project's, not matplotlib's); `--panel-frames` keeps the lossles
 segment per MCU row, bit-equal to panel.jpeg_encode_host; the stream is ours, restated from ITU-T T.81, unpinned) instead of
 with PIL in the file workers (`host`, the default): the files' bytes come home instead of the raw sheets.
 
+The frames as a video (new; the reference leaves that to an external encoder): `--video [--video-fps N] [--video-quality Q]
+[--video-frames]` also writes every frame of a clip, key frames included, into <save-dir>/Generated_frames/<clip>_video.avi
+(Motion-JPEG in a plain RIFF AVI; a frame is panel.jpeg_encode_host of exactly the bytes its PNG holds, encoded on the GPU from
+the float frames by rib_jpeg_float; `--video-frames` keeps the .jpg files in <clip>_video/).  `--frames none` (with --video) writes
+only the video: no PNG is encoded and the raw frames stay on the device.  Container and stream are this project's, unpinned: PIL
+is the only decoder that has read them.
+
 Backgrounds without a DAIN folder: `--background mci` makes every background frame on the GPU from the segment's two key
 frames - a classical motion-compensated interpolation (background.py states it in integers; rib_mci_field / rib_mci_frames) -
 and never reads <input>/DAIN.  It is this project's interpolation, not DAIN: the generator was trained on DAIN backgrounds, the
@@ -131,7 +138,10 @@ def main(opts):
                                              panels=opts.panels, panel_frames=opts.panel_frames,
                                              panel_quality=90 if opts.panel_quality is None else opts.panel_quality,
                                              panel_fps=30 if opts.panel_fps is None else opts.panel_fps,
-                                             panel_encode=opts.panel_encode or "host", background=opts.background)
+                                             panel_encode=opts.panel_encode or "host", background=opts.background,
+                                             video=opts.video, video_fps=30 if opts.video_fps is None else opts.video_fps,
+                                             video_quality=90 if opts.video_quality is None else opts.video_quality,
+                                             video_frames=opts.video_frames, frames=opts.frames)
     print(summary_line(evaluator, rank, world))
     if world > 1:
         print("[rank {}/{}] wrote {} frames".format(rank, world, len(written)))
@@ -193,6 +203,15 @@ def build_parser():
                              "frame, as the reference; 'mci': interpolated on the GPU from each segment's two key frames (motion-compensated, "
                              "this project's, not DAIN; the generator was trained on DAIN backgrounds and the quality on real footage has "
                              "not been measured) - no DAIN folder is read, frames are named after their pose files")
+    parser.add_argument("--video", action="store_true",
+                        help="also write every frame of a clip, key frames included, as <save-dir>/Generated_frames/<clip>_video.avi "
+                             "(Motion-JPEG; a frame is the JPEG of exactly the bytes its PNG holds, encoded on the GPU)")
+    parser.add_argument("--video-fps", type=float, default=None, help="with --video: frames per second of the video (default 30)")
+    parser.add_argument("--video-quality", type=int, default=None, help="with --video: JPEG quality of the video's frames, 1-100 (default 90)")
+    parser.add_argument("--video-frames", action="store_true", help="with --video: keep the frames' JPEG files as <clip>_video/%%04d.jpg")
+    parser.add_argument("--frames", choices=("png", "none"), default="png",
+                        help="'png' (default): the reference's folder of PNG frames; 'none' (only with --video): the video is the only "
+                             "output - no PNG is encoded or written, the raw frames are not downloaded")
     return parser
 
 
@@ -219,6 +238,14 @@ def parse_args(argv=None):
         parser.error("--panel-quality must be in 1..100")
     if opts.panel_fps is not None and not opts.panel_fps > 0:
         parser.error("--panel-fps must be positive")
+    if opts.frames == "none" and not opts.video:
+        parser.error("--frames none writes nothing unless --video is given")
+    if not opts.video and (opts.video_frames or opts.video_quality is not None or opts.video_fps is not None):
+        parser.error("--video-fps, --video-quality and --video-frames are settings of --video")
+    if opts.video_quality is not None and not 1 <= opts.video_quality <= 100:
+        parser.error("--video-quality must be in 1..100")
+    if opts.video_fps is not None and not opts.video_fps > 0:
+        parser.error("--video-fps must be positive")
     return opts
 
 

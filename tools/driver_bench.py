@@ -3,6 +3,7 @@
 
     python tools/driver_bench.py [--size 512 | --height 320 --width 480] [--keys 5] [--rate 32] [--lanes 2] [--batch B] [--chunk 4]
                                   [--src-width 1920 --src-height 1080] [--resize-on host|gpu] [--metrics [--pose-mask]] [--panels [--panel-encode host|gpu]]
+                                  [--video [--frames none]]
 
 Writes a clip in the reference's directory layout (inputs/ DAIN/ Predict_motion/), runs
 Evaluator.evaluate_from_folder twice (the first run also builds launch plans) and prints the
@@ -12,6 +13,8 @@ so that the driver has to resize them; --resize-on says where (Evaluator(resize_
 frame per frame (gt/) and measures every generated frame against it (evaluate_from_folder(metrics=True)); --pose-mask measures
 under the mask drawn from each frame's pose (pose_mask=True), so that the cost of either can be read off two runs.  --panels also composes the six-pane diagnostic sheet of every frame and
 writes the clip's Motion-JPEG video (evaluate_from_folder(panels=True)); --panel-encode says where its JPEG frames are encoded.
+--video also writes the frames themselves as <clip>_video.avi (video=True: rib_jpeg_float on the lane's stream); --frames none
+writes only that video (frames="none": no PNG is encoded, the PNG level then plays no part).
 """
 import argparse, json, os, sys, tempfile, time
 import numpy as np, torch
@@ -74,7 +77,11 @@ def main():
     ap.add_argument("--panel-encode", default="host", choices=("host", "gpu"), help="with --panels: PIL in the file workers or rib_jpeg (panel_encode=...)")
     ap.add_argument("--background", default="dain", choices=("dain", "mci"),
                     help="'mci': the background frames are interpolated on the GPU from the key frames and the clip's DAIN folder is not read (background=...)")
+    ap.add_argument("--video", action="store_true", help="also write the frames as <clip>_video.avi, JPEG-encoded on the GPU (video=True)")
+    ap.add_argument("--frames", default="png", choices=("png", "none"), help="with --video: 'none' writes no PNG frames (frames=...)")
     a = ap.parse_args()
+    if a.frames == "none" and not a.video:
+        ap.error("--frames none is a setting of --video")
     if a.background == "mci" and a.resize_on == "gpu":
         ap.error("--background mci with --resize-on gpu is not supported")
     if a.panel_encode != "host" and not a.panels:
@@ -98,7 +105,7 @@ def main():
             t0 = time.perf_counter()
             out = E.evaluate_from_folder(G, *dirs, os.path.join(root, "out%d" % rep), gt_dir=os.path.join(root, "gt") if a.metrics else None,
                                          metrics=a.metrics, pose_mask=a.pose_mask, panels=a.panels, panel_encode=a.panel_encode,
-                                         background=a.background)
+                                         background=a.background, video=a.video, frames=a.frames)
             torch.cuda.synchronize()
             walls.append(time.perf_counter() - t0)
         tm = dict(E.timings)
@@ -110,6 +117,7 @@ def main():
                       "cpus": len(os.sched_getaffinity(0)), "cpu_budget": ev.cpu_budget(), "png_compress_level": a.compress,
                       "src_height": a.src_height or H, "src_width": a.src_width or W, "resize_on": a.resize_on, "background": a.background,
                       "metrics": a.metrics, "pose_mask": a.pose_mask, "metrics_overall": overall, "panels": a.panels, "panel_encode": a.panel_encode,
+                      "video": a.video, "frames_written": a.frames,
                       "wall_s": wall, "wall_s_runs": [round(w, 4) for w in walls[1:]], "frames_per_s_end_to_end": n / wall,
                       "phase_s_last_run": {k: round(v, 4) for k, v in tm.items() if k not in ("frames", "units", "timeline", "peak_units_in_flight")},
                       "peak_units_in_flight": tm.get("peak_units_in_flight"),

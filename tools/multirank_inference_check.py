@@ -45,6 +45,7 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="0 (default): the driver's own batching by frame size; N: chains of N segments")
     ap.add_argument("--no-reproducible", action="store_true", help="pass --no-reproducible to the CLI: every group size runs its own measured table; "
                                                                    "frames may then differ by one uint8 step between world sizes")
+    ap.add_argument("--video", action="store_true", help="pass --video to the CLI: every clip's <clip>_video.avi must be byte-identical too")
     a = ap.parse_args()
     import render_in_between_amd as rib
     from render_in_between_amd import synth
@@ -63,12 +64,16 @@ def main():
     for g in (1, a.gpus):
         out = os.path.join(tmp, "out%d" % g)
         t0 = time.time()
-        r = subprocess.run([sys.executable, cli, "--config", cpath, "--input-dir", tmp, "--save-dir", out, "--gpus", str(g), "--dtype", a.dtype, "--batch", str(a.batch)] + (["--no-reproducible"] if a.no_reproducible else []),
+        r = subprocess.run([sys.executable, cli, "--config", cpath, "--input-dir", tmp, "--save-dir", out, "--gpus", str(g), "--dtype", a.dtype, "--batch", str(a.batch)] + (["--no-reproducible"] if a.no_reproducible else []) + (["--video"] if a.video else []),
                            capture_output=True, text=True)
         if r.returncode != 0:
             print(r.stdout[-2000:], r.stderr[-4000:]); raise SystemExit("inference.py --gpus %d failed (rc %d)" % (g, r.returncode))
         res[g] = (out, time.time() - t0, [l for l in r.stdout.splitlines() if "rank" in l or "broadcast" in l])
     files = sorted(os.path.relpath(os.path.join(d, f), res[1][0]) for d, _, fs in os.walk(res[1][0]) for f in fs)
+    videos = [f for f in files if f.endswith(".avi")]
+    assert len(videos) == (len(a.keys) if a.video else 0), videos
+    videos_same = sum(open(os.path.join(res[1][0], f), "rb").read() == open(os.path.join(res[a.gpus][0], f), "rb").read() for f in videos)
+    files = [f for f in files if not f.endswith(".avi")]
     assert len(files) == n, (len(files), n)
     from PIL import Image
     same, worst = 0, 0
@@ -76,10 +81,10 @@ def main():
         same += open(os.path.join(res[1][0], f), "rb").read() == open(os.path.join(res[a.gpus][0], f), "rb").read()
         worst = max(worst, int(np.abs(np.asarray(Image.open(os.path.join(res[1][0], f))).astype(int) - np.asarray(Image.open(os.path.join(res[a.gpus][0], f))).astype(int)).max()))
     print(json.dumps({"frames": n, "ranks": a.gpus, "dtype": a.dtype, "size": [H, W], "batch": a.batch, "reproducible": not a.no_reproducible, "png_files_byte_identical": same,
-                      "all_identical": same == n, "max_abs_pixel_difference": worst, "seconds_1_rank": round(res[1][1], 2), "seconds_%d_ranks" % a.gpus: round(res[a.gpus][1], 2),
+                      "all_identical": same == n, "videos": len(videos), "videos_byte_identical": videos_same, "max_abs_pixel_difference": worst, "seconds_1_rank": round(res[1][1], 2), "seconds_%d_ranks" % a.gpus: round(res[a.gpus][1], 2),
                       "rank_lines": res[a.gpus][2], "one_rank_line": res[1][2]}))
     shutil.rmtree(tmp)
-    if (not a.no_reproducible and same != n) or worst > 1:      # the default policy promises the same bytes at every world size
+    if (not a.no_reproducible and (same != n or videos_same != len(videos))) or worst > 1:      # the default policy promises the same bytes at every world size
         raise SystemExit(1)
 
 
