@@ -92,6 +92,26 @@ int ribm_forward(ribm_handle* h, int N, int L, int rate, const float* src, const
                  const float* src_pos, const float* tgt, const uint8_t* tgt_mask, const float* tgt_pos,
                  float* joints, float* reco, void* ws, size_t ws_bytes, void* stream /* hipStream_t */);
 
+/* ---- the bridge to stage 2: replaces, for one clip, what the two commands do between the network's output and the
+ * (landmarks, confidence) the generator's folder driver draws from - Evaluator._post_process (HMM/models/evaluator.py:218-232),
+ * motion2openpose (HMM/utils/utils.py:179-230), the json file, and read_json_keypoint of that file (PGNR/utils/utils.py:12-60).
+ * motion/pose_io.py:openpose_arrays is the definition; the kernel is bit-equal to it (every fp64 operation rounded on its own).
+ *   ribm_set_pose_stats   mean, std: host fp64 [19][2], the dataset's pose statistics; called once (copies, synchronises).
+ *                         Needs no weights.  The model must have input_joints == 38 (19 joints x (x, y)).
+ *   ribm_openpose
+ *     joints     fp32 [L][N][38] on the device: what ribm_forward wrote, or any clip in that layout
+ *     conf       fp64 [N][19][L] on the device: the joints' confidences
+ *     scale, offset   image = network * scale + offset (openpose_scale, openpose_offset)
+ *     keypoints  fp64 [N][L][19][3] on the device: (x, y, confidence) of body joints 0-14, both big toes, the mean left and
+ *                right hand; a frame in which the reader finds no person (fewer than 4 of its first 15 joints above 0.1) is
+ *                all zeros, a hand without confidence a zero row
+ * One launch on the caller's stream, one thread per (clip, frame, joint); no workspace, no atomics, nothing synchronises; a
+ * frame's values depend on neither N nor L.  RIBM_ERR_INVALID / RIBM_ERR_STATE (statistics never set, host-only handle)
+ * launch nothing. */
+int ribm_set_pose_stats(ribm_handle* h, const double* mean, const double* std);
+int ribm_openpose(ribm_handle* h, int N, int L, const float* joints, const double* conf, double scale, double offset,
+                  double* keypoints, void* stream /* hipStream_t */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -409,6 +409,95 @@ __global__ __launch_bounds__(256) void km_interp(const float* reco, float* cente
   }
 }
 
+// The bridge to stage 2 (ribm_openpose): network output -> the 19 x (x, y, confidence) keypoints the generator's folder
+// driver reads back from stage 1's OpenPose json, without the file.  motion/pose_io.py:openpose_arrays is the definition
+// and names the three host functions this composes; every fp64 operation below is one of theirs, in their order, each
+// rounded on its own (numpy never fuses a product into a sum, so neither may the compiler: contract(off)).
+constexpr int POSE_JOINTS = 19, POSE_ROOT = 8, POSE_BODY = 15, POSE_HAND = 17, HAND_COPIES = 21;
+
+struct PoseParams {
+  const float* joints;    // [L][N][38]   what ribm_forward wrote
+  const double* conf;     // [N][19][L]
+  const double* stats;    // mean [19][2], then std [19][2]
+  double* out;            // [N][L][19][3]
+  double scale, offset;
+  int N, L;
+};
+
+// one coordinate (a = 0: x, 1: y) of joint j of the frame whose 38 channels start at fr, in image pixels
+__device__ __forceinline__ double pose_coord(const float* fr, const double* stats, double scale, double offset, int j, int a) {
+#pragma clang fp contract(off)
+  const double* mean = stats;
+  const double* sd = stats + 2 * POSE_JOINTS;
+  const int cc = 2 * (POSE_JOINTS - 1) + a;                 // the root's trajectory is the last network joint
+  const double prod_c = (double)fr[cc] * sd[cc];
+  const double centre = prod_c + mean[cc];
+  double local = 0.0;                                        // the root itself: the zero row _post_process re-inserts
+  if (j != POSE_ROOT) {
+    const int k = 2 * (j < POSE_ROOT ? j : j - 1) + a;
+    const double prod = (double)fr[k] * sd[k];
+    local = prod + mean[k];
+  }
+  const double world = local + centre;
+  const double scaled = world * scale;
+  return scaled + offset;
+}
+
+// the mean of HAND_COPIES equal rows as numpy takes it down axis 0: a running sum in row order, then one division
+__device__ __forceinline__ double mean_of_copies(double v) {
+#pragma clang fp contract(off)
+  double s = v;
+  for (int i = 1; i < HAND_COPIES; ++i) s = s + v;
+  return s / (double)HAND_COPIES;
+}
+
+// one thread per (clip, frame, joint); grid ceil(N * L * 19 / 256), block 256.  Every thread evaluates its frame's person
+// rule itself (15 confidences, at most 30 coordinates): no shared state, so a frame's values cannot depend on N, L or its neighbours.
+__global__ __launch_bounds__(256) void km_openpose(const PoseParams p) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)p.N * p.L * POSE_JOINTS) return;
+  const int j = (int)(idx % POSE_JOINTS);
+  const long f = idx / POSE_JOINTS;
+  const int l = (int)(f % p.L), n = (int)(f / p.L);
+  const float* fr = p.joints + ((size_t)l * p.N + n) * (2 * POSE_JOINTS);
+  const double* cf = p.conf + (size_t)n * POSE_JOINTS * p.L + l;      // joint k at cf[k * L]
+  // _largest_person of the one person stage 1 writes: at least 4 of the first 15 joints above 0.1, and a bounding-box area
+  // that compares greater than -1 (a NaN area, from a NaN or an infinite joint, does not)
+  int nvalid = 0;
+  bool nan = false;
+  double x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
+  for (int k = 0; k < POSE_BODY; ++k) {
+    if (!(cf[(size_t)k * p.L] > 0.1)) continue;
+    ++nvalid;
+    const double x = pose_coord(fr, p.stats, p.scale, p.offset, k, 0), y = pose_coord(fr, p.stats, p.scale, p.offset, k, 1);
+    nan = nan || x != x || y != y;
+    x0 = x < x0 ? x : x0; x1 = x > x1 ? x : x1;
+    y0 = y < y0 ? y : y0; y1 = y > y1 ? y : y1;
+  }
+  bool person = nvalid >= 4 && !nan;
+  if (person) {
+#pragma clang fp contract(off)
+    const double w = x1 - x0, hgt = y1 - y0;
+    const double area = w * hgt;
+    person = area > -1.0;
+  }
+  double o0 = 0.0, o1 = 0.0, o2 = 0.0;
+  if (person) {
+    const double c = cf[(size_t)j * p.L];
+    if (j < POSE_HAND) {                                     // body joints 0-14 and the toes: as written
+      o0 = pose_coord(fr, p.stats, p.scale, p.offset, j, 0);
+      o1 = pose_coord(fr, p.stats, p.scale, p.offset, j, 1);
+      o2 = c;
+    } else if (c > 0.0) {                                    // a hand: _mean_valid of its 21 copies, the confidence column too
+      o0 = mean_of_copies(pose_coord(fr, p.stats, p.scale, p.offset, j, 0));
+      o1 = mean_of_copies(pose_coord(fr, p.stats, p.scale, p.offset, j, 1));
+      o2 = mean_of_copies(c);
+    }
+  }
+  double* o = p.out + (size_t)idx * 3;
+  o[0] = o0; o[1] = o1; o[2] = o2;
+}
+
 std::string fmt(const char* f, ...) {
   char buf[512];
   va_list ap;
@@ -440,6 +529,8 @@ struct ribm_handle {
   size_t blob_floats = 0;
   bool ready = false;
   int launches = 0;
+  double* d_stats = nullptr;    // ribm_set_pose_stats: mean [19][2] then std [19][2]
+  bool stats_set = false;
 };
 
 namespace {
@@ -546,6 +637,7 @@ int ribm_create(const ribm_config* cfg, int device, ribm_handle** out) {
 void ribm_destroy(ribm_handle* h) {
   if (!h) return;
   if (h->d_blob) (void)hipFree(h->d_blob);
+  if (h->d_stats) (void)hipFree(h->d_stats);
   delete h;
 }
 
@@ -757,6 +849,41 @@ int ribm_forward(ribm_handle* h, int N, int L, int rate, const float* src, const
   linear(Tt, rowD, D, "decoder.norm", nullptr, 0, "joints_embed.weight", 0, C, "joints_embed.bias", -1, center, cs, joints, lnc);
   HIPM_TRY(h, hipGetLastError());
   h->launches = launches;
+  return RIBM_OK;
+}
+
+int ribm_set_pose_stats(ribm_handle* h, const double* mean, const double* std_) {
+  if (!h) return RIBM_ERR_INVALID;
+  if (!mean || !std_) return fail(h, RIBM_ERR_INVALID, "ribm_set_pose_stats: null argument");
+  if (h->c.input_joints != 2 * POSE_JOINTS)
+    return fail(h, RIBM_ERR_INVALID, fmt("ribm_set_pose_stats: the OpenPose layout has %d channels, this model %d", 2 * POSE_JOINTS, h->c.input_joints));
+  if (h->device < 0) return fail(h, RIBM_ERR_STATE, "ribm_set_pose_stats: host-only handle (device < 0)");
+  double host[4 * POSE_JOINTS];
+  std::memcpy(host, mean, 2 * POSE_JOINTS * sizeof(double));
+  std::memcpy(host + 2 * POSE_JOINTS, std_, 2 * POSE_JOINTS * sizeof(double));
+  HIPM_TRY(h, hipSetDevice(h->device));
+  if (!h->d_stats) HIPM_TRY(h, hipMalloc(&h->d_stats, sizeof host));
+  h->stats_set = false;
+  HIPM_TRY(h, hipMemcpy(h->d_stats, host, sizeof host, hipMemcpyHostToDevice));
+  h->stats_set = true;
+  return RIBM_OK;
+}
+
+int ribm_openpose(ribm_handle* h, int N, int L, const float* joints, const double* conf, double scale, double offset,
+                  double* keypoints, void* stream_) {
+  if (!h) return RIBM_ERR_INVALID;
+  if (h->device < 0) return fail(h, RIBM_ERR_STATE, "ribm_openpose: host-only handle (device < 0) cannot launch");
+  if (h->c.input_joints != 2 * POSE_JOINTS)
+    return fail(h, RIBM_ERR_INVALID, fmt("ribm_openpose: the OpenPose layout has C = %d channels, this model %d", 2 * POSE_JOINTS, h->c.input_joints));
+  if (N < 1 || L < 1 || (long)N * L > (1 << 24)) return fail(h, RIBM_ERR_INVALID, fmt("ribm_openpose: unsupported clip batch N=%d L=%d", N, L));
+  if (!joints || !conf || !keypoints) return fail(h, RIBM_ERR_INVALID, "ribm_openpose: null tensor");
+  if (!h->stats_set) return fail(h, RIBM_ERR_STATE, "ribm_openpose before ribm_set_pose_stats");
+  PoseParams p;
+  p.joints = joints; p.conf = conf; p.stats = h->d_stats; p.out = keypoints;
+  p.scale = scale; p.offset = offset; p.N = N; p.L = L;
+  const long total = (long)N * L * POSE_JOINTS;
+  hipLaunchKernelGGL(km_openpose, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, p);
+  HIPM_TRY(h, hipGetLastError());
   return RIBM_OK;
 }
 

@@ -518,7 +518,8 @@ class Evaluator:
     def evaluate_from_folder(self, model, train_dir, dain_dir, pose_dir, save_dir, gt_dir=None, gen_vid=False,
                              rank=None, world=None, metrics=False, mask_dir=None, pose_mask=False,
                              panels=False, panel_frames=False, panel_quality=90, panel_fps=30, panel_encode="host",
-                             background="dain", video=False, video_fps=30, video_quality=90, video_frames=False, frames="png"):
+                             background="dain", video=False, video_fps=30, video_quality=90, video_frames=False, frames="png",
+                             poses="folder", key_pose_dir=None, upsample_rate=8, motion=None, save_poses=False):
         """rank / world: this process's share of the independent units (default: the torch.distributed process
         group when one is initialised, else everything).  Returns the frames THIS rank wrote.
         The call is one `_FolderPipeline` (below): plan a clip -> decode -> upload -> render -> sink, pipelined over units
@@ -561,7 +562,30 @@ class Evaluator:
         lengths ride home in the unit's one copy and the finisher fetches exactly the files' bytes and writes them: no worker,
         no PIL.  A model behind the reference's protocol encodes with jpeg_encode_host on the host: the same files.
         frames="none" (only with video=True; default "png"): no frame PNG is encoded, staged or written and the frames' raw bytes
-        stay on the device; the call returns the names of the .jpg files this rank wrote.  video=False changes nothing."""
+        stay on the device; the call returns the names of the .jpg files this rank wrote.  video=False changes nothing.
+        poses="keyframes" (default "folder": one OpenPose json per output frame under pose_dir/<clip>/, what stage 1's own
+        command writes): stage 1 runs here.  key_pose_dir/<clip>/ holds one OpenPose json per KEY frame; `motion` is the
+        motion model (motion.model.ModelInference built with its dataset: motion/inference.py:load_model(config, dataset=...));
+        plan_clip interpolates the clip upsample_rate-fold (a power of two) with ModelInference.interpolate_clip - one forward
+        pass, one bridge launch (ribm_openpose), one copy home per clip, run by every rank for itself - and frame i's decode
+        task gets row i of that [L, 19, 3] array where it got a json path: exactly the array rasterise.read_json_keypoint
+        returns for the file stage 1's command would have written (motion.pose_io.openpose_arrays), so every output is the
+        two-command run's.  pose_dir may be None and is never listed, read or written; the clips are key_pose_dir's folders.
+        Under background="mci" frame i is named "%06d" % i, the stem stage 1's command gives its file.  "keyframes-linear":
+        the same from the linearly interpolated clip (stage 1's Linear_motion folder).  save_poses=True also writes
+        <save_dir>/../Predict_motion/<clip>/ and Linear_motion/<clip>/ - beside save_dir, where stage 1's command run with
+        the same --save-dir puts them - through that command's own motion2openpose (rank 0; for inspection)."""
+        if poses not in ("folder", "keyframes", "keyframes-linear"):
+            raise ValueError("evaluate_from_folder: poses must be 'folder', 'keyframes' or 'keyframes-linear', got %r" % (poses,))
+        if poses == "folder" and (key_pose_dir is not None or upsample_rate != 8 or motion is not None or save_poses):
+            raise ValueError("evaluate_from_folder: key_pose_dir, upsample_rate, motion and save_poses are settings of poses='keyframes' / 'keyframes-linear'")
+        if poses != "folder":
+            if key_pose_dir is None:
+                raise ValueError("evaluate_from_folder: poses=%r needs key_pose_dir (one OpenPose json per key frame)" % (poses,))
+            if motion is None or not hasattr(motion, "interpolate_clip"):
+                raise ValueError("evaluate_from_folder: poses=%r needs motion= (the motion model, motion.model.ModelInference)" % (poses,))
+            if not (isinstance(upsample_rate, int) and upsample_rate >= 1 and upsample_rate & (upsample_rate - 1) == 0):
+                raise ValueError("evaluate_from_folder: upsample_rate must be a power of two, got %r" % (upsample_rate,))
         if background not in ("dain", "mci"):
             raise ValueError("evaluate_from_folder: background must be 'dain' or 'mci', got %r" % (background,))
         if background == "mci" and self.resize_on == "gpu":
@@ -599,14 +623,16 @@ class Evaluator:
         pipe = _FolderPipeline(self, model, rank, world, gt_dir, metrics=bool(metrics), mask_dir=mask_dir, pose_mask=bool(pose_mask),
                                panels=bool(panels), panel_frames=bool(panel_frames), panel_quality=int(panel_quality),
                                panel_encode=panel_encode, background=background, video=bool(video), video_quality=int(video_quality),
-                               video_frames=bool(video_frames), write_png=frames == "png")
+                               video_frames=bool(video_frames), write_png=frames == "png",
+                               key_poses=None if poses == "folder" else (motion, key_pose_dir, upsample_rate, poses == "keyframes-linear", bool(save_poses)))
         self.background = background
         self.timings = pipe.tm
         if metrics and pipe.native:
             self._quality_model = model
         try:
             with self._plan_policy(model, pipe.native):
-                for sub in [f for f in sorted(os.listdir(pose_dir)) if os.path.isdir(os.path.join(pose_dir, f))]:
+                clips_dir = pose_dir if poses == "folder" else key_pose_dir
+                for sub in [f for f in sorted(os.listdir(clips_dir)) if os.path.isdir(os.path.join(clips_dir, f))]:
                     print("Evaluating {} .....".format(sub))
                     clip = pipe.plan_clip(sub, train_dir, dain_dir, pose_dir, save_dir)
                     if pipe.native:
@@ -706,8 +732,10 @@ class _FolderPipeline:
 
     def __init__(self, ev, model, rank, world, gt_dir, metrics=False, mask_dir=None, pose_mask=False,
                  panels=False, panel_frames=False, panel_quality=90, panel_encode="host", background="dain",
-                 video=False, video_quality=90, video_frames=False, write_png=True):
+                 video=False, video_quality=90, video_frames=False, write_png=True, key_poses=None):
         self.mci = background == "mci"
+        # poses="keyframes": (motion model, key-pose folder, upsample rate, take the linear clip, also write the json folders)
+        self.key_poses = key_poses
         # video: the frames' JPEG files (video.py); write_png False (frames="none"): they are the only files of a frame
         self.video, self.video_quality, self.video_frames, self.write_png = video, video_quality, video_frames, write_png
         self.ev, self.model, self.rank, self.world, self.gt_dir = ev, model, rank, world, gt_dir
@@ -788,6 +816,26 @@ class _FolderPipeline:
         return self.save_q(u8, clip.names[i]) if self.write_png else clip.video_name(i)
 
     # ---- stage 0: plan ---------------------------------------------------------------------------------------------------
+    def interpolate_poses(self, sub, n_key, save_dir):
+        """poses="keyframes": stage 1 for one clip -> (the [19, 3] keypoint array of every frame, the sample rate).  Every rank
+        runs it for itself (about a millisecond of GPU work and no communication), so the frames cannot depend on the number
+        of ranks; the array comes home in one copy and its rows take the place of the json paths."""
+        motion, key_pose_dir, rate, linear, save = self.key_poses
+        json_dir = os.path.join(key_pose_dir, sub)
+        n_pose = len(_list(json_dir, ("json",)))
+        if n_pose != n_key:
+            raise ValueError("poses='keyframes': clip %s has %d key-pose files and %d key frames; each key frame needs its pose"
+                             % (sub, n_pose, n_key))
+        folders = None
+        if save and self.rank == 0:
+            root = os.path.dirname(os.path.abspath(save_dir))
+            folders = {"pred_dir": os.path.join(root, "Predict_motion", sub), "linear_dir": os.path.join(root, "Linear_motion", sub)}
+        pred, lin = motion.interpolate_clip(json_dir, rate, save_dir=folders)
+        rows = lin if linear else pred
+        if len(rows) != (n_key - 1) * rate + 1:
+            raise ValueError("poses='keyframes': clip %s: stage 1 returned %d frames for %d key frames at rate %d" % (sub, len(rows), n_key, rate))
+        return [np.ascontiguousarray(rows[i]) for i in range(len(rows))], rate
+
     def plan_clip(self, sub, train_dir, dain_dir, pose_dir, save_dir):
         ev = self.ev
         frames_dir = os.path.join(save_dir, sub)
@@ -795,12 +843,17 @@ class _FolderPipeline:
             os.makedirs(frames_dir, exist_ok=True)
         image_list = _list(os.path.join(train_dir, sub), ("jpg", "png"))
         dain_list = None if self.mci else _list(os.path.join(dain_dir, sub), ("jpg", "png"))
-        pose_list = _list(os.path.join(pose_dir, sub), ("json",))
         if self.mci and len(image_list) < 2:
             raise ValueError("background='mci': clip %s has %d key frame(s); a segment needs two" % (sub, len(image_list)))
-        sample_rate = sample_rate_of(len(pose_list), len(image_list))
+        if self.key_poses is not None:
+            pose_list, sample_rate = self.interpolate_poses(sub, len(image_list), save_dir)
+        else:
+            pose_list = _list(os.path.join(pose_dir, sub), ("json",))
+            sample_rate = sample_rate_of(len(pose_list), len(image_list))
         seq_len = (len(image_list) - 1) * sample_rate + 1
-        if self.mci:                         # no DAIN list to name the frames after: the pose file's stem
+        if self.mci and self.key_poses is not None:      # the stems stage 1's own command gives its files
+            names = [os.path.join(frames_dir, "%06d.png" % i) for i in range(seq_len)]
+        elif self.mci:                       # no DAIN list to name the frames after: the pose file's stem
             def stem(path):
                 base = os.path.splitext(os.path.basename(path))[0]
                 return base[:-len("_keypoints")] if base.endswith("_keypoints") else base

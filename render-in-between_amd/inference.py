@@ -37,6 +37,14 @@ frames - a classical motion-compensated interpolation (background.py states it i
 and never reads <input>/DAIN.  It is this project's interpolation, not DAIN: the generator was trained on DAIN backgrounds, the
 quality on real footage has not been measured, and motion beyond +-32 px between key frames falls outside the search.  Frames
 are then named after their pose files.  The default, `--background dain`, is the reference's contract.
+
+Poses without a Predict_motion folder: `--poses keyframes --pose-dir DIR [--upsample-rate N] [--motion-config PATH]` runs stage 1
+(the motion transformer, motion/inference.py) inside this command: DIR/<clip>/ holds one OpenPose json per key frame, each clip is
+interpolated N-fold on the GPU and its keypoints go straight from the network's output to the frames' rasteriser tables
+(ribm_openpose; motion/pose_io.py:openpose_arrays states what the json files in between would have held, bit for bit) - the
+frames are the two-command run's.  <input-dir>/Predict_motion is not read.  `keyframes-linear` takes the linearly interpolated
+clip (stage 1's Linear_motion folder); `--save-poses` also writes <save-dir>/Predict_motion and <save-dir>/Linear_motion as stage 1's
+own command does.  With `--background mci --video --frames none` one command turns key frames and their detections into the clip.
 """
 import argparse
 import os
@@ -85,6 +93,14 @@ def load_generator(config, device=None, rank=0, world=1, dtype="f32"):
     return net_G
 
 
+def load_motion(path, device=None):
+    """Stage 1 for --poses keyframes: the motion transformer with its checkpoint and the dataset that reads a key-pose folder
+    (motion/inference.py:load_model; every rank loads the 2 M parameters itself)."""
+    from render_in_between_amd.motion import inference as stage1, pose_io
+    config = stage1.get_config(path)
+    return stage1.load_model(config, device, dataset=pose_io.OpenPoseClips(config))
+
+
 def summary_line(evaluator, rank=0, world=1):
     """One line per rank at the end of a run: what was rendered and where the wall time went.  The phases are the launch
     thread's waits (load: for decoded inputs; rasterise + generate: enqueueing the GPU work; save: the encode tail after the
@@ -131,7 +147,11 @@ def main(opts):
                           png_compress_level=None if opts.png_level == "reference" else int(opts.png_level), resize_on=opts.resize_on)
     train_dir = os.path.join(opts.input_dir, "inputs")
     dain_dir = os.path.join(opts.input_dir, "DAIN") if opts.background == "dain" else None
-    pose_dir = os.path.join(opts.input_dir, "Predict_motion")
+    pose_dir = os.path.join(opts.input_dir, "Predict_motion") if opts.poses == "folder" else None
+    poses_kw = {}
+    if opts.poses != "folder":
+        poses_kw = dict(poses=opts.poses, key_pose_dir=opts.pose_dir, upsample_rate=8 if opts.upsample_rate is None else opts.upsample_rate,
+                        motion=load_motion(opts.motion_config or os.path.join(_HERE, "configs", "motion.yaml"), device), save_poses=opts.save_poses)
     save_dir = os.path.join(opts.save_dir, "Generated_frames")
     written = evaluator.evaluate_from_folder(net_G, train_dir, dain_dir, pose_dir, save_dir, gt_dir=opts.gt_dir, gen_vid=False,
                                              metrics=opts.metrics, mask_dir=opts.mask_dir, pose_mask=opts.pose_mask,
@@ -141,7 +161,7 @@ def main(opts):
                                              panel_encode=opts.panel_encode or "host", background=opts.background,
                                              video=opts.video, video_fps=30 if opts.video_fps is None else opts.video_fps,
                                              video_quality=90 if opts.video_quality is None else opts.video_quality,
-                                             video_frames=opts.video_frames, frames=opts.frames)
+                                             video_frames=opts.video_frames, frames=opts.frames, **poses_kw)
     print(summary_line(evaluator, rank, world))
     if world > 1:
         print("[rank {}/{}] wrote {} frames".format(rank, world, len(written)))
@@ -212,6 +232,17 @@ def build_parser():
     parser.add_argument("--frames", choices=("png", "none"), default="png",
                         help="'png' (default): the reference's folder of PNG frames; 'none' (only with --video): the video is the only "
                              "output - no PNG is encoded or written, the raw frames are not downloaded")
+    parser.add_argument("--poses", default="folder",
+                        help="where the frames' poses come from. 'folder' (default): <input-dir>/Predict_motion/<clip>/, one OpenPose json per "
+                             "output frame, as the reference (written by motion/inference.py); 'keyframes': --pose-dir holds one json per KEY "
+                             "frame and the motion transformer interpolates them inside this command - the same frames, no Predict_motion "
+                             "folder; 'keyframes-linear': the same from the linearly interpolated poses (stage 1's Linear_motion)")
+    parser.add_argument("--pose-dir", type=str, default=None, help="with --poses keyframes*: <pose-dir>/<clip>/*.json, the key frames' OpenPose detections")
+    parser.add_argument("--upsample-rate", type=int, default=None, help="with --poses keyframes*: output frames per key-frame interval, a power of two (default 8)")
+    parser.add_argument("--motion-config", type=str, default=None, help="with --poses keyframes*: stage 1's config file (default configs/motion.yaml)")
+    parser.add_argument("--save-poses", action="store_true",
+                        help="with --poses keyframes*: also write <save-dir>/Predict_motion/<clip>/ and <save-dir>/Linear_motion/<clip>/, the "
+                             "json files of stage 1's own command (for inspection; nothing reads them)")
     return parser
 
 
@@ -222,6 +253,14 @@ def parse_args(argv=None):
         parser.error("--png-level must be 'reference' or a zlib level 0-9")
     if opts.background not in ("dain", "mci"):
         parser.error("--background must be 'dain' or 'mci', got %r" % (opts.background,))
+    if opts.poses not in ("folder", "keyframes", "keyframes-linear"):
+        parser.error("--poses must be 'folder', 'keyframes' or 'keyframes-linear', got %r" % (opts.poses,))
+    if opts.poses == "folder" and (opts.pose_dir is not None or opts.upsample_rate is not None or opts.motion_config is not None or opts.save_poses):
+        parser.error("--pose-dir, --upsample-rate, --motion-config and --save-poses are settings of --poses keyframes / keyframes-linear")
+    if opts.poses != "folder" and opts.pose_dir is None:
+        parser.error("--poses %s needs --pose-dir (the key frames' OpenPose json folders)" % opts.poses)
+    if opts.upsample_rate is not None and (opts.upsample_rate < 1 or opts.upsample_rate & (opts.upsample_rate - 1)):
+        parser.error("--upsample-rate must be a power of two")
     if opts.background == "mci" and opts.resize_on == "gpu":
         parser.error("--background mci with --resize-on gpu is not supported (there is no DAIN list to plan the GPU resize for)")
     if opts.metrics and opts.gt_dir is None:

@@ -53,13 +53,21 @@ def image_size(path):
         return im.size
 
 
-def scaled_pose(json_path, orig_size, width, height):
-    """json -> (landmarks, conf) in model-size pixels: the keypoints follow the image resize (A.Resize keypoint rule,
-    evaluator.py:24-26,219)."""
-    pose = rasterise.read_json_keypoint(json_path)
+def scale_pose(pose, orig_size, width, height):
+    """[19, 3] keypoints in the pixels of an image of orig_size -> (landmarks, conf) in model-size pixels: the keypoints
+    follow the image resize (A.Resize keypoint rule, evaluator.py:24-26,219)."""
     sx, sy = width / orig_size[0], height / orig_size[1]
     lm = [(pose[i, 0] * sx, pose[i, 1] * sy) for i in range(pose.shape[0])]
     return lm, [pose[i, 2] for i in range(pose.shape[0])]
+
+
+def scaled_pose(pose, orig_size, width, height):
+    """scale_pose of a frame's pose as the plan hands it out: the path of its OpenPose json, read here
+    (rasterise.read_json_keypoint), or - poses="keyframes" - the frame's [19, 3] row of the clip's array, which is what that
+    reader would have returned."""
+    if not isinstance(pose, np.ndarray):
+        pose = rasterise.read_json_keypoint(pose)
+    return scale_pose(pose, orig_size, width, height)
 
 
 def load_frame(dain_path, ref_img_path, pose_path, is_key, want_tables, width, height, resize, thres1, thres2):

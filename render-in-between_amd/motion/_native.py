@@ -37,6 +37,8 @@ SIGNATURES = {
     "ribm_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "ribm_num_launches": (C.c_int, [C.c_void_p]),
     "ribm_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.c_size_t, C.c_void_p]),
+    "ribm_set_pose_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ribm_openpose": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -31,8 +31,9 @@ def get_config(path):
         return AttrDict(yaml.load(stream, Loader=yaml.FullLoader))
 
 
-def load_model(config, device=None):
-    """trainer.pos_encode / trainer.transformer with the checkpoint (HMM/models/trainer.py:64-74)."""
+def load_model(config, device=None, dataset=None):
+    """trainer.pos_encode / trainer.transformer with the checkpoint (HMM/models/trainer.py:64-74).  dataset
+    (pose_io.OpenPoseClips): for ModelInference.interpolate_clip, the generator's folder driver's way in."""
     spec = MotionSpec.from_cfg(config)
     transformer = model.MotionTransformer(spec, device=device)
     path = config.model_pretrain
@@ -42,7 +43,7 @@ def load_model(config, device=None):
     else:
         raise ValueError("=> No checkpoint found at '{}'".format(path))
     transformer.load_state_dict(checkpoint)
-    return model.ModelInference(model.PositionEmbeddingSine1D(spec.pos_hidden_dim // 2, normalize=True), transformer)
+    return model.ModelInference(model.PositionEmbeddingSine1D(spec.pos_hidden_dim // 2, normalize=True), transformer, dataset=dataset)
 
 
 def main(opts):

@@ -16,6 +16,7 @@ import ctypes as C
 import math
 from typing import Dict, Optional
 
+import numpy as np
 import torch
 
 from . import _native
@@ -181,14 +182,50 @@ class MotionTransformer:
 
     __call__ = forward
 
+    def set_pose_stats(self, mean_pose, std_pose):
+        """The dataset's pose statistics, fp64 [19][2] each (pose_io.OpenPoseClips.mean_pose / std_pose), for openpose()."""
+        mean = np.ascontiguousarray(mean_pose, np.float64)
+        std = np.ascontiguousarray(std_pose, np.float64)
+        if mean.shape != (19, 2) or std.shape != (19, 2):
+            raise RuntimeError("pose statistics must be [19][2], got %s and %s" % (mean.shape, std.shape))
+        with torch.cuda.device(self.device):
+            _native.check(self._h, self._lib.ribm_set_pose_stats(self._h, C.c_void_p(mean.ctypes.data), C.c_void_p(std.ctypes.data)))
+        return self
+
+    def openpose(self, joints, conf, scale, offset, out=None):
+        """The bridge to stage 2 (ribm_openpose; pose_io.openpose_arrays is its definition): joints fp32 [L][N][38] as forward()
+        returns them, conf fp64 [N][19][L] -> keypoints fp64 [N][L][19][3] on this device, one launch on the current stream.
+        Tensors that are not on this device, of another dtype or not contiguous are errors: nothing is converted here."""
+        def ok(t, dt):
+            return torch.is_tensor(t) and t.device == self.device and t.dtype == dt and t.is_contiguous()
+        if not ok(joints, torch.float32) or joints.dim() != 3:
+            raise RuntimeError("openpose: joints must be a contiguous float32 [L][N][C] tensor on %s" % (self.device,))
+        L, N, Cj = joints.shape
+        if not ok(conf, torch.float64) or tuple(conf.shape) != (N, 19, L):
+            raise RuntimeError("openpose: conf must be a contiguous float64 [N][19][L] = %s tensor on %s" % ((N, 19, L), self.device))
+        if Cj != self.spec.input_joints:
+            raise RuntimeError("openpose: joints has %d channels, the model %d" % (Cj, self.spec.input_joints))
+        if out is None:
+            out = torch.empty((N, L, 19, 3), dtype=torch.float64, device=self.device)
+        elif not ok(out, torch.float64) or tuple(out.shape) != (N, L, 19, 3):
+            raise RuntimeError("openpose: out must be a contiguous float64 [N][L][19][3] tensor on %s" % (self.device,))
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _native.check(self._h, self._lib.ribm_openpose(self._h, N, L, _ptr(joints), _ptr(conf), float(scale), float(offset), _ptr(out), st))
+        return out
+
 
 class ModelInference:
-    """Model_inference (HMM/inference.py:12-41)."""
+    """Model_inference (HMM/inference.py:12-41).  dataset (pose_io.OpenPoseClips; optional): what interpolate_clip reads a
+    key-pose folder with; its pose statistics go to the transformer once."""
 
-    def __init__(self, enc, transformer):
+    def __init__(self, enc, transformer, dataset=None):
         self.pos_encode = enc
         self.transformer = transformer
         self.device = transformer.device
+        self.dataset = dataset
+        if dataset is not None:
+            transformer.set_pose_stats(dataset.mean_pose, dataset.std_pose)
 
     def inference(self, data, interp, encoder_mask, decoder_mask, rate):
         self.pos_encode.eval()
@@ -199,3 +236,25 @@ class ModelInference:
         tgt_mask = torch.unsqueeze(decoder_mask, dim=0).to(self.device)
         pred, _ = self.transformer.forward(src, src_mask, self.pos_encode(src_mask), tgt, tgt_mask, self.pos_encode(tgt_mask), rate)
         return pred.permute(1, 2, 0)
+
+    def interpolate_clip(self, json_dir, sample_rate, save_dir=None):
+        """One clip from its key-pose folder to the keypoints the generator's folder driver draws from, without the json
+        files in between: -> (pred, linear), fp64 [L][19][3] numpy arrays - row i is what rasterise.read_json_keypoint gives
+        for file i of Predict_motion/<clip>/ and of Linear_motion/<clip>/ as motion/inference.py writes them
+        (pose_io.openpose_arrays states it; the transformer's bridge kernel computes it, bit-equal).  The forward pass is the
+        stand-alone command's (N = 1); the bridge then takes the prediction and the linearly interpolated clip - permuted to
+        [L][N][C] on the host - as the two clips of ONE launch, and the result comes home in one copy.
+        save_dir = {"pred_dir": ..., "linear_dir": ...}: also write both folders, through the stand-alone command's own
+        motion2openpose (for inspection; the arrays do not come from them)."""
+        from . import pose_io
+        if self.dataset is None:
+            raise RuntimeError("interpolate_clip: this ModelInference was built without a dataset (pose_io.OpenPoseClips)")
+        (scale, offset, conf), data, interp, encoder_mask, decoder_mask = self.dataset.get_openpose_data(json_dir, sample_rate)
+        pred = self.inference(data, interp, encoder_mask, decoder_mask, sample_rate)                 # [1][C][L], a view of [L][1][C]
+        lin = interp.t().contiguous().unsqueeze(1).to(self.device)                                   # [L][1][C]
+        both = torch.cat([pred.permute(2, 0, 1), lin], dim=1).contiguous()                           # [L][2][C]
+        cf = torch.from_numpy(np.ascontiguousarray(conf.transpose(1, 0, 2), np.float64)).to(self.device)     # [19][1][L] -> [1][19][L]
+        kp = self.transformer.openpose(both, cf.expand(2, -1, -1).contiguous(), scale, offset).cpu().numpy()
+        if save_dir is not None:
+            pose_io.write_clip_folders(self.dataset, pred, interp.unsqueeze(0), conf, scale, offset, sample_rate, save_dir)
+        return kp[0], kp[1]

@@ -73,6 +73,21 @@ def openpose2motion(json_dir, scale=None, offset=None, max_frame=None, thres=0.0
     return motion.transpose(1, 2, 0), conf[:, :, np.newaxis].transpose(1, 2, 0), (scale, offset)
 
 
+def openpose_document(joints, c):
+    """The OpenPose json document of one frame: joints [19][2] in image coordinates, c [19][1] confidences -> the 25-joint body
+    layout (0-14, big toes at 19 and 22) and each hand as 21 copies of its one joint (utils.py:188-228)."""
+    body = np.pad(np.concatenate([joints[:15], c[:15]], axis=1), ((0, 10), (0, 0)), "constant", constant_values=0.0)
+    body[19, :] = np.concatenate([joints[15], c[15]], axis=None)
+    body[22, :] = np.concatenate([joints[16], c[16]], axis=None)
+
+    def hand(j):
+        return np.concatenate([joints[j], c[j]], axis=None)[np.newaxis, :].repeat(21, axis=0).reshape(-1).tolist()
+    person = {"person_id": [-1], "pose_keypoints_2d": body.reshape(-1).tolist(), "face_keypoints_2d": [],
+              "hand_left_keypoints_2d": hand(17), "hand_right_keypoints_2d": hand(18),
+              "pose_keypoints_3d": [], "face_keypoints_3d": [], "hand_left_keypoints_3d": [], "hand_right_keypoints_3d": []}
+    return {"version": 1.3, "people": [person]}
+
+
 def motion2openpose(motion, conf, save_json_dir, scale=512.0, offset=256.0, sample_rate=8):
     if not os.path.exists(save_json_dir):
         print("Creating directory: {}".format(save_json_dir))
@@ -80,17 +95,65 @@ def motion2openpose(motion, conf, save_json_dir, scale=512.0, offset=256.0, samp
     for i in range(motion.shape[-1]):
         joints = motion[:, :, i].copy() * scale + offset
         c = conf[:, :, i].copy()
-        body = np.pad(np.concatenate([joints[:15], c[:15]], axis=1), ((0, 10), (0, 0)), "constant", constant_values=0.0)
-        body[19, :] = np.concatenate([joints[15], c[15]], axis=None)
-        body[22, :] = np.concatenate([joints[16], c[16]], axis=None)
-
-        def hand(j):
-            return np.concatenate([joints[j], c[j]], axis=None)[np.newaxis, :].repeat(21, axis=0).reshape(-1).tolist()
-        person = {"person_id": [-1], "pose_keypoints_2d": body.reshape(-1).tolist(), "face_keypoints_2d": [],
-                  "hand_left_keypoints_2d": hand(17), "hand_right_keypoints_2d": hand(18),
-                  "pose_keypoints_3d": [], "face_keypoints_3d": [], "hand_left_keypoints_3d": [], "hand_right_keypoints_3d": []}
         with open(os.path.join(save_json_dir, "{:06d}_keypoints.json".format(i)), "w") as fp:
-            json.dump({"version": 1.3, "people": [person]}, fp)
+            json.dump(openpose_document(joints, c), fp)
+
+
+def post_process(d, mean_pose, std_pose):
+    """Evaluator._post_process of one clip as a function of arrays: d fp32 [C][L] network output -> fp64 [19][2][L] in
+    network coordinates (de-normalised in two roundings, the root re-inserted as a zero row, the root's trajectory added)."""
+    d = d.reshape(-1, 2, d.shape[-1])
+    d = d * std_pose[:, :, np.newaxis] + mean_pose[:, :, np.newaxis]
+    centers = d[-1].copy()
+    inv = np.r_[d[:ROOT_IDX], np.zeros((1, 2, d.shape[-1])), d[ROOT_IDX:-1]]
+    return inv + centers.reshape((1, 2, -1))
+
+
+def openpose_arrays(motion, conf, scale, offset, mean_pose, std_pose):
+    """THE DEFINITION of what the generator's folder driver draws a clip from when stage 1 runs in its process
+    (evaluate_from_folder(poses="keyframes")), and of the transformer's bridge kernel (ribm_openpose, bit-equal):
+    motion fp32 [C][L] (C = 38: the network's output, or the linearly interpolated clip), conf fp64 [19][1][L], scale / offset
+    (openpose_scale, openpose_offset), the dataset's pose statistics fp64 [19][2]  ->  fp64 [L][19][3], row i = (x, y,
+    confidence) of the 19 joints of frame i.
+
+    It is a composition of what the two commands do to a clip between the network and the driver's (landmarks, conf), by the
+    very functions they run - nothing is restated and no arithmetic is added:
+      post_process (Evaluator._post_process)   fp32 -> fp64, * std + mean in two roundings, root re-inserted, + centres
+      motion2openpose's frame                  * scale + offset, openpose_document: 25-joint body, each hand 21 copies
+      rasterise.keypoints_of (read_json_keypoint of the parsed file)
+                                               _largest_person: fewer than 4 of the first 15 joints above 0.1 (or a bounding
+                                               box whose area is NaN) -> all zeros; body joints 0-14, 19, 22; _mean_valid of
+                                               the 21 copies - their running sum / 21, not always the double itself; a hand
+                                               with confidence <= 0 -> a zero row
+    The file between the last two is left out: json.dump writes a double as its shortest round-tripping repr and json.load
+    parses that back to the same double (NaN and the infinities included), so the document parsed is the document dumped."""
+    from ..rasterise import keypoints_of
+    motion = np.asarray(motion)
+    if motion.dtype != np.float32 or motion.ndim != 2 or motion.shape[0] != 38:
+        raise ValueError("openpose_arrays: motion must be float32 [38][L], got %s %s" % (motion.dtype, motion.shape))
+    conf = np.asarray(conf, np.float64)
+    if conf.shape != (19, 1, motion.shape[1]):
+        raise ValueError("openpose_arrays: conf must be [19][1][L] = %s, got %s" % ((19, 1, motion.shape[1]), conf.shape))
+    world = post_process(motion, mean_pose, std_pose)
+    out = np.zeros((motion.shape[1], 19, 3))
+    for i in range(motion.shape[1]):
+        joints = world[:, :, i].copy() * scale + offset
+        out[i] = keypoints_of(openpose_document(joints, conf[:, :, i].copy()))
+    return out
+
+
+def write_clip_folders(dataset, output, interp_motion, conf, scale, offset, sample_rate, save_dir):
+    """The two json folders of one clip as Evaluator.interpolate_openpose writes them: output / interp_motion fp32 [1][C][L]
+    tensors; an existing folder is replaced."""
+    out = post_process(output.detach().cpu().numpy()[0], dataset.mean_pose, dataset.std_pose)
+    interp = post_process(interp_motion.detach().cpu().numpy()[0], dataset.mean_pose, dataset.std_pose)
+    for key in ("pred_dir", "linear_dir"):
+        if os.path.exists(save_dir[key]):
+            shutil.rmtree(save_dir[key])
+            print("detete {} ... ".format(save_dir[key]))
+    motion2openpose(out, conf, save_dir["pred_dir"], scale=scale, offset=offset, sample_rate=sample_rate)
+    motion2openpose(interp, conf, save_dir["linear_dir"], scale=scale, offset=offset, sample_rate=sample_rate)
+    return out, interp
 
 
 class OpenPoseClips:
@@ -161,23 +224,12 @@ class Evaluator:
         self.model = model
 
     def _post_process(self, data, start=0):
-        d = data.detach().cpu().numpy()[0].reshape(-1, 2, data.shape[-1])
-        d = d * self.dataset.std_pose[:, :, np.newaxis] + self.dataset.mean_pose[:, :, np.newaxis]
-        centers = d[-1].copy()
-        inv = np.r_[d[:ROOT_IDX], np.zeros((1, 2, d.shape[-1])), d[ROOT_IDX:-1]]
-        return inv + centers.reshape((1, 2, -1))
+        return post_process(data.detach().cpu().numpy()[0], self.dataset.mean_pose, self.dataset.std_pose)
 
     def interpolate_openpose(self, json_dir, sample_rate, save_dir):
         (scale, offset, conf), input_motion, interp_motion, encoder_mask, decoder_mask = \
             self.dataset.get_openpose_data(json_dir, sample_rate)
         output = self.model.inference(input_motion, interp_motion, encoder_mask, decoder_mask, sample_rate)
-        out = self._post_process(output, 0)
-        interp = self._post_process(interp_motion.unsqueeze(0), 0)
-        for key in ("pred_dir", "linear_dir"):
-            if os.path.exists(save_dir[key]):
-                shutil.rmtree(save_dir[key])
-                print("detete {} ... ".format(save_dir[key]))
-        motion2openpose(out, conf, save_dir["pred_dir"], scale=scale, offset=offset, sample_rate=sample_rate)
-        motion2openpose(interp, conf, save_dir["linear_dir"], scale=scale, offset=offset, sample_rate=sample_rate)
+        out, interp = write_clip_folders(self.dataset, output, interp_motion.unsqueeze(0), conf, scale, offset, sample_rate, save_dir)
         print("Inference done!")
         return out, interp

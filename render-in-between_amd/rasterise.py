@@ -67,7 +67,11 @@ def read_json_keypoint(path):
     """OpenPose json -> (19, 3) [x, y, confidence]: body joints 0-14, toes 19 and 22, mean
     left / right hand (utils.py:12-60)."""
     with open(path) as f:
-        d = json.load(f)
+        return keypoints_of(json.load(f))
+
+
+def keypoints_of(d):
+    """read_json_keypoint of a parsed OpenPose document (what json.load gave, or the dict about to be dumped)."""
     people = d.get("people", [])
     idx = _largest_person(people) if people else -1
     if idx == -1:

@@ -3,7 +3,7 @@
 
     python tools/driver_bench.py [--size 512 | --height 320 --width 480] [--keys 5] [--rate 32] [--lanes 2] [--batch B] [--chunk 4]
                                   [--src-width 1920 --src-height 1080] [--resize-on host|gpu] [--metrics [--pose-mask]] [--panels [--panel-encode host|gpu]]
-                                  [--video [--frames none]]
+                                  [--video [--frames none]] [--poses folder|keyframes]
 
 Writes a clip in the reference's directory layout (inputs/ DAIN/ Predict_motion/), runs
 Evaluator.evaluate_from_folder twice (the first run also builds launch plans) and prints the
@@ -14,7 +14,9 @@ frame per frame (gt/) and measures every generated frame against it (evaluate_fr
 under the mask drawn from each frame's pose (pose_mask=True), so that the cost of either can be read off two runs.  --panels also composes the six-pane diagnostic sheet of every frame and
 writes the clip's Motion-JPEG video (evaluate_from_folder(panels=True)); --panel-encode says where its JPEG frames are encoded.
 --video also writes the frames themselves as <clip>_video.avi (video=True: rib_jpeg_float on the lane's stream); --frames none
-writes only that video (frames="none": no PNG is encoded, the PNG level then plays no part).
+writes only that video (frames="none": no PNG is encoded, the PNG level then plays no part).  --poses keyframes runs stage 1
+in the driver (poses="keyframes": a seed-defined motion transformer interpolates the key frames' poses of key_poses/, no json is
+read per frame; --rate must then be a power of two); the per-clip event time of stage 1 plus the bridge is reported too.
 """
 import argparse, json, os, sys, tempfile, time
 import numpy as np, torch
@@ -50,6 +52,10 @@ def write_clip(root, n_key, rate, H, W, src_h=0, src_w=0, gt=False):
                            "hand_left_keypoints_2d": hand(lm[17]), "hand_right_keypoints_2d": hand(lm[18])}]}
         with open(os.path.join(root, "Predict_motion", "clip", "f%04d_keypoints.json" % i), "w") as f:
             json.dump(doc, f)
+        if i % rate == 0:                     # the key frames' detections: what poses="keyframes" starts from
+            os.makedirs(os.path.join(root, "key_poses", "clip"), exist_ok=True)
+            with open(os.path.join(root, "key_poses", "clip", "%04d_keypoints.json" % (i // rate)), "w") as f:
+                json.dump(doc, f)
     return n
 
 
@@ -79,7 +85,11 @@ def main():
                     help="'mci': the background frames are interpolated on the GPU from the key frames and the clip's DAIN folder is not read (background=...)")
     ap.add_argument("--video", action="store_true", help="also write the frames as <clip>_video.avi, JPEG-encoded on the GPU (video=True)")
     ap.add_argument("--frames", default="png", choices=("png", "none"), help="with --video: 'none' writes no PNG frames (frames=...)")
+    ap.add_argument("--poses", default="folder", choices=("folder", "keyframes"),
+                    help="'keyframes': the motion transformer interpolates the key frames' poses inside the driver (poses=...)")
     a = ap.parse_args()
+    if a.poses == "keyframes" and a.rate & (a.rate - 1):
+        ap.error("--poses keyframes needs a power-of-two --rate")
     if a.frames == "none" and not a.video:
         ap.error("--frames none is a setting of --video")
     if a.background == "mci" and a.resize_on == "gpu":
@@ -100,12 +110,29 @@ def main():
         dirs = [os.path.join(root, d) for d in ("inputs", "DAIN", "Predict_motion")]
         if a.background == "mci":
             dirs[1] = None
+        kw, stage1_ms = {}, None
+        if a.poses == "keyframes":
+            from render_in_between_amd.motion import model as mmodel, pose_io, synth as msynth
+            from render_in_between_amd.motion.spec import MotionSpec
+            mspec = MotionSpec()
+            tr = mmodel.MotionTransformer(mspec)
+            tr.load_state_dict(msynth.make_state_dict(mspec, 0))
+            motion = mmodel.ModelInference(mmodel.PositionEmbeddingSine1D(mspec.pos_hidden_dim // 2, normalize=True), tr,
+                                           dataset=pose_io.OpenPoseClips({}))
+            dirs[2] = None
+            kw = dict(poses="keyframes", key_pose_dir=os.path.join(root, "key_poses"), upsample_rate=a.rate, motion=motion)
+            motion.interpolate_clip(os.path.join(root, "key_poses", "clip"), a.rate)            # warm
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            motion.interpolate_clip(os.path.join(root, "key_poses", "clip"), a.rate)
+            e1.record(); e1.synchronize()
+            stage1_ms = e0.elapsed_time(e1)     # host reading of the key-pose files included: the events bracket the whole call
         walls = []
         for rep in range(1 + a.reps):           # the first run also builds launch plans and pools: not counted
             t0 = time.perf_counter()
             out = E.evaluate_from_folder(G, *dirs, os.path.join(root, "out%d" % rep), gt_dir=os.path.join(root, "gt") if a.metrics else None,
                                          metrics=a.metrics, pose_mask=a.pose_mask, panels=a.panels, panel_encode=a.panel_encode,
-                                         background=a.background, video=a.video, frames=a.frames)
+                                         background=a.background, video=a.video, frames=a.frames, **kw)
             torch.cuda.synchronize()
             walls.append(time.perf_counter() - t0)
         tm = dict(E.timings)
@@ -117,7 +144,7 @@ def main():
                       "cpus": len(os.sched_getaffinity(0)), "cpu_budget": ev.cpu_budget(), "png_compress_level": a.compress,
                       "src_height": a.src_height or H, "src_width": a.src_width or W, "resize_on": a.resize_on, "background": a.background,
                       "metrics": a.metrics, "pose_mask": a.pose_mask, "metrics_overall": overall, "panels": a.panels, "panel_encode": a.panel_encode,
-                      "video": a.video, "frames_written": a.frames,
+                      "video": a.video, "frames_written": a.frames, "poses": a.poses, "stage1_plus_bridge_ms_per_clip": stage1_ms,
                       "wall_s": wall, "wall_s_runs": [round(w, 4) for w in walls[1:]], "frames_per_s_end_to_end": n / wall,
                       "phase_s_last_run": {k: round(v, 4) for k, v in tm.items() if k not in ("frames", "units", "timeline", "peak_units_in_flight")},
                       "peak_units_in_flight": tm.get("peak_units_in_flight"),
