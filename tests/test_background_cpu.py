@@ -225,6 +225,148 @@ def test_320x480_pair_on_the_host():
     assert dt < 60.0
 
 
+# ---- inputs for the rare branches (tests/test_gpu_mci_edges.py runs the kernels on them) ----------------------------------------
+# Smooth textures almost never give two candidates one cost, move by a few pixels and are a few blocks large; the kernels'
+# tie order, their 6-bit displacement fields and far-clamped windows, their loops' second passes and their clamps on frames
+# smaller than a tile then never decide a result.  These builders make inputs on which they do, and
+# test_the_inputs_reach_the_rare_branches holds the builders to that with the definition alone.
+TIE_KINDS = ("stripes16", "checker8", "checker8_low", "stripes4", "checker2", "diagonal16", "antidiagonal16", "flat")
+TIE_SIZES = [(67, 93), (40, 56)]
+LONG_MOTIONS = [(38, 0), (-38, 36), (0, -38), (30, 30)]          # (dx, dy) px between the key frames; 38 is outside the +-32 px search
+LONG_SIZES = [(96, 160), (67, 93)]
+WIDE_SIZES = [(8, 2056), (5, 1030), (16, 4100)]                  # W > 1024: the strip loop's second pass; W % 4 = 0, 2, 0
+TINY_SIZES = [(1, 1), (3, 5), (7, 9), (8, 8), (9, 33), (31, 17), (33, 15), (1, 40), (40, 1)]
+
+
+def _grey(plane):
+    return np.ascontiguousarray(np.repeat(np.asarray(plane, np.uint8)[..., None], 3, 2))
+
+
+def tie_pair(kind, h, w):
+    """A periodic pattern and the same pattern shifted by half a period: many displacements match equally well."""
+    Y, X = np.mgrid[0:h, 0:w]
+    if kind == "stripes16":
+        f = lambda o: ((X + o) % 16 < 8) * 255
+        return _grey(f(0)), _grey(f(8))
+    if kind in ("checker8", "checker8_low"):
+        lo, hi = (0, 255) if kind == "checker8" else (100, 106)
+        f = lambda o: np.where((((X + o) >> 3) + (Y >> 3)) & 1, hi, lo)
+        return _grey(f(0)), _grey(f(8))
+    if kind == "stripes4":
+        f = lambda o: ((X + o) % 4 < 2) * 255
+        return _grey(f(0)), _grey(f(2))
+    if kind == "checker2":
+        f = lambda o: ((((X + o) >> 1) + (Y >> 1)) & 1) * 255
+        return _grey(f(0)), _grey(f(2))
+    if kind == "diagonal16":
+        f = lambda o: ((X + Y + o) % 16 < 8) * 200
+        return _grey(f(0)), _grey(f(8))
+    if kind == "antidiagonal16":
+        f = lambda o: ((X - Y + o) % 16 < 8) * 200
+        return _grey(f(0)), _grey(f(8))
+    if kind == "flat":
+        return np.full((h, w, 3), 90, np.uint8), np.full((h, w, 3), 200, np.uint8)
+    raise ValueError(kind)
+
+
+def tie_shares(a, b):
+    """Per level (2, 1, 0): the share of blocks whose minimal cost is reached by two or more candidates, so that the lower
+    fields of the packed key decide the winner.  The candidates are those of block_field_levels."""
+    pa, pb = bg.pyramid(bg.luma(a)), bg.pyramid(bg.luma(b))
+    levels = bg.block_field_levels(a, b)
+    shares = []
+    for i, lvl in enumerate(range(bg.LEVELS - 1, -1, -1)):
+        Hb, Wb = bg.field_shape(*pa[lvl].shape)
+        if i == 0:
+            sx = sy = np.zeros((Hb, Wb), np.int32)
+            radius = bg.SEARCH_TOP
+        else:
+            by, bx = np.arange(Hb) >> 1, np.arange(Wb) >> 1
+            sx, sy = 2 * levels[i - 1][0][by][:, bx], 2 * levels[i - 1][1][by][:, bx]
+            radius = bg.REFINE
+        costs = np.stack([bg.block_cost(pa[lvl], pb[lvl], sx + ddx, sy + ddy)
+                          for ddy in range(-radius, radius + 1) for ddx in range(-radius, radius + 1)])
+        shares.append(float(((costs == costs.min(0)).sum(0) >= 2).mean()))
+    return shares
+
+
+def last_candidate_shares(a, b):
+    """Levels 1 and 0: the share of blocks won by start + (1, 1), the last of the nine candidates - in k_mci_search<1> the only
+    one whose lanes lie in the wave's upper half."""
+    levels = bg.block_field_levels(a, b)
+    shares = []
+    for i in (1, 2):
+        (dx, dy), (cx, cy) = levels[i], levels[i - 1]
+        by, bx = np.arange(dx.shape[0]) >> 1, np.arange(dx.shape[1]) >> 1
+        shares.append(float(((dx - 2 * cx[by][:, bx] == 1) & (dy - 2 * cy[by][:, bx] == 1)).mean()))
+    return shares
+
+
+def moving_pair(h, w, dx, dy, seed):
+    """Two crops of one smooth texture, the second displaced by (dx, dy) px."""
+    m = max(abs(dx), abs(dy), 1)
+    tex = texture(h + 2 * m, w + 2 * m, seed)
+    a = tex[m:m + h, m:m + w]
+    b = tex[m - dy:m - dy + h, m - dx:m - dx + w]
+    return np.ascontiguousarray(a), np.ascontiguousarray(b)
+
+
+def long_pair(h, w, i):
+    dx, dy = LONG_MOTIONS[i]
+    return moving_pair(h, w, dx, dy, 20 + i)
+
+
+def wide_pair(h, w):
+    return moving_pair(h, w, 10, -2, 30 + h)
+
+
+def random_pair(h, w, seed):
+    """Unrelated random content in A and B."""
+    rng = np.random.default_rng([seed, h, w])
+    return rng.integers(0, 256, (h, w, 3), dtype=np.uint8), rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+
+
+def test_the_inputs_reach_the_rare_branches():
+    # ties: every level has an input on which a fifth of the blocks or more are decided by the key's lower fields
+    h, w = TIE_SIZES[0]
+    shares = {}
+    for kind in TIE_KINDS:
+        a, b = tie_pair(kind, h, w)
+        assert a.shape == b.shape == (h, w, 3) and a.dtype == b.dtype == np.uint8
+        shares[kind] = tie_shares(a, b)
+        print("ties %-14s levels 2, 1, 0: %.2f %.2f %.2f" % ((kind,) + tuple(shares[kind])))
+        if kind == "flat":                                              # LAMBDA's term makes d = 0 unique
+            assert shares[kind] == [0.0, 0.0, 0.0] and not bg.mci_field_host(a, b).any()
+    for i in range(bg.LEVELS):
+        assert max(s[i] for s in shares.values()) >= 0.2, (i, shares)
+    for kind in ("stripes16", "checker8", "checker8_low"):
+        assert shares[kind][0] == 1.0, (kind, shares[kind])
+    assert any(bg.mci_field_host(*tie_pair(kind, h, w)).any() for kind in TIE_KINDS)
+    # ... and on one of them the last candidate wins a fifth of the blocks of levels 1 and 0 (on the others it never wins)
+    last = last_candidate_shares(*tie_pair("antidiagonal16", h, w))
+    print("ties antidiagonal16: start + (1, 1) wins %.2f %.2f of the blocks of levels 1, 0" % tuple(last))
+    assert min(last) >= 0.2 and min(shares["antidiagonal16"]) >= 0.2
+    # long vectors: both signs of the largest displacement in both components, and many blocks near it
+    h, w = LONG_SIZES[0]
+    fields = [bg.mci_field_host(*long_pair(h, w, i)) for i in range(len(LONG_MOTIONS))]
+    for i, f in enumerate(fields):
+        print("long %-10s dx %d..%d dy %d..%d, share of |d| >= 16: %.2f"
+              % (LONG_MOTIONS[i], f[..., 0].min(), f[..., 0].max(), f[..., 1].min(), f[..., 1].max(), (np.abs(f).max(-1) >= 16).mean()))
+    allf = np.stack(fields)
+    assert np.abs(allf).max() == bg.MAX_DISP
+    for c in (0, 1):
+        assert allf[..., c].min() == -bg.MAX_DISP and allf[..., c].max() == bg.MAX_DISP, c
+    assert (np.abs(allf).max(-1) >= 16).mean() >= 0.2
+    # sizes: the field shapes, and a tiny frame whose field is not zero
+    moved = 0
+    for h, w in TINY_SIZES + WIDE_SIZES:
+        a, b = random_pair(h, w, 1) if (h, w) in TINY_SIZES else wide_pair(h, w)
+        f = bg.mci_field_host(a, b)
+        assert f.shape == bg.field_shape(h, w) + (2,) == ((h + 7) // 8, (w + 7) // 8, 2)
+        moved += bool(f.any()) and (h, w) in TINY_SIZES
+    assert moved >= 1
+
+
 # ---- the driver -----------------------------------------------------------------------------------------------------------------
 def _cfg():
     return rib.AttrDict(gen=rib.hsm_gen_config(**MID_CFG), model_height=32, model_width=48, gauss_sigma=5,
