@@ -40,6 +40,7 @@ from __future__ import annotations
 
 import collections
 import contextlib
+import math
 import os
 import time
 from concurrent.futures import ThreadPoolExecutor
@@ -218,6 +219,19 @@ def _shm_close_all():
         blk.close()
     _SHM_ALL.clear()
     _SHM_FREE.clear()
+
+
+def download_layout(sections):
+    """The layout of a unit's download buffer: sections = [(name, nbytes)] in buffer order ->
+    ({name: (offset, nbytes)}, total bytes).  Every section starts on a multiple of 256 - any dtype may be viewed there, on
+    the device and in a shared block - and a section of no bytes is left out."""
+    table, end = {}, 0
+    for name, nbytes in sections:
+        if nbytes:
+            off = (end + 255) // 256 * 256
+            table[name] = (off, nbytes)
+            end = off + nbytes
+    return table, end
 
 
 def _process_pool(n):
@@ -1153,56 +1167,80 @@ class _FolderPipeline:
 
     # ---- stage 3: render -------------------------------------------------------------------------------------------------
     def render(self, clip, ui, g, st, lab, dn, gtd, ready):
-        """The unit's chain (evaluator.py:240-244,252: a segment starts from its key frame; inside it prev <- fused frame), the
-        quantiser and ONE asynchronous copy into page-locked host memory, all on the lane's stream.  Returns what the sink needs."""
-        gi, _, c0, _ = clip.units[ui]
+        """The unit's chain (evaluator.py:240-244,252: a segment starts from its key frame; inside it prev <- fused frame), then
+        everything the unit sends home - in ONE device buffer of named sections (download_layout; DESIGN 4e has the table),
+        filled by the quantiser, rib_quality, rib_panel and the two JPEG encoders, each under its option - and ONE asynchronous
+        copy into page-locked host memory, all on the lane's stream.  Returns the record the sink reads: the same keys for
+        every unit, None where the unit has no such section."""
+        gi, members, c0, _ = clip.units[ui]
         with torch.cuda.stream(st):
             st.wait_event(ready)
             imgs, masks, fz = g.chain(gtd if c0 == 0 else clip.prev_of[gi], lab, dn, want_all=self.panels)      # fz [Tc,B,3,H,W]
             clip.prev_of[gi] = fz[-1]
-            if self.panels:
-                return self._render_panels(clip, ui, g, st, imgs, masks, fz, lab, dn, gtd)
+            t0 = time.perf_counter()
+            n, H, W = fz.shape[0] * fz.shape[1], fz.shape[3], fz.shape[4]
+            frames = fz.reshape(n, 3, H, W)
+            gtp, klab, kdn, keys, dnp = clip.pan.pop(ui) if self.panels else (None,) * 5
+            nk = kdn.shape[0] if kdn is not None else 0          # panels: a first chunk also draws the key frames it starts from
+            SH, SW = self.sheet_hw if self.panels else (0, 0)
+            home = self.panels and (not self.jpeg_gpu or self.panel_frames)     # the raw sheets travel home
+            spec = (("frames", torch.uint8, (n, H, W, 3), self.write_png),
+                    ("qual", torch.float32, (4, n), clip.measure),       # OURS PSNR, OURS SSIM, DAIN PSNR, DAIN SSIM
+                    ("sheet_len", torch.int32, (n + nk,), self.jpeg_gpu),        # (jpeg_gpu implies panels)
+                    ("video_len", torch.int32, (self.video_count(clip, ui),), self.video),
+                    ("sheets", torch.uint8, (n + nk, SH, SW, 3), home))
+            table, total = download_layout([(name, math.prod(shape) * dtype.itemsize if on else 0) for name, dtype, shape, on in spec])
+            assert total, "a unit sends something home: frames, metrics, sheets or a video"
+
+            def sections(flat):                  # the typed views of a buffer laid out by `table`, on the device or on the host
+                views = dict.fromkeys(name for name, _, _, _ in spec)
+                for name, dtype, shape, _ in spec:
+                    if name in table:
+                        off, nbytes = table[name]
+                        views[name] = flat[off:off + nbytes].view(dtype).view(shape)
+                return views
+            buf = torch.empty(total, dtype=torch.uint8, device=g.device)
+            dev = sections(buf)
+            keep = [fz, lab, dn, gtd, buf]
+            if self.write_png:
+                g.quantise(frames, out=dev["frames"])
             if clip.measure:
-                return self._render_measured(clip, ui, g, st, fz, lab, dn, gtd)
+                gtf, mk = clip.meas.pop(ui)
+                g.quality(frames, gtf, mk, out=dev["qual"][0:2])
+                g.quality(dn.reshape(n, 3, H, W), gtf, mk, out=dev["qual"][2:4])
+                keep += [gtf, mk]
+            jpeg = vid = None
+            if self.panels:                      # under panel_encode="gpu" without panel_frames the sheets stay on the device
+                sheets = dev["sheets"] if home else torch.empty((n + nk, SH, SW, 3), dtype=torch.uint8, device=g.device)
+                g.panel(imgs.reshape(n, 3, H, W), masks.reshape(n, 1, H, W), frames, dnp, gtp, lab.reshape(n, *lab.shape[2:]),
+                        titles=self.titles_dev, out=sheets[:n])
+                if nk:
+                    g.panel(None, None, None, kdn, keys, klab, titles=self.titles_dev, out=sheets[n:])
+                keep += [imgs, masks, gtp, klab, kdn, keys, dnp]
+                if self.jpeg_gpu:
+                    jpeg = self.encode_jpeg(g, sheets, dev["sheet_len"])
+                    keep += [sheets, jpeg]
             if self.video:
-                return self._render_video(clip, ui, g, st, fz, lab, dn, gtd)
-            q = g.quantise(fz.reshape(-1, *fz.shape[2:]))                  # [Tc*B,H,W,3] uint8
-            out_blk = _shm_get(q.numel()) if self.procs is not None else None       # shared with the encode workers, page-locked
-            pinned = out_blk.t[:q.numel()].view(q.shape) if out_blk is not None else torch.empty(q.shape, dtype=torch.uint8, pin_memory=True)
-            pinned.copy_(q, non_blocking=True)
+                vid = self.encode_video(clip, ui, g, frames, gtd, dev["video_len"])
+                keep += [vid]
+            out_blk = _shm_get(total) if self.procs is not None else None       # shared with the encode workers, page-locked
+            flat = out_blk.t[:total] if out_blk is not None else torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            flat.copy_(buf, non_blocking=True)
             done = torch.cuda.Event()
             done.record(st)
-        return {"done": done, "pinned": pinned, "out_blk": out_blk, "keep": (fz, q, lab, dn, gtd)}
-
-    def _render_measured(self, clip, ui, g, st, fz, lab, dn, gtd):
-        """render() of a measured unit (on the lane's stream, inside its stream context): the quantised frames and the
-        per-frame metrics - rib_quality of the fused frames and of the DAIN frames against the GT frames - share one device
-        buffer, [uint8 frames | float32 [4, Tc*B]: OURS PSNR, OURS SSIM, DAIN PSNR, DAIN SSIM], and come home in the unit's
-        one device-to-host copy."""
-        t0 = time.perf_counter()
-        n = fz.shape[0] * fz.shape[1]
-        frames = fz.reshape(n, *fz.shape[2:])
-        nq = frames.numel() if self.write_png else 0                     # uint8 bytes of the quantised frames (frames="none": none)
-        off = (nq + 255) // 256 * 256
-        off_w = off + 4 * n * 4                                          # video: the int32 lengths of the frames' (and keys') files
-        nv = self.video_count(clip, ui)
-        total = off_w + 4 * nv
-        buf = torch.empty(total, dtype=torch.uint8, device=g.device)
-        q = g.quantise(frames, out=buf[:nq].view(n, frames.shape[2], frames.shape[3], frames.shape[1])) if self.write_png else None
-        vals = buf[off:off_w].view(torch.float32).view(4, n)
-        gtf, mk = clip.meas.pop(ui)
-        g.quality(frames, gtf, mk, out=vals[0:2])
-        g.quality(dn.reshape(n, *dn.shape[2:]), gtf, mk, out=vals[2:4])
-        vid = self.encode_video(clip, ui, g, frames, gtd, buf[off_w:].view(torch.int32)) if self.video else None
-        out_blk = _shm_get(total) if self.procs is not None else None
-        flat = out_blk.t[:total] if out_blk is not None else torch.empty(total, dtype=torch.uint8, pin_memory=True)
-        flat.copy_(buf, non_blocking=True)
-        done = torch.cuda.Event()
-        done.record(st)
-        self.tm["metrics"] += time.perf_counter() - t0
-        return {"done": done, "pinned": flat[:nq].view(q.shape) if q is not None else None, "out_blk": out_blk,
-                "keep": (fz, q, lab, dn, gtd, buf, gtf, mk, vid), "qual": flat[off:off_w].view(torch.float32).view(4, n),
-                "video": vid + (flat[off_w:total].view(torch.int32),) if vid else None}
+            if self.panels:
+                self.tm["panels"] = self.tm.get("panels", 0.0) + time.perf_counter() - t0
+            elif clip.measure:
+                self.tm["metrics"] += time.perf_counter() - t0
+        host = sections(flat)
+        # the files of the two encoders stay on the device until the sink knows their lengths: (files, cap, lengths on the host)
+        # frames_off / sheets_off: where the file workers find those two sections in the shared block
+        return {"done": done, "out_blk": out_blk, "keep": tuple(keep),
+                "frames": host["frames"], "qual": host["qual"], "sheets": host["sheets"],
+                "frames_off": table["frames"][0] if "frames" in table else None,
+                "sheets_off": table["sheets"][0] if "sheets" in table else None,
+                "jpeg": jpeg + (host["sheet_len"],) if jpeg else None, "video": vid + (host["video_len"],) if vid else None,
+                "sheet_frames": clip.unit_frames(ui) + ([clip.segs[si][0] for si in members] if nk else []) if self.panels else None}
 
     def video_count(self, clip, ui):
         """video: the files a unit encodes - its frames and, in a first chunk, the key frames it starts from (else 0)."""
@@ -1228,86 +1266,6 @@ class _FolderPipeline:
         if nk:
             g.jpeg_f32_into(gtd.to(torch.float32).contiguous(), files[n * cap:], lengths[n:], self.video_quality, cap)
         return files, cap
-
-    def _render_video(self, clip, ui, g, st, fz, lab, dn, gtd):
-        """render() of a plain unit under video=True (on the lane's stream, inside its stream context): one device buffer,
-        [uint8 frames (not under frames="none") | int32 file lengths [Tc*B + keys]], filled by the quantiser and rib_jpeg_float
-        and brought home in the unit's one copy; the files stay on the device until the sink knows their lengths."""
-        n = fz.shape[0] * fz.shape[1]
-        H, W = fz.shape[3], fz.shape[4]
-        frames = fz.reshape(n, 3, H, W)
-        nq = frames.numel() if self.write_png else 0
-        off_w = (nq + 255) // 256 * 256
-        total = off_w + 4 * self.video_count(clip, ui)
-        buf = torch.empty(total, dtype=torch.uint8, device=g.device)
-        q = g.quantise(frames, out=buf[:nq].view(n, H, W, 3)) if self.write_png else None
-        vid = self.encode_video(clip, ui, g, frames, gtd, buf[off_w:].view(torch.int32))
-        out_blk = _shm_get(total) if self.procs is not None else None
-        flat = out_blk.t[:total] if out_blk is not None else torch.empty(total, dtype=torch.uint8, pin_memory=True)
-        flat.copy_(buf, non_blocking=True)
-        done = torch.cuda.Event()
-        done.record(st)
-        return {"done": done, "pinned": flat[:nq].view(n, H, W, 3) if q is not None else None, "out_blk": out_blk,
-                "keep": (fz, q, lab, dn, gtd, buf, vid), "video": vid + (flat[off_w:total].view(torch.int32),)}
-
-    def _render_panels(self, clip, ui, g, st, imgs, masks, fz, lab, dn, gtd):
-        """render() of a unit under panels=True (on the lane's stream, inside its stream context): one device buffer,
-        [uint8 frames | float32 [4, Tc*B] metrics (measured units) | uint8 sheets [Tc*B + keys, SH, SW, 3]], filled by the
-        quantiser, rib_quality and rib_panel - one launch for the unit's frames and, in a first chunk, one in key-frame mode for
-        the key frames the unit starts from - and brought home in the unit's one device-to-host copy.
-        panel_encode="gpu": rib_jpeg encodes the sheets right there; the buffer carries [.. | int32 file lengths [Tc*B + keys]]
-        in the sheets' place (and the sheets behind them only under panel_frames), the files stay on the device until the
-        unit's sink knows their lengths (fetch_jpeg)."""
-        t0 = time.perf_counter()
-        n = fz.shape[0] * fz.shape[1]
-        H, W = fz.shape[3], fz.shape[4]
-        frames = fz.reshape(n, 3, H, W)
-        nq = frames.numel() if self.write_png else 0
-        SH, SW = self.sheet_hw
-        gtp, klab, kdn, keys, dnp = clip.pan.pop(ui)
-        nk = kdn.shape[0] if kdn is not None else 0
-        off_v = (nq + 255) // 256 * 256
-        off_l = (off_v + (4 * n * 4 if clip.measure else 0) + 255) // 256 * 256
-        off_w = off_l + ((4 * (n + nk) + 255) // 256 * 256 if self.jpeg_gpu else 0)      # video: the lengths of the frames' files
-        nv = self.video_count(clip, ui)
-        off_s = off_w + (4 * nv + 255) // 256 * 256
-        home = not self.jpeg_gpu or self.panel_frames        # the raw sheets travel home
-        total = off_s + ((n + nk) * SH * SW * 3 if home else 0)
-        buf = torch.empty(total, dtype=torch.uint8, device=g.device)
-        q = g.quantise(frames, out=buf[:nq].view(n, H, W, 3)) if self.write_png else None
-        keep = [fz, imgs, masks, q, lab, dn, gtd, buf, gtp, klab, kdn, keys, dnp]
-        if clip.measure:
-            vals = buf[off_v:off_v + 16 * n].view(torch.float32).view(4, n)
-            gtm, mk = clip.meas.pop(ui)
-            g.quality(frames, gtm, mk, out=vals[0:2])
-            g.quality(dn.reshape(n, 3, H, W), gtm, mk, out=vals[2:4])
-            keep += [gtm, mk]
-        sheets = buf[off_s:].view(n + nk, SH, SW, 3) if home else torch.empty((n + nk, SH, SW, 3), dtype=torch.uint8, device=g.device)
-        g.panel(imgs.reshape(n, 3, H, W), masks.reshape(n, 1, H, W), frames, dnp, gtp, lab.reshape(n, *lab.shape[2:]),
-                titles=self.titles_dev, out=sheets[:n])
-        if nk:
-            g.panel(None, None, None, kdn, keys, klab, titles=self.titles_dev, out=sheets[n:])
-        jpeg = None
-        if self.jpeg_gpu:
-            jpeg = self.encode_jpeg(g, sheets, buf[off_l:off_l + 4 * (n + nk)].view(torch.int32))
-            keep += [sheets, jpeg]
-        vid = None
-        if self.video:
-            vid = self.encode_video(clip, ui, g, frames, gtd, buf[off_w:off_w + 4 * nv].view(torch.int32))
-            keep += [vid]
-        out_blk = _shm_get(total) if self.procs is not None else None
-        flat = out_blk.t[:total] if out_blk is not None else torch.empty(total, dtype=torch.uint8, pin_memory=True)
-        flat.copy_(buf, non_blocking=True)
-        done = torch.cuda.Event()
-        done.record(st)
-        self.tm["panels"] = self.tm.get("panels", 0.0) + time.perf_counter() - t0
-        _, members, c0, _ = clip.units[ui]
-        return {"done": done, "pinned": flat[:nq].view(q.shape) if q is not None else None, "out_blk": out_blk, "keep": tuple(keep),
-                "video": vid + (flat[off_w:off_w + 4 * nv].view(torch.int32),) if vid else None,
-                "qual": flat[off_v:off_v + 16 * n].view(torch.float32).view(4, n) if clip.measure else None,
-                "sheets": flat[off_s:].view(n + nk, SH, SW, 3) if home else None, "sheet_off": off_s,
-                "jpeg": jpeg + (flat[off_l:off_l + 4 * (n + nk)].view(torch.int32),) if jpeg else None,
-                "sheet_frames": clip.unit_frames(ui) + ([clip.segs[si][0] for si in members] if nk else [])}
 
     def save_sheets(self, clip, frames, sheets, out_blk=None, off=0):
         """Submits the encodes of the sheets of `frames` (uint8 [n, SH, SW, 3] on the host; out_blk: the shared block they lie
@@ -1439,8 +1397,8 @@ class _FolderPipeline:
         # per unit: inputs decoded, launches enqueued, results on the host, files written (seconds since the call began)
         mark = [round(t_loaded, 4), round(t_enq, 4), round(time.perf_counter() - self.t_wall, 4)]
         self.tm.setdefault("timeline", []).append(mark)
-        if r.get("qual") is not None:           # the unit's per-frame metrics rode in the same copy
-            self.record(clip, out_frames, r.pop("qual").numpy().astype(np.float64))
+        if r["qual"] is not None:               # the unit's per-frame metrics rode in the same copy
+            self.record(clip, out_frames, r["qual"].numpy().astype(np.float64))
         in_blk = clip.stage_blk.pop(ui, None)
         clip.stage.pop(ui, None)                # (the views of the block go before the block does)
         clip.stage_gt.pop(ui, None)
@@ -1451,36 +1409,25 @@ class _FolderPipeline:
             _shm_put(in_blk)
         out_blk = r["out_blk"]
         # panels: the JPEG (and PNG) encodes of the unit's sheets fan out beside the PNG encodes of its frames
-        sheet_fs = self.save_sheets(clip, r["sheet_frames"], r["sheets"], out_blk, r["sheet_off"]) if r.get("sheets") is not None else []
-        jpeg = r.pop("jpeg", None)              # panel_encode="gpu": the files' bytes come home now that their lengths have,
-                                                # while the workers encode the PNGs
-        vid = r.pop("video", None)              # video: likewise the frames' own files
-        vres = None
+        sheet_fs = self.save_sheets(clip, r["sheet_frames"], r["sheets"], out_blk, r["sheets_off"]) if r["sheets"] is not None else []
+        fs = []
+        if self.write_png and out_blk is not None:      # the workers read frame j in the block, from the section's offset on
+            off, fsz = r["frames_off"], ev.height * ev.width * 3
+            fs = [self.procs.submit(io_worker.save_png_shm, out_blk.name, off + j * fsz, ev.height, ev.width, clip.names[out_frames[j]], self.level)
+                  for j in range(len(out_frames))]
+        elif self.write_png:
+            qn = r["frames"].numpy()
+            fs = [self.pool.submit(self.save_q, qn[j], clip.names[out_frames[j]]) for j in range(len(out_frames))]
+        # panel_encode="gpu" / video: the files' bytes come home now that their lengths have, while the workers encode the PNGs
+        if r["jpeg"] is not None:
+            self.fetch_jpeg(clip, r["sheet_frames"], r["jpeg"])
+        vres = self.fetch_jpeg(clip, self.video_frames_of(clip, ui), r["video"], video=True) if r["video"] is not None else None
+        res = [f.result(timeout=IO_TIMEOUT_S) for f in fs]
+        for f in sheet_fs:
+            f.result(timeout=IO_TIMEOUT_S)
+        r["frames"] = r["qual"] = r["sheets"] = r["jpeg"] = r["video"] = None       # (the views of the block go before the block does)
         if out_blk is not None:
-            fsz = ev.height * ev.width * 3
-            fs = [self.procs.submit(io_worker.save_png_shm, out_blk.name, j * fsz, ev.height, ev.width, clip.names[out_frames[j]], self.level)
-                  for j in range(len(out_frames))] if self.write_png else []
-            if jpeg is not None:
-                self.fetch_jpeg(clip, r["sheet_frames"], jpeg)
-            if vid is not None:
-                vres = self.fetch_jpeg(clip, self.video_frames_of(clip, ui), vid, video=True)
-            res = [f.result(timeout=IO_TIMEOUT_S) for f in fs]
-            for f in sheet_fs:
-                f.result(timeout=IO_TIMEOUT_S)
-            r["pinned"] = r["sheets"] = None
             _shm_put(out_blk)
-        else:
-            saves = []
-            if self.write_png:
-                qn = r["pinned"].numpy()
-                saves = self.pool.map(lambda j: self.save_q(qn[j], clip.names[out_frames[j]]), range(len(out_frames)))
-            if jpeg is not None:
-                self.fetch_jpeg(clip, r["sheet_frames"], jpeg)
-            if vid is not None:
-                vres = self.fetch_jpeg(clip, self.video_frames_of(clip, ui), vid, video=True)
-            res = list(saves)
-            for f in sheet_fs:
-                f.result(timeout=IO_TIMEOUT_S)
         r["keep"] = None
         mark.append(round(time.perf_counter() - self.t_wall, 4))
         return res if self.write_png else vres      # frames="none": the .jpg names, the unit's frames and then its key frames

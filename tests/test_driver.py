@@ -363,3 +363,37 @@ def test_cpu_budget_is_positive_and_bounded_by_the_affinity_mask():
     assert 1 <= n <= len(os.sched_getaffinity(0))
     E = ev.Evaluator(rib.AttrDict(gen=rib.hsm_gen_config(**MID_CFG), model_height=32, model_width=48))
     assert 1 <= E.io_threads <= max(1, n - 1) or n == 1
+
+
+def test_download_layout_over_every_combination_of_sections():
+    """evaluator.download_layout, the one place where the offsets of a unit's download buffer are made: all 32
+    on/off combinations of the five sections at n = 3 frames + nk = 2 key frames of 32x48 and an odd sheet size.  Sections
+    start on multiples of 256, in table order, without overlap; `frames` is at 0; a section of no bytes is absent; the total
+    is the end of the last one; torch accepts the float32 / int32 views at those offsets."""
+    import itertools
+    n, nk, H, W, SH, SW = 3, 2, 32, 48, 107, 151
+    sizes = [("frames", n * H * W * 3), ("qual", 4 * n * 4), ("sheet_len", 4 * (n + nk)), ("video_len", 4 * (n + nk)),
+             ("sheets", (n + nk) * SH * SW * 3)]
+    assert all(nbytes % 256 for _, nbytes in sizes[1:])         # every section behind `frames` needs its padding
+    for on in itertools.product((False, True), repeat=5):
+        sections = [(name, nbytes if o else 0) for (name, nbytes), o in zip(sizes, on)]
+        table, total = ev.download_layout(sections)
+        assert list(table) == [name for (name, _), o in zip(sizes, on) if o], on
+        end = 0
+        for name, (off, nbytes) in table.items():
+            assert off % 256 == 0 and off >= end and nbytes == dict(sizes)[name] > 0, (on, name)
+            assert off - end < 256, (on, name)                  # padding only: no hole of a section's size
+            end = off + nbytes
+        assert total == end, on
+        if on[0]:
+            assert table["frames"][0] == 0
+        flat = torch.zeros(total, dtype=torch.uint8)
+        for name, dtype in (("qual", torch.float32), ("sheet_len", torch.int32), ("video_len", torch.int32)):
+            if name in table:
+                off, nbytes = table[name]
+                v = flat[off:off + nbytes].view(dtype)
+                assert v.numel() * 4 == nbytes
+                v.fill_(1)                                      # ... and a write through it stays inside the section
+                assert not flat[:off].any() and not flat[off + nbytes:].any() and bool((flat[off:off + nbytes].view(dtype) == 1).all())
+                flat.zero_()
+    assert ev.download_layout([]) == ({}, 0) and ev.download_layout([("qual", 0)]) == ({}, 0)
