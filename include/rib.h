@@ -279,15 +279,24 @@ int rib_jpeg_float(rib_handle* h, int T, int H, int W, const float* src_f32_nchw
 /* ---- motion-compensated interpolation (MCI) of a segment's two key frames: the folder driver's background="mci" ----
  * This project's interpolation, NOT DAIN (the reference reads one DAIN frame per output frame; DAIN is an external network with
  * its own CUDA ops): the generator was trained on DAIN backgrounds and the quality of this substitute on real footage has not
- * been measured.  background.py (mci_field_host, mci_frames_host) states both results in integers - luma, a three-level
- * pyramid, bilateral 8x8 block matching (full search over [-4,4]^2 at quarter size, i.e. +-32 px of motion between the key
- * frames; +-1 refinements at half and full size; the minimum of (cost, dx^2+dy^2, dy, dx)), a 3x3 median, a bilinear per-pixel
- * field in 1/256 px, two fixed-point bilinear samples and a blend - and the kernels are bit-equal to it.
+ * been measured.  background.py (mci_field_host, mci_frames_host) states both results in integers - luma, a pyramid of
+ * L = 3 levels, bilateral 8x8 block matching (full search over [-4,4]^2 on the top level - at quarter size, i.e. +-32 px of
+ * motion between the key frames; +-1 refinements on every level below; the minimum of (cost, dx^2+dy^2, dy, dx)), a 3x3 median,
+ * a bilinear per-pixel field in 1/256 px, two fixed-point bilinear samples and a blend - and the kernels are bit-equal to it.
+ * No occlusion reasoning, no sub-pel search.
  * rib_mci_field: a_u8, b_u8 uint8 NHWC [B,H,W,3] on the device (left and right key frame of B segments at the model size) ->
  * field_i16 int16 [B,Hb,Wb,2] on the device, (dx, dy) per 8x8 block of the intermediate frame (rib_mci_field_shape:
  * Hb = ceil(H/8), Wb = ceil(W/8)); once per segment.  workspace: rib_mci_workspace_bytes(h, B, H, W) bytes on the device, 16-byte
  * aligned, nothing to clear.  Five launches on `stream` (luma + pyramid, three searches, median), no atomics, no
  * synchronisation: a segment's field does not depend on B.
+ * rib_mci_field_levels / rib_mci_workspace_bytes_levels: the same with L = levels in 3, 4, 5 pyramid levels (the driver's
+ * --mci-range 32, 64, 128: the nominal range 4 * 2^(L-1) * 2 px between the key frames).  The field's components reach 19, 39 or
+ * 79, i.e. 38, 78 or 158 px of motion between the key frames; levels 3 and 4 of the pyramid come from the same launch as the
+ * others and each extra level adds one +-1 search: L + 2 launches (five, six, seven; an added launch took 6.7 - 7.3 us on an MI355X
+ * at 512x512, B = 4, the field 54 / 61 / 69 us of kernel time: profiles/r12_mci_range.txt), the same contracts otherwise.  A wider
+ * search has more room for a false match on periodic content.  rib_mci_field and rib_mci_workspace_bytes ARE levels = 3: the
+ * same workspace size, the same five launches.  levels outside 3..5: RIB_ERR_INVALID with a rib_last_error text, nothing
+ * launched (the size query returns 0).  rib_mci_frames takes the field of any L.
  * rib_mci_frames: frames k_first .. k_first + T - 1 (0 <= k <= sample_rate, a power of two <= 1024; k = 0 is A, k = sample_rate
  * is B) of all B segments in ONE launch: out_f32_nchw float32 [T,B,3,H,W], ((u8 / 255 - 0.5) / 0.5) exactly as the driver's
  * upload computes it (the arithmetic of rib_resize_cubic's float output), and / or out_u8_nhwc uint8 [T,B,H,W,3]; a NULL output
@@ -298,6 +307,9 @@ void rib_mci_field_shape(int H, int W, int* Hb, int* Wb);
 size_t rib_mci_workspace_bytes(rib_handle* h, int B, int H, int W);
 int rib_mci_field(rib_handle* h, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
                   void* workspace, void* hip_stream);
+size_t rib_mci_workspace_bytes_levels(rib_handle* h, int B, int H, int W, int levels);
+int rib_mci_field_levels(rib_handle* h, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
+                         int levels, void* workspace, void* hip_stream);
 int rib_mci_frames(rib_handle* h, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const int16_t* field_i16,
                    int sample_rate, int k_first, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream);
 

@@ -8,16 +8,20 @@ The two functions below ARE the definition; the HIP kernels (csrc/mci.hip.h: rib
 bit-equal to them (tests/test_gpu_mci.py).  Every step is integer or fixed point with a stated order and stated tie-breaks:
 
   luma       Y = (77 R + 150 G + 29 B + 128) >> 8.
-  pyramid    levels 0 (full), 1, 2; level l+1 is ceil(h/2) x ceil(w/2), a pixel is (the sum of its 2x2 parents, coordinates
-             clamped to the edge, + 2) >> 2.
+  pyramid    levels 0 (full) .. L-1, L = 3 unless asked otherwise (`levels`, below); level l+1 is ceil(h/2) x ceil(w/2), a pixel
+             is (the sum of its 2x2 parents, coordinates clamped to the edge, + 2) >> 2.
   matching   bilateral block matching: one displacement d = (dx, dy) per BLOCK x BLOCK block of the INTERMEDIATE frame's grid
              (so the field has no holes), cost(d) = sum over the block's pixels p inside the image of
              |Y_A(clamp(p - d)) - Y_B(clamp(p + d))| + LAMBDA * (|dx| + |dy|).
-  search     level 2: every d in [-SEARCH_TOP, SEARCH_TOP]^2 (+-4 at quarter size, i.e. +-32 px of motion between the key frames
-             at full size: faster motion falls outside the search); levels 1 and 0: start = twice the displacement of the coarser
-             block that holds this block's centre (block (by >> 1, bx >> 1)), candidates start + [-REFINE, REFINE]^2.  The winner
-             is the minimum of the tuple (cost, dx*dx + dy*dy, dy, dx) - packed into one integer (pack_key), so it does not
-             depend on the order of evaluation.
+  search     level L-1: every d in [-SEARCH_TOP, SEARCH_TOP]^2 (L = 3: +-4 at quarter size, i.e. +-32 px of motion between the
+             key frames at full size: faster motion falls outside the search); every level below: start = twice the displacement
+             of the coarser block that holds this block's centre (block (by >> 1, bx >> 1)), candidates
+             start + [-REFINE, REFINE]^2.  The winner is the minimum of the tuple (cost, dx*dx + dy*dy, dy, dx) - packed into one
+             integer (pack_key; pack_key_wide above three levels), so it does not depend on the order of evaluation.
+  levels     L in 3 (the default), 4, 5: the nominal range 4 * 2^(L-1) * 2 = 32, 64 or 128 px of motion between the key frames
+             (the driver's mci_range).  The level-0 field reaches max_disp(L) = 19, 39 or 79 in either component, i.e. 38, 78
+             or 158 px of motion.  Nothing else changes with L; a wider search has more room for a false match on periodic
+             content (LAMBDA only breaks near-ties).
   median     3x3 componentwise median over the level-0 block field, coordinates clamped at the border.
   per pixel  D(p): bilinear between the four nearest block centres (block b's centre is at 8 b + 3.5), block coordinates
              clamped at the border; the weights are exact in 1/16 per axis, so D is an exact integer in 1/256 px
@@ -34,14 +38,16 @@ from __future__ import annotations
 import numpy as np
 
 BLOCK = 8                 # block side, on every pyramid level
-LEVELS = 3                # pyramid levels 0..2
-SEARCH_TOP = 4            # level 2: full search over [-4, 4]^2
-REFINE = 1                # levels 1, 0: start + [-1, 1]^2
+LEVELS = 3                # pyramid levels 0..2: the default
+MIN_LEVELS, MAX_LEVELS = 3, 5             # `levels` of mci_field_host / block_field_levels
+SEARCH_TOP = 4            # the top level (2 by default): full search over [-4, 4]^2
+REFINE = 1                # every level below: start + [-1, 1]^2
 LAMBDA = 4                # cost of one pixel of |dx| + |dy| (a block's SAD is at most 64 * 255)
 FIELD_FRAC_BITS = 8       # D(p) in 1/256 px: 4 bits of bilinear weight per axis
 SAMPLE_FRAC_BITS = 8      # sampling positions in 1/256 px
 MAX_DISP = 2 * (2 * SEARCH_TOP + REFINE) + REFINE      # 19: the largest |dx|, |dy| of the level-0 field
 KEY_BIAS = 32             # pack_key: dy + 32, dx + 32 in 6 bits each (MAX_DISP < 32)
+WIDE_KEY_BIAS = 128       # pack_key_wide: dy + 128, dx + 128 in 8 bits each (max_disp(5) = 79 < 128)
 MAX_SAMPLE_RATE = 1024
 
 
@@ -65,9 +71,23 @@ def down2(y):
     return ((v[r0][:, c0] + v[r0][:, c1] + v[r1][:, c0] + v[r1][:, c1] + 2) >> 2).astype(np.uint8)
 
 
-def pyramid(y):
+def check_levels(levels, who):
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not MIN_LEVELS <= levels <= MAX_LEVELS:
+        raise ValueError("%s: levels must be %d..%d (a range of 32, 64 or 128 px), got %r" % (who, MIN_LEVELS, MAX_LEVELS, levels))
+    return int(levels)
+
+
+def max_disp(levels):
+    """The largest |dx|, |dy| the level-0 field of a `levels`-level search can hold: 19, 39, 79."""
+    d = SEARCH_TOP
+    for _ in range(check_levels(levels, "max_disp") - 1):
+        d = 2 * d + REFINE
+    return d
+
+
+def pyramid(y, levels=LEVELS):
     out = [y]
-    for _ in range(LEVELS - 1):
+    for _ in range(levels - 1):
         out.append(down2(out[-1]))
     return out
 
@@ -76,6 +96,20 @@ def pack_key(cost, dx, dy):
     """The tuple (cost, dx*dx + dy*dy, dy, dx) as one non-negative integer whose order is the tuple's order."""
     return (cost.astype(np.int64) << 22) | ((dx * dx + dy * dy).astype(np.int64) << 12) | ((dy + KEY_BIAS).astype(np.int64) << 6) \
         | (dx + KEY_BIAS).astype(np.int64)
+
+
+def pack_key_wide(cost, dx, dy):
+    """pack_key with room for max_disp(5): cost << 30 | (dx*dx + dy*dy) << 16 | (dy + 128) << 8 | (dx + 128), for
+    cost <= 64 * 255 + 4 * 158 < 2^15, dx*dx + dy*dy <= 2 * 79^2 = 12482 < 2^14 and |dx|, |dy| <= 79 < 128.  The same order: the
+    tuple's, so the same winner."""
+    return (cost.astype(np.int64) << 30) | ((dx * dx + dy * dy).astype(np.int64) << 16) | ((dy + WIDE_KEY_BIAS).astype(np.int64) << 8) \
+        | (dx + WIDE_KEY_BIAS).astype(np.int64)
+
+
+def unpack_key_wide(key):
+    """(cost, dx, dy) of a pack_key_wide key."""
+    key = np.asarray(key, np.int64)
+    return key >> 30, ((key & 255) - WIDE_KEY_BIAS).astype(np.int32), (((key >> 8) & 255) - WIDE_KEY_BIAS).astype(np.int32)
 
 
 def block_cost(ya, yb, dx, dy):
@@ -92,14 +126,18 @@ def block_cost(ya, yb, dx, dy):
     return sad.reshape(Hb, BLOCK, Wb, BLOCK).sum((1, 3)) + LAMBDA * (np.abs(dx) + np.abs(dy))
 
 
-def search(ya, yb, sx, sy, radius):
-    """The winner of start + [-radius, radius]^2 for every block: sx, sy int [Hb, Wb] -> (dx, dy) int32 [Hb, Wb]."""
+def search(ya, yb, sx, sy, radius, wide=False):
+    """The winner of start + [-radius, radius]^2 for every block: sx, sy int [Hb, Wb] -> (dx, dy) int32 [Hb, Wb].  wide: the
+    key is pack_key_wide (displacements beyond KEY_BIAS); the winner is the tuple's minimum either way."""
     best = None
+    pack = pack_key_wide if wide else pack_key
     for ddy in range(-radius, radius + 1):
         for ddx in range(-radius, radius + 1):
             dx, dy = sx + ddx, sy + ddy
-            key = pack_key(block_cost(ya, yb, dx, dy), dx, dy)
+            key = pack(block_cost(ya, yb, dx, dy), dx, dy)
             best = key if best is None else np.minimum(best, key)
+    if wide:
+        return unpack_key_wide(best)[1:]
     return ((best & 63) - KEY_BIAS).astype(np.int32), (((best >> 6) & 63) - KEY_BIAS).astype(np.int32)
 
 
@@ -111,12 +149,14 @@ def median3(f):
     return np.sort(nine, axis=0)[4]
 
 
-def block_field_levels(a_u8, b_u8):
-    """The block fields of levels 2, 1, 0 before the median: [(dx, dy)] coarse to fine (the tests look at them)."""
-    pa, pb = pyramid(luma(a_u8)), pyramid(luma(b_u8))
+def block_field_levels(a_u8, b_u8, levels=LEVELS):
+    """The block fields of levels L-1 .. 0 (L = levels: 3, 4 or 5) before the median: [(dx, dy)] coarse to fine (the tests look
+    at them)."""
+    levels = check_levels(levels, "block_field_levels")
+    pa, pb = pyramid(luma(a_u8), levels), pyramid(luma(b_u8), levels)
     out = []
     dx = dy = None
-    for lvl in range(LEVELS - 1, -1, -1):
+    for lvl in range(levels - 1, -1, -1):
         Hb, Wb = field_shape(*pa[lvl].shape)
         if dx is None:
             sx = sy = np.zeros((Hb, Wb), np.int32)
@@ -125,20 +165,22 @@ def block_field_levels(a_u8, b_u8):
             by, bx = np.arange(Hb) >> 1, np.arange(Wb) >> 1
             sx, sy = 2 * dx[by][:, bx], 2 * dy[by][:, bx]
             radius = REFINE
-        dx, dy = search(pa[lvl], pb[lvl], sx, sy, radius)
+        dx, dy = search(pa[lvl], pb[lvl], sx, sy, radius, wide=levels > LEVELS)
         out.append((dx, dy))
     return out
 
 
-def mci_field_host(a_u8, b_u8):
+def mci_field_host(a_u8, b_u8, levels=LEVELS):
     """The block displacement field of a key-frame pair: a_u8, b_u8 uint8 [H, W, 3] (left and right key frame at the model
     size) -> int16 [Hb, Wb, 2], [..., 0] = dx, [..., 1] = dy, in full-size pixels of HALF the motion between the key frames
-    (the intermediate frame's pixel p shows A's p - d and B's p + d)."""
+    (the intermediate frame's pixel p shows A's p - d and B's p + d).  levels: 3 (the default), 4 or 5 pyramid levels, i.e. a
+    search over 32, 64 or 128 px of motion between the key frames; |dx|, |dy| <= max_disp(levels)."""
+    levels = check_levels(levels, "mci_field_host")
     a_u8, b_u8 = np.asarray(a_u8), np.asarray(b_u8)
     if a_u8.dtype != np.uint8 or a_u8.ndim != 3 or a_u8.shape[2] != 3 or a_u8.shape != b_u8.shape or b_u8.dtype != np.uint8:
         raise ValueError("mci_field_host: two uint8 [H, W, 3] frames of one size, got %s %s and %s %s"
                          % (a_u8.dtype, a_u8.shape, b_u8.dtype, b_u8.shape))
-    dx, dy = block_field_levels(a_u8, b_u8)[-1]
+    dx, dy = block_field_levels(a_u8, b_u8, levels)[-1]
     return np.stack([median3(dx), median3(dy)], -1).astype(np.int16)
 
 

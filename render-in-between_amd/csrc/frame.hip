@@ -339,20 +339,21 @@ int rib_jpeg_float(rib_handle* handle, int T, int H, int W, const float* src_f32
                  int32_t* lengths, void* workspace, void* hip_stream) {
   return jpeg_enqueue<float>("rib_jpeg_float", handle, T, H, W, src_f32_nchw, quality, dst, dst_stride, lengths, workspace, hip_stream);
 }
-// rib_mci_*: the workspace of one (B, H, W) - the three luma levels of the 2B key frames and the block fields of levels 2, 1 and
-// 0 (before the median)
+// rib_mci_*: the workspace of one (B, H, W, levels) - the luma levels of the 2B key frames, then the block fields of the levels
+// (before the median); an extra level's plane and field follow those of the level below, so three levels lie where they lay
 namespace {
-struct MciLayout { int h[3], w[3], Hb[3], Wb[3]; size_t y[3], f[3], total; };
-static bool mci_layout(int B, int H, int W, MciLayout* L) {
+struct MciLayout { int h[MCI_MAX_LEVELS], w[MCI_MAX_LEVELS], Hb[MCI_MAX_LEVELS], Wb[MCI_MAX_LEVELS]; size_t y[MCI_MAX_LEVELS], f[MCI_MAX_LEVELS], total; };
+static bool mci_layout(int B, int H, int W, int levels, MciLayout* L) {
   if (B < 1 || B > 32767 || H < 1 || W < 1 || H > MCI_MAX_SIDE || W > MCI_MAX_SIDE) return false;
+  if (levels < MCI_MIN_LEVELS || levels > MCI_MAX_LEVELS) return false;
   size_t o = 0;
-  for (int l = 0; l < 3; ++l) {
+  for (int l = 0; l < levels; ++l) {
     L->h[l] = l ? (L->h[l - 1] + 1) / 2 : H; L->w[l] = l ? (L->w[l - 1] + 1) / 2 : W;
     L->Hb[l] = (L->h[l] + MCI_BLOCK - 1) / MCI_BLOCK; L->Wb[l] = (L->w[l] + MCI_BLOCK - 1) / MCI_BLOCK;
     L->y[l] = o; o += align256((size_t)2 * B * L->h[l] * L->w[l]);
   }
   if ((size_t)B * L->Hb[0] * L->Wb[0] > (size_t)INT32_MAX / 2) return false;      // block indices (and their (dx, dy) pairs) stay in int
-  for (int l = 0; l < 3; ++l) { L->f[l] = o; o += align256((size_t)B * L->Hb[l] * L->Wb[l] * 2 * sizeof(int16_t)); }
+  for (int l = 0; l < levels; ++l) { L->f[l] = o; o += align256((size_t)B * L->Hb[l] * L->Wb[l] * 2 * sizeof(int16_t)); }
   L->total = o;
   return true;
 }
@@ -363,20 +364,24 @@ void rib_mci_field_shape(int H, int W, int* Hb, int* Wb) {
   if (Wb) *Wb = W < 1 ? 0 : (W + MCI_BLOCK - 1) / MCI_BLOCK;
 }
 
-size_t rib_mci_workspace_bytes(rib_handle* h, int B, int H, int W) {
+size_t rib_mci_workspace_bytes_levels(rib_handle* h, int B, int H, int W, int levels) {
   MciLayout L;
-  if (!h || !mci_layout(B, H, W, &L)) return 0;
+  if (!h || !mci_layout(B, H, W, levels, &L)) return 0;
   return L.total;
 }
 
-int rib_mci_field(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
-                  void* workspace, void* hip_stream) {
+size_t rib_mci_workspace_bytes(rib_handle* h, int B, int H, int W) { return rib_mci_workspace_bytes_levels(h, B, H, W, MCI_MIN_LEVELS); }
+
+int rib_mci_field_levels(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
+                         int levels, void* workspace, void* hip_stream) {
   FrameState* h = frame_state(handle);
   if (!h) return RIB_ERR_INVALID;
   if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_mci_field: host-only handle");
   if (!a_u8 || !b_u8 || !field_i16 || !workspace) return fail(h, RIB_ERR_INVALID, "rib_mci_field: null pointer");
+  if (levels < MCI_MIN_LEVELS || levels > MCI_MAX_LEVELS)
+    return fail(h, RIB_ERR_INVALID, fmt("rib_mci_field: levels=%d: %d..%d pyramid levels (a search over 32, 64 or 128 px)", levels, MCI_MIN_LEVELS, MCI_MAX_LEVELS));
   MciLayout L;
-  if (!mci_layout(B, H, W, &L))
+  if (!mci_layout(B, H, W, levels, &L))
     return fail(h, RIB_ERR_INVALID, fmt("rib_mci_field: B=%d H=%d W=%d: 1 <= B <= 32767, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", B, H, W, MCI_MAX_SIDE));
   if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0 || (reinterpret_cast<uintptr_t>(field_i16) & 3) != 0)
     return fail(h, RIB_ERR_INVALID, "rib_mci_field: workspace must be 16-byte aligned, the field 4-byte aligned");
@@ -385,17 +390,20 @@ int rib_mci_field(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, 
   uint8_t* ws = static_cast<uint8_t*>(workspace);
   MciLumaParams lp;
   lp.a = a_u8; lp.b = b_u8; lp.y0 = ws + L.y[0]; lp.y1 = ws + L.y[1]; lp.y2 = ws + L.y[2];
+  lp.y3 = levels > 3 ? ws + L.y[3] : nullptr; lp.y4 = levels > 4 ? ws + L.y[4] : nullptr;
   lp.B = B; lp.H = H; lp.W = W; lp.h1 = L.h[1]; lp.w1 = L.w[1]; lp.h2 = L.h[2]; lp.w2 = L.w[2]; lp.tilesX = (W + 31) / 32;
+  lp.h3 = levels > 3 ? L.h[3] : 0; lp.w3 = levels > 3 ? L.w[3] : 0; lp.h4 = levels > 4 ? L.h[4] : 0; lp.w4 = levels > 4 ? L.w[4] : 0;
   hipLaunchKernelGGL(k_mci_luma_pyramid, dim3(lp.tilesX * ((H + 31) / 32), 2 * B), dim3(256), 0, st, lp);
   HIP_TRY(h, hipGetLastError());
-  for (int l = 2; l >= 0; --l) {
+  const int top = levels - 1;
+  for (int l = top; l >= 0; --l) {
     MciSearchParams sp;
-    sp.y = ws + L.y[l]; sp.coarse = l == 2 ? nullptr : reinterpret_cast<const int16_t*>(ws + L.f[l + 1]);
+    sp.y = ws + L.y[l]; sp.coarse = l == top ? nullptr : reinterpret_cast<const int16_t*>(ws + L.f[l + 1]);
     sp.out = reinterpret_cast<int16_t*>(ws + L.f[l]);
     sp.B = B; sp.h = L.h[l]; sp.w = L.w[l]; sp.Hb = L.Hb[l]; sp.Wb = L.Wb[l];
-    sp.Hbc = l == 2 ? 1 : L.Hb[l + 1]; sp.Wbc = l == 2 ? 1 : L.Wb[l + 1];
+    sp.Hbc = l == top ? 1 : L.Hb[l + 1]; sp.Wbc = l == top ? 1 : L.Wb[l + 1];
     const dim3 grid((sp.Hb * sp.Wb + MCI_RUN - 1) / MCI_RUN, B);
-    if (l == 2) hipLaunchKernelGGL(k_mci_search<MCI_TOP_R>, grid, dim3(256), 0, st, sp);
+    if (l == top) hipLaunchKernelGGL(k_mci_search<MCI_TOP_R>, grid, dim3(256), 0, st, sp);
     else hipLaunchKernelGGL(k_mci_search<1>, grid, dim3(256), 0, st, sp);
     HIP_TRY(h, hipGetLastError());
   }
@@ -406,6 +414,11 @@ int rib_mci_field(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, 
   return RIB_OK;
 }
 
+int rib_mci_field(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
+                  void* workspace, void* hip_stream) {
+  return rib_mci_field_levels(handle, B, H, W, a_u8, b_u8, field_i16, MCI_MIN_LEVELS, workspace, hip_stream);
+}
+
 int rib_mci_frames(rib_handle* handle, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const int16_t* field_i16,
                    int sample_rate, int k_first, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream) {
   FrameState* h = frame_state(handle);
@@ -414,7 +427,7 @@ int rib_mci_frames(rib_handle* handle, int T, int B, int H, int W, const uint8_t
   if (!a_u8 || !b_u8 || !field_i16) return fail(h, RIB_ERR_INVALID, "rib_mci_frames: null pointer");
   if (!out_f32_nchw && !out_u8_nhwc) return fail(h, RIB_ERR_INVALID, "rib_mci_frames: both outputs are null");
   MciLayout L;
-  if (T < 1 || !mci_layout(B, H, W, &L) || (size_t)T * B > 65535)
+  if (T < 1 || !mci_layout(B, H, W, MCI_MIN_LEVELS, &L) || (size_t)T * B > 65535)
     return fail(h, RIB_ERR_INVALID, fmt("rib_mci_frames: T=%d B=%d H=%d W=%d: T, B >= 1, T * B <= 65535, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", T, B, H, W, MCI_MAX_SIDE));
   if (sample_rate < 1 || sample_rate > MCI_MAX_RATE || (sample_rate & (sample_rate - 1)) != 0)
     return fail(h, RIB_ERR_INVALID, fmt("rib_mci_frames: sample_rate=%d: a power of two in 1..%d", sample_rate, MCI_MAX_RATE));

@@ -4,15 +4,18 @@
 // background.py (mci_field_host, mci_frames_host) states the result in integers; every kernel here is bit-equal to it.
 //
 //   k_mci_luma_pyramid  grid (tiles of 32 x 32, 2B): luma Y = (77 R + 150 G + 29 B + 128) >> 8 of one tile and, from LDS, its
-//                       16 x 16 of level 1 and 8 x 8 of level 2 ((2x2 parents, clamped, + 2) >> 2): aligned tiles nest, a
+//                       16 x 16 of level 1 and 8 x 8 of level 2 ((2x2 parents, clamped, + 2) >> 2) - and, where a wider search
+//                       wants them (y3, y4 not null), its 4 x 4 of level 3 and 2 x 2 of level 4: aligned tiles nest, a
 //                       clamped parent is the tile's own.  Image n < B is A[n], else B[n - B].
 //   k_mci_search<R>     grid (runs of MCI_RUN blocks, B): bilateral block matching of one pyramid level.  A workgroup owns a
 //                       run of MCI_RUN consecutive blocks; it stages, once, the two luma windows of every block - (8 + 2R)^2
 //                       bytes of A around p - start and of B around p + start, already clamped - in LDS; a wave then takes a
 //                       block, its lanes the candidates (R = 4: 81 candidates, one per lane in two passes; R = 1: 9
 //                       candidates x 4 row pairs, summed over the 4 lanes by shuffles), and the winner is the wave minimum
-//                       of the packed key (cost << 22 | dx^2 + dy^2 << 12 | dy + 32 << 6 | dx + 32): the order of the tuple
-//                       (cost, |d|^2, dy, dx), whatever the lane order.  No atomics.
+//                       of the packed key (background.pack_key_wide: cost << 30 | dx^2 + dy^2 << 16 | dy + 128 << 8 | dx + 128,
+//                       room for the +-79 of five levels): the order of the tuple (cost, |d|^2, dy, dx), whatever the lane
+//                       order - and whatever the layout, so three levels give background.pack_key's winners.  No atomics.
+//                       The top level of L (3, 4 or 5) runs <MCI_TOP_R> from start 0, every level below <1>.
 //   k_mci_median        3x3 componentwise median of the level-0 field, clamped.
 //   k_mci_frames        grid (H, T * B): a workgroup owns ONE row of one frame; a thread takes 4 consecutive x: D(p) bilinear
 //                       from the block field (exact, 1/256 px), the two fixed-point bilinear samples, the blend; float4 stores
@@ -26,19 +29,22 @@
 
 namespace rib {
 
-constexpr int MCI_BLOCK = 8, MCI_LAMBDA = 4, MCI_TOP_R = 4, MCI_KEY_BIAS = 32;      // background.py BLOCK, LAMBDA, SEARCH_TOP, KEY_BIAS
+constexpr int MCI_BLOCK = 8, MCI_LAMBDA = 4, MCI_TOP_R = 4, MCI_KEY_BIAS = 128;     // background.py BLOCK, LAMBDA, SEARCH_TOP, WIDE_KEY_BIAS
+constexpr int MCI_MIN_LEVELS = 3, MCI_MAX_LEVELS = 5;                               // background.py MIN_LEVELS, MAX_LEVELS
 constexpr int MCI_RUN = 8;                  // blocks per workgroup of k_mci_search
 constexpr int MCI_MAX_SIDE = 16384, MCI_MAX_RATE = 1024;
 
 struct MciLumaParams {
   const uint8_t *a, *b;                     // [B, H, W, 3]
-  uint8_t *y0, *y1, *y2;                    // [2B, h_l, w_l]
-  int B, H, W, h1, w1, h2, w2, tilesX;
+  uint8_t *y0, *y1, *y2, *y3, *y4;          // [2B, h_l, w_l]; y3, y4 null: not wanted (y4 only with y3)
+  int B, H, W, h1, w1, h2, w2, h3, w3, h4, w4, tilesX;
 };
 
 __global__ __launch_bounds__(256) void k_mci_luma_pyramid(MciLumaParams p) {
   __shared__ uint8_t s0[32][32];
   __shared__ uint8_t s1[16][16];
+  __shared__ uint8_t s2[8][8];
+  __shared__ uint8_t s3[4][4];
   const int tid = threadIdx.x, n = blockIdx.y;
   const int ty = blockIdx.x / p.tilesX, tx = blockIdx.x - ty * p.tilesX;
   const uint8_t* src = (n < p.B ? p.a + (size_t)n * p.H * p.W * 3 : p.b + (size_t)(n - p.B) * p.H * p.W * 3);
@@ -67,7 +73,29 @@ __global__ __launch_bounds__(256) void k_mci_luma_pyramid(MciLumaParams p) {
     const int ly = tid >> 3, lx = tid & 7, y = ty * 8 + ly, x = tx * 8 + lx;
     if (y < p.h2 && x < p.w2) {
       const int r0 = 2 * ly, r1 = min(2 * y + 1, p.h1 - 1) - ty * 16, c0 = 2 * lx, c1 = min(2 * x + 1, p.w1 - 1) - tx * 16;
-      p.y2[((size_t)n * p.h2 + y) * p.w2 + x] = (uint8_t)((s1[r0][c0] + s1[r0][c1] + s1[r1][c0] + s1[r1][c1] + 2) >> 2);
+      const uint8_t v = (uint8_t)((s1[r0][c0] + s1[r0][c1] + s1[r1][c0] + s1[r1][c1] + 2) >> 2);
+      s2[ly][lx] = v;
+      p.y2[((size_t)n * p.h2 + y) * p.w2 + x] = v;
+    }
+  }
+  if (!p.y3) return;                        // (uniform: three levels end here, as they always did)
+  __syncthreads();
+  if (tid < 16) {
+    const int ly = tid >> 2, lx = tid & 3, y = ty * 4 + ly, x = tx * 4 + lx;
+    if (y < p.h3 && x < p.w3) {
+      const int r0 = 2 * ly, r1 = min(2 * y + 1, p.h2 - 1) - ty * 8, c0 = 2 * lx, c1 = min(2 * x + 1, p.w2 - 1) - tx * 8;
+      const uint8_t v = (uint8_t)((s2[r0][c0] + s2[r0][c1] + s2[r1][c0] + s2[r1][c1] + 2) >> 2);
+      s3[ly][lx] = v;
+      p.y3[((size_t)n * p.h3 + y) * p.w3 + x] = v;
+    }
+  }
+  if (!p.y4) return;
+  __syncthreads();
+  if (tid < 4) {
+    const int ly = tid >> 1, lx = tid & 1, y = ty * 2 + ly, x = tx * 2 + lx;
+    if (y < p.h4 && x < p.w4) {
+      const int r0 = 2 * ly, r1 = min(2 * y + 1, p.h3 - 1) - ty * 4, c0 = 2 * lx, c1 = min(2 * x + 1, p.w3 - 1) - tx * 4;
+      p.y4[((size_t)n * p.h4 + y) * p.w4 + x] = (uint8_t)((s3[r0][c0] + s3[r0][c1] + s3[r1][c0] + s3[r1][c1] + 2) >> 2);
     }
   }
 }
@@ -133,9 +161,9 @@ __global__ __launch_bounds__(256) void k_mci_search(MciSearchParams p) {
 #pragma unroll
       for (int m = 1; m < PARTS; m <<= 1) sad += __shfl_xor(sad, m);
       const int dx = sx + ddx, dy = sy + ddy;
-      const unsigned long long key = ((unsigned long long)(sad + MCI_LAMBDA * (abs(dx) + abs(dy))) << 22) |
-                                     ((unsigned long long)(dx * dx + dy * dy) << 12) |
-                                     ((unsigned long long)((dy + MCI_KEY_BIAS) & 63) << 6) | (unsigned long long)((dx + MCI_KEY_BIAS) & 63);
+      const unsigned long long key = ((unsigned long long)(sad + MCI_LAMBDA * (abs(dx) + abs(dy))) << 30) |
+                                     ((unsigned long long)(dx * dx + dy * dy) << 16) |
+                                     ((unsigned long long)((dy + MCI_KEY_BIAS) & 255) << 8) | (unsigned long long)((dx + MCI_KEY_BIAS) & 255);
       if (active && key < best) best = key;
     }
 #pragma unroll
@@ -145,8 +173,8 @@ __global__ __launch_bounds__(256) void k_mci_search(MciSearchParams p) {
     }
     if (lane == 0) {
       int16_t* o = p.out + ((size_t)b * nblk + blk) * 2;
-      o[0] = (int16_t)((int)(best & 63) - MCI_KEY_BIAS);
-      o[1] = (int16_t)((int)((best >> 6) & 63) - MCI_KEY_BIAS);
+      o[0] = (int16_t)((int)(best & 255) - MCI_KEY_BIAS);
+      o[1] = (int16_t)((int)((best >> 8) & 255) - MCI_KEY_BIAS);
     }
   }
 }

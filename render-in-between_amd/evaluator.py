@@ -50,6 +50,8 @@ import numpy as np
 import torch
 
 from . import background as _background
+
+MCI_RANGES = {32: 3, 64: 4, 128: 5}      # evaluate_from_folder's mci_range (px of motion between key frames) -> pyramid levels
 from . import io_worker, rasterise
 from . import metrics as _metrics
 from . import panel as _panel
@@ -532,7 +534,7 @@ class Evaluator:
     def evaluate_from_folder(self, model, train_dir, dain_dir, pose_dir, save_dir, gt_dir=None, gen_vid=False,
                              rank=None, world=None, metrics=False, mask_dir=None, pose_mask=False,
                              panels=False, panel_frames=False, panel_quality=90, panel_fps=30, panel_encode="host",
-                             background="dain", video=False, video_fps=30, video_quality=90, video_frames=False, frames="png",
+                             background="dain", mci_range=32, video=False, video_fps=30, video_quality=90, video_frames=False, frames="png",
                              poses="folder", key_pose_dir=None, upsample_rate=8, motion=None, save_poses=False):
         """rank / world: this process's share of the independent units (default: the torch.distributed process
         group when one is initialised, else everything).  Returns the frames THIS rank wrote.
@@ -562,7 +564,10 @@ class Evaluator:
         background="mci" (default "dain": one background frame per output frame from dain_dir, as the reference): the
         background frames are a motion-compensated interpolation of each segment's two key frames (background.py states it in
         integers; this project's interpolation, NOT DAIN - the generator was trained on DAIN backgrounds, the quality on real
-        footage has not been measured, and motion beyond +-32 px between key frames falls outside the search).  dain_dir may be
+        footage has not been measured, and motion beyond +-32 px between key frames falls outside the search).
+        mci_range=64 or 128 (default 32; a setting of background="mci") widens that search to +-64 or +-128 px by a fourth and a
+        fifth pyramid level (background.mci_field_host's levels = 4, 5): one more short launch per level and group, and more
+        room for a false match on periodic content.  dain_dir may be
         None and is never listed or read; a frame's file is named after its pose file (stem without a trailing "_keypoints").
         On the native path the field is made once per group of segments (rib_mci_field) and every unit's frames by one launch
         (rib_mci_frames) on the upload stream - no DAIN bytes are staged or decoded; a model behind the reference's protocol is
@@ -605,6 +610,10 @@ class Evaluator:
         if background == "mci" and self.resize_on == "gpu":
             raise ValueError("evaluate_from_folder: background='mci' with resize_on='gpu' is not supported (there is no DAIN list to "
                              "plan the GPU resize for)")
+        if mci_range not in MCI_RANGES:
+            raise ValueError("evaluate_from_folder: mci_range must be 32, 64 or 128 (px of motion between key frames), got %r" % (mci_range,))
+        if background != "mci" and mci_range != 32:
+            raise ValueError("evaluate_from_folder: mci_range is a setting of background='mci'")
         if gen_vid:
             # the reference also writes <save_dir>/<clip>.mp4 (evaluator.py:267-269, utils.make_video) from a matplotlib canvas
             # through an H.264 encoder; neither is built, and silently ignoring the flag would drop an output the caller asked for
@@ -636,10 +645,10 @@ class Evaluator:
         self.metrics = self.metrics_report = None
         pipe = _FolderPipeline(self, model, rank, world, gt_dir, metrics=bool(metrics), mask_dir=mask_dir, pose_mask=bool(pose_mask),
                                panels=bool(panels), panel_frames=bool(panel_frames), panel_quality=int(panel_quality),
-                               panel_encode=panel_encode, background=background, video=bool(video), video_quality=int(video_quality),
+                               panel_encode=panel_encode, background=background, mci_levels=MCI_RANGES[mci_range], video=bool(video), video_quality=int(video_quality),
                                video_frames=bool(video_frames), write_png=frames == "png",
                                key_poses=None if poses == "folder" else (motion, key_pose_dir, upsample_rate, poses == "keyframes-linear", bool(save_poses)))
-        self.background = background
+        self.background, self.mci_range = background, mci_range
         self.timings = pipe.tm
         if metrics and pipe.native:
             self._quality_model = model
@@ -745,9 +754,9 @@ class _FolderPipeline:
     (tests/test_driver.py)."""
 
     def __init__(self, ev, model, rank, world, gt_dir, metrics=False, mask_dir=None, pose_mask=False,
-                 panels=False, panel_frames=False, panel_quality=90, panel_encode="host", background="dain",
+                 panels=False, panel_frames=False, panel_quality=90, panel_encode="host", background="dain", mci_levels=3,
                  video=False, video_quality=90, video_frames=False, write_png=True, key_poses=None):
-        self.mci = background == "mci"
+        self.mci, self.mci_levels = background == "mci", mci_levels      # (levels: background.mci_field_host's, from mci_range)
         # poses="keyframes": (motion model, key-pose folder, upsample rate, take the linear clip, also write the json folders)
         self.key_poses = key_poses
         # video: the frames' JPEG files (video.py); write_png False (frames="none"): they are the only files of a frame
@@ -1107,7 +1116,7 @@ class _FolderPipeline:
                         mk[0, b].copy_(clip.key_u8[k])
                         mk[1, b].copy_(clip.key_u8[k + clip.sample_rate])
                     kab = mk.to(g.device, non_blocking=True)
-                    clip.mci_of[gi] = (kab[0], kab[1], g.mci_field(kab[0], kab[1]))
+                    clip.mci_of[gi] = (kab[0], kab[1], g.mci_field(kab[0], kab[1], self.mci_levels))
                 ka, kb, field = clip.mci_of[gi]
                 dn = g.mci_frames(ka, kb, field, clip.sample_rate, k_first=c0 + 1, count=Tc, normalised="both" if self.panels else True)
                 if self.panels:
@@ -1493,7 +1502,7 @@ class _FolderPipeline:
             poses = [g[2] for g in got]
             if self.mci:                         # the host definition of the background frames (background.py)
                 ka, kb = clip.key_u8[k].numpy(), clip.key_u8[k + clip.sample_rate].numpy()
-                u8 = _background.mci_frames_host(ka, kb, _background.mci_field_host(ka, kb), clip.sample_rate, [i - k for i in frames])
+                u8 = _background.mci_frames_host(ka, kb, _background.mci_field_host(ka, kb, self.mci_levels), clip.sample_rate, [i - k for i in frames])
                 # the floats the native chain reads (the device's normalisation, stated on the host); the sheets' DAIN pane
                 # shows the host's normalisation, as the native path's does (normalise_exact)
                 dn = torch.from_numpy(_background.normalised_upload(u8)).unsqueeze(1)

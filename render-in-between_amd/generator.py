@@ -566,22 +566,24 @@ class Generator:
             raise ValueError("%s: empty key frames %s" % (who, tuple(a.shape)))
         return a, b, single
 
-    def mci_field(self, a_u8, b_u8):
-        """The block displacement field of B key-frame pairs on the GPU (rib_mci_field; background.mci_field_host is the
+    def mci_field(self, a_u8, b_u8, levels=3):
+        """The block displacement field of B key-frame pairs on the GPU (rib_mci_field_levels; background.mci_field_host is the
         definition and is bit-equal): a_u8, b_u8 uint8 [B,H,W,3] (or [H,W,3]) on this device, the left and right key frame of
-        each segment at the model size -> int16 [B,Hb,Wb,2] (or [Hb,Wb,2]), (dx, dy) per 8x8 block.  This project's
-        interpolation, not DAIN.  Five launches on the current stream."""
+        each segment at the model size -> int16 [B,Hb,Wb,2] (or [Hb,Wb,2]), (dx, dy) per 8x8 block.  levels: 3 (the default),
+        4 or 5 pyramid levels, a search over 32, 64 or 128 px of motion between the key frames.  This project's
+        interpolation, not DAIN.  levels + 2 launches on the current stream: five by default."""
+        from .background import check_levels, field_shape
+        levels = check_levels(levels, "mci_field")
         a, b, single = self._mci_pair(a_u8, b_u8, "mci_field")
         B, H, W, _ = a.shape
-        n = int(self._lib.rib_mci_workspace_bytes(self._h, B, H, W))
+        n = int(self._lib.rib_mci_workspace_bytes_levels(self._h, B, H, W, levels))
         if n == 0:
             raise ValueError("mci_field: B=%d H=%d W=%d: 1 <= B <= 32767, H and W in 1..16384" % (B, H, W))
-        from .background import field_shape
         Hb, Wb = field_shape(H, W)
         with torch.cuda.device(self.device):
             ws = torch.empty(n, dtype=torch.uint8, device=self.device)      # (per call: it belongs to the stream the call is enqueued on)
             field = torch.empty((B, Hb, Wb, 2), dtype=torch.int16, device=self.device)
-            _native.check(self._h, self._lib.rib_mci_field(self._h, B, H, W, _ptr(a), _ptr(b), _ptr(field), _ptr(ws), self._stream()))
+            _native.check(self._h, self._lib.rib_mci_field_levels(self._h, B, H, W, _ptr(a), _ptr(b), _ptr(field), levels, _ptr(ws), self._stream()))
         return field[0] if single else field
 
     def mci_frames(self, a_u8, b_u8, field, sample_rate, k_first=1, count=None, normalised=True, out=None):

@@ -35,8 +35,11 @@ is the only decoder that has read them.
 Backgrounds without a DAIN folder: `--background mci` makes every background frame on the GPU from the segment's two key
 frames - a classical motion-compensated interpolation (background.py states it in integers; rib_mci_field / rib_mci_frames) -
 and never reads <input>/DAIN.  It is this project's interpolation, not DAIN: the generator was trained on DAIN backgrounds, the
-quality on real footage has not been measured, and motion beyond +-32 px between key frames falls outside the search.  Frames
-are then named after their pose files.  The default, `--background dain`, is the reference's contract.
+quality on real footage has not been measured, and motion beyond +-32 px between key frames falls outside the search.
+`--mci-range 64` or `128` (default 32) widens the search by a fourth and a fifth pyramid level: the field then reaches 78 or 158 px
+of motion between key frames (38 at the default) for six or seven launches per group of segments where the default takes five.
+Still no occlusion reasoning and no sub-pel search, and a wider search has more room for a false match on periodic content.
+Frames are then named after their pose files.  The default, `--background dain`, is the reference's contract.
 
 Poses without a Predict_motion folder: `--poses keyframes --pose-dir DIR [--upsample-rate N] [--motion-config PATH]` runs stage 1
 (the motion transformer, motion/inference.py) inside this command: DIR/<clip>/ holds one OpenPose json per key frame, each clip is
@@ -116,7 +119,8 @@ def summary_line(evaluator, rank=0, world=1):
                "reference (zlib 6)" if evaluator.png_compress_level is None else str(evaluator.png_compress_level),
                evaluator.batch or evaluator.default_batch(), "batch-invariant" if evaluator.reproducible else "per-batch",
                getattr(evaluator, "resize_on", "host"),
-               {"dain": "DAIN frames", "mci": "mci (interpolated from the key frames)"}[getattr(evaluator, "background", "dain")]))
+               {"dain": "DAIN frames", "mci": "mci (interpolated from the key frames, range %d px)" % getattr(evaluator, "mci_range", 32)}
+               [getattr(evaluator, "background", "dain")]))
     rep = getattr(evaluator, "metrics_report", None)
     if "metrics" in tm and rep is not None:
         o = rep["overall"]
@@ -158,7 +162,7 @@ def main(opts):
                                              panels=opts.panels, panel_frames=opts.panel_frames,
                                              panel_quality=90 if opts.panel_quality is None else opts.panel_quality,
                                              panel_fps=30 if opts.panel_fps is None else opts.panel_fps,
-                                             panel_encode=opts.panel_encode or "host", background=opts.background,
+                                             panel_encode=opts.panel_encode or "host", background=opts.background, mci_range=opts.mci_range,
                                              video=opts.video, video_fps=30 if opts.video_fps is None else opts.video_fps,
                                              video_quality=90 if opts.video_quality is None else opts.video_quality,
                                              video_frames=opts.video_frames, frames=opts.frames, **poses_kw)
@@ -223,6 +227,11 @@ def build_parser():
                              "frame, as the reference; 'mci': interpolated on the GPU from each segment's two key frames (motion-compensated, "
                              "this project's, not DAIN; the generator was trained on DAIN backgrounds and the quality on real footage has "
                              "not been measured) - no DAIN folder is read, frames are named after their pose files")
+    parser.add_argument("--mci-range", type=int, default=None,
+                        help="with --background mci: the motion between two key frames the search covers, 32 (default), 64 or 128 px "
+                             "(3, 4 or 5 pyramid levels; the field reaches 38, 78 or 158 px; five, six or seven launches per group of "
+                             "segments). Fast pans and passing objects want 64 or 128; a wider search has more room for a false match "
+                             "on periodic content, and there is still no occlusion reasoning and no sub-pel search")
     parser.add_argument("--video", action="store_true",
                         help="also write every frame of a clip, key frames included, as <save-dir>/Generated_frames/<clip>_video.avi "
                              "(Motion-JPEG; a frame is the JPEG of exactly the bytes its PNG holds, encoded on the GPU)")
@@ -261,6 +270,11 @@ def parse_args(argv=None):
         parser.error("--poses %s needs --pose-dir (the key frames' OpenPose json folders)" % opts.poses)
     if opts.upsample_rate is not None and (opts.upsample_rate < 1 or opts.upsample_rate & (opts.upsample_rate - 1)):
         parser.error("--upsample-rate must be a power of two")
+    if opts.mci_range is not None and opts.background != "mci":
+        parser.error("--mci-range is a setting of --background mci")
+    if opts.mci_range not in (None, 32, 64, 128):
+        parser.error("--mci-range must be 32, 64 or 128, got %r" % (opts.mci_range,))
+    opts.mci_range = 32 if opts.mci_range is None else opts.mci_range
     if opts.background == "mci" and opts.resize_on == "gpu":
         parser.error("--background mci with --resize-on gpu is not supported (there is no DAIN list to plan the GPU resize for)")
     if opts.metrics and opts.gt_dir is None:
