@@ -302,7 +302,17 @@ int rib_jpeg_float(rib_handle* h, int T, int H, int W, const float* src_f32_nchw
  * upload computes it (the arithmetic of rib_resize_cubic's float output), and / or out_u8_nhwc uint8 [T,B,H,W,3]; a NULL output
  * is not wanted (both NULL is an error).  Every element written; a frame's bytes do not depend on T or B.
  * B outside 1..32767, B * Hb * Wb >= 2^30, T < 1, T * B > 65535, H or W outside 1..16384, a bad sample_rate or frame range, NULL or misaligned pointers:
- * RIB_ERR_INVALID with a rib_last_error text, nothing launched (the size query returns 0). */
+ * RIB_ERR_INVALID with a rib_last_error text, nothing launched (the size query returns 0).
+ * rib_mci_field_border / rib_mci_frames_border: the same with a border mode (the driver's --mci-border; background.py's
+ * border=): 0 = "clamp", the results above - rib_mci_field_levels and rib_mci_frames ARE border = 0 of these two, the same
+ * kernels; 1 = "valid", one-sided at the FRAME border.  Field: a block's pixel counts for a candidate d only when p - d and p + d
+ * both lie inside the level's plane (n pixels, a closed-form rectangle, of the block's N); a candidate is valid when 4 n >= N,
+ * costs (64 * SAD over those n) / n + LAMBDA (|dx| + |dy|), the winner is the minimum key over the valid candidates, and a block
+ * whose start candidate is not valid keeps its start.  Frames: a sample is valid when its position lies in [0, (H-1) << 8] x
+ * [0, (W-1) << 8]; where exactly one of the two samples is valid the output is that sample alone (a hard switch), otherwise the
+ * blend.  Interior occlusion - a foreground object covering background - is NOT handled.  The same workspace size, the same
+ * L + 2 launches and one launch, the same contracts; border outside {0, 1}: RIB_ERR_INVALID with a rib_last_error text,
+ * nothing launched. */
 void rib_mci_field_shape(int H, int W, int* Hb, int* Wb);
 size_t rib_mci_workspace_bytes(rib_handle* h, int B, int H, int W);
 int rib_mci_field(rib_handle* h, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
@@ -312,6 +322,10 @@ int rib_mci_field_levels(rib_handle* h, int B, int H, int W, const uint8_t* a_u8
                          int levels, void* workspace, void* hip_stream);
 int rib_mci_frames(rib_handle* h, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const int16_t* field_i16,
                    int sample_rate, int k_first, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream);
+int rib_mci_field_border(rib_handle* h, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
+                         int levels, int border, void* workspace, void* hip_stream);
+int rib_mci_frames_border(rib_handle* h, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const int16_t* field_i16,
+                          int sample_rate, int k_first, int border, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream);
 
 /* Extension op named by the north star but absent from the reference: bilinear
  * flow-grid warp, semantics of torch.nn.functional.grid_sample(img, base+flow*2/(size-1),

@@ -32,7 +32,20 @@ bit-equal to them (tests/test_gpu_mci.py).  Every step is integer or fixed point
              (sum of the four taps times their 8-bit weight products + 2^15) >> 16, per channel;
              out = ((s-k) a + k b + s/2) >> log2 s.
 
-No occlusion reasoning and no sub-pel search: see DESIGN ("Motion-compensated backgrounds") for what that costs."""
+  border     "clamp" (the default) is everything above.  "valid" (the driver's mci_border) is one-sided at the FRAME border, in
+             two places.  Matching: a pixel p of a block counts for candidate d only when p - d and p + d both lie inside the
+             plane - the rectangle |dx| <= X <= w-1-|dx|, |dy| <= Y <= h-1-|dy| cut with the block, n pixels of the block's N
+             inside the plane; a candidate is valid when 4 n >= N, its cost is (64 * SAD over those n) // n + LAMBDA * (|dx| +
+             |dy|) (at most 16320 + 632 < 2^15: pack_key_wide holds it, and is the key for every L), the winner the minimum
+             key over the valid candidates; a block whose start candidate is not valid searches nothing and keeps its start
+             (on the top level start = 0 is always valid; below it, an invalid start IS a block that, at the coarser level's
+             vector, one key frame does not show).  Frames: a sample is valid when its position lies in [0, (H-1) << 8] x
+             [0, (W-1) << 8] (its bilinear footprint then needs no clamp); where exactly one of the two samples is valid the
+             output is that sample alone - a hard switch, with a seam where it flips; otherwise the blend above.  k = 0 and
+             k = s stay A and B.  Median and per-pixel field are unchanged.
+
+No sub-pel search, and no occlusion reasoning beyond the frame border under border="valid" - a foreground object that covers
+background is not handled: see DESIGN ("Motion-compensated backgrounds") for what that costs."""
 from __future__ import annotations
 
 import numpy as np
@@ -49,6 +62,8 @@ MAX_DISP = 2 * (2 * SEARCH_TOP + REFINE) + REFINE      # 19: the largest |dx|, |
 KEY_BIAS = 32             # pack_key: dy + 32, dx + 32 in 6 bits each (MAX_DISP < 32)
 WIDE_KEY_BIAS = 128       # pack_key_wide: dy + 128, dx + 128 in 8 bits each (max_disp(5) = 79 < 128)
 MAX_SAMPLE_RATE = 1024
+BORDERS = ("clamp", "valid")              # `border` of the functions below; rib_mci_*_border's 0 and 1
+VALID_SHARE = 4           # border="valid": a candidate counts when VALID_SHARE * n >= N
 
 
 def field_shape(height, width):
@@ -75,6 +90,12 @@ def check_levels(levels, who):
     if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not MIN_LEVELS <= levels <= MAX_LEVELS:
         raise ValueError("%s: levels must be %d..%d (a range of 32, 64 or 128 px), got %r" % (who, MIN_LEVELS, MAX_LEVELS, levels))
     return int(levels)
+
+
+def check_border(border, who):
+    if not isinstance(border, str) or border not in BORDERS:
+        raise ValueError("%s: border must be 'clamp' or 'valid', got %r" % (who, border))
+    return border
 
 
 def max_disp(levels):
@@ -126,9 +147,59 @@ def block_cost(ya, yb, dx, dy):
     return sad.reshape(Hb, BLOCK, Wb, BLOCK).sum((1, 3)) + LAMBDA * (np.abs(dx) + np.abs(dy))
 
 
-def search(ya, yb, sx, sy, radius, wide=False):
+def valid_counts(h, w, dx, dy):
+    """border="valid": (n, N) int64 [Hb, Wb] of one level - n the pixels p of each block with p - d and p + d inside the h x w
+    plane (the rectangle |dx| <= X <= w-1-|dx|, |dy| <= Y <= h-1-|dy| cut with the block), N the block's pixels inside it."""
+    Hb, Wb = field_shape(h, w)
+    y0, x0 = BLOCK * np.arange(Hb, dtype=np.int64)[:, None], BLOCK * np.arange(Wb, dtype=np.int64)[None, :]
+    y1, x1 = np.minimum(y0 + BLOCK - 1, h - 1), np.minimum(x0 + BLOCK - 1, w - 1)
+    ax, ay = np.abs(dx).astype(np.int64), np.abs(dy).astype(np.int64)
+    nx = np.maximum(np.minimum(x1, w - 1 - ax) - np.maximum(x0, ax) + 1, 0)
+    ny = np.maximum(np.minimum(y1, h - 1 - ay) - np.maximum(y0, ay) + 1, 0)
+    return nx * ny, (y1 - y0 + 1) * (x1 - x0 + 1)
+
+
+def block_cost_valid(ya, yb, dx, dy):
+    """border="valid": (cost, valid) of every block of one level - cost(d) = (64 * SAD over the pixels whose two samples are
+    both inside the plane) // n + LAMBDA * (|dx| + |dy|), int64 [Hb, Wb] (0 where n = 0); valid = 4 n >= N, bool [Hb, Wb]."""
+    h, w = ya.shape
+    Hb, Wb = field_shape(h, w)
+    px = np.repeat(np.repeat(dx, BLOCK, 0), BLOCK, 1)[:h, :w]
+    py = np.repeat(np.repeat(dy, BLOCK, 0), BLOCK, 1)[:h, :w]
+    Y, X = np.mgrid[0:h, 0:w]
+    inside = (Y - py >= 0) & (Y - py <= h - 1) & (Y + py >= 0) & (Y + py <= h - 1) \
+        & (X - px >= 0) & (X - px <= w - 1) & (X + px >= 0) & (X + px <= w - 1)
+    a = ya[np.clip(Y - py, 0, h - 1), np.clip(X - px, 0, w - 1)].astype(np.int32)
+    b = yb[np.clip(Y + py, 0, h - 1), np.clip(X + px, 0, w - 1)].astype(np.int32)
+    sad = np.zeros((Hb * BLOCK, Wb * BLOCK), np.int64)
+    sad[:h, :w] = np.where(inside, np.abs(a - b), 0)
+    n, N = valid_counts(h, w, dx, dy)
+    cost = (64 * sad.reshape(Hb, BLOCK, Wb, BLOCK).sum((1, 3))) // np.maximum(n, 1) + LAMBDA * (np.abs(dx) + np.abs(dy))
+    return cost, VALID_SHARE * n >= N
+
+
+def search_valid(ya, yb, sx, sy, radius):
+    """search under border="valid": the minimum pack_key_wide key over the valid candidates; a block whose start candidate
+    is not valid keeps its start."""
+    never = np.int64(1) << 62
+    best = None
+    for ddy in range(-radius, radius + 1):
+        for ddx in range(-radius, radius + 1):
+            dx, dy = sx + ddx, sy + ddy
+            cost, ok = block_cost_valid(ya, yb, dx, dy)
+            key = np.where(ok, pack_key_wide(np.where(ok, cost, 0), np.where(ok, dx, 0), np.where(ok, dy, 0)), never)
+            best = key if best is None else np.minimum(best, key)
+    searched = block_cost_valid(ya, yb, sx, sy)[1]
+    _, wx, wy = unpack_key_wide(np.where(searched, best, 0))
+    return np.where(searched, wx, sx).astype(np.int32), np.where(searched, wy, sy).astype(np.int32)
+
+
+def search(ya, yb, sx, sy, radius, wide=False, border="clamp"):
     """The winner of start + [-radius, radius]^2 for every block: sx, sy int [Hb, Wb] -> (dx, dy) int32 [Hb, Wb].  wide: the
-    key is pack_key_wide (displacements beyond KEY_BIAS); the winner is the tuple's minimum either way."""
+    key is pack_key_wide (displacements beyond KEY_BIAS); the winner is the tuple's minimum either way.  border="valid": the
+    one-sided cost over the valid candidates (always the wide key), see the module's text."""
+    if check_border(border, "search") == "valid":
+        return search_valid(ya, yb, sx, sy, radius)
     best = None
     pack = pack_key_wide if wide else pack_key
     for ddy in range(-radius, radius + 1):
@@ -149,10 +220,11 @@ def median3(f):
     return np.sort(nine, axis=0)[4]
 
 
-def block_field_levels(a_u8, b_u8, levels=LEVELS):
+def block_field_levels(a_u8, b_u8, levels=LEVELS, border="clamp"):
     """The block fields of levels L-1 .. 0 (L = levels: 3, 4 or 5) before the median: [(dx, dy)] coarse to fine (the tests look
     at them)."""
     levels = check_levels(levels, "block_field_levels")
+    check_border(border, "block_field_levels")
     pa, pb = pyramid(luma(a_u8), levels), pyramid(luma(b_u8), levels)
     out = []
     dx = dy = None
@@ -165,22 +237,24 @@ def block_field_levels(a_u8, b_u8, levels=LEVELS):
             by, bx = np.arange(Hb) >> 1, np.arange(Wb) >> 1
             sx, sy = 2 * dx[by][:, bx], 2 * dy[by][:, bx]
             radius = REFINE
-        dx, dy = search(pa[lvl], pb[lvl], sx, sy, radius, wide=levels > LEVELS)
+        dx, dy = search(pa[lvl], pb[lvl], sx, sy, radius, wide=levels > LEVELS, border=border)
         out.append((dx, dy))
     return out
 
 
-def mci_field_host(a_u8, b_u8, levels=LEVELS):
+def mci_field_host(a_u8, b_u8, levels=LEVELS, border="clamp"):
     """The block displacement field of a key-frame pair: a_u8, b_u8 uint8 [H, W, 3] (left and right key frame at the model
     size) -> int16 [Hb, Wb, 2], [..., 0] = dx, [..., 1] = dy, in full-size pixels of HALF the motion between the key frames
     (the intermediate frame's pixel p shows A's p - d and B's p + d).  levels: 3 (the default), 4 or 5 pyramid levels, i.e. a
-    search over 32, 64 or 128 px of motion between the key frames; |dx|, |dy| <= max_disp(levels)."""
+    search over 32, 64 or 128 px of motion between the key frames; |dx|, |dy| <= max_disp(levels).  border: "clamp" (the
+    default) or "valid", the one-sided matching at the frame border."""
     levels = check_levels(levels, "mci_field_host")
+    check_border(border, "mci_field_host")
     a_u8, b_u8 = np.asarray(a_u8), np.asarray(b_u8)
     if a_u8.dtype != np.uint8 or a_u8.ndim != 3 or a_u8.shape[2] != 3 or a_u8.shape != b_u8.shape or b_u8.dtype != np.uint8:
         raise ValueError("mci_field_host: two uint8 [H, W, 3] frames of one size, got %s %s and %s %s"
                          % (a_u8.dtype, a_u8.shape, b_u8.dtype, b_u8.shape))
-    dx, dy = block_field_levels(a_u8, b_u8, levels)[-1]
+    dx, dy = block_field_levels(a_u8, b_u8, levels, border)[-1]
     return np.stack([median3(dx), median3(dy)], -1).astype(np.int16)
 
 
@@ -217,9 +291,16 @@ def log2_rate(sample_rate):
     return s.bit_length() - 1
 
 
-def mci_frames_host(a_u8, b_u8, field, sample_rate, ks):
+def sample_valid(py, px, height, width):
+    """border="valid": bool [H, W], the positions (1/256 px) whose bilinear footprint lies inside the frame."""
+    return (py >= 0) & (py <= (height - 1) << SAMPLE_FRAC_BITS) & (px >= 0) & (px <= (width - 1) << SAMPLE_FRAC_BITS)
+
+
+def mci_frames_host(a_u8, b_u8, field, sample_rate, ks, border="clamp"):
     """Frames ks (each 0 <= k <= sample_rate; k = 0 is A, k = sample_rate is B) of the segment between the key frames a_u8 and
-    b_u8 (uint8 [H, W, 3]) from their block field (mci_field_host) -> uint8 [len(ks), H, W, 3]."""
+    b_u8 (uint8 [H, W, 3]) from their block field (mci_field_host) -> uint8 [len(ks), H, W, 3].  border="valid": where exactly
+    one of a pixel's two samples lies inside the frame the output is that sample alone."""
+    check_border(border, "mci_frames_host")
     a_u8, b_u8, field = np.asarray(a_u8), np.asarray(b_u8), np.asarray(field)
     if a_u8.dtype != np.uint8 or a_u8.ndim != 3 or a_u8.shape[2] != 3 or a_u8.shape != b_u8.shape or b_u8.dtype != np.uint8:
         raise ValueError("mci_frames_host: two uint8 [H, W, 3] frames of one size, got %s and %s" % (a_u8.shape, b_u8.shape))
@@ -237,7 +318,11 @@ def mci_frames_host(a_u8, b_u8, field, sample_rate, ks):
         bx, by = (2 * (s - k) * Dx + s // 2) >> ls, (2 * (s - k) * Dy + s // 2) >> ls
         a = sample_bilinear(a_u8, Y - ay, X - ax)
         b = sample_bilinear(b_u8, Y + by, X + bx)
-        out[j] = (((s - k) * a + k * b + s // 2) >> ls).astype(np.uint8)
+        o = ((s - k) * a + k * b + s // 2) >> ls
+        if border == "valid":
+            oka, okb = sample_valid(Y - ay, X - ax, H, W)[..., None], sample_valid(Y + by, X + bx, H, W)[..., None]
+            o = np.where(oka == okb, o, np.where(oka, a, b))
+        out[j] = o.astype(np.uint8)
     return out
 
 

@@ -372,14 +372,16 @@ size_t rib_mci_workspace_bytes_levels(rib_handle* h, int B, int H, int W, int le
 
 size_t rib_mci_workspace_bytes(rib_handle* h, int B, int H, int W) { return rib_mci_workspace_bytes_levels(h, B, H, W, MCI_MIN_LEVELS); }
 
-int rib_mci_field_levels(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
-                         int levels, void* workspace, void* hip_stream) {
+int rib_mci_field_border(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
+                         int levels, int border, void* workspace, void* hip_stream) {
   FrameState* h = frame_state(handle);
   if (!h) return RIB_ERR_INVALID;
   if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_mci_field: host-only handle");
   if (!a_u8 || !b_u8 || !field_i16 || !workspace) return fail(h, RIB_ERR_INVALID, "rib_mci_field: null pointer");
   if (levels < MCI_MIN_LEVELS || levels > MCI_MAX_LEVELS)
     return fail(h, RIB_ERR_INVALID, fmt("rib_mci_field: levels=%d: %d..%d pyramid levels (a search over 32, 64 or 128 px)", levels, MCI_MIN_LEVELS, MCI_MAX_LEVELS));
+  if (border != 0 && border != 1)
+    return fail(h, RIB_ERR_INVALID, fmt("rib_mci_field: border=%d: 0 (clamped samples) or 1 (valid samples only)", border));
   MciLayout L;
   if (!mci_layout(B, H, W, levels, &L))
     return fail(h, RIB_ERR_INVALID, fmt("rib_mci_field: B=%d H=%d W=%d: 1 <= B <= 32767, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", B, H, W, MCI_MAX_SIDE));
@@ -403,8 +405,13 @@ int rib_mci_field_levels(rib_handle* handle, int B, int H, int W, const uint8_t*
     sp.B = B; sp.h = L.h[l]; sp.w = L.w[l]; sp.Hb = L.Hb[l]; sp.Wb = L.Wb[l];
     sp.Hbc = l == top ? 1 : L.Hb[l + 1]; sp.Wbc = l == top ? 1 : L.Wb[l + 1];
     const dim3 grid((sp.Hb * sp.Wb + MCI_RUN - 1) / MCI_RUN, B);
-    if (l == top) hipLaunchKernelGGL(k_mci_search<MCI_TOP_R>, grid, dim3(256), 0, st, sp);
-    else hipLaunchKernelGGL(k_mci_search<1>, grid, dim3(256), 0, st, sp);
+    if (border) {
+      if (l == top) hipLaunchKernelGGL((k_mci_search<MCI_TOP_R, true>), grid, dim3(256), 0, st, sp);
+      else hipLaunchKernelGGL((k_mci_search<1, true>), grid, dim3(256), 0, st, sp);
+    } else {
+      if (l == top) hipLaunchKernelGGL(k_mci_search<MCI_TOP_R>, grid, dim3(256), 0, st, sp);
+      else hipLaunchKernelGGL(k_mci_search<1>, grid, dim3(256), 0, st, sp);
+    }
     HIP_TRY(h, hipGetLastError());
   }
   const int n = B * L.Hb[0] * L.Wb[0];
@@ -414,13 +421,18 @@ int rib_mci_field_levels(rib_handle* handle, int B, int H, int W, const uint8_t*
   return RIB_OK;
 }
 
+int rib_mci_field_levels(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
+                         int levels, void* workspace, void* hip_stream) {
+  return rib_mci_field_border(handle, B, H, W, a_u8, b_u8, field_i16, levels, 0, workspace, hip_stream);
+}
+
 int rib_mci_field(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
                   void* workspace, void* hip_stream) {
   return rib_mci_field_levels(handle, B, H, W, a_u8, b_u8, field_i16, MCI_MIN_LEVELS, workspace, hip_stream);
 }
 
-int rib_mci_frames(rib_handle* handle, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const int16_t* field_i16,
-                   int sample_rate, int k_first, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream) {
+int rib_mci_frames_border(rib_handle* handle, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const int16_t* field_i16,
+                          int sample_rate, int k_first, int border, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream) {
   FrameState* h = frame_state(handle);
   if (!h) return RIB_ERR_INVALID;
   if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_mci_frames: host-only handle");
@@ -433,6 +445,8 @@ int rib_mci_frames(rib_handle* handle, int T, int B, int H, int W, const uint8_t
     return fail(h, RIB_ERR_INVALID, fmt("rib_mci_frames: sample_rate=%d: a power of two in 1..%d", sample_rate, MCI_MAX_RATE));
   if (k_first < 0 || k_first + T - 1 > sample_rate)
     return fail(h, RIB_ERR_INVALID, fmt("rib_mci_frames: frames %d..%d are outside the segment 0..%d", k_first, k_first + T - 1, sample_rate));
+  if (border != 0 && border != 1)
+    return fail(h, RIB_ERR_INVALID, fmt("rib_mci_frames: border=%d: 0 (clamped samples) or 1 (valid samples only)", border));
   if ((reinterpret_cast<uintptr_t>(field_i16) & 1) != 0 || (reinterpret_cast<uintptr_t>(out_f32_nchw) & 3) != 0)
     return fail(h, RIB_ERR_INVALID, "rib_mci_frames: misaligned pointer");
   MciFramesParams fp;
@@ -443,8 +457,14 @@ int rib_mci_frames(rib_handle* handle, int T, int B, int H, int W, const uint8_t
   fp.vec = (W % 4 == 0 && (reinterpret_cast<uintptr_t>(out_f32_nchw) & 15) == 0 && (reinterpret_cast<uintptr_t>(out_u8_nhwc) & 3) == 0) ? 1 : 0;
   HIP_TRY(h, hipSetDevice(h->device));
   const size_t lds = out_u8_nhwc ? (size_t)W * 3 + 32 : 0;
-  hipLaunchKernelGGL(k_mci_frames, dim3(H, T * B), dim3(256), lds, reinterpret_cast<hipStream_t>(hip_stream), fp);
+  if (border) hipLaunchKernelGGL(k_mci_frames<true>, dim3(H, T * B), dim3(256), lds, reinterpret_cast<hipStream_t>(hip_stream), fp);
+  else hipLaunchKernelGGL(k_mci_frames<false>, dim3(H, T * B), dim3(256), lds, reinterpret_cast<hipStream_t>(hip_stream), fp);
   HIP_TRY(h, hipGetLastError());
   return RIB_OK;
+}
+
+int rib_mci_frames(rib_handle* handle, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const int16_t* field_i16,
+                   int sample_rate, int k_first, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream) {
+  return rib_mci_frames_border(handle, T, B, H, W, a_u8, b_u8, field_i16, sample_rate, k_first, 0, out_f32_nchw, out_u8_nhwc, hip_stream);
 }
 }  // extern "C"

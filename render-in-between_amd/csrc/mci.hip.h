@@ -16,11 +16,22 @@
 //                       room for the +-79 of five levels): the order of the tuple (cost, |d|^2, dy, dx), whatever the lane
 //                       order - and whatever the layout, so three levels give background.pack_key's winners.  No atomics.
 //                       The top level of L (3, 4 or 5) runs <MCI_TOP_R> from start 0, every level below <1>.
+//                       <R, VALID = true> (border = 1, background.py's border="valid"): the one-sided cost at the frame border.
+//                       The staged windows are the same clamped ones; a candidate's valid pixels - p - d and p + d both inside
+//                       the plane - are a closed-form rectangle of the block (from the block's origin, d and h, w); the SAD
+//                       sums over it only, by a select per pixel inside the default's loops, whose bounds are uniform per
+//                       block (loops from the rectangle's own, per-lane bounds took 36.8 us where these take 19.6 on level 0 of
+//                       512 x 512, B = 4: profiles/r13_mci_border.txt); n = nx * ny needs no mask and no reduction (the four row
+//                       lanes of R = 1 sum their SADs and all know n), cost = 64 * SAD / n + LAMBDA's term, candidates with
+//                       4 n < N do not compete, and a block whose start itself is such a candidate (uniform per wave) stores
+//                       its start.
 //   k_mci_median        3x3 componentwise median of the level-0 field, clamped.
 //   k_mci_frames        grid (H, T * B): a workgroup owns ONE row of one frame; a thread takes 4 consecutive x: D(p) bilinear
 //                       from the block field (exact, 1/256 px), the two fixed-point bilinear samples, the blend; float4 stores
 //                       per channel plane of the normalised NCHW tensor, and the uint8 NHWC row through LDS as 16-byte
-//                       stores contiguous across the wave (k_panel's scheme).  Either output may be null.
+//                       stores contiguous across the wave (k_panel's scheme).  Either output may be null.  <VALID = true>:
+//                       a sample is valid when its position lies in [0, (H-1) << 8] x [0, (W-1) << 8]; where exactly one of
+//                       the two is, the output is that sample instead of the blend (four comparisons per sample, a select).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -107,7 +118,14 @@ struct MciSearchParams {
   int B, h, w, Hb, Wb, Hbc, Wbc;
 };
 
-template <int R>
+// border = 1: the pixels of the block rows / columns [o, o + len) whose p - d and p + d lie in [0, size): [lo, hi) relative to o
+__device__ inline void mci_valid_span(int o, int len, int d, int size, int& lo, int& hi) {
+  const int ad = abs(d);
+  lo = max(ad - o, 0);
+  hi = max(min(len, size - ad - o), lo);
+}
+
+template <int R, bool VALID = false>
 __global__ __launch_bounds__(256) void k_mci_search(MciSearchParams p) {
   constexpr int WS = MCI_BLOCK + 2 * R, WIN = WS * WS, SIDE = 2 * R + 1, NC = SIDE * SIDE;
   constexpr int PARTS = (NC * 4 <= 64) ? 4 : 1, ROWS = MCI_BLOCK / PARTS;
@@ -146,25 +164,48 @@ __global__ __launch_bounds__(256) void k_mci_search(MciSearchParams p) {
     const int sx = s_start[j][0], sy = s_start[j][1];
     const uint8_t *wa = s_win[j][0], *wb = s_win[j][1];
     unsigned long long best = ~0ull;
+    if constexpr (VALID) {                  // the start candidate itself has too few valid pixels: nothing to search
+      int xl, xh, yl, yh;
+      mci_valid_span(MCI_BLOCK * bx, pw, sx, p.w, xl, xh);
+      mci_valid_span(MCI_BLOCK * by, ph, sy, p.h, yl, yh);
+      if (4 * (xh - xl) * (yh - yl) < pw * ph) {      // (uniform per wave: the shuffles below are not reached by any lane)
+        if (lane == 0) {
+          int16_t* o = p.out + ((size_t)b * nblk + blk) * 2;
+          o[0] = (int16_t)sx; o[1] = (int16_t)sy;
+        }
+        continue;
+      }
+    }
     for (int c0 = 0; c0 < NC * PARTS; c0 += 64) {
       const int id = c0 + lane, c = id / PARTS, part = id - c * PARTS;
       const bool active = c < NC;
       const int ddy = active ? c / SIDE - R : 0, ddx = active ? c - (c / SIDE) * SIDE - R : 0;
       int sad = 0;
+      int xl = 0, xh = pw, yl = 0, yh = ph;      // VALID: the candidate's rectangle, on each of its PARTS lanes
+      if constexpr (VALID) {
+        mci_valid_span(MCI_BLOCK * bx, pw, sx + ddx, p.w, xl, xh);
+        mci_valid_span(MCI_BLOCK * by, ph, sy + ddy, p.h, yl, yh);
+      }
+      const int n = (xh - xl) * (yh - yl);
       for (int r = part * ROWS; r < (part + 1) * ROWS; ++r) {
         if (r < ph) {
           const uint8_t* ra = wa + (r - ddy + R) * WS + (R - ddx);
           const uint8_t* rb = wb + (r + ddy + R) * WS + (R + ddx);
-          for (int x = 0; x < pw; ++x) sad += abs((int)ra[x] - (int)rb[x]);
+          for (int x = 0; x < pw; ++x) {
+            if constexpr (VALID) sad += (r >= yl && r < yh && x >= xl && x < xh) ? abs((int)ra[x] - (int)rb[x]) : 0;
+            else sad += abs((int)ra[x] - (int)rb[x]);
+          }
         }
       }
 #pragma unroll
       for (int m = 1; m < PARTS; m <<= 1) sad += __shfl_xor(sad, m);
+      if constexpr (VALID) sad = (64 * sad) / max(n, 1);      // (n = 0: not a candidate, below)
+      const bool counts = VALID ? active && 4 * n >= pw * ph : active;
       const int dx = sx + ddx, dy = sy + ddy;
       const unsigned long long key = ((unsigned long long)(sad + MCI_LAMBDA * (abs(dx) + abs(dy))) << 30) |
                                      ((unsigned long long)(dx * dx + dy * dy) << 16) |
                                      ((unsigned long long)((dy + MCI_KEY_BIAS) & 255) << 8) | (unsigned long long)((dx + MCI_KEY_BIAS) & 255);
-      if (active && key < best) best = key;
+      if (counts && key < best) best = key;
     }
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
@@ -229,6 +270,7 @@ __device__ inline void mci_sample(const uint8_t* img, int H, int W, int py, int 
     v[c] = ((256 - fy) * ((256 - fx) * p00[c] + fx * p01[c]) + fy * ((256 - fx) * p10[c] + fx * p11[c]) + (1 << 15)) >> 16;
 }
 
+template <bool VALID = false>
 __global__ __launch_bounds__(256) void k_mci_frames(MciFramesParams p) {
   extern __shared__ __attribute__((aligned(16))) uint8_t s_mci[];
   const int y = blockIdx.x, tb = blockIdx.y, t = tb / p.B, bi = tb - t * p.B;
@@ -261,8 +303,19 @@ __global__ __launch_bounds__(256) void k_mci_frames(MciFramesParams p) {
       int va[3], vb[3];
       mci_sample(A, H, W, (y << 8) - ay, (x << 8) - ax, va);
       mci_sample(Bf, H, W, (y << 8) + by, (x << 8) + bx, vb);
+      if constexpr (VALID) {
+        const int pay = (y << 8) - ay, pax = (x << 8) - ax, pby = (y << 8) + by, pbx = (x << 8) + bx;
+        const int ymax = (H - 1) << 8, xmax = (W - 1) << 8;
+        const bool oka = pay >= 0 && pay <= ymax && pax >= 0 && pax <= xmax, okb = pby >= 0 && pby <= ymax && pbx >= 0 && pbx <= xmax;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) q[j * 3 + c] = (uint8_t)(((s - k) * va[c] + k * vb[c] + (s >> 1)) >> ls);
+        for (int c = 0; c < 3; ++c) {
+          const int blend = ((s - k) * va[c] + k * vb[c] + (s >> 1)) >> ls;
+          q[j * 3 + c] = (uint8_t)(oka == okb ? blend : oka ? va[c] : vb[c]);
+        }
+      } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) q[j * 3 + c] = (uint8_t)(((s - k) * va[c] + k * vb[c] + (s >> 1)) >> ls);
+      }
     }
     if (p.out_f32) {
 #pragma unroll

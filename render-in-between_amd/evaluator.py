@@ -535,7 +535,7 @@ class Evaluator:
                              rank=None, world=None, metrics=False, mask_dir=None, pose_mask=False,
                              panels=False, panel_frames=False, panel_quality=90, panel_fps=30, panel_encode="host",
                              background="dain", mci_range=32, video=False, video_fps=30, video_quality=90, video_frames=False, frames="png",
-                             poses="folder", key_pose_dir=None, upsample_rate=8, motion=None, save_poses=False):
+                             poses="folder", key_pose_dir=None, upsample_rate=8, motion=None, save_poses=False, mci_border="clamp"):
         """rank / world: this process's share of the independent units (default: the torch.distributed process
         group when one is initialised, else everything).  Returns the frames THIS rank wrote.
         The call is one `_FolderPipeline` (below): plan a clip -> decode -> upload -> render -> sink, pipelined over units
@@ -567,7 +567,10 @@ class Evaluator:
         footage has not been measured, and motion beyond +-32 px between key frames falls outside the search).
         mci_range=64 or 128 (default 32; a setting of background="mci") widens that search to +-64 or +-128 px by a fourth and a
         fifth pyramid level (background.mci_field_host's levels = 4, 5): one more short launch per level and group, and more
-        room for a false match on periodic content.  dain_dir may be
+        room for a false match on periodic content.  mci_border="valid" (default "clamp"; a setting of background="mci") makes
+        matching and sampling one-sided at the FRAME border (background.py's border="valid"): a strip that only one key frame
+        shows is taken from that key frame alone, not blended with a smear of the other's edge; occlusion inside the frame (a
+        foreground object covering background) is not handled.  dain_dir may be
         None and is never listed or read; a frame's file is named after its pose file (stem without a trailing "_keypoints").
         On the native path the field is made once per group of segments (rib_mci_field) and every unit's frames by one launch
         (rib_mci_frames) on the upload stream - no DAIN bytes are staged or decoded; a model behind the reference's protocol is
@@ -614,6 +617,10 @@ class Evaluator:
             raise ValueError("evaluate_from_folder: mci_range must be 32, 64 or 128 (px of motion between key frames), got %r" % (mci_range,))
         if background != "mci" and mci_range != 32:
             raise ValueError("evaluate_from_folder: mci_range is a setting of background='mci'")
+        if not isinstance(mci_border, str) or mci_border not in _background.BORDERS:
+            raise ValueError("evaluate_from_folder: mci_border must be 'clamp' or 'valid', got %r" % (mci_border,))
+        if background != "mci" and mci_border != "clamp":
+            raise ValueError("evaluate_from_folder: mci_border is a setting of background='mci'")
         if gen_vid:
             # the reference also writes <save_dir>/<clip>.mp4 (evaluator.py:267-269, utils.make_video) from a matplotlib canvas
             # through an H.264 encoder; neither is built, and silently ignoring the flag would drop an output the caller asked for
@@ -645,10 +652,10 @@ class Evaluator:
         self.metrics = self.metrics_report = None
         pipe = _FolderPipeline(self, model, rank, world, gt_dir, metrics=bool(metrics), mask_dir=mask_dir, pose_mask=bool(pose_mask),
                                panels=bool(panels), panel_frames=bool(panel_frames), panel_quality=int(panel_quality),
-                               panel_encode=panel_encode, background=background, mci_levels=MCI_RANGES[mci_range], video=bool(video), video_quality=int(video_quality),
+                               panel_encode=panel_encode, background=background, mci_levels=MCI_RANGES[mci_range], mci_border=mci_border, video=bool(video), video_quality=int(video_quality),
                                video_frames=bool(video_frames), write_png=frames == "png",
                                key_poses=None if poses == "folder" else (motion, key_pose_dir, upsample_rate, poses == "keyframes-linear", bool(save_poses)))
-        self.background, self.mci_range = background, mci_range
+        self.background, self.mci_range, self.mci_border = background, mci_range, mci_border
         self.timings = pipe.tm
         if metrics and pipe.native:
             self._quality_model = model
@@ -755,8 +762,10 @@ class _FolderPipeline:
 
     def __init__(self, ev, model, rank, world, gt_dir, metrics=False, mask_dir=None, pose_mask=False,
                  panels=False, panel_frames=False, panel_quality=90, panel_encode="host", background="dain", mci_levels=3,
-                 video=False, video_quality=90, video_frames=False, write_png=True, key_poses=None):
+                 video=False, video_quality=90, video_frames=False, write_png=True, key_poses=None, mci_border="clamp"):
         self.mci, self.mci_levels = background == "mci", mci_levels      # (levels: background.mci_field_host's, from mci_range)
+        self.mci_border = mci_border        # background.py's border; "clamp": the calls below are those of before the mode existed
+        self.mci_kw = {} if mci_border == "clamp" else {"border": mci_border}
         # poses="keyframes": (motion model, key-pose folder, upsample rate, take the linear clip, also write the json folders)
         self.key_poses = key_poses
         # video: the frames' JPEG files (video.py); write_png False (frames="none"): they are the only files of a frame
@@ -1116,9 +1125,10 @@ class _FolderPipeline:
                         mk[0, b].copy_(clip.key_u8[k])
                         mk[1, b].copy_(clip.key_u8[k + clip.sample_rate])
                     kab = mk.to(g.device, non_blocking=True)
-                    clip.mci_of[gi] = (kab[0], kab[1], g.mci_field(kab[0], kab[1], self.mci_levels))
+                    clip.mci_of[gi] = (kab[0], kab[1], g.mci_field(kab[0], kab[1], self.mci_levels, **self.mci_kw))
                 ka, kb, field = clip.mci_of[gi]
-                dn = g.mci_frames(ka, kb, field, clip.sample_rate, k_first=c0 + 1, count=Tc, normalised="both" if self.panels else True)
+                dn = g.mci_frames(ka, kb, field, clip.sample_rate, k_first=c0 + 1, count=Tc, normalised="both" if self.panels else True,
+                                  **self.mci_kw)
                 if self.panels:
                     dn, dnu8 = dn
             else:
@@ -1502,7 +1512,8 @@ class _FolderPipeline:
             poses = [g[2] for g in got]
             if self.mci:                         # the host definition of the background frames (background.py)
                 ka, kb = clip.key_u8[k].numpy(), clip.key_u8[k + clip.sample_rate].numpy()
-                u8 = _background.mci_frames_host(ka, kb, _background.mci_field_host(ka, kb, self.mci_levels), clip.sample_rate, [i - k for i in frames])
+                u8 = _background.mci_frames_host(ka, kb, _background.mci_field_host(ka, kb, self.mci_levels, **self.mci_kw), clip.sample_rate,
+                                                 [i - k for i in frames], **self.mci_kw)
                 # the floats the native chain reads (the device's normalisation, stated on the host); the sheets' DAIN pane
                 # shows the host's normalisation, as the native path's does (normalise_exact)
                 dn = torch.from_numpy(_background.normalised_upload(u8)).unsqueeze(1)

@@ -39,6 +39,9 @@ quality on real footage has not been measured, and motion beyond +-32 px between
 `--mci-range 64` or `128` (default 32) widens the search by a fourth and a fifth pyramid level: the field then reaches 78 or 158 px
 of motion between key frames (38 at the default) for six or seven launches per group of segments where the default takes five.
 Still no occlusion reasoning and no sub-pel search, and a wider search has more room for a false match on periodic content.
+`--mci-border valid` (default `clamp`) is one-sided at the frame border: a strip that enters or leaves the frame between the two
+key frames is matched on, and taken from, the key frame that shows it, where `clamp` blends it with a smear of the other key
+frame's edge column.  Frame border only: a foreground object that covers background inside the frame is not handled.
 Frames are then named after their pose files.  The default, `--background dain`, is the reference's contract.
 
 Poses without a Predict_motion folder: `--poses keyframes --pose-dir DIR [--upsample-rate N] [--motion-config PATH]` runs stage 1
@@ -119,7 +122,8 @@ def summary_line(evaluator, rank=0, world=1):
                "reference (zlib 6)" if evaluator.png_compress_level is None else str(evaluator.png_compress_level),
                evaluator.batch or evaluator.default_batch(), "batch-invariant" if evaluator.reproducible else "per-batch",
                getattr(evaluator, "resize_on", "host"),
-               {"dain": "DAIN frames", "mci": "mci (interpolated from the key frames, range %d px)" % getattr(evaluator, "mci_range", 32)}
+               {"dain": "DAIN frames", "mci": "mci (interpolated from the key frames, range %d px, border %s)"
+                       % (getattr(evaluator, "mci_range", 32), getattr(evaluator, "mci_border", "clamp"))}
                [getattr(evaluator, "background", "dain")]))
     rep = getattr(evaluator, "metrics_report", None)
     if "metrics" in tm and rep is not None:
@@ -163,6 +167,7 @@ def main(opts):
                                              panel_quality=90 if opts.panel_quality is None else opts.panel_quality,
                                              panel_fps=30 if opts.panel_fps is None else opts.panel_fps,
                                              panel_encode=opts.panel_encode or "host", background=opts.background, mci_range=opts.mci_range,
+                                             mci_border=opts.mci_border,
                                              video=opts.video, video_fps=30 if opts.video_fps is None else opts.video_fps,
                                              video_quality=90 if opts.video_quality is None else opts.video_quality,
                                              video_frames=opts.video_frames, frames=opts.frames, **poses_kw)
@@ -232,6 +237,12 @@ def build_parser():
                              "(3, 4 or 5 pyramid levels; the field reaches 38, 78 or 158 px; five, six or seven launches per group of "
                              "segments). Fast pans and passing objects want 64 or 128; a wider search has more room for a false match "
                              "on periodic content, and there is still no occlusion reasoning and no sub-pel search")
+    parser.add_argument("--mci-border", default=None,
+                        help="with --background mci: what happens where a sample leaves the frame. 'clamp' (default): matching and "
+                             "sampling read the edge pixel; 'valid': one-sided at the frame border - a block is matched on the pixels both "
+                             "key frames show, a pixel that only one key frame shows is that key frame's sample alone (a hard switch), so a "
+                             "strip entering or leaving the frame shows its content, not a smear. Frame border only: no occlusion "
+                             "reasoning inside the frame")
     parser.add_argument("--video", action="store_true",
                         help="also write every frame of a clip, key frames included, as <save-dir>/Generated_frames/<clip>_video.avi "
                              "(Motion-JPEG; a frame is the JPEG of exactly the bytes its PNG holds, encoded on the GPU)")
@@ -275,6 +286,11 @@ def parse_args(argv=None):
     if opts.mci_range not in (None, 32, 64, 128):
         parser.error("--mci-range must be 32, 64 or 128, got %r" % (opts.mci_range,))
     opts.mci_range = 32 if opts.mci_range is None else opts.mci_range
+    if opts.mci_border is not None and opts.background != "mci":
+        parser.error("--mci-border is a setting of --background mci")
+    if opts.mci_border not in (None, "clamp", "valid"):
+        parser.error("--mci-border must be 'clamp' or 'valid', got %r" % (opts.mci_border,))
+    opts.mci_border = "clamp" if opts.mci_border is None else opts.mci_border
     if opts.background == "mci" and opts.resize_on == "gpu":
         parser.error("--background mci with --resize-on gpu is not supported (there is no DAIN list to plan the GPU resize for)")
     if opts.metrics and opts.gt_dir is None:

@@ -84,6 +84,7 @@ def main():
     ap.add_argument("--background", default="dain", choices=("dain", "mci"),
                     help="'mci': the background frames are interpolated on the GPU from the key frames and the clip's DAIN folder is not read (background=...)")
     ap.add_argument("--mci-range", type=int, default=32, choices=(32, 64, 128), help="with --background mci: the search's range in px between key frames (mci_range=...)")
+    ap.add_argument("--mci-border", default="clamp", choices=("clamp", "valid"), help="with --background mci: the border mode (mci_border=...)")
     ap.add_argument("--video", action="store_true", help="also write the frames as <clip>_video.avi, JPEG-encoded on the GPU (video=True)")
     ap.add_argument("--frames", default="png", choices=("png", "none"), help="with --video: 'none' writes no PNG frames (frames=...)")
     ap.add_argument("--poses", default="folder", choices=("folder", "keyframes"),
@@ -97,6 +98,8 @@ def main():
         ap.error("--background mci with --resize-on gpu is not supported")
     if a.mci_range != 32 and a.background != "mci":
         ap.error("--mci-range is a setting of --background mci")
+    if a.mci_border != "clamp" and a.background != "mci":
+        ap.error("--mci-border is a setting of --background mci")
     if a.panel_encode != "host" and not a.panels:
         ap.error("--panel-encode is a setting of --panels")
     if a.pose_mask and not a.metrics:
@@ -136,7 +139,8 @@ def main():
             out = E.evaluate_from_folder(G, *dirs, os.path.join(root, "out%d" % rep), gt_dir=os.path.join(root, "gt") if a.metrics else None,
                                          metrics=a.metrics, pose_mask=a.pose_mask, panels=a.panels, panel_encode=a.panel_encode,
                                          background=a.background, video=a.video, frames=a.frames, **kw,
-                                         **({"mci_range": a.mci_range} if a.background == "mci" else {}))
+                                         **({"mci_range": a.mci_range} if a.background == "mci" else {}),
+                                         **({"mci_border": a.mci_border} if a.mci_border != "clamp" else {}))
             torch.cuda.synchronize()
             walls.append(time.perf_counter() - t0)
         tm = dict(E.timings)
@@ -147,6 +151,7 @@ def main():
                       "batch": a.batch or E.default_batch(), "chunk": a.chunk, "io_threads": E.io_threads, "io_mode": a.io_mode,
                       "cpus": len(os.sched_getaffinity(0)), "cpu_budget": ev.cpu_budget(), "png_compress_level": a.compress,
                       "src_height": a.src_height or H, "src_width": a.src_width or W, "resize_on": a.resize_on, "background": a.background, "mci_range": a.mci_range if a.background == "mci" else None,
+                      "mci_border": a.mci_border if a.background == "mci" else None,
                       "metrics": a.metrics, "pose_mask": a.pose_mask, "metrics_overall": overall, "panels": a.panels, "panel_encode": a.panel_encode,
                       "video": a.video, "frames_written": a.frames, "poses": a.poses, "stage1_plus_bridge_ms_per_clip": stage1_ms,
                       "wall_s": wall, "wall_s_runs": [round(w, 4) for w in walls[1:]], "frames_per_s_end_to_end": n / wall,

@@ -2,10 +2,11 @@
 """The motion-compensated background on its own: rib_mci_field and rib_mci_frames (Generator.mci_field / mci_frames) on one
 unit - B segments of H x W at sample rate s - for a kernel trace.
 
-    rocprofv3 --kernel-trace --stats -d DIR -- python tools/mci_bench.py [--size 512] [--batch 4] [--rate 8] [--reps 20] [--u8] [--levels 3]
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/mci_bench.py [--size 512] [--batch 4] [--rate 8] [--reps 20] [--u8] [--levels 3] [--border clamp]
 
 --levels 3 (the default), 4 or 5: the pyramid levels of the field's search, the driver's --mci-range 32, 64 or 128; the scene's
-motion between the key frames grows with it (a quarter of that range in x, 3/16 in y).
+motion between the key frames grows with it (a quarter of that range in x, 3/16 in y).  --border valid: the one-sided border mode
+(the driver's --mci-border; k_mci_search<R, true> and k_mci_frames<true> in the trace).
 
 Prints one JSON line: the wall time of the field's launches (levels + 2: five by default) and of the frames launch between two events (median of
 --reps, after a warm-up), the frames launch's byte floor (12 bytes of float32 out per pixel and frame, 3 more with --u8, the
@@ -45,7 +46,9 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--u8", action="store_true", help="also write the uint8 NHWC frames (the sheets' DAIN pane)")
     ap.add_argument("--levels", type=int, default=3, choices=(3, 4, 5), help="pyramid levels of the search (--mci-range 32, 64, 128)")
+    ap.add_argument("--border", default="clamp", choices=("clamp", "valid"), help="the border mode (--mci-border)")
     a = ap.parse_args()
+    kw = {} if a.border == "clamp" else {"border": a.border}       # (clamp: the calls of before the mode existed)
     H, W, B, s = a.height or a.size, a.width or a.size, a.batch, a.rate
     m = 16 << (a.levels - 3)                   # margin of the scene around the key frames: the second crop moves by (m/2, -3m/8)
     G = rib.Generator(rib.hsm_gen_config()).eval()                 # no weights needed: these kernels read none
@@ -54,14 +57,14 @@ def main():
                                           size=(H + 2 * m, W + 2 * m), mode="bilinear", align_corners=False)
     big = (big + torch.rand(B, 3, H + 2 * m, W + 2 * m, device="cuda", generator=g) * 24).clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1)
     ka, kb = big[:, m:m + H, m:m + W].contiguous(), big[:, m - 3 * m // 8:m - 3 * m // 8 + H, m + m // 2:m + m // 2 + W].contiguous()
-    field = G.mci_field(ka, kb, a.levels)
+    field = G.mci_field(ka, kb, a.levels, **kw)
     T = s - 1
     f32 = torch.empty(T, B, 3, H, W, dtype=torch.float32, device="cuda")
     u8 = torch.empty(T, B, H, W, 3, dtype=torch.uint8, device="cuda") if a.u8 else None
-    fms = timed(lambda: G.mci_field(ka, kb, a.levels), a.reps)
-    rms = timed(lambda: G.mci_frames(ka, kb, field, s, normalised="both" if a.u8 else True, out=(f32, u8) if a.u8 else f32), a.reps)
+    fms = timed(lambda: G.mci_field(ka, kb, a.levels, **kw), a.reps)
+    rms = timed(lambda: G.mci_frames(ka, kb, field, s, normalised="both" if a.u8 else True, out=(f32, u8) if a.u8 else f32, **kw), a.reps)
     floor = (12 + (3 if a.u8 else 0)) * H * W * T * B + 2 * 3 * H * W * B
-    print(json.dumps({"height": H, "width": W, "batch": B, "rate": s, "levels": a.levels, "frames": T * B, "u8": a.u8,
+    print(json.dumps({"height": H, "width": W, "batch": B, "rate": s, "levels": a.levels, "border": a.border, "frames": T * B, "u8": a.u8,
                       "field_event_us_median": round(fms[len(fms) // 2] * 1e3, 2), "field_event_us_min": round(fms[0] * 1e3, 2),
                       "frames_event_us_median": round(rms[len(rms) // 2] * 1e3, 2), "frames_event_us_min": round(rms[0] * 1e3, 2),
                       "frames_floor_bytes": floor, "frames_floor_us_at_6.3TB/s": round(floor / 6.3e12 * 1e6, 2),
