@@ -280,52 +280,39 @@ int rib_jpeg_float(rib_handle* h, int T, int H, int W, const float* src_f32_nchw
  * This project's interpolation, NOT DAIN (the reference reads one DAIN frame per output frame; DAIN is an external network with
  * its own CUDA ops): the generator was trained on DAIN backgrounds and the quality of this substitute on real footage has not
  * been measured.  background.py (mci_field_host, mci_frames_host) states both results in integers - luma, a pyramid of
- * L = 3 levels, bilateral 8x8 block matching (full search over [-4,4]^2 on the top level - at quarter size, i.e. +-32 px of
- * motion between the key frames; +-1 refinements on every level below; the minimum of (cost, dx^2+dy^2, dy, dx)), a 3x3 median,
+ * L levels, bilateral 8x8 block matching (full search over [-4,4]^2 on the top level - with L = 3 at quarter size, i.e. +-32 px
+ * of motion between the key frames; +-1 refinements on every level below; the minimum of (cost, dx^2+dy^2, dy, dx)), a 3x3 median,
  * a bilinear per-pixel field in 1/256 px, two fixed-point bilinear samples and a blend - and the kernels are bit-equal to it.
  * No occlusion reasoning, no sub-pel search.
  * rib_mci_field: a_u8, b_u8 uint8 NHWC [B,H,W,3] on the device (left and right key frame of B segments at the model size) ->
  * field_i16 int16 [B,Hb,Wb,2] on the device, (dx, dy) per 8x8 block of the intermediate frame (rib_mci_field_shape:
- * Hb = ceil(H/8), Wb = ceil(W/8)); once per segment.  workspace: rib_mci_workspace_bytes(h, B, H, W) bytes on the device, 16-byte
- * aligned, nothing to clear.  Five launches on `stream` (luma + pyramid, three searches, median), no atomics, no
- * synchronisation: a segment's field does not depend on B.
- * rib_mci_field_levels / rib_mci_workspace_bytes_levels: the same with L = levels in 3, 4, 5 pyramid levels (the driver's
- * --mci-range 32, 64, 128: the nominal range 4 * 2^(L-1) * 2 px between the key frames).  The field's components reach 19, 39 or
- * 79, i.e. 38, 78 or 158 px of motion between the key frames; levels 3 and 4 of the pyramid come from the same launch as the
- * others and each extra level adds one +-1 search: L + 2 launches (five, six, seven; an added launch took 6.7 - 7.3 us on an MI355X
- * at 512x512, B = 4, the field 54 / 61 / 69 us of kernel time: profiles/r12_mci_range.txt), the same contracts otherwise.  A wider
- * search has more room for a false match on periodic content.  rib_mci_field and rib_mci_workspace_bytes ARE levels = 3: the
- * same workspace size, the same five launches.  levels outside 3..5: RIB_ERR_INVALID with a rib_last_error text, nothing
- * launched (the size query returns 0).  rib_mci_frames takes the field of any L.
+ * Hb = ceil(H/8), Wb = ceil(W/8)); once per segment.  levels: L = 3, 4 or 5 pyramid levels (the driver's --mci-range 32, 64, 128:
+ * the nominal range 4 * 2^(L-1) * 2 px between the key frames); the field's components reach 19, 39 or 79, i.e. 38, 78 or 158 px
+ * of motion between the key frames, and a wider search has more room for a false match on periodic content.  border (the
+ * driver's --mci-border; background.py's border=): 0 = "clamp", samples clamped to the edge; 1 = "valid", one-sided at the FRAME
+ * border: a block's pixel counts for a candidate d only when p - d and p + d both lie inside the level's plane (n pixels, a
+ * closed-form rectangle, of the block's N); a candidate is valid when 4 n >= N, costs (64 * SAD over those n) / n +
+ * LAMBDA (|dx| + |dy|), the winner is the minimum key over the valid candidates, and a block whose start candidate is not valid
+ * keeps its start.  workspace: rib_mci_workspace_bytes(h, B, H, W, levels) bytes on the device, 16-byte aligned, nothing to
+ * clear.  L + 2 launches on `stream` (luma + pyramid, one search per level, median: five, six, seven; an added launch took
+ * 6.7 - 7.3 us on an MI355X at 512x512, B = 4, the field 54 / 61 / 69 us of kernel time: profiles/r12_mci_range.txt), the same
+ * for either border; no atomics, no synchronisation: a segment's field does not depend on B.
  * rib_mci_frames: frames k_first .. k_first + T - 1 (0 <= k <= sample_rate, a power of two <= 1024; k = 0 is A, k = sample_rate
- * is B) of all B segments in ONE launch: out_f32_nchw float32 [T,B,3,H,W], ((u8 / 255 - 0.5) / 0.5) exactly as the driver's
- * upload computes it (the arithmetic of rib_resize_cubic's float output), and / or out_u8_nhwc uint8 [T,B,H,W,3]; a NULL output
- * is not wanted (both NULL is an error).  Every element written; a frame's bytes do not depend on T or B.
- * B outside 1..32767, B * Hb * Wb >= 2^30, T < 1, T * B > 65535, H or W outside 1..16384, a bad sample_rate or frame range, NULL or misaligned pointers:
- * RIB_ERR_INVALID with a rib_last_error text, nothing launched (the size query returns 0).
- * rib_mci_field_border / rib_mci_frames_border: the same with a border mode (the driver's --mci-border; background.py's
- * border=): 0 = "clamp", the results above - rib_mci_field_levels and rib_mci_frames ARE border = 0 of these two, the same
- * kernels; 1 = "valid", one-sided at the FRAME border.  Field: a block's pixel counts for a candidate d only when p - d and p + d
- * both lie inside the level's plane (n pixels, a closed-form rectangle, of the block's N); a candidate is valid when 4 n >= N,
- * costs (64 * SAD over those n) / n + LAMBDA (|dx| + |dy|), the winner is the minimum key over the valid candidates, and a block
- * whose start candidate is not valid keeps its start.  Frames: a sample is valid when its position lies in [0, (H-1) << 8] x
- * [0, (W-1) << 8]; where exactly one of the two samples is valid the output is that sample alone (a hard switch), otherwise the
- * blend.  Interior occlusion - a foreground object covering background - is NOT handled.  The same workspace size, the same
- * L + 2 launches and one launch, the same contracts; border outside {0, 1}: RIB_ERR_INVALID with a rib_last_error text,
- * nothing launched. */
+ * is B) of all B segments in ONE launch, from the field of any L: out_f32_nchw float32 [T,B,3,H,W], ((u8 / 255 - 0.5) / 0.5)
+ * exactly as the driver's upload computes it (the arithmetic of rib_resize_cubic's float output), and / or out_u8_nhwc uint8
+ * [T,B,H,W,3]; a NULL output is not wanted (both NULL is an error).  border: 0 = the blend of the two clamped samples; 1 = a
+ * sample is valid when its position lies in [0, (H-1) << 8] x [0, (W-1) << 8], and where exactly one of the two samples is
+ * valid the output is that sample alone (a hard switch), otherwise the blend.  Interior occlusion - a foreground object
+ * covering background - is NOT handled.  Every element written; a frame's bytes do not depend on T or B.
+ * levels outside 3..5, border outside {0, 1}, B outside 1..32767, B * Hb * Wb >= 2^30, T < 1, T * B > 65535, H or W outside
+ * 1..16384, a bad sample_rate or frame range, NULL or misaligned pointers: RIB_ERR_INVALID with a rib_last_error text, nothing
+ * launched (the size query returns 0). */
 void rib_mci_field_shape(int H, int W, int* Hb, int* Wb);
-size_t rib_mci_workspace_bytes(rib_handle* h, int B, int H, int W);
+size_t rib_mci_workspace_bytes(rib_handle* h, int B, int H, int W, int levels);
 int rib_mci_field(rib_handle* h, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
-                  void* workspace, void* hip_stream);
-size_t rib_mci_workspace_bytes_levels(rib_handle* h, int B, int H, int W, int levels);
-int rib_mci_field_levels(rib_handle* h, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
-                         int levels, void* workspace, void* hip_stream);
+                  int levels, int border, void* workspace, void* hip_stream);
 int rib_mci_frames(rib_handle* h, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const int16_t* field_i16,
-                   int sample_rate, int k_first, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream);
-int rib_mci_field_border(rib_handle* h, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
-                         int levels, int border, void* workspace, void* hip_stream);
-int rib_mci_frames_border(rib_handle* h, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const int16_t* field_i16,
-                          int sample_rate, int k_first, int border, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream);
+                   int sample_rate, int k_first, int border, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream);
 
 /* Extension op named by the north star but absent from the reference: bilinear
  * flow-grid warp, semantics of torch.nn.functional.grid_sample(img, base+flow*2/(size-1),

@@ -62,7 +62,8 @@ MAX_DISP = 2 * (2 * SEARCH_TOP + REFINE) + REFINE      # 19: the largest |dx|, |
 KEY_BIAS = 32             # pack_key: dy + 32, dx + 32 in 6 bits each (MAX_DISP < 32)
 WIDE_KEY_BIAS = 128       # pack_key_wide: dy + 128, dx + 128 in 8 bits each (max_disp(5) = 79 < 128)
 MAX_SAMPLE_RATE = 1024
-BORDERS = ("clamp", "valid")              # `border` of the functions below; rib_mci_*_border's 0 and 1
+BORDERS = ("clamp", "valid")              # `border` of the functions below; 0 and 1 of rib_mci_field / rib_mci_frames
+RANGES = {32: 3, 64: 4, 128: 5}           # the driver's mci_range (px of motion between the key frames) -> levels
 VALID_SHARE = 4           # border="valid": a candidate counts when VALID_SHARE * n >= N
 
 
@@ -96,6 +97,24 @@ def check_border(border, who):
     if not isinstance(border, str) or border not in BORDERS:
         raise ValueError("%s: border must be 'clamp' or 'valid', got %r" % (who, border))
     return border
+
+
+def check_settings(background, mci_range, mci_border, resize_on, who="evaluate_from_folder"):
+    """The folder driver's background settings -> (levels, border) for the functions below."""
+    if background not in ("dain", "mci"):
+        raise ValueError("%s: background must be 'dain' or 'mci', got %r" % (who, background))
+    if background == "mci" and resize_on == "gpu":
+        raise ValueError("%s: background='mci' with resize_on='gpu' is not supported (there is no DAIN list to "
+                         "plan the GPU resize for)" % who)
+    if mci_range not in RANGES:
+        raise ValueError("%s: mci_range must be 32, 64 or 128 (px of motion between key frames), got %r" % (who, mci_range))
+    if background != "mci" and mci_range != 32:
+        raise ValueError("%s: mci_range is a setting of background='mci'" % who)
+    if not isinstance(mci_border, str) or mci_border not in BORDERS:
+        raise ValueError("%s: mci_border must be 'clamp' or 'valid', got %r" % (who, mci_border))
+    if background != "mci" and mci_border != "clamp":
+        raise ValueError("%s: mci_border is a setting of background='mci'" % who)
+    return RANGES[mci_range], mci_border
 
 
 def max_disp(levels):

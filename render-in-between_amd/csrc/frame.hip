@@ -364,16 +364,14 @@ void rib_mci_field_shape(int H, int W, int* Hb, int* Wb) {
   if (Wb) *Wb = W < 1 ? 0 : (W + MCI_BLOCK - 1) / MCI_BLOCK;
 }
 
-size_t rib_mci_workspace_bytes_levels(rib_handle* h, int B, int H, int W, int levels) {
+size_t rib_mci_workspace_bytes(rib_handle* h, int B, int H, int W, int levels) {
   MciLayout L;
   if (!h || !mci_layout(B, H, W, levels, &L)) return 0;
   return L.total;
 }
 
-size_t rib_mci_workspace_bytes(rib_handle* h, int B, int H, int W) { return rib_mci_workspace_bytes_levels(h, B, H, W, MCI_MIN_LEVELS); }
-
-int rib_mci_field_border(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
-                         int levels, int border, void* workspace, void* hip_stream) {
+int rib_mci_field(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
+                  int levels, int border, void* workspace, void* hip_stream) {
   FrameState* h = frame_state(handle);
   if (!h) return RIB_ERR_INVALID;
   if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_mci_field: host-only handle");
@@ -421,18 +419,8 @@ int rib_mci_field_border(rib_handle* handle, int B, int H, int W, const uint8_t*
   return RIB_OK;
 }
 
-int rib_mci_field_levels(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
-                         int levels, void* workspace, void* hip_stream) {
-  return rib_mci_field_border(handle, B, H, W, a_u8, b_u8, field_i16, levels, 0, workspace, hip_stream);
-}
-
-int rib_mci_field(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
-                  void* workspace, void* hip_stream) {
-  return rib_mci_field_levels(handle, B, H, W, a_u8, b_u8, field_i16, MCI_MIN_LEVELS, workspace, hip_stream);
-}
-
-int rib_mci_frames_border(rib_handle* handle, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const int16_t* field_i16,
-                          int sample_rate, int k_first, int border, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream) {
+int rib_mci_frames(rib_handle* handle, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const int16_t* field_i16,
+                   int sample_rate, int k_first, int border, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream) {
   FrameState* h = frame_state(handle);
   if (!h) return RIB_ERR_INVALID;
   if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_mci_frames: host-only handle");
@@ -461,10 +449,5 @@ int rib_mci_frames_border(rib_handle* handle, int T, int B, int H, int W, const 
   else hipLaunchKernelGGL(k_mci_frames<false>, dim3(H, T * B), dim3(256), lds, reinterpret_cast<hipStream_t>(hip_stream), fp);
   HIP_TRY(h, hipGetLastError());
   return RIB_OK;
-}
-
-int rib_mci_frames(rib_handle* handle, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const int16_t* field_i16,
-                   int sample_rate, int k_first, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream) {
-  return rib_mci_frames_border(handle, T, B, H, W, a_u8, b_u8, field_i16, sample_rate, k_first, 0, out_f32_nchw, out_u8_nhwc, hip_stream);
 }
 }  // extern "C"

@@ -50,8 +50,6 @@ import numpy as np
 import torch
 
 from . import background as _background
-
-MCI_RANGES = {32: 3, 64: 4, 128: 5}      # evaluate_from_folder's mci_range (px of motion between key frames) -> pyramid levels
 from . import io_worker, rasterise
 from . import metrics as _metrics
 from . import panel as _panel
@@ -608,19 +606,7 @@ class Evaluator:
                 raise ValueError("evaluate_from_folder: poses=%r needs motion= (the motion model, motion.model.ModelInference)" % (poses,))
             if not (isinstance(upsample_rate, int) and upsample_rate >= 1 and upsample_rate & (upsample_rate - 1) == 0):
                 raise ValueError("evaluate_from_folder: upsample_rate must be a power of two, got %r" % (upsample_rate,))
-        if background not in ("dain", "mci"):
-            raise ValueError("evaluate_from_folder: background must be 'dain' or 'mci', got %r" % (background,))
-        if background == "mci" and self.resize_on == "gpu":
-            raise ValueError("evaluate_from_folder: background='mci' with resize_on='gpu' is not supported (there is no DAIN list to "
-                             "plan the GPU resize for)")
-        if mci_range not in MCI_RANGES:
-            raise ValueError("evaluate_from_folder: mci_range must be 32, 64 or 128 (px of motion between key frames), got %r" % (mci_range,))
-        if background != "mci" and mci_range != 32:
-            raise ValueError("evaluate_from_folder: mci_range is a setting of background='mci'")
-        if not isinstance(mci_border, str) or mci_border not in _background.BORDERS:
-            raise ValueError("evaluate_from_folder: mci_border must be 'clamp' or 'valid', got %r" % (mci_border,))
-        if background != "mci" and mci_border != "clamp":
-            raise ValueError("evaluate_from_folder: mci_border is a setting of background='mci'")
+        mci_levels, mci_border = _background.check_settings(background, mci_range, mci_border, self.resize_on)
         if gen_vid:
             # the reference also writes <save_dir>/<clip>.mp4 (evaluator.py:267-269, utils.make_video) from a matplotlib canvas
             # through an H.264 encoder; neither is built, and silently ignoring the flag would drop an output the caller asked for
@@ -652,7 +638,7 @@ class Evaluator:
         self.metrics = self.metrics_report = None
         pipe = _FolderPipeline(self, model, rank, world, gt_dir, metrics=bool(metrics), mask_dir=mask_dir, pose_mask=bool(pose_mask),
                                panels=bool(panels), panel_frames=bool(panel_frames), panel_quality=int(panel_quality),
-                               panel_encode=panel_encode, background=background, mci_levels=MCI_RANGES[mci_range], mci_border=mci_border, video=bool(video), video_quality=int(video_quality),
+                               panel_encode=panel_encode, background=background, mci_levels=mci_levels, mci_border=mci_border, video=bool(video), video_quality=int(video_quality),
                                video_frames=bool(video_frames), write_png=frames == "png",
                                key_poses=None if poses == "folder" else (motion, key_pose_dir, upsample_rate, poses == "keyframes-linear", bool(save_poses)))
         self.background, self.mci_range, self.mci_border = background, mci_range, mci_border
@@ -764,8 +750,7 @@ class _FolderPipeline:
                  panels=False, panel_frames=False, panel_quality=90, panel_encode="host", background="dain", mci_levels=3,
                  video=False, video_quality=90, video_frames=False, write_png=True, key_poses=None, mci_border="clamp"):
         self.mci, self.mci_levels = background == "mci", mci_levels      # (levels: background.mci_field_host's, from mci_range)
-        self.mci_border = mci_border        # background.py's border; "clamp": the calls below are those of before the mode existed
-        self.mci_kw = {} if mci_border == "clamp" else {"border": mci_border}
+        self.mci_border = mci_border        # background.py's border
         # poses="keyframes": (motion model, key-pose folder, upsample rate, take the linear clip, also write the json folders)
         self.key_poses = key_poses
         # video: the frames' JPEG files (video.py); write_png False (frames="none"): they are the only files of a frame
@@ -1125,10 +1110,10 @@ class _FolderPipeline:
                         mk[0, b].copy_(clip.key_u8[k])
                         mk[1, b].copy_(clip.key_u8[k + clip.sample_rate])
                     kab = mk.to(g.device, non_blocking=True)
-                    clip.mci_of[gi] = (kab[0], kab[1], g.mci_field(kab[0], kab[1], self.mci_levels, **self.mci_kw))
+                    clip.mci_of[gi] = (kab[0], kab[1], g.mci_field(kab[0], kab[1], self.mci_levels, border=self.mci_border))
                 ka, kb, field = clip.mci_of[gi]
                 dn = g.mci_frames(ka, kb, field, clip.sample_rate, k_first=c0 + 1, count=Tc, normalised="both" if self.panels else True,
-                                  **self.mci_kw)
+                                  border=self.mci_border)
                 if self.panels:
                     dn, dnu8 = dn
             else:
@@ -1512,8 +1497,8 @@ class _FolderPipeline:
             poses = [g[2] for g in got]
             if self.mci:                         # the host definition of the background frames (background.py)
                 ka, kb = clip.key_u8[k].numpy(), clip.key_u8[k + clip.sample_rate].numpy()
-                u8 = _background.mci_frames_host(ka, kb, _background.mci_field_host(ka, kb, self.mci_levels, **self.mci_kw), clip.sample_rate,
-                                                 [i - k for i in frames], **self.mci_kw)
+                u8 = _background.mci_frames_host(ka, kb, _background.mci_field_host(ka, kb, self.mci_levels, border=self.mci_border), clip.sample_rate,
+                                                 [i - k for i in frames], border=self.mci_border)
                 # the floats the native chain reads (the device's normalisation, stated on the host); the sheets' DAIN pane
                 # shows the host's normalisation, as the native path's does (normalise_exact)
                 dn = torch.from_numpy(_background.normalised_upload(u8)).unsqueeze(1)

@@ -567,7 +567,7 @@ class Generator:
         return a, b, single
 
     def mci_field(self, a_u8, b_u8, levels=3, border="clamp"):
-        """The block displacement field of B key-frame pairs on the GPU (rib_mci_field_border; background.mci_field_host is the
+        """The block displacement field of B key-frame pairs on the GPU (rib_mci_field; background.mci_field_host is the
         definition and is bit-equal): a_u8, b_u8 uint8 [B,H,W,3] (or [H,W,3]) on this device, the left and right key frame of
         each segment at the model size -> int16 [B,Hb,Wb,2] (or [Hb,Wb,2]), (dx, dy) per 8x8 block.  levels: 3 (the default),
         4 or 5 pyramid levels, a search over 32, 64 or 128 px of motion between the key frames.  This project's
@@ -578,20 +578,20 @@ class Generator:
         border = BORDERS.index(check_border(border, "mci_field"))
         a, b, single = self._mci_pair(a_u8, b_u8, "mci_field")
         B, H, W, _ = a.shape
-        n = int(self._lib.rib_mci_workspace_bytes_levels(self._h, B, H, W, levels))
+        n = int(self._lib.rib_mci_workspace_bytes(self._h, B, H, W, levels))
         if n == 0:
             raise ValueError("mci_field: B=%d H=%d W=%d: 1 <= B <= 32767, H and W in 1..16384" % (B, H, W))
         Hb, Wb = field_shape(H, W)
         with torch.cuda.device(self.device):
             ws = torch.empty(n, dtype=torch.uint8, device=self.device)      # (per call: it belongs to the stream the call is enqueued on)
             field = torch.empty((B, Hb, Wb, 2), dtype=torch.int16, device=self.device)
-            _native.check(self._h, self._lib.rib_mci_field_border(self._h, B, H, W, _ptr(a), _ptr(b), _ptr(field), levels, border, _ptr(ws),
-                                                                  self._stream()))
+            _native.check(self._h, self._lib.rib_mci_field(self._h, B, H, W, _ptr(a), _ptr(b), _ptr(field), levels, border, _ptr(ws),
+                                                           self._stream()))
         return field[0] if single else field
 
     def mci_frames(self, a_u8, b_u8, field, sample_rate, k_first=1, count=None, normalised=True, out=None, border="clamp"):
         """Frames k_first .. k_first + count - 1 (count None: up to sample_rate - 1) of B segments from their key frames and
-        block fields, all in one launch (rib_mci_frames_border; background.mci_frames_host is the definition and is bit-equal):
+        block fields, all in one launch (rib_mci_frames; background.mci_frames_host is the definition and is bit-equal):
         a_u8, b_u8 uint8 [B,H,W,3], field int16 [B,Hb,Wb,2] (mci_field) on this device, sample_rate a power of two.
         normalised=True: float32 [T,B,3,H,W], ToTensor + Normalize(0.5, 0.5) as the folder driver's upload computes it;
         False: uint8 [T,B,H,W,3]; "both": the pair (float32, uint8).  [H,W,3] key frames give [T,3,H,W] / [T,H,W,3].
@@ -628,8 +628,8 @@ class Generator:
         with torch.cuda.device(self.device):
             rf = dest(of, fshape, torch.float32) if normalised in (True, "both") else None
             ru = dest(ou, ushape, torch.uint8) if normalised in (False, "both") else None
-            _native.check(self._h, self._lib.rib_mci_frames_border(self._h, T, B, H, W, _ptr(a), _ptr(b), _ptr(f), s, k_first, border,
-                                                                   _ptr(rf), _ptr(ru), self._stream()))
+            _native.check(self._h, self._lib.rib_mci_frames(self._h, T, B, H, W, _ptr(a), _ptr(b), _ptr(f), s, k_first, border,
+                                                            _ptr(rf), _ptr(ru), self._stream()))
         res = tuple((r[:, 0] if single else r) for r in (rf, ru) if r is not None)
         return res if normalised == "both" else res[0]
 

@@ -2,6 +2,7 @@
 reference-protocol path on it (no GPU).  Scenes: seeded band-limited random textures - two octaves of Gaussian-filtered noise,
 sigma 8 px (it survives to pyramid level 2, whose Nyquist wavelength is 8 px) and sigma 2.5 px (detail inside an 8x8 block)."""
 import os
+import re
 import socket
 
 import numpy as np
@@ -573,4 +574,6 @@ def test_abi_is_declared_and_bound():
     hdr = open(os.path.join(ROOT, "include", "rib.h")).read()
     for name in ("rib_mci_field_shape", "rib_mci_workspace_bytes", "rib_mci_field", "rib_mci_frames"):
         assert name + "(" in hdr and name in _native.SIGNATURES
-    assert len(_native.SIGNATURES["rib_mci_frames"][1]) == 13 and len(_native.SIGNATURES["rib_mci_field"][1]) == 9
+    assert len(_native.SIGNATURES["rib_mci_frames"][1]) == 14 and len(_native.SIGNATURES["rib_mci_field"][1]) == 11
+    declared = re.findall(r"^\w+ (rib_mci_\w+)\(", hdr, re.M)                 # one entry per operation, and the shape query
+    assert len(declared) == 4 and set(declared) == {n for n in _native.SIGNATURES if n.startswith("rib_mci_")}

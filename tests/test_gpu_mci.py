@@ -115,9 +115,9 @@ def test_outputs_float_uint8_and_null(h, w):
     G.mci_frames(ta, tb, tf, 4, normalised=False, out=only_u)
     assert torch.equal(only_f, f32) and torch.equal(only_u, u8)
     L = G._lib
-    assert L.rib_mci_frames(G._h, 1, 1, h, w, ta.data_ptr(), tb.data_ptr(), tf.data_ptr(), 4, 1, None, None, None) != 0
+    assert L.rib_mci_frames(G._h, 1, 1, h, w, ta.data_ptr(), tb.data_ptr(), tf.data_ptr(), 4, 1, 0, None, None, None) != 0
     assert b"both outputs are null" in L.rib_last_error(G._h)
-    assert L.rib_mci_frames(G._h, 1, 1, h, w, ta.data_ptr(), tb.data_ptr(), tf.data_ptr(), 3, 1, only_f.data_ptr(), None, None) != 0
+    assert L.rib_mci_frames(G._h, 1, 1, h, w, ta.data_ptr(), tb.data_ptr(), tf.data_ptr(), 3, 1, 0, only_f.data_ptr(), None, None) != 0
     assert b"power of two" in L.rib_last_error(G._h)
     with pytest.raises(ValueError, match="outside the segment"):
         G.mci_frames(ta, tb, tf, 4, k_first=3, count=3)

@@ -1,7 +1,8 @@
-"""rib_mci_field_border / rib_mci_frames_border (csrc/mci.hip.h: k_mci_search<R, true>, k_mci_frames<true>;
+"""rib_mci_field / rib_mci_frames with border = 1 (csrc/mci.hip.h: k_mci_search<R, true>, k_mci_frames<true>;
 Generator.mci_field / mci_frames(..., border="valid")) - the one-sided border mode of the interpolated backgrounds - against
-background.py's border="valid", bit for bit; border = 0 through the new entries against the old entries; and the folder driver
+background.py's border="valid", bit for bit; border = 0 as the default of both; and the folder driver
 with mci_border="valid".  The inputs and what they must reach are built and held in tests/test_mci_border_cpu.py."""
+import functools
 import os
 
 import numpy as np
@@ -10,6 +11,7 @@ import torch
 
 import render_in_between_amd as rib
 from render_in_between_amd import background as bg, evaluator as ev
+from tests.mci_gpu_common import check_defaults, check_field, dev, ref
 from tests.test_background_cpu import moving_pair, random_pair, tie_pair
 from tests.test_gpu_mci import Protocol, handle
 from tests.test_mci_border_cpu import BORDER_TIE_KINDS, GPU_PARTIAL_SIZES, GPU_TRANSLATIONS, INHERIT, ODD_SIZES, gpu_translation_pairs
@@ -19,36 +21,11 @@ pytestmark = pytest.mark.gpu
 
 LEVELS = (3, 4, 5)
 RIB_ERR_INVALID = -1                                                    # include/rib.h
-_PAIRS, _REF = {}, {}
-
-
-def ref(key, levels, make):
-    """(a, b, field) of the definition with border="valid": an input is built once, a field computed once."""
-    if key not in _PAIRS:
-        _PAIRS[key] = make()
-    if (key, levels) not in _REF:
-        _REF[key, levels] = _PAIRS[key] + (bg.mci_field_host(*_PAIRS[key], levels, border="valid"),)
-    return _REF[key, levels]
+_translation_pairs = functools.lru_cache(None)(gpu_translation_pairs)
 
 
 def translation_refs(levels):
-    if ("shift", levels, 0) not in _PAIRS:
-        for i, pair in enumerate(gpu_translation_pairs(levels)):
-            _PAIRS["shift", levels, i] = pair
-    return [ref(("shift", levels, i), levels, None) for i in range(len(GPU_TRANSLATIONS[levels][2]))]
-
-
-def dev(G, *arrays):
-    return tuple(torch.from_numpy(np.ascontiguousarray(x)).to(G.device) for x in arrays)
-
-
-def check_field(G, refs, levels):
-    ta, tb = dev(G, np.stack([r[0] for r in refs]), np.stack([r[1] for r in refs]))
-    field = G.mci_field(ta, tb, levels, border="valid")
-    want = np.stack([r[2] for r in refs])
-    assert field.dtype == torch.int16 and tuple(field.shape) == want.shape
-    assert torch.equal(field.cpu(), torch.from_numpy(want)), (levels, refs[0][0].shape)
-    return field
+    return [ref(("shift", levels, i), lambda: _translation_pairs(levels)[i], levels, "valid") for i in range(len(GPU_TRANSLATIONS[levels][2]))]
 
 
 def check_frames(G, r, s, k_first, count, normalised="both"):
@@ -74,9 +51,9 @@ def test_translation_fields_in_a_batch_and_alone(levels):
     refs = translation_refs(levels)
     for (dx, dy), r in zip(GPU_TRANSLATIONS[levels][2], refs):
         assert (r[2] == (dx, dy)).all()
-    batch = check_field(G, refs, levels)
+    batch = check_field(G, refs, levels, "valid")
     for i, r in enumerate(refs):
-        assert torch.equal(check_field(G, [r], levels)[0], batch[i])
+        assert torch.equal(check_field(G, [r], levels, "valid")[0], batch[i])
         frames = check_frames(G, r, 8, 0, 9)
         assert np.array_equal(frames[0], r[0]) and np.array_equal(frames[8], r[1])
         assert not np.array_equal(frames[3], bg.mci_frames_host(r[0], r[1], r[2], 8, [3])[0])        # (the mode decides pixels here)
@@ -87,26 +64,26 @@ def test_translation_fields_in_a_batch_and_alone(levels):
 def test_partial_blocks_and_tiles(h, w, levels):
     """67 x 93, 130 x 250: N < 64 on every level, a last run of fewer than MCI_RUN blocks; a pan and unrelated content."""
     G = handle()
-    refs = [ref(("pan", h, w), levels, lambda: moving_pair(h, w, 30, -20, 50)), ref(("rand", h, w), levels, lambda: random_pair(h, w, 2))]
+    refs = [ref(("pan", h, w), lambda: moving_pair(h, w, 30, -20, 50), levels, "valid"), ref(("rand", h, w), lambda: random_pair(h, w, 2), levels, "valid")]
     assert refs[0][2].any() and not np.array_equal(refs[0][2], bg.mci_field_host(refs[0][0], refs[0][1], levels))
-    check_field(G, refs, levels)
+    check_field(G, refs, levels, "valid")
     check_frames(G, refs[0], 8, 0, 9)
 
 
 def test_inherited_blocks():
     """A 38 px pan in a 56 px frame: half of the level-0 blocks keep their start (tests/test_mci_border_cpu.py counts them)."""
     G = handle()
-    r = ref(("inherit",), 3, lambda: moving_pair(*INHERIT))
-    check_field(G, [r], 3)
+    r = ref(("inherit",), lambda: moving_pair(*INHERIT), 3, "valid")
+    check_field(G, [r], 3, "valid")
     check_frames(G, r, 8, 1, 7)
 
 
 @pytest.mark.parametrize("levels", LEVELS)
 def test_ties_under_the_normalised_cost(levels):
     G = handle()
-    refs = [ref(("tie", kind), levels, lambda: tie_pair(kind, 64, 64)) for kind in BORDER_TIE_KINDS]
+    refs = [ref(("tie", kind), lambda: tie_pair(kind, 64, 64), levels, "valid") for kind in BORDER_TIE_KINDS]
     assert any(r[2].any() for r in refs)
-    check_field(G, refs, levels)
+    check_field(G, refs, levels, "valid")
     check_frames(G, refs[3], 4, 1, 3)
 
 
@@ -115,8 +92,8 @@ def test_ties_under_the_normalised_cost(levels):
 def test_sizes_down_to_one_pixel(h, w, levels):
     """1 x 1 .. 40 x 1: planes with room for d = 0 alone, blocks of one pixel row or column."""
     G = handle()
-    r = ref(("odd", h, w), levels, lambda: random_pair(h, w, 1))
-    check_field(G, [r], levels)
+    r = ref(("odd", h, w), lambda: random_pair(h, w, 1), levels, "valid")
+    check_field(G, [r], levels, "valid")
     check_frames(G, r, 4, 0, 5)
 
 
@@ -125,11 +102,11 @@ def test_a_saturated_wide_pair(levels):
     """About twice the range between the key frames: long vectors, and inheritance where they leave the frame."""
     G = handle()
     if levels == 3:
-        r = ref(("long", 3), 3, lambda: moving_pair(96, 160, -38, 36, 21))
+        r = ref(("long", 3), lambda: moving_pair(96, 160, -38, 36, 21), 3, "valid")
     else:
-        r = ref(("long", levels), levels, lambda: wide_pair(levels, 96, 160, 2 if levels == 5 else 0))
+        r = ref(("long", levels), lambda: wide_pair(levels, 96, 160, 2 if levels == 5 else 0), levels, "valid")
     assert np.abs(r[2]).max() > {3: 16, 4: 32, 5: 64}[levels]
-    check_field(G, [r], levels)
+    check_field(G, [r], levels, "valid")
     check_frames(G, r, 8, 0, 9)
 
 
@@ -141,7 +118,7 @@ def test_sample_rates_one_and_1024():
     assert np.array_equal(frames[0], r[0]) and np.array_equal(frames[1], r[1])
     for k in (0, 1, 512, 1023, 1024):
         check_frames(G, r, bg.MAX_SAMPLE_RATE, k, 1)
-    r = ref(("long", 5), 5, lambda: wide_pair(5, 96, 160, 2))          # the widest field at the largest rate
+    r = ref(("long", 5), lambda: wide_pair(5, 96, 160, 2), 5, "valid")          # the widest field at the largest rate
     for k in (1, 1023):
         check_frames(G, r, bg.MAX_SAMPLE_RATE, k, 1)
 
@@ -151,7 +128,7 @@ def test_outputs_strips_and_unaligned_destinations(h, w):
     """W = 1030: a thread takes a second strip of four pixels, W % 4 = 2; W = 93: W % 4 = 1.  Float only, uint8 only and both;
     then the uint8 output 1 and 7 bytes off a 16-byte line of a larger allocation, around which nothing may change."""
     G = handle()
-    r = ref(("strip", h, w), 3, lambda: moving_pair(h, w, 36, -4, 30 + h))
+    r = ref(("strip", h, w), lambda: moving_pair(h, w, 36, -4, 30 + h), 3, "valid")
     a, b, f = r
     assert f.any()
     want = check_frames(G, r, 4, 1, 3, normalised="both")
@@ -171,38 +148,13 @@ def test_outputs_strips_and_unaligned_destinations(h, w):
 
 
 # ---- mode equivalence and errors ---------------------------------------------------------------------------------------------------
-def test_border_zero_through_the_new_entries_is_the_old_entries():
+def test_the_clamp_border_is_the_default_at_every_level():
+    """On saturated, tied, tiny and wide inputs at their levels (mci_gpu_common.check_defaults)."""
     G = handle()
-    L = G._lib
     inputs = [(5, wide_pair(5, 96, 160, 1)), (4, wide_pair(4, 67, 93, 0)), (3, tie_pair("checker8", 67, 93)), (3, random_pair(33, 15, 1)),
               (4, random_pair(1, 1, 1)), (3, moving_pair(16, 1030, 36, -4, 46))]
     for levels, (a, b) in inputs:
-        h, w = a.shape[:2]
-        ta, tb = dev(G, a, b)
-        ws = torch.empty(L.rib_mci_workspace_bytes_levels(G._h, 1, h, w, levels), dtype=torch.uint8, device=G.device)
-        Hb, Wb = bg.field_shape(h, w)
-        old = torch.full((Hb, Wb, 2), 77, dtype=torch.int16, device=G.device)
-        new = torch.full((Hb, Wb, 2), 78, dtype=torch.int16, device=G.device)
-        assert L.rib_mci_field_levels(G._h, 1, h, w, ta.data_ptr(), tb.data_ptr(), old.data_ptr(), levels, ws.data_ptr(), None) == 0
-        assert L.rib_mci_field_border(G._h, 1, h, w, ta.data_ptr(), tb.data_ptr(), new.data_ptr(), levels, 0, ws.data_ptr(), None) == 0
-        torch.cuda.synchronize()
-        assert torch.equal(old, new) and torch.equal(old.cpu(), torch.from_numpy(bg.mci_field_host(a, b, levels)))
-        assert torch.equal(G.mci_field(ta, tb, levels), old) and torch.equal(G.mci_field(ta, tb, levels, border="clamp"), old)
-        T = 5
-        outs = []
-        for entry in ("old", "new"):
-            f32 = torch.full((T, 1, 3, h, w), 7.0, device=G.device)
-            u8 = torch.full((T, 1, h, w, 3), 9, dtype=torch.uint8, device=G.device)
-            args = (G._h, T, 1, h, w, ta.data_ptr(), tb.data_ptr(), old.data_ptr(), 4, 0)
-            if entry == "old":
-                assert L.rib_mci_frames(*args, f32.data_ptr(), u8.data_ptr(), None) == 0
-            else:
-                assert L.rib_mci_frames_border(*args, 0, f32.data_ptr(), u8.data_ptr(), None) == 0
-            outs.append((f32, u8))
-        torch.cuda.synchronize()
-        assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
-        assert torch.equal(outs[0][1][:, 0].cpu(), torch.from_numpy(bg.mci_frames_host(a, b, old.cpu().numpy(), 4, range(5))))
-        assert torch.equal(G.mci_frames(ta, tb, old, 4, k_first=0, count=T, normalised=False, border="clamp"), outs[0][1][:, 0])
+        check_defaults(G, a, b, levels)
 
 
 def test_a_bad_border_through_the_c_abi():
@@ -212,14 +164,14 @@ def test_a_bad_border_through_the_c_abi():
     a, b = random_pair(h, w, 1)
     ta, tb = dev(G, a, b)
     Hb, Wb = bg.field_shape(h, w)
-    ws = torch.empty(L.rib_mci_workspace_bytes_levels(G._h, 1, h, w, 3), dtype=torch.uint8, device=G.device)
+    ws = torch.empty(L.rib_mci_workspace_bytes(G._h, 1, h, w, 3), dtype=torch.uint8, device=G.device)
     zero = torch.zeros((Hb, Wb, 2), dtype=torch.int16, device=G.device)
     for bad in (2, -1, 255):
         field = torch.full((Hb, Wb, 2), 77, dtype=torch.int16, device=G.device)
-        rc = L.rib_mci_field_border(G._h, 1, h, w, ta.data_ptr(), tb.data_ptr(), field.data_ptr(), 3, bad, ws.data_ptr(), None)
+        rc = L.rib_mci_field(G._h, 1, h, w, ta.data_ptr(), tb.data_ptr(), field.data_ptr(), 3, bad, ws.data_ptr(), None)
         assert rc == RIB_ERR_INVALID and b"border=%d" % bad in L.rib_last_error(G._h)
         out = torch.full((1, 1, h, w, 3), 9, dtype=torch.uint8, device=G.device)
-        rc = L.rib_mci_frames_border(G._h, 1, 1, h, w, ta.data_ptr(), tb.data_ptr(), zero.data_ptr(), 4, 1, bad, None, out.data_ptr(), None)
+        rc = L.rib_mci_frames(G._h, 1, 1, h, w, ta.data_ptr(), tb.data_ptr(), zero.data_ptr(), 4, 1, bad, None, out.data_ptr(), None)
         assert rc == RIB_ERR_INVALID and b"border=%d" % bad in L.rib_last_error(G._h)
         torch.cuda.synchronize()
         assert (field == 77).all() and (out == 9).all()                     # nothing was launched

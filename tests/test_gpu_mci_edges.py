@@ -9,25 +9,12 @@ import pytest
 import torch
 
 from render_in_between_amd import background as bg
+from tests.mci_gpu_common import dev, ref
 from tests.test_background_cpu import (LONG_MOTIONS, LONG_SIZES, TIE_KINDS, TIE_SIZES, TINY_SIZES, WIDE_SIZES, long_pair, moving_pair,
                                        random_pair, texture, tie_pair, wide_pair)
 from tests.test_gpu_mci import handle
 
 pytestmark = pytest.mark.gpu
-
-_REF = {}
-
-
-def ref(key, make):
-    """(a, b, field) of the definition, computed once per input."""
-    if key not in _REF:
-        a, b = make()
-        _REF[key] = (a, b, bg.mci_field_host(a, b))
-    return _REF[key]
-
-
-def dev(G, *arrays):
-    return tuple(torch.from_numpy(np.ascontiguousarray(x)).to(G.device) for x in arrays)
 
 
 def check_pairs(G, refs, s, ks=None, both=True):

@@ -1,4 +1,4 @@
-"""rib_mci_field_levels (csrc/mci.hip.h; Generator.mci_field(..., levels)) with four and five pyramid levels - the driver's
+"""rib_mci_field (csrc/mci.hip.h; Generator.mci_field(..., levels)) with four and five pyramid levels - the driver's
 mci_range = 64 and 128 - against background.mci_field_host(..., levels), bit for bit: fields saturated at +-39 and +-79 (beyond
 what the old 6-bit key fields held), ties on the new top levels, frames smaller than a top-level block and pyramid levels of
 1 x 1, batches, rib_mci_frames on such a field, and the native folder driver.  tests/test_mci_range_cpu.py builds the inputs and
@@ -11,6 +11,7 @@ import torch
 
 import render_in_between_amd as rib
 from render_in_between_amd import background as bg, evaluator as ev
+from tests.mci_gpu_common import check_defaults, check_field, dev, ref
 from tests.test_background_cpu import random_pair, tie_pair
 from tests.test_gpu_mci import Protocol, handle
 from tests.test_mci_range_cpu import ODD_SIZES, WIDE_MOTIONS, WIDE_SIZES, WIDE_TIE_KINDS, WIDE_TIE_SIZES, wide_pair, write_moving_clips
@@ -19,33 +20,10 @@ pytestmark = pytest.mark.gpu
 
 LEVELS = (4, 5)
 RIB_ERR_INVALID = -1                                                    # include/rib.h
-_PAIRS, _REF = {}, {}
-
-
-def ref(key, levels, make):
-    """(a, b, field) of the definition with `levels` levels: an input is built once, a field computed once."""
-    if key not in _PAIRS:
-        _PAIRS[key] = make()
-    if (key, levels) not in _REF:
-        _REF[key, levels] = _PAIRS[key] + (bg.mci_field_host(*_PAIRS[key], levels),)
-    return _REF[key, levels]
 
 
 def wide_ref(levels, h, w, i):
-    return ref(("wide", levels, h, w, i), levels, lambda: wide_pair(levels, h, w, i))
-
-
-def dev(G, *arrays):
-    return tuple(torch.from_numpy(np.ascontiguousarray(x)).to(G.device) for x in arrays)
-
-
-def check_field(G, refs, levels):
-    ta, tb = dev(G, np.stack([r[0] for r in refs]), np.stack([r[1] for r in refs]))
-    field = G.mci_field(ta, tb, levels)
-    want = np.stack([r[2] for r in refs])
-    assert field.dtype == torch.int16 and tuple(field.shape) == want.shape
-    assert torch.equal(field.cpu(), torch.from_numpy(want)), (levels, refs[0][0].shape)
-    return field
+    return ref(("wide", levels, h, w, i), lambda: wide_pair(levels, h, w, i), levels)
 
 
 @pytest.mark.parametrize("levels", LEVELS)
@@ -65,7 +43,7 @@ def test_fields_saturated_at_the_widest_displacement(h, w, levels):
 @pytest.mark.parametrize("h,w", WIDE_TIE_SIZES)
 def test_ties_on_the_new_top_levels(h, w, levels):
     G = handle()
-    refs = [ref(("tie", kind, h, w), levels, lambda: tie_pair(kind, h, w)) for kind in WIDE_TIE_KINDS]
+    refs = [ref(("tie", kind, h, w), lambda: tie_pair(kind, h, w), levels) for kind in WIDE_TIE_KINDS]
     assert any(r[2].any() for r in refs)
     check_field(G, refs, levels)
 
@@ -74,7 +52,7 @@ def test_ties_on_the_new_top_levels(h, w, levels):
 @pytest.mark.parametrize("h,w", ODD_SIZES)
 def test_sizes_down_to_one_pixel(h, w, levels):
     G = handle()
-    check_field(G, [ref(("odd", h, w), levels, lambda: random_pair(h, w, 1))], levels)
+    check_field(G, [ref(("odd", h, w), lambda: random_pair(h, w, 1), levels)], levels)
 
 
 @pytest.mark.parametrize("levels", LEVELS)
@@ -82,8 +60,8 @@ def test_a_batch_of_three_different_pairs(levels):
     """B = 3: the three single calls' fields - no pair reads another's planes or fields (the 2B images of the new levels)."""
     G = handle()
     h, w = WIDE_SIZES[1]
-    refs = [wide_ref(levels, h, w, 1), ref(("tie", "diagonal16", h, w), levels, lambda: tie_pair("diagonal16", h, w)),
-            ref(("rand", h, w), levels, lambda: random_pair(h, w, 2))]
+    refs = [wide_ref(levels, h, w, 1), ref(("tie", "diagonal16", h, w), lambda: tie_pair("diagonal16", h, w), levels),
+            ref(("rand", h, w), lambda: random_pair(h, w, 2), levels)]
     assert not np.array_equal(refs[0][2], refs[1][2]) and not np.array_equal(refs[1][2], refs[2][2])
     batch = check_field(G, refs, levels)
     for i, r in enumerate(refs):
@@ -91,28 +69,13 @@ def test_a_batch_of_three_different_pairs(levels):
         assert torch.equal(G.mci_field(ta, tb, levels), batch[i])
 
 
-def test_three_levels_through_the_new_entry_are_the_old_entry():
-    """rib_mci_field_levels(levels = 3) and Generator.mci_field(a, b, levels=3) against rib_mci_field itself, byte for byte, and
-    the two size queries."""
+def test_three_levels_and_the_clamp_border_are_the_defaults():
+    """On saturated, tied, tiny and odd inputs (mci_gpu_common.check_defaults)."""
     G = handle()
-    L = G._lib
     inputs = [wide_ref(5, *WIDE_SIZES[0], 1)[:2], wide_ref(4, *WIDE_SIZES[1], 0)[:2], tie_pair("checker8", 67, 93), random_pair(33, 15, 1),
               random_pair(1, 1, 1), random_pair(130, 250, 1)]
     for a, b in inputs:
-        h, w = a.shape[:2]
-        ta, tb = dev(G, a, b)
-        n = L.rib_mci_workspace_bytes(G._h, 1, h, w)
-        assert n == L.rib_mci_workspace_bytes_levels(G._h, 1, h, w, 3) > 0
-        assert n < L.rib_mci_workspace_bytes_levels(G._h, 1, h, w, 4) < L.rib_mci_workspace_bytes_levels(G._h, 1, h, w, 5)
-        ws = torch.empty(n, dtype=torch.uint8, device=G.device)
-        Hb, Wb = bg.field_shape(h, w)
-        old = torch.full((Hb, Wb, 2), 77, dtype=torch.int16, device=G.device)
-        assert L.rib_mci_field(G._h, 1, h, w, ta.data_ptr(), tb.data_ptr(), old.data_ptr(), ws.data_ptr(), None) == 0
-        new = torch.full((Hb, Wb, 2), 78, dtype=torch.int16, device=G.device)
-        assert L.rib_mci_field_levels(G._h, 1, h, w, ta.data_ptr(), tb.data_ptr(), new.data_ptr(), 3, ws.data_ptr(), None) == 0
-        torch.cuda.synchronize()
-        assert torch.equal(old, new) and torch.equal(G.mci_field(ta, tb), old) and torch.equal(G.mci_field(ta, tb, levels=3), old)
-        assert torch.equal(old.cpu(), torch.from_numpy(bg.mci_field_host(a, b)))
+        check_defaults(G, a, b)
 
 
 def test_frames_from_a_field_of_plus_minus_79():
@@ -176,11 +139,11 @@ def test_bad_levels_through_the_c_abi():
     a, b = random_pair(h, w, 1)
     ta, tb = dev(G, a, b)
     Hb, Wb = bg.field_shape(h, w)
-    ws = torch.empty(L.rib_mci_workspace_bytes_levels(G._h, 1, h, w, 5), dtype=torch.uint8, device=G.device)
+    ws = torch.empty(L.rib_mci_workspace_bytes(G._h, 1, h, w, 5), dtype=torch.uint8, device=G.device)
     for bad in (2, 6, 0, -1):
-        assert L.rib_mci_workspace_bytes_levels(G._h, 1, h, w, bad) == 0
+        assert L.rib_mci_workspace_bytes(G._h, 1, h, w, bad) == 0
         field = torch.full((Hb, Wb, 2), 77, dtype=torch.int16, device=G.device)
-        rc = L.rib_mci_field_levels(G._h, 1, h, w, ta.data_ptr(), tb.data_ptr(), field.data_ptr(), bad, ws.data_ptr(), None)
+        rc = L.rib_mci_field(G._h, 1, h, w, ta.data_ptr(), tb.data_ptr(), field.data_ptr(), bad, 0, ws.data_ptr(), None)
         assert rc == RIB_ERR_INVALID
         assert b"levels=%d" % bad in L.rib_last_error(G._h)
         torch.cuda.synchronize()

@@ -362,6 +362,7 @@ def test_argument_errors(tmp_path):
 def test_abi_is_declared_and_bound():
     from render_in_between_amd import _native
     hdr = open(os.path.join(ROOT, "include", "rib.h")).read()
-    for name in ("rib_mci_workspace_bytes_levels", "rib_mci_field_levels"):
+    for name in ("rib_mci_workspace_bytes", "rib_mci_field"):                  # the entries that take `levels`
         assert name + "(" in hdr and name in _native.SIGNATURES
-    assert len(_native.SIGNATURES["rib_mci_field_levels"][1]) == 10 and len(_native.SIGNATURES["rib_mci_workspace_bytes_levels"][1]) == 5
+    assert "rib_mci_workspace_bytes(rib_handle* h, int B, int H, int W, int levels);" in hdr and "int levels, int border, void* workspace" in hdr
+    assert len(_native.SIGNATURES["rib_mci_field"][1]) == 11 and len(_native.SIGNATURES["rib_mci_workspace_bytes"][1]) == 5
