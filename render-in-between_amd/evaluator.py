@@ -120,11 +120,11 @@ class _ProcessPool:
                     os.environ[k] = v
         self.n = n
 
-    def submit(self, fn, *args):
+    def submit(self, fn, *args, **kw):
         from concurrent.futures import Future
         fut = Future()
         fut.set_running_or_notify_cancel()
-        self._pool.apply_async(fn, args, callback=fut.set_result, error_callback=fut.set_exception)
+        self._pool.apply_async(fn, args, kw, callback=fut.set_result, error_callback=fut.set_exception)
         return fut
 
     def shutdown(self):
@@ -221,8 +221,8 @@ def _shm_close_all():
     _SHM_FREE.clear()
 
 
-def download_layout(sections):
-    """The layout of a unit's download buffer: sections = [(name, nbytes)] in buffer order ->
+def block_layout(sections):
+    """The layout of a unit's staging block or download buffer: sections = [(name, nbytes)] in buffer order ->
     ({name: (offset, nbytes)}, total bytes).  Every section starts on a multiple of 256 - any dtype may be viewed there, on
     the device and in a shared block - and a section of no bytes is left out."""
     table, end = {}, 0
@@ -232,6 +232,37 @@ def download_layout(sections):
             table[name] = (off, nbytes)
             end = off + nbytes
     return table, end
+
+
+def spec_bytes(spec):
+    """A block's spec [(name, dtype, shape, on)] as block_layout's sections: a section that is off takes no bytes."""
+    return [(name, math.prod(shape) * dtype.itemsize if on else 0) for name, dtype, shape, on in spec]
+
+
+def section_views(flat, spec, table):
+    """The typed views of a buffer laid out by `table`, on the device or on the host: {name: view} over every section of the
+    spec, None where the table has no such section."""
+    views = dict.fromkeys(name for name, _, _, _ in spec)
+    for name, dtype, shape, _ in spec:
+        if name in table:
+            off, nbytes = table[name]
+            views[name] = flat[off:off + nbytes].view(dtype).view(shape)
+    return views
+
+
+def staging_spec(Tc, Bc, model_hw, src_dain=None, src_gt=None, want_gt=False, masks=False, keys=False, mci=False, mci_keys=False):
+    """The spec of a unit's staging block, which the decode tasks fill and upload() sends to the GPU (DESIGN 4e has the table):
+    Tc time steps of Bc segments at the model size (H, W).  src_dain / src_gt: (w0, h0) at which that list is staged for the
+    GPU resize (resize_on="gpu"), None: the model size; want_gt, masks: ground-truth frames / masks are staged; keys: a first
+    chunk under panels, the DAIN frames of the key frames it starts from; mci: background="mci", no DAIN bytes at all;
+    mci_keys: its first chunk, the group's left and right key frames."""
+    H, W = model_hw
+    (wd, hd), (wg, hg) = src_dain or (W, H), src_gt or (W, H)
+    return (("dain", torch.uint8, (Tc, Bc, hd, wd, 3), not mci),
+            ("gt", torch.uint8, (Tc, Bc, hg, wg, 3), want_gt),
+            ("mask", torch.uint8, (Tc, Bc, H, W), masks),
+            ("key", torch.uint8, (Bc, H, W, 3), keys and not mci),
+            ("mci_keys", torch.uint8, (2, Bc, H, W, 3), mci and mci_keys))
 
 
 def _process_pool(n):
@@ -678,8 +709,6 @@ class _Clip:
         self.measure = measure              # metrics: every generated frame is measured against gtlist[i]
         self.mask_list = mask_list          # metrics: mask file of every frame index, or None
         self.records = {}                   # metrics: frame index -> {i, file, DAIN_PSNR, DAIN_SSIM, OURS_PSNR, OURS_SSIM}
-        self.stage_gt = {}                  # metrics: unit -> uint8 [Tc,B,H,W,3] staged GT frames (same block as `stage`)
-        self.stage_mask = {}                # metrics with masks: unit -> uint8 [Tc,B,H,W] staged 0/1 masks
         self.meas = {}                      # metrics: unit -> (GT frames [Tc*B,3,H,W], masks [Tc*B,H,W] or None) on the device
         self.names = names                  # output file of every frame index
         self.dain_list, self.image_list, self.pose_list, self.gtlist = dain_list, image_list, pose_list, gtlist
@@ -687,8 +716,9 @@ class _Clip:
         self.keys = keys                    # this rank's key frames (they pass through, evaluator.py:240-244)
         self.segs = segs                    # this rank's segments [(key, [frame indices])]
         self.units = units                  # native path: [(group, [segment indices], c0, c1)] - a unit is a time chunk of a group
-        self.stage = {}                     # unit -> uint8 staging tensor [Tc,B,H,W,3], page-locked; the decoders fill it in place
-        self.stage_blk = {}                 # unit -> the shared block behind it (worker processes)
+        # unit -> {"blk": the shared block (worker processes) or None, "table": its block_layout, "views": the sections of
+        # staging_spec, page-locked; the decoders fill them in place}
+        self.staged = {}
         self.slot = {}                      # frame index -> (unit, t, b): where its DAIN frame goes
         self.loads = {}                     # frame index -> future of (dain | None, key frame | None, pose or rasteriser tables)
         self.futs = {}                      # frame index -> future of its file name, or (unit future, position in the unit)
@@ -697,18 +727,17 @@ class _Clip:
         # resize_on="gpu": (w0, h0) at which the DAIN / GT frames are staged for the GPU resize; None: resized on the host
         self.src_dain = self.src_gt = None
         # panels: the sheets' folder; GT frames are staged for the Ground Truth pane whenever a gt_dir is given (want_gt: staged,
-        # measured or not); the DAIN frames of a first chunk's key frames get a section of the unit's block (key_slot: key frame
-        # index -> (unit, b)); key_of: group -> its key frames [B,3,H,W] on the device (the Ground Truth pane without a gt_dir);
-        # pan: unit -> what upload() prepared for the unit's sheets
+        # measured or not); the key frames of a first chunk belong to its unit (key_slot: key frame index -> (unit, b)), whose
+        # block has their DAIN frames in its `key` section; key_of: group -> its key frames [B,3,H,W] on the device (the Ground
+        # Truth pane without a gt_dir); pan: unit -> what upload() prepared for the unit's sheets
         self.panel_dir = None
         self.want_gt = measure
-        self.stage_key, self.key_slot, self.key_of, self.pan = {}, {}, {}, {}
+        self.key_slot, self.key_of, self.pan = {}, {}, {}
         self.sheet_futs = []                # futures of sheet files that ride in no unit's sink
         # background="mci": key frame index -> its uint8 HWC bytes as decoded and resized (filled by the decode tasks);
         # group -> (left keys, right keys uint8 [B,H,W,3], field int16 [B,Hb,Wb,2]) on the device, made in the group's first
         # chunk and kept for its later chunks beside prev_of; both are released at the end of run_native / run_reference
         self.key_u8, self.mci_of = {}, {}
-        self.stage_mk = {}                  # background="mci": first-chunk unit -> uint8 [2,B,H,W,3] section of its staging block
         # video: the folder of the frames' .jpg files; out_names: what drain() reports for every frame index - the PNG, or under
         # frames="none" the .jpg
         self.video_dir = None
@@ -943,20 +972,21 @@ class _FolderPipeline:
         dain = None if (staged_raw or self.mci) else (ev.load_image_u8 if self.native else ev.load_image)(clip.dain_list[i])[0]
         if i in clip.slot:
             ui, t, b = clip.slot[i]
+            views = clip.staged[ui]["views"]
             if staged_raw:                       # resize_on="gpu": at the file's own size, straight into the slot
-                io_worker.decode_raw_into(clip.stage[ui][t, b].numpy(), 0, clip.dain_list[i], clip.src_dain)
+                io_worker.decode_raw_into(views["dain"][t, b].numpy(), 0, clip.dain_list[i], clip.src_dain)
             elif not self.mci:                   # (background="mci": nothing to stage, the background frames are made on the GPU)
-                clip.stage[ui][t, b].copy_(dain)
+                views["dain"][t, b].copy_(dain)
             dain = None
             if clip.want_gt and clip.src_gt is not None:
-                io_worker.decode_raw_into(clip.stage_gt[ui][t, b].numpy(), 0, clip.gtlist[i], clip.src_gt)
+                io_worker.decode_raw_into(views["gt"][t, b].numpy(), 0, clip.gtlist[i], clip.src_gt)
             elif clip.want_gt:                   # the GT frame (and mask) of a measured frame, through the same resize
-                clip.stage_gt[ui][t, b].copy_(ev.load_image_u8(clip.gtlist[i])[0])
+                views["gt"][t, b].copy_(ev.load_image_u8(clip.gtlist[i])[0])
             if clip.measure and clip.mask_list is not None:
-                clip.stage_mask[ui][t, b].copy_(torch.from_numpy(io_worker.load_mask_u8(clip.mask_list[i], ev.width, ev.height)))
+                views["mask"][t, b].copy_(torch.from_numpy(io_worker.load_mask_u8(clip.mask_list[i], ev.width, ev.height)))
         elif i in clip.key_slot and not self.mci:        # panels: a key frame's DAIN frame, for its sheet
-            ui, b, _ = clip.key_slot[i]
-            clip.stage_key[ui][b].copy_(dain)
+            ui, b = clip.key_slot[i]
+            clip.staged[ui]["views"]["key"][b].copy_(dain)
             dain = None
         ref_img = clip.ref_image(i)
         if self.mci and i % clip.sample_rate == 0:       # one decode: the uint8 bytes for the interpolation, normalised for the chain
@@ -970,31 +1000,34 @@ class _FolderPipeline:
             pose = rasterise.frame_tables(pose[0], pose[1], ev.height, ev.width, ev.skeleton_thres, ev.foot_thres)
         return dain, gt, pose
 
+    @staticmethod
+    def slot_offset(clip, ui, section, b, t=0):
+        """Byte offset, in unit ui's staging block, of slot (t, b) of a section - `key` has one slot per segment, the others
+        one per time step and segment - or -1 where the block has no such section.  The one place that computes a slot's offset."""
+        table, (_, members, c0, c1) = clip.staged[ui]["table"], clip.units[ui]
+        if section not in table:
+            return -1
+        off, nbytes = table[section]
+        slots = len(members) * (1 if section == "key" else c1 - c0)
+        return off + (t * len(members) + b) * (nbytes // slots)
+
     def decode_in_worker(self, clip, i):
         """The same pre-load in a worker process; its result is unpacked (arrays wrapped as tensors) by the pool's result thread
         as soon as it arrives.  The worker decodes the DAIN frame straight into the unit's shared staging block."""
         from concurrent.futures import Future
         ev = self.ev
-        name, off = "", -1
-        extra = ()
-        if i in clip.slot:
+        name, off, gt_off, mask_off, raw = "", -1, -1, -1, (None, None)
+        if i in clip.slot:                       # a section the unit's block does not have (slot_offset: -1) is not decoded
             ui, t, b = clip.slot[i]
-            Tc, Bc = clip.stage[ui].shape[:2]
-            k = t * Bc + b
-            fsz = clip.stage[ui][0, 0].numel()   # a slot of the DAIN section: the model size, or the source size (resize_on="gpu")
-            name, off = clip.stage_blk[ui].name, (-1 if self.mci else k * fsz)
-            if clip.want_gt:                     # GT frame (and mask) of a measured frame: further sections of the same block
-                gsz = clip.stage_gt[ui][0, 0].numel()
-                mask_off = Tc * Bc * (fsz + gsz) + k * ev.height * ev.width if clip.mask_list is not None else -1
-                extra = (Tc * Bc * fsz + k * gsz, clip.mask_list[i] if clip.mask_list is not None else None, mask_off)
-            if clip.src_dain is not None or clip.src_gt is not None:
-                extra = (extra or (-1, None, -1)) + (clip.src_dain, clip.src_gt if clip.measure else None)
+            name, raw = clip.staged[ui]["blk"].name, (clip.src_dain, clip.src_gt)
+            off, gt_off, mask_off = (self.slot_offset(clip, ui, section, b, t) for section in ("dain", "gt", "mask"))
         elif i in clip.key_slot:                 # panels: a key frame's DAIN frame goes to the key section, at the model size
-            ui, _, off = clip.key_slot[i]
-            name = clip.stage_blk[ui].name
+            ui, b = clip.key_slot[i]
+            name, off = clip.staged[ui]["blk"].name, self.slot_offset(clip, ui, "key", b)
         src = self.procs.submit(io_worker.load_frame_shm, name, off, None if self.mci else clip.dain_list[i], clip.ref_image(i), clip.pose_list[i],
                                 i % clip.sample_rate == 0, self.gpu_labels, ev.width, ev.height, ev.resize, ev.skeleton_thres, ev.foot_thres,
-                                *extra)
+                                gt_offset=gt_off, mask_path=clip.mask_list[i] if mask_off >= 0 else None, mask_offset=mask_off,
+                                dain_raw=raw[0], gt_raw=raw[1])
         out = Future()
 
         def unpack(f):
@@ -1024,44 +1057,17 @@ class _FolderPipeline:
         while clip.opened <= min(upto, len(clip.units) - 1):
             ui = clip.opened
             _, members, c0, c1 = clip.units[ui]
-            # a section is staged at the model size, or (resize_on="gpu") at the list's source size for the GPU resize
-            (wd, hd), (wg, hg) = clip.src_dain or (ev.width, ev.height), clip.src_gt or (ev.width, ev.height)
-            shape, shape_gt = (c1 - c0, len(members), hd, wd, 3), (c1 - c0, len(members), hg, wg, 3)
-            shape_mask = (c1 - c0, len(members), ev.height, ev.width)
-            if self.mci:                        # no DAIN section: the unit stages no DAIN bytes
-                shape = (c1 - c0, len(members), 0, 0, 3)
-            nb, nb_gt, nb_mask = (int(np.prod(s_)) for s_ in (shape, shape_gt, shape_mask))
-            # metrics / panels: [DAIN frames | GT frames | masks | DAIN frames of the key frames] side by side in the unit's one
-            # staging block; the last section only for a first chunk under panels (key-frame sheets)
-            if not clip.want_gt:
-                nb_gt = 0
-            if clip.mask_list is None:
-                nb_mask = 0
-            fkey = ev.height * ev.width * 3
-            nb_key = len(members) * fkey if (self.panels and c0 == 0 and not self.mci) else 0
-            # background="mci", first chunk: the group's left and right key frames' bytes go up from the unit's own block too
-            nb_mk = 2 * len(members) * fkey if (self.mci and c0 == 0) else 0
-            total = max(1, nb + nb_gt + nb_mask + nb_mk) if self.mci else nb + nb_gt + nb_mask + nb_key
-            if self.procs is not None:      # shared with the decode workers and page-locked (back on the free list once uploaded)
-                clip.stage_blk[ui] = _shm_get(total)            # (size classes of 1 MB: the block may be larger than the unit)
-                flat = clip.stage_blk[ui].t[:total]
-            else:
-                flat = torch.empty(total, dtype=torch.uint8, pin_memory=True)
-            clip.stage[ui] = flat[:nb].view(*shape)
-            if clip.want_gt:
-                clip.stage_gt[ui] = flat[nb:nb + nb_gt].view(*shape_gt)
-            if clip.mask_list is not None:
-                clip.stage_mask[ui] = flat[nb + nb_gt:nb + nb_gt + nb_mask].view(*shape_mask)
-            if nb_mk:
-                clip.stage_mk[ui] = flat[total - nb_mk:total].view(2, len(members), ev.height, ev.width, 3)
-            if nb_key:
-                clip.stage_key[ui] = flat[total - nb_key:].view(len(members), ev.height, ev.width, 3)
-                for b, si in enumerate(members):
-                    clip.key_slot[clip.segs[si][0]] = (ui, b, total - nb_key + b * fkey)
-            elif self.panels and c0 == 0:       # background="mci": a key frame's own bytes are its background pane, nothing is staged
-                for b, si in enumerate(members):
-                    clip.key_slot[clip.segs[si][0]] = (ui, b, -1)
+            # one block per unit; a later chunk under background="mci" may stage nothing at all and still gets its byte
+            spec = staging_spec(c1 - c0, len(members), (ev.height, ev.width), clip.src_dain, clip.src_gt, want_gt=clip.want_gt,
+                                masks=clip.mask_list is not None, keys=self.panels and c0 == 0, mci=self.mci, mci_keys=c0 == 0)
+            table, total = block_layout(spec_bytes(spec))
+            # worker processes: shared with them and page-locked (size classes of 1 MB: the block may be larger than the unit)
+            blk = _shm_get(max(1, total)) if self.procs is not None else None
+            flat = blk.t if blk is not None else torch.empty(max(1, total), dtype=torch.uint8, pin_memory=True)
+            clip.staged[ui] = {"blk": blk, "table": table, "views": section_views(flat, spec, table)}
             for b, si in enumerate(members):
+                if self.panels and c0 == 0:     # (background="mci": the block has no `key` section, a key frame is its own background)
+                    clip.key_slot[clip.segs[si][0]] = (ui, b)
                 for t in range(c0, c1):
                     clip.slot[clip.segs[si][1][t]] = (ui, t - c0, b)
             # decode in the order the launch thread will ask for the frames: the unit's key frames first
@@ -1087,6 +1093,7 @@ class _FolderPipeline:
         ev = self.ev
         gi, members, c0, c1 = clip.units[ui]
         Tc, Bc = c1 - c0, len(members)
+        views = clip.staged[ui]["views"]        # page-locked, of the unit's block: they go back to the pool with it (sink)
         if self.up is None:
             self.up = torch.cuda.Stream(device=self.model.device)
         # panels: the label maps of a first chunk's key frames (their sheets' Skeleton pane) are drawn in the unit's own call
@@ -1105,11 +1112,10 @@ class _FolderPipeline:
                     ks = [clip.segs[si][0] for si in members]
                     for k in ks:
                         clip.loads[k + clip.sample_rate].result(timeout=IO_TIMEOUT_S)
-                    mk = clip.stage_mk[ui]    # page-locked, part of the unit's block: it goes back to the pool with it (sink)
                     for b, k in enumerate(ks):
-                        mk[0, b].copy_(clip.key_u8[k])
-                        mk[1, b].copy_(clip.key_u8[k + clip.sample_rate])
-                    kab = mk.to(g.device, non_blocking=True)
+                        views["mci_keys"][0, b].copy_(clip.key_u8[k])
+                        views["mci_keys"][1, b].copy_(clip.key_u8[k + clip.sample_rate])
+                    kab = views["mci_keys"].to(g.device, non_blocking=True)
                     clip.mci_of[gi] = (kab[0], kab[1], g.mci_field(kab[0], kab[1], self.mci_levels, border=self.mci_border))
                 ka, kb, field = clip.mci_of[gi]
                 dn = g.mci_frames(ka, kb, field, clip.sample_rate, k_first=c0 + 1, count=Tc, normalised="both" if self.panels else True,
@@ -1117,7 +1123,7 @@ class _FolderPipeline:
                 if self.panels:
                     dn, dnu8 = dn
             else:
-                staged = clip.stage[ui].to(g.device, non_blocking=True)
+                staged = views["dain"].to(g.device, non_blocking=True)
                 if clip.src_dain is not None:      # resize_on="gpu": resize + ToTensor + Normalize in one kernel (rib_resize_cubic)
                     dn = g.resize_u8(staged.flatten(0, 1), ev.width, ev.height, normalised=True).view(Tc, Bc, 3, ev.height, ev.width)
                 else:
@@ -1126,7 +1132,7 @@ class _FolderPipeline:
             gtd = gt.to(g.device) if gt is not None else None
             gtf = staged_gt = None
             if clip.want_gt:
-                staged_gt = clip.stage_gt[ui].to(g.device, non_blocking=True)
+                staged_gt = views["gt"].to(g.device, non_blocking=True)
             if clip.measure:                   # the GT frames normalised as the DAIN frames are
                 if clip.src_gt is not None:
                     gtf = g.resize_u8(staged_gt.flatten(0, 1), ev.width, ev.height, normalised=True)
@@ -1134,8 +1140,8 @@ class _FolderPipeline:
                     gtf = staged_gt.permute(0, 1, 4, 2, 3).to(torch.float32)
                     gtf = ((gtf / 255.0 - 0.5) / 0.5).reshape(Tc * Bc, 3, ev.height, ev.width).contiguous()
             if clip.measure:                   # masks 0/1 -> float
-                mk = (clip.stage_mask[ui].to(g.device, non_blocking=True).to(torch.float32).reshape(Tc * Bc, ev.height, ev.width)
-                      if ui in clip.stage_mask else None)
+                mk = (views["mask"].to(g.device, non_blocking=True).to(torch.float32).reshape(Tc * Bc, ev.height, ev.width)
+                      if views["mask"] is not None else None)
                 if self.pose_mask:             # drawn here from the unit's own peaks (rib_human_mask): no file, no staging
                     mk = g.human_mask(np.stack([self.peaks_of(p_) for p_ in poses]), ev.height, ev.width)
                 clip.meas[ui] = (gtf, mk)
@@ -1155,7 +1161,7 @@ class _FolderPipeline:
                 if self.mci:                   # a key frame's background is frame k = 0 of its segment: the key frame itself
                     kdn = normalise_exact(clip.mci_of[gi][0]) if key_poses else None
                 else:
-                    kdn = normalise_exact(clip.stage_key[ui].to(g.device, non_blocking=True)) if key_poses else None
+                    kdn = normalise_exact(views["key"].to(g.device, non_blocking=True)) if key_poses else None
                 if staged_gt is not None:
                     gtp = shown(staged_gt, clip.src_gt)
                 else:                          # no gt_dir: the Ground Truth pane is the segment's left key frame (evaluator.py:209-212)
@@ -1172,7 +1178,7 @@ class _FolderPipeline:
     # ---- stage 3: render -------------------------------------------------------------------------------------------------
     def render(self, clip, ui, g, st, lab, dn, gtd, ready):
         """The unit's chain (evaluator.py:240-244,252: a segment starts from its key frame; inside it prev <- fused frame), then
-        everything the unit sends home - in ONE device buffer of named sections (download_layout; DESIGN 4e has the table),
+        everything the unit sends home - in ONE device buffer of named sections (block_layout; DESIGN 4e has the table),
         filled by the quantiser, rib_quality, rib_panel and the two JPEG encoders, each under its option - and ONE asynchronous
         copy into page-locked host memory, all on the lane's stream.  Returns the record the sink reads: the same keys for
         every unit, None where the unit has no such section."""
@@ -1193,18 +1199,10 @@ class _FolderPipeline:
                     ("sheet_len", torch.int32, (n + nk,), self.jpeg_gpu),        # (jpeg_gpu implies panels)
                     ("video_len", torch.int32, (self.video_count(clip, ui),), self.video),
                     ("sheets", torch.uint8, (n + nk, SH, SW, 3), home))
-            table, total = download_layout([(name, math.prod(shape) * dtype.itemsize if on else 0) for name, dtype, shape, on in spec])
+            table, total = block_layout(spec_bytes(spec))
             assert total, "a unit sends something home: frames, metrics, sheets or a video"
-
-            def sections(flat):                  # the typed views of a buffer laid out by `table`, on the device or on the host
-                views = dict.fromkeys(name for name, _, _, _ in spec)
-                for name, dtype, shape, _ in spec:
-                    if name in table:
-                        off, nbytes = table[name]
-                        views[name] = flat[off:off + nbytes].view(dtype).view(shape)
-                return views
             buf = torch.empty(total, dtype=torch.uint8, device=g.device)
-            dev = sections(buf)
+            dev = section_views(buf, spec, table)
             keep = [fz, lab, dn, gtd, buf]
             if self.write_png:
                 g.quantise(frames, out=dev["frames"])
@@ -1236,7 +1234,7 @@ class _FolderPipeline:
                 self.tm["panels"] = self.tm.get("panels", 0.0) + time.perf_counter() - t0
             elif clip.measure:
                 self.tm["metrics"] += time.perf_counter() - t0
-        host = sections(flat)
+        host = section_views(flat, spec, table)
         # the files of the two encoders stay on the device until the sink knows their lengths: (files, cap, lengths on the host)
         # frames_off / sheets_off: where the file workers find those two sections in the shared block
         return {"done": done, "out_blk": out_blk, "keep": tuple(keep),
@@ -1315,79 +1313,69 @@ class _FolderPipeline:
             streams[device] = torch.cuda.Stream(device)
         return streams[device]
 
-    def loose_key_sheets(self, clip, g, st):
-        """panels: the sheets of this rank's key frames that start no unit of its own (a clip's last key frame; every key frame of
-        a model that renders nothing): a small unit of their own - labels, one rib_panel launch in key-frame mode, one copy."""
+    def loose_keys(self, clip, g, st):
+        """panels / video: the sheets and the video files of this rank's key frames that start no segment of its own (a clip's
+        last key frame; every key frame of a rank that renders nothing): a small unit of their own - labels, one rib_panel
+        launch in key-frame mode, the two encoders - whose download is laid out and copied as a unit's is (render)."""
         ev = self.ev
-        loose = [k for k in clip.keys if k not in clip.key_slot]
-        if not loose:
-            return
-        got = [clip.loads[k].result(timeout=IO_TIMEOUT_S) for k in loose]
-        if self.mci:                             # a key frame's background is the key frame itself (frame k = 0 of the interpolation)
-            dains = [clip.key_u8[k] for k in loose]
-        else:
-            dains = list(self.pool.map(lambda k: ev.load_image_u8(clip.dain_list[k])[0], loose))
-        poses = [g_[2] for g_ in got]
-        with torch.cuda.stream(st):
-            if self.gpu_labels:
-                klab = rasterise.rasterise_tables(g, poses, ev.height, ev.width, ev.gauss_sigma)
-            else:
-                klab = ev.make_labels(g if hasattr(g, "rasterise") else self.model, poses).to(g.device)
-            if self.titles_dev is None:
-                self.titles_dev = torch.from_numpy(self.titles).to(g.device)
-            kdn = normalise_exact(torch.stack(dains).to(g.device))
-            keys = torch.stack([g_[1] for g_ in got]).to(g.device)
-            sheets = g.panel(None, None, None, kdn, keys, klab, titles=self.titles_dev)
-            jpeg = out_blk = pinned = None
-            if self.jpeg_gpu:                    # the files stay on the device until their lengths are home
-                lengths = torch.empty(len(loose), dtype=torch.int32, device=g.device)
-                home = torch.empty(len(loose), dtype=torch.int32, pin_memory=True)
-                jpeg = self.encode_jpeg(g, sheets, lengths)
-                home.copy_(lengths, non_blocking=True)
-                jpeg = jpeg + (home,)
-            if not self.jpeg_gpu or self.panel_frames:
-                out_blk = _shm_get(sheets.numel()) if self.procs is not None else None
-                pinned = (out_blk.t[:sheets.numel()] if out_blk is not None else torch.empty(sheets.numel(), dtype=torch.uint8, pin_memory=True)).view(sheets.shape)
-                pinned.copy_(sheets, non_blocking=True)
-            done = torch.cuda.Event()
-            done.record(st)
-
-        def finish(keep=(sheets, kdn, keys, klab)):
-            done.synchronize()
-            res = self.fetch_jpeg(clip, loose, jpeg) if jpeg is not None else []
-            if pinned is not None:
-                res += [f.result(timeout=IO_TIMEOUT_S) for f in self.save_sheets(clip, loose, pinned, out_blk)]
-            if out_blk is not None:
-                _shm_put(out_blk)
-            return res
-        clip.sheet_futs.append(self.finishers.submit(finish))
-
-    def loose_key_video(self, clip, g, st):
-        """video: the files of this rank's key frames that start no unit of its own (a clip's last key frame; every key frame of
-        a rank that renders nothing) - the rule of loose_key_sheets: a small unit of their own, one rib_jpeg_float, the lengths
-        home first, then exactly the files' bytes."""
         started = {k for k, _ in clip.segs}
         loose = [k for k in clip.keys if k not in started]
         if not loose:
             return
-        keys = torch.stack([clip.loads[k].result(timeout=IO_TIMEOUT_S)[1] for k in loose])
+        got = [clip.loads[k].result(timeout=IO_TIMEOUT_S) for k in loose]
+        n, (SH, SW) = len(loose), self.sheet_hw if self.panels else (0, 0)
+        home = self.panels and (not self.jpeg_gpu or self.panel_frames)     # the raw sheets travel home
+        spec = (("sheet_len", torch.int32, (n,), self.jpeg_gpu), ("video_len", torch.int32, (n,), self.video),
+                ("sheets", torch.uint8, (n, SH, SW, 3), home))
+        table, total = block_layout(spec_bytes(spec))
+        if self.panels and self.mci:             # a key frame's background is the key frame itself (frame k = 0 of the interpolation)
+            dains = [clip.key_u8[k] for k in loose]
+        elif self.panels:
+            dains = list(self.pool.map(lambda k: ev.load_image_u8(clip.dain_list[k])[0], loose))
         with torch.cuda.stream(st):
-            keys = keys.to(g.device, torch.float32).contiguous()
-            cap = g.jpeg_max_bytes(*keys.shape[2:])
-            files = torch.empty(len(loose) * cap, dtype=torch.uint8, device=g.device)
-            lengths = torch.empty(len(loose), dtype=torch.int32, device=g.device)
-            home = torch.empty(len(loose), dtype=torch.int32, pin_memory=True)
-            g.jpeg_f32_into(keys, files, lengths, self.video_quality, cap)
-            home.copy_(lengths, non_blocking=True)
+            buf = torch.empty(total, dtype=torch.uint8, device=g.device)
+            dev = section_views(buf, spec, table)
+            keys = torch.stack([g_[1] for g_ in got]).to(g.device, torch.float32).contiguous()
+            keep, jpeg, vid = [buf, keys], None, None
+            if self.panels:
+                poses = [g_[2] for g_ in got]
+                if self.gpu_labels:
+                    klab = rasterise.rasterise_tables(g, poses, ev.height, ev.width, ev.gauss_sigma)
+                else:
+                    klab = ev.make_labels(g if hasattr(g, "rasterise") else self.model, poses).to(g.device)
+                if self.titles_dev is None:
+                    self.titles_dev = torch.from_numpy(self.titles).to(g.device)
+                kdn = normalise_exact(torch.stack(dains).to(g.device))
+                sheets = dev["sheets"] if home else torch.empty((n, SH, SW, 3), dtype=torch.uint8, device=g.device)
+                g.panel(None, None, None, kdn, keys, klab, titles=self.titles_dev, out=sheets)
+                keep += [sheets, kdn, klab]
+                if self.jpeg_gpu:                # the files of both encoders stay on the device until their lengths are home
+                    jpeg = self.encode_jpeg(g, sheets, dev["sheet_len"])
+            if self.video:
+                cap = g.jpeg_max_bytes(*keys.shape[2:])
+                vid = (torch.empty(n * cap, dtype=torch.uint8, device=g.device), cap)
+                g.jpeg_f32_into(keys, vid[0], dev["video_len"], self.video_quality, cap)
+            out_blk = _shm_get(total) if self.procs is not None else None
+            flat = out_blk.t[:total] if out_blk is not None else torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            flat.copy_(buf, non_blocking=True)
             done = torch.cuda.Event()
             done.record(st)
+        host = section_views(flat, spec, table)
 
-        def finish(keep=(keys, lengths)):
+        def finish(keep=keep):
             done.synchronize()
-            return self.fetch_jpeg(clip, loose, (files, cap, home), video=True)
+            if jpeg is not None:
+                self.fetch_jpeg(clip, loose, jpeg + (host["sheet_len"],))
+            names = self.fetch_jpeg(clip, loose, vid + (host["video_len"],), video=True) if vid is not None else None
+            if home:
+                for f in self.save_sheets(clip, loose, host["sheets"], out_blk, table["sheets"][0]):
+                    f.result(timeout=IO_TIMEOUT_S)
+            if out_blk is not None:
+                _shm_put(out_blk)
+            return names                         # frames="none": the .jpg names of the loose key frames, in order
         fut = self.finishers.submit(finish)
         clip.sheet_futs.append(fut)
-        if not self.write_png:
+        if self.video and not self.write_png:
             for j, k in enumerate(loose):
                 clip.futs[k] = (fut, j)
 
@@ -1403,12 +1391,7 @@ class _FolderPipeline:
         self.tm.setdefault("timeline", []).append(mark)
         if r["qual"] is not None:               # the unit's per-frame metrics rode in the same copy
             self.record(clip, out_frames, r["qual"].numpy().astype(np.float64))
-        in_blk = clip.stage_blk.pop(ui, None)
-        clip.stage.pop(ui, None)                # (the views of the block go before the block does)
-        clip.stage_gt.pop(ui, None)
-        clip.stage_mask.pop(ui, None)
-        clip.stage_key.pop(ui, None)
-        clip.stage_mk.pop(ui, None)
+        in_blk = clip.staged.pop(ui)["blk"]     # the record holds every view of the block: they go before the block does
         if in_blk is not None:
             _shm_put(in_blk)
         out_blk = r["out_blk"]
@@ -1463,10 +1446,8 @@ class _FolderPipeline:
                 clip.futs[i] = (seg_fut, j)
         for k in clip.keys:
             self.submit_load(clip, k)
-        if self.panels:
-            self.loose_key_sheets(clip, *(lanes[0] if lanes else (self.model, torch.cuda.current_stream(self.model.device))))
-        if self.video:
-            self.loose_key_video(clip, *(lanes[0] if lanes else (self.model, torch.cuda.current_stream(self.model.device))))
+        if self.panels or self.video:
+            self.loose_keys(clip, *(lanes[0] if lanes else (self.model, torch.cuda.current_stream(self.model.device))))
         tm["units"] = tm.get("units", 0) + len(clip.units)
         tm["frames"] += len(clip.futs)
         # background="mci": the groups' key frames and fields are only read by launches already enqueued on the upload stream,

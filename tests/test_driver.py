@@ -365,8 +365,8 @@ def test_cpu_budget_is_positive_and_bounded_by_the_affinity_mask():
     assert 1 <= E.io_threads <= max(1, n - 1) or n == 1
 
 
-def test_download_layout_over_every_combination_of_sections():
-    """evaluator.download_layout, the one place where the offsets of a unit's download buffer are made: all 32
+def test_block_layout_over_every_combination_of_sections():
+    """evaluator.block_layout, the one place where the offsets of a unit's download buffer are made: all 32
     on/off combinations of the five sections at n = 3 frames + nk = 2 key frames of 32x48 and an odd sheet size.  Sections
     start on multiples of 256, in table order, without overlap; `frames` is at 0; a section of no bytes is absent; the total
     is the end of the last one; torch accepts the float32 / int32 views at those offsets."""
@@ -377,7 +377,7 @@ def test_download_layout_over_every_combination_of_sections():
     assert all(nbytes % 256 for _, nbytes in sizes[1:])         # every section behind `frames` needs its padding
     for on in itertools.product((False, True), repeat=5):
         sections = [(name, nbytes if o else 0) for (name, nbytes), o in zip(sizes, on)]
-        table, total = ev.download_layout(sections)
+        table, total = ev.block_layout(sections)
         assert list(table) == [name for (name, _), o in zip(sizes, on) if o], on
         end = 0
         for name, (off, nbytes) in table.items():
@@ -396,4 +396,4 @@ def test_download_layout_over_every_combination_of_sections():
                 v.fill_(1)                                      # ... and a write through it stays inside the section
                 assert not flat[:off].any() and not flat[off + nbytes:].any() and bool((flat[off:off + nbytes].view(dtype) == 1).all())
                 flat.zero_()
-    assert ev.download_layout([]) == ({}, 0) and ev.download_layout([("qual", 0)]) == ({}, 0)
+    assert ev.block_layout([]) == ({}, 0) and ev.block_layout([("qual", 0)]) == ({}, 0)

@@ -1,4 +1,4 @@
-"""The folder driver's download buffer on the MI355X with several output options at once (evaluator.download_layout):
+"""The folder driver's download buffer on the MI355X with several output options at once (evaluator.block_layout):
 every option alone is pinned by its own test (test_gpu_quality / _panel / _jpeg / _video); here they share one unit's buffer -
 metrics with video, and all five sections together - and every output must be the bytes the option writes alone."""
 import os

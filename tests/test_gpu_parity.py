@@ -428,7 +428,7 @@ def test_driver_pipeline_stages_can_be_driven_one_at_a_time(tmp_path):
             st = torch.cuda.current_stream(G.device)
             for ui in range(len(clip.units)):
                 pipe.open_units(clip, ui)                          # no decode-ahead: exactly this unit
-                assert clip.opened == ui + 1 and ui in clip.stage and (ui in clip.stage_blk) == (mode == "process")
+                assert clip.opened == ui + 1 and ui in clip.staged and (clip.staged[ui]["blk"] is not None) == (mode == "process")
                 poses, gt = pipe.wait_decoded(clip, ui)
                 assert len(poses) == len(clip.unit_frames(ui)) and (gt is not None) == (clip.units[ui][2] == 0)
                 lab, dn, gtd, ready = pipe.upload(clip, ui, G, st, poses, gt)
@@ -436,7 +436,7 @@ def test_driver_pipeline_stages_can_be_driven_one_at_a_time(tmp_path):
                 r = pipe.render(clip, ui, G, st, lab, dn, gtd, ready)
                 names = pipe.sink(clip, ui, r, 0.0, 0.0)           # on this thread: returns when the unit's files exist
                 assert names == [clip.names[i] for i in clip.unit_frames(ui)] and all(os.path.exists(f) for f in names)
-                assert ui not in clip.stage and ui not in clip.stage_blk and r["keep"] is None
+                assert ui not in clip.staged and r["keep"] is None
                 for j, i in enumerate(clip.unit_frames(ui)):
                     f = Future()
                     f.set_result(names)
