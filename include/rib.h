@@ -283,7 +283,7 @@ int rib_jpeg_float(rib_handle* h, int T, int H, int W, const float* src_f32_nchw
  * L levels, bilateral 8x8 block matching (full search over [-4,4]^2 on the top level - with L = 3 at quarter size, i.e. +-32 px
  * of motion between the key frames; +-1 refinements on every level below; the minimum of (cost, dx^2+dy^2, dy, dx)), a 3x3 median,
  * a bilinear per-pixel field in 1/256 px, two fixed-point bilinear samples and a blend - and the kernels are bit-equal to it.
- * No occlusion reasoning, no sub-pel search.
+ * No occlusion reasoning inside the frame.  The search itself is in whole pixels; rib_halfpel_refine (below) adds one half-pel step.
  * rib_mci_field: a_u8, b_u8 uint8 NHWC [B,H,W,3] on the device (left and right key frame of B segments at the model size) ->
  * field_i16 int16 [B,Hb,Wb,2] on the device, (dx, dy) per 8x8 block of the intermediate frame (rib_mci_field_shape:
  * Hb = ceil(H/8), Wb = ceil(W/8)); once per segment.  levels: L = 3, 4 or 5 pyramid levels (the driver's --mci-range 32, 64, 128:
@@ -306,13 +306,36 @@ int rib_jpeg_float(rib_handle* h, int T, int H, int W, const float* src_f32_nchw
  * covering background - is NOT handled.  Every element written; a frame's bytes do not depend on T or B.
  * levels outside 3..5, border outside {0, 1}, B outside 1..32767, B * Hb * Wb >= 2^30, T < 1, T * B > 65535, H or W outside
  * 1..16384, a bad sample_rate or frame range, NULL or misaligned pointers: RIB_ERR_INVALID with a rib_last_error text, nothing
- * launched (the size query returns 0). */
+ * launched (the size query returns 0).
+ * rib_halfpel_refine (the driver's --mci-precision half; background.mci_refine_host, bit-equal): the integer field writes the motion
+ * between the key frames as 2 d, an even number of pixels; this turns field_i16 (rib_mci_field's, any L) into field_half_i16,
+ * int16 [B,Hb,Wb,2] in HALF pixels: per block the minimum of (cost, hx^2+hy^2, hy, hx) over h in 2 d + [-1,1]^2, cost = the SAD of
+ * the half-pel planes (a half position is the rounded mean of its two or four pixels) at clamp(2p - h) in A and clamp(2p + h) in
+ * B + 2 (|hx| + |hy|); border = 1: rib_mci_field's one-sided rule in half-pel coordinates (a block whose start 2 d is not valid
+ * keeps 2 d).  ONE launch on `stream`, luma computed from the RGB bytes: no workspace, nothing of rib_mci_field's workspace is
+ * read; no atomics, a segment's result does not depend on B.  field_half_i16 == field_i16 (in place) is allowed; both 4-byte
+ * aligned.  Components beyond +-79 (no rib_mci_field result has them) cannot be refused without reading the device: such input
+ * is undefined - the kernel clamps it to +-79, so nothing is read out of bounds.  Half-pel samples are bilinear and therefore
+ * soft; a block whose integer vector is more than one half-pel step from the truth stays wrong; no quarter-pel, no sub-pel search
+ * on the coarse levels.
+ * rib_halfpel_frames: rib_mci_frames for a field in half pixels (offsets k D / s and (s-k) D / s): the same host body, the same
+ * kernel template, the same contract and refusals; the field 2 f gives the bytes rib_mci_frames gives for f.  It is an entry of
+ * its own only because rib_mci_frames' 14 arguments are pinned by existing callers and tests; folding it into rib_mci_frames as
+ * a `precision` argument is the follow-up (one entry per operation).  The two entries are named rib_halfpel_*, not rib_mci_*: the
+ * rib_mci_* family is held at four entries (one per operation and the shape query) by the suite, and the fold brings it back to that.
+ * Both: border outside {0, 1}, bad B, H, W, T, sample rate or frame range, NULL or misaligned pointers: RIB_ERR_INVALID with a
+ * rib_last_error text, nothing launched. */
 void rib_mci_field_shape(int H, int W, int* Hb, int* Wb);
 size_t rib_mci_workspace_bytes(rib_handle* h, int B, int H, int W, int levels);
 int rib_mci_field(rib_handle* h, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
                   int levels, int border, void* workspace, void* hip_stream);
 int rib_mci_frames(rib_handle* h, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const int16_t* field_i16,
                    int sample_rate, int k_first, int border, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream);
+int rib_halfpel_refine(rib_handle* h, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8,
+                   const int16_t* field_i16, int16_t* field_half_i16, int border, void* hip_stream);
+int rib_halfpel_frames(rib_handle* h, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8,
+                        const int16_t* field_half_i16, int sample_rate, int k_first, int border,
+                        float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream);
 
 /* Extension op named by the north star but absent from the reference: bilinear
  * flow-grid warp, semantics of torch.nn.functional.grid_sample(img, base+flow*2/(size-1),

@@ -4,8 +4,8 @@ frame per output frame from <input>/DAIN/ (an external network with its own CUDA
 needs "a plausible frame at time t made from the two key frames", which the mask network keeps where the person is not.
 The generator was trained on DAIN backgrounds; the quality of this substitute on real footage has not been measured.
 
-The two functions below ARE the definition; the HIP kernels (csrc/mci.hip.h: rib_mci_field / rib_mci_frames) are held
-bit-equal to them (tests/test_gpu_mci.py).  Every step is integer or fixed point with a stated order and stated tie-breaks:
+The functions below ARE the definition; the HIP kernels (csrc/mci.hip.h: rib_mci_field / rib_halfpel_refine / rib_mci_frames /
+rib_halfpel_frames) are held bit-equal to them (tests/test_gpu_mci.py, tests/test_gpu_mci_halfpel.py).  Every step is integer or fixed point with a stated order and stated tie-breaks:
 
   luma       Y = (77 R + 150 G + 29 B + 128) >> 8.
   pyramid    levels 0 (full) .. L-1, L = 3 unless asked otherwise (`levels`, below); level l+1 is ceil(h/2) x ceil(w/2), a pixel
@@ -44,8 +44,25 @@ bit-equal to them (tests/test_gpu_mci.py).  Every step is integer or fixed point
              output is that sample alone - a hard switch, with a seam where it flips; otherwise the blend above.  k = 0 and
              k = s stay A and B.  Median and per-pixel field are unchanged.
 
-No sub-pel search, and no occlusion reasoning beyond the frame border under border="valid" - a foreground object that covers
-background is not handled: see DESIGN ("Motion-compensated backgrounds") for what that costs."""
+  half-pel   (mci_refine_host, the driver's mci_precision="half"; off by default).  The integer field writes the motion between the
+             key frames as 2 d: even.  One more step after the median, no second median: the half-pel plane U(Y) of a luma plane
+             is [2h-1, 2w-1], U[Q, P] = (Y[y0,x0] + Y[y0,x1] + Y[y1,x0] + Y[y1,x1] + 2) >> 2 with y0 = Q >> 1,
+             y1 = min(y0 + (Q & 1), h-1) and the same for the column (even coordinates are Y; a half position is (a + b + 1) >> 1
+             or the four-tap mean).  Every block tries h in 2 d + [-1, 1]^2, cost(h) = sum over the block's pixels p inside the
+             image of |U_A(clamp(2p - h)) - U_B(clamp(2p + h))| + LAMBDA_HALF * (|hx| + |hy|), clamped to the half-pel plane
+             (LAMBDA_HALF = 2: h = 2 d costs what d costs on level 0); the winner is the minimum of (cost, hx*hx + hy*hy, hy, hx)
+             (pack_key_half: |h| <= 159).  border="valid": block_cost_valid's rule in half-pel coordinates - a pixel counts when
+             2p - h and 2p + h both lie in [0, 2(w-1)] x [0, 2(h-1)] (ceil(|hx|/2) <= X <= w-1-ceil(|hx|/2), the same in Y: n of
+             N), a candidate is valid when 4 n >= N, costs (64 * SAD over those n) // n + LAMBDA_HALF * (|hx| + |hy|), and a block
+             whose start 2 d is not valid keeps 2 d.  The result is a field in HALF pixels; mci_frames_host(precision="half")
+             reads it: the offsets are (k Dh + s/2) >> log2 s and ((s-k) Dh + s/2) >> log2 s, Dh the same bilinear per-pixel
+             field, now in 1/256 of a half pixel - so the field 2 f gives the bytes precision="full" gives for f.  Half-pel
+             samples are bilinear and therefore soft; a block whose integer vector is more than one half-pel step from the
+             truth stays wrong.
+
+No quarter-pel search, no sub-pel search on the coarse levels, and no occlusion reasoning beyond the frame border under
+border="valid" - a foreground object that covers background is not handled: see DESIGN ("Motion-compensated backgrounds") for
+what that costs."""
 from __future__ import annotations
 
 import numpy as np
@@ -65,6 +82,9 @@ MAX_SAMPLE_RATE = 1024
 BORDERS = ("clamp", "valid")              # `border` of the functions below; 0 and 1 of rib_mci_field / rib_mci_frames
 RANGES = {32: 3, 64: 4, 128: 5}           # the driver's mci_range (px of motion between the key frames) -> levels
 VALID_SHARE = 4           # border="valid": a candidate counts when VALID_SHARE * n >= N
+LAMBDA_HALF = 2           # mci_refine_host: cost of one HALF pixel of |hx| + |hy| (h = 2 d costs what d costs on level 0)
+HALF_KEY_BIAS = 256       # pack_key_half: hy + 256, hx + 256 in 9 bits each (|h| <= 2 * max_disp(5) + 1 = 159)
+PRECISIONS = ("full", "half")             # `precision` of mci_frames_host; the driver's mci_precision
 
 
 def field_shape(height, width):
@@ -99,8 +119,16 @@ def check_border(border, who):
     return border
 
 
-def check_settings(background, mci_range, mci_border, resize_on, who="evaluate_from_folder"):
-    """The folder driver's background settings -> (levels, border) for the functions below."""
+def check_precision(precision, who):
+    if not isinstance(precision, str) or precision not in PRECISIONS:
+        raise ValueError("%s: precision must be 'full' or 'half', got %r" % (who, precision))
+    return precision
+
+
+def check_settings(background, mci_range, mci_border, resize_on, who="evaluate_from_folder", mci_precision="full"):
+    """The folder driver's background settings -> (levels, border) for the functions below.
+    mci_precision: "full" (the default) or "half" (mci_refine_host after the field, mci_frames_host(precision="half")); checked
+    here, and the caller's to pass on."""
     if background not in ("dain", "mci"):
         raise ValueError("%s: background must be 'dain' or 'mci', got %r" % (who, background))
     if background == "mci" and resize_on == "gpu":
@@ -114,6 +142,10 @@ def check_settings(background, mci_range, mci_border, resize_on, who="evaluate_f
         raise ValueError("%s: mci_border must be 'clamp' or 'valid', got %r" % (who, mci_border))
     if background != "mci" and mci_border != "clamp":
         raise ValueError("%s: mci_border is a setting of background='mci'" % who)
+    if not isinstance(mci_precision, str) or mci_precision not in PRECISIONS:
+        raise ValueError("%s: mci_precision must be 'full' or 'half', got %r" % (who, mci_precision))
+    if background != "mci" and mci_precision != "full":
+        raise ValueError("%s: mci_precision is a setting of background='mci'" % who)
     return RANGES[mci_range], mci_border
 
 
@@ -277,6 +309,92 @@ def mci_field_host(a_u8, b_u8, levels=LEVELS, border="clamp"):
     return np.stack([median3(dx), median3(dy)], -1).astype(np.int16)
 
 
+def half_plane(y):
+    """U(Y): uint8 [h, w] -> uint8 [2h-1, 2w-1], the plane at half-pel positions (even coordinates are Y itself)."""
+    h, w = y.shape
+    Q, P = np.arange(2 * h - 1), np.arange(2 * w - 1)
+    r0, c0 = Q >> 1, P >> 1
+    r1, c1 = np.minimum(r0 + (Q & 1), h - 1), np.minimum(c0 + (P & 1), w - 1)
+    v = y.astype(np.int32)
+    return ((v[r0][:, c0] + v[r0][:, c1] + v[r1][:, c0] + v[r1][:, c1] + 2) >> 2).astype(np.uint8)
+
+
+def pack_key_half(cost, hx, hy):
+    """The tuple (cost, hx*hx + hy*hy, hy, hx) of a half-pel candidate as one integer in the tuple's order: cost << 34 |
+    (hx*hx + hy*hy) << 18 | (hy + 256) << 9 | (hx + 256), for cost <= 64 * 255 + 2 * 318 < 2^15, hx*hx + hy*hy <= 2 * 159^2 =
+    50562 < 2^16 and |hx|, |hy| <= 159 < 256."""
+    return (cost.astype(np.int64) << 34) | ((hx * hx + hy * hy).astype(np.int64) << 18) | ((hy + HALF_KEY_BIAS).astype(np.int64) << 9) \
+        | (hx + HALF_KEY_BIAS).astype(np.int64)
+
+
+def unpack_key_half(key):
+    """(cost, hx, hy) of a pack_key_half key."""
+    key = np.asarray(key, np.int64)
+    return key >> 34, ((key & 511) - HALF_KEY_BIAS).astype(np.int32), (((key >> 9) & 511) - HALF_KEY_BIAS).astype(np.int32)
+
+
+def valid_counts_half(h, w, hx, hy):
+    """valid_counts in half-pel coordinates: the pixels p with 2p - h and 2p + h inside [0, 2(w-1)] x [0, 2(h-1)] are those with
+    p -+ ceil(|h| / 2) inside the plane."""
+    return valid_counts(h, w, (np.abs(hx) + 1) >> 1, (np.abs(hy) + 1) >> 1)
+
+
+def block_cost_half(ua, ub, hx, hy, border="clamp"):
+    """(cost, valid) of the half-pel candidate (hx, hy) int [Hb, Wb] of every block: ua, ub the half-pel planes [2h-1, 2w-1].
+    border="clamp": the SAD over the block's pixels, samples clamped to the half-pel plane, + LAMBDA_HALF's term; valid
+    everywhere.  border="valid": block_cost_valid's rule (cost 0 where n = 0)."""
+    h, w = (ua.shape[0] + 1) // 2, (ua.shape[1] + 1) // 2
+    Hb, Wb = field_shape(h, w)
+    px = np.repeat(np.repeat(hx, BLOCK, 0), BLOCK, 1)[:h, :w]
+    py = np.repeat(np.repeat(hy, BLOCK, 0), BLOCK, 1)[:h, :w]
+    Y, X = np.mgrid[0:h, 0:w]
+    ay, ax, by, bx = 2 * Y - py, 2 * X - px, 2 * Y + py, 2 * X + px
+    ymax, xmax = 2 * (h - 1), 2 * (w - 1)
+    a = ua[np.clip(ay, 0, ymax), np.clip(ax, 0, xmax)].astype(np.int32)
+    b = ub[np.clip(by, 0, ymax), np.clip(bx, 0, xmax)].astype(np.int32)
+    diff = np.abs(a - b)
+    penalty = LAMBDA_HALF * (np.abs(hx) + np.abs(hy))
+    sad = np.zeros((Hb * BLOCK, Wb * BLOCK), np.int64)
+    if border == "clamp":
+        sad[:h, :w] = diff
+        return sad.reshape(Hb, BLOCK, Wb, BLOCK).sum((1, 3)) + penalty, np.ones((Hb, Wb), bool)
+    inside = (ay >= 0) & (ay <= ymax) & (by >= 0) & (by <= ymax) & (ax >= 0) & (ax <= xmax) & (bx >= 0) & (bx <= xmax)
+    sad[:h, :w] = np.where(inside, diff, 0)
+    n, N = valid_counts_half(h, w, hx, hy)
+    return (64 * sad.reshape(Hb, BLOCK, Wb, BLOCK).sum((1, 3))) // np.maximum(n, 1) + penalty, VALID_SHARE * n >= N
+
+
+def mci_refine_host(a_u8, b_u8, field, border="clamp"):
+    """The half-pel refinement of a block field: a_u8, b_u8 uint8 [H, W, 3], field int16 [Hb, Wb, 2] of mci_field_host (any
+    levels; |d| <= max_disp(5)) -> int16 [Hb, Wb, 2] in HALF pixels: for every block the minimum of (cost, hx*hx + hy*hy, hy, hx)
+    over h in 2 d + [-1, 1]^2 (see the module's text); border="valid": over the valid candidates, and a block whose start 2 d is
+    not valid keeps 2 d.  For mci_frames_host(precision="half")."""
+    check_border(border, "mci_refine_host")
+    a_u8, b_u8, field = np.asarray(a_u8), np.asarray(b_u8), np.asarray(field)
+    if a_u8.dtype != np.uint8 or a_u8.ndim != 3 or a_u8.shape[2] != 3 or a_u8.shape != b_u8.shape or b_u8.dtype != np.uint8:
+        raise ValueError("mci_refine_host: two uint8 [H, W, 3] frames of one size, got %s %s and %s %s"
+                         % (a_u8.dtype, a_u8.shape, b_u8.dtype, b_u8.shape))
+    H, W = a_u8.shape[:2]
+    Hb, Wb = field_shape(H, W)
+    if tuple(field.shape) != (Hb, Wb, 2) or field.dtype != np.int16:
+        raise ValueError("mci_refine_host: the field of a %dx%d frame is int16 [%d, %d, 2], got %s %s" % (H, W, Hb, Wb, field.dtype, tuple(field.shape)))
+    if field.size and np.abs(field.astype(np.int32)).max() > max_disp(MAX_LEVELS):
+        raise ValueError("mci_refine_host: the field's components must lie in -%d..%d" % (max_disp(MAX_LEVELS), max_disp(MAX_LEVELS)))
+    ua, ub = half_plane(luma(a_u8)), half_plane(luma(b_u8))
+    sx, sy = 2 * field[..., 0].astype(np.int32), 2 * field[..., 1].astype(np.int32)
+    never = np.int64(1) << 62
+    best = None
+    for ey in range(-REFINE, REFINE + 1):
+        for ex in range(-REFINE, REFINE + 1):
+            hx, hy = sx + ex, sy + ey
+            cost, ok = block_cost_half(ua, ub, hx, hy, border)
+            key = np.where(ok, pack_key_half(np.where(ok, cost, 0), hx, hy), never)
+            best = key if best is None else np.minimum(best, key)
+    searched = block_cost_half(ua, ub, sx, sy, border)[1]
+    _, wx, wy = unpack_key_half(np.where(searched, best, 0))
+    return np.stack([np.where(searched, wx, sx), np.where(searched, wy, sy)], -1).astype(np.int16)
+
+
 def pixel_field(field, height, width):
     """D(p) of every pixel: int16 [Hb, Wb, 2] -> (Dx, Dy) int32 [H, W] in 1/256 px."""
     Hb, Wb = field_shape(height, width)
@@ -315,11 +433,13 @@ def sample_valid(py, px, height, width):
     return (py >= 0) & (py <= (height - 1) << SAMPLE_FRAC_BITS) & (px >= 0) & (px <= (width - 1) << SAMPLE_FRAC_BITS)
 
 
-def mci_frames_host(a_u8, b_u8, field, sample_rate, ks, border="clamp"):
+def mci_frames_host(a_u8, b_u8, field, sample_rate, ks, border="clamp", precision="full"):
     """Frames ks (each 0 <= k <= sample_rate; k = 0 is A, k = sample_rate is B) of the segment between the key frames a_u8 and
     b_u8 (uint8 [H, W, 3]) from their block field (mci_field_host) -> uint8 [len(ks), H, W, 3].  border="valid": where exactly
-    one of a pixel's two samples lies inside the frame the output is that sample alone."""
+    one of a pixel's two samples lies inside the frame the output is that sample alone.  precision="half": the field is
+    mci_refine_host's, in half pixels - the offsets are k Dh / s and (s-k) Dh / s in place of 2k D / s and 2(s-k) D / s."""
     check_border(border, "mci_frames_host")
+    unit = 1 if check_precision(precision, "mci_frames_host") == "half" else 2
     a_u8, b_u8, field = np.asarray(a_u8), np.asarray(b_u8), np.asarray(field)
     if a_u8.dtype != np.uint8 or a_u8.ndim != 3 or a_u8.shape[2] != 3 or a_u8.shape != b_u8.shape or b_u8.dtype != np.uint8:
         raise ValueError("mci_frames_host: two uint8 [H, W, 3] frames of one size, got %s and %s" % (a_u8.shape, b_u8.shape))
@@ -333,8 +453,8 @@ def mci_frames_host(a_u8, b_u8, field, sample_rate, ks, border="clamp"):
         k = int(k)
         if not 0 <= k <= s:
             raise ValueError("mci_frames_host: frame %d is outside the segment 0..%d" % (k, s))
-        ax, ay = (2 * k * Dx + s // 2) >> ls, (2 * k * Dy + s // 2) >> ls
-        bx, by = (2 * (s - k) * Dx + s // 2) >> ls, (2 * (s - k) * Dy + s // 2) >> ls
+        ax, ay = (unit * k * Dx + s // 2) >> ls, (unit * k * Dy + s // 2) >> ls
+        bx, by = (unit * (s - k) * Dx + s // 2) >> ls, (unit * (s - k) * Dy + s // 2) >> ls
         a = sample_bilinear(a_u8, Y - ay, X - ax)
         b = sample_bilinear(b_u8, Y + by, X + bx)
         o = ((s - k) * a + k * b + s // 2) >> ls

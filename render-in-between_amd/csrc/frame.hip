@@ -419,24 +419,51 @@ int rib_mci_field(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, 
   return RIB_OK;
 }
 
-int rib_mci_frames(rib_handle* handle, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const int16_t* field_i16,
-                   int sample_rate, int k_first, int border, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream) {
+int rib_halfpel_refine(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const int16_t* field_i16,
+                   int16_t* field_half_i16, int border, void* hip_stream) {
   FrameState* h = frame_state(handle);
   if (!h) return RIB_ERR_INVALID;
-  if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_mci_frames: host-only handle");
-  if (!a_u8 || !b_u8 || !field_i16) return fail(h, RIB_ERR_INVALID, "rib_mci_frames: null pointer");
-  if (!out_f32_nchw && !out_u8_nhwc) return fail(h, RIB_ERR_INVALID, "rib_mci_frames: both outputs are null");
+  if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_halfpel_refine: host-only handle");
+  if (!a_u8 || !b_u8 || !field_i16 || !field_half_i16) return fail(h, RIB_ERR_INVALID, "rib_halfpel_refine: null pointer");
+  if (border != 0 && border != 1)
+    return fail(h, RIB_ERR_INVALID, fmt("rib_halfpel_refine: border=%d: 0 (clamped samples) or 1 (valid samples only)", border));
+  MciLayout L;
+  if (!mci_layout(B, H, W, MCI_MIN_LEVELS, &L))
+    return fail(h, RIB_ERR_INVALID, fmt("rib_halfpel_refine: B=%d H=%d W=%d: 1 <= B <= 32767, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", B, H, W, MCI_MAX_SIDE));
+  if ((reinterpret_cast<uintptr_t>(field_i16) & 3) != 0 || (reinterpret_cast<uintptr_t>(field_half_i16) & 3) != 0)
+    return fail(h, RIB_ERR_INVALID, "rib_halfpel_refine: the fields must be 4-byte aligned");
+  HIP_TRY(h, hipSetDevice(h->device));
+  MciRefineParams rp;
+  rp.a = a_u8; rp.b = b_u8; rp.field = field_i16; rp.out = field_half_i16;
+  rp.B = B; rp.H = H; rp.W = W; rp.Hb = L.Hb[0]; rp.Wb = L.Wb[0];
+  const dim3 grid((rp.Hb * rp.Wb + MCI_RUN - 1) / MCI_RUN, B);
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  if (border) hipLaunchKernelGGL(k_mci_refine<true>, grid, dim3(256), 0, st, rp);
+  else hipLaunchKernelGGL(k_mci_refine<false>, grid, dim3(256), 0, st, rp);
+  HIP_TRY(h, hipGetLastError());
+  return RIB_OK;
+}
+
+// rib_mci_frames / rib_halfpel_frames: one body, one kernel template; half: the field is rib_halfpel_refine's, in half pixels
+static int mci_frames_enqueue(const char* who, bool half, rib_handle* handle, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8,
+                              const int16_t* field_i16, int sample_rate, int k_first, int border, float* out_f32_nchw, uint8_t* out_u8_nhwc,
+                              void* hip_stream) {
+  FrameState* h = frame_state(handle);
+  if (!h) return RIB_ERR_INVALID;
+  if (h->device < 0) return fail(h, RIB_ERR_INVALID, fmt("%s: host-only handle", who));
+  if (!a_u8 || !b_u8 || !field_i16) return fail(h, RIB_ERR_INVALID, fmt("%s: null pointer", who));
+  if (!out_f32_nchw && !out_u8_nhwc) return fail(h, RIB_ERR_INVALID, fmt("%s: both outputs are null", who));
   MciLayout L;
   if (T < 1 || !mci_layout(B, H, W, MCI_MIN_LEVELS, &L) || (size_t)T * B > 65535)
-    return fail(h, RIB_ERR_INVALID, fmt("rib_mci_frames: T=%d B=%d H=%d W=%d: T, B >= 1, T * B <= 65535, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", T, B, H, W, MCI_MAX_SIDE));
+    return fail(h, RIB_ERR_INVALID, fmt("%s: T=%d B=%d H=%d W=%d: T, B >= 1, T * B <= 65535, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", who, T, B, H, W, MCI_MAX_SIDE));
   if (sample_rate < 1 || sample_rate > MCI_MAX_RATE || (sample_rate & (sample_rate - 1)) != 0)
-    return fail(h, RIB_ERR_INVALID, fmt("rib_mci_frames: sample_rate=%d: a power of two in 1..%d", sample_rate, MCI_MAX_RATE));
+    return fail(h, RIB_ERR_INVALID, fmt("%s: sample_rate=%d: a power of two in 1..%d", who, sample_rate, MCI_MAX_RATE));
   if (k_first < 0 || k_first + T - 1 > sample_rate)
-    return fail(h, RIB_ERR_INVALID, fmt("rib_mci_frames: frames %d..%d are outside the segment 0..%d", k_first, k_first + T - 1, sample_rate));
+    return fail(h, RIB_ERR_INVALID, fmt("%s: frames %d..%d are outside the segment 0..%d", who, k_first, k_first + T - 1, sample_rate));
   if (border != 0 && border != 1)
-    return fail(h, RIB_ERR_INVALID, fmt("rib_mci_frames: border=%d: 0 (clamped samples) or 1 (valid samples only)", border));
+    return fail(h, RIB_ERR_INVALID, fmt("%s: border=%d: 0 (clamped samples) or 1 (valid samples only)", who, border));
   if ((reinterpret_cast<uintptr_t>(field_i16) & 1) != 0 || (reinterpret_cast<uintptr_t>(out_f32_nchw) & 3) != 0)
-    return fail(h, RIB_ERR_INVALID, "rib_mci_frames: misaligned pointer");
+    return fail(h, RIB_ERR_INVALID, fmt("%s: misaligned pointer", who));
   MciFramesParams fp;
   fp.a = a_u8; fp.b = b_u8; fp.field = field_i16; fp.out_f32 = out_f32_nchw; fp.out_u8 = out_u8_nhwc;
   fp.T = T; fp.B = B; fp.H = H; fp.W = W; fp.Hb = L.Hb[0]; fp.Wb = L.Wb[0]; fp.s = sample_rate; fp.k_first = k_first;
@@ -445,9 +472,28 @@ int rib_mci_frames(rib_handle* handle, int T, int B, int H, int W, const uint8_t
   fp.vec = (W % 4 == 0 && (reinterpret_cast<uintptr_t>(out_f32_nchw) & 15) == 0 && (reinterpret_cast<uintptr_t>(out_u8_nhwc) & 3) == 0) ? 1 : 0;
   HIP_TRY(h, hipSetDevice(h->device));
   const size_t lds = out_u8_nhwc ? (size_t)W * 3 + 32 : 0;
-  if (border) hipLaunchKernelGGL(k_mci_frames<true>, dim3(H, T * B), dim3(256), lds, reinterpret_cast<hipStream_t>(hip_stream), fp);
-  else hipLaunchKernelGGL(k_mci_frames<false>, dim3(H, T * B), dim3(256), lds, reinterpret_cast<hipStream_t>(hip_stream), fp);
+  const dim3 grid(H, T * B);
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  if (half) {
+    if (border) hipLaunchKernelGGL((k_mci_frames<true, true>), grid, dim3(256), lds, st, fp);
+    else hipLaunchKernelGGL((k_mci_frames<false, true>), grid, dim3(256), lds, st, fp);
+  } else {
+    if (border) hipLaunchKernelGGL((k_mci_frames<true, false>), grid, dim3(256), lds, st, fp);
+    else hipLaunchKernelGGL((k_mci_frames<false, false>), grid, dim3(256), lds, st, fp);
+  }
   HIP_TRY(h, hipGetLastError());
   return RIB_OK;
+}
+
+int rib_mci_frames(rib_handle* handle, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const int16_t* field_i16,
+                   int sample_rate, int k_first, int border, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream) {
+  return mci_frames_enqueue("rib_mci_frames", false, handle, T, B, H, W, a_u8, b_u8, field_i16, sample_rate, k_first, border, out_f32_nchw,
+                            out_u8_nhwc, hip_stream);
+}
+
+int rib_halfpel_frames(rib_handle* handle, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const int16_t* field_half_i16,
+                        int sample_rate, int k_first, int border, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream) {
+  return mci_frames_enqueue("rib_halfpel_frames", true, handle, T, B, H, W, a_u8, b_u8, field_half_i16, sample_rate, k_first, border,
+                            out_f32_nchw, out_u8_nhwc, hip_stream);
 }
 }  // extern "C"

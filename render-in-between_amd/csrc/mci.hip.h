@@ -1,7 +1,7 @@
 // mci.hip.h — motion-compensated interpolation of a segment's two key frames: the folder driver's background="mci"
-// (rib_mci_field / rib_mci_frames, include/rib.h).  This project's interpolation, not DAIN.
+// (rib_mci_field / rib_halfpel_refine / rib_mci_frames / rib_halfpel_frames, include/rib.h).  This project's interpolation, not DAIN.
 //
-// background.py (mci_field_host, mci_frames_host) states the result in integers; every kernel here is bit-equal to it.
+// background.py (mci_field_host, mci_refine_host, mci_frames_host) states the result in integers; every kernel here is bit-equal to it.
 //
 //   k_mci_luma_pyramid  grid (tiles of 32 x 32, 2B): luma Y = (77 R + 150 G + 29 B + 128) >> 8 of one tile and, from LDS, its
 //                       16 x 16 of level 1 and 8 x 8 of level 2 ((2x2 parents, clamped, + 2) >> 2) - and, where a wider search
@@ -26,12 +26,24 @@
 //                       4 n < N do not compete, and a block whose start itself is such a candidate (uniform per wave) stores
 //                       its start.
 //   k_mci_median        3x3 componentwise median of the level-0 field, clamped.
+//   k_mci_refine        (rib_halfpel_refine; background.mci_refine_host) grid (runs of MCI_RUN blocks, B), one launch shaped like
+//                       k_mci_search<1>: the half-pel refinement of the field after the median.  A workgroup stages, per block,
+//                       the clamped 10 x 10 INTEGER luma windows of A around p - d and of B around p + d, luma computed from the
+//                       RGB bytes while staging (no workspace, nothing of rib_mci_field's is read); a wave takes a block, its
+//                       lanes the 9 candidates h = 2 d + e x 4 row pairs; a half-pel value is the rounded mean of the one, two or
+//                       four staged integers around it (the definition's half_plane; the clamped window repeats an edge pixel
+//                       where the half-pel plane is clamped, and the mean of a pixel with itself is the pixel); the winner is the
+//                       wave minimum of background.pack_key_half.  <VALID = true>: the rectangle of p -+ ceil(|h| / 2) inside
+//                       the plane, as above.  A block reads only its own vector, staged before any is written: out may be the
+//                       input.  |d| is clamped to 79 (max_disp(5)), so the key's fields always hold h.
 //   k_mci_frames        grid (H, T * B): a workgroup owns ONE row of one frame; a thread takes 4 consecutive x: D(p) bilinear
 //                       from the block field (exact, 1/256 px), the two fixed-point bilinear samples, the blend; float4 stores
 //                       per channel plane of the normalised NCHW tensor, and the uint8 NHWC row through LDS as 16-byte
 //                       stores contiguous across the wave (k_panel's scheme).  Either output may be null.  <VALID = true>:
 //                       a sample is valid when its position lies in [0, (H-1) << 8] x [0, (W-1) << 8]; where exactly one of
 //                       the two is, the output is that sample instead of the blend (four comparisons per sample, a select).
+//                       <VALID, HALF = true> (rib_halfpel_frames): the field is in half pixels, the offsets k D / s and
+//                       (s-k) D / s; the multiplier is a compile-time constant, <VALID, false> is the code it was.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -44,6 +56,7 @@ constexpr int MCI_BLOCK = 8, MCI_LAMBDA = 4, MCI_TOP_R = 4, MCI_KEY_BIAS = 128; 
 constexpr int MCI_MIN_LEVELS = 3, MCI_MAX_LEVELS = 5;                               // background.py MIN_LEVELS, MAX_LEVELS
 constexpr int MCI_RUN = 8;                  // blocks per workgroup of k_mci_search
 constexpr int MCI_MAX_SIDE = 16384, MCI_MAX_RATE = 1024;
+constexpr int MCI_MAX_DISP = 79, MCI_LAMBDA_HALF = 2, MCI_HALF_KEY_BIAS = 256;      // background.py max_disp(5), LAMBDA_HALF, HALF_KEY_BIAS
 
 struct MciLumaParams {
   const uint8_t *a, *b;                     // [B, H, W, 3]
@@ -220,6 +233,112 @@ __global__ __launch_bounds__(256) void k_mci_search(MciSearchParams p) {
   }
 }
 
+struct MciRefineParams {
+  const uint8_t *a, *b;                     // [B, H, W, 3]
+  const int16_t* field;                     // [B, Hb, Wb, 2] integer (dx, dy), after the median
+  int16_t* out;                             // [B, Hb, Wb, 2] in half pixels; may be `field` itself
+  int B, H, W, Hb, Wb;
+};
+
+// the half-pel value at offset (oy, ox) + ((fy, fx) halves) of a staged integer window: background.half_plane's rounding (a
+// repeated tap gives (a + b + 1) >> 1 or the pixel itself)
+__device__ inline int mci_half_tap(const uint8_t* w, int ws, int fy, int fx) {
+  return (w[0] + w[fx] + w[fy * ws] + w[fy * ws + fx] + 2) >> 2;
+}
+
+template <bool VALID = false>
+__global__ __launch_bounds__(256) void k_mci_refine(MciRefineParams p) {
+  constexpr int R = 1, WS = MCI_BLOCK + 2 * R, WIN = WS * WS, SIDE = 3, NC = 9, PARTS = 4, ROWS = MCI_BLOCK / PARTS;
+  __shared__ uint8_t s_win[MCI_RUN][2][WIN];
+  __shared__ int s_start[MCI_RUN][2];
+  const int tid = threadIdx.x, b = blockIdx.y;
+  const int nblk = p.Hb * p.Wb, blk0 = blockIdx.x * MCI_RUN;
+  if (tid < MCI_RUN) {                      // a block reads its own vector only, and before any is written: in place is allowed
+    int sx = 0, sy = 0;
+    const int blk = blk0 + tid;
+    if (blk < nblk) {
+      const int16_t* c = p.field + ((size_t)b * nblk + blk) * 2;
+      sx = min(max((int)c[0], -MCI_MAX_DISP), MCI_MAX_DISP); sy = min(max((int)c[1], -MCI_MAX_DISP), MCI_MAX_DISP);
+    }
+    s_start[tid][0] = sx; s_start[tid][1] = sy;
+  }
+  __syncthreads();
+  for (int i = tid; i < MCI_RUN * 2 * WIN; i += 256) {
+    const int j = i / (2 * WIN), rem = i - j * 2 * WIN, which = rem / WIN, e = rem - which * WIN;
+    const int wy = e / WS, wx = e - wy * WS, blk = blk0 + j;
+    if (blk < nblk) {
+      const int by = blk / p.Wb, bx = blk - by * p.Wb, sgn = which ? 1 : -1;
+      const int y = min(max(MCI_BLOCK * by + sgn * s_start[j][1] - R + wy, 0), p.H - 1);
+      const int x = min(max(MCI_BLOCK * bx + sgn * s_start[j][0] - R + wx, 0), p.W - 1);
+      const uint8_t* px = (which ? p.b : p.a) + (((size_t)b * p.H + y) * p.W + x) * 3;
+      s_win[j][which][e] = (uint8_t)((77 * px[0] + 150 * px[1] + 29 * px[2] + 128) >> 8);
+    }
+  }
+  __syncthreads();
+  const int wave = tid >> 6, lane = tid & 63;
+  for (int j = wave; j < MCI_RUN; j += 4) {
+    const int blk = blk0 + j;
+    if (blk >= nblk) break;                 // (uniform per wave; no barrier below)
+    const int by = blk / p.Wb, bx = blk - by * p.Wb;
+    const int ph = min(MCI_BLOCK, p.H - MCI_BLOCK * by), pw = min(MCI_BLOCK, p.W - MCI_BLOCK * bx);
+    const int sx = s_start[j][0], sy = s_start[j][1];
+    const uint8_t *wa = s_win[j][0], *wb = s_win[j][1];
+    int16_t* o = p.out + ((size_t)b * nblk + blk) * 2;
+    if constexpr (VALID) {                  // the start 2 d keeps the pixels d keeps; too few of them: nothing to search
+      int xl, xh, yl, yh;
+      mci_valid_span(MCI_BLOCK * bx, pw, sx, p.W, xl, xh);
+      mci_valid_span(MCI_BLOCK * by, ph, sy, p.H, yl, yh);
+      if (4 * (xh - xl) * (yh - yl) < pw * ph) {      // (uniform per wave: the shuffles below are not reached by any lane)
+        if (lane == 0) { o[0] = (int16_t)(2 * sx); o[1] = (int16_t)(2 * sy); }
+        continue;
+      }
+    }
+    const int c = lane / PARTS, part = lane - c * PARTS;
+    const bool active = c < NC;
+    const int ey = active ? c / SIDE - R : 0, ex = active ? c - (c / SIDE) * SIDE - R : 0;
+    const int hx = 2 * sx + ex, hy = 2 * sy + ey;
+    int xl = 0, xh = pw, yl = 0, yh = ph;
+    if constexpr (VALID) {                  // 2p - h and 2p + h inside the half-pel plane: p -+ ceil(|h| / 2) inside the plane
+      mci_valid_span(MCI_BLOCK * bx, pw, (abs(hx) + 1) >> 1, p.W, xl, xh);
+      mci_valid_span(MCI_BLOCK * by, ph, (abs(hy) + 1) >> 1, p.H, yl, yh);
+    }
+    const int n = (xh - xl) * (yh - yl);
+    // A at 2(p - d) - e: e = 1 starts one integer pixel lower; B at 2(p + d) + e: e = -1 does; e != 0 is a half position
+    const int fy = ey != 0, fx = ex != 0;
+    const int ay = R - (ey > 0), ax = R - (ex > 0), cy = R - (ey < 0), cx = R - (ex < 0);
+    int sad = 0;
+    for (int r = part * ROWS; r < (part + 1) * ROWS; ++r) {
+      if (r < ph) {
+        const uint8_t* ra = wa + (r + ay) * WS + ax;
+        const uint8_t* rb = wb + (r + cy) * WS + cx;
+        for (int x = 0; x < pw; ++x) {
+          const int d = abs(mci_half_tap(ra + x, WS, fy, fx) - mci_half_tap(rb + x, WS, fy, fx));
+          if constexpr (VALID) sad += (r >= yl && r < yh && x >= xl && x < xh) ? d : 0;
+          else sad += d;
+        }
+      }
+    }
+#pragma unroll
+    for (int m = 1; m < PARTS; m <<= 1) sad += __shfl_xor(sad, m);
+    if constexpr (VALID) sad = (64 * sad) / max(n, 1);      // (n = 0: not a candidate, below)
+    const bool counts = VALID ? active && 4 * n >= pw * ph : active;
+    // background.pack_key_half: cost << 34 | hx^2 + hy^2 << 18 | hy + 256 << 9 | hx + 256
+    unsigned long long best = ~0ull;
+    if (counts)
+      best = ((unsigned long long)(sad + MCI_LAMBDA_HALF * (abs(hx) + abs(hy))) << 34) | ((unsigned long long)(hx * hx + hy * hy) << 18) |
+             ((unsigned long long)(hy + MCI_HALF_KEY_BIAS) << 9) | (unsigned long long)(hx + MCI_HALF_KEY_BIAS);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      const unsigned long long v = __shfl_xor(best, m);
+      if (v < best) best = v;
+    }
+    if (lane == 0) {
+      o[0] = (int16_t)((int)(best & 511) - MCI_HALF_KEY_BIAS);
+      o[1] = (int16_t)((int)((best >> 9) & 511) - MCI_HALF_KEY_BIAS);
+    }
+  }
+}
+
 // the median of nine by a fixed network of 19 compare-exchanges (statically indexed: the values stay in registers)
 __device__ inline void mci_cx(int& a, int& b) { const int lo = min(a, b), hi = max(a, b); a = lo; b = hi; }
 __device__ inline int mci_median9(int v[9]) {
@@ -270,8 +389,9 @@ __device__ inline void mci_sample(const uint8_t* img, int H, int W, int py, int 
     v[c] = ((256 - fy) * ((256 - fx) * p00[c] + fx * p01[c]) + fy * ((256 - fx) * p10[c] + fx * p11[c]) + (1 << 15)) >> 16;
 }
 
-template <bool VALID = false>
+template <bool VALID = false, bool HALF = false>
 __global__ __launch_bounds__(256) void k_mci_frames(MciFramesParams p) {
+  constexpr int UNIT = HALF ? 1 : 2;        // the field's unit in half pixels: the motion between the key frames is UNIT * D
   extern __shared__ __attribute__((aligned(16))) uint8_t s_mci[];
   const int y = blockIdx.x, tb = blockIdx.y, t = tb / p.B, bi = tb - t * p.B;
   const int H = p.H, W = p.W, k = p.k_first + t, s = p.s, ls = p.ls;
@@ -298,8 +418,8 @@ __global__ __launch_bounds__(256) void k_mci_frames(MciFramesParams p) {
       const int16_t *f10 = fld + (r1 * p.Wb + c0) * 2, *f11 = fld + (r1 * p.Wb + c1) * 2;
       const int Dx = (16 - fy) * ((16 - fx) * f00[0] + fx * f01[0]) + fy * ((16 - fx) * f10[0] + fx * f11[0]);
       const int Dy = (16 - fy) * ((16 - fx) * f00[1] + fx * f01[1]) + fy * ((16 - fx) * f10[1] + fx * f11[1]);
-      const int ax = (2 * k * Dx + (s >> 1)) >> ls, ay = (2 * k * Dy + (s >> 1)) >> ls;
-      const int bx = (2 * (s - k) * Dx + (s >> 1)) >> ls, by = (2 * (s - k) * Dy + (s >> 1)) >> ls;
+      const int ax = (UNIT * k * Dx + (s >> 1)) >> ls, ay = (UNIT * k * Dy + (s >> 1)) >> ls;
+      const int bx = (UNIT * (s - k) * Dx + (s >> 1)) >> ls, by = (UNIT * (s - k) * Dy + (s >> 1)) >> ls;
       int va[3], vb[3];
       mci_sample(A, H, W, (y << 8) - ay, (x << 8) - ax, va);
       mci_sample(Bf, H, W, (y << 8) + by, (x << 8) + bx, vb);

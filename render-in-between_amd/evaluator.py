@@ -564,7 +564,8 @@ class Evaluator:
                              rank=None, world=None, metrics=False, mask_dir=None, pose_mask=False,
                              panels=False, panel_frames=False, panel_quality=90, panel_fps=30, panel_encode="host",
                              background="dain", mci_range=32, video=False, video_fps=30, video_quality=90, video_frames=False, frames="png",
-                             poses="folder", key_pose_dir=None, upsample_rate=8, motion=None, save_poses=False, mci_border="clamp"):
+                             poses="folder", key_pose_dir=None, upsample_rate=8, motion=None, save_poses=False, mci_border="clamp",
+                             mci_precision="full"):
         """rank / world: this process's share of the independent units (default: the torch.distributed process
         group when one is initialised, else everything).  Returns the frames THIS rank wrote.
         The call is one `_FolderPipeline` (below): plan a clip -> decode -> upload -> render -> sink, pipelined over units
@@ -599,7 +600,11 @@ class Evaluator:
         room for a false match on periodic content.  mci_border="valid" (default "clamp"; a setting of background="mci") makes
         matching and sampling one-sided at the FRAME border (background.py's border="valid"): a strip that only one key frame
         shows is taken from that key frame alone, not blended with a smear of the other's edge; occlusion inside the frame (a
-        foreground object covering background) is not handled.  dain_dir may be
+        foreground object covering background) is not handled.  mci_precision="half" (default "full"; a setting of
+        background="mci"): the integer field writes the motion between the key frames as an even number of pixels; one more
+        launch per group (rib_halfpel_refine; background.mci_refine_host) refines every block's vector by half a pixel and the frames
+        are sampled from that field (rib_halfpel_frames; mci_frames_host(precision="half")).  Half-pel samples are bilinear and
+        soft, and a block whose integer vector is more than one half-pel step from the truth stays wrong.  dain_dir may be
         None and is never listed or read; a frame's file is named after its pose file (stem without a trailing "_keypoints").
         On the native path the field is made once per group of segments (rib_mci_field) and every unit's frames by one launch
         (rib_mci_frames) on the upload stream - no DAIN bytes are staged or decoded; a model behind the reference's protocol is
@@ -637,7 +642,7 @@ class Evaluator:
                 raise ValueError("evaluate_from_folder: poses=%r needs motion= (the motion model, motion.model.ModelInference)" % (poses,))
             if not (isinstance(upsample_rate, int) and upsample_rate >= 1 and upsample_rate & (upsample_rate - 1) == 0):
                 raise ValueError("evaluate_from_folder: upsample_rate must be a power of two, got %r" % (upsample_rate,))
-        mci_levels, mci_border = _background.check_settings(background, mci_range, mci_border, self.resize_on)
+        mci_levels, mci_border = _background.check_settings(background, mci_range, mci_border, self.resize_on, mci_precision=mci_precision)
         if gen_vid:
             # the reference also writes <save_dir>/<clip>.mp4 (evaluator.py:267-269, utils.make_video) from a matplotlib canvas
             # through an H.264 encoder; neither is built, and silently ignoring the flag would drop an output the caller asked for
@@ -669,10 +674,10 @@ class Evaluator:
         self.metrics = self.metrics_report = None
         pipe = _FolderPipeline(self, model, rank, world, gt_dir, metrics=bool(metrics), mask_dir=mask_dir, pose_mask=bool(pose_mask),
                                panels=bool(panels), panel_frames=bool(panel_frames), panel_quality=int(panel_quality),
-                               panel_encode=panel_encode, background=background, mci_levels=mci_levels, mci_border=mci_border, video=bool(video), video_quality=int(video_quality),
+                               panel_encode=panel_encode, background=background, mci_levels=mci_levels, mci_border=mci_border, mci_precision=mci_precision, video=bool(video), video_quality=int(video_quality),
                                video_frames=bool(video_frames), write_png=frames == "png",
                                key_poses=None if poses == "folder" else (motion, key_pose_dir, upsample_rate, poses == "keyframes-linear", bool(save_poses)))
-        self.background, self.mci_range, self.mci_border = background, mci_range, mci_border
+        self.background, self.mci_range, self.mci_border, self.mci_precision = background, mci_range, mci_border, mci_precision
         self.timings = pipe.tm
         if metrics and pipe.native:
             self._quality_model = model
@@ -777,9 +782,10 @@ class _FolderPipeline:
 
     def __init__(self, ev, model, rank, world, gt_dir, metrics=False, mask_dir=None, pose_mask=False,
                  panels=False, panel_frames=False, panel_quality=90, panel_encode="host", background="dain", mci_levels=3,
-                 video=False, video_quality=90, video_frames=False, write_png=True, key_poses=None, mci_border="clamp"):
+                 video=False, video_quality=90, video_frames=False, write_png=True, key_poses=None, mci_border="clamp", mci_precision="full"):
         self.mci, self.mci_levels = background == "mci", mci_levels      # (levels: background.mci_field_host's, from mci_range)
         self.mci_border = mci_border        # background.py's border
+        self.mci_half = mci_precision == "half"      # background.py's precision: the field is refined once per group, in half pixels
         # poses="keyframes": (motion model, key-pose folder, upsample rate, take the linear clip, also write the json folders)
         self.key_poses = key_poses
         # video: the frames' JPEG files (video.py); write_png False (frames="none"): they are the only files of a frame
@@ -798,6 +804,8 @@ class _FolderPipeline:
             raise RuntimeError("panels=True: this model has no GPU sheet kernel (rib_panel)")
         if self.native and self.mci and not hasattr(model, "mci_frames"):
             raise RuntimeError("background='mci': this model has no GPU interpolation kernels (rib_mci_field / rib_mci_frames)")
+        if self.native and self.mci_half and not hasattr(model, "mci_refine"):
+            raise RuntimeError("mci_precision='half': this model has no GPU refinement kernel (rib_halfpel_refine)")
         self.jpeg_gpu = panels and panel_encode == "gpu"     # the sheets' JPEG files are jpeg_encode_host's bytes (rib_jpeg on the native path)
         if self.native and self.jpeg_gpu and not hasattr(model, "jpeg_into"):
             raise RuntimeError("panel_encode='gpu': this model has no GPU JPEG kernels (rib_jpeg)")
@@ -1116,10 +1124,13 @@ class _FolderPipeline:
                         views["mci_keys"][0, b].copy_(clip.key_u8[k])
                         views["mci_keys"][1, b].copy_(clip.key_u8[k + clip.sample_rate])
                     kab = views["mci_keys"].to(g.device, non_blocking=True)
-                    clip.mci_of[gi] = (kab[0], kab[1], g.mci_field(kab[0], kab[1], self.mci_levels, border=self.mci_border))
+                    field = g.mci_field(kab[0], kab[1], self.mci_levels, border=self.mci_border)
+                    if self.mci_half:           # one more launch behind the field's, on the same stream; in place
+                        field = g.mci_refine(kab[0], kab[1], field, border=self.mci_border, out=field)
+                    clip.mci_of[gi] = (kab[0], kab[1], field)
                 ka, kb, field = clip.mci_of[gi]
                 dn = g.mci_frames(ka, kb, field, clip.sample_rate, k_first=c0 + 1, count=Tc, normalised="both" if self.panels else True,
-                                  border=self.mci_border)
+                                  border=self.mci_border, precision="half" if self.mci_half else "full")
                 if self.panels:
                     dn, dnu8 = dn
             else:
@@ -1478,8 +1489,11 @@ class _FolderPipeline:
             poses = [g[2] for g in got]
             if self.mci:                         # the host definition of the background frames (background.py)
                 ka, kb = clip.key_u8[k].numpy(), clip.key_u8[k + clip.sample_rate].numpy()
-                u8 = _background.mci_frames_host(ka, kb, _background.mci_field_host(ka, kb, self.mci_levels, border=self.mci_border), clip.sample_rate,
-                                                 [i - k for i in frames], border=self.mci_border)
+                field = _background.mci_field_host(ka, kb, self.mci_levels, border=self.mci_border)
+                if self.mci_half:
+                    field = _background.mci_refine_host(ka, kb, field, border=self.mci_border)
+                u8 = _background.mci_frames_host(ka, kb, field, clip.sample_rate, [i - k for i in frames], border=self.mci_border,
+                                                 precision="half" if self.mci_half else "full")
                 # the floats the native chain reads (the device's normalisation, stated on the host); the sheets' DAIN pane
                 # shows the host's normalisation, as the native path's does (normalise_exact)
                 dn = torch.from_numpy(_background.normalised_upload(u8)).unsqueeze(1)

@@ -589,16 +589,44 @@ class Generator:
                                                            self._stream()))
         return field[0] if single else field
 
-    def mci_frames(self, a_u8, b_u8, field, sample_rate, k_first=1, count=None, normalised=True, out=None, border="clamp"):
+    def mci_refine(self, a_u8, b_u8, field, border="clamp", out=None):
+        """The half-pel refinement of mci_field's result on the GPU (rib_halfpel_refine; background.mci_refine_host is the
+        definition and is bit-equal): a_u8, b_u8 uint8 [B,H,W,3] (or [H,W,3]), field int16 [B,Hb,Wb,2] (or [Hb,Wb,2]) on this
+        device, components within +-79 -> a new int16 tensor of the same shape in HALF pixels, for
+        mci_frames(precision="half").  out: optional contiguous destination of the field's shape; it may be the field itself (in
+        place: a block reads only its own vector).  One launch on the current stream, no workspace."""
+        from .background import BORDERS, check_border, field_shape
+        border = BORDERS.index(check_border(border, "mci_refine"))
+        a, b, single = self._mci_pair(a_u8, b_u8, "mci_refine")
+        B, H, W, _ = a.shape
+        Hb, Wb = field_shape(H, W)
+        if not torch.is_tensor(field) or field.dtype != torch.int16 or field.device != self.device:
+            raise ValueError("mci_refine: field must be an int16 tensor on %s (mci_field)" % (self.device,))
+        f = (field.unsqueeze(0) if field.dim() == 3 else field).contiguous()
+        if tuple(f.shape) != (B, Hb, Wb, 2):
+            raise ValueError("mci_refine: the field of %d %dx%d segments is [%d, %d, %d, 2], got %s" % (B, H, W, B, Hb, Wb, tuple(field.shape)))
+        with torch.cuda.device(self.device):
+            if out is None:
+                res = torch.empty_like(f)
+            else:
+                res = out.unsqueeze(0) if (torch.is_tensor(out) and out.dim() == 3) else out
+                if not torch.is_tensor(res) or tuple(res.shape) != (B, Hb, Wb, 2) or res.dtype != torch.int16 or not res.is_contiguous() or res.device != self.device:
+                    raise ValueError("mci_refine: out must be a contiguous int16 %s tensor on %s" % ((B, Hb, Wb, 2), self.device))
+            _native.check(self._h, self._lib.rib_halfpel_refine(self._h, B, H, W, _ptr(a), _ptr(b), _ptr(f), _ptr(res), border, self._stream()))
+        return res[0] if single else res
+
+    def mci_frames(self, a_u8, b_u8, field, sample_rate, k_first=1, count=None, normalised=True, out=None, border="clamp", precision="full"):
         """Frames k_first .. k_first + count - 1 (count None: up to sample_rate - 1) of B segments from their key frames and
         block fields, all in one launch (rib_mci_frames; background.mci_frames_host is the definition and is bit-equal):
         a_u8, b_u8 uint8 [B,H,W,3], field int16 [B,Hb,Wb,2] (mci_field) on this device, sample_rate a power of two.
         normalised=True: float32 [T,B,3,H,W], ToTensor + Normalize(0.5, 0.5) as the folder driver's upload computes it;
         False: uint8 [T,B,H,W,3]; "both": the pair (float32, uint8).  [H,W,3] key frames give [T,3,H,W] / [T,H,W,3].
         out: optional contiguous destination (for "both": a pair).  border: "clamp" (the default) or "valid": where exactly
-        one of a pixel's two samples lies inside the frame, that sample alone."""
-        from .background import BORDERS, check_border, field_shape, log2_rate
+        one of a pixel's two samples lies inside the frame, that sample alone.  precision: "full" (the default) or "half": the
+        field is mci_refine's, in half pixels (rib_halfpel_frames)."""
+        from .background import BORDERS, check_border, check_precision, field_shape, log2_rate
         border = BORDERS.index(check_border(border, "mci_frames"))
+        entry = self._lib.rib_halfpel_frames if check_precision(precision, "mci_frames") == "half" else self._lib.rib_mci_frames
         a, b, single = self._mci_pair(a_u8, b_u8, "mci_frames")
         B, H, W, _ = a.shape
         Hb, Wb = field_shape(H, W)
@@ -628,8 +656,7 @@ class Generator:
         with torch.cuda.device(self.device):
             rf = dest(of, fshape, torch.float32) if normalised in (True, "both") else None
             ru = dest(ou, ushape, torch.uint8) if normalised in (False, "both") else None
-            _native.check(self._h, self._lib.rib_mci_frames(self._h, T, B, H, W, _ptr(a), _ptr(b), _ptr(f), s, k_first, border,
-                                                            _ptr(rf), _ptr(ru), self._stream()))
+            _native.check(self._h, entry(self._h, T, B, H, W, _ptr(a), _ptr(b), _ptr(f), s, k_first, border, _ptr(rf), _ptr(ru), self._stream()))
         res = tuple((r[:, 0] if single else r) for r in (rf, ru) if r is not None)
         return res if normalised == "both" else res[0]
 

@@ -38,10 +38,14 @@ and never reads <input>/DAIN.  It is this project's interpolation, not DAIN: the
 quality on real footage has not been measured, and motion beyond +-32 px between key frames falls outside the search.
 `--mci-range 64` or `128` (default 32) widens the search by a fourth and a fifth pyramid level: the field then reaches 78 or 158 px
 of motion between key frames (38 at the default) for six or seven launches per group of segments where the default takes five.
-Still no occlusion reasoning and no sub-pel search, and a wider search has more room for a false match on periodic content.
+Still no occlusion reasoning, and a wider search has more room for a false match on periodic content.
 `--mci-border valid` (default `clamp`) is one-sided at the frame border: a strip that enters or leaves the frame between the two
 key frames is matched on, and taken from, the key frame that shows it, where `clamp` blends it with a smear of the other key
 frame's edge column.  Frame border only: a foreground object that covers background inside the frame is not handled.
+`--mci-precision half` (default `full`): the search is in whole pixels, so the motion between two key frames is always written as
+an even number; one more launch per group (rib_halfpel_refine) refines every block's vector by half a pixel and the frames are sampled
+from that field (rib_halfpel_frames).  Half-pel samples are bilinear and soft; a block whose whole-pixel vector is more than one
+half-pel step from the truth stays wrong; no quarter-pel.
 Frames are then named after their pose files.  The default, `--background dain`, is the reference's contract.
 
 Poses without a Predict_motion folder: `--poses keyframes --pose-dir DIR [--upsample-rate N] [--motion-config PATH]` runs stage 1
@@ -122,8 +126,9 @@ def summary_line(evaluator, rank=0, world=1):
                "reference (zlib 6)" if evaluator.png_compress_level is None else str(evaluator.png_compress_level),
                evaluator.batch or evaluator.default_batch(), "batch-invariant" if evaluator.reproducible else "per-batch",
                getattr(evaluator, "resize_on", "host"),
-               {"dain": "DAIN frames", "mci": "mci (interpolated from the key frames, range %d px, border %s)"
-                       % (getattr(evaluator, "mci_range", 32), getattr(evaluator, "mci_border", "clamp"))}
+               {"dain": "DAIN frames", "mci": "mci (interpolated from the key frames, range %d px, border %s%s)"
+                       % (getattr(evaluator, "mci_range", 32), getattr(evaluator, "mci_border", "clamp"),
+                          ", half-pel" if getattr(evaluator, "mci_precision", "full") == "half" else "")}
                [getattr(evaluator, "background", "dain")]))
     rep = getattr(evaluator, "metrics_report", None)
     if "metrics" in tm and rep is not None:
@@ -167,7 +172,7 @@ def main(opts):
                                              panel_quality=90 if opts.panel_quality is None else opts.panel_quality,
                                              panel_fps=30 if opts.panel_fps is None else opts.panel_fps,
                                              panel_encode=opts.panel_encode or "host", background=opts.background, mci_range=opts.mci_range,
-                                             mci_border=opts.mci_border,
+                                             mci_border=opts.mci_border, mci_precision=opts.mci_precision,
                                              video=opts.video, video_fps=30 if opts.video_fps is None else opts.video_fps,
                                              video_quality=90 if opts.video_quality is None else opts.video_quality,
                                              video_frames=opts.video_frames, frames=opts.frames, **poses_kw)
@@ -236,13 +241,18 @@ def build_parser():
                         help="with --background mci: the motion between two key frames the search covers, 32 (default), 64 or 128 px "
                              "(3, 4 or 5 pyramid levels; the field reaches 38, 78 or 158 px; five, six or seven launches per group of "
                              "segments). Fast pans and passing objects want 64 or 128; a wider search has more room for a false match "
-                             "on periodic content, and there is still no occlusion reasoning and no sub-pel search")
+                             "on periodic content, and there is still no occlusion reasoning; the search is in whole pixels (see --mci-precision)")
     parser.add_argument("--mci-border", default=None,
                         help="with --background mci: what happens where a sample leaves the frame. 'clamp' (default): matching and "
                              "sampling read the edge pixel; 'valid': one-sided at the frame border - a block is matched on the pixels both "
                              "key frames show, a pixel that only one key frame shows is that key frame's sample alone (a hard switch), so a "
                              "strip entering or leaving the frame shows its content, not a smear. Frame border only: no occlusion "
                              "reasoning inside the frame")
+    parser.add_argument("--mci-precision", default=None,
+                        help="with --background mci: the unit of the motion field. 'full' (default): whole pixels, so the motion between "
+                             "two key frames is an even number of pixels; 'half': one more launch per group refines every block's vector "
+                             "by half a pixel (bilinear half-pel samples, soft; a block more than one half-pel step from the truth stays "
+                             "wrong; no quarter-pel)")
     parser.add_argument("--video", action="store_true",
                         help="also write every frame of a clip, key frames included, as <save-dir>/Generated_frames/<clip>_video.avi "
                              "(Motion-JPEG; a frame is the JPEG of exactly the bytes its PNG holds, encoded on the GPU)")
@@ -291,6 +301,11 @@ def parse_args(argv=None):
     if opts.mci_border not in (None, "clamp", "valid"):
         parser.error("--mci-border must be 'clamp' or 'valid', got %r" % (opts.mci_border,))
     opts.mci_border = "clamp" if opts.mci_border is None else opts.mci_border
+    if opts.mci_precision is not None and opts.background != "mci":
+        parser.error("--mci-precision is a setting of --background mci")
+    if opts.mci_precision not in (None, "full", "half"):
+        parser.error("--mci-precision must be 'full' or 'half', got %r" % (opts.mci_precision,))
+    opts.mci_precision = "full" if opts.mci_precision is None else opts.mci_precision
     if opts.background == "mci" and opts.resize_on == "gpu":
         parser.error("--background mci with --resize-on gpu is not supported (there is no DAIN list to plan the GPU resize for)")
     if opts.metrics and opts.gt_dir is None:

@@ -85,6 +85,7 @@ def main():
                     help="'mci': the background frames are interpolated on the GPU from the key frames and the clip's DAIN folder is not read (background=...)")
     ap.add_argument("--mci-range", type=int, default=32, choices=(32, 64, 128), help="with --background mci: the search's range in px between key frames (mci_range=...)")
     ap.add_argument("--mci-border", default="clamp", choices=("clamp", "valid"), help="with --background mci: the border mode (mci_border=...)")
+    ap.add_argument("--mci-precision", default="full", choices=("full", "half"), help="with --background mci: half-pel refinement of the field (mci_precision=...)")
     ap.add_argument("--video", action="store_true", help="also write the frames as <clip>_video.avi, JPEG-encoded on the GPU (video=True)")
     ap.add_argument("--frames", default="png", choices=("png", "none"), help="with --video: 'none' writes no PNG frames (frames=...)")
     ap.add_argument("--poses", default="folder", choices=("folder", "keyframes"),
@@ -98,6 +99,8 @@ def main():
         ap.error("--background mci with --resize-on gpu is not supported")
     if a.mci_range != 32 and a.background != "mci":
         ap.error("--mci-range is a setting of --background mci")
+    if a.mci_precision != "full" and a.background != "mci":
+        ap.error("--mci-precision is a setting of --background mci")
     if a.mci_border != "clamp" and a.background != "mci":
         ap.error("--mci-border is a setting of --background mci")
     if a.panel_encode != "host" and not a.panels:
@@ -140,7 +143,8 @@ def main():
                                          metrics=a.metrics, pose_mask=a.pose_mask, panels=a.panels, panel_encode=a.panel_encode,
                                          background=a.background, video=a.video, frames=a.frames, **kw,
                                          **({"mci_range": a.mci_range} if a.background == "mci" else {}),
-                                         **({"mci_border": a.mci_border} if a.mci_border != "clamp" else {}))
+                                         **({"mci_border": a.mci_border} if a.mci_border != "clamp" else {}),
+                                         **({"mci_precision": a.mci_precision} if a.mci_precision != "full" else {}))
             torch.cuda.synchronize()
             walls.append(time.perf_counter() - t0)
         tm = dict(E.timings)
@@ -152,6 +156,7 @@ def main():
                       "cpus": len(os.sched_getaffinity(0)), "cpu_budget": ev.cpu_budget(), "png_compress_level": a.compress,
                       "src_height": a.src_height or H, "src_width": a.src_width or W, "resize_on": a.resize_on, "background": a.background, "mci_range": a.mci_range if a.background == "mci" else None,
                       "mci_border": a.mci_border if a.background == "mci" else None,
+                      "mci_precision": a.mci_precision if a.background == "mci" else None,
                       "metrics": a.metrics, "pose_mask": a.pose_mask, "metrics_overall": overall, "panels": a.panels, "panel_encode": a.panel_encode,
                       "video": a.video, "frames_written": a.frames, "poses": a.poses, "stage1_plus_bridge_ms_per_clip": stage1_ms,
                       "wall_s": wall, "wall_s_runs": [round(w, 4) for w in walls[1:]], "frames_per_s_end_to_end": n / wall,

@@ -2,11 +2,13 @@
 """The motion-compensated background on its own: rib_mci_field and rib_mci_frames (Generator.mci_field / mci_frames) on one
 unit - B segments of H x W at sample rate s - for a kernel trace.
 
-    rocprofv3 --kernel-trace --stats -d DIR -- python tools/mci_bench.py [--size 512] [--batch 4] [--rate 8] [--reps 20] [--u8] [--levels 3] [--border clamp]
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/mci_bench.py [--size 512] [--batch 4] [--rate 8] [--reps 20] [--u8] [--levels 3] [--border clamp] [--precision full]
 
 --levels 3 (the default), 4 or 5: the pyramid levels of the field's search, the driver's --mci-range 32, 64 or 128; the scene's
 motion between the key frames grows with it (a quarter of that range in x, 3/16 in y).  --border valid: the one-sided border mode
-(the driver's --mci-border; k_mci_search<R, true> and k_mci_frames<true> in the trace).
+(the driver's --mci-border; k_mci_search<R, true> and k_mci_frames<true> in the trace).  --precision half (the driver's
+--mci-precision): the refine launch (rib_halfpel_refine, k_mci_refine in the trace) is timed beside the field, and the frames are
+rib_halfpel_frames's from the refined field (k_mci_frames<.., true>); the default times what it always timed.
 
 Prints one JSON line: the wall time of the field's launches (levels + 2: five by default) and of the frames launch between two events (median of
 --reps, after a warm-up), the frames launch's byte floor (12 bytes of float32 out per pixel and frame, 3 more with --u8, the
@@ -47,6 +49,7 @@ def main():
     ap.add_argument("--u8", action="store_true", help="also write the uint8 NHWC frames (the sheets' DAIN pane)")
     ap.add_argument("--levels", type=int, default=3, choices=(3, 4, 5), help="pyramid levels of the search (--mci-range 32, 64, 128)")
     ap.add_argument("--border", default="clamp", choices=("clamp", "valid"), help="the border mode (--mci-border)")
+    ap.add_argument("--precision", default="full", choices=("full", "half"), help="the field's unit (--mci-precision): half also times the refine launch")
     a = ap.parse_args()
     kw = {} if a.border == "clamp" else {"border": a.border}       # (clamp: the calls of before the mode existed)
     H, W, B, s = a.height or a.size, a.width or a.size, a.batch, a.rate
@@ -58,17 +61,25 @@ def main():
     big = (big + torch.rand(B, 3, H + 2 * m, W + 2 * m, device="cuda", generator=g) * 24).clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1)
     ka, kb = big[:, m:m + H, m:m + W].contiguous(), big[:, m - 3 * m // 8:m - 3 * m // 8 + H, m + m // 2:m + m // 2 + W].contiguous()
     field = G.mci_field(ka, kb, a.levels, **kw)
+    half, fkw, extra = a.precision == "half", dict(kw), {}
+    if half:
+        whole = field
+        field = G.mci_refine(ka, kb, whole, **kw)
+        fkw["precision"] = "half"
+        nms = timed(lambda: G.mci_refine(ka, kb, whole, **kw), a.reps)
+        extra = {"refine_event_us_median": round(nms[len(nms) // 2] * 1e3, 2), "refine_event_us_min": round(nms[0] * 1e3, 2),
+                 "refined_odd_fraction": round(float(((field & 1) != 0).any(-1).float().mean()), 3)}
     T = s - 1
     f32 = torch.empty(T, B, 3, H, W, dtype=torch.float32, device="cuda")
     u8 = torch.empty(T, B, H, W, 3, dtype=torch.uint8, device="cuda") if a.u8 else None
     fms = timed(lambda: G.mci_field(ka, kb, a.levels, **kw), a.reps)
-    rms = timed(lambda: G.mci_frames(ka, kb, field, s, normalised="both" if a.u8 else True, out=(f32, u8) if a.u8 else f32, **kw), a.reps)
+    rms = timed(lambda: G.mci_frames(ka, kb, field, s, normalised="both" if a.u8 else True, out=(f32, u8) if a.u8 else f32, **fkw), a.reps)
     floor = (12 + (3 if a.u8 else 0)) * H * W * T * B + 2 * 3 * H * W * B
-    print(json.dumps({"height": H, "width": W, "batch": B, "rate": s, "levels": a.levels, "border": a.border, "frames": T * B, "u8": a.u8,
+    print(json.dumps({"height": H, "width": W, "batch": B, "rate": s, "levels": a.levels, "border": a.border, "precision": a.precision, "frames": T * B, "u8": a.u8,
                       "field_event_us_median": round(fms[len(fms) // 2] * 1e3, 2), "field_event_us_min": round(fms[0] * 1e3, 2),
                       "frames_event_us_median": round(rms[len(rms) // 2] * 1e3, 2), "frames_event_us_min": round(rms[0] * 1e3, 2),
                       "frames_floor_bytes": floor, "frames_floor_us_at_6.3TB/s": round(floor / 6.3e12 * 1e6, 2),
-                      "field_nonzero_fraction": round(float((field != 0).float().mean()), 3), "field_max_abs": int(field.abs().max())}))
+                      "field_nonzero_fraction": round(float((field != 0).float().mean()), 3), "field_max_abs": int(field.abs().max()), **extra}))
 
 
 if __name__ == "__main__":
