@@ -416,6 +416,14 @@ int rib_graph_stats(rib_handle* h, int64_t* captures, int64_t* replays);
 int rib_set_plan_batch(rib_handle* h, int n);
 int rib_get_plan_batch(const rib_handle* h);
 
+/* ---- staged Winograd input transforms (no reference counterpart).  On (the default) the `.wino_in` launches of the fp32
+ * plans stage each workgroup's input patch in LDS, so that every element is fetched and modulated once instead of once per
+ * (tile, row) unit that reads it; off runs the unstaged kernels.  Both sides write the same bits everywhere and have the
+ * same launch list and workspace; only the grids of the `.wino_in` launches differ (A/B measurements, GPU test).
+ * RIB_WINO_IN_UNSTAGED=1 in the environment at rib_create starts a handle with it off.  Changing it drops the cached
+ * plans and the captured chain graphs, as the other setters do. ---- */
+int rib_set_wino_in_staging(rib_handle* h, int on);
+
 /* ---- build identity (no reference counterpart: the reference is interpreted Python).  A static string
  *   "librib stamp=<lib> shards=<s0>,...,<s23> consistent=<0|1> variants=<n> frame=<f> compiler=<...>"
  * where <lib> is the content hash (csrc/build.py: sha256 over rib.hip, kernels.hip.h, rib_host.h, pixel_ops.hip.h, igemm.hip.h,

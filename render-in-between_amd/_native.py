@@ -99,6 +99,7 @@ SIGNATURES = {
     "rib_graph_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "rib_set_plan_batch": (C.c_int, [C.c_void_p, C.c_int]),
     "rib_get_plan_batch": (C.c_int, [C.c_void_p]),
+    "rib_set_wino_in_staging": (C.c_int, [C.c_void_p, C.c_int]),
 }
 
 

@@ -429,6 +429,7 @@ struct WinoInParams {
   StatSrc st;                                // consumer-side finalize: replaces pro_scale / pro_shift when st.part != nullptr
   float* v; int tilesY, tilesX;
   int nslices, ublocks;                      // grid.x = ublocks * nslices (channel slices of 64)
+  int sty, stx;                              // k_wino_in_staged: tiles of a workgroup's block (ublocks = number of blocks); else 0
   // WSRC_SPADE: the input is the output of an unfused SPADE that is never stored (round 3): x is the tensor being
   // normalised (at half resolution when x_ups), (scale, shift) its InstanceNorm, gamma/beta come from the condition level's
   // slab (k_spade_modulate's arithmetic, spade_mod1), then LeakyReLU when pro_lrelu
@@ -544,6 +545,16 @@ __device__ __forceinline__ float4 wino_value(const WinoInParams& p, const WinoCo
 #define RIB_F4_SUB(a, b) make_float4((a).x - (b).x, (a).y - (b).y, (a).z - (b).z, (a).w - (b).w)
 #define RIB_F4_ADD(a, b) make_float4((a).x + (b).x, (a).y + (b).y, (a).z + (b).z, (a).w + (b).w)
 
+// row r of V = (B^T d) B from row r of B^T d (t[0..3]), one store per position; vb: this tile's and these four channels' element
+// of position 0.  SC: columns 1, 2 only
+template <bool SC>
+__device__ __forceinline__ void wino_store_row(float* vb, size_t plane, int r, const float4 (&t)[4]) {
+  if constexpr (!SC) *reinterpret_cast<float4*>(vb + (size_t)(r * 4 + 0) * plane) = RIB_F4_SUB(t[0], t[2]);
+  *reinterpret_cast<float4*>(vb + (size_t)(r * 4 + 1) * plane) = RIB_F4_ADD(t[1], t[2]);
+  *reinterpret_cast<float4*>(vb + (size_t)(r * 4 + 2) * plane) = RIB_F4_SUB(t[2], t[1]);
+  if constexpr (!SC) *reinterpret_cast<float4*>(vb + (size_t)(r * 4 + 3) * plane) = RIB_F4_SUB(t[1], t[3]);
+}
+
 // SC: the source of the 1x1 shortcut - rows and columns 1, 2 of the transformed tile only
 template <int MODE, bool SC>
 __device__ __forceinline__ void wino_in_slice(const WinoInParams& p, int slice, int ub, double* red, float* s_sc, float* s_sh) {
@@ -589,11 +600,7 @@ __device__ __forceinline__ void wino_in_slice(const WinoInParams& p, int slice, 
       t[q] = make_float4(v[0].x + sg * v[1].x, v[0].y + sg * v[1].y, v[0].z + sg * v[1].z, v[0].w + sg * v[1].w);
     }
     const size_t plane = (size_t)ntiles * p.ldv;              // one position's [tiles][ldv] matrix
-    float* vb = p.v + (size_t)n * 16 * plane + (size_t)tile * p.ldv + c4 * 4;
-    if constexpr (!SC) *reinterpret_cast<float4*>(vb + (size_t)(r * 4 + 0) * plane) = RIB_F4_SUB(t[0], t[2]);
-    *reinterpret_cast<float4*>(vb + (size_t)(r * 4 + 1) * plane) = RIB_F4_ADD(t[1], t[2]);
-    *reinterpret_cast<float4*>(vb + (size_t)(r * 4 + 2) * plane) = RIB_F4_SUB(t[2], t[1]);
-    if constexpr (!SC) *reinterpret_cast<float4*>(vb + (size_t)(r * 4 + 3) * plane) = RIB_F4_SUB(t[1], t[3]);
+    wino_store_row<SC>(p.v + (size_t)n * 16 * plane + (size_t)tile * p.ldv + c4 * 4, plane, r, t);
   }
 }
 
@@ -722,6 +729,24 @@ __device__ __forceinline__ float4 f4_fma(float a, float4 x, float4 acc) {
 }
 __device__ __forceinline__ float4 f4_scale(float a, float4 x) { return make_float4(a * x.x, a * x.y, a * x.z, a * x.w); }
 
+// row r of V = (B^T d) B from row r of B^T d (t[0..5]): V[r][j] = sum_q B^T[j][q] t[q] (compile-time coefficients), one store per
+// position; vb: this tile's and these four channels' element of position 0.  SC: columns 1..4 only
+template <bool SC>
+__device__ __forceinline__ void wino4_store_row(float* vb, size_t plane, int r, const float4 (&t)[6]) {
+  const float4 ev1 = f4_fma(-9.f / 4, t[2], t[4]), od1 = f4_fma(-27.f / 16, t[1], f4_scale(3.f / 4, t[3]));
+  const float4 ev2 = f4_fma(-9.f / 16, t[2], t[4]), od2 = f4_fma(-27.f / 32, t[1], f4_scale(3.f / 2, t[3]));
+  if constexpr (!SC) {
+    const float4 e24 = f4_fma(-45.f / 16, t[2], t[4]);               // -45/16 t2 + t4
+    const float4 o13 = f4_fma(-45.f / 16, t[3], t[5]);               // -45/16 t3 + t5
+    *reinterpret_cast<float4*>(vb + (size_t)(r * 6 + 0) * plane) = f4_fma(81.f / 64, t[0], e24);
+    *reinterpret_cast<float4*>(vb + (size_t)(r * 6 + 5) * plane) = f4_fma(81.f / 64, t[1], o13);
+  }
+  *reinterpret_cast<float4*>(vb + (size_t)(r * 6 + 1) * plane) = RIB_F4_ADD(ev1, od1);
+  *reinterpret_cast<float4*>(vb + (size_t)(r * 6 + 2) * plane) = RIB_F4_SUB(ev1, od1);
+  *reinterpret_cast<float4*>(vb + (size_t)(r * 6 + 3) * plane) = RIB_F4_ADD(ev2, od2);
+  *reinterpret_cast<float4*>(vb + (size_t)(r * 6 + 4) * plane) = RIB_F4_SUB(ev2, od2);
+}
+
 // thread = ((tile, transformed row r), 4 channels of the slice); row r of B^T d needs the 3 or 4 input rows with a non-zero coefficient
 // SC: the source of the 1x1 shortcut - rows and columns 1..4 of the transformed tile only
 template <int MODE, bool SC>
@@ -790,20 +815,7 @@ __device__ __forceinline__ void wino4_in_slice(const WinoInParams& p, int slice,
       }
     }
     const size_t plane = (size_t)ntiles * p.ldv;
-    float* vb = p.v + (size_t)n * 36 * plane + (size_t)tile * p.ldv + c4 * 4;
-    // columns: V[r][j] = sum_q B^T[j][q] t[q] (compile-time coefficients)
-    const float4 ev1 = f4_fma(-9.f / 4, t[2], t[4]), od1 = f4_fma(-27.f / 16, t[1], f4_scale(3.f / 4, t[3]));
-    const float4 ev2 = f4_fma(-9.f / 16, t[2], t[4]), od2 = f4_fma(-27.f / 32, t[1], f4_scale(3.f / 2, t[3]));
-    if constexpr (!SC) {
-      const float4 e24 = f4_fma(-45.f / 16, t[2], t[4]);               // -45/16 t2 + t4
-      const float4 o13 = f4_fma(-45.f / 16, t[3], t[5]);               // -45/16 t3 + t5
-      *reinterpret_cast<float4*>(vb + (size_t)(r * 6 + 0) * plane) = f4_fma(81.f / 64, t[0], e24);
-      *reinterpret_cast<float4*>(vb + (size_t)(r * 6 + 5) * plane) = f4_fma(81.f / 64, t[1], o13);
-    }
-    *reinterpret_cast<float4*>(vb + (size_t)(r * 6 + 1) * plane) = RIB_F4_ADD(ev1, od1);
-    *reinterpret_cast<float4*>(vb + (size_t)(r * 6 + 2) * plane) = RIB_F4_SUB(ev1, od1);
-    *reinterpret_cast<float4*>(vb + (size_t)(r * 6 + 3) * plane) = RIB_F4_ADD(ev2, od2);
-    *reinterpret_cast<float4*>(vb + (size_t)(r * 6 + 4) * plane) = RIB_F4_SUB(ev2, od2);
+    wino4_store_row<SC>(p.v + (size_t)n * 36 * plane + (size_t)tile * p.ldv + c4 * 4, plane, r, t);
   }
 }
 
@@ -817,6 +829,120 @@ __global__ __launch_bounds__(256) void k_wino4_in(const WinoInParams p) {
     if (slice >= n1) { wino4_in_slice<MODE2, true>(wino_second(p), slice - n1, ub, red, s_sc, s_sh); return; }
   }
   wino4_in_slice<MODE, false>(p, slice, ub, red, s_sc, s_sh);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Staged input transforms (round 10): every input element fetched and modulated ONCE per workgroup.  In k_wino_in / k_wino4_in
+// a unit (tile, row r) fetches its own input rows: a pixel lies in 4 (2.25) overlapping tiles and in 2 (3-4) of a tile's
+// rows, so every element - in WSRC_SPADE three 16-byte loads and spade_mod1 - is fetched and computed about 8 times.  Here a
+// workgroup owns a channel slice and a BLOCK of p.sty x p.stx whole tiles (blockIdx.x = tile block * nslices + slice):
+//   1. thread (pixel slot = tid / 16, 4 channels = tid % 16) issues wino_fetch for its <= 7 pixels of the block's patch
+//      ((M sty + 2) x (M stx + 2) pixels, halo included, coordinates clamped as in the unstaged kernels);
+//   2. the workgroup reduces its statistics partials (wino_in_consts / block_stats_64) while those loads are in flight;
+//   3. wino_value once per element, zero for an element outside the image, the value to the LDS patch [pixel][64 channels];
+//      WSRC_JOIN: the block's own pixels (not the halo) also go to p.o - every pixel of the image lies in exactly one tile,
+//      hence in exactly one block;
+//   4. one barrier;
+//   5. the units (tile, row r) of the block read their rows from the patch (16 lanes x 16 contiguous bytes per pixel: any 16
+//      lanes of a 128-bit LDS read cover the 64 banks once) and run the arithmetic of the unstaged kernels in the same order:
+//      V is bit-identical, and so is p.o.
+// A second source (the 1x1 shortcut's input: own pixels only, 2x row redundancy) keeps the unstaged code; its workgroups
+// stride over the units by the number of tile blocks.  Threads of channels beyond Cin take part in every barrier and skip
+// loads and stores.  The patch is sized for the largest block (10 x 10 pixels: 4x4 tiles of F(2x2), 2x2 tiles of F(4x4)).
+// ---------------------------------------------------------------------------------------------
+constexpr int WINO_STAGE_MAX_PX = 100;
+constexpr int WINO_STAGE_LDS_BYTES = WINO_STAGE_MAX_PX * 64 * 4 + 4 * 64 * 2 * 8 + 2 * 64 * 4;      // patch + red + s_sc / s_sh
+
+template <int M, int MODE>
+__device__ __forceinline__ void wino_in_staged_slice(const WinoInParams& p, int slice, int blk, float4* patch, double* red, float* s_sc,
+                                                     float* s_sh) {
+  constexpr int NR = M + 2, NF = (WINO_STAGE_MAX_PX + 15) / 16;
+  const int n = blockIdx.y;
+  const int lane = threadIdx.x & 15, slot = threadIdx.x >> 4;
+  const int c4 = slice * 16 + lane;
+  const bool cok = c4 < p.Cin / 4;
+  const int nbx = (p.tilesX + p.stx - 1) / p.stx;
+  const int ty0 = (blk / nbx) * p.sty, tx0 = (blk % nbx) * p.stx;          // the block's first tile
+  const int ph = M * p.sty + 2, pw = M * p.stx + 2, npix = ph * pw;        // the patch; its origin is the first tile's
+  const int y0 = M * ty0 - 1, x0 = M * tx0 - 1;
+  WinoRaw<MODE> d[NF];
+#pragma unroll
+  for (int i = 0; i < NF; ++i) {
+    const int pi = i * 16 + slot;
+    if (cok && pi < npix) wino_fetch<MODE>(p, n, min(max(y0 + pi / pw, 0), p.H - 1), min(max(x0 + pi % pw, 0), p.W - 1), c4, d[i]);
+  }
+  WinoConsts<MODE> kc;
+  wino_in_consts<MODE>(p, n, slice, c4, cok, red, s_sc, s_sh, kc);
+#pragma unroll
+  for (int i = 0; i < NF; ++i) {
+    const int pi = i * 16 + slot;
+    if (cok && pi < npix) {
+      const int py = pi / pw, px = pi % pw, iy = y0 + py, ix = x0 + px;
+      const bool inb = iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
+      float4 w = wino_value<MODE>(p, kc, d[i]);
+      if constexpr (MODE == WSRC_JOIN) {
+        if (inb && py >= 1 && py < ph - 1 && px >= 1 && px < pw - 1) *reinterpret_cast<float4*>(p.o + (((size_t)n * p.H + iy) * p.W + ix) * p.xC + c4 * 4) = w;
+      }
+      if (!inb) w = make_float4(0.f, 0.f, 0.f, 0.f);   // zero padding after the prologue
+      patch[pi * 16 + lane] = w;
+    }
+  }
+  __syncthreads();
+  if (!cok) return;      // (behind the last barrier)
+  const int ntiles = p.tilesY * p.tilesX;
+  const size_t plane = (size_t)ntiles * p.ldv;
+  for (int u = slot; u < p.sty * p.stx * NR; u += 16) {
+    const int r = u % NR, tl = u / NR, tyl = tl / p.stx, txl = tl % p.stx;
+    const int ty = ty0 + tyl, tx = tx0 + txl;
+    if (ty >= p.tilesY || tx >= p.tilesX) continue;
+    const float4* d0 = patch + ((M * tyl) * pw + M * txl) * 16 + lane;      // element (a, q) of the tile: d0[(a * pw + q) * 16]
+    float* vb = p.v + (size_t)n * (NR * NR) * plane + (size_t)(ty * p.tilesX + tx) * p.ldv + c4 * 4;
+    if constexpr (M == 2) {
+      const int ia = r == 0 ? 0 : (r == 2 ? 2 : 1), ib = r == 0 ? 2 : (r == 1 ? 2 : (r == 2 ? 1 : 3));      // as wino_in_slice
+      const float sg = r == 1 ? 1.f : -1.f;
+      float4 t[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float4 v0 = d0[(ia * pw + q) * 16], v1 = d0[(ib * pw + q) * 16];
+        t[q] = make_float4(v0.x + sg * v1.x, v0.y + sg * v1.y, v0.z + sg * v1.z, v0.w + sg * v1.w);
+      }
+      wino_store_row<false>(vb, plane, r, t);
+    } else {
+      const int a0 = r == 0 ? 0 : 1, da = (r == 0 || r == 5) ? 2 : 1, na = (r == 0 || r == 5) ? 3 : 4;      // as wino4_in_slice
+      float4 t[6];
+#pragma unroll
+      for (int q = 0; q < 6; ++q) t[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+      // WSRC_PLAIN keeps the unstaged kernel's fourth step of a three-row unit (coefficient 0 on the last row again): it is
+      // not a no-op on the bits (-0 + 0 * w = +0)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (MODE != WSRC_PLAIN && k >= na) break;
+        const int a = a0 + min(k, na - 1) * da;
+        const float coef = k < na ? kWino4BT[r][a] : 0.f;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) t[q] = f4_fma(coef, d0[(a * pw + q) * 16], t[q]);
+      }
+      wino4_store_row<false>(vb, plane, r, t);
+    }
+  }
+}
+
+template <int M, int MODE, int MODE2 = -1>
+__global__ __launch_bounds__(256) void k_wino_in_staged(const WinoInParams p) {
+  __shared__ float4 patch[WINO_STAGE_MAX_PX * 16];
+  __shared__ double red[4 * 64 * 2];
+  __shared__ float s_sc[64], s_sh[64];
+  static_assert(sizeof(patch) + sizeof(red) + sizeof(s_sc) + sizeof(s_sh) == WINO_STAGE_LDS_BYTES, "the planner's figure");
+  const int slice = blockIdx.x % p.nslices, blk = blockIdx.x / p.nslices;      // p.ublocks = tile blocks
+  if constexpr (MODE2 >= 0) {
+    const int n1 = p.nslices - p.nslices2;
+    if (slice >= n1) {
+      if constexpr (M == 4) wino4_in_slice<MODE2, true>(wino_second(p), slice - n1, blk, red, s_sc, s_sh);
+      else wino_in_slice<MODE2, true>(wino_second(p), slice - n1, blk, red, s_sc, s_sh);
+      return;
+    }
+  }
+  wino_in_staged_slice<M, MODE>(p, slice, blk, patch, red, s_sc, s_sh);
 }
 
 // grid (ublocks * nslices, B); thread = ((tile, output row r of the 4x4 tile), 4 channels of the slice)

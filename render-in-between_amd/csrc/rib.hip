@@ -513,6 +513,7 @@ struct Op {
   int wino_m = 0;      // 2 or 4 on the three launches of a Winograd convolution
   int wi_mode = 0;     // k_wino_in: WSRC_PLAIN / WSRC_SPADE / WSRC_JOIN
   int wi_mode2 = -1;   // k_wino_in with a second source (the 1x1 shortcut's input): WSRC_PLAIN / WSRC_SPADE; -1: none
+  bool wi_staged = false;   // k_wino_in_staged (WinoInParams::sty x stx tiles per workgroup) instead of k_wino_in / k_wino4_in
   int lowc_ce = 0, lowc_ncol = 0, lowc_tw = 32;
   OpParams params;
   struct Binding { PRef ref; unsigned field = 0; };      // field: byte offset of the pointer inside `params`
@@ -640,6 +641,10 @@ struct rib_handle : rib::FrameState {     // device, err, label_nc and the frame
   bool mc16() const { return prec_mode != PREC_F32; }                    // the matrix-core kernels read 16-bit filter copies, 16-channel steps
   int padc(int c) const { return mc16() ? pad16(c) : pad8(c); }          // channel padding of an activation
   int esz() const { return mc16() ? 2 : 4; }                       // bytes per stored activation element
+  // rib_set_wino_in_staging: the Winograd input transforms stage each input patch in LDS once (k_wino_in_staged); off = every
+  // unit fetches its own rows (k_wino_in / k_wino4_in).  Same V and the same launch list either way; RIB_WINO_IN_UNSTAGED=1
+  // in the environment of rib_create starts a handle with it off
+  bool wino_in_staging = true;
   bool keep_taps = false;      // rib_set_debug_taps: intermediate activations stay intact until the end of a forward
   // rib_set_plan_batch: > 0 = every launch plan, whatever its batch, follows the kernel choices (tuned table / cost model, split-K,
   // Winograd tile, fused or level-wise SPADE) of THIS batch size, so that a sample's arithmetic does not depend on how many other
@@ -810,6 +815,24 @@ template <int CE, int NCOL> static void launch_lowc_t(int tw, dim3 grid, hipStre
   if (tw == 16) RIB_KLAUNCH((k_conv_lowc<CE, NCOL, ST_F32, 16>), grid, dim3(256), 0, st, p);
   else RIB_KLAUNCH((k_conv_lowc<CE, NCOL, ST_F32, 32>), grid, dim3(256), 0, st, p);
 }
+// the Winograd input transform of tile M: staged (k_wino_in_staged) or not, by source mode and second-source mode
+template <int M, bool STAGED, int MODE, int MODE2 = -1> static void launch_wino_in_t(dim3 grid, hipStream_t st, const WinoInParams& p) {
+  if constexpr (STAGED) RIB_KLAUNCH((k_wino_in_staged<M, MODE, MODE2>), grid, dim3(256), 0, st, p);
+  else if constexpr (M == 4) RIB_KLAUNCH((k_wino4_in<MODE, MODE2>), grid, dim3(256), 0, st, p);
+  else RIB_KLAUNCH((k_wino_in<MODE, MODE2>), grid, dim3(256), 0, st, p);
+}
+template <int M, bool STAGED> static void launch_wino_in(const Op& op, hipStream_t st, const WinoInParams& p) {
+  if (op.wi_mode2 >= 0) {      // with the shortcut's input as a second source
+    const bool s1 = op.wi_mode == WSRC_SPADE, s2 = op.wi_mode2 == WSRC_SPADE;
+    if (s1 && s2) launch_wino_in_t<M, STAGED, WSRC_SPADE, WSRC_SPADE>(op.grid, st, p);
+    else if (s1) launch_wino_in_t<M, STAGED, WSRC_SPADE, WSRC_PLAIN>(op.grid, st, p);
+    else if (s2) launch_wino_in_t<M, STAGED, WSRC_PLAIN, WSRC_SPADE>(op.grid, st, p);
+    else launch_wino_in_t<M, STAGED, WSRC_PLAIN, WSRC_PLAIN>(op.grid, st, p);
+  } else if (op.wi_mode == WSRC_SPADE) launch_wino_in_t<M, STAGED, WSRC_SPADE>(op.grid, st, p);
+  else if (op.wi_mode == WSRC_JOIN) launch_wino_in_t<M, STAGED, WSRC_JOIN>(op.grid, st, p);
+  else launch_wino_in_t<M, STAGED, WSRC_PLAIN>(op.grid, st, p);
+}
+
 static void launch_lowc(int ce, int ncol, int tw, dim3 grid, hipStream_t st, const LowcParams& p) {
   if (ce == 6 && ncol == 64) launch_lowc_t<6, 64>(tw, grid, st, p);
   else if (ce == 10 && ncol == 32) launch_lowc_t<10, 32>(tw, grid, st, p);
@@ -1442,6 +1465,24 @@ struct Builder {
       const int nsl = (c.cinp + 63) / 64 + wi.nslices2, units = ntiles * (wm + 2);
       // (every workgroup that reduces partials re-reads tiles x 64 channels x 16 bytes: few, fatter workgroups then)
       wi.nslices = nsl; wi.ublocks = std::max(1, std::min((units + 15) / 16, (wi.st.tiles > 0 ? 512 : 4096) / nsl));
+      // Staged (k_wino_in_staged): workgroup = (block of sty x stx whole tiles, patch in LDS) x (slice of 64 channels).  The
+      // largest block of the list wins whose grid still has a workgroup per CU, or as many as the unstaged grid where that
+      // one has fewer (a fatter block fetches fewer halo pixels twice: 100 / 64 for 10 x 10 against 36 / 16 for 6 x 6).
+      // The launch stays unstaged when (a) the staged kernel's static LDS would leave fewer than 2 workgroups per CU - it is
+      // sized for the largest patch of the list, so this holds for every block or for none - or (b) no block of the list
+      // keeps the grid at that bar.  Every class (tile x first source) of the 512x512 frame is faster staged
+      // (profiles/r10_wino_in_staged.txt), so none is excluded here.
+      if (h->wino_in_staging) {
+        static const int kBlocks2[][2] = {{4, 4}, {2, 4}, {2, 2}}, kBlocks4[][2] = {{2, 2}, {1, 2}, {1, 1}};
+        const int need = std::min((int)(wi.ublocks * nsl * B), 256 /* CUs */);
+        const bool fits = 2 * WINO_STAGE_LDS_BYTES <= 160 * 1024 /* LDS of a CU */;
+        for (int i = 0; i < 3 && fits && !op.wi_staged; ++i) {
+          const int sty = std::min((wm == 4 ? kBlocks4 : kBlocks2)[i][0], tilesY), stx = std::min((wm == 4 ? kBlocks4 : kBlocks2)[i][1], tilesX);
+          const int nblocks = ((tilesY + sty - 1) / sty) * ((tilesX + stx - 1) / stx);
+          if ((wm * sty + 2) * (wm * stx + 2) > WINO_STAGE_MAX_PX || nblocks * nsl * B < need) continue;
+          op.wi_staged = true; wi.sty = sty; wi.stx = stx; wi.ublocks = nblocks;
+        }
+      }
       op.grid = dim3(wi.ublocks * nsl, B, 1);
       push(op);
     }
@@ -2311,27 +2352,10 @@ int run_plan(rib_handle* h, Plan* P, const Resolver& R, hipStream_t st, bool ski
       case OP_SPLITEPI: RIB_LAUNCH_ST(bf16, k_splitk_epilogue, op.grid, dim3(256), 0, st, std::get<SplitEpiParams>(params)); break;
       case OP_POOL: RIB_LAUNCH_ST(bf16, k_avgpool, op.grid, dim3(256), 0, st, std::get<PoolParams>(params)); break;
       case OP_INADD: RIB_LAUNCH_ST(bf16, k_in_add, op.grid, dim3(256), 0, st, std::get<InAddParams>(params)); break;
-      case OP_WINO_IN: {
-        const WinoInParams& p = std::get<WinoInParams>(params);
-        if (op.wi_mode2 >= 0) {      // with the shortcut's input as a second source
-          const bool s1 = op.wi_mode == WSRC_SPADE, s2 = op.wi_mode2 == WSRC_SPADE;
-#define RIB_WINO_IN2(K)                                                                                     \
-          if (s1 && s2) RIB_KLAUNCH((K<WSRC_SPADE, WSRC_SPADE>), op.grid, dim3(256), 0, st, p);             \
-          else if (s1) RIB_KLAUNCH((K<WSRC_SPADE, WSRC_PLAIN>), op.grid, dim3(256), 0, st, p);              \
-          else if (s2) RIB_KLAUNCH((K<WSRC_PLAIN, WSRC_SPADE>), op.grid, dim3(256), 0, st, p);              \
-          else RIB_KLAUNCH((K<WSRC_PLAIN, WSRC_PLAIN>), op.grid, dim3(256), 0, st, p)
-          if (op.wino_m == 4) { RIB_WINO_IN2(k_wino4_in); } else { RIB_WINO_IN2(k_wino_in); }
-#undef RIB_WINO_IN2
-        } else if (op.wino_m == 4) {
-          if (op.wi_mode == WSRC_SPADE) RIB_KLAUNCH(k_wino4_in<WSRC_SPADE>, op.grid, dim3(256), 0, st, p);
-          else if (op.wi_mode == WSRC_JOIN) RIB_KLAUNCH(k_wino4_in<WSRC_JOIN>, op.grid, dim3(256), 0, st, p);
-          else RIB_KLAUNCH(k_wino4_in<WSRC_PLAIN>, op.grid, dim3(256), 0, st, p);
-        } else {
-          if (op.wi_mode == WSRC_SPADE) RIB_KLAUNCH(k_wino_in<WSRC_SPADE>, op.grid, dim3(256), 0, st, p);
-          else if (op.wi_mode == WSRC_JOIN) RIB_KLAUNCH(k_wino_in<WSRC_JOIN>, op.grid, dim3(256), 0, st, p);
-          else RIB_KLAUNCH(k_wino_in<WSRC_PLAIN>, op.grid, dim3(256), 0, st, p);
-        }
-      } break;
+      case OP_WINO_IN:
+        if (op.wino_m == 4) { if (op.wi_staged) launch_wino_in<4, true>(op, st, std::get<WinoInParams>(params)); else launch_wino_in<4, false>(op, st, std::get<WinoInParams>(params)); }
+        else { if (op.wi_staged) launch_wino_in<2, true>(op, st, std::get<WinoInParams>(params)); else launch_wino_in<2, false>(op, st, std::get<WinoInParams>(params)); }
+        break;
       case OP_WINO_OUT:
         if (op.wino_m == 4) RIB_KLAUNCH(k_wino4_out, op.grid, dim3(256), 0, st, std::get<WinoOutParams>(params));
         else RIB_KLAUNCH(k_wino_out, op.grid, dim3(256), 0, st, std::get<WinoOutParams>(params));
@@ -2376,6 +2400,7 @@ int rib_create(const rib_config* cfg, int device, rib_handle** out) {
   std::unique_ptr<rib_handle> h(new rib_handle());
   h->g.c = c; h->device = device; h->label_nc = c.label_nc;
   h->graph_replay = getenv("RIB_GRAPH") != nullptr && atoi(getenv("RIB_GRAPH")) != 0;
+  h->wino_in_staging = !(getenv("RIB_WINO_IN_UNSTAGED") != nullptr && atoi(getenv("RIB_WINO_IN_UNSTAGED")) != 0);
   for (int i = 0; i <= c.emb_down; ++i) {
     if (h->g.cond_ch(i) != h->g.emb_ch(i)) return bad("embed/generator max_num_filters disagree on the cond map width");
     if (h->g.emb_ch(i) % 32 != 0) return bad(fmt("embed width %d at level %d is not a multiple of 32", h->g.emb_ch(i), i));
@@ -2885,6 +2910,13 @@ int rib_set_debug_taps(rib_handle* h, int enable) {
   return RIB_OK;
 }
 
+int rib_set_wino_in_staging(rib_handle* h, int on) {
+  if (!h) return RIB_ERR_INVALID;
+  if (h->wino_in_staging != (on != 0)) { h->plans.clear(); drop_chain_graphs(h); }   // the grids of the .wino_in launches depend on it
+  h->wino_in_staging = on != 0;
+  return RIB_OK;
+}
+
 int rib_num_taps(rib_handle* h, int B, int H, int W) {
   if (!h) return RIB_ERR_INVALID;
   Plan* P = get_plan(h, B, H, W);
@@ -2976,6 +3008,9 @@ static int launch_info_head(const Op& op, char* buf, size_t buflen) {
   else if (op.kind() == OP_LOWC)
     snprintf(buf, buflen, "%s|%d|%u,%u,%u|lowc (caller's NCHW tensors, K = 9 x %d real channels) 8x%d tile, %d columns|%.0f", op.name.c_str(), op.kclass,
              op.grid.x, op.grid.y, op.grid.z, op.lowc_ce, op.lowc_tw, op.lowc_ncol, op.flops);
+  else if (op.kind() == OP_WINO_IN && op.wi_staged)
+    snprintf(buf, buflen, "%s|%d|%u,%u,%u|staged, %dx%d tiles per workgroup|0", op.name.c_str(), op.kclass, op.grid.x, op.grid.y, op.grid.z,
+             op.as<WinoInParams>().sty, op.as<WinoInParams>().stx);
   else
     snprintf(buf, buflen, "%s|%d|%u,%u,%u||0", op.name.c_str(), op.kclass, op.grid.x, op.grid.y, op.grid.z);
   return RIB_OK;

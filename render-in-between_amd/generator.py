@@ -340,6 +340,12 @@ class Generator:
                 _ptr(fuses), _ptr(ws), ws.numel(), self._stream()))
         return imgs, masks, fuses
 
+    def set_wino_in_staging(self, on=True):
+        """Staged Winograd input transforms (rib_set_wino_in_staging, include/rib.h): on by default; off runs the unstaged
+        kernels, which write the same bits.  Rebuilds the launch plans; the workspace a shape needs stays the same."""
+        _native.check(self._h, self._lib.rib_set_wino_in_staging(self._h, 1 if on else 0))
+        return self
+
     def set_graph_replay(self, on=True):
         """rib_chain as ONE HIP graph launch per (shape, tensors): see include/rib.h.  Also on with RIB_GRAPH=1."""
         _native.check(self._h, self._lib.rib_set_graph_replay(self._h, 1 if on else 0))
