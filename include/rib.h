@@ -184,6 +184,25 @@ int rib_quality(rib_handle* h, int B, int C, int H, int W, const float* pred, co
 int rib_resize_cubic(rib_handle* h, int N, int H0, int W0, int H, int W, const uint8_t* src_u8_nhwc,
                         const int32_t* ix, const int32_t* cx, const int32_t* iy, const int32_t* cy,
                         uint8_t* out_u8_nhwc, float* out_f32_nchw, void* hip_stream);
+/* ---- the frame at the source resolution (this project's addition: the reference writes its frames at the model size) ----
+ * The fuse of N frames at the SOURCE size H0 x W0, from the model-size prediction and blend mask and the source-size
+ * background: pred fp32 NCHW [N,3,H,W] in [-1,1], mask fp32 [N,1,H,W] in [0,1] (finite, as for rib_quantise), bg uint8 NHWC
+ * [N,H0,W0,3] -> out uint8 NHWC [N,H0,W0,3].  composite.py (composite_host) states the result in integers and the kernel is
+ * bit-equal to it: P = uint8(clip(pred*0.5+0.5, 0, 1)*255) (rib_quantise's arithmetic), M = uint8(clip(mask, 0, 1)*255), both
+ * in double and truncating; Pu, Mu = rib_resize_cubic's resize of P and M from H x W to H0 x W0 (a mask overshoot saturates);
+ * out = (Pu*Mu + bg*(255 - Mu) + 127) / 255 in int32 per channel.  M = 0 keeps the background's bytes, M = 255 gives Pu.
+ * ix, cx [W0,4] and iy, cy [H0,4] int32 device arrays: the tap tables of resize._cubic_taps(W0, W) and (H0, H), made on the
+ * host as for rib_resize_cubic (the float32 weight arithmetic is not restated on the device); indices outside the input are
+ * clamped.  Every size pair is allowed: enlargement, H0 == H and W0 == W (no resampling: the taps are the identity) and
+ * reduction on either axis (strong reductions take a slower path of the same kernel).  pred and mask 4-byte aligned; bg and
+ * out at any byte alignment.  out == bg (in place) is allowed: a pixel reads no background byte but its own; any other
+ * overlap is not.  One launch, no workspace, no atomics, integer arithmetic only after the two quantisers: a frame's bytes
+ * do not depend on N.  Sizes < 1, N outside 1..65535, a frame of 2 GiB or more, a NULL pointer: RIB_ERR_INVALID with a
+ * rib_last_error text, and nothing is launched. */
+int rib_composite(rib_handle* h, int N, int H, int W, int H0, int W0,
+                  const float* pred_f32_nchw, const float* mask_f32_n1hw, const uint8_t* bg_u8_nhwc,
+                  const int32_t* ix, const int32_t* cx, const int32_t* iy, const int32_t* cy,
+                  uint8_t* out_u8_nhwc, void* hip_stream);
 /* ---- label-map rasterisation --------------------------------------------------
  * Replaces, per frame, Dataset._generate_skeleton + _generate_pose_map
  * (PGNR/datasets/HSM_auto_dataset.py:205-251; drawing rules PGNR/utils/keypoint2img.py:36-88,132-147)

@@ -58,6 +58,7 @@ SIGNATURES = {
     "rib_quality_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "rib_quality": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p]),
     "rib_resize_cubic": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 8),
+    "rib_composite": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 9),
     "rib_warp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4),
     "rib_rasterise_workspace_bytes": (C.c_size_t, [C.c_void_p] + [C.c_int] * 6),
     "rib_rasterise": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,

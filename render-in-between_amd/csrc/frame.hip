@@ -1,5 +1,5 @@
 // frame.hip — the folder driver's frame utilities behind the C ABI (include/rib.h): blend, quantise, cubic resize, PSNR/SSIM,
-// flow warp, label rasteriser, pose mask, diagnostic sheet, JPEG encoder and the motion-compensated background (MCI).  The second host object of librib.so (frame.o,
+// flow warp, source-size composite, label rasteriser, pose mask, diagnostic sheet, JPEG encoder and the motion-compensated background (MCI).  The second host object of librib.so (frame.o,
 // csrc/build.py).  None of these entries touches a launch plan, the weight blob or a tuned choice: of a handle they use the
 // device index, the error string and the small state of rib::FrameState (rib_host.h), reached through frame_state().
 //
@@ -14,6 +14,7 @@
 #include "panel.hip.h"
 #include "jpeg.hip.h"
 #include "mci.hip.h"
+#include "composite.hip.h"
 #include "rib_host.h"
 
 #include <algorithm>
@@ -71,6 +72,35 @@ int rib_resize_cubic(rib_handle* handle, int N, int H0, int W0, int H, int W, co
   hipLaunchKernelGGL(k_resize_cubic_u8, dim3(tilesX * tilesY, N), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream), src,
               reinterpret_cast<const int4*>(ix), reinterpret_cast<const int4*>(cx), reinterpret_cast<const int4*>(iy),
               reinterpret_cast<const int4*>(cy), out_u8, out_f32, H0, W0, H, W, tilesX);
+  HIP_TRY(h, hipGetLastError());
+  return RIB_OK;
+}
+
+int rib_composite(rib_handle* handle, int N, int H, int W, int H0, int W0, const float* pred, const float* mask, const uint8_t* bg,
+                  const int32_t* ix, const int32_t* cx, const int32_t* iy, const int32_t* cy, uint8_t* out, void* hip_stream) {
+  FrameState* h = frame_state(handle);
+  if (!h) return RIB_ERR_INVALID;
+  if (!pred || !mask || !bg || !ix || !cx || !iy || !cy || !out) return fail(h, RIB_ERR_INVALID, "rib_composite: null pointer");
+  if (N < 1 || H < 1 || W < 1 || H0 < 1 || W0 < 1 || N > 65535)
+    return fail(h, RIB_ERR_INVALID, fmt("rib_composite: N=%d H=%d W=%d H0=%d W0=%d: sizes must be positive (N <= 65535)", N, H, W, H0, W0));
+  if ((size_t)H0 * W0 * 3 > (size_t)INT32_MAX || (size_t)H * W * 3 > (size_t)INT32_MAX)
+    return fail(h, RIB_ERR_INVALID, "rib_composite: a frame must be smaller than 2 GiB");
+  if ((reinterpret_cast<uintptr_t>(pred) & 3) != 0 || (reinterpret_cast<uintptr_t>(mask) & 3) != 0)
+    return fail(h, RIB_ERR_INVALID, "rib_composite: pred and mask must be 4-byte aligned");
+  if (h->device >= 0) HIP_TRY(h, hipSetDevice(h->device));
+  CompositeParams cp;
+  cp.pred = pred; cp.mask = mask; cp.bg = bg; cp.out = out;
+  cp.ix = reinterpret_cast<const int4*>(ix); cp.cx = reinterpret_cast<const int4*>(cx);
+  cp.iy = reinterpret_cast<const int4*>(iy); cp.cy = reinterpret_cast<const int4*>(cy);
+  cp.H = H; cp.W = W; cp.H0 = H0; cp.W0 = W0;
+  cp.tilesX = (W0 + CMP_TW - 1) / CMP_TW;
+  const int tilesY = (H0 + CMP_TH - 1) / CMP_TH;
+  // the input patch of a tile, bounded from the sizes alone: kept in LDS where it fits the budget, else no patch at all
+  cp.pwMax = std::min(composite_patch_bound(CMP_TW, W0, W), W);
+  cp.phMax = std::min(composite_patch_bound(CMP_TH, H0, H), H);
+  if (cp.pwMax > CMP_PW || cp.phMax > CMP_PH) cp.pwMax = cp.phMax = 0;
+  hipLaunchKernelGGL(k_composite, dim3(cp.tilesX * tilesY, N), dim3(256), composite_lds_bytes(cp.pwMax, cp.phMax),
+                     reinterpret_cast<hipStream_t>(hip_stream), cp);
   HIP_TRY(h, hipGetLastError());
   return RIB_OK;
 }

@@ -50,9 +50,11 @@ import numpy as np
 import torch
 
 from . import background as _background
+from . import composite as _composite
 from . import io_worker, rasterise
 from . import metrics as _metrics
 from . import panel as _panel
+from . import resize as _resize
 from . import video as _video
 
 
@@ -250,19 +252,25 @@ def section_views(flat, spec, table):
     return views
 
 
-def staging_spec(Tc, Bc, model_hw, src_dain=None, src_gt=None, want_gt=False, masks=False, keys=False, mci=False, mci_keys=False):
+def staging_spec(Tc, Bc, model_hw, src_dain=None, src_gt=None, want_gt=False, masks=False, keys=False, mci=False, mci_keys=False,
+                 src_keys=None):
     """The spec of a unit's staging block, which the decode tasks fill and upload() sends to the GPU (DESIGN 4e has the table):
     Tc time steps of Bc segments at the model size (H, W).  src_dain / src_gt: (w0, h0) at which that list is staged for the
     GPU resize (resize_on="gpu"), None: the model size; want_gt, masks: ground-truth frames / masks are staged; keys: a first
     chunk under panels, the DAIN frames of the key frames it starts from; mci: background="mci", no DAIN bytes at all;
-    mci_keys: its first chunk, the group's left and right key frames."""
+    mci_keys: its first chunk, the group's left and right key frames.  src_keys: (w0, h0) - a first chunk under
+    output_size="source" with video, the key frames it starts from at the output size, for their video files; the section
+    `key_src` exists in the spec only then."""
     H, W = model_hw
     (wd, hd), (wg, hg) = src_dain or (W, H), src_gt or (W, H)
-    return (("dain", torch.uint8, (Tc, Bc, hd, wd, 3), not mci),
+    spec = (("dain", torch.uint8, (Tc, Bc, hd, wd, 3), not mci),
             ("gt", torch.uint8, (Tc, Bc, hg, wg, 3), want_gt),
             ("mask", torch.uint8, (Tc, Bc, H, W), masks),
             ("key", torch.uint8, (Bc, H, W, 3), keys and not mci),
             ("mci_keys", torch.uint8, (2, Bc, H, W, 3), mci and mci_keys))
+    if src_keys is not None:
+        spec += (("key_src", torch.uint8, (Bc, src_keys[1], src_keys[0], 3), True),)
+    return spec
 
 
 def _process_pool(n):
@@ -317,12 +325,14 @@ def shm_windows_bytes(unit_bytes):
     return (DECODE_AHEAD + MAX_UNITS_IN_FLIGHT + 4) * int(unit_bytes)
 
 
-def plan_gpu_resize(dain_sizes, gt_sizes, model_size, slots_per_unit, mask=False, shm_free=None):
+def plan_gpu_resize(dain_sizes, gt_sizes, model_size, slots_per_unit, mask=False, shm_free=None, out_slot_bytes=0):
     """Which frame lists of a clip does Evaluator(resize_on="gpu") stage at their SOURCE size for the GPU resize
     (rib_resize_cubic), and which fall back to the host resize?  A pure function of sizes and budgets.
     dain_sizes / gt_sizes: [(w0, h0)] header sizes of the clip's DAIN frames / measured ground-truth frames (gt_sizes None: no
     metrics); model_size (W, H); slots_per_unit: frames of one pipeline unit (chunk x batch); mask: a mask is staged per slot
-    too; shm_free: bytes the shared staging blocks may take (None: staging is not in shared memory, no budget applies).
+    too; shm_free: bytes the shared staging blocks may take (None: staging is not in shared memory, no budget applies);
+    out_slot_bytes: bytes per slot by which the unit's download block, which lies in the same shared memory, exceeds the model
+    size's (output_size="source": a frame at the source size), counted over the same windows.
     -> ({"DAIN": (w0, h0) or None, "GT": (w0, h0) or None}, [(list name, reason)]): the source size of each list that goes to
     the GPU (None: host resize) and one reason per list that was asked for and falls back.
     Rules: the sizes inside a list must be uniform (the two lists may differ from each other); then the unit's staging block
@@ -341,7 +351,7 @@ def plan_gpu_resize(dain_sizes, gt_sizes, model_size, slots_per_unit, mask=False
     if shm_free is not None:
         def need():
             per_slot = sum((s_[0] * s_[1] if s_ is not None else W * H) * 3 for n_, s_ in src.items() if n_ == "DAIN" or gt_sizes is not None)
-            return shm_windows_bytes(slots_per_unit * (per_slot + (W * H if mask else 0)))
+            return shm_windows_bytes(slots_per_unit * (per_slot + (W * H if mask else 0) + out_slot_bytes))
         for name in ("GT", "DAIN"):
             if src[name] is not None and need() > shm_free:
                 why.append((name, "the staging windows at %dx%d need %.0f MB of shared memory, %.0f MB are free"
@@ -565,7 +575,7 @@ class Evaluator:
                              panels=False, panel_frames=False, panel_quality=90, panel_fps=30, panel_encode="host",
                              background="dain", mci_range=32, video=False, video_fps=30, video_quality=90, video_frames=False, frames="png",
                              poses="folder", key_pose_dir=None, upsample_rate=8, motion=None, save_poses=False, mci_border="clamp",
-                             mci_precision="full"):
+                             mci_precision="full", output_size="model"):
         """rank / world: this process's share of the independent units (default: the torch.distributed process
         group when one is initialised, else everything).  Returns the frames THIS rank wrote.
         The call is one `_FolderPipeline` (below): plan a clip -> decode -> upload -> render -> sink, pipelined over units
@@ -630,7 +640,19 @@ class Evaluator:
         Under background="mci" frame i is named "%06d" % i, the stem stage 1's command gives its file.  "keyframes-linear":
         the same from the linearly interpolated clip (stage 1's Linear_motion folder).  save_poses=True also writes
         <save_dir>/../Predict_motion/<clip>/ and Linear_motion/<clip>/ - beside save_dir, where stage 1's command run with
-        the same --save-dir puts them - through that command's own motion2openpose (rank 0; for inspection)."""
+        the same --save-dir puts them - through that command's own motion2openpose (rank 0; for inspection).
+        output_size="source" (default "model": every file at the model size, as the reference): the frames' PNGs and the video
+        are written at the clip's SOURCE size, the uniform size (w0, h0) of its DAIN frames: an in-between frame is
+        composite.composite_host of the chain's predicted image and blend mask and the DAIN file's own pixels - the person is
+        a cubic enlargement of the model-size prediction (soft), the background keeps every source pixel - and a key frame is
+        the key-frame file's own pixels (resize.resize_cubic_u8 to (w0, h0) if its size differs).  The chain itself, the
+        metrics and the sheets stay at the model size.  On the native path this needs resize_on="gpu" (the source-size bytes
+        are on the device only there): one rib_composite launch fills the `frames` section of the unit's download buffer, and
+        with video the files come from rib_jpeg on those bytes; a clip whose DAIN list the plan sends back to the host resize
+        (mixed sizes, shared-memory budget) is an error before any of its files is written.  A model behind the reference's
+        protocol decodes each DAIN file once more at its own size and goes through composite_host, and its generator is fed the
+        background floats the native chain reads (background.normalised_upload, as under background="mci"): the same files.
+        background="mci" is not supported with it (the interpolation runs at the model size)."""
         if poses not in ("folder", "keyframes", "keyframes-linear"):
             raise ValueError("evaluate_from_folder: poses must be 'folder', 'keyframes' or 'keyframes-linear', got %r" % (poses,))
         if poses == "folder" and (key_pose_dir is not None or upsample_rate != 8 or motion is not None or save_poses):
@@ -643,6 +665,10 @@ class Evaluator:
             if not (isinstance(upsample_rate, int) and upsample_rate >= 1 and upsample_rate & (upsample_rate - 1) == 0):
                 raise ValueError("evaluate_from_folder: upsample_rate must be a power of two, got %r" % (upsample_rate,))
         mci_levels, mci_border = _background.check_settings(background, mci_range, mci_border, self.resize_on, mci_precision=mci_precision)
+        _composite.check_output_size(output_size, "evaluate_from_folder")
+        if output_size == "source" and background == "mci":
+            raise ValueError("evaluate_from_folder: output_size='source' with background='mci' is not supported: the interpolation "
+                             "runs at the model size (a source-size interpolation is a follow-up)")
         if gen_vid:
             # the reference also writes <save_dir>/<clip>.mp4 (evaluator.py:267-269, utils.make_video) from a matplotlib canvas
             # through an H.264 encoder; neither is built, and silently ignoring the flag would drop an output the caller asked for
@@ -675,9 +701,10 @@ class Evaluator:
         pipe = _FolderPipeline(self, model, rank, world, gt_dir, metrics=bool(metrics), mask_dir=mask_dir, pose_mask=bool(pose_mask),
                                panels=bool(panels), panel_frames=bool(panel_frames), panel_quality=int(panel_quality),
                                panel_encode=panel_encode, background=background, mci_levels=mci_levels, mci_border=mci_border, mci_precision=mci_precision, video=bool(video), video_quality=int(video_quality),
-                               video_frames=bool(video_frames), write_png=frames == "png",
+                               video_frames=bool(video_frames), write_png=frames == "png", output_size=output_size,
                                key_poses=None if poses == "folder" else (motion, key_pose_dir, upsample_rate, poses == "keyframes-linear", bool(save_poses)))
         self.background, self.mci_range, self.mci_border, self.mci_precision = background, mci_range, mci_border, mci_precision
+        self.output_size = output_size
         self.timings = pipe.tm
         if metrics and pipe.native:
             self._quality_model = model
@@ -747,6 +774,11 @@ class _Clip:
         # frames="none" the .jpg
         self.video_dir = None
         self.out_names = names
+        # output_size="source": (w0, h0) of the clip's files, the uniform size of its DAIN frames; key_src: key frame index ->
+        # future of its uint8 HWC pixels at that size (the key file's own, resized only if its size differs); src_of: unit ->
+        # (the staged DAIN frames uint8 [Tc,B,h0,w0,3], a first chunk's key frames uint8 [B,h0,w0,3] or None) on the device
+        self.out_size = None
+        self.key_src, self.src_of = {}, {}
 
     def sheet_names(self, i, png):
         """(jpg, png or None) of frame i's sheet."""
@@ -782,7 +814,9 @@ class _FolderPipeline:
 
     def __init__(self, ev, model, rank, world, gt_dir, metrics=False, mask_dir=None, pose_mask=False,
                  panels=False, panel_frames=False, panel_quality=90, panel_encode="host", background="dain", mci_levels=3,
-                 video=False, video_quality=90, video_frames=False, write_png=True, key_poses=None, mci_border="clamp", mci_precision="full"):
+                 video=False, video_quality=90, video_frames=False, write_png=True, key_poses=None, mci_border="clamp", mci_precision="full",
+                 output_size="model"):
+        self.source = output_size == "source"      # composite.py: the frames' files at the clip's source size
         self.mci, self.mci_levels = background == "mci", mci_levels      # (levels: background.mci_field_host's, from mci_range)
         self.mci_border = mci_border        # background.py's border
         self.mci_half = mci_precision == "half"      # background.py's precision: the field is refined once per group, in half pixels
@@ -811,6 +845,14 @@ class _FolderPipeline:
             raise RuntimeError("panel_encode='gpu': this model has no GPU JPEG kernels (rib_jpeg)")
         if self.native and video and not hasattr(model, "jpeg_f32_into"):
             raise RuntimeError("video=True: this model has no GPU JPEG kernels for float frames (rib_jpeg_float)")
+        if self.source and self.native:
+            if ev.resize_on != "gpu":
+                raise ValueError("output_size='source' needs resize_on='gpu' on the native path: the background frames' source-size "
+                                 "bytes are on the device only there (Evaluator(resize_on='gpu'), inference.py --resize-on gpu)")
+            if not hasattr(model, "composite"):
+                raise RuntimeError("output_size='source': this model has no GPU composite kernel (rib_composite)")
+            if video and not hasattr(model, "jpeg_into"):
+                raise RuntimeError("output_size='source' with video=True: this model has no GPU JPEG kernels (rib_jpeg)")
         self.gpu_labels = self.native and ev.label_fn is None and hasattr(model, "rasterise")
         per_slot = (1.0 + (1.0 if (metrics or (panels and gt_dir is not None)) else 0.0) + (1.0 / 3 if mask_dir is not None else 0.0))
         if panels:                           # a unit's download block also carries its sheets (six panes and the borders per frame)
@@ -864,10 +906,31 @@ class _FolderPipeline:
         """Frame i's files from its float tensor x [1,3,H,W] on the host (key frames; every frame of the reference path): the
         PNG unless frames="none", and under video=True - on the reference path: the native path encodes every frame on the
         GPU - the .jpg of the same uint8 array."""
-        u8 = self.host_u8(x)
+        return self.save_u8(clip, i, self.host_u8(x))
+
+    def save_u8(self, clip, i, u8):
+        """Frame i's files from the uint8 HWC array its PNG holds (save_frame_host; output_size="source": the arrays below)."""
         if self.video and not self.native:
             _video.save_frame_host(u8, clip.video_name(i), self.video_quality)
         return self.save_q(u8, clip.names[i]) if self.write_png else clip.video_name(i)
+
+    def key_source_u8(self, clip, i):
+        """output_size="source": key frame i's file as its PNG shows it - the file's own pixels, uint8 HWC, resized
+        (resize.resize_cubic_u8, on the host as key frames are) only if its size is not the clip's (w0, h0)."""
+        w0, h0 = clip.out_size
+        u8 = io_worker.decode_u8(clip.ref_image(i))
+        if (u8.shape[1], u8.shape[0]) != (w0, h0):
+            u8 = _resize.resize_cubic_u8(u8, w0, h0)
+        return np.array(u8)                      # (a writable copy: PIL's array is not, and the staging views copy from it)
+
+    def save_source_host(self, clip, i, img, mask):
+        """output_size="source" behind the reference's protocol: frame i's files from the model's predicted image [1,3,H,W] and
+        blend mask [1,1,H,W] and the DAIN file decoded once more at its own size (composite.composite_host)."""
+        bg = io_worker.decode_u8(clip.dain_list[i])
+        if (bg.shape[1], bg.shape[0]) != tuple(clip.out_size):
+            raise ValueError("%s is %dx%d, the clip's output size is %dx%d" % ((clip.dain_list[i], bg.shape[1], bg.shape[0]) + tuple(clip.out_size)))
+        u8 = _composite.composite_host(img.detach().cpu().float().numpy(), mask.detach().cpu().float().numpy(), bg[None])[0]
+        return self.save_u8(clip, i, u8)
 
     # ---- stage 0: plan ---------------------------------------------------------------------------------------------------
     def interpolate_poses(self, sub, n_key, save_dir):
@@ -905,6 +968,13 @@ class _FolderPipeline:
             pose_list = _list(os.path.join(pose_dir, sub), ("json",))
             sample_rate = sample_rate_of(len(pose_list), len(image_list))
         seq_len = (len(image_list) - 1) * sample_rate + 1
+        out_size = None
+        if self.source:                      # one size per clip, read from the headers before anything of the clip is written
+            kinds = sorted({tuple(self.image_size(p)) for p in dain_list[:seq_len]})
+            if len(kinds) != 1:
+                raise ValueError("output_size='source': clip %s: the DAIN frames have mixed sizes (%s); the clip's files need one size"
+                                 % (sub, ", ".join("%dx%d" % k for k in kinds[:4])))
+            out_size = kinds[0]
         if self.mci and self.key_poses is not None:      # the stems stage 1's own command gives its files
             names = [os.path.join(frames_dir, "%06d.png" % i) for i in range(seq_len)]
         elif self.mci:                       # no DAIN list to name the frames after: the pose file's stem
@@ -947,6 +1017,7 @@ class _FolderPipeline:
                     units.append((gi, members, c0, min(T, c0 + step)))
         clip = _Clip(names, dain_list, image_list, pose_list, gtlist, sample_rate, my_keys, segs, units, sub=sub,
                      measure=self.metrics, mask_list=mask_list)
+        clip.out_size = out_size
         if self.video:
             clip.video_dir = _video.video_dir(save_dir, sub)
             os.makedirs(clip.video_dir, exist_ok=True)
@@ -965,8 +1036,13 @@ class _FolderPipeline:
             src, why = plan_gpu_resize([self.image_size(dain_list[i]) for i in staged],
                                        [self.image_size(gtlist[i]) for i in staged] if self.metrics else None,
                                        (ev.width, ev.height), slots, mask=mask_list is not None,
-                                       shm_free=_shm_free_bytes() if self.procs is not None else None)
+                                       shm_free=_shm_free_bytes() if self.procs is not None else None,
+                                       out_slot_bytes=max(0, out_size[0] * out_size[1] - ev.width * ev.height) * 3
+                                       if (self.source and self.write_png) else 0)
             clip.src_dain, clip.src_gt = src["DAIN"], src["GT"]
+            if self.source and clip.src_dain is None:      # never a silent change of the output's size
+                raise ValueError("output_size='source': clip %s: the DAIN list falls back to the host resize, so its source-size bytes "
+                                 "would not be on the device: %s" % (sub, "; ".join(r_ for n_, r_ in why if n_ == "DAIN") or "no reason given"))
             for name, reason in why:
                 print("resize_on='gpu': clip {}: the {} list falls back to the host resize: {}".format(sub, name, reason))
         self.clips.append(clip)
@@ -977,7 +1053,12 @@ class _FolderPipeline:
         """Pre-load of frame i on a pool thread (evaluator.py:205-235)."""
         ev = self.ev
         staged_raw = i in clip.slot and clip.src_dain is not None
-        dain = None if (staged_raw or self.mci) else (ev.load_image_u8 if self.native else ev.load_image)(clip.dain_list[i])[0]
+        if self.source and not self.native:
+            # output_size="source" is held to the native path's files, and that path exists under resize_on="gpu" only: a model behind
+            # the reference's protocol reads the very floats that chain reads (the device's normalisation, as under background="mci")
+            dain = torch.from_numpy(_background.normalised_upload(ev._decode_resized_u8(clip.dain_list[i])[0]))
+        else:
+            dain = None if (staged_raw or self.mci) else (ev.load_image_u8 if self.native else ev.load_image)(clip.dain_list[i])[0]
         if i in clip.slot:
             ui, t, b = clip.slot[i]
             views = clip.staged[ui]["views"]
@@ -1016,7 +1097,7 @@ class _FolderPipeline:
         if section not in table:
             return -1
         off, nbytes = table[section]
-        slots = len(members) * (1 if section == "key" else c1 - c0)
+        slots = len(members) * (1 if section in ("key", "key_src") else c1 - c0)
         return off + (t * len(members) + b) * (nbytes // slots)
 
     def decode_in_worker(self, clip, i):
@@ -1054,9 +1135,15 @@ class _FolderPipeline:
             return
         clip.loads[i] = self.decode_in_worker(clip, i) if self.procs is not None else self.pool.submit(self.decode_here, clip, i)
         # key frames pass through (evaluator.py:240-244); native path under frames="none": their only file comes from the GPU
+        if self.source and i in clip.keys and i not in clip.key_src:
+            clip.key_src[i] = self.pool.submit(self.key_source_u8, clip, i)
         if i in clip.keys and i not in clip.futs and (self.write_png or not self.native):
-            clip.futs[i] = self.finishers.submit(
-                lambda: self.save_frame_host(clip, i, clip.loads[i].result(timeout=IO_TIMEOUT_S)[1].unsqueeze(0)))
+            if self.source:                      # the key file's own pixels (the future is held here: the clip's table is cleared early)
+                ks = clip.key_src[i]
+                clip.futs[i] = self.finishers.submit(lambda: self.save_u8(clip, i, ks.result(timeout=IO_TIMEOUT_S)))
+            else:
+                clip.futs[i] = self.finishers.submit(
+                    lambda: self.save_frame_host(clip, i, clip.loads[i].result(timeout=IO_TIMEOUT_S)[1].unsqueeze(0)))
 
     def open_units(self, clip, upto):
         """Staging block, slots and decode tasks of the units up to index `upto`: the launch thread keeps DECODE_AHEAD units open
@@ -1067,7 +1154,8 @@ class _FolderPipeline:
             _, members, c0, c1 = clip.units[ui]
             # one block per unit; a later chunk under background="mci" may stage nothing at all and still gets its byte
             spec = staging_spec(c1 - c0, len(members), (ev.height, ev.width), clip.src_dain, clip.src_gt, want_gt=clip.want_gt,
-                                masks=clip.mask_list is not None, keys=self.panels and c0 == 0, mci=self.mci, mci_keys=c0 == 0)
+                                masks=clip.mask_list is not None, keys=self.panels and c0 == 0, mci=self.mci, mci_keys=c0 == 0,
+                                src_keys=clip.out_size if (self.source and self.video and c0 == 0) else None)
             table, total = block_layout(spec_bytes(spec))
             # worker processes: shared with them and page-locked (size classes of 1 MB: the block may be larger than the unit)
             blk = _shm_get(max(1, total)) if self.procs is not None else None
@@ -1140,6 +1228,13 @@ class _FolderPipeline:
                 else:
                     dn = staged.permute(0, 1, 4, 2, 3).to(torch.float32)
                     dn = ((dn / 255.0 - 0.5) / 0.5).contiguous()                      # [Tc,B,3,H,W]
+            if self.source:                    # the staged frames stay as they are for the composite; a first chunk's key frames
+                ksrc = None                    # go up at the output size for their video files
+                if views.get("key_src") is not None:
+                    for b, si in enumerate(members):
+                        views["key_src"][b].copy_(torch.from_numpy(clip.key_src[clip.segs[si][0]].result(timeout=IO_TIMEOUT_S)))
+                    ksrc = views["key_src"].to(g.device, non_blocking=True)
+                clip.src_of[ui] = (staged, ksrc)
             gtd = gt.to(g.device) if gt is not None else None
             gtf = staged_gt = None
             if clip.want_gt:
@@ -1181,7 +1276,7 @@ class _FolderPipeline:
                 clip.pan[ui] = (gtp, klab, kdn, clip.key_of[gi], dnp)
             ready = torch.cuda.Event()
             ready.record(self.up)
-        for t_ in (lab, dn, gtd) + tuple(clip.meas.get(ui, ())) + tuple(clip.pan.get(ui, ())):
+        for t_ in (lab, dn, gtd) + tuple(clip.meas.get(ui, ())) + tuple(clip.pan.get(ui, ())) + tuple(clip.src_of.get(ui, ())):
             if t_ is not None:
                 t_.record_stream(st)
         return lab, dn, gtd, ready
@@ -1196,7 +1291,7 @@ class _FolderPipeline:
         gi, members, c0, _ = clip.units[ui]
         with torch.cuda.stream(st):
             st.wait_event(ready)
-            imgs, masks, fz = g.chain(gtd if c0 == 0 else clip.prev_of[gi], lab, dn, want_all=self.panels)      # fz [Tc,B,3,H,W]
+            imgs, masks, fz = g.chain(gtd if c0 == 0 else clip.prev_of[gi], lab, dn, want_all=self.panels or self.source)      # fz [Tc,B,3,H,W]
             clip.prev_of[gi] = fz[-1]
             t0 = time.perf_counter()
             n, H, W = fz.shape[0] * fz.shape[1], fz.shape[3], fz.shape[4]
@@ -1205,7 +1300,9 @@ class _FolderPipeline:
             nk = kdn.shape[0] if kdn is not None else 0          # panels: a first chunk also draws the key frames it starts from
             SH, SW = self.sheet_hw if self.panels else (0, 0)
             home = self.panels and (not self.jpeg_gpu or self.panel_frames)     # the raw sheets travel home
-            spec = (("frames", torch.uint8, (n, H, W, 3), self.write_png),
+            # output_size="source": the frames' files are at the clip's (w0, h0); the chain, the metrics and the sheets stay at H x W
+            W0, H0 = clip.out_size if self.source else (W, H)
+            spec = (("frames", torch.uint8, (n, H0, W0, 3), self.write_png),
                     ("qual", torch.float32, (4, n), clip.measure),       # OURS PSNR, OURS SSIM, DAIN PSNR, DAIN SSIM
                     ("sheet_len", torch.int32, (n + nk,), self.jpeg_gpu),        # (jpeg_gpu implies panels)
                     ("video_len", torch.int32, (self.video_count(clip, ui),), self.video),
@@ -1215,7 +1312,13 @@ class _FolderPipeline:
             buf = torch.empty(total, dtype=torch.uint8, device=g.device)
             dev = section_views(buf, spec, table)
             keep = [fz, lab, dn, gtd, buf]
-            if self.write_png:
+            shown = None
+            if self.source:                      # one launch: quantise, enlarge and blend over the staged frames' own pixels
+                staged, ksrc = clip.src_of.pop(ui)
+                shown = dev["frames"] if self.write_png else torch.empty((n, H0, W0, 3), dtype=torch.uint8, device=g.device)
+                g.composite(imgs.reshape(n, 3, H, W), masks.reshape(n, 1, H, W), staged.flatten(0, 1), out=shown)
+                keep += [imgs, masks, staged, ksrc, shown]
+            elif self.write_png:
                 g.quantise(frames, out=dev["frames"])
             if clip.measure:
                 gtf, mk = clip.meas.pop(ui)
@@ -1233,7 +1336,10 @@ class _FolderPipeline:
                 if self.jpeg_gpu:
                     jpeg = self.encode_jpeg(g, sheets, dev["sheet_len"])
                     keep += [sheets, jpeg]
-            if self.video:
+            if self.video and self.source:
+                vid = self.encode_video_u8(g, shown, ksrc, dev["video_len"])
+                keep += [vid]
+            elif self.video:
                 vid = self.encode_video(clip, ui, g, frames, gtd, dev["video_len"])
                 keep += [vid]
             out_blk = _shm_get(total) if self.procs is not None else None       # shared with the encode workers, page-locked
@@ -1250,7 +1356,7 @@ class _FolderPipeline:
         # frames_off / sheets_off: where the file workers find those two sections in the shared block
         return {"done": done, "out_blk": out_blk, "keep": tuple(keep),
                 "frames": host["frames"], "qual": host["qual"], "sheets": host["sheets"],
-                "frames_off": table["frames"][0] if "frames" in table else None,
+                "frames_off": table["frames"][0] if "frames" in table else None, "frame_hw": (H0, W0),
                 "sheets_off": table["sheets"][0] if "sheets" in table else None,
                 "jpeg": jpeg + (host["sheet_len"],) if jpeg else None, "video": vid + (host["video_len"],) if vid else None,
                 "sheet_frames": clip.unit_frames(ui) + ([clip.segs[si][0] for si in members] if nk else []) if self.panels else None}
@@ -1278,6 +1384,19 @@ class _FolderPipeline:
         g.jpeg_f32_into(frames.to(torch.float32).contiguous(), files[:n * cap], lengths[:n], self.video_quality, cap)
         if nk:
             g.jpeg_f32_into(gtd.to(torch.float32).contiguous(), files[n * cap:], lengths[n:], self.video_quality, cap)
+        return files, cap
+
+    def encode_video_u8(self, g, shown, ksrc, lengths):
+        """video=True under output_size="source", on the lane's stream: rib_jpeg of the unit's frames uint8 [n,H0,W0,3] - the
+        very bytes of their PNGs - and, in a first chunk, of the key frames ksrc uint8 [B,H0,W0,3] it starts from, one call
+        each -> (files, cap) as encode_video's."""
+        n, H0, W0, _ = shown.shape
+        nk = lengths.numel() - n
+        cap = g.jpeg_max_bytes(H0, W0)
+        files = torch.empty((n + nk) * cap, dtype=torch.uint8, device=g.device)
+        g.jpeg_into(shown, files[:n * cap], lengths[:n], self.video_quality, cap)
+        if nk:
+            g.jpeg_into(ksrc.contiguous(), files[n * cap:], lengths[n:], self.video_quality, cap)
         return files, cap
 
     def save_sheets(self, clip, frames, sheets, out_blk=None, off=0):
@@ -1362,7 +1481,13 @@ class _FolderPipeline:
                 keep += [sheets, kdn, klab]
                 if self.jpeg_gpu:                # the files of both encoders stay on the device until their lengths are home
                     jpeg = self.encode_jpeg(g, sheets, dev["sheet_len"])
-            if self.video:
+            if self.video and self.source:       # the key files' own pixels at the clip's output size
+                ku8 = torch.from_numpy(np.stack([clip.key_src[k].result(timeout=IO_TIMEOUT_S) for k in loose])).to(g.device)
+                cap = g.jpeg_max_bytes(*ku8.shape[1:3])
+                vid = (torch.empty(n * cap, dtype=torch.uint8, device=g.device), cap)
+                g.jpeg_into(ku8, vid[0], dev["video_len"], self.video_quality, cap)
+                keep += [ku8]
+            elif self.video:
                 cap = g.jpeg_max_bytes(*keys.shape[2:])
                 vid = (torch.empty(n * cap, dtype=torch.uint8, device=g.device), cap)
                 g.jpeg_f32_into(keys, vid[0], dev["video_len"], self.video_quality, cap)
@@ -1410,8 +1535,9 @@ class _FolderPipeline:
         sheet_fs = self.save_sheets(clip, r["sheet_frames"], r["sheets"], out_blk, r["sheets_off"]) if r["sheets"] is not None else []
         fs = []
         if self.write_png and out_blk is not None:      # the workers read frame j in the block, from the section's offset on
-            off, fsz = r["frames_off"], ev.height * ev.width * 3
-            fs = [self.procs.submit(io_worker.save_png_shm, out_blk.name, off + j * fsz, ev.height, ev.width, clip.names[out_frames[j]], self.level)
+            (fh, fw), off = r["frame_hw"], r["frames_off"]
+            fsz = fh * fw * 3
+            fs = [self.procs.submit(io_worker.save_png_shm, out_blk.name, off + j * fsz, fh, fw, clip.names[out_frames[j]], self.level)
                   for j in range(len(out_frames))]
         elif self.write_png:
             qn = r["frames"].numpy()
@@ -1465,6 +1591,7 @@ class _FolderPipeline:
         # where they were allocated: released with the clip (pipe.clips keeps the _Clip itself until drain)
         clip.mci_of.clear()
         clip.key_u8.clear()
+        clip.key_src.clear()
 
     @property
     def sheet_saver(self):
@@ -1511,7 +1638,10 @@ class _FolderPipeline:
             tm["rasterise"] += t2 - t1
             tm["generate"] += time.perf_counter() - t2
             for t, i in enumerate(frames):
-                clip.futs[i] = self.pool.submit(self.save_frame_host, clip, i, outs[t])
+                if self.source:                  # composite_host of the frame's (img, mask) over the DAIN file's own pixels
+                    clip.futs[i] = self.pool.submit(self.save_source_host, clip, i, *shown[t])
+                else:
+                    clip.futs[i] = self.pool.submit(self.save_frame_host, clip, i, outs[t])
             if self.panels:                      # the host statement of the sheet (panel.compose_host), a segment at a time
                 def host(xs):
                     return torch.cat([x.detach().cpu().float() for x in xs]).numpy()
@@ -1545,6 +1675,7 @@ class _FolderPipeline:
         tm["units"] = tm.get("units", 0)
         tm["frames"] += len(clip.futs)
         clip.key_u8.clear()
+        clip.key_src.clear()
 
     # ---- metrics ---------------------------------------------------------------------------------------------------------
     @staticmethod

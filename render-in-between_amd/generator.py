@@ -406,6 +406,22 @@ class Generator:
                 _ptr(ws), ws.numel(), self._stream()))
         return out[0], out[1]
 
+    def _cubic_tables(self, H0, W0, height, width):
+        """The device tap tables ix, cx [width,4], iy, cy [height,4] of a cubic resize H0 x W0 -> height x width
+        (resize._cubic_taps), as four pointers; built once per size pair and kept on the device."""
+        cache = self.__dict__.setdefault("_resize_taps", {})
+        taps = cache.get((H0, W0, height, width))
+        if taps is None:
+            from .resize import _cubic_taps
+            import numpy as np
+            (ix, cx), (iy, cy) = _cubic_taps(width, W0), _cubic_taps(height, H0)
+            host = np.concatenate([a.astype(np.int32).reshape(-1) for a in (ix, cx, iy, cy)])
+            # (kept for the life of the handle: a few KB per size pair, and a launch enqueued on another stream may still read it)
+            taps = cache[(H0, W0, height, width)] = torch.from_numpy(host).to(self.device)
+        nx, ny = width * 4 * 4, height * 4 * 4            # bytes of one table of each axis
+        base = taps.data_ptr()
+        return [C.c_void_p(base + o) for o in (0, nx, 2 * nx, 2 * nx + ny)]
+
     def resize_u8(self, frames_u8, width, height, normalised=False, out=None):
         """The folder driver's frame resize on the GPU (rib_resize_cubic): uint8 [N,H0,W0,3] (or [H0,W0,3]) on this device
         -> uint8 [N,height,width,3] (or [height,width,3]), bit-exact to resize.resize_cubic_u8; normalised=True: float32
@@ -431,18 +447,7 @@ class Generator:
             res = out.unsqueeze(0) if (single and out.dim() == 3) else out
             if tuple(res.shape) != shape or res.dtype != dtype or not res.is_contiguous() or res.device != self.device:
                 raise ValueError("resize_u8: out must be a contiguous %s %s tensor on %s" % (shape, dtype, self.device))
-        cache = self.__dict__.setdefault("_resize_taps", {})
-        taps = cache.get((H0, W0, height, width))
-        if taps is None:
-            from .resize import _cubic_taps
-            import numpy as np
-            (ix, cx), (iy, cy) = _cubic_taps(width, W0), _cubic_taps(height, H0)
-            host = np.concatenate([a.astype(np.int32).reshape(-1) for a in (ix, cx, iy, cy)])
-            # (kept for the life of the handle: a few KB per size pair, and a launch enqueued on another stream may still read it)
-            taps = cache[(H0, W0, height, width)] = torch.from_numpy(host).to(self.device)
-        nx, ny = width * 4 * 4, height * 4 * 4            # bytes of one table of each axis
-        base = taps.data_ptr()
-        tabs = [C.c_void_p(base + o) for o in (0, nx, 2 * nx, 2 * nx + ny)]
+        tabs = self._cubic_tables(H0, W0, height, width)
         with torch.cuda.device(self.device):
             _native.check(self._h, self._lib.rib_resize_cubic(
                 self._h, N, H0, W0, height, width, _ptr(src), *tabs,
@@ -450,6 +455,48 @@ class Generator:
         if out is not None:
             return out
         return res[0] if single else res
+
+    def composite(self, pred, mask, bg_u8, out=None):
+        """The fused frame at the SOURCE size on the GPU (rib_composite, csrc/composite.hip.h; composite.composite_host is the
+        definition and is bit-equal): pred [n,3,H,W] in [-1,1] and mask [n,1,H,W] in [0,1] at the model size (float32; 16-bit
+        tensors are converted), bg_u8 uint8 [n,H0,W0,3] at the source size, all on this device -> uint8 [n,H0,W0,3]:
+        the 8-bit cubic enlargement of the quantised prediction over the background's own pixels, weighted by the enlarged
+        8-bit mask.  Any size pair.  out: optional contiguous uint8 destination of bg_u8's shape at any byte offset, e.g. a
+        section of a download buffer; it may be bg_u8 itself (in place).  One launch on the current stream."""
+        for t, ch, name in ((pred, 3, "pred"), (mask, 1, "mask")):
+            if not torch.is_tensor(t) or t.dim() != 4 or t.shape[1] != ch or t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+                raise ValueError("composite: %s must be a float [n,%d,H,W] tensor, got %s %s"
+                                 % (name, ch, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
+            if t.device != self.device:
+                raise ValueError("composite: %s is on %s, the generator on %s" % (name, t.device, self.device))
+        if not torch.is_tensor(bg_u8) or bg_u8.dtype != torch.uint8 or bg_u8.dim() != 4 or bg_u8.shape[-1] != 3:
+            raise ValueError("composite: bg_u8 must be a uint8 [n,H0,W0,3] tensor, got %s %s"
+                             % (getattr(bg_u8, "dtype", type(bg_u8)), tuple(getattr(bg_u8, "shape", ()))))
+        if bg_u8.device != self.device:
+            raise ValueError("composite: bg_u8 is on %s, the generator on %s (upload the frames first)" % (bg_u8.device, self.device))
+        N, _, H, W = pred.shape
+        _, H0, W0, _ = bg_u8.shape
+        if tuple(mask.shape) != (N, 1, H, W) or bg_u8.shape[0] != N:
+            raise ValueError("composite: pred %s, mask %s and bg_u8 %s do not describe the same frames"
+                             % (tuple(pred.shape), tuple(mask.shape), tuple(bg_u8.shape)))
+        if min(N, H, W, H0, W0) < 1 or N > 65535:
+            raise ValueError("composite: 1 <= n <= 65535 non-empty frames (pred %s, bg_u8 %s)" % (tuple(pred.shape), tuple(bg_u8.shape)))
+        pred = pred.to(torch.float32).contiguous()
+        mask = mask.to(torch.float32).contiguous()
+        if out is None:
+            res = torch.empty((N, H0, W0, 3), dtype=torch.uint8, device=self.device)
+        else:
+            res = out
+            if not torch.is_tensor(res) or tuple(res.shape) != (N, H0, W0, 3) or res.dtype != torch.uint8 or not res.is_contiguous() \
+                    or res.device != self.device:
+                raise ValueError("composite: out must be a contiguous uint8 %s tensor on %s" % ((N, H0, W0, 3), self.device))
+        # in place on the caller's own frames; a background that had to be made contiguous is a copy and cannot alias out
+        bg = bg_u8 if bg_u8.is_contiguous() else bg_u8.contiguous()
+        tabs = self._cubic_tables(H, W, H0, W0)
+        with torch.cuda.device(self.device):
+            _native.check(self._h, self._lib.rib_composite(self._h, N, H, W, H0, W0, _ptr(pred), _ptr(mask), _ptr(bg), *tabs,
+                                                           _ptr(res), self._stream()))
+        return res
 
     def warp(self, img, flow):
         img = img.to(self.device, torch.float32).contiguous(); flow = flow.to(self.device, torch.float32).contiguous()

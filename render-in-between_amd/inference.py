@@ -130,6 +130,8 @@ def summary_line(evaluator, rank=0, world=1):
                        % (getattr(evaluator, "mci_range", 32), getattr(evaluator, "mci_border", "clamp"),
                           ", half-pel" if getattr(evaluator, "mci_precision", "full") == "half" else "")}
                [getattr(evaluator, "background", "dain")]))
+    if getattr(evaluator, "output_size", "model") == "source":
+        line += " | files at the source size"
     rep = getattr(evaluator, "metrics_report", None)
     if "metrics" in tm and rep is not None:
         o = rep["overall"]
@@ -175,7 +177,7 @@ def main(opts):
                                              mci_border=opts.mci_border, mci_precision=opts.mci_precision,
                                              video=opts.video, video_fps=30 if opts.video_fps is None else opts.video_fps,
                                              video_quality=90 if opts.video_quality is None else opts.video_quality,
-                                             video_frames=opts.video_frames, frames=opts.frames, **poses_kw)
+                                             video_frames=opts.video_frames, frames=opts.frames, output_size=opts.output_size, **poses_kw)
     print(summary_line(evaluator, rank, world))
     if world > 1:
         print("[rank {}/{}] wrote {} frames".format(rank, world, len(written)))
@@ -262,6 +264,12 @@ def build_parser():
     parser.add_argument("--frames", choices=("png", "none"), default="png",
                         help="'png' (default): the reference's folder of PNG frames; 'none' (only with --video): the video is the only "
                              "output - no PNG is encoded or written, the raw frames are not downloaded")
+    parser.add_argument("--output-size", choices=("model", "source"), default="model",
+                        help="'model' (default): every file at the model size, as the reference; 'source' (needs --resize-on gpu): the "
+                             "PNGs and the --video clip at the size of the clip's DAIN frames - the background keeps every source pixel, "
+                             "the generated person is a cubic enlargement of the model-size prediction (softer than its surroundings and "
+                             "than the key frames, which are their files' own pixels), blended on the GPU in one launch; --metrics and "
+                             "--panels stay at the model size; not with --background mci")
     parser.add_argument("--poses", default="folder",
                         help="where the frames' poses come from. 'folder' (default): <input-dir>/Predict_motion/<clip>/, one OpenPose json per "
                              "output frame, as the reference (written by motion/inference.py); 'keyframes': --pose-dir holds one json per KEY "
@@ -308,6 +316,10 @@ def parse_args(argv=None):
     opts.mci_precision = "full" if opts.mci_precision is None else opts.mci_precision
     if opts.background == "mci" and opts.resize_on == "gpu":
         parser.error("--background mci with --resize-on gpu is not supported (there is no DAIN list to plan the GPU resize for)")
+    if opts.output_size == "source" and opts.background == "mci":
+        parser.error("--output-size source with --background mci is not supported: the interpolation runs at the model size")
+    if opts.output_size == "source" and opts.resize_on != "gpu":
+        parser.error("--output-size source needs --resize-on gpu: the background frames' source-size bytes are on the device only there")
     if opts.metrics and opts.gt_dir is None:
         parser.error("--metrics needs --gt-dir (the ground-truth frames)")
     if opts.mask_dir is not None and not opts.metrics:

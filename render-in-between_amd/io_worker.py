@@ -29,6 +29,12 @@ def decode_resized_u8(path, width, height, resize="cv2"):
     return resize_cubic_u8(np.asarray(img, dtype=np.uint8), width, height), (w0, h0)
 
 
+def decode_u8(path):
+    """PIL decode -> RGB uint8 HWC at the file's OWN size (output_size="source": a key frame's pixels, a DAIN frame on the host path)."""
+    from PIL import Image
+    return np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8)
+
+
 def decode_raw_into(buf, offset, path, size):
     """The "do not resize" decode of Evaluator(resize_on="gpu"): PIL decode -> RGB uint8 HWC at the file's OWN size, written to
     bytes [offset, offset + h0*w0*3) of `buf` (a shared block's buffer, or any writable buffer); the GPU resizes it

@@ -3,7 +3,7 @@
 
     python tools/driver_bench.py [--size 512 | --height 320 --width 480] [--keys 5] [--rate 32] [--lanes 2] [--batch B] [--chunk 4]
                                   [--src-width 1920 --src-height 1080] [--resize-on host|gpu] [--metrics [--pose-mask]] [--panels [--panel-encode host|gpu]]
-                                  [--video [--frames none]] [--poses folder|keyframes]
+                                  [--video [--frames none]] [--poses folder|keyframes] [--output-size model|source]
 
 Writes a clip in the reference's directory layout (inputs/ DAIN/ Predict_motion/), runs
 Evaluator.evaluate_from_folder twice (the first run also builds launch plans) and prints the
@@ -17,6 +17,8 @@ writes the clip's Motion-JPEG video (evaluate_from_folder(panels=True)); --panel
 writes only that video (frames="none": no PNG is encoded, the PNG level then plays no part).  --poses keyframes runs stage 1
 in the driver (poses="keyframes": a seed-defined motion transformer interpolates the key frames' poses of key_poses/, no json is
 read per frame; --rate must then be a power of two); the per-clip event time of stage 1 plus the bridge is reported too.
+--output-size source (with --resize-on gpu) writes the frames' files at the size of the input files (output_size="source": one
+rib_composite launch per unit; the PNG encode then works on source-size frames).
 """
 import argparse, json, os, sys, tempfile, time
 import numpy as np, torch
@@ -90,7 +92,11 @@ def main():
     ap.add_argument("--frames", default="png", choices=("png", "none"), help="with --video: 'none' writes no PNG frames (frames=...)")
     ap.add_argument("--poses", default="folder", choices=("folder", "keyframes"),
                     help="'keyframes': the motion transformer interpolates the key frames' poses inside the driver (poses=...)")
+    ap.add_argument("--output-size", default="model", choices=("model", "source"),
+                    help="'source' (with --resize-on gpu): the frames' files at the input files' size, composited on the GPU (output_size=...)")
     a = ap.parse_args()
+    if a.output_size == "source" and (a.resize_on != "gpu" or a.background == "mci"):
+        ap.error("--output-size source needs --resize-on gpu and is not supported with --background mci")
     if a.poses == "keyframes" and a.rate & (a.rate - 1):
         ap.error("--poses keyframes needs a power-of-two --rate")
     if a.frames == "none" and not a.video:
@@ -142,6 +148,7 @@ def main():
             out = E.evaluate_from_folder(G, *dirs, os.path.join(root, "out%d" % rep), gt_dir=os.path.join(root, "gt") if a.metrics else None,
                                          metrics=a.metrics, pose_mask=a.pose_mask, panels=a.panels, panel_encode=a.panel_encode,
                                          background=a.background, video=a.video, frames=a.frames, **kw,
+                                         **({"output_size": a.output_size} if a.output_size != "model" else {}),
                                          **({"mci_range": a.mci_range} if a.background == "mci" else {}),
                                          **({"mci_border": a.mci_border} if a.mci_border != "clamp" else {}),
                                          **({"mci_precision": a.mci_precision} if a.mci_precision != "full" else {}))
@@ -154,7 +161,7 @@ def main():
     print(json.dumps({"height": H, "width": W, "dtype": a.dtype, "frames": n, "generated": gen, "lanes": a.lanes,
                       "batch": a.batch or E.default_batch(), "chunk": a.chunk, "io_threads": E.io_threads, "io_mode": a.io_mode,
                       "cpus": len(os.sched_getaffinity(0)), "cpu_budget": ev.cpu_budget(), "png_compress_level": a.compress,
-                      "src_height": a.src_height or H, "src_width": a.src_width or W, "resize_on": a.resize_on, "background": a.background, "mci_range": a.mci_range if a.background == "mci" else None,
+                      "src_height": a.src_height or H, "src_width": a.src_width or W, "resize_on": a.resize_on, "output_size": a.output_size, "background": a.background, "mci_range": a.mci_range if a.background == "mci" else None,
                       "mci_border": a.mci_border if a.background == "mci" else None,
                       "mci_precision": a.mci_precision if a.background == "mci" else None,
                       "metrics": a.metrics, "pose_mask": a.pose_mask, "metrics_overall": overall, "panels": a.panels, "panel_encode": a.panel_encode,
