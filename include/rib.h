@@ -343,7 +343,24 @@ int rib_jpeg_float(rib_handle* h, int T, int H, int W, const float* src_f32_nchw
  * a `precision` argument is the follow-up (one entry per operation).  The two entries are named rib_halfpel_*, not rib_mci_*: the
  * rib_mci_* family is held at four entries (one per operation and the shape query) by the suite, and the fold brings it back to that.
  * Both: border outside {0, 1}, bad B, H, W, T, sample rate or frame range, NULL or misaligned pointers: RIB_ERR_INVALID with a
- * rib_last_error text, nothing launched. */
+ * rib_last_error text, nothing launched.
+ * rib_scaled_frames (the driver's --output-size keyframes; background.mci_frames_scaled_host, bit-equal): rib_mci_frames' uint8
+ * frames at the key frames' OWN size - "field at the model size, samples at the key frames' size".  a0_u8, b0_u8 uint8 NHWC
+ * [B,H0,W0,3] are the key frame files' pixels, field_i16 the [B,Hb,Wb,2] field of the H x W MODEL-size key frames (Hb = ceil(H/8),
+ * Wb = ceil(W/8); rib_mci_field's with precision = 0, rib_halfpel_refine's with precision = 1) -> out_u8_nhwc uint8
+ * [T,B,H0,W0,3], any byte alignment.  Per output pixel (Y0, X0): (1) TX = ((2 X0 + 1) * 16 W) / W0 - 128 is its centre's position in
+ * 1/256 block from block centre 0 (TY with H, H0), c0 = TX >> 8, fx = TX & 255, c0 and c0 + 1 clamped to the field; (2) D16 = the
+ * bilinear sum of the four vectors with the 8-bit weights, D8 = (D16 + 128) >> 8 in 1/256 model px; (3) DSx = (D8x * SX + 32768) >>
+ * 16 with SX = (W0 * 65536 + W / 2) / W (SY with H0, H; a 64-bit product) in 1/256 px of the output; (4) rib_mci_frames' offsets,
+ * samples, blend and border = 1 rule with DS, H0, W0.  With (H0, W0) == (H, W) the bytes are rib_mci_frames'.  There is no float
+ * output: the generator is fed rib_mci_frames' floats at the model size.  ONE launch on `stream`, no workspace, no atomics, no
+ * synchronisation; every byte written; a frame's bytes do not depend on T or B.  rib_mci_frames' refusals, and also: H0 or W0
+ * outside 1..16384, W0 > 16 W, W > 16 W0 (the same for the heights: beyond a ratio of 16 an offset could leave int32), precision
+ * outside {0, 1}, out NULL: RIB_ERR_INVALID with a rib_last_error text that names the entry, nothing launched.  The field has the
+ * model's resolution - motion detail finer than an 8x8 model block is not followed - and, as above, interior occlusion is not handled. */
+int rib_scaled_frames(rib_handle* h, int T, int B, int H, int W, int H0, int W0, const uint8_t* a0_u8, const uint8_t* b0_u8,
+                      const int16_t* field_i16, int sample_rate, int k_first, int border, int precision, uint8_t* out_u8_nhwc,
+                      void* hip_stream);
 void rib_mci_field_shape(int H, int W, int* Hb, int* Wb);
 size_t rib_mci_workspace_bytes(rib_handle* h, int B, int H, int W, int levels);
 int rib_mci_field(rib_handle* h, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,

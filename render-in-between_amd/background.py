@@ -60,6 +60,12 @@ rib_halfpel_frames) are held bit-equal to them (tests/test_gpu_mci.py, tests/tes
              samples are bilinear and therefore soft; a block whose integer vector is more than one half-pel step from the
              truth stays wrong.
 
+  key frames' size   (mci_frames_scaled_host, the driver's output_size="keyframes"; rib_scaled_frames, tests/test_gpu_mci_scaled.py).  The
+             field stays the model-size one; frame k is sampled from the key frame FILES' own pixels [h0, w0, 3]: a pixel's vector is
+             the bilinear field at its centre's position in the model's block grid, scaled to output pixels by a 16.16 factor, then
+             the lines of "frame k" and "border" above in output coordinates - the function's text has the four steps.  Motion
+             detail finer than a model block is not followed.
+
 No quarter-pel search, no sub-pel search on the coarse levels, and no occlusion reasoning beyond the frame border under
 border="valid" - a foreground object that covers background is not handled: see DESIGN ("Motion-compensated backgrounds") for
 what that costs."""
@@ -460,6 +466,84 @@ def mci_frames_host(a_u8, b_u8, field, sample_rate, ks, border="clamp", precisio
         o = ((s - k) * a + k * b + s // 2) >> ls
         if border == "valid":
             oka, okb = sample_valid(Y - ay, X - ax, H, W)[..., None], sample_valid(Y + by, X + bx, H, W)[..., None]
+            o = np.where(oka == okb, o, np.where(oka, a, b))
+        out[j] = o.astype(np.uint8)
+    return out
+
+
+SCALED_MAX_RATIO = 16     # mci_frames_scaled_host: the key frames' sides are within 1/16 .. 16 times the model's
+SCALED_MAX_SIDE = 16384   # ... and every side lies in 1..16384
+SCALE_FRAC_BITS = 16      # the model -> output scale factors SX, SY are 16.16
+
+
+def scaled_factors(model_hw, out_hw, who="mci_frames_scaled_host"):
+    """(SY, SX) of mci_frames_scaled_host, 16.16: round(h0 / H * 65536), round(w0 / W * 65536); the bounds are checked here."""
+    (H, W), (h0, w0) = (int(v) for v in model_hw), (int(v) for v in out_hw)
+    if not all(1 <= v <= SCALED_MAX_SIDE for v in (H, W, h0, w0)):
+        raise ValueError("%s: every side must lie in 1..%d, got model %dx%d, key frames %dx%d" % (who, SCALED_MAX_SIDE, H, W, h0, w0))
+    if w0 > SCALED_MAX_RATIO * W or W > SCALED_MAX_RATIO * w0 or h0 > SCALED_MAX_RATIO * H or H > SCALED_MAX_RATIO * h0:
+        raise ValueError("%s: the key frames (%dx%d) must be within 1/%d .. %d times the model size (%dx%d) on each axis"
+                         % (who, h0, w0, SCALED_MAX_RATIO, SCALED_MAX_RATIO, H, W))
+    return ((h0 << SCALE_FRAC_BITS) + H // 2) // H, ((w0 << SCALE_FRAC_BITS) + W // 2) // W
+
+
+def pixel_field_scaled(field, model_hw, out_hw):
+    """D(p) of every pixel of an h0 x w0 frame from the block field of the H x W model frame, in 1/256 px of the OUTPUT frame:
+    int16 [Hb, Wb, 2] -> (DSx, DSy) int32 [h0, w0].  Steps 1-3 of mci_frames_scaled_host."""
+    (H, W), (h0, w0) = (int(v) for v in model_hw), (int(v) for v in out_hw)
+    SY, SX = scaled_factors((H, W), (h0, w0))
+    Hb, Wb = field_shape(H, W)
+    if tuple(field.shape) != (Hb, Wb, 2):
+        raise ValueError("mci_frames_scaled_host: the field of a %dx%d model frame is [%d, %d, 2], got %s" % (H, W, Hb, Wb, tuple(field.shape)))
+    f = field.astype(np.int32)
+    ty = ((2 * np.arange(h0, dtype=np.int64) + 1) * H * 16) // h0 - 128      # position in 1/256 block from centre 0
+    tx = ((2 * np.arange(w0, dtype=np.int64) + 1) * W * 16) // w0 - 128
+    r0, fy = ty >> 8, (ty & 255).astype(np.int32)[:, None, None]
+    c0, fx = tx >> 8, (tx & 255).astype(np.int32)[None, :, None]
+    r1, r0 = np.clip(r0 + 1, 0, Hb - 1), np.clip(r0, 0, Hb - 1)
+    c1, c0 = np.clip(c0 + 1, 0, Wb - 1), np.clip(c0, 0, Wb - 1)
+    d16 = (256 - fy) * ((256 - fx) * f[r0][:, c0] + fx * f[r0][:, c1]) + fy * ((256 - fx) * f[r1][:, c0] + fx * f[r1][:, c1])
+    d8 = ((d16 + 128) >> 8).astype(np.int64)                                  # 1/256 model px
+    dsx = ((d8[..., 0] * SX + (1 << 15)) >> SCALE_FRAC_BITS).astype(np.int32)
+    dsy = ((d8[..., 1] * SY + (1 << 15)) >> SCALE_FRAC_BITS).astype(np.int32)
+    return dsx, dsy
+
+
+def mci_frames_scaled_host(a0_u8, b0_u8, field, model_hw, sample_rate, ks, border="clamp", precision="full"):
+    """mci_frames_host at the key frames' OWN size: "field at the model size, samples at the key frames' size".  a0_u8, b0_u8
+    uint8 [h0, w0, 3] are the key frame files' pixels, field the int16 [Hb, Wb, 2] block field of the model-size key frames
+    (mci_field_host / mci_refine_host of the H x W frames, model_hw = (H, W)) -> uint8 [len(ks), h0, w0, 3].  Per output pixel
+    (Y0, X0):
+      1  TX = ((2 X0 + 1) * W * 16) // w0 - 128, the pixel centre's position in 1/256 block from block centre 0 (TY with H, h0);
+         c0 = TX >> 8, fx = TX & 255, c0 and c0 + 1 clamped to the field (rows the same);
+      2  D16 = (256-fy) ((256-fx) f00 + fx f01) + fy ((256-fx) f10 + fx f11) per component, D8 = (D16 + 128) >> 8: 1/256 model px;
+      3  SX = (w0 * 65536 + W // 2) // W (SY with h0, H), DSx = (D8x * SX + 32768) >> 16 (64-bit product): 1/256 px of the output;
+      4  mci_frames_host's lines with DSx, DSy, h0, w0: offsets (unit k DS + s/2) >> log2 s, sample_bilinear, the blend, and under
+         border="valid" sample_valid in output coordinates.
+    With (h0, w0) == (H, W) it is mci_frames_host, byte for byte.  The sides lie in 1..16384 and within a factor 16 of the
+    model's (the largest unit * k * DS then stays below 2^31)."""
+    check_border(border, "mci_frames_scaled_host")
+    unit = 1 if check_precision(precision, "mci_frames_scaled_host") == "half" else 2
+    a0_u8, b0_u8, field = np.asarray(a0_u8), np.asarray(b0_u8), np.asarray(field)
+    if a0_u8.dtype != np.uint8 or a0_u8.ndim != 3 or a0_u8.shape[2] != 3 or a0_u8.shape != b0_u8.shape or b0_u8.dtype != np.uint8:
+        raise ValueError("mci_frames_scaled_host: two uint8 [h0, w0, 3] frames of one size, got %s and %s" % (a0_u8.shape, b0_u8.shape))
+    s, ls = int(sample_rate), log2_rate(sample_rate)
+    h0, w0 = a0_u8.shape[:2]
+    Dx, Dy = pixel_field_scaled(field, model_hw, (h0, w0))
+    Y, X = np.mgrid[0:h0, 0:w0]
+    Y, X = (Y << SAMPLE_FRAC_BITS).astype(np.int32), (X << SAMPLE_FRAC_BITS).astype(np.int32)
+    out = np.empty((len(ks), h0, w0, 3), np.uint8)
+    for j, k in enumerate(ks):
+        k = int(k)
+        if not 0 <= k <= s:
+            raise ValueError("mci_frames_scaled_host: frame %d is outside the segment 0..%d" % (k, s))
+        ax, ay = (unit * k * Dx + s // 2) >> ls, (unit * k * Dy + s // 2) >> ls
+        bx, by = (unit * (s - k) * Dx + s // 2) >> ls, (unit * (s - k) * Dy + s // 2) >> ls
+        a = sample_bilinear(a0_u8, Y - ay, X - ax)
+        b = sample_bilinear(b0_u8, Y + by, X + bx)
+        o = ((s - k) * a + k * b + s // 2) >> ls
+        if border == "valid":
+            oka, okb = sample_valid(Y - ay, X - ax, h0, w0)[..., None], sample_valid(Y + by, X + bx, h0, w0)[..., None]
             o = np.where(oka == okb, o, np.where(oka, a, b))
         out[j] = o.astype(np.uint8)
     return out

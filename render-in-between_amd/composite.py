@@ -24,7 +24,7 @@ import numpy as np
 
 from . import panel, resize
 
-OUTPUT_SIZES = ("model", "source")
+OUTPUT_SIZES = ("model", "source", "keyframes")      # "keyframes": background="mci" at the size of the key frame files
 
 
 def check_output_size(value, who="output_size"):

@@ -526,4 +526,57 @@ int rib_halfpel_frames(rib_handle* handle, int T, int B, int H, int W, const uin
   return mci_frames_enqueue("rib_halfpel_frames", true, handle, T, B, H, W, a_u8, b_u8, field_half_i16, sample_rate, k_first, border,
                             out_f32_nchw, out_u8_nhwc, hip_stream);
 }
+
+// rib_scaled_frames: rib_mci_frames' uint8 output at the key frames' own size H0 x W0 from the MODEL-size (H x W) field
+int rib_scaled_frames(rib_handle* handle, int T, int B, int H, int W, int H0, int W0, const uint8_t* a0_u8, const uint8_t* b0_u8,
+                      const int16_t* field_i16, int sample_rate, int k_first, int border, int precision, uint8_t* out_u8_nhwc,
+                      void* hip_stream) {
+  static const char who[] = "rib_scaled_frames";
+  constexpr int MAX_RATIO = 16;             // background.SCALED_MAX_RATIO: the largest unit * k * DS stays below 2^31
+  FrameState* h = frame_state(handle);
+  if (!h) return RIB_ERR_INVALID;
+  if (h->device < 0) return fail(h, RIB_ERR_INVALID, fmt("%s: host-only handle", who));
+  if (!a0_u8 || !b0_u8 || !field_i16 || !out_u8_nhwc) return fail(h, RIB_ERR_INVALID, fmt("%s: null pointer", who));
+  MciLayout L;
+  if (T < 1 || !mci_layout(B, H, W, MCI_MIN_LEVELS, &L) || (size_t)T * B > 65535)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: T=%d B=%d H=%d W=%d: T, B >= 1, T * B <= 65535, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", who, T, B, H, W, MCI_MAX_SIDE));
+  if (H0 < 1 || W0 < 1 || H0 > MCI_MAX_SIDE || W0 > MCI_MAX_SIDE)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: H0=%d W0=%d: the key frames' sides lie in 1..%d", who, H0, W0, MCI_MAX_SIDE));
+  if (W0 > MAX_RATIO * W || W > MAX_RATIO * W0 || H0 > MAX_RATIO * H || H > MAX_RATIO * H0)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: key frames %dx%d, model %dx%d: each axis within 1/%d .. %d times the model's", who, H0, W0, H, W, MAX_RATIO, MAX_RATIO));
+  if (sample_rate < 1 || sample_rate > MCI_MAX_RATE || (sample_rate & (sample_rate - 1)) != 0)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: sample_rate=%d: a power of two in 1..%d", who, sample_rate, MCI_MAX_RATE));
+  if (k_first < 0 || k_first + T - 1 > sample_rate)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: frames %d..%d are outside the segment 0..%d", who, k_first, k_first + T - 1, sample_rate));
+  if (border != 0 && border != 1)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: border=%d: 0 (clamped samples) or 1 (valid samples only)", who, border));
+  if (precision != 0 && precision != 1)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: precision=%d: 0 (the field in pixels) or 1 (in half pixels)", who, precision));
+  if ((reinterpret_cast<uintptr_t>(field_i16) & 1) != 0) return fail(h, RIB_ERR_INVALID, fmt("%s: misaligned pointer", who));
+  ScaledFramesParams fp;
+  fp.a = a0_u8; fp.b = b0_u8; fp.field = field_i16; fp.out = out_u8_nhwc;
+  fp.T = T; fp.B = B; fp.H0 = H0; fp.W0 = W0; fp.Hb = L.Hb[0]; fp.Wb = L.Wb[0]; fp.s = sample_rate; fp.k_first = k_first;
+  fp.ls = 0;
+  while ((1 << fp.ls) < sample_rate) ++fp.ls;
+  fp.sx = (int)(((int64_t)W0 * 65536 + W / 2) / W); fp.sy = (int)(((int64_t)H0 * 65536 + H / 2) / H);
+  fp.qax = 32 * W / W0; fp.rax = 32 * W % W0; fp.q0x = 16 * W / W0; fp.r0x = 16 * W % W0;
+  fp.qay = 32 * H / H0; fp.ray = 32 * H % H0; fp.q0y = 16 * H / H0; fp.r0y = 16 * H % H0;
+  fp.vec = (W0 % 4 == 0 && (reinterpret_cast<uintptr_t>(out_u8_nhwc) & 3) == 0) ? 1 : 0;
+  fp.v_off = (W0 * 3 + 31) & ~15;           // the row at any shift 0..15, whole 16-byte lines
+  const size_t with_field = (size_t)fp.v_off + (size_t)fp.Wb * sizeof(int2);
+  fp.stage = with_field <= 65536 ? 1 : 0;
+  const size_t lds = fp.stage ? with_field : (size_t)fp.v_off;
+  HIP_TRY(h, hipSetDevice(h->device));
+  const dim3 grid(H0, T * B);
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  if (precision) {
+    if (border) hipLaunchKernelGGL((k_scaled_frames<true, true>), grid, dim3(256), lds, st, fp);
+    else hipLaunchKernelGGL((k_scaled_frames<false, true>), grid, dim3(256), lds, st, fp);
+  } else {
+    if (border) hipLaunchKernelGGL((k_scaled_frames<true, false>), grid, dim3(256), lds, st, fp);
+    else hipLaunchKernelGGL((k_scaled_frames<false, false>), grid, dim3(256), lds, st, fp);
+  }
+  HIP_TRY(h, hipGetLastError());
+  return RIB_OK;
+}
 }  // extern "C"

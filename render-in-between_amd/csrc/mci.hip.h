@@ -1,7 +1,9 @@
 // mci.hip.h — motion-compensated interpolation of a segment's two key frames: the folder driver's background="mci"
-// (rib_mci_field / rib_halfpel_refine / rib_mci_frames / rib_halfpel_frames, include/rib.h).  This project's interpolation, not DAIN.
+// (rib_mci_field / rib_halfpel_refine / rib_mci_frames / rib_halfpel_frames, and rib_scaled_frames for output_size="keyframes";
+// include/rib.h).  This project's interpolation, not DAIN.
 //
-// background.py (mci_field_host, mci_refine_host, mci_frames_host) states the result in integers; every kernel here is bit-equal to it.
+// background.py (mci_field_host, mci_refine_host, mci_frames_host, mci_frames_scaled_host) states the result in integers; every kernel
+// here is bit-equal to it.
 //
 //   k_mci_luma_pyramid  grid (tiles of 32 x 32, 2B): luma Y = (77 R + 150 G + 29 B + 128) >> 8 of one tile and, from LDS, its
 //                       16 x 16 of level 1 and 8 x 8 of level 2 ((2x2 parents, clamped, + 2) >> 2) - and, where a wider search
@@ -44,6 +46,16 @@
 //                       the two is, the output is that sample instead of the blend (four comparisons per sample, a select).
 //                       <VALID, HALF = true> (rib_halfpel_frames): the field is in half pixels, the offsets k D / s and
 //                       (s-k) D / s; the multiplier is a compile-time constant, <VALID, false> is the code it was.
+//   k_scaled_frames     (rib_scaled_frames; background.mci_frames_scaled_host) grid (H0, T * B): k_mci_frames at the key frames' OWN
+//                       size H0 x W0 - the field stays the model-size one (H x W), the samples are taken from the full-size key
+//                       frames.  The row's TY, r0, r1, fy are uniform per workgroup, so the two field rows it needs are blended
+//                       vertically ONCE, V[c] = (256-fy) f[r0][c] + fy f[r1][c] (exact: integers), into LDS - Wb (dx, dy) int32 pairs,
+//                       at most 16 KB - and a pixel reads two of them: D16 = (256-fx) V[c0] + fx V[c1], the definition's sum in another
+//                       order.  TX = ((2 X0 + 1) 16 W) // W0 - 128 would need 33 bits; it is X0 * qa + q0 + (X0 * ra + r0) // W0 with
+//                       qa, ra = divmod(32 W, W0) and q0, r0 = divmod(16 W, W0) from the host, every term below 2^29: one 32-bit
+//                       division per thread, its three further x by adding.  The two 64-bit products D8 * SX, D8 * SY (16.16 factors
+//                       from the host) are the only wide arithmetic.  uint8 NHWC output only, through LDS as 16-byte stores like
+//                       k_mci_frames.  stage = 0 (row + field rows beyond 64 KB of LDS: both widths above 16 376): V from global.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -465,6 +477,109 @@ __global__ __launch_bounds__(256) void k_mci_frames(MciFramesParams p) {
     }
   }
   if (!grow) return;                        // (uniform: no thread reaches the barrier)
+  __syncthreads();
+  const int nlines = (shift + rowbytes + 15) >> 4;
+  uint8_t* gline = grow - shift;            // 16-byte aligned; only bytes [shift, shift + rowbytes) are this row's
+  for (int j = threadIdx.x; j < nlines; j += 256) {
+    const int lo = j * 16;
+    if (lo >= shift && lo + 16 <= shift + rowbytes) {
+      *reinterpret_cast<uint4*>(gline + lo) = reinterpret_cast<const uint4*>(s_mci)[j];
+    } else {
+      for (int kk = max(lo, shift); kk < min(lo + 16, shift + rowbytes); ++kk) gline[kk] = s_mci[kk];
+    }
+  }
+}
+
+struct ScaledFramesParams {
+  const uint8_t *a, *b;                     // [B, H0, W0, 3]: the key frames at their own size
+  const int16_t* field;                     // [B, Hb, Wb, 2]: the block field of the MODEL-size key frames
+  uint8_t* out;                             // [T, B, H0, W0, 3]
+  int T, B, H0, W0, Hb, Wb, s, ls, k_first;
+  int sx, sy;                               // 16.16: (W0 * 65536 + W / 2) / W, (H0 * 65536 + H / 2) / H
+  int qax, rax, q0x, r0x;                   // divmod(32 W, W0), divmod(16 W, W0)
+  int qay, ray, q0y, r0y;                   // divmod(32 H, H0), divmod(16 H, H0)
+  int vec;                                  // W0 % 4 == 0 and out 4-byte aligned: dword LDS writes
+  int stage;                                // the blended field row fits in LDS beside the output row
+  int v_off;                                // its byte offset in the dynamic LDS (a multiple of 16)
+};
+
+template <bool VALID = false, bool HALF = false>
+__global__ __launch_bounds__(256) void k_scaled_frames(ScaledFramesParams p) {
+  constexpr int UNIT = HALF ? 1 : 2;
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_mci[];
+  const int y = blockIdx.x, tb = blockIdx.y, t = tb / p.B, bi = tb - t * p.B;
+  const int H0 = p.H0, W0 = p.W0, k = p.k_first + t, s = p.s, ls = p.ls;
+  const int rowbytes = W0 * 3;
+  uint8_t* grow = p.out + ((size_t)tb * H0 + y) * (size_t)rowbytes;
+  const int shift = (int)(reinterpret_cast<uintptr_t>(grow) & 15);
+  uint8_t* srow = s_mci + shift;
+  int2* sV = reinterpret_cast<int2*>(s_mci + p.v_off);
+  const uint8_t* A = p.a + (size_t)bi * H0 * W0 * 3;
+  const uint8_t* Bf = p.b + (size_t)bi * H0 * W0 * 3;
+  const int16_t* fld = p.field + (size_t)bi * p.Hb * p.Wb * 2;
+  // TY = ((2 y + 1) * 16 H) / H0 - 128 without 33 bits: y * ray + r0y < 2^28 + 2^14
+  const int tyy = y * p.qay + p.q0y + (int)((unsigned)(y * p.ray + p.r0y) / (unsigned)H0) - 128, fy = tyy & 255;
+  const int r0 = min(max(tyy >> 8, 0), p.Hb - 1), r1 = min(max((tyy >> 8) + 1, 0), p.Hb - 1);
+  const int16_t *frow0 = fld + (size_t)r0 * p.Wb * 2, *frow1 = fld + (size_t)r1 * p.Wb * 2;
+  if (p.stage) {
+    for (int c = threadIdx.x; c < p.Wb; c += 256)
+      sV[c] = make_int2((256 - fy) * frow0[2 * c] + fy * frow1[2 * c], (256 - fy) * frow0[2 * c + 1] + fy * frow1[2 * c + 1]);
+    __syncthreads();
+  }
+  const int W4 = (W0 + 3) >> 2;
+  for (int item = threadIdx.x; item < W4; item += 256) {
+    const int x0 = item * 4;
+    const unsigned num = (unsigned)(x0 * p.rax + p.r0x);
+    int tq = x0 * p.qax + p.q0x + (int)(num / (unsigned)W0) - 128;      // TX of x0
+    int trem = (int)(num % (unsigned)W0);
+    uint8_t q[12];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int x = x0 + j;                 // (x >= W0 in the last item: every index below is clamped, nothing of it is stored)
+      const int fx = tq & 255;
+      const int c0 = min(max(tq >> 8, 0), p.Wb - 1), c1 = min(max((tq >> 8) + 1, 0), p.Wb - 1);
+      tq += p.qax; trem += p.rax;           // TX of x + 1
+      if (trem >= W0) { trem -= W0; ++tq; }
+      int2 v0, v1;
+      if (p.stage) {
+        v0 = sV[c0]; v1 = sV[c1];
+      } else {
+        v0 = make_int2((256 - fy) * frow0[2 * c0] + fy * frow1[2 * c0], (256 - fy) * frow0[2 * c0 + 1] + fy * frow1[2 * c0 + 1]);
+        v1 = make_int2((256 - fy) * frow0[2 * c1] + fy * frow1[2 * c1], (256 - fy) * frow0[2 * c1 + 1] + fy * frow1[2 * c1 + 1]);
+      }
+      const int D8x = ((256 - fx) * v0.x + fx * v1.x + 128) >> 8, D8y = ((256 - fx) * v0.y + fx * v1.y + 128) >> 8;      // 1/256 model px
+      const int Dx = (int)(((long long)D8x * p.sx + 32768) >> 16), Dy = (int)(((long long)D8y * p.sy + 32768) >> 16);   // 1/256 output px
+      const int ax = (UNIT * k * Dx + (s >> 1)) >> ls, ay = (UNIT * k * Dy + (s >> 1)) >> ls;
+      const int bx = (UNIT * (s - k) * Dx + (s >> 1)) >> ls, by = (UNIT * (s - k) * Dy + (s >> 1)) >> ls;
+      const int pay = (y << 8) - ay, pax = (x << 8) - ax, pby = (y << 8) + by, pbx = (x << 8) + bx;
+      int va[3], vb[3];
+      mci_sample(A, H0, W0, pay, pax, va);
+      mci_sample(Bf, H0, W0, pby, pbx, vb);
+      if constexpr (VALID) {
+        const int ymax = (H0 - 1) << 8, xmax = (W0 - 1) << 8;
+        const bool oka = pay >= 0 && pay <= ymax && pax >= 0 && pax <= xmax, okb = pby >= 0 && pby <= ymax && pbx >= 0 && pbx <= xmax;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const int blend = ((s - k) * va[c] + k * vb[c] + (s >> 1)) >> ls;
+          q[j * 3 + c] = (uint8_t)(oka == okb ? blend : oka ? va[c] : vb[c]);
+        }
+      } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) q[j * 3 + c] = (uint8_t)(((s - k) * va[c] + k * vb[c] + (s >> 1)) >> ls);
+      }
+    }
+    uint8_t* dst = srow + x0 * 3;
+    if (p.vec) {
+#pragma unroll
+      for (int d = 0; d < 3; ++d)
+        reinterpret_cast<uint32_t*>(dst)[d] = (uint32_t)q[4 * d] | ((uint32_t)q[4 * d + 1] << 8) | ((uint32_t)q[4 * d + 2] << 16) | ((uint32_t)q[4 * d + 3] << 24);
+    } else {
+      const int nb = min(4, W0 - x0) * 3;
+#pragma unroll
+      for (int j = 0; j < 12; ++j)
+        if (j < nb) dst[j] = q[j];
+    }
+  }
   __syncthreads();
   const int nlines = (shift + rowbytes + 15) >> 4;
   uint8_t* gline = grow - shift;            // 16-byte aligned; only bytes [shift, shift + rowbytes) are this row's

@@ -253,14 +253,15 @@ def section_views(flat, spec, table):
 
 
 def staging_spec(Tc, Bc, model_hw, src_dain=None, src_gt=None, want_gt=False, masks=False, keys=False, mci=False, mci_keys=False,
-                 src_keys=None):
+                 src_keys=None, mci_keys_src=None):
     """The spec of a unit's staging block, which the decode tasks fill and upload() sends to the GPU (DESIGN 4e has the table):
     Tc time steps of Bc segments at the model size (H, W).  src_dain / src_gt: (w0, h0) at which that list is staged for the
     GPU resize (resize_on="gpu"), None: the model size; want_gt, masks: ground-truth frames / masks are staged; keys: a first
     chunk under panels, the DAIN frames of the key frames it starts from; mci: background="mci", no DAIN bytes at all;
     mci_keys: its first chunk, the group's left and right key frames.  src_keys: (w0, h0) - a first chunk under
     output_size="source" with video, the key frames it starts from at the output size, for their video files; the section
-    `key_src` exists in the spec only then."""
+    `key_src` exists in the spec only then.  mci_keys_src: (w0, h0) - a group's first chunk under output_size="keyframes", its
+    left and right key frames' own pixels for rib_scaled_frames; the section `mci_keys_src` exists only then, after `key_src`."""
     H, W = model_hw
     (wd, hd), (wg, hg) = src_dain or (W, H), src_gt or (W, H)
     spec = (("dain", torch.uint8, (Tc, Bc, hd, wd, 3), not mci),
@@ -270,6 +271,8 @@ def staging_spec(Tc, Bc, model_hw, src_dain=None, src_gt=None, want_gt=False, ma
             ("mci_keys", torch.uint8, (2, Bc, H, W, 3), mci and mci_keys))
     if src_keys is not None:
         spec += (("key_src", torch.uint8, (Bc, src_keys[1], src_keys[0], 3), True),)
+    if mci_keys_src is not None:
+        spec += (("mci_keys_src", torch.uint8, (2, Bc, mci_keys_src[1], mci_keys_src[0], 3), True),)
     return spec
 
 
@@ -652,7 +655,18 @@ class Evaluator:
         (mixed sizes, shared-memory budget) is an error before any of its files is written.  A model behind the reference's
         protocol decodes each DAIN file once more at its own size and goes through composite_host, and its generator is fed the
         background floats the native chain reads (background.normalised_upload, as under background="mci"): the same files.
-        background="mci" is not supported with it (the interpolation runs at the model size)."""
+        background="mci" is not supported with it (the interpolation runs at the model size): that is output_size="keyframes".
+        output_size="keyframes" (a setting of background="mci"): the same at the key frames' size - the files are written at
+        the uniform size (w0, h0) of the clip's key frame files (a clip with mixed sizes is an error before any of its files is
+        written; so is one whose larger blocks do not fit the shared memory).  The field stays exactly the model-size one
+        (mci_field_host / mci_refine_host of the host-resized keys) and the chain reads the floats it reads under "model"; only
+        the background pixels are sampled from the full-size key frames (background.mci_frames_scaled_host: the field at the
+        model size, the samples at the key frames' size), an in-between frame is composite_host of the chain's image and mask
+        over them and a key frame is its file's own pixels.  On the native path a group's first chunk also stages the key
+        files' own pixels (`mci_keys_src`), one rib_scaled_frames launch per unit on the upload stream makes the unit's
+        backgrounds, and render, composite, PNG workers and video are the code of "source".  It is this project's
+        interpolation, not DAIN; motion detail finer than an 8x8 model block is not followed; the person is a cubic
+        enlargement; no interior occlusion reasoning; unmeasured on real footage."""
         if poses not in ("folder", "keyframes", "keyframes-linear"):
             raise ValueError("evaluate_from_folder: poses must be 'folder', 'keyframes' or 'keyframes-linear', got %r" % (poses,))
         if poses == "folder" and (key_pose_dir is not None or upsample_rate != 8 or motion is not None or save_poses):
@@ -668,7 +682,10 @@ class Evaluator:
         _composite.check_output_size(output_size, "evaluate_from_folder")
         if output_size == "source" and background == "mci":
             raise ValueError("evaluate_from_folder: output_size='source' with background='mci' is not supported: the interpolation "
-                             "runs at the model size (a source-size interpolation is a follow-up)")
+                             "runs at the model size (a source-size interpolation is a follow-up); use output_size='keyframes'")
+        if output_size == "keyframes" and background != "mci":
+            raise ValueError("evaluate_from_folder: output_size='keyframes' is a setting of background='mci' (the size of the key "
+                             "frame files); with DAIN frames use output_size='source'")
         if gen_vid:
             # the reference also writes <save_dir>/<clip>.mp4 (evaluator.py:267-269, utils.make_video) from a matplotlib canvas
             # through an H.264 encoder; neither is built, and silently ignoring the flag would drop an output the caller asked for
@@ -768,13 +785,15 @@ class _Clip:
         self.sheet_futs = []                # futures of sheet files that ride in no unit's sink
         # background="mci": key frame index -> its uint8 HWC bytes as decoded and resized (filled by the decode tasks);
         # group -> (left keys, right keys uint8 [B,H,W,3], field int16 [B,Hb,Wb,2]) on the device, made in the group's first
-        # chunk and kept for its later chunks beside prev_of; both are released at the end of run_native / run_reference
+        # chunk and kept for its later chunks beside prev_of (output_size="keyframes": + the left and right keys' own pixels uint8
+        # [B,h0,w0,3], else None, None); both are released at the end of run_native / run_reference
         self.key_u8, self.mci_of = {}, {}
         # video: the folder of the frames' .jpg files; out_names: what drain() reports for every frame index - the PNG, or under
         # frames="none" the .jpg
         self.video_dir = None
         self.out_names = names
-        # output_size="source": (w0, h0) of the clip's files, the uniform size of its DAIN frames; key_src: key frame index ->
+        # output_size="source" / "keyframes": (w0, h0) of the clip's files, the uniform size of its DAIN frames / of its key frame
+        # files (under "keyframes" src_of's staged frames are rib_scaled_frames' backgrounds); key_src: key frame index ->
         # future of its uint8 HWC pixels at that size (the key file's own, resized only if its size differs); src_of: unit ->
         # (the staged DAIN frames uint8 [Tc,B,h0,w0,3], a first chunk's key frames uint8 [B,h0,w0,3] or None) on the device
         self.out_size = None
@@ -816,7 +835,10 @@ class _FolderPipeline:
                  panels=False, panel_frames=False, panel_quality=90, panel_encode="host", background="dain", mci_levels=3,
                  video=False, video_quality=90, video_frames=False, write_png=True, key_poses=None, mci_border="clamp", mci_precision="full",
                  output_size="model"):
-        self.source = output_size == "source"      # composite.py: the frames' files at the clip's source size
+        # composite.py: the frames' files at the clip's own size - the DAIN frames' ("source") or, under background="mci", the key
+        # frame files' ("keyframes": keysize; the backgrounds are then rib_scaled_frames', everything after them is "source"'s code)
+        self.source = output_size in ("source", "keyframes")
+        self.keysize = output_size == "keyframes"
         self.mci, self.mci_levels = background == "mci", mci_levels      # (levels: background.mci_field_host's, from mci_range)
         self.mci_border = mci_border        # background.py's border
         self.mci_half = mci_precision == "half"      # background.py's precision: the field is refined once per group, in half pixels
@@ -845,8 +867,10 @@ class _FolderPipeline:
             raise RuntimeError("panel_encode='gpu': this model has no GPU JPEG kernels (rib_jpeg)")
         if self.native and video and not hasattr(model, "jpeg_f32_into"):
             raise RuntimeError("video=True: this model has no GPU JPEG kernels for float frames (rib_jpeg_float)")
+        if self.keysize and self.native and not hasattr(model, "mci_frames_scaled"):
+            raise RuntimeError("output_size='keyframes': this model has no GPU kernel for the key frames' size (rib_scaled_frames)")
         if self.source and self.native:
-            if ev.resize_on != "gpu":
+            if ev.resize_on != "gpu" and not self.keysize:
                 raise ValueError("output_size='source' needs resize_on='gpu' on the native path: the background frames' source-size "
                                  "bytes are on the device only there (Evaluator(resize_on='gpu'), inference.py --resize-on gpu)")
             if not hasattr(model, "composite"):
@@ -862,6 +886,7 @@ class _FolderPipeline:
             self.sheet_hw = (sh, sw)
             self.titles = _panel.title_bitmap(ev.width)
             self.titles_dev = None           # ... on the device, uploaded once (native path)
+        self.per_slot = per_slot
         self.procs = _process_pool(ev.io_threads) if (self.native and ev.io_mode == "process" and ev._shm_fits(per_slot)) else None
         self.pool, self.finishers = ev._pool, ev._finishers
         self.level = ev.png_compress_level
@@ -932,6 +957,12 @@ class _FolderPipeline:
         u8 = _composite.composite_host(img.detach().cpu().float().numpy(), mask.detach().cpu().float().numpy(), bg[None])[0]
         return self.save_u8(clip, i, u8)
 
+    def save_keysize_host(self, clip, i, img, mask, bg):
+        """output_size="keyframes" behind the reference's protocol: frame i's files from the model's predicted image and blend mask
+        and bg uint8 [h0,w0,3], its frame of background.mci_frames_scaled_host (composite.composite_host)."""
+        u8 = _composite.composite_host(img.detach().cpu().float().numpy(), mask.detach().cpu().float().numpy(), bg[None])[0]
+        return self.save_u8(clip, i, u8)
+
     # ---- stage 0: plan ---------------------------------------------------------------------------------------------------
     def interpolate_poses(self, sub, n_key, save_dir):
         """poses="keyframes": stage 1 for one clip -> (the [19, 3] keypoint array of every frame, the sample rate).  Every rank
@@ -969,7 +1000,7 @@ class _FolderPipeline:
             sample_rate = sample_rate_of(len(pose_list), len(image_list))
         seq_len = (len(image_list) - 1) * sample_rate + 1
         out_size = None
-        if self.source:                      # one size per clip, read from the headers before anything of the clip is written
+        if self.source and not self.keysize:      # one size per clip, read from the headers before anything of the clip is written
             kinds = sorted({tuple(self.image_size(p)) for p in dain_list[:seq_len]})
             if len(kinds) != 1:
                 raise ValueError("output_size='source': clip %s: the DAIN frames have mixed sizes (%s); the clip's files need one size"
@@ -993,6 +1024,14 @@ class _FolderPipeline:
                 mask_list = _list(os.path.join(self.mask_dir, sub), ("jpg", "png"))
                 if len(mask_list) < seq_len:
                     raise ValueError("metrics: %s has %d masks, the clip has %d frames" % (os.path.join(self.mask_dir, sub), len(mask_list), seq_len))
+        if self.keysize:                     # the size of the key frame files (every rank reads all of the clip's: one answer)
+            key_files = [gtlist[i] if gtlist is not None else image_list[i // sample_rate] for i in range(0, seq_len, sample_rate)]
+            kinds = sorted({tuple(self.image_size(p)) for p in key_files})
+            if len(kinds) != 1:
+                raise ValueError("output_size='keyframes': clip %s: the key frames have mixed sizes (%s); the clip's files need one size"
+                                 % (sub, ", ".join("%dx%d" % k for k in kinds[:4])))
+            out_size = kinds[0]
+            _background.scaled_factors((ev.height, ev.width), (out_size[1], out_size[0]), "output_size='keyframes': clip %s" % sub)
         keys, segs = split_segments(seq_len, sample_rate)
         # this rank's share: a segment is one unit of the deal and brings the key frame it starts from along (that frame is
         # decoded for the chain anyway); a key frame without a segment (the last one) is a unit of its own
@@ -1045,6 +1084,20 @@ class _FolderPipeline:
                                  "would not be on the device: %s" % (sub, "; ".join(r_ for n_, r_ in why if n_ == "DAIN") or "no reason given"))
             for name, reason in why:
                 print("resize_on='gpu': clip {}: the {} list falls back to the host resize: {}".format(sub, name, reason))
+        if self.keysize and units and self.procs is not None:
+            # the blocks at the key frames' size count, as "source" counts its own: a first chunk stages both key frames of every
+            # segment (with video the left ones once more), the download block a frame per slot - beside the model-size staging
+            # that _shm_fits counted.  A clip that does not fit is an error, never a silent change of size
+            w0, h0 = out_size
+            slots = max((c1 - c0) * len(members) for _, members, c0, c1 in units)
+            width = max(len(members) for _, members, _, _ in units)
+            need = shm_windows_bytes(int(slots * ev.height * ev.width * 3 * self.per_slot) + (2 + bool(self.video)) * width * w0 * h0 * 3
+                                     + (slots * w0 * h0 * 3 if self.write_png else 0))
+            free = _shm_free_bytes()
+            if need > free:
+                raise ValueError("output_size='keyframes': clip %s: the staging windows at %dx%d need %.0f MB of shared memory, %.0f MB "
+                                 "are free (a smaller chunk or batch needs less; io_mode='thread' needs none)"
+                                 % (sub, w0, h0, need / 1e6, free / 1e6))
         self.clips.append(clip)
         return clip
 
@@ -1053,7 +1106,7 @@ class _FolderPipeline:
         """Pre-load of frame i on a pool thread (evaluator.py:205-235)."""
         ev = self.ev
         staged_raw = i in clip.slot and clip.src_dain is not None
-        if self.source and not self.native:
+        if self.source and not self.native and not self.mci:
             # output_size="source" is held to the native path's files, and that path exists under resize_on="gpu" only: a model behind
             # the reference's protocol reads the very floats that chain reads (the device's normalisation, as under background="mci")
             dain = torch.from_numpy(_background.normalised_upload(ev._decode_resized_u8(clip.dain_list[i])[0]))
@@ -1135,7 +1188,8 @@ class _FolderPipeline:
             return
         clip.loads[i] = self.decode_in_worker(clip, i) if self.procs is not None else self.pool.submit(self.decode_here, clip, i)
         # key frames pass through (evaluator.py:240-244); native path under frames="none": their only file comes from the GPU
-        if self.source and i in clip.keys and i not in clip.key_src:
+        # (output_size="keyframes": every key frame a segment of this rank touches - the right ones too - for rib_scaled_frames)
+        if self.source and (i in clip.keys or (self.keysize and i % clip.sample_rate == 0)) and i not in clip.key_src:
             clip.key_src[i] = self.pool.submit(self.key_source_u8, clip, i)
         if i in clip.keys and i not in clip.futs and (self.write_png or not self.native):
             if self.source:                      # the key file's own pixels (the future is held here: the clip's table is cleared early)
@@ -1155,7 +1209,8 @@ class _FolderPipeline:
             # one block per unit; a later chunk under background="mci" may stage nothing at all and still gets its byte
             spec = staging_spec(c1 - c0, len(members), (ev.height, ev.width), clip.src_dain, clip.src_gt, want_gt=clip.want_gt,
                                 masks=clip.mask_list is not None, keys=self.panels and c0 == 0, mci=self.mci, mci_keys=c0 == 0,
-                                src_keys=clip.out_size if (self.source and self.video and c0 == 0) else None)
+                                src_keys=clip.out_size if (self.source and self.video and c0 == 0) else None,
+                                mci_keys_src=clip.out_size if (self.keysize and c0 == 0) else None)
             table, total = block_layout(spec_bytes(spec))
             # worker processes: shared with them and page-locked (size classes of 1 MB: the block may be larger than the unit)
             blk = _shm_get(max(1, total)) if self.procs is not None else None
@@ -1215,12 +1270,21 @@ class _FolderPipeline:
                     field = g.mci_field(kab[0], kab[1], self.mci_levels, border=self.mci_border)
                     if self.mci_half:           # one more launch behind the field's, on the same stream; in place
                         field = g.mci_refine(kab[0], kab[1], field, border=self.mci_border, out=field)
-                    clip.mci_of[gi] = (kab[0], kab[1], field)
-                ka, kb, field = clip.mci_of[gi]
+                    kab0 = (None, None)
+                    if self.keysize:            # the key files' own pixels, beside the field: what the unit's backgrounds are sampled from
+                        for b, k in enumerate(ks):
+                            views["mci_keys_src"][0, b].copy_(torch.from_numpy(clip.key_src[k].result(timeout=IO_TIMEOUT_S)))
+                            views["mci_keys_src"][1, b].copy_(torch.from_numpy(clip.key_src[k + clip.sample_rate].result(timeout=IO_TIMEOUT_S)))
+                        kab0 = views["mci_keys_src"].to(g.device, non_blocking=True)
+                    clip.mci_of[gi] = (kab[0], kab[1], field, kab0[0], kab0[1])
+                ka, kb, field, ka0, kb0 = clip.mci_of[gi]
                 dn = g.mci_frames(ka, kb, field, clip.sample_rate, k_first=c0 + 1, count=Tc, normalised="both" if self.panels else True,
                                   border=self.mci_border, precision="half" if self.mci_half else "full")
                 if self.panels:
                     dn, dnu8 = dn
+                if self.keysize:               # ONE launch: the unit's backgrounds uint8 [Tc,B,h0,w0,3], "source"'s staged frames
+                    staged = g.mci_frames_scaled(ka0, kb0, field, (ev.height, ev.width), clip.sample_rate, k_first=c0 + 1, count=Tc,
+                                                 border=self.mci_border, precision="half" if self.mci_half else "full")
             else:
                 staged = views["dain"].to(g.device, non_blocking=True)
                 if clip.src_dain is not None:      # resize_on="gpu": resize + ToTensor + Normalize in one kernel (rib_resize_cubic)
@@ -1625,6 +1689,11 @@ class _FolderPipeline:
                 # shows the host's normalisation, as the native path's does (normalise_exact)
                 dn = torch.from_numpy(_background.normalised_upload(u8)).unsqueeze(1)
                 dn_shown = torch.from_numpy(_background.normalised(u8)).unsqueeze(1)
+                if self.keysize:                 # the same field, the samples from the key files' own pixels: the files' backgrounds
+                    bg0 = _background.mci_frames_scaled_host(clip.key_src[k].result(timeout=IO_TIMEOUT_S),
+                                                             clip.key_src[k + clip.sample_rate].result(timeout=IO_TIMEOUT_S), field,
+                                                             (ev.height, ev.width), clip.sample_rate, [i - k for i in frames],
+                                                             border=self.mci_border, precision="half" if self.mci_half else "full")
             else:
                 dn = dn_shown = torch.stack([g[0] for g in got]).unsqueeze(1)
             lab = ev.make_labels(model, poses).unsqueeze(1)
@@ -1638,7 +1707,9 @@ class _FolderPipeline:
             tm["rasterise"] += t2 - t1
             tm["generate"] += time.perf_counter() - t2
             for t, i in enumerate(frames):
-                if self.source:                  # composite_host of the frame's (img, mask) over the DAIN file's own pixels
+                if self.keysize:                 # composite_host of the frame's (img, mask) over its full-size interpolated background
+                    clip.futs[i] = self.pool.submit(self.save_keysize_host, clip, i, *shown[t], bg0[t])
+                elif self.source:                # composite_host of the frame's (img, mask) over the DAIN file's own pixels
                     clip.futs[i] = self.pool.submit(self.save_source_host, clip, i, *shown[t])
                 else:
                     clip.futs[i] = self.pool.submit(self.save_frame_host, clip, i, outs[t])

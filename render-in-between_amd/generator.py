@@ -713,6 +713,45 @@ class Generator:
         res = tuple((r[:, 0] if single else r) for r in (rf, ru) if r is not None)
         return res if normalised == "both" else res[0]
 
+    def mci_frames_scaled(self, a0_u8, b0_u8, field, model_hw, sample_rate, k_first=0, count=None, border="clamp", precision="full", out=None):
+        """mci_frames' uint8 frames at the key frames' OWN size, one launch (rib_scaled_frames; background.mci_frames_scaled_host
+        is the definition and is bit-equal): a0_u8, b0_u8 uint8 [B,h0,w0,3] (or [h0,w0,3]) are the key frame files' pixels on
+        this device, field the int16 [B,Hb,Wb,2] field of the MODEL-size key frames (mci_field, or mci_refine with
+        precision="half"), model_hw = (H, W) that model size -> uint8 [T,B,h0,w0,3] ([T,h0,w0,3]), frames k_first ..
+        k_first + count - 1 (count None: up to sample_rate - 1).  The field is read at the model's resolution, the pixels are
+        sampled from the full-size key frames; with (h0, w0) == (H, W) the bytes are mci_frames'.  Sides in 1..16384, each axis
+        within 1/16 .. 16 times the model's.  out: optional contiguous uint8 destination, any byte offset."""
+        from .background import BORDERS, PRECISIONS, check_border, check_precision, field_shape, log2_rate, scaled_factors
+        border = BORDERS.index(check_border(border, "mci_frames_scaled"))
+        precision = PRECISIONS.index(check_precision(precision, "mci_frames_scaled"))
+        a, b, single = self._mci_pair(a0_u8, b0_u8, "mci_frames_scaled")
+        B, h0, w0, _ = a.shape
+        H, W = (int(v) for v in model_hw)
+        scaled_factors((H, W), (h0, w0), "mci_frames_scaled")
+        Hb, Wb = field_shape(H, W)
+        log2_rate(sample_rate)
+        s = int(sample_rate)
+        if not torch.is_tensor(field) or field.dtype != torch.int16 or field.device != self.device:
+            raise ValueError("mci_frames_scaled: field must be an int16 tensor on %s (mci_field)" % (self.device,))
+        f = (field.unsqueeze(0) if field.dim() == 3 else field).contiguous()
+        if tuple(f.shape) != (B, Hb, Wb, 2):
+            raise ValueError("mci_frames_scaled: the field of %d %dx%d model frames is [%d, %d, %d, 2], got %s" % (B, H, W, B, Hb, Wb, tuple(field.shape)))
+        k_first = int(k_first)
+        T = (s - k_first) if count is None else int(count)
+        if T < 1 or k_first < 0 or k_first + T - 1 > s:
+            raise ValueError("mci_frames_scaled: frames %d..%d are outside the segment 0..%d" % (k_first, k_first + T - 1, s))
+        shape = (T, B, h0, w0, 3)
+        with torch.cuda.device(self.device):
+            if out is None:
+                res = torch.empty(shape, dtype=torch.uint8, device=self.device)
+            else:
+                res = out.unsqueeze(1) if (single and torch.is_tensor(out) and out.dim() == 4) else out
+                if not torch.is_tensor(res) or tuple(res.shape) != shape or res.dtype != torch.uint8 or not res.is_contiguous() or res.device != self.device:
+                    raise ValueError("mci_frames_scaled: out must be a contiguous uint8 %s tensor on %s" % (shape, self.device))
+            _native.check(self._h, self._lib.rib_scaled_frames(self._h, T, B, H, W, h0, w0, _ptr(a), _ptr(b), _ptr(f), s, k_first, border,
+                                                               precision, _ptr(res), self._stream()))
+        return res[:, 0] if single else res
+
     def jpeg_max_bytes(self, height, width):
         """Upper bound of one JPEG file of a height x width image, header included (rib_jpeg_max_bytes; panel.jpeg_max_bytes)."""
         n = int(self._lib.rib_jpeg_max_bytes(int(height), int(width)))

@@ -55,6 +55,14 @@ interpolated N-fold on the GPU and its keypoints go straight from the network's 
 frames are the two-command run's.  <input-dir>/Predict_motion is not read.  `keyframes-linear` takes the linearly interpolated
 clip (stage 1's Linear_motion folder); `--save-poses` also writes <save-dir>/Predict_motion and <save-dir>/Linear_motion as stage 1's
 own command does.  With `--background mci --video --frames none` one command turns key frames and their detections into the clip.
+
+The interpolated backgrounds at the key frames' own size: `--background mci --output-size keyframes` writes the PNGs and the --video
+clip at the size of the clip's key frame files (one size per clip; e.g. 1920x1080) where `--output-size model` squashes them to
+the model size.  The motion field stays the model-size one; only the background pixels are sampled from the full-size key frames
+(rib_scaled_frames, background.mci_frames_scaled_host) and the generated person is composited over them (rib_composite).  The one
+command is then `--poses keyframes --pose-dir DIR --background mci --output-size keyframes --video --frames none`.  It is this
+project's interpolation, not DAIN; the field has the model's resolution (motion detail finer than an 8x8 model block, about 30 px
+at 1080p from 512, is not followed); the person is a cubic enlargement; no interior occlusion reasoning; unmeasured on real footage.
 """
 import argparse
 import os
@@ -132,6 +140,8 @@ def summary_line(evaluator, rank=0, world=1):
                [getattr(evaluator, "background", "dain")]))
     if getattr(evaluator, "output_size", "model") == "source":
         line += " | files at the source size"
+    if getattr(evaluator, "output_size", "model") == "keyframes":
+        line += " | files at the key frames' size"
     rep = getattr(evaluator, "metrics_report", None)
     if "metrics" in tm and rep is not None:
         o = rep["overall"]
@@ -264,12 +274,15 @@ def build_parser():
     parser.add_argument("--frames", choices=("png", "none"), default="png",
                         help="'png' (default): the reference's folder of PNG frames; 'none' (only with --video): the video is the only "
                              "output - no PNG is encoded or written, the raw frames are not downloaded")
-    parser.add_argument("--output-size", choices=("model", "source"), default="model",
+    parser.add_argument("--output-size", choices=("model", "source", "keyframes"), default="model",
                         help="'model' (default): every file at the model size, as the reference; 'source' (needs --resize-on gpu): the "
                              "PNGs and the --video clip at the size of the clip's DAIN frames - the background keeps every source pixel, "
                              "the generated person is a cubic enlargement of the model-size prediction (softer than its surroundings and "
                              "than the key frames, which are their files' own pixels), blended on the GPU in one launch; --metrics and "
-                             "--panels stay at the model size; not with --background mci")
+                             "--panels stay at the model size; not with --background mci; 'keyframes' (a setting of --background mci): "
+                             "the same at the key frames' size - the PNGs and the --video clip at the size of the clip's key frame files, "
+                             "the interpolated background sampled from the full-size key frames with the model-size motion field (motion "
+                             "detail finer than an 8x8 model block is not followed), the person composited over it")
     parser.add_argument("--poses", default="folder",
                         help="where the frames' poses come from. 'folder' (default): <input-dir>/Predict_motion/<clip>/, one OpenPose json per "
                              "output frame, as the reference (written by motion/inference.py); 'keyframes': --pose-dir holds one json per KEY "
@@ -317,7 +330,11 @@ def parse_args(argv=None):
     if opts.background == "mci" and opts.resize_on == "gpu":
         parser.error("--background mci with --resize-on gpu is not supported (there is no DAIN list to plan the GPU resize for)")
     if opts.output_size == "source" and opts.background == "mci":
-        parser.error("--output-size source with --background mci is not supported: the interpolation runs at the model size")
+        parser.error("--output-size source with --background mci is not supported: the interpolation runs at the model size; "
+                     "use --output-size keyframes")
+    if opts.output_size == "keyframes" and opts.background != "mci":
+        parser.error("--output-size keyframes is a setting of --background mci (the size of the key frame files); with DAIN frames "
+                     "use --output-size source")
     if opts.output_size == "source" and opts.resize_on != "gpu":
         parser.error("--output-size source needs --resize-on gpu: the background frames' source-size bytes are on the device only there")
     if opts.metrics and opts.gt_dir is None:

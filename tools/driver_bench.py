@@ -3,7 +3,7 @@
 
     python tools/driver_bench.py [--size 512 | --height 320 --width 480] [--keys 5] [--rate 32] [--lanes 2] [--batch B] [--chunk 4]
                                   [--src-width 1920 --src-height 1080] [--resize-on host|gpu] [--metrics [--pose-mask]] [--panels [--panel-encode host|gpu]]
-                                  [--video [--frames none]] [--poses folder|keyframes] [--output-size model|source]
+                                  [--video [--frames none]] [--poses folder|keyframes] [--output-size model|source|keyframes]
 
 Writes a clip in the reference's directory layout (inputs/ DAIN/ Predict_motion/), runs
 Evaluator.evaluate_from_folder twice (the first run also builds launch plans) and prints the
@@ -18,7 +18,9 @@ writes only that video (frames="none": no PNG is encoded, the PNG level then pla
 in the driver (poses="keyframes": a seed-defined motion transformer interpolates the key frames' poses of key_poses/, no json is
 read per frame; --rate must then be a power of two); the per-clip event time of stage 1 plus the bridge is reported too.
 --output-size source (with --resize-on gpu) writes the frames' files at the size of the input files (output_size="source": one
-rib_composite launch per unit; the PNG encode then works on source-size frames).
+rib_composite launch per unit; the PNG encode then works on source-size frames).  --output-size keyframes (with --background mci)
+does the same at the size of the key frame files (output_size="keyframes": one rib_scaled_frames launch per unit makes the
+backgrounds, --src-width / --src-height say how large the key frames are).
 """
 import argparse, json, os, sys, tempfile, time
 import numpy as np, torch
@@ -28,7 +30,7 @@ from render_in_between_amd import evaluator as ev, synth
 from tools.raster_bench import person
 
 
-def write_clip(root, n_key, rate, H, W, src_h=0, src_w=0, gt=False):
+def write_clip(root, n_key, rate, H, W, src_h=0, src_w=0, gt=False, dain=True):
     from PIL import Image
     rng = np.random.default_rng(0)
     n = (n_key - 1) * rate + 1
@@ -42,7 +44,8 @@ def write_clip(root, n_key, rate, H, W, src_h=0, src_w=0, gt=False):
     for k in range(n_key):
         Image.fromarray(img(k)).save(os.path.join(root, "inputs", "clip", "%04d.png" % k))
     for i in range(n):
-        Image.fromarray(img(100 + i)).save(os.path.join(root, "DAIN", "clip", "f%04d.png" % i))
+        if dain:                              # (background="mci" reads none: most of the time a 1080p clip takes to write)
+            Image.fromarray(img(100 + i)).save(os.path.join(root, "DAIN", "clip", "f%04d.png" % i))
         if gt:
             Image.fromarray(img(1000 + i)).save(os.path.join(root, "gt", "clip", "f%04d.png" % i))
         lm, conf = person(rng, sh, sw)
@@ -92,9 +95,12 @@ def main():
     ap.add_argument("--frames", default="png", choices=("png", "none"), help="with --video: 'none' writes no PNG frames (frames=...)")
     ap.add_argument("--poses", default="folder", choices=("folder", "keyframes"),
                     help="'keyframes': the motion transformer interpolates the key frames' poses inside the driver (poses=...)")
-    ap.add_argument("--output-size", default="model", choices=("model", "source"),
-                    help="'source' (with --resize-on gpu): the frames' files at the input files' size, composited on the GPU (output_size=...)")
+    ap.add_argument("--output-size", default="model", choices=("model", "source", "keyframes"),
+                    help="'source' (with --resize-on gpu): the frames' files at the input files' size, composited on the GPU; 'keyframes' "
+                         "(with --background mci): the same from the key frame files, the backgrounds by rib_scaled_frames (output_size=...)")
     a = ap.parse_args()
+    if a.output_size == "keyframes" and a.background != "mci":
+        ap.error("--output-size keyframes is a setting of --background mci")
     if a.output_size == "source" and (a.resize_on != "gpu" or a.background == "mci"):
         ap.error("--output-size source needs --resize-on gpu and is not supported with --background mci")
     if a.poses == "keyframes" and a.rate & (a.rate - 1):
@@ -119,7 +125,7 @@ def main():
     G = rib.Generator(cfg.gen, compute_dtype=a.dtype).eval()
     G.load_state_dict(synth.make_state_dict(spec, 0, power_iters=3))
     with tempfile.TemporaryDirectory() as root:
-        n = write_clip(root, a.keys, a.rate, H, W, a.src_height, a.src_width, gt=a.metrics)
+        n = write_clip(root, a.keys, a.rate, H, W, a.src_height, a.src_width, gt=a.metrics, dain=a.background != "mci")
         E = ev.Evaluator(cfg, lanes=a.lanes, batch=a.batch or None, chunk=a.chunk, io_threads=a.io_threads or None,
                          png_compress_level=None if a.compress < 0 else a.compress, io_mode=a.io_mode, resize_on=a.resize_on)
         dirs = [os.path.join(root, d) for d in ("inputs", "DAIN", "Predict_motion")]
