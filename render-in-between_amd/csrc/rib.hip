@@ -7,7 +7,7 @@
 //     fold (PGNR/models/layers/weight_norm.py:84-85 hook), filter re-layout, one device blob;
 //   * a static launch plan per (B,H,W): workspace layout + the ordered kernel launches that
 //     restate Generator.forward (PGNR/models/generator.py:181-234) and MaskGenerator.forward
-//     (:493-510);
+//     (:493-510) - its data model is plan.h, its builder planner.h, both parts of this translation unit;
 //   * the autoregressive segment driver (PGNR/models/evaluator.py:238-262).
 //
 // The folder driver's frame utilities (rib_blend ... rib_jpeg) are a second object, frame.hip; rib_host.h holds what the two share.
@@ -147,8 +147,6 @@ struct ConvDef {
   int cinp = 0, coutp = 0;
   // bf16 storage mode: bf16 copies of the filters (same [CoutPad][tap][CinPad] layout), offsets in floats of the blob
   size_t w16_off = 0, wp16_off = 0;
-  // Winograd F(2x2, 3x3) filters U = G g G^T, [16 positions][CoutPad][CinPad] fp32, and a zero bias vector for the
-  // batched GEMM (the real bias is added by the output transform); 0: the layer never runs that way
   // Winograd: the layer may run in the Winograd domain (wino_ok); the transformed filter sets U = G g G^T live OUTSIDE the
   // blob, made on the device from the folded filters when a plan first needs one (WinoSet, ensure_wino_set); zero_off: a
   // zero bias vector for the batched GEMM (the real bias is added by the output transform)
@@ -471,146 +469,9 @@ const Variant* pick_gemm_dma(int prec, long Z, int M, int N, int K) {
   return best;
 }
 
-// ------------------------------------------------------------------------------------------
-// launch plan
-// ------------------------------------------------------------------------------------------
-enum OpKind { OP_PACK, OP_IGEMM, OP_FINALIZE, OP_POOL, OP_INADD, OP_SPLITEPI, OP_MODULATE, OP_WINO_IN, OP_WINO_OUT, OP_LOWC, OP_GEMM };
-
-// pointer encoding inside a plan: workspace-relative offsets (bytes) or weight-blob offsets
-// (floats); resolved at launch time.
-enum PtrSpace { PS_NULL = 0, PS_WS, PS_WEIGHT, PS_USER, PS_WINO };   // PS_WINO: off = index of a Winograd filter set of the handle
-enum UserSlot { U_LABEL = 0, U_FAKE, U_PREV, U_IMG, U_MASK, U_FUSE, U_COUNT };   // U_FUSE: optional fused frame (null: no blend)
-struct PRef {
-  PtrSpace sp = PS_NULL;
-  size_t off = 0;   // bytes for WS, floats for WEIGHT, slot id for USER
-};
-
-// A plan runs its launches in order on the caller's stream.  (Rounds 1-2 carried an option to run the condition encoder
-// and the label branch on side streams: measured slower three times - two queues cost more than the overlap returns on
-// this runtime - and incompatible with the lifetime-shared workspace; retired in round 3.)
-
-// One planned launch: the fields every launch shares, a few launch selectors, the parameter struct of ITS kernel family
-// with the scalar fields filled in, and one list of pointer bindings - which pointer field of that struct resolves to which
-// PRef.  The bindings are the only home of a pointer: run_plan resolves them, the workspace lifetime analysis walks them
-// (Builder::for_each_pref) and the byte model asks them (bound()); the pointer fields of `params` itself stay null.
-using OpParams = std::variant<PackParams, IgemmParams, FinalizeParams, PoolParams, InAddParams, SplitEpiParams, ModulateParams,
-                              WinoInParams, WinoOutParams, LowcParams, GemmDmaParams>;      // in the order of OpKind
-static_assert(std::is_same<std::variant_alternative_t<OP_IGEMM, OpParams>, IgemmParams>::value &&
-              std::is_same<std::variant_alternative_t<OP_GEMM, OpParams>, GemmDmaParams>::value, "OpParams follows OpKind");
-struct Op {
-  int kclass = 0;
-  std::string name;
-  std::string for_op;        // a finalize launch emitted on behalf of this consumer (rib_time_op times them together)
-  bool label_only = false;   // depends on the label map only (pack.label, down_first, the mask network's label branch)
-  dim3 grid;
-  double flops = 0;
-  const Variant* var = nullptr;   // k_igemm / k_gemm_dma tile
-  int small_co = 0;   // > 0: a head convolution with small_co output channels: k_conv_head (matrix cores, taps as GEMM
-                      //      columns) when `head`, else k_conv_small (direct, vector ALUs), instead of k_igemm
-  bool head = false;
-  bool fuse_blend = false;   // the mask head also writes the driver's blend into user slot U_FUSE when the caller gave one
-  bool wino = false;   // this GEMM launch is the 16- / 36-way batched Winograd-domain GEMM (executes 4/9 or 1/4 of its nine-tap FLOP count)
-  int wino_m = 0;      // 2 or 4 on the three launches of a Winograd convolution
-  int wi_mode = 0;     // k_wino_in: WSRC_PLAIN / WSRC_SPADE / WSRC_JOIN
-  int wi_mode2 = -1;   // k_wino_in with a second source (the 1x1 shortcut's input): WSRC_PLAIN / WSRC_SPADE; -1: none
-  bool wi_staged = false;   // k_wino_in_staged (WinoInParams::sty x stx tiles per workgroup) instead of k_wino_in / k_wino4_in
-  int lowc_ce = 0, lowc_ncol = 0, lowc_tw = 32;
-  OpParams params;
-  struct Binding { PRef ref; unsigned field = 0; };      // field: byte offset of the pointer inside `params`
-  static constexpr int kMaxBindings = 24;            // (the largest families, k_wino_in and k_igemm, have 20 and 18 pointers)
-  Binding binds[kMaxBindings];
-  int nbinds = 0;
-
-  OpKind kind() const { return (OpKind)params.index(); }
-  template <class P> const P& as() const { return std::get<P>(params); }
-  // a pointer field of the parameter struct P (or of a StatSrc inside it) as its byte offset; P must be this op's family
-  template <class P, class T> unsigned field_of(T* P::*f) const {
-    return (unsigned)(reinterpret_cast<const char*>(&(as<P>().*f)) - reinterpret_cast<const char*>(&params));
-  }
-  template <class P, class T> unsigned field_of(StatSrc P::*s, T* StatSrc::*f) const {
-    return (unsigned)(reinterpret_cast<const char*>(&((as<P>().*s).*f)) - reinterpret_cast<const char*>(&params));
-  }
-  PRef ref_at(unsigned field) const {
-    for (int i = 0; i < nbinds; ++i) if (binds[i].field == field) return binds[i].ref;
-    return PRef();
-  }
-  // binding a field again replaces its reference; a null reference unbinds it
-  void bind_at(unsigned field, PRef r) {
-    int i = 0;
-    while (i < nbinds && binds[i].field != field) ++i;
-    if (r.sp == PS_NULL) { if (i < nbinds) binds[i] = binds[--nbinds]; return; }
-    if (i == kMaxBindings) abort();      // (unreachable: a family has fewer pointer fields than that)
-    binds[i] = Binding{r, field};
-    if (i == nbinds) ++nbinds;
-  }
-  template <class P, class T> bool bound(T* P::*f) const { return ref_at(field_of(f)).sp != PS_NULL; }
-};
-// An Op under construction, typed by its kernel family: bind() takes pointer fields of P only, so a misspelt field or a
-// field of another family does not compile.  push() stores the Op part.
-template <class P> struct OpOf : Op {
-  OpOf(int kclass_, const std::string& name_) { kclass = kclass_; name = name_; memset(&params.emplace<P>(), 0, sizeof(P)); }
-  P& p() { return std::get<P>(params); }
-  template <class T> void bind(T* P::*f, PRef r) { bind_at(field_of(f), r); }
-  template <class T> void bind(StatSrc P::*s, T* StatSrc::*f, PRef r) { bind_at(field_of(s, f), r); }
-  template <class T> PRef ref(T* P::*f) const { return ref_at(field_of(f)); }
-};
-
-struct PendingStats {
-  Op fin;
-  bool pushed = false;
-  size_t part_off = 0; int tiles = 0, Cs = 0; float inv_count = 0.f;
-  bool affine = false; size_t g_off = 0, be_off = 0;
-};
-
-struct Tap { std::string name; size_t off; int Cp, C, H, W; };
-
-struct LazySrc;
-struct Act {       // NHWC activation in the workspace
-  size_t off = 0;  // bytes
-  int Cp = 0, C = 0, H = 0, W = 0;
-  // virt: never materialised - the channel concatenation of up to three of the caller's NCHW fp32 tensors, read in place
-  // by k_conv_lowc (usrc: user slots, uc: their channel counts)
-  bool virt = false; int usrc[3] = {0, 0, 0}, uc[3] = {0, 0, 0};
-  // lazy: never stored - the output of an unfused SPADE (WSRC_SPADE) or of a mask-network join (WSRC_JOIN) that the
-  // Winograd input transform of its only consumer computes on the fly (Builder::conv_wino)
-  std::shared_ptr<LazySrc> lazy;
-};
-struct PendingStats;
-struct Norm {      // (scale, shift) arrays [B][ld]
-  size_t sc = 0, sh = 0; int ld = 0;
-  bool valid = false;
-  // the k_stats_finalize launch that would fill the arrays, not emitted yet: a consumer that can reduce the
-  // producer's partial sums itself (k_igemm prologue / SPADE epilogue, few partials) takes them from here and the
-  // launch never happens; any other consumer emits it first (Builder::materialize)
-  std::shared_ptr<PendingStats> pend;
-};
-
-struct LazySrc {
-  int mode = 0;                 // WSRC_SPADE / WSRC_JOIN
-  std::string name;             // the launch this replaces (for error messages)
-  Act x; Norm nx;               // SPADE: tensor being normalised + its statistics; JOIN: t1 + n1
-  bool x_ups = false, lrelu = false;
-  size_t slab_off = 0; int slab_ld = 0, col0 = 0; size_t sbias_off = 0;      // SPADE: gamma/beta slab of the level, this group's bias
-  bool has2 = false; Act x2; Norm n2; Act xres; Act o;                         // JOIN: ts + ns (learned shortcut) or xres; o = the stored join
-};
-
-// results of the label-only launches, as (offset, bytes) into the plan's workspace: in an autoregressive chain the
-// label maps of all T frames are known up front, so rib_chain runs these launches ONCE at batch T*B (a
-// labels-only plan) and copies each frame's slices into the frame plan's slots
-struct LabelSlots { size_t x0 = 0, x0_b = 0, nx_sc = 0, nx_sh = 0, nx_b = 0, cat = 0, cat_b = 0, ncat_sc = 0, ncat_sh = 0, ncat_b = 0; };
-
-struct Plan {
-  bool labels_only = false;
-  LabelSlots ls;
-  int B, H, W;
-  size_t ws_bytes = 0;
-  size_t ws_virtual = 0;   // bytes before lifetime-based reuse (one range per buffer)
-  std::vector<Op> ops;
-  std::vector<Tap> taps;
-  double flops[RIB_KC_COUNT] = {0};
-};
-
 }  // namespace
+
+#include "plan.h"      // PRef, Op, OpOf, Act, Norm, LazySrc, Plan: the plan's data model
 
 struct rib_handle : rib::FrameState {     // device, err, label_nc and the frame utilities' own state: rib_host.h
   Cfg g;
@@ -994,1230 +855,11 @@ const std::vector<float>* tensor_data(rib_handle* h, const std::string& name) {
   return t.set ? &t.data : nullptr;
 }
 
-// ------------------------------------------------------------------------------------------
-// plan builder
-// ------------------------------------------------------------------------------------------
-// ------------------------------------------------------------------------------------------
-// FusionPolicy: every decision of the launch plan that is a POLICY rather than arithmetic - which launches are fused, which
-// kernel family serves a layer, where a tensor is never materialised - by name, with the switch that turns it off for an
-// A/B or a test.  One instance per plan build, read from the environment at that moment (tests flip the switches between
-// two Generator constructions).  Three more switches act where the weight LAYOUT is assigned, because they decide which
-// filter copies exist at all (assign_weight_layout: RIB_NO_WINO, RIB_NO_LOWC, RIB_NO_SPADE16), one where the k_gemm_dma tile
-// of a GEMM is picked (pick_gemm_dma: RIB_NO_DMA), one in the tile order of a grid (xcd_chunk_of: RIB_NO_XCD).
-// The tuned tables (rib_set_choice) choose WITHIN what the policy allows: tile variant, split-K factor, Winograd tile.
-// ------------------------------------------------------------------------------------------
-struct FusionPolicy {
-  // InstanceNorm statistics: a consumer that can reduce <= STATS_MAX_PARTIALS producer partials itself does so and the
-  // k_stats_finalize launch never exists (RIB_NO_CONSUMER_STATS=1: one finalize launch per normalised tensor)
-  bool consumer_stats = !getenv("RIB_NO_CONSUMER_STATS");
-  // heads with <= 3 output channels: k_conv_head (taps as MFMA columns; RIB_NO_HEADCONV=1 -> k_conv_small, direct on the
-  // vector ALUs; RIB_NO_SMALLCONV=1 -> k_igemm with the columns padded to 16)
-  bool head_conv = !getenv("RIB_NO_HEADCONV");
-  bool small_conv = !getenv("RIB_NO_SMALLCONV");
-  // 3x3 stride-1 layers on maps of at most this many pixels run in the Winograd domain (k_wino_in / batched GEMM / k_wino_out)
-  long wino_max_px = getenv("RIB_WINO_MAX_PX") ? atol(getenv("RIB_WINO_MAX_PX")) : 16384;
-  int wino_force = getenv("RIB_WINO_M") ? atoi(getenv("RIB_WINO_M")) : 0;      // 2 / 4: that Winograd tile wherever one is eligible
-  // grid-level split-K (+ a k_splitk_epilogue launch) for layers whose tile grid cannot fill the chip
-  bool split_k = !getenv("RIB_NO_SPLITK");
-  // layers with <= 16 output channels on the 16-column MFMA path (v_mfma_f32_16x16x4_f32; fp32 storage only)
-  bool n16 = !getenv("RIB_NO_N16");
-  // k_conv_lowc tile width: 0 = per layer (16 for the store-bound 64-column layer without statistics, else 32)
-  int lowc_tw = getenv("RIB_LOWC_TW") ? (atoi(getenv("RIB_LOWC_TW")) == 16 ? 16 : 32) : 0;
-  // condition levels of at most this many pixels compute gamma/beta of ALL their SPADEs in one GEMM into a slab (0: off)
-  long cond_gemm_max_px = getenv("RIB_COND_GEMM_MAX_PX") ? atol(getenv("RIB_COND_GEMM_MAX_PX")) : 4096;
-  // SPADE on maps of <= 4096 pixels (x batch): unfused (slab GEMM + k_spade_modulate) instead of k_igemm<SPADE>
-  bool unfused_spade = !getenv("RIB_NO_UNFUSED_SPADE");
-  // an unfused SPADE's output / a mask-network join whose only consumer is a Winograd input transform is never stored
-  bool lazy_sources = !getenv("RIB_NO_LAZY");
-  // the learned 1x1 shortcut of a res block as extra K chunks of conv_block_1 (one launch less, no shortcut tensor)
-  bool fuse_shortcut = !getenv("RIB_NO_FUSE_SHORTCUT");
-  // conv_block_1 of a learned-shortcut block in the Winograd domain, the shortcut as extra K columns at the centre-tap positions
-  // (Builder::shortcut_wino_m).  On only where the tuned table has an entry for the layer's .wino / .wino4 launch - shapes nobody
-  // measured keep the direct launch; RIB_NO_WINO_SHORTCUT=1: nowhere; RIB_WINO_SHORTCUT_M=2 / 4: wherever eligible, that tile
-  bool wino_shortcut = !getenv("RIB_NO_WINO_SHORTCUT");
-  int wino_shortcut_m = getenv("RIB_WINO_SHORTCUT_M") ? atoi(getenv("RIB_WINO_SHORTCUT_M")) : 0;
-  // buffers with disjoint lifetimes share workspace bytes (assign_physical)
-  bool ws_reuse = !getenv("RIB_NO_WS_REUSE");
-  // level i of the mask network's label encoder and of its image encoder in ONE paired launch (batch-1 frame plans).
-  // Asked on every forward, ahead of the plan cache (plan_pairs): a function of its own, so that asking reads this switch alone
-  static bool pair_mask_encoders() { return !getenv("RIB_NO_PAIR"); }
-};
+}  // namespace
 
-struct Builder {
-  rib_handle* h;
-  Plan* P;
-  int B;
-  const FusionPolicy pol;
-  size_t ws = 0;
-  std::string error;
-  bool mark_label = false;
-  bool pair_mask = false;    // the two encoders of the mask network level by level in paired launches (mask_branches_paired)
-  bool defer_stats = true;   // false: every k_stats_finalize launch is emitted where its producer is (labels-only plans)
-  // a consumer needs the (scale, shift) ARRAYS of n: emit the finalize launch now if it is still pending
-  void materialize(const Norm& n, const std::string& consumer = std::string()) {
-    if (n.pend && !n.pend->pushed) { n.pend->pushed = true; n.pend->fin.for_op = consumer; push(n.pend->fin); }
-  }
-  // the producer's partial sums are still there for a consumer-side finalize
-  static bool has_partials(const Norm& n) { return n.pend && !n.pend->pushed; }
-  // emit or defer the finalize launch f of a producer with `tiles` partials per sample
-  void finalize_or_defer(Op& f, Norm* out, bool now, size_t part_off, int tiles, int Cs, float inv_count, bool affine, size_t g_off, size_t be_off) {
-    if (now || !pol.consumer_stats || !defer_stats || mark_label || tiles > STATS_MAX_PARTIALS) { push(f); return; }
-    auto ps = std::make_shared<PendingStats>();
-    ps->fin = f; ps->part_off = part_off; ps->tiles = tiles; ps->Cs = Cs; ps->inv_count = inv_count;
-    ps->affine = affine; ps->g_off = g_off; ps->be_off = be_off;
-    out->pend = ps;
-  }
-  // A light consumer (k_wino_in, k_spade_modulate, k_in_add: channel slices of 64) reduces the producer's partials itself:
-  // fills the scalars of the op's StatSrc `src` and binds its pointers from the pending finalize of n, which then never
-  // launches unless another consumer needs the arrays.  false: the partials are gone / too many / the launch is forced ->
-  // the caller materializes.
-  template <class P> bool take_partials(const Norm& n, OpOf<P>& op, StatSrc P::*src) {
-    if (!has_partials(n) || n.pend->tiles > STATS_MAX_PARTIALS) return false;
-    const PendingStats& ps = *n.pend;
-    StatSrc& st = op.p().*src;
-    st.tiles = ps.tiles; st.Cs = ps.Cs; st.inv_count = ps.inv_count;
-    op.bind(src, &StatSrc::part, WS(ps.part_off));
-    if (ps.affine) { op.bind(src, &StatSrc::gamma, WT(ps.g_off)); op.bind(src, &StatSrc::beta, WT(ps.be_off)); }
-    return true;
-  }
-  // the k_stats_finalize launch of a producer that left `tiles` partial sums per image (Cs columns, C of them stored) at part_off
-  OpOf<FinalizeParams> finalize_op(const std::string& producer, size_t part_off, int tiles, int Cs, int C, const Norm& out, size_t choff,
-                                   int H, int W, const ConvDef* affine, int images) {
-    OpOf<FinalizeParams> f(RIB_KC_STATS, producer + ".stats");
-    FinalizeParams& q = f.p();
-    q.tiles = tiles; q.Cs = Cs; q.C = C; q.ld = out.ld; q.off = (int)choff;
-    q.inv_count = 1.0f / ((float)H * (float)W); q.eps = 1e-5f;
-    f.bind(&FinalizeParams::part, WS(part_off));
-    if (affine) { f.bind(&FinalizeParams::gamma, WT(affine->g_off)); f.bind(&FinalizeParams::beta, WT(affine->be_off)); }
-    f.bind(&FinalizeParams::scale, WS(out.sc)); f.bind(&FinalizeParams::shift, WS(out.sh));
-    f.grid = dim3((Cs + 15) / 16, images, 1);
-    return f;
-  }
-  // gamma/beta slab of a condition level (cond_level_gemm): [B][H*W][ld] fp32, group columns at SpadeGroup::col0
-  struct LevelSlab { size_t off = 0; int ld = 0; };
-  std::map<int, LevelSlab> level_slab;
-  int tuneB = 0;      // batch whose tuned choices / cost-model decisions this plan follows (0: its own).  The labels-only
-                      // plan of a chain follows the frame plan's, so that its results are bit-identical to per-frame launches
-  int TB_() const { return tuneB > 0 ? tuneB : B; }
-  void push(Op op) {
-    op.label_only = mark_label;
-    P->ops.push_back(op);
-  }
+#include "planner.h"      // FusionPolicy, Builder: a shape -> a Plan
 
-  // Workspace layout.  During the build every buffer gets its own range of a virtual address space (bump
-  // allocation, as the plan used to run: 1.1 GB at 512x512); assign_physical() then gives buffers whose lifetimes
-  // (first .. last launch that touches them) do not overlap the same bytes, so that the working set of a frame stays
-  // inside the 256 MB memory-side cache instead of streaming 1.1 GB of distinct addresses through it.
-  struct AllocRec { size_t voff, bytes, phys; int first, last; };
-  std::vector<AllocRec> allocs;
-  size_t alloc(size_t bytes) {
-    size_t o = ws; ws += align256(bytes);
-    allocs.push_back(AllocRec{o, align256(bytes), o, INT_MAX, -1});
-    return o;
-  }
-  Act act(int C, int H, int W) {
-    Act a; a.C = C; a.Cp = h->padc(C); a.H = H; a.W = W;
-    a.off = alloc((size_t)B * H * W * a.Cp * h->esz());
-    return a;
-  }
-  Norm norm(int Cp, int images = 0) {
-    Norm n; n.ld = Cp; n.valid = true;
-    n.sc = alloc((size_t)(images ? images : B) * Cp * sizeof(float));
-    n.sh = alloc((size_t)(images ? images : B) * Cp * sizeof(float));
-    return n;
-  }
-  Act act_n(int images, int C, int H, int W) {     // an activation of `images` images instead of B
-    Act a; a.C = C; a.Cp = h->padc(C); a.H = H; a.W = W;
-    a.off = alloc((size_t)images * H * W * a.Cp * h->esz());
-    return a;
-  }
-  // an activation that is never materialised: up to three of the caller's NCHW tensors, concatenated along channels
-  Act virt(int C, int H, int W, int s0, int c0, int s1 = 0, int c1 = 0, int s2 = 0, int c2 = 0) {
-    Act a; a.virt = true; a.C = C; a.Cp = 0; a.H = H; a.W = W;
-    a.usrc[0] = s0; a.uc[0] = c0; a.usrc[1] = s1; a.uc[1] = c1; a.usrc[2] = s2; a.uc[2] = c2;
-    return a;
-  }
-  // every consumer of a packed input tensor has a k_conv_lowc instantiation
-  bool lowc_serves(std::initializer_list<const char*> names) {
-    for (const char* nm : names) {
-      auto it = h->conv_index.find(nm);
-      if (it == h->conv_index.end() || !h->convs[it->second].wl_off) return false;
-    }
-    return true;
-  }
-  // conv_img can skip its NHWC copy only on the head kernel (conv(): `small` + `head`)
-  bool head_without_nhwc(const ConvDef& c) {
-    return c.cout <= 3 && c.ks == 3 && c.stride == 1 && (c.cinp == 16 || c.cinp == 32) && pol.small_conv && pol.head_conv;
-  }
-  static PRef WS(size_t off) { PRef r; r.sp = PS_WS; r.off = off; return r; }
-  static PRef WT(size_t off) { PRef r; r.sp = PS_WEIGHT; r.off = off; return r; }
-  static PRef US(int slot) { PRef r; r.sp = PS_USER; r.off = (size_t)slot; return r; }
-  static PRef WINO(int set) { PRef r; r.sp = PS_WINO; r.off = (size_t)set; return r; }
-  void tap(const std::string& name, const Act& a) { P->taps.push_back(Tap{name, a.off, a.Cp, a.C, a.H, a.W}); }
-
-  // ---- generic convolution launch --------------------------------------------------------
-  struct ConvArgs {
-    const ConvDef* cd = nullptr;
-    Act in;                 // input activation (stored size; half-res when ups)
-    bool ups = false;
-    const Norm* pro = nullptr; size_t pro_choff = 0;   // prologue affine (+channel offset into the arrays)
-    bool pro_lrelu = false;
-    Act out; int yoff = 0;  // destination buffer and channel offset
-    int cout_store = -1;    // columns stored (default: out slice padded width)
-    int act = ACT_NONE;
-    const Act* res = nullptr; bool res_ups = false;
-    const ConvDef* aux = nullptr; Act aux_in;   // fused 1x1 shortcut operand (accumulated into the same output)
-    PRef y_nchw;            // optional NCHW copy
-    PRef y_user;            // when set, y is this user tensor (yC = cout exactly)
-    bool y_none = false;    // no NHWC destination at all (a head that only writes its NCHW copy)
-    bool want_stats = false;
-    Norm* stats_out = nullptr; size_t stats_choff = 0;  // finalize target (+channel offset)
-    bool affine = false;    // finalize with the conv's IN gamma/beta
-    bool stats_now = false; // emit the finalize launch at the producer (the arrays are shared / copied between plans)
-    // Two convolutions of identical shape in one launch (IgemmParams::pair): `pair` is the second one; `in` / `out` hold
-    // 2B images (image 2b + j belongs to convolution j).  pair_merge: the outputs of a pair land in ONE image of `out`
-    // (B images) at channel offsets yoff and yoff + pair_yoff, and their statistics in one row of stats_out.
-    const ConvDef* pair = nullptr; bool pair_merge = false; int pair_yoff = 0;
-    bool no_split = false;              // never grid-level split-K (the paired launch cannot, and its unpaired twins must match it)
-    std::vector<std::string> choice_names;   // tuned-choice keys tried before the op's own name
-  };
-
-  // Winograd F(2x2, 3x3) / F(4x4, 3x3) on the small maps (k_wino_in / batched 1x1 k_igemm / k_wino_out; kernels.hip.h):
-  // maps up to 128x128 (1024x1024 frames: +3.5 % at batch 1 and 4); beyond that V and M (4x the activation each)
-  // leave the caches and the direct kernel, which fills the chip there, was not beaten
-  // (opname: of a convolution with a fused shortcut - the tuned table decides for those, shortcut_wino_m)
-  bool runs_wino(const ConvArgs& a, int Hout, int Wout, const std::string& opname = std::string()) const {
-    const ConvDef& c = *a.cd;
-    return h->prec() == PREC_F32 && (a.aux ? c.wino_s_ok : c.wino_ok) && !a.ups && !a.res_ups && !a.pair && !a.in.virt && a.y_nchw.sp == PS_NULL &&
-           a.y_user.sp == PS_NULL && (long)Hout * Wout <= pol.wino_max_px && Hout >= 2 && Wout >= 2 &&
-           (!a.aux || (!a.res && shortcut_wino_m(c, *a.aux, opname, Hout, Wout) != 0));
-  }
-  // F(4x4, 3x3) where its per-position GEMM still has >= 256 rows (conv_wino), else F(2x2, 3x3)
-  int default_wino_m(int Hout, int Wout) const { return (long)TB_() * ((Hout + 3) / 4) * ((Wout + 3) / 4) >= 256 ? 4 : 2; }
-  // Winograd tile (2 / 4) of a 3x3 convolution with its learned 1x1 shortcut fused in, 0: it stays a direct launch.  The cost
-  // model keeps the direct launch; a tuned entry for "<op>.wino" or "<op>.wino4" of this shape (its variant: the GEMM tile)
-  // switches the layer over.  The batched GEMM with a K extent per position exists in k_gemm_dma only.
-  int shortcut_wino_m(const ConvDef& c, const ConvDef& s, const std::string& opname, int Hout, int Wout) const {
-    if (!pol.wino_shortcut || !pol.fuse_shortcut || opname.empty() || !c.fb_off || s.ks != 1 || s.coutp != c.coutp || s.cinp % 32 != 0 || c.cinp % 32 != 0) return 0;
-    if (!pick_gemm_dma(h->prec(), 16, 64, c.coutp, c.cinp)) return 0;
-    if (pol.wino_shortcut_m == 2 || pol.wino_shortcut_m == 4) return pol.wino_shortcut_m;
-    const int d = default_wino_m(Hout, Wout);
-    for (int m : {d, 6 - d})
-      if (h->choices.count(fmt("%d,%d,%d|%s%s", TB_(), P->H, P->W, opname.c_str(), m == 2 ? ".wino" : ".wino4"))) return m;
-    return 0;
-  }
-  // would conv `cd` on an HxW map (stride 1, plain arguments) run in the Winograd domain?  (callers that want to hand it a lazy input)
-  bool would_wino(const ConvDef& cd, int H, int W) const { ConvArgs t; t.cd = &cd; return runs_wino(t, H, W); }
-
-  bool conv(const ConvArgs& a, const std::string& opname) {
-    const ConvDef& c = *a.cd;
-    const int Hout = a.ups ? a.in.H * 2 : (c.stride == 2 ? a.in.H / 2 : a.in.H);
-    const int Wout = a.ups ? a.in.W * 2 : (c.stride == 2 ? a.in.W / 2 : a.in.W);
-    if (a.in.virt) return conv_lowc(a, opname);
-    const int nB = a.pair ? 2 * B : B;       // images in `in`
-    if (a.pair) {
-      const ConvDef& d = *a.pair;
-      if (d.cinp != c.cinp || d.coutp != c.coutp || d.cout != c.cout || d.ks != c.ks || d.stride != c.stride || d.ups_in || c.ups_in || a.ups || a.res || a.aux ||
-          a.y_nchw.sp != PS_NULL || a.y_user.sp != PS_NULL || a.y_none || !a.want_stats || c.in_affine != d.in_affine || d.w_off <= c.w_off || d.b_off <= c.b_off ||
-          (c.in_affine && (d.g_off <= c.g_off || d.g_off - c.g_off != d.be_off - c.be_off)) || (h->mc16() && d.w16_off <= c.w16_off)) {
-        error = opname + ": the two convolutions of a paired launch must have the same shape"; return false;
-      }
-    }
-    if (a.in.Cp != c.cinp) { error = fmt("%s: input channels %d != expected %d", opname.c_str(), a.in.Cp, c.cinp); return false; }
-    if (runs_wino(a, Hout, Wout, opname)) return conv_wino(a, opname, Hout, Wout);
-    if (a.in.lazy) { error = opname + ": a lazy input (" + a.in.lazy->name + ") needs the Winograd path"; return false; }
-    if (a.aux && a.aux_in.lazy) { error = opname + ": a lazy shortcut input (" + a.aux_in.lazy->name + ") needs the Winograd path"; return false; }
-    // split-K needs the slab-summing epilogue: float4 channel groups that tile a 256-thread block,
-    // and no NCHW side copy
-    const bool can_split = (256 % (c.coutp / 4) == 0) && a.y_nchw.sp == PS_NULL && !a.pair && !a.no_split && pol.split_k;
-    // the 16-column path serves layers with <= 16 output channels and no residual read
-    const bool can_n16 = c.cout <= 16 && !a.res && !h->mc16() && pol.n16;
-    Choice ch = choose_variant(h->prec(), c.stride, c.ks, a.ups, false, c.coutp, TB_(), Hout, Wout, c.cinp, can_split, a.aux ? a.aux->cinp : 0, can_n16);
-    {
-      auto it = h->choices.end();
-      for (const std::string& nm : a.choice_names) {
-        it = h->choices.find(fmt("%d,%d,%d|%s", TB_(), P->H, P->W, nm.c_str()));
-        if (it != h->choices.end()) break;
-      }
-      if (it == h->choices.end()) it = h->choices.find(fmt("%d,%d,%d|%s", TB_(), P->H, P->W, opname.c_str()));
-      if (it != h->choices.end()) {
-        const Variant& tv = kVariants[it->second.first];
-        const int ts = it->second.second;
-        const bool ok = !tv.dma() && !(tv.DMAK && (a.aux || ts != 1)) && !(tv.DMAK && !tv.fn_pro && !tv.fn && (a.pro || a.pro_lrelu)) && tv.BF16 == h->prec() && tv.STRIDE == c.stride && tv.KS == c.ks && tv.UPS == a.ups && !tv.SPADE && c.cinp % tv.BK == 0 &&
-                        (!a.aux || a.aux->cinp % tv.BK == 0) && (tv.NF != 0 || (can_n16 && ts == 1)) &&
-                        ts >= 1 && ts <= c.cinp / tv.BK && (ts == 1 || can_split);
-        if (!ok) { error = fmt("%s: tuned choice (variant %d, ksplit %d) does not fit this layer", opname.c_str(), it->second.first, ts); return false; }
-        ch.v = &tv; ch.ksplit = ts;
-      }
-    }
-    const Variant* v = ch.v;
-    if (!v) { error = fmt("%s: no kernel variant for Cin=%d stride=%d ks=%d ups=%d", opname.c_str(), c.cinp, c.stride, c.ks, (int)a.ups); return false; }
-    const int S = ch.ksplit;
-    OpOf<IgemmParams> op(RIB_KC_IGEMM, opname); op.var = v;
-    IgemmParams& p = op.p();
-    p.Hin = a.in.H; p.Win = a.in.W; p.xC = a.in.Cp; p.Cin = c.cinp;
-    p.pro_ld = a.pro ? a.pro->ld : 0; p.pro_lrelu = a.pro_lrelu ? 1 : 0;
-    p.CoutPad = c.coutp;
-    p.Hout = Hout; p.Wout = Wout;
-    // phase-decomposed upsample conv: tiles of SOURCE pixels (each yields a 2TH x 2TW output patch)
-    p.tilesX = ((a.ups ? a.in.W : Wout) + v->TW() - 1) / v->TW(); p.tilesY = ((a.ups ? a.in.H : Hout) + v->TH() - 1) / v->TH();
-    p.xcd_chunk = xcd_chunk_of(p.tilesX * p.tilesY);
-    if (a.ups && (!c.ups_in || c.ks != 3 || c.stride != 1)) { error = opname + ": no phase filters for this upsample convolution"; return false; }
-    p.act = a.act; p.ksplit = S;
-    op.bind(&IgemmParams::x, WS(a.in.off));
-    // heads with 1..4 output channels (conv_img, conv_mask.0): direct convolution on the vector ALUs; the
-    // matrix-core kernels would pad N to 16 columns.  y_nchw's channel count is Cout of the conv itself.
-    const bool small = c.cout <= 4 && c.ks == 3 && c.stride == 1 && !a.ups && !a.res && !a.aux && !a.want_stats &&
-                       c.cinp <= 32 && 256 % (c.cinp / 4) == 0 &&   // halo tile + filter within the default 64 KB of dynamic LDS
-                       pol.small_conv;
-    if (a.pro) {
-      // (a consumer-side finalize in the PROLOGUE was tried and removed: its (scale, shift) table cost every prologue
-      // variant 4 KB of LDS - an occupancy step for several of them - to save four launches; the SPADE epilogue keeps its own)
-      materialize(*a.pro, opname);
-      op.bind(&IgemmParams::pro_scale, WS(a.pro->sc + a.pro_choff * sizeof(float)));
-      op.bind(&IgemmParams::pro_shift, WS(a.pro->sh + a.pro_choff * sizeof(float)));
-    }
-    // matrix-core kernels of a bf16 handle read the bf16 filter copies; the direct head convolutions keep fp32 filters
-    const bool w16 = h->mc16() && !small;
-    op.bind(&IgemmParams::w, WT(a.ups ? (w16 ? c.wp16_off : c.wp_off) : (w16 ? c.w16_off : c.w_off))); op.bind(&IgemmParams::bias, WT(c.b_off));
-    double aux_flops = 0.0;
-    if (a.aux) {
-      if (c.ks != 3 || c.stride != 1 || a.ups || !c.fb_off || a.aux->ks != 1 || a.aux->coutp != c.coutp || a.aux_in.Cp != a.aux->cinp ||
-          a.aux_in.H != Hout || a.aux_in.W != Wout) { error = opname + ": fused shortcut operand does not fit"; return false; }
-      op.bind(&IgemmParams::x2, WS(a.aux_in.off)); op.bind(&IgemmParams::w2, WT(h->mc16() ? a.aux->w16_off : a.aux->w_off)); op.bind(&IgemmParams::bias, WT(c.fb_off));
-      p.x2C = a.aux_in.Cp; p.Cin2 = a.aux->cinp;
-      aux_flops = 2.0 * a.aux->cin * a.aux->cout * (double)Hout * Wout * B;
-    }
-    if (a.y_user.sp != PS_NULL) {
-      op.bind(&IgemmParams::y, a.y_user); p.yC = c.cout; p.yoff = 0; p.Cout = c.cout; p.y_f32 = 1;   // a caller's fp32 tensor
-    } else if (a.y_none) {
-      p.yC = 0; p.yoff = 0; p.Cout = a.cout_store >= 0 ? a.cout_store : c.cout;
-    } else {
-      op.bind(&IgemmParams::y, WS(a.out.off)); p.yC = a.out.Cp; p.yoff = a.yoff;
-      p.Cout = a.cout_store >= 0 ? a.cout_store : h->padc(c.cout);
-      if (a.out.H != Hout || a.out.W != Wout) { error = fmt("%s: output size mismatch", opname.c_str()); return false; }
-    }
-    if (a.pair) {
-      const bool w16p = h->mc16();
-      p.w_mod = 2;
-      p.w_stride = (unsigned)(w16p ? 2 * (a.pair->w16_off - c.w16_off) : a.pair->w_off - c.w_off);      // elements of the filter's storage type
-      p.b_stride = (unsigned)(a.pair->b_off - c.b_off);
-      p.pair = a.pair_merge ? 1 : 0; p.pair_yoff = a.pair_yoff;
-    }
-    if (a.res) { op.bind(&IgemmParams::res, WS(a.res->off)); p.resC = a.res->Cp; p.res_ups = a.res_ups ? 1 : 0; }
-    op.bind(&IgemmParams::y_nchw, a.y_nchw);
-    if (a.y_none && !(small && c.cout <= 3 && (c.cinp == 16 || c.cinp == 32) && pol.head_conv && a.y_nchw.sp != PS_NULL)) {
-      error = opname + ": only the head kernel can run without an NHWC destination"; return false;
-    }
-    if (small) {
-      op.small_co = c.cout;
-      op.head = c.cout <= 3 && (c.cinp == 16 || c.cinp == 32) && pol.head_conv;
-      // the mask head has every pixel's mask in a register: the driver's blend (evaluator.py:256-258) rides along
-      op.fuse_blend = op.head && c.cout == 1 && a.y_user.sp == PS_USER && a.y_user.off == (size_t)U_MASK;
-      p.bl_C = h->g.c.image_nc;
-      p.ksplit = 1;
-      p.tilesX = (Wout + 15) / 16; p.tilesY = (Hout + 15) / 16; p.xcd_chunk = xcd_chunk_of(p.tilesX * p.tilesY);
-      op.grid = dim3(p.tilesX * p.tilesY, 1, B);
-      op.flops = 2.0 * c.cin * c.ks * c.ks * c.cout * (double)Hout * Wout * B;
-      P->flops[RIB_KC_IGEMM] += op.flops;
-      push(op);
-      return true;
-    }
-    int tiles = p.tilesX * p.tilesY;
-    size_t part_off = 0;
-    op.grid = dim3(tiles, v->NF == 0 ? 1 : (c.coutp + v->BN() - 1) / v->BN(), nB * S);
-    op.flops = 2.0 * c.cin * c.ks * c.ks * c.cout * (double)Hout * Wout * nB + aux_flops;
-    P->flops[RIB_KC_IGEMM] += op.flops;
-    if (a.pair && (S != 1 || v->NF == 0)) { error = opname + ": a paired launch cannot split K or use the 16-column path"; return false; }
-    if (S == 1) {
-      if (a.want_stats) { part_off = alloc((size_t)nB * tiles * 2 * c.coutp * sizeof(double)); op.bind(&IgemmParams::stat_part, WS(part_off)); }
-      push(op);
-    } else {
-      // split-K: the conv writes raw partial slabs; a second kernel sums them and runs the epilogue
-      const size_t slab_off = alloc((size_t)S * B * Hout * Wout * c.coutp * sizeof(float));
-      op.bind(&IgemmParams::slab, WS(slab_off));
-      OpOf<SplitEpiParams> e(RIB_KC_CONVAUX, opname + ".splitk_sum");
-      SplitEpiParams& q = e.p();
-      q.ksplit = S; q.B = B; q.CoutPad = c.coutp; q.yC = p.yC; q.yoff = p.yoff; q.Cout = p.Cout;
-      q.act = p.act; q.resC = p.resC; q.res_ups = p.res_ups; q.Hout = Hout; q.Wout = Wout;
-      const int slots = 256 / (c.coutp / 4), ppb = slots * 4;
-      const int blocks = (Hout * Wout + ppb - 1) / ppb;
-      q.blocks = blocks;
-      // the epilogue launch takes over the convolution's bias, destination and residual
-      e.bind(&SplitEpiParams::slab, WS(slab_off)); e.bind(&SplitEpiParams::bias, op.ref(&IgemmParams::bias));
-      e.bind(&SplitEpiParams::y, op.ref(&IgemmParams::y)); e.bind(&SplitEpiParams::res, op.ref(&IgemmParams::res));
-      if (a.want_stats) { part_off = alloc((size_t)B * blocks * 2 * c.coutp * sizeof(double)); e.bind(&SplitEpiParams::stat_part, WS(part_off)); }
-      e.grid = dim3(blocks, B, 1);
-      tiles = blocks;   // the statistics partials now come from the epilogue kernel's blocks
-      op.bind(&IgemmParams::y, PRef()); op.bind(&IgemmParams::res, PRef());
-      push(op);
-      push(e);
-    }
-    if (a.want_stats) {
-      OpOf<FinalizeParams> f = finalize_op(opname, part_off, tiles, c.coutp, h->padc(c.cout), *a.stats_out, a.stats_choff, Hout, Wout, a.affine ? &c : nullptr, nB);
-      if (a.pair) { f.p().g_stride = a.affine ? (int)(a.pair->g_off - c.g_off) : 0; f.p().pair_merge = a.pair_merge ? 1 : 0; f.p().pair_off = a.pair_yoff; }
-      // (a channel offset means two producers share the arrays - the concatenated encoders of the mask network -
-      // and consumers would need two partial sources: those keep their launch; so does a paired launch)
-      finalize_or_defer(f, a.stats_out, a.stats_choff != 0 || a.stats_now || a.pair != nullptr, part_off, tiles, c.coutp, f.p().inv_count, a.affine, c.g_off, c.be_off);
-    }
-    return true;
-  }
-
-  // first-layer 3x3 convolution over the caller's NCHW tensors (k_conv_lowc): no packed copy, reduction over the real channels
-  bool conv_lowc(const ConvArgs& a, const std::string& opname) {
-    const ConvDef& c = *a.cd;
-    const int H = a.in.H, W = a.in.W;
-    if (!c.wl_off || c.ks != 3 || c.stride != 1 || a.ups || a.pro || a.res || a.aux || a.y_nchw.sp != PS_NULL || a.y_user.sp != PS_NULL ||
-        a.in.uc[0] + a.in.uc[1] + a.in.uc[2] != c.cin) { error = opname + ": not a layer k_conv_lowc can run"; return false; }
-    if (a.out.H != H || a.out.W != W) { error = fmt("%s: output size mismatch", opname.c_str()); return false; }
-    OpOf<LowcParams> op(RIB_KC_IGEMM, opname); op.lowc_ce = c.lowc_ce; op.lowc_ncol = c.lowc_ncol;
-    LowcParams& p = op.p();
-    p.c0 = a.in.uc[0]; p.c1 = a.in.uc[1]; p.c2 = a.in.uc[2];
-    p.H = H; p.W = W; p.yC = a.out.Cp; p.yoff = a.yoff; p.Cout = a.cout_store >= 0 ? a.cout_store : h->padc(c.cout);
-    p.act = a.act; p.CoutPad = c.coutp;
-    // 8x16 tiles (2048 workgroups at 512x512: two rounds, whose gather / MFMA / store phases overlap) win where the layer is
-    // store-bound and has no statistics (conv_first 44.6 -> 38.4 us); with statistics the finalize of twice the partials
-    // eats the gain (down_lbl.0 -3 +3 us) and the 16-column layer loses (29.5 -> 32.7)
-    const int tw = pol.lowc_tw ? pol.lowc_tw : ((c.lowc_ncol == 64 && !a.want_stats) ? 16 : 32);
-    op.lowc_tw = tw;
-    p.tilesX = (W + tw - 1) / tw; p.tilesY = (H + 7) / 8;
-    if (p.Cout > c.lowc_ncol || c.cout > c.lowc_ncol) { error = opname + ": more output columns than the k_conv_lowc instantiation has"; return false; }
-    op.bind(&LowcParams::s0, US(a.in.usrc[0])); if (p.c1) op.bind(&LowcParams::s1, US(a.in.usrc[1])); if (p.c2) op.bind(&LowcParams::s2, US(a.in.usrc[2]));
-    op.bind(&LowcParams::w, WT(c.wl_off)); op.bind(&LowcParams::bias, WT(c.b_off)); op.bind(&LowcParams::y, WS(a.out.off));
-    const int tiles = p.tilesX * p.tilesY;
-    size_t part_off = 0;
-    if (a.want_stats) { part_off = alloc((size_t)B * tiles * 2 * c.coutp * sizeof(double)); op.bind(&LowcParams::stat_part, WS(part_off)); }
-    op.grid = dim3(tiles, B, 1);
-    op.flops = 2.0 * c.cin * 9.0 * c.cout * (double)H * W * B;
-    P->flops[RIB_KC_IGEMM] += op.flops;
-    push(op);
-    if (a.want_stats) {
-      OpOf<FinalizeParams> f = finalize_op(opname, part_off, tiles, c.coutp, h->padc(c.cout), *a.stats_out, a.stats_choff, H, W, a.affine ? &c : nullptr, B);
-      finalize_or_defer(f, a.stats_out, a.stats_choff != 0 || a.stats_now, part_off, tiles, c.coutp, f.p().inv_count, a.affine, c.g_off, c.be_off);
-    }
-    return true;
-  }
-
-  bool conv_wino(const ConvArgs& a, const std::string& opname, int Hout, int Wout) {
-    const ConvDef& c = *a.cd;
-    // F(4x4, 3x3) (36 positions, 1/4 of the multiplications) where its per-position GEMM still has >= 256 rows (maps of
-    // 64x64 and more at batch 1); below that the 36 GEMMs are filter-streaming-bound (512x512 filters x 36 = 38 MB for 64
-    // rows) and F(2x2, 3x3) (16 positions, 4/9) is faster.  Measured per layer at 512x512, transforms included:
-    // 256->256 at 64x64 42.4 -> 37.3 us, 512->256 at 64x64 67.4 -> 56.2; 512->512 at 32x32 38.3 -> 41.0 (kept on F(2x2)).
-    // RIB_WINO_M = 2 / 4 forces one of them.
-    const int wino_force = pol.wino_force;
-    const int wm = a.aux ? shortcut_wino_m(c, *a.aux, opname, Hout, Wout) : (wino_force == 2 || wino_force == 4 ? wino_force : default_wino_m(Hout, Wout));
-    const int NP = (wm + 2) * (wm + 2);      // output tile edge, Winograd positions
-    const int tilesY = (Hout + wm - 1) / wm, tilesX = (Wout + wm - 1) / wm, ntiles = tilesY * tilesX;
-    const std::string gname = opname + (wm == 2 ? ".wino" : ".wino4");
-    // a fused 1x1 shortcut: K2 more columns in every row of V and U, written / read at the centre-tap positions only (kmask)
-    const int K2 = a.aux ? a.aux->cinp : 0, ldv = c.cinp + K2;
-    unsigned long long kmask = 0;
-    if (a.aux) {
-      if (a.aux_in.Cp != K2 || a.aux_in.H != Hout || a.aux_in.W != Wout || a.in.H != Hout || a.in.W != Wout) { error = opname + ": fused shortcut operand does not fit"; return false; }
-      for (int r = 1; r <= wm; ++r) for (int q = 1; q <= wm; ++q) kmask |= 1ull << (r * (wm + 2) + q);
-    }
-    const size_t v_off = alloc((size_t)B * NP * ntiles * ldv * sizeof(float));
-    const size_t m_off = alloc((size_t)B * NP * ntiles * c.coutp * sizeof(float));
-    {   // input transform (with the convolution's prologue)
-      OpOf<WinoInParams> op(RIB_KC_CONVAUX, opname + ".wino_in"); op.for_op = gname; op.wino_m = wm;
-      WinoInParams& wi = op.p();
-      wi.H = a.in.H; wi.W = a.in.W; wi.xC = a.in.Cp; wi.Cin = c.cinp; wi.tilesY = tilesY; wi.tilesX = tilesX;
-      wi.pro_lrelu = a.pro_lrelu ? 1 : 0; wi.ldv = ldv;
-      op.bind(&WinoInParams::x, WS(a.in.off)); op.bind(&WinoInParams::v, WS(v_off));
-      if (a.in.lazy) {
-        const LazySrc& L = *a.in.lazy;
-        if (a.pro || a.pro_lrelu) { error = gname + ": a lazy input carries its own prologue"; return false; }
-        op.wi_mode = L.mode;
-        op.bind(&WinoInParams::x, WS(L.x.off)); wi.xC = L.x.Cp;
-        wi.pro_ld = L.nx.ld;
-        if (!take_partials(L.nx, op, &WinoInParams::st)) { materialize(L.nx, gname); op.bind(&WinoInParams::pro_scale, WS(L.nx.sc)); op.bind(&WinoInParams::pro_shift, WS(L.nx.sh)); }
-        if (L.mode == WSRC_SPADE) {
-          wi.x_ups = L.x_ups ? 1 : 0; wi.pro_lrelu = L.lrelu ? 1 : 0;
-          op.bind(&WinoInParams::slab, WS(L.slab_off)); wi.slab_ld = L.slab_ld; wi.col0 = L.col0; op.bind(&WinoInParams::sbias, WT(L.sbias_off));
-        } else {
-          if (L.has2) {
-            op.bind(&WinoInParams::x2, WS(L.x2.off));
-            if (L.n2.ld != L.nx.ld) { error = gname + ": join operands with different statistics rows"; return false; }
-            if (!take_partials(L.n2, op, &WinoInParams::st2)) { materialize(L.n2, gname); op.bind(&WinoInParams::pro2_scale, WS(L.n2.sc)); op.bind(&WinoInParams::pro2_shift, WS(L.n2.sh)); }
-          } else op.bind(&WinoInParams::xres, WS(L.xres.off));
-          op.bind(&WinoInParams::o, WS(L.o.off));
-        }
-      } else if (a.pro && !(a.pro_choff == 0 && take_partials(*a.pro, op, &WinoInParams::st))) {
-        materialize(*a.pro, gname);
-        wi.pro_ld = a.pro->ld;
-        op.bind(&WinoInParams::pro_scale, WS(a.pro->sc + a.pro_choff * sizeof(float))); op.bind(&WinoInParams::pro_shift, WS(a.pro->sh + a.pro_choff * sizeof(float)));
-      }
-      if (a.aux) {      // second source: the shortcut's input, stored or the never-stored second set of the block's first SPADE
-        if (op.wi_mode == WSRC_JOIN) { error = gname + ": a join cannot carry a second source"; return false; }
-        wi.nslices2 = (K2 + 63) / 64; wi.Cin2 = K2; wi.xC2 = a.aux_in.Cp;
-        op.wi_mode2 = WSRC_PLAIN;
-        if (a.aux_in.lazy) {
-          const LazySrc& L = *a.aux_in.lazy;
-          if (L.mode != WSRC_SPADE) { error = gname + ": lazy shortcut input of an unknown kind"; return false; }
-          op.wi_mode2 = WSRC_SPADE;
-          op.bind(&WinoInParams::x2, WS(L.x.off)); wi.xC2 = L.x.Cp; wi.pro2_ld = L.nx.ld; wi.x2_ups = L.x_ups ? 1 : 0; wi.lrelu2 = L.lrelu ? 1 : 0;
-          if (!take_partials(L.nx, op, &WinoInParams::st2)) { materialize(L.nx, gname); op.bind(&WinoInParams::pro2_scale, WS(L.nx.sc)); op.bind(&WinoInParams::pro2_shift, WS(L.nx.sh)); }
-          op.bind(&WinoInParams::slab2, WS(L.slab_off)); wi.slab2_ld = L.slab_ld; wi.col0_2 = L.col0; op.bind(&WinoInParams::sbias2, WT(L.sbias_off));
-        } else op.bind(&WinoInParams::x2, WS(a.aux_in.off));
-      }
-      // workgroup = (16 (tile, transformed row) units per pass) x (slice of 64 channels)
-      const int nsl = (c.cinp + 63) / 64 + wi.nslices2, units = ntiles * (wm + 2);
-      // (every workgroup that reduces partials re-reads tiles x 64 channels x 16 bytes: few, fatter workgroups then)
-      wi.nslices = nsl; wi.ublocks = std::max(1, std::min((units + 15) / 16, (wi.st.tiles > 0 ? 512 : 4096) / nsl));
-      // Staged (k_wino_in_staged): workgroup = (block of sty x stx whole tiles, patch in LDS) x (slice of 64 channels).  The
-      // largest block of the list wins whose grid still has a workgroup per CU, or as many as the unstaged grid where that
-      // one has fewer (a fatter block fetches fewer halo pixels twice: 100 / 64 for 10 x 10 against 36 / 16 for 6 x 6).
-      // The launch stays unstaged when (a) the staged kernel's static LDS would leave fewer than 2 workgroups per CU - it is
-      // sized for the largest patch of the list, so this holds for every block or for none - or (b) no block of the list
-      // keeps the grid at that bar.  Every class (tile x first source) of the 512x512 frame is faster staged
-      // (profiles/r10_wino_in_staged.txt), so none is excluded here.
-      if (h->wino_in_staging) {
-        static const int kBlocks2[][2] = {{4, 4}, {2, 4}, {2, 2}}, kBlocks4[][2] = {{2, 2}, {1, 2}, {1, 1}};
-        const int need = std::min((int)(wi.ublocks * nsl * B), 256 /* CUs */);
-        const bool fits = 2 * WINO_STAGE_LDS_BYTES <= 160 * 1024 /* LDS of a CU */;
-        for (int i = 0; i < 3 && fits && !op.wi_staged; ++i) {
-          const int sty = std::min((wm == 4 ? kBlocks4 : kBlocks2)[i][0], tilesY), stx = std::min((wm == 4 ? kBlocks4 : kBlocks2)[i][1], tilesX);
-          const int nblocks = ((tilesY + sty - 1) / sty) * ((tilesX + stx - 1) / stx);
-          if ((wm * sty + 2) * (wm * stx + 2) > WINO_STAGE_MAX_PX || nblocks * nsl * B < need) continue;
-          op.wi_staged = true; wi.sty = sty; wi.stx = stx; wi.ublocks = nblocks;
-        }
-      }
-      op.grid = dim3(wi.ublocks * nsl, B, 1);
-      push(op);
-    }
-    {   // the 16 / 36 GEMMs as one 1x1 "convolution" of NP*B samples of a tilesY x tilesX image, one filter set per position
-      // k_gemm_dma (operands staged by LDS-DMA) unless a tuned choice names a k_igemm 1x1 variant; TB_() decides as for every choice
-      Choice ch;
-      ch.v = pick_gemm_dma(h->prec(), (long)TB_() * NP, ntiles, c.coutp, c.cinp);
-      if (!ch.v) ch = choose_variant(h->prec(), 1, 1, false, false, c.coutp, TB_() * NP, tilesY, tilesX, c.cinp, false, 0, false);
-      auto it = h->choices.find(fmt("%d,%d,%d|%s", TB_(), P->H, P->W, gname.c_str()));
-      if (it != h->choices.end()) {
-        const Variant& tv = kVariants[it->second.first];
-        if (tv.BF16 != h->prec() || tv.KS != 1 || tv.STRIDE != 1 || tv.UPS || tv.SPADE || tv.NF == 0 || c.cinp % tv.BK != 0 || it->second.second != 1 || (a.aux && !tv.dma())) {
-          error = fmt("%s: tuned choice (variant %d, ksplit %d) does not fit this layer", gname.c_str(), it->second.first, it->second.second); return false;
-        }
-        ch.v = &tv; ch.ksplit = 1;
-      }
-      const Variant* v = ch.v;
-      if (!v) { error = gname + ": no 1x1 kernel variant"; return false; }
-      if (a.aux && !v->dma()) { error = gname + ": the fused shortcut needs a k_gemm_dma tile"; return false; }
-      const int set = ensure_wino_set(h, (int)(&c - h->convs.data()), wm, a.aux ? (int)(a.aux - h->convs.data()) : -1);
-      if (set < 0) { error = gname + ": " + h->err; return false; }
-      // the convolution's algorithmic count (executed: 4/9 or 1/4 of it) + the shortcut's (executed as it is)
-      const double fl = 2.0 * c.cin * 9.0 * c.cout * (double)Hout * Wout * B + (a.aux ? 2.0 * a.aux->cin * a.aux->cout * (double)Hout * Wout * B : 0.0);
-      P->flops[RIB_KC_IGEMM] += fl;
-      if (v->dma()) {
-        // M[n*NP + xi] = V[n*NP + xi] . U[xi]^T: Z = B*NP problems of ntiles x coutp x cinp
-        OpOf<GemmDmaParams> op(RIB_KC_IGEMM, gname); op.var = v; op.wino = true; op.wino_m = wm; op.flops = fl;
-        GemmDmaParams& g = op.p();
-        g.M = ntiles; g.N = c.coutp; g.K = c.cinp; g.lda = ldv; g.ldc = c.coutp;
-        g.sA = (size_t)ntiles * ldv; g.sB = (size_t)c.coutp * ldv; g.sC = (size_t)ntiles * c.coutp; g.modB = NP;
-        g.K2 = K2; g.kmask = kmask;
-        op.bind(&GemmDmaParams::A, WS(v_off)); op.bind(&GemmDmaParams::B, WINO(set)); op.bind(&GemmDmaParams::C, WS(m_off));
-        op.grid = dim3((ntiles + v->BM() - 1) / v->BM(), (c.coutp + v->BN() - 1) / v->BN(), B * NP);
-        push(op);
-      } else {
-      OpOf<IgemmParams> op(RIB_KC_IGEMM, gname); op.var = v; op.wino = true; op.wino_m = wm; op.flops = fl;
-      IgemmParams& p = op.p();
-      p.Hin = tilesY; p.Win = tilesX; p.xC = c.cinp; p.Cin = c.cinp; p.CoutPad = c.coutp; p.Hout = tilesY; p.Wout = tilesX;
-      p.tilesX = (tilesX + v->TW() - 1) / v->TW(); p.tilesY = (tilesY + v->TH() - 1) / v->TH(); p.xcd_chunk = xcd_chunk_of(p.tilesX * p.tilesY);
-      p.act = ACT_NONE; p.ksplit = 1; p.yC = c.coutp; p.yoff = 0; p.Cout = c.coutp;
-      p.w_mod = NP; p.w_stride = (unsigned)((size_t)c.coutp * c.cinp);
-      op.bind(&IgemmParams::x, WS(v_off)); op.bind(&IgemmParams::w, WINO(set)); op.bind(&IgemmParams::bias, WT(c.zero_off)); op.bind(&IgemmParams::y, WS(m_off));
-      op.grid = dim3(p.tilesX * p.tilesY, (c.coutp + v->BN() - 1) / v->BN(), B * NP);
-      push(op);
-      }
-    }
-    {   // output transform + the convolution's epilogue
-      OpOf<WinoOutParams> op(RIB_KC_CONVAUX, opname + ".wino_out"); op.for_op = gname; op.wino_m = wm;
-      WinoOutParams& wo = op.p();
-      // workgroup = (16 (tile, output row) units per pass) x (slice of 64 channels); ONE statistics partial per unit block,
-      // at most STATS_MAX_PARTIALS of them, so the consumer of the normalised tensor can reduce them itself
-      const int nsl = (c.coutp + 63) / 64, units = ntiles * wm;
-      const int blocks = std::max(1, std::min((units + 15) / 16, (int)STATS_MAX_PARTIALS));
-      wo.tilesY = tilesY; wo.tilesX = tilesX; wo.CoutPad = c.coutp; wo.ublocks = blocks; wo.nslices = nsl;
-      wo.yC = a.out.Cp; wo.yoff = a.yoff; wo.Cout = a.cout_store >= 0 ? a.cout_store : h->padc(c.cout);
-      wo.Hout = Hout; wo.Wout = Wout; wo.act = a.act;
-      if (a.out.H != Hout || a.out.W != Wout) { error = fmt("%s: output size mismatch", opname.c_str()); return false; }
-      op.bind(&WinoOutParams::m, WS(m_off)); op.bind(&WinoOutParams::bias, WT(a.aux ? c.fb_off : c.b_off)); op.bind(&WinoOutParams::y, WS(a.out.off));
-      if (a.res) { op.bind(&WinoOutParams::res, WS(a.res->off)); wo.resC = a.res->Cp; }
-      size_t part_off = 0;
-      if (a.want_stats) { part_off = alloc((size_t)B * blocks * 2 * c.coutp * sizeof(double)); op.bind(&WinoOutParams::stat_part, WS(part_off)); }
-      op.grid = dim3(blocks * nsl, B, 1);
-      push(op);
-      if (a.want_stats) {
-        OpOf<FinalizeParams> f = finalize_op(opname, part_off, blocks, c.coutp, h->padc(c.cout), *a.stats_out, a.stats_choff, Hout, Wout, a.affine ? &c : nullptr, B);
-        finalize_or_defer(f, a.stats_out, a.stats_choff != 0 || a.stats_now, part_off, blocks, c.coutp, f.p().inv_count, a.affine, c.g_off, c.be_off);
-      }
-    }
-    return true;
-  }
-
-  // ---- gamma/beta of EVERY SPADE of a condition level in one 1x1 GEMM (round 3) -----------------------------------------
-  // The gamma/beta of a SPADE depend only on the condition map.  On the small deep maps (<= 64x64 at 512x512, batch 1) each
-  // SPADE's own GEMM is a 10-30 us launch of which 10-13 us are ramp and drain, and the ten of them
-  // that ran unfused were ten such launches.  The filter matrices of a level's SPADE groups lie back to back in the blob,
-  // so ONE k_igemm 1x1 launch on cond[level] with N = sum of their columns (8192 at level 4, 2048 at level 3 of HSM.yaml:
-  // 8.6 GFLOP each) writes a slab [B][H*W][N] and every SPADE of the level is then only its k_spade_modulate on its own
-  // column range.  Levels whose map is larger stay fused (gamma/beta never touch memory there).
-  bool cond_level_gemm(int level, const Act& cond) {
-    const long max_px = pol.cond_gemm_max_px;   // 0: off
-    const auto it = h->level_groups.find(level);
-    if (it == h->level_groups.end() || it->second.size() < 2 || (long)TB_() * cond.H * cond.W > max_px) return true;
-    int N = 0; double fl = 0.0;
-    for (int gi : it->second) {
-      const SpadeGroup& sg = h->spades[gi];
-      if (sg.col0 != N || h->padc(sg.cond) != cond.Cp) { error = fmt("cond level %d: SPADE group %s does not continue the level's filter matrix", level, sg.key.c_str()); return false; }
-      N += sg.npad;
-      fl += 2.0 * sg.cond * 2.0 * sg.nsets * sg.C * (double)cond.H * cond.W * B;
-    }
-    const SpadeGroup& first = h->spades[it->second[0]];
-    const std::string name = fmt("cond_%d.gammabeta", level);
-    Choice ch;
-    ch.v = pick_gemm_dma(h->prec(), TB_(), cond.H * cond.W, N, cond.Cp);
-    if (!ch.v) ch = choose_variant(h->prec(), 1, 1, false, false, N, TB_(), cond.H, cond.W, cond.Cp, false);
-    {
-      auto ct = h->choices.find(fmt("%d,%d,%d|%s", TB_(), P->H, P->W, name.c_str()));
-      if (ct != h->choices.end()) {
-        const Variant& tv = kVariants[ct->second.first];
-        if (tv.BF16 != h->prec() || tv.KS != 1 || tv.STRIDE != 1 || tv.UPS || tv.SPADE || tv.NF == 0 || cond.Cp % tv.BK != 0 || ct->second.second != 1) {
-          error = fmt("%s: tuned choice (variant %d, ksplit %d) does not fit this launch", name.c_str(), ct->second.first, ct->second.second); return false;
-        }
-        ch.v = &tv; ch.ksplit = 1;
-      }
-    }
-    const Variant* v = ch.v;
-    if (!v) { error = name + ": no 1x1 kernel variant"; return false; }
-    const size_t slab_off = alloc((size_t)B * cond.H * cond.W * N * sizeof(float));
-    P->flops[RIB_KC_SPADE] += fl;
-    LevelSlab ls; ls.off = slab_off; ls.ld = N;
-    level_slab[level] = ls;
-    if (v->dma()) {
-      // slab[b] = cond[b] . W_level^T: B problems of (H*W) x N x Cp
-      OpOf<GemmDmaParams> op(RIB_KC_SPADE, name); op.var = v; op.flops = fl;
-      GemmDmaParams& g = op.p();
-      g.M = cond.H * cond.W; g.N = N; g.K = cond.Cp; g.lda = cond.Cp; g.ldc = N;
-      g.sA = (size_t)g.M * cond.Cp; g.sB = 0; g.sC = (size_t)g.M * N; g.modB = 0;
-      op.bind(&GemmDmaParams::A, WS(cond.off)); op.bind(&GemmDmaParams::B, WT(h->mc16() ? first.w16_off : first.w_off)); op.bind(&GemmDmaParams::C, WS(slab_off));
-      op.grid = dim3((g.M + v->BM() - 1) / v->BM(), (N + v->BN() - 1) / v->BN(), B);
-      push(op);
-      return true;
-    }
-    OpOf<IgemmParams> op(RIB_KC_SPADE, name); op.var = v; op.flops = fl;
-    IgemmParams& p = op.p();
-    p.Hin = cond.H; p.Win = cond.W; p.xC = cond.Cp; p.Cin = cond.Cp;
-    p.CoutPad = N; p.Hout = cond.H; p.Wout = cond.W; p.ksplit = 1;
-    p.tilesX = (cond.W + v->TW() - 1) / v->TW(); p.tilesY = (cond.H + v->TH() - 1) / v->TH(); p.xcd_chunk = xcd_chunk_of(p.tilesX * p.tilesY);
-    op.bind(&IgemmParams::x, WS(cond.off)); op.bind(&IgemmParams::w, WT(h->mc16() ? first.w16_off : first.w_off));
-    op.bind(&IgemmParams::bias, WT(first.b_off)); op.bind(&IgemmParams::slab, WS(slab_off));
-    op.grid = dim3(p.tilesX * p.tilesY, (N + v->BN() - 1) / v->BN(), B);
-    push(op);
-    return true;
-  }
-
-  // ---- SPADE launch: ys0 (= lrelu(mod0(x))), optional ys1 (= mods(x), no activation) -------
-  // lazy_ok: the only consumer of ys0 is a convolution that runs in the Winograd domain - when this SPADE is just a modulate
-  // of the level's gamma/beta slab, ys0 is not stored: the convolution's input transform computes it (LazySrc).
-  // lazy1_ok: the same for ys1, the second set (the input of the learned shortcut, consumed by conv_block_1's input transform
-  // as its second source).  A set whose consumer needs it stored is produced by k_spade_modulate, for that set alone.
-  bool spade(const std::string& key, const Act& cond, const Act& x, bool x_ups, const Norm& nx,
-             Act* ys0, Act* ys1, bool act0, bool lazy_ok = false, bool lazy1_ok = false) {
-    const SpadeGroup& sg = h->spades[h->spade_index.at(key)];
-    const int Hout = x_ups ? x.H * 2 : x.H, Wout = x_ups ? x.W * 2 : x.W;
-    if (cond.H != Hout || cond.W != Wout) { error = fmt("%s: cond map %dx%d != %dx%d (SPADE resize must be the identity)", key.c_str(), cond.H, cond.W, Hout, Wout); return false; }
-    if (cond.Cp != h->padc(sg.cond) || cond.Cp % 32 != 0) { error = fmt("%s: cond channels %d unsupported (need a multiple of 32)", key.c_str(), cond.Cp); return false; }
-    if (x.Cp != sg.Cp) { error = fmt("%s: x channels %d != %d", key.c_str(), x.Cp, sg.Cp); return false; }
-    // Fused (one kernel: gamma/beta GEMM + modulate epilogue) where the map is large; UNFUSED on the
-    // small deep maps, where the fused kernel is one long K chain on a handful of workgroups: the
-    // GEMM runs as a split-K 1x1 convolution into partial slabs and k_spade_modulate finishes.
-    const Variant* v = choose_variant(h->prec(), 1, 1, false, true, sg.npad, TB_(), Hout, Wout, cond.Cp, false).v;
-    if (sg.w1_off)      // 16 modulated channels: the one-fragment layout halves the matrix work (first fitting NF = 1 variant)
-      for (int i = 0; i < kNumVariants; ++i) {
-        const Variant& t = kVariants[i];
-        if (t.SPADE && t.NF == 1 && t.BF16 == h->prec() && t.KW == 1 && t.TB == 1 && cond.Cp % t.BK == 0) { v = &t; break; }
-      }
-    Choice uf;   // unfused candidate
-    const bool small_map = (long)Hout * Wout * TB_() <= 4096 && pol.unfused_spade;
-    if (small_map) uf = choose_variant(h->prec(), 1, 1, false, false, sg.npad, TB_(), Hout, Wout, cond.Cp, true);
-    bool unfused = small_map && uf.v != nullptr;
-    {
-      auto it = h->choices.find(fmt("%d,%d,%d|%s", TB_(), P->H, P->W, (key + ".spade").c_str()));
-      if (it != h->choices.end()) {
-        const Variant& tv = kVariants[it->second.first];
-        const int ts = it->second.second;
-        if (tv.dma() || tv.BF16 != h->prec() || tv.KS != 1 || tv.STRIDE != 1 || tv.UPS || cond.Cp % tv.BK != 0 || ts < 1 || ts > cond.Cp / tv.BK || (tv.SPADE && ts != 1) ||
-            (tv.SPADE && tv.NF == 1 && !sg.w1_off)) {
-          error = key + ": tuned SPADE choice does not fit"; return false;
-        }
-        if (tv.SPADE) { v = &tv; unfused = false; }
-        else { uf.v = &tv; uf.ksplit = ts; unfused = true; }
-      }
-    }
-    // the level's gamma/beta GEMM already ran (cond_level_gemm): this SPADE is only its modulate
-    const auto lvl = level_slab.find(sg.level);
-    const bool from_level = lvl != level_slab.end();
-    if (from_level) unfused = true;
-    if (!unfused && !v) { error = "no SPADE variant"; return false; }
-    const bool no_lazy = !pol.lazy_sources;
-    // sets that are never stored; set 1 lies (Cp / 32) gamma/beta column groups of 64 behind set 0, in the slab and in the bias
-    const bool can_lazy = from_level && !h->keep_taps && !no_lazy && h->prec() == PREC_F32;
-    // (set 0 of a two-set SPADE only together with set 1: where conv_block_1 keeps its direct launch the plan stays as it was)
-    const bool lz1 = can_lazy && lazy1_ok && sg.nsets == 2 && sg.Cp % 32 == 0;
-    const bool lz0 = can_lazy && lazy_ok && (sg.nsets == 1 || lz1);
-    const int set1_col = sg.Cp / 32 * 64;
-    for (int set = 0; set < 2; ++set) {
-      if (!(set ? lz1 : lz0)) continue;
-      auto L = std::make_shared<LazySrc>();
-      L->mode = WSRC_SPADE; L->name = key + ".spade.modulate"; L->x = x; L->nx = nx; L->x_ups = x_ups; L->lrelu = set ? false : act0;
-      L->slab_off = lvl->second.off; L->slab_ld = lvl->second.ld; L->col0 = sg.col0 + set * set1_col; L->sbias_off = sg.b_off + set * set1_col;
-      Act y; y.C = sg.C; y.Cp = sg.Cp; y.H = Hout; y.W = Wout; y.lazy = L;
-      *(set ? ys1 : ys0) = y;
-    }
-    if (lz0 && (lz1 || sg.nsets == 1)) return true;
-    // the stored sets: both, or set 0 alone when only set 1 is lazy (a launch over the first set's columns)
-    const int mnsets = lz1 ? 1 : sg.nsets;
-    if (unfused) {
-      *ys0 = act(sg.C, Hout, Wout);
-      if (sg.nsets == 2 && !lz1) *ys1 = act(sg.C, Hout, Wout);
-      int S = 1, slab_ld = 0, col0 = 0;
-      size_t slab_off = 0;
-      if (from_level) {
-        slab_off = lvl->second.off; slab_ld = lvl->second.ld; col0 = sg.col0;
-      } else {
-        const Variant* cv = uf.v; S = uf.ksplit;
-        slab_off = alloc((size_t)S * B * Hout * Wout * sg.npad * sizeof(float)); slab_ld = sg.npad;
-        OpOf<IgemmParams> op(RIB_KC_SPADE, key + ".spade"); op.var = cv;
-        IgemmParams& p = op.p();
-        p.Hin = cond.H; p.Win = cond.W; p.xC = cond.Cp; p.Cin = cond.Cp;
-        p.CoutPad = sg.npad; p.Hout = Hout; p.Wout = Wout; p.ksplit = S;
-        p.tilesX = (Wout + cv->TW() - 1) / cv->TW(); p.tilesY = (Hout + cv->TH() - 1) / cv->TH(); p.xcd_chunk = xcd_chunk_of(p.tilesX * p.tilesY);
-        op.bind(&IgemmParams::x, WS(cond.off)); op.bind(&IgemmParams::w, WT(h->mc16() ? sg.w16_off : sg.w_off));
-        op.bind(&IgemmParams::bias, WT(sg.b_off)); op.bind(&IgemmParams::slab, WS(slab_off));
-        op.grid = dim3(p.tilesX * p.tilesY, (sg.npad + cv->BN() - 1) / cv->BN(), B * S);
-        op.flops = 2.0 * sg.cond * 2.0 * sg.nsets * sg.C * (double)Hout * Wout * B;
-        P->flops[RIB_KC_SPADE] += op.flops;
-        push(op);
-      }
-      OpOf<ModulateParams> mo(RIB_KC_ELTWISE, key + ".spade.modulate");
-      ModulateParams& mp = mo.p();
-      mp.ksplit = S; mp.B = B; mp.slab_ld = slab_ld; mp.col0 = col0; mp.xmC = x.Cp; mp.xm_ups = x_ups ? 1 : 0;
-      mp.m_ld = nx.ld; mp.C = sg.Cp; mp.nsets = mnsets; mp.act0 = act0 ? ACT_LRELU : ACT_NONE; mp.act1 = ACT_NONE;
-      mp.Hout = Hout; mp.Wout = Wout;
-      mo.bind(&ModulateParams::slab, WS(slab_off)); mo.bind(&ModulateParams::bias, WT(sg.b_off)); mo.bind(&ModulateParams::xm, WS(x.off));
-      // a slice of 64 virtual channels lies inside one set when C is a multiple of 64: the modulate can then reduce the
-      // producer's partials of its own channels
-      if (!(sg.Cp % 64 == 0 && nx.pend && !nx.pend->affine && sg.Cp <= nx.pend->Cs && take_partials(nx, mo, &ModulateParams::st))) {
-        materialize(nx, key + ".spade");
-        mo.bind(&ModulateParams::m_scale, WS(nx.sc)); mo.bind(&ModulateParams::m_shift, WS(nx.sh));
-      }
-      mo.bind(&ModulateParams::ys0, WS(ys0->off)); if (mnsets == 2) mo.bind(&ModulateParams::ys1, WS(ys1->off));
-      const int nsl = (mnsets * sg.Cp + 63) / 64;
-      mp.nslices = nsl; mp.pblocks = std::max(1, std::min((Hout * Wout + 15) / 16, (mp.st.tiles > 0 ? 384 : 2048) / nsl));
-      mo.grid = dim3(mp.pblocks * nsl, B, 1);
-      push(mo);
-      return true;
-    }
-    *ys0 = act(sg.C, Hout, Wout);
-    if (sg.nsets == 2) *ys1 = act(sg.C, Hout, Wout);
-    OpOf<IgemmParams> op(RIB_KC_SPADE, key + ".spade"); op.var = v;
-    IgemmParams& p = op.p();
-    p.Hin = cond.H; p.Win = cond.W; p.xC = cond.Cp; p.Cin = cond.Cp;
-    const bool one_frag = v->NF == 1;      // [gamma(16) | beta(16)] layout
-    const int ncols = one_frag ? 32 : sg.npad;
-    p.CoutPad = ncols; p.Hout = Hout; p.Wout = Wout;
-    p.tilesX = (Wout + v->TW() - 1) / v->TW(); p.tilesY = (Hout + v->TH() - 1) / v->TH(); p.xcd_chunk = xcd_chunk_of(p.tilesX * p.tilesY);
-    p.ksplit = 1;
-    p.xmC = x.Cp; p.xm_ups = x_ups ? 1 : 0; p.m_ld = nx.ld; p.C = sg.Cp; p.nsets = sg.nsets;
-    p.act0 = act0 ? ACT_LRELU : ACT_NONE; p.act1 = ACT_NONE;
-    op.bind(&IgemmParams::x, WS(cond.off)); op.bind(&IgemmParams::w, WT(h->mc16() ? sg.w16_off : sg.w_off)); op.bind(&IgemmParams::bias, WT(sg.b_off));
-    if (one_frag) { op.bind(&IgemmParams::w, WT(sg.w1_off)); op.bind(&IgemmParams::bias, WT(sg.b1_off)); }
-    op.bind(&IgemmParams::xm, WS(x.off));
-    if (has_partials(nx) && !nx.pend->affine && sg.Cp <= nx.pend->Cs) {   // consumer-side finalize in the SPADE epilogue
-      const PendingStats& ps = *nx.pend;
-      op.bind(&IgemmParams::m_part, WS(ps.part_off)); p.m_tiles = ps.tiles; p.m_Cs = ps.Cs; p.m_inv = ps.inv_count;
-    } else {
-      materialize(nx, key + ".spade");
-      op.bind(&IgemmParams::m_scale, WS(nx.sc)); op.bind(&IgemmParams::m_shift, WS(nx.sh));
-    }
-    op.bind(&IgemmParams::ys0, WS(ys0->off)); if (sg.nsets == 2) op.bind(&IgemmParams::ys1, WS(ys1->off));
-    op.grid = dim3(p.tilesX * p.tilesY, (ncols + v->BN() - 1) / v->BN(), B);
-    op.flops = 2.0 * sg.cond * 2.0 * sg.nsets * sg.C * (double)Hout * Wout * B;
-    P->flops[RIB_KC_SPADE] += op.flops;
-    push(op);
-    return true;
-  }
-
-  // ---- Res2dBlock 'NACNAC' (PGNR/models/layers/residual.py:129-151) -------------------------
-  bool spade_block(const std::string& name, const Act& x, bool x_ups, const Norm& nx, const Act& cond,
-                   Act* out, Norm* nout) {
-    const ConvDef& c0 = conv_of(h, name + ".conv_block_0");
-    const ConvDef& c1 = conv_of(h, name + ".conv_block_1");
-    const bool learned = h->conv_index.count(name + ".conv_block_s") > 0;
-    const int Hout = x_ups ? x.H * 2 : x.H, Wout = x_ups ? x.W * 2 : x.W;
-    Act ys0, ys1;
-    Act hbuf = act(c0.cout, Hout, Wout);
-    Norm nh = norm(hbuf.Cp);
-    // learned shortcut (residual.py:98-108): its 1x1 convolution on SPADE_s(x) is fused into conv_block_1's launch as extra
-    // K chunks accumulating into the same output tile - of the direct kernel, or of the Winograd-domain GEMM (wino1 below)
-    const bool fuse_s = learned && pol.fuse_shortcut;
-    // conv_block_1 runs in the Winograd domain with an identity shortcut at the same resolution (the res blocks), or with a
-    // fused learned shortcut where the tuned table says so (shortcut_wino_m); both SPADE outputs it consumes are then lazy
-    bool wino1;
-    { ConvArgs t; t.cd = &c1;
-      if (fuse_s) t.aux = &conv_of(h, name + ".conv_block_s"); else { t.res = &x; t.res_ups = !learned && x_ups; }
-      wino1 = runs_wino(t, Hout, Wout, name + ".conv_block_1"); }
-    { ConvArgs a; a.cd = &c0; a.out = hbuf; a.want_stats = true; a.stats_out = &nh;
-      if (!spade(name + ".0", cond, x, x_ups, nx, &ys0, &ys1, true, runs_wino(a, Hout, Wout), fuse_s && wino1)) return false;
-      if (!ys0.lazy) tap(name + ".ys0", ys0);
-      a.in = ys0;
-      if (!conv(a, name + ".conv_block_0")) return false; }
-    tap(name + ".h", hbuf);
-    Act y1, dummy;
-    if (!spade(name + ".1", cond, hbuf, false, nh, &y1, &dummy, true, (!learned || fuse_s) && wino1)) return false;
-    if (!y1.lazy) tap(name + ".y1", y1);
-    Act outs;
-    if (learned && !fuse_s) {
-      const ConvDef& cs = conv_of(h, name + ".conv_block_s");
-      outs = act(cs.cout, Hout, Wout);
-      ConvArgs a; a.cd = &cs; a.in = ys1; a.out = outs;
-      if (!conv(a, name + ".conv_block_s")) return false;
-    }
-    *out = act(c1.cout, Hout, Wout);
-    { ConvArgs a; a.cd = &c1; a.in = y1; a.out = *out;
-      if (fuse_s) { a.aux = &conv_of(h, name + ".conv_block_s"); a.aux_in = ys1; }
-      else a.res = learned ? &outs : &x;
-      a.res_ups = !learned && x_ups;   // identity shortcut of an upsampled input: x_up[y][x] = x[y>>1][x>>1]
-      if (nout) { *nout = norm(out->Cp); a.want_stats = true; a.stats_out = nout; }
-      if (!conv(a, name + ".conv_block_1")) return false; }
-    tap(name, *out);
-    return true;
-  }
-
-  // one of the two stride-2 encoders of the mask network (generator.py:449-459); its last level
-  // lands in half of the concatenated tensor and of the concatenated (scale, shift) arrays
-  bool mask_branch(int b, const Act& input, const Act& CAT, const Norm& ncat, int chm) {
-    const rib_config& c = h->g.c;
-    const std::string m = "flow_network_temp";
-    const char* branches[2] = {"down_lbl", "down_img"};
-    Act cur = input; Norm ncur; bool have = false;
-    for (int i = 0; i <= c.mask_down; ++i) {
-      const ConvDef& cd = conv_of(h, m + "." + branches[b] + "." + std::to_string(i));
-      const bool lastl = (i == c.mask_down);
-      Act o = lastl ? CAT : act(cd.cout, i == 0 ? cur.H : cur.H / 2, i == 0 ? cur.W : cur.W / 2);
-      Norm no = lastl ? ncat : norm(h->padc(cd.cout));
-      ConvArgs a; a.cd = &cd; a.in = cur; a.out = o;
-      if (have) { a.pro = &ncur; a.pro_lrelu = true; }
-      if (i >= 1) {      // same kernel choice as the paired launch of this level (mask_branches_paired): bit-identical results
-        a.no_split = true;
-        a.choice_names = {m + ".down_pair." + std::to_string(i), m + ".down_img." + std::to_string(i)};
-      }
-      // the last level's (scale, shift) land in the shared arrays of the concatenated tensor: its finalize is emitted at
-      // the producer (`no` is a local copy of ncat: a deferred finalize attached to it would be lost)
-      if (lastl) { a.yoff = b * chm; a.stats_choff = (size_t)b * chm; a.stats_now = true; }
-      a.want_stats = true; a.stats_out = &no; a.affine = true;
-      if (!conv(a, cd.name)) return false;
-      if (!lastl) tap(std::string("mask.") + (b == 0 ? "lbl_" : "img_") + std::to_string(i) + ".raw", o);
-      cur = o; ncur = no; have = true;
-    }
-    return true;
-  }
-
-  // Both stride-2 encoders of the mask network, level by level (round 3): level i >= 1 of the label encoder and of the image
-  // encoder are the same convolution on different tensors with different filters (32 -> 64 -> 128 -> 256 channels at
-  // HSM.yaml's widths, 2.4 GFLOP each), ~35 us launches that cannot fill the chip one at a time: ONE launch computes both
-  // (IgemmParams::pair).  Level 0 reads different inputs (22 / 9 channels): two launches into the two halves of a 2-image
-  // buffer.  Batch 1 only; a chain keeps the encoders apart (its label encoder runs once per segment at batch T).
-  bool mask_branches_paired(const Act& L, const Act& I9, const Act& CAT, const Norm& ncat, int chm) {
-    const rib_config& c = h->g.c;
-    const std::string m = "flow_network_temp";
-    const Act* inputs[2] = {&L, &I9};
-    const char* branches[2] = {"down_lbl", "down_img"};
-    Act cur; Norm ncur;
-    {
-      const ConvDef& c0 = conv_of(h, m + ".down_lbl.0");
-      cur = act_n(2, c0.cout, L.H, L.W); ncur = norm(h->padc(c0.cout), 2);
-      const size_t img_bytes = (size_t)L.H * L.W * cur.Cp * h->esz();
-      for (int b = 0; b < 2; ++b) {
-        const ConvDef& cd = conv_of(h, m + "." + branches[b] + ".0");
-        Act o = cur; o.off += b * img_bytes;                                   // image b of the pair buffer
-        Norm no = ncur; no.sc += (size_t)b * ncur.ld * sizeof(float); no.sh += (size_t)b * ncur.ld * sizeof(float);
-        ConvArgs a; a.cd = &cd; a.in = *inputs[b]; a.out = o; a.want_stats = true; a.stats_out = &no; a.affine = true; a.stats_now = true;
-        if (!conv(a, cd.name)) return false;
-        tap(std::string("mask.") + (b == 0 ? "lbl_0" : "img_0") + ".raw", o);
-      }
-    }
-    for (int i = 1; i <= c.mask_down; ++i) {
-      const ConvDef& cl = conv_of(h, m + ".down_lbl." + std::to_string(i));
-      const ConvDef& ci = conv_of(h, m + ".down_img." + std::to_string(i));
-      const bool lastl = (i == c.mask_down);
-      Act o = lastl ? CAT : act_n(2, cl.cout, cur.H / 2, cur.W / 2);
-      Norm no = lastl ? ncat : norm(h->padc(cl.cout), 2);
-      ConvArgs a; a.cd = &cl; a.pair = &ci; a.in = cur; a.out = o; a.pro = &ncur; a.pro_lrelu = true;
-      if (lastl) { a.pair_merge = true; a.pair_yoff = chm; }
-      a.want_stats = true; a.stats_out = &no; a.affine = true; a.no_split = true;
-      a.choice_names = {m + ".down_pair." + std::to_string(i), m + ".down_img." + std::to_string(i)};
-      if (!conv(a, m + ".down_pair." + std::to_string(i))) return false;
-      if (!lastl) {
-        const size_t img_bytes = (size_t)o.H * o.W * o.Cp * h->esz();
-        Act ol = o, oi = o; oi.off += img_bytes;
-        tap("mask.lbl_" + std::to_string(i) + ".raw", ol);
-        tap("mask.img_" + std::to_string(i) + ".raw", oi);
-      }
-      cur = o; ncur = no;
-    }
-    return true;
-  }
-
-  // every workspace reference of a launch
-  template <typename F> static void for_each_pref(Op& op, F f) {
-    for (int i = 0; i < op.nbinds; ++i) if (op.binds[i].ref.sp == PS_WS) f(op.binds[i].ref);
-  }
-  AllocRec* alloc_of(size_t voff) {
-    // allocations are in increasing voff order
-    size_t lo = 0, hi = allocs.size();
-    while (lo + 1 < hi) { const size_t mid = (lo + hi) / 2; if (allocs[mid].voff <= voff) lo = mid; else hi = mid; }
-    return (!allocs.empty() && voff >= allocs[lo].voff && voff < allocs[lo].voff + allocs[lo].bytes) ? &allocs[lo] : nullptr;
-  }
-  // Lifetime analysis + placement; rewrites every workspace reference of the plan.  The plan runs its launches in
-  // order on one stream, so a buffer is live from the first to the last launch that names it; buffers written outside
-  // the plan (the label-only results rib_chain gathers into their slots before it runs the frame) are live from the
-  // start, tapped activations (debug) until the end.
-  bool assign_physical() {
-    const bool reuse = pol.ws_reuse && !P->labels_only;
-    if (!reuse) { P->ws_bytes = ws; return true; }
-    bool bad = false;
-    for (size_t i = 0; i < P->ops.size(); ++i)
-      for_each_pref(P->ops[i], [&](PRef& r) {
-        AllocRec* a = alloc_of(r.off);
-        if (!a) { bad = true; return; }
-        a->first = std::min(a->first, (int)i); a->last = std::max(a->last, (int)i);
-      });
-    if (bad) { error = "workspace reference outside every allocation"; return false; }
-    const LabelSlots& l = P->ls;
-    for (size_t off : {l.x0, l.nx_sc, l.nx_sh, l.cat, l.ncat_sc, l.ncat_sh})
-      if (AllocRec* a = alloc_of(off)) a->first = -1;
-    if (h->keep_taps)
-      for (const Tap& t : P->taps)
-        if (AllocRec* a = alloc_of(t.off)) a->last = INT_MAX;
-    // placement: largest first, each at the lowest offset where it does not meet a placed buffer with an overlapping lifetime
-    std::vector<int> order;
-    for (size_t i = 0; i < allocs.size(); ++i) if (allocs[i].last >= 0 || allocs[i].first == -1) order.push_back((int)i);
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return allocs[a].bytes != allocs[b].bytes ? allocs[a].bytes > allocs[b].bytes : a < b; });
-    std::vector<int> placed;
-    size_t top = 0;
-    for (int i : order) {
-      AllocRec& a = allocs[i];
-      std::vector<std::pair<size_t, size_t>> busy;     // physical ranges of the placed buffers alive together with a
-      for (int j : placed) {
-        const AllocRec& b = allocs[j];
-        if (b.first <= a.last && a.first <= b.last) busy.push_back({b.phys, b.phys + b.bytes});
-      }
-      std::sort(busy.begin(), busy.end());
-      size_t at = 0;
-      for (auto& r : busy) { if (at + a.bytes <= r.first) break; at = std::max(at, r.second); }
-      a.phys = at;
-      top = std::max(top, at + a.bytes);
-      placed.push_back(i);
-    }
-    auto remap = [&](size_t voff) { AllocRec* a = alloc_of(voff); return a ? a->phys + (voff - a->voff) : voff; };
-    for (Op& op : P->ops) for_each_pref(op, [&](PRef& r) { r.off = remap(r.off); });
-    LabelSlots& m = P->ls;
-    m.x0 = remap(m.x0); m.nx_sc = remap(m.nx_sc); m.nx_sh = remap(m.nx_sh); m.cat = remap(m.cat); m.ncat_sc = remap(m.ncat_sc); m.ncat_sh = remap(m.ncat_sh);
-    for (Tap& t : P->taps) t.off = remap(t.off);
-    P->ws_virtual = ws;
-    P->ws_bytes = top;
-    return true;
-  }
-
-  void record_label_slots(const Act& x, const Norm& nx, const Act& CAT, const Norm& ncat) {
-    LabelSlots& l = P->ls;
-    l.x0 = x.off; l.x0_b = (size_t)B * x.H * x.W * x.Cp * h->esz();
-    l.nx_sc = nx.sc; l.nx_sh = nx.sh; l.nx_b = (size_t)B * nx.ld * sizeof(float);
-    l.cat = CAT.off; l.cat_b = (size_t)B * CAT.H * CAT.W * CAT.Cp * h->esz();
-    l.ncat_sc = ncat.sc; l.ncat_sh = ncat.sh; l.ncat_b = (size_t)B * ncat.ld * sizeof(float);
-  }
-
-  // the label-only launches alone (for rib_chain's batched pre-pass): pack.label, the mask network's label branch,
-  // down_first; same tensors, same launch arguments as in build()
-  bool build_labels() {
-    const Cfg& g = h->g;
-    const rib_config& c = g.c;
-    const int H = P->H, W = P->W;
-    P->labels_only = true;
-    defer_stats = false;
-    const bool vL = lowc_serves({"down_first", "flow_network_temp.down_lbl.0"});
-    Act L = vL ? virt(c.label_nc, H, W, U_LABEL, c.label_nc) : act(c.label_nc, H, W);
-    if (!vL && L.Cp > 32) { error = "input channel counts above 32 are not supported by the pack kernel"; return false; }
-    if (!vL) {
-      OpOf<PackParams> op(RIB_KC_PACK, "pack.label");
-      op.p().c0 = c.label_nc; op.p().dC = L.Cp; op.p().HW = H * W;
-      op.bind(&PackParams::s0, US(U_LABEL)); op.bind(&PackParams::dst, WS(L.off));
-      op.grid = dim3((H * W + 63) / 64, B, 1);
-      push(op);
-    }
-    const int chm = g.mask_nf(c.mask_down);
-    if (h->padc(chm) != chm) { error = "mask network width must be a multiple of 8 (16 with bf16 storage)"; return false; }
-    Act CAT = act(2 * chm, H >> c.mask_down, W >> c.mask_down);
-    Norm ncat = norm(CAT.Cp);
-    if (!mask_branch(0, L, CAT, ncat, chm)) return false;
-    const ConvDef& df = conv_of(h, "down_first");
-    Act x = act(df.cout, H, W); Norm nx = norm(x.Cp);
-    ConvArgs a; a.cd = &df; a.in = L; a.out = x; a.want_stats = true; a.stats_out = &nx;
-    if (!conv(a, "down_first")) return false;
-    record_label_slots(x, nx, CAT, ncat);
-    return assign_physical();
-  }
-
-  // ---- the frame plan, sub-network by sub-network (Generator.forward, PGNR/models/generator.py:181-234) ------------------
-  // Tensors that more than one sub-network touches.  The planners below run in the order of `build()`, which is the order
-  // of the launches AND of the workspace allocations (assign_physical() shares bytes by lifetime afterwards).
-  struct Frame {
-    Act L;                    // label map [B,22,H,W]: virtual (the caller's tensor, read in place by k_conv_lowc) or packed NHWC
-    Act Ein;                  // cat([img_fake, img_prev]) (generator.py:197): the embedder's input
-    Act I9;                   // cat([img_prev, img_fake, img]) (generator.py:232): the mask network's image input
-    std::vector<Act> cond;    // condition maps of the embedder, level 0 (full resolution) .. emb_down
-    Act CAT; Norm ncat;       // the mask network's concatenated encoder outputs [label | image] and their InstanceNorm
-    int chm = 0, Hm = 0, Wm = 0;
-  };
-
-  // boundary: NCHW user tensors -> NHWC (+concat, +zero channel padding), or nothing at all where k_conv_lowc reads them in place
-  bool plan_boundary(Frame& F) {
-    const Cfg& g = h->g;
-    const rib_config& c = g.c;
-    const int H = P->H, W = P->W;
-    // Where the first layers can read the caller's NCHW tensors in place (k_conv_lowc) there is no packed copy at all
-    const bool vL = lowc_serves({"down_first", "flow_network_temp.down_lbl.0"});
-    const bool vE = lowc_serves({"ref_embedding.conv_first"});
-    const bool vI = lowc_serves({"flow_network_temp.down_img.0"}) && head_without_nhwc(conv_of(h, "conv_img"));
-    F.L = vL ? virt(c.label_nc, H, W, U_LABEL, c.label_nc) : act(c.label_nc, H, W);
-    F.Ein = vE ? virt(c.image_nc * 2, H, W, U_FAKE, c.image_nc, U_PREV, c.image_nc) : act(c.image_nc * 2, H, W);     // cat([img_fake, img_prev]) generator.py:197
-    F.I9 = vI ? virt(c.image_nc * 3, H, W, U_PREV, c.image_nc, U_FAKE, c.image_nc, U_IMG, c.image_nc) : act(c.image_nc * 3, H, W);   // cat([img_prev, img_fake, img]) generator.py:232
-    auto pack = [&](const std::string& nm, const Act& dst, int s0, int c0, int s1, int c1) {
-      OpOf<PackParams> op(RIB_KC_PACK, nm);
-      op.p().c0 = c0; op.p().c1 = c1; op.p().dC = dst.Cp; op.p().HW = H * W;
-      op.bind(&PackParams::s0, US(s0)); if (c1) op.bind(&PackParams::s1, US(s1));
-      op.bind(&PackParams::dst, WS(dst.off));
-      op.grid = dim3((H * W + 63) / 64, B, 1);
-      push(op);
-    };
-    if (F.L.Cp > 32 || F.Ein.Cp > 32 || F.I9.Cp > 32) { error = "input channel counts above 32 are not supported by the pack kernel"; return false; }   // (Cp = 0 for the unpacked ones)
-    mark_label = true;
-    if (!vL) pack("pack.label", F.L, U_LABEL, c.label_nc, 0, 0);
-    mark_label = false;
-    if (!vI) pack("pack.img9", F.I9, U_PREV, c.image_nc, U_FAKE, c.image_nc);           // cat([img_prev, img_fake, .]) generator.py:232
-    if (!vE) pack("pack.embed_in", F.Ein, U_FAKE, c.image_nc, U_PREV, c.image_nc);      // cat([img_fake, img_prev]) generator.py:197
-
-    return true;
-  }
-
-  // ref_embedding (LabelEmbedder 'encoder', generator.py:360-387) + gamma/beta of the SPADEs of the small condition levels
-  bool plan_embedder(Frame& F) {
-    const Cfg& g = h->g;
-    const rib_config& c = g.c;
-    const int H = P->H, W = P->W;
-    std::vector<Act>& cond = F.cond;
-    cond.assign(c.emb_down + 1, Act());
-    {
-      const ConvDef& cf = conv_of(h, "ref_embedding.conv_first");
-      cond[0] = act(cf.cout, H, W);
-      ConvArgs a; a.cd = &cf; a.in = F.Ein; a.out = cond[0]; a.act = ACT_LRELU;
-      if (!conv(a, "ref_embedding.conv_first")) return false;
-      tap("cond_0", cond[0]);
-      for (int i = 0; i < c.emb_down; ++i) {
-        const ConvDef& cd = conv_of(h, "ref_embedding.down_" + std::to_string(i));
-        cond[i + 1] = act(cd.cout, cond[i].H / 2, cond[i].W / 2);
-        ConvArgs b; b.cd = &cd; b.in = cond[i]; b.out = cond[i + 1]; b.act = ACT_LRELU;
-        if (!conv(b, cd.name)) return false;
-        tap("cond_" + std::to_string(i + 1), cond[i + 1]);
-      }
-    }
-    // gamma/beta of all SPADEs of the small condition levels, one GEMM per level (cond_level_gemm)
-    for (int j = 0; j <= c.emb_down; ++j)
-      if (!cond_level_gemm(j, cond[j])) return false;
-
-    return true;
-  }
-
-  // label encoder of the mask network: depends only on the label map, so a chain runs it once per segment (labels-only plan);
-  // in a paired frame plan it rides with the image encoder instead (plan_mask_net)
-  bool plan_mask_label_branch(Frame& F) {
-    const Cfg& g = h->g;
-    const rib_config& c = g.c;
-    const int H = P->H, W = P->W;
-    F.chm = g.mask_nf(c.mask_down);
-    F.Hm = H >> c.mask_down; F.Wm = W >> c.mask_down;
-    const int chm = F.chm;
-    if (h->padc(chm) != chm) { error = "mask network width must be a multiple of 8 (16 with bf16 storage)"; return false; }
-    F.CAT = act(2 * chm, F.Hm, F.Wm);
-    F.ncat = norm(F.CAT.Cp);
-    if (!pair_mask) {
-      mark_label = true;
-      if (!mask_branch(0, F.L, F.CAT, F.ncat, chm)) return false;
-      mark_label = false;
-    }
-
-    return true;
-  }
-
-  // main generator (generator.py:201-228): down_first, down_0..D with AvgPool, res blocks, up_D..0, conv_img + tanh
-  bool plan_trunk(Frame& F) {
-    const Cfg& g = h->g;
-    const rib_config& c = g.c;
-    const int H = P->H, W = P->W;
-    const int D = c.num_down_img;
-    const std::vector<Act>& cond = F.cond;
-    Act x; Norm nx;
-    {
-      const ConvDef& df = conv_of(h, "down_first");
-      x = act(df.cout, H, W); nx = norm(x.Cp);
-      ConvArgs a; a.cd = &df; a.in = F.L; a.out = x; a.want_stats = true; a.stats_out = &nx;
-      mark_label = true;
-      if (!conv(a, "down_first")) return false;
-      mark_label = false;
-      tap("down_first", x);
-    }
-    record_label_slots(x, nx, F.CAT, F.ncat);
-    for (int i = 0; i <= D; ++i) {
-      Act out; Norm nout;
-      const bool last = (i == D);
-      if (!spade_block("down_" + std::to_string(i), x, false, nx, cond[std::min(c.emb_down, i)], &out, last ? &nout : nullptr)) return false;
-      if (!last) {   // self.downsample = AvgPool2d(3, 2, 1) (generator.py:127,207-208)
-        if (out.Cp % 4 != 0 || 256 % (out.Cp / 4) != 0) { error = "avgpool: unsupported channel count"; return false; }
-        Act pooled = act(out.C, out.H / 2, out.W / 2);
-        Norm np = norm(pooled.Cp);
-        const int slots = 256 / (out.Cp / 4), ppb = slots * 4;
-        const int blocks = (pooled.H * pooled.W + ppb - 1) / ppb;
-        const size_t part = alloc((size_t)B * blocks * 2 * out.Cp * sizeof(double));
-        OpOf<PoolParams> op(RIB_KC_POOL, "down_" + std::to_string(i) + ".pool");
-        op.p().H = out.H; op.p().W = out.W; op.p().C = out.Cp; op.p().blocks = blocks;
-        op.bind(&PoolParams::x, WS(out.off)); op.bind(&PoolParams::y, WS(pooled.off)); op.bind(&PoolParams::stat_part, WS(part));
-        op.grid = dim3(blocks, B, 1);
-        push(op);
-        OpOf<FinalizeParams> f = finalize_op(op.name, part, blocks, out.Cp, out.Cp, np, 0, pooled.H, pooled.W, nullptr, B);
-        finalize_or_defer(f, &np, false, part, blocks, out.Cp, f.p().inv_count, false, 0, 0);
-        x = pooled; nx = np;
-      } else { x = out; nx = nout; }
-    }
-    const int jres = std::min(c.emb_down, D + 1);
-    for (int i = 0; i < g.num_res_blocks(); ++i) {
-      Act out; Norm nout;
-      if (!spade_block("res_" + std::to_string(i), x, false, nx, cond[jres], &out, &nout)) return false;
-      x = out; nx = nout;
-    }
-    bool ups = false;
-    for (int i = D; i >= 0; --i) {
-      Act out; Norm nout;
-      // statistics of a nearest-x2 upsampled tensor equal those of the tensor itself, so the
-      // producer's (scale, shift) are reused and the upsample is folded into the consumer's read
-      if (!spade_block("up_" + std::to_string(i), x, ups, nx, cond[std::min(i, c.emb_down)], &out, i != 0 ? &nout : nullptr)) return false;
-      x = out; nx = nout; ups = true;
-    }
-    {   // conv_img 'AC' + tanh (generator.py:114-116,228); also lands in img9[6:9]
-      const ConvDef& ci = conv_of(h, "conv_img");
-      ConvArgs a; a.cd = &ci; a.in = x; a.pro_lrelu = true; a.out = F.I9; a.yoff = c.image_nc * 2;
-      a.cout_store = c.image_nc; a.act = ACT_TANH; a.y_nchw = US(U_IMG);
-      a.y_none = F.I9.virt;      // the mask network then reads the image from the caller's NCHW tensor
-      if (!conv(a, "conv_img")) return false;
-    }
-
-    return true;
-  }
-
-  // MaskGenerator (generator.py:493-510): image encoder (paired with the label encoder where the plan pairs), join with the
-  // label branch, res_flow blocks, phase-convolution decoder, sigmoid head (+ the driver's blend)
-  bool plan_mask_net(Frame& F) {
-    const Cfg& g = h->g;
-    const rib_config& c = g.c;
-    const int H = P->H, W = P->W;
-    const std::string m = "flow_network_temp";
-    const int chm = F.chm, Hm = F.Hm, Wm = F.Wm;
-    const Act& CAT = F.CAT; const Norm& ncat = F.ncat;
-    if (pair_mask ? !mask_branches_paired(F.L, F.I9, CAT, ncat, chm) : !mask_branch(1, F.I9, CAT, ncat, chm)) return false;
-    tap("mask.cat.raw", CAT);
-    Act r; bool first = true;
-    for (int i = 0; i < c.mask_res_blocks; ++i) {
-      const std::string bn = m + ".res_flow." + std::to_string(i);
-      const ConvDef& c0 = conv_of(h, bn + ".conv_block_0");
-      const ConvDef& c1 = conv_of(h, bn + ".conv_block_1");
-      const bool learned = h->conv_index.count(bn + ".conv_block_s") > 0;
-      const Act xin = first ? CAT : r;                              // (lazy: the previous block's join, computed by this block's first input transform)
-      const Act xin_stored = xin.lazy ? xin.lazy->o : xin;          // ... which also stores it: the residual of this block's join
-      Act t0 = act(c0.cout, Hm, Wm); Norm n0 = norm(t0.Cp);
-      { ConvArgs a; a.cd = &c0; a.in = xin; a.out = t0; if (first) { a.pro = &ncat; a.pro_lrelu = true; }
-        a.want_stats = true; a.stats_out = &n0; a.affine = true;
-        if (!conv(a, c0.name)) return false; }
-      Act t1 = act(c1.cout, Hm, Wm); Norm n1 = norm(t1.Cp);
-      { ConvArgs a; a.cd = &c1; a.in = t0; a.out = t1; a.pro = &n0; a.pro_lrelu = true;
-        a.want_stats = true; a.stats_out = &n1; a.affine = true;
-        if (!conv(a, c1.name)) return false; }
-      Act ts; Norm ns;
-      if (learned) {
-        const ConvDef& cs = conv_of(h, bn + ".conv_block_s");
-        ts = act(cs.cout, Hm, Wm); ns = norm(ts.Cp);
-        ConvArgs a; a.cd = &cs; a.in = xin; a.out = ts; if (first) { a.pro = &ncat; a.pro_lrelu = true; }
-        a.want_stats = true; a.stats_out = &ns; a.affine = true;
-        if (!conv(a, cs.name)) return false;
-      } else if (first) { error = "mask res block 0 must have a learned shortcut"; return false; }
-      Act o = act(c1.cout, Hm, Wm);
-      {
-        // the join feeds the next block's conv_block_0 (no prologue): when that runs in the Winograd domain its input
-        // transform computes the join on the fly and stores it
-        const bool no_lazy = !pol.lazy_sources;
-        ConvArgs t;
-        if (i + 1 < c.mask_res_blocks) t.cd = &conv_of(h, m + ".res_flow." + std::to_string(i + 1) + ".conv_block_0");
-        if (t.cd && !no_lazy && h->prec() == PREC_F32 && runs_wino(t, Hm, Wm) && t.cd->cinp == o.Cp && n1.ld == o.Cp) {
-          auto L = std::make_shared<LazySrc>();
-          L->mode = WSRC_JOIN; L->name = bn + ".join"; L->x = t1; L->nx = n1; L->o = o;
-          if (learned) { L->has2 = true; L->x2 = ts; L->n2 = ns; } else L->xres = xin_stored;
-          Act y = o; y.lazy = L;
-          tap("mask.res_" + std::to_string(i), o);
-          r = y; first = false;
-          continue;
-        }
-      }
-      OpOf<InAddParams> op(RIB_KC_ELTWISE, bn + ".join");
-      InAddParams& ap = op.p();
-      ap.C = o.Cp; ap.HW = Hm * Wm; ap.ld = n1.ld;
-      op.bind(&InAddParams::t1, WS(t1.off));
-      if (!take_partials(n1, op, &InAddParams::st1)) { materialize(n1); op.bind(&InAddParams::sc1, WS(n1.sc)); op.bind(&InAddParams::sh1, WS(n1.sh)); }
-      if (learned) {
-        op.bind(&InAddParams::ts, WS(ts.off));
-        if (!take_partials(ns, op, &InAddParams::sts)) { materialize(ns); op.bind(&InAddParams::scs, WS(ns.sc)); op.bind(&InAddParams::shs, WS(ns.sh)); }
-      } else op.bind(&InAddParams::xres, WS(xin_stored.off));
-      op.bind(&InAddParams::out, WS(o.off));
-      const int nsl = (o.Cp + 63) / 64;
-      ap.nslices = nsl; ap.pblocks = std::max(1, std::min((Hm * Wm + 15) / 16, ((ap.st1.tiles > 0 || ap.sts.tiles > 0) ? 384 : 2048) / nsl));
-      op.grid = dim3(ap.pblocks * nsl, B, 1);
-      push(op);
-      tap("mask.res_" + std::to_string(i), o);
-      r = o; first = false;
-    }
-    Act cur = r; Norm ncur; bool have = false;
-    for (int j = 0; j < c.mask_down; ++j) {
-      const ConvDef& cd = conv_of(h, m + ".up_flow." + std::to_string(2 * j + 1));
-      Act o = act(cd.cout, cur.H * 2, cur.W * 2); Norm no = norm(o.Cp);
-      ConvArgs a; a.cd = &cd; a.in = cur; a.ups = true; a.out = o;
-      if (have) { a.pro = &ncur; a.pro_lrelu = true; }
-      a.want_stats = true; a.stats_out = &no; a.affine = true;
-      if (!conv(a, cd.name)) return false;
-      tap("mask.up_" + std::to_string(j) + ".raw", o);
-      cur = o; ncur = no; have = true;
-    }
-    {
-      const ConvDef& cm = conv_of(h, m + ".conv_mask.0");
-      ConvArgs a; a.cd = &cm; a.in = cur; if (have) { a.pro = &ncur; a.pro_lrelu = true; }
-      a.act = ACT_SIGMOID; a.y_user = US(U_MASK);
-      if (!conv(a, cm.name)) return false;
-    }
-    return true;
-  }
-
-  bool build() {
-    Frame F;
-    return plan_boundary(F) && plan_embedder(F) && plan_mask_label_branch(F) && plan_trunk(F) && plan_mask_net(F) && assign_physical();
-  }
-};
+namespace {
 
 // PLAN_LABELS: the label-only launches alone (rib_chain's batched pre-pass).  PLAN_UNPAIRED: a frame plan that keeps the mask
 // network's label encoder in launches of its own (rib_chain skips them); the default frame plan pairs the two encoders

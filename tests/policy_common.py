@@ -1,7 +1,7 @@
 """What tests/test_policy_cpu.py and tests/test_gpu_policy.py share: the table of launch-plan policy switches and the helpers
 that build a plan, or render a frame, on each side of one.
 
-Every switch of `struct FusionPolicy` (csrc/rib.hip) and the ones read elsewhere (RIB_NO_XCD, RIB_NO_PAIR) gives two
+Every switch of `struct FusionPolicy` (csrc/planner.h) and the ones read elsewhere (RIB_NO_XCD, RIB_NO_PAIR) gives two
 implementations of the same frame from the same inputs.  A row of CASES names the switch setting, the shape, the relation the
 two frames must satisfy and what the setting changes in the launch list.  The CPU file proves on host-only handles that
 every row changes the plan in the way it names (no GPU case is vacuous); the GPU file renders both sides on workspaces
@@ -160,7 +160,7 @@ MASK_DOWN = 3      # levels of the mask network's encoders below the first (HSM 
 
 
 def tap_of_launch(name):
-    """The debug tap a launch writes (Builder::spade_block / mask_branch / frame, csrc/rib.hip), or None: a launch that writes
+    """The debug tap a launch writes (Builder::spade_block / mask_branch / frame, csrc/planner.h), or None: a launch that writes
     statistics arrays, a gamma/beta slab, a pooled map or a caller's tensor."""
     if name.endswith(".stats") or name.endswith(".gammabeta"):
         return None

@@ -115,7 +115,7 @@ def test_the_xcd_shape_has_grids_the_tile_order_changes(monkeypatch, case):
 
 def test_every_policy_switch_has_a_row():
     src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "render-in-between_amd", "csrc")
-    with open(os.path.join(src, "rib.hip")) as f:
+    with open(os.path.join(src, "planner.h")) as f:
         text = f.read()
     policy = text[text.index("struct FusionPolicy {"):text.index("struct Builder {")]
     switches = set(re.findall(r'getenv\("(RIB_[A-Z0-9_]+)"\)', policy)) | {"RIB_NO_XCD"}

@@ -25,7 +25,7 @@ from render_in_between_amd import _native, tuning
 B, H, W = SHAPE = (2, 48, 80)      # every map from 48x80 down to 3x5 leaves partial tiles; batch 2: the sample stride
 INPUT_SEED = 3                     # synth.make_inputs(spec, 2, 48, 80, 3): the inputs of the two 16-bit frame tests
 KSPLITS = (1, 2, 3, 4)             # every factor the 16-bit table names
-# launch -> the tap that is its direct product (Builder::spade_block / mask_branch / frame, csrc/rib.hip)
+# launch -> the tap that is its direct product (Builder::spade_block / mask_branch / frame, csrc/planner.h)
 LAUNCHES = (
     ("up_4.conv_block_1", "up_4"),                              # 3x3 + its shortcut, deepest map
     ("res_0.conv_block_0", "res_0.h"),
