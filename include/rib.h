@@ -294,6 +294,36 @@ int rib_jpeg(rib_handle* h, int T, int H, int W, const uint8_t* src_u8_nhwc, int
  * workspace, refusals and errors, two launches, no atomics, a frame's bytes independent of T. */
 int rib_jpeg_float(rib_handle* h, int T, int H, int W, const float* src_f32_nchw, int quality,
                  uint8_t* dst, size_t dst_stride, int32_t* lengths, void* workspace, void* hip_stream);
+/* ---- lossless PNG of the folder driver's frames, encoded on the GPU (evaluate_from_folder(png_on="gpu")) ----
+ * T images uint8 NHWC [T,H,W,3] on the device -> T complete PNG files: 8 bit, colour type 2, no interlace; a zlib stream cut
+ * into one IDAT chunk for its two header bytes (78 01), one IDAT chunk per strip of 8 image rows (the last strip may be
+ * shorter) and one IDAT chunk for the Adler-32, so that every chunk CRC is one strip's own business.  Per row the one of the
+ * five PNG filters with the smallest sum of |int8(filtered byte)| (a tie: the lower type; "above" is the raw row, also across
+ * strips); per strip one dynamic-Huffman deflate block whose only matches are runs at distance 1 (a run of R equal bytes: a
+ * literal, then lengths min(m, 258) while m >= 4, then m literals) and whose literal/length code is the cheapest of K given
+ * tables, header included (a tie: the lower k); a strip that is not the last ends with an empty stored block, so every strip
+ * is whole bytes.  The stream and the tables are this project's; png.py (encode_host) states every byte in integers, and the
+ * kernels are bit-equal to it.  No LZ77 search, no tree built on the device, no checksum that spans workgroups.
+ * code_lengths: HOST uint8 [K][286], 1 <= K <= 16; every table a complete prefix code (Kraft sum exactly 1) with lengths in
+ * 1..15, every length of table 0 at most 9.  The library validates them, builds the canonical codes (RFC 1951 3.2.2) and the
+ * block headers with png.py's rule on the host and keeps the device copy on the handle; they are uploaded again only when
+ * their bytes change (the upload is ordered on `stream`).
+ * Frame t's file starts at dst + t * dst_stride and lengths[t] (device, int32) receives its size.  rib_png_max_bytes(H, W) is an
+ * upper bound of one file (table 0 prices a literal at <= 9 bits and a match of >= 4 bytes at <= 9 + 5 + 1 bits; png.py
+ * max_bytes); with dst_stride >= rib_png_max_bytes no frame is refused.  A smaller dst_stride is allowed: a frame whose file
+ * would not fit writes nothing and gets lengths[t] = 0 - the call only enqueues and returns RIB_OK, the caller reads the
+ * refusal from lengths.  Bytes of a frame's stride behind lengths[t] are not written.
+ * workspace: rib_png_workspace_bytes(h, T, H, W) bytes on the device, 16-byte aligned (one staging slot per strip, sized by
+ * the same bound, and four words per strip: length, chunk CRC, Adler A, Adler B); nothing has to be cleared.
+ * Enqueues two launches on `stream` (strips; lengths scan + Adler combination + assembly), no synchronisation, no atomics on
+ * global memory, no floats: a frame's bytes do not depend on T.  T outside 1..65535, H outside 1..65535, W outside 1..4096, a
+ * dst_stride of 0 or of 2 GiB or more, a NULL or misaligned pointer, K outside 1..16 or an invalid table: RIB_ERR_INVALID with
+ * a rib_last_error text, nothing launched (the two size queries return 0). */
+size_t rib_png_max_bytes(int H, int W);
+size_t rib_png_workspace_bytes(rib_handle* h, int T, int H, int W);
+int rib_png(rib_handle* h, int T, int H, int W, const uint8_t* src_u8_nhwc,
+            const uint8_t* code_lengths /* HOST [K][286] */, int K,
+            uint8_t* dst, size_t dst_stride, int32_t* lengths, void* workspace, void* hip_stream);
 
 /* ---- motion-compensated interpolation (MCI) of a segment's two key frames: the folder driver's background="mci" ----
  * This project's interpolation, NOT DAIN (the reference reads one DAIN frame per output frame; DAIN is an external network with

@@ -7,7 +7,7 @@ the working tree.  librib.so is linked from two host objects - rib.o (rib.hip: t
 small kernels of kernels.hip.h; plan.h and planner.h, the launch plan's data model and its builder, are parts of that translation unit) and frame.o (frame.hip: the folder driver's frame utilities and their kernel headers) - and
 RIB_NSECTIONS (variants.hip.h: 24) igemm_shard_<s>.o objects, each holding one section of the k_igemm tile variants
 (variants.def): the kernel instantiations dominate the build and compile as a queue of parallel jobs (about 2 min on 8
-cores).  Every object has its own dependency list (RIB_DEPS, FRAME_DEPS, SHARD_DEPS): editing jpeg.hip.h, mci.hip.h or composite.hip.h rebuilds frame.o only,
+cores).  Every object has its own dependency list (RIB_DEPS, FRAME_DEPS, SHARD_DEPS): editing jpeg.hip.h, png.hip.h, mci.hip.h or composite.hip.h rebuilds frame.o only,
 editing the planner (planner.h, plan.h) rebuilds rib.o only; rib_host.h, pixel_ops.hip.h and rib.h (SHARED_DEPS) are what the objects share.
 
 Build stamps.  Every object is compiled with -DRIB_BUILD_STAMP="<hash>" where <hash> is the sha256 over the CONTENT
@@ -45,7 +45,7 @@ PIXEL_OPS = os.path.join(HERE, "pixel_ops.hip.h")       # blend1 / quantise_u8 /
 SHARED_DEPS = [os.path.join(HERE, "rib_host.h"), PIXEL_OPS, os.path.join(INC, "rib.h")]      # what rib.o and frame.o share
 SHARD_DEPS = [SHARD_SRC] + [os.path.join(HERE, f) for f in ("igemm.hip.h", "variants.hip.h", "variants.def")] + [PIXEL_OPS]
 RIB_DEPS = [SRC] + [os.path.join(HERE, f) for f in ("plan.h", "planner.h", "kernels.hip.h")] + SHARED_DEPS + SHARD_DEPS[1:-1]
-FRAME_DEPS = [FRAME_SRC] + [os.path.join(HERE, f) for f in ("frame_kernels.hip.h", "raster.hip.h", "quality.hip.h", "resize.hip.h", "human_mask.hip.h", "panel.hip.h", "jpeg.hip.h", "mci.hip.h", "composite.hip.h")] + SHARED_DEPS
+FRAME_DEPS = [FRAME_SRC] + [os.path.join(HERE, f) for f in ("frame_kernels.hip.h", "raster.hip.h", "quality.hip.h", "resize.hip.h", "human_mask.hip.h", "panel.hip.h", "jpeg.hip.h", "png.hip.h", "mci.hip.h", "composite.hip.h")] + SHARED_DEPS
 DEPS = RIB_DEPS + [d for d in FRAME_DEPS if d not in RIB_DEPS]      # every file the two host objects are made from
 OUT = os.path.join(HERE, "librib.so")
 # stage 1 (motion transformer, include/rib_motion.h) is its own small library

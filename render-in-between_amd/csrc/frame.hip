@@ -1,5 +1,5 @@
 // frame.hip — the folder driver's frame utilities behind the C ABI (include/rib.h): blend, quantise, cubic resize, PSNR/SSIM,
-// flow warp, source-size composite, label rasteriser, pose mask, diagnostic sheet, JPEG encoder and the motion-compensated background (MCI).  The second host object of librib.so (frame.o,
+// flow warp, source-size composite, label rasteriser, pose mask, diagnostic sheet, JPEG encoder, PNG encoder and the motion-compensated background (MCI).  The second host object of librib.so (frame.o,
 // csrc/build.py).  None of these entries touches a launch plan, the weight blob or a tuned choice: of a handle they use the
 // device index, the error string and the small state of rib::FrameState (rib_host.h), reached through frame_state().
 //
@@ -13,6 +13,7 @@
 #include "human_mask.hip.h"
 #include "panel.hip.h"
 #include "jpeg.hip.h"
+#include "png.hip.h"
 #include "mci.hip.h"
 #include "composite.hip.h"
 #include "rib_host.h"
@@ -368,6 +369,76 @@ int rib_jpeg(rib_handle* handle, int T, int H, int W, const uint8_t* src_u8_nhwc
 int rib_jpeg_float(rib_handle* handle, int T, int H, int W, const float* src_f32_nchw, int quality, uint8_t* dst, size_t dst_stride,
                  int32_t* lengths, void* workspace, void* hip_stream) {
   return jpeg_enqueue<float>("rib_jpeg_float", handle, T, H, W, src_f32_nchw, quality, dst, dst_stride, lengths, workspace, hip_stream);
+}
+static size_t png_strips(int H) { return ((size_t)H + PNG_STRIP_ROWS - 1) / PNG_STRIP_ROWS; }
+
+size_t rib_png_max_bytes(int H, int W) {
+  if (H < 1 || W < 1 || H > PNG_MAX_H || W > PNG_MAX_W) return 0;
+  const size_t rowN = 1 + 3 * (size_t)W, full = (size_t)H / PNG_STRIP_ROWS, rest = (size_t)H % PNG_STRIP_ROWS;
+  size_t total = (size_t)PNG_PREFIX_BYTES + 16 + 12 + full * (12 + png_strip_data_bound(PNG_STRIP_ROWS * rowN));
+  if (rest) total += 12 + png_strip_data_bound(rest * rowN);
+  return total;
+}
+
+size_t rib_png_workspace_bytes(rib_handle* h, int T, int H, int W) {
+  if (!h || T < 1 || T > 65535 || H < 1 || W < 1 || H > PNG_MAX_H || W > PNG_MAX_W) return 0;
+  const size_t strips = (size_t)T * png_strips(H);
+  return align256(strips * png_slot_bytes(W)) + strips * 4 * sizeof(int32_t);      // the slots, then four words per strip
+}
+
+int rib_png(rib_handle* handle, int T, int H, int W, const uint8_t* src_u8_nhwc, const uint8_t* code_lengths, int K, uint8_t* dst,
+            size_t dst_stride, int32_t* lengths, void* workspace, void* hip_stream) {
+  FrameState* h = frame_state(handle);
+  if (!h) return RIB_ERR_INVALID;
+  if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_png: host-only handle");
+  if (!src_u8_nhwc || !code_lengths || !dst || !lengths || !workspace) return fail(h, RIB_ERR_INVALID, "rib_png: null pointer");
+  if (T < 1 || T > 65535 || H < 1 || H > PNG_MAX_H || W < 1 || W > PNG_MAX_W)
+    return fail(h, RIB_ERR_INVALID, fmt("rib_png: T=%d H=%d W=%d: 1 <= T <= 65535, 1 <= H <= %d, 1 <= W <= %d", T, H, W, PNG_MAX_H, PNG_MAX_W));
+  if (dst_stride < 1 || dst_stride > (size_t)INT32_MAX) return fail(h, RIB_ERR_INVALID, fmt("rib_png: dst_stride=%zu: at least 1, below 2 GiB", dst_stride));
+  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0 || (reinterpret_cast<uintptr_t>(lengths) & 3) != 0)
+    return fail(h, RIB_ERR_INVALID, "rib_png: workspace must be 16-byte aligned, lengths 4-byte aligned");
+  if (K < 1 || K > PNG_MAX_TABLES) return fail(h, RIB_ERR_INVALID, fmt("rib_png: K=%d: 1 <= K <= %d tables", K, PNG_MAX_TABLES));
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  PngTableState& ts = h->png;
+  const std::string key(reinterpret_cast<const char*>(code_lengths), (size_t)K * PNG_NSYM);
+  if (!ts.dev || ts.key != key) {                        // new tables: validate, build, upload on `stream`
+    PngDeviceTables* host = static_cast<PngDeviceTables*>(malloc(sizeof(PngDeviceTables)));
+    std::string why;
+    if (!host || !png_build_tables(code_lengths, K, host, &why)) {
+      free(host);
+      return fail(h, RIB_ERR_INVALID, "rib_png: code tables: " + (host ? why : std::string("out of memory")));
+    }
+    ts.host_all.push_back(host);
+    void* dev = nullptr;
+    HIP_TRY(h, hipMalloc(&dev, sizeof(PngDeviceTables)));
+    ts.dev_all.push_back(dev);
+    HIP_TRY(h, hipMemcpyAsync(dev, host, sizeof(PngDeviceTables), hipMemcpyHostToDevice, st));
+    ts.dev = dev;
+    ts.key = key;
+  }
+  PngParams pp;
+  pp.src = src_u8_nhwc; pp.tab = static_cast<const PngDeviceTables*>(ts.dev);
+  pp.H = H; pp.W = W; pp.strips = (int)png_strips(H);
+  pp.slot = (uint32_t)png_slot_bytes(W);
+  const size_t strips = (size_t)T * pp.strips;
+  pp.slots = static_cast<uint8_t*>(workspace);
+  pp.meta = reinterpret_cast<int32_t*>(pp.slots + align256(strips * pp.slot));
+  PngAssembleParams ap;
+  ap.slots = pp.slots; ap.meta = pp.meta; ap.dst = dst; ap.lengths = lengths; ap.dst_stride = dst_stride;
+  ap.H = H; ap.W = W; ap.strips = pp.strips; ap.slot = pp.slot;
+  png_make_prefix(ap.prefix, H, W);
+  const size_t lds = ((size_t)std::min(H, PNG_STRIP_ROWS) * (1 + 3 * (size_t)W) + 15) / 16 * 16;
+  if (!ts.lds_ready) {                                   // once per handle, as rib_warp does: up to 98 320 bytes at W = 4096
+    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_png_strips), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)((PNG_STRIP_ROWS * (1 + 3 * (size_t)PNG_MAX_W) + 15) / 16 * 16)));
+    ts.lds_ready = true;
+  }
+  hipLaunchKernelGGL(k_png_strips, dim3(pp.strips, T), dim3(256), lds, st, pp);
+  HIP_TRY(h, hipGetLastError());
+  hipLaunchKernelGGL(k_png_assemble, dim3(pp.strips, T), dim3(256), 0, st, ap);
+  HIP_TRY(h, hipGetLastError());
+  return RIB_OK;
 }
 // rib_mci_*: the workspace of one (B, H, W, levels) - the luma levels of the 2B key frames, then the block fields of the levels
 // (before the median); an extra level's plane and field follow those of the level below, so three levels lie where they lay

@@ -1071,6 +1071,7 @@ void rib_destroy(rib_handle* h) {
   if (!h) return;
   drop_chain_graphs(h);
   h->stage.release();
+  h->png.release();
   if (h->d_blob) (void)hipFree(h->d_blob);
   free_wino_sets(h);
   for (auto& pe : h->prof_events) (void)hipEventDestroy(pe.second);

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <vector>
 
 namespace rib {
 
@@ -70,6 +71,22 @@ struct StageRing {
   }
 };
 
+// rib_png's code tables as the handle keeps them: the bytes they were built from (uploaded again only when these change) and
+// the device copy (png.hip.h: PngDeviceTables).  A change of tables takes a new buffer on both sides, and the old ones live as
+// long as the handle: work already enqueued, on any stream, may still read them.
+struct PngTableState {
+  void* dev = nullptr;         // the current device copy
+  std::string key;             // the K * 286 code lengths it was built from
+  std::vector<void*> dev_all;
+  std::vector<void*> host_all; // what the uploads were staged from
+  bool lds_ready = false;      // k_png_strips' dynamic-LDS limit has been raised on this handle's device
+  void release() {
+    for (void* d : dev_all) (void)hipFree(d);
+    for (void* h : host_all) free(h);
+    dev_all.clear(); host_all.clear(); dev = nullptr; key.clear();
+  }
+};
+
 // the part of a rib_handle the frame utilities use (rib.hip: struct rib_handle : rib::FrameState)
 struct FrameState {
   int device = 0;              // < 0: host-only handle
@@ -77,6 +94,7 @@ struct FrameState {
   int label_nc = 0;            // rib_config::label_nc (rib_rasterise checks its channel count against it)
   bool warp_lds_ready = false; // rib_warp has raised k_warp's dynamic-LDS limit on this handle's device
   StageRing stage;
+  PngTableState png;
 };
 
 // frame.hip's one way to the state of a handle; defined in rib.hip, where rib_handle is complete

@@ -578,7 +578,7 @@ class Evaluator:
                              panels=False, panel_frames=False, panel_quality=90, panel_fps=30, panel_encode="host",
                              background="dain", mci_range=32, video=False, video_fps=30, video_quality=90, video_frames=False, frames="png",
                              poses="folder", key_pose_dir=None, upsample_rate=8, motion=None, save_poses=False, mci_border="clamp",
-                             mci_precision="full", output_size="model"):
+                             mci_precision="full", output_size="model", png_on="host"):
         """rank / world: this process's share of the independent units (default: the torch.distributed process
         group when one is initialised, else everything).  Returns the frames THIS rank wrote.
         The call is one `_FolderPipeline` (below): plan a clip -> decode -> upload -> render -> sink, pipelined over units
@@ -666,7 +666,27 @@ class Evaluator:
         files' own pixels (`mci_keys_src`), one rib_scaled_frames launch per unit on the upload stream makes the unit's
         backgrounds, and render, composite, PNG workers and video are the code of "source".  It is this project's
         interpolation, not DAIN; motion detail finer than an 8x8 model block is not followed; the person is a cubic
-        enlargement; no interior occlusion reasoning; unmeasured on real footage."""
+        enlargement; no interior occlusion reasoning; unmeasured on real footage.
+        png_on="gpu" (default "host": PIL in the worker processes, every file and launch as before): on the native path every
+        frame PNG this rank writes - key frames included - is encoded on the lane's stream by rib_png from the device uint8
+        frame the host workers would have been handed (rib_quantise's bytes at the model size, rib_composite's under
+        output_size="source" / "keyframes", a key frame's own bytes), in the units and the order video=True encodes them; the
+        lengths ride home in the unit's one copy (`png_len`), the finisher fetches exactly the files' bytes and writes them
+        under the PNG's name, and no raw frame is staged or copied home for the PNG workers.  A file is png.encode_host of the
+        pixels the default run's PNG holds: the same names and pixels, this project's stream (png.py), not the reference's
+        bytes; W <= 4096.  Not with a model behind the reference's protocol, frames="none" or an explicit PNG level; the
+        sheets' lossless copies (panel_frames) stay with the host workers, video=True may be combined and is unchanged."""
+        if png_on not in ("host", "gpu"):
+            raise ValueError("evaluate_from_folder: png_on must be 'host' or 'gpu', got %r" % (png_on,))
+        if png_on == "gpu":
+            if frames != "png":
+                raise ValueError("evaluate_from_folder: png_on='gpu' encodes the frames' PNG files: not with frames=%r" % (frames,))
+            if self.png_compress_level is not None:
+                raise ValueError("evaluate_from_folder: png_on='gpu' writes this project's own stream (png.py): an explicit PNG level "
+                                 "(png_compress_level=%r) is a setting of the host encoder" % (self.png_compress_level,))
+            if not (hasattr(model, "chain") and hasattr(model, "quantise") and hasattr(model, "png_into")):
+                raise ValueError("evaluate_from_folder: png_on='gpu' needs the native path (rib_png): this model only speaks the "
+                                 "reference's protocol")
         if poses not in ("folder", "keyframes", "keyframes-linear"):
             raise ValueError("evaluate_from_folder: poses must be 'folder', 'keyframes' or 'keyframes-linear', got %r" % (poses,))
         if poses == "folder" and (key_pose_dir is not None or upsample_rate != 8 or motion is not None or save_poses):
@@ -718,7 +738,7 @@ class Evaluator:
         pipe = _FolderPipeline(self, model, rank, world, gt_dir, metrics=bool(metrics), mask_dir=mask_dir, pose_mask=bool(pose_mask),
                                panels=bool(panels), panel_frames=bool(panel_frames), panel_quality=int(panel_quality),
                                panel_encode=panel_encode, background=background, mci_levels=mci_levels, mci_border=mci_border, mci_precision=mci_precision, video=bool(video), video_quality=int(video_quality),
-                               video_frames=bool(video_frames), write_png=frames == "png", output_size=output_size,
+                               video_frames=bool(video_frames), write_png=frames == "png", output_size=output_size, png_gpu=png_on == "gpu",
                                key_poses=None if poses == "folder" else (motion, key_pose_dir, upsample_rate, poses == "keyframes-linear", bool(save_poses)))
         self.background, self.mci_range, self.mci_border, self.mci_precision = background, mci_range, mci_border, mci_precision
         self.output_size = output_size
@@ -834,7 +854,7 @@ class _FolderPipeline:
     def __init__(self, ev, model, rank, world, gt_dir, metrics=False, mask_dir=None, pose_mask=False,
                  panels=False, panel_frames=False, panel_quality=90, panel_encode="host", background="dain", mci_levels=3,
                  video=False, video_quality=90, video_frames=False, write_png=True, key_poses=None, mci_border="clamp", mci_precision="full",
-                 output_size="model"):
+                 output_size="model", png_gpu=False):
         # composite.py: the frames' files at the clip's own size - the DAIN frames' ("source") or, under background="mci", the key
         # frame files' ("keyframes": keysize; the backgrounds are then rib_scaled_frames', everything after them is "source"'s code)
         self.source = output_size in ("source", "keyframes")
@@ -846,6 +866,10 @@ class _FolderPipeline:
         self.key_poses = key_poses
         # video: the frames' JPEG files (video.py); write_png False (frames="none"): they are the only files of a frame
         self.video, self.video_quality, self.video_frames, self.write_png = video, video_quality, video_frames, write_png
+        # png_on="gpu": the frames' PNG files come from rib_png on the lane's stream (png.py); stage_png: the raw frames go home
+        # for the PNG workers
+        self.png_gpu = png_gpu
+        self.stage_png = write_png and not png_gpu
         self.ev, self.model, self.rank, self.world, self.gt_dir = ev, model, rank, world, gt_dir
         self.metrics, self.mask_dir, self.pose_mask = metrics, mask_dir, pose_mask
         self.panels, self.panel_frames, self.panel_quality = panels, panel_frames, panel_quality
@@ -1077,7 +1101,7 @@ class _FolderPipeline:
                                        (ev.width, ev.height), slots, mask=mask_list is not None,
                                        shm_free=_shm_free_bytes() if self.procs is not None else None,
                                        out_slot_bytes=max(0, out_size[0] * out_size[1] - ev.width * ev.height) * 3
-                                       if (self.source and self.write_png) else 0)
+                                       if (self.source and self.stage_png) else 0)
             clip.src_dain, clip.src_gt = src["DAIN"], src["GT"]
             if self.source and clip.src_dain is None:      # never a silent change of the output's size
                 raise ValueError("output_size='source': clip %s: the DAIN list falls back to the host resize, so its source-size bytes "
@@ -1091,8 +1115,8 @@ class _FolderPipeline:
             w0, h0 = out_size
             slots = max((c1 - c0) * len(members) for _, members, c0, c1 in units)
             width = max(len(members) for _, members, _, _ in units)
-            need = shm_windows_bytes(int(slots * ev.height * ev.width * 3 * self.per_slot) + (2 + bool(self.video)) * width * w0 * h0 * 3
-                                     + (slots * w0 * h0 * 3 if self.write_png else 0))
+            need = shm_windows_bytes(int(slots * ev.height * ev.width * 3 * self.per_slot) + (2 + bool(self.video or self.png_gpu)) * width * w0 * h0 * 3
+                                     + (slots * w0 * h0 * 3 if self.stage_png else 0))
             free = _shm_free_bytes()
             if need > free:
                 raise ValueError("output_size='keyframes': clip %s: the staging windows at %dx%d need %.0f MB of shared memory, %.0f MB "
@@ -1191,7 +1215,7 @@ class _FolderPipeline:
         # (output_size="keyframes": every key frame a segment of this rank touches - the right ones too - for rib_scaled_frames)
         if self.source and (i in clip.keys or (self.keysize and i % clip.sample_rate == 0)) and i not in clip.key_src:
             clip.key_src[i] = self.pool.submit(self.key_source_u8, clip, i)
-        if i in clip.keys and i not in clip.futs and (self.write_png or not self.native):
+        if i in clip.keys and i not in clip.futs and (self.stage_png or not self.native):
             if self.source:                      # the key file's own pixels (the future is held here: the clip's table is cleared early)
                 ks = clip.key_src[i]
                 clip.futs[i] = self.finishers.submit(lambda: self.save_u8(clip, i, ks.result(timeout=IO_TIMEOUT_S)))
@@ -1209,7 +1233,7 @@ class _FolderPipeline:
             # one block per unit; a later chunk under background="mci" may stage nothing at all and still gets its byte
             spec = staging_spec(c1 - c0, len(members), (ev.height, ev.width), clip.src_dain, clip.src_gt, want_gt=clip.want_gt,
                                 masks=clip.mask_list is not None, keys=self.panels and c0 == 0, mci=self.mci, mci_keys=c0 == 0,
-                                src_keys=clip.out_size if (self.source and self.video and c0 == 0) else None,
+                                src_keys=clip.out_size if (self.source and (self.video or self.png_gpu) and c0 == 0) else None,
                                 mci_keys_src=clip.out_size if (self.keysize and c0 == 0) else None)
             table, total = block_layout(spec_bytes(spec))
             # worker processes: shared with them and page-locked (size classes of 1 MB: the block may be larger than the unit)
@@ -1366,10 +1390,11 @@ class _FolderPipeline:
             home = self.panels and (not self.jpeg_gpu or self.panel_frames)     # the raw sheets travel home
             # output_size="source": the frames' files are at the clip's (w0, h0); the chain, the metrics and the sheets stay at H x W
             W0, H0 = clip.out_size if self.source else (W, H)
-            spec = (("frames", torch.uint8, (n, H0, W0, 3), self.write_png),
+            spec = (("frames", torch.uint8, (n, H0, W0, 3), self.stage_png),
                     ("qual", torch.float32, (4, n), clip.measure),       # OURS PSNR, OURS SSIM, DAIN PSNR, DAIN SSIM
                     ("sheet_len", torch.int32, (n + nk,), self.jpeg_gpu),        # (jpeg_gpu implies panels)
                     ("video_len", torch.int32, (self.video_count(clip, ui),), self.video),
+                    ("png_len", torch.int32, (self.file_count(clip, ui),), self.png_gpu),
                     ("sheets", torch.uint8, (n + nk, SH, SW, 3), home))
             table, total = block_layout(spec_bytes(spec))
             assert total, "a unit sends something home: frames, metrics, sheets or a video"
@@ -1379,17 +1404,27 @@ class _FolderPipeline:
             shown = None
             if self.source:                      # one launch: quantise, enlarge and blend over the staged frames' own pixels
                 staged, ksrc = clip.src_of.pop(ui)
-                shown = dev["frames"] if self.write_png else torch.empty((n, H0, W0, 3), dtype=torch.uint8, device=g.device)
+                shown = dev["frames"] if self.stage_png else torch.empty((n, H0, W0, 3), dtype=torch.uint8, device=g.device)
                 g.composite(imgs.reshape(n, 3, H, W), masks.reshape(n, 1, H, W), staged.flatten(0, 1), out=shown)
                 keep += [imgs, masks, staged, ksrc, shown]
-            elif self.write_png:
+            elif self.stage_png:
                 g.quantise(frames, out=dev["frames"])
             if clip.measure:
                 gtf, mk = clip.meas.pop(ui)
                 g.quality(frames, gtf, mk, out=dev["qual"][0:2])
                 g.quality(dn.reshape(n, 3, H, W), gtf, mk, out=dev["qual"][2:4])
                 keep += [gtf, mk]
-            jpeg = vid = None
+            jpeg = vid = pngs = None
+            if self.png_gpu:                     # the frames' PNG files from the bytes the workers would have been handed
+                u8 = shown if self.source else g.quantise(frames)
+                if c0 != 0:
+                    ku8 = None
+                elif self.source:
+                    ku8 = ksrc.contiguous()
+                else:                            # a key frame passes through: the bytes of its tensor (save_frame_host)
+                    ku8 = g.quantise(gtd.to(torch.float32).contiguous())
+                pngs = self.encode_png(g, u8, ku8, dev["png_len"])
+                keep += [u8, ku8, pngs]
             if self.panels:                      # under panel_encode="gpu" without panel_frames the sheets stay on the device
                 sheets = dev["sheets"] if home else torch.empty((n + nk, SH, SW, 3), dtype=torch.uint8, device=g.device)
                 g.panel(imgs.reshape(n, 3, H, W), masks.reshape(n, 1, H, W), frames, dnp, gtp, lab.reshape(n, *lab.shape[2:]),
@@ -1423,14 +1458,18 @@ class _FolderPipeline:
                 "frames_off": table["frames"][0] if "frames" in table else None, "frame_hw": (H0, W0),
                 "sheets_off": table["sheets"][0] if "sheets" in table else None,
                 "jpeg": jpeg + (host["sheet_len"],) if jpeg else None, "video": vid + (host["video_len"],) if vid else None,
+                "png": pngs + (host["png_len"],) if pngs else None,
                 "sheet_frames": clip.unit_frames(ui) + ([clip.segs[si][0] for si in members] if nk else []) if self.panels else None}
 
-    def video_count(self, clip, ui):
-        """video: the files a unit encodes - its frames and, in a first chunk, the key frames it starts from (else 0)."""
-        if not self.video:
-            return 0
+    @staticmethod
+    def file_count(clip, ui):
+        """video / png_on="gpu": the files a unit encodes per kind - its frames and, in a first chunk, the key frames it starts from."""
         _, members, c0, c1 = clip.units[ui]
         return (c1 - c0) * len(members) + (len(members) if c0 == 0 else 0)
+
+    def video_count(self, clip, ui):
+        """video: the files a unit encodes (file_count; else 0)."""
+        return self.file_count(clip, ui) if self.video else 0
 
     def video_frames_of(self, clip, ui):
         """The frame indices of a unit's video files, in the order encode_video writes them."""
@@ -1463,6 +1502,19 @@ class _FolderPipeline:
             g.jpeg_into(ksrc.contiguous(), files[n * cap:], lengths[n:], self.video_quality, cap)
         return files, cap
 
+    def encode_png(self, g, u8, ku8, lengths):
+        """png_on="gpu", on the lane's stream: rib_png of the unit's frames uint8 [n,H0,W0,3] and - in a first chunk - of the key
+        frames ku8 uint8 [B,H0,W0,3] it starts from (else None), one call each -> (files, cap) as encode_video's.  cap is the
+        proven bound (rib_png_max_bytes): no frame can be refused."""
+        n, H0, W0, _ = u8.shape
+        nk = lengths.numel() - n
+        cap = g.png_max_bytes(H0, W0)
+        files = torch.empty((n + nk) * cap, dtype=torch.uint8, device=g.device)
+        g.png_into(u8, files[:n * cap], lengths[:n], cap)
+        if nk:
+            g.png_into(ku8, files[n * cap:], lengths[n:], cap)
+        return files, cap
+
     def save_sheets(self, clip, frames, sheets, out_blk=None, off=0):
         """Submits the encodes of the sheets of `frames` (uint8 [n, SH, SW, 3] on the host; out_blk: the shared block they lie
         in, from byte `off`) -> futures.  panel_encode="gpu": only the lossless copies are left to encode (panel_frames)."""
@@ -1486,19 +1538,25 @@ class _FolderPipeline:
         g.jpeg_into(sheets, files, lengths, self.panel_quality, cap)
         return files, cap
 
-    def fetch_jpeg(self, clip, frames, jpeg, video=False):
-        """panel_encode="gpu", on a finisher thread once the unit's copy is home: jpeg = (files, cap, lengths on the host) -
-        exactly the files' bytes come home and are written as the sheets' %04d.jpg, by this thread: no worker, no PIL.
-        video: the files are the frames' own (encode_video) and go to the clip's video folder."""
-        files, cap, lengths = jpeg
+    # the three kinds of files that are encoded on the GPU: (the option and entry a refusal names, what a file is, its name)
+    FILE_KINDS = {"sheet": ("panel_encode='gpu': rib_jpeg", "sheet", lambda clip, i: clip.sheet_names(i, False)[0]),
+                  "video": ("video=True: rib_jpeg_float", "frame", lambda clip, i: clip.video_name(i)),
+                  "png": ("png_on='gpu': rib_png", "frame", lambda clip, i: clip.names[i])}
+
+    def fetch_files(self, clip, frames, enc, kind="sheet"):
+        """On a finisher thread once the unit's copy is home: enc = (files, cap, lengths on the host) of one encoder - exactly the
+        files' bytes come home and are written by this thread: no worker, no PIL.  kind (FILE_KINDS): "sheet", the sheets'
+        %04d.jpg (panel_encode="gpu"); "video", the frames' own .jpg in the clip's video folder (encode_video); "png", the
+        frames' PNG files under their own names (png_on="gpu", encode_png).  A zero length raises, naming the frame."""
+        files, cap, lengths = enc
+        what, noun, name_of = self.FILE_KINDS[kind]
         sizes = [int(v) for v in lengths.tolist()]
         if not all(0 < v <= cap for v in sizes):
-            raise RuntimeError("%s refused a %s (lengths %s, cap %d)" % ("video=True: rib_jpeg_float" if video else "panel_encode='gpu': rib_jpeg",
-                                                                          "frame" if video else "sheet", sizes, cap))
+            bad = [name_of(clip, i) for i, v in zip(frames, sizes) if not 0 < v <= cap]
+            raise RuntimeError("%s refused a %s: %s (lengths %s, cap %d)" % (what, noun, ", ".join(bad), sizes, cap))
         with torch.cuda.stream(self.copy_stream(files.device)):
             host = [files[j * cap:j * cap + sizes[j]].cpu() for j in range(len(frames))]     # each returns when its bytes are home
-        return [_panel.save_jpeg(host[j].numpy().tobytes(), clip.video_name(i) if video else clip.sheet_names(i, False)[0])
-                for j, i in enumerate(frames)]
+        return [_panel.save_jpeg(host[j].numpy().tobytes(), name_of(clip, i)) for j, i in enumerate(frames)]
 
     def copy_stream(self, device):
         """The stream of the finishers' exact-size file copies (one per device): the lane's work they read is complete."""
@@ -1520,7 +1578,7 @@ class _FolderPipeline:
         n, (SH, SW) = len(loose), self.sheet_hw if self.panels else (0, 0)
         home = self.panels and (not self.jpeg_gpu or self.panel_frames)     # the raw sheets travel home
         spec = (("sheet_len", torch.int32, (n,), self.jpeg_gpu), ("video_len", torch.int32, (n,), self.video),
-                ("sheets", torch.uint8, (n, SH, SW, 3), home))
+                ("png_len", torch.int32, (n,), self.png_gpu), ("sheets", torch.uint8, (n, SH, SW, 3), home))
         table, total = block_layout(spec_bytes(spec))
         if self.panels and self.mci:             # a key frame's background is the key frame itself (frame k = 0 of the interpolation)
             dains = [clip.key_u8[k] for k in loose]
@@ -1530,7 +1588,7 @@ class _FolderPipeline:
             buf = torch.empty(total, dtype=torch.uint8, device=g.device)
             dev = section_views(buf, spec, table)
             keys = torch.stack([g_[1] for g_ in got]).to(g.device, torch.float32).contiguous()
-            keep, jpeg, vid = [buf, keys], None, None
+            keep, jpeg, vid, pngs = [buf, keys], None, None, None
             if self.panels:
                 poses = [g_[2] for g_ in got]
                 if self.gpu_labels:
@@ -1545,12 +1603,17 @@ class _FolderPipeline:
                 keep += [sheets, kdn, klab]
                 if self.jpeg_gpu:                # the files of both encoders stay on the device until their lengths are home
                     jpeg = self.encode_jpeg(g, sheets, dev["sheet_len"])
-            if self.video and self.source:       # the key files' own pixels at the clip's output size
+            ku8 = None
+            if (self.video or self.png_gpu) and self.source:       # the key files' own pixels at the clip's output size
                 ku8 = torch.from_numpy(np.stack([clip.key_src[k].result(timeout=IO_TIMEOUT_S) for k in loose])).to(g.device)
+                keep += [ku8]
+            if self.png_gpu:
+                pngs = self.encode_png(g, ku8 if self.source else g.quantise(keys), None, dev["png_len"])
+                keep += [pngs]
+            if self.video and self.source:
                 cap = g.jpeg_max_bytes(*ku8.shape[1:3])
                 vid = (torch.empty(n * cap, dtype=torch.uint8, device=g.device), cap)
                 g.jpeg_into(ku8, vid[0], dev["video_len"], self.video_quality, cap)
-                keep += [ku8]
             elif self.video:
                 cap = g.jpeg_max_bytes(*keys.shape[2:])
                 vid = (torch.empty(n * cap, dtype=torch.uint8, device=g.device), cap)
@@ -1565,17 +1628,19 @@ class _FolderPipeline:
         def finish(keep=keep):
             done.synchronize()
             if jpeg is not None:
-                self.fetch_jpeg(clip, loose, jpeg + (host["sheet_len"],))
-            names = self.fetch_jpeg(clip, loose, vid + (host["video_len"],), video=True) if vid is not None else None
+                self.fetch_files(clip, loose, jpeg + (host["sheet_len"],))
+            names = self.fetch_files(clip, loose, vid + (host["video_len"],), "video") if vid is not None else None
+            if pngs is not None:                 # (png_on="gpu" implies frames="png": the names reported are the PNGs')
+                names = self.fetch_files(clip, loose, pngs + (host["png_len"],), "png")
             if home:
                 for f in self.save_sheets(clip, loose, host["sheets"], out_blk, table["sheets"][0]):
                     f.result(timeout=IO_TIMEOUT_S)
             if out_blk is not None:
                 _shm_put(out_blk)
-            return names                         # frames="none": the .jpg names of the loose key frames, in order
+            return names                         # frames="none": the .jpg names of the loose key frames, in order; png_on="gpu": the PNGs'
         fut = self.finishers.submit(finish)
         clip.sheet_futs.append(fut)
-        if self.video and not self.write_png:
+        if (self.video and not self.write_png) or self.png_gpu:
             for j, k in enumerate(loose):
                 clip.futs[k] = (fut, j)
 
@@ -1598,26 +1663,29 @@ class _FolderPipeline:
         # panels: the JPEG (and PNG) encodes of the unit's sheets fan out beside the PNG encodes of its frames
         sheet_fs = self.save_sheets(clip, r["sheet_frames"], r["sheets"], out_blk, r["sheets_off"]) if r["sheets"] is not None else []
         fs = []
-        if self.write_png and out_blk is not None:      # the workers read frame j in the block, from the section's offset on
+        if self.stage_png and out_blk is not None:      # the workers read frame j in the block, from the section's offset on
             (fh, fw), off = r["frame_hw"], r["frames_off"]
             fsz = fh * fw * 3
             fs = [self.procs.submit(io_worker.save_png_shm, out_blk.name, off + j * fsz, fh, fw, clip.names[out_frames[j]], self.level)
                   for j in range(len(out_frames))]
-        elif self.write_png:
+        elif self.stage_png:
             qn = r["frames"].numpy()
             fs = [self.pool.submit(self.save_q, qn[j], clip.names[out_frames[j]]) for j in range(len(out_frames))]
         # panel_encode="gpu" / video: the files' bytes come home now that their lengths have, while the workers encode the PNGs
         if r["jpeg"] is not None:
-            self.fetch_jpeg(clip, r["sheet_frames"], r["jpeg"])
-        vres = self.fetch_jpeg(clip, self.video_frames_of(clip, ui), r["video"], video=True) if r["video"] is not None else None
+            self.fetch_files(clip, r["sheet_frames"], r["jpeg"])
+        vres = self.fetch_files(clip, self.video_frames_of(clip, ui), r["video"], "video") if r["video"] is not None else None
+        pres = self.fetch_files(clip, self.video_frames_of(clip, ui), r["png"], "png") if r["png"] is not None else None
         res = [f.result(timeout=IO_TIMEOUT_S) for f in fs]
         for f in sheet_fs:
             f.result(timeout=IO_TIMEOUT_S)
-        r["frames"] = r["qual"] = r["sheets"] = r["jpeg"] = r["video"] = None       # (the views of the block go before the block does)
+        r["frames"] = r["qual"] = r["sheets"] = r["jpeg"] = r["video"] = r["png"] = None       # (the views of the block go before the block does)
         if out_blk is not None:
             _shm_put(out_blk)
         r["keep"] = None
         mark.append(round(time.perf_counter() - self.t_wall, 4))
+        if self.png_gpu:
+            return pres                         # the PNG names, the unit's frames and then its key frames
         return res if self.write_png else vres      # frames="none": the .jpg names, the unit's frames and then its key frames
 
     # ---- drivers ---------------------------------------------------------------------------------------------------------
@@ -1643,11 +1711,11 @@ class _FolderPipeline:
             seg_fut = self.finishers.submit(self.sink, clip, ui, r, t1 - self.t_wall, t3 - self.t_wall)
             self.inflight.append(seg_fut)
             tm["peak_units_in_flight"] = max(tm["peak_units_in_flight"], len(self.inflight))
-            for j, i in enumerate(clip.unit_frames(ui) if self.write_png else self.video_frames_of(clip, ui)):
+            for j, i in enumerate(clip.unit_frames(ui) if self.stage_png else self.video_frames_of(clip, ui)):
                 clip.futs[i] = (seg_fut, j)
         for k in clip.keys:
             self.submit_load(clip, k)
-        if self.panels or self.video:
+        if self.panels or self.video or self.png_gpu:
             self.loose_keys(clip, *(lanes[0] if lanes else (self.model, torch.cuda.current_stream(self.model.device))))
         tm["units"] = tm.get("units", 0) + len(clip.units)
         tm["frames"] += len(clip.futs)

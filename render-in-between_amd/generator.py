@@ -17,6 +17,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Dict, Optional
 
+import numpy as np
 import torch
 
 from . import _native
@@ -808,6 +809,67 @@ class Generator:
         n = lengths.cpu().tolist()
         if not all(v > 0 for v in n):
             raise RuntimeError("jpeg: a frame exceeded rib_jpeg_max_bytes (%d bytes): the staging bound is wrong" % cap)
+        return [dst[t * cap:t * cap + n[t]].cpu().numpy().tobytes() for t in range(T)]
+
+    def png_max_bytes(self, height, width):
+        """Upper bound of one PNG file of a height x width frame (rib_png_max_bytes; png.max_bytes)."""
+        n = int(self._lib.rib_png_max_bytes(int(height), int(width)))
+        if n == 0:
+            raise ValueError("png: height must be in 1..65535 and width in 1..4096, got %dx%d" % (height, width))
+        return n
+
+    def png_into(self, frames_u8, dst, lengths, cap=None, tables=None):
+        """The lower-level form of png(): encodes uint8 [T,H,W,3] on this device into the caller's buffers and only enqueues (two
+        launches on the current stream, no synchronisation).  dst: a contiguous 1-D uint8 device tensor of at least T * cap
+        bytes, any byte alignment - frame t's file starts at dst[t * cap]; lengths: a contiguous int32 [T] device tensor
+        receiving each file's size.  cap (default dst.numel() // T) below png_max_bytes(H, W) is allowed: a frame whose file
+        would not fit writes nothing and gets length 0, which the caller has to check once the lengths are home.  Bytes of a
+        frame's cap behind its length are not written.  tables: uint8 [K, 286] code lengths, by default png.TABLES (the library
+        validates them and keeps their device copy on the handle).  -> cap."""
+        if not torch.is_tensor(frames_u8) or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3 or frames_u8.dtype != torch.uint8 \
+                or frames_u8.device != self.device or not frames_u8.is_contiguous():
+            raise ValueError("png: frames must be a contiguous uint8 [T,H,W,3] tensor on %s" % (self.device,))
+        T, H, W, _ = frames_u8.shape
+        self.png_max_bytes(H, W)
+        if T < 1 or T > 65535:
+            raise ValueError("png: 1 <= T <= 65535 frames, got %d" % T)
+        if dst.dim() != 1 or dst.dtype != torch.uint8 or dst.device != self.device or not dst.is_contiguous():
+            raise ValueError("png: dst must be a contiguous 1-D uint8 tensor on %s" % (self.device,))
+        if tuple(lengths.shape) != (T,) or lengths.dtype != torch.int32 or lengths.device != self.device or not lengths.is_contiguous():
+            raise ValueError("png: lengths must be a contiguous int32 [%d] tensor on %s" % (T, self.device))
+        cap = dst.numel() // T if cap is None else int(cap)
+        if cap < 1 or cap >= 2 ** 31 or T * cap > dst.numel():
+            raise ValueError("png: cap=%d: at least 1, below 2 GiB, and T * cap within dst (%d bytes)" % (cap, dst.numel()))
+        if tables is None:
+            from . import png as _png
+            tables = _png.TABLES
+        tables = np.ascontiguousarray(tables)
+        if tables.dtype != np.uint8 or tables.ndim != 2 or tables.shape[1] != 286:
+            raise ValueError("png: tables must be a uint8 [K, 286] array")
+        n = int(self._lib.rib_png_workspace_bytes(self._h, T, H, W))
+        cache = self.__dict__.setdefault("_png_ws", {})
+        ws = cache.get((T, H, W))
+        if ws is None:
+            ws = cache[(T, H, W)] = torch.empty(n, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _native.check(self._h, self._lib.rib_png(self._h, T, H, W, _ptr(frames_u8), tables.ctypes.data, int(tables.shape[0]), _ptr(dst),
+                                                     cap, _ptr(lengths), _ptr(ws), self._stream()))
+        return cap
+
+    def png(self, frames_u8, tables=None):
+        """Lossless PNG files of T frames on the GPU (rib_png, csrc/png.hip.h; png.encode_host is the definition and is bit-equal):
+        uint8 [T,H,W,3] on this device -> list of T bytes objects.  Every file has png_max_bytes(H, W) of room, so none is
+        refused; the lengths come home first, then exactly the files' bytes."""
+        if not torch.is_tensor(frames_u8) or frames_u8.dim() != 4:
+            raise ValueError("png: frames must be a uint8 [T,H,W,3] tensor")
+        T, H, W, _ = frames_u8.shape
+        cap = self.png_max_bytes(H, W)
+        dst = torch.empty(T * cap, dtype=torch.uint8, device=self.device)
+        lengths = torch.empty(T, dtype=torch.int32, device=self.device)
+        self.png_into(frames_u8, dst, lengths, cap, tables)
+        n = lengths.cpu().tolist()
+        if not all(v > 0 for v in n):
+            raise RuntimeError("png: a frame exceeded rib_png_max_bytes (%d bytes): the bound is wrong" % cap)
         return [dst[t * cap:t * cap + n[t]].cpu().numpy().tobytes() for t in range(T)]
 
     def jpeg_f32_into(self, frames, dst, lengths, quality=90, cap=None):

@@ -32,6 +32,13 @@ the float frames by rib_jpeg_float; `--video-frames` keeps the .jpg files in <cl
 only the video: no PNG is encoded and the raw frames stay on the device.  Container and stream are this project's, unpinned: PIL
 is the only decoder that has read them.
 
+Lossless frames encoded on the GPU: `--png-on gpu` (default `host`: PIL in the file workers) writes every frame PNG - key frames
+included - with rib_png on the lane's stream: per strip of 8 rows a PNG filter per row, runs at distance 1 as the only matches and
+the cheapest of a fixed set of Huffman tables (png.py states every byte; stream and tables are this project's, every standard
+decoder reads the file).  The same names and pixels as the default run, other file bytes: typically the size of zlib level 1,
+larger than level 6 on smooth content and than level 1 on flat graphics; frames up to 4096 wide.  Not with --frames none or an
+explicit --png-level; --panel-frames sheets stay with the host workers.
+
 Backgrounds without a DAIN folder: `--background mci` makes every background frame on the GPU from the segment's two key
 frames - a classical motion-compensated interpolation (background.py states it in integers; rib_mci_field / rib_mci_frames) -
 and never reads <input>/DAIN.  It is this project's interpolation, not DAIN: the generator was trained on DAIN backgrounds, the
@@ -187,7 +194,8 @@ def main(opts):
                                              mci_border=opts.mci_border, mci_precision=opts.mci_precision,
                                              video=opts.video, video_fps=30 if opts.video_fps is None else opts.video_fps,
                                              video_quality=90 if opts.video_quality is None else opts.video_quality,
-                                             video_frames=opts.video_frames, frames=opts.frames, output_size=opts.output_size, **poses_kw)
+                                             video_frames=opts.video_frames, frames=opts.frames, output_size=opts.output_size, png_on=opts.png_on,
+                                             **poses_kw)
     print(summary_line(evaluator, rank, world))
     if world > 1:
         print("[rank {}/{}] wrote {} frames".format(rank, world, len(written)))
@@ -212,6 +220,11 @@ def build_parser():
                         help="'reference' (default): PIL's default deflate level 6, the very bytes PGNR/utils/utils.py:139-142 writes - 54 ms of "
                              "CPU per 512x512 frame, i.e. the end-to-end rate is bound by the host cores (~200 frames/s on 16); 0-9: that zlib "
                              "level - same pixels, other file bytes (1: ~2x the end-to-end rate, ~25 %% larger files)")
+    parser.add_argument("--png-on", choices=("host", "gpu"), default="host",
+                        help="where the frames' PNG files are encoded. 'host' (default): PIL in the file workers, at --png-level; 'gpu': the "
+                             "HIP encoder (rib_png; png.py states the stream: run-length plus table-selected Huffman, this project's own) - "
+                             "the same names and pixels, other file bytes, about the size of zlib level 1; not with --frames none or an "
+                             "explicit --png-level")
     parser.add_argument("--reproducible", action=argparse.BooleanOptionalAction, default=True,
                         help="(default) every group size follows the kernel choices of the full group, so a frame's bytes do not depend "
                              "on segment grouping, on --gpus N or on --batch 1 vs N-rank shares; --no-reproducible lets ragged groups "
@@ -302,6 +315,10 @@ def parse_args(argv=None):
     opts = parser.parse_args(argv)
     if opts.png_level != "reference" and opts.png_level not in [str(i) for i in range(10)]:
         parser.error("--png-level must be 'reference' or a zlib level 0-9")
+    if opts.png_on == "gpu" and opts.png_level != "reference":
+        parser.error("--png-on gpu writes this project's own stream: --png-level is a setting of the host encoder")
+    if opts.png_on == "gpu" and opts.frames != "png":
+        parser.error("--png-on gpu encodes the frames' PNG files: not with --frames %s" % opts.frames)
     if opts.background not in ("dain", "mci"):
         parser.error("--background must be 'dain' or 'mci', got %r" % (opts.background,))
     if opts.poses not in ("folder", "keyframes", "keyframes-linear"):

@@ -4,6 +4,7 @@
     python tools/driver_bench.py [--size 512 | --height 320 --width 480] [--keys 5] [--rate 32] [--lanes 2] [--batch B] [--chunk 4]
                                   [--src-width 1920 --src-height 1080] [--resize-on host|gpu] [--metrics [--pose-mask]] [--panels [--panel-encode host|gpu]]
                                   [--video [--frames none]] [--poses folder|keyframes] [--output-size model|source|keyframes]
+                                  [--png-on host|gpu]
 
 Writes a clip in the reference's directory layout (inputs/ DAIN/ Predict_motion/), runs
 Evaluator.evaluate_from_folder twice (the first run also builds launch plans) and prints the
@@ -21,6 +22,8 @@ read per frame; --rate must then be a power of two); the per-clip event time of 
 rib_composite launch per unit; the PNG encode then works on source-size frames).  --output-size keyframes (with --background mci)
 does the same at the size of the key frame files (output_size="keyframes": one rib_scaled_frames launch per unit makes the
 backgrounds, --src-width / --src-height say how large the key frames are).
+--png-on gpu encodes the frames' PNG files on the lane's stream (png_on="gpu": rib_png, this project's own stream; --compress
+then plays no part and must be left at its default); the bytes of the last run's PNG files are reported either way.
 """
 import argparse, json, os, sys, tempfile, time
 import numpy as np, torch
@@ -98,7 +101,10 @@ def main():
     ap.add_argument("--output-size", default="model", choices=("model", "source", "keyframes"),
                     help="'source' (with --resize-on gpu): the frames' files at the input files' size, composited on the GPU; 'keyframes' "
                          "(with --background mci): the same from the key frame files, the backgrounds by rib_scaled_frames (output_size=...)")
+    ap.add_argument("--png-on", default="host", choices=("host", "gpu"), help="where the frames' PNG files are encoded: PIL in the file workers or rib_png (png_on=...)")
     a = ap.parse_args()
+    if a.png_on == "gpu" and (a.compress >= 0 or a.frames == "none"):
+        ap.error("--png-on gpu is not combined with --compress or --frames none")
     if a.output_size == "keyframes" and a.background != "mci":
         ap.error("--output-size keyframes is a setting of --background mci")
     if a.output_size == "source" and (a.resize_on != "gpu" or a.background == "mci"):
@@ -155,12 +161,14 @@ def main():
                                          metrics=a.metrics, pose_mask=a.pose_mask, panels=a.panels, panel_encode=a.panel_encode,
                                          background=a.background, video=a.video, frames=a.frames, **kw,
                                          **({"output_size": a.output_size} if a.output_size != "model" else {}),
+                                         **({"png_on": a.png_on} if a.png_on != "host" else {}),
                                          **({"mci_range": a.mci_range} if a.background == "mci" else {}),
                                          **({"mci_border": a.mci_border} if a.mci_border != "clamp" else {}),
                                          **({"mci_precision": a.mci_precision} if a.mci_precision != "full" else {}))
             torch.cuda.synchronize()
             walls.append(time.perf_counter() - t0)
         tm = dict(E.timings)
+        png_bytes = sum(os.path.getsize(f) for f in out if f.endswith(".png"))
         overall = dict(E.metrics_report["overall"]) if a.metrics else None
     gen = n - a.keys
     wall = sorted(walls[1:])[len(walls[1:]) // 2]
@@ -171,7 +179,7 @@ def main():
                       "mci_border": a.mci_border if a.background == "mci" else None,
                       "mci_precision": a.mci_precision if a.background == "mci" else None,
                       "metrics": a.metrics, "pose_mask": a.pose_mask, "metrics_overall": overall, "panels": a.panels, "panel_encode": a.panel_encode,
-                      "video": a.video, "frames_written": a.frames, "poses": a.poses, "stage1_plus_bridge_ms_per_clip": stage1_ms,
+                      "video": a.video, "frames_written": a.frames, "png_on": a.png_on, "png_bytes_last_run": png_bytes, "poses": a.poses, "stage1_plus_bridge_ms_per_clip": stage1_ms,
                       "wall_s": wall, "wall_s_runs": [round(w, 4) for w in walls[1:]], "frames_per_s_end_to_end": n / wall,
                       "phase_s_last_run": {k: round(v, 4) for k, v in tm.items() if k not in ("frames", "units", "timeline", "peak_units_in_flight")},
                       "peak_units_in_flight": tm.get("peak_units_in_flight"),
