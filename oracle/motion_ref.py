@@ -74,7 +74,7 @@ def multihead_attention(q_in, k_in, v_in, sd, prefix, nhead, attn_mask=None, key
     q = q.reshape(Lq, N * nhead, hd).transpose(0, 1)
     k = k.reshape(Lk, N * nhead, hd).transpose(0, 1)
     v = v.reshape(Lk, N * nhead, hd).transpose(0, 1)
-    bias = torch.zeros(N, 1, Lq, Lk)
+    bias = torch.zeros(N, 1, Lq, Lk, dtype=q.dtype)
     if attn_mask is not None:
         bias = bias.masked_fill(attn_mask.view(1, 1, Lq, Lk), float("-inf"))
     if key_padding_mask is not None:
@@ -164,6 +164,16 @@ def transformer_forward(sd: Dict[str, torch.Tensor], cfg: dict, src, src_mask, s
     t = layer_norm(t, sd, "decoder.norm")
     joints = F.linear(t, sd["joints_embed.weight"], sd["joints_embed.bias"]) + center
     return joints, reco
+
+
+def transformer_forward_f64(sd, cfg, src, src_mask, src_pos, tgt, tgt_mask, tgt_pos, rate: int):
+    """transformer_forward with every operation in double: the state dict and the float inputs are cast, the
+    positional tables keep their fp32 values (they are inputs, the product reads the same table).  What is
+    left of the difference to a kernel is the kernel's own rounding, not the oracle's.  -> double (joints, reco)."""
+    def f64(t):
+        return t.to(torch.float64)
+    return transformer_forward({k: f64(v) for k, v in sd.items()}, cfg, f64(src), src_mask, f64(src_pos), f64(tgt), tgt_mask,
+                               f64(tgt_pos), rate)
 
 
 def model_inference(sd, cfg, data, interp, encoder_mask, decoder_mask, rate):
