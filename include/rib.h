@@ -332,7 +332,7 @@ int rib_png(rib_handle* h, int T, int H, int W, const uint8_t* src_u8_nhwc,
  * L levels, bilateral 8x8 block matching (full search over [-4,4]^2 on the top level - with L = 3 at quarter size, i.e. +-32 px
  * of motion between the key frames; +-1 refinements on every level below; the minimum of (cost, dx^2+dy^2, dy, dx)), a 3x3 median,
  * a bilinear per-pixel field in 1/256 px, two fixed-point bilinear samples and a blend - and the kernels are bit-equal to it.
- * No occlusion reasoning inside the frame.  The search itself is in whole pixels; rib_halfpel_refine (below) adds one half-pel step.
+ * No occlusion reasoning inside the frame unless the person is excluded (`rib_masked_*`, below).  The search itself is in whole pixels; rib_halfpel_refine (below) adds one half-pel step.
  * rib_mci_field: a_u8, b_u8 uint8 NHWC [B,H,W,3] on the device (left and right key frame of B segments at the model size) ->
  * field_i16 int16 [B,Hb,Wb,2] on the device, (dx, dy) per 8x8 block of the intermediate frame (rib_mci_field_shape:
  * Hb = ceil(H/8), Wb = ceil(W/8)); once per segment.  levels: L = 3, 4 or 5 pyramid levels (the driver's --mci-range 32, 64, 128:
@@ -352,7 +352,7 @@ int rib_png(rib_handle* h, int T, int H, int W, const uint8_t* src_u8_nhwc,
  * [T,B,H,W,3]; a NULL output is not wanted (both NULL is an error).  border: 0 = the blend of the two clamped samples; 1 = a
  * sample is valid when its position lies in [0, (H-1) << 8] x [0, (W-1) << 8], and where exactly one of the two samples is
  * valid the output is that sample alone (a hard switch), otherwise the blend.  Interior occlusion - a foreground object
- * covering background - is NOT handled.  Every element written; a frame's bytes do not depend on T or B.
+ * covering background - is NOT handled unless the person is excluded (`rib_masked_*`).  Every element written; a frame's bytes do not depend on T or B.
  * levels outside 3..5, border outside {0, 1}, B outside 1..32767, B * Hb * Wb >= 2^30, T < 1, T * B > 65535, H or W outside
  * 1..16384, a bad sample_rate or frame range, NULL or misaligned pointers: RIB_ERR_INVALID with a rib_last_error text, nothing
  * launched (the size query returns 0).
@@ -387,7 +387,34 @@ int rib_png(rib_handle* h, int T, int H, int W, const uint8_t* src_u8_nhwc,
  * synchronisation; every byte written; a frame's bytes do not depend on T or B.  rib_mci_frames' refusals, and also: H0 or W0
  * outside 1..16384, W0 > 16 W, W > 16 W0 (the same for the heights: beyond a ratio of 16 an offset could leave int32), precision
  * outside {0, 1}, out NULL: RIB_ERR_INVALID with a rib_last_error text that names the entry, nothing launched.  The field has the
- * model's resolution - motion detail finer than an 8x8 model block is not followed - and, as above, interior occlusion is not handled. */
+ * model's resolution - motion detail finer than an 8x8 model block is not followed - and, as above, interior occlusion is not handled.
+ * rib_masked_workspace_bytes / rib_masked_field / rib_masked_frames (the driver's --mci-person exclude; background.mci_field_masked_host
+ * and mci_frames_masked_host, bit-equal): rib_mci_field and rib_mci_frames with the person kept out.  ma_u8, mb_u8 uint8 [B,H,W] on
+ * the device, nonzero = EXCLUDED, for key frame A and key frame B (the driver passes rib_human_mask of the two key frames' poses).
+ * Field: an OR pyramid of the masks (a pixel is set iff any of its 2x2 clamped parents is); on every level and for either border a
+ * block's pixel p counts for candidate d iff the border rule lets it count and MA(clamp(p - d)) == 0 and MB(clamp(p + d)) == 0 (n
+ * counted pixels of the block's N); a candidate is valid iff 4 n >= N, costs (64 * SAD over the counted pixels) / n + LAMBDA (|dx| +
+ * |dy|), the winner is the minimum key over the valid candidates, and a block whose start candidate is not valid is not searched
+ * and keeps its start.  On the TOP level such a block then takes the vector of the searched block within Chebyshev distance 8 that
+ * minimises (max(|Dy|,|Dx|), |Dy|+|Dx|, Dy, Dx), or (0, 0); below it, it keeps twice the coarser block's vector.  Median and
+ * per-pixel field are rib_mci_field's.  workspace: rib_masked_workspace_bytes(h, B, H, W, levels) bytes on the device (rib_mci_field's
+ * plus the mask planes, one plane of flags and the top level's field before the fill), 16-byte aligned, nothing to clear.  L + 4
+ * launches on `stream` (rib_mci_field's, the mask pyramid and the fill); no atomics, no synchronisation, a segment's field does not
+ * depend on B.  Frames: a sample is clean iff the border rule calls it valid (border = 0: always) and the four taps of its bilinear
+ * footprint in its key frame's mask, clamped as the sample's taps are, are all zero; where exactly one of a pixel's two samples is
+ * clean the output is that sample alone (a hard switch, with a seam where it flips), otherwise the blend; k = 0 and k = sample_rate
+ * stay A and B.  precision: 0 = the field in whole pixels (rib_mci_frames), 1 = in half pixels (rib_halfpel_frames) - here an
+ * argument, not a second entry.  ONE launch, both outputs as rib_mci_frames', a frame's bytes do not depend on T or B.  With
+ * all-zero masks the frames are rib_mci_frames' and, under border = 1, the field rib_mci_field's.  The refusals are those of the
+ * unmasked entries, and also: a NULL mask, precision outside {0, 1}: RIB_ERR_INVALID with a rib_last_error text that names the
+ * entry, nothing launched (the size query returns 0).  The three are named rib_masked_*, not rib_mci_*: that family stays at four.
+ * Only the masked pixels are kept out: background hidden in BOTH key frames stays a blend, and other moving objects are not handled. */
+size_t rib_masked_workspace_bytes(rib_handle* h, int B, int H, int W, int levels);
+int rib_masked_field(rib_handle* h, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const uint8_t* ma_u8,
+                     const uint8_t* mb_u8, int16_t* field_i16, int levels, int border, void* workspace, void* hip_stream);
+int rib_masked_frames(rib_handle* h, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const uint8_t* ma_u8,
+                      const uint8_t* mb_u8, const int16_t* field_i16, int sample_rate, int k_first, int border, int precision,
+                      float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream);
 int rib_scaled_frames(rib_handle* h, int T, int B, int H, int W, int H0, int W0, const uint8_t* a0_u8, const uint8_t* b0_u8,
                       const int16_t* field_i16, int sample_rate, int k_first, int border, int precision, uint8_t* out_u8_nhwc,
                       void* hip_stream);

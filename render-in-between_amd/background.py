@@ -66,9 +66,31 @@ rib_halfpel_frames) are held bit-equal to them (tests/test_gpu_mci.py, tests/tes
              the lines of "frame k" and "border" above in output coordinates - the function's text has the four steps.  Motion
              detail finer than a model block is not followed.
 
+  person     (mci_field_masked_host / mci_frames_masked_host, the driver's mci_person="exclude"; rib_masked_field / rib_masked_frames,
+             tests/test_gpu_mci_person.py; off by default).  ma, mb uint8 [H, W], nonzero = EXCLUDED, for key frame A and B: the
+             driver passes the human masks of the two key frames' poses.  Mask pyramid: level l+1 is ceil(h/2) x ceil(w/2), a pixel
+             is 1 iff any of its 2x2 parents (clamped as the luma pyramid clamps them) is nonzero.  Masked cost, on every level
+             and for either border: a block's pixel p counts for candidate d iff the border rule lets it count (clamp: always;
+             valid: the rectangle above) and MA(clamp(p - d)) == 0 and MB(clamp(p + d)) == 0; n the counted pixels, N the block's
+             pixels inside the plane; a candidate is valid iff VALID_SHARE * n >= N, costs (64 * SAD over the counted pixels) // n
+             + LAMBDA * (|dx| + |dy|), the key is pack_key_wide for every L, the winner the minimum key over the valid candidates;
+             a block whose start candidate is not valid is NOT SEARCHED: it keeps its start and a per-block flag says so -
+             block_cost_valid / search_valid with a counted n in place of the closed-form rectangle.  Fill, on the TOP level only:
+             a block that was not searched takes the vector of the SEARCHED block within Chebyshev distance FILL_RADIUS = 8 that
+             minimises (max(|Dy|, |Dx|), |Dy| + |Dx|, Dy, Dx) (D = source - block, in blocks), (0, 0) if there is none; only
+             searched blocks are sources, so the result does not depend on the order of evaluation.  Below the top a block that is
+             not searched keeps its start - twice the coarser block's vector, by then background motion.  Median and per-pixel
+             field are unchanged.  Frames: a sample is CLEAN iff the border rule calls it valid (clamp: always) and the four taps of
+             its bilinear footprint in the level-0 mask of its key frame (coordinates clamped as sample_bilinear clamps them) are
+             all zero; where exactly one of a pixel's two samples is clean the output is that sample alone, otherwise the blend -
+             the "valid" switch with one more condition.  All-zero masks: border="valid" gives mci_field_host's field bit for bit,
+             "clamp" gives it when both sides are multiples of 8 << (L-1) (every block full: 64 SAD // 64 = SAD), the frames are
+             mci_frames_host's for every shape; all-one masks: the zero field and the plain cross-fade.  Only the person is
+             handled, by the reference's coarse pose mask; background hidden in BOTH key frames stays a blend.
+
 No quarter-pel search, no sub-pel search on the coarse levels, and no occlusion reasoning beyond the frame border under
-border="valid" - a foreground object that covers background is not handled: see DESIGN ("Motion-compensated backgrounds") for
-what that costs."""
+border="valid" - a foreground object that covers background is not handled unless the person is excluded (`rib_masked_*`): see
+DESIGN ("Motion-compensated backgrounds") for what that costs."""
 from __future__ import annotations
 
 import numpy as np
@@ -91,6 +113,8 @@ VALID_SHARE = 4           # border="valid": a candidate counts when VALID_SHARE 
 LAMBDA_HALF = 2           # mci_refine_host: cost of one HALF pixel of |hx| + |hy| (h = 2 d costs what d costs on level 0)
 HALF_KEY_BIAS = 256       # pack_key_half: hy + 256, hx + 256 in 9 bits each (|h| <= 2 * max_disp(5) + 1 = 159)
 PRECISIONS = ("full", "half")             # `precision` of mci_frames_host; the driver's mci_precision
+PERSONS = ("keep", "exclude")             # the driver's mci_person: "exclude" = the *_masked_host functions with the key frames' human masks
+FILL_RADIUS = 8           # mci_field_masked_host: a top-level block that was not searched looks this far (Chebyshev, in blocks) for a searched one
 
 
 def field_shape(height, width):
@@ -131,10 +155,23 @@ def check_precision(precision, who):
     return precision
 
 
-def check_settings(background, mci_range, mci_border, resize_on, who="evaluate_from_folder", mci_precision="full"):
+def check_settings(background, mci_range, mci_border, resize_on, who="evaluate_from_folder", mci_precision="full", mci_person="keep",
+                   output_size="model"):
     """The folder driver's background settings -> (levels, border) for the functions below.
     mci_precision: "full" (the default) or "half" (mci_refine_host after the field, mci_frames_host(precision="half")); checked
-    here, and the caller's to pass on."""
+    here, and the caller's to pass on.  mci_person: "keep" (the default) or "exclude" (mci_field_masked_host /
+    mci_frames_masked_host with the key frames' human masks); refused with mci_precision="half" and with output_size="keyframes",
+    which have no masked form yet."""
+    if not isinstance(mci_person, str) or mci_person not in PERSONS:
+        raise ValueError("%s: mci_person must be 'keep' or 'exclude', got %r" % (who, mci_person))
+    if background != "mci" and mci_person != "keep":
+        raise ValueError("%s: mci_person is a setting of background='mci'" % who)
+    if mci_person == "exclude" and mci_precision == "half":
+        raise ValueError("%s: mci_person='exclude' with mci_precision='half' is not supported yet (the half-pel refinement has no "
+                         "masked form: a masked rib_halfpel_refine is the follow-up)" % who)
+    if mci_person == "exclude" and output_size == "keyframes":
+        raise ValueError("%s: mci_person='exclude' with output_size='keyframes' is not supported yet (rib_scaled_frames has no "
+                         "masked form: a masked rib_scaled_frames is the follow-up)" % who)
     if background not in ("dain", "mci"):
         raise ValueError("%s: background must be 'dain' or 'mci', got %r" % (who, background))
     if background == "mci" and resize_on == "gpu":
@@ -467,6 +504,179 @@ def mci_frames_host(a_u8, b_u8, field, sample_rate, ks, border="clamp", precisio
         if border == "valid":
             oka, okb = sample_valid(Y - ay, X - ax, H, W)[..., None], sample_valid(Y + by, X + bx, H, W)[..., None]
             o = np.where(oka == okb, o, np.where(oka, a, b))
+        out[j] = o.astype(np.uint8)
+    return out
+
+
+# ---- the person kept out (mci_person="exclude"): the module text's "person" paragraph ---------------------------------------
+
+def check_masks(ma, mb, height, width, who):
+    """ma, mb -> bool [H, W] (nonzero = excluded)."""
+    ma, mb = np.asarray(ma), np.asarray(mb)
+    for m in (ma, mb):
+        if m.dtype != np.uint8 or tuple(m.shape) != (height, width):
+            raise ValueError("%s: the masks of %dx%d key frames are uint8 [%d, %d], got %s %s" % (who, height, width, height, width, m.dtype, tuple(m.shape)))
+    return ma != 0, mb != 0
+
+
+def down2_or(m):
+    """One step of the mask pyramid: bool [h, w] -> bool [ceil(h/2), ceil(w/2)], a pixel is set iff any of its 2x2 parents
+    (clamped as down2 clamps them) is."""
+    h, w = m.shape
+    r0, c0 = 2 * np.arange((h + 1) // 2), 2 * np.arange((w + 1) // 2)
+    r1, c1 = np.minimum(r0 + 1, h - 1), np.minimum(c0 + 1, w - 1)
+    return m[r0][:, c0] | m[r0][:, c1] | m[r1][:, c0] | m[r1][:, c1]
+
+
+def mask_pyramid(m, levels=LEVELS):
+    """uint8 or bool [H, W] (nonzero = excluded) -> [bool planes], level 0 first."""
+    out = [np.asarray(m) != 0]
+    for _ in range(levels - 1):
+        out.append(down2_or(out[-1]))
+    return out
+
+
+def block_cost_masked(ya, yb, ma, mb, dx, dy, border="clamp"):
+    """(cost, valid, n) of every block of one level with the excluded pixels left out: block_cost_valid with a counted n.  A
+    pixel p counts iff the border rule lets it (clamp: always; valid: p - d and p + d inside the plane) and ma(clamp(p - d)) and
+    mb(clamp(p + d)) are both clear; cost = (64 * SAD over the counted pixels) // n + LAMBDA * (|dx| + |dy|) (0 where n = 0),
+    valid = VALID_SHARE * n >= N, N the block's pixels inside the plane."""
+    h, w = ya.shape
+    Hb, Wb = field_shape(h, w)
+    px = np.repeat(np.repeat(dx, BLOCK, 0), BLOCK, 1)[:h, :w]
+    py = np.repeat(np.repeat(dy, BLOCK, 0), BLOCK, 1)[:h, :w]
+    Y, X = np.mgrid[0:h, 0:w]
+    ay, ax, by, bx = np.clip(Y - py, 0, h - 1), np.clip(X - px, 0, w - 1), np.clip(Y + py, 0, h - 1), np.clip(X + px, 0, w - 1)
+    counts = ~ma[ay, ax] & ~mb[by, bx]
+    if border == "valid":
+        counts &= (Y - py >= 0) & (Y - py <= h - 1) & (Y + py >= 0) & (Y + py <= h - 1) \
+            & (X - px >= 0) & (X - px <= w - 1) & (X + px >= 0) & (X + px <= w - 1)
+    a, b = ya[ay, ax].astype(np.int32), yb[by, bx].astype(np.int32)
+    sad = np.zeros((Hb * BLOCK, Wb * BLOCK), np.int64)
+    sad[:h, :w] = np.where(counts, np.abs(a - b), 0)
+    cnt = np.zeros((Hb * BLOCK, Wb * BLOCK), np.int64)
+    cnt[:h, :w] = counts
+    n = cnt.reshape(Hb, BLOCK, Wb, BLOCK).sum((1, 3))
+    N = valid_counts(h, w, np.zeros_like(dx), np.zeros_like(dy))[1]
+    cost = (64 * sad.reshape(Hb, BLOCK, Wb, BLOCK).sum((1, 3))) // np.maximum(n, 1) + LAMBDA * (np.abs(dx) + np.abs(dy))
+    return cost, VALID_SHARE * n >= N, n
+
+
+def search_masked(ya, yb, ma, mb, sx, sy, radius, border="clamp"):
+    """search_valid over block_cost_masked -> (dx, dy int32 [Hb, Wb], searched bool [Hb, Wb]): the minimum pack_key_wide key over
+    the valid candidates; a block whose start candidate is not valid is not searched and keeps its start."""
+    never = np.int64(1) << 62
+    best = None
+    for ddy in range(-radius, radius + 1):
+        for ddx in range(-radius, radius + 1):
+            dx, dy = sx + ddx, sy + ddy
+            cost, ok, _ = block_cost_masked(ya, yb, ma, mb, dx, dy, border)
+            key = np.where(ok, pack_key_wide(np.where(ok, cost, 0), np.where(ok, dx, 0), np.where(ok, dy, 0)), never)
+            best = key if best is None else np.minimum(best, key)
+    searched = block_cost_masked(ya, yb, ma, mb, sx, sy, border)[1]
+    _, wx, wy = unpack_key_wide(np.where(searched, best, 0))
+    return np.where(searched, wx, sx).astype(np.int32), np.where(searched, wy, sy).astype(np.int32), searched
+
+
+def fill_unsearched(dx, dy, searched, radius=FILL_RADIUS):
+    """The top level's fill: a block that was not searched takes the vector of the searched block within Chebyshev distance
+    `radius` that minimises (max(|Dy|, |Dx|), |Dy| + |Dx|, Dy, Dx), D = source - block; none: (0, 0).  Searched blocks keep
+    theirs.  Only the INPUT's searched blocks are sources."""
+    Hb, Wb = searched.shape
+    ox, oy = np.where(searched, dx, 0).astype(np.int32), np.where(searched, dy, 0).astype(np.int32)
+    for by, bx in zip(*np.nonzero(~searched)):
+        best = None
+        for sy in range(max(by - radius, 0), min(by + radius, Hb - 1) + 1):
+            for sx in range(max(bx - radius, 0), min(bx + radius, Wb - 1) + 1):
+                if searched[sy, sx]:
+                    ddy, ddx = int(sy - by), int(sx - bx)
+                    key = (max(abs(ddy), abs(ddx)), abs(ddy) + abs(ddx), ddy, ddx)
+                    if best is None or key < best:
+                        best = key
+        if best is not None:
+            ox[by, bx], oy[by, bx] = dx[by + best[2], bx + best[3]], dy[by + best[2], bx + best[3]]
+    return ox, oy
+
+
+def block_field_levels_masked(a_u8, b_u8, ma, mb, levels=LEVELS, border="clamp"):
+    """block_field_levels with the excluded pixels left out: [(dx, dy, searched)] coarse to fine, before the median; the top
+    level's (dx, dy) are those after the fill (what the level below starts from), `searched` the flags before it."""
+    levels = check_levels(levels, "block_field_levels_masked")
+    check_border(border, "block_field_levels_masked")
+    pa, pb = pyramid(luma(a_u8), levels), pyramid(luma(b_u8), levels)
+    qa, qb = mask_pyramid(ma, levels), mask_pyramid(mb, levels)
+    out = []
+    dx = dy = None
+    for lvl in range(levels - 1, -1, -1):
+        Hb, Wb = field_shape(*pa[lvl].shape)
+        if dx is None:
+            sx = sy = np.zeros((Hb, Wb), np.int32)
+            dx, dy, searched = search_masked(pa[lvl], pb[lvl], qa[lvl], qb[lvl], sx, sy, SEARCH_TOP, border)
+            dx, dy = fill_unsearched(dx, dy, searched)
+        else:
+            by, bx = np.arange(Hb) >> 1, np.arange(Wb) >> 1
+            sx, sy = 2 * dx[by][:, bx], 2 * dy[by][:, bx]
+            dx, dy, searched = search_masked(pa[lvl], pb[lvl], qa[lvl], qb[lvl], sx, sy, REFINE, border)
+        out.append((dx, dy, searched))
+    return out
+
+
+def mci_field_masked_host(a_u8, b_u8, ma, mb, levels=LEVELS, border="clamp"):
+    """mci_field_host with the person kept out of the matching: ma, mb uint8 [H, W], nonzero = excluded, for key frame A and B
+    (the module text's "person" paragraph) -> int16 [Hb, Wb, 2]."""
+    levels = check_levels(levels, "mci_field_masked_host")
+    check_border(border, "mci_field_masked_host")
+    a_u8, b_u8 = np.asarray(a_u8), np.asarray(b_u8)
+    if a_u8.dtype != np.uint8 or a_u8.ndim != 3 or a_u8.shape[2] != 3 or a_u8.shape != b_u8.shape or b_u8.dtype != np.uint8:
+        raise ValueError("mci_field_masked_host: two uint8 [H, W, 3] frames of one size, got %s %s and %s %s"
+                         % (a_u8.dtype, a_u8.shape, b_u8.dtype, b_u8.shape))
+    ma, mb = check_masks(ma, mb, a_u8.shape[0], a_u8.shape[1], "mci_field_masked_host")
+    dx, dy, _ = block_field_levels_masked(a_u8, b_u8, ma, mb, levels, border)[-1]
+    return np.stack([median3(dx), median3(dy)], -1).astype(np.int16)
+
+
+def sample_clean(mask, py, px):
+    """bool [H, W]: the positions (1/256 px) whose four bilinear taps in `mask` (bool [H, W], set = excluded; coordinates
+    clamped as sample_bilinear clamps them) are all clear."""
+    h, w = mask.shape
+    y0, x0 = py >> SAMPLE_FRAC_BITS, px >> SAMPLE_FRAC_BITS
+    y1, y0 = np.clip(y0 + 1, 0, h - 1), np.clip(y0, 0, h - 1)
+    x1, x0 = np.clip(x0 + 1, 0, w - 1), np.clip(x0, 0, w - 1)
+    return ~(mask[y0, x0] | mask[y0, x1] | mask[y1, x0] | mask[y1, x1])
+
+
+def mci_frames_masked_host(a_u8, b_u8, ma, mb, field, sample_rate, ks, border="clamp", precision="full"):
+    """mci_frames_host with the person kept out: a sample is clean iff the border rule calls it valid (clamp: always) and
+    sample_clean holds in its key frame's mask; where exactly one of a pixel's two samples is clean the output is that sample
+    alone, otherwise the blend.  k = 0 and k = sample_rate stay A and B.  -> uint8 [len(ks), H, W, 3]."""
+    check_border(border, "mci_frames_masked_host")
+    unit = 1 if check_precision(precision, "mci_frames_masked_host") == "half" else 2
+    a_u8, b_u8, field = np.asarray(a_u8), np.asarray(b_u8), np.asarray(field)
+    if a_u8.dtype != np.uint8 or a_u8.ndim != 3 or a_u8.shape[2] != 3 or a_u8.shape != b_u8.shape or b_u8.dtype != np.uint8:
+        raise ValueError("mci_frames_masked_host: two uint8 [H, W, 3] frames of one size, got %s and %s" % (a_u8.shape, b_u8.shape))
+    s, ls = int(sample_rate), log2_rate(sample_rate)
+    H, W = a_u8.shape[:2]
+    ma, mb = check_masks(ma, mb, H, W, "mci_frames_masked_host")
+    Dx, Dy = pixel_field(field, H, W)
+    Y, X = np.mgrid[0:H, 0:W]
+    Y, X = (Y << SAMPLE_FRAC_BITS).astype(np.int32), (X << SAMPLE_FRAC_BITS).astype(np.int32)
+    out = np.empty((len(ks), H, W, 3), np.uint8)
+    for j, k in enumerate(ks):
+        k = int(k)
+        if not 0 <= k <= s:
+            raise ValueError("mci_frames_masked_host: frame %d is outside the segment 0..%d" % (k, s))
+        ax, ay = (unit * k * Dx + s // 2) >> ls, (unit * k * Dy + s // 2) >> ls
+        bx, by = (unit * (s - k) * Dx + s // 2) >> ls, (unit * (s - k) * Dy + s // 2) >> ls
+        a = sample_bilinear(a_u8, Y - ay, X - ax)
+        b = sample_bilinear(b_u8, Y + by, X + bx)
+        o = ((s - k) * a + k * b + s // 2) >> ls
+        oka, okb = sample_clean(ma, Y - ay, X - ax), sample_clean(mb, Y + by, X + bx)
+        if border == "valid":
+            oka, okb = oka & sample_valid(Y - ay, X - ax, H, W), okb & sample_valid(Y + by, X + bx, H, W)
+        oka, okb = oka[..., None], okb[..., None]
+        o = np.where(oka == okb, o, np.where(oka, a, b))
+        if k == 0 or k == s:                # the key frames themselves, whatever their masks
+            o = a if k == 0 else b
         out[j] = o.astype(np.uint8)
     return out
 

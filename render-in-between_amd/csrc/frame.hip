@@ -520,6 +520,94 @@ int rib_mci_field(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, 
   return RIB_OK;
 }
 
+// rib_masked_*: rib_mci_field's workspace, then the mask planes of the levels, the searched flags (one plane, level 0's size: a
+// level's flags are read - by the fill, on the top level only - before the next level writes its own) and the top level's field
+// before the fill
+namespace {
+struct MaskedLayout { MciLayout L; size_t m[MCI_MAX_LEVELS], flags, raw, total; };
+static bool masked_layout(int B, int H, int W, int levels, MaskedLayout* M) {
+  if (!mci_layout(B, H, W, levels, &M->L)) return false;
+  const MciLayout& L = M->L;
+  size_t o = L.total;
+  for (int l = 0; l < levels; ++l) { M->m[l] = o; o += align256((size_t)2 * B * L.h[l] * L.w[l]); }
+  M->flags = o; o += align256((size_t)B * L.Hb[0] * L.Wb[0]);
+  M->raw = o; o += align256((size_t)B * L.Hb[levels - 1] * L.Wb[levels - 1] * 2 * sizeof(int16_t));
+  M->total = o;
+  return true;
+}
+}  // namespace
+
+size_t rib_masked_workspace_bytes(rib_handle* h, int B, int H, int W, int levels) {
+  MaskedLayout M;
+  if (!h || !masked_layout(B, H, W, levels, &M)) return 0;
+  return M.total;
+}
+
+int rib_masked_field(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const uint8_t* ma_u8,
+                     const uint8_t* mb_u8, int16_t* field_i16, int levels, int border, void* workspace, void* hip_stream) {
+  FrameState* h = frame_state(handle);
+  if (!h) return RIB_ERR_INVALID;
+  if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_masked_field: host-only handle");
+  if (!a_u8 || !b_u8 || !ma_u8 || !mb_u8 || !field_i16 || !workspace) return fail(h, RIB_ERR_INVALID, "rib_masked_field: null pointer");
+  if (levels < MCI_MIN_LEVELS || levels > MCI_MAX_LEVELS)
+    return fail(h, RIB_ERR_INVALID, fmt("rib_masked_field: levels=%d: %d..%d pyramid levels (a search over 32, 64 or 128 px)", levels, MCI_MIN_LEVELS, MCI_MAX_LEVELS));
+  if (border != 0 && border != 1)
+    return fail(h, RIB_ERR_INVALID, fmt("rib_masked_field: border=%d: 0 (clamped samples) or 1 (valid samples only)", border));
+  MaskedLayout M;
+  if (!masked_layout(B, H, W, levels, &M))
+    return fail(h, RIB_ERR_INVALID, fmt("rib_masked_field: B=%d H=%d W=%d: 1 <= B <= 32767, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", B, H, W, MCI_MAX_SIDE));
+  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0 || (reinterpret_cast<uintptr_t>(field_i16) & 3) != 0)
+    return fail(h, RIB_ERR_INVALID, "rib_masked_field: workspace must be 16-byte aligned, the field 4-byte aligned");
+  const MciLayout& L = M.L;
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  uint8_t* ws = static_cast<uint8_t*>(workspace);
+  MciLumaParams lp;
+  lp.a = a_u8; lp.b = b_u8; lp.y0 = ws + L.y[0]; lp.y1 = ws + L.y[1]; lp.y2 = ws + L.y[2];
+  lp.y3 = levels > 3 ? ws + L.y[3] : nullptr; lp.y4 = levels > 4 ? ws + L.y[4] : nullptr;
+  lp.B = B; lp.H = H; lp.W = W; lp.h1 = L.h[1]; lp.w1 = L.w[1]; lp.h2 = L.h[2]; lp.w2 = L.w[2]; lp.tilesX = (W + 31) / 32;
+  lp.h3 = levels > 3 ? L.h[3] : 0; lp.w3 = levels > 3 ? L.w[3] : 0; lp.h4 = levels > 4 ? L.h[4] : 0; lp.w4 = levels > 4 ? L.w[4] : 0;
+  const dim3 tiles(lp.tilesX * ((H + 31) / 32), 2 * B);
+  hipLaunchKernelGGL(k_mci_luma_pyramid, tiles, dim3(256), 0, st, lp);
+  HIP_TRY(h, hipGetLastError());
+  MciMaskParams mp;
+  mp.ma = ma_u8; mp.mb = mb_u8; mp.B = B; mp.levels = levels; mp.tilesX = lp.tilesX;
+  for (int l = 0; l < MCI_MAX_LEVELS; ++l) {
+    mp.m[l] = l < levels ? ws + M.m[l] : nullptr; mp.h[l] = l < levels ? L.h[l] : 0; mp.w[l] = l < levels ? L.w[l] : 0;
+  }
+  hipLaunchKernelGGL(k_mci_mask_pyramid, tiles, dim3(256), 0, st, mp);
+  HIP_TRY(h, hipGetLastError());
+  const int top = levels - 1;
+  for (int l = top; l >= 0; --l) {
+    MciSearchParams sp;
+    sp.y = ws + L.y[l]; sp.coarse = l == top ? nullptr : reinterpret_cast<const int16_t*>(ws + L.f[l + 1]);
+    sp.out = reinterpret_cast<int16_t*>(ws + (l == top ? M.raw : L.f[l]));
+    sp.B = B; sp.h = L.h[l]; sp.w = L.w[l]; sp.Hb = L.Hb[l]; sp.Wb = L.Wb[l];
+    sp.Hbc = l == top ? 1 : L.Hb[l + 1]; sp.Wbc = l == top ? 1 : L.Wb[l + 1];
+    sp.m = ws + M.m[l]; sp.searched = ws + M.flags;
+    const dim3 grid((sp.Hb * sp.Wb + MCI_RUN - 1) / MCI_RUN, B);
+    if (border) {
+      if (l == top) hipLaunchKernelGGL((k_mci_search<MCI_TOP_R, true, true>), grid, dim3(256), 0, st, sp);
+      else hipLaunchKernelGGL((k_mci_search<1, true, true>), grid, dim3(256), 0, st, sp);
+    } else {
+      if (l == top) hipLaunchKernelGGL((k_mci_search<MCI_TOP_R, false, true>), grid, dim3(256), 0, st, sp);
+      else hipLaunchKernelGGL((k_mci_search<1, false, true>), grid, dim3(256), 0, st, sp);
+    }
+    HIP_TRY(h, hipGetLastError());
+    if (l == top) {                         // the fill reads the raw field and the flags, and writes the field the level below starts from
+      const int nt = B * sp.Hb * sp.Wb;
+      hipLaunchKernelGGL(k_mci_fill, dim3(std::min((nt + 255) / 256, 1024)), dim3(256), 0, st, reinterpret_cast<const int16_t*>(ws + M.raw),
+                         static_cast<const uint8_t*>(ws + M.flags), reinterpret_cast<int16_t*>(ws + L.f[top]), B, sp.Hb, sp.Wb);
+      HIP_TRY(h, hipGetLastError());
+    }
+  }
+  const int n = B * L.Hb[0] * L.Wb[0];
+  hipLaunchKernelGGL(k_mci_median, dim3(std::min((n + 255) / 256, 1024)), dim3(256), 0, st,
+                     reinterpret_cast<const int16_t*>(ws + L.f[0]), field_i16, B, L.Hb[0], L.Wb[0]);
+  HIP_TRY(h, hipGetLastError());
+  return RIB_OK;
+}
+
 int rib_halfpel_refine(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const int16_t* field_i16,
                    int16_t* field_half_i16, int border, void* hip_stream) {
   FrameState* h = frame_state(handle);
@@ -546,13 +634,14 @@ int rib_halfpel_refine(rib_handle* handle, int B, int H, int W, const uint8_t* a
 }
 
 // rib_mci_frames / rib_halfpel_frames: one body, one kernel template; half: the field is rib_halfpel_refine's, in half pixels
+// rib_masked_frames: the same body again; masked: ma_u8, mb_u8 are wanted, and the kernel is <.., MASKED = true>
 static int mci_frames_enqueue(const char* who, bool half, rib_handle* handle, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8,
                               const int16_t* field_i16, int sample_rate, int k_first, int border, float* out_f32_nchw, uint8_t* out_u8_nhwc,
-                              void* hip_stream) {
+                              void* hip_stream, bool masked = false, const uint8_t* ma_u8 = nullptr, const uint8_t* mb_u8 = nullptr) {
   FrameState* h = frame_state(handle);
   if (!h) return RIB_ERR_INVALID;
   if (h->device < 0) return fail(h, RIB_ERR_INVALID, fmt("%s: host-only handle", who));
-  if (!a_u8 || !b_u8 || !field_i16) return fail(h, RIB_ERR_INVALID, fmt("%s: null pointer", who));
+  if (!a_u8 || !b_u8 || !field_i16 || (masked && (!ma_u8 || !mb_u8))) return fail(h, RIB_ERR_INVALID, fmt("%s: null pointer", who));
   if (!out_f32_nchw && !out_u8_nhwc) return fail(h, RIB_ERR_INVALID, fmt("%s: both outputs are null", who));
   MciLayout L;
   if (T < 1 || !mci_layout(B, H, W, MCI_MIN_LEVELS, &L) || (size_t)T * B > 65535)
@@ -571,11 +660,20 @@ static int mci_frames_enqueue(const char* who, bool half, rib_handle* handle, in
   fp.ls = 0;
   while ((1 << fp.ls) < sample_rate) ++fp.ls;
   fp.vec = (W % 4 == 0 && (reinterpret_cast<uintptr_t>(out_f32_nchw) & 15) == 0 && (reinterpret_cast<uintptr_t>(out_u8_nhwc) & 3) == 0) ? 1 : 0;
+  fp.ma = ma_u8; fp.mb = mb_u8;
   HIP_TRY(h, hipSetDevice(h->device));
   const size_t lds = out_u8_nhwc ? (size_t)W * 3 + 32 : 0;
   const dim3 grid(H, T * B);
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  if (half) {
+  if (masked) {
+    if (half) {
+      if (border) hipLaunchKernelGGL((k_mci_frames<true, true, true>), grid, dim3(256), lds, st, fp);
+      else hipLaunchKernelGGL((k_mci_frames<false, true, true>), grid, dim3(256), lds, st, fp);
+    } else {
+      if (border) hipLaunchKernelGGL((k_mci_frames<true, false, true>), grid, dim3(256), lds, st, fp);
+      else hipLaunchKernelGGL((k_mci_frames<false, false, true>), grid, dim3(256), lds, st, fp);
+    }
+  } else if (half) {
     if (border) hipLaunchKernelGGL((k_mci_frames<true, true>), grid, dim3(256), lds, st, fp);
     else hipLaunchKernelGGL((k_mci_frames<false, true>), grid, dim3(256), lds, st, fp);
   } else {
@@ -596,6 +694,17 @@ int rib_halfpel_frames(rib_handle* handle, int T, int B, int H, int W, const uin
                         int sample_rate, int k_first, int border, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream) {
   return mci_frames_enqueue("rib_halfpel_frames", true, handle, T, B, H, W, a_u8, b_u8, field_half_i16, sample_rate, k_first, border,
                             out_f32_nchw, out_u8_nhwc, hip_stream);
+}
+
+int rib_masked_frames(rib_handle* handle, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const uint8_t* ma_u8,
+                      const uint8_t* mb_u8, const int16_t* field_i16, int sample_rate, int k_first, int border, int precision,
+                      float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream) {
+  if (precision != 0 && precision != 1) {
+    FrameState* h = frame_state(handle);
+    return h ? fail(h, RIB_ERR_INVALID, fmt("rib_masked_frames: precision=%d: 0 (the field in whole pixels) or 1 (in half pixels)", precision)) : RIB_ERR_INVALID;
+  }
+  return mci_frames_enqueue("rib_masked_frames", precision == 1, handle, T, B, H, W, a_u8, b_u8, field_i16, sample_rate, k_first, border,
+                            out_f32_nchw, out_u8_nhwc, hip_stream, true, ma_u8, mb_u8);
 }
 
 // rib_scaled_frames: rib_mci_frames' uint8 output at the key frames' own size H0 x W0 from the MODEL-size (H x W) field

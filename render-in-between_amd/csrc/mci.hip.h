@@ -1,6 +1,6 @@
 // mci.hip.h — motion-compensated interpolation of a segment's two key frames: the folder driver's background="mci"
-// (rib_mci_field / rib_halfpel_refine / rib_mci_frames / rib_halfpel_frames, and rib_scaled_frames for output_size="keyframes";
-// include/rib.h).  This project's interpolation, not DAIN.
+// (rib_mci_field / rib_halfpel_refine / rib_mci_frames / rib_halfpel_frames, rib_scaled_frames for output_size="keyframes", and
+// rib_masked_field / rib_masked_frames for mci_person="exclude"; include/rib.h).  This project's interpolation, not DAIN.
 //
 // background.py (mci_field_host, mci_refine_host, mci_frames_host, mci_frames_scaled_host) states the result in integers; every kernel
 // here is bit-equal to it.
@@ -56,6 +56,25 @@
 //                       division per thread, its three further x by adding.  The two 64-bit products D8 * SX, D8 * SY (16.16 factors
 //                       from the host) are the only wide arithmetic.  uint8 NHWC output only, through LDS as 16-byte stores like
 //                       k_mci_frames.  stage = 0 (row + field rows beyond 64 KB of LDS: both widths above 16 376): V from global.
+//
+// The person kept out (rib_masked_field / rib_masked_frames; background.mci_field_masked_host / mci_frames_masked_host): new
+// instantiations beside the ones above, which stay the instruction streams they were (every masked line sits under
+// `if constexpr (MASKED)`; the parameter structs only grew at their ends).
+//   k_mci_mask_pyramid  k_mci_luma_pyramid's grid and tiling over the two exclusion masks [B, H, W]: level 0 as 0 / 1 and every
+//                       further level as the OR of the 2x2 clamped parents, level by level through two LDS planes.
+//   k_mci_search<R, VALID, MASKED = true>  the two mask windows are staged beside the two luma windows (R = 4: 4 KB more per
+//                       workgroup, 8.1 KB in all); a pixel counts when the border rule lets it and both mask bytes at the candidate's
+//                       offsets are clear - one more term in the select inside the default's uniform loops, and a count n beside
+//                       the SAD, summed over the row lanes of R = 1 by the same shuffles; cost = 64 * SAD / n + LAMBDA's term for
+//                       either border.  The start candidate's n is one ballot (lane i takes the block's pixel i): 4 n < N is
+//                       uniform per wave, the block stores its start and searched = 0 and the shuffles are reached by no lane.
+//   k_mci_fill          the top level only, one thread per block: a block with searched = 0 takes the vector of the searched block
+//                       within Chebyshev distance 8 that minimises (ring, |Dy| + |Dx|, Dy, Dx), ring by ring, or (0, 0).  It reads
+//                       the raw field and the flags and writes ANOTHER buffer (the field the level below starts from): no thread
+//                       reads what another writes, and the result does not depend on the order.
+//   k_mci_frames<VALID, HALF, MASKED = true>  four byte gathers per sample in its key frame's mask (mci_sample's clamps) and one
+//                       more term in VALID's select: clean = valid under the border rule and all four taps clear; k = 0 and k = s
+//                       stay A and B.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -136,11 +155,52 @@ __global__ __launch_bounds__(256) void k_mci_luma_pyramid(MciLumaParams p) {
   }
 }
 
+// rib_masked_field: the OR pyramid of the two exclusion masks, k_mci_luma_pyramid's tiling with "any parent set" in place of the
+// rounded mean (background.mask_pyramid).  Level 0 is stored as 0 / 1, so every reader tests one byte.
+struct MciMaskParams {
+  const uint8_t *ma, *mb;                   // [B, H, W], nonzero = excluded
+  uint8_t* m[MCI_MAX_LEVELS];               // [2B, h_l, w_l] 0 / 1; levels beyond `levels` are not touched
+  int h[MCI_MAX_LEVELS], w[MCI_MAX_LEVELS];
+  int B, levels, tilesX;
+};
+
+__global__ __launch_bounds__(256) void k_mci_mask_pyramid(MciMaskParams p) {
+  __shared__ uint8_t s[2][32][32];          // level l of the tile in s[l & 1], side 32 >> l
+  const int tid = threadIdx.x, n = blockIdx.y;
+  const int ty = blockIdx.x / p.tilesX, tx = blockIdx.x - ty * p.tilesX;
+  const int H = p.h[0], W = p.w[0];
+  const uint8_t* src = (n < p.B ? p.ma + (size_t)n * H * W : p.mb + (size_t)(n - p.B) * H * W);
+  for (int i = tid; i < 1024; i += 256) {
+    const int ly = i >> 5, lx = i & 31, y = ty * 32 + ly, x = tx * 32 + lx;
+    if (y < H && x < W) {
+      const uint8_t v = src[(size_t)y * W + x] != 0;
+      s[0][ly][lx] = v;
+      p.m[0][((size_t)n * H + y) * W + x] = v;
+    }
+  }
+  for (int l = 1; l < p.levels; ++l) {      // (uniform: every thread reaches every barrier)
+    __syncthreads();
+    const int side = 32 >> l, hl = p.h[l], wl = p.w[l], hp = p.h[l - 1], wp = p.w[l - 1];
+    for (int i = tid; i < side * side; i += 256) {
+      const int ly = i / side, lx = i - ly * side, y = ty * side + ly, x = tx * side + lx;
+      if (y < hl && x < wl) {               // aligned tiles nest: a clamped parent is the tile's own
+        const int r0 = 2 * ly, r1 = min(2 * y + 1, hp - 1) - ty * 2 * side, c0 = 2 * lx, c1 = min(2 * x + 1, wp - 1) - tx * 2 * side;
+        const uint8_t(*sp)[32] = s[(l - 1) & 1];
+        const uint8_t v = sp[r0][c0] | sp[r0][c1] | sp[r1][c0] | sp[r1][c1];
+        s[l & 1][ly][lx] = v;
+        p.m[l][((size_t)n * hl + y) * wl + x] = v;
+      }
+    }
+  }
+}
+
 struct MciSearchParams {
   const uint8_t* y;                         // [2B, h, w]: A[b] at b, B[b] at B + b
   const int16_t* coarse;                    // [B, Hbc, Wbc, 2] (dx, dy) of the coarser level, or null (start = 0)
   int16_t* out;                             // [B, Hb, Wb, 2]
   int B, h, w, Hb, Wb, Hbc, Wbc;
+  const uint8_t* m;                         // <.., MASKED = true> only: [2B, h, w] 0 / 1, the level's plane of k_mci_mask_pyramid
+  uint8_t* searched;                        // <.., MASKED = true> only: [B, Hb, Wb], 1 = the block's start was valid and it was searched
 };
 
 // border = 1: the pixels of the block rows / columns [o, o + len) whose p - d and p + d lie in [0, size): [lo, hi) relative to o
@@ -150,12 +210,17 @@ __device__ inline void mci_valid_span(int o, int len, int d, int size, int& lo, 
   hi = max(min(len, size - ad - o), lo);
 }
 
-template <int R, bool VALID = false>
+template <int R, bool VALID = false, bool MASKED = false>
 __global__ __launch_bounds__(256) void k_mci_search(MciSearchParams p) {
   constexpr int WS = MCI_BLOCK + 2 * R, WIN = WS * WS, SIDE = 2 * R + 1, NC = SIDE * SIDE;
   constexpr int PARTS = (NC * 4 <= 64) ? 4 : 1, ROWS = MCI_BLOCK / PARTS;
   __shared__ uint8_t s_win[MCI_RUN][2][WIN];
   __shared__ int s_start[MCI_RUN][2];
+  uint8_t(*s_msk)[2][WIN] = nullptr;        // MASKED: the two mask windows beside the two luma windows (R = 4: 4 KB more, 8.1 KB in all)
+  if constexpr (MASKED) {
+    __shared__ uint8_t s_mwin[MCI_RUN][2][WIN];
+    s_msk = s_mwin;
+  }
   const int tid = threadIdx.x, b = blockIdx.y;
   const int nblk = p.Hb * p.Wb, blk0 = blockIdx.x * MCI_RUN;
   if (tid < MCI_RUN) {
@@ -177,6 +242,7 @@ __global__ __launch_bounds__(256) void k_mci_search(MciSearchParams p) {
       const int y = min(max(MCI_BLOCK * by + sgn * s_start[j][1] - R + wy, 0), p.h - 1);
       const int x = min(max(MCI_BLOCK * bx + sgn * s_start[j][0] - R + wx, 0), p.w - 1);
       s_win[j][which][e] = p.y[((size_t)(which ? p.B + b : b) * p.h + y) * p.w + x];
+      if constexpr (MASKED) s_msk[j][which][e] = p.m[((size_t)(which ? p.B + b : b) * p.h + y) * p.w + x];
     }
   }
   __syncthreads();
@@ -189,7 +255,27 @@ __global__ __launch_bounds__(256) void k_mci_search(MciSearchParams p) {
     const int sx = s_start[j][0], sy = s_start[j][1];
     const uint8_t *wa = s_win[j][0], *wb = s_win[j][1];
     unsigned long long best = ~0ull;
-    if constexpr (VALID) {                  // the start candidate itself has too few valid pixels: nothing to search
+    if constexpr (MASKED) {                 // the start candidate: lane i takes the block's pixel i, the count is a ballot
+      const uint8_t *qa = s_msk[j][0], *qb = s_msk[j][1];
+      const int r = lane >> 3, x = lane & 7;
+      bool ok = r < ph && x < pw && !(qa[(r + R) * WS + R + x] | qb[(r + R) * WS + R + x]);
+      if constexpr (VALID) {
+        int xl, xh, yl, yh;
+        mci_valid_span(MCI_BLOCK * bx, pw, sx, p.w, xl, xh);
+        mci_valid_span(MCI_BLOCK * by, ph, sy, p.h, yl, yh);
+        ok = ok && r >= yl && r < yh && x >= xl && x < xh;
+      }
+      const int n0 = __popcll(__ballot(ok));
+      const bool go = 4 * n0 >= pw * ph;    // (uniform per wave: the shuffles below are reached by all lanes or by none)
+      if (lane == 0) p.searched[(size_t)b * nblk + blk] = go;
+      if (!go) {
+        if (lane == 0) {
+          int16_t* o = p.out + ((size_t)b * nblk + blk) * 2;
+          o[0] = (int16_t)sx; o[1] = (int16_t)sy;
+        }
+        continue;
+      }
+    } else if constexpr (VALID) {           // the start candidate itself has too few valid pixels: nothing to search
       int xl, xh, yl, yh;
       mci_valid_span(MCI_BLOCK * bx, pw, sx, p.w, xl, xh);
       mci_valid_span(MCI_BLOCK * by, ph, sy, p.h, yl, yh);
@@ -211,21 +297,36 @@ __global__ __launch_bounds__(256) void k_mci_search(MciSearchParams p) {
         mci_valid_span(MCI_BLOCK * bx, pw, sx + ddx, p.w, xl, xh);
         mci_valid_span(MCI_BLOCK * by, ph, sy + ddy, p.h, yl, yh);
       }
-      const int n = (xh - xl) * (yh - yl);
+      int n = (xh - xl) * (yh - yl);          // MASKED: counted below
+      if constexpr (MASKED) n = 0;
       for (int r = part * ROWS; r < (part + 1) * ROWS; ++r) {
         if (r < ph) {
           const uint8_t* ra = wa + (r - ddy + R) * WS + (R - ddx);
           const uint8_t* rb = wb + (r + ddy + R) * WS + (R + ddx);
-          for (int x = 0; x < pw; ++x) {
-            if constexpr (VALID) sad += (r >= yl && r < yh && x >= xl && x < xh) ? abs((int)ra[x] - (int)rb[x]) : 0;
-            else sad += abs((int)ra[x] - (int)rb[x]);
+          if constexpr (MASKED) {             // the same offsets in the mask windows; one more term in the select, and a count
+            const uint8_t* ka = s_msk[j][0] + (r - ddy + R) * WS + (R - ddx);
+            const uint8_t* kb = s_msk[j][1] + (r + ddy + R) * WS + (R + ddx);
+            for (int x = 0; x < pw; ++x) {
+              const bool ok = !(ka[x] | kb[x]) && (!VALID || (r >= yl && r < yh && x >= xl && x < xh));
+              sad += ok ? abs((int)ra[x] - (int)rb[x]) : 0;
+              n += ok;
+            }
+          } else {
+            for (int x = 0; x < pw; ++x) {
+              if constexpr (VALID) sad += (r >= yl && r < yh && x >= xl && x < xh) ? abs((int)ra[x] - (int)rb[x]) : 0;
+              else sad += abs((int)ra[x] - (int)rb[x]);
+            }
           }
         }
       }
 #pragma unroll
       for (int m = 1; m < PARTS; m <<= 1) sad += __shfl_xor(sad, m);
-      if constexpr (VALID) sad = (64 * sad) / max(n, 1);      // (n = 0: not a candidate, below)
-      const bool counts = VALID ? active && 4 * n >= pw * ph : active;
+      if constexpr (MASKED) {
+#pragma unroll
+        for (int m = 1; m < PARTS; m <<= 1) n += __shfl_xor(n, m);
+      }
+      if constexpr (VALID || MASKED) sad = (64 * sad) / max(n, 1);      // (n = 0: not a candidate, below)
+      const bool counts = (VALID || MASKED) ? active && 4 * n >= pw * ph : active;
       const int dx = sx + ddx, dy = sy + ddy;
       const unsigned long long key = ((unsigned long long)(sad + MCI_LAMBDA * (abs(dx) + abs(dy))) << 30) |
                                      ((unsigned long long)(dx * dx + dy * dy) << 16) |
@@ -380,6 +481,41 @@ __global__ __launch_bounds__(256) void k_mci_median(const int16_t* __restrict__ 
   }
 }
 
+// rib_masked_field, the top level only (background.fill_unsearched): a block that was not searched takes the vector of the searched
+// block within Chebyshev distance MCI_FILL_RADIUS that minimises (max(|Dy|, |Dx|), |Dy| + |Dx|, Dy, Dx), or (0, 0).  One thread per
+// block, rings outwards; `in` and `out` are different buffers, so no thread reads what another writes.
+constexpr int MCI_FILL_RADIUS = 8;          // background.py FILL_RADIUS
+
+__global__ __launch_bounds__(256) void k_mci_fill(const int16_t* __restrict__ in, const uint8_t* __restrict__ searched, int16_t* __restrict__ out,
+                                                  int B, int Hb, int Wb) {
+  const int nblk = Hb * Wb;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < B * nblk; i += gridDim.x * 256) {
+    const int b = i / nblk, blk = i - b * nblk, by = blk / Wb, bx = blk - by * Wb;
+    const uint8_t* flg = searched + (size_t)b * nblk;
+    int src = -1;
+    if (flg[blk]) src = blk;
+    for (int c = 1; c <= MCI_FILL_RADIUS && src < 0; ++c) {      // ring c: the first key component; the rest by the packed minimum
+      int best = INT32_MAX;
+      for (int dy = -c; dy <= c; ++dy) {
+        const int y = by + dy;
+        if (y < 0 || y >= Hb) continue;
+        const int step = (dy == -c || dy == c) ? 1 : 2 * c;      // the ring's top and bottom rows are whole, the others their two ends
+        for (int dx = -c; dx <= c; dx += step) {
+          const int x = bx + dx;
+          if (x < 0 || x >= Wb || !flg[y * Wb + x]) continue;
+          const int key = ((abs(dy) + abs(dx)) << 12) | ((dy + 32) << 6) | (dx + 32);
+          best = min(best, key);
+        }
+      }
+      if (best != INT32_MAX) src = (by + ((best >> 6) & 63) - 32) * Wb + bx + (best & 63) - 32;
+    }
+    int vx = 0, vy = 0;
+    if (src >= 0) { const int16_t* v = in + ((size_t)b * nblk + src) * 2; vx = v[0]; vy = v[1]; }
+    out[(size_t)i * 2] = (int16_t)vx;
+    out[(size_t)i * 2 + 1] = (int16_t)vy;
+  }
+}
+
 struct MciFramesParams {
   const uint8_t *a, *b;                     // [B, H, W, 3]
   const int16_t* field;                     // [B, Hb, Wb, 2]
@@ -387,7 +523,16 @@ struct MciFramesParams {
   uint8_t* out_u8;                          // [T, B, H, W, 3] or null
   int T, B, H, W, Hb, Wb, s, ls, k_first;
   int vec;                                  // W % 4 == 0 and the outputs are aligned: float4 stores, dword LDS writes
+  const uint8_t *ma, *mb;                   // <.., MASKED = true> only: [B, H, W], nonzero = excluded
 };
+
+// MASKED: the four taps of a sample's bilinear footprint in its key frame's mask are all clear (background.sample_clean;
+// mci_sample's clamps)
+__device__ inline bool mci_clean(const uint8_t* m, int H, int W, int py, int px) {
+  const int y0 = min(max(py >> 8, 0), H - 1), y1 = min(max((py >> 8) + 1, 0), H - 1);
+  const int x0 = min(max(px >> 8, 0), W - 1), x1 = min(max((px >> 8) + 1, 0), W - 1);
+  return !(m[(size_t)y0 * W + x0] | m[(size_t)y0 * W + x1] | m[(size_t)y1 * W + x0] | m[(size_t)y1 * W + x1]);
+}
 
 // one bilinear sample of an RGB frame at (py, px) in 1/256 px, edge clamp (background.sample_bilinear)
 __device__ inline void mci_sample(const uint8_t* img, int H, int W, int py, int px, int v[3]) {
@@ -401,7 +546,7 @@ __device__ inline void mci_sample(const uint8_t* img, int H, int W, int py, int 
     v[c] = ((256 - fy) * ((256 - fx) * p00[c] + fx * p01[c]) + fy * ((256 - fx) * p10[c] + fx * p11[c]) + (1 << 15)) >> 16;
 }
 
-template <bool VALID = false, bool HALF = false>
+template <bool VALID = false, bool HALF = false, bool MASKED = false>
 __global__ __launch_bounds__(256) void k_mci_frames(MciFramesParams p) {
   constexpr int UNIT = HALF ? 1 : 2;        // the field's unit in half pixels: the motion between the key frames is UNIT * D
   extern __shared__ __attribute__((aligned(16))) uint8_t s_mci[];
@@ -435,7 +580,22 @@ __global__ __launch_bounds__(256) void k_mci_frames(MciFramesParams p) {
       int va[3], vb[3];
       mci_sample(A, H, W, (y << 8) - ay, (x << 8) - ax, va);
       mci_sample(Bf, H, W, (y << 8) + by, (x << 8) + bx, vb);
-      if constexpr (VALID) {
+      if constexpr (MASKED) {                 // VALID's switch with one more condition; k = 0 and k = s stay A and B
+        const int pay = (y << 8) - ay, pax = (x << 8) - ax, pby = (y << 8) + by, pbx = (x << 8) + bx;
+        bool oka = mci_clean(p.ma + (size_t)bi * H * W, H, W, pay, pax), okb = mci_clean(p.mb + (size_t)bi * H * W, H, W, pby, pbx);
+        if constexpr (VALID) {
+          const int ymax = (H - 1) << 8, xmax = (W - 1) << 8;
+          oka = oka && pay >= 0 && pay <= ymax && pax >= 0 && pax <= xmax;
+          okb = okb && pby >= 0 && pby <= ymax && pbx >= 0 && pbx <= xmax;
+        }
+        if (k == 0) { oka = true; okb = false; }
+        if (k == s) { oka = false; okb = true; }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const int blend = ((s - k) * va[c] + k * vb[c] + (s >> 1)) >> ls;
+          q[j * 3 + c] = (uint8_t)(oka == okb ? blend : oka ? va[c] : vb[c]);
+        }
+      } else if constexpr (VALID) {
         const int pay = (y << 8) - ay, pax = (x << 8) - ax, pby = (y << 8) + by, pbx = (x << 8) + bx;
         const int ymax = (H - 1) << 8, xmax = (W - 1) << 8;
         const bool oka = pay >= 0 && pay <= ymax && pax >= 0 && pax <= xmax, okb = pby >= 0 && pby <= ymax && pbx >= 0 && pbx <= xmax;

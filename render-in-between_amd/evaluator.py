@@ -578,7 +578,7 @@ class Evaluator:
                              panels=False, panel_frames=False, panel_quality=90, panel_fps=30, panel_encode="host",
                              background="dain", mci_range=32, video=False, video_fps=30, video_quality=90, video_frames=False, frames="png",
                              poses="folder", key_pose_dir=None, upsample_rate=8, motion=None, save_poses=False, mci_border="clamp",
-                             mci_precision="full", output_size="model", png_on="host"):
+                             mci_precision="full", output_size="model", png_on="host", mci_person="keep"):
         """rank / world: this process's share of the independent units (default: the torch.distributed process
         group when one is initialised, else everything).  Returns the frames THIS rank wrote.
         The call is one `_FolderPipeline` (below): plan a clip -> decode -> upload -> render -> sink, pipelined over units
@@ -613,7 +613,15 @@ class Evaluator:
         room for a false match on periodic content.  mci_border="valid" (default "clamp"; a setting of background="mci") makes
         matching and sampling one-sided at the FRAME border (background.py's border="valid"): a strip that only one key frame
         shows is taken from that key frame alone, not blended with a smear of the other's edge; occlusion inside the frame (a
-        foreground object covering background) is not handled.  mci_precision="half" (default "full"; a setting of
+        foreground object covering background) is not handled unless the person is excluded: mci_person="exclude" (default
+        "keep"; a setting of background="mci") takes the human masks of a segment's two key frames' poses (rasterise.human_mask; on
+        the native path rib_human_mask on the upload stream, once per group where the field is made) as EXCLUDED pixels: they do
+        not count in the block matching (background.mci_field_masked_host; rib_masked_field), and where exactly one of a pixel's
+        two samples avoids them the background is that sample alone (mci_frames_masked_host; rib_masked_frames).  The mask is
+        the reference's coarse pose mask - hair, loose clothing and carried objects outside it still ghost; there is a hard
+        seam where cleanliness flips; only the person is handled; background hidden in both key frames stays a blend; a key
+        frame without a detected person has an all-zero mask.  It is refused with mci_precision="half" (the refinement has no
+        masked form yet) and with output_size="keyframes" (rib_scaled_frames has none).  mci_precision="half" (default "full"; a setting of
         background="mci"): the integer field writes the motion between the key frames as an even number of pixels; one more
         launch per group (rib_halfpel_refine; background.mci_refine_host) refines every block's vector by half a pixel and the frames
         are sampled from that field (rib_halfpel_frames; mci_frames_host(precision="half")).  Half-pel samples are bilinear and
@@ -698,8 +706,9 @@ class Evaluator:
                 raise ValueError("evaluate_from_folder: poses=%r needs motion= (the motion model, motion.model.ModelInference)" % (poses,))
             if not (isinstance(upsample_rate, int) and upsample_rate >= 1 and upsample_rate & (upsample_rate - 1) == 0):
                 raise ValueError("evaluate_from_folder: upsample_rate must be a power of two, got %r" % (upsample_rate,))
-        mci_levels, mci_border = _background.check_settings(background, mci_range, mci_border, self.resize_on, mci_precision=mci_precision)
         _composite.check_output_size(output_size, "evaluate_from_folder")
+        mci_levels, mci_border = _background.check_settings(background, mci_range, mci_border, self.resize_on, mci_precision=mci_precision,
+                                                            mci_person=mci_person, output_size=output_size)
         if output_size == "source" and background == "mci":
             raise ValueError("evaluate_from_folder: output_size='source' with background='mci' is not supported: the interpolation "
                              "runs at the model size (a source-size interpolation is a follow-up); use output_size='keyframes'")
@@ -737,10 +746,11 @@ class Evaluator:
         self.metrics = self.metrics_report = None
         pipe = _FolderPipeline(self, model, rank, world, gt_dir, metrics=bool(metrics), mask_dir=mask_dir, pose_mask=bool(pose_mask),
                                panels=bool(panels), panel_frames=bool(panel_frames), panel_quality=int(panel_quality),
-                               panel_encode=panel_encode, background=background, mci_levels=mci_levels, mci_border=mci_border, mci_precision=mci_precision, video=bool(video), video_quality=int(video_quality),
+                               panel_encode=panel_encode, background=background, mci_levels=mci_levels, mci_border=mci_border, mci_precision=mci_precision, mci_person=mci_person, video=bool(video), video_quality=int(video_quality),
                                video_frames=bool(video_frames), write_png=frames == "png", output_size=output_size, png_gpu=png_on == "gpu",
                                key_poses=None if poses == "folder" else (motion, key_pose_dir, upsample_rate, poses == "keyframes-linear", bool(save_poses)))
         self.background, self.mci_range, self.mci_border, self.mci_precision = background, mci_range, mci_border, mci_precision
+        self.mci_person = mci_person
         self.output_size = output_size
         self.timings = pipe.tm
         if metrics and pipe.native:
@@ -854,7 +864,7 @@ class _FolderPipeline:
     def __init__(self, ev, model, rank, world, gt_dir, metrics=False, mask_dir=None, pose_mask=False,
                  panels=False, panel_frames=False, panel_quality=90, panel_encode="host", background="dain", mci_levels=3,
                  video=False, video_quality=90, video_frames=False, write_png=True, key_poses=None, mci_border="clamp", mci_precision="full",
-                 output_size="model", png_gpu=False):
+                 output_size="model", png_gpu=False, mci_person="keep"):
         # composite.py: the frames' files at the clip's own size - the DAIN frames' ("source") or, under background="mci", the key
         # frame files' ("keyframes": keysize; the backgrounds are then rib_scaled_frames', everything after them is "source"'s code)
         self.source = output_size in ("source", "keyframes")
@@ -862,6 +872,7 @@ class _FolderPipeline:
         self.mci, self.mci_levels = background == "mci", mci_levels      # (levels: background.mci_field_host's, from mci_range)
         self.mci_border = mci_border        # background.py's border
         self.mci_half = mci_precision == "half"      # background.py's precision: the field is refined once per group, in half pixels
+        self.mci_exclude = mci_person == "exclude"   # background.py's "person": the key frames' human masks keep the person out
         # poses="keyframes": (motion model, key-pose folder, upsample rate, take the linear clip, also write the json folders)
         self.key_poses = key_poses
         # video: the frames' JPEG files (video.py); write_png False (frames="none"): they are the only files of a frame
@@ -884,6 +895,8 @@ class _FolderPipeline:
             raise RuntimeError("panels=True: this model has no GPU sheet kernel (rib_panel)")
         if self.native and self.mci and not hasattr(model, "mci_frames"):
             raise RuntimeError("background='mci': this model has no GPU interpolation kernels (rib_mci_field / rib_mci_frames)")
+        if self.native and self.mci_exclude and not (hasattr(model, "mci_frames_masked") and hasattr(model, "human_mask")):
+            raise RuntimeError("mci_person='exclude': this model has no GPU kernels for it (rib_masked_field / rib_masked_frames / rib_human_mask)")
         if self.native and self.mci_half and not hasattr(model, "mci_refine"):
             raise RuntimeError("mci_precision='half': this model has no GPU refinement kernel (rib_halfpel_refine)")
         self.jpeg_gpu = panels and panel_encode == "gpu"     # the sheets' JPEG files are jpeg_encode_host's bytes (rib_jpeg on the native path)
@@ -1291,7 +1304,13 @@ class _FolderPipeline:
                         views["mci_keys"][0, b].copy_(clip.key_u8[k])
                         views["mci_keys"][1, b].copy_(clip.key_u8[k + clip.sample_rate])
                     kab = views["mci_keys"].to(g.device, non_blocking=True)
-                    field = g.mci_field(kab[0], kab[1], self.mci_levels, border=self.mci_border)
+                    qab = (None, None)
+                    if self.mci_exclude:        # the human masks of the two key frames' poses (rib_human_mask), 1 = excluded; no person: all zero
+                        pk = np.stack([self.peaks_of(clip.loads[k + d].result(timeout=IO_TIMEOUT_S)[2]) for d in (0, clip.sample_rate) for k in ks])
+                        qab = (g.human_mask(pk, ev.height, ev.width) > 0).to(torch.uint8).view(2, len(ks), ev.height, ev.width)
+                        field = g.mci_field_masked(kab[0], kab[1], qab[0], qab[1], self.mci_levels, border=self.mci_border)
+                    else:
+                        field = g.mci_field(kab[0], kab[1], self.mci_levels, border=self.mci_border)
                     if self.mci_half:           # one more launch behind the field's, on the same stream; in place
                         field = g.mci_refine(kab[0], kab[1], field, border=self.mci_border, out=field)
                     kab0 = (None, None)
@@ -1300,10 +1319,14 @@ class _FolderPipeline:
                             views["mci_keys_src"][0, b].copy_(torch.from_numpy(clip.key_src[k].result(timeout=IO_TIMEOUT_S)))
                             views["mci_keys_src"][1, b].copy_(torch.from_numpy(clip.key_src[k + clip.sample_rate].result(timeout=IO_TIMEOUT_S)))
                         kab0 = views["mci_keys_src"].to(g.device, non_blocking=True)
-                    clip.mci_of[gi] = (kab[0], kab[1], field, kab0[0], kab0[1])
-                ka, kb, field, ka0, kb0 = clip.mci_of[gi]
-                dn = g.mci_frames(ka, kb, field, clip.sample_rate, k_first=c0 + 1, count=Tc, normalised="both" if self.panels else True,
-                                  border=self.mci_border, precision="half" if self.mci_half else "full")
+                    clip.mci_of[gi] = (kab[0], kab[1], field, kab0[0], kab0[1], qab[0], qab[1])
+                ka, kb, field, ka0, kb0, qa, qb = clip.mci_of[gi]
+                if self.mci_exclude:
+                    dn = g.mci_frames_masked(ka, kb, qa, qb, field, clip.sample_rate, k_first=c0 + 1, count=Tc,
+                                             normalised="both" if self.panels else True, border=self.mci_border)
+                else:
+                    dn = g.mci_frames(ka, kb, field, clip.sample_rate, k_first=c0 + 1, count=Tc, normalised="both" if self.panels else True,
+                                      border=self.mci_border, precision="half" if self.mci_half else "full")
                 if self.panels:
                     dn, dnu8 = dn
                 if self.keysize:               # ONE launch: the unit's backgrounds uint8 [Tc,B,h0,w0,3], "source"'s staged frames
@@ -1748,11 +1771,17 @@ class _FolderPipeline:
             poses = [g[2] for g in got]
             if self.mci:                         # the host definition of the background frames (background.py)
                 ka, kb = clip.key_u8[k].numpy(), clip.key_u8[k + clip.sample_rate].numpy()
-                field = _background.mci_field_host(ka, kb, self.mci_levels, border=self.mci_border)
-                if self.mci_half:
-                    field = _background.mci_refine_host(ka, kb, field, border=self.mci_border)
-                u8 = _background.mci_frames_host(ka, kb, field, clip.sample_rate, [i - k for i in frames], border=self.mci_border,
-                                                 precision="half" if self.mci_half else "full")
+                if self.mci_exclude:             # the host statement of the two key frames' human masks, 1 = excluded
+                    qa, qb = (rasterise.human_mask(self.peaks_of(clip.loads[j].result()[2]), ev.height, ev.width).astype(np.uint8)
+                              for j in (k, k + clip.sample_rate))
+                    field = _background.mci_field_masked_host(ka, kb, qa, qb, self.mci_levels, border=self.mci_border)
+                    u8 = _background.mci_frames_masked_host(ka, kb, qa, qb, field, clip.sample_rate, [i - k for i in frames], border=self.mci_border)
+                else:
+                    field = _background.mci_field_host(ka, kb, self.mci_levels, border=self.mci_border)
+                    if self.mci_half:
+                        field = _background.mci_refine_host(ka, kb, field, border=self.mci_border)
+                    u8 = _background.mci_frames_host(ka, kb, field, clip.sample_rate, [i - k for i in frames], border=self.mci_border,
+                                                     precision="half" if self.mci_half else "full")
                 # the floats the native chain reads (the device's normalisation, stated on the host); the sheets' DAIN pane
                 # shows the host's normalisation, as the native path's does (normalise_exact)
                 dn = torch.from_numpy(_background.normalised_upload(u8)).unsqueeze(1)

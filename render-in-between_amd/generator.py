@@ -714,6 +714,83 @@ class Generator:
         res = tuple((r[:, 0] if single else r) for r in (rf, ru) if r is not None)
         return res if normalised == "both" else res[0]
 
+    def _mci_masks(self, ma, mb, shape, single, who):
+        """ma, mb uint8 [B,H,W] (or [H,W] beside [H,W,3] key frames) on this device, nonzero = excluded -> contiguous [B,H,W]."""
+        out = []
+        for m in (ma, mb):
+            if not torch.is_tensor(m) or m.dtype != torch.uint8 or m.device != self.device:
+                raise ValueError("%s: a mask must be a uint8 tensor on %s, got %s" % (who, self.device, getattr(m, "dtype", type(m))))
+            m = m.unsqueeze(0) if (single and m.dim() == 2) else m
+            if tuple(m.shape) != tuple(shape):
+                raise ValueError("%s: the masks of %s key frames are uint8 %s, got %s" % (who, tuple(shape) + (3,), tuple(shape), tuple(m.shape)))
+            out.append(m.contiguous())
+        return out
+
+    def mci_field_masked(self, a_u8, b_u8, ma, mb, levels=3, border="clamp"):
+        """mci_field with the person kept out of the matching (rib_masked_field; background.mci_field_masked_host is the
+        definition and is bit-equal): ma, mb uint8 [B,H,W] (or [H,W]) on this device, nonzero = excluded, for the left and the
+        right key frame -> int16 [B,Hb,Wb,2] (or [Hb,Wb,2]).  levels + 4 launches on the current stream."""
+        from .background import BORDERS, check_border, check_levels, field_shape
+        levels = check_levels(levels, "mci_field_masked")
+        border = BORDERS.index(check_border(border, "mci_field_masked"))
+        a, b, single = self._mci_pair(a_u8, b_u8, "mci_field_masked")
+        B, H, W, _ = a.shape
+        qa, qb = self._mci_masks(ma, mb, (B, H, W), single, "mci_field_masked")
+        n = int(self._lib.rib_masked_workspace_bytes(self._h, B, H, W, levels))
+        if n == 0:
+            raise ValueError("mci_field_masked: B=%d H=%d W=%d: 1 <= B <= 32767, H and W in 1..16384" % (B, H, W))
+        Hb, Wb = field_shape(H, W)
+        with torch.cuda.device(self.device):
+            ws = torch.empty(n, dtype=torch.uint8, device=self.device)      # (per call: it belongs to the stream the call is enqueued on)
+            field = torch.empty((B, Hb, Wb, 2), dtype=torch.int16, device=self.device)
+            _native.check(self._h, self._lib.rib_masked_field(self._h, B, H, W, _ptr(a), _ptr(b), _ptr(qa), _ptr(qb), _ptr(field), levels,
+                                                              border, _ptr(ws), self._stream()))
+        return field[0] if single else field
+
+    def mci_frames_masked(self, a_u8, b_u8, ma, mb, field, sample_rate, k_first=1, count=None, normalised=True, out=None, border="clamp",
+                          precision="full"):
+        """mci_frames with the person kept out (rib_masked_frames; background.mci_frames_masked_host is the definition and is
+        bit-equal): ma, mb uint8 [B,H,W] (or [H,W]) on this device, nonzero = excluded; where exactly one of a pixel's two samples
+        is clean - valid under `border`, and the four taps of its footprint in its key frame's mask all zero - the output is that
+        sample alone.  Everything else - field, frames, normalised (True, False, "both"), out, precision - is mci_frames'."""
+        from .background import BORDERS, PRECISIONS, check_border, check_precision, field_shape, log2_rate
+        border = BORDERS.index(check_border(border, "mci_frames_masked"))
+        precision = PRECISIONS.index(check_precision(precision, "mci_frames_masked"))
+        a, b, single = self._mci_pair(a_u8, b_u8, "mci_frames_masked")
+        B, H, W, _ = a.shape
+        qa, qb = self._mci_masks(ma, mb, (B, H, W), single, "mci_frames_masked")
+        Hb, Wb = field_shape(H, W)
+        log2_rate(sample_rate)
+        s = int(sample_rate)
+        if not torch.is_tensor(field) or field.dtype != torch.int16 or field.device != self.device:
+            raise ValueError("mci_frames_masked: field must be an int16 tensor on %s (mci_field_masked)" % (self.device,))
+        f = (field.unsqueeze(0) if field.dim() == 3 else field).contiguous()
+        if tuple(f.shape) != (B, Hb, Wb, 2):
+            raise ValueError("mci_frames_masked: the field of %d %dx%d segments is [%d, %d, %d, 2], got %s" % (B, H, W, B, Hb, Wb, tuple(field.shape)))
+        k_first = int(k_first)
+        T = (s - k_first) if count is None else int(count)
+        if T < 1 or k_first < 0 or k_first + T - 1 > s:
+            raise ValueError("mci_frames_masked: frames %d..%d are outside the segment 0..%d" % (k_first, k_first + T - 1, s))
+        if normalised not in (True, False, "both"):
+            raise ValueError("mci_frames_masked: normalised must be True, False or 'both'")
+        fshape, ushape = (T, B, 3, H, W), (T, B, H, W, 3)
+        of, ou = (out if normalised == "both" else (out, None) if normalised else (None, out)) if out is not None else (None, None)
+
+        def dest(t, shape, dtype):
+            if t is None:
+                return torch.empty(shape, dtype=dtype, device=self.device)
+            v = t.unsqueeze(1) if (single and t.dim() == 4) else t
+            if tuple(v.shape) != shape or v.dtype != dtype or not v.is_contiguous() or v.device != self.device:
+                raise ValueError("mci_frames_masked: out must be a contiguous %s %s tensor on %s" % (shape, dtype, self.device))
+            return v
+        with torch.cuda.device(self.device):
+            rf = dest(of, fshape, torch.float32) if normalised in (True, "both") else None
+            ru = dest(ou, ushape, torch.uint8) if normalised in (False, "both") else None
+            _native.check(self._h, self._lib.rib_masked_frames(self._h, T, B, H, W, _ptr(a), _ptr(b), _ptr(qa), _ptr(qb), _ptr(f), s, k_first,
+                                                               border, precision, _ptr(rf), _ptr(ru), self._stream()))
+        res = tuple((r[:, 0] if single else r) for r in (rf, ru) if r is not None)
+        return res if normalised == "both" else res[0]
+
     def mci_frames_scaled(self, a0_u8, b0_u8, field, model_hw, sample_rate, k_first=0, count=None, border="clamp", precision="full", out=None):
         """mci_frames' uint8 frames at the key frames' OWN size, one launch (rib_scaled_frames; background.mci_frames_scaled_host
         is the definition and is bit-equal): a0_u8, b0_u8 uint8 [B,h0,w0,3] (or [h0,w0,3]) are the key frame files' pixels on

@@ -53,6 +53,15 @@ frame's edge column.  Frame border only: a foreground object that covers backgro
 an even number; one more launch per group (rib_halfpel_refine) refines every block's vector by half a pixel and the frames are sampled
 from that field (rib_halfpel_frames).  Half-pel samples are bilinear and soft; a block whose whole-pixel vector is more than one
 half-pel step from the truth stays wrong; no quarter-pel.
+`--mci-person exclude` (default `keep`): the driver knows where the person is in both key frames - it reads their poses - and the
+block matcher otherwise matches person pixels against background pixels, so every in-between background carries a half-transparent
+ghost of the person where key frame A has them and another where B has them.  `exclude` takes the human masks of the two key
+frames' poses (rib_human_mask) as excluded pixels: they do not count in the matching (rib_masked_field), and a pixel that only one
+key frame shows without the person is that key frame's sample alone (rib_masked_frames).  The limits, plainly: the mask is the
+reference's coarse pose mask, so hair, loose clothing and carried objects outside it still ghost; there is a hard seam where
+cleanliness flips; only the person is handled, not other moving objects; background hidden in both key frames stays a blend; the
+generator and its mask network were trained on DAIN frames that show a blurred person; quality on real footage is unmeasured.
+Not yet with `--mci-precision half` nor `--output-size keyframes`.
 Frames are then named after their pose files.  The default, `--background dain`, is the reference's contract.
 
 Poses without a Predict_motion folder: `--poses keyframes --pose-dir DIR [--upsample-rate N] [--motion-config PATH]` runs stage 1
@@ -143,7 +152,8 @@ def summary_line(evaluator, rank=0, world=1):
                getattr(evaluator, "resize_on", "host"),
                {"dain": "DAIN frames", "mci": "mci (interpolated from the key frames, range %d px, border %s%s)"
                        % (getattr(evaluator, "mci_range", 32), getattr(evaluator, "mci_border", "clamp"),
-                          ", half-pel" if getattr(evaluator, "mci_precision", "full") == "half" else "")}
+                          (", half-pel" if getattr(evaluator, "mci_precision", "full") == "half" else "")
+                          + (", person excluded" if getattr(evaluator, "mci_person", "keep") == "exclude" else ""))}
                [getattr(evaluator, "background", "dain")]))
     if getattr(evaluator, "output_size", "model") == "source":
         line += " | files at the source size"
@@ -191,7 +201,7 @@ def main(opts):
                                              panel_quality=90 if opts.panel_quality is None else opts.panel_quality,
                                              panel_fps=30 if opts.panel_fps is None else opts.panel_fps,
                                              panel_encode=opts.panel_encode or "host", background=opts.background, mci_range=opts.mci_range,
-                                             mci_border=opts.mci_border, mci_precision=opts.mci_precision,
+                                             mci_border=opts.mci_border, mci_precision=opts.mci_precision, mci_person=opts.mci_person,
                                              video=opts.video, video_fps=30 if opts.video_fps is None else opts.video_fps,
                                              video_quality=90 if opts.video_quality is None else opts.video_quality,
                                              video_frames=opts.video_frames, frames=opts.frames, output_size=opts.output_size, png_on=opts.png_on,
@@ -278,6 +288,15 @@ def build_parser():
                              "two key frames is an even number of pixels; 'half': one more launch per group refines every block's vector "
                              "by half a pixel (bilinear half-pel samples, soft; a block more than one half-pel step from the truth stays "
                              "wrong; no quarter-pel)")
+    parser.add_argument("--mci-person", default=None,
+                        help="with --background mci: 'keep' (default): the person's pixels take part in the matching, and every "
+                             "in-between background carries a ghost of the person at both key frames' positions; 'exclude': the human "
+                             "masks of the two key frames' poses are kept out of the matching, and a pixel that only one key frame shows "
+                             "without the person is that key frame's sample alone. The mask is the reference's coarse pose mask (hair, "
+                             "loose clothing and carried objects outside it still ghost); a hard seam where cleanliness flips; only the "
+                             "person, not other moving objects; background hidden in both key frames stays a blend; the generator was "
+                             "trained on DAIN frames that show a blurred person; unmeasured on real footage. Not yet with "
+                             "--mci-precision half (no masked refinement) nor --output-size keyframes (no masked rib_scaled_frames)")
     parser.add_argument("--video", action="store_true",
                         help="also write every frame of a clip, key frames included, as <save-dir>/Generated_frames/<clip>_video.avi "
                              "(Motion-JPEG; a frame is the JPEG of exactly the bytes its PNG holds, encoded on the GPU)")
@@ -344,6 +363,17 @@ def parse_args(argv=None):
     if opts.mci_precision not in (None, "full", "half"):
         parser.error("--mci-precision must be 'full' or 'half', got %r" % (opts.mci_precision,))
     opts.mci_precision = "full" if opts.mci_precision is None else opts.mci_precision
+    if opts.mci_person is not None and opts.background != "mci":
+        parser.error("--mci-person is a setting of --background mci")
+    if opts.mci_person not in (None, "keep", "exclude"):
+        parser.error("--mci-person must be 'keep' or 'exclude', got %r" % (opts.mci_person,))
+    opts.mci_person = "keep" if opts.mci_person is None else opts.mci_person
+    if opts.mci_person == "exclude" and opts.mci_precision == "half":
+        parser.error("--mci-person exclude with --mci-precision half is not supported yet: the half-pel refinement has no masked form "
+                     "(a masked rib_halfpel_refine is the follow-up)")
+    if opts.mci_person == "exclude" and opts.output_size == "keyframes":
+        parser.error("--mci-person exclude with --output-size keyframes is not supported yet: rib_scaled_frames has no masked form "
+                     "(the follow-up)")
     if opts.background == "mci" and opts.resize_on == "gpu":
         parser.error("--background mci with --resize-on gpu is not supported (there is no DAIN list to plan the GPU resize for)")
     if opts.output_size == "source" and opts.background == "mci":

@@ -94,6 +94,8 @@ def main():
     ap.add_argument("--mci-range", type=int, default=32, choices=(32, 64, 128), help="with --background mci: the search's range in px between key frames (mci_range=...)")
     ap.add_argument("--mci-border", default="clamp", choices=("clamp", "valid"), help="with --background mci: the border mode (mci_border=...)")
     ap.add_argument("--mci-precision", default="full", choices=("full", "half"), help="with --background mci: half-pel refinement of the field (mci_precision=...)")
+    ap.add_argument("--mci-person", default="keep", choices=("keep", "exclude"),
+                    help="with --background mci: the key frames' human masks are kept out of the interpolation (mci_person=...)")
     ap.add_argument("--video", action="store_true", help="also write the frames as <clip>_video.avi, JPEG-encoded on the GPU (video=True)")
     ap.add_argument("--frames", default="png", choices=("png", "none"), help="with --video: 'none' writes no PNG frames (frames=...)")
     ap.add_argument("--poses", default="folder", choices=("folder", "keyframes"),
@@ -119,6 +121,8 @@ def main():
         ap.error("--mci-range is a setting of --background mci")
     if a.mci_precision != "full" and a.background != "mci":
         ap.error("--mci-precision is a setting of --background mci")
+    if a.mci_person != "keep" and a.background != "mci":
+        ap.error("--mci-person is a setting of --background mci")
     if a.mci_border != "clamp" and a.background != "mci":
         ap.error("--mci-border is a setting of --background mci")
     if a.panel_encode != "host" and not a.panels:
@@ -164,7 +168,8 @@ def main():
                                          **({"png_on": a.png_on} if a.png_on != "host" else {}),
                                          **({"mci_range": a.mci_range} if a.background == "mci" else {}),
                                          **({"mci_border": a.mci_border} if a.mci_border != "clamp" else {}),
-                                         **({"mci_precision": a.mci_precision} if a.mci_precision != "full" else {}))
+                                         **({"mci_precision": a.mci_precision} if a.mci_precision != "full" else {}),
+                                         **({"mci_person": a.mci_person} if a.mci_person != "keep" else {}))
             torch.cuda.synchronize()
             walls.append(time.perf_counter() - t0)
         tm = dict(E.timings)
@@ -178,6 +183,7 @@ def main():
                       "src_height": a.src_height or H, "src_width": a.src_width or W, "resize_on": a.resize_on, "output_size": a.output_size, "background": a.background, "mci_range": a.mci_range if a.background == "mci" else None,
                       "mci_border": a.mci_border if a.background == "mci" else None,
                       "mci_precision": a.mci_precision if a.background == "mci" else None,
+                      "mci_person": a.mci_person if a.background == "mci" else None,
                       "metrics": a.metrics, "pose_mask": a.pose_mask, "metrics_overall": overall, "panels": a.panels, "panel_encode": a.panel_encode,
                       "video": a.video, "frames_written": a.frames, "png_on": a.png_on, "png_bytes_last_run": png_bytes, "poses": a.poses, "stage1_plus_bridge_ms_per_clip": stage1_ms,
                       "wall_s": wall, "wall_s_runs": [round(w, 4) for w in walls[1:]], "frames_per_s_end_to_end": n / wall,

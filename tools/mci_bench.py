@@ -2,13 +2,17 @@
 """The motion-compensated background on its own: rib_mci_field and rib_mci_frames (Generator.mci_field / mci_frames) on one
 unit - B segments of H x W at sample rate s - for a kernel trace.
 
-    rocprofv3 --kernel-trace --stats -d DIR -- python tools/mci_bench.py [--size 512] [--batch 4] [--rate 8] [--reps 20] [--u8] [--levels 3] [--border clamp] [--precision full]
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/mci_bench.py [--size 512] [--batch 4] [--rate 8] [--reps 20] [--u8] [--levels 3] [--border clamp] [--precision full] [--person]
 
 --levels 3 (the default), 4 or 5: the pyramid levels of the field's search, the driver's --mci-range 32, 64 or 128; the scene's
 motion between the key frames grows with it (a quarter of that range in x, 3/16 in y).  --border valid: the one-sided border mode
 (the driver's --mci-border; k_mci_search<R, true> and k_mci_frames<true> in the trace).  --precision half (the driver's
 --mci-precision): the refine launch (rib_halfpel_refine, k_mci_refine in the trace) is timed beside the field, and the frames are
 rib_halfpel_frames's from the refined field (k_mci_frames<.., true>); the default times what it always timed.
+--person (the driver's --mci-person exclude): AFTER everything above, the same unit through rib_masked_field / rib_masked_frames
+(Generator.mci_field_masked / mci_frames_masked) with an upright ellipse per key frame as the excluded pixels, a sixth of the
+width wide and moved by an eighth of the width between the key frames - k_mci_mask_pyramid, k_mci_search<R, .., true>, k_mci_fill
+and k_mci_frames<.., .., true> in the same trace, beside the unmasked rows; not with --precision half.
 
 Prints one JSON line: the wall time of the field's launches (levels + 2: five by default) and of the frames launch between two events (median of
 --reps, after a warm-up), the frames launch's byte floor (12 bytes of float32 out per pixel and frame, 3 more with --u8, the
@@ -50,7 +54,10 @@ def main():
     ap.add_argument("--levels", type=int, default=3, choices=(3, 4, 5), help="pyramid levels of the search (--mci-range 32, 64, 128)")
     ap.add_argument("--border", default="clamp", choices=("clamp", "valid"), help="the border mode (--mci-border)")
     ap.add_argument("--precision", default="full", choices=("full", "half"), help="the field's unit (--mci-precision): half also times the refine launch")
+    ap.add_argument("--person", action="store_true", help="also time the masked entries (--mci-person exclude) on the same unit")
     a = ap.parse_args()
+    if a.person and a.precision == "half":
+        ap.error("--person times the whole-pixel masked entries: not with --precision half")
     kw = {} if a.border == "clamp" else {"border": a.border}       # (clamp: the calls of before the mode existed)
     H, W, B, s = a.height or a.size, a.width or a.size, a.batch, a.rate
     m = 16 << (a.levels - 3)                   # margin of the scene around the key frames: the second crop moves by (m/2, -3m/8)
@@ -75,6 +82,17 @@ def main():
     fms = timed(lambda: G.mci_field(ka, kb, a.levels, **kw), a.reps)
     rms = timed(lambda: G.mci_frames(ka, kb, field, s, normalised="both" if a.u8 else True, out=(f32, u8) if a.u8 else f32, **fkw), a.reps)
     floor = (12 + (3 if a.u8 else 0)) * H * W * T * B + 2 * 3 * H * W * B
+    if a.person:
+        Y, X = torch.meshgrid(torch.arange(H, device="cuda"), torch.arange(W, device="cuda"), indexing="ij")
+        oval = lambda cx: ((((X - cx) * 12 // W) ** 2 + ((Y - H // 2) * 3 // H) ** 2) <= 1).to(torch.uint8).expand(B, H, W).contiguous()
+        qa, qb = oval(W // 2 - W // 16), oval(W // 2 + W // 16)
+        mfield = G.mci_field_masked(ka, kb, qa, qb, a.levels, **kw)
+        pms = timed(lambda: G.mci_field_masked(ka, kb, qa, qb, a.levels, **kw), a.reps)
+        qms = timed(lambda: G.mci_frames_masked(ka, kb, qa, qb, mfield, s, normalised="both" if a.u8 else True, out=(f32, u8) if a.u8 else f32, **kw), a.reps)
+        extra.update({"person": True, "excluded_fraction": round(float((qa != 0).float().mean()), 3),
+                      "masked_field_event_us_median": round(pms[len(pms) // 2] * 1e3, 2), "masked_field_event_us_min": round(pms[0] * 1e3, 2),
+                      "masked_frames_event_us_median": round(qms[len(qms) // 2] * 1e3, 2), "masked_frames_event_us_min": round(qms[0] * 1e3, 2),
+                      "masked_field_differs_fraction": round(float((mfield != field).any(-1).float().mean()), 3)})
     print(json.dumps({"height": H, "width": W, "batch": B, "rate": s, "levels": a.levels, "border": a.border, "precision": a.precision, "frames": T * B, "u8": a.u8,
                       "field_event_us_median": round(fms[len(fms) // 2] * 1e3, 2), "field_event_us_min": round(fms[0] * 1e3, 2),
                       "frames_event_us_median": round(rms[len(rms) // 2] * 1e3, 2), "frames_event_us_min": round(rms[0] * 1e3, 2),
