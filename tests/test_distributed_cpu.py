@@ -264,7 +264,8 @@ def test_a_failed_start_up_names_rank_device_backend_and_ipc_mode(monkeypatch, c
     assert capfd.readouterr().err == ""
     # the launcher: a fresh child per rank; a non-zero exit is reported on stderr and returned, stdout stays the ranks'
     script = tmp_path / "rank.py"
-    script.write_text("import os, sys\nprint('line of rank', os.environ['RANK'])\nsys.exit(3 if os.environ['RANK'] == '1' else 0)\n")
+    # (one write per rank: the ranks share the stdout, and the pieces of a print() of two arguments have come out interleaved)
+    script.write_text("import os, sys\nsys.stdout.write('line of rank %s\\n' % os.environ['RANK'])\nsys.exit(3 if os.environ['RANK'] == '1' else 0)\n")
     rc = ribdist.self_launch(str(script), [], 2)
     out = capfd.readouterr()
     assert rc != 0 and "[rib launcher] 2 ranks of rank.py ended with exit code" in out.err and "HSA_ENABLE_IPC_MODE_LEGACY=0" in out.err

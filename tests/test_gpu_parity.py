@@ -737,7 +737,11 @@ def test_every_kernel_variant_is_correct_wherever_it_fits():
     """Forces, on representative launches (3x3 with a fused 1x1 shortcut, stride 2, upsampled gather,
     1x1, 16-column, SPADE), every tile variant x split-K that the plan accepts - including the
     in-workgroup split-K (KW) and three-slices-per-barrier (TB) twins - and checks the frame against
-    the plan's default choice.  A variant that does not fit a launch is rejected by the plan builder."""
+    the plan's default choice.  A variant that does not fit a launch is rejected by the plan builder.
+    The per-variant proof is elsewhere: tests/test_gpu_variants32.py forces every fp32 variant and every (geometry, split-K)
+    pair the measured table pins at 2x48x80 and holds each forced launch's own product tap to the default plan and to the
+    fp64 oracle on a poisoned workspace (tests/test_variants32_cpu.py proves that its list leaves none out); the bf16 / half
+    twins have tests/test_gpu_variants16.py."""
     import ctypes as C
     from render_in_between_amd import _native
     spec, sd, _ = build("full", 0)

@@ -12,18 +12,16 @@ use - shape, launches, their taps, split-K factors - and asserts that the list l
 
 "Accepted" is what tools/variant_usage.py reads: after rib_set_choice the plan still builds (rib_num_launches > 0) and
 the launch's info line names the forced variant and split (a SPADE that is only a modulate of its level's slab builds
-a plan too, but runs no kernel of its own: that is not an acceptance)."""
-import ctypes as C
+a plan too, but runs no kernel of its own: that is not an acceptance).  The helpers are tests/variants_common.py's, which
+the fp32 files (tests/test_variants32_cpu.py, tests/test_gpu_variants32.py) use too."""
 import functools
-import re
 
 import pytest
 
-import render_in_between_amd as rib
-from render_in_between_amd import _native, tuning
+from tests.variants_common import (B, H, INPUT_SEED, NUM_TAPS, PREC, SHAPE, W, accepted_of, gemm_launch, gemm_tap,      # noqa: F401
+                                   gemm_taps, host_handle, launch_lines, tap_list, takes_choice, variants)               # (the GPU file's too)
+from tests import variants_common
 
-B, H, W = SHAPE = (2, 48, 80)      # every map from 48x80 down to 3x5 leaves partial tiles; batch 2: the sample stride
-INPUT_SEED = 3                     # synth.make_inputs(spec, 2, 48, 80, 3): the inputs of the two 16-bit frame tests
 KSPLITS = (1, 2, 3, 4)             # every factor the 16-bit table names
 # launch -> the tap that is its direct product (Builder::spade_block / mask_branch / frame, csrc/planner.h)
 LAUNCHES = (
@@ -43,91 +41,7 @@ LAUNCHES = (
 )
 GEMM_LEVELS = (1, 2, 3, 4)         # cond_<k>.gammabeta: the level's gamma/beta slab, read by the first SPADE of that level
 GEMM_TILES = {"128x64", "64x64", "64x128", "128x128"}
-NUM_TAPS = 68                      # taps of the plan of SHAPE: "every earlier tap is bit-equal" is only as long as this list
-DTYPES = {"bf16": (1, 1), "f16": (3, 2)}      # name -> (rib_set_compute_dtype code, what rib_variant_info returns)
-
-
-def gemm_launch(k):
-    return "cond_%d.gammabeta" % k
-
-
-def host_handle(fmt):
-    """A host-only handle of the full HSM configuration in the 16-bit mode `fmt`, debug taps on (as the GPU test runs)."""
-    lib = _native.lib()
-    spec = rib.GenSpec.from_cfg(rib.hsm_gen_config())
-    c = _native.RibConfig(**{n: getattr(spec, n) for n, _ in _native.RibConfig._fields_})
-    h = C.c_void_p()
-    assert lib.rib_create(C.byref(c), -1, C.byref(h)) == 0, lib.rib_last_error(None)
-    assert lib.rib_set_compute_dtype(h, DTYPES[fmt][0]) == 0
-    assert lib.rib_set_debug_taps(h, 1) == 0
-    return lib, h
-
-
-@functools.lru_cache(maxsize=None)
-def variants(fmt):
-    """({index: geometry[12]} of the k_igemm variants, {index: "BMxBN"} of the k_gemm_dma tiles) of a precision."""
-    lib = _native.lib()
-    g = (C.c_int * 12)()
-    igemm, tiles = {}, {}
-    for i in range(lib.rib_num_variants()):
-        if lib.rib_variant_info(i, g) != DTYPES[fmt][1]:
-            continue
-        if g[0] == 0:                                  # FRW = 0: a k_gemm_dma tile of (32 WM MF) x (32 WN NF)
-            tiles[i] = "%dx%d" % (32 * g[1] * g[3], 32 * g[2] * g[4])
-        else:
-            igemm[i] = tuple(g)
-    return igemm, tiles
-
-
-def launch_lines(lib, h):
-    """{launch name: its rib_debug_launch_info line} of the plan of SHAPE, or None where no plan can be built."""
-    n = lib.rib_num_launches(h, B, H, W)
-    if n <= 0:
-        return None
-    buf = C.create_string_buffer(512)
-    out = {}
-    for i in range(n):
-        assert lib.rib_debug_launch_info(h, B, H, W, i, buf, 512) == 0
-        line = buf.value.decode()
-        out[line.split("|", 1)[0]] = line
-    return out
-
-
-def tap_list(lib, h):
-    """[(name, C, H, W)] of the plan's taps, in plan order."""
-    name = C.c_char_p(); ch = C.c_int(); th = C.c_int(); tw = C.c_int()
-    out = []
-    for i in range(lib.rib_num_taps(h, B, H, W)):
-        assert lib.rib_tap_info(h, B, H, W, i, C.byref(name), C.byref(ch), C.byref(th), C.byref(tw)) == 0
-        out.append((name.value.decode(), ch.value, th.value, tw.value))
-    return out
-
-
-def gemm_tap(taps, k):
-    """The tap that reads cond_<k>.gammabeta's slab first: the first `.ys0` in plan order on a map of cond_<k>'s size (there
-    the gamma/beta are fp32 and the modulate is elementwise, so the tap carries one rounding of the GEMM's product)."""
-    size = {n: (th, tw) for n, _, th, tw in taps}["cond_%d" % k]
-    return next(n for n, _, th, tw in taps if n.endswith(".ys0") and (th, tw) == size)
-
-
-def gemm_taps(taps, k):
-    """Every SPADE output tap (`.ys0`, `.y1`) on a map of cond_<k>'s size, in plan order: the tapped readers of the level's slab,
-    gemm_tap(taps, k) first."""
-    size = {n: (th, tw) for n, _, th, tw in taps}["cond_%d" % k]
-    return [n for n, _, th, tw in taps if n.endswith((".ys0", ".y1")) and (th, tw) == size]
-
-
-def takes_choice(lib, h, fmt, launch, vi, ks):
-    """Pins (variant, ksplit) on `launch`: does the plan of SHAPE still build, and does the launch's line name that choice?
-    The choice stays pinned (the caller renders with it, or erases it with variant -1)."""
-    assert lib.rib_set_choice(h, B, H, W, launch.encode(), vi, ks) == 0
-    if lib.rib_workspace_bytes(h, B, H, W) == 0:
-        return False                                   # the plan builder refuses: does not fit this launch
-    line = launch_lines(lib, h).get(launch, "")
-    tile = variants(fmt)[1].get(vi)
-    if tile is not None:
-        return ks == 1 and ("gemm (LDS-DMA staged operands) tile %s " % tile) in line
-    return re.search(r" ksplit%d .* v%d\|" % (ks, vi), line) is not None
+DTYPES = {fmt: PREC[fmt] for fmt in ("bf16", "f16")}
 
 
 def candidates(fmt, launch):
@@ -139,29 +53,12 @@ def candidates(fmt, launch):
 @functools.lru_cache(maxsize=None)
 def accepted(fmt, launch):
     """((variant index, ksplit), ...) that the plan builder accepts for `launch` at SHAPE, in the order the GPU test tries them."""
-    lib, h = host_handle(fmt)
-    try:
-        out = tuple(c for c in candidates(fmt, launch) if takes_choice(lib, h, fmt, launch, *c))
-        assert lib.rib_set_choice(h, B, H, W, launch.encode(), -1, 1) == 0
-    finally:
-        lib.rib_destroy(h)
-    return out
+    return accepted_of(fmt, launch, candidates(fmt, launch))
 
 
 def table_pairs():
-    """({(geometry[12], ksplit)} of the k_igemm entries, {"BMxBN"} of the GEMM tiles) that the 16-bit table pins, over all
-    its shapes (an entry: geometry[10] + [ksplit] (+ [KW, TB]), tuning.apply)."""
-    pairs, tiles = set(), set()
-    for entry in tuning.load(dtype="bf16").values():
-        for choice in entry.values():
-            kw = int(choice[11]) if len(choice) > 11 else 1
-            tb = int(choice[12]) if len(choice) > 12 else 1
-            g = tuple(int(v) for v in choice[:10]) + (kw, tb)
-            if g[0] == 0:
-                tiles.add("%dx%d" % (32 * g[1] * g[3], 32 * g[2] * g[4]))
-            else:
-                pairs.add((g, int(choice[10])))
-    return pairs, tiles
+    """The (geometry, split-K) pairs and the GEMM tiles that the 16-bit table (tuning_gfx950_bf16.json) pins."""
+    return variants_common.table_pairs("bf16")
 
 
 @pytest.mark.parametrize("fmt", sorted(DTYPES))
