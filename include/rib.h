@@ -418,6 +418,34 @@ int rib_masked_frames(rib_handle* h, int T, int B, int H, int W, const uint8_t* 
 int rib_scaled_frames(rib_handle* h, int T, int B, int H, int W, int H0, int W0, const uint8_t* a0_u8, const uint8_t* b0_u8,
                       const int16_t* field_i16, int sample_rate, int k_first, int border, int precision, uint8_t* out_u8_nhwc,
                       void* hip_stream);
+/* rib_cubic_frames / rib_cubic_scaled (the driver's --mci-sampler cubic; background.sample_cubic and the sampler="cubic" forms of
+ * mci_frames_host, mci_frames_masked_host and mci_frames_scaled_host, bit-equal): the frames of rib_mci_frames / rib_halfpel_frames /
+ * rib_masked_frames and of rib_scaled_frames with every bilinear sample replaced by a 4x4 Catmull-Rom (A = -1/2) sample and NOTHING
+ * else changed - offsets, blend, k = 0 / k = s, both outputs, alignment and the "ONE launch, no workspace" contract are theirs.
+ * The sample at (py, px) in 1/256 px: tap rows (py >> 8) - 1 .. + 2, tap columns (px >> 8) - 1 .. + 2, each clamped to the frame;
+ * weights in 1/128 per axis from f = p & 255 by integers: n0 = -f^3 + 512 f^2 - 65536 f, n1 = 3 f^3 - 1280 f^2 + 2 * 256^3,
+ * n2 = -3 f^3 + 1024 f^2 + 65536 f, n3 = f^3 - 256 f^2, w_i = (n_i + 2^17) >> 18, the residual 128 - sum(w) added to the larger of
+ * w1, w2 (w1 on a tie); acc = sum_r wy[r] * (sum_c wx[c] * tap[r][c]) (|acc| < 2^23), result clip((acc + 8192) >> 14, 0, 255): the
+ * Catmull-Rom kernel overshoots at strong edges and the result is clamped.  border = 1: the rule is rib_mci_frames' (the sample's POSITION
+ * lies inside the frame; taps beyond the edge clamp), so the one-sided pixels are the bilinear entry's.  ma_u8, mb_u8 as
+ * rib_masked_frames' - both NULL: the person is kept; both given: a sample is clean iff all 16 clamped taps are clear (the clean /
+ * blend seam moves by a pixel against the 2x2 footprint's); exactly one NULL: RIB_ERR_INVALID.  precision: 0 = the field in
+ * whole pixels, 1 = in half pixels.  Where every offset is a whole pixel (k = 0, k = s, often k = s / 2) the bytes are the
+ * bilinear entries'.
+ * staging: 0 = a tile (64 consecutive x of one output row, one wave) whose taps fit a 12 x 76 window per key frame reads them from LDS,
+ * staged with one dword load per pixel, and every other tile gathers them directly (background.cubic_tile_staged states the rule);
+ * 1 = never stage.  It is a DIAGNOSTIC for the tests and the benches: the bytes never depend on it.
+ * The refusals are rib_masked_frames' / rib_scaled_frames' (sides 1..16384, sample_rate a power of two <= 1024, the frame range,
+ * border and precision in {0, 1}, the scaled form's ratio of 16, NULL or misaligned pointers, both outputs NULL), and also staging
+ * outside {0, 1}: RIB_ERR_INVALID with a rib_last_error text that begins with the entry's name, nothing launched.  Named rib_cubic_*,
+ * not rib_mci_*: that family stays at four.  This is still this project's interpolation: no interior occlusion reasoning. */
+int rib_cubic_frames(rib_handle* h, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8,
+                     const uint8_t* ma_u8, const uint8_t* mb_u8,   /* both NULL: the person is kept; exactly one NULL: invalid */
+                     const int16_t* field_i16, int sample_rate, int k_first, int border, int precision, int staging,
+                     float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream);
+int rib_cubic_scaled(rib_handle* h, int T, int B, int H, int W, int H0, int W0, const uint8_t* a0_u8, const uint8_t* b0_u8,
+                     const int16_t* field_i16, int sample_rate, int k_first, int border, int precision, int staging,
+                     uint8_t* out_u8_nhwc, void* hip_stream);
 void rib_mci_field_shape(int H, int W, int* Hb, int* Wb);
 size_t rib_mci_workspace_bytes(rib_handle* h, int B, int H, int W, int levels);
 int rib_mci_field(rib_handle* h, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,

@@ -88,6 +88,18 @@ rib_halfpel_frames) are held bit-equal to them (tests/test_gpu_mci.py, tests/tes
              mci_frames_host's for every shape; all-one masks: the zero field and the plain cross-fade.  Only the person is
              handled, by the reference's coarse pose mask; background hidden in BOTH key frames stays a blend.
 
+  sampler    (sampler="cubic" of the three mci_frames_*_host functions, the driver's mci_sampler; rib_cubic_frames / rib_cubic_scaled,
+             tests/test_gpu_mci_cubic.py; "bilinear" by default).  A bilinear sample at a fractional position is a low-pass filter that
+             disappears where the offset is a whole pixel (k = 0, k = s, often k = s / 2), so the backgrounds of a clip pulse between
+             sharp and soft at the key-frame rate.  "cubic" replaces sample_bilinear by sample_cubic - 4x4 taps, Catmull-Rom (A = -1/2)
+             weights in 1/128 per axis (cubic_weights, integers only), tap rows and columns clamped to the frame, acc = sum_r wy[r]
+             sum_c wx[c] v[r][c], result clip((acc + 8192) >> 14, 0, 255) - and NOTHING else: offsets, blend, k = 0 / k = s, and the
+             border rule (sample_valid looks at the POSITION, so the one-sided pixels are the bilinear sampler's).  Masked: a sample
+             is clean iff all 16 clamped taps are clear (sample_clean_cubic): the clean / blend seam moves by a pixel.  Where every
+             offset is a whole pixel the bytes are the bilinear sampler's.  Catmull-Rom overshoots at strong edges; the result is
+             clamped.  cubic_tile_staged states, from the sample positions alone, which tiles the kernels read from an LDS window
+             and which they gather directly; the bytes do not depend on it.
+
 No quarter-pel search, no sub-pel search on the coarse levels, and no occlusion reasoning beyond the frame border under
 border="valid" - a foreground object that covers background is not handled unless the person is excluded (`rib_masked_*`): see
 DESIGN ("Motion-compensated backgrounds") for what that costs."""
@@ -114,6 +126,9 @@ LAMBDA_HALF = 2           # mci_refine_host: cost of one HALF pixel of |hx| + |h
 HALF_KEY_BIAS = 256       # pack_key_half: hy + 256, hx + 256 in 9 bits each (|h| <= 2 * max_disp(5) + 1 = 159)
 PRECISIONS = ("full", "half")             # `precision` of mci_frames_host; the driver's mci_precision
 PERSONS = ("keep", "exclude")             # the driver's mci_person: "exclude" = the *_masked_host functions with the key frames' human masks
+SAMPLERS = ("bilinear", "cubic")          # `sampler` of the mci_frames_*_host functions; the driver's mci_sampler
+CUBIC_TILE = 64           # cubic_tile_staged: a tile is 64 consecutive x of one output row (one wave of k_cubic_frames / k_cubic_scaled)
+CUBIC_WIN_ROWS, CUBIC_WIN_COLS = 12, 76   # ... and it is staged when the taps of both its samples fit this window per key frame
 FILL_RADIUS = 8           # mci_field_masked_host: a top-level block that was not searched looks this far (Chebyshev, in blocks) for a searched one
 
 
@@ -155,13 +170,25 @@ def check_precision(precision, who):
     return precision
 
 
+def check_sampler(sampler, who):
+    if not isinstance(sampler, str) or sampler not in SAMPLERS:
+        raise ValueError("%s: sampler must be 'bilinear' or 'cubic', got %r" % (who, sampler))
+    return sampler
+
+
 def check_settings(background, mci_range, mci_border, resize_on, who="evaluate_from_folder", mci_precision="full", mci_person="keep",
-                   output_size="model"):
+                   output_size="model", mci_sampler="bilinear"):
     """The folder driver's background settings -> (levels, border) for the functions below.
+    mci_sampler: "bilinear" (the default) or "cubic" (sampler="cubic" of the mci_frames_*_host functions: sample_cubic in
+    place of sample_bilinear); checked here, and the caller's to pass on.
     mci_precision: "full" (the default) or "half" (mci_refine_host after the field, mci_frames_host(precision="half")); checked
     here, and the caller's to pass on.  mci_person: "keep" (the default) or "exclude" (mci_field_masked_host /
     mci_frames_masked_host with the key frames' human masks); refused with mci_precision="half" and with output_size="keyframes",
     which have no masked form yet."""
+    if not isinstance(mci_sampler, str) or mci_sampler not in SAMPLERS:
+        raise ValueError("%s: mci_sampler must be 'bilinear' or 'cubic', got %r" % (who, mci_sampler))
+    if background != "mci" and mci_sampler != "bilinear":
+        raise ValueError("%s: mci_sampler is a setting of background='mci'" % who)
     if not isinstance(mci_person, str) or mci_person not in PERSONS:
         raise ValueError("%s: mci_person must be 'keep' or 'exclude', got %r" % (who, mci_person))
     if background != "mci" and mci_person != "keep":
@@ -464,6 +491,91 @@ def sample_bilinear(img, py, px):
     return ((256 - fy) * ((256 - fx) * v[y0, x0] + fx * v[y0, x1]) + fy * ((256 - fx) * v[y1, x0] + fx * v[y1, x1]) + (1 << 15)) >> 16
 
 
+def cubic_weights():
+    """The Catmull-Rom (A = -1/2) tap weights of sample_cubic at t = f / 256, f = 0..255, in 1/128: int32 [256, 4], integers
+    only.  Numerators over 2 * 256^3: n0 = -f^3 + 512 f^2 - 65536 f, n1 = 3 f^3 - 1280 f^2 + 2 * 256^3,
+    n2 = -3 f^3 + 1024 f^2 + 65536 f, n3 = f^3 - 256 f^2; w_i = (n_i + 2^17) >> 18 (arithmetic shift); the residual
+    128 - sum(w) goes to w1 if w1 >= w2, else to w2.  Every row sums to 128, w[0] = (0, 128, 0, 0), w[128] = (-8, 72, 72, -8),
+    the values lie in -9..128, and w[256 - f] is w[f] reversed for every f in 1..255 (tests/test_mci_cubic_cpu.py asserts all of
+    it).  The kernels compute the same formula (csrc/mci.hip.h cubic_weight_row); there is no second table."""
+    f = np.arange(256, dtype=np.int64)
+    n = np.stack([-f ** 3 + 512 * f * f - 65536 * f, 3 * f ** 3 - 1280 * f * f + 2 * 256 ** 3,
+                  -3 * f ** 3 + 1024 * f * f + 65536 * f, f ** 3 - 256 * f * f], 1)
+    w = (n + (1 << 17)) >> 18
+    rest = 128 - w.sum(1)
+    first = w[:, 1] >= w[:, 2]
+    w[:, 1] += np.where(first, rest, 0)
+    w[:, 2] += np.where(first, 0, rest)
+    return w.astype(np.int32)
+
+
+_CUBIC_W = cubic_weights()
+
+
+def sample_cubic(img, py, px):
+    """img uint8 [H, W, 3] at positions (py, px) int32 [...] in 1/256 px -> int32 [..., 3] in 0..255: the 4x4 Catmull-Rom sample.
+    Tap rows (py >> 8) - 1 .. + 2 and tap columns (px >> 8) - 1 .. + 2, each clamped to the frame; wy = cubic_weights()[py & 255],
+    wx = cubic_weights()[px & 255]; per tap row h_r = sum_c wx[c] v[r][c], acc = sum_r wy[r] h_r, and the result is
+    clip((acc + 8192) >> 14, 0, 255) per channel (Catmull-Rom overshoots at strong edges; the clip is part of the definition).
+    int32 holds it: sum |w| <= 160 per axis (f = 128), so |h_r| <= 255 * 160 = 40800 and |acc| <= 255 * 160^2 = 6528000 < 2^23
+    (the taps' signs cannot all favour one side: the largest |acc| an image can reach is 255 * (144^2 + 16^2) = 5352960)."""
+    h, w = img.shape[:2]
+    y0, x0 = py >> SAMPLE_FRAC_BITS, px >> SAMPLE_FRAC_BITS
+    wy, wx = _CUBIC_W[py & 255], _CUBIC_W[px & 255]
+    v = img.astype(np.int32)
+    acc = 0
+    for r in range(4):
+        yr = np.clip(y0 - 1 + r, 0, h - 1)
+        hr = 0
+        for c in range(4):
+            hr = hr + wx[..., c, None] * v[yr, np.clip(x0 - 1 + c, 0, w - 1)]
+        acc = acc + wy[..., r, None] * hr
+    return np.clip((acc + (1 << 13)) >> 14, 0, 255)
+
+
+def sample_clean_cubic(mask, py, px):
+    """sample_clean for sample_cubic: bool [...], the positions whose 16 taps in `mask` (bool [H, W], set = excluded; rows and
+    columns clamped as sample_cubic clamps them) are all clear."""
+    h, w = mask.shape
+    y0, x0 = py >> SAMPLE_FRAC_BITS, px >> SAMPLE_FRAC_BITS
+    hit = False
+    for r in range(4):
+        yr = np.clip(y0 - 1 + r, 0, h - 1)
+        for c in range(4):
+            hit = hit | mask[yr, np.clip(x0 - 1 + c, 0, w - 1)]
+    return ~hit
+
+
+def cubic_tile_staged(pay, pax, pby, pbx):
+    """The staging rule of k_cubic_frames / k_cubic_scaled as a function of the sample positions alone: pay, pax (the sample of
+    key frame A) and pby, pbx (of B), int [H, W] in 1/256 px, of ONE output frame -> bool [H, ceil(W / 64)], True where the tile
+    (64 consecutive x of one row; the last may be short) reads its taps from the staged window, False where it gathers them
+    directly.  A tile is staged iff, for each key frame, the UNCLAMPED tap rows (p >> 8) - 1 .. + 2 of its pixels span at most
+    CUBIC_WIN_ROWS rows and the tap columns at most CUBIC_WIN_COLS columns.  The bytes do not depend on it."""
+    pay, pax, pby, pbx = (np.asarray(v) >> SAMPLE_FRAC_BITS for v in (pay, pax, pby, pbx))
+    H, W = pay.shape
+    tiles = (W + CUBIC_TILE - 1) // CUBIC_TILE
+    out = np.ones((H, tiles), bool)
+    for t in range(tiles):
+        sl = slice(t * CUBIC_TILE, min((t + 1) * CUBIC_TILE, W))
+        for ty, tx in ((pay, pax), (pby, pbx)):
+            out[:, t] &= (ty[:, sl].max(1) - ty[:, sl].min(1) + 4 <= CUBIC_WIN_ROWS) & (tx[:, sl].max(1) - tx[:, sl].min(1) + 4 <= CUBIC_WIN_COLS)
+    return out
+
+
+def sample_positions(field, sample_rate, k, height, width, precision="full", model_hw=None):
+    """(pay, pax, pby, pbx) int32 [h, w] of frame k as mci_frames_host computes them (model_hw given: as mci_frames_scaled_host
+    does for height x width key frames): the input of cubic_tile_staged."""
+    unit = 1 if check_precision(precision, "sample_positions") == "half" else 2
+    s, ls = int(sample_rate), log2_rate(sample_rate)
+    Dx, Dy = pixel_field(field, height, width) if model_hw is None else pixel_field_scaled(field, model_hw, (height, width))
+    Y, X = np.mgrid[0:height, 0:width]
+    Y, X = (Y << SAMPLE_FRAC_BITS).astype(np.int32), (X << SAMPLE_FRAC_BITS).astype(np.int32)
+    ax, ay = (unit * k * Dx + s // 2) >> ls, (unit * k * Dy + s // 2) >> ls
+    bx, by = (unit * (s - k) * Dx + s // 2) >> ls, (unit * (s - k) * Dy + s // 2) >> ls
+    return Y - ay, X - ax, Y + by, X + bx
+
+
 def log2_rate(sample_rate):
     s = int(sample_rate)
     if s < 1 or s > MAX_SAMPLE_RATE or s & (s - 1):
@@ -476,13 +588,16 @@ def sample_valid(py, px, height, width):
     return (py >= 0) & (py <= (height - 1) << SAMPLE_FRAC_BITS) & (px >= 0) & (px <= (width - 1) << SAMPLE_FRAC_BITS)
 
 
-def mci_frames_host(a_u8, b_u8, field, sample_rate, ks, border="clamp", precision="full"):
+def mci_frames_host(a_u8, b_u8, field, sample_rate, ks, border="clamp", precision="full", sampler="bilinear"):
     """Frames ks (each 0 <= k <= sample_rate; k = 0 is A, k = sample_rate is B) of the segment between the key frames a_u8 and
     b_u8 (uint8 [H, W, 3]) from their block field (mci_field_host) -> uint8 [len(ks), H, W, 3].  border="valid": where exactly
     one of a pixel's two samples lies inside the frame the output is that sample alone.  precision="half": the field is
-    mci_refine_host's, in half pixels - the offsets are k Dh / s and (s-k) Dh / s in place of 2k D / s and 2(s-k) D / s."""
+    mci_refine_host's, in half pixels - the offsets are k Dh / s and (s-k) Dh / s in place of 2k D / s and 2(s-k) D / s.
+    sampler="cubic": sample_cubic in place of sample_bilinear and nothing else - the offsets, the blend, the border rule
+    (sample_valid: the POSITION lies inside the frame; taps beyond the edge clamp) and k = 0, k = s are unchanged."""
     check_border(border, "mci_frames_host")
     unit = 1 if check_precision(precision, "mci_frames_host") == "half" else 2
+    sample = sample_cubic if check_sampler(sampler, "mci_frames_host") == "cubic" else sample_bilinear
     a_u8, b_u8, field = np.asarray(a_u8), np.asarray(b_u8), np.asarray(field)
     if a_u8.dtype != np.uint8 or a_u8.ndim != 3 or a_u8.shape[2] != 3 or a_u8.shape != b_u8.shape or b_u8.dtype != np.uint8:
         raise ValueError("mci_frames_host: two uint8 [H, W, 3] frames of one size, got %s and %s" % (a_u8.shape, b_u8.shape))
@@ -498,8 +613,8 @@ def mci_frames_host(a_u8, b_u8, field, sample_rate, ks, border="clamp", precisio
             raise ValueError("mci_frames_host: frame %d is outside the segment 0..%d" % (k, s))
         ax, ay = (unit * k * Dx + s // 2) >> ls, (unit * k * Dy + s // 2) >> ls
         bx, by = (unit * (s - k) * Dx + s // 2) >> ls, (unit * (s - k) * Dy + s // 2) >> ls
-        a = sample_bilinear(a_u8, Y - ay, X - ax)
-        b = sample_bilinear(b_u8, Y + by, X + bx)
+        a = sample(a_u8, Y - ay, X - ax)
+        b = sample(b_u8, Y + by, X + bx)
         o = ((s - k) * a + k * b + s // 2) >> ls
         if border == "valid":
             oka, okb = sample_valid(Y - ay, X - ax, H, W)[..., None], sample_valid(Y + by, X + bx, H, W)[..., None]
@@ -645,12 +760,15 @@ def sample_clean(mask, py, px):
     return ~(mask[y0, x0] | mask[y0, x1] | mask[y1, x0] | mask[y1, x1])
 
 
-def mci_frames_masked_host(a_u8, b_u8, ma, mb, field, sample_rate, ks, border="clamp", precision="full"):
+def mci_frames_masked_host(a_u8, b_u8, ma, mb, field, sample_rate, ks, border="clamp", precision="full", sampler="bilinear"):
     """mci_frames_host with the person kept out: a sample is clean iff the border rule calls it valid (clamp: always) and
     sample_clean holds in its key frame's mask; where exactly one of a pixel's two samples is clean the output is that sample
-    alone, otherwise the blend.  k = 0 and k = sample_rate stay A and B.  -> uint8 [len(ks), H, W, 3]."""
+    alone, otherwise the blend.  k = 0 and k = sample_rate stay A and B.  -> uint8 [len(ks), H, W, 3].  sampler="cubic":
+    sample_cubic, and a sample is clean iff all 16 of its taps are clear (sample_clean_cubic)."""
     check_border(border, "mci_frames_masked_host")
     unit = 1 if check_precision(precision, "mci_frames_masked_host") == "half" else 2
+    sample = sample_cubic if check_sampler(sampler, "mci_frames_masked_host") == "cubic" else sample_bilinear
+    clean = sample_clean_cubic if sampler == "cubic" else sample_clean
     a_u8, b_u8, field = np.asarray(a_u8), np.asarray(b_u8), np.asarray(field)
     if a_u8.dtype != np.uint8 or a_u8.ndim != 3 or a_u8.shape[2] != 3 or a_u8.shape != b_u8.shape or b_u8.dtype != np.uint8:
         raise ValueError("mci_frames_masked_host: two uint8 [H, W, 3] frames of one size, got %s and %s" % (a_u8.shape, b_u8.shape))
@@ -667,10 +785,10 @@ def mci_frames_masked_host(a_u8, b_u8, ma, mb, field, sample_rate, ks, border="c
             raise ValueError("mci_frames_masked_host: frame %d is outside the segment 0..%d" % (k, s))
         ax, ay = (unit * k * Dx + s // 2) >> ls, (unit * k * Dy + s // 2) >> ls
         bx, by = (unit * (s - k) * Dx + s // 2) >> ls, (unit * (s - k) * Dy + s // 2) >> ls
-        a = sample_bilinear(a_u8, Y - ay, X - ax)
-        b = sample_bilinear(b_u8, Y + by, X + bx)
+        a = sample(a_u8, Y - ay, X - ax)
+        b = sample(b_u8, Y + by, X + bx)
         o = ((s - k) * a + k * b + s // 2) >> ls
-        oka, okb = sample_clean(ma, Y - ay, X - ax), sample_clean(mb, Y + by, X + bx)
+        oka, okb = clean(ma, Y - ay, X - ax), clean(mb, Y + by, X + bx)
         if border == "valid":
             oka, okb = oka & sample_valid(Y - ay, X - ax, H, W), okb & sample_valid(Y + by, X + bx, H, W)
         oka, okb = oka[..., None], okb[..., None]
@@ -719,7 +837,7 @@ def pixel_field_scaled(field, model_hw, out_hw):
     return dsx, dsy
 
 
-def mci_frames_scaled_host(a0_u8, b0_u8, field, model_hw, sample_rate, ks, border="clamp", precision="full"):
+def mci_frames_scaled_host(a0_u8, b0_u8, field, model_hw, sample_rate, ks, border="clamp", precision="full", sampler="bilinear"):
     """mci_frames_host at the key frames' OWN size: "field at the model size, samples at the key frames' size".  a0_u8, b0_u8
     uint8 [h0, w0, 3] are the key frame files' pixels, field the int16 [Hb, Wb, 2] block field of the model-size key frames
     (mci_field_host / mci_refine_host of the H x W frames, model_hw = (H, W)) -> uint8 [len(ks), h0, w0, 3].  Per output pixel
@@ -731,9 +849,10 @@ def mci_frames_scaled_host(a0_u8, b0_u8, field, model_hw, sample_rate, ks, borde
       4  mci_frames_host's lines with DSx, DSy, h0, w0: offsets (unit k DS + s/2) >> log2 s, sample_bilinear, the blend, and under
          border="valid" sample_valid in output coordinates.
     With (h0, w0) == (H, W) it is mci_frames_host, byte for byte.  The sides lie in 1..16384 and within a factor 16 of the
-    model's (the largest unit * k * DS then stays below 2^31)."""
+    model's (the largest unit * k * DS then stays below 2^31).  sampler="cubic": sample_cubic in step 4, nothing else."""
     check_border(border, "mci_frames_scaled_host")
     unit = 1 if check_precision(precision, "mci_frames_scaled_host") == "half" else 2
+    sample = sample_cubic if check_sampler(sampler, "mci_frames_scaled_host") == "cubic" else sample_bilinear
     a0_u8, b0_u8, field = np.asarray(a0_u8), np.asarray(b0_u8), np.asarray(field)
     if a0_u8.dtype != np.uint8 or a0_u8.ndim != 3 or a0_u8.shape[2] != 3 or a0_u8.shape != b0_u8.shape or b0_u8.dtype != np.uint8:
         raise ValueError("mci_frames_scaled_host: two uint8 [h0, w0, 3] frames of one size, got %s and %s" % (a0_u8.shape, b0_u8.shape))
@@ -749,8 +868,8 @@ def mci_frames_scaled_host(a0_u8, b0_u8, field, model_hw, sample_rate, ks, borde
             raise ValueError("mci_frames_scaled_host: frame %d is outside the segment 0..%d" % (k, s))
         ax, ay = (unit * k * Dx + s // 2) >> ls, (unit * k * Dy + s // 2) >> ls
         bx, by = (unit * (s - k) * Dx + s // 2) >> ls, (unit * (s - k) * Dy + s // 2) >> ls
-        a = sample_bilinear(a0_u8, Y - ay, X - ax)
-        b = sample_bilinear(b0_u8, Y + by, X + bx)
+        a = sample(a0_u8, Y - ay, X - ax)
+        b = sample(b0_u8, Y + by, X + bx)
         o = ((s - k) * a + k * b + s // 2) >> ls
         if border == "valid":
             oka, okb = sample_valid(Y - ay, X - ax, h0, w0)[..., None], sample_valid(Y + by, X + bx, h0, w0)[..., None]

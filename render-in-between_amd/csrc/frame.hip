@@ -759,4 +759,130 @@ int rib_scaled_frames(rib_handle* handle, int T, int B, int H, int W, int H0, in
   HIP_TRY(h, hipGetLastError());
   return RIB_OK;
 }
+
+// rib_cubic_frames / rib_cubic_scaled: the 4x4 cubic sampler (background.sample_cubic) behind rib_mci_frames' / rib_halfpel_frames' /
+// rib_masked_frames' and rib_scaled_frames' contracts.  The dynamic LDS is the output row, [the blended field row,] the 2 KB weight
+// table and - staging = 0 - the four waves' windows; beyond 64 KB (rows wider than about 11 000 pixels) the kernel is told so.
+extern "C++" {
+namespace {
+template <typename K, typename P>
+static hipError_t cubic_launch(K kernel, dim3 grid, size_t lds, hipStream_t st, const P& params) {
+  if (lds > 65536) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, params);
+  return hipGetLastError();
+}
+}  // namespace
+}  // extern "C++"
+
+int rib_cubic_frames(rib_handle* handle, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const uint8_t* ma_u8,
+                     const uint8_t* mb_u8, const int16_t* field_i16, int sample_rate, int k_first, int border, int precision, int staging,
+                     float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream) {
+  static const char who[] = "rib_cubic_frames";
+  FrameState* h = frame_state(handle);
+  if (!h) return RIB_ERR_INVALID;
+  if (h->device < 0) return fail(h, RIB_ERR_INVALID, fmt("%s: host-only handle", who));
+  if (!a_u8 || !b_u8 || !field_i16) return fail(h, RIB_ERR_INVALID, fmt("%s: null pointer", who));
+  if ((ma_u8 == nullptr) != (mb_u8 == nullptr))
+    return fail(h, RIB_ERR_INVALID, fmt("%s: exactly one mask is null (both: the person is excluded; neither: kept)", who));
+  if (!out_f32_nchw && !out_u8_nhwc) return fail(h, RIB_ERR_INVALID, fmt("%s: both outputs are null", who));
+  MciLayout L;
+  if (T < 1 || !mci_layout(B, H, W, MCI_MIN_LEVELS, &L) || (size_t)T * B > 65535)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: T=%d B=%d H=%d W=%d: T, B >= 1, T * B <= 65535, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", who, T, B, H, W, MCI_MAX_SIDE));
+  if (sample_rate < 1 || sample_rate > MCI_MAX_RATE || (sample_rate & (sample_rate - 1)) != 0)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: sample_rate=%d: a power of two in 1..%d", who, sample_rate, MCI_MAX_RATE));
+  if (k_first < 0 || k_first + T - 1 > sample_rate)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: frames %d..%d are outside the segment 0..%d", who, k_first, k_first + T - 1, sample_rate));
+  if (border != 0 && border != 1)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: border=%d: 0 (clamped samples) or 1 (valid samples only)", who, border));
+  if (precision != 0 && precision != 1)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: precision=%d: 0 (the field in whole pixels) or 1 (in half pixels)", who, precision));
+  if (staging != 0 && staging != 1)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: staging=%d: 0 (the per-tile rule) or 1 (never stage: a diagnostic)", who, staging));
+  if ((reinterpret_cast<uintptr_t>(field_i16) & 1) != 0 || (reinterpret_cast<uintptr_t>(out_f32_nchw) & 3) != 0)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: misaligned pointer", who));
+  CubicFramesParams fp;
+  fp.a = a_u8; fp.b = b_u8; fp.ma = ma_u8; fp.mb = mb_u8; fp.field = field_i16; fp.out_f32 = out_f32_nchw; fp.out_u8 = out_u8_nhwc;
+  fp.T = T; fp.B = B; fp.H = H; fp.W = W; fp.Hb = L.Hb[0]; fp.Wb = L.Wb[0]; fp.s = sample_rate; fp.k_first = k_first;
+  fp.ls = 0;
+  while ((1 << fp.ls) < sample_rate) ++fp.ls;
+  fp.stage = staging == 0 ? 1 : 0;
+  fp.w_off = out_u8_nhwc ? (W * 3 + 32 + 15) & ~15 : 0;
+  const size_t lds = (size_t)fp.w_off + CUBIC_WTAB_BYTES + (fp.stage ? CUBIC_WIN_BYTES : 0);
+  HIP_TRY(h, hipSetDevice(h->device));
+  const dim3 grid(H, T * B);
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  const int variant = (ma_u8 ? 4 : 0) | (precision ? 2 : 0) | (border ? 1 : 0);
+  hipError_t e = hipSuccess;
+  switch (variant) {
+    case 0: e = cubic_launch(k_cubic_frames<false, false, false>, grid, lds, st, fp); break;
+    case 1: e = cubic_launch(k_cubic_frames<true, false, false>, grid, lds, st, fp); break;
+    case 2: e = cubic_launch(k_cubic_frames<false, true, false>, grid, lds, st, fp); break;
+    case 3: e = cubic_launch(k_cubic_frames<true, true, false>, grid, lds, st, fp); break;
+    case 4: e = cubic_launch(k_cubic_frames<false, false, true>, grid, lds, st, fp); break;
+    case 5: e = cubic_launch(k_cubic_frames<true, false, true>, grid, lds, st, fp); break;
+    case 6: e = cubic_launch(k_cubic_frames<false, true, true>, grid, lds, st, fp); break;
+    default: e = cubic_launch(k_cubic_frames<true, true, true>, grid, lds, st, fp); break;
+  }
+  HIP_TRY(h, e);
+  return RIB_OK;
+}
+
+int rib_cubic_scaled(rib_handle* handle, int T, int B, int H, int W, int H0, int W0, const uint8_t* a0_u8, const uint8_t* b0_u8,
+                     const int16_t* field_i16, int sample_rate, int k_first, int border, int precision, int staging, uint8_t* out_u8_nhwc,
+                     void* hip_stream) {
+  static const char who[] = "rib_cubic_scaled";
+  constexpr int MAX_RATIO = 16;             // background.SCALED_MAX_RATIO
+  FrameState* h = frame_state(handle);
+  if (!h) return RIB_ERR_INVALID;
+  if (h->device < 0) return fail(h, RIB_ERR_INVALID, fmt("%s: host-only handle", who));
+  if (!a0_u8 || !b0_u8 || !field_i16 || !out_u8_nhwc) return fail(h, RIB_ERR_INVALID, fmt("%s: null pointer", who));
+  MciLayout L;
+  if (T < 1 || !mci_layout(B, H, W, MCI_MIN_LEVELS, &L) || (size_t)T * B > 65535)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: T=%d B=%d H=%d W=%d: T, B >= 1, T * B <= 65535, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", who, T, B, H, W, MCI_MAX_SIDE));
+  if (H0 < 1 || W0 < 1 || H0 > MCI_MAX_SIDE || W0 > MCI_MAX_SIDE)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: H0=%d W0=%d: the key frames' sides lie in 1..%d", who, H0, W0, MCI_MAX_SIDE));
+  if (W0 > MAX_RATIO * W || W > MAX_RATIO * W0 || H0 > MAX_RATIO * H || H > MAX_RATIO * H0)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: key frames %dx%d, model %dx%d: each axis within 1/%d .. %d times the model's", who, H0, W0, H, W, MAX_RATIO, MAX_RATIO));
+  if (sample_rate < 1 || sample_rate > MCI_MAX_RATE || (sample_rate & (sample_rate - 1)) != 0)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: sample_rate=%d: a power of two in 1..%d", who, sample_rate, MCI_MAX_RATE));
+  if (k_first < 0 || k_first + T - 1 > sample_rate)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: frames %d..%d are outside the segment 0..%d", who, k_first, k_first + T - 1, sample_rate));
+  if (border != 0 && border != 1)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: border=%d: 0 (clamped samples) or 1 (valid samples only)", who, border));
+  if (precision != 0 && precision != 1)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: precision=%d: 0 (the field in pixels) or 1 (in half pixels)", who, precision));
+  if (staging != 0 && staging != 1)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: staging=%d: 0 (the per-tile rule) or 1 (never stage: a diagnostic)", who, staging));
+  if ((reinterpret_cast<uintptr_t>(field_i16) & 1) != 0) return fail(h, RIB_ERR_INVALID, fmt("%s: misaligned pointer", who));
+  CubicScaledParams cp;
+  ScaledFramesParams& fp = cp.f;
+  fp.a = a0_u8; fp.b = b0_u8; fp.field = field_i16; fp.out = out_u8_nhwc;
+  fp.T = T; fp.B = B; fp.H0 = H0; fp.W0 = W0; fp.Hb = L.Hb[0]; fp.Wb = L.Wb[0]; fp.s = sample_rate; fp.k_first = k_first;
+  fp.ls = 0;
+  while ((1 << fp.ls) < sample_rate) ++fp.ls;
+  fp.sx = (int)(((int64_t)W0 * 65536 + W / 2) / W); fp.sy = (int)(((int64_t)H0 * 65536 + H / 2) / H);
+  fp.qax = 32 * W / W0; fp.rax = 32 * W % W0; fp.q0x = 16 * W / W0; fp.r0x = 16 * W % W0;
+  fp.qay = 32 * H / H0; fp.ray = 32 * H % H0; fp.q0y = 16 * H / H0; fp.r0y = 16 * H % H0;
+  fp.vec = 0;
+  fp.v_off = (W0 * 3 + 31) & ~15;           // the row at any shift 0..15, whole 16-byte lines
+  fp.stage = 1;                             // the blended field row always has room: at most 49 168 + 16 384 + 2 048 + 29 184 bytes of the CU's 160 KB
+  cp.w_off = fp.v_off + ((fp.Wb * (int)sizeof(int2) + 15) & ~15);
+  cp.stage_win = staging == 0 ? 1 : 0;
+  const size_t lds = (size_t)cp.w_off + CUBIC_WTAB_BYTES + (cp.stage_win ? CUBIC_WIN_BYTES : 0);
+  HIP_TRY(h, hipSetDevice(h->device));
+  const dim3 grid(H0, T * B);
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  hipError_t e = hipSuccess;
+  switch ((precision ? 2 : 0) | (border ? 1 : 0)) {
+    case 0: e = cubic_launch(k_cubic_scaled<false, false>, grid, lds, st, cp); break;
+    case 1: e = cubic_launch(k_cubic_scaled<true, false>, grid, lds, st, cp); break;
+    case 2: e = cubic_launch(k_cubic_scaled<false, true>, grid, lds, st, cp); break;
+    default: e = cubic_launch(k_cubic_scaled<true, true>, grid, lds, st, cp); break;
+  }
+  HIP_TRY(h, e);
+  return RIB_OK;
+}
 }  // extern "C"

@@ -75,6 +75,9 @@
 //   k_mci_frames<VALID, HALF, MASKED = true>  four byte gathers per sample in its key frame's mask (mci_sample's clamps) and one
 //                       more term in VALID's select: clean = valid under the border rule and all four taps clear; k = 0 and k = s
 //                       stay A and B.
+//
+// The 4x4 cubic sampler (rib_cubic_frames / rib_cubic_scaled; background.sample_cubic, the driver's mci_sampler="cubic"): k_cubic_frames
+// and k_cubic_scaled at the end of this file, kernels of their own beside k_mci_frames and k_scaled_frames, which are not touched.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -751,6 +754,334 @@ __global__ __launch_bounds__(256) void k_scaled_frames(ScaledFramesParams p) {
       for (int kk = max(lo, shift); kk < min(lo + 16, shift + rowbytes); ++kk) gline[kk] = s_mci[kk];
     }
   }
+}
+
+// ---- 4x4 cubic sampling (rib_cubic_frames / rib_cubic_scaled; background.sample_cubic, the driver's mci_sampler="cubic") ------------
+// New kernels beside k_mci_frames / k_scaled_frames, which are not touched.  Same grids (one workgroup per output row), same field
+// arithmetic, same blend and border rule, same LDS scheme for the uint8 output row; what differs is the sample - 16 taps per key
+// frame, Catmull-Rom weights in 1/128 per axis (background.cubic_weights) - and how the taps are fetched:
+//   tile      64 consecutive x of the row, one wave, one pixel per lane (a row's tiles go round the workgroup's four waves).  Every
+//             lane first has its two sample positions in registers; the wave reduces min and max of the integer tap coordinates
+//             per key frame (packed int16 pairs, DPP row operations: no LDS traffic).
+//   staged    both bounding boxes fit CUBIC_WIN_ROWS x CUBIC_WIN_COLS (background.cubic_tile_staged states the rule): the wave
+//             copies the boxes into its own LDS windows, one RGBX dword per pixel, lanes along x so a row's loads are consecutive -
+//             one dword load per pixel (the three bytes and a neighbour's, from the byte before: packed RGB has no alignment to
+//             offer), clamped while staging, MASKED: the mask byte in X.  A tap is then one aligned ds_read_b32, and "all 16 taps
+//             clear" is the OR of the X bytes.  Only the box is staged, not the whole window: at rest 4 x 67 pixels per key frame,
+//             five loads per lane where the direct path issues 32 (a 16-bit and an 8-bit gather per tap).
+//   direct    otherwise (or staging = 1): the definition, tap by tap, three byte gathers each.
+//   Both paths live in one kernel and a launch mixes them tile by tile: the choice is uniform per wave, the window is the wave's
+//   own (written and read by the same wave, fenced at wavefront scope), and the only workgroup barriers - after the weight table,
+//   before the row's write-out - are reached by every thread.
+//   weights   a 2 KB LDS table (256 x 4 int16) filled at kernel start by the integer formula of background.cubic_weights.
+constexpr int CUBIC_TILE = 64, CUBIC_WIN_ROWS = 12, CUBIC_WIN_COLS = 76;      // background.py CUBIC_TILE, CUBIC_WIN_ROWS, CUBIC_WIN_COLS
+constexpr int CUBIC_WIN = CUBIC_WIN_ROWS * CUBIC_WIN_COLS;                    // dwords of one key frame's window
+constexpr int CUBIC_WTAB_BYTES = 256 * 4 * (int)sizeof(int16_t);
+constexpr int CUBIC_WIN_BYTES = 4 * 2 * CUBIC_WIN * (int)sizeof(uint32_t);    // four waves, two key frames each: 29 184
+constexpr uint32_t CUBIC_CLEAN = 0xff000000u;      // a staged or gathered tap's X byte: nonzero = excluded (MASKED), else 0
+
+typedef short cubic_w4 __attribute__((ext_vector_type(4)));
+typedef short cubic_s2 __attribute__((ext_vector_type(2)));
+
+// background.cubic_weights' row f
+__device__ inline cubic_w4 cubic_weight_row(int f) {
+  const int f2 = f * f, f3 = f2 * f;
+  int w0 = (-f3 + 512 * f2 - 65536 * f + (1 << 17)) >> 18;
+  int w1 = (3 * f3 - 1280 * f2 + 2 * 256 * 256 * 256 + (1 << 17)) >> 18;
+  int w2 = (-3 * f3 + 1024 * f2 + 65536 * f + (1 << 17)) >> 18;
+  int w3 = (f3 - 256 * f2 + (1 << 17)) >> 18;
+  const int rest = 128 - (w0 + w1 + w2 + w3);
+  if (w1 >= w2) w1 += rest; else w2 += rest;
+  cubic_w4 w;
+  w.x = (short)w0; w.y = (short)w1; w.z = (short)w2; w.w = (short)w3;
+  return w;
+}
+
+__device__ inline int cubic_pack(int lo, int hi) { return (int)(((uint32_t)lo & 0xffffu) | ((uint32_t)hi << 16)); }
+__device__ inline int cubic_pkmin(int a, int b) {
+  return __builtin_bit_cast(int, __builtin_elementwise_min(__builtin_bit_cast(cubic_s2, a), __builtin_bit_cast(cubic_s2, b)));
+}
+template <int CTRL, int ROWS>
+__device__ inline int cubic_dpp(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, ROWS, 0xf, false); }
+// the minimum of both int16 halves over the 64 lanes of a full wave
+__device__ inline int cubic_wave_pkmin(int v) {
+  v = cubic_pkmin(v, cubic_dpp<0xB1, 0xf>(v));      // quad_perm:[1,0,3,2]
+  v = cubic_pkmin(v, cubic_dpp<0x4E, 0xf>(v));      // quad_perm:[2,3,0,1]
+  v = cubic_pkmin(v, cubic_dpp<0x141, 0xf>(v));     // row_half_mirror
+  v = cubic_pkmin(v, cubic_dpp<0x140, 0xf>(v));     // row_mirror: every row of 16 holds its minimum
+  v = cubic_pkmin(v, cubic_dpp<0x142, 0xa>(v));     // row_bcast:15 into rows 1 and 3
+  v = cubic_pkmin(v, cubic_dpp<0x143, 0xc>(v));     // row_bcast:31 into rows 2 and 3: lane 63 holds the wave's
+  return __builtin_amdgcn_readlane(v, 63);
+}
+
+// pixel (y, x), inside the frame, as R | G << 8 | B << 16 and, MASKED, (mask != 0) << 24
+template <bool MASKED>
+__device__ inline uint32_t cubic_gather(const uint8_t* img, const uint8_t* msk, int W, int y, int x) {
+  const int i = __mul24(y, W) + x;          // y, W <= 16384: the product fits 24-bit operands, a frame's 3 i stays below 2^30
+  const uint8_t* q = img + (uint32_t)(3 * i);
+  uint32_t v = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16);
+  if constexpr (MASKED) v |= (uint32_t)(msk[i] != 0) << 24;
+  return v;
+}
+// the same value by ONE load: the dword that starts a byte early (the frame's first pixel has no byte before it)
+template <bool MASKED>
+__device__ inline uint32_t cubic_load(const uint8_t* img, const uint8_t* msk, int W, int y, int x) {
+  const int i = __mul24(y, W) + x;
+  if (i == 0) return cubic_gather<MASKED>(img, msk, W, y, x);
+  uint32_t v;
+  __builtin_memcpy(&v, img + (uint32_t)(3 * i - 1), 4);
+  v >>= 8;
+  if constexpr (MASKED) v |= (uint32_t)(msk[i] != 0) << 24;
+  return v;
+}
+
+// one tap row: acc[c] += wy * sum_j wx[j] * channel c of t[j].  Every factor fits 24 bits (|w| <= 128, a byte, |h| <= 40800): __mul24 is the
+// full-rate multiply where the plain one compiled to v_mul_lo_u32, a quarter of the rate
+__device__ inline void cubic_row(const uint32_t t[4], cubic_w4 wx, int wy, int acc[3]) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int h = __mul24(wx.x, (int)((t[0] >> (8 * c)) & 255)) + __mul24(wx.y, (int)((t[1] >> (8 * c)) & 255)) +
+                  __mul24(wx.z, (int)((t[2] >> (8 * c)) & 255)) + __mul24(wx.w, (int)((t[3] >> (8 * c)) & 255));
+    acc[c] += __mul24(wy, h);
+  }
+}
+
+struct CubicKey {                           // one key frame of one batch item
+  const uint8_t *img, *msk;                 // [H, W, 3]; MASKED: [H, W], nonzero = excluded
+  int py, px;                               // this lane's sample position, 1/256 px
+};
+
+// the wave's two cubic samples (background.sample_cubic) of a tile: v[f][c], and clean[f] = all 16 taps clear (MASKED).  Every
+// lane of the wave is here (a lane beyond the row's end brings a neighbour's positions); `win` is this wave's 2 * CUBIC_WIN dwords,
+// used when may_stage and the rule holds.
+template <bool MASKED>
+__device__ inline void cubic_samples(CubicKey key[2], int H, int W, bool may_stage, uint32_t* win, const cubic_w4* wtab, int lane, int v[2][3],
+                                     bool clean[2]) {
+  int ty[2], tx[2], lo[2], hi[2];
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    ty[f] = key[f].py >> 8; tx[f] = key[f].px >> 8;
+    lo[f] = cubic_wave_pkmin(cubic_pack(ty[f], tx[f]));
+    hi[f] = cubic_wave_pkmin(cubic_pack(-ty[f], -tx[f]));
+  }
+  int ymin[2], xmin[2], nrows[2], ncols[2];
+  bool staged = may_stage;
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    ymin[f] = (int16_t)(lo[f] & 0xffff); xmin[f] = lo[f] >> 16;
+    nrows[f] = -(int)(int16_t)(hi[f] & 0xffff) - ymin[f] + 4; ncols[f] = -(hi[f] >> 16) - xmin[f] + 4;
+    staged = staged && nrows[f] <= CUBIC_WIN_ROWS && ncols[f] <= CUBIC_WIN_COLS;      // (uniform per wave: lo, hi are readlane results)
+  }
+  if (staged) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // the previous tile's reads of the window are done
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int f = 0; f < 2; ++f) {
+      const int n = nrows[f] * ncols[f], inv = ((1 << 20) + ncols[f] - 1) / ncols[f];      // e / ncols = e * inv >> 20 for e < 912
+      uint32_t* w = win + f * CUBIC_WIN;
+      for (int e = lane; e < n; e += CUBIC_TILE) {
+        const int r = __mul24(e, inv) >> 20, c = e - __mul24(r, ncols[f]);
+        const int y = min(max(ymin[f] - 1 + r, 0), H - 1), x = min(max(xmin[f] - 1 + c, 0), W - 1);
+        w[r * CUBIC_WIN_COLS + c] = cubic_load<MASKED>(key[f].img, key[f].msk, W, y, x);
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // a lane reads what other lanes of its wave wrote
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    const cubic_w4 wy = wtab[key[f].py & 255], wx = wtab[key[f].px & 255];
+    const int wyr[4] = {wy.x, wy.y, wy.z, wy.w};
+    int acc[3] = {0, 0, 0};
+    uint32_t any = 0;
+    if (staged) {
+      const uint32_t* w = win + f * CUBIC_WIN + (ty[f] - ymin[f]) * CUBIC_WIN_COLS + (tx[f] - xmin[f]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const uint32_t t[4] = {w[r * CUBIC_WIN_COLS], w[r * CUBIC_WIN_COLS + 1], w[r * CUBIC_WIN_COLS + 2], w[r * CUBIC_WIN_COLS + 3]};
+        any |= t[0] | t[1] | t[2] | t[3];
+        cubic_row(t, wx, wyr[r], acc);
+      }
+    } else {
+      int xs[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) xs[c] = min(max(tx[f] - 1 + c, 0), W - 1);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int y = min(max(ty[f] - 1 + r, 0), H - 1);
+        uint32_t t[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) t[c] = cubic_gather<MASKED>(key[f].img, key[f].msk, W, y, xs[c]);
+        any |= t[0] | t[1] | t[2] | t[3];
+        cubic_row(t, wx, wyr[r], acc);
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[f][c] = min(max((acc[c] + (1 << 13)) >> 14, 0), 255);
+    clean[f] = !(any & CUBIC_CLEAN);
+  }
+}
+
+struct CubicFramesParams {
+  const uint8_t *a, *b;                     // [B, H, W, 3]
+  const uint8_t *ma, *mb;                   // MASKED only: [B, H, W], nonzero = excluded
+  const int16_t* field;                     // [B, Hb, Wb, 2]
+  float* out_f32;                           // [T, B, 3, H, W] or null
+  uint8_t* out_u8;                          // [T, B, H, W, 3] or null
+  int T, B, H, W, Hb, Wb, s, ls, k_first;
+  int stage;                                // 1: the windows exist and a tile that fits is staged; 0: every tile gathers (rib.h `staging` = 1)
+  int w_off;                                // byte offset of the weight table in the dynamic LDS (a multiple of 16); the windows follow it
+};
+
+// the switch of k_mci_frames: where exactly one of the two samples is ok the output is that sample, otherwise the blend
+__device__ inline void cubic_blend(const int v[2][3], bool oka, bool okb, int k, int s, int ls, uint8_t q[3]) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int blend = (__mul24(s - k, v[0][c]) + __mul24(k, v[1][c]) + (s >> 1)) >> ls;      // s <= 1024, a byte
+    q[c] = (uint8_t)(oka == okb ? blend : oka ? v[0][c] : v[1][c]);
+  }
+}
+
+// the uint8 row from LDS as 16-byte stores contiguous across the workgroup (k_mci_frames' scheme)
+__device__ inline void cubic_store_row(const uint8_t* lds, uint8_t* grow, int shift, int rowbytes) {
+  const int nlines = (shift + rowbytes + 15) >> 4;
+  uint8_t* gline = grow - shift;            // 16-byte aligned; only bytes [shift, shift + rowbytes) are this row's
+  for (int j = threadIdx.x; j < nlines; j += 256) {
+    const int lo = j * 16;
+    if (lo >= shift && lo + 16 <= shift + rowbytes) {
+      *reinterpret_cast<uint4*>(gline + lo) = reinterpret_cast<const uint4*>(lds)[j];
+    } else {
+      for (int kk = max(lo, shift); kk < min(lo + 16, shift + rowbytes); ++kk) gline[kk] = lds[kk];
+    }
+  }
+}
+
+template <bool VALID = false, bool HALF = false, bool MASKED = false>
+__global__ __launch_bounds__(256) void k_cubic_frames(CubicFramesParams p) {
+  constexpr int UNIT = HALF ? 1 : 2;
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_mci[];
+  const int y = blockIdx.x, tb = blockIdx.y, t = tb / p.B, bi = tb - t * p.B;
+  const int H = p.H, W = p.W, k = p.k_first + t, s = p.s, ls = p.ls;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int rowbytes = W * 3;
+  uint8_t* grow = p.out_u8 ? p.out_u8 + ((size_t)tb * H + y) * (size_t)rowbytes : nullptr;
+  const int shift = (int)(reinterpret_cast<uintptr_t>(grow) & 15);
+  uint8_t* srow = s_mci + shift;
+  cubic_w4* wtab = reinterpret_cast<cubic_w4*>(s_mci + p.w_off);
+  uint32_t* win = reinterpret_cast<uint32_t*>(s_mci + p.w_off + CUBIC_WTAB_BYTES) + wave * 2 * CUBIC_WIN;
+  wtab[threadIdx.x] = cubic_weight_row(threadIdx.x);
+  __syncthreads();
+  const size_t HW = (size_t)H * W;
+  const uint8_t* A = p.a + (size_t)bi * HW * 3;
+  const uint8_t* Bf = p.b + (size_t)bi * HW * 3;
+  const uint8_t* MA = MASKED ? p.ma + (size_t)bi * HW : nullptr;
+  const uint8_t* MB = MASKED ? p.mb + (size_t)bi * HW : nullptr;
+  const int16_t* fld = p.field + (size_t)bi * p.Hb * p.Wb * 2;
+  const int tyy = 2 * y - (MCI_BLOCK - 1), fy = tyy & 15;
+  const int r0 = min(max(tyy >> 4, 0), p.Hb - 1), r1 = min(max((tyy >> 4) + 1, 0), p.Hb - 1);
+  const int ntiles = (W + CUBIC_TILE - 1) / CUBIC_TILE;
+  for (int tile = wave; tile < ntiles; tile += 4) {      // (uniform per wave: every lane of the wave is in cubic_samples)
+    const int xo = tile * CUBIC_TILE + lane, x = min(xo, W - 1);
+    const int txx = 2 * x - (MCI_BLOCK - 1), fx = txx & 15;
+    const int c0 = min(max(txx >> 4, 0), p.Wb - 1), c1 = min(max((txx >> 4) + 1, 0), p.Wb - 1);
+    const int16_t *f00 = fld + (r0 * p.Wb + c0) * 2, *f01 = fld + (r0 * p.Wb + c1) * 2;
+    const int16_t *f10 = fld + (r1 * p.Wb + c0) * 2, *f11 = fld + (r1 * p.Wb + c1) * 2;
+    const int Dx = (16 - fy) * ((16 - fx) * f00[0] + fx * f01[0]) + fy * ((16 - fx) * f10[0] + fx * f11[0]);
+    const int Dy = (16 - fy) * ((16 - fx) * f00[1] + fx * f01[1]) + fy * ((16 - fx) * f10[1] + fx * f11[1]);
+    const int ax = (UNIT * k * Dx + (s >> 1)) >> ls, ay = (UNIT * k * Dy + (s >> 1)) >> ls;
+    const int bx = (UNIT * (s - k) * Dx + (s >> 1)) >> ls, by = (UNIT * (s - k) * Dy + (s >> 1)) >> ls;
+    CubicKey key[2] = {{A, MA, (y << 8) - ay, (x << 8) - ax}, {Bf, MB, (y << 8) + by, (x << 8) + bx}};
+    int v[2][3];
+    bool ok[2];
+    cubic_samples<MASKED>(key, H, W, p.stage != 0, win, wtab, lane, v, ok);
+    if constexpr (VALID) {
+      const int ymax = (H - 1) << 8, xmax = (W - 1) << 8;
+#pragma unroll
+      for (int f = 0; f < 2; ++f) ok[f] = ok[f] && key[f].py >= 0 && key[f].py <= ymax && key[f].px >= 0 && key[f].px <= xmax;
+    }
+    if constexpr (MASKED) {                 // k = 0 and k = s stay A and B
+      if (k == 0) { ok[0] = true; ok[1] = false; }
+      if (k == s) { ok[0] = false; ok[1] = true; }
+    }
+    uint8_t q[3];
+    cubic_blend(v, ok[0], ok[1], k, s, ls, q);
+    if (xo < W) {
+      if (p.out_f32) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) p.out_f32[((size_t)tb * 3 + c) * HW + (size_t)y * W + xo] = rsz_normalise(q[c]);
+      }
+      if (grow) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) srow[xo * 3 + c] = q[c];
+      }
+    }
+  }
+  if (!grow) return;                        // (uniform: no thread reaches the barrier)
+  __syncthreads();
+  cubic_store_row(s_mci, grow, shift, rowbytes);
+}
+
+struct CubicScaledParams {
+  ScaledFramesParams f;                     // k_scaled_frames' own (vec is not used: a lane writes one pixel)
+  int stage_win;                            // CubicFramesParams::stage
+  int w_off;                                // byte offset of the weight table in the dynamic LDS; the windows follow it
+};
+
+template <bool VALID = false, bool HALF = false>
+__global__ __launch_bounds__(256) void k_cubic_scaled(CubicScaledParams cp) {
+  constexpr int UNIT = HALF ? 1 : 2;
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_mci[];
+  const ScaledFramesParams& p = cp.f;
+  const int y = blockIdx.x, tb = blockIdx.y, t = tb / p.B, bi = tb - t * p.B;
+  const int H0 = p.H0, W0 = p.W0, k = p.k_first + t, s = p.s, ls = p.ls;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int rowbytes = W0 * 3;
+  uint8_t* grow = p.out + ((size_t)tb * H0 + y) * (size_t)rowbytes;
+  const int shift = (int)(reinterpret_cast<uintptr_t>(grow) & 15);
+  uint8_t* srow = s_mci + shift;
+  int2* sV = reinterpret_cast<int2*>(s_mci + p.v_off);
+  cubic_w4* wtab = reinterpret_cast<cubic_w4*>(s_mci + cp.w_off);
+  uint32_t* win = reinterpret_cast<uint32_t*>(s_mci + cp.w_off + CUBIC_WTAB_BYTES) + wave * 2 * CUBIC_WIN;
+  const uint8_t* A = p.a + (size_t)bi * H0 * W0 * 3;
+  const uint8_t* Bf = p.b + (size_t)bi * H0 * W0 * 3;
+  const int16_t* fld = p.field + (size_t)bi * p.Hb * p.Wb * 2;
+  // TY as k_scaled_frames computes it
+  const int tyy = y * p.qay + p.q0y + (int)((unsigned)(y * p.ray + p.r0y) / (unsigned)H0) - 128, fy = tyy & 255;
+  const int r0 = min(max(tyy >> 8, 0), p.Hb - 1), r1 = min(max((tyy >> 8) + 1, 0), p.Hb - 1);
+  const int16_t *frow0 = fld + (size_t)r0 * p.Wb * 2, *frow1 = fld + (size_t)r1 * p.Wb * 2;
+  wtab[threadIdx.x] = cubic_weight_row(threadIdx.x);
+  for (int c = threadIdx.x; c < p.Wb; c += 256)      // the once-blended field row; it always has room (the host raises the kernel's LDS limit)
+    sV[c] = make_int2((256 - fy) * frow0[2 * c] + fy * frow1[2 * c], (256 - fy) * frow0[2 * c + 1] + fy * frow1[2 * c + 1]);
+  __syncthreads();
+  const int ntiles = (W0 + CUBIC_TILE - 1) / CUBIC_TILE;
+  for (int tile = wave; tile < ntiles; tile += 4) {      // (uniform per wave)
+    const int xo = tile * CUBIC_TILE + lane, x = min(xo, W0 - 1);
+    const int tq = x * p.qax + p.q0x + (int)((unsigned)(x * p.rax + p.r0x) / (unsigned)W0) - 128, fx = tq & 255;      // TX of x: below 2^29 per term
+    const int c0 = min(max(tq >> 8, 0), p.Wb - 1), c1 = min(max((tq >> 8) + 1, 0), p.Wb - 1);
+    const int2 v0 = sV[c0], v1 = sV[c1];
+    const int D8x = ((256 - fx) * v0.x + fx * v1.x + 128) >> 8, D8y = ((256 - fx) * v0.y + fx * v1.y + 128) >> 8;      // 1/256 model px
+    const int Dx = (int)(((long long)D8x * p.sx + 32768) >> 16), Dy = (int)(((long long)D8y * p.sy + 32768) >> 16);   // 1/256 output px
+    const int ax = (UNIT * k * Dx + (s >> 1)) >> ls, ay = (UNIT * k * Dy + (s >> 1)) >> ls;
+    const int bx = (UNIT * (s - k) * Dx + (s >> 1)) >> ls, by = (UNIT * (s - k) * Dy + (s >> 1)) >> ls;
+    CubicKey key[2] = {{A, nullptr, (y << 8) - ay, (x << 8) - ax}, {Bf, nullptr, (y << 8) + by, (x << 8) + bx}};
+    int v[2][3];
+    bool ok[2];
+    cubic_samples<false>(key, H0, W0, cp.stage_win != 0, win, wtab, lane, v, ok);
+    if constexpr (VALID) {
+      const int ymax = (H0 - 1) << 8, xmax = (W0 - 1) << 8;
+#pragma unroll
+      for (int f = 0; f < 2; ++f) ok[f] = key[f].py >= 0 && key[f].py <= ymax && key[f].px >= 0 && key[f].px <= xmax;
+    }
+    uint8_t q[3];
+    cubic_blend(v, ok[0], ok[1], k, s, ls, q);
+    if (xo < W0) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) srow[xo * 3 + c] = q[c];
+    }
+  }
+  __syncthreads();
+  cubic_store_row(s_mci, grow, shift, rowbytes);
 }
 
 }  // namespace rib

@@ -578,7 +578,7 @@ class Evaluator:
                              panels=False, panel_frames=False, panel_quality=90, panel_fps=30, panel_encode="host",
                              background="dain", mci_range=32, video=False, video_fps=30, video_quality=90, video_frames=False, frames="png",
                              poses="folder", key_pose_dir=None, upsample_rate=8, motion=None, save_poses=False, mci_border="clamp",
-                             mci_precision="full", output_size="model", png_on="host", mci_person="keep"):
+                             mci_precision="full", output_size="model", png_on="host", mci_person="keep", mci_sampler="bilinear"):
         """rank / world: this process's share of the independent units (default: the torch.distributed process
         group when one is initialised, else everything).  Returns the frames THIS rank wrote.
         The call is one `_FolderPipeline` (below): plan a clip -> decode -> upload -> render -> sink, pipelined over units
@@ -625,7 +625,15 @@ class Evaluator:
         background="mci"): the integer field writes the motion between the key frames as an even number of pixels; one more
         launch per group (rib_halfpel_refine; background.mci_refine_host) refines every block's vector by half a pixel and the frames
         are sampled from that field (rib_halfpel_frames; mci_frames_host(precision="half")).  Half-pel samples are bilinear and
-        soft, and a block whose integer vector is more than one half-pel step from the truth stays wrong.  dain_dir may be
+        soft, and a block whose integer vector is more than one half-pel step from the truth stays wrong.
+        mci_sampler="cubic" (default "bilinear"; a setting of background="mci", legal with every combination above): every
+        background sample is a 4x4 Catmull-Rom sample (background.sample_cubic; rib_cubic_frames / rib_cubic_scaled) in place of the
+        bilinear one - the model-size floats the chain reads AND, under output_size="keyframes", the full-size backgrounds.  Frames
+        whose offsets are whole pixels (k = 0, k = s, often k = s / 2) keep their bytes; the others no longer turn soft, so the
+        background stops pulsing at the key-frame rate.  Catmull-Rom overshoots at strong edges (the result is clamped); the
+        exclusion footprint of mci_person="exclude" is 4x4, so the clean / blend seam moves by a pixel; it is still this project's
+        interpolation without interior occlusion reasoning, the generator was trained on DAIN backgrounds, and the quality on
+        real footage is unmeasured.  dain_dir may be
         None and is never listed or read; a frame's file is named after its pose file (stem without a trailing "_keypoints").
         On the native path the field is made once per group of segments (rib_mci_field) and every unit's frames by one launch
         (rib_mci_frames) on the upload stream - no DAIN bytes are staged or decoded; a model behind the reference's protocol is
@@ -708,7 +716,7 @@ class Evaluator:
                 raise ValueError("evaluate_from_folder: upsample_rate must be a power of two, got %r" % (upsample_rate,))
         _composite.check_output_size(output_size, "evaluate_from_folder")
         mci_levels, mci_border = _background.check_settings(background, mci_range, mci_border, self.resize_on, mci_precision=mci_precision,
-                                                            mci_person=mci_person, output_size=output_size)
+                                                            mci_person=mci_person, output_size=output_size, mci_sampler=mci_sampler)
         if output_size == "source" and background == "mci":
             raise ValueError("evaluate_from_folder: output_size='source' with background='mci' is not supported: the interpolation "
                              "runs at the model size (a source-size interpolation is a follow-up); use output_size='keyframes'")
@@ -746,11 +754,11 @@ class Evaluator:
         self.metrics = self.metrics_report = None
         pipe = _FolderPipeline(self, model, rank, world, gt_dir, metrics=bool(metrics), mask_dir=mask_dir, pose_mask=bool(pose_mask),
                                panels=bool(panels), panel_frames=bool(panel_frames), panel_quality=int(panel_quality),
-                               panel_encode=panel_encode, background=background, mci_levels=mci_levels, mci_border=mci_border, mci_precision=mci_precision, mci_person=mci_person, video=bool(video), video_quality=int(video_quality),
+                               panel_encode=panel_encode, background=background, mci_levels=mci_levels, mci_border=mci_border, mci_precision=mci_precision, mci_person=mci_person, mci_sampler=mci_sampler, video=bool(video), video_quality=int(video_quality),
                                video_frames=bool(video_frames), write_png=frames == "png", output_size=output_size, png_gpu=png_on == "gpu",
                                key_poses=None if poses == "folder" else (motion, key_pose_dir, upsample_rate, poses == "keyframes-linear", bool(save_poses)))
         self.background, self.mci_range, self.mci_border, self.mci_precision = background, mci_range, mci_border, mci_precision
-        self.mci_person = mci_person
+        self.mci_person, self.mci_sampler = mci_person, mci_sampler
         self.output_size = output_size
         self.timings = pipe.tm
         if metrics and pipe.native:
@@ -864,7 +872,7 @@ class _FolderPipeline:
     def __init__(self, ev, model, rank, world, gt_dir, metrics=False, mask_dir=None, pose_mask=False,
                  panels=False, panel_frames=False, panel_quality=90, panel_encode="host", background="dain", mci_levels=3,
                  video=False, video_quality=90, video_frames=False, write_png=True, key_poses=None, mci_border="clamp", mci_precision="full",
-                 output_size="model", png_gpu=False, mci_person="keep"):
+                 output_size="model", png_gpu=False, mci_person="keep", mci_sampler="bilinear"):
         # composite.py: the frames' files at the clip's own size - the DAIN frames' ("source") or, under background="mci", the key
         # frame files' ("keyframes": keysize; the backgrounds are then rib_scaled_frames', everything after them is "source"'s code)
         self.source = output_size in ("source", "keyframes")
@@ -873,6 +881,7 @@ class _FolderPipeline:
         self.mci_border = mci_border        # background.py's border
         self.mci_half = mci_precision == "half"      # background.py's precision: the field is refined once per group, in half pixels
         self.mci_exclude = mci_person == "exclude"   # background.py's "person": the key frames' human masks keep the person out
+        self.mci_sampler = mci_sampler               # background.py's sampler: "cubic" = sample_cubic / rib_cubic_* for every background sample
         # poses="keyframes": (motion model, key-pose folder, upsample rate, take the linear clip, also write the json folders)
         self.key_poses = key_poses
         # video: the frames' JPEG files (video.py); write_png False (frames="none"): they are the only files of a frame
@@ -1323,15 +1332,15 @@ class _FolderPipeline:
                 ka, kb, field, ka0, kb0, qa, qb = clip.mci_of[gi]
                 if self.mci_exclude:
                     dn = g.mci_frames_masked(ka, kb, qa, qb, field, clip.sample_rate, k_first=c0 + 1, count=Tc,
-                                             normalised="both" if self.panels else True, border=self.mci_border)
+                                             normalised="both" if self.panels else True, border=self.mci_border, sampler=self.mci_sampler)
                 else:
                     dn = g.mci_frames(ka, kb, field, clip.sample_rate, k_first=c0 + 1, count=Tc, normalised="both" if self.panels else True,
-                                      border=self.mci_border, precision="half" if self.mci_half else "full")
+                                      border=self.mci_border, precision="half" if self.mci_half else "full", sampler=self.mci_sampler)
                 if self.panels:
                     dn, dnu8 = dn
                 if self.keysize:               # ONE launch: the unit's backgrounds uint8 [Tc,B,h0,w0,3], "source"'s staged frames
                     staged = g.mci_frames_scaled(ka0, kb0, field, (ev.height, ev.width), clip.sample_rate, k_first=c0 + 1, count=Tc,
-                                                 border=self.mci_border, precision="half" if self.mci_half else "full")
+                                                 border=self.mci_border, precision="half" if self.mci_half else "full", sampler=self.mci_sampler)
             else:
                 staged = views["dain"].to(g.device, non_blocking=True)
                 if clip.src_dain is not None:      # resize_on="gpu": resize + ToTensor + Normalize in one kernel (rib_resize_cubic)
@@ -1775,13 +1784,14 @@ class _FolderPipeline:
                     qa, qb = (rasterise.human_mask(self.peaks_of(clip.loads[j].result()[2]), ev.height, ev.width).astype(np.uint8)
                               for j in (k, k + clip.sample_rate))
                     field = _background.mci_field_masked_host(ka, kb, qa, qb, self.mci_levels, border=self.mci_border)
-                    u8 = _background.mci_frames_masked_host(ka, kb, qa, qb, field, clip.sample_rate, [i - k for i in frames], border=self.mci_border)
+                    u8 = _background.mci_frames_masked_host(ka, kb, qa, qb, field, clip.sample_rate, [i - k for i in frames], border=self.mci_border,
+                                                            sampler=self.mci_sampler)
                 else:
                     field = _background.mci_field_host(ka, kb, self.mci_levels, border=self.mci_border)
                     if self.mci_half:
                         field = _background.mci_refine_host(ka, kb, field, border=self.mci_border)
                     u8 = _background.mci_frames_host(ka, kb, field, clip.sample_rate, [i - k for i in frames], border=self.mci_border,
-                                                     precision="half" if self.mci_half else "full")
+                                                     precision="half" if self.mci_half else "full", sampler=self.mci_sampler)
                 # the floats the native chain reads (the device's normalisation, stated on the host); the sheets' DAIN pane
                 # shows the host's normalisation, as the native path's does (normalise_exact)
                 dn = torch.from_numpy(_background.normalised_upload(u8)).unsqueeze(1)
@@ -1790,7 +1800,8 @@ class _FolderPipeline:
                     bg0 = _background.mci_frames_scaled_host(clip.key_src[k].result(timeout=IO_TIMEOUT_S),
                                                              clip.key_src[k + clip.sample_rate].result(timeout=IO_TIMEOUT_S), field,
                                                              (ev.height, ev.width), clip.sample_rate, [i - k for i in frames],
-                                                             border=self.mci_border, precision="half" if self.mci_half else "full")
+                                                             border=self.mci_border, precision="half" if self.mci_half else "full",
+                                                             sampler=self.mci_sampler)
             else:
                 dn = dn_shown = torch.stack([g[0] for g in got]).unsqueeze(1)
             lab = ev.make_labels(model, poses).unsqueeze(1)

@@ -669,7 +669,8 @@ class Generator:
             _native.check(self._h, self._lib.rib_halfpel_refine(self._h, B, H, W, _ptr(a), _ptr(b), _ptr(f), _ptr(res), border, self._stream()))
         return res[0] if single else res
 
-    def mci_frames(self, a_u8, b_u8, field, sample_rate, k_first=1, count=None, normalised=True, out=None, border="clamp", precision="full"):
+    def mci_frames(self, a_u8, b_u8, field, sample_rate, k_first=1, count=None, normalised=True, out=None, border="clamp", precision="full",
+                   sampler="bilinear", _staging=0):
         """Frames k_first .. k_first + count - 1 (count None: up to sample_rate - 1) of B segments from their key frames and
         block fields, all in one launch (rib_mci_frames; background.mci_frames_host is the definition and is bit-equal):
         a_u8, b_u8 uint8 [B,H,W,3], field int16 [B,Hb,Wb,2] (mci_field) on this device, sample_rate a power of two.
@@ -677,9 +678,12 @@ class Generator:
         False: uint8 [T,B,H,W,3]; "both": the pair (float32, uint8).  [H,W,3] key frames give [T,3,H,W] / [T,H,W,3].
         out: optional contiguous destination (for "both": a pair).  border: "clamp" (the default) or "valid": where exactly
         one of a pixel's two samples lies inside the frame, that sample alone.  precision: "full" (the default) or "half": the
-        field is mci_refine's, in half pixels (rib_halfpel_frames)."""
-        from .background import BORDERS, check_border, check_precision, field_shape, log2_rate
+        field is mci_refine's, in half pixels (rib_halfpel_frames).  sampler: "bilinear" (the default) or "cubic": the 4x4
+        Catmull-Rom sample (rib_cubic_frames; background.sample_cubic), nothing else changed; _staging (cubic only) is that
+        entry's diagnostic: 0 = the per-tile rule, 1 = never stage - the bytes do not depend on it."""
+        from .background import BORDERS, PRECISIONS, check_border, check_precision, check_sampler, field_shape, log2_rate
         border = BORDERS.index(check_border(border, "mci_frames"))
+        cubic = check_sampler(sampler, "mci_frames") == "cubic"
         entry = self._lib.rib_halfpel_frames if check_precision(precision, "mci_frames") == "half" else self._lib.rib_mci_frames
         a, b, single = self._mci_pair(a_u8, b_u8, "mci_frames")
         B, H, W, _ = a.shape
@@ -710,7 +714,11 @@ class Generator:
         with torch.cuda.device(self.device):
             rf = dest(of, fshape, torch.float32) if normalised in (True, "both") else None
             ru = dest(ou, ushape, torch.uint8) if normalised in (False, "both") else None
-            _native.check(self._h, entry(self._h, T, B, H, W, _ptr(a), _ptr(b), _ptr(f), s, k_first, border, _ptr(rf), _ptr(ru), self._stream()))
+            if cubic:
+                _native.check(self._h, self._lib.rib_cubic_frames(self._h, T, B, H, W, _ptr(a), _ptr(b), None, None, _ptr(f), s, k_first, border,
+                                                                  PRECISIONS.index(precision), int(_staging), _ptr(rf), _ptr(ru), self._stream()))
+            else:
+                _native.check(self._h, entry(self._h, T, B, H, W, _ptr(a), _ptr(b), _ptr(f), s, k_first, border, _ptr(rf), _ptr(ru), self._stream()))
         res = tuple((r[:, 0] if single else r) for r in (rf, ru) if r is not None)
         return res if normalised == "both" else res[0]
 
@@ -748,13 +756,15 @@ class Generator:
         return field[0] if single else field
 
     def mci_frames_masked(self, a_u8, b_u8, ma, mb, field, sample_rate, k_first=1, count=None, normalised=True, out=None, border="clamp",
-                          precision="full"):
+                          precision="full", sampler="bilinear", _staging=0):
         """mci_frames with the person kept out (rib_masked_frames; background.mci_frames_masked_host is the definition and is
         bit-equal): ma, mb uint8 [B,H,W] (or [H,W]) on this device, nonzero = excluded; where exactly one of a pixel's two samples
         is clean - valid under `border`, and the four taps of its footprint in its key frame's mask all zero - the output is that
-        sample alone.  Everything else - field, frames, normalised (True, False, "both"), out, precision - is mci_frames'."""
-        from .background import BORDERS, PRECISIONS, check_border, check_precision, field_shape, log2_rate
+        sample alone.  Everything else - field, frames, normalised (True, False, "both"), out, precision, sampler, _staging - is
+        mci_frames'; sampler="cubic" (rib_cubic_frames with the masks): a sample is clean iff all 16 of its taps are clear."""
+        from .background import BORDERS, PRECISIONS, check_border, check_precision, check_sampler, field_shape, log2_rate
         border = BORDERS.index(check_border(border, "mci_frames_masked"))
+        cubic = check_sampler(sampler, "mci_frames_masked") == "cubic"
         precision = PRECISIONS.index(check_precision(precision, "mci_frames_masked"))
         a, b, single = self._mci_pair(a_u8, b_u8, "mci_frames_masked")
         B, H, W, _ = a.shape
@@ -786,21 +796,28 @@ class Generator:
         with torch.cuda.device(self.device):
             rf = dest(of, fshape, torch.float32) if normalised in (True, "both") else None
             ru = dest(ou, ushape, torch.uint8) if normalised in (False, "both") else None
-            _native.check(self._h, self._lib.rib_masked_frames(self._h, T, B, H, W, _ptr(a), _ptr(b), _ptr(qa), _ptr(qb), _ptr(f), s, k_first,
-                                                               border, precision, _ptr(rf), _ptr(ru), self._stream()))
+            if cubic:
+                _native.check(self._h, self._lib.rib_cubic_frames(self._h, T, B, H, W, _ptr(a), _ptr(b), _ptr(qa), _ptr(qb), _ptr(f), s, k_first,
+                                                                  border, precision, int(_staging), _ptr(rf), _ptr(ru), self._stream()))
+            else:
+                _native.check(self._h, self._lib.rib_masked_frames(self._h, T, B, H, W, _ptr(a), _ptr(b), _ptr(qa), _ptr(qb), _ptr(f), s, k_first,
+                                                                   border, precision, _ptr(rf), _ptr(ru), self._stream()))
         res = tuple((r[:, 0] if single else r) for r in (rf, ru) if r is not None)
         return res if normalised == "both" else res[0]
 
-    def mci_frames_scaled(self, a0_u8, b0_u8, field, model_hw, sample_rate, k_first=0, count=None, border="clamp", precision="full", out=None):
+    def mci_frames_scaled(self, a0_u8, b0_u8, field, model_hw, sample_rate, k_first=0, count=None, border="clamp", precision="full", out=None,
+                          sampler="bilinear", _staging=0):
         """mci_frames' uint8 frames at the key frames' OWN size, one launch (rib_scaled_frames; background.mci_frames_scaled_host
         is the definition and is bit-equal): a0_u8, b0_u8 uint8 [B,h0,w0,3] (or [h0,w0,3]) are the key frame files' pixels on
         this device, field the int16 [B,Hb,Wb,2] field of the MODEL-size key frames (mci_field, or mci_refine with
         precision="half"), model_hw = (H, W) that model size -> uint8 [T,B,h0,w0,3] ([T,h0,w0,3]), frames k_first ..
         k_first + count - 1 (count None: up to sample_rate - 1).  The field is read at the model's resolution, the pixels are
         sampled from the full-size key frames; with (h0, w0) == (H, W) the bytes are mci_frames'.  Sides in 1..16384, each axis
-        within 1/16 .. 16 times the model's.  out: optional contiguous uint8 destination, any byte offset."""
-        from .background import BORDERS, PRECISIONS, check_border, check_precision, field_shape, log2_rate, scaled_factors
+        within 1/16 .. 16 times the model's.  out: optional contiguous uint8 destination, any byte offset.  sampler="cubic":
+        rib_cubic_scaled (background.sample_cubic in place of the bilinear sample); _staging is its diagnostic, as mci_frames'."""
+        from .background import BORDERS, PRECISIONS, check_border, check_precision, check_sampler, field_shape, log2_rate, scaled_factors
         border = BORDERS.index(check_border(border, "mci_frames_scaled"))
+        cubic = check_sampler(sampler, "mci_frames_scaled") == "cubic"
         precision = PRECISIONS.index(check_precision(precision, "mci_frames_scaled"))
         a, b, single = self._mci_pair(a0_u8, b0_u8, "mci_frames_scaled")
         B, h0, w0, _ = a.shape
@@ -826,8 +843,12 @@ class Generator:
                 res = out.unsqueeze(1) if (single and torch.is_tensor(out) and out.dim() == 4) else out
                 if not torch.is_tensor(res) or tuple(res.shape) != shape or res.dtype != torch.uint8 or not res.is_contiguous() or res.device != self.device:
                     raise ValueError("mci_frames_scaled: out must be a contiguous uint8 %s tensor on %s" % (shape, self.device))
-            _native.check(self._h, self._lib.rib_scaled_frames(self._h, T, B, H, W, h0, w0, _ptr(a), _ptr(b), _ptr(f), s, k_first, border,
-                                                               precision, _ptr(res), self._stream()))
+            if cubic:
+                _native.check(self._h, self._lib.rib_cubic_scaled(self._h, T, B, H, W, h0, w0, _ptr(a), _ptr(b), _ptr(f), s, k_first, border,
+                                                                  precision, int(_staging), _ptr(res), self._stream()))
+            else:
+                _native.check(self._h, self._lib.rib_scaled_frames(self._h, T, B, H, W, h0, w0, _ptr(a), _ptr(b), _ptr(f), s, k_first, border,
+                                                                   precision, _ptr(res), self._stream()))
         return res[:, 0] if single else res
 
     def jpeg_max_bytes(self, height, width):

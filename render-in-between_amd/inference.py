@@ -62,6 +62,13 @@ reference's coarse pose mask, so hair, loose clothing and carried objects outsid
 cleanliness flips; only the person is handled, not other moving objects; background hidden in both key frames stays a blend; the
 generator and its mask network were trained on DAIN frames that show a blurred person; quality on real footage is unmeasured.
 Not yet with `--mci-precision half` nor `--output-size keyframes`.
+`--mci-sampler cubic` (default `bilinear`): a bilinear sample at a fractional position is a low-pass filter that disappears where
+the offset is a whole pixel - at k = 0, k = s and often k = s / 2 of a segment - so the background pulses between sharp and soft at
+the key-frame rate.  `cubic` takes every background sample as a 4x4 Catmull-Rom sample (rib_cubic_frames; under `--output-size
+keyframes` also the full-size backgrounds, rib_cubic_scaled); frames at whole-pixel offsets keep their bytes.  It combines with every
+setting above.  The limits, plainly: Catmull-Rom overshoots at strong edges and the result is clamped; with `--mci-person exclude`
+the exclusion footprint is 4x4, so the clean / blend seam moves by a pixel; it is still this project's interpolation, without
+interior occlusion reasoning; the generator was trained on DAIN backgrounds; quality on real footage is unmeasured.
 Frames are then named after their pose files.  The default, `--background dain`, is the reference's contract.
 
 Poses without a Predict_motion folder: `--poses keyframes --pose-dir DIR [--upsample-rate N] [--motion-config PATH]` runs stage 1
@@ -153,7 +160,8 @@ def summary_line(evaluator, rank=0, world=1):
                {"dain": "DAIN frames", "mci": "mci (interpolated from the key frames, range %d px, border %s%s)"
                        % (getattr(evaluator, "mci_range", 32), getattr(evaluator, "mci_border", "clamp"),
                           (", half-pel" if getattr(evaluator, "mci_precision", "full") == "half" else "")
-                          + (", person excluded" if getattr(evaluator, "mci_person", "keep") == "exclude" else ""))}
+                          + (", person excluded" if getattr(evaluator, "mci_person", "keep") == "exclude" else "")
+                          + (", cubic sampler" if getattr(evaluator, "mci_sampler", "bilinear") == "cubic" else ""))}
                [getattr(evaluator, "background", "dain")]))
     if getattr(evaluator, "output_size", "model") == "source":
         line += " | files at the source size"
@@ -202,7 +210,7 @@ def main(opts):
                                              panel_fps=30 if opts.panel_fps is None else opts.panel_fps,
                                              panel_encode=opts.panel_encode or "host", background=opts.background, mci_range=opts.mci_range,
                                              mci_border=opts.mci_border, mci_precision=opts.mci_precision, mci_person=opts.mci_person,
-                                             video=opts.video, video_fps=30 if opts.video_fps is None else opts.video_fps,
+                                             mci_sampler=opts.mci_sampler, video=opts.video, video_fps=30 if opts.video_fps is None else opts.video_fps,
                                              video_quality=90 if opts.video_quality is None else opts.video_quality,
                                              video_frames=opts.video_frames, frames=opts.frames, output_size=opts.output_size, png_on=opts.png_on,
                                              **poses_kw)
@@ -297,6 +305,14 @@ def build_parser():
                              "person, not other moving objects; background hidden in both key frames stays a blend; the generator was "
                              "trained on DAIN frames that show a blurred person; unmeasured on real footage. Not yet with "
                              "--mci-precision half (no masked refinement) nor --output-size keyframes (no masked rib_scaled_frames)")
+    parser.add_argument("--mci-sampler", default=None,
+                        help="with --background mci: 'bilinear' (default): the in-between backgrounds turn soft wherever the offset is "
+                             "fractional and sharp where it is whole, so they pulse at the key-frame rate; 'cubic': every background "
+                             "sample is a 4x4 Catmull-Rom sample (with --output-size keyframes also the full-size backgrounds); frames "
+                             "at whole-pixel offsets keep their bytes. Works with every other --mci-* setting. Catmull-Rom overshoots "
+                             "at strong edges and the result is clamped; with --mci-person exclude the exclusion footprint is 4x4, so "
+                             "the clean/blend seam moves by a pixel; still this project's interpolation, without interior occlusion "
+                             "reasoning; the generator was trained on DAIN backgrounds; quality on real footage is unmeasured")
     parser.add_argument("--video", action="store_true",
                         help="also write every frame of a clip, key frames included, as <save-dir>/Generated_frames/<clip>_video.avi "
                              "(Motion-JPEG; a frame is the JPEG of exactly the bytes its PNG holds, encoded on the GPU)")
@@ -368,6 +384,11 @@ def parse_args(argv=None):
     if opts.mci_person not in (None, "keep", "exclude"):
         parser.error("--mci-person must be 'keep' or 'exclude', got %r" % (opts.mci_person,))
     opts.mci_person = "keep" if opts.mci_person is None else opts.mci_person
+    if opts.mci_sampler is not None and opts.background != "mci":
+        parser.error("--mci-sampler is a setting of --background mci")
+    if opts.mci_sampler not in (None, "bilinear", "cubic"):
+        parser.error("--mci-sampler must be 'bilinear' or 'cubic', got %r" % (opts.mci_sampler,))
+    opts.mci_sampler = "bilinear" if opts.mci_sampler is None else opts.mci_sampler
     if opts.mci_person == "exclude" and opts.mci_precision == "half":
         parser.error("--mci-person exclude with --mci-precision half is not supported yet: the half-pel refinement has no masked form "
                      "(a masked rib_halfpel_refine is the follow-up)")

@@ -3,6 +3,7 @@
 unit - B segments of H x W at sample rate s - for a kernel trace.
 
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/mci_bench.py [--size 512] [--batch 4] [--rate 8] [--reps 20] [--u8] [--levels 3] [--border clamp] [--precision full] [--person]
+                                                     [--sampler bilinear] [--staging 0]
 
 --levels 3 (the default), 4 or 5: the pyramid levels of the field's search, the driver's --mci-range 32, 64 or 128; the scene's
 motion between the key frames grows with it (a quarter of that range in x, 3/16 in y).  --border valid: the one-sided border mode
@@ -13,6 +14,10 @@ rib_halfpel_frames's from the refined field (k_mci_frames<.., true>); the defaul
 (Generator.mci_field_masked / mci_frames_masked) with an upright ellipse per key frame as the excluded pixels, a sixth of the
 width wide and moved by an eighth of the width between the key frames - k_mci_mask_pyramid, k_mci_search<R, .., true>, k_mci_fill
 and k_mci_frames<.., .., true> in the same trace, beside the unmasked rows; not with --precision half.
+--sampler cubic (the driver's --mci-sampler): AFTER everything above, the same frames launch through rib_cubic_frames (k_cubic_frames
+in the same trace, beside k_mci_frames' rows; with --person also its masked form); --staging 1 passes that entry's diagnostic
+"never stage" (every tile gathers its taps directly), 0 is the per-tile rule.  The JSON then also holds the share of tiles the
+rule stages on this field (background.cubic_tile_staged, on the host, segment 0).
 
 Prints one JSON line: the wall time of the field's launches (levels + 2: five by default) and of the frames launch between two events (median of
 --reps, after a warm-up), the frames launch's byte floor (12 bytes of float32 out per pixel and frame, 3 more with --u8, the
@@ -55,6 +60,8 @@ def main():
     ap.add_argument("--border", default="clamp", choices=("clamp", "valid"), help="the border mode (--mci-border)")
     ap.add_argument("--precision", default="full", choices=("full", "half"), help="the field's unit (--mci-precision): half also times the refine launch")
     ap.add_argument("--person", action="store_true", help="also time the masked entries (--mci-person exclude) on the same unit")
+    ap.add_argument("--sampler", default="bilinear", choices=("bilinear", "cubic"), help="cubic: also time rib_cubic_frames on the same unit (--mci-sampler)")
+    ap.add_argument("--staging", type=int, default=0, choices=(0, 1), help="with --sampler cubic: 0 = the per-tile staging rule, 1 = never stage (a diagnostic)")
     a = ap.parse_args()
     if a.person and a.precision == "half":
         ap.error("--person times the whole-pixel masked entries: not with --precision half")
@@ -93,6 +100,18 @@ def main():
                       "masked_field_event_us_median": round(pms[len(pms) // 2] * 1e3, 2), "masked_field_event_us_min": round(pms[0] * 1e3, 2),
                       "masked_frames_event_us_median": round(qms[len(qms) // 2] * 1e3, 2), "masked_frames_event_us_min": round(qms[0] * 1e3, 2),
                       "masked_field_differs_fraction": round(float((mfield != field).any(-1).float().mean()), 3)})
+    if a.sampler == "cubic":
+        from render_in_between_amd import background as bg
+        ckw = dict(fkw, sampler="cubic", _staging=a.staging)
+        cms = timed(lambda: G.mci_frames(ka, kb, field, s, normalised="both" if a.u8 else True, out=(f32, u8) if a.u8 else f32, **ckw), a.reps)
+        f0 = field[0].cpu().numpy()
+        share = [float(bg.cubic_tile_staged(*bg.sample_positions(f0, s, k, H, W, a.precision)).mean()) for k in range(1, s)]
+        extra.update({"sampler": "cubic", "staging": a.staging, "cubic_frames_event_us_median": round(cms[len(cms) // 2] * 1e3, 2),
+                      "cubic_frames_event_us_min": round(cms[0] * 1e3, 2), "cubic_tiles_staged_by_the_rule": round(sum(share) / len(share), 3)})
+        if a.person:
+            xms = timed(lambda: G.mci_frames_masked(ka, kb, qa, qb, mfield, s, normalised="both" if a.u8 else True, out=(f32, u8) if a.u8 else f32,
+                                                    **dict(kw, sampler="cubic", _staging=a.staging)), a.reps)
+            extra.update({"cubic_masked_frames_event_us_median": round(xms[len(xms) // 2] * 1e3, 2), "cubic_masked_frames_event_us_min": round(xms[0] * 1e3, 2)})
     print(json.dumps({"height": H, "width": W, "batch": B, "rate": s, "levels": a.levels, "border": a.border, "precision": a.precision, "frames": T * B, "u8": a.u8,
                       "field_event_us_median": round(fms[len(fms) // 2] * 1e3, 2), "field_event_us_min": round(fms[0] * 1e3, 2),
                       "frames_event_us_median": round(rms[len(rms) // 2] * 1e3, 2), "frames_event_us_min": round(rms[0] * 1e3, 2),

@@ -5,11 +5,14 @@ output at the model size, for a kernel trace.
 
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/scaled_frames_bench.py [--size 512] [--src-height 1080 --src-width 1920]
                                                      [--batch 4] [--rate 8] [--count 4] [--border clamp] [--precision full] [--reps 20]
+                                                     [--sampler bilinear] [--staging 0]
 
 Prints one JSON line: the time of each launch between two events (median and min of --reps, after a warm-up) and each launch's
 byte floor - every output byte written once, the two key frames read once - with what that floor takes at 6.3 TB/s.  The kernels'
 own times are the k_scaled_frames and k_mci_frames rows of the trace.  The key frames are a smooth synthetic scene and its
 translate, the field is rib_mci_field's (rib_halfpel_refine's with --precision half) of their model-size resize.
+--sampler cubic: AFTER the two launches above, the same unit through rib_cubic_scaled (k_cubic_scaled in the same trace, beside
+k_scaled_frames' rows); --staging 1 is that entry's diagnostic "never stage", 0 the per-tile rule.
 """
 import argparse, json, os, sys
 import torch
@@ -29,6 +32,8 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--border", default="clamp", choices=("clamp", "valid"))
     ap.add_argument("--precision", default="full", choices=("full", "half"))
+    ap.add_argument("--sampler", default="bilinear", choices=("bilinear", "cubic"), help="cubic: also time rib_cubic_scaled on the same unit")
+    ap.add_argument("--staging", type=int, default=0, choices=(0, 1), help="with --sampler cubic: 0 = the per-tile staging rule, 1 = never stage")
     a = ap.parse_args()
     H = W = a.size
     H0, W0, B, s, T = a.src_height, a.src_width, a.batch, a.rate, a.count
@@ -49,13 +54,21 @@ def main():
     sms = timed(lambda: G.mci_frames_scaled(ka0, kb0, field, (H, W), s, k_first=1, count=T, out=big_out, **kw), a.reps)
     mms = timed(lambda: G.mci_frames(ka, kb, field, s, k_first=1, count=T, normalised=False, out=small_out, **kw), a.reps)
     floor = lambda h, w: 3 * h * w * T * B + 2 * 3 * h * w * B
+    extra = {}
+    if a.sampler == "cubic":
+        from render_in_between_amd import background as bg
+        cms = timed(lambda: G.mci_frames_scaled(ka0, kb0, field, (H, W), s, k_first=1, count=T, out=big_out, sampler="cubic", _staging=a.staging, **kw), a.reps)
+        f0 = field[0].cpu().numpy()
+        share = [float(bg.cubic_tile_staged(*bg.sample_positions(f0, s, k, H0, W0, a.precision, model_hw=(H, W))).mean()) for k in range(1, 1 + T)]
+        extra = {"sampler": "cubic", "staging": a.staging, "cubic_scaled_event_us_median": round(cms[len(cms) // 2] * 1e3, 2),
+                 "cubic_scaled_event_us_min": round(cms[0] * 1e3, 2), "cubic_tiles_staged_by_the_rule": round(sum(share) / len(share), 3)}
     print(json.dumps({"height": H, "width": W, "src_height": H0, "src_width": W0, "batch": B, "rate": s, "frames": T * B, "border": a.border,
                       "precision": a.precision,
                       "scaled_event_us_median": round(sms[len(sms) // 2] * 1e3, 2), "scaled_event_us_min": round(sms[0] * 1e3, 2),
                       "scaled_floor_bytes": floor(H0, W0), "scaled_floor_us_at_6.3TB/s": round(floor(H0, W0) / 6.3e12 * 1e6, 2),
                       "model_u8_event_us_median": round(mms[len(mms) // 2] * 1e3, 2), "model_u8_event_us_min": round(mms[0] * 1e3, 2),
                       "model_u8_floor_bytes": floor(H, W), "model_u8_floor_us_at_6.3TB/s": round(floor(H, W) / 6.3e12 * 1e6, 2),
-                      "field_nonzero_fraction": round(float((field != 0).float().mean()), 3), "field_max_abs": int(field.abs().max())}))
+                      "field_nonzero_fraction": round(float((field != 0).float().mean()), 3), "field_max_abs": int(field.abs().max()), **extra}))
 
 
 if __name__ == "__main__":
