@@ -446,6 +446,31 @@ int rib_cubic_frames(rib_handle* h, int T, int B, int H, int W, const uint8_t* a
 int rib_cubic_scaled(rib_handle* h, int T, int B, int H, int W, int H0, int W0, const uint8_t* a0_u8, const uint8_t* b0_u8,
                      const int16_t* field_i16, int sample_rate, int k_first, int border, int precision, int staging,
                      uint8_t* out_u8_nhwc, void* hip_stream);
+/* rib_detail_workspace_bytes / rib_detail_field (the driver's --mci-detail keyframes; background.mci_detail_field_host, bit-equal): the block
+ * field REFINED AT THE KEY FRAMES' OWN SIZE.  Under rib_scaled_frames the field holds whole MODEL pixels - multiples of 3.75 output pixels
+ * at 512 -> 1920 - so a block's two samples are misregistered by up to one quantum.  a0_u8, b0_u8 uint8 NHWC [B,H0,W0,3] are the key frame
+ * files' pixels, field_i16 the [B,Hb,Wb,2] field of the H x W MODEL-size key frames (rib_mci_field's with precision = 0,
+ * rib_halfpel_refine's in half pixels with precision = 1) -> out_field_i16 int16 [B,H0b,W0b,2], H0b = ceil(H0/8), W0b = ceil(W0/8): a block
+ * field of the FULL-SIZE frames in WHOLE OUTPUT pixels of half the motion, rib_mci_field's meaning at that size.  Per block (by, bx):
+ * start = rib_scaled_frames' steps (1)-(3) at the pixel (min(8 by + 4, H0 - 1), min(8 bx + 4, W0 - 1)), rounded to whole pixels as (DS +
+ * 128) >> 8 (precision = 1: (DS + 256) >> 9); the winner of start + [-R, R]^2 on the full-size lumas under rib_mci_field's rules (border =
+ * 0: the clamped SAD + 4 (|dx| + |dy|), the minimum of (cost, dx^2+dy^2, dy, dx); border = 1: the one-sided cost over the candidates with
+ * 4 n >= N, and a block whose start is not valid keeps its start), R = min(4, max(1, (c + 1) / 2)), c = max(ceil(W0/W), ceil(H0/H)) - half
+ * the model-pixel quantum: 1 up to ratio 2, 2 up to 4, 3 up to 6, 4 beyond; above ratio 8 the search no longer covers the quantum; then
+ * rib_mci_field's 3x3 median.  The key is 64-bit with 12 bits per component: components reach 79 * 16 + 4 = 1268 (1276 from half pixels).
+ * The frames at the key frames' size are rib_mci_frames / rib_cubic_frames on (a0_u8, b0_u8, out_field_i16) at H0 x W0: the existing
+ * entries (2 * 1024 * 1276 * 256 < 2^31); there is no new frame entry and no half-pel step at full size.  workspace:
+ * rib_detail_workspace_bytes(h, B, H0, W0) bytes on the device, 16-byte aligned, nothing to clear - the field before the median and
+ * nothing else; it must not overlap out_field_i16.  TWO launches on `stream` (the search, which computes every start itself and the luma
+ * while staging, and the median); no atomics, no synchronisation, a segment's field does not depend on B.  Model-size components beyond
+ * +-79 (+-159 in half pixels) cannot be refused without reading the device: the kernel clamps them, nothing is read out of bounds.
+ * B outside 1..32767, a side outside 1..16384, B * ceil(H0/8) * ceil(W0/8) >= 2^30, W0 > 16 W, W > 16 W0 (the same for the heights),
+ * precision or border outside {0, 1}, NULL or misaligned pointers (fields 4-byte, workspace 16-byte): RIB_ERR_INVALID with a rib_last_error
+ * text that names the entry, nothing launched (the size query returns 0).  Named rib_detail_*, not rib_mci_*: that family stays at four.
+ * This is still this project's interpolation: no interior occlusion reasoning, and a wrong model-size vector stays wrong beyond R. */
+size_t rib_detail_workspace_bytes(rib_handle* h, int B, int H0, int W0);
+int rib_detail_field(rib_handle* h, int B, int H, int W, int H0, int W0, const uint8_t* a0_u8, const uint8_t* b0_u8,
+                     const int16_t* field_i16, int precision, int border, int16_t* out_field_i16, void* workspace, void* hip_stream);
 void rib_mci_field_shape(int H, int W, int* Hb, int* Wb);
 size_t rib_mci_workspace_bytes(rib_handle* h, int B, int H, int W, int levels);
 int rib_mci_field(rib_handle* h, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,

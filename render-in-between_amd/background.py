@@ -100,6 +100,18 @@ rib_halfpel_frames) are held bit-equal to them (tests/test_gpu_mci.py, tests/tes
              clamped.  cubic_tile_staged states, from the sample positions alone, which tiles the kernels read from an LDS window
              and which they gather directly; the bytes do not depend on it.
 
+  detail     (mci_detail_field_host, the driver's mci_detail="keyframes"; rib_detail_field, tests/test_gpu_mci_detail.py; "model" by
+             default).  Under "key frames' size" the block field holds whole MODEL pixels - multiples of 3.75 output pixels at
+             512 -> 1920 - so the two samples of a block are misregistered by up to one quantum and the full-size background is a
+             soft double image even where the model-size field is right.  One more search, at the key frames' own size: a block field
+             of the full-size key frames, [ceil(h0/8), ceil(w0/8), 2] in whole OUTPUT pixels, every block started from the scaled
+             model-size vector at its centre pixel and searched over start + [-R, R]^2 (detail_radius: half the quantum, at most 4)
+             on the full-size lumas with the rules above (clamp / valid, the tuple's minimum; pack_key_detail holds +-1268), then
+             the median.  The frames are mci_frames_host on the full-size key frames with that field, precision="full": no new
+             frame function, no half-pel step at full size (below ratio 2 a model half-pel is finer than a full-size pixel).  The
+             model-size floats the generator reads stay the model-size field's.  A wrong model-size vector stays wrong beyond R;
+             above ratio 8 R no longer covers the quantum; no interior occlusion reasoning.
+
 No quarter-pel search, no sub-pel search on the coarse levels, and no occlusion reasoning beyond the frame border under
 border="valid" - a foreground object that covers background is not handled unless the person is excluded (`rib_masked_*`): see
 DESIGN ("Motion-compensated backgrounds") for what that costs."""
@@ -130,6 +142,10 @@ SAMPLERS = ("bilinear", "cubic")          # `sampler` of the mci_frames_*_host f
 CUBIC_TILE = 64           # cubic_tile_staged: a tile is 64 consecutive x of one output row (one wave of k_cubic_frames / k_cubic_scaled)
 CUBIC_WIN_ROWS, CUBIC_WIN_COLS = 12, 76   # ... and it is staged when the taps of both its samples fit this window per key frame
 FILL_RADIUS = 8           # mci_field_masked_host: a top-level block that was not searched looks this far (Chebyshev, in blocks) for a searched one
+DETAILS = ("model", "keyframes")          # the driver's mci_detail: "keyframes" = mci_detail_field_host, the field refined at the key frames' size
+DETAIL_MAX_RADIUS = 4     # detail_radius: at most +-4 output pixels around the scaled model-size vector (covers the quantum up to ratio 8)
+DETAIL_MAX_DISP = 79 * 16 + DETAIL_MAX_RADIUS          # 1268: max_disp(5) at ratio 16, plus the radius
+DETAIL_KEY_BIAS = 2048    # pack_key_detail: dy + 2048, dx + 2048 in 12 bits each (DETAIL_MAX_DISP < 2048)
 
 
 def field_shape(height, width):
@@ -219,6 +235,19 @@ def check_settings(background, mci_range, mci_border, resize_on, who="evaluate_f
     return RANGES[mci_range], mci_border
 
 
+def check_detail(background, output_size, mci_detail="model", who="evaluate_from_folder"):
+    """The folder driver's mci_detail, checked beside check_settings (whose parameter list is pinned by tests/test_mci_cubic_cpu.py, so
+    the setting has a check of its own): "model" (the default) or "keyframes" (mci_detail_field_host: the block field refined at the
+    key frames' own size, the frames then mci_frames_host on the full-size key frames), which needs background="mci" with
+    output_size="keyframes" -> mci_detail, the caller's to pass on."""
+    if not isinstance(mci_detail, str) or mci_detail not in DETAILS:
+        raise ValueError("%s: mci_detail must be 'model' or 'keyframes', got %r" % (who, mci_detail))
+    if mci_detail != "model" and (background != "mci" or output_size != "keyframes"):
+        raise ValueError("%s: mci_detail='keyframes' is a setting of background='mci' with output_size='keyframes' (the field is "
+                         "refined at the key frames' own size)" % who)
+    return mci_detail
+
+
 def max_disp(levels):
     """The largest |dx|, |dy| the level-0 field of a `levels`-level search can hold: 19, 39, 79."""
     d = SEARCH_TOP
@@ -252,6 +281,22 @@ def unpack_key_wide(key):
     """(cost, dx, dy) of a pack_key_wide key."""
     key = np.asarray(key, np.int64)
     return key >> 30, ((key & 255) - WIDE_KEY_BIAS).astype(np.int32), (((key >> 8) & 255) - WIDE_KEY_BIAS).astype(np.int32)
+
+
+def pack_key_detail(cost, dx, dy):
+    """pack_key_wide with room for mci_detail_field_host's vectors (whole pixels of the key frames' own size): cost << 46 |
+    (dx*dx + dy*dy) << 24 | (dy + 2048) << 12 | (dx + 2048).  |dx|, |dy| <= DETAIL_MAX_DISP = 79 * 16 + 4 = 1268 from a field in
+    whole pixels, and 1276 from one in half pixels (159 half pixels at ratio 16 round to 1272); so cost <= 64 * 255 + 4 * 2 * 1276 =
+    26528 < 2^15, dx*dx + dy*dy <= 2 * 1276^2 = 3256352 < 2^22 and the components < 2048: 61 bits, below search_valid's "never"
+    (2^62).  The same order: the tuple's, so wherever pack_key_wide holds the candidates the winner is the same."""
+    return (cost.astype(np.int64) << 46) | ((dx * dx + dy * dy).astype(np.int64) << 24) | ((dy + DETAIL_KEY_BIAS).astype(np.int64) << 12) \
+        | (dx + DETAIL_KEY_BIAS).astype(np.int64)
+
+
+def unpack_key_detail(key):
+    """(cost, dx, dy) of a pack_key_detail key."""
+    key = np.asarray(key, np.int64)
+    return key >> 46, ((key & 4095) - DETAIL_KEY_BIAS).astype(np.int32), (((key >> 12) & 4095) - DETAIL_KEY_BIAS).astype(np.int32)
 
 
 def block_cost(ya, yb, dx, dy):
@@ -876,6 +921,90 @@ def mci_frames_scaled_host(a0_u8, b0_u8, field, model_hw, sample_rate, ks, borde
             o = np.where(oka == okb, o, np.where(oka, a, b))
         out[j] = o.astype(np.uint8)
     return out
+
+
+def detail_radius(model_hw, out_hw):
+    """The search radius of mci_detail_field_host in output pixels: min(4, max(1, (c + 1) // 2)) with c = max(ceil(w0 / W),
+    ceil(h0 / H)) - half the model-pixel quantum: 1 up to ratio 2, 2 up to 4, 3 up to 6, 4 beyond (512 -> 1920: 2).  The cap is a
+    limit: above ratio 8 the search no longer covers the quantum."""
+    (H, W), (h0, w0) = (int(v) for v in model_hw), (int(v) for v in out_hw)
+    scaled_factors((H, W), (h0, w0), "detail_radius")
+    c = max((w0 + W - 1) // W, (h0 + H - 1) // H)
+    return min(DETAIL_MAX_RADIUS, max(1, (c + 1) // 2))
+
+
+def detail_start(field, model_hw, out_hw, precision="full"):
+    """The start vectors of mci_detail_field_host: (sx, sy) int32 [H0b, W0b], pixel_field_scaled at every full-size block's pixel
+    (min(8 by + 4, h0 - 1), min(8 bx + 4, w0 - 1)), rounded to whole output pixels of d: (DS + 128) >> 8, or (DS + 256) >> 9 where
+    the field is in half pixels."""
+    h0, w0 = (int(v) for v in out_hw)
+    H0b, W0b = field_shape(h0, w0)
+    dsx, dsy = pixel_field_scaled(np.asarray(field), model_hw, (h0, w0))
+    ys, xs = np.minimum(BLOCK * np.arange(H0b) + 4, h0 - 1), np.minimum(BLOCK * np.arange(W0b) + 4, w0 - 1)
+    dsx, dsy = dsx[ys][:, xs], dsy[ys][:, xs]
+    if check_precision(precision, "detail_start") == "half":
+        return (dsx + 256) >> 9, (dsy + 256) >> 9
+    return (dsx + 128) >> 8, (dsy + 128) >> 8
+
+
+def search_detail(ya, yb, sx, sy, radius, border="clamp"):
+    """search(..., wide=True, border) with pack_key_detail in place of pack_key_wide: the same cost functions, the same tuple, the
+    same rules ("valid": the minimum over the valid candidates, and a block whose start is not valid keeps its start), room for
+    |d| <= DETAIL_MAX_DISP.  Where pack_key_wide holds every candidate (|d| <= max_disp(5) = 79: its |d|^2 field has 14 bits) the winners
+    are search's."""
+    valid = check_border(border, "search_detail") == "valid"
+    never = np.int64(1) << 62
+    best = None
+    for ddy in range(-radius, radius + 1):
+        for ddx in range(-radius, radius + 1):
+            dx, dy = sx + ddx, sy + ddy
+            if valid:
+                cost, ok = block_cost_valid(ya, yb, dx, dy)
+                key = np.where(ok, pack_key_detail(np.where(ok, cost, 0), dx, dy), never)
+            else:
+                key = pack_key_detail(block_cost(ya, yb, dx, dy), dx, dy)
+            best = key if best is None else np.minimum(best, key)
+    if not valid:
+        return unpack_key_detail(best)[1:]
+    searched = block_cost_valid(ya, yb, sx, sy)[1]
+    _, wx, wy = unpack_key_detail(np.where(searched, best, 0))
+    return np.where(searched, wx, sx).astype(np.int32), np.where(searched, wy, sy).astype(np.int32)
+
+
+def mci_detail_field_host(a0_u8, b0_u8, field, model_hw, border="clamp", precision="full"):
+    """The block field of the FULL-SIZE key frames (the driver's mci_detail="keyframes"; rib_detail_field, bit-equal): a0_u8, b0_u8
+    uint8 [h0, w0, 3] the key frame files' pixels, field int16 [Hb, Wb, 2] the block field of the model-size (model_hw = (H, W))
+    key frames - mci_field_host's, or with precision="half" mci_refine_host's in half pixels - -> int16 [H0b, W0b, 2], H0b =
+    ceil(h0 / 8), W0b = ceil(w0 / 8), in WHOLE OUTPUT pixels of half the motion: mci_field_host's meaning at that size.
+      start   detail_start: the scaled per-pixel field at the block's pixel (min(8 by + 4, h0 - 1), min(8 bx + 4, w0 - 1)),
+              rounded to whole pixels;
+      search  start + [-R, R]^2, R = detail_radius(model_hw, (h0, w0)), on luma(a0_u8), luma(b0_u8) with the module's rules:
+              "clamp" block_cost and the minimum of (cost, dx*dx + dy*dy, dy, dx); "valid" search_valid's one-sided cost,
+              4 n >= N, and a block whose start is not valid keeps its start; the key is pack_key_detail;
+      median  median3 per component.
+    The frames at the key frames' size are mci_frames_host(a0_u8, b0_u8, F0, s, ks, border, precision="full", sampler): the
+    EXISTING definition with the existing samplers - there is no new frame function, and no half-pel step at full size.  Its
+    int32 offsets hold the longest vector: 2 * 1024 * 1268 * 256 < 2^31.  The field's components must lie in -79..79 (-159..159
+    in half pixels), max_disp(5)'s; the result's lie within +-1268."""
+    check_border(border, "mci_detail_field_host")
+    half = check_precision(precision, "mci_detail_field_host") == "half"
+    a0_u8, b0_u8, field = np.asarray(a0_u8), np.asarray(b0_u8), np.asarray(field)
+    if a0_u8.dtype != np.uint8 or a0_u8.ndim != 3 or a0_u8.shape[2] != 3 or a0_u8.shape != b0_u8.shape or b0_u8.dtype != np.uint8:
+        raise ValueError("mci_detail_field_host: two uint8 [h0, w0, 3] frames of one size, got %s %s and %s %s"
+                         % (a0_u8.dtype, a0_u8.shape, b0_u8.dtype, b0_u8.shape))
+    h0, w0 = a0_u8.shape[:2]
+    H, W = (int(v) for v in model_hw)
+    radius = detail_radius((H, W), (h0, w0))
+    Hb, Wb = field_shape(H, W)
+    if tuple(field.shape) != (Hb, Wb, 2) or field.dtype != np.int16:
+        raise ValueError("mci_detail_field_host: the field of a %dx%d model frame is int16 [%d, %d, 2], got %s %s"
+                         % (H, W, Hb, Wb, field.dtype, tuple(field.shape)))
+    lim = max_disp(MAX_LEVELS) * 2 + 1 if half else max_disp(MAX_LEVELS)
+    if field.size and np.abs(field.astype(np.int32)).max() > lim:
+        raise ValueError("mci_detail_field_host: the field's components must lie in -%d..%d" % (lim, lim))
+    sx, sy = detail_start(field, (H, W), (h0, w0), precision)
+    dx, dy = search_detail(luma(a0_u8), luma(b0_u8), sx.astype(np.int32), sy.astype(np.int32), radius, border)
+    return np.stack([median3(dx), median3(dy)], -1).astype(np.int16)
 
 
 def normalised(u8):

@@ -633,6 +633,70 @@ int rib_halfpel_refine(rib_handle* handle, int B, int H, int W, const uint8_t* a
   return RIB_OK;
 }
 
+// rib_detail_field: the block field of the FULL-SIZE key frames (background.mci_detail_field_host).  The workspace holds the field before the
+// median and nothing else.
+namespace {
+constexpr int DETAIL_MAX_RATIO = 16;        // background.SCALED_MAX_RATIO
+static bool detail_layout(int B, int H0, int W0, int* H0b, int* W0b, size_t* bytes) {
+  if (B < 1 || B > 32767 || H0 < 1 || W0 < 1 || H0 > MCI_MAX_SIDE || W0 > MCI_MAX_SIDE) return false;
+  *H0b = (H0 + MCI_BLOCK - 1) / MCI_BLOCK; *W0b = (W0 + MCI_BLOCK - 1) / MCI_BLOCK;
+  if ((size_t)B * *H0b * *W0b > (size_t)INT32_MAX / 2) return false;
+  *bytes = align256((size_t)B * *H0b * *W0b * 2 * sizeof(int16_t));
+  return true;
+}
+}  // namespace
+
+size_t rib_detail_workspace_bytes(rib_handle* h, int B, int H0, int W0) {
+  int H0b, W0b;
+  size_t n;
+  if (!h || !detail_layout(B, H0, W0, &H0b, &W0b, &n)) return 0;
+  return n;
+}
+
+int rib_detail_field(rib_handle* handle, int B, int H, int W, int H0, int W0, const uint8_t* a0_u8, const uint8_t* b0_u8,
+                     const int16_t* field_i16, int precision, int border, int16_t* out_field_i16, void* workspace, void* hip_stream) {
+  static const char who[] = "rib_detail_field";
+  FrameState* h = frame_state(handle);
+  if (!h) return RIB_ERR_INVALID;
+  if (h->device < 0) return fail(h, RIB_ERR_INVALID, fmt("%s: host-only handle", who));
+  if (!a0_u8 || !b0_u8 || !field_i16 || !out_field_i16 || !workspace) return fail(h, RIB_ERR_INVALID, fmt("%s: null pointer", who));
+  MciLayout L;
+  if (!mci_layout(B, H, W, MCI_MIN_LEVELS, &L))
+    return fail(h, RIB_ERR_INVALID, fmt("%s: B=%d H=%d W=%d: 1 <= B <= 32767, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", who, B, H, W, MCI_MAX_SIDE));
+  int H0b, W0b;
+  size_t bytes;
+  if (!detail_layout(B, H0, W0, &H0b, &W0b, &bytes))
+    return fail(h, RIB_ERR_INVALID, fmt("%s: B=%d H0=%d W0=%d: the key frames' sides lie in 1..%d, B * ceil(H0/8) * ceil(W0/8) < 2^30", who, B, H0, W0, MCI_MAX_SIDE));
+  if (W0 > DETAIL_MAX_RATIO * W || W > DETAIL_MAX_RATIO * W0 || H0 > DETAIL_MAX_RATIO * H || H > DETAIL_MAX_RATIO * H0)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: key frames %dx%d, model %dx%d: each axis within 1/%d .. %d times the model's", who, H0, W0, H, W, DETAIL_MAX_RATIO, DETAIL_MAX_RATIO));
+  if (precision != 0 && precision != 1)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: precision=%d: 0 (the field in pixels) or 1 (in half pixels)", who, precision));
+  if (border != 0 && border != 1)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: border=%d: 0 (clamped samples) or 1 (valid samples only)", who, border));
+  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0 || (reinterpret_cast<uintptr_t>(field_i16) & 3) != 0 || (reinterpret_cast<uintptr_t>(out_field_i16) & 3) != 0)
+    return fail(h, RIB_ERR_INVALID, fmt("%s: workspace must be 16-byte aligned, the fields 4-byte aligned", who));
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  DetailSearchParams sp;
+  sp.a = a0_u8; sp.b = b0_u8; sp.field = field_i16; sp.out = static_cast<int16_t*>(workspace);
+  sp.B = B; sp.H = H; sp.W = W; sp.H0 = H0; sp.W0 = W0; sp.Hb = L.Hb[0]; sp.Wb = L.Wb[0]; sp.H0b = H0b; sp.W0b = W0b;
+  sp.sx = (int)(((int64_t)W0 * 65536 + W / 2) / W); sp.sy = (int)(((int64_t)H0 * 65536 + H / 2) / H);
+  sp.half = precision;
+  const int c = std::max((W0 + W - 1) / W, (H0 + H - 1) / H);
+  const int radius = std::min(DETAIL_MAX_R, std::max(1, (c + 1) / 2));      // background.detail_radius
+  const dim3 grid((H0b * W0b + MCI_RUN - 1) / MCI_RUN, B);
+  void (*const kernels[2][DETAIL_MAX_R])(DetailSearchParams) = {
+      {k_detail_search<1, false>, k_detail_search<2, false>, k_detail_search<3, false>, k_detail_search<4, false>},
+      {k_detail_search<1, true>, k_detail_search<2, true>, k_detail_search<3, true>, k_detail_search<4, true>}};
+  hipLaunchKernelGGL(kernels[border][radius - 1], grid, dim3(256), 0, st, sp);
+  HIP_TRY(h, hipGetLastError());
+  const int n = B * H0b * W0b;
+  hipLaunchKernelGGL(k_mci_median, dim3(std::min((n + 255) / 256, 1024)), dim3(256), 0, st, static_cast<const int16_t*>(workspace), out_field_i16, B,
+                     H0b, W0b);
+  HIP_TRY(h, hipGetLastError());
+  return RIB_OK;
+}
+
 // rib_mci_frames / rib_halfpel_frames: one body, one kernel template; half: the field is rib_halfpel_refine's, in half pixels
 // rib_masked_frames: the same body again; masked: ma_u8, mb_u8 are wanted, and the kernel is <.., MASKED = true>
 static int mci_frames_enqueue(const char* who, bool half, rib_handle* handle, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8,

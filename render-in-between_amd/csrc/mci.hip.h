@@ -1084,4 +1084,140 @@ __global__ __launch_bounds__(256) void k_cubic_scaled(CubicScaledParams cp) {
   cubic_store_row(s_mci, grow, shift, rowbytes);
 }
 
+// ---- the field refined at the key frames' own size (rib_detail_field; background.mci_detail_field_host, the driver's mci_detail="keyframes") ----
+// k_detail_search<R>  grid (runs of MCI_RUN blocks of the FULL-SIZE frame, B), shaped like k_mci_search and k_mci_refine.  A workgroup
+//                     owns a run of MCI_RUN blocks; thread j < MCI_RUN computes block j's start itself - background.detail_start: the
+//                     bilinear model-size field at the block's pixel (min(8 by + 4, H0 - 1), min(8 bx + 4, W0 - 1)) from its four
+//                     vectors, D8 = (D16 + 128) >> 8, DS = (D8 * S + 32768) >> 16 (64-bit product, 16.16 factors from the host),
+//                     start = (DS + 128) >> 8, or (DS + 256) >> 9 where the field is in half pixels - so there is no start launch and
+//                     no start buffer; the two clamped (8 + 2R)^2 windows of A around p - start and of B around p + start are staged as
+//                     luma computed from the RGB bytes while staging (no full-size luma plane); a wave takes a block, its lanes the
+//                     candidates times PARTS row parts (R = 1: 9 x 4, R = 2: 25 x 2, R = 3: 49, R = 4: 81 in two passes); the winner is
+//                     the wave minimum, by shuffles, of background.pack_key_detail: cost << 46 | dx^2 + dy^2 << 24 | dy + 2048 << 12 |
+//                     dx + 2048 - the tuple's order with room for |d| <= 79 * 16 + 4 = 1268.  <R, VALID = true>: k_mci_search's
+//                     rectangle, 64 * SAD / n, 4 n >= N, and a block whose start is not valid stores its start.  No atomics, nothing of
+//                     another block read or written: independent of B.  The model-size vectors are clamped to +-79 (+-159 in half
+//                     pixels), so the key's fields always hold d; every staged coordinate is clamped to the frame.
+//                     k_mci_median follows, as it is.
+constexpr int DETAIL_KEY_BIAS = 2048, DETAIL_MAX_R = 4;      // background.py DETAIL_KEY_BIAS, DETAIL_MAX_RADIUS
+
+struct DetailSearchParams {
+  const uint8_t *a, *b;                     // [B, H0, W0, 3]: the key frames at their own size
+  const int16_t* field;                     // [B, Hb, Wb, 2]: the block field of the MODEL-size key frames
+  int16_t* out;                             // [B, H0b, W0b, 2] in whole output pixels, before the median
+  int B, H, W, H0, W0, Hb, Wb, H0b, W0b;
+  int sx, sy;                               // 16.16: (W0 * 65536 + W / 2) / W, (H0 * 65536 + H / 2) / H
+  int half;                                 // the field is in half pixels
+};
+
+// background.pixel_field_scaled's position of output coordinate v (of n0) in 1/256 block of the model's axis (n): 64-bit, once per block
+__device__ inline int detail_pos(int v, int n, int n0) { return (int)(((long long)(2 * v + 1) * n * 16) / n0) - 128; }
+
+template <int R, bool VALID = false>
+__global__ __launch_bounds__(256) void k_detail_search(DetailSearchParams p) {
+  constexpr int WS = MCI_BLOCK + 2 * R, WIN = WS * WS, SIDE = 2 * R + 1, NC = SIDE * SIDE;
+  constexpr int PARTS = (NC * 4 <= 64) ? 4 : (NC * 2 <= 64) ? 2 : 1, ROWS = MCI_BLOCK / PARTS;
+  __shared__ uint8_t s_win[MCI_RUN][2][WIN];
+  __shared__ int s_start[MCI_RUN][2];
+  const int tid = threadIdx.x, b = blockIdx.y;
+  const int nblk = p.H0b * p.W0b, blk0 = blockIdx.x * MCI_RUN;
+  if (tid < MCI_RUN) {
+    int sx = 0, sy = 0;
+    const int blk = blk0 + tid;
+    if (blk < nblk) {
+      const int by = blk / p.W0b, bx = blk - by * p.W0b;
+      const int ty = detail_pos(min(MCI_BLOCK * by + 4, p.H0 - 1), p.H, p.H0), tx = detail_pos(min(MCI_BLOCK * bx + 4, p.W0 - 1), p.W, p.W0);
+      const int fy = ty & 255, fx = tx & 255;
+      const int r0 = min(max(ty >> 8, 0), p.Hb - 1), r1 = min(max((ty >> 8) + 1, 0), p.Hb - 1);
+      const int c0 = min(max(tx >> 8, 0), p.Wb - 1), c1 = min(max((tx >> 8) + 1, 0), p.Wb - 1);
+      const int16_t* f = p.field + (size_t)b * p.Hb * p.Wb * 2;
+      const int lim = p.half ? 2 * MCI_MAX_DISP + 1 : MCI_MAX_DISP;
+      int d[2];
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const int f00 = min(max((int)f[(r0 * p.Wb + c0) * 2 + c], -lim), lim), f01 = min(max((int)f[(r0 * p.Wb + c1) * 2 + c], -lim), lim);
+        const int f10 = min(max((int)f[(r1 * p.Wb + c0) * 2 + c], -lim), lim), f11 = min(max((int)f[(r1 * p.Wb + c1) * 2 + c], -lim), lim);
+        const int d16 = (256 - fy) * ((256 - fx) * f00 + fx * f01) + fy * ((256 - fx) * f10 + fx * f11);
+        const int d8 = (d16 + 128) >> 8;                                                        // 1/256 model px
+        const int ds = (int)(((long long)d8 * (c ? p.sy : p.sx) + 32768) >> 16);               // 1/256 output px
+        d[c] = p.half ? (ds + 256) >> 9 : (ds + 128) >> 8;
+      }
+      sx = d[0]; sy = d[1];
+    }
+    s_start[tid][0] = sx; s_start[tid][1] = sy;
+  }
+  __syncthreads();
+  for (int i = tid; i < MCI_RUN * 2 * WIN; i += 256) {
+    const int j = i / (2 * WIN), rem = i - j * 2 * WIN, which = rem / WIN, e = rem - which * WIN;
+    const int wy = e / WS, wx = e - wy * WS, blk = blk0 + j;
+    if (blk < nblk) {
+      const int by = blk / p.W0b, bx = blk - by * p.W0b, sgn = which ? 1 : -1;
+      const int y = min(max(MCI_BLOCK * by + sgn * s_start[j][1] - R + wy, 0), p.H0 - 1);
+      const int x = min(max(MCI_BLOCK * bx + sgn * s_start[j][0] - R + wx, 0), p.W0 - 1);
+      const uint8_t* px = (which ? p.b : p.a) + (((size_t)b * p.H0 + y) * p.W0 + x) * 3;
+      s_win[j][which][e] = (uint8_t)((77 * px[0] + 150 * px[1] + 29 * px[2] + 128) >> 8);
+    }
+  }
+  __syncthreads();
+  const int wave = tid >> 6, lane = tid & 63;
+  for (int j = wave; j < MCI_RUN; j += 4) {
+    const int blk = blk0 + j;
+    if (blk >= nblk) break;                 // (uniform per wave; no barrier below)
+    const int by = blk / p.W0b, bx = blk - by * p.W0b;
+    const int ph = min(MCI_BLOCK, p.H0 - MCI_BLOCK * by), pw = min(MCI_BLOCK, p.W0 - MCI_BLOCK * bx);
+    const int sx = s_start[j][0], sy = s_start[j][1];
+    const uint8_t *wa = s_win[j][0], *wb = s_win[j][1];
+    int16_t* o = p.out + ((size_t)b * nblk + blk) * 2;
+    if constexpr (VALID) {                  // the start candidate itself has too few valid pixels: nothing to search
+      int xl, xh, yl, yh;
+      mci_valid_span(MCI_BLOCK * bx, pw, sx, p.W0, xl, xh);
+      mci_valid_span(MCI_BLOCK * by, ph, sy, p.H0, yl, yh);
+      if (4 * (xh - xl) * (yh - yl) < pw * ph) {      // (uniform per wave: the shuffles below are not reached by any lane)
+        if (lane == 0) { o[0] = (int16_t)sx; o[1] = (int16_t)sy; }
+        continue;
+      }
+    }
+    unsigned long long best = ~0ull;
+    for (int c0 = 0; c0 < NC * PARTS; c0 += 64) {
+      const int id = c0 + lane, c = id / PARTS, part = id - c * PARTS;
+      const bool active = c < NC;
+      const int ddy = active ? c / SIDE - R : 0, ddx = active ? c - (c / SIDE) * SIDE - R : 0;
+      int xl = 0, xh = pw, yl = 0, yh = ph;      // VALID: the candidate's rectangle, on each of its PARTS lanes
+      if constexpr (VALID) {
+        mci_valid_span(MCI_BLOCK * bx, pw, sx + ddx, p.W0, xl, xh);
+        mci_valid_span(MCI_BLOCK * by, ph, sy + ddy, p.H0, yl, yh);
+      }
+      const int n = (xh - xl) * (yh - yl);
+      int sad = 0;
+      for (int r = part * ROWS; r < (part + 1) * ROWS; ++r) {
+        if (r < ph) {
+          const uint8_t* ra = wa + (r - ddy + R) * WS + (R - ddx);
+          const uint8_t* rb = wb + (r + ddy + R) * WS + (R + ddx);
+          for (int x = 0; x < pw; ++x) {
+            if constexpr (VALID) sad += (r >= yl && r < yh && x >= xl && x < xh) ? abs((int)ra[x] - (int)rb[x]) : 0;
+            else sad += abs((int)ra[x] - (int)rb[x]);
+          }
+        }
+      }
+#pragma unroll
+      for (int m = 1; m < PARTS; m <<= 1) sad += __shfl_xor(sad, m);
+      if constexpr (VALID) sad = (64 * sad) / max(n, 1);      // (n = 0: not a candidate, below)
+      const bool counts = VALID ? active && 4 * n >= pw * ph : active;
+      const int dx = sx + ddx, dy = sy + ddy;
+      const unsigned long long key = ((unsigned long long)(sad + MCI_LAMBDA * (abs(dx) + abs(dy))) << 46) | ((unsigned long long)(dx * dx + dy * dy) << 24) |
+                                     ((unsigned long long)(dy + DETAIL_KEY_BIAS) << 12) | (unsigned long long)(dx + DETAIL_KEY_BIAS);
+      if (counts && key < best) best = key;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      const unsigned long long v = __shfl_xor(best, m);
+      if (v < best) best = v;
+    }
+    if (lane == 0) {
+      o[0] = (int16_t)((int)(best & 4095) - DETAIL_KEY_BIAS);
+      o[1] = (int16_t)((int)((best >> 12) & 4095) - DETAIL_KEY_BIAS);
+    }
+  }
+}
+
 }  // namespace rib

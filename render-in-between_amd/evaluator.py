@@ -578,7 +578,7 @@ class Evaluator:
                              panels=False, panel_frames=False, panel_quality=90, panel_fps=30, panel_encode="host",
                              background="dain", mci_range=32, video=False, video_fps=30, video_quality=90, video_frames=False, frames="png",
                              poses="folder", key_pose_dir=None, upsample_rate=8, motion=None, save_poses=False, mci_border="clamp",
-                             mci_precision="full", output_size="model", png_on="host", mci_person="keep", mci_sampler="bilinear"):
+                             mci_precision="full", output_size="model", png_on="host", mci_person="keep", mci_sampler="bilinear", mci_detail="model"):
         """rank / world: this process's share of the independent units (default: the torch.distributed process
         group when one is initialised, else everything).  Returns the frames THIS rank wrote.
         The call is one `_FolderPipeline` (below): plan a clip -> decode -> upload -> render -> sink, pipelined over units
@@ -633,7 +633,14 @@ class Evaluator:
         background stops pulsing at the key-frame rate.  Catmull-Rom overshoots at strong edges (the result is clamped); the
         exclusion footprint of mci_person="exclude" is 4x4, so the clean / blend seam moves by a pixel; it is still this project's
         interpolation without interior occlusion reasoning, the generator was trained on DAIN backgrounds, and the quality on
-        real footage is unmeasured.  dain_dir may be
+        real footage is unmeasured.
+        mci_detail="keyframes" (default "model"; only with background="mci" and output_size="keyframes"): the model-size field holds
+        whole model pixels, so at full size a block's two samples are misregistered by up to one quantum (3.75 px at 512 -> 1920);
+        one more search per group at the key frames' own size (rib_detail_field; background.mci_detail_field_host) refines every 8x8
+        full-size block's vector by up to +-detail_radius whole output pixels, and the full-size backgrounds are the existing frame
+        entry's (rib_mci_frames / rib_cubic_frames; mci_frames_host) on the full-size key frames with that field.  The model-size
+        floats the chain reads are unchanged.  A wrong model-size vector stays wrong beyond the radius, which is capped at 4 (above a
+        size ratio of 8 it no longer covers the quantum); no interior occlusion reasoning; unmeasured on real footage.  dain_dir may be
         None and is never listed or read; a frame's file is named after its pose file (stem without a trailing "_keypoints").
         On the native path the field is made once per group of segments (rib_mci_field) and every unit's frames by one launch
         (rib_mci_frames) on the upload stream - no DAIN bytes are staged or decoded; a model behind the reference's protocol is
@@ -715,6 +722,7 @@ class Evaluator:
             if not (isinstance(upsample_rate, int) and upsample_rate >= 1 and upsample_rate & (upsample_rate - 1) == 0):
                 raise ValueError("evaluate_from_folder: upsample_rate must be a power of two, got %r" % (upsample_rate,))
         _composite.check_output_size(output_size, "evaluate_from_folder")
+        _background.check_detail(background, output_size, mci_detail)
         mci_levels, mci_border = _background.check_settings(background, mci_range, mci_border, self.resize_on, mci_precision=mci_precision,
                                                             mci_person=mci_person, output_size=output_size, mci_sampler=mci_sampler)
         if output_size == "source" and background == "mci":
@@ -754,11 +762,11 @@ class Evaluator:
         self.metrics = self.metrics_report = None
         pipe = _FolderPipeline(self, model, rank, world, gt_dir, metrics=bool(metrics), mask_dir=mask_dir, pose_mask=bool(pose_mask),
                                panels=bool(panels), panel_frames=bool(panel_frames), panel_quality=int(panel_quality),
-                               panel_encode=panel_encode, background=background, mci_levels=mci_levels, mci_border=mci_border, mci_precision=mci_precision, mci_person=mci_person, mci_sampler=mci_sampler, video=bool(video), video_quality=int(video_quality),
+                               panel_encode=panel_encode, background=background, mci_levels=mci_levels, mci_border=mci_border, mci_precision=mci_precision, mci_person=mci_person, mci_sampler=mci_sampler, mci_detail=mci_detail, video=bool(video), video_quality=int(video_quality),
                                video_frames=bool(video_frames), write_png=frames == "png", output_size=output_size, png_gpu=png_on == "gpu",
                                key_poses=None if poses == "folder" else (motion, key_pose_dir, upsample_rate, poses == "keyframes-linear", bool(save_poses)))
         self.background, self.mci_range, self.mci_border, self.mci_precision = background, mci_range, mci_border, mci_precision
-        self.mci_person, self.mci_sampler = mci_person, mci_sampler
+        self.mci_person, self.mci_sampler, self.mci_detail = mci_person, mci_sampler, mci_detail
         self.output_size = output_size
         self.timings = pipe.tm
         if metrics and pipe.native:
@@ -872,7 +880,7 @@ class _FolderPipeline:
     def __init__(self, ev, model, rank, world, gt_dir, metrics=False, mask_dir=None, pose_mask=False,
                  panels=False, panel_frames=False, panel_quality=90, panel_encode="host", background="dain", mci_levels=3,
                  video=False, video_quality=90, video_frames=False, write_png=True, key_poses=None, mci_border="clamp", mci_precision="full",
-                 output_size="model", png_gpu=False, mci_person="keep", mci_sampler="bilinear"):
+                 output_size="model", png_gpu=False, mci_person="keep", mci_sampler="bilinear", mci_detail="model"):
         # composite.py: the frames' files at the clip's own size - the DAIN frames' ("source") or, under background="mci", the key
         # frame files' ("keyframes": keysize; the backgrounds are then rib_scaled_frames', everything after them is "source"'s code)
         self.source = output_size in ("source", "keyframes")
@@ -882,6 +890,7 @@ class _FolderPipeline:
         self.mci_half = mci_precision == "half"      # background.py's precision: the field is refined once per group, in half pixels
         self.mci_exclude = mci_person == "exclude"   # background.py's "person": the key frames' human masks keep the person out
         self.mci_sampler = mci_sampler               # background.py's sampler: "cubic" = sample_cubic / rib_cubic_* for every background sample
+        self.mci_detail = mci_detail == "keyframes"  # background.py's "detail": the field refined at the key frames' size (output_size="keyframes" only)
         # poses="keyframes": (motion model, key-pose folder, upsample rate, take the linear clip, also write the json folders)
         self.key_poses = key_poses
         # video: the frames' JPEG files (video.py); write_png False (frames="none"): they are the only files of a frame
@@ -915,6 +924,8 @@ class _FolderPipeline:
             raise RuntimeError("video=True: this model has no GPU JPEG kernels for float frames (rib_jpeg_float)")
         if self.keysize and self.native and not hasattr(model, "mci_frames_scaled"):
             raise RuntimeError("output_size='keyframes': this model has no GPU kernel for the key frames' size (rib_scaled_frames)")
+        if self.mci_detail and self.native and not hasattr(model, "mci_detail_field"):
+            raise RuntimeError("mci_detail='keyframes': this model has no GPU kernel for the full-size field (rib_detail_field)")
         if self.source and self.native:
             if ev.resize_on != "gpu" and not self.keysize:
                 raise ValueError("output_size='source' needs resize_on='gpu' on the native path: the background frames' source-size "
@@ -1328,8 +1339,12 @@ class _FolderPipeline:
                             views["mci_keys_src"][0, b].copy_(torch.from_numpy(clip.key_src[k].result(timeout=IO_TIMEOUT_S)))
                             views["mci_keys_src"][1, b].copy_(torch.from_numpy(clip.key_src[k + clip.sample_rate].result(timeout=IO_TIMEOUT_S)))
                         kab0 = views["mci_keys_src"].to(g.device, non_blocking=True)
-                    clip.mci_of[gi] = (kab[0], kab[1], field, kab0[0], kab0[1], qab[0], qab[1])
-                ka, kb, field, ka0, kb0, qa, qb = clip.mci_of[gi]
+                    field0 = None
+                    if self.mci_detail:         # the field refined at the key frames' own size, once per group, behind the field (two launches)
+                        field0 = g.mci_detail_field(kab0[0], kab0[1], field, (ev.height, ev.width), border=self.mci_border,
+                                                    precision="half" if self.mci_half else "full")
+                    clip.mci_of[gi] = (kab[0], kab[1], field, kab0[0], kab0[1], qab[0], qab[1], field0)
+                ka, kb, field, ka0, kb0, qa, qb, field0 = clip.mci_of[gi]
                 if self.mci_exclude:
                     dn = g.mci_frames_masked(ka, kb, qa, qb, field, clip.sample_rate, k_first=c0 + 1, count=Tc,
                                              normalised="both" if self.panels else True, border=self.mci_border, sampler=self.mci_sampler)
@@ -1338,7 +1353,10 @@ class _FolderPipeline:
                                       border=self.mci_border, precision="half" if self.mci_half else "full", sampler=self.mci_sampler)
                 if self.panels:
                     dn, dnu8 = dn
-                if self.keysize:               # ONE launch: the unit's backgrounds uint8 [Tc,B,h0,w0,3], "source"'s staged frames
+                if self.mci_detail:            # ONE launch, the existing frame entry at the key frames' size with the full-size field (whole pixels)
+                    staged = g.mci_frames(ka0, kb0, field0, clip.sample_rate, k_first=c0 + 1, count=Tc, normalised=False, border=self.mci_border,
+                                          sampler=self.mci_sampler)
+                elif self.keysize:             # ONE launch: the unit's backgrounds uint8 [Tc,B,h0,w0,3], "source"'s staged frames
                     staged = g.mci_frames_scaled(ka0, kb0, field, (ev.height, ev.width), clip.sample_rate, k_first=c0 + 1, count=Tc,
                                                  border=self.mci_border, precision="half" if self.mci_half else "full", sampler=self.mci_sampler)
             else:
@@ -1796,7 +1814,13 @@ class _FolderPipeline:
                 # shows the host's normalisation, as the native path's does (normalise_exact)
                 dn = torch.from_numpy(_background.normalised_upload(u8)).unsqueeze(1)
                 dn_shown = torch.from_numpy(_background.normalised(u8)).unsqueeze(1)
-                if self.keysize:                 # the same field, the samples from the key files' own pixels: the files' backgrounds
+                if self.mci_detail:              # the field refined at the key files' own size, then the existing frame definition there
+                    ka0, kb0 = (clip.key_src[j].result(timeout=IO_TIMEOUT_S) for j in (k, k + clip.sample_rate))
+                    field0 = _background.mci_detail_field_host(ka0, kb0, field, (ev.height, ev.width), border=self.mci_border,
+                                                               precision="half" if self.mci_half else "full")
+                    bg0 = _background.mci_frames_host(ka0, kb0, field0, clip.sample_rate, [i - k for i in frames], border=self.mci_border,
+                                                      sampler=self.mci_sampler)
+                elif self.keysize:               # the same field, the samples from the key files' own pixels: the files' backgrounds
                     bg0 = _background.mci_frames_scaled_host(clip.key_src[k].result(timeout=IO_TIMEOUT_S),
                                                              clip.key_src[k + clip.sample_rate].result(timeout=IO_TIMEOUT_S), field,
                                                              (ev.height, ev.width), clip.sample_rate, [i - k for i in frames],

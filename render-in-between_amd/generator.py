@@ -669,6 +669,38 @@ class Generator:
             _native.check(self._h, self._lib.rib_halfpel_refine(self._h, B, H, W, _ptr(a), _ptr(b), _ptr(f), _ptr(res), border, self._stream()))
         return res[0] if single else res
 
+    def mci_detail_field(self, a0_u8, b0_u8, field, model_hw, border="clamp", precision="full"):
+        """The block field refined at the key frames' OWN size on the GPU (rib_detail_field; background.mci_detail_field_host is the
+        definition and is bit-equal): a0_u8, b0_u8 uint8 [B,h0,w0,3] (or [h0,w0,3]) the key frame files' pixels on this device,
+        field the int16 [B,Hb,Wb,2] field of the MODEL-size key frames (mci_field, or mci_refine's in half pixels with
+        precision="half"), model_hw = (H, W) -> int16 [B,ceil(h0/8),ceil(w0/8),2] in whole output pixels: every block starts from
+        the scaled model-size vector at its centre and searches +-detail_radius around it on the full-size lumas, then the median.
+        The frames at that size are mci_frames(a0_u8, b0_u8, F0, ..., normalised=False, precision="full", sampler=...).  Two
+        launches on the current stream."""
+        from .background import BORDERS, PRECISIONS, check_border, check_precision, field_shape, scaled_factors
+        border = BORDERS.index(check_border(border, "mci_detail_field"))
+        precision = PRECISIONS.index(check_precision(precision, "mci_detail_field"))
+        a, b, single = self._mci_pair(a0_u8, b0_u8, "mci_detail_field")
+        B, h0, w0, _ = a.shape
+        H, W = (int(v) for v in model_hw)
+        scaled_factors((H, W), (h0, w0), "mci_detail_field")
+        Hb, Wb = field_shape(H, W)
+        if not torch.is_tensor(field) or field.dtype != torch.int16 or field.device != self.device:
+            raise ValueError("mci_detail_field: field must be an int16 tensor on %s (mci_field)" % (self.device,))
+        f = (field.unsqueeze(0) if field.dim() == 3 else field).contiguous()
+        if tuple(f.shape) != (B, Hb, Wb, 2):
+            raise ValueError("mci_detail_field: the field of %d %dx%d model frames is [%d, %d, %d, 2], got %s" % (B, H, W, B, Hb, Wb, tuple(field.shape)))
+        n = int(self._lib.rib_detail_workspace_bytes(self._h, B, h0, w0))
+        if n == 0:
+            raise ValueError("mci_detail_field: B=%d h0=%d w0=%d: 1 <= B <= 32767, the sides in 1..16384" % (B, h0, w0))
+        H0b, W0b = field_shape(h0, w0)
+        with torch.cuda.device(self.device):
+            ws = torch.empty(n, dtype=torch.uint8, device=self.device)      # (per call: it belongs to the stream the call is enqueued on)
+            res = torch.empty((B, H0b, W0b, 2), dtype=torch.int16, device=self.device)
+            _native.check(self._h, self._lib.rib_detail_field(self._h, B, H, W, h0, w0, _ptr(a), _ptr(b), _ptr(f), precision, border, _ptr(res),
+                                                              _ptr(ws), self._stream()))
+        return res[0] if single else res
+
     def mci_frames(self, a_u8, b_u8, field, sample_rate, k_first=1, count=None, normalised=True, out=None, border="clamp", precision="full",
                    sampler="bilinear", _staging=0):
         """Frames k_first .. k_first + count - 1 (count None: up to sample_rate - 1) of B segments from their key frames and

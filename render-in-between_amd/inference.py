@@ -86,6 +86,15 @@ the model size.  The motion field stays the model-size one; only the background 
 command is then `--poses keyframes --pose-dir DIR --background mci --output-size keyframes --video --frames none`.  It is this
 project's interpolation, not DAIN; the field has the model's resolution (motion detail finer than an 8x8 model block, about 30 px
 at 1080p from 512, is not followed); the person is a cubic enlargement; no interior occlusion reasoning; unmeasured on real footage.
+`--mci-detail keyframes` (default `model`; only with `--background mci --output-size keyframes`): the model-size field holds whole
+model pixels - multiples of 3.75 output pixels at 512 -> 1920 - so a block's two samples are misregistered by up to one quantum and
+the full-size background is a soft double image even where the field is right.  One more search per group, at the key frames' own
+size (rib_detail_field, background.mci_detail_field_host): every 8x8 block of the full-size frame starts from the scaled model-size
+vector and looks +-R whole output pixels around it (R = half the quantum, at most 4), then the median; the full-size backgrounds are
+the existing frame kernels' on the full-size key frames with that field.  The model-size frames the generator reads do not change.
+The limits, plainly: it is this project's interpolation, not DAIN; no interior occlusion reasoning; a model-size vector that is
+wrong stays wrong beyond R; above a size ratio of 8 the radius no longer covers the quantum; whole pixels only at full size (below
+ratio 2 `--mci-precision half` is finer); the person is still a cubic enlargement; real footage is unmeasured.
 """
 import argparse
 import os
@@ -161,7 +170,8 @@ def summary_line(evaluator, rank=0, world=1):
                        % (getattr(evaluator, "mci_range", 32), getattr(evaluator, "mci_border", "clamp"),
                           (", half-pel" if getattr(evaluator, "mci_precision", "full") == "half" else "")
                           + (", person excluded" if getattr(evaluator, "mci_person", "keep") == "exclude" else "")
-                          + (", cubic sampler" if getattr(evaluator, "mci_sampler", "bilinear") == "cubic" else ""))}
+                          + (", cubic sampler" if getattr(evaluator, "mci_sampler", "bilinear") == "cubic" else "")
+                          + (", field refined at the key frames' size" if getattr(evaluator, "mci_detail", "model") == "keyframes" else ""))}
                [getattr(evaluator, "background", "dain")]))
     if getattr(evaluator, "output_size", "model") == "source":
         line += " | files at the source size"
@@ -210,7 +220,7 @@ def main(opts):
                                              panel_fps=30 if opts.panel_fps is None else opts.panel_fps,
                                              panel_encode=opts.panel_encode or "host", background=opts.background, mci_range=opts.mci_range,
                                              mci_border=opts.mci_border, mci_precision=opts.mci_precision, mci_person=opts.mci_person,
-                                             mci_sampler=opts.mci_sampler, video=opts.video, video_fps=30 if opts.video_fps is None else opts.video_fps,
+                                             mci_sampler=opts.mci_sampler, mci_detail=opts.mci_detail, video=opts.video, video_fps=30 if opts.video_fps is None else opts.video_fps,
                                              video_quality=90 if opts.video_quality is None else opts.video_quality,
                                              video_frames=opts.video_frames, frames=opts.frames, output_size=opts.output_size, png_on=opts.png_on,
                                              **poses_kw)
@@ -313,6 +323,15 @@ def build_parser():
                              "at strong edges and the result is clamped; with --mci-person exclude the exclusion footprint is 4x4, so "
                              "the clean/blend seam moves by a pixel; still this project's interpolation, without interior occlusion "
                              "reasoning; the generator was trained on DAIN backgrounds; quality on real footage is unmeasured")
+    parser.add_argument("--mci-detail", default=None,
+                        help="with --background mci --output-size keyframes: 'model' (default): the full-size backgrounds follow the "
+                             "model-size motion field, whose vectors are whole model pixels (multiples of 3.75 output pixels at 512 -> "
+                             "1920), so a block's two samples are misregistered by up to one quantum - a soft double image; 'keyframes': "
+                             "one more search per group at the key frames' own size refines every 8x8 full-size block's vector by up to "
+                             "+-R whole output pixels (R = half the quantum, at most 4), and the existing frame kernels sample the "
+                             "full-size key frames with that field. Still this project's interpolation, without interior occlusion "
+                             "reasoning; a wrong model-size vector stays wrong beyond R; the radius is capped above a size ratio of 8; "
+                             "the person is still a cubic enlargement; quality on real footage is unmeasured")
     parser.add_argument("--video", action="store_true",
                         help="also write every frame of a clip, key frames included, as <save-dir>/Generated_frames/<clip>_video.avi "
                              "(Motion-JPEG; a frame is the JPEG of exactly the bytes its PNG holds, encoded on the GPU)")
@@ -389,6 +408,13 @@ def parse_args(argv=None):
     if opts.mci_sampler not in (None, "bilinear", "cubic"):
         parser.error("--mci-sampler must be 'bilinear' or 'cubic', got %r" % (opts.mci_sampler,))
     opts.mci_sampler = "bilinear" if opts.mci_sampler is None else opts.mci_sampler
+    if opts.mci_detail not in (None, "model", "keyframes"):
+        parser.error("--mci-detail must be 'model' or 'keyframes', got %r" % (opts.mci_detail,))
+    if opts.mci_detail is not None and opts.background != "mci":
+        parser.error("--mci-detail is a setting of --background mci")
+    if opts.mci_detail == "keyframes" and opts.output_size != "keyframes":
+        parser.error("--mci-detail keyframes needs --output-size keyframes (the field is refined at the key frames' own size)")
+    opts.mci_detail = "model" if opts.mci_detail is None else opts.mci_detail
     if opts.mci_person == "exclude" and opts.mci_precision == "half":
         parser.error("--mci-person exclude with --mci-precision half is not supported yet: the half-pel refinement has no masked form "
                      "(a masked rib_halfpel_refine is the follow-up)")

@@ -96,6 +96,8 @@ def main():
     ap.add_argument("--mci-precision", default="full", choices=("full", "half"), help="with --background mci: half-pel refinement of the field (mci_precision=...)")
     ap.add_argument("--mci-person", default="keep", choices=("keep", "exclude"),
                     help="with --background mci: the key frames' human masks are kept out of the interpolation (mci_person=...)")
+    ap.add_argument("--mci-detail", default="model", choices=("model", "keyframes"),
+                    help="with --background mci --output-size keyframes: refine the field at the key frames' size (mci_detail=...)")
     ap.add_argument("--mci-sampler", default="bilinear", choices=("bilinear", "cubic"),
                     help="with --background mci: the 4x4 cubic sampler for every background sample (mci_sampler=...)")
     ap.add_argument("--video", action="store_true", help="also write the frames as <clip>_video.avi, JPEG-encoded on the GPU (video=True)")
@@ -125,6 +127,8 @@ def main():
         ap.error("--mci-precision is a setting of --background mci")
     if a.mci_person != "keep" and a.background != "mci":
         ap.error("--mci-person is a setting of --background mci")
+    if a.mci_detail != "model" and (a.background != "mci" or a.output_size != "keyframes"):
+        ap.error("--mci-detail keyframes is a setting of --background mci --output-size keyframes")
     if a.mci_sampler != "bilinear" and a.background != "mci":
         ap.error("--mci-sampler is a setting of --background mci")
     if a.mci_border != "clamp" and a.background != "mci":
@@ -174,7 +178,8 @@ def main():
                                          **({"mci_border": a.mci_border} if a.mci_border != "clamp" else {}),
                                          **({"mci_precision": a.mci_precision} if a.mci_precision != "full" else {}),
                                          **({"mci_person": a.mci_person} if a.mci_person != "keep" else {}),
-                                         **({"mci_sampler": a.mci_sampler} if a.mci_sampler != "bilinear" else {}))
+                                         **({"mci_sampler": a.mci_sampler} if a.mci_sampler != "bilinear" else {}),
+                                         **({"mci_detail": a.mci_detail} if a.mci_detail != "model" else {}))
             torch.cuda.synchronize()
             walls.append(time.perf_counter() - t0)
         tm = dict(E.timings)
@@ -190,6 +195,7 @@ def main():
                       "mci_precision": a.mci_precision if a.background == "mci" else None,
                       "mci_person": a.mci_person if a.background == "mci" else None,
                       "mci_sampler": a.mci_sampler if a.background == "mci" else None,
+                      "mci_detail": a.mci_detail if a.background == "mci" else None,
                       "metrics": a.metrics, "pose_mask": a.pose_mask, "metrics_overall": overall, "panels": a.panels, "panel_encode": a.panel_encode,
                       "video": a.video, "frames_written": a.frames, "png_on": a.png_on, "png_bytes_last_run": png_bytes, "poses": a.poses, "stage1_plus_bridge_ms_per_clip": stage1_ms,
                       "wall_s": wall, "wall_s_runs": [round(w, 4) for w in walls[1:]], "frames_per_s_end_to_end": n / wall,
