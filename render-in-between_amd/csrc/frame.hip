@@ -458,7 +458,123 @@ static bool mci_layout(int B, int H, int W, int levels, MciLayout* L) {
   L->total = o;
   return true;
 }
+
+// rib_masked_*: rib_mci_field's workspace, then the mask planes of the levels, the searched flags (one plane, level 0's size: a
+// level's flags are read - by the fill, on the top level only - before the next level writes its own) and the top level's field
+// before the fill
+struct MaskedLayout { MciLayout L; size_t m[MCI_MAX_LEVELS], flags, raw, total; };
+static void masked_extend(int B, int levels, MaskedLayout* M) {      // M->L is mci_layout's of these levels
+  const MciLayout& L = M->L;
+  size_t o = L.total;
+  for (int l = 0; l < levels; ++l) { M->m[l] = o; o += align256((size_t)2 * B * L.h[l] * L.w[l]); }
+  M->flags = o; o += align256((size_t)B * L.Hb[0] * L.Wb[0]);
+  M->raw = o; o += align256((size_t)B * L.Hb[levels - 1] * L.Wb[levels - 1] * 2 * sizeof(int16_t));
+  M->total = o;
+}
+
+// rib_detail_field: the workspace holds the full-size field before the median and nothing else
+static bool detail_layout(int B, int H0, int W0, int* H0b, int* W0b, size_t* bytes) {
+  if (B < 1 || B > 32767 || H0 < 1 || W0 < 1 || H0 > MCI_MAX_SIDE || W0 > MCI_MAX_SIDE) return false;
+  *H0b = (H0 + MCI_BLOCK - 1) / MCI_BLOCK; *W0b = (W0 + MCI_BLOCK - 1) / MCI_BLOCK;
+  if ((size_t)B * *H0b * *W0b > (size_t)INT32_MAX / 2) return false;
+  *bytes = align256((size_t)B * *H0b * *W0b * 2 * sizeof(int16_t));
+  return true;
+}
+
+// ---- one function per rule of the rib_* entries below.  A rule's refusal stands here once; an entry lists its rules in its own
+// order, chained by ||, and reports the first that fails.
+constexpr int SCALED_MAX_RATIO = 16;        // background.SCALED_MAX_RATIO: the largest unit * k * DS stays below 2^31
+
+static int refuse(FrameState* h, const std::string& msg) { return fail(h, RIB_ERR_INVALID, msg); }
+static bool off_alignment(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+
+static int mci_handle(rib_handle* handle, const char* who, FrameState** h) {
+  *h = frame_state(handle);
+  if (!*h) return RIB_ERR_INVALID;
+  return (*h)->device < 0 ? refuse(*h, fmt("%s: host-only handle", who)) : RIB_OK;
+}
+static int need_pointers(FrameState* h, const char* who, bool all) { return all ? RIB_OK : refuse(h, fmt("%s: null pointer", who)); }
+static int need_an_output(FrameState* h, const char* who, const void* f32, const void* u8) {
+  return f32 || u8 ? RIB_OK : refuse(h, fmt("%s: both outputs are null", who));
+}
+static int check_shape(FrameState* h, const char* who, int B, int H, int W, int levels, MciLayout* L) {
+  if (mci_layout(B, H, W, levels, L)) return RIB_OK;
+  return refuse(h, fmt("%s: B=%d H=%d W=%d: 1 <= B <= 32767, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", who, B, H, W, MCI_MAX_SIDE));
+}
+static int check_frames_shape(FrameState* h, const char* who, int T, int B, int H, int W, MciLayout* L) {
+  if (T >= 1 && mci_layout(B, H, W, MCI_MIN_LEVELS, L) && (size_t)T * B <= 65535) return RIB_OK;
+  return refuse(h, fmt("%s: T=%d B=%d H=%d W=%d: T, B >= 1, T * B <= 65535, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", who, T, B, H, W, MCI_MAX_SIDE));
+}
+static int check_keyframe_sides(FrameState* h, const char* who, int H0, int W0) {
+  if (H0 >= 1 && W0 >= 1 && H0 <= MCI_MAX_SIDE && W0 <= MCI_MAX_SIDE) return RIB_OK;
+  return refuse(h, fmt("%s: H0=%d W0=%d: the key frames' sides lie in 1..%d", who, H0, W0, MCI_MAX_SIDE));
+}
+static int check_ratio(FrameState* h, const char* who, int H, int W, int H0, int W0) {
+  constexpr int R = SCALED_MAX_RATIO;
+  if (W0 <= R * W && W <= R * W0 && H0 <= R * H && H <= R * H0) return RIB_OK;
+  return refuse(h, fmt("%s: key frames %dx%d, model %dx%d: each axis within 1/%d .. %d times the model's", who, H0, W0, H, W, R, R));
+}
+static int check_rate(FrameState* h, const char* who, int sample_rate) {
+  if (sample_rate >= 1 && sample_rate <= MCI_MAX_RATE && (sample_rate & (sample_rate - 1)) == 0) return RIB_OK;
+  return refuse(h, fmt("%s: sample_rate=%d: a power of two in 1..%d", who, sample_rate, MCI_MAX_RATE));
+}
+static int check_span(FrameState* h, const char* who, int T, int sample_rate, int k_first) {
+  if (k_first >= 0 && k_first + T - 1 <= sample_rate) return RIB_OK;
+  return refuse(h, fmt("%s: frames %d..%d are outside the segment 0..%d", who, k_first, k_first + T - 1, sample_rate));
+}
+static int check_border(FrameState* h, const char* who, int border) {
+  return border == 0 || border == 1 ? RIB_OK : refuse(h, fmt("%s: border=%d: 0 (clamped samples) or 1 (valid samples only)", who, border));
+}
+static int check_precision(FrameState* h, const char* who, int precision) {
+  if (precision == 0 || precision == 1) return RIB_OK;
+  return refuse(h, fmt("%s: precision=%d: 0 (the field in whole pixels) or 1 (in half pixels)", who, precision));
+}
+static int check_staging(FrameState* h, const char* who, int staging) {
+  return staging == 0 || staging == 1 ? RIB_OK : refuse(h, fmt("%s: staging=%d: 0 (the per-tile rule) or 1 (never stage: a diagnostic)", who, staging));
+}
+static int check_frame_pointers(FrameState* h, const char* who, const void* field_i16, const void* out_f32) {
+  return off_alignment(field_i16, 1) || off_alignment(out_f32, 3) ? refuse(h, fmt("%s: misaligned pointer", who)) : RIB_OK;
+}
+
+static int scale_16_16(int n0, int n) { return (int)(((int64_t)n0 * 65536 + n / 2) / n); }      // background.scaled_factors
+// what k_scaled_frames and k_cubic_scaled want of the two sizes: the 16.16 factors, the divmods behind TX and TY, the row's room in LDS
+static void scaled_geometry(int H, int W, int H0, int W0, ScaledFramesParams* fp) {
+  fp->sx = scale_16_16(W0, W); fp->sy = scale_16_16(H0, H);
+  fp->qax = 32 * W / W0; fp->rax = 32 * W % W0; fp->q0x = 16 * W / W0; fp->r0x = 16 * W % W0;
+  fp->qay = 32 * H / H0; fp->ray = 32 * H % H0; fp->q0y = 16 * H / H0; fp->r0y = 16 * H % H0;
+  fp->v_off = (W0 * 3 + 31) & ~15;          // the row at any shift 0..15, whole 16-byte lines
+}
+
+static int enqueue_median(FrameState* h, hipStream_t st, const int16_t* in, int16_t* out, int B, int Hb, int Wb) {
+  const int n = B * Hb * Wb;
+  hipLaunchKernelGGL(k_mci_median, dim3(std::min((n + 255) / 256, 1024)), dim3(256), 0, st, in, out, B, Hb, Wb);
+  HIP_TRY(h, hipGetLastError());
+  return RIB_OK;
+}
 }  // namespace
+
+extern "C++" {
+namespace {
+// the frame kernels' parameter structs all carry the segment the same way: s, its log2 and the first frame
+template <typename P>
+static void set_segment(P& fp, int sample_rate, int k_first) {
+  fp.s = sample_rate; fp.k_first = k_first;
+  fp.ls = 0;
+  while ((1 << fp.ls) < sample_rate) ++fp.ls;
+}
+
+// the cubic kernels' dynamic LDS may pass 64 KB (rows wider than about 11 000 pixels): the kernel is told so
+template <typename K, typename P>
+static hipError_t cubic_launch(K kernel, dim3 grid, size_t lds, hipStream_t st, const P& params) {
+  if (lds > 65536) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, params);
+  return hipGetLastError();
+}
+}  // namespace
+}  // extern "C++"
 
 void rib_mci_field_shape(int H, int W, int* Hb, int* Wb) {
   if (Hb) *Hb = H < 1 ? 0 : (H + MCI_BLOCK - 1) / MCI_BLOCK;
@@ -471,94 +587,31 @@ size_t rib_mci_workspace_bytes(rib_handle* h, int B, int H, int W, int levels) {
   return L.total;
 }
 
-int rib_mci_field(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
-                  int levels, int border, void* workspace, void* hip_stream) {
-  FrameState* h = frame_state(handle);
-  if (!h) return RIB_ERR_INVALID;
-  if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_mci_field: host-only handle");
-  if (!a_u8 || !b_u8 || !field_i16 || !workspace) return fail(h, RIB_ERR_INVALID, "rib_mci_field: null pointer");
-  if (levels < MCI_MIN_LEVELS || levels > MCI_MAX_LEVELS)
-    return fail(h, RIB_ERR_INVALID, fmt("rib_mci_field: levels=%d: %d..%d pyramid levels (a search over 32, 64 or 128 px)", levels, MCI_MIN_LEVELS, MCI_MAX_LEVELS));
-  if (border != 0 && border != 1)
-    return fail(h, RIB_ERR_INVALID, fmt("rib_mci_field: border=%d: 0 (clamped samples) or 1 (valid samples only)", border));
-  MciLayout L;
-  if (!mci_layout(B, H, W, levels, &L))
-    return fail(h, RIB_ERR_INVALID, fmt("rib_mci_field: B=%d H=%d W=%d: 1 <= B <= 32767, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", B, H, W, MCI_MAX_SIDE));
-  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0 || (reinterpret_cast<uintptr_t>(field_i16) & 3) != 0)
-    return fail(h, RIB_ERR_INVALID, "rib_mci_field: workspace must be 16-byte aligned, the field 4-byte aligned");
-  HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  uint8_t* ws = static_cast<uint8_t*>(workspace);
-  MciLumaParams lp;
-  lp.a = a_u8; lp.b = b_u8; lp.y0 = ws + L.y[0]; lp.y1 = ws + L.y[1]; lp.y2 = ws + L.y[2];
-  lp.y3 = levels > 3 ? ws + L.y[3] : nullptr; lp.y4 = levels > 4 ? ws + L.y[4] : nullptr;
-  lp.B = B; lp.H = H; lp.W = W; lp.h1 = L.h[1]; lp.w1 = L.w[1]; lp.h2 = L.h[2]; lp.w2 = L.w[2]; lp.tilesX = (W + 31) / 32;
-  lp.h3 = levels > 3 ? L.h[3] : 0; lp.w3 = levels > 3 ? L.w[3] : 0; lp.h4 = levels > 4 ? L.h[4] : 0; lp.w4 = levels > 4 ? L.w[4] : 0;
-  hipLaunchKernelGGL(k_mci_luma_pyramid, dim3(lp.tilesX * ((H + 31) / 32), 2 * B), dim3(256), 0, st, lp);
-  HIP_TRY(h, hipGetLastError());
-  const int top = levels - 1;
-  for (int l = top; l >= 0; --l) {
-    MciSearchParams sp;
-    sp.y = ws + L.y[l]; sp.coarse = l == top ? nullptr : reinterpret_cast<const int16_t*>(ws + L.f[l + 1]);
-    sp.out = reinterpret_cast<int16_t*>(ws + L.f[l]);
-    sp.B = B; sp.h = L.h[l]; sp.w = L.w[l]; sp.Hb = L.Hb[l]; sp.Wb = L.Wb[l];
-    sp.Hbc = l == top ? 1 : L.Hb[l + 1]; sp.Wbc = l == top ? 1 : L.Wb[l + 1];
-    const dim3 grid((sp.Hb * sp.Wb + MCI_RUN - 1) / MCI_RUN, B);
-    if (border) {
-      if (l == top) hipLaunchKernelGGL((k_mci_search<MCI_TOP_R, true>), grid, dim3(256), 0, st, sp);
-      else hipLaunchKernelGGL((k_mci_search<1, true>), grid, dim3(256), 0, st, sp);
-    } else {
-      if (l == top) hipLaunchKernelGGL(k_mci_search<MCI_TOP_R>, grid, dim3(256), 0, st, sp);
-      else hipLaunchKernelGGL(k_mci_search<1>, grid, dim3(256), 0, st, sp);
-    }
-    HIP_TRY(h, hipGetLastError());
-  }
-  const int n = B * L.Hb[0] * L.Wb[0];
-  hipLaunchKernelGGL(k_mci_median, dim3(std::min((n + 255) / 256, 1024)), dim3(256), 0, st,
-                     reinterpret_cast<const int16_t*>(ws + L.f[0]), field_i16, B, L.Hb[0], L.Wb[0]);
-  HIP_TRY(h, hipGetLastError());
-  return RIB_OK;
-}
-
-// rib_masked_*: rib_mci_field's workspace, then the mask planes of the levels, the searched flags (one plane, level 0's size: a
-// level's flags are read - by the fill, on the top level only - before the next level writes its own) and the top level's field
-// before the fill
-namespace {
-struct MaskedLayout { MciLayout L; size_t m[MCI_MAX_LEVELS], flags, raw, total; };
-static bool masked_layout(int B, int H, int W, int levels, MaskedLayout* M) {
-  if (!mci_layout(B, H, W, levels, &M->L)) return false;
-  const MciLayout& L = M->L;
-  size_t o = L.total;
-  for (int l = 0; l < levels; ++l) { M->m[l] = o; o += align256((size_t)2 * B * L.h[l] * L.w[l]); }
-  M->flags = o; o += align256((size_t)B * L.Hb[0] * L.Wb[0]);
-  M->raw = o; o += align256((size_t)B * L.Hb[levels - 1] * L.Wb[levels - 1] * 2 * sizeof(int16_t));
-  M->total = o;
-  return true;
-}
-}  // namespace
-
 size_t rib_masked_workspace_bytes(rib_handle* h, int B, int H, int W, int levels) {
   MaskedLayout M;
-  if (!h || !masked_layout(B, H, W, levels, &M)) return 0;
+  if (!h || !mci_layout(B, H, W, levels, &M.L)) return 0;
+  masked_extend(B, levels, &M);
   return M.total;
 }
 
-int rib_masked_field(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const uint8_t* ma_u8,
-                     const uint8_t* mb_u8, int16_t* field_i16, int levels, int border, void* workspace, void* hip_stream) {
-  FrameState* h = frame_state(handle);
-  if (!h) return RIB_ERR_INVALID;
-  if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_masked_field: host-only handle");
-  if (!a_u8 || !b_u8 || !ma_u8 || !mb_u8 || !field_i16 || !workspace) return fail(h, RIB_ERR_INVALID, "rib_masked_field: null pointer");
-  if (levels < MCI_MIN_LEVELS || levels > MCI_MAX_LEVELS)
-    return fail(h, RIB_ERR_INVALID, fmt("rib_masked_field: levels=%d: %d..%d pyramid levels (a search over 32, 64 or 128 px)", levels, MCI_MIN_LEVELS, MCI_MAX_LEVELS));
-  if (border != 0 && border != 1)
-    return fail(h, RIB_ERR_INVALID, fmt("rib_masked_field: border=%d: 0 (clamped samples) or 1 (valid samples only)", border));
+// rib_mci_field / rib_masked_field: one body.  masked: ma_u8, mb_u8 are wanted, the workspace is rib_masked_workspace_bytes', and the
+// mask pyramid, the <.., MASKED = true> searches with their flags and the top level's fill run as well.
+static int mci_field_enqueue(const char* who, bool masked, rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8,
+                             const uint8_t* ma_u8, const uint8_t* mb_u8, int16_t* field_i16, int levels, int border, void* workspace,
+                             void* hip_stream) {
+  FrameState* h;
   MaskedLayout M;
-  if (!masked_layout(B, H, W, levels, &M))
-    return fail(h, RIB_ERR_INVALID, fmt("rib_masked_field: B=%d H=%d W=%d: 1 <= B <= 32767, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", B, H, W, MCI_MAX_SIDE));
-  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0 || (reinterpret_cast<uintptr_t>(field_i16) & 3) != 0)
-    return fail(h, RIB_ERR_INVALID, "rib_masked_field: workspace must be 16-byte aligned, the field 4-byte aligned");
-  const MciLayout& L = M.L;
+  MciLayout& L = M.L;
+  int rc;
+  if ((rc = mci_handle(handle, who, &h)) ||
+      (rc = need_pointers(h, who, a_u8 && b_u8 && field_i16 && workspace && (!masked || (ma_u8 && mb_u8)))))
+    return rc;
+  if (levels < MCI_MIN_LEVELS || levels > MCI_MAX_LEVELS)
+    return refuse(h, fmt("%s: levels=%d: %d..%d pyramid levels (a search over 32, 64 or 128 px)", who, levels, MCI_MIN_LEVELS, MCI_MAX_LEVELS));
+  if ((rc = check_border(h, who, border)) || (rc = check_shape(h, who, B, H, W, levels, &L))) return rc;
+  if (off_alignment(workspace, 15) || off_alignment(field_i16, 3))
+    return refuse(h, fmt("%s: workspace must be 16-byte aligned, the field 4-byte aligned", who));
+  if (masked) masked_extend(B, levels, &M);
   HIP_TRY(h, hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   uint8_t* ws = static_cast<uint8_t*>(workspace);
@@ -570,82 +623,72 @@ int rib_masked_field(rib_handle* handle, int B, int H, int W, const uint8_t* a_u
   const dim3 tiles(lp.tilesX * ((H + 31) / 32), 2 * B);
   hipLaunchKernelGGL(k_mci_luma_pyramid, tiles, dim3(256), 0, st, lp);
   HIP_TRY(h, hipGetLastError());
-  MciMaskParams mp;
-  mp.ma = ma_u8; mp.mb = mb_u8; mp.B = B; mp.levels = levels; mp.tilesX = lp.tilesX;
-  for (int l = 0; l < MCI_MAX_LEVELS; ++l) {
-    mp.m[l] = l < levels ? ws + M.m[l] : nullptr; mp.h[l] = l < levels ? L.h[l] : 0; mp.w[l] = l < levels ? L.w[l] : 0;
+  if (masked) {
+    MciMaskParams mp;
+    mp.ma = ma_u8; mp.mb = mb_u8; mp.B = B; mp.levels = levels; mp.tilesX = lp.tilesX;
+    for (int l = 0; l < MCI_MAX_LEVELS; ++l) {
+      mp.m[l] = l < levels ? ws + M.m[l] : nullptr; mp.h[l] = l < levels ? L.h[l] : 0; mp.w[l] = l < levels ? L.w[l] : 0;
+    }
+    hipLaunchKernelGGL(k_mci_mask_pyramid, tiles, dim3(256), 0, st, mp);
+    HIP_TRY(h, hipGetLastError());
   }
-  hipLaunchKernelGGL(k_mci_mask_pyramid, tiles, dim3(256), 0, st, mp);
-  HIP_TRY(h, hipGetLastError());
+  void (*const search[2][2][2])(MciSearchParams) = {      // [masked][border][top level]
+      {{k_mci_search<1, false, false>, k_mci_search<MCI_TOP_R, false, false>}, {k_mci_search<1, true, false>, k_mci_search<MCI_TOP_R, true, false>}},
+      {{k_mci_search<1, false, true>, k_mci_search<MCI_TOP_R, false, true>}, {k_mci_search<1, true, true>, k_mci_search<MCI_TOP_R, true, true>}}};
   const int top = levels - 1;
   for (int l = top; l >= 0; --l) {
     MciSearchParams sp;
     sp.y = ws + L.y[l]; sp.coarse = l == top ? nullptr : reinterpret_cast<const int16_t*>(ws + L.f[l + 1]);
-    sp.out = reinterpret_cast<int16_t*>(ws + (l == top ? M.raw : L.f[l]));
+    sp.out = reinterpret_cast<int16_t*>(ws + (masked && l == top ? M.raw : L.f[l]));
     sp.B = B; sp.h = L.h[l]; sp.w = L.w[l]; sp.Hb = L.Hb[l]; sp.Wb = L.Wb[l];
     sp.Hbc = l == top ? 1 : L.Hb[l + 1]; sp.Wbc = l == top ? 1 : L.Wb[l + 1];
-    sp.m = ws + M.m[l]; sp.searched = ws + M.flags;
+    sp.m = masked ? ws + M.m[l] : nullptr; sp.searched = masked ? ws + M.flags : nullptr;
     const dim3 grid((sp.Hb * sp.Wb + MCI_RUN - 1) / MCI_RUN, B);
-    if (border) {
-      if (l == top) hipLaunchKernelGGL((k_mci_search<MCI_TOP_R, true, true>), grid, dim3(256), 0, st, sp);
-      else hipLaunchKernelGGL((k_mci_search<1, true, true>), grid, dim3(256), 0, st, sp);
-    } else {
-      if (l == top) hipLaunchKernelGGL((k_mci_search<MCI_TOP_R, false, true>), grid, dim3(256), 0, st, sp);
-      else hipLaunchKernelGGL((k_mci_search<1, false, true>), grid, dim3(256), 0, st, sp);
-    }
+    hipLaunchKernelGGL(search[masked][border][l == top], grid, dim3(256), 0, st, sp);
     HIP_TRY(h, hipGetLastError());
-    if (l == top) {                         // the fill reads the raw field and the flags, and writes the field the level below starts from
+    if (masked && l == top) {               // the fill reads the raw field and the flags, and writes the field the level below starts from
       const int nt = B * sp.Hb * sp.Wb;
       hipLaunchKernelGGL(k_mci_fill, dim3(std::min((nt + 255) / 256, 1024)), dim3(256), 0, st, reinterpret_cast<const int16_t*>(ws + M.raw),
                          static_cast<const uint8_t*>(ws + M.flags), reinterpret_cast<int16_t*>(ws + L.f[top]), B, sp.Hb, sp.Wb);
       HIP_TRY(h, hipGetLastError());
     }
   }
-  const int n = B * L.Hb[0] * L.Wb[0];
-  hipLaunchKernelGGL(k_mci_median, dim3(std::min((n + 255) / 256, 1024)), dim3(256), 0, st,
-                     reinterpret_cast<const int16_t*>(ws + L.f[0]), field_i16, B, L.Hb[0], L.Wb[0]);
-  HIP_TRY(h, hipGetLastError());
-  return RIB_OK;
+  return enqueue_median(h, st, reinterpret_cast<const int16_t*>(ws + L.f[0]), field_i16, B, L.Hb[0], L.Wb[0]);
+}
+
+int rib_mci_field(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,
+                  int levels, int border, void* workspace, void* hip_stream) {
+  return mci_field_enqueue("rib_mci_field", false, handle, B, H, W, a_u8, b_u8, nullptr, nullptr, field_i16, levels, border, workspace, hip_stream);
+}
+
+int rib_masked_field(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const uint8_t* ma_u8,
+                     const uint8_t* mb_u8, int16_t* field_i16, int levels, int border, void* workspace, void* hip_stream) {
+  return mci_field_enqueue("rib_masked_field", true, handle, B, H, W, a_u8, b_u8, ma_u8, mb_u8, field_i16, levels, border, workspace, hip_stream);
 }
 
 int rib_halfpel_refine(rib_handle* handle, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const int16_t* field_i16,
                    int16_t* field_half_i16, int border, void* hip_stream) {
-  FrameState* h = frame_state(handle);
-  if (!h) return RIB_ERR_INVALID;
-  if (h->device < 0) return fail(h, RIB_ERR_INVALID, "rib_halfpel_refine: host-only handle");
-  if (!a_u8 || !b_u8 || !field_i16 || !field_half_i16) return fail(h, RIB_ERR_INVALID, "rib_halfpel_refine: null pointer");
-  if (border != 0 && border != 1)
-    return fail(h, RIB_ERR_INVALID, fmt("rib_halfpel_refine: border=%d: 0 (clamped samples) or 1 (valid samples only)", border));
+  static const char who[] = "rib_halfpel_refine";
+  FrameState* h;
   MciLayout L;
-  if (!mci_layout(B, H, W, MCI_MIN_LEVELS, &L))
-    return fail(h, RIB_ERR_INVALID, fmt("rib_halfpel_refine: B=%d H=%d W=%d: 1 <= B <= 32767, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", B, H, W, MCI_MAX_SIDE));
-  if ((reinterpret_cast<uintptr_t>(field_i16) & 3) != 0 || (reinterpret_cast<uintptr_t>(field_half_i16) & 3) != 0)
-    return fail(h, RIB_ERR_INVALID, "rib_halfpel_refine: the fields must be 4-byte aligned");
+  int rc;
+  if ((rc = mci_handle(handle, who, &h)) || (rc = need_pointers(h, who, a_u8 && b_u8 && field_i16 && field_half_i16)) ||
+      (rc = check_border(h, who, border)) || (rc = check_shape(h, who, B, H, W, MCI_MIN_LEVELS, &L)))
+    return rc;
+  if (off_alignment(field_i16, 3) || off_alignment(field_half_i16, 3)) return refuse(h, fmt("%s: the fields must be 4-byte aligned", who));
   HIP_TRY(h, hipSetDevice(h->device));
   MciRefineParams rp;
   rp.a = a_u8; rp.b = b_u8; rp.field = field_i16; rp.out = field_half_i16;
   rp.B = B; rp.H = H; rp.W = W; rp.Hb = L.Hb[0]; rp.Wb = L.Wb[0];
   const dim3 grid((rp.Hb * rp.Wb + MCI_RUN - 1) / MCI_RUN, B);
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  if (border) hipLaunchKernelGGL(k_mci_refine<true>, grid, dim3(256), 0, st, rp);
-  else hipLaunchKernelGGL(k_mci_refine<false>, grid, dim3(256), 0, st, rp);
+  void (*const kernels[2])(MciRefineParams) = {k_mci_refine<false>, k_mci_refine<true>};
+  hipLaunchKernelGGL(kernels[border], grid, dim3(256), 0, st, rp);
   HIP_TRY(h, hipGetLastError());
   return RIB_OK;
 }
 
-// rib_detail_field: the block field of the FULL-SIZE key frames (background.mci_detail_field_host).  The workspace holds the field before the
-// median and nothing else.
-namespace {
-constexpr int DETAIL_MAX_RATIO = 16;        // background.SCALED_MAX_RATIO
-static bool detail_layout(int B, int H0, int W0, int* H0b, int* W0b, size_t* bytes) {
-  if (B < 1 || B > 32767 || H0 < 1 || W0 < 1 || H0 > MCI_MAX_SIDE || W0 > MCI_MAX_SIDE) return false;
-  *H0b = (H0 + MCI_BLOCK - 1) / MCI_BLOCK; *W0b = (W0 + MCI_BLOCK - 1) / MCI_BLOCK;
-  if ((size_t)B * *H0b * *W0b > (size_t)INT32_MAX / 2) return false;
-  *bytes = align256((size_t)B * *H0b * *W0b * 2 * sizeof(int16_t));
-  return true;
-}
-}  // namespace
-
+// rib_detail_field: the block field of the FULL-SIZE key frames (background.mci_detail_field_host)
 size_t rib_detail_workspace_bytes(rib_handle* h, int B, int H0, int W0) {
   int H0b, W0b;
   size_t n;
@@ -656,31 +699,24 @@ size_t rib_detail_workspace_bytes(rib_handle* h, int B, int H0, int W0) {
 int rib_detail_field(rib_handle* handle, int B, int H, int W, int H0, int W0, const uint8_t* a0_u8, const uint8_t* b0_u8,
                      const int16_t* field_i16, int precision, int border, int16_t* out_field_i16, void* workspace, void* hip_stream) {
   static const char who[] = "rib_detail_field";
-  FrameState* h = frame_state(handle);
-  if (!h) return RIB_ERR_INVALID;
-  if (h->device < 0) return fail(h, RIB_ERR_INVALID, fmt("%s: host-only handle", who));
-  if (!a0_u8 || !b0_u8 || !field_i16 || !out_field_i16 || !workspace) return fail(h, RIB_ERR_INVALID, fmt("%s: null pointer", who));
+  FrameState* h;
   MciLayout L;
-  if (!mci_layout(B, H, W, MCI_MIN_LEVELS, &L))
-    return fail(h, RIB_ERR_INVALID, fmt("%s: B=%d H=%d W=%d: 1 <= B <= 32767, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", who, B, H, W, MCI_MAX_SIDE));
-  int H0b, W0b;
+  int rc, H0b, W0b;
   size_t bytes;
+  if ((rc = mci_handle(handle, who, &h)) || (rc = need_pointers(h, who, a0_u8 && b0_u8 && field_i16 && out_field_i16 && workspace)) ||
+      (rc = check_shape(h, who, B, H, W, MCI_MIN_LEVELS, &L)))
+    return rc;
   if (!detail_layout(B, H0, W0, &H0b, &W0b, &bytes))
-    return fail(h, RIB_ERR_INVALID, fmt("%s: B=%d H0=%d W0=%d: the key frames' sides lie in 1..%d, B * ceil(H0/8) * ceil(W0/8) < 2^30", who, B, H0, W0, MCI_MAX_SIDE));
-  if (W0 > DETAIL_MAX_RATIO * W || W > DETAIL_MAX_RATIO * W0 || H0 > DETAIL_MAX_RATIO * H || H > DETAIL_MAX_RATIO * H0)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: key frames %dx%d, model %dx%d: each axis within 1/%d .. %d times the model's", who, H0, W0, H, W, DETAIL_MAX_RATIO, DETAIL_MAX_RATIO));
-  if (precision != 0 && precision != 1)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: precision=%d: 0 (the field in pixels) or 1 (in half pixels)", who, precision));
-  if (border != 0 && border != 1)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: border=%d: 0 (clamped samples) or 1 (valid samples only)", who, border));
-  if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0 || (reinterpret_cast<uintptr_t>(field_i16) & 3) != 0 || (reinterpret_cast<uintptr_t>(out_field_i16) & 3) != 0)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: workspace must be 16-byte aligned, the fields 4-byte aligned", who));
+    return refuse(h, fmt("%s: B=%d H0=%d W0=%d: the key frames' sides lie in 1..%d, B * ceil(H0/8) * ceil(W0/8) < 2^30", who, B, H0, W0, MCI_MAX_SIDE));
+  if ((rc = check_ratio(h, who, H, W, H0, W0)) || (rc = check_precision(h, who, precision)) || (rc = check_border(h, who, border))) return rc;
+  if (off_alignment(workspace, 15) || off_alignment(field_i16, 3) || off_alignment(out_field_i16, 3))
+    return refuse(h, fmt("%s: workspace must be 16-byte aligned, the fields 4-byte aligned", who));
   HIP_TRY(h, hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   DetailSearchParams sp;
   sp.a = a0_u8; sp.b = b0_u8; sp.field = field_i16; sp.out = static_cast<int16_t*>(workspace);
   sp.B = B; sp.H = H; sp.W = W; sp.H0 = H0; sp.W0 = W0; sp.Hb = L.Hb[0]; sp.Wb = L.Wb[0]; sp.H0b = H0b; sp.W0b = W0b;
-  sp.sx = (int)(((int64_t)W0 * 65536 + W / 2) / W); sp.sy = (int)(((int64_t)H0 * 65536 + H / 2) / H);
+  sp.sx = scale_16_16(W0, W); sp.sy = scale_16_16(H0, H);
   sp.half = precision;
   const int c = std::max((W0 + W - 1) / W, (H0 + H - 1) / H);
   const int radius = std::min(DETAIL_MAX_R, std::max(1, (c + 1) / 2));      // background.detail_radius
@@ -690,11 +726,7 @@ int rib_detail_field(rib_handle* handle, int B, int H, int W, int H0, int W0, co
       {k_detail_search<1, true>, k_detail_search<2, true>, k_detail_search<3, true>, k_detail_search<4, true>}};
   hipLaunchKernelGGL(kernels[border][radius - 1], grid, dim3(256), 0, st, sp);
   HIP_TRY(h, hipGetLastError());
-  const int n = B * H0b * W0b;
-  hipLaunchKernelGGL(k_mci_median, dim3(std::min((n + 255) / 256, 1024)), dim3(256), 0, st, static_cast<const int16_t*>(workspace), out_field_i16, B,
-                     H0b, W0b);
-  HIP_TRY(h, hipGetLastError());
-  return RIB_OK;
+  return enqueue_median(h, st, static_cast<const int16_t*>(workspace), out_field_i16, B, H0b, W0b);
 }
 
 // rib_mci_frames / rib_halfpel_frames: one body, one kernel template; half: the field is rib_halfpel_refine's, in half pixels
@@ -702,48 +734,26 @@ int rib_detail_field(rib_handle* handle, int B, int H, int W, int H0, int W0, co
 static int mci_frames_enqueue(const char* who, bool half, rib_handle* handle, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8,
                               const int16_t* field_i16, int sample_rate, int k_first, int border, float* out_f32_nchw, uint8_t* out_u8_nhwc,
                               void* hip_stream, bool masked = false, const uint8_t* ma_u8 = nullptr, const uint8_t* mb_u8 = nullptr) {
-  FrameState* h = frame_state(handle);
-  if (!h) return RIB_ERR_INVALID;
-  if (h->device < 0) return fail(h, RIB_ERR_INVALID, fmt("%s: host-only handle", who));
-  if (!a_u8 || !b_u8 || !field_i16 || (masked && (!ma_u8 || !mb_u8))) return fail(h, RIB_ERR_INVALID, fmt("%s: null pointer", who));
-  if (!out_f32_nchw && !out_u8_nhwc) return fail(h, RIB_ERR_INVALID, fmt("%s: both outputs are null", who));
+  FrameState* h;
   MciLayout L;
-  if (T < 1 || !mci_layout(B, H, W, MCI_MIN_LEVELS, &L) || (size_t)T * B > 65535)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: T=%d B=%d H=%d W=%d: T, B >= 1, T * B <= 65535, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", who, T, B, H, W, MCI_MAX_SIDE));
-  if (sample_rate < 1 || sample_rate > MCI_MAX_RATE || (sample_rate & (sample_rate - 1)) != 0)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: sample_rate=%d: a power of two in 1..%d", who, sample_rate, MCI_MAX_RATE));
-  if (k_first < 0 || k_first + T - 1 > sample_rate)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: frames %d..%d are outside the segment 0..%d", who, k_first, k_first + T - 1, sample_rate));
-  if (border != 0 && border != 1)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: border=%d: 0 (clamped samples) or 1 (valid samples only)", who, border));
-  if ((reinterpret_cast<uintptr_t>(field_i16) & 1) != 0 || (reinterpret_cast<uintptr_t>(out_f32_nchw) & 3) != 0)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: misaligned pointer", who));
+  int rc;
+  if ((rc = mci_handle(handle, who, &h)) || (rc = need_pointers(h, who, a_u8 && b_u8 && field_i16 && (!masked || (ma_u8 && mb_u8)))) ||
+      (rc = need_an_output(h, who, out_f32_nchw, out_u8_nhwc)) || (rc = check_frames_shape(h, who, T, B, H, W, &L)) ||
+      (rc = check_rate(h, who, sample_rate)) || (rc = check_span(h, who, T, sample_rate, k_first)) || (rc = check_border(h, who, border)) ||
+      (rc = check_frame_pointers(h, who, field_i16, out_f32_nchw)))
+    return rc;
   MciFramesParams fp;
   fp.a = a_u8; fp.b = b_u8; fp.field = field_i16; fp.out_f32 = out_f32_nchw; fp.out_u8 = out_u8_nhwc;
-  fp.T = T; fp.B = B; fp.H = H; fp.W = W; fp.Hb = L.Hb[0]; fp.Wb = L.Wb[0]; fp.s = sample_rate; fp.k_first = k_first;
-  fp.ls = 0;
-  while ((1 << fp.ls) < sample_rate) ++fp.ls;
-  fp.vec = (W % 4 == 0 && (reinterpret_cast<uintptr_t>(out_f32_nchw) & 15) == 0 && (reinterpret_cast<uintptr_t>(out_u8_nhwc) & 3) == 0) ? 1 : 0;
+  fp.T = T; fp.B = B; fp.H = H; fp.W = W; fp.Hb = L.Hb[0]; fp.Wb = L.Wb[0];
+  set_segment(fp, sample_rate, k_first);
+  fp.vec = (W % 4 == 0 && !off_alignment(out_f32_nchw, 15) && !off_alignment(out_u8_nhwc, 3)) ? 1 : 0;
   fp.ma = ma_u8; fp.mb = mb_u8;
   HIP_TRY(h, hipSetDevice(h->device));
   const size_t lds = out_u8_nhwc ? (size_t)W * 3 + 32 : 0;
-  const dim3 grid(H, T * B);
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  if (masked) {
-    if (half) {
-      if (border) hipLaunchKernelGGL((k_mci_frames<true, true, true>), grid, dim3(256), lds, st, fp);
-      else hipLaunchKernelGGL((k_mci_frames<false, true, true>), grid, dim3(256), lds, st, fp);
-    } else {
-      if (border) hipLaunchKernelGGL((k_mci_frames<true, false, true>), grid, dim3(256), lds, st, fp);
-      else hipLaunchKernelGGL((k_mci_frames<false, false, true>), grid, dim3(256), lds, st, fp);
-    }
-  } else if (half) {
-    if (border) hipLaunchKernelGGL((k_mci_frames<true, true>), grid, dim3(256), lds, st, fp);
-    else hipLaunchKernelGGL((k_mci_frames<false, true>), grid, dim3(256), lds, st, fp);
-  } else {
-    if (border) hipLaunchKernelGGL((k_mci_frames<true, false>), grid, dim3(256), lds, st, fp);
-    else hipLaunchKernelGGL((k_mci_frames<false, false>), grid, dim3(256), lds, st, fp);
-  }
+  void (*const kernels[2][2][2])(MciFramesParams) = {      // [masked][half][border]
+      {{k_mci_frames<false, false, false>, k_mci_frames<true, false, false>}, {k_mci_frames<false, true, false>, k_mci_frames<true, true, false>}},
+      {{k_mci_frames<false, false, true>, k_mci_frames<true, false, true>}, {k_mci_frames<false, true, true>, k_mci_frames<true, true, true>}}};
+  hipLaunchKernelGGL(kernels[masked][half][border], dim3(H, T * B), dim3(256), lds, reinterpret_cast<hipStream_t>(hip_stream), fp);
   HIP_TRY(h, hipGetLastError());
   return RIB_OK;
 }
@@ -763,12 +773,30 @@ int rib_halfpel_frames(rib_handle* handle, int T, int B, int H, int W, const uin
 int rib_masked_frames(rib_handle* handle, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const uint8_t* ma_u8,
                       const uint8_t* mb_u8, const int16_t* field_i16, int sample_rate, int k_first, int border, int precision,
                       float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream) {
-  if (precision != 0 && precision != 1) {
-    FrameState* h = frame_state(handle);
-    return h ? fail(h, RIB_ERR_INVALID, fmt("rib_masked_frames: precision=%d: 0 (the field in whole pixels) or 1 (in half pixels)", precision)) : RIB_ERR_INVALID;
-  }
+  FrameState* h = frame_state(handle);
+  if (!h) return RIB_ERR_INVALID;
+  if (int rc = check_precision(h, "rib_masked_frames", precision)) return rc;      // (this entry's first rule, before host-only, as it always was)
   return mci_frames_enqueue("rib_masked_frames", precision == 1, handle, T, B, H, W, a_u8, b_u8, field_i16, sample_rate, k_first, border,
                             out_f32_nchw, out_u8_nhwc, hip_stream, true, ma_u8, mb_u8);
+}
+
+// rib_scaled_frames / rib_cubic_scaled: the rules they share, in their order (staging = 0 where the entry has none), and what of
+// ScaledFramesParams follows from the shapes and the segment
+static int scaled_checks(const char* who, rib_handle* handle, int T, int B, int H, int W, int H0, int W0, bool pointers, const int16_t* field_i16,
+                         int sample_rate, int k_first, int border, int precision, int staging, FrameState** hp, ScaledFramesParams* fp) {
+  MciLayout L;
+  int rc;
+  if ((rc = mci_handle(handle, who, hp))) return rc;
+  FrameState* h = *hp;
+  if ((rc = need_pointers(h, who, pointers)) || (rc = check_frames_shape(h, who, T, B, H, W, &L)) || (rc = check_keyframe_sides(h, who, H0, W0)) ||
+      (rc = check_ratio(h, who, H, W, H0, W0)) || (rc = check_rate(h, who, sample_rate)) || (rc = check_span(h, who, T, sample_rate, k_first)) ||
+      (rc = check_border(h, who, border)) || (rc = check_precision(h, who, precision)) || (rc = check_staging(h, who, staging)) ||
+      (rc = check_frame_pointers(h, who, field_i16, nullptr)))
+    return rc;
+  fp->T = T; fp->B = B; fp->H0 = H0; fp->W0 = W0; fp->Hb = L.Hb[0]; fp->Wb = L.Wb[0];
+  set_segment(*fp, sample_rate, k_first);
+  scaled_geometry(H, W, H0, W0, fp);
+  return RIB_OK;
 }
 
 // rib_scaled_frames: rib_mci_frames' uint8 output at the key frames' own size H0 x W0 from the MODEL-size (H x W) field
@@ -776,120 +804,56 @@ int rib_scaled_frames(rib_handle* handle, int T, int B, int H, int W, int H0, in
                       const int16_t* field_i16, int sample_rate, int k_first, int border, int precision, uint8_t* out_u8_nhwc,
                       void* hip_stream) {
   static const char who[] = "rib_scaled_frames";
-  constexpr int MAX_RATIO = 16;             // background.SCALED_MAX_RATIO: the largest unit * k * DS stays below 2^31
-  FrameState* h = frame_state(handle);
-  if (!h) return RIB_ERR_INVALID;
-  if (h->device < 0) return fail(h, RIB_ERR_INVALID, fmt("%s: host-only handle", who));
-  if (!a0_u8 || !b0_u8 || !field_i16 || !out_u8_nhwc) return fail(h, RIB_ERR_INVALID, fmt("%s: null pointer", who));
-  MciLayout L;
-  if (T < 1 || !mci_layout(B, H, W, MCI_MIN_LEVELS, &L) || (size_t)T * B > 65535)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: T=%d B=%d H=%d W=%d: T, B >= 1, T * B <= 65535, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", who, T, B, H, W, MCI_MAX_SIDE));
-  if (H0 < 1 || W0 < 1 || H0 > MCI_MAX_SIDE || W0 > MCI_MAX_SIDE)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: H0=%d W0=%d: the key frames' sides lie in 1..%d", who, H0, W0, MCI_MAX_SIDE));
-  if (W0 > MAX_RATIO * W || W > MAX_RATIO * W0 || H0 > MAX_RATIO * H || H > MAX_RATIO * H0)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: key frames %dx%d, model %dx%d: each axis within 1/%d .. %d times the model's", who, H0, W0, H, W, MAX_RATIO, MAX_RATIO));
-  if (sample_rate < 1 || sample_rate > MCI_MAX_RATE || (sample_rate & (sample_rate - 1)) != 0)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: sample_rate=%d: a power of two in 1..%d", who, sample_rate, MCI_MAX_RATE));
-  if (k_first < 0 || k_first + T - 1 > sample_rate)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: frames %d..%d are outside the segment 0..%d", who, k_first, k_first + T - 1, sample_rate));
-  if (border != 0 && border != 1)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: border=%d: 0 (clamped samples) or 1 (valid samples only)", who, border));
-  if (precision != 0 && precision != 1)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: precision=%d: 0 (the field in pixels) or 1 (in half pixels)", who, precision));
-  if ((reinterpret_cast<uintptr_t>(field_i16) & 1) != 0) return fail(h, RIB_ERR_INVALID, fmt("%s: misaligned pointer", who));
+  FrameState* h;
   ScaledFramesParams fp;
+  int rc;
+  if ((rc = scaled_checks(who, handle, T, B, H, W, H0, W0, a0_u8 && b0_u8 && field_i16 && out_u8_nhwc, field_i16, sample_rate, k_first, border,
+                          precision, 0, &h, &fp)))
+    return rc;
   fp.a = a0_u8; fp.b = b0_u8; fp.field = field_i16; fp.out = out_u8_nhwc;
-  fp.T = T; fp.B = B; fp.H0 = H0; fp.W0 = W0; fp.Hb = L.Hb[0]; fp.Wb = L.Wb[0]; fp.s = sample_rate; fp.k_first = k_first;
-  fp.ls = 0;
-  while ((1 << fp.ls) < sample_rate) ++fp.ls;
-  fp.sx = (int)(((int64_t)W0 * 65536 + W / 2) / W); fp.sy = (int)(((int64_t)H0 * 65536 + H / 2) / H);
-  fp.qax = 32 * W / W0; fp.rax = 32 * W % W0; fp.q0x = 16 * W / W0; fp.r0x = 16 * W % W0;
-  fp.qay = 32 * H / H0; fp.ray = 32 * H % H0; fp.q0y = 16 * H / H0; fp.r0y = 16 * H % H0;
-  fp.vec = (W0 % 4 == 0 && (reinterpret_cast<uintptr_t>(out_u8_nhwc) & 3) == 0) ? 1 : 0;
-  fp.v_off = (W0 * 3 + 31) & ~15;           // the row at any shift 0..15, whole 16-byte lines
+  fp.vec = (W0 % 4 == 0 && !off_alignment(out_u8_nhwc, 3)) ? 1 : 0;
   const size_t with_field = (size_t)fp.v_off + (size_t)fp.Wb * sizeof(int2);
   fp.stage = with_field <= 65536 ? 1 : 0;
   const size_t lds = fp.stage ? with_field : (size_t)fp.v_off;
   HIP_TRY(h, hipSetDevice(h->device));
-  const dim3 grid(H0, T * B);
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  if (precision) {
-    if (border) hipLaunchKernelGGL((k_scaled_frames<true, true>), grid, dim3(256), lds, st, fp);
-    else hipLaunchKernelGGL((k_scaled_frames<false, true>), grid, dim3(256), lds, st, fp);
-  } else {
-    if (border) hipLaunchKernelGGL((k_scaled_frames<true, false>), grid, dim3(256), lds, st, fp);
-    else hipLaunchKernelGGL((k_scaled_frames<false, false>), grid, dim3(256), lds, st, fp);
-  }
+  void (*const kernels[2][2])(ScaledFramesParams) = {      // [precision][border]
+      {k_scaled_frames<false, false>, k_scaled_frames<true, false>}, {k_scaled_frames<false, true>, k_scaled_frames<true, true>}};
+  hipLaunchKernelGGL(kernels[precision][border], dim3(H0, T * B), dim3(256), lds, reinterpret_cast<hipStream_t>(hip_stream), fp);
   HIP_TRY(h, hipGetLastError());
   return RIB_OK;
 }
 
 // rib_cubic_frames / rib_cubic_scaled: the 4x4 cubic sampler (background.sample_cubic) behind rib_mci_frames' / rib_halfpel_frames' /
 // rib_masked_frames' and rib_scaled_frames' contracts.  The dynamic LDS is the output row, [the blended field row,] the 2 KB weight
-// table and - staging = 0 - the four waves' windows; beyond 64 KB (rows wider than about 11 000 pixels) the kernel is told so.
-extern "C++" {
-namespace {
-template <typename K, typename P>
-static hipError_t cubic_launch(K kernel, dim3 grid, size_t lds, hipStream_t st, const P& params) {
-  if (lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, params);
-  return hipGetLastError();
-}
-}  // namespace
-}  // extern "C++"
+// table and - staging = 0 - the four waves' windows.
 
 int rib_cubic_frames(rib_handle* handle, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const uint8_t* ma_u8,
                      const uint8_t* mb_u8, const int16_t* field_i16, int sample_rate, int k_first, int border, int precision, int staging,
                      float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream) {
   static const char who[] = "rib_cubic_frames";
-  FrameState* h = frame_state(handle);
-  if (!h) return RIB_ERR_INVALID;
-  if (h->device < 0) return fail(h, RIB_ERR_INVALID, fmt("%s: host-only handle", who));
-  if (!a_u8 || !b_u8 || !field_i16) return fail(h, RIB_ERR_INVALID, fmt("%s: null pointer", who));
-  if ((ma_u8 == nullptr) != (mb_u8 == nullptr))
-    return fail(h, RIB_ERR_INVALID, fmt("%s: exactly one mask is null (both: the person is excluded; neither: kept)", who));
-  if (!out_f32_nchw && !out_u8_nhwc) return fail(h, RIB_ERR_INVALID, fmt("%s: both outputs are null", who));
+  FrameState* h;
   MciLayout L;
-  if (T < 1 || !mci_layout(B, H, W, MCI_MIN_LEVELS, &L) || (size_t)T * B > 65535)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: T=%d B=%d H=%d W=%d: T, B >= 1, T * B <= 65535, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", who, T, B, H, W, MCI_MAX_SIDE));
-  if (sample_rate < 1 || sample_rate > MCI_MAX_RATE || (sample_rate & (sample_rate - 1)) != 0)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: sample_rate=%d: a power of two in 1..%d", who, sample_rate, MCI_MAX_RATE));
-  if (k_first < 0 || k_first + T - 1 > sample_rate)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: frames %d..%d are outside the segment 0..%d", who, k_first, k_first + T - 1, sample_rate));
-  if (border != 0 && border != 1)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: border=%d: 0 (clamped samples) or 1 (valid samples only)", who, border));
-  if (precision != 0 && precision != 1)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: precision=%d: 0 (the field in whole pixels) or 1 (in half pixels)", who, precision));
-  if (staging != 0 && staging != 1)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: staging=%d: 0 (the per-tile rule) or 1 (never stage: a diagnostic)", who, staging));
-  if ((reinterpret_cast<uintptr_t>(field_i16) & 1) != 0 || (reinterpret_cast<uintptr_t>(out_f32_nchw) & 3) != 0)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: misaligned pointer", who));
+  int rc;
+  if ((rc = mci_handle(handle, who, &h)) || (rc = need_pointers(h, who, a_u8 && b_u8 && field_i16))) return rc;
+  if ((ma_u8 == nullptr) != (mb_u8 == nullptr))
+    return refuse(h, fmt("%s: exactly one mask is null (both: the person is excluded; neither: kept)", who));
+  if ((rc = need_an_output(h, who, out_f32_nchw, out_u8_nhwc)) || (rc = check_frames_shape(h, who, T, B, H, W, &L)) ||
+      (rc = check_rate(h, who, sample_rate)) || (rc = check_span(h, who, T, sample_rate, k_first)) || (rc = check_border(h, who, border)) ||
+      (rc = check_precision(h, who, precision)) || (rc = check_staging(h, who, staging)) ||
+      (rc = check_frame_pointers(h, who, field_i16, out_f32_nchw)))
+    return rc;
   CubicFramesParams fp;
   fp.a = a_u8; fp.b = b_u8; fp.ma = ma_u8; fp.mb = mb_u8; fp.field = field_i16; fp.out_f32 = out_f32_nchw; fp.out_u8 = out_u8_nhwc;
-  fp.T = T; fp.B = B; fp.H = H; fp.W = W; fp.Hb = L.Hb[0]; fp.Wb = L.Wb[0]; fp.s = sample_rate; fp.k_first = k_first;
-  fp.ls = 0;
-  while ((1 << fp.ls) < sample_rate) ++fp.ls;
+  fp.T = T; fp.B = B; fp.H = H; fp.W = W; fp.Hb = L.Hb[0]; fp.Wb = L.Wb[0];
+  set_segment(fp, sample_rate, k_first);
   fp.stage = staging == 0 ? 1 : 0;
   fp.w_off = out_u8_nhwc ? (W * 3 + 32 + 15) & ~15 : 0;
   const size_t lds = (size_t)fp.w_off + CUBIC_WTAB_BYTES + (fp.stage ? CUBIC_WIN_BYTES : 0);
   HIP_TRY(h, hipSetDevice(h->device));
-  const dim3 grid(H, T * B);
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  const int variant = (ma_u8 ? 4 : 0) | (precision ? 2 : 0) | (border ? 1 : 0);
-  hipError_t e = hipSuccess;
-  switch (variant) {
-    case 0: e = cubic_launch(k_cubic_frames<false, false, false>, grid, lds, st, fp); break;
-    case 1: e = cubic_launch(k_cubic_frames<true, false, false>, grid, lds, st, fp); break;
-    case 2: e = cubic_launch(k_cubic_frames<false, true, false>, grid, lds, st, fp); break;
-    case 3: e = cubic_launch(k_cubic_frames<true, true, false>, grid, lds, st, fp); break;
-    case 4: e = cubic_launch(k_cubic_frames<false, false, true>, grid, lds, st, fp); break;
-    case 5: e = cubic_launch(k_cubic_frames<true, false, true>, grid, lds, st, fp); break;
-    case 6: e = cubic_launch(k_cubic_frames<false, true, true>, grid, lds, st, fp); break;
-    default: e = cubic_launch(k_cubic_frames<true, true, true>, grid, lds, st, fp); break;
-  }
+  void (*const kernels[2][2][2])(CubicFramesParams) = {      // [masked][precision][border]
+      {{k_cubic_frames<false, false, false>, k_cubic_frames<true, false, false>}, {k_cubic_frames<false, true, false>, k_cubic_frames<true, true, false>}},
+      {{k_cubic_frames<false, false, true>, k_cubic_frames<true, false, true>}, {k_cubic_frames<false, true, true>, k_cubic_frames<true, true, true>}}};
+  const hipError_t e = cubic_launch(kernels[ma_u8 != nullptr][precision][border], dim3(H, T * B), lds, reinterpret_cast<hipStream_t>(hip_stream), fp);
   HIP_TRY(h, e);
   return RIB_OK;
 }
@@ -898,54 +862,23 @@ int rib_cubic_scaled(rib_handle* handle, int T, int B, int H, int W, int H0, int
                      const int16_t* field_i16, int sample_rate, int k_first, int border, int precision, int staging, uint8_t* out_u8_nhwc,
                      void* hip_stream) {
   static const char who[] = "rib_cubic_scaled";
-  constexpr int MAX_RATIO = 16;             // background.SCALED_MAX_RATIO
-  FrameState* h = frame_state(handle);
-  if (!h) return RIB_ERR_INVALID;
-  if (h->device < 0) return fail(h, RIB_ERR_INVALID, fmt("%s: host-only handle", who));
-  if (!a0_u8 || !b0_u8 || !field_i16 || !out_u8_nhwc) return fail(h, RIB_ERR_INVALID, fmt("%s: null pointer", who));
-  MciLayout L;
-  if (T < 1 || !mci_layout(B, H, W, MCI_MIN_LEVELS, &L) || (size_t)T * B > 65535)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: T=%d B=%d H=%d W=%d: T, B >= 1, T * B <= 65535, H and W in 1..%d, B * ceil(H/8) * ceil(W/8) < 2^30", who, T, B, H, W, MCI_MAX_SIDE));
-  if (H0 < 1 || W0 < 1 || H0 > MCI_MAX_SIDE || W0 > MCI_MAX_SIDE)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: H0=%d W0=%d: the key frames' sides lie in 1..%d", who, H0, W0, MCI_MAX_SIDE));
-  if (W0 > MAX_RATIO * W || W > MAX_RATIO * W0 || H0 > MAX_RATIO * H || H > MAX_RATIO * H0)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: key frames %dx%d, model %dx%d: each axis within 1/%d .. %d times the model's", who, H0, W0, H, W, MAX_RATIO, MAX_RATIO));
-  if (sample_rate < 1 || sample_rate > MCI_MAX_RATE || (sample_rate & (sample_rate - 1)) != 0)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: sample_rate=%d: a power of two in 1..%d", who, sample_rate, MCI_MAX_RATE));
-  if (k_first < 0 || k_first + T - 1 > sample_rate)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: frames %d..%d are outside the segment 0..%d", who, k_first, k_first + T - 1, sample_rate));
-  if (border != 0 && border != 1)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: border=%d: 0 (clamped samples) or 1 (valid samples only)", who, border));
-  if (precision != 0 && precision != 1)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: precision=%d: 0 (the field in pixels) or 1 (in half pixels)", who, precision));
-  if (staging != 0 && staging != 1)
-    return fail(h, RIB_ERR_INVALID, fmt("%s: staging=%d: 0 (the per-tile rule) or 1 (never stage: a diagnostic)", who, staging));
-  if ((reinterpret_cast<uintptr_t>(field_i16) & 1) != 0) return fail(h, RIB_ERR_INVALID, fmt("%s: misaligned pointer", who));
+  FrameState* h;
   CubicScaledParams cp;
   ScaledFramesParams& fp = cp.f;
+  int rc;
+  if ((rc = scaled_checks(who, handle, T, B, H, W, H0, W0, a0_u8 && b0_u8 && field_i16 && out_u8_nhwc, field_i16, sample_rate, k_first, border,
+                          precision, staging, &h, &fp)))
+    return rc;
   fp.a = a0_u8; fp.b = b0_u8; fp.field = field_i16; fp.out = out_u8_nhwc;
-  fp.T = T; fp.B = B; fp.H0 = H0; fp.W0 = W0; fp.Hb = L.Hb[0]; fp.Wb = L.Wb[0]; fp.s = sample_rate; fp.k_first = k_first;
-  fp.ls = 0;
-  while ((1 << fp.ls) < sample_rate) ++fp.ls;
-  fp.sx = (int)(((int64_t)W0 * 65536 + W / 2) / W); fp.sy = (int)(((int64_t)H0 * 65536 + H / 2) / H);
-  fp.qax = 32 * W / W0; fp.rax = 32 * W % W0; fp.q0x = 16 * W / W0; fp.r0x = 16 * W % W0;
-  fp.qay = 32 * H / H0; fp.ray = 32 * H % H0; fp.q0y = 16 * H / H0; fp.r0y = 16 * H % H0;
   fp.vec = 0;
-  fp.v_off = (W0 * 3 + 31) & ~15;           // the row at any shift 0..15, whole 16-byte lines
-  fp.stage = 1;                             // the blended field row always has room: at most 49 168 + 16 384 + 2 048 + 29 184 bytes of the CU's 160 KB
+  fp.stage = 1;                            // the blended field row always has room: at most 49 168 + 16 384 + 2 048 + 29 184 bytes of the CU's 160 KB
   cp.w_off = fp.v_off + ((fp.Wb * (int)sizeof(int2) + 15) & ~15);
   cp.stage_win = staging == 0 ? 1 : 0;
   const size_t lds = (size_t)cp.w_off + CUBIC_WTAB_BYTES + (cp.stage_win ? CUBIC_WIN_BYTES : 0);
   HIP_TRY(h, hipSetDevice(h->device));
-  const dim3 grid(H0, T * B);
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  hipError_t e = hipSuccess;
-  switch ((precision ? 2 : 0) | (border ? 1 : 0)) {
-    case 0: e = cubic_launch(k_cubic_scaled<false, false>, grid, lds, st, cp); break;
-    case 1: e = cubic_launch(k_cubic_scaled<true, false>, grid, lds, st, cp); break;
-    case 2: e = cubic_launch(k_cubic_scaled<false, true>, grid, lds, st, cp); break;
-    default: e = cubic_launch(k_cubic_scaled<true, true>, grid, lds, st, cp); break;
-  }
+  void (*const kernels[2][2])(CubicScaledParams) = {      // [precision][border]
+      {k_cubic_scaled<false, false>, k_cubic_scaled<true, false>}, {k_cubic_scaled<false, true>, k_cubic_scaled<true, true>}};
+  const hipError_t e = cubic_launch(kernels[precision][border], dim3(H0, T * B), lds, reinterpret_cast<hipStream_t>(hip_stream), cp);
   HIP_TRY(h, e);
   return RIB_OK;
 }

@@ -1,83 +1,78 @@
-// mci.hip.h — motion-compensated interpolation of a segment's two key frames: the folder driver's background="mci"
-// (rib_mci_field / rib_halfpel_refine / rib_mci_frames / rib_halfpel_frames, rib_scaled_frames for output_size="keyframes", and
-// rib_masked_field / rib_masked_frames for mci_person="exclude"; include/rib.h).  This project's interpolation, not DAIN.
+// mci.hip.h — motion-compensated interpolation of a segment's two key frames: the folder driver's background="mci" (include/rib.h:
+// rib_mci_field / rib_masked_field / rib_halfpel_refine / rib_detail_field make the block field; rib_mci_frames / rib_halfpel_frames /
+// rib_masked_frames / rib_scaled_frames / rib_cubic_frames / rib_cubic_scaled the frames).  This project's interpolation, not DAIN.
+// background.py states every result in integers; every kernel here is bit-equal to it.
 //
-// background.py (mci_field_host, mci_refine_host, mci_frames_host, mci_frames_scaled_host) states the result in integers; every kernel
-// here is bit-equal to it.
+// SHARED PIECES
+//   mci_luma        Y = (77 R + 150 G + 29 B + 128) >> 8: the pyramid's level 0, and what k_mci_refine and k_detail_search stage.
+//   mci_valid_span  border = 1: the pixels of a block whose p - d and p + d lie inside the plane, per axis - a closed-form rectangle.
+//   The frame kernels' (above k_mci_frames): mci_offsets (the two samples' offsets k D / s and (s-k) D / s; HALF: the field is in half
+//   pixels, the multiplier a compile-time constant), mci_inside (VALID: a sample is valid when its position lies in [0, (H-1) << 8] x
+//   [0, (W-1) << 8]), mci_blend (where exactly one of the two samples is ok the output is that sample instead of the blend),
+//   mci_field_at (D(p) bilinear from the block field: exact, 1/256 px), the scaled pair's mci_scaled_pos / mci_field_row / mci_scaled_d,
+//   mci_store_row (the uint8 NHWC row through LDS as 16-byte stores contiguous across the workgroup, k_panel's scheme).
+//   k_scaled_frames and k_cubic_scaled are written with all of them, k_cubic_frames with offsets, blend, field_at and store_row,
+//   k_mci_frames with store_row.  The three block matchers and k_mci_frames' arms are written out: profiles/r22_mci_refactor.txt.
 //
-//   k_mci_luma_pyramid  grid (tiles of 32 x 32, 2B): luma Y = (77 R + 150 G + 29 B + 128) >> 8 of one tile and, from LDS, its
-//                       16 x 16 of level 1 and 8 x 8 of level 2 ((2x2 parents, clamped, + 2) >> 2) - and, where a wider search
-//                       wants them (y3, y4 not null), its 4 x 4 of level 3 and 2 x 2 of level 4: aligned tiles nest, a
-//                       clamped parent is the tile's own.  Image n < B is A[n], else B[n - B].
-//   k_mci_search<R>     grid (runs of MCI_RUN blocks, B): bilateral block matching of one pyramid level.  A workgroup owns a
-//                       run of MCI_RUN consecutive blocks; it stages, once, the two luma windows of every block - (8 + 2R)^2
-//                       bytes of A around p - start and of B around p + start, already clamped - in LDS; a wave then takes a
-//                       block, its lanes the candidates (R = 4: 81 candidates, one per lane in two passes; R = 1: 9
-//                       candidates x 4 row pairs, summed over the 4 lanes by shuffles), and the winner is the wave minimum
-//                       of the packed key (background.pack_key_wide: cost << 30 | dx^2 + dy^2 << 16 | dy + 128 << 8 | dx + 128,
-//                       room for the +-79 of five levels): the order of the tuple (cost, |d|^2, dy, dx), whatever the lane
-//                       order - and whatever the layout, so three levels give background.pack_key's winners.  No atomics.
-//                       The top level of L (3, 4 or 5) runs <MCI_TOP_R> from start 0, every level below <1>.
-//                       <R, VALID = true> (border = 1, background.py's border="valid"): the one-sided cost at the frame border.
-//                       The staged windows are the same clamped ones; a candidate's valid pixels - p - d and p + d both inside
-//                       the plane - are a closed-form rectangle of the block (from the block's origin, d and h, w); the SAD
-//                       sums over it only, by a select per pixel inside the default's loops, whose bounds are uniform per
-//                       block (loops from the rectangle's own, per-lane bounds took 36.8 us where these take 19.6 on level 0 of
-//                       512 x 512, B = 4: profiles/r13_mci_border.txt); n = nx * ny needs no mask and no reduction (the four row
-//                       lanes of R = 1 sum their SADs and all know n), cost = 64 * SAD / n + LAMBDA's term, candidates with
-//                       4 n < N do not compete, and a block whose start itself is such a candidate (uniform per wave) stores
-//                       its start.
-//   k_mci_median        3x3 componentwise median of the level-0 field, clamped.
-//   k_mci_refine        (rib_halfpel_refine; background.mci_refine_host) grid (runs of MCI_RUN blocks, B), one launch shaped like
-//                       k_mci_search<1>: the half-pel refinement of the field after the median.  A workgroup stages, per block,
-//                       the clamped 10 x 10 INTEGER luma windows of A around p - d and of B around p + d, luma computed from the
-//                       RGB bytes while staging (no workspace, nothing of rib_mci_field's is read); a wave takes a block, its
-//                       lanes the 9 candidates h = 2 d + e x 4 row pairs; a half-pel value is the rounded mean of the one, two or
-//                       four staged integers around it (the definition's half_plane; the clamped window repeats an edge pixel
-//                       where the half-pel plane is clamped, and the mean of a pixel with itself is the pixel); the winner is the
-//                       wave minimum of background.pack_key_half.  <VALID = true>: the rectangle of p -+ ceil(|h| / 2) inside
-//                       the plane, as above.  A block reads only its own vector, staged before any is written: out may be the
-//                       input.  |d| is clamped to 79 (max_disp(5)), so the key's fields always hold h.
-//   k_mci_frames        grid (H, T * B): a workgroup owns ONE row of one frame; a thread takes 4 consecutive x: D(p) bilinear
-//                       from the block field (exact, 1/256 px), the two fixed-point bilinear samples, the blend; float4 stores
-//                       per channel plane of the normalised NCHW tensor, and the uint8 NHWC row through LDS as 16-byte
-//                       stores contiguous across the wave (k_panel's scheme).  Either output may be null.  <VALID = true>:
-//                       a sample is valid when its position lies in [0, (H-1) << 8] x [0, (W-1) << 8]; where exactly one of
-//                       the two is, the output is that sample instead of the blend (four comparisons per sample, a select).
-//                       <VALID, HALF = true> (rib_halfpel_frames): the field is in half pixels, the offsets k D / s and
-//                       (s-k) D / s; the multiplier is a compile-time constant, <VALID, false> is the code it was.
-//   k_scaled_frames     (rib_scaled_frames; background.mci_frames_scaled_host) grid (H0, T * B): k_mci_frames at the key frames' OWN
-//                       size H0 x W0 - the field stays the model-size one (H x W), the samples are taken from the full-size key
-//                       frames.  The row's TY, r0, r1, fy are uniform per workgroup, so the two field rows it needs are blended
-//                       vertically ONCE, V[c] = (256-fy) f[r0][c] + fy f[r1][c] (exact: integers), into LDS - Wb (dx, dy) int32 pairs,
-//                       at most 16 KB - and a pixel reads two of them: D16 = (256-fx) V[c0] + fx V[c1], the definition's sum in another
-//                       order.  TX = ((2 X0 + 1) 16 W) // W0 - 128 would need 33 bits; it is X0 * qa + q0 + (X0 * ra + r0) // W0 with
-//                       qa, ra = divmod(32 W, W0) and q0, r0 = divmod(16 W, W0) from the host, every term below 2^29: one 32-bit
-//                       division per thread, its three further x by adding.  The two 64-bit products D8 * SX, D8 * SY (16.16 factors
-//                       from the host) are the only wide arithmetic.  uint8 NHWC output only, through LDS as 16-byte stores like
-//                       k_mci_frames.  stage = 0 (row + field rows beyond 64 KB of LDS: both widths above 16 376): V from global.
+// THE FIELD
+//   k_mci_luma_pyramid  grid (tiles of 32 x 32, 2B): the luma of one tile and, from LDS, its 16 x 16 of level 1 and 8 x 8 of level 2
+//                       ((2x2 parents, clamped, + 2) >> 2) - and, where a wider search wants them (y3, y4 not null), its 4 x 4 of
+//                       level 3 and 2 x 2 of level 4: aligned tiles nest, a clamped parent is the tile's own.  Image n < B is A[n],
+//                       else B[n - B].
+//   k_mci_mask_pyramid  (MASKED) the same grid and tiling over the two exclusion masks [B, H, W]: level 0 as 0 / 1 and every further
+//                       level as the OR of the 2x2 clamped parents, level by level through two LDS planes.
+//   k_mci_search<R>     grid (runs of MCI_RUN blocks, B): bilateral block matching of one pyramid level.  A workgroup owns a run of
+//                       MCI_RUN consecutive blocks; it stages, once, the two luma windows of every block - (8 + 2R)^2 bytes of A
+//                       around p - start and of B around p + start, already clamped - in LDS; a wave then takes a block, its lanes
+//                       the candidates (R = 4: 81 candidates, one per lane in two passes; R = 1: 9 candidates x 4 row pairs, summed
+//                       over the 4 lanes by shuffles), and the winner is the wave minimum of the packed key (background.pack_key_wide:
+//                       cost << 30 | dx^2 + dy^2 << 16 | dy + 128 << 8 | dx + 128, room for the +-79 of five levels): the order of
+//                       the tuple (cost, |d|^2, dy, dx), whatever the lane order - and whatever the layout, so three levels give
+//                       background.pack_key's winners.  No atomics.  The top level of L (3, 4 or 5) runs <MCI_TOP_R> from start 0,
+//                       every level below <1>.
+//     <R, VALID = true>   (background.py's border="valid") the one-sided cost at the frame border.  The staged windows are the same
+//                       clamped ones; the SAD sums over the candidate's rectangle only, by a select per pixel inside the default's
+//                       loops, whose bounds are uniform per block (loops from the rectangle's own, per-lane bounds took 36.8 us where
+//                       these take 19.6 on level 0 of 512 x 512, B = 4: profiles/r13_mci_border.txt); n = nx * ny needs no mask and
+//                       no reduction (the four row lanes of R = 1 sum their SADs and all know n), cost = 64 * SAD / n + LAMBDA's
+//                       term, candidates with 4 n < N do not compete, and a block whose start itself is such a candidate (uniform
+//                       per wave) stores its start.
+//     <R, VALID, MASKED = true>  (the person kept out; every masked line sits under `if constexpr (MASKED)`) the two mask windows are
+//                       staged beside the two luma windows (R = 4: 4 KB more per workgroup, 8.1 KB in all); a pixel counts when the
+//                       border rule lets it and both mask bytes at the candidate's offsets are clear - one more term in the select,
+//                       and a count n beside the SAD, summed over the row lanes of R = 1 by the same shuffles; cost = 64 * SAD / n +
+//                       LAMBDA's term for either border.  The start candidate's n is one ballot (lane i takes the block's pixel i):
+//                       4 n < N is uniform per wave, the block stores its start and searched = 0 and no lane reaches the shuffles.
+//   k_mci_fill          (MASKED) the top level only, one thread per block: a block with searched = 0 takes the vector of the searched
+//                       block within Chebyshev distance 8 that minimises (ring, |Dy| + |Dx|, Dy, Dx), ring by ring, or (0, 0).  It
+//                       reads the raw field and the flags and writes ANOTHER buffer (the field the level below starts from): no
+//                       thread reads what another writes, and the result does not depend on the order.
+//   k_mci_median        3x3 componentwise median of the level-0 field (and of k_detail_search's), clamped.
+//   k_mci_refine        (rib_halfpel_refine) one launch shaped like k_mci_search<1>: the half-pel refinement of the field after the
+//                       median.  The windows are the clamped 10 x 10 INTEGER lumas of A around p - d and of B around p + d, computed
+//                       from the RGB bytes while staging (no workspace); the lanes are the 9 candidates h = 2 d + e x 4 row pairs; a
+//                       half-pel value is the rounded mean of the one, two or four staged integers around it (the definition's
+//                       half_plane; the clamped window repeats an edge pixel where the half-pel plane is clamped, and the mean of a
+//                       pixel with itself is the pixel); the winner is the wave minimum of background.pack_key_half.  <VALID = true>:
+//                       the rectangle of p -+ ceil(|h| / 2).  A block reads only its own vector, staged before any is written: out
+//                       may be the input.  |d| is clamped to 79 (max_disp(5)), so the key's fields always hold h.
+//   k_detail_search<R>  (rib_detail_field) the same search on blocks of the FULL-SIZE frame: the comment at the kernel.
 //
-// The person kept out (rib_masked_field / rib_masked_frames; background.mci_field_masked_host / mci_frames_masked_host): new
-// instantiations beside the ones above, which stay the instruction streams they were (every masked line sits under
-// `if constexpr (MASKED)`; the parameter structs only grew at their ends).
-//   k_mci_mask_pyramid  k_mci_luma_pyramid's grid and tiling over the two exclusion masks [B, H, W]: level 0 as 0 / 1 and every
-//                       further level as the OR of the 2x2 clamped parents, level by level through two LDS planes.
-//   k_mci_search<R, VALID, MASKED = true>  the two mask windows are staged beside the two luma windows (R = 4: 4 KB more per
-//                       workgroup, 8.1 KB in all); a pixel counts when the border rule lets it and both mask bytes at the candidate's
-//                       offsets are clear - one more term in the select inside the default's uniform loops, and a count n beside
-//                       the SAD, summed over the row lanes of R = 1 by the same shuffles; cost = 64 * SAD / n + LAMBDA's term for
-//                       either border.  The start candidate's n is one ballot (lane i takes the block's pixel i): 4 n < N is
-//                       uniform per wave, the block stores its start and searched = 0 and the shuffles are reached by no lane.
-//   k_mci_fill          the top level only, one thread per block: a block with searched = 0 takes the vector of the searched block
-//                       within Chebyshev distance 8 that minimises (ring, |Dy| + |Dx|, Dy, Dx), ring by ring, or (0, 0).  It reads
-//                       the raw field and the flags and writes ANOTHER buffer (the field the level below starts from): no thread
-//                       reads what another writes, and the result does not depend on the order.
-//   k_mci_frames<VALID, HALF, MASKED = true>  four byte gathers per sample in its key frame's mask (mci_sample's clamps) and one
-//                       more term in VALID's select: clean = valid under the border rule and all four taps clear; k = 0 and k = s
-//                       stay A and B.
-//
-// The 4x4 cubic sampler (rib_cubic_frames / rib_cubic_scaled; background.sample_cubic, the driver's mci_sampler="cubic"): k_cubic_frames
-// and k_cubic_scaled at the end of this file, kernels of their own beside k_mci_frames and k_scaled_frames, which are not touched.
+// THE FRAMES   grid (rows, T * B): a workgroup owns ONE row of one frame.
+//   k_mci_frames<VALID, HALF, MASKED>  a thread takes 4 consecutive x: D(p), the two fixed-point bilinear samples (mci_sample), the
+//                       blend; float4 stores per channel plane of the normalised NCHW tensor, and the uint8 row.  Either output may
+//                       be null.  VALID: four comparisons per sample, a select.  MASKED: four byte gathers per sample in its key
+//                       frame's mask (mci_clean) and one more term in the select: clean = valid under the border rule and all four
+//                       taps clear; k = 0 and k = s stay A and B.
+//   k_scaled_frames<VALID, HALF>  (rib_scaled_frames) k_mci_frames at the key frames' OWN size H0 x W0 - the field stays the model-size
+//                       one (H x W), the samples are taken from the full-size key frames.  The row's TY, r0, r1, fy are uniform per
+//                       workgroup, so the two field rows it needs are blended vertically ONCE into LDS - Wb (dx, dy) int32 pairs, at
+//                       most 16 KB - and a pixel reads two of them: the definition's sum in another order.  One 32-bit division per
+//                       thread for TX (mci_scaled_pos), its three further x by adding; the two 64-bit products of mci_scaled_d are
+//                       the only wide arithmetic.  uint8 NHWC output only.  stage = 0 (row + field rows beyond 64 KB of LDS: both
+//                       widths above 16 376): V from global.
+//   k_cubic_frames, k_cubic_scaled  the same two with the 4x4 cubic sample (background.sample_cubic), a lane per pixel: the section
+//                       further down says how the taps are fetched.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -91,6 +86,9 @@ constexpr int MCI_MIN_LEVELS = 3, MCI_MAX_LEVELS = 5;                           
 constexpr int MCI_RUN = 8;                  // blocks per workgroup of k_mci_search
 constexpr int MCI_MAX_SIDE = 16384, MCI_MAX_RATE = 1024;
 constexpr int MCI_MAX_DISP = 79, MCI_LAMBDA_HALF = 2, MCI_HALF_KEY_BIAS = 256;      // background.py max_disp(5), LAMBDA_HALF, HALF_KEY_BIAS
+
+// luma of an RGB pixel (background.luma): the pyramid's level 0, and what k_mci_refine and k_detail_search stage
+__device__ inline uint8_t mci_luma(const uint8_t* px) { return (uint8_t)((77 * px[0] + 150 * px[1] + 29 * px[2] + 128) >> 8); }
 
 struct MciLumaParams {
   const uint8_t *a, *b;                     // [B, H, W, 3]
@@ -111,7 +109,7 @@ __global__ __launch_bounds__(256) void k_mci_luma_pyramid(MciLumaParams p) {
     const int ly = i >> 5, lx = i & 31, y = y00 + ly, x = x00 + lx;
     if (y < p.H && x < p.W) {
       const uint8_t* px = src + ((size_t)y * p.W + x) * 3;
-      const uint8_t v = (uint8_t)((77 * px[0] + 150 * px[1] + 29 * px[2] + 128) >> 8);
+      const uint8_t v = mci_luma(px);
       s0[ly][lx] = v;
       p.y0[((size_t)n * p.H + y) * p.W + x] = v;
     }
@@ -387,7 +385,7 @@ __global__ __launch_bounds__(256) void k_mci_refine(MciRefineParams p) {
       const int y = min(max(MCI_BLOCK * by + sgn * s_start[j][1] - R + wy, 0), p.H - 1);
       const int x = min(max(MCI_BLOCK * bx + sgn * s_start[j][0] - R + wx, 0), p.W - 1);
       const uint8_t* px = (which ? p.b : p.a) + (((size_t)b * p.H + y) * p.W + x) * 3;
-      s_win[j][which][e] = (uint8_t)((77 * px[0] + 150 * px[1] + 29 * px[2] + 128) >> 8);
+      s_win[j][which][e] = mci_luma(px);
     }
   }
   __syncthreads();
@@ -549,6 +547,75 @@ __device__ inline void mci_sample(const uint8_t* img, int H, int W, int py, int 
     v[c] = ((256 - fy) * ((256 - fx) * p00[c] + fx * p01[c]) + fy * ((256 - fx) * p10[c] + fx * p11[c]) + (1 << 15)) >> 16;
 }
 
+// ---- the frame kernels' shared pieces (k_mci_frames, k_scaled_frames, k_cubic_frames, k_cubic_scaled) ----------------------------------
+// the two samples' offsets from the pixel, 1/256 px: k D / s towards A and (s - k) D / s towards B, rounded; UNIT is the field's
+// unit in half pixels (HALF ? 1 : 2), so the motion between the key frames is UNIT * D
+template <int UNIT>
+__device__ inline void mci_offsets(int Dx, int Dy, int k, int s, int ls, int& ax, int& ay, int& bx, int& by) {
+  ax = (UNIT * k * Dx + (s >> 1)) >> ls; ay = (UNIT * k * Dy + (s >> 1)) >> ls;
+  bx = (UNIT * (s - k) * Dx + (s >> 1)) >> ls; by = (UNIT * (s - k) * Dy + (s >> 1)) >> ls;
+}
+
+// VALID: the sample position lies in [0, (H-1) << 8] x [0, (W-1) << 8]
+__device__ inline bool mci_inside(int py, int px, int H, int W) { return py >= 0 && py <= ((H - 1) << 8) && px >= 0 && px <= ((W - 1) << 8); }
+
+// where exactly one of the two samples is ok the output is that sample, otherwise the blend (VALID's and MASKED's switch; with both
+// ok known at compile time only the blend is left)
+__device__ inline void mci_blend(const int v[2][3], bool oka, bool okb, int k, int s, int ls, uint8_t q[3]) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int blend = (__mul24(s - k, v[0][c]) + __mul24(k, v[1][c]) + (s >> 1)) >> ls;      // s <= 1024, a byte: both fit 24 bits
+    q[c] = (uint8_t)(oka == okb ? blend : oka ? v[0][c] : v[1][c]);
+  }
+}
+
+// D(p) at the model size, bilinear from the block field in sixteenths of a block (exact, 1/256 px): rows r0, r1 and fy are the
+// workgroup's, the column pair follows from x
+__device__ inline void mci_field_at(const int16_t* fld, int Wb, int r0, int r1, int fy, int x, int& Dx, int& Dy) {
+  const int txx = 2 * x - (MCI_BLOCK - 1), fx = txx & 15;
+  const int c0 = min(max(txx >> 4, 0), Wb - 1), c1 = min(max((txx >> 4) + 1, 0), Wb - 1);
+  const int16_t *f00 = fld + (r0 * Wb + c0) * 2, *f01 = fld + (r0 * Wb + c1) * 2;
+  const int16_t *f10 = fld + (r1 * Wb + c0) * 2, *f11 = fld + (r1 * Wb + c1) * 2;
+  Dx = (16 - fy) * ((16 - fx) * f00[0] + fx * f01[0]) + fy * ((16 - fx) * f10[0] + fx * f11[0]);
+  Dy = (16 - fy) * ((16 - fx) * f00[1] + fx * f01[1]) + fy * ((16 - fx) * f10[1] + fx * f11[1]);
+}
+
+// the scaled pair (k_scaled_frames, k_cubic_scaled).  The position of output coordinate v in 1/256 block of the model's axis,
+// ((2 v + 1) 16 N) // N0 - 128, would need 33 bits; it is v * qa + q0 + (v * ra + r0) // N0 with qa, ra = divmod(32 N, N0) and q0, r0 =
+// divmod(16 N, N0) from the host, every term below 2^29: one 32-bit division.  rem is that division's remainder, for stepping to v + 1.
+__device__ inline int mci_scaled_pos(int v, int qa, int ra, int q0, int r0, int n0, int& rem) {
+  const unsigned num = (unsigned)(v * ra + r0);
+  rem = (int)(num % (unsigned)n0);
+  return v * qa + q0 + (int)(num / (unsigned)n0) - 128;
+}
+__device__ inline int mci_scaled_pos(int v, int qa, int ra, int q0, int r0, int n0) {      // where nothing steps on: TY, and k_cubic_scaled's TX
+  int rem;
+  return mci_scaled_pos(v, qa, ra, q0, r0, n0, rem);
+}
+// column c of the two field rows blended vertically ONCE, V[c] = (256-fy) f[r0][c] + fy f[r1][c] (exact: integers)
+__device__ inline int2 mci_field_row(const int16_t* frow0, const int16_t* frow1, int fy, int c) {
+  return make_int2((256 - fy) * frow0[2 * c] + fy * frow1[2 * c], (256 - fy) * frow0[2 * c + 1] + fy * frow1[2 * c + 1]);
+}
+// D16 = (256-fx) V[c0] + fx V[c1] -> D8 in 1/256 model px -> D in 1/256 output px by the 16.16 factors (the only wide arithmetic)
+__device__ inline void mci_scaled_d(int2 v0, int2 v1, int fx, int sx, int sy, int& Dx, int& Dy) {
+  const int D8x = ((256 - fx) * v0.x + fx * v1.x + 128) >> 8, D8y = ((256 - fx) * v0.y + fx * v1.y + 128) >> 8;
+  Dx = (int)(((long long)D8x * sx + 32768) >> 16); Dy = (int)(((long long)D8y * sy + 32768) >> 16);
+}
+
+// the uint8 row from LDS as 16-byte stores contiguous across the workgroup (k_panel's scheme)
+__device__ inline void mci_store_row(const uint8_t* lds, uint8_t* grow, int shift, int rowbytes) {
+  const int nlines = (shift + rowbytes + 15) >> 4;
+  uint8_t* gline = grow - shift;            // 16-byte aligned; only bytes [shift, shift + rowbytes) are this row's
+  for (int j = threadIdx.x; j < nlines; j += 256) {
+    const int lo = j * 16;
+    if (lo >= shift && lo + 16 <= shift + rowbytes) {
+      *reinterpret_cast<uint4*>(gline + lo) = reinterpret_cast<const uint4*>(lds)[j];
+    } else {
+      for (int kk = max(lo, shift); kk < min(lo + 16, shift + rowbytes); ++kk) gline[kk] = lds[kk];
+    }
+  }
+}
+
 template <bool VALID = false, bool HALF = false, bool MASKED = false>
 __global__ __launch_bounds__(256) void k_mci_frames(MciFramesParams p) {
   constexpr int UNIT = HALF ? 1 : 2;        // the field's unit in half pixels: the motion between the key frames is UNIT * D
@@ -641,16 +708,7 @@ __global__ __launch_bounds__(256) void k_mci_frames(MciFramesParams p) {
   }
   if (!grow) return;                        // (uniform: no thread reaches the barrier)
   __syncthreads();
-  const int nlines = (shift + rowbytes + 15) >> 4;
-  uint8_t* gline = grow - shift;            // 16-byte aligned; only bytes [shift, shift + rowbytes) are this row's
-  for (int j = threadIdx.x; j < nlines; j += 256) {
-    const int lo = j * 16;
-    if (lo >= shift && lo + 16 <= shift + rowbytes) {
-      *reinterpret_cast<uint4*>(gline + lo) = reinterpret_cast<const uint4*>(s_mci)[j];
-    } else {
-      for (int kk = max(lo, shift); kk < min(lo + 16, shift + rowbytes); ++kk) gline[kk] = s_mci[kk];
-    }
-  }
+  mci_store_row(s_mci, grow, shift, rowbytes);
 }
 
 struct ScaledFramesParams {
@@ -680,21 +738,17 @@ __global__ __launch_bounds__(256) void k_scaled_frames(ScaledFramesParams p) {
   const uint8_t* A = p.a + (size_t)bi * H0 * W0 * 3;
   const uint8_t* Bf = p.b + (size_t)bi * H0 * W0 * 3;
   const int16_t* fld = p.field + (size_t)bi * p.Hb * p.Wb * 2;
-  // TY = ((2 y + 1) * 16 H) / H0 - 128 without 33 bits: y * ray + r0y < 2^28 + 2^14
-  const int tyy = y * p.qay + p.q0y + (int)((unsigned)(y * p.ray + p.r0y) / (unsigned)H0) - 128, fy = tyy & 255;
+  const int tyy = mci_scaled_pos(y, p.qay, p.ray, p.q0y, p.r0y, H0), fy = tyy & 255;      // TY: y * ray + r0y < 2^28 + 2^14
   const int r0 = min(max(tyy >> 8, 0), p.Hb - 1), r1 = min(max((tyy >> 8) + 1, 0), p.Hb - 1);
   const int16_t *frow0 = fld + (size_t)r0 * p.Wb * 2, *frow1 = fld + (size_t)r1 * p.Wb * 2;
   if (p.stage) {
-    for (int c = threadIdx.x; c < p.Wb; c += 256)
-      sV[c] = make_int2((256 - fy) * frow0[2 * c] + fy * frow1[2 * c], (256 - fy) * frow0[2 * c + 1] + fy * frow1[2 * c + 1]);
+    for (int c = threadIdx.x; c < p.Wb; c += 256) sV[c] = mci_field_row(frow0, frow1, fy, c);
     __syncthreads();
   }
   const int W4 = (W0 + 3) >> 2;
   for (int item = threadIdx.x; item < W4; item += 256) {
     const int x0 = item * 4;
-    const unsigned num = (unsigned)(x0 * p.rax + p.r0x);
-    int tq = x0 * p.qax + p.q0x + (int)(num / (unsigned)W0) - 128;      // TX of x0
-    int trem = (int)(num % (unsigned)W0);
+    int trem, tq = mci_scaled_pos(x0, p.qax, p.rax, p.q0x, p.r0x, W0, trem);      // TX of x0; its three further x by adding
     uint8_t q[12];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -704,34 +758,18 @@ __global__ __launch_bounds__(256) void k_scaled_frames(ScaledFramesParams p) {
       tq += p.qax; trem += p.rax;           // TX of x + 1
       if (trem >= W0) { trem -= W0; ++tq; }
       int2 v0, v1;
-      if (p.stage) {
-        v0 = sV[c0]; v1 = sV[c1];
-      } else {
-        v0 = make_int2((256 - fy) * frow0[2 * c0] + fy * frow1[2 * c0], (256 - fy) * frow0[2 * c0 + 1] + fy * frow1[2 * c0 + 1]);
-        v1 = make_int2((256 - fy) * frow0[2 * c1] + fy * frow1[2 * c1], (256 - fy) * frow0[2 * c1 + 1] + fy * frow1[2 * c1 + 1]);
-      }
-      const int D8x = ((256 - fx) * v0.x + fx * v1.x + 128) >> 8, D8y = ((256 - fx) * v0.y + fx * v1.y + 128) >> 8;      // 1/256 model px
-      const int Dx = (int)(((long long)D8x * p.sx + 32768) >> 16), Dy = (int)(((long long)D8y * p.sy + 32768) >> 16);   // 1/256 output px
-      const int ax = (UNIT * k * Dx + (s >> 1)) >> ls, ay = (UNIT * k * Dy + (s >> 1)) >> ls;
-      const int bx = (UNIT * (s - k) * Dx + (s >> 1)) >> ls, by = (UNIT * (s - k) * Dy + (s >> 1)) >> ls;
+      if (p.stage) { v0 = sV[c0]; v1 = sV[c1]; }
+      else { v0 = mci_field_row(frow0, frow1, fy, c0); v1 = mci_field_row(frow0, frow1, fy, c1); }
+      int Dx, Dy, ax, ay, bx, by;
+      mci_scaled_d(v0, v1, fx, p.sx, p.sy, Dx, Dy);
+      mci_offsets<UNIT>(Dx, Dy, k, s, ls, ax, ay, bx, by);
       const int pay = (y << 8) - ay, pax = (x << 8) - ax, pby = (y << 8) + by, pbx = (x << 8) + bx;
-      int va[3], vb[3];
-      mci_sample(A, H0, W0, pay, pax, va);
-      mci_sample(Bf, H0, W0, pby, pbx, vb);
-      if constexpr (VALID) {
-        const int ymax = (H0 - 1) << 8, xmax = (W0 - 1) << 8;
-        const bool oka = pay >= 0 && pay <= ymax && pax >= 0 && pax <= xmax, okb = pby >= 0 && pby <= ymax && pbx >= 0 && pbx <= xmax;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const int blend = ((s - k) * va[c] + k * vb[c] + (s >> 1)) >> ls;
-          q[j * 3 + c] = (uint8_t)(oka == okb ? blend : oka ? va[c] : vb[c]);
-        }
-      } else {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) q[j * 3 + c] = (uint8_t)(((s - k) * va[c] + k * vb[c] + (s >> 1)) >> ls);
-      }
+      int v[2][3];
+      mci_sample(A, H0, W0, pay, pax, v[0]);
+      mci_sample(Bf, H0, W0, pby, pbx, v[1]);
+      mci_blend(v, !VALID || mci_inside(pay, pax, H0, W0), !VALID || mci_inside(pby, pbx, H0, W0), k, s, ls, q + j * 3);
     }
-    uint8_t* dst = srow + x0 * 3;
+    uint8_t* dst = srow + x0 * 3;           // (written out as in k_mci_frames: DESIGN.md 4g-shared)
     if (p.vec) {
 #pragma unroll
       for (int d = 0; d < 3; ++d)
@@ -744,21 +782,12 @@ __global__ __launch_bounds__(256) void k_scaled_frames(ScaledFramesParams p) {
     }
   }
   __syncthreads();
-  const int nlines = (shift + rowbytes + 15) >> 4;
-  uint8_t* gline = grow - shift;            // 16-byte aligned; only bytes [shift, shift + rowbytes) are this row's
-  for (int j = threadIdx.x; j < nlines; j += 256) {
-    const int lo = j * 16;
-    if (lo >= shift && lo + 16 <= shift + rowbytes) {
-      *reinterpret_cast<uint4*>(gline + lo) = reinterpret_cast<const uint4*>(s_mci)[j];
-    } else {
-      for (int kk = max(lo, shift); kk < min(lo + 16, shift + rowbytes); ++kk) gline[kk] = s_mci[kk];
-    }
-  }
+  mci_store_row(s_mci, grow, shift, rowbytes);
 }
 
 // ---- 4x4 cubic sampling (rib_cubic_frames / rib_cubic_scaled; background.sample_cubic, the driver's mci_sampler="cubic") ------------
-// New kernels beside k_mci_frames / k_scaled_frames, which are not touched.  Same grids (one workgroup per output row), same field
-// arithmetic, same blend and border rule, same LDS scheme for the uint8 output row; what differs is the sample - 16 taps per key
+// k_mci_frames' and k_scaled_frames' grids (one workgroup per output row) and their shared pieces: the field arithmetic, the blend and
+// border rule, the LDS scheme for the uint8 output row; what differs is the sample - 16 taps per key
 // frame, Catmull-Rom weights in 1/128 per axis (background.cubic_weights) - and how the taps are fetched:
 //   tile      64 consecutive x of the row, one wave, one pixel per lane (a row's tiles go round the workgroup's four waves).  Every
 //             lane first has its two sample positions in registers; the wave reduces min and max of the integer tap coordinates
@@ -934,29 +963,6 @@ struct CubicFramesParams {
   int w_off;                                // byte offset of the weight table in the dynamic LDS (a multiple of 16); the windows follow it
 };
 
-// the switch of k_mci_frames: where exactly one of the two samples is ok the output is that sample, otherwise the blend
-__device__ inline void cubic_blend(const int v[2][3], bool oka, bool okb, int k, int s, int ls, uint8_t q[3]) {
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const int blend = (__mul24(s - k, v[0][c]) + __mul24(k, v[1][c]) + (s >> 1)) >> ls;      // s <= 1024, a byte
-    q[c] = (uint8_t)(oka == okb ? blend : oka ? v[0][c] : v[1][c]);
-  }
-}
-
-// the uint8 row from LDS as 16-byte stores contiguous across the workgroup (k_mci_frames' scheme)
-__device__ inline void cubic_store_row(const uint8_t* lds, uint8_t* grow, int shift, int rowbytes) {
-  const int nlines = (shift + rowbytes + 15) >> 4;
-  uint8_t* gline = grow - shift;            // 16-byte aligned; only bytes [shift, shift + rowbytes) are this row's
-  for (int j = threadIdx.x; j < nlines; j += 256) {
-    const int lo = j * 16;
-    if (lo >= shift && lo + 16 <= shift + rowbytes) {
-      *reinterpret_cast<uint4*>(gline + lo) = reinterpret_cast<const uint4*>(lds)[j];
-    } else {
-      for (int kk = max(lo, shift); kk < min(lo + 16, shift + rowbytes); ++kk) gline[kk] = lds[kk];
-    }
-  }
-}
-
 template <bool VALID = false, bool HALF = false, bool MASKED = false>
 __global__ __launch_bounds__(256) void k_cubic_frames(CubicFramesParams p) {
   constexpr int UNIT = HALF ? 1 : 2;
@@ -983,14 +989,9 @@ __global__ __launch_bounds__(256) void k_cubic_frames(CubicFramesParams p) {
   const int ntiles = (W + CUBIC_TILE - 1) / CUBIC_TILE;
   for (int tile = wave; tile < ntiles; tile += 4) {      // (uniform per wave: every lane of the wave is in cubic_samples)
     const int xo = tile * CUBIC_TILE + lane, x = min(xo, W - 1);
-    const int txx = 2 * x - (MCI_BLOCK - 1), fx = txx & 15;
-    const int c0 = min(max(txx >> 4, 0), p.Wb - 1), c1 = min(max((txx >> 4) + 1, 0), p.Wb - 1);
-    const int16_t *f00 = fld + (r0 * p.Wb + c0) * 2, *f01 = fld + (r0 * p.Wb + c1) * 2;
-    const int16_t *f10 = fld + (r1 * p.Wb + c0) * 2, *f11 = fld + (r1 * p.Wb + c1) * 2;
-    const int Dx = (16 - fy) * ((16 - fx) * f00[0] + fx * f01[0]) + fy * ((16 - fx) * f10[0] + fx * f11[0]);
-    const int Dy = (16 - fy) * ((16 - fx) * f00[1] + fx * f01[1]) + fy * ((16 - fx) * f10[1] + fx * f11[1]);
-    const int ax = (UNIT * k * Dx + (s >> 1)) >> ls, ay = (UNIT * k * Dy + (s >> 1)) >> ls;
-    const int bx = (UNIT * (s - k) * Dx + (s >> 1)) >> ls, by = (UNIT * (s - k) * Dy + (s >> 1)) >> ls;
+    int Dx, Dy, ax, ay, bx, by;
+    mci_field_at(fld, p.Wb, r0, r1, fy, x, Dx, Dy);
+    mci_offsets<UNIT>(Dx, Dy, k, s, ls, ax, ay, bx, by);
     CubicKey key[2] = {{A, MA, (y << 8) - ay, (x << 8) - ax}, {Bf, MB, (y << 8) + by, (x << 8) + bx}};
     int v[2][3];
     bool ok[2];
@@ -1005,7 +1006,7 @@ __global__ __launch_bounds__(256) void k_cubic_frames(CubicFramesParams p) {
       if (k == s) { ok[0] = false; ok[1] = true; }
     }
     uint8_t q[3];
-    cubic_blend(v, ok[0], ok[1], k, s, ls, q);
+    mci_blend(v, ok[0], ok[1], k, s, ls, q);
     if (xo < W) {
       if (p.out_f32) {
 #pragma unroll
@@ -1019,7 +1020,7 @@ __global__ __launch_bounds__(256) void k_cubic_frames(CubicFramesParams p) {
   }
   if (!grow) return;                        // (uniform: no thread reaches the barrier)
   __syncthreads();
-  cubic_store_row(s_mci, grow, shift, rowbytes);
+  mci_store_row(s_mci, grow, shift, rowbytes);
 }
 
 struct CubicScaledParams {
@@ -1046,42 +1047,37 @@ __global__ __launch_bounds__(256) void k_cubic_scaled(CubicScaledParams cp) {
   const uint8_t* A = p.a + (size_t)bi * H0 * W0 * 3;
   const uint8_t* Bf = p.b + (size_t)bi * H0 * W0 * 3;
   const int16_t* fld = p.field + (size_t)bi * p.Hb * p.Wb * 2;
-  // TY as k_scaled_frames computes it
-  const int tyy = y * p.qay + p.q0y + (int)((unsigned)(y * p.ray + p.r0y) / (unsigned)H0) - 128, fy = tyy & 255;
+  const int tyy = mci_scaled_pos(y, p.qay, p.ray, p.q0y, p.r0y, H0), fy = tyy & 255;
   const int r0 = min(max(tyy >> 8, 0), p.Hb - 1), r1 = min(max((tyy >> 8) + 1, 0), p.Hb - 1);
   const int16_t *frow0 = fld + (size_t)r0 * p.Wb * 2, *frow1 = fld + (size_t)r1 * p.Wb * 2;
   wtab[threadIdx.x] = cubic_weight_row(threadIdx.x);
-  for (int c = threadIdx.x; c < p.Wb; c += 256)      // the once-blended field row; it always has room (the host raises the kernel's LDS limit)
-    sV[c] = make_int2((256 - fy) * frow0[2 * c] + fy * frow1[2 * c], (256 - fy) * frow0[2 * c + 1] + fy * frow1[2 * c + 1]);
+  for (int c = threadIdx.x; c < p.Wb; c += 256) sV[c] = mci_field_row(frow0, frow1, fy, c);      // it always has room (the host raises the kernel's LDS limit)
   __syncthreads();
   const int ntiles = (W0 + CUBIC_TILE - 1) / CUBIC_TILE;
   for (int tile = wave; tile < ntiles; tile += 4) {      // (uniform per wave)
     const int xo = tile * CUBIC_TILE + lane, x = min(xo, W0 - 1);
-    const int tq = x * p.qax + p.q0x + (int)((unsigned)(x * p.rax + p.r0x) / (unsigned)W0) - 128, fx = tq & 255;      // TX of x: below 2^29 per term
+    const int tq = mci_scaled_pos(x, p.qax, p.rax, p.q0x, p.r0x, W0), fx = tq & 255;      // (a lane takes one x: nothing to step)
     const int c0 = min(max(tq >> 8, 0), p.Wb - 1), c1 = min(max((tq >> 8) + 1, 0), p.Wb - 1);
-    const int2 v0 = sV[c0], v1 = sV[c1];
-    const int D8x = ((256 - fx) * v0.x + fx * v1.x + 128) >> 8, D8y = ((256 - fx) * v0.y + fx * v1.y + 128) >> 8;      // 1/256 model px
-    const int Dx = (int)(((long long)D8x * p.sx + 32768) >> 16), Dy = (int)(((long long)D8y * p.sy + 32768) >> 16);   // 1/256 output px
-    const int ax = (UNIT * k * Dx + (s >> 1)) >> ls, ay = (UNIT * k * Dy + (s >> 1)) >> ls;
-    const int bx = (UNIT * (s - k) * Dx + (s >> 1)) >> ls, by = (UNIT * (s - k) * Dy + (s >> 1)) >> ls;
+    int Dx, Dy, ax, ay, bx, by;
+    mci_scaled_d(sV[c0], sV[c1], fx, p.sx, p.sy, Dx, Dy);
+    mci_offsets<UNIT>(Dx, Dy, k, s, ls, ax, ay, bx, by);
     CubicKey key[2] = {{A, nullptr, (y << 8) - ay, (x << 8) - ax}, {Bf, nullptr, (y << 8) + by, (x << 8) + bx}};
     int v[2][3];
     bool ok[2];
     cubic_samples<false>(key, H0, W0, cp.stage_win != 0, win, wtab, lane, v, ok);
     if constexpr (VALID) {
-      const int ymax = (H0 - 1) << 8, xmax = (W0 - 1) << 8;
 #pragma unroll
-      for (int f = 0; f < 2; ++f) ok[f] = key[f].py >= 0 && key[f].py <= ymax && key[f].px >= 0 && key[f].px <= xmax;
+      for (int f = 0; f < 2; ++f) ok[f] = mci_inside(key[f].py, key[f].px, H0, W0);
     }
     uint8_t q[3];
-    cubic_blend(v, ok[0], ok[1], k, s, ls, q);
+    mci_blend(v, ok[0], ok[1], k, s, ls, q);
     if (xo < W0) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) srow[xo * 3 + c] = q[c];
     }
   }
   __syncthreads();
-  cubic_store_row(s_mci, grow, shift, rowbytes);
+  mci_store_row(s_mci, grow, shift, rowbytes);
 }
 
 // ---- the field refined at the key frames' own size (rib_detail_field; background.mci_detail_field_host, the driver's mci_detail="keyframes") ----
@@ -1155,7 +1151,7 @@ __global__ __launch_bounds__(256) void k_detail_search(DetailSearchParams p) {
       const int y = min(max(MCI_BLOCK * by + sgn * s_start[j][1] - R + wy, 0), p.H0 - 1);
       const int x = min(max(MCI_BLOCK * bx + sgn * s_start[j][0] - R + wx, 0), p.W0 - 1);
       const uint8_t* px = (which ? p.b : p.a) + (((size_t)b * p.H0 + y) * p.W0 + x) * 3;
-      s_win[j][which][e] = (uint8_t)((77 * px[0] + 150 * px[1] + 29 * px[2] + 128) >> 8);
+      s_win[j][which][e] = mci_luma(px);
     }
   }
   __syncthreads();

@@ -620,6 +620,27 @@ class Generator:
             raise ValueError("%s: empty key frames %s" % (who, tuple(a.shape)))
         return a, b, single
 
+    def _mci_field_arg(self, field, B, H, W, who, hint=("segments", "mci_field")):
+        """field int16 [B,Hb,Wb,2] (or [Hb,Wb,2]) on this device -> contiguous [B,Hb,Wb,2].  hint: what the B frames of H x W are
+        called in the refusal, and the method the field comes from."""
+        from .background import field_shape
+        Hb, Wb = field_shape(H, W)
+        if not torch.is_tensor(field) or field.dtype != torch.int16 or field.device != self.device:
+            raise ValueError("%s: field must be an int16 tensor on %s (%s)" % (who, self.device, hint[1]))
+        f = (field.unsqueeze(0) if field.dim() == 3 else field).contiguous()
+        if tuple(f.shape) != (B, Hb, Wb, 2):
+            raise ValueError("%s: the field of %d %dx%d %s is [%d, %d, %d, 2], got %s" % (who, B, H, W, hint[0], B, Hb, Wb, tuple(field.shape)))
+        return f
+
+    @staticmethod
+    def _mci_span(s, k_first, count, who):
+        """(k_first, T): frames k_first .. k_first + T - 1 of a segment of s steps; count None: up to s - 1."""
+        k_first = int(k_first)
+        T = (s - k_first) if count is None else int(count)
+        if T < 1 or k_first < 0 or k_first + T - 1 > s:
+            raise ValueError("%s: frames %d..%d are outside the segment 0..%d" % (who, k_first, k_first + T - 1, s))
+        return k_first, T
+
     def mci_field(self, a_u8, b_u8, levels=3, border="clamp"):
         """The block displacement field of B key-frame pairs on the GPU (rib_mci_field; background.mci_field_host is the
         definition and is bit-equal): a_u8, b_u8 uint8 [B,H,W,3] (or [H,W,3]) on this device, the left and right key frame of
@@ -654,11 +675,7 @@ class Generator:
         a, b, single = self._mci_pair(a_u8, b_u8, "mci_refine")
         B, H, W, _ = a.shape
         Hb, Wb = field_shape(H, W)
-        if not torch.is_tensor(field) or field.dtype != torch.int16 or field.device != self.device:
-            raise ValueError("mci_refine: field must be an int16 tensor on %s (mci_field)" % (self.device,))
-        f = (field.unsqueeze(0) if field.dim() == 3 else field).contiguous()
-        if tuple(f.shape) != (B, Hb, Wb, 2):
-            raise ValueError("mci_refine: the field of %d %dx%d segments is [%d, %d, %d, 2], got %s" % (B, H, W, B, Hb, Wb, tuple(field.shape)))
+        f = self._mci_field_arg(field, B, H, W, "mci_refine")
         with torch.cuda.device(self.device):
             if out is None:
                 res = torch.empty_like(f)
@@ -684,12 +701,7 @@ class Generator:
         B, h0, w0, _ = a.shape
         H, W = (int(v) for v in model_hw)
         scaled_factors((H, W), (h0, w0), "mci_detail_field")
-        Hb, Wb = field_shape(H, W)
-        if not torch.is_tensor(field) or field.dtype != torch.int16 or field.device != self.device:
-            raise ValueError("mci_detail_field: field must be an int16 tensor on %s (mci_field)" % (self.device,))
-        f = (field.unsqueeze(0) if field.dim() == 3 else field).contiguous()
-        if tuple(f.shape) != (B, Hb, Wb, 2):
-            raise ValueError("mci_detail_field: the field of %d %dx%d model frames is [%d, %d, %d, 2], got %s" % (B, H, W, B, Hb, Wb, tuple(field.shape)))
+        f = self._mci_field_arg(field, B, H, W, "mci_detail_field", ("model frames", "mci_field"))
         n = int(self._lib.rib_detail_workspace_bytes(self._h, B, h0, w0))
         if n == 0:
             raise ValueError("mci_detail_field: B=%d h0=%d w0=%d: 1 <= B <= 32767, the sides in 1..16384" % (B, h0, w0))
@@ -713,26 +725,24 @@ class Generator:
         field is mci_refine's, in half pixels (rib_halfpel_frames).  sampler: "bilinear" (the default) or "cubic": the 4x4
         Catmull-Rom sample (rib_cubic_frames; background.sample_cubic), nothing else changed; _staging (cubic only) is that
         entry's diagnostic: 0 = the per-tile rule, 1 = never stage - the bytes do not depend on it."""
-        from .background import BORDERS, PRECISIONS, check_border, check_precision, check_sampler, field_shape, log2_rate
-        border = BORDERS.index(check_border(border, "mci_frames"))
-        cubic = check_sampler(sampler, "mci_frames") == "cubic"
-        entry = self._lib.rib_halfpel_frames if check_precision(precision, "mci_frames") == "half" else self._lib.rib_mci_frames
-        a, b, single = self._mci_pair(a_u8, b_u8, "mci_frames")
+        return self._mci_frames_body("mci_frames", a_u8, b_u8, None, field, sample_rate, k_first, count, normalised, out, border, precision,
+                                     sampler, _staging)
+
+    def _mci_frames_body(self, who, a_u8, b_u8, masks, field, sample_rate, k_first, count, normalised, out, border, precision, sampler, staging):
+        """mci_frames (masks None) and mci_frames_masked (masks = (ma, mb)): one check per argument, in one order, and one launch."""
+        from .background import BORDERS, PRECISIONS, check_border, check_precision, check_sampler, log2_rate
+        border = BORDERS.index(check_border(border, who))
+        cubic = check_sampler(sampler, who) == "cubic"
+        precision = PRECISIONS.index(check_precision(precision, who))
+        a, b, single = self._mci_pair(a_u8, b_u8, who)
         B, H, W, _ = a.shape
-        Hb, Wb = field_shape(H, W)
+        qa, qb = self._mci_masks(masks[0], masks[1], (B, H, W), single, who) if masks is not None else (None, None)
         log2_rate(sample_rate)
         s = int(sample_rate)
-        if not torch.is_tensor(field) or field.dtype != torch.int16 or field.device != self.device:
-            raise ValueError("mci_frames: field must be an int16 tensor on %s (mci_field)" % (self.device,))
-        f = (field.unsqueeze(0) if field.dim() == 3 else field).contiguous()
-        if tuple(f.shape) != (B, Hb, Wb, 2):
-            raise ValueError("mci_frames: the field of %d %dx%d segments is [%d, %d, %d, 2], got %s" % (B, H, W, B, Hb, Wb, tuple(field.shape)))
-        k_first = int(k_first)
-        T = (s - k_first) if count is None else int(count)
-        if T < 1 or k_first < 0 or k_first + T - 1 > s:
-            raise ValueError("mci_frames: frames %d..%d are outside the segment 0..%d" % (k_first, k_first + T - 1, s))
+        f = self._mci_field_arg(field, B, H, W, who, ("segments", "mci_field" if masks is None else "mci_field_masked"))
+        k_first, T = self._mci_span(s, k_first, count, who)
         if normalised not in (True, False, "both"):
-            raise ValueError("mci_frames: normalised must be True, False or 'both'")
+            raise ValueError("%s: normalised must be True, False or 'both'" % who)
         fshape, ushape = (T, B, 3, H, W), (T, B, H, W, 3)
         of, ou = (out if normalised == "both" else (out, None) if normalised else (None, out)) if out is not None else (None, None)
 
@@ -741,16 +751,20 @@ class Generator:
                 return torch.empty(shape, dtype=dtype, device=self.device)
             v = t.unsqueeze(1) if (single and t.dim() == 4) else t
             if tuple(v.shape) != shape or v.dtype != dtype or not v.is_contiguous() or v.device != self.device:
-                raise ValueError("mci_frames: out must be a contiguous %s %s tensor on %s" % (shape, dtype, self.device))
+                raise ValueError("%s: out must be a contiguous %s %s tensor on %s" % (who, shape, dtype, self.device))
             return v
         with torch.cuda.device(self.device):
             rf = dest(of, fshape, torch.float32) if normalised in (True, "both") else None
             ru = dest(ou, ushape, torch.uint8) if normalised in (False, "both") else None
+            head, tail = (self._h, T, B, H, W, _ptr(a), _ptr(b)), (_ptr(rf), _ptr(ru), self._stream())
             if cubic:
-                _native.check(self._h, self._lib.rib_cubic_frames(self._h, T, B, H, W, _ptr(a), _ptr(b), None, None, _ptr(f), s, k_first, border,
-                                                                  PRECISIONS.index(precision), int(_staging), _ptr(rf), _ptr(ru), self._stream()))
+                rc = self._lib.rib_cubic_frames(*head, _ptr(qa), _ptr(qb), _ptr(f), s, k_first, border, precision, int(staging), *tail)
+            elif masks is not None:
+                rc = self._lib.rib_masked_frames(*head, _ptr(qa), _ptr(qb), _ptr(f), s, k_first, border, precision, *tail)
             else:
-                _native.check(self._h, entry(self._h, T, B, H, W, _ptr(a), _ptr(b), _ptr(f), s, k_first, border, _ptr(rf), _ptr(ru), self._stream()))
+                entry = self._lib.rib_halfpel_frames if precision else self._lib.rib_mci_frames
+                rc = entry(*head, _ptr(f), s, k_first, border, *tail)
+            _native.check(self._h, rc)
         res = tuple((r[:, 0] if single else r) for r in (rf, ru) if r is not None)
         return res if normalised == "both" else res[0]
 
@@ -794,48 +808,8 @@ class Generator:
         is clean - valid under `border`, and the four taps of its footprint in its key frame's mask all zero - the output is that
         sample alone.  Everything else - field, frames, normalised (True, False, "both"), out, precision, sampler, _staging - is
         mci_frames'; sampler="cubic" (rib_cubic_frames with the masks): a sample is clean iff all 16 of its taps are clear."""
-        from .background import BORDERS, PRECISIONS, check_border, check_precision, check_sampler, field_shape, log2_rate
-        border = BORDERS.index(check_border(border, "mci_frames_masked"))
-        cubic = check_sampler(sampler, "mci_frames_masked") == "cubic"
-        precision = PRECISIONS.index(check_precision(precision, "mci_frames_masked"))
-        a, b, single = self._mci_pair(a_u8, b_u8, "mci_frames_masked")
-        B, H, W, _ = a.shape
-        qa, qb = self._mci_masks(ma, mb, (B, H, W), single, "mci_frames_masked")
-        Hb, Wb = field_shape(H, W)
-        log2_rate(sample_rate)
-        s = int(sample_rate)
-        if not torch.is_tensor(field) or field.dtype != torch.int16 or field.device != self.device:
-            raise ValueError("mci_frames_masked: field must be an int16 tensor on %s (mci_field_masked)" % (self.device,))
-        f = (field.unsqueeze(0) if field.dim() == 3 else field).contiguous()
-        if tuple(f.shape) != (B, Hb, Wb, 2):
-            raise ValueError("mci_frames_masked: the field of %d %dx%d segments is [%d, %d, %d, 2], got %s" % (B, H, W, B, Hb, Wb, tuple(field.shape)))
-        k_first = int(k_first)
-        T = (s - k_first) if count is None else int(count)
-        if T < 1 or k_first < 0 or k_first + T - 1 > s:
-            raise ValueError("mci_frames_masked: frames %d..%d are outside the segment 0..%d" % (k_first, k_first + T - 1, s))
-        if normalised not in (True, False, "both"):
-            raise ValueError("mci_frames_masked: normalised must be True, False or 'both'")
-        fshape, ushape = (T, B, 3, H, W), (T, B, H, W, 3)
-        of, ou = (out if normalised == "both" else (out, None) if normalised else (None, out)) if out is not None else (None, None)
-
-        def dest(t, shape, dtype):
-            if t is None:
-                return torch.empty(shape, dtype=dtype, device=self.device)
-            v = t.unsqueeze(1) if (single and t.dim() == 4) else t
-            if tuple(v.shape) != shape or v.dtype != dtype or not v.is_contiguous() or v.device != self.device:
-                raise ValueError("mci_frames_masked: out must be a contiguous %s %s tensor on %s" % (shape, dtype, self.device))
-            return v
-        with torch.cuda.device(self.device):
-            rf = dest(of, fshape, torch.float32) if normalised in (True, "both") else None
-            ru = dest(ou, ushape, torch.uint8) if normalised in (False, "both") else None
-            if cubic:
-                _native.check(self._h, self._lib.rib_cubic_frames(self._h, T, B, H, W, _ptr(a), _ptr(b), _ptr(qa), _ptr(qb), _ptr(f), s, k_first,
-                                                                  border, precision, int(_staging), _ptr(rf), _ptr(ru), self._stream()))
-            else:
-                _native.check(self._h, self._lib.rib_masked_frames(self._h, T, B, H, W, _ptr(a), _ptr(b), _ptr(qa), _ptr(qb), _ptr(f), s, k_first,
-                                                                   border, precision, _ptr(rf), _ptr(ru), self._stream()))
-        res = tuple((r[:, 0] if single else r) for r in (rf, ru) if r is not None)
-        return res if normalised == "both" else res[0]
+        return self._mci_frames_body("mci_frames_masked", a_u8, b_u8, (ma, mb), field, sample_rate, k_first, count, normalised, out, border,
+                                     precision, sampler, _staging)
 
     def mci_frames_scaled(self, a0_u8, b0_u8, field, model_hw, sample_rate, k_first=0, count=None, border="clamp", precision="full", out=None,
                           sampler="bilinear", _staging=0):
@@ -847,7 +821,7 @@ class Generator:
         sampled from the full-size key frames; with (h0, w0) == (H, W) the bytes are mci_frames'.  Sides in 1..16384, each axis
         within 1/16 .. 16 times the model's.  out: optional contiguous uint8 destination, any byte offset.  sampler="cubic":
         rib_cubic_scaled (background.sample_cubic in place of the bilinear sample); _staging is its diagnostic, as mci_frames'."""
-        from .background import BORDERS, PRECISIONS, check_border, check_precision, check_sampler, field_shape, log2_rate, scaled_factors
+        from .background import BORDERS, PRECISIONS, check_border, check_precision, check_sampler, log2_rate, scaled_factors
         border = BORDERS.index(check_border(border, "mci_frames_scaled"))
         cubic = check_sampler(sampler, "mci_frames_scaled") == "cubic"
         precision = PRECISIONS.index(check_precision(precision, "mci_frames_scaled"))
@@ -855,18 +829,10 @@ class Generator:
         B, h0, w0, _ = a.shape
         H, W = (int(v) for v in model_hw)
         scaled_factors((H, W), (h0, w0), "mci_frames_scaled")
-        Hb, Wb = field_shape(H, W)
         log2_rate(sample_rate)
         s = int(sample_rate)
-        if not torch.is_tensor(field) or field.dtype != torch.int16 or field.device != self.device:
-            raise ValueError("mci_frames_scaled: field must be an int16 tensor on %s (mci_field)" % (self.device,))
-        f = (field.unsqueeze(0) if field.dim() == 3 else field).contiguous()
-        if tuple(f.shape) != (B, Hb, Wb, 2):
-            raise ValueError("mci_frames_scaled: the field of %d %dx%d model frames is [%d, %d, %d, 2], got %s" % (B, H, W, B, Hb, Wb, tuple(field.shape)))
-        k_first = int(k_first)
-        T = (s - k_first) if count is None else int(count)
-        if T < 1 or k_first < 0 or k_first + T - 1 > s:
-            raise ValueError("mci_frames_scaled: frames %d..%d are outside the segment 0..%d" % (k_first, k_first + T - 1, s))
+        f = self._mci_field_arg(field, B, H, W, "mci_frames_scaled", ("model frames", "mci_field"))
+        k_first, T = self._mci_span(s, k_first, count, "mci_frames_scaled")
         shape = (T, B, h0, w0, 3)
         with torch.cuda.device(self.device):
             if out is None:
