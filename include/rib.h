@@ -471,6 +471,42 @@ int rib_cubic_scaled(rib_handle* h, int T, int B, int H, int W, int H0, int W0, 
 size_t rib_detail_workspace_bytes(rib_handle* h, int B, int H0, int W0);
 int rib_detail_field(rib_handle* h, int B, int H, int W, int H0, int W0, const uint8_t* a0_u8, const uint8_t* b0_u8,
                      const int16_t* field_i16, int precision, int border, int16_t* out_field_i16, void* workspace, void* hip_stream);
+/* rib_accel_workspace_bytes / rib_accel_field / rib_accel_frames (the driver's --mci-motion quadratic; background.mci_accel_host and
+ * mci_frames_accel_host, bit-equal): the second-order trajectory across key frames.  The entries above move a segment's content at
+ * constant velocity; these read the neighbouring segments' fields as well.
+ * Field: cur_i16 int16 [B,Hb,Wb,2] the block fields of B segments (any of the field entries above: the entry takes the FIELD's
+ * shape, so it serves the model-size fields and rib_detail_field's alike), prev_i16 / next_i16 the fields of the segments before and after
+ * each, same shape and unit; half: 0 = whole pixels, 1 = half pixels (rib_halfpel_refine's).  Which neighbours exist: a NULL prev_i16
+ * (next_i16) says no item has one; present_u8, NULL or uint8 [B,2] on the device, says it per item - present[2 b] nonzero: item b has a
+ * previous segment, present[2 b + 1]: a next one (the planes of absent neighbours are not read) - for groups whose members differ;
+ * NULL: every item has each neighbour whose pointer is given.  Per block (by, bx) with (fx, fy) = cur >> half (floor): prev is read at
+ * block (clamp((8 by + 4 - 2 fy) >> 3), clamp((8 bx + 4 - 2 fx) >> 3)), next at (clamp((8 by + 4 + 2 fy) >> 3), clamp((8 bx + 4 + 2 fx)
+ * >> 3)); both: a = next - prev; only next: 2 (next - cur); only prev: 2 (cur - prev); neither: 0; then rib_mci_field's 3x3 median ->
+ * accel_i16 int16 [B,Hb,Wb,2] in the fields' unit (|a| <= 4 max|field|: 5104 at most, for components within +-1276).  workspace:
+ * rib_accel_workspace_bytes(h, B, Hb, Wb) bytes on the device, 16-byte aligned, nothing to clear (the field before the median); it must
+ * not overlap accel_i16.  TWO launches on `stream`; no atomics, no synchronisation, an item's result does not depend on B.  B outside
+ * 1..32767, Hb or Wb outside 1..2048, B * Hb * Wb >= 2^30, half outside {0, 1}, cur, accel or workspace NULL, a misaligned pointer:
+ * RIB_ERR_INVALID with a rib_last_error text that names the entry, nothing launched (the size query returns 0).
+ * Frames: rib_mci_frames' arguments, contract and outputs with accel_i16 (the field above, for the same B segments), and as arguments
+ * what the other frame entries are named for: precision (0 whole, 1 half pixels: field_i16's AND accel_i16's unit), sampler (0 bilinear,
+ * 1 rib_cubic_frames' 4x4 sample, staged per tile by its rule on the CORRECTED positions), ma_u8 / mb_u8 (both NULL: the person is kept;
+ * both given: rib_masked_frames' / rib_cubic_frames' clean-sample rule).  Acc(p) is bilinear from accel_i16 exactly as D(p) is from
+ * field_i16 (1/256 of the unit); with UNIT = 2 (precision 0) or 1, c = (UNIT * k * (s - k) * Acc + 2 s^2) >> (2 log2 s + 2), a 64-bit
+ * product and an arithmetic shift; A is sampled at p - off_a + c and B at p + off_b + c, off_a, off_b rib_mci_frames' rounded offsets:
+ * BOTH samples move by c, which is 0 at k = 0 and k = s and a / 8 in the middle.  Blend, border = 1 and the masks act on those
+ * positions.  An all-zero accel_i16 gives the bytes of rib_mci_frames / rib_halfpel_frames / rib_masked_frames / rib_cubic_frames.  ONE
+ * launch, no workspace; a frame's bytes do not depend on T or B.  The refusals, each RIB_ERR_INVALID with a rib_last_error text that
+ * names the entry, nothing launched: rib_mci_frames' (sizes, sample_rate a power of two <= 1024, the frame range, border, NULL or
+ * misaligned pointers, both outputs NULL), precision or sampler outside {0, 1}, accel_i16 NULL or misaligned, exactly one mask NULL.
+ * Named rib_accel_*, not rib_mci_*: that family stays at four.  Second order from three fields: a wrong neighbour field gives a wrong
+ * correction, the median is the only guard, and there is still no interior occlusion reasoning. */
+size_t rib_accel_workspace_bytes(rib_handle* h, int B, int Hb, int Wb);
+int rib_accel_field(rib_handle* h, int B, int Hb, int Wb, const int16_t* prev_i16, const int16_t* cur_i16, const int16_t* next_i16,
+                    const uint8_t* present_u8, int half, int16_t* accel_i16, void* workspace, void* hip_stream);
+int rib_accel_frames(rib_handle* h, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8,
+                     const uint8_t* ma_u8, const uint8_t* mb_u8,   /* both NULL: the person is kept; exactly one NULL: invalid */
+                     const int16_t* field_i16, const int16_t* accel_i16, int sample_rate, int k_first, int border, int precision,
+                     int sampler, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream);
 void rib_mci_field_shape(int H, int W, int* Hb, int* Wb);
 size_t rib_mci_workspace_bytes(rib_handle* h, int B, int H, int W, int levels);
 int rib_mci_field(rib_handle* h, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, int16_t* field_i16,

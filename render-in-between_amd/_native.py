@@ -87,6 +87,9 @@ SIGNATURES = {
     "rib_cubic_scaled": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p] * 2),
     "rib_detail_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "rib_detail_field": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3 + [C.c_int] * 2 + [C.c_void_p] * 3),
+    "rib_accel_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "rib_accel_field": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3),
+    "rib_accel_frames": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_void_p] * 3),
     "rib_set_debug_taps": (C.c_int, [C.c_void_p, C.c_int]),
     "rib_num_taps": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "rib_tap_info": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char_p),

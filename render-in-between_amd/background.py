@@ -112,9 +112,20 @@ rib_halfpel_frames) are held bit-equal to them (tests/test_gpu_mci.py, tests/tes
              model-size floats the generator reads stay the model-size field's.  A wrong model-size vector stays wrong beyond R;
              above ratio 8 R no longer covers the quantum; no interior occlusion reasoning.
 
-No quarter-pel search, no sub-pel search on the coarse levels, and no occlusion reasoning beyond the frame border under
-border="valid" - a foreground object that covers background is not handled unless the person is excluded (`rib_masked_*`): see
-DESIGN ("Motion-compensated backgrounds") for what that costs."""
+  motion     (mci_accel_host / mci_frames_accel_host, the driver's mci_motion="quadratic"; rib_accel_field / rib_accel_frames,
+             tests/test_gpu_mci_motion.py; "linear" by default).  Everything above moves a segment's content at constant velocity, so
+             across a clip it runs along a polyline whose velocity jumps at every key frame.  "quadratic" is the second-order
+             trajectory from three fields: a block's acceleration a is the difference of the NEXT and the PREVIOUS segment's vectors,
+             each read at the block the content comes from or goes to (two vectors away: motion-compensated lookups, clamped), one-
+             sided (twice the difference to the segment's own vector) where a clip has no segment on one side, 0 where it has none;
+             then the 3x3 median.  Frame k: Acc(p) bilinear from that block field exactly as D(p) is, and BOTH samples move by
+             c = (UNIT k (s - k) Acc + 2 s^2) >> (2 log2 s + 2) - a t (1 - t) / 2 at t = k / s, zero at the key frames, a / 8 in the
+             middle.  Offsets, sampler, blend, border and person rules are unchanged and act on the corrected positions; a zero
+             acceleration field gives the linear bytes.  A wrong neighbour field gives a wrong correction: the median is the only guard.
+
+No quarter-pel search, no sub-pel search on the coarse levels, nothing above second order in time, and no occlusion reasoning
+beyond the frame border under border="valid" - a foreground object that covers background is not handled
+unless the person is excluded (`rib_masked_*`): see DESIGN ("Motion-compensated backgrounds") for what that costs."""
 from __future__ import annotations
 
 import numpy as np
@@ -146,6 +157,7 @@ DETAILS = ("model", "keyframes")          # the driver's mci_detail: "keyframes"
 DETAIL_MAX_RADIUS = 4     # detail_radius: at most +-4 output pixels around the scaled model-size vector (covers the quantum up to ratio 8)
 DETAIL_MAX_DISP = 79 * 16 + DETAIL_MAX_RADIUS          # 1268: max_disp(5) at ratio 16, plus the radius
 DETAIL_KEY_BIAS = 2048    # pack_key_detail: dy + 2048, dx + 2048 in 12 bits each (DETAIL_MAX_DISP < 2048)
+MOTIONS = ("linear", "quadratic")         # the driver's mci_motion: "quadratic" = mci_accel_host / mci_frames_accel_host, the second-order trajectory
 
 
 def field_shape(height, width):
@@ -246,6 +258,22 @@ def check_detail(background, output_size, mci_detail="model", who="evaluate_from
         raise ValueError("%s: mci_detail='keyframes' is a setting of background='mci' with output_size='keyframes' (the field is "
                          "refined at the key frames' own size)" % who)
     return mci_detail
+
+
+def check_motion(background, mci_motion="linear", who="evaluate_from_folder", output_size="model", mci_detail="model"):
+    """The folder driver's mci_motion, checked beside check_settings and check_detail (check_settings' parameter list is pinned): "linear"
+    (the default: constant velocity between two key frames) or "quadratic" (mci_accel_host / mci_frames_accel_host: the second-order
+    trajectory from the neighbouring segments' fields), which needs background="mci" -> mci_motion, the caller's to pass on.
+    output_size="keyframes" takes it only with mci_detail="keyframes" (the frames are then mci_frames_accel_host on the full-size key
+    frames); the scaled frame functions have no acceleration yet."""
+    if not isinstance(mci_motion, str) or mci_motion not in MOTIONS:
+        raise ValueError("%s: mci_motion must be 'linear' or 'quadratic', got %r" % (who, mci_motion))
+    if mci_motion != "linear" and background != "mci":
+        raise ValueError("%s: mci_motion is a setting of background='mci'" % who)
+    if mci_motion != "linear" and output_size == "keyframes" and mci_detail != "keyframes":
+        raise ValueError("%s: mci_motion='quadratic' with output_size='keyframes' needs mci_detail='keyframes' for now (the scaled entries "
+                         "take no acceleration: a scaled acceleration in rib_scaled_frames / rib_cubic_scaled is the follow-up)" % who)
+    return mci_motion
 
 
 def max_disp(levels):
@@ -1005,6 +1033,122 @@ def mci_detail_field_host(a0_u8, b0_u8, field, model_hw, border="clamp", precisi
     sx, sy = detail_start(field, (H, W), (h0, w0), precision)
     dx, dy = search_detail(luma(a0_u8), luma(b0_u8), sx.astype(np.int32), sy.astype(np.int32), radius, border)
     return np.stack([median3(dx), median3(dy)], -1).astype(np.int16)
+
+
+# ---- quadratic motion across key frames (mci_motion="quadratic"): the module text's "motion" paragraph ------------------------------
+
+ACCEL_MAX = 4 * (DETAIL_MAX_DISP + 8)     # 5104: the largest |component| of mci_accel_host (fields within +-1276, pack_key_detail's bound)
+
+
+def mci_accel_host(f_prev, f, f_next, unit_shift=0):
+    """The block acceleration field of one segment (rib_accel_field, bit-equal): f int16 [Hb, Wb, 2] the segment's block field
+    (mci_field_host / mci_field_masked_host / mci_detail_field_host in whole pixels, unit_shift = 0; mci_refine_host's in half pixels,
+    unit_shift = 1), f_prev and f_next the fields of the segments before and after it, same shape and unit, either None ->
+    int16 [Hb, Wb, 2] in the FIELD'S unit.  Per block (by, bx) with vector (fx, fy) = f[by, bx] >> unit_shift (whole pixels, floor):
+      lookups  motion compensated: the previous field at block (clamp((8 by + 4 - 2 fy) >> 3), clamp((8 bx + 4 - 2 fx) >> 3)), the next
+               one at (clamp((8 by + 4 + 2 fy) >> 3), clamp((8 bx + 4 + 2 fx) >> 3)) - what passes this block's centre was two vectors
+               away one segment earlier, and will be two vectors on one segment later;
+      both     a = next - prev: (v_next - v_prev) / 2 with v = 2 f the motion across a segment;
+      one      only next: a = 2 (next - f); only prev: a = 2 (f - prev); neither: a = 0;
+      median   median3 per component.
+    a is the change of a segment's motion from one segment to the next in pixels (UNIT * a / 2 with mci_frames_host's UNIT).
+    Bound: |a| <= 4 max|f|: 316 from max_disp(5), 636 from its half-pel field, ACCEL_MAX = 5104 from the +-1276 that pack_key_detail
+    holds for the fields of the key frames' size - int16 holds it, and the fields' components must lie within +-1276."""
+    f = np.asarray(f)
+    if f.dtype != np.int16 or f.ndim != 3 or f.shape[2] != 2 or f.size == 0:
+        raise ValueError("mci_accel_host: the field is int16 [Hb, Wb, 2], got %s %s" % (f.dtype, tuple(f.shape)))
+    if unit_shift not in (0, 1):
+        raise ValueError("mci_accel_host: unit_shift is 0 (whole pixels) or 1 (half pixels), got %r" % (unit_shift,))
+    Hb, Wb = f.shape[:2]
+    side = []
+    for g in (f_prev, f_next):
+        g = None if g is None else np.asarray(g)
+        if g is not None and (g.dtype != np.int16 or g.shape != f.shape):
+            raise ValueError("mci_accel_host: a neighbour's field is int16 %s like the segment's, got %s %s" % (tuple(f.shape), g.dtype, tuple(g.shape)))
+        side.append(g)
+    for g in [f] + [g for g in side if g is not None]:
+        if np.abs(g.astype(np.int32)).max() > ACCEL_MAX // 4:
+            raise ValueError("mci_accel_host: the fields' components must lie in -%d..%d" % (ACCEL_MAX // 4, ACCEL_MAX // 4))
+    cur = f.astype(np.int32)
+    wx, wy = cur[..., 0] >> unit_shift, cur[..., 1] >> unit_shift
+    by, bx = np.mgrid[0:Hb, 0:Wb]
+
+    def at(g, sign):
+        return g.astype(np.int32)[np.clip((BLOCK * by + 4 + sign * 2 * wy) >> 3, 0, Hb - 1), np.clip((BLOCK * bx + 4 + sign * 2 * wx) >> 3, 0, Wb - 1)]
+    prev, nxt = side
+    if prev is not None and nxt is not None:
+        a = at(nxt, 1) - at(prev, -1)
+    elif nxt is not None:
+        a = 2 * (at(nxt, 1) - cur)
+    elif prev is not None:
+        a = 2 * (cur - at(prev, -1))
+    else:
+        a = np.zeros_like(cur)
+    return np.stack([median3(a[..., 0]), median3(a[..., 1])], -1).astype(np.int16)
+
+
+def accel_correction(accel, sample_rate, k, height, width, precision="full"):
+    """(cx, cy) int32 [H, W], 1/256 px: what mci_frames_accel_host adds to BOTH sample positions of frame k.  Acc(p) is pixel_field of
+    the block acceleration field (bilinear between the block centres, exact in 1/256 of the field's unit); c = (UNIT * k * (s - k) * Acc +
+    2 s^2) >> (2 log2 s + 2), the product in 64 bits, the shift arithmetic (floor): a t (1 - t) / 2 at t = k / s, rounded."""
+    unit = 1 if check_precision(precision, "accel_correction") == "half" else 2
+    s, ls = int(sample_rate), log2_rate(sample_rate)
+    Ax, Ay = pixel_field(np.asarray(accel), height, width)
+    m = np.int64(unit * int(k) * (s - int(k)))
+    return tuple(((m * A.astype(np.int64) + 2 * s * s) >> (2 * ls + 2)).astype(np.int32) for A in (Ax, Ay))
+
+
+def mci_frames_accel_host(a_u8, b_u8, field, accel, sample_rate, ks, border="clamp", precision="full", sampler="bilinear", ma=None, mb=None):
+    """mci_frames_host (ma, mb None) / mci_frames_masked_host (both given) on a second-order trajectory (rib_accel_frames, bit-equal):
+    accel int16 [Hb, Wb, 2] is mci_accel_host's field of the segment, in `field`'s unit.  A point that moves x(tau) = x0 + u tau +
+    a tau^2 / 2 with x(1) - x(0) = UNIT D and passes the pixel p at t = k / s was at x(0) = p - t UNIT D + c and will be at
+    x(1) = p + (1 - t) UNIT D + c, c = a t (1 - t) / 2: BOTH samples move by the same correction (accel_correction), which vanishes at
+    k = 0 and k = s and is a / 8 in the middle.  A is sampled at p - off_a + c, B at p + off_b + c, off_a and off_b mci_frames_host's
+    rounded offsets; the sampler, the blend, the k = 0 / k = s rule, the "valid" switch and the clean-sample switch act on those
+    positions as they do there.  accel all zero: the bytes of mci_frames_host / mci_frames_masked_host, for every shape and setting.
+    -> uint8 [len(ks), H, W, 3]."""
+    who = "mci_frames_accel_host"
+    check_border(border, who)
+    unit = 1 if check_precision(precision, who) == "half" else 2
+    cubic = check_sampler(sampler, who) == "cubic"
+    sample = sample_cubic if cubic else sample_bilinear
+    a_u8, b_u8, field, accel = np.asarray(a_u8), np.asarray(b_u8), np.asarray(field), np.asarray(accel)
+    if a_u8.dtype != np.uint8 or a_u8.ndim != 3 or a_u8.shape[2] != 3 or a_u8.shape != b_u8.shape or b_u8.dtype != np.uint8:
+        raise ValueError("%s: two uint8 [H, W, 3] frames of one size, got %s and %s" % (who, a_u8.shape, b_u8.shape))
+    if (ma is None) != (mb is None):
+        raise ValueError("%s: the masks are given together or not at all" % who)
+    s, ls = int(sample_rate), log2_rate(sample_rate)
+    H, W = a_u8.shape[:2]
+    if accel.dtype != np.int16 or accel.shape != field.shape:
+        raise ValueError("%s: the acceleration field is int16 %s like the block field, got %s %s" % (who, tuple(field.shape), accel.dtype, tuple(accel.shape)))
+    masked = ma is not None
+    if masked:
+        ma, mb = check_masks(ma, mb, H, W, who)
+        clean = sample_clean_cubic if cubic else sample_clean
+    Dx, Dy = pixel_field(field, H, W)
+    Y, X = np.mgrid[0:H, 0:W]
+    Y, X = (Y << SAMPLE_FRAC_BITS).astype(np.int32), (X << SAMPLE_FRAC_BITS).astype(np.int32)
+    out = np.empty((len(ks), H, W, 3), np.uint8)
+    for j, k in enumerate(ks):
+        k = int(k)
+        if not 0 <= k <= s:
+            raise ValueError("%s: frame %d is outside the segment 0..%d" % (who, k, s))
+        cx, cy = accel_correction(accel, s, k, H, W, precision)
+        pay, pax = Y - ((unit * k * Dy + s // 2) >> ls) + cy, X - ((unit * k * Dx + s // 2) >> ls) + cx
+        pby, pbx = Y + ((unit * (s - k) * Dy + s // 2) >> ls) + cy, X + ((unit * (s - k) * Dx + s // 2) >> ls) + cx
+        a, b = sample(a_u8, pay, pax), sample(b_u8, pby, pbx)
+        o = ((s - k) * a + k * b + s // 2) >> ls
+        oka = okb = np.ones((H, W), bool)
+        if masked:
+            oka, okb = clean(ma, pay, pax), clean(mb, pby, pbx)
+        if border == "valid":
+            oka, okb = oka & sample_valid(pay, pax, H, W), okb & sample_valid(pby, pbx, H, W)
+        oka, okb = oka[..., None], okb[..., None]
+        o = np.where(oka == okb, o, np.where(oka, a, b))
+        if masked and (k == 0 or k == s):   # the key frames themselves, whatever their masks
+            o = a if k == 0 else b
+        out[j] = o.astype(np.uint8)
+    return out
 
 
 def normalised(u8):

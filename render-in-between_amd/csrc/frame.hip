@@ -882,4 +882,101 @@ int rib_cubic_scaled(rib_handle* handle, int T, int B, int H, int W, int H0, int
   HIP_TRY(h, e);
   return RIB_OK;
 }
+
+// rib_accel_field / rib_accel_frames: the second-order trajectory across key frames (background.mci_accel_host / mci_frames_accel_host).
+// The field entry takes block-field shapes, not frame sizes: it serves the model-size fields and rib_detail_field's alike.
+static bool accel_layout(int B, int Hb, int Wb, size_t* bytes) {
+  constexpr int MAX_BLOCKS = MCI_MAX_SIDE / MCI_BLOCK;
+  if (B < 1 || B > 32767 || Hb < 1 || Wb < 1 || Hb > MAX_BLOCKS || Wb > MAX_BLOCKS || (size_t)B * Hb * Wb > (size_t)INT32_MAX / 2) return false;
+  *bytes = align256((size_t)B * Hb * Wb * 2 * sizeof(int16_t));
+  return true;
+}
+
+size_t rib_accel_workspace_bytes(rib_handle* h, int B, int Hb, int Wb) {
+  size_t n;
+  return h && accel_layout(B, Hb, Wb, &n) ? n : 0;
+}
+
+int rib_accel_field(rib_handle* handle, int B, int Hb, int Wb, const int16_t* prev_i16, const int16_t* cur_i16, const int16_t* next_i16,
+                    const uint8_t* present_u8, int half, int16_t* accel_i16, void* workspace, void* hip_stream) {
+  static const char who[] = "rib_accel_field";
+  FrameState* h;
+  size_t bytes;
+  int rc;
+  if ((rc = mci_handle(handle, who, &h)) || (rc = need_pointers(h, who, cur_i16 && accel_i16 && workspace))) return rc;
+  if (!accel_layout(B, Hb, Wb, &bytes))
+    return refuse(h, fmt("%s: B=%d Hb=%d Wb=%d: 1 <= B <= 32767, Hb and Wb in 1..%d, B * Hb * Wb < 2^30", who, B, Hb, Wb, MCI_MAX_SIDE / MCI_BLOCK));
+  if (half != 0 && half != 1) return refuse(h, fmt("%s: half=%d: 0 (the fields in whole pixels) or 1 (in half pixels)", who, half));
+  if (off_alignment(prev_i16, 1) || off_alignment(cur_i16, 1) || off_alignment(next_i16, 1) || off_alignment(accel_i16, 1) || off_alignment(workspace, 15))
+    return refuse(h, fmt("%s: misaligned pointer", who));
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  MciAccelParams ap;
+  ap.prev = prev_i16; ap.cur = cur_i16; ap.next = next_i16; ap.present = present_u8; ap.out = static_cast<int16_t*>(workspace);
+  ap.B = B; ap.Hb = Hb; ap.Wb = Wb; ap.shift = half;
+  hipLaunchKernelGGL(k_mci_accel, dim3(std::min((B * Hb * Wb + 255) / 256, 1024)), dim3(256), 0, st, ap);
+  HIP_TRY(h, hipGetLastError());
+  return enqueue_median(h, st, static_cast<const int16_t*>(workspace), accel_i16, B, Hb, Wb);
+}
+
+static int check_sampler(FrameState* h, const char* who, int sampler) {
+  return sampler == 0 || sampler == 1 ? RIB_OK : refuse(h, fmt("%s: sampler=%d: 0 (bilinear) or 1 (the 4x4 cubic sample)", who, sampler));
+}
+static int check_accel_pointer(FrameState* h, const char* who, const void* accel_i16) {
+  if (!accel_i16) return refuse(h, fmt("%s: the acceleration field is null (rib_accel_field makes it)", who));
+  return off_alignment(accel_i16, 1) ? refuse(h, fmt("%s: misaligned acceleration field", who)) : RIB_OK;
+}
+static int check_mask_pair(FrameState* h, const char* who, const void* ma_u8, const void* mb_u8) {
+  if ((ma_u8 == nullptr) == (mb_u8 == nullptr)) return RIB_OK;
+  return refuse(h, fmt("%s: exactly one mask is null (both: the person is excluded; neither: kept)", who));
+}
+
+int rib_accel_frames(rib_handle* handle, int T, int B, int H, int W, const uint8_t* a_u8, const uint8_t* b_u8, const uint8_t* ma_u8,
+                     const uint8_t* mb_u8, const int16_t* field_i16, const int16_t* accel_i16, int sample_rate, int k_first, int border,
+                     int precision, int sampler, float* out_f32_nchw, uint8_t* out_u8_nhwc, void* hip_stream) {
+  static const char who[] = "rib_accel_frames";
+  FrameState* h;
+  MciLayout L;
+  int rc;
+  if ((rc = mci_handle(handle, who, &h)) || (rc = need_pointers(h, who, a_u8 && b_u8 && field_i16)) ||
+      (rc = need_an_output(h, who, out_f32_nchw, out_u8_nhwc)) || (rc = check_frames_shape(h, who, T, B, H, W, &L)) ||
+      (rc = check_rate(h, who, sample_rate)) || (rc = check_span(h, who, T, sample_rate, k_first)) || (rc = check_border(h, who, border)) ||
+      (rc = check_precision(h, who, precision)) || (rc = check_sampler(h, who, sampler)) || (rc = check_accel_pointer(h, who, accel_i16)) ||
+      (rc = check_mask_pair(h, who, ma_u8, mb_u8)) || (rc = check_frame_pointers(h, who, field_i16, out_f32_nchw)))
+    return rc;
+  const bool masked = ma_u8 != nullptr;
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  HIP_TRY(h, hipSetDevice(h->device));
+  if (sampler == 1) {
+    CubicAccelParams ap;
+    CubicFramesParams& fp = ap.f;
+    fp.a = a_u8; fp.b = b_u8; fp.ma = ma_u8; fp.mb = mb_u8; fp.field = field_i16; fp.out_f32 = out_f32_nchw; fp.out_u8 = out_u8_nhwc;
+    fp.T = T; fp.B = B; fp.H = H; fp.W = W; fp.Hb = L.Hb[0]; fp.Wb = L.Wb[0];
+    set_segment(fp, sample_rate, k_first);
+    fp.stage = 1;
+    fp.w_off = out_u8_nhwc ? (W * 3 + 32 + 15) & ~15 : 0;
+    ap.accel = accel_i16;
+    const size_t lds = (size_t)fp.w_off + CUBIC_WTAB_BYTES + CUBIC_WIN_BYTES;
+    void (*const kernels[2][2][2])(CubicAccelParams) = {      // [masked][precision][border]
+        {{k_cubic_accel<false, false, false>, k_cubic_accel<true, false, false>}, {k_cubic_accel<false, true, false>, k_cubic_accel<true, true, false>}},
+        {{k_cubic_accel<false, false, true>, k_cubic_accel<true, false, true>}, {k_cubic_accel<false, true, true>, k_cubic_accel<true, true, true>}}};
+    HIP_TRY(h, cubic_launch(kernels[masked][precision][border], dim3(H, T * B), lds, st, ap));
+    return RIB_OK;
+  }
+  AccelFramesParams ap;
+  MciFramesParams& fp = ap.f;
+  fp.a = a_u8; fp.b = b_u8; fp.field = field_i16; fp.out_f32 = out_f32_nchw; fp.out_u8 = out_u8_nhwc;
+  fp.T = T; fp.B = B; fp.H = H; fp.W = W; fp.Hb = L.Hb[0]; fp.Wb = L.Wb[0];
+  set_segment(fp, sample_rate, k_first);
+  fp.vec = (W % 4 == 0 && !off_alignment(out_f32_nchw, 15) && !off_alignment(out_u8_nhwc, 3)) ? 1 : 0;
+  fp.ma = ma_u8; fp.mb = mb_u8;
+  ap.accel = accel_i16;
+  const size_t lds = out_u8_nhwc ? (size_t)W * 3 + 32 : 0;
+  void (*const kernels[2][2][2])(AccelFramesParams) = {      // [masked][precision][border]
+      {{k_accel_frames<false, false, false>, k_accel_frames<true, false, false>}, {k_accel_frames<false, true, false>, k_accel_frames<true, true, false>}},
+      {{k_accel_frames<false, false, true>, k_accel_frames<true, false, true>}, {k_accel_frames<false, true, true>, k_accel_frames<true, true, true>}}};
+  hipLaunchKernelGGL(kernels[masked][precision][border], dim3(H, T * B), dim3(256), lds, st, ap);
+  HIP_TRY(h, hipGetLastError());
+  return RIB_OK;
+}
 }  // extern "C"

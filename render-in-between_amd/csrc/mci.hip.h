@@ -1,6 +1,7 @@
 // mci.hip.h — motion-compensated interpolation of a segment's two key frames: the folder driver's background="mci" (include/rib.h:
 // rib_mci_field / rib_masked_field / rib_halfpel_refine / rib_detail_field make the block field; rib_mci_frames / rib_halfpel_frames /
-// rib_masked_frames / rib_scaled_frames / rib_cubic_frames / rib_cubic_scaled the frames).  This project's interpolation, not DAIN.
+// rib_masked_frames / rib_scaled_frames / rib_cubic_frames / rib_cubic_scaled the frames; rib_accel_field / rib_accel_frames the
+// second-order trajectory across key frames, at the end of this file).  This project's interpolation, not DAIN.
 // background.py states every result in integers; every kernel here is bit-equal to it.
 //
 // SHARED PIECES
@@ -1214,6 +1215,205 @@ __global__ __launch_bounds__(256) void k_detail_search(DetailSearchParams p) {
       o[1] = (int16_t)((int)((best >> 12) & 4095) - DETAIL_KEY_BIAS);
     }
   }
+}
+
+// ---- quadratic motion across key frames (rib_accel_field / rib_accel_frames; background.mci_accel_host / mci_frames_accel_host, the
+// driver's mci_motion="quadratic") -------------------------------------------------------------------------------------------------
+// k_mci_accel         one thread per block of one segment (a flat grid over B * Hb * Wb, as k_mci_median's): the block's own vector in
+//                     whole pixels (a half-pel field shifted with floor), the previous segment's field read at the block two vectors
+//                     back, the next one's two vectors on (block coordinates clamped), a = next - prev, or twice the one-sided
+//                     difference to the block's own vector where one neighbour is missing, or 0: the field BEFORE the median;
+//                     k_mci_median follows, as it is.  prev / next null: no item has that neighbour; present [B, 2] (prev, next)
+//                     bytes: per item, for groups whose members differ.  Every index is clamped; nothing of `out` is read.
+// k_accel_frames<VALID, HALF, MASKED>, k_cubic_accel<VALID, HALF, MASKED>
+//                     k_mci_frames' and k_cubic_frames' grids, outputs and LDS schemes, written with the shared pieces; per pixel one
+//                     more mci_field_at in the acceleration field and mci_accel_c: BOTH sample positions move by c = UNIT k (s - k)
+//                     Acc / (4 s^2), rounded, a 64-bit product.  The cubic tile's staging rule (cubic_samples) sees the corrected
+//                     positions.  They are kernels of their own so that k_mci_frames and k_cubic_frames keep their instruction streams.
+struct MciAccelParams {
+  const int16_t *prev, *cur, *next;         // [B, Hb, Wb, 2]; prev, next may be null
+  const uint8_t* present;                   // [B, 2] (prev, next) nonzero = this item has it, or null: every item has what is not null
+  int16_t* out;                             // [B, Hb, Wb, 2] before the median
+  int B, Hb, Wb, shift;                     // shift: 1 = the fields are in half pixels
+};
+
+__global__ __launch_bounds__(256) void k_mci_accel(MciAccelParams p) {
+  const int nblk = p.Hb * p.Wb;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < p.B * nblk; i += gridDim.x * 256) {
+    const int b = i / nblk, blk = i - b * nblk, by = blk / p.Wb, bx = blk - by * p.Wb;
+    const size_t item = (size_t)b * nblk;
+    const int fx = p.cur[(item + blk) * 2], fy = p.cur[(item + blk) * 2 + 1];
+    const int wx = fx >> p.shift, wy = fy >> p.shift;
+    const bool hp = p.prev && (!p.present || p.present[2 * b]), hn = p.next && (!p.present || p.present[2 * b + 1]);
+    int px = fx, py = fy, nx = fx, ny = fy;   // a missing side stands in as the block's own vector: the one-sided difference
+    if (hp) {
+      const int y = min(max((MCI_BLOCK * by + 4 - 2 * wy) >> 3, 0), p.Hb - 1), x = min(max((MCI_BLOCK * bx + 4 - 2 * wx) >> 3, 0), p.Wb - 1);
+      const int16_t* s = p.prev + (item + y * p.Wb + x) * 2;
+      px = s[0]; py = s[1];
+    }
+    if (hn) {
+      const int y = min(max((MCI_BLOCK * by + 4 + 2 * wy) >> 3, 0), p.Hb - 1), x = min(max((MCI_BLOCK * bx + 4 + 2 * wx) >> 3, 0), p.Wb - 1);
+      const int16_t* s = p.next + (item + y * p.Wb + x) * 2;
+      nx = s[0]; ny = s[1];
+    }
+    const int m = hp && hn ? 1 : 2;           // (neither: next - prev is 0 already)
+    p.out[(item + blk) * 2] = (int16_t)(m * (nx - px));
+    p.out[(item + blk) * 2 + 1] = (int16_t)(m * (ny - py));
+  }
+}
+
+// c of one component: (m * Acc + 2 s^2) >> (2 log2 s + 2) with m = UNIT * k * (s - k) <= 2^19 and Acc in 1/256 of the field's unit
+// (|Acc| < 2^23): the product needs 64 bits from s = 64 on
+__device__ inline int mci_accel_c(int Acc, int m, int ls) { return (int)(((long long)m * Acc + (2ll << (2 * ls))) >> (2 * ls + 2)); }
+
+struct AccelFramesParams {
+  MciFramesParams f;                        // k_mci_frames' own
+  const int16_t* accel;                     // [B, Hb, Wb, 2]: k_mci_accel's field after the median, in the field's unit
+};
+
+template <bool VALID = false, bool HALF = false, bool MASKED = false>
+__global__ __launch_bounds__(256) void k_accel_frames(AccelFramesParams ap) {
+  constexpr int UNIT = HALF ? 1 : 2;
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_mci[];
+  const MciFramesParams& p = ap.f;
+  const int y = blockIdx.x, tb = blockIdx.y, t = tb / p.B, bi = tb - t * p.B;
+  const int H = p.H, W = p.W, k = p.k_first + t, s = p.s, ls = p.ls;
+  const int rowbytes = W * 3;
+  uint8_t* grow = p.out_u8 ? p.out_u8 + ((size_t)tb * H + y) * (size_t)rowbytes : nullptr;
+  const int shift = (int)(reinterpret_cast<uintptr_t>(grow) & 15);
+  uint8_t* srow = s_mci + shift;
+  const size_t HW = (size_t)H * W;
+  const uint8_t* A = p.a + (size_t)bi * HW * 3;
+  const uint8_t* Bf = p.b + (size_t)bi * HW * 3;
+  const int16_t* fld = p.field + (size_t)bi * p.Hb * p.Wb * 2;
+  const int16_t* acc = ap.accel + (size_t)bi * p.Hb * p.Wb * 2;
+  const int tyy = 2 * y - (MCI_BLOCK - 1), fy = tyy & 15;
+  const int r0 = min(max(tyy >> 4, 0), p.Hb - 1), r1 = min(max((tyy >> 4) + 1, 0), p.Hb - 1);
+  const int m = UNIT * k * (s - k);
+  const int W4 = (W + 3) >> 2;
+  for (int item = threadIdx.x; item < W4; item += 256) {
+    const int x0 = item * 4;
+    uint8_t q[12];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int x = min(x0 + j, W - 1);
+      int Dx, Dy, Ax, Ay, ax, ay, bx, by;
+      mci_field_at(fld, p.Wb, r0, r1, fy, x, Dx, Dy);
+      mci_field_at(acc, p.Wb, r0, r1, fy, x, Ax, Ay);
+      mci_offsets<UNIT>(Dx, Dy, k, s, ls, ax, ay, bx, by);
+      const int cx = mci_accel_c(Ax, m, ls), cy = mci_accel_c(Ay, m, ls);
+      const int pay = (y << 8) - ay + cy, pax = (x << 8) - ax + cx, pby = (y << 8) + by + cy, pbx = (x << 8) + bx + cx;
+      int v[2][3];
+      mci_sample(A, H, W, pay, pax, v[0]);
+      mci_sample(Bf, H, W, pby, pbx, v[1]);
+      bool oka = !VALID || mci_inside(pay, pax, H, W), okb = !VALID || mci_inside(pby, pbx, H, W);
+      if constexpr (MASKED) {                 // clean = valid under the border rule and all four taps clear; k = 0 and k = s stay A and B
+        oka = oka && mci_clean(p.ma + (size_t)bi * HW, H, W, pay, pax);
+        okb = okb && mci_clean(p.mb + (size_t)bi * HW, H, W, pby, pbx);
+        if (k == 0) { oka = true; okb = false; }
+        if (k == s) { oka = false; okb = true; }
+      }
+      mci_blend(v, oka, okb, k, s, ls, q + j * 3);
+    }
+    if (p.out_f32) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        float* dst = p.out_f32 + ((size_t)tb * 3 + c) * HW + (size_t)y * W + x0;
+        if (p.vec) {
+          *reinterpret_cast<float4*>(dst) = make_float4(rsz_normalise(q[c]), rsz_normalise(q[3 + c]), rsz_normalise(q[6 + c]), rsz_normalise(q[9 + c]));
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (x0 + j < W) dst[j] = rsz_normalise(q[j * 3 + c]);
+        }
+      }
+    }
+    if (grow) {                             // (written out as in k_mci_frames: DESIGN.md 4g-shared)
+      uint8_t* dst = srow + x0 * 3;
+      if (p.vec) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d)
+          reinterpret_cast<uint32_t*>(dst)[d] = (uint32_t)q[4 * d] | ((uint32_t)q[4 * d + 1] << 8) | ((uint32_t)q[4 * d + 2] << 16) | ((uint32_t)q[4 * d + 3] << 24);
+      } else {
+        const int nb = min(4, W - x0) * 3;
+#pragma unroll
+        for (int j = 0; j < 12; ++j)
+          if (j < nb) dst[j] = q[j];
+      }
+    }
+  }
+  if (!grow) return;                        // (uniform: no thread reaches the barrier)
+  __syncthreads();
+  mci_store_row(s_mci, grow, shift, rowbytes);
+}
+
+struct CubicAccelParams {
+  CubicFramesParams f;                      // k_cubic_frames' own
+  const int16_t* accel;                     // [B, Hb, Wb, 2]
+};
+
+template <bool VALID = false, bool HALF = false, bool MASKED = false>
+__global__ __launch_bounds__(256) void k_cubic_accel(CubicAccelParams ap) {
+  constexpr int UNIT = HALF ? 1 : 2;
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_mci[];
+  const CubicFramesParams& p = ap.f;
+  const int y = blockIdx.x, tb = blockIdx.y, t = tb / p.B, bi = tb - t * p.B;
+  const int H = p.H, W = p.W, k = p.k_first + t, s = p.s, ls = p.ls;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int rowbytes = W * 3;
+  uint8_t* grow = p.out_u8 ? p.out_u8 + ((size_t)tb * H + y) * (size_t)rowbytes : nullptr;
+  const int shift = (int)(reinterpret_cast<uintptr_t>(grow) & 15);
+  uint8_t* srow = s_mci + shift;
+  cubic_w4* wtab = reinterpret_cast<cubic_w4*>(s_mci + p.w_off);
+  uint32_t* win = reinterpret_cast<uint32_t*>(s_mci + p.w_off + CUBIC_WTAB_BYTES) + wave * 2 * CUBIC_WIN;
+  wtab[threadIdx.x] = cubic_weight_row(threadIdx.x);
+  __syncthreads();
+  const size_t HW = (size_t)H * W;
+  const uint8_t* A = p.a + (size_t)bi * HW * 3;
+  const uint8_t* Bf = p.b + (size_t)bi * HW * 3;
+  const uint8_t* MA = MASKED ? p.ma + (size_t)bi * HW : nullptr;
+  const uint8_t* MB = MASKED ? p.mb + (size_t)bi * HW : nullptr;
+  const int16_t* fld = p.field + (size_t)bi * p.Hb * p.Wb * 2;
+  const int16_t* acc = ap.accel + (size_t)bi * p.Hb * p.Wb * 2;
+  const int tyy = 2 * y - (MCI_BLOCK - 1), fy = tyy & 15;
+  const int r0 = min(max(tyy >> 4, 0), p.Hb - 1), r1 = min(max((tyy >> 4) + 1, 0), p.Hb - 1);
+  const int m = UNIT * k * (s - k);
+  const int ntiles = (W + CUBIC_TILE - 1) / CUBIC_TILE;
+  for (int tile = wave; tile < ntiles; tile += 4) {      // (uniform per wave: every lane of the wave is in cubic_samples)
+    const int xo = tile * CUBIC_TILE + lane, x = min(xo, W - 1);
+    int Dx, Dy, Ax, Ay, ax, ay, bx, by;
+    mci_field_at(fld, p.Wb, r0, r1, fy, x, Dx, Dy);
+    mci_field_at(acc, p.Wb, r0, r1, fy, x, Ax, Ay);
+    mci_offsets<UNIT>(Dx, Dy, k, s, ls, ax, ay, bx, by);
+    const int cx = mci_accel_c(Ax, m, ls), cy = mci_accel_c(Ay, m, ls);
+    CubicKey key[2] = {{A, MA, (y << 8) - ay + cy, (x << 8) - ax + cx}, {Bf, MB, (y << 8) + by + cy, (x << 8) + bx + cx}};
+    int v[2][3];
+    bool ok[2];
+    cubic_samples<MASKED>(key, H, W, p.stage != 0, win, wtab, lane, v, ok);
+    if constexpr (VALID) {
+#pragma unroll
+      for (int f = 0; f < 2; ++f) ok[f] = ok[f] && mci_inside(key[f].py, key[f].px, H, W);
+    }
+    if constexpr (MASKED) {                 // k = 0 and k = s stay A and B
+      if (k == 0) { ok[0] = true; ok[1] = false; }
+      if (k == s) { ok[0] = false; ok[1] = true; }
+    }
+    uint8_t q[3];
+    mci_blend(v, ok[0], ok[1], k, s, ls, q);
+    if (xo < W) {
+      if (p.out_f32) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) p.out_f32[((size_t)tb * 3 + c) * HW + (size_t)y * W + xo] = rsz_normalise(q[c]);
+      }
+      if (grow) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) srow[xo * 3 + c] = q[c];
+      }
+    }
+  }
+  if (!grow) return;                        // (uniform: no thread reaches the barrier)
+  __syncthreads();
+  mci_store_row(s_mci, grow, shift, rowbytes);
 }
 
 }  // namespace rib

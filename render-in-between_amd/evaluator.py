@@ -253,7 +253,7 @@ def section_views(flat, spec, table):
 
 
 def staging_spec(Tc, Bc, model_hw, src_dain=None, src_gt=None, want_gt=False, masks=False, keys=False, mci=False, mci_keys=False,
-                 src_keys=None, mci_keys_src=None):
+                 src_keys=None, mci_keys_src=None, mci_quad=False):
     """The spec of a unit's staging block, which the decode tasks fill and upload() sends to the GPU (DESIGN 4e has the table):
     Tc time steps of Bc segments at the model size (H, W).  src_dain / src_gt: (w0, h0) at which that list is staged for the
     GPU resize (resize_on="gpu"), None: the model size; want_gt, masks: ground-truth frames / masks are staged; keys: a first
@@ -261,19 +261,37 @@ def staging_spec(Tc, Bc, model_hw, src_dain=None, src_gt=None, want_gt=False, ma
     mci_keys: its first chunk, the group's left and right key frames.  src_keys: (w0, h0) - a first chunk under
     output_size="source" with video, the key frames it starts from at the output size, for their video files; the section
     `key_src` exists in the spec only then.  mci_keys_src: (w0, h0) - a group's first chunk under output_size="keyframes", its
-    left and right key frames' own pixels for rib_scaled_frames; the section `mci_keys_src` exists only then, after `key_src`."""
+    left and right key frames' own pixels for rib_scaled_frames; the section `mci_keys_src` exists only then, after `key_src`.
+    mci_quad: mci_motion="quadratic" - both key-frame sections hold FOUR key frames per member: left, right, the one before the left
+    and the one after the right (MCI_KEY_ROLES; where the clip has none, the left / right one again)."""
     H, W = model_hw
     (wd, hd), (wg, hg) = src_dain or (W, H), src_gt or (W, H)
+    nk = len(MCI_KEY_ROLES) if mci_quad else 2
     spec = (("dain", torch.uint8, (Tc, Bc, hd, wd, 3), not mci),
             ("gt", torch.uint8, (Tc, Bc, hg, wg, 3), want_gt),
             ("mask", torch.uint8, (Tc, Bc, H, W), masks),
             ("key", torch.uint8, (Bc, H, W, 3), keys and not mci),
-            ("mci_keys", torch.uint8, (2, Bc, H, W, 3), mci and mci_keys))
+            ("mci_keys", torch.uint8, (nk, Bc, H, W, 3), mci and mci_keys))
     if src_keys is not None:
         spec += (("key_src", torch.uint8, (Bc, src_keys[1], src_keys[0], 3), True),)
     if mci_keys_src is not None:
-        spec += (("mci_keys_src", torch.uint8, (2, Bc, mci_keys_src[1], mci_keys_src[0], 3), True),)
+        spec += (("mci_keys_src", torch.uint8, (nk, Bc, mci_keys_src[1], mci_keys_src[0], 3), True),)
     return spec
+
+
+MCI_KEY_ROLES = (0, 1, -1, 2)               # the key frames of a member's `mci_keys` / `mci_keys_src`, in segments from its left key frame
+
+
+def mci_key_frames(k, sample_rate, seq_len, quad):
+    """The key frames a segment starting at frame k stages for its backgrounds, in the sections' order: [left, right], and under
+    mci_motion="quadratic" also the key frame before and the one after (MCI_KEY_ROLES) -> ([frame index], (has_prev, has_next)).
+    A neighbour the clip does not have stands in as the left / right key frame itself and is flagged absent."""
+    roles = MCI_KEY_ROLES if quad else MCI_KEY_ROLES[:2]
+    has = (k - sample_rate >= 0, k + 2 * sample_rate <= seq_len - 1)
+    idx = [k + r * sample_rate for r in roles]
+    if quad:
+        idx[2], idx[3] = (idx[2] if has[0] else k), (idx[3] if has[1] else k + sample_rate)
+    return idx, has
 
 
 def _process_pool(n):
@@ -578,7 +596,8 @@ class Evaluator:
                              panels=False, panel_frames=False, panel_quality=90, panel_fps=30, panel_encode="host",
                              background="dain", mci_range=32, video=False, video_fps=30, video_quality=90, video_frames=False, frames="png",
                              poses="folder", key_pose_dir=None, upsample_rate=8, motion=None, save_poses=False, mci_border="clamp",
-                             mci_precision="full", output_size="model", png_on="host", mci_person="keep", mci_sampler="bilinear", mci_detail="model"):
+                             mci_precision="full", output_size="model", png_on="host", mci_person="keep", mci_sampler="bilinear", mci_detail="model",
+                             mci_motion="linear"):
         """rank / world: this process's share of the independent units (default: the torch.distributed process
         group when one is initialised, else everything).  Returns the frames THIS rank wrote.
         The call is one `_FolderPipeline` (below): plan a clip -> decode -> upload -> render -> sink, pipelined over units
@@ -640,7 +659,19 @@ class Evaluator:
         full-size block's vector by up to +-detail_radius whole output pixels, and the full-size backgrounds are the existing frame
         entry's (rib_mci_frames / rib_cubic_frames; mci_frames_host) on the full-size key frames with that field.  The model-size
         floats the chain reads are unchanged.  A wrong model-size vector stays wrong beyond the radius, which is capped at 4 (above a
-        size ratio of 8 it no longer covers the quantum); no interior occlusion reasoning; unmeasured on real footage.  dain_dir may be
+        size ratio of 8 it no longer covers the quantum); no interior occlusion reasoning; unmeasured on real footage.
+        mci_motion="quadratic" (default "linear"; a setting of background="mci"): between two key frames the background no longer moves
+        at constant velocity.  A segment (k, k + s) also reads the key frames k - s and k + 2 s where the clip has them (decoded by
+        the rank that renders the segment, so the files do not depend on ranks or grouping); the fields of the segments before and
+        after come from the same field entry (with mci_person="exclude" from their own key frames' pose masks, with
+        mci_precision="half" refined, with mci_detail="keyframes" refined at the key frames' size), all three in one batched call; one
+        rib_accel_field per group (background.mci_accel_host) makes the block acceleration, and every unit's frames come from
+        rib_accel_frames (mci_frames_accel_host): both samples of a pixel move by a t (1 - t) / 2.  A clip's first and last segment use
+        the one-sided difference; a clip of one segment has zero acceleration and gets the linear files byte for byte.  About three
+        times the field work per group.  Second order from three fields: a wrong neighbour field gives a wrong correction, the 3x3
+        median is the only guard; no interior occlusion reasoning; unmeasured on real footage.  Refused for now with
+        output_size="keyframes" unless mci_detail="keyframes" (the scaled entries rib_scaled_frames / rib_cubic_scaled take no
+        acceleration yet).  dain_dir may be
         None and is never listed or read; a frame's file is named after its pose file (stem without a trailing "_keypoints").
         On the native path the field is made once per group of segments (rib_mci_field) and every unit's frames by one launch
         (rib_mci_frames) on the upload stream - no DAIN bytes are staged or decoded; a model behind the reference's protocol is
@@ -723,6 +754,7 @@ class Evaluator:
                 raise ValueError("evaluate_from_folder: upsample_rate must be a power of two, got %r" % (upsample_rate,))
         _composite.check_output_size(output_size, "evaluate_from_folder")
         _background.check_detail(background, output_size, mci_detail)
+        _background.check_motion(background, mci_motion, output_size=output_size, mci_detail=mci_detail)
         mci_levels, mci_border = _background.check_settings(background, mci_range, mci_border, self.resize_on, mci_precision=mci_precision,
                                                             mci_person=mci_person, output_size=output_size, mci_sampler=mci_sampler)
         if output_size == "source" and background == "mci":
@@ -763,10 +795,10 @@ class Evaluator:
         pipe = _FolderPipeline(self, model, rank, world, gt_dir, metrics=bool(metrics), mask_dir=mask_dir, pose_mask=bool(pose_mask),
                                panels=bool(panels), panel_frames=bool(panel_frames), panel_quality=int(panel_quality),
                                panel_encode=panel_encode, background=background, mci_levels=mci_levels, mci_border=mci_border, mci_precision=mci_precision, mci_person=mci_person, mci_sampler=mci_sampler, mci_detail=mci_detail, video=bool(video), video_quality=int(video_quality),
-                               video_frames=bool(video_frames), write_png=frames == "png", output_size=output_size, png_gpu=png_on == "gpu",
+                               video_frames=bool(video_frames), write_png=frames == "png", output_size=output_size, png_gpu=png_on == "gpu", mci_motion=mci_motion,
                                key_poses=None if poses == "folder" else (motion, key_pose_dir, upsample_rate, poses == "keyframes-linear", bool(save_poses)))
         self.background, self.mci_range, self.mci_border, self.mci_precision = background, mci_range, mci_border, mci_precision
-        self.mci_person, self.mci_sampler, self.mci_detail = mci_person, mci_sampler, mci_detail
+        self.mci_person, self.mci_sampler, self.mci_detail, self.mci_motion = mci_person, mci_sampler, mci_detail, mci_motion
         self.output_size = output_size
         self.timings = pipe.tm
         if metrics and pipe.native:
@@ -880,7 +912,7 @@ class _FolderPipeline:
     def __init__(self, ev, model, rank, world, gt_dir, metrics=False, mask_dir=None, pose_mask=False,
                  panels=False, panel_frames=False, panel_quality=90, panel_encode="host", background="dain", mci_levels=3,
                  video=False, video_quality=90, video_frames=False, write_png=True, key_poses=None, mci_border="clamp", mci_precision="full",
-                 output_size="model", png_gpu=False, mci_person="keep", mci_sampler="bilinear", mci_detail="model"):
+                 output_size="model", png_gpu=False, mci_person="keep", mci_sampler="bilinear", mci_detail="model", mci_motion="linear"):
         # composite.py: the frames' files at the clip's own size - the DAIN frames' ("source") or, under background="mci", the key
         # frame files' ("keyframes": keysize; the backgrounds are then rib_scaled_frames', everything after them is "source"'s code)
         self.source = output_size in ("source", "keyframes")
@@ -891,6 +923,7 @@ class _FolderPipeline:
         self.mci_exclude = mci_person == "exclude"   # background.py's "person": the key frames' human masks keep the person out
         self.mci_sampler = mci_sampler               # background.py's sampler: "cubic" = sample_cubic / rib_cubic_* for every background sample
         self.mci_detail = mci_detail == "keyframes"  # background.py's "detail": the field refined at the key frames' size (output_size="keyframes" only)
+        self.mci_quad = mci_motion == "quadratic"    # background.py's "motion": the neighbouring segments' fields give every block an acceleration
         # poses="keyframes": (motion model, key-pose folder, upsample rate, take the linear clip, also write the json folders)
         self.key_poses = key_poses
         # video: the frames' JPEG files (video.py); write_png False (frames="none"): they are the only files of a frame
@@ -926,6 +959,8 @@ class _FolderPipeline:
             raise RuntimeError("output_size='keyframes': this model has no GPU kernel for the key frames' size (rib_scaled_frames)")
         if self.mci_detail and self.native and not hasattr(model, "mci_detail_field"):
             raise RuntimeError("mci_detail='keyframes': this model has no GPU kernel for the full-size field (rib_detail_field)")
+        if self.mci_quad and self.native and not (hasattr(model, "mci_accel_field") and hasattr(model, "mci_frames_accel")):
+            raise RuntimeError("mci_motion='quadratic': this model has no GPU kernels for it (rib_accel_field / rib_accel_frames)")
         if self.source and self.native:
             if ev.resize_on != "gpu" and not self.keysize:
                 raise ValueError("output_size='source' needs resize_on='gpu' on the native path: the background frames' source-size "
@@ -936,6 +971,8 @@ class _FolderPipeline:
                 raise RuntimeError("output_size='source' with video=True: this model has no GPU JPEG kernels (rib_jpeg)")
         self.gpu_labels = self.native and ev.label_fn is None and hasattr(model, "rasterise")
         per_slot = (1.0 + (1.0 if (metrics or (panels and gt_dir is not None)) else 0.0) + (1.0 / 3 if mask_dir is not None else 0.0))
+        if self.mci_quad:                    # a first chunk stages four key frames per member where the budget's frame per slot holds `chunk`
+            per_slot += max(0.0, float(len(MCI_KEY_ROLES)) / max(1, ev.chunk) - 1.0)
         if panels:                           # a unit's download block also carries its sheets (six panes and the borders per frame)
             sh, sw = _panel.layout(ev.height, ev.width)["sheet"]
             if not self.jpeg_gpu or panel_frames:                # (under panel_encode="gpu" only the lossless copies need the raw sheets)
@@ -1148,7 +1185,7 @@ class _FolderPipeline:
             w0, h0 = out_size
             slots = max((c1 - c0) * len(members) for _, members, c0, c1 in units)
             width = max(len(members) for _, members, _, _ in units)
-            need = shm_windows_bytes(int(slots * ev.height * ev.width * 3 * self.per_slot) + (2 + bool(self.video or self.png_gpu)) * width * w0 * h0 * 3
+            need = shm_windows_bytes(int(slots * ev.height * ev.width * 3 * self.per_slot) + ((len(MCI_KEY_ROLES) if self.mci_quad else 2) + bool(self.video or self.png_gpu)) * width * w0 * h0 * 3
                                      + (slots * w0 * h0 * 3 if self.stage_png else 0))
             free = _shm_free_bytes()
             if need > free:
@@ -1267,7 +1304,7 @@ class _FolderPipeline:
             spec = staging_spec(c1 - c0, len(members), (ev.height, ev.width), clip.src_dain, clip.src_gt, want_gt=clip.want_gt,
                                 masks=clip.mask_list is not None, keys=self.panels and c0 == 0, mci=self.mci, mci_keys=c0 == 0,
                                 src_keys=clip.out_size if (self.source and (self.video or self.png_gpu) and c0 == 0) else None,
-                                mci_keys_src=clip.out_size if (self.keysize and c0 == 0) else None)
+                                mci_keys_src=clip.out_size if (self.keysize and c0 == 0) else None, mci_quad=self.mci_quad)
             table, total = block_layout(spec_bytes(spec))
             # worker processes: shared with them and page-locked (size classes of 1 MB: the block may be larger than the unit)
             blk = _shm_get(max(1, total)) if self.procs is not None else None
@@ -1282,8 +1319,9 @@ class _FolderPipeline:
             for i in ([clip.segs[si][0] for si in members] if c0 == 0 else []) + clip.unit_frames(ui):
                 self.submit_load(clip, i)
             if self.mci and c0 == 0:            # the right key frames: decoded (not written: that is their own unit's rank)
-                for si in members:
-                    self.submit_load(clip, clip.segs[si][0] + clip.sample_rate)
+                for si in members:              # (mci_motion="quadratic": and the key frames of the segments before and after)
+                    for i in mci_key_frames(clip.segs[si][0], clip.sample_rate, len(clip.names), self.mci_quad)[0][1:]:
+                        self.submit_load(clip, i)
             clip.opened += 1
 
     # ---- stage 2: upload -------------------------------------------------------------------------------------------------
@@ -1318,34 +1356,55 @@ class _FolderPipeline:
             if self.mci:
                 if c0 == 0:                    # once per group: the key frames' bytes go up and the field is made
                     ks = [clip.segs[si][0] for si in members]
-                    for k in ks:
-                        clip.loads[k + clip.sample_rate].result(timeout=IO_TIMEOUT_S)
-                    for b, k in enumerate(ks):
-                        views["mci_keys"][0, b].copy_(clip.key_u8[k])
-                        views["mci_keys"][1, b].copy_(clip.key_u8[k + clip.sample_rate])
+                    # per member the key frames of the sections (mci_key_frames: left, right; quadratic: and the ones around them)
+                    keyf = [mci_key_frames(k, clip.sample_rate, len(clip.names), self.mci_quad) for k in ks]
+                    nk = len(keyf[0][0])
+                    for idx, _ in keyf:
+                        for i in idx[1:]:
+                            clip.loads[i].result(timeout=IO_TIMEOUT_S)
+                    for b, (idx, _) in enumerate(keyf):
+                        for r, i in enumerate(idx):
+                            views["mci_keys"][r, b].copy_(clip.key_u8[i])
                     kab = views["mci_keys"].to(g.device, non_blocking=True)
+                    # the segments whose fields are made, as (left, right) rows of the sections: the group's own and, quadratic, the
+                    # ones before and after it - all in ONE batched call per entry (a segment's field does not depend on the batch)
+                    sides = ((0, 1), (2, 0), (1, 3)) if self.mci_quad else ((0, 1),)
+                    pair = (lambda x: (torch.cat([x[i] for i, _ in sides]), torch.cat([x[j] for _, j in sides]))) if self.mci_quad else (lambda x: (x[0], x[1]))
+                    pa, pb = pair(kab)
                     qab = (None, None)
-                    if self.mci_exclude:        # the human masks of the two key frames' poses (rib_human_mask), 1 = excluded; no person: all zero
-                        pk = np.stack([self.peaks_of(clip.loads[k + d].result(timeout=IO_TIMEOUT_S)[2]) for d in (0, clip.sample_rate) for k in ks])
-                        qab = (g.human_mask(pk, ev.height, ev.width) > 0).to(torch.uint8).view(2, len(ks), ev.height, ev.width)
-                        field = g.mci_field_masked(kab[0], kab[1], qab[0], qab[1], self.mci_levels, border=self.mci_border)
+                    if self.mci_exclude:        # the human masks of the key frames' poses (rib_human_mask), 1 = excluded; no person: all zero
+                        pk = np.stack([self.peaks_of(clip.loads[idx[r]].result(timeout=IO_TIMEOUT_S)[2]) for r in range(nk) for idx, _ in keyf])
+                        qab = (g.human_mask(pk, ev.height, ev.width) > 0).to(torch.uint8).view(nk, len(ks), ev.height, ev.width)
+                        field = g.mci_field_masked(pa, pb, *pair(qab), self.mci_levels, border=self.mci_border)
                     else:
-                        field = g.mci_field(kab[0], kab[1], self.mci_levels, border=self.mci_border)
+                        field = g.mci_field(pa, pb, self.mci_levels, border=self.mci_border)
                     if self.mci_half:           # one more launch behind the field's, on the same stream; in place
-                        field = g.mci_refine(kab[0], kab[1], field, border=self.mci_border, out=field)
+                        field = g.mci_refine(pa, pb, field, border=self.mci_border, out=field)
                     kab0 = (None, None)
                     if self.keysize:            # the key files' own pixels, beside the field: what the unit's backgrounds are sampled from
-                        for b, k in enumerate(ks):
-                            views["mci_keys_src"][0, b].copy_(torch.from_numpy(clip.key_src[k].result(timeout=IO_TIMEOUT_S)))
-                            views["mci_keys_src"][1, b].copy_(torch.from_numpy(clip.key_src[k + clip.sample_rate].result(timeout=IO_TIMEOUT_S)))
+                        for b, (idx, _) in enumerate(keyf):
+                            for r, i in enumerate(idx):
+                                views["mci_keys_src"][r, b].copy_(torch.from_numpy(clip.key_src[i].result(timeout=IO_TIMEOUT_S)))
                         kab0 = views["mci_keys_src"].to(g.device, non_blocking=True)
                     field0 = None
                     if self.mci_detail:         # the field refined at the key frames' own size, once per group, behind the field (two launches)
-                        field0 = g.mci_detail_field(kab0[0], kab0[1], field, (ev.height, ev.width), border=self.mci_border,
+                        field0 = g.mci_detail_field(*pair(kab0), field, (ev.height, ev.width), border=self.mci_border,
                                                     precision="half" if self.mci_half else "full")
-                    clip.mci_of[gi] = (kab[0], kab[1], field, kab0[0], kab0[1], qab[0], qab[1], field0)
-                ka, kb, field, ka0, kb0, qa, qb, field0 = clip.mci_of[gi]
-                if self.mci_exclude:
+                    accel = accel0 = None
+                    if self.mci_quad:           # own | before | after -> the block acceleration (two launches), the own fields stay
+                        n, present = len(ks), [has for _, has in keyf]
+                        accel = g.mci_accel_field(field[n:2 * n], field[:n], field[2 * n:], precision="half" if self.mci_half else "full", present=present)
+                        if self.mci_detail:
+                            accel0 = g.mci_accel_field(field0[n:2 * n], field0[:n], field0[2 * n:], present=present)
+                            field0 = field0[:n]
+                        field = field[:n]
+                    clip.mci_of[gi] = (kab[0], kab[1], field, kab0[0], kab0[1], qab[0], qab[1], field0, accel, accel0)
+                ka, kb, field, ka0, kb0, qa, qb, field0, accel, accel0 = clip.mci_of[gi]
+                if self.mci_quad:              # ONE launch, as below: every sample moved by the acceleration's correction
+                    dn = g.mci_frames_accel(ka, kb, field, accel, clip.sample_rate, k_first=c0 + 1, count=Tc, normalised="both" if self.panels else True,
+                                            border=self.mci_border, precision="half" if self.mci_half else "full", sampler=self.mci_sampler,
+                                            masks=(qa, qb) if self.mci_exclude else None)
+                elif self.mci_exclude:
                     dn = g.mci_frames_masked(ka, kb, qa, qb, field, clip.sample_rate, k_first=c0 + 1, count=Tc,
                                              normalised="both" if self.panels else True, border=self.mci_border, sampler=self.mci_sampler)
                 else:
@@ -1353,7 +1412,10 @@ class _FolderPipeline:
                                       border=self.mci_border, precision="half" if self.mci_half else "full", sampler=self.mci_sampler)
                 if self.panels:
                     dn, dnu8 = dn
-                if self.mci_detail:            # ONE launch, the existing frame entry at the key frames' size with the full-size field (whole pixels)
+                if self.mci_detail and self.mci_quad:      # ONE launch at the key frames' size: the full-size field and its acceleration
+                    staged = g.mci_frames_accel(ka0, kb0, field0, accel0, clip.sample_rate, k_first=c0 + 1, count=Tc, normalised=False,
+                                                border=self.mci_border, sampler=self.mci_sampler)
+                elif self.mci_detail:          # ONE launch, the existing frame entry at the key frames' size with the full-size field (whole pixels)
                     staged = g.mci_frames(ka0, kb0, field0, clip.sample_rate, k_first=c0 + 1, count=Tc, normalised=False, border=self.mci_border,
                                           sampler=self.mci_sampler)
                 elif self.keysize:             # ONE launch: the unit's backgrounds uint8 [Tc,B,h0,w0,3], "source"'s staged frames
@@ -1781,10 +1843,43 @@ class _FolderPipeline:
         is held to (panel.jpeg_encode_host) - the same files as the native path writes."""
         return io_worker.save_sheet_defined if self.jpeg_gpu else io_worker.save_sheet
 
+    def quadratic_host(self, clip, k, ks):
+        """mci_motion="quadratic" by the host definition, for the segment that starts at key frame k: the fields of the segment and of
+        the ones before and after it (every setting as the linear path applies it), background.mci_accel_host, and frames ks by
+        mci_frames_accel_host -> (uint8 [len(ks), H, W, 3] at the model size, the same at the key files' size under
+        mci_detail="keyframes", else None)."""
+        ev, s, B = self.ev, clip.sample_rate, _background
+        idx, has = mci_key_frames(k, s, len(clip.names), True)
+        pose = {i: clip.loads[i].result(timeout=IO_TIMEOUT_S)[2] for i in set(idx)}
+        key = {i: clip.key_u8[i].numpy() for i in pose}
+        msk = {i: rasterise.human_mask(self.peaks_of(p), ev.height, ev.width).astype(np.uint8) for i, p in pose.items()} if self.mci_exclude else {}
+        src = {i: clip.key_src[i].result(timeout=IO_TIMEOUT_S) for i in pose} if self.mci_detail else {}
+        prec = "half" if self.mci_half else "full"
+
+        def fields(i, j):                        # of the segment between key frames i and j: (model size, key files' size or None)
+            if self.mci_exclude:
+                f = B.mci_field_masked_host(key[i], key[j], msk[i], msk[j], self.mci_levels, border=self.mci_border)
+            else:
+                f = B.mci_field_host(key[i], key[j], self.mci_levels, border=self.mci_border)
+            if self.mci_half:
+                f = B.mci_refine_host(key[i], key[j], f, border=self.mci_border)
+            return f, B.mci_detail_field_host(src[i], src[j], f, (ev.height, ev.width), border=self.mci_border, precision=prec) if self.mci_detail else None
+        own = fields(idx[0], idx[1])
+        prev = fields(idx[2], idx[0]) if has[0] else (None, None)
+        nxt = fields(idx[1], idx[3]) if has[1] else (None, None)
+        masks = dict(ma=msk[idx[0]], mb=msk[idx[1]]) if self.mci_exclude else {}
+        u8 = B.mci_frames_accel_host(key[idx[0]], key[idx[1]], own[0], B.mci_accel_host(prev[0], own[0], nxt[0], unit_shift=int(self.mci_half)), s, ks,
+                                     border=self.mci_border, precision=prec, sampler=self.mci_sampler, **masks)
+        if not self.mci_detail:
+            return u8, None
+        return u8, B.mci_frames_accel_host(src[idx[0]], src[idx[1]], own[1], B.mci_accel_host(prev[1], own[1], nxt[1]), s, ks, border=self.mci_border,
+                                           sampler=self.mci_sampler)
+
     def run_reference(self, clip):
         """Any callable that only speaks the reference's protocol (img, mask = model(label, None, dain, prev)): frame by frame."""
         ev, tm, model = self.ev, self.tm, self.model
-        right = {k + clip.sample_rate for k, _ in clip.segs} if self.mci else set()     # decoded, written by their own rank
+        # decoded, written by their own rank: the right key frames (quadratic: and those of the segments before and after)
+        right = {i for k, _ in clip.segs for i in mci_key_frames(k, clip.sample_rate, len(clip.names), self.mci_quad)[0]} if self.mci else set()
         for i in sorted(set(clip.keys) | right | {i for _, frames in clip.segs for i in frames}):
             self.submit_load(clip, i)
         for k, frames in clip.segs:
@@ -1798,7 +1893,9 @@ class _FolderPipeline:
             poses = [g[2] for g in got]
             if self.mci:                         # the host definition of the background frames (background.py)
                 ka, kb = clip.key_u8[k].numpy(), clip.key_u8[k + clip.sample_rate].numpy()
-                if self.mci_exclude:             # the host statement of the two key frames' human masks, 1 = excluded
+                if self.mci_quad:                # three segments' fields, the acceleration, the frames: every setting in one place
+                    u8, bg0 = self.quadratic_host(clip, k, [i - k for i in frames])
+                elif self.mci_exclude:           # the host statement of the two key frames' human masks, 1 = excluded
                     qa, qb = (rasterise.human_mask(self.peaks_of(clip.loads[j].result()[2]), ev.height, ev.width).astype(np.uint8)
                               for j in (k, k + clip.sample_rate))
                     field = _background.mci_field_masked_host(ka, kb, qa, qb, self.mci_levels, border=self.mci_border)
@@ -1814,7 +1911,9 @@ class _FolderPipeline:
                 # shows the host's normalisation, as the native path's does (normalise_exact)
                 dn = torch.from_numpy(_background.normalised_upload(u8)).unsqueeze(1)
                 dn_shown = torch.from_numpy(_background.normalised(u8)).unsqueeze(1)
-                if self.mci_detail:              # the field refined at the key files' own size, then the existing frame definition there
+                if self.mci_quad:
+                    pass                         # (bg0 is quadratic_host's)
+                elif self.mci_detail:            # the field refined at the key files' own size, then the existing frame definition there
                     ka0, kb0 = (clip.key_src[j].result(timeout=IO_TIMEOUT_S) for j in (k, k + clip.sample_rate))
                     field0 = _background.mci_detail_field_host(ka0, kb0, field, (ev.height, ev.width), border=self.mci_border,
                                                                precision="half" if self.mci_half else "full")

@@ -728,8 +728,10 @@ class Generator:
         return self._mci_frames_body("mci_frames", a_u8, b_u8, None, field, sample_rate, k_first, count, normalised, out, border, precision,
                                      sampler, _staging)
 
-    def _mci_frames_body(self, who, a_u8, b_u8, masks, field, sample_rate, k_first, count, normalised, out, border, precision, sampler, staging):
-        """mci_frames (masks None) and mci_frames_masked (masks = (ma, mb)): one check per argument, in one order, and one launch."""
+    def _mci_frames_body(self, who, a_u8, b_u8, masks, field, sample_rate, k_first, count, normalised, out, border, precision, sampler, staging,
+                         accel=None):
+        """mci_frames (masks None), mci_frames_masked (masks = (ma, mb)) and mci_frames_accel (accel given, masks either): one check per
+        argument, in one order, and one launch."""
         from .background import BORDERS, PRECISIONS, check_border, check_precision, check_sampler, log2_rate
         border = BORDERS.index(check_border(border, who))
         cubic = check_sampler(sampler, who) == "cubic"
@@ -741,6 +743,7 @@ class Generator:
         s = int(sample_rate)
         f = self._mci_field_arg(field, B, H, W, who, ("segments", "mci_field" if masks is None else "mci_field_masked"))
         k_first, T = self._mci_span(s, k_first, count, who)
+        acc = self._mci_field_arg(accel, B, H, W, who, ("segments", "mci_accel_field")) if accel is not None else None
         if normalised not in (True, False, "both"):
             raise ValueError("%s: normalised must be True, False or 'both'" % who)
         fshape, ushape = (T, B, 3, H, W), (T, B, H, W, 3)
@@ -757,7 +760,9 @@ class Generator:
             rf = dest(of, fshape, torch.float32) if normalised in (True, "both") else None
             ru = dest(ou, ushape, torch.uint8) if normalised in (False, "both") else None
             head, tail = (self._h, T, B, H, W, _ptr(a), _ptr(b)), (_ptr(rf), _ptr(ru), self._stream())
-            if cubic:
+            if acc is not None:
+                rc = self._lib.rib_accel_frames(*head, _ptr(qa), _ptr(qb), _ptr(f), _ptr(acc), s, k_first, border, precision, int(cubic), *tail)
+            elif cubic:
                 rc = self._lib.rib_cubic_frames(*head, _ptr(qa), _ptr(qb), _ptr(f), s, k_first, border, precision, int(staging), *tail)
             elif masks is not None:
                 rc = self._lib.rib_masked_frames(*head, _ptr(qa), _ptr(qb), _ptr(f), s, k_first, border, precision, *tail)
@@ -810,6 +815,49 @@ class Generator:
         mci_frames'; sampler="cubic" (rib_cubic_frames with the masks): a sample is clean iff all 16 of its taps are clear."""
         return self._mci_frames_body("mci_frames_masked", a_u8, b_u8, (ma, mb), field, sample_rate, k_first, count, normalised, out, border,
                                      precision, sampler, _staging)
+
+    def mci_accel_field(self, prev, cur, next, precision="full", present=None):
+        """The block acceleration field of B segments on the GPU (rib_accel_field; background.mci_accel_host is the definition and is
+        bit-equal): cur int16 [B,Hb,Wb,2] (or [Hb,Wb,2]) the segments' block fields on this device (mci_field, mci_field_masked,
+        mci_detail_field; mci_refine's with precision="half"), prev and next the fields of the segments before and after each, same
+        shape, either None (no segment has one).  present: None, or B pairs (has_prev, has_next) - a uint8 [B,2] tensor on this device
+        or a host sequence, uploaded - for a batch whose members differ; a neighbour that is absent for an item is not read there.
+        -> int16 of cur's shape, in the fields' unit, for mci_frames_accel.  Two launches on the current stream."""
+        from .background import PRECISIONS, check_precision
+        half = PRECISIONS.index(check_precision(precision, "mci_accel_field"))
+        if not torch.is_tensor(cur) or cur.dim() not in (3, 4) or min(cur.shape) < 1:
+            raise ValueError("mci_accel_field: the field must be an int16 [B,Hb,Wb,2] or [Hb,Wb,2] tensor, got %s" % (tuple(getattr(cur, "shape", ())),))
+        single = cur.dim() == 3
+        B, Hb, Wb = (1,) + tuple(cur.shape[:2]) if single else tuple(cur.shape[:3])
+        f = self._mci_field_arg(cur, B, 8 * Hb, 8 * Wb, "mci_accel_field")
+        fp, fn = (None if g is None else self._mci_field_arg(g, B, 8 * Hb, 8 * Wb, "mci_accel_field", ("segments", "the neighbouring segment")) for g in (prev, next))
+        if present is not None:
+            if not torch.is_tensor(present):
+                present = torch.tensor([[int(bool(v)) for v in pair] for pair in present], dtype=torch.uint8).reshape(-1, 2).to(self.device)
+            if tuple(present.shape) != (B, 2) or present.dtype != torch.uint8 or present.device != self.device:
+                raise ValueError("mci_accel_field: present must be %d pairs (has_prev, has_next): uint8 [%d, 2] on %s" % (B, B, self.device))
+            present = present.contiguous()
+        n = int(self._lib.rib_accel_workspace_bytes(self._h, B, Hb, Wb))
+        if n == 0:
+            raise ValueError("mci_accel_field: B=%d Hb=%d Wb=%d: 1 <= B <= 32767, Hb and Wb in 1..2048" % (B, Hb, Wb))
+        with torch.cuda.device(self.device):
+            ws = torch.empty(n, dtype=torch.uint8, device=self.device)      # (per call: it belongs to the stream the call is enqueued on)
+            res = torch.empty_like(f)
+            _native.check(self._h, self._lib.rib_accel_field(self._h, B, Hb, Wb, _ptr(fp), _ptr(f), _ptr(fn), _ptr(present), half, _ptr(res),
+                                                             _ptr(ws), self._stream()))
+        return res[0] if single else res
+
+    def mci_frames_accel(self, a_u8, b_u8, field, accel, sample_rate, k_first=1, count=None, normalised=True, out=None, border="clamp",
+                         precision="full", sampler="bilinear", masks=None):
+        """mci_frames / mci_frames_masked on a second-order trajectory, one launch (rib_accel_frames; background.mci_frames_accel_host is
+        the definition and is bit-equal): accel int16 [B,Hb,Wb,2] is mci_accel_field's result for the same segments, in `field`'s unit;
+        both of a pixel's samples move by c = accel * t (1 - t) / 2 at t = k / sample_rate.  masks: None (the person is kept) or
+        (ma, mb) as mci_frames_masked's.  Everything else - field, frames, normalised (True, False, "both"), out, border, precision,
+        sampler - is mci_frames'; an all-zero accel gives its bytes."""
+        if accel is None:
+            raise ValueError("mci_frames_accel: accel must be an int16 tensor on %s (mci_accel_field)" % (self.device,))
+        return self._mci_frames_body("mci_frames_accel", a_u8, b_u8, masks, field, sample_rate, k_first, count, normalised, out, border, precision,
+                                     sampler, 0, accel=accel)
 
     def mci_frames_scaled(self, a0_u8, b0_u8, field, model_hw, sample_rate, k_first=0, count=None, border="clamp", precision="full", out=None,
                           sampler="bilinear", _staging=0):

@@ -95,6 +95,13 @@ the existing frame kernels' on the full-size key frames with that field.  The mo
 The limits, plainly: it is this project's interpolation, not DAIN; no interior occlusion reasoning; a model-size vector that is
 wrong stays wrong beyond R; above a size ratio of 8 the radius no longer covers the quantum; whole pixels only at full size (below
 ratio 2 `--mci-precision half` is finer); the person is still a cubic enlargement; real footage is unmeasured.
+`--mci-motion quadratic` (default `linear`; only with `--background mci`): between two key frames everything above moves the
+background at constant velocity, so its velocity jumps at every key frame while the person's poses follow curved trajectories.
+With `quadratic` a segment also reads the key frames before and after it; the three motion fields give every block an acceleration
+(rib_accel_field, background.mci_accel_host) and both samples of every pixel move by a t (1 - t) / 2 (rib_accel_frames,
+background.mci_frames_accel_host).  The limits, plainly: second order from three fields - a wrong neighbour field gives a wrong
+correction and the median is the only guard; no interior occlusion reasoning; about three times the field work per group; with
+`--output-size keyframes` only together with `--mci-detail keyframes`; real footage is unmeasured.
 """
 import argparse
 import os
@@ -171,7 +178,8 @@ def summary_line(evaluator, rank=0, world=1):
                           (", half-pel" if getattr(evaluator, "mci_precision", "full") == "half" else "")
                           + (", person excluded" if getattr(evaluator, "mci_person", "keep") == "exclude" else "")
                           + (", cubic sampler" if getattr(evaluator, "mci_sampler", "bilinear") == "cubic" else "")
-                          + (", field refined at the key frames' size" if getattr(evaluator, "mci_detail", "model") == "keyframes" else ""))}
+                          + (", field refined at the key frames' size" if getattr(evaluator, "mci_detail", "model") == "keyframes" else "")
+                          + (", quadratic motion" if getattr(evaluator, "mci_motion", "linear") == "quadratic" else ""))}
                [getattr(evaluator, "background", "dain")]))
     if getattr(evaluator, "output_size", "model") == "source":
         line += " | files at the source size"
@@ -223,7 +231,7 @@ def main(opts):
                                              mci_sampler=opts.mci_sampler, mci_detail=opts.mci_detail, video=opts.video, video_fps=30 if opts.video_fps is None else opts.video_fps,
                                              video_quality=90 if opts.video_quality is None else opts.video_quality,
                                              video_frames=opts.video_frames, frames=opts.frames, output_size=opts.output_size, png_on=opts.png_on,
-                                             **poses_kw)
+                                             **({"mci_motion": opts.mci_motion} if opts.mci_motion != "linear" else {}), **poses_kw)
     print(summary_line(evaluator, rank, world))
     if world > 1:
         print("[rank {}/{}] wrote {} frames".format(rank, world, len(written)))
@@ -323,6 +331,16 @@ def build_parser():
                              "at strong edges and the result is clamped; with --mci-person exclude the exclusion footprint is 4x4, so "
                              "the clean/blend seam moves by a pixel; still this project's interpolation, without interior occlusion "
                              "reasoning; the generator was trained on DAIN backgrounds; quality on real footage is unmeasured")
+    parser.add_argument("--mci-motion", default=None,
+                        help="with --background mci: 'linear' (default): between two key frames the background moves at constant "
+                             "velocity, so across the clip its velocity jumps at every key frame and the person - whose poses follow "
+                             "curved trajectories - slides against it; 'quadratic': the fields of the segments before and after give "
+                             "every 8x8 block an acceleration a and both samples of a pixel move by a t (1 - t) / 2 (a / 8 in the "
+                             "middle of a segment). A clip's first and last segment use the one-sided difference, a clip of one "
+                             "segment gets the linear files. About three times the field work per group. Second order from three "
+                             "fields: a wrong neighbour field gives a wrong correction and the 3x3 median is the only guard; still no "
+                             "interior occlusion reasoning; with --output-size keyframes only together with --mci-detail keyframes; "
+                             "quality on real footage is unmeasured")
     parser.add_argument("--mci-detail", default=None,
                         help="with --background mci --output-size keyframes: 'model' (default): the full-size backgrounds follow the "
                              "model-size motion field, whose vectors are whole model pixels (multiples of 3.75 output pixels at 512 -> "
@@ -415,6 +433,14 @@ def parse_args(argv=None):
     if opts.mci_detail == "keyframes" and opts.output_size != "keyframes":
         parser.error("--mci-detail keyframes needs --output-size keyframes (the field is refined at the key frames' own size)")
     opts.mci_detail = "model" if opts.mci_detail is None else opts.mci_detail
+    if opts.mci_motion not in (None, "linear", "quadratic"):
+        parser.error("--mci-motion must be 'linear' or 'quadratic', got %r" % (opts.mci_motion,))
+    if opts.mci_motion is not None and opts.background != "mci":
+        parser.error("--mci-motion is a setting of --background mci")
+    if opts.mci_motion == "quadratic" and opts.output_size == "keyframes" and opts.mci_detail != "keyframes":
+        parser.error("--mci-motion quadratic with --output-size keyframes needs --mci-detail keyframes for now (the scaled entries take no "
+                     "acceleration: a scaled acceleration in rib_scaled_frames / rib_cubic_scaled is the follow-up)")
+    opts.mci_motion = "linear" if opts.mci_motion is None else opts.mci_motion
     if opts.mci_person == "exclude" and opts.mci_precision == "half":
         parser.error("--mci-person exclude with --mci-precision half is not supported yet: the half-pel refinement has no masked form "
                      "(a masked rib_halfpel_refine is the follow-up)")

@@ -100,6 +100,8 @@ def main():
                     help="with --background mci --output-size keyframes: refine the field at the key frames' size (mci_detail=...)")
     ap.add_argument("--mci-sampler", default="bilinear", choices=("bilinear", "cubic"),
                     help="with --background mci: the 4x4 cubic sampler for every background sample (mci_sampler=...)")
+    ap.add_argument("--mci-motion", default="linear", choices=("linear", "quadratic"),
+                    help="with --background mci: the second-order trajectory from the neighbouring segments' fields (mci_motion=...)")
     ap.add_argument("--video", action="store_true", help="also write the frames as <clip>_video.avi, JPEG-encoded on the GPU (video=True)")
     ap.add_argument("--frames", default="png", choices=("png", "none"), help="with --video: 'none' writes no PNG frames (frames=...)")
     ap.add_argument("--poses", default="folder", choices=("folder", "keyframes"),
@@ -131,6 +133,8 @@ def main():
         ap.error("--mci-detail keyframes is a setting of --background mci --output-size keyframes")
     if a.mci_sampler != "bilinear" and a.background != "mci":
         ap.error("--mci-sampler is a setting of --background mci")
+    if a.mci_motion != "linear" and (a.background != "mci" or (a.output_size == "keyframes" and a.mci_detail != "keyframes")):
+        ap.error("--mci-motion quadratic is a setting of --background mci, with --output-size keyframes only together with --mci-detail keyframes")
     if a.mci_border != "clamp" and a.background != "mci":
         ap.error("--mci-border is a setting of --background mci")
     if a.panel_encode != "host" and not a.panels:
@@ -179,7 +183,8 @@ def main():
                                          **({"mci_precision": a.mci_precision} if a.mci_precision != "full" else {}),
                                          **({"mci_person": a.mci_person} if a.mci_person != "keep" else {}),
                                          **({"mci_sampler": a.mci_sampler} if a.mci_sampler != "bilinear" else {}),
-                                         **({"mci_detail": a.mci_detail} if a.mci_detail != "model" else {}))
+                                         **({"mci_detail": a.mci_detail} if a.mci_detail != "model" else {}),
+                                         **({"mci_motion": a.mci_motion} if a.mci_motion != "linear" else {}))
             torch.cuda.synchronize()
             walls.append(time.perf_counter() - t0)
         tm = dict(E.timings)
@@ -196,6 +201,7 @@ def main():
                       "mci_person": a.mci_person if a.background == "mci" else None,
                       "mci_sampler": a.mci_sampler if a.background == "mci" else None,
                       "mci_detail": a.mci_detail if a.background == "mci" else None,
+                      **({"mci_motion": a.mci_motion} if a.mci_motion != "linear" else {}),
                       "metrics": a.metrics, "pose_mask": a.pose_mask, "metrics_overall": overall, "panels": a.panels, "panel_encode": a.panel_encode,
                       "video": a.video, "frames_written": a.frames, "png_on": a.png_on, "png_bytes_last_run": png_bytes, "poses": a.poses, "stage1_plus_bridge_ms_per_clip": stage1_ms,
                       "wall_s": wall, "wall_s_runs": [round(w, 4) for w in walls[1:]], "frames_per_s_end_to_end": n / wall,

@@ -18,6 +18,11 @@ and k_mci_frames<.., .., true> in the same trace, beside the unmasked rows; not 
 in the same trace, beside k_mci_frames' rows; with --person also its masked form); --staging 1 passes that entry's diagnostic
 "never stage" (every tile gathers its taps directly), 0 is the per-tile rule.  The JSON then also holds the share of tiles the
 rule stages on this field (background.cubic_tile_staged, on the host, segment 0).
+--mci-motion quadratic (the driver's --mci-motion): AFTER everything above, what that setting adds per group - the fields of the
+segment and of the segments before and after it in ONE call over 3 B pairs (the scene moves by half the segment's motion before it
+and by the same motion after it; with --precision half the refine launch over the same 3 B), rib_accel_field (k_mci_accel and one
+more k_mci_median in the trace) - and the frames through rib_accel_frames (k_accel_frames beside k_mci_frames' rows; with --sampler
+cubic also k_cubic_accel beside k_cubic_frames').
 
 Prints one JSON line: the wall time of the field's launches (levels + 2: five by default) and of the frames launch between two events (median of
 --reps, after a warm-up), the frames launch's byte floor (12 bytes of float32 out per pixel and frame, 3 more with --u8, the
@@ -62,6 +67,8 @@ def main():
     ap.add_argument("--person", action="store_true", help="also time the masked entries (--mci-person exclude) on the same unit")
     ap.add_argument("--sampler", default="bilinear", choices=("bilinear", "cubic"), help="cubic: also time rib_cubic_frames on the same unit (--mci-sampler)")
     ap.add_argument("--staging", type=int, default=0, choices=(0, 1), help="with --sampler cubic: 0 = the per-tile staging rule, 1 = never stage (a diagnostic)")
+    ap.add_argument("--mci-motion", default="linear", choices=("linear", "quadratic"),
+                    help="quadratic: also time the three segments' fields in one call, rib_accel_field and rib_accel_frames on the same unit (--mci-motion)")
     a = ap.parse_args()
     if a.person and a.precision == "half":
         ap.error("--person times the whole-pixel masked entries: not with --precision half")
@@ -112,6 +119,28 @@ def main():
             xms = timed(lambda: G.mci_frames_masked(ka, kb, qa, qb, mfield, s, normalised="both" if a.u8 else True, out=(f32, u8) if a.u8 else f32,
                                                     **dict(kw, sampler="cubic", _staging=a.staging)), a.reps)
             extra.update({"cubic_masked_frames_event_us_median": round(xms[len(xms) // 2] * 1e3, 2), "cubic_masked_frames_event_us_min": round(xms[0] * 1e3, 2)})
+    if a.mci_motion == "quadratic":
+        # the key frames before and after: the scene moved by half the segment's motion before it and by the same motion after it
+        kp = big[:, m + 3 * m // 16:m + 3 * m // 16 + H, m - m // 4:m - m // 4 + W].contiguous()
+        kn = big[:, m - 3 * m // 4:m - 3 * m // 4 + H, m + m:m + m + W].contiguous()
+        pa, pb = torch.cat([ka, kp, kb]), torch.cat([kb, ka, kn])      # own | before | after: one batched call per entry, as the driver's
+
+        def three_fields():
+            f3 = G.mci_field(pa, pb, a.levels, **kw)
+            return G.mci_refine(pa, pb, f3, out=f3, **kw) if half else f3
+        f3 = three_fields()
+        accel = G.mci_accel_field(f3[B:2 * B], f3[:B], f3[2 * B:], precision=a.precision)
+        tms = timed(three_fields, a.reps)
+        ams = timed(lambda: G.mci_accel_field(f3[B:2 * B], f3[:B], f3[2 * B:], precision=a.precision), a.reps)
+        out = dict(normalised="both" if a.u8 else True, out=(f32, u8) if a.u8 else f32)
+        qms = timed(lambda: G.mci_frames_accel(ka, kb, f3[:B], accel, s, **out, **fkw), a.reps)
+        extra.update({"mci_motion": "quadratic", "three_fields_event_us_median": round(tms[len(tms) // 2] * 1e3, 2), "three_fields_event_us_min": round(tms[0] * 1e3, 2),
+                      "accel_field_event_us_median": round(ams[len(ams) // 2] * 1e3, 2), "accel_field_event_us_min": round(ams[0] * 1e3, 2),
+                      "accel_frames_event_us_median": round(qms[len(qms) // 2] * 1e3, 2), "accel_frames_event_us_min": round(qms[0] * 1e3, 2),
+                      "accel_nonzero_fraction": round(float((accel != 0).float().mean()), 3), "accel_max_abs": int(accel.abs().max())})
+        if a.sampler == "cubic":
+            yms = timed(lambda: G.mci_frames_accel(ka, kb, f3[:B], accel, s, **out, **dict(fkw, sampler="cubic")), a.reps)
+            extra.update({"cubic_accel_frames_event_us_median": round(yms[len(yms) // 2] * 1e3, 2), "cubic_accel_frames_event_us_min": round(yms[0] * 1e3, 2)})
     print(json.dumps({"height": H, "width": W, "batch": B, "rate": s, "levels": a.levels, "border": a.border, "precision": a.precision, "frames": T * B, "u8": a.u8,
                       "field_event_us_median": round(fms[len(fms) // 2] * 1e3, 2), "field_event_us_min": round(fms[0] * 1e3, 2),
                       "frames_event_us_median": round(rms[len(rms) // 2] * 1e3, 2), "frames_event_us_min": round(rms[0] * 1e3, 2),
